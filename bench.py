@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the DDPM reverse-diffusion sampler on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,9 +18,17 @@ step) over the batch; K consecutive steps of the T=1000 grid are timed inside ON
 together with the uint8 epilogue and (N>1) the gather of finished samples.  value = images per second
 of a full T=1000 run = N*64 / (ms_per_step * 1000 steps).  With the default K=1000 that is a measured
 full run, for smaller K it is the per-step time extrapolated to 1000 steps (all steps launch identical
-kernels).
+kernels).  K > 1000 times consecutive sampling calls over the same inputs, 1000 steps each and the remainder
+last (W > 1000 warms up the same way).
 
-Besides the driver's fields the JSON line carries
+--dump-outputs DIR writes what the timed path returned in its last call, after the clock stops: DIR/images.npy (the
+uint8 images of the global batch as float32, [N*64, 64, 64, 3]) and DIR/latents.npy (rank 0's final latents, float32
+[64, 3, 64, 64]).  Weights, x_T and every z_t are seeded, so equal arguments give equal inputs.
+
+A plain run sets up, warms up, times the K steps, dumps, and prints the JSON line with `roofline`, `validated`,
+`cpu_baseline` and `e2e` null.  --full adds the legs below, after the clock has stopped (--no-validate, --no-e2e and
+--no-cpu-baseline drop single legs of a --full run):
+
   roofline      the dominant kernel (the stride-1 Winograd F(2x2,3x3) convolutions with fp32-equivalent bf16x3 products, 33
                 launches per step): bf16 FLOPs the kernel ISSUES to the matrix pipe per launch (6 bf16 term products per fp32
                 product of the Winograd algorithm, which itself multiplies 16/36 of the direct form) / average launch duration
@@ -28,7 +36,7 @@ Besides the driver's fields the JSON line carries
                 kernel executes on, frac <= 1 by construction; the fp32-equivalent rate against the f32 peak, the direct-form
                 ("algorithmic") rate, the HBM fraction and the whole conv3x3 class are reported beside it
   validated     after the clock stops: all timed images finite, and image 0 of the timed batch bit-equal to its own B=1 run of
-                the same K steps (the run fails otherwise)
+                the steps of the last timed call (the run fails otherwise)
   cpu_baseline  the CPU oracle (oracle/, torch fp32) timed on this box's host cores on a bounded sample
   e2e_images_per_sec   host-inclusive rate of Sampler.generate_seeds (seeds in -> uint8 images on the host out: x_T and
                 z_t drawn by the per-image CPU generators, uploads, T steps, epilogue, download) -- SURVEY 8(d)'s
@@ -289,6 +297,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous, shard, gather, max over ranks and the JSON line without the sampler (gloo when there is no GPU)")
     ap.add_argument("--no-validate", action="store_true", help="skip the post-clock check of the timed images")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the post-clock validation, the host-inclusive leg, the roofline "
+                         "profile and the CPU baseline (a plain run prints those fields as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the images and latents of the timed path's last call as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -317,8 +330,8 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     K, W, B = args.steps, args.warmup, args.batch
-    if not (1 <= K <= T_FULL and 0 <= W <= T_FULL):
-        raise SystemExit("--steps and --warmup must be within 1..1000")
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     sd = synthetic_unet_state_dict()
     sampler = Sampler(dev)
@@ -333,6 +346,12 @@ def main():
         z = torch.randn(n_noise, B, 3, SIZE, SIZE, generator=g, device=dev)
         return sched, x_T, z
 
+    def make_runs(n_steps):
+        """the sampling calls of n steps: 1000-step calls and the remainder last, inputs shared by calls of one length"""
+        lengths = [T_FULL] * (n_steps // T_FULL) + ([n_steps % T_FULL] if n_steps % T_FULL else [])
+        inputs = {n: make_run(n) for n in set(lengths)}
+        return [inputs[n] for n in lengths]
+
     def barrier():
         if world > 1:
             torch.distributed.barrier()
@@ -341,22 +360,25 @@ def main():
     log(f"model loaded on {dev}; warm-up {W} steps")
     # warm-up: W untimed steps (also sizes the library workspace)
     if W > 0:
-        sched, x_T, z = make_run(W)
-        warm = run_sampling_loop(model, sched, x_T, z)
+        for sched, x_T, z in make_runs(W):
+            warm = run_sampling_loop(model, sched, x_T, z)
         if world > 1:
             # the collectives of the timed region once, untimed: RCCL builds its point-to-point connections on first use
             # (hundreds of milliseconds -- more than a 20-step run), and the all-reduce of the timing as well
             sdist.gather_images(warm.images, B * world, dst=0)
             sdist.max_over_ranks(0.0, dev)
-    sched, x_T, z = make_run(K)
+    runs = make_runs(K)
     barrier()
     t0 = time.perf_counter()
-    res = run_sampling_loop(model, sched, x_T, z)            # K steps + uint8 epilogue
+    steps_done = 0
+    for sched, x_T, z in runs:
+        res = run_sampling_loop(model, sched, x_T, z)        # up to 1000 steps + uint8 epilogue
+        steps_done += res.steps_done
     gathered = sdist.gather_images(res.images, B * world, dst=0)
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = sdist.max_over_ranks(elapsed, dev)
-    assert res.steps_done == K
+    assert steps_done == K
     if rank == 0:
         assert gathered.shape == (B * world, SIZE, SIZE, 3)
 
@@ -364,20 +386,28 @@ def main():
     value = B * world / (ms_per_step * 1e-3 * T_FULL)
     log(f"timed {K} steps: {ms_per_step:.3f} ms/step -> {value:.3f} images/sec")
 
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "images.npy"), gathered.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), res.latents.cpu().numpy().astype(np.float32))
+        log(f"outputs of the last timed call written to {args.dump_outputs}")
+
     # ---- after the clock has stopped: are the timed images the right images?  Every latent of the timed batch is finite, and
-    # image 0 re-sampled ALONE (B = 1, the same x_T, the same noise, the same K steps) has the same bits -- an image's chain
-    # depends on its own inputs only, so any kernel that mixed images, skipped work for part of the batch
-    # or read another batch's buffers shows here.  Every rank checks its own shard; a failure ends the run non-zero.
+    # image 0 re-sampled ALONE (B = 1, the same x_T, the same noise, the same steps as the last timed call) has the same bits --
+    # an image's chain depends on its own inputs only, so any kernel that mixed images, skipped work for
+    # part of the batch or read another batch's buffers shows here.  Every rank checks its own shard; a failure ends the run
+    # non-zero.
     validated = None
-    if not args.no_validate:
+    if args.full and not args.no_validate:
         finite = bool(torch.isfinite(res.latents).all().item())
         one = run_sampling_loop(model, sched, x_T[:1].contiguous(), z[:, :1].contiguous() if z.shape[0] else z[:, :1])
         same_x = bool(torch.equal(one.latents[0], res.latents[0]))
         same_u8 = bool(torch.equal(one.images[0], res.images[0]))
         spread = int(res.images.to(torch.int32).amax().item() - res.images.to(torch.int32).amin().item())
-        validated = {"all_latents_finite": finite, "image0_bit_equal_to_its_B1_run": same_x and same_u8, "steps": K,
+        validated = {"all_latents_finite": finite, "image0_bit_equal_to_its_B1_run": same_x and same_u8, "steps": res.steps_done,
                      "uint8_range_of_batch": spread}
-        if not (finite and same_x and same_u8 and one.steps_done == K):
+        if not (finite and same_x and same_u8 and one.steps_done == res.steps_done):
             raise SystemExit(f"bench validation failed on rank {rank}: {validated}")
         log(f"validated: {validated}")
 
@@ -388,7 +418,7 @@ def main():
     # 20-step run would report as a 2x slower rate.
     e2e = None
     KE = min(T_FULL, args.e2e_steps if args.e2e_steps > 0 else max(K, 256))
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         from synt_isic_amd.dist import shard_range
         lo, hi = shard_range(B * world, world, rank)
         seeds = list(range(lo, hi))
@@ -408,7 +438,7 @@ def main():
 
     roofline = None
     cpu = None
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- roofline leg: HIP events around every conv3x3 launch on the launch stream
         n_prof = max(1, min(args.profile_steps, K))
         sched_p, x_p, z_p = make_run(n_prof)

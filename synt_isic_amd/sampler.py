@@ -134,7 +134,9 @@ class NoiseStream:
         self.x_T[b] = torch.randn((1,) + self.chw, generator=self.gens[b])[0]
 
     def _draw_z(self, slot: int, n: int, b: int) -> None:
-        self.host[slot][:n, b] = torch.randn((n,) + self.chw, generator=self.gens[b])
+        # numpy copies on this worker thread alone: a torch copy of this size starts an intra-op thread team from every worker
+        # at once (workers x intra-op threads), which on a host with a CPU quota spins the quota away
+        self.host[slot][:n, b].numpy()[...] = torch.randn((n,) + self.chw, generator=self.gens[b]).numpy()
 
     def prefetch(self, slot: int, n: int) -> None:
         """start drawing the next n noise tensors of every image into pinned buffer ``slot``"""

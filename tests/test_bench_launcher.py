@@ -19,6 +19,9 @@ def _run(args, env=None, timeout=300):
     e = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
+    # the plumbing is tested on the CPU (gloo) on every machine: on a GPU box the dry run would otherwise take one device per
+    # rank, and a box with fewer GPUs than ranks cannot run it
+    e.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
     e.update(env or {})
     return subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
 

@@ -179,7 +179,8 @@ def test_two_ranks_share_the_gpu_rehearsal(tmp_path):
         outs[world] = np.load(out)
     assert outs[1].shape == (6, 64, 64, 3) and np.array_equal(outs[1], outs[2])
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline", "--no-e2e", "--profile-steps", "1"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-e2e", "--profile-steps", "1"], env=env, cwd=root, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -192,14 +193,14 @@ BF3_LAUNCHES_PER_STEP = 33.0      # the stride-1 conv3x3 launches of a step with
 
 
 def test_bench_line_contract():
-    """`python bench.py` (short run, no CPU leg) as the driver starts it: ONE JSON line on stdout carrying the metric of
+    """`python bench.py --full` (short run, no CPU leg): ONE JSON line on stdout carrying the metric of
     BASELINE.json, a roofline object for the dominant kernel (the bf16x3 Winograd form) and the
     host-inclusive leg; the HIP-event per-launch figures are self-consistent."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -228,3 +229,35 @@ def test_bench_line_contract():
     # the host-inclusive leg has its own step count (>= 256) so that its fixed costs do not pose as the rate
     assert d["e2e"]["T"] >= 256 and d["e2e_images_per_sec"] > 0.5 * d["value"]
 
+
+
+def test_plain_bench_run_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full prints the headline fields with the --full legs null; --dump-outputs writes the
+    timed path's last call.  --steps 1003 times a 1000-step call and then a 3-step call over the same seeded inputs, so its
+    outputs equal those of a separate --steps 3 run bit for bit."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for K in (3, 1003):
+        d = tmp_path / f"k{K}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == K and line["config"]["steps_timed"] == K and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 64.0 / (line["ms_per_step"] * 1e-3 * 1000)) < 1e-6 * line["value"]
+        assert line["unit"] == "images/sec" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert all(line[k] is None for k in ("roofline", "validated", "cpu_baseline", "e2e", "e2e_images_per_sec"))
+        out[K] = {n: np.load(d / f"{n}.npy") for n in ("images", "latents")}
+        assert sum(a.nbytes for a in out[K].values()) <= 64 << 20
+    a = out[3]
+    assert a["images"].dtype == np.float32 and a["images"].shape == (64, 64, 64, 3)
+    assert a["latents"].dtype == np.float32 and a["latents"].shape == (64, 3, 64, 64) and np.isfinite(a["latents"]).all()
+    assert (a["images"] == np.round(a["images"])).all() and a["images"].min() >= 0 and a["images"].max() <= 255
+    for n in ("images", "latents"):
+        assert np.array_equal(a[n], out[1003][n]), n

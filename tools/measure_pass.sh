@@ -11,8 +11,11 @@ rc=$?
 echo "pytest rc=$rc"; tail -4 gpurun_out/pytest_gpu.log
 # a failing, timed-out (124) or aborted (134) suite stops the pass: no numbers are published from a library that fails its tests
 if [ $rc -ne 0 ] || grep -q "Memory access fault" gpurun_out/pytest_gpu.log; then tail -40 gpurun_out/pytest_gpu.log; exit 1; fi
-timeout -k 10 600 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.log || { tail -5 gpurun_out/bench_default.log; exit 1; }
-tail -4 gpurun_out/bench_default.log
+# the default bench with every leg (--full: roofline, validation, host-inclusive leg, CPU baseline); tools/publish_pass.sh reads it
+# from measure_out/
+mkdir -p measure_out
+timeout -k 10 600 python bench.py --full > measure_out/bench_default.json 2> measure_out/bench_default.log || { tail -5 measure_out/bench_default.log; exit 1; }
+tail -4 measure_out/bench_default.log
 bash tools/prof_stats.sh r04 | cut -c1-150 | head -14
 cd $R && bash tools/prof_pmc.sh sq SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE | cut -c1-200 | head -8
 cd $R && bash tools/prof_pmc.sh fetch FETCH_SIZE GRBM_GUI_ACTIVE | cut -c1-200 | head -6

@@ -4,8 +4,8 @@
 set -e
 rnd=${1:?round}; tag=${2:?tag of the bench line}
 d=profiles/$rnd; g=gpurun_out
-cp $g/bench_default.json $d/bench_default_T1000_$tag.json
-cp $g/bench_default.log $d/bench_default_T1000_$tag.log
+cp measure_out/bench_default.json $d/bench_default_T1000_$tag.json
+cp measure_out/bench_default.log $d/bench_default_T1000_$tag.log
 cp $g/${rnd}_kernel_stats.csv $d/bench_steps20_kernel_stats.csv
 cp $g/pmc_summary_${rnd}.json $d/pmc_summary.json
 for t in sq fetch write; do test -s $g/${t}_counters.csv; cp $g/${t}_counters.csv $d/pmc_${t}_per_kernel.txt; done
