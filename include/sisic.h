@@ -257,7 +257,9 @@ int sisic_add_noise(sisic_ctx*, const float* x0, const float* noise, const float
                     const float* sqrt_one_minus_alpha_prod, float* out, int B, int64_t per_sample, void* stream);
 /* noise_pred = model(noisy, timesteps).sample in training mode (train_diffusion.py:218): the inference kernels, every
  * activation and GroupNorm statistic kept for the backward pass.  timesteps: host int64 [B], one per sample.
- * `sample` is read again by sisic_unet_backward (conv_in's weight gradient): it must stay valid until then.          */
+ * `sample` is read again by sisic_unet_backward (conv_in's weight gradient): it must stay valid until then.
+ * SISIC_EINVAL, before anything is recorded, when an attention level would hold more tokens than the attention backward
+ * pass takes (136x136 trains, 144x144 does not; inference has no such limit).                                         */
 int sisic_unet_train_forward(sisic_unet*, const float* sample, const int64_t* timesteps, float* out, int B, int H, int W,
                              void* stream);
 /* F.mse_loss(pred, target) (train_diffusion.py:219): loss_dev[0] = mean((pred - target)^2) (NULL: kept internally),

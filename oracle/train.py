@@ -32,7 +32,7 @@ def loss_and_grads(sd: Dict[str, torch.Tensor], images: torch.Tensor, noise: tor
     noisy = sched.add_noise(images.to(dtype), noise.to(dtype), timesteps)
     with torch.enable_grad():
         if dtype == torch.float64:
-            pred = _forward64(params, noisy, timesteps)
+            pred = unet_forward64(params, noisy, timesteps)
         else:
             pred = ounet.unet_forward(params, noisy, timesteps)
         loss = F.mse_loss(pred, noise.to(dtype))
@@ -40,7 +40,7 @@ def loss_and_grads(sd: Dict[str, torch.Tensor], images: torch.Tensor, noise: tor
     return float(loss.detach()), OrderedDict((k, g.detach()) for k, g in zip(params, grads)), pred.detach()
 
 
-def _forward64(params, noisy, timesteps):
+def unet_forward64(params, noisy, timesteps):
     """oracle/unet.py computes its sinusoid in fp32; for the float64 reference the embedding is rebuilt in float64 from
     the same fp32 frequency table so that only rounding, not the definition, differs."""
     orig = ounet.timestep_embedding

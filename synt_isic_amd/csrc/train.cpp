@@ -322,6 +322,23 @@ int require_train(sisic_unet* u, const char* what) {
     return SISIC_OK;
 }
 
+// The backward pass keeps an attention block's whole key/value rows in LDS (launch_attention_bwd): a resolution whose
+// attention levels have more tokens than that records a forward that could never be back-propagated.  Refused before anything
+// is recorded, so that no backward pass half-accumulates gradients before it fails.
+int check_trainable_resolution(sisic_unet* u, int H, int W) {
+    const sisic_unet_config& cfg = u->cfg;
+    const int n = cfg.n_blocks;
+    for (int lvl = 0; lvl < n; ++lvl) {
+        // down block lvl, up block n-1-lvl and (at the lowest level) the mid block run at H >> lvl x W >> lvl
+        if (!(cfg.down_attn[lvl] || cfg.up_attn[n - 1 - lvl] || lvl == n - 1)) continue;
+        const int h = H >> lvl, w = W >> lvl;
+        SISIC_REQUIRE((int64_t)h * w <= ATTN_BWD_MAX_TOKENS,
+                      "train_forward: %dx%d cannot be trained: its %dx%d attention level has %lld tokens, the attention backward "
+                      "pass takes at most %d", H, W, h, w, (long long)h * w, ATTN_BWD_MAX_TOKENS);
+    }
+    return SISIC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,6 +409,7 @@ int sisic_unet_train_forward(sisic_unet* u, const float* sample, const int64_t* 
     TrainState* tr = u->train.get();
     release_tape(u);                                       // a forward without a backward: drop the old tape
     SISIC_TRY(unet_check_shape(u, B, H, W));
+    SISIC_TRY(check_trainable_resolution(u, H, W));
     SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
     const int Hd = u->hidden, nin = 2 * u->cfg.n_freqs;
     SISIC_TRY(unet_grow(&tr->emb, &tr->emb_cap, (size_t)B * nin));

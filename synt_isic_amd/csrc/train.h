@@ -56,6 +56,12 @@ int launch_gn_bwd(sisic_ctx*, const float* da, const float* in0, int c0, const f
 int launch_accum_split(sisic_ctx*, const float* da, int B, int C, int HW, float* g0, int c0, float* g1, int c1, hipStream_t s);
 int launch_accum_pool2(sisic_ctx*, const float* da, int planes, int H, int W, float* g, hipStream_t s);
 int launch_add_inplace(sisic_ctx*, float* dst, const float* src, size_t n, hipStream_t s);
+// attention_bwd keeps a head's whole key/value rows in LDS, 32 + 3 floats per token within 160 KB: the most tokens it
+// accepts.  launch_attention_bwd refuses more, and sisic_unet_train_forward refuses a resolution whose attention levels have more.
+constexpr int ATTN_BWD_LDS_BYTES = 160 * 1024;
+constexpr int ATTN_BWD_MAX_TOKENS = 1170;
+static_assert(ATTN_BWD_MAX_TOKENS * 35 * 4 <= ATTN_BWD_LDS_BYTES && (ATTN_BWD_MAX_TOKENS + 1) * 35 * 4 > ATTN_BWD_LDS_BYTES,
+              "ATTN_BWD_MAX_TOKENS is the most tokens whose key/value rows fit the LDS");
 int launch_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                          int head_dim, hipStream_t s);
 int launch_linear_wgrad(sisic_ctx*, const float* dy, int ld, const float* x, int B, int R, int K, float* dW, hipStream_t s);

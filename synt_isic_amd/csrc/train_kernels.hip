@@ -869,11 +869,11 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
 
 int launch_attention_bwd(sisic_ctx* ctx, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                          int head_dim, hipStream_t s) {
-    SISIC_REQUIRE(qkv && o && dO && dqkv && head_dim == 8 && C % 8 == 0, "attention_bwd: bad arguments");
+    SISIC_REQUIRE(qkv && o && dO && dqkv && head_dim == 8 && C % 8 == 0 && N >= 0, "attention_bwd: bad arguments");
+    SISIC_REQUIRE(N <= ATTN_BWD_MAX_TOKENS, "attention_bwd: %d tokens do not fit the LDS (max %d)", N, ATTN_BWD_MAX_TOKENS);
     const size_t lds = ((size_t)N * 32 + 3 * (size_t)N) * sizeof(float);
-    SISIC_REQUIRE(lds <= 160 * 1024, "attention_bwd: %d tokens do not fit the LDS (max 1170)", N);
     static std::atomic<uint64_t> lds_opt_in{0};
-    SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(attention_bwd_kernel), 160 * 1024, lds_opt_in));
+    SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(attention_bwd_kernel), ATTN_BWD_LDS_BYTES, lds_opt_in));
     ProfileScope prof(ctx, s, PK_ATTN, 32.0 * B * C * N, 10.0 * B * C * double(N) * N);
     hipLaunchKernelGGL(attention_bwd_kernel, dim3(B * (C / 8)), dim3(ATB_THREADS), lds, s, qkv, o, dO, dqkv, C, N, 0.35355339059327373f);
     SISIC_HIP(hipGetLastError());
