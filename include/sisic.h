@@ -241,6 +241,37 @@ int sisic_sample_frames(sisic_unet*, float* x, int B, int H, int W, int T, const
                         const float* coef, float clip, const float* noise, float* traj, const int* traj_row,
                         uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream);
 
+/* ---- device noise ("device noise contract") ------------------------------------------------------
+ * z for image b (64-bit seed s_b), step index i of a run and element e of the image's n_per_image floats comes from one
+ * Philox4x32-10 block per four consecutive elements: counter (e >> 2, i, tag, 0), key (s_b & 0xffffffff, s_b >> 32), words
+ * (r0, r1) -> elements 4q, 4q+1 and (r2, r3) -> 4q+2, 4q+3 by Box-Muller (cos, sin) with u1 = ((r >> 8) + 1) * 2^-24,
+ * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T.  A pure function of
+ * (seed, step, tag, element): independent of the batch, the GPU count, graph or eager mode.  1 <= n_per_image <= 2^34.
+ * seeds: HOST uint64 [B], read before the call returns.
+ * sisic_noise_fill: out dev float [B, n_per_image];
+ * sisic_noise_bits: the same blocks as raw words, out dev uint32 [B, 4 * ceil(n_per_image / 4)].                         */
+int sisic_noise_fill(sisic_ctx*, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream);
+int sisic_noise_bits(sisic_ctx*, uint32_t* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream);
+/* sisic_ddpm_step over n = B * n_per_image floats with z generated in the kernel (tag 0) for step index `step`; unlike the
+ * entries above, seeds is a DEVICE uint64 [B] (the caller's buffer: the sampling loop below keeps its own).  out may be x.
+ * Any alignment and any n_per_image: tensors off a 16-byte line, or images that are not whole blocks, take an
+ * element-by-element path with the same values.                                                                        */
+int sisic_ddpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
+                        float c1, float sigma, float clip, void* stream);
+/* sisic_sample_frames with the per-step noise generated inside the scheduler-step kernel (tag 0) instead of read from a
+ * buffer: bit-identical to sisic_sample_frames given rows filled by sisic_noise_fill(step = step0 + i) for the steps i with
+ * sigma != 0.  seeds: HOST uint64 [B], read before the call returns.  step i of this call draws with step index step0 + i
+ * (a run cut into several calls passes its offset; step0 >= 0).  Steps with sigma == 0 draw nothing.  In graph mode the
+ * captured step of a shape serves every seed list and step0; buffer-noise and generated-noise calls capture different
+ * steps, so alternating between the two at one shape re-captures (sisic_unet_graph_builds).                              */
+int sisic_sample_frames_rng(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps,
+                            const float* coef, float clip, const uint64_t* seeds, int step0, float* traj,
+                            const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
+                            void* stream);
+
 /* ---- training step (diffusion/train_diffusion.py:201-266) -----------------------------------
  * fp32 throughout.  The reference wraps the forward in torch.cuda.amp.autocast() (fp16 matmuls/convolutions) and scales the
  * loss with a GradScaler; here the GradScaler PROTOCOL is implemented (loss_scale multiplies d loss, the optimizer step

@@ -98,6 +98,16 @@ SIGNATURES = {
     "sisic_sample_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                       C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_noise_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint32,
+                                   C.c_uint32, C.c_void_p]),
+    "sisic_noise_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint32,
+                                   C.c_uint32, C.c_void_p]),
+    "sisic_ddpm_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                      C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_void_p]),
+    "sisic_sample_frames_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
+                                          C.c_float, C.POINTER(C.c_uint64), C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                          C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "sisic_unet_train_begin": (C.c_int, [C.c_void_p]),
     "sisic_unet_train_end": (C.c_int, [C.c_void_p]),
     "sisic_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

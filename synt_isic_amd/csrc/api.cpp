@@ -164,6 +164,26 @@ int sisic_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
                             static_cast<hipStream_t>(stream));
 }
 
+int sisic_noise_fill(sisic_ctx* ctx, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream) {
+    SISIC_REQUIRE(ctx, "noise_fill: null context");
+    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, false, static_cast<hipStream_t>(stream));
+}
+
+int sisic_noise_bits(sisic_ctx* ctx, uint32_t* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream) {
+    SISIC_REQUIRE(ctx, "noise_bits: null context");
+    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, true, static_cast<hipStream_t>(stream));
+}
+
+int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
+                        float c1, float sigma, float clip, void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddpm_step_rng: null context or empty batch");
+    return launch_ddpm_step_rng(ctx, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod,
+                                sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
+}
+
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {
     SISIC_REQUIRE(ctx, "denorm_u8: null context");
     return launch_denorm_u8(ctx, x, out, B, C, H, W, static_cast<hipStream_t>(stream));

@@ -170,11 +170,20 @@ int launch_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int
 int launch_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* out, int64_t n,
                      float sb, float sa, float c0, float c1, float sigma, float clip, hipStream_t s);
 // graph-replayed sampling loop (elementwise.hip): per-step parameters selected on the device by a step index
-size_t loop_state_bytes();     // {int step; int pad; const float* noise_base}
+size_t loop_state_bytes();     // {int step; int step_base; const float* noise_base}
 int launch_loop_select_row(sisic_ctx*, const float* table, int R, const void* state, float* out, hipStream_t s);
 int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s);
 int launch_ddpm_step_indexed(sisic_ctx*, const float* eps, float* x, int64_t n, const void* state, const float* coef,
                              const int* zrow, float clip, hipStream_t s);
+// device noise (noise_device.h): the step with z generated in the kernel from the images' seeds (device
+// uint64 [n / n_per_image]), eager and graph-replayed forms; the blocks as a buffer of normals or raw words (HOST seeds)
+int launch_ddpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* out, int64_t n, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
+                         float clip, hipStream_t s);
+int launch_ddpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, int64_t n, int64_t n_per_image, const void* state,
+                                 const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
+int launch_noise_fill(sisic_ctx*, void* out, int B, int64_t n_per_image, const uint64_t* seeds_host, uint32_t step,
+                      uint32_t tag, bool bits, hipStream_t s);
 int launch_denorm_u8(sisic_ctx*, const float* x, uint8_t* out, int B, int C, int H, int W, hipStream_t s, int form = 0);
 // time embedding: sinusoid -> linear1 -> SiLU -> linear2 -> SiLU  (weights transposed [in][out])
 // save_* (optional, training): the sinusoid [B, 2 n_freqs] and the two linear outputs before their SiLU [B, hidden]

@@ -5,6 +5,7 @@
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
 //   * transpose2d_kernel: weight re-layout at load time
 #include "common.h"
+#include "noise_device.h"
 #include "pack_device.h"
 
 namespace sisic {
@@ -23,23 +24,48 @@ __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, f
     return r;
 }
 
-__global__ void __launch_bounds__(256)
-ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
-                 float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
-                 int vec4) {
-    const bool noise = (z != nullptr) && (sigma != 0.0f);
+// Where a step's z comes from: a buffer the caller filled, or the counter-based generator of noise_device.h (the device-noise
+// contract).  Both feed the same ddpm_one, so the step's arithmetic after z does not depend on the source.
+struct BufferNoise {
+    const float* __restrict__ z;
+    __device__ __forceinline__ bool present() const { return z != nullptr; }
+    __device__ __forceinline__ bool vec_ok() const { return (reinterpret_cast<uintptr_t>(z) & 15) == 0; }
+    __device__ __forceinline__ float4 get4(int64_t i4) const { return reinterpret_cast<const float4*>(z)[i4]; }
+    __device__ __forceinline__ float get1(int64_t i) const { return z[i]; }
+};
+
+struct PhiloxNoise {
+    const uint64_t* seeds;    // [B] device
+    int64_t npi;              // floats per image
+    uint32_t step;            // step index of the run (position in its timestep list)
+    __device__ __forceinline__ bool present() const { return true; }
+    __device__ __forceinline__ bool vec_ok() const { return (npi & 3) == 0; }     // otherwise a block straddles two images
+    __device__ __forceinline__ float4 get4(int64_t i4) const {
+        const int64_t q_per_image = npi >> 2, b = i4 / q_per_image;
+        return noise_normal4(seeds[b], (uint32_t)(i4 - b * q_per_image), step, 0u);
+    }
+    __device__ __forceinline__ float get1(int64_t i) const {
+        const int64_t b = i / npi;
+        return noise_normal1(seeds[b], i - b * npi, step, 0u);
+    }
+};
+
+// out may alias x (the loop steps in place): every element is read before it is written, by the thread that writes it
+template <class Z>
+__device__ __forceinline__ void ddpm_step_body(const float* __restrict__ eps, const float* x, float* out, int64_t n, float sb,
+                                               float sa, float c0, float c1, float sigma, float clip, bool vec4, const Z zs) {
+    const bool noise = zs.present() && (sigma != 0.0f);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (vec4) {
         const int64_t n4 = n >> 2;
         const float4* e4 = reinterpret_cast<const float4*>(eps);
         const float4* x4 = reinterpret_cast<const float4*>(x);
-        const float4* z4 = reinterpret_cast<const float4*>(z);
         float4* o4 = reinterpret_cast<float4*>(out);
         for (int64_t i = t0; i < n4; i += stride) {
             const float4 e = e4[i], xv = x4[i];
             float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (noise) zv = z4[i];
+            if (noise) zv = zs.get4(i);
             float4 r;
             r.x = ddpm_one(e.x, xv.x, zv.x, sb, sa, c0, c1, sigma, clip, noise);
             r.y = ddpm_one(e.y, xv.y, zv.y, sb, sa, c0, c1, sigma, clip, noise);
@@ -48,11 +74,27 @@ ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __r
             o4[i] = r;
         }
         for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
-            out[i] = ddpm_one(eps[i], x[i], noise ? z[i] : 0.f, sb, sa, c0, c1, sigma, clip, noise);
+            out[i] = ddpm_one(eps[i], x[i], noise ? zs.get1(i) : 0.f, sb, sa, c0, c1, sigma, clip, noise);
     } else {
         for (int64_t i = t0; i < n; i += stride)
-            out[i] = ddpm_one(eps[i], x[i], noise ? z[i] : 0.f, sb, sa, c0, c1, sigma, clip, noise);
+            out[i] = ddpm_one(eps[i], x[i], noise ? zs.get1(i) : 0.f, sb, sa, c0, c1, sigma, clip, noise);
     }
+}
+
+__global__ void __launch_bounds__(256)
+ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
+                 float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
+                 int vec4) {
+    ddpm_step_body(eps, x, out, n, sb, sa, c0, c1, sigma, clip, vec4 != 0, BufferNoise{z});
+}
+
+// the same step with z generated in the kernel (sisic_sample_frames_rng, eager form)
+__global__ void __launch_bounds__(256)
+ddpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
+                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
+                     float clip, int vec4) {
+    const PhiloxNoise zs{seeds, n_per_image, step};
+    ddpm_step_body(eps, x, out, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
 }
 
 int launch_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n, float sb,
@@ -72,13 +114,36 @@ int launch_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const flo
     return SISIC_OK;
 }
 
+// counter word 0 of a block is its index in the image: 32 bits
+static constexpr int64_t NOISE_MAX_PER_IMAGE = (int64_t)1 << 34;
+
+int launch_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int64_t n, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
+                         float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && out && seeds_dev && n > 0, "ddpm_step_rng: null tensor or empty");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "ddpm_step_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
+    SISIC_REQUIRE(sa != 0.0f, "ddpm_step_rng: sqrt_alpha_prod is zero");
+    ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(ddpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step, sb,
+                       sa, c0, c1, sigma, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // ---- the same step with its per-step parameters read from device memory (graph-replayed sampling loop) ----------------
 // One captured step is replayed for every step of the loop, so nothing that changes from step to step may be a launch
 // argument: the loop keeps {step index, noise base pointer} and its per-step tables (coefficients, noise row of the step
-// or -1) in device memory; this kernel selects its row, ddpm_advance_kernel moves the index on.
+// or -1) in device memory; this kernel selects its row, ddpm_advance_kernel moves the index on.  Nothing that changes from
+// call to call either: a generated-noise call's first step index is `step_base`, and its seeds lie in a library-owned
+// buffer whose address is part of the captured launch.
 struct LoopState {
     int step;
-    int pad;
+    int step_base;            // generated noise: the Philox step index is step_base + step (0 in buffer-noise calls)
     const float* noise;       // base of the [n_noise, n] noise rows of this call
 };
 
@@ -89,32 +154,19 @@ ddpm_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, con
     const float sb = coef[5 * step + 0], sa = coef[5 * step + 1], c0 = coef[5 * step + 2], c1 = coef[5 * step + 3],
                 sigma = coef[5 * step + 4];
     const int zr = zrow[step];
-    const float* z = zr >= 0 ? st->noise + (int64_t)zr * n : nullptr;
-    const bool noise = (z != nullptr) && (sigma != 0.0f);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (vec4 && ((reinterpret_cast<uintptr_t>(z) & 15) == 0)) {
-        const int64_t n4 = n >> 2;
-        const float4* e4 = reinterpret_cast<const float4*>(eps);
-        float4* x4 = reinterpret_cast<float4*>(x);
-        const float4* z4 = reinterpret_cast<const float4*>(z);
-        for (int64_t i = t0; i < n4; i += stride) {
-            const float4 e = e4[i], xv = x4[i];
-            float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (noise) zv = z4[i];
-            float4 r;
-            r.x = ddpm_one(e.x, xv.x, zv.x, sb, sa, c0, c1, sigma, clip, noise);
-            r.y = ddpm_one(e.y, xv.y, zv.y, sb, sa, c0, c1, sigma, clip, noise);
-            r.z = ddpm_one(e.z, xv.z, zv.z, sb, sa, c0, c1, sigma, clip, noise);
-            r.w = ddpm_one(e.w, xv.w, zv.w, sb, sa, c0, c1, sigma, clip, noise);
-            x4[i] = r;
-        }
-        for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
-            x[i] = ddpm_one(eps[i], x[i], noise ? z[i] : 0.f, sb, sa, c0, c1, sigma, clip, noise);
-    } else {
-        for (int64_t i = t0; i < n; i += stride)
-            x[i] = ddpm_one(eps[i], x[i], noise ? z[i] : 0.f, sb, sa, c0, c1, sigma, clip, noise);
-    }
+    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
+    ddpm_step_body(eps, x, x, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
+}
+
+__global__ void __launch_bounds__(256)
+ddpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
+                             const LoopState* __restrict__ st, const float* __restrict__ coef,
+                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
+    const int step = st->step;
+    const float sb = coef[5 * step + 0], sa = coef[5 * step + 1], c0 = coef[5 * step + 2], c1 = coef[5 * step + 3],
+                sigma = coef[5 * step + 4];
+    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+    ddpm_step_body(eps, x, x, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
 }
 
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
@@ -152,7 +204,81 @@ int launch_ddpm_step_indexed(sisic_ctx* ctx, const float* eps, float* x, int64_t
     return SISIC_OK;
 }
 
+int launch_ddpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, int64_t n, int64_t n_per_image, const void* state,
+                                 const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && state && coef && seeds_dev && n > 0, "ddpm_step_indexed_rng: null argument");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "ddpm_step_indexed_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
+    ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image,
+                       static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 size_t loop_state_bytes() { return sizeof(LoopState); }
+
+// ---- stand-alone noise: the blocks of noise_device.h as a buffer -----------------------------------------------------------
+// For tests and for callers that want z_t (or an x_T, tag 1) in memory.  Seeds travel as a launch argument, up to
+// NOISE_PACK images per launch (blockIdx.y): no device buffer to own, nothing to order between calls.
+constexpr int NOISE_PACK = 64;
+struct SeedPack { uint64_t s[NOISE_PACK]; };
+
+// out: [images of this launch, n_per_image] normals
+__global__ void __launch_bounds__(256)
+noise_fill_kernel(float* out, int64_t n_per_image, SeedPack seeds, uint32_t step, uint32_t tag, int vec4) {
+    const uint64_t seed = seeds.s[blockIdx.y];
+    float* o = out + (int64_t)blockIdx.y * n_per_image;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (vec4) {
+        for (int64_t q = t0; q < (n_per_image >> 2); q += stride)
+            reinterpret_cast<float4*>(o)[q] = noise_normal4(seed, (uint32_t)q, step, tag);
+    } else {
+        for (int64_t e = t0; e < n_per_image; e += stride) o[e] = noise_normal1(seed, e, step, tag);
+    }
+}
+
+// out: [images of this launch, 4 * ceil(n_per_image / 4)] raw words, whole blocks
+__global__ void __launch_bounds__(256)
+noise_bits_kernel(uint32_t* out, int64_t blocks_per_image, SeedPack seeds, uint32_t step, uint32_t tag) {
+    const uint64_t seed = seeds.s[blockIdx.y];
+    uint32_t* o = out + (int64_t)blockIdx.y * blocks_per_image * 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < blocks_per_image; q += stride) {
+        const uint4 r = noise_bits4(seed, (uint32_t)q, step, tag);
+        o[4 * q + 0] = r.x; o[4 * q + 1] = r.y; o[4 * q + 2] = r.z; o[4 * q + 3] = r.w;
+    }
+}
+
+int launch_noise_fill(sisic_ctx* ctx, void* out, int B, int64_t n_per_image, const uint64_t* seeds_host, uint32_t step,
+                      uint32_t tag, bool bits, hipStream_t s) {
+    SISIC_REQUIRE(out && seeds_host && B > 0, "noise_fill: null argument or empty batch");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE, "noise_fill: n_per_image %lld (1 .. 2^34)", (long long)n_per_image);
+    const int64_t blocks_per_image = (n_per_image + 3) / 4;
+    const int64_t row = bits ? blocks_per_image * 4 : n_per_image;
+    ProfileScope prof(ctx, s, PK_OTHER, 4.0 * (double)row * B, 0.0);
+    const int vec4 = (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = (bits || vec4) ? blocks_per_image : n_per_image;
+    const int gx = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    for (int b0 = 0; b0 < B; b0 += NOISE_PACK) {
+        const int nb = std::min(NOISE_PACK, B - b0);
+        SeedPack pack = {};
+        for (int k = 0; k < nb; ++k) pack.s[k] = seeds_host[b0 + k];
+        if (bits)
+            hipLaunchKernelGGL(noise_bits_kernel, dim3(gx, nb), dim3(256), 0, s, static_cast<uint32_t*>(out) + (int64_t)b0 * row,
+                               blocks_per_image, pack, step, tag);
+        else
+            hipLaunchKernelGGL(noise_fill_kernel, dim3(gx, nb), dim3(256), 0, s, static_cast<float*>(out) + (int64_t)b0 * row,
+                               n_per_image, pack, step, tag, vec4);
+        SISIC_HIP(hipGetLastError());
+    }
+    return SISIC_OK;
+}
 
 // ---- de-normalise to uint8 HWC ---------------------------------------------------------------
 // FORM 0: image_generator.py:441-447     clamp((x + 1) / 2, 0, 1) * 255, truncated

@@ -679,7 +679,7 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)sisic_unet_train_end(u);
     (void)hipDeviceSynchronize();
     pool_release_all(u);
-    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur})
+    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -776,20 +776,26 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
 
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
 // launches for every step, so that a captured step can be replayed.
-static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, hipStream_t s) {
+static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, bool rng, hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + 5 * 1000);
     SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
     SISIC_TRY(run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
-    SISIC_TRY(launch_ddpm_step_indexed(u->ctx, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev, clip, s));
+    if (rng)
+        SISIC_TRY(launch_ddpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state, coef_dev,
+                                               reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
+    else
+        SISIC_TRY(launch_ddpm_step_indexed(u->ctx, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev, clip, s));
     return launch_loop_advance(u->ctx, state, s);
 }
 
 // The loop as ONE captured step replayed T-1 times (hipGraph): at batch 1 a step is ~190 launches of 5-20 us kernels and
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
+// rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
 static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, const float* noise,
-                        float* traj, const int* traj_row, const volatile int* cancel, int* steps_done, hipStream_t caller) {
+                        bool rng, int step0, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
+                        hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
     SISIC_REQUIRE(T <= 1000, "sample: at most 1000 steps per call");
@@ -804,11 +810,12 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     SISIC_TRY(grow(&u->x_work, &u->x_work_cap, n));
     SISIC_TRY(grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)u->tproj_R));
     SISIC_TRY(grow(&u->loop_tables, &u->loop_tables_cap, (size_t)4 + 5 * 1000 + 1000));
-    // tables of this call: {step = 0, noise base}, coefficients, noise row per step (-1: the step adds no noise)
+    // tables of this call: {step = 0, step base, noise base}, coefficients, noise row per step (-1: the step adds no noise)
     std::vector<float> tab(4 + 5 * 1000 + 1000, 0.0f);
     {
-        int step0 = 0;
-        std::memcpy(&tab[0], &step0, sizeof(int));
+        const int first = 0, base = rng ? step0 : 0;
+        std::memcpy(&tab[0], &first, sizeof(int));
+        std::memcpy(&tab[1], &base, sizeof(int));
         std::memcpy(&tab[2], &noise, sizeof(noise));
         std::memcpy(&tab[4], coef, (size_t)T * 5 * sizeof(float));
         int* zr = reinterpret_cast<int*>(&tab[4 + 5 * 1000]);
@@ -839,7 +846,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
-                  u->loop_key.gen == gen;
+                  u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev);
         for (int k = 0; k < 5; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
@@ -847,7 +854,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, s);
+        rc = loop_step(u, B, H, W, n, clip, rng, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
@@ -857,7 +864,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, s);
+            const int crc = loop_step(u, B, H, W, n, clip, rng, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -869,6 +876,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             SISIC_HIP(hipGraphInstantiate(&u->loop_exec, g, nullptr, nullptr, 0));
             u->loop_key.B = B; u->loop_key.H = H; u->loop_key.W = W; u->loop_key.clip = clip; u->loop_key.s = s;
             u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
+            u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
             for (int k = 0; k < 5; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
@@ -894,9 +902,11 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
     return sisic_sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, traj, nullptr, out_u8, cancel, steps_done, stream);
 }
 
-int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
-                        float clip, const float* noise, float* traj, const int* traj_row, uint8_t* out_u8,
-                        const volatile int* cancel, int* steps_done, void* stream) {
+// The loop behind sisic_sample_frames (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames_rng (seeds: HOST uint64 [B],
+// noise NULL): the two differ in where the scheduler step takes z from, nothing else.
+static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                         float clip, const float* noise, const uint64_t* seeds, int step0, float* traj, const int* traj_row,
+                         uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
     SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
     if (traj_row)
@@ -911,6 +921,14 @@ int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, con
     SISIC_REQUIRE(u->cfg.out_channels == C, "sample: in/out channels differ");
     const size_t n = (size_t)B * C * H * W;
     SISIC_TRY(grow(&u->eps_buf, &u->eps_floats, n));
+    const bool rng = seeds != nullptr;
+    if (rng) {
+        // 2^31 step indices is ample (a run has at most 1000) and keeps step0 + i inside the int of the device-side state
+        SISIC_REQUIRE(step0 >= 0 && step0 <= INT32_MAX - T, "sample_rng: step0 %d", step0);
+        static_assert(sizeof(uint64_t) == 2 * sizeof(float), "seeds are staged as pairs of floats");
+        SISIC_TRY(grow(&u->seeds_dev, &u->seeds_cap, 2 * (size_t)std::max(B, 64)));
+        SISIC_TRY(stage_upload(u, reinterpret_cast<const float*>(seeds), 2 * (size_t)B, u->seeds_dev, s));
+    }
 
     // every step's time embedding and time_emb_proj rows in one batch before the loop
     std::vector<float> tv(T);
@@ -921,7 +939,7 @@ int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, con
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, noise, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, noise, rng, step0, traj, traj_row, cancel, steps_done, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
@@ -941,13 +959,33 @@ int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, con
         const float* c = coef + (size_t)i * 5;
         const float* z = nullptr;
         if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-        SISIC_TRY(launch_ddpm_step(u->ctx, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip, s));
+        if (rng)
+            SISIC_TRY(launch_ddpm_step_rng(u->ctx, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B),
+                                           reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
+                                           c[3], c[4], clip, s));
+        else
+            SISIC_TRY(launch_ddpm_step(u->ctx, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip, s));
         const int row = traj_row ? traj_row[i] : i;
         if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (steps_done) *steps_done = i + 1;
     }
     if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
     return SISIC_OK;
+}
+
+int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                        float clip, const float* noise, float* traj, const int* traj_row, uint8_t* out_u8,
+                        const volatile int* cancel, int* steps_done, void* stream) {
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, nullptr, 0, traj, traj_row, out_u8, cancel, steps_done,
+                         stream);
+}
+
+int sisic_sample_frames_rng(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                            float clip, const uint64_t* seeds, int step0, float* traj, const int* traj_row, uint8_t* out_u8,
+                            const volatile int* cancel, int* steps_done, void* stream) {
+    SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, nullptr, seeds, step0, traj, traj_row, out_u8, cancel,
+                         steps_done, stream);
 }
 
 }  // extern "C"

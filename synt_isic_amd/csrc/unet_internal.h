@@ -204,6 +204,8 @@ struct sisic_unet {
     struct LoopKey {
         int B = 0, H = 0, W = 0; float clip = 0; hipStream_t s = nullptr; bool latency = false; uint64_t gen = 0;
         const void* ptrs[5] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur at capture time: each can be re-allocated
+        bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
+        const void* seeds = nullptr;     // ... from the seeds at this address
     } loop_key;
     bool loop_valid = false;
     int64_t loop_builds = 0;             // captures + instantiations so far (sisic_unet_graph_builds)
@@ -214,6 +216,8 @@ struct sisic_unet {
     size_t loop_tables_cap = 0;
     float* tproj_cur = nullptr;
     size_t tproj_cur_cap = 0;
+    float* seeds_dev = nullptr;          // uint64 [B] seeds of the running sisic_sample_frames_rng call (sized in floats: 2 per seed)
+    size_t seeds_cap = 0;
 
     int add(const std::string& name, int64_t numel) {
         index[name] = (int)names.size();

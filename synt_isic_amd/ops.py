@@ -172,6 +172,57 @@ def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
     return out
 
 
+def _seed_array(seeds):
+    """HOST uint64 [B] as the C ABI takes it; seeds are 64-bit unsigned (negative values are refused, not wrapped)."""
+    seeds = [int(s) for s in seeds]
+    if not seeds or any(s < 0 or s >> 64 for s in seeds):
+        raise ValueError("seeds must be a non-empty sequence of integers in 0 .. 2**64-1")
+    return (C.c_uint64 * len(seeds))(*seeds)
+
+
+def noise_fill(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") -> torch.Tensor:
+    """sisic_noise_fill: fp32 [B, n_per_image] normals of the device-noise contract for
+    ``(seeds[b], step, tag)`` -- what the scheduler step of ``sisic_sample_frames_rng`` adds at step index ``step`` (tag 0)."""
+    lib = _lib.load()
+    device = torch.device(device)
+    arr = _seed_array(seeds)
+    out = torch.empty((len(arr), int(n_per_image)), dtype=torch.float32, device=device)
+    check(lib.sisic_noise_fill(context(device), out.data_ptr(), len(arr), int(n_per_image), arr, int(step), int(tag),
+                               _stream(device)))
+    return out
+
+
+def noise_bits(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") -> torch.Tensor:
+    """sisic_noise_bits: the Philox4x32-10 words behind ``noise_fill``, [B, 4*ceil(n_per_image/4)] (int32 tensor holding the
+    uint32 bit patterns: view it as uint32 on the host)."""
+    lib = _lib.load()
+    device = torch.device(device)
+    arr = _seed_array(seeds)
+    words = 4 * ((int(n_per_image) + 3) // 4)
+    out = torch.empty((len(arr), words), dtype=torch.int32, device=device)
+    check(lib.sisic_noise_bits(context(device), out.data_ptr(), len(arr), int(n_per_image), arr, int(step), int(tag),
+                               _stream(device)))
+    return out
+
+
+def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ddpm_step`` with z generated in the kernel: eps, x are [B, ...] (or flat with B = len(seeds) equal images);
+    image b draws ``noise_fill([seeds[b]], n_per_image, step)``."""
+    lib = _lib.load()
+    arr = _seed_array(seeds)
+    B = len(arr)
+    if x.numel() % B:
+        raise ValueError(f"{x.numel()} elements are not {B} equal images")
+    if out is None:
+        out = torch.empty_like(x)
+    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    sb, sa, c0, c1, sigma = (float(v) for v in coef)
+    check(lib.sisic_ddpm_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+                                  seeds_dev.data_ptr(), int(step), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
+    return out
+
+
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,
                  gn_shift=None, gn_silu=False) -> torch.Tensor:
     """d/dW of ``conv2d`` with the same prologue / index maps: dW [Cout, Cin, k, k] from the forward input(s) and the

@@ -10,6 +10,11 @@ Noise contract (a defined extension): image b owns one C
 ``torch.Generator().manual_seed(seed_b)``; ``x_T[b]`` is drawn first, then ``z_t[b]``
 for every step with t > 0 in loop order.  Results are independent of the batch an
 image is sampled in and of how images are sharded over GPUs.
+
+``noise="device"`` (off by default) is a second contract with the same independence: ``x_T[b]`` from torch's device
+generator seeded with ``seed_b`` (the reference's own spelling on a GPU, so its ``noise_hash``), and every ``z_t[b]``
+generated inside the scheduler-step kernel by Philox4x32-10 keyed with ``seed_b``: no host RNG,
+no noise buffer, no upload.  The two modes give different images for one seed.
 """
 from __future__ import annotations
 
@@ -61,6 +66,39 @@ def draw_noise(seeds: Sequence[int], n_noise_steps: int, chw: Tuple[int, int, in
             # one draw of n*numel values == n consecutive draws of numel (numel is a multiple of 16)
             z[:, b] = torch.randn((n_noise_steps,) + tuple(chw), generator=g)
     return x_T, z
+
+
+NOISE_MODES = ("host", "device")
+
+
+def _check_noise_mode(noise: str) -> str:
+    if noise not in NOISE_MODES:
+        raise ValueError(f"noise must be one of {NOISE_MODES}, got {noise!r}")
+    return noise
+
+
+@dataclass(frozen=True)
+class DeviceNoise:
+    """Per-step noise generated inside the scheduler-step kernel (``sisic_sample_frames_rng``): image b of the batch draws
+    with ``seeds[b]``, step i of the loop with step index ``step0 + i`` (a run cut into several calls passes its offset)."""
+    seeds: Tuple[int, ...]
+    step0: int = 0
+
+    def __post_init__(self):
+        object.__setattr__(self, "seeds", tuple(int(s) for s in self.seeds))
+        if any(s < 0 or s >> 64 for s in self.seeds):
+            raise ValueError("seeds must be integers in 0 .. 2**64-1")
+
+
+def draw_x_T_device(seeds: Sequence[int], chw: Tuple[int, int, int], device: torch.device) -> torch.Tensor:
+    """x_T [B,C,H,W] on ``device``, image by image from ``torch.Generator(device=device).manual_seed(seed_b)``: the
+    reference's spelling (image_generator.py:369-381), so ``noise_hash`` is what it records for that seed on that device."""
+    rows = []
+    for s in seeds:
+        g = torch.Generator(device=device)
+        g.manual_seed(int(s))
+        rows.append(torch.randn((1,) + tuple(chw), device=device, generator=g))
+    return torch.cat(rows, dim=0)
 
 
 class NoiseStream:
@@ -239,8 +277,9 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
 def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: torch.Tensor,
                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
                       cancel_flag: Optional[C.c_int] = None) -> SampleResult:
-    """x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), or a ``NoiseStream``
-    (the loop then runs segment by segment while the stream draws and uploads the next segment's noise).
+    """x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
+    (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
+    ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
     return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``)."""
     if isinstance(noise, NoiseStream):
         return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices)
@@ -253,6 +292,11 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: t
     T = ts.numel()
     coef = scheduler.coefficient_table().contiguous()
     n_noise = int((coef[:, 4] != 0).sum())
+    device_noise = noise if isinstance(noise, DeviceNoise) else None
+    if device_noise is not None:
+        if len(device_noise.seeds) != B:
+            raise ValueError(f"DeviceNoise holds {len(device_noise.seeds)} seeds for a batch of {B}")
+        noise = None
     if noise is not None:
         if tuple(noise.shape) != (n_noise, B, Cc, H, W) or noise.device != dev or noise.dtype != torch.float32:
             raise ValueError(f"noise must be fp32 {(n_noise, B, Cc, H, W)} on {dev}, got {tuple(noise.shape)}")
@@ -263,14 +307,18 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: t
     out_u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
     done = C.c_int(0)
     clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
-    rc = lib.sisic_sample_frames(model.handle, x.data_ptr(), B, H, W, T,
-                                 C.cast(ts.data_ptr(), _lib.c_int64_p), C.cast(coef.data_ptr(), _lib.c_float_p),
-                                 float(clip), noise.data_ptr() if noise is not None else None,
-                                 traj.data_ptr() if traj is not None and len(kept) else None,
-                                 rows.ctypes.data_as(C.POINTER(C.c_int)) if rows is not None and len(kept) else None,
-                                 out_u8.data_ptr(),
-                                 C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    head = (model.handle, x.data_ptr(), B, H, W, T, C.cast(ts.data_ptr(), _lib.c_int64_p),
+            C.cast(coef.data_ptr(), _lib.c_float_p), float(clip))
+    tail = (traj.data_ptr() if traj is not None and len(kept) else None,
+            rows.ctypes.data_as(C.POINTER(C.c_int)) if rows is not None and len(kept) else None,
+            out_u8.data_ptr(),
+            C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if device_noise is not None:
+        seeds = (C.c_uint64 * B)(*device_noise.seeds)
+        rc = lib.sisic_sample_frames_rng(*head, seeds, int(device_noise.step0), *tail)
+    else:
+        rc = lib.sisic_sample_frames(*head, noise.data_ptr() if noise is not None else None, *tail)
     if rc != _lib.SISIC_ECANCEL:
         check(rc)
     cancelled = rc == _lib.SISIC_ECANCEL
@@ -442,9 +490,13 @@ class Sampler:
         return self.generate_seeds(class_name, seeds, T, **kwargs)
 
     def generate_seeds(self, class_name: str, seeds: Sequence[int], T: int, size: Tuple[int, int] = (128, 128),
-                       return_trajectory: bool = False, save_every_n: Optional[int] = None) -> SampleResult:
+                       return_trajectory: bool = False, save_every_n: Optional[int] = None,
+                       noise: str = "host") -> SampleResult:
         """save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
-        xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise."""
+        xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise.
+        noise: "host" (the default: one CPU generator per image, see the module docstring) or "device" (x_T from torch's
+        device generator, z_t generated in the step kernel: no host RNG, no noise buffers; other images for the same seed)."""
+        _check_noise_mode(noise)
         if class_name not in self.models:
             raise KeyError(f"no model loaded for class '{class_name}'")
         model = self.models[class_name]
@@ -454,6 +506,15 @@ class Sampler:
             save_indices = trajectory_save_indices([int(t) for t in sched.timesteps], save_every_n)
         n_noise = sum(1 for t in sched.timesteps if int(t) > 0)
         H, W = size
+        if noise == "device":
+            x_T = draw_x_T_device(seeds, (model.config.in_channels, H, W), self.device)
+            hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
+            res = run_sampling_loop(model, sched, x_T, DeviceNoise(tuple(seeds)), return_trajectory=return_trajectory,
+                                    save_indices=save_indices, cancel_flag=self.cancel)
+            torch.cuda.current_stream(self.device).synchronize()
+            res.seeds = [int(s) for s in seeds]
+            res.noise_hashes = hashes
+            return res
         # noise is drawn segment by segment on worker threads while the GPU samples (NoiseStream); the values are
         # those of draw_noise(seeds, n_noise, ...)
         ns = NoiseStream(seeds, (model.config.in_channels, H, W), self.device, self.noise_segment_steps,
@@ -471,7 +532,7 @@ class Sampler:
 
     def generate(self, seed: int, class_name: str, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,
-                 save_every_n: Optional[int] = None):
+                 save_every_n: Optional[int] = None, noise: str = "host"):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -482,6 +543,7 @@ class Sampler:
         ``(seed + md5_offset(class) + i) & 0x7fffffff`` (image_generator.py:626-631).
         postprocess=True applies the class colour statistics (``load_color_statistics``) to the uint8 images like
         ``generate_single_image(..., postprocess=True)`` does before saving (image_generator.py:449-452).
+        noise: "host" or "device", as in ``generate_seeds``.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
         """
         if seed_is_base:
@@ -489,7 +551,7 @@ class Sampler:
         else:
             seeds = [(int(seed) + i) & 0x7FFFFFFF for i in range(count)]
         res = self.generate_images(class_name, seeds, T, size=size, return_trajectory=return_trajectory,
-                                   save_every_n=save_every_n)
+                                   save_every_n=save_every_n, noise=noise)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:
