@@ -245,7 +245,8 @@ int sisic_sample_frames(sisic_unet*, float* x, int B, int H, int W, int T, const
  * z for image b (64-bit seed s_b), step index i of a run and element e of the image's n_per_image floats comes from one
  * Philox4x32-10 block per four consecutive elements: counter (e >> 2, i, tag, 0), key (s_b & 0xffffffff, s_b >> 32), words
  * (r0, r1) -> elements 4q, 4q+1 and (r2, r3) -> 4q+2, 4q+3 by Box-Muller (cos, sin) with u1 = ((r >> 8) + 1) * 2^-24,
- * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T.  A pure function of
+ * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T; tag 2: the noise
+ * interventions of sisic_intervene.  A pure function of
  * (seed, step, tag, element): independent of the batch, the GPU count, graph or eager mode.  1 <= n_per_image <= 2^34.
  * seeds: HOST uint64 [B], read before the call returns.
  * sisic_noise_fill: out dev float [B, n_per_image];
@@ -379,6 +380,58 @@ int sisic_class_scores(sisic_ctx*, const float* logits, int B, int n_classes, in
  * masks[s, y/patch, x/patch] != 0, else 0.  image: dev [C,H,W]; masks: dev uint8 [S,H/patch,W/patch].  */
 int sisic_mask_patches(sisic_ctx*, const float* image, const uint8_t* masks, float* out, int S, int C, int H, int W,
                        int patch, void* stream);
+
+/* ---- counterfactual interventions and causal-shift metrics (xai/XAI.py:1454-1700, stage 2 of :2822-2896) ---------------
+ * sisic_intervene builds J modified images in one launch (64 jobs per launch beyond that).  Job j takes frame
+ * jobs[j].frame of frames (dev [F,C,H,W]) and mask jobs[j].mask of masks (dev uint8 [M,H,W], non-zero = inside the region,
+ * shared by the channels) and writes
+ *     out[j] = clamp(image * (1 - m) + intervention * m, -1, 1)
+ * The clamp covers the WHOLE image as in the reference (XAI.py:1575): values of an early-trajectory latent outside [-1, 1]
+ * change outside the mask too.  m is 0 or 1, so inside [-1, 1] the blend is the image or the intervention bit for bit.
+ * intervention, by jobs[j].type:
+ *   0 noise           z * noise_std
+ *   1 gaussian_noise  z * max(noise_std, 0.5 * std(image)), std = the unbiased standard deviation of the image's C*H*W values
+ *   2 zero            0
+ *   3 mean            the channel's mean over H x W
+ *   4 blur            blur_kernel x blur_kernel box average, stride 1, zero padding k/2, divisor k*k (F.avg_pool2d); an even
+ *                     blur_kernel becomes k + 1 (XAI.py:1513); 1 <= k <= 31
+ *   5 inpaint         the 5 x 5 box average with zero padding (XAI.py:1530-1538)
+ *   6 shuffle         intervention[c, p] = image[c, src_index[j, c, p]]: the caller's permutation of the masked pixels of
+ *                     every channel (identity elsewhere); an index outside 0 .. H*W-1 reads pixel p itself
+ * z: the device-noise contract above with seeds[j] (HOST uint64 [J]), step 0 and tag 2 -- element e of job j is element e of
+ * sisic_noise_fill(out, J, C*H*W, seeds, 0, 2), a pure function of (seed, element).
+ * src_index: dev int32 [J,C,H*W], read by shuffle jobs only; may be NULL when no job is a shuffle.
+ * intervention_out: dev [J,C,H,W] receiving the intervention itself, or NULL.
+ * stats: dev [J,4] = mask coverage (mean of m), mean |image - out|, max |image - out|, mean |intervention|
+ * (the 'statistics' of XAI.py:1587-1593).
+ * Every reduction runs in a fixed order inside the job's own workgroup: a job's output depends on the job alone, not on its
+ * position in the table or on the other jobs, and two runs are bit-equal.  Any C, H, W.  The job table is validated before
+ * anything is launched: a frame or mask index out of range, an unknown type, a blur kernel out of range or a shuffle
+ * without src_index return SISIC_EINVAL.                                                                              */
+typedef struct sisic_intervention_job {
+    int frame;          /* row of frames, 0 .. F-1 */
+    int mask;           /* row of masks, 0 .. M-1  */
+    int type;           /* 0 .. 6, see above        */
+    int blur_kernel;    /* type 4 only              */
+    float noise_std;    /* types 0 and 1            */
+} sisic_intervention_job;
+int sisic_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* masks, int M, int C, int H, int W, int J,
+                    const sisic_intervention_job* jobs, const uint64_t* seeds, const int32_t* src_index, float* out,
+                    float* intervention_out, float* stats, void* stream);
+
+/* compute_causal_shift_comprehensive (XAI.py:1600-1700) for J modified images at once, from logits the caller obtained with
+ * ONE sisic_resnet_forward over originals and modified images: logits_orig dev [F,n], logits_mod dev [J,n], job_frame HOST
+ * int [J] (the original of job j).  Softmax in fp32 with the maximum subtracted; score(c) = log(p_c + 1e-8).
+ * rows: dev [J, 6*n + 7] fp32.  Row j holds, for every class c, the six floats at 6*c:
+ *     orig_score, mod_score, cfi = orig_score - mod_score, delta = |cfi| / (|orig_score| + 1e-8), p_orig, p_mod
+ * and then, at 6*n:
+ *     argmax p_orig, argmax p_mod (class ids as floats, the first maximum), max p_orig, max p_mod,
+ *     KL = sum_c p_orig (log p_orig - log(p_mod + 1e-8))            (a term with p_orig = 0 is 0, as F.kl_div defines it),
+ *     JS = 0.5 * sum_c [ p_orig (log p_orig - l_c) + p_mod (log p_mod - l_c) ],  l_c = log((p_orig + p_mod)/2 + 1e-8),
+ *     TV = 0.5 * sum_c |p_orig - p_mod|.
+ * A frame index out of range returns SISIC_EINVAL.                                                                   */
+int sisic_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n_classes,
+                      const int* job_frame, float* rows, void* stream);
 
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------- */
 /* When enabled, every conv launch is bracketed by HIP events on its own stream and

@@ -57,6 +57,12 @@ class UNetConfigC(C.Structure):
     ]
 
 
+class InterventionJob(C.Structure):
+    """struct sisic_intervention_job"""
+    _fields_ = [("frame", C.c_int), ("mask", C.c_int), ("type", C.c_int), ("blur_kernel", C.c_int),
+                ("noise_std", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -148,6 +154,11 @@ SIGNATURES = {
                                      C.c_void_p]),
     "sisic_mask_patches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_void_p]),
+    "sisic_intervene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(InterventionJob), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "sisic_cfi_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.c_void_p, C.c_void_p]),
     "sisic_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "sisic_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), c_int64_p, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -194,6 +194,20 @@ int sisic_denorm_u8_form(sisic_ctx* ctx, const float* x, uint8_t* out, int B, in
     return launch_denorm_u8(ctx, x, out, B, C, H, W, static_cast<hipStream_t>(stream), form);
 }
 
+int sisic_intervene(sisic_ctx* ctx, const float* frames, int F, const uint8_t* masks, int M, int C, int H, int W, int J,
+                    const sisic_intervention_job* jobs, const uint64_t* seeds, const int32_t* src_index, float* out,
+                    float* intervention_out, float* stats, void* stream) {
+    SISIC_REQUIRE(ctx, "intervene: null context");
+    return launch_intervene(ctx, frames, F, masks, M, C, H, W, J, jobs, seeds, src_index, out, intervention_out, stats,
+                            static_cast<hipStream_t>(stream));
+}
+
+int sisic_cfi_metrics(sisic_ctx* ctx, const float* logits_orig, int F, const float* logits_mod, int J, int n_classes,
+                      const int* job_frame, float* rows, void* stream) {
+    SISIC_REQUIRE(ctx, "cfi_metrics: null context");
+    return launch_cfi_metrics(ctx, logits_orig, F, logits_mod, J, n_classes, job_frame, rows, static_cast<hipStream_t>(stream));
+}
+
 int sisic_profile_enable(sisic_ctx* ctx, int on) {
     SISIC_REQUIRE(ctx, "profile_enable: null context");
     ctx->profiling = on != 0;

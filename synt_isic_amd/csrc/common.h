@@ -205,4 +205,11 @@ int launch_class_scores(sisic_ctx*, const float* logits, int B, int n, int targe
 int launch_mask_patches(sisic_ctx*, const float* image, const uint8_t* masks, float* out, int S, int C, int H, int W,
                         int patch, hipStream_t s);
 
+// xai_kernels.hip: counterfactual interventions and causal-shift metrics (include/sisic.h)
+int launch_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* masks, int M, int C, int H, int W, int J,
+                     const sisic_intervention_job* jobs, const uint64_t* seeds, const int32_t* src_index, float* out,
+                     float* intervention_out, float* stats, hipStream_t s);
+int launch_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n,
+                       const int* job_frame, float* rows, hipStream_t s);
+
 }  // namespace sisic

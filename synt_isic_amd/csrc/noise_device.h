@@ -1,7 +1,7 @@
 // noise_device.h -- the device-noise contract: Philox4x32-10 + Box-Muller, one block per four
 // consecutive elements of an image.  A pure function of (seed, step, tag, element): no state, nothing to synchronise.
-// Included by elementwise.hip only, so that every user is compiled with that file's -ffp-contract=off and the step kernels
-// and the stand-alone fill kernel produce the same bits.
+// Included by elementwise.hip and xai_kernels.hip only, both compiled with -ffp-contract=off (csrc/Makefile), so that the step
+// kernels, the stand-alone fill kernel and the noise interventions produce the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -281,6 +281,68 @@ def denorm_u8(x: torch.Tensor, form="image_generator") -> torch.Tensor:
     return out
 
 
+INTERVENTION_TYPES = {"noise": 0, "gaussian_noise": 1, "zero": 2, "mean": 3, "blur": 4, "inpaint": 5, "shuffle": 6}
+CFI_PER_CLASS = 6          # orig_score, mod_score, cfi, delta, p_orig, p_mod
+CFI_TAIL = 7               # argmax p_orig, argmax p_mod, max p_orig, max p_mod, KL, JS, TV
+
+
+def intervene(frames: torch.Tensor, masks: torch.Tensor, jobs, seeds, src_index: Optional[torch.Tensor] = None,
+              with_intervention: bool = False):
+    """sisic_intervene: frames [F,C,H,W] fp32, masks uint8 [M,H,W], ``jobs`` a sequence of
+    ``(frame, mask, type, blur_kernel, noise_std)`` with ``type`` a name of INTERVENTION_TYPES or its number, ``seeds`` one
+    64-bit seed per job, ``src_index`` int32 [J,C,H*W] for shuffle jobs.  Returns ``(modified [J,C,H,W], intervention
+    [J,C,H,W] or None, stats [J,4])``: stats = mask coverage, mean |image - modified|, max |image - modified|, mean |intervention|."""
+    lib = _lib.load()
+    if frames.dim() != 4:
+        raise ValueError(f"frames must be [F,C,H,W], got {tuple(frames.shape)}")
+    F_, Cc, H, W = frames.shape
+    if not masks.is_cuda or masks.dtype != torch.uint8 or not masks.is_contiguous() or masks.dim() != 3 \
+            or tuple(masks.shape[1:]) != (H, W) or masks.device != frames.device:
+        raise ValueError(f"masks must be a contiguous uint8 [M,{H},{W}] tensor on {frames.device} (got {masks.dtype}, "
+                         f"{tuple(masks.shape)}, {masks.device})")
+    jobs = list(jobs)
+    J = len(jobs)
+    if J == 0:
+        raise ValueError("no intervention jobs")
+    table = (_lib.InterventionJob * J)()
+    for j, (f, m, typ, k, std) in enumerate(jobs):
+        if isinstance(typ, str):
+            if typ not in INTERVENTION_TYPES:
+                raise ValueError(f"unknown intervention type '{typ}' (one of {', '.join(INTERVENTION_TYPES)})")
+            typ = INTERVENTION_TYPES[typ]
+        table[j] = _lib.InterventionJob(int(f), int(m), int(typ), int(k), float(std))
+    arr = _seed_array(seeds)
+    if len(arr) != J:
+        raise ValueError(f"{len(arr)} seeds for {J} jobs")
+    if src_index is not None and (not src_index.is_cuda or src_index.dtype != torch.int32 or not src_index.is_contiguous()
+                                  or tuple(src_index.shape) != (J, Cc, H * W) or src_index.device != frames.device):
+        raise ValueError(f"src_index must be a contiguous int32 {(J, Cc, H * W)} tensor on {frames.device}")
+    out = torch.empty((J, Cc, H, W), dtype=torch.float32, device=frames.device)
+    iv = torch.empty_like(out) if with_intervention else None
+    stats = torch.empty((J, 4), dtype=torch.float32, device=frames.device)
+    check(lib.sisic_intervene(context(frames.device), _ptr(frames, "frames"), F_, masks.data_ptr(), masks.shape[0], Cc, H, W, J,
+                              table, arr, None if src_index is None else src_index.data_ptr(), out.data_ptr(),
+                              None if iv is None else iv.data_ptr(), stats.data_ptr(), _stream(frames.device)))
+    return out, iv, stats
+
+
+def cfi_metrics(logits_orig: torch.Tensor, logits_mod: torch.Tensor, job_frame) -> torch.Tensor:
+    """sisic_cfi_metrics: logits_orig [F,n], logits_mod [J,n], job_frame[j] = the row of logits_orig that job j modified.
+    Returns the [J, 6n+7] rows documented in include/sisic.h."""
+    lib = _lib.load()
+    if logits_orig.dim() != 2 or logits_mod.dim() != 2 or logits_orig.shape[1] != logits_mod.shape[1]:
+        raise ValueError(f"logits must be [F,n] and [J,n], got {tuple(logits_orig.shape)} and {tuple(logits_mod.shape)}")
+    J, n = logits_mod.shape
+    frames = [int(f) for f in job_frame]
+    if len(frames) != J:
+        raise ValueError(f"{len(frames)} frame indices for {J} rows of logits")
+    rows = torch.empty((J, CFI_PER_CLASS * n + CFI_TAIL), dtype=torch.float32, device=logits_mod.device)
+    check(lib.sisic_cfi_metrics(context(logits_mod.device), _ptr(logits_orig, "logits_orig"), logits_orig.shape[0],
+                                _ptr(logits_mod, "logits_mod"), J, n, (C.c_int * J)(*frames), rows.data_ptr(),
+                                _stream(logits_mod.device)))
+    return rows
+
+
 _KINDS = {"conv3x3": 0, "conv1x1": 1, "groupnorm": 2, "attention": 3, "ddpm_step": 4, "other": 5,
           "conv3x3_winograd_main": 6, "conv3x3_winograd_bf16x3": 7}
 

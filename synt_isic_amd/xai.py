@@ -16,6 +16,17 @@
                                      v(S) = F(Dec(x_T; S)) (transitions applied only on the steps in S, the other
                                      steps are skipped) and the unbiased permutation estimator.  The reference
                                      documents this form but does not implement it.
+
+Stage 2 of ``run_comprehensive_xai_pipeline`` (XAI.py:2822-2896), counterfactual interventions and their causal shift:
+
+* ``select_regions``               -- XAI.py:1340-1451: top-k / bottom-k regions of an attribution map with the morphological
+                                     clean-up (host, numpy; no scipy).
+* ``counterfactual_intervention``  -- XAI.py:1454-1597 for one image, on ``sisic_intervene``.
+* ``compute_causal_shift``         -- XAI.py:1600-1700: ONE classifier batch of (original, modified) + ``sisic_cfi_metrics``
+                                     instead of 18 batch-1 forwards.
+* ``compute_combined_attribution`` -- XAI.py:1236-1291: the weighted sum of the passes above.
+* ``intervention_stage``           -- XAI.py:2829-2875: every (key frame, region, intervention type) in ONE ``sisic_intervene``
+                                     launch, ONE classifier batch and ONE ``sisic_cfi_metrics`` launch.
 """
 from __future__ import annotations
 
@@ -27,7 +38,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .classifier import HipMelanomaClassifier
+from .classifier import CLASS_NAMES, HipMelanomaClassifier
 from .sampler import Sampler, draw_noise, run_sampling_loop
 
 SHAP_N_SAMPLES = 512          # xai/XAI.py SHAP_N_SAMPLES
@@ -211,3 +222,315 @@ def time_shap_permutation(sampler: Sampler, classifier: HipMelanomaClassifier, c
     phi /= n_permutations
     return {"phi": phi, "v_full": np.float64(v_full), "v_empty": np.float64(v_empty),
             "timesteps": np.array([int(t) for t in sched.timesteps])}
+
+
+# ---- stage 2: regions, counterfactual interventions, causal shift (XAI.py:1340-1700, :2822-2896) ---------------------------
+TOP_K_PERCENT = 10            # xai/XAI.py:238
+INTERVENTION_TYPES = ("blur",)  # xai/XAI.py:265
+NOISE_STD = 0.5               # xai/XAI.py:266
+BLUR_KERNEL_SIZE = 5          # xai/XAI.py:267
+
+
+def _structure_offsets(connectivity: int) -> List[Tuple[int, int]]:
+    """3x3 structuring element: the cross for connectivity 4, the full square otherwise (XAI.py:1390-1393)."""
+    return [(dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if connectivity != 4 or dy == 0 or dx == 0]
+
+
+def _binary_dilate(mask: np.ndarray, offsets) -> np.ndarray:
+    H, W = mask.shape
+    padded = np.zeros((H + 2, W + 2), dtype=bool)
+    padded[1:-1, 1:-1] = mask
+    out = np.zeros((H, W), dtype=bool)
+    for dy, dx in offsets:
+        out |= padded[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+    return out
+
+
+def _binary_erode(mask: np.ndarray, offsets) -> np.ndarray:
+    """the outside counts as 0, as for the dilation: border pixels go"""
+    H, W = mask.shape
+    padded = np.zeros((H + 2, W + 2), dtype=bool)
+    padded[1:-1, 1:-1] = mask
+    out = np.ones((H, W), dtype=bool)
+    for dy, dx in offsets:
+        out &= padded[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+    return out
+
+
+def _drop_small_components(mask: np.ndarray, offsets, min_size: int) -> np.ndarray:
+    """keep the connected components (neighbourhood = ``offsets``) of at least ``min_size`` pixels: a flood fill per component"""
+    H, W = mask.shape
+    Wp = W + 2
+    cells = bytearray(np.pad(mask, 1).astype(np.uint8).tobytes())        # 1 = unvisited mask pixel; the zero frame stops the fill
+    steps = [dy * Wp + dx for dy, dx in offsets if (dy, dx) != (0, 0)]
+    kept: List[int] = []
+    for start in np.flatnonzero(np.pad(mask, 1)).tolist():
+        if cells[start] != 1:
+            continue
+        cells[start] = 2
+        component = [start]
+        k = 0
+        while k < len(component):
+            here = component[k]
+            k += 1
+            for st in steps:
+                nb = here + st
+                if cells[nb] == 1:
+                    cells[nb] = 2
+                    component.append(nb)
+        if len(component) >= min_size:
+            kept.extend(component)
+    out = np.zeros((H + 2) * Wp, dtype=bool)
+    out[kept] = True
+    return out.reshape(H + 2, Wp)[1:-1, 1:-1].copy()
+
+
+def select_regions(attribution_map, k_percent: float = TOP_K_PERCENT, region_type: str = "top",
+                   morphology_cleanup: bool = True, connectivity: int = 8) -> Dict:
+    """``select_regions_advanced`` (XAI.py:1340-1451): the {mask, threshold, statistics, metadata} dict of the top-k or
+    bottom-k percent of an attribution map (L2 norm over channels for [C,H,W] / [1,C,H,W] input, |.| for [H,W]).  The
+    clean-up is binary closing x2, opening x1 with the 3x3 structure of ``connectivity``, then components smaller than
+    max(10, 1% of the map) are dropped -- in numpy, pixel for pixel what scipy.ndimage gives (tests/test_xai_regions.py)."""
+    attr = attribution_map.detach().cpu().numpy() if torch.is_tensor(attribution_map) else np.array(attribution_map)
+    original_shape = attr.shape
+    if attr.ndim == 4:
+        attr = attr[0]
+    attr = np.linalg.norm(attr, axis=0) if attr.ndim == 3 else np.abs(attr)
+    if region_type == "top":
+        threshold = np.percentile(attr.flatten(), 100 - k_percent)
+        mask = attr >= threshold
+    elif region_type == "bottom":
+        threshold = np.percentile(attr.flatten(), k_percent)
+        mask = attr <= threshold
+    else:
+        raise ValueError(f"unknown region_type '{region_type}' ('top' or 'bottom')")
+    if morphology_cleanup:
+        offs = _structure_offsets(connectivity)
+        for op in (_binary_dilate, _binary_dilate, _binary_erode, _binary_erode,      # closing, 2 iterations
+                   _binary_erode, _binary_dilate):                                      # opening, 1 iteration
+            mask = op(mask, offs)
+        mask = _drop_small_components(mask, offs, max(10, int(0.01 * mask.size)))
+    selected = np.sum(mask)
+    inside = attr[mask]
+    has = selected > 0
+    return {
+        "mask": mask,
+        "threshold": threshold,
+        "statistics": {
+            "total_pixels": attr.size,
+            "selected_pixels": selected,
+            "target_percentage": k_percent,
+            "actual_percentage": (selected / attr.size) * 100,
+            "threshold_value": threshold,
+            "mean_attribution": np.mean(attr),
+            "std_attribution": np.std(attr),
+            "mean_attribution_selected": np.mean(inside) if has else 0,
+            "std_attribution_selected": np.std(inside) if has else 0,
+            "max_attribution_selected": np.max(inside) if has else 0,
+            "min_attribution_selected": np.min(inside) if has else 0,
+        },
+        "metadata": {"region_type": region_type, "morphology_cleanup": morphology_cleanup, "connectivity": connectivity,
+                     "original_shape": original_shape},
+    }
+
+
+def _mask_2d(mask, H: int, W: int) -> torch.Tensor:
+    """a region mask (numpy or tensor, any leading 1-dimensions) as a CPU bool [H,W]"""
+    m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask.detach().cpu()
+    if m.numel() != H * W or tuple(m.shape[-2:]) != (H, W):
+        raise ValueError(f"mask of shape {tuple(m.shape)} does not cover a {H}x{W} image")
+    return m.reshape(H, W) != 0
+
+
+def _shuffle_index(mask: torch.Tensor, channels: int, generator: torch.Generator) -> torch.Tensor:
+    """int32 [C,H*W] source pixels of the 'shuffle' intervention (XAI.py:1540-1566): one ``torch.randperm`` per channel over the
+    masked pixels (none when fewer than 2 are masked), the identity elsewhere."""
+    flat = mask.reshape(-1)
+    inside = torch.nonzero(flat).reshape(-1)
+    src = torch.arange(flat.numel(), dtype=torch.int64).repeat(channels, 1)
+    if inside.numel() > 1:
+        for c in range(channels):
+            src[c, inside] = inside[torch.randperm(inside.numel(), generator=generator)]
+    return src.to(torch.int32)
+
+
+def _intervention_entry(image, modified, intervention, mask, stats_row, intervention_type: str, parameters: Dict) -> Dict:
+    """the dict ``counterfactual_intervention_advanced`` returns (XAI.py:1582-1595)"""
+    return {
+        "modified_image": modified,
+        "intervention": intervention,
+        "mask_tensor": mask.to(image.device, torch.float32).reshape(1, 1, *mask.shape),
+        "difference": torch.abs(image - modified),
+        "statistics": {"intervention_type": intervention_type, "mask_coverage": float(stats_row[0]),
+                       "mean_difference": float(stats_row[1]), "max_difference": float(stats_row[2]),
+                       "intervention_strength": float(stats_row[3])},
+        "parameters": parameters,
+    }
+
+
+@torch.no_grad()
+def counterfactual_intervention(image: torch.Tensor, mask, intervention_type: str = "noise", **kwargs) -> Dict:
+    """``counterfactual_intervention_advanced`` (XAI.py:1454-1597) for one image [1,C,H,W] on the GPU:
+    modified = clamp(image * (1 - M) + intervention * M, -1, 1).  kwargs: ``noise_std`` (0.5), ``blur_kernel`` (5) and
+    ``seed`` (0) -- the noise types draw the device-noise blocks of that seed (tag 2), 'shuffle' one ``torch.randperm`` per
+    channel from a CPU generator seeded with it.  An unknown type is an error (the reference falls back to noise)."""
+    if image.dim() == 3:
+        image = image.unsqueeze(0)
+    if image.dim() != 4 or image.shape[0] != 1:
+        raise ValueError(f"counterfactual_intervention takes one image [1,C,H,W], got {tuple(image.shape)}")
+    if intervention_type not in ops.INTERVENTION_TYPES:
+        raise ValueError(f"unknown intervention type '{intervention_type}' (one of {', '.join(ops.INTERVENTION_TYPES)})")
+    image = image.to(torch.float32).contiguous()
+    _, Cc, H, W = image.shape
+    m = _mask_2d(mask, H, W)
+    seed = int(kwargs.get("seed", 0))
+    src = None
+    if intervention_type == "shuffle":
+        src = _shuffle_index(m, Cc, torch.Generator().manual_seed(seed)).unsqueeze(0).contiguous().to(image.device)
+    job = (0, 0, intervention_type, int(kwargs.get("blur_kernel", BLUR_KERNEL_SIZE)), float(kwargs.get("noise_std", NOISE_STD)))
+    out, iv, stats = ops.intervene(image, m.to(torch.uint8).unsqueeze(0).contiguous().to(image.device), [job], [seed],
+                                   src_index=src, with_intervention=True)
+    return _intervention_entry(image, out, iv, m, stats[0].cpu(), intervention_type, kwargs)
+
+
+def _causal_shift_entry(row: np.ndarray, n: int, target_class: int, include_all_classes: bool) -> Dict:
+    """one row of ``sisic_cfi_metrics`` as the dict of XAI.py:1641-1698"""
+    names = CLASS_NAMES if n == len(CLASS_NAMES) else tuple(str(c) for c in range(n))
+    per = row[:ops.CFI_PER_CLASS * n].reshape(n, ops.CFI_PER_CLASS)
+    tail = row[ops.CFI_PER_CLASS * n:]
+    t = per[target_class]
+    po, pm = int(tail[0]), int(tail[1])
+    res = {
+        "target_class_analysis": {
+            "class_id": target_class, "class_name": names[target_class], "cfi": float(t[2]), "delta": float(t[3]),
+            "original_score": float(t[0]), "modified_score": float(t[1]), "original_probability": float(t[4]),
+            "modified_probability": float(t[5]), "probability_shift": float(t[4] - t[5]),
+        },
+        "prediction_analysis": {
+            "original_prediction": po, "original_prediction_name": names[po], "modified_prediction": pm,
+            "modified_prediction_name": names[pm], "prediction_changed": bool(po != pm),
+            "original_confidence": float(tail[2]), "modified_confidence": float(tail[3]),
+            "confidence_drop": float(tail[2] - tail[3]),
+        },
+    }
+    if include_all_classes:
+        res["all_classes_analysis"] = [
+            {"class_id": c, "class_name": names[c], "cfi": float(per[c, 2]), "delta": float(per[c, 3]),
+             "original_probability": float(per[c, 4]), "modified_probability": float(per[c, 5]),
+             "probability_shift": float(per[c, 4] - per[c, 5])} for c in range(n)]
+    res["distribution_analysis"] = {"kl_divergence": float(tail[4]), "js_divergence": float(tail[5]),
+                                    "total_variation": float(tail[6])}
+    return res
+
+
+@torch.no_grad()
+def compute_causal_shift(classifier: HipMelanomaClassifier, original_image: torch.Tensor, modified_image: torch.Tensor,
+                         target_class: int, include_all_classes: bool = True) -> Dict:
+    """``compute_causal_shift_comprehensive`` (XAI.py:1600-1700) for one (original, modified) pair [1,3,H,W]: CFI, delta, the
+    probabilities and predictions, KL / JS / total variation -- one classifier batch of two images and ``sisic_cfi_metrics``."""
+    dev = classifier.device
+    pair = torch.cat([original_image.to(dev, torch.float32), modified_image.to(dev, torch.float32)], dim=0)
+    if pair.shape[0] != 2:
+        raise ValueError("compute_causal_shift takes one original and one modified image [1,3,H,W]")
+    logits = classifier.forward(pair)
+    row = ops.cfi_metrics(logits[:1], logits[1:], [0])[0].cpu().numpy()
+    return _causal_shift_entry(row, logits.shape[1], int(target_class), include_all_classes)
+
+
+@torch.no_grad()
+def compute_combined_attribution(classifier: HipMelanomaClassifier, image: torch.Tensor, target_class: int,
+                                 methods: Sequence[str] = ("ig", "shap"), weights: Optional[Sequence[float]] = None,
+                                 ig_kwargs: Optional[Dict] = None, shap_kwargs: Optional[Dict] = None):
+    """XAI.py:1236-1291: (sum_m weight_m * attribution_m, method_details) over 'ig', 'shap' and 'gradient'; equal weights by
+    default.  A method name the reference does not know is skipped as there; none left is an error."""
+    methods = list(methods)
+    if weights is None:
+        weights = [1.0 / len(methods)] * len(methods)
+    image = image.to(classifier.device, torch.float32)
+    total = None
+    details = {}
+    for method, weight in zip(methods, weights):
+        if method == "ig":
+            attr = compute_integrated_gradients(classifier, image, target_class, **(ig_kwargs or {}))
+        elif method == "shap":
+            attr = compute_shap_approximation(classifier, image, target_class, **(shap_kwargs or {}))
+        elif method == "gradient":
+            attr = compute_gradient_attribution(classifier, image, target_class)
+        else:
+            continue
+        total = attr * weight if total is None else total + attr * weight
+        details[method] = {"weight": weight, "mean_attribution": float(attr.abs().mean()),
+                           "max_attribution": float(attr.abs().max())}
+    if total is None:
+        raise RuntimeError(f"no attribution computed: none of {methods} is one of 'ig', 'shap', 'gradient'")
+    return total, details
+
+
+def key_steps(n_frames: int) -> List[int]:
+    """The frames stage 2 intervenes on (XAI.py:2829): first, middle and the last four, as indices 0 .. n-1 (a negative index
+    of a short trajectory counts from the end, as it does there) without repeats, in that order."""
+    if n_frames <= 0:
+        return []
+    n = n_frames
+    out: List[int] = []
+    for i in (0, n // 2, n - 4, n - 3, n - 2, n - 1):
+        i %= n
+        if i not in out:
+            out.append(i)
+    return out
+
+
+@torch.no_grad()
+def intervention_stage(classifier: HipMelanomaClassifier, trajectory, timesteps: Sequence[float], region_data: Dict,
+                       target_class: int, intervention_types: Sequence[str] = INTERVENTION_TYPES, seed: int = 0,
+                       noise_std: float = NOISE_STD, blur_kernel: int = BLUR_KERNEL_SIZE):
+    """Stage 2 of ``run_comprehensive_xai_pipeline`` (XAI.py:2829-2875).  ``region_data["t_<timestep>"]["top_k" | "bottom_k"]
+    ["mask"]`` are the regions of stage 1 (``select_regions``); key frames without an entry are skipped.  Returns
+    ``(interventions, cfi)`` as the reference stores them: ``interventions[step_key][region][type]`` = the dict of
+    ``counterfactual_intervention``, ``cfi[step_key]["<region>_<type>"]`` = the dict of ``compute_causal_shift``.
+    Jobs are ordered key frame -> region -> type; job j draws with seed ``seed + j``.  One ``sisic_intervene`` launch, one
+    ``classifier.forward`` over the key frames followed by every modified image, one ``sisic_cfi_metrics`` launch."""
+    frames = _as_batch(trajectory)
+    if frames.shape[0] != len(timesteps):
+        raise ValueError(f"{frames.shape[0]} frames but {len(timesteps)} timesteps")
+    types = list(intervention_types)
+    for t in types:
+        if t not in ops.INTERVENTION_TYPES:
+            raise ValueError(f"unknown intervention type '{t}' (one of {', '.join(ops.INTERVENTION_TYPES)})")
+    dev = classifier.device
+    _, Cc, H, W = frames.shape
+    regions = ("top_k", "bottom_k")
+    used = [(i, f"t_{float(timesteps[i]):.0f}") for i in key_steps(frames.shape[0])]
+    used = [(i, key) for i, key in used if key in region_data]
+    if not used or not types:
+        return {}, {}
+    originals = frames[[i for i, _ in used]].to(dev, torch.float32).contiguous()
+    masks = [_mask_2d(region_data[key][r]["mask"], H, W) for _, key in used for r in regions]
+    jobs, labels = [], []
+    for f, (_, key) in enumerate(used):
+        for r in range(len(regions)):
+            for t in types:
+                jobs.append((f, 2 * f + r, t, blur_kernel, noise_std))
+                labels.append((key, regions[r], t))
+    J = len(jobs)
+    seeds = [int(seed) + j for j in range(J)]
+    src = None
+    if "shuffle" in types:
+        identity = torch.arange(H * W, dtype=torch.int32).repeat(Cc, 1)
+        src = torch.stack([_shuffle_index(masks[m], Cc, torch.Generator().manual_seed(seeds[j])) if t == "shuffle" else identity
+                           for j, (_, m, t, _, _) in enumerate(jobs)]).contiguous().to(dev)
+    masks_dev = torch.stack(masks).to(torch.uint8).contiguous().to(dev)
+    modified, iv, stats = ops.intervene(originals, masks_dev, jobs, seeds, src_index=src, with_intervention=True)
+    logits = classifier.forward(torch.cat([originals, modified], dim=0))
+    F_ = originals.shape[0]
+    rows = ops.cfi_metrics(logits[:F_], logits[F_:], [f for f, *_ in jobs]).cpu().numpy()
+    stats = stats.cpu()
+    interventions: Dict = {}
+    cfi: Dict = {}
+    for j, (key, region, t) in enumerate(labels):
+        f, m = jobs[j][0], jobs[j][1]
+        params = {"noise_std": noise_std, "blur_kernel": blur_kernel, "seed": seeds[j]}
+        entry = _intervention_entry(originals[f:f + 1], modified[j:j + 1], iv[j:j + 1], masks[m], stats[j], t, params)
+        interventions.setdefault(key, {}).setdefault(region, {})[t] = entry
+        cfi.setdefault(key, {})[f"{region}_{t}"] = _causal_shift_entry(rows[j], logits.shape[1], int(target_class), True)
+    return interventions, cfi
