@@ -91,7 +91,11 @@ typedef struct sisic_conv_args {
     const float* w_winograd; /* dev, layout of sisic_conv_winograd_pack, or NULL: when given, 3x3 stride-1
                                 convolutions may run as Winograd F(2x2,3x3) (tile_cfg 60..74 force a form; 74 = the
                                 fp32-equivalent bf16x3 form, the automatic choice for whole 64-channel x 16x16-pixel
-                                tiles; 1x1: tile_cfg 28 = the bf16x3 pointwise kernel, 20 = the f32 one)             */
+                                tiles; 1x1: tile_cfg 28 = the bf16x3 pointwise kernel, 20 = the f32 one).
+                                For ksize 3, stride 2 the field carries the layout of sisic_conv_s2_pack instead, or NULL:
+                                when given, the convolution may run with fp32-equivalent products on the bf16 matrix pipe
+                                (tile_cfg 36 forces it; needs no upsample, no GroupNorm prologue, c1 == 0, c0 % 8 == 0 and
+                                Cout % 64 == 0 -- everything else runs the f32 kernel as with NULL)                  */
     float* stats_out;        /* dev [B,Cout,slots,4] or NULL: each workgroup also writes (count, sum, sum of squared
                                 deviations from its own mean, 0) of the values it stored, per image and channel, so that the GroupNorm
                                 that follows needs sisic_groupnorm_finalize only (no second pass over `out`).
@@ -124,6 +128,12 @@ int sisic_conv_stats_slots(const sisic_conv_args* args);
  * more than the f32 layout alone.                                                             */
 int64_t sisic_conv_winograd_numel(int Cout, int Cin);
 int sisic_conv_winograd_pack(sisic_ctx*, const float* w_oihw, int Cout, int Cin, float* u_packed, void* stream);
+
+/* The split filter of the stride-2 3x3 kernel: an OIHW 3x3 weight as three bf16 terms per element in the operand order of
+ * the bf16x3 kernel, [8-channel chunk][tap][64-channel tile][768 dwords], zero padded: number of floats (-1: bad shape), and
+ * dev OIHW -> dev buffer of that many floats.  Passed as sisic_conv_args.w_winograd of a ksize 3, stride 2 convolution.  */
+int64_t sisic_conv_s2_numel(int Cout, int Cin);
+int sisic_conv_s2_pack(sisic_ctx*, const float* w_oihw, int Cout, int Cin, float* out, void* stream);
 
 /* number of floats of the packed form of an OIHW weight [Cout,Cin,k,k] (-1: unsupported ksize).  For ksize 1 this is 3.5 x
  * the [Cin_pad][1][Cout_pad] layout: the direct kernel's, the pointwise kernel's and the bf16x3 split are all written. */

@@ -73,6 +73,8 @@ SIGNATURES = {
     "sisic_conv_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sisic_conv_winograd_numel": (C.c_int64, [C.c_int, C.c_int]),
     "sisic_conv_winograd_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sisic_conv_s2_numel": (C.c_int64, [C.c_int, C.c_int]),
+    "sisic_conv_s2_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sisic_conv2d": (C.c_int, [C.c_void_p, C.POINTER(ConvArgs), C.c_void_p]),
     "sisic_conv_stats_slots": (C.c_int, [C.POINTER(ConvArgs)]),
     "sisic_conv_finalizes": (C.c_int, [C.POINTER(ConvArgs)]),

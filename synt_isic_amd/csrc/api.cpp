@@ -117,6 +117,16 @@ int sisic_conv_pack_weights(sisic_ctx* ctx, const float* w, int Cout, int Cin, i
     return launch_conv_pack(ctx, w, Cout, Cin, ksize, packed, static_cast<hipStream_t>(stream));
 }
 
+int64_t sisic_conv_s2_numel(int Cout, int Cin) {
+    if (Cout <= 0 || Cin <= 0) return -1;
+    return conv_s2_packed_floats(Cout, Cin);
+}
+
+int sisic_conv_s2_pack(sisic_ctx* ctx, const float* w, int Cout, int Cin, float* out, void* stream) {
+    SISIC_REQUIRE(ctx && w && out && Cout > 0 && Cin > 0, "conv_s2_pack: bad arguments");
+    return launch_conv_s2_pack(ctx, w, Cout, Cin, out, static_cast<hipStream_t>(stream));
+}
+
 int64_t sisic_conv_winograd_numel(int Cout, int Cin) {
     if (Cout <= 0 || Cin <= 0) return -1;
     return winograd_packed_numel(Cout, Cin);

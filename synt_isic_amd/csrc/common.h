@@ -153,6 +153,13 @@ int launch_conv_pointwise(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
 // conv_pointwise_bf3.hip: the same GEMM with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 28)
 bool conv_pointwise_bf3_applicable(const sisic_conv_args& a);
 int launch_conv_pointwise_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
+// conv_s2_bf3.hip: 3x3 stride-2 convolutions with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 36); the split
+// filter (conv_s2_pack_bf3_elem, pack_device.h) travels in sisic_conv_args.w_winograd
+bool conv_s2_bf3_applicable(const sisic_conv_args& a);
+int conv_s2_bf3_stats_slots(const sisic_conv_args& a);
+int launch_conv_s2_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
+int64_t conv_s2_packed_floats(int Cout, int Cin);
+int launch_conv_s2_pack(sisic_ctx*, const float* w, int Cout, int Cin, float* out, hipStream_t s);
 // mean_rstd (optional, training): [B, groups, 2] = (mean, rstd) of every (sample, group)
 int launch_gn_finalize(sisic_ctx*, const float* st0, int c0, int slots0, const float* st1, int c1, int slots1, int B,
                        int HW, int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,

@@ -482,6 +482,7 @@ int launch_conv_pack(sisic_ctx*, const float* w, int Cout, int Cin, int k, float
 //           14: 1,1,2,4,TW16  15: 1,1,2,4,TW8 (8 waves, PIX128)   50: vector-ALU kernel for Cout <= 4
 //           16 / 17: cfg 4's 64x64 tile with two K-split wave groups (8 waves), 16- / 8-channel chunks
 //   3x3 s2: 11: 2,1,1,4,TW32  12: 2,1,1,4,TW16  13: 1,1,2,2,TW8   18 / 19: cfg 13's tile with two K-split wave groups, 16- / 8-channel chunks
+//           36: the bf16x3 kernel of conv_s2_bf3.hip
 //   1x1   : 21: 2,2,1,4,TW256 22: 1,1,2,2,TW64  23: 2,1,1,4,TW128
 //   1x1 s2: 31: 2,1,1,4,TW32  32: 2,1,1,4,TW16  33: 1,1,2,2,TW8      7x7 s2: 41: 2,1,1,4,TW32 (CIC 4)
 static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query);
@@ -688,6 +689,13 @@ static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t
             case 15: return launch_cfg<3, 1, 1, 1, 2, 4, 8, 8, 4>(ctx, p, s);
         }
     } else {
+        // tile_cfg 36: fp32-equivalent products on the bf16 matrix pipe (conv_s2_bf3.hip) where a split filter was supplied -- unless SISIC_S2_BF16X3=0.  (Conditions on the arguments' shape only: an
+        // image's bits must not depend on the batch it is in.)
+        static const bool s2b_on = [] { const char* e = std::getenv("SISIC_S2_BF16X3"); return !e || std::atoi(e) != 0; }();
+        if ((cfg == 0 && s2b_on && conv_s2_bf3_applicable(a)) || cfg == 36) {
+            if (slots_query) { *slots_query = conv_s2_bf3_applicable(a) ? conv_s2_bf3_stats_slots(a) : 0; return SISIC_OK; }
+            return launch_conv_s2_bf3(ctx, a, s);
+        }
         if (cfg == 0) cfg = p.Wout >= 24 ? 11 : (p.Wout >= 12 ? 12 : 18);   // measured (tools/conv_bench.py, B=64; 16->8: 66 -> 57 us)
         switch (cfg) {
             case 11: return launch_cfg<3, 2, 2, 1, 1, 4, 32, 8>(ctx, p, s);

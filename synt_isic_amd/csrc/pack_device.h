@@ -133,6 +133,36 @@ __device__ __forceinline__ void winograd_pack_bf3_elem(size_t i, const float* __
     out[i] = pk;
 }
 
+// OIHW 3x3 -> the A operands of the stride-2 bf16x3 kernel (conv_s2_bf3.hip): [chunk of 8 ci][tap 0..8][64-channel tile]
+// [768 dwords], the 768 dwords laid out as the third region of conv_pack_elem above: (hi, mid) of channel block 0 [64 lanes][4],
+// of block 1, then lo of block 0 [64 lanes][2] and of block 1; zero padded.  i over (Cin_pad8 / 8) * 9 * (cout_pad / 64) * 768
+__device__ __forceinline__ void conv_s2_pack_bf3_elem(size_t i, const float* __restrict__ w, int Cout, int Cin, int cout_pad,
+                                                      unsigned* __restrict__ out) {
+    const int n_co64 = cout_pad >> 6;
+    const int wd = (int)(i % 768);
+    size_t r = i / 768;
+    const int tile = (int)(r % n_co64); r /= n_co64;
+    const int tap = (int)(r % 9);
+    const int chunk = (int)(r / 9);
+    int blk, ln, term, pair;
+    if (wd < 512) { blk = wd >> 8; ln = (wd >> 2) & 63; term = (wd >> 1) & 1; pair = wd & 1; }      // 0 hi, 1 mid
+    else { blk = (wd - 512) >> 7; ln = (wd >> 1) & 63; term = 2; pair = wd & 1; }                   // 2 lo
+    const int co = 64 * tile + 32 * blk + (ln & 31), g = ln >> 5;
+    unsigned pk = 0;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int ci = 8 * chunk + 4 * g + 2 * pair + e;
+        const float v = (co < Cout && ci < Cin) ? w[((size_t)co * Cin + ci) * 9 + tap] : 0.0f;
+        const unsigned hi = __float_as_uint(v) & 0xffff0000u;
+        const float r1 = v - __uint_as_float(hi);
+        const unsigned mid = __float_as_uint(r1) & 0xffff0000u;
+        const float r2 = r1 - __uint_as_float(mid);
+        const unsigned t = term == 0 ? hi : (term == 1 ? mid : __float_as_uint(r2));
+        pk |= (t >> 16) << (16 * e);
+    }
+    out[i] = pk;
+}
+
 // W'[ci][co][KK-1-t] = W[co][ci][t]: the filter of the backward-data convolution; i over Cout * Cin * KK
 __device__ __forceinline__ void transpose_flip_elem(size_t i, const float* __restrict__ w, int Cout, int Cin, int KK,
                                                     float* __restrict__ wt) {

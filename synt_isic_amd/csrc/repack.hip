@@ -39,6 +39,7 @@ __global__ void __launch_bounds__(PB_THREADS) pack_batch_kernel(const PackJob* _
             case PackJob::WINO_FIRST: winograd_pack_elem(i, j.src, j.a, j.b, j.d, j.e, j.dst); break;
             case PackJob::WINO_WIDE: winograd_pack_wide_elem(i, j.src, j.a, j.b, j.dst); break;
             case PackJob::WINO_BF3: winograd_pack_bf3_elem(i, j.src, j.a, j.b, reinterpret_cast<unsigned*>(j.dst)); break;
+            case PackJob::CONV_S2_BF3: conv_s2_pack_bf3_elem(i, j.src, j.a, j.b, j.e, reinterpret_cast<unsigned*>(j.dst)); break;
         }
     }
 }
@@ -82,6 +83,10 @@ PackJob pack_job_wino_bf3(int Cout, int Cin, float* packed) {           // reads
     const size_t wide = (size_t)round_up(Cin, 16) * 16 * round_up(Cout, 128);
     j.dst = packed + winograd_first_floats(Cout, Cin) + wide;
     j.a = conv_cout_pad(Cout); j.b = round_up(Cout, 128); j.total = wide + wide / 2; return j;
+}
+PackJob pack_job_conv_s2(const float* w, int Cout, int Cin, float* out) {          // launch_conv_s2_pack (conv_s2_bf3.hip)
+    PackJob j{}; j.kind = PackJob::CONV_S2_BF3; j.src = w; j.dst = out; j.a = Cout; j.b = Cin; j.e = conv_cout_pad(Cout);
+    j.total = (size_t)conv_s2_packed_floats(Cout, Cin); return j;
 }
 
 }  // namespace sisic

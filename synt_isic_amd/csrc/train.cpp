@@ -65,6 +65,7 @@ int build_repack_plan(sisic_unet* u) {
             ph[1].push_back(pack_job_wino_wide(c->cout, c->cin, c->wino));
             ph[1].push_back(pack_job_wino_bf3(c->cout, c->cin, c->wino));
         }
+        if (c->s2) ph[0].push_back(pack_job_conv_s2(w, c->cout, c->cin, c->s2));
         if (c == &u->conv_in) continue;                       // the network input needs no gradient
         SISIC_REQUIRE(c->raw_t && c->packed_t, "repack plan: backward filters are not prepared");
         ph[0].push_back(pack_job_flip(w, c->cout, c->cin, c->k * c->k, c->raw_t));

@@ -140,6 +140,10 @@ int prepare_conv(sisic_unet* u, ConvW& c, hipStream_t s) {
         SISIC_TRY(dev_alloc(u, (size_t)winograd_packed_numel(c.cout, c.cin), &c.wino));
         SISIC_TRY(launch_winograd_pack(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, c.wino, s));
     }
+    if (c.k == 3 && c.strided) {
+        SISIC_TRY(dev_alloc(u, (size_t)conv_s2_packed_floats(c.cout, c.cin), &c.s2));
+        SISIC_TRY(launch_conv_s2_pack(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, c.s2, s));
+    }
     return SISIC_OK;
 }
 void prepare_norm(sisic_unet* u, NormW& n) {
@@ -205,7 +209,7 @@ int prepare_all(sisic_unet* u, hipStream_t s) {
 }
 
 // forget every derived buffer (they were freed): the next prepare_all allocates afresh
-void reset_conv(ConvW& c) { c.packed = c.wino = c.raw_t = c.packed_t = c.wino_t = nullptr; }
+void reset_conv(ConvW& c) { c.packed = c.wino = c.s2 = c.raw_t = c.packed_t = c.wino_t = nullptr; }
 void reset_attn(AttnW& a) {
     a.qkv_cat = a.qkv_packed = a.qkv_bias = a.qkv_raw_t = a.qkv_packed_t = nullptr;
     reset_conv(a.out);
@@ -389,7 +393,8 @@ struct Fwd {
         a.in0 = in0; a.c0 = c0; a.in1 = in1; a.c1 = c1;
         a.B = B; a.Hin = H; a.Win = W; a.upsample = ups; a.ksize = c.k; a.stride = stride;
         a.w_packed = c.packed; a.bias = c.bias; a.Cout = c.cout;
-        a.w_winograd = (stride == 1 && u->use_winograd) ? c.wino : nullptr;
+        // (stride 2: the field carries the split filter of the bf16x3 downsampler kernel, sisic.h)
+        a.w_winograd = stride == 1 ? (u->use_winograd ? c.wino : nullptr) : (stride == 2 ? c.s2 : nullptr);
         if (gn_prologue) { a.gn_scale = gsc; a.gn_shift = gsh; a.gn_silu = silu ? 1 : 0; }
         a.chan_bias = chan_bias; a.chan_bias_stride = tproj_stride;
         a.residual = residual; a.out = out;

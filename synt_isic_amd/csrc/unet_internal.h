@@ -17,6 +17,7 @@ struct ConvW {            // one convolution's parameters
     float* packed = nullptr;      // device, packed layout
     float* wino = nullptr;        // device, Winograd-domain filters (3x3 stride-1 convolutions only)
     bool strided = false;         // stride-2 downsampler: no Winograd form
+    float* s2 = nullptr;          // device, the split filter of the stride-2 bf16x3 kernel (downsamplers only; conv_s2_bf3.hip)
     const float* bias = nullptr;  // device
     // training only (train.cpp): filters of the backward-data convolution, W'[ci][co][k*k-1-t] = W[co][ci][t]
     float* raw_t = nullptr;       // OIHW of the transposed, tap-flipped filter

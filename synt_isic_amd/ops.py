@@ -70,6 +70,17 @@ def pack_winograd_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def pack_conv_s2_weight(w: torch.Tensor) -> torch.Tensor:
+    """OIHW 3x3 -> the split (bf16x3) filter of the stride-2 kernel (sisic_conv_s2_pack); passed to conv2d as ``w_winograd``."""
+    lib = _lib.load()
+    cout, cin, k, k2 = w.shape
+    if k != 3 or k2 != 3:
+        raise ValueError("the stride-2 bf16x3 kernel needs a 3x3 weight")
+    out = torch.empty(lib.sisic_conv_s2_numel(cout, cin), dtype=torch.float32, device=w.device)
+    check(lib.sisic_conv_s2_pack(context(w.device), _ptr(w, "weight"), cout, cin, out.data_ptr(), _stream(w.device)))
+    return out
+
+
 def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: int, *, bias=None, x2=None, stride=1,
            upsample=False, gn_scale=None, gn_shift=None, gn_silu=False, chan_bias=None, residual=None,
            relu=False, tile_cfg=0, w_winograd=None, with_stats=False, out=None, finalize=None):

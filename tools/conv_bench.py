@@ -71,7 +71,7 @@ def cfgs_for(k, stride, which):
     if k == 1:
         return [0, 22, 23, 24, 25, 26, 27]
     if stride == 2:
-        return [0, 11, 12, 13]
+        return [0, 11, 12, 13, 18, 36]      # 36: the bf16x3 kernel (conv_s2_bf3.hip)
     return [4, 16, 17, 66, 0]
 
 
@@ -98,6 +98,7 @@ def main():
         w = torch.randn(cout, c0 + c1, k, k, device=dev) * 0.05
         wp = ops.pack_conv_weight(w)
         wino = ops.pack_winograd_weight(w) if (k == 3 and stride == 1 and cout > 4) else None
+        s2 = ops.pack_conv_s2_weight(w) if (k == 3 and stride == 2) else None
         bias = torch.randn(cout, device=dev)
         Hc = 2 * H if ups else H
         Ho = (Hc + 2 * (k // 2) - k) // stride + 1
@@ -111,7 +112,8 @@ def main():
             def run():
                 return ops.conv2d(x, wp, cout, k, bias=bias, x2=x2, stride=stride, upsample=bool(ups),
                                   gn_scale=gs, gn_shift=gb, gn_silu=(gn == 1), residual=r, tile_cfg=cfg,
-                                  w_winograd=wino if (cfg == 0 or 60 <= cfg <= 79 or cfg in (90, 91, 92)) else None)
+                                  w_winograd=(s2 if cfg in (0, 36) else None) if stride == 2 else
+                                  (wino if (cfg == 0 or 60 <= cfg <= 79 or cfg in (90, 91, 92)) else None))
             try:
                 run()
             except Exception as e:  # cfg not applicable
