@@ -71,6 +71,12 @@ struct sisic_ctx {
     struct SplitK { float* p = nullptr; size_t floats = 0; };
     std::map<hipStream_t, SplitK> splitk;
     std::mutex splitk_mutex;
+    // item tables of the bf16x3 Winograd kernel (conv_winograd_bf3.inc): one per launch geometry, filled on the device the
+    // first time the geometry is met, never moved or freed before the context (captured graphs hold their addresses)
+    // (fill_done: recorded behind the fill; until it has passed, only launches on the filling stream use the table)
+    struct Bf3Items { int key[9]; unsigned* tab = nullptr; hipStream_t fill_stream = nullptr; hipEvent_t fill_done = nullptr; };
+    std::vector<Bf3Items> bf3_items;
+    std::mutex bf3_items_mutex;
     std::atomic<uint64_t> scratch_generation{0};    // bumped whenever a scratch buffer is re-allocated: captured graphs that
                                                     // may hold its old address are rebuilt
 };

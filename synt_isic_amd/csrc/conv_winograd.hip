@@ -84,6 +84,10 @@ struct WinoParams {
     float* fin_mean_rstd;
     int fin_groups;
     float fin_eps;
+    // conv_winograd_bf3.inc: workgroups launched (a persistent workgroup's stride from item to item) and the geometry's item
+    // table, one 64-byte Bf3Item per work item (nullptr: the kernel derives everything from the item's index itself)
+    int grid;
+    const unsigned* items;
 };
 
 constexpr int W_CIC = 8;            // input channels per chunk

@@ -97,7 +97,90 @@ typedef unsigned bf3_u4 __attribute__((ext_vector_type(4)));
 typedef float bf3_f2 __attribute__((ext_vector_type(2)));
 typedef unsigned bf3_u2 __attribute__((ext_vector_type(2)));
 
-template <int PRO, bool UPS = false>      // UPS: nearest-2x input (an instance of its own: the other one keeps its branch-free loop)
+// ---- the item table.  What a workgroup derives from a work item's index L -- the remapped (channel tile, tile position,
+// image), the images' element offsets in every tensor, the tile's flags -- is a function of the launch GEOMETRY alone (B, plane,
+// channels, grid), not of data or pointers: the same in all 16 waves, in every launch of the layer and in every step of a run.
+// It is computed once per geometry by bf3_item_table_kernel into one 64-byte record per item (offsets only, never pointers:
+// one table serves every launch of the geometry), and a wave fetches a record with ONE scalar load where it needs it -- the
+// 64 bytes stay in the scalar cache, so nothing of them is held (spilled) across the channel loop.
+struct Bf3Item {
+    unsigned b0, co0, oy0, ox0;
+    unsigned slot;              // gy * groups_x + gx
+    unsigned in0_off, in1_off;  // elements: the item's image in in0 / in1
+    unsigned out_off;           // ... in out / residual
+    unsigned gn_off;            // b0 * Cin: gn_scale / gn_shift
+    unsigned cb_off;            // b0 * chan_bias_stride
+    unsigned stats_off;         // float4s: (b0 * Cout + co0) * slots + slot
+    unsigned fin_off;           // b0 * Cout + co0: fin_scale / fin_shift
+    unsigned flags;
+    unsigned tile_cnt, inv_cnt; // float bits: pixels of the tile inside the plane, and 1 / that
+    unsigned tile_off;          // bytes: pixel (oy0, ox0) in a plane of the output
+};
+static_assert(sizeof(Bf3Item) == 64, "one s_load_dwordx16 per record");
+enum : unsigned {
+    BF3_IT_WHOLE = 1,      // the 16 x 16 tile lies wholly inside the plane
+    BF3_IT_EVEN_W = 2,     // even plane width
+    BF3_IT_NEW_TILE = 4,   // another tile position than the same workgroup's item before (or its first item)
+    BF3_IT_LAST = 8,       // the workgroup's last item
+};
+typedef unsigned bf3_u16 __attribute__((ext_vector_type(16)));
+// (constant address space: a scalar load wherever it stands -- behind the stores of the item before the compiler makes loads
+//  through a global pointer vector loads; the index is made opaque so that a second fetch of a record is a second load and not
+//  sixteen registers kept from the first)
+__device__ __forceinline__ bf3_u16 bf3_item_fetch(const unsigned* tab, int L) {
+    asm volatile("" : "+s"(L));
+    return *(reinterpret_cast<const __attribute__((address_space(4))) bf3_u16*>((size_t)tab) + L);
+}
+#define BF3_IT(rec, field) ((rec)[offsetof(Bf3Item, field) / 4])
+
+// XCD-aware bijective remap of item l (conv_mfma.hip) and its (channel tile, tile column, tile row, image)
+__device__ __forceinline__ void bf3_decode(const WinoParams& p, int l, int& co_t, int& gx, int& gy, int& b0) {
+    const int nwg = p.nwg;
+    const int xcd = l & 7, slot = l >> 3, q = nwg >> 3, r = nwg & 7;
+    const int work = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    co_t = work % p.n_co_tiles;
+    int grp = work / p.n_co_tiles;
+    gx = grp % p.groups_x;
+    grp /= p.groups_x;
+    gy = grp % p.groups_y;
+    b0 = grp / p.groups_y;
+}
+
+__global__ void bf3_item_table_kernel(const WinoParams p, unsigned* __restrict__ tab) {
+    const int L = blockIdx.x * blockDim.x + threadIdx.x;
+    if (L >= p.nwg) return;
+    int co_t, gx, gy, b0;
+    bf3_decode(p, L, co_t, gx, gy, b0);
+    const int oy0 = gy * 16, ox0 = gx * 16, co0 = co_t * 64;
+    const unsigned HWin = (unsigned)(p.Hin * p.Win), HWo = (unsigned)(p.Hc * p.Wc), slots = (unsigned)(p.groups_x * p.groups_y);
+    Bf3Item it;
+    it.b0 = (unsigned)b0; it.co0 = (unsigned)co0; it.oy0 = (unsigned)oy0; it.ox0 = (unsigned)ox0;
+    it.slot = (unsigned)(gy * p.groups_x + gx);
+    it.in0_off = (unsigned)b0 * (unsigned)p.c0 * HWin;          // (launch_bf3: every product below 2^32)
+    it.in1_off = (unsigned)b0 * (unsigned)p.c1 * HWin;
+    it.out_off = (unsigned)b0 * (unsigned)p.Cout * HWo;
+    it.gn_off = (unsigned)b0 * (unsigned)(p.c0 + p.c1);
+    it.cb_off = (unsigned)b0 * (unsigned)p.chan_bias_stride;
+    it.stats_off = ((unsigned)b0 * (unsigned)p.Cout + (unsigned)co0) * slots + it.slot;
+    it.fin_off = (unsigned)b0 * (unsigned)p.Cout + (unsigned)co0;
+    bool new_tile = true;
+    if (L >= p.grid) {
+        int co_p, gx_p, gy_p, b_p;
+        bf3_decode(p, L - p.grid, co_p, gx_p, gy_p, b_p);
+        new_tile = gx != gx_p || gy != gy_p;
+    }
+    it.flags = ((oy0 + 16 <= p.Hc && ox0 + 16 <= p.Wc) ? BF3_IT_WHOLE : 0u) | ((p.Wc & 1) == 0 ? BF3_IT_EVEN_W : 0u) |
+               (new_tile ? BF3_IT_NEW_TILE : 0u) | (L + p.grid >= p.nwg ? BF3_IT_LAST : 0u);
+    const float tile_cnt = (float)(min(16, p.Hc - oy0) * min(16, p.Wc - ox0));
+    it.tile_cnt = __float_as_uint(tile_cnt);
+    it.inv_cnt = __float_as_uint(1.0f / tile_cnt);
+    it.tile_off = 4u * (unsigned)(oy0 * p.Wc + ox0);
+    reinterpret_cast<Bf3Item*>(tab)[L] = it;
+}
+
+// TAB: the per-item values come from the item table (p.items); without it (no table for this geometry, SISIC_BF3_ITEM_TABLE=0)
+// the instance derives them from the item's index itself -- the same values, the same bits
+template <int PRO, bool UPS = false, bool TAB = false>      // UPS: nearest-2x input (an instance of its own: the other one keeps its branch-free loop)
 __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoParams p) {
     using G = Bf3Geom<PRO>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -124,13 +207,16 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         oy0 = gy * 2 * G::TY; ox0 = gx * 2 * G::TX;
         co0 = co_t * G::CO_T;
     };
-    decode(L);
+    if constexpr (!TAB) decode(L);
     const int n = p.nchunks;
     // With a whole number of images between a workgroup's successive items (the remap is then regular: nwg a multiple of 8, and
     // gridDim.x / 8 consecutive work indices apart) the next item is the same channel tile and position `img_step` images on: no
     // decode (a hundred scalar instructions of division), no new plan.
-    const int per_img = p.n_co_tiles * p.groups_x * p.groups_y;
-    const int img_step = ((p.nwg & 7) == 0 && (int)(gridDim.x >> 3) % per_img == 0) ? (int)(gridDim.x >> 3) / per_img : 0;
+    int img_step = 0;
+    if constexpr (!TAB) {
+        const int per_img = p.n_co_tiles * p.groups_x * p.groups_y;
+        img_step = ((p.nwg & 7) == 0 && (int)(gridDim.x >> 3) % per_img == 0) ? (int)(gridDim.x >> 3) / per_img : 0;
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -194,7 +280,20 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in0 + (size_t)b0 * p.c0 * HWin), 0, -1, 0x00020000);
         rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in1 ? p.in1 + (size_t)b0 * p.c1 * HWin : p.in0), 0, -1, 0x00020000);
     };
-    set_sources();
+    auto set_sources_item = [&](const bf3_u16& it) {      // the same two, the image's offsets from its record
+        rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in0 + (size_t)BF3_IT(it, in0_off)), 0, -1, 0x00020000);
+        rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in1 ? p.in1 + (size_t)BF3_IT(it, in1_off) : p.in0), 0, -1, 0x00020000);
+    };
+    int gn_base = 0;                                      // the item's image in gn_scale / gn_shift
+    if constexpr (TAB) {
+        const bf3_u16 it = bf3_item_fetch(p.items, L);
+        b0 = (int)BF3_IT(it, b0); co0 = (int)BF3_IT(it, co0); co_t = co0 >> 6; oy0 = (int)BF3_IT(it, oy0); ox0 = (int)BF3_IT(it, ox0);
+        gx = gy = 0;
+        set_sources_item(it);
+        gn_base = (int)BF3_IT(it, gn_off);
+    } else {
+        set_sources();
+    }
     plan(std::false_type{});
 
     // ---- the wave's position (i, j) of V = B^T d B: rows (a, b) and columns (c, e) of the 4 x 4 patch with signs,
@@ -384,7 +483,7 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
     float gn_pre0 = 0.0f, gn_pre1 = 0.0f;
     auto prefetch_gn = [&] {
         if constexpr (PRO != 0) {
-            const int ci = b0 * Cin + min(wave_u * 64 + fresh_lane(), Cin - 1);
+            const int ci = (TAB ? gn_base : b0 * Cin) + min(wave_u * 64 + fresh_lane(), Cin - 1);
             gn_pre0 = p.gn_scale[ci];
             gn_pre1 = p.gn_shift[ci];
         }
@@ -428,8 +527,14 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         hoff[0] = (int)(h.x & 0xffffu); hoff[1] = (int)(h.x >> 16); hoff[2] = (int)h.y;
     }
     lane_addresses();
-    const float tile_cnt = (float)(min(2 * G::TY, p.Hc - oy0) * min(2 * G::TX, p.Wc - ox0));
-    const float inv_cnt = 1.0f / tile_cnt;
+    float tile_cnt = 0.0f, inv_cnt = 0.0f;       // (from the item's record behind the channel loop)
+    if constexpr (!TAB) {
+        tile_cnt = (float)(min(2 * G::TY, p.Hc - oy0) * min(2 * G::TX, p.Wc - ox0));
+        inv_cnt = 1.0f / tile_cnt;
+    }
+    // the next item's record is asked for here, a channel loop ahead of its use: a line of the scalar cache, not registers
+    unsigned it_warm = 0;
+    if constexpr (TAB) it_warm = bf3_item_fetch(p.items, min(L + p.grid, p.nwg - 1))[0];
 
     // (the zeroed padding slots are never staged to: no barrier between the zeroing and the first staging)
     if constexpr (PRO != 0) {
@@ -442,7 +547,7 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         }
         for (int c = c0t + G::THREADS; c < n * W_CIC; c += G::THREADS) {
             const bool cv = c < Cin;
-            const int ci = b0 * Cin + min(c, Cin - 1);
+            const int ci = (TAB ? gn_base : b0 * Cin) + min(c, Cin - 1);
             const float gsc = p.gn_scale[ci], gsh = p.gn_shift[ci];
             *reinterpret_cast<bf3_f2*>(GN_lds + 2 * c) = bf3_f2{cv ? gsc : 0.0f, cv ? gsh : 0.0f};
         }
@@ -455,6 +560,7 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
     stage_halo(0, 0, hs[0]);
     if (n > 2) load_halo(2, hs[0]);
     __syncthreads();
+    if constexpr (TAB) asm volatile("" :: "s"(it_warm));
     BF3_STAMP(1);                                // prologue done
     {
         // chunk c is in halo buffer c & 1 and its A operands in ua.  The staging of chunk c + 1 (GroupNorm, SiLU: latency-bound
@@ -533,84 +639,185 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
     // (ONE vector load -- lanes 0..3 the bias of the four rounds, lanes 4..7 the embedding -- requested here, after the channel loop (kept across it, it
     //  was a spill), and waited for where it is first used, in the rounds: behind the stores of the item before, the compiler may not turn these into scalar loads any more, and as eight
     //  uniform loads each would be a global load + s_waitcnt vmcnt(0) of its own, 4 us per item)
-    float eadd_v = 0.0f;
-    {
-        const int ln = fresh_lane();
-        const int coc = min(co0 + (ln & 3) * G::RCO + cor, p.Cout - 1);
-        const float* src = ln < 4 ? (p.bias ? p.bias + coc : nullptr)
-                                  : (ln < 8 && p.chan_bias ? p.chan_bias + (size_t)b0 * p.chan_bias_stride + coc : nullptr);
-        if (src) eadd_v = *src;                      // (one load site: a second assignment behind a pending load would be a wait)
-    }
-    // ---- output transform: four rounds of 16 channels through LDS, [position][channel][tile]; in a round one wave = one
-    // channel x 64 tiles.  Everything global goes through buffer resources: the channel is a scalar offset, the lane's pixel a
-    // 32-bit one computed once, and a lane whose pixel is outside the image carries an offset past the image (the range check
-    // drops its store) -- no address arithmetic and no exec masks in the rounds.
     const int HWo = p.Hc * p.Wc;
     const int et = fresh_lane(), e_half = et >> 5, e_l31 = et & 31;
     const int ety = et >> 3, etx = et & 7;
-    const int eoy = oy0 + 2 * ety, eox = ox0 + 2 * etx;
-    const bool even_w = (p.Wc & 1) == 0;            // uniform: both columns of a tile are inside together, rows are 8-byte aligned
     const bool has_res = p.residual != nullptr;
+    bool even_w;                                    // uniform: both columns of a tile are inside together, rows are 8-byte aligned
     unsigned ld_off[2][2], st_off[2][2];
     bool pin[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            pin[i][j] = eoy + i < p.Hc && eox + j < p.Wc;
-            // (a lane outside the image re-reads a pixel inside it; with an even width -- the 8-byte residual loads -- the
-            //  clamped column is EVEN, Wc - 2, so that the pair it reads ends with the row: ADVICE r03.  The range check of
-            //  `rsr` below stays as a second line of defence; it relies on gfx9's raw-buffer rule that the scalar offset
-            //  takes part in the check.)
-            ld_off[i][j] = 4u * (unsigned)(min(eoy + i, p.Hc - 1) * p.Wc + min(eox + j, p.Wc - (even_w ? 2 - j : 1)));
-            st_off[i][j] = pin[i][j] ? ld_off[i][j] : 0x80000000u;      // + the channel offset: still past the image (launch_bf3 checks its size)
-        }
-    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)b0 * p.Cout * HWo, 0, 4 * p.Cout * HWo, 0x00020000);
-    // (range-checked like the output: the 8-byte residual load of a lane clamped to the last column of the last row reads one float
-    //  past its image -- past the tensor for the last image; out of range reads return 0 instead)
-    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_res ? p.residual + (size_t)b0 * p.Cout * HWo : p.out), 0, 4 * p.Cout * HWo, 0x00020000);
-
+    __amdgpu_buffer_rsrc_t rso;
     bf3_f2 eres[G::ROUNDS][2];
+    float eadd[G::ROUNDS];
+    int co0_c, b0_c, slot_c, L_next;
+    bool more;
+    unsigned stats_base = 0, fin_base = 0;          // (item table: the item's first slot in stats, its first channel in fin_*)
+    if constexpr (TAB) {
+        // ---- the item's record again, and the next item's with it (both lines are in the scalar cache: the item's top asked for them)
+        const bf3_u16 it = bf3_item_fetch(p.items, L);
+        const bf3_u16 nx = bf3_item_fetch(p.items, min(L + p.grid, p.nwg - 1));
+        const unsigned flags = BF3_IT(it, flags);
+        co0_c = (int)BF3_IT(it, co0); b0_c = (int)BF3_IT(it, b0); slot_c = (int)BF3_IT(it, slot);
+        stats_base = BF3_IT(it, stats_off); fin_base = BF3_IT(it, fin_off);
+        tile_cnt = __uint_as_float(BF3_IT(it, tile_cnt)); inv_cnt = __uint_as_float(BF3_IT(it, inv_cnt));
+        even_w = (flags & BF3_IT_EVEN_W) != 0;
+        // bias and embedding of the wave's channel in the four rounds: EIGHT scalar loads (constant address space), waited for
+        // with the rounds' first LDS traffic -- no vector load whose wait would also be a wait for the residual requests below
+        unsigned coc4[G::ROUNDS];
+        unsigned ebias[G::ROUNDS], eemb[G::ROUNDS];       // (float bits)
 #pragma unroll
-    for (int q = 0; q < G::ROUNDS; ++q) {
-        const int coc = min(co0 + q * G::RCO + cor, p.Cout - 1);
-        const unsigned soff = 4u * (unsigned)(coc * HWo);
+        for (int q = 0; q < G::ROUNDS; ++q) {
+            coc4[q] = (unsigned)min(co0_c + q * G::RCO + cor, p.Cout - 1);
+            ebias[q] = 0u; eemb[q] = 0u;
+        }
+        typedef const __attribute__((address_space(4))) unsigned* cbits_ptr;
+        if (p.bias) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) eres[q][i] = bf3_f2{0.0f, 0.0f};
+            for (int q = 0; q < G::ROUNDS; ++q) ebias[q] = reinterpret_cast<cbits_ptr>((size_t)p.bias)[coc4[q]];
+        }
+        if (p.chan_bias) {
+            cbits_ptr cb = reinterpret_cast<cbits_ptr>((size_t)p.chan_bias) + BF3_IT(it, cb_off);
+#pragma unroll
+            for (int q = 0; q < G::ROUNDS; ++q) eemb[q] = cb[coc4[q]];
+        }
+        // ---- the lanes' pixel offsets.  A tile wholly inside a plane of even width (every item of every UNet layer): affine in
+        // the lane, nothing to clamp, every pixel stored; otherwise the clamped offsets and the range-check sentinels
+        if ((flags & (BF3_IT_WHOLE | BF3_IT_EVEN_W)) == (BF3_IT_WHOLE | BF3_IT_EVEN_W)) {
+            const unsigned o = BF3_IT(it, tile_off) + (unsigned)ety * (8u * (unsigned)p.Wc) + 8u * (unsigned)etx;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    pin[i][j] = true;
+                    ld_off[i][j] = st_off[i][j] = o + (unsigned)i * (4u * (unsigned)p.Wc) + 4u * (unsigned)j;
+                }
+        } else {
+            const int eoy = (int)BF3_IT(it, oy0) + 2 * ety, eox = (int)BF3_IT(it, ox0) + 2 * etx;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    pin[i][j] = eoy + i < p.Hc && eox + j < p.Wc;
+                    ld_off[i][j] = 4u * (unsigned)(min(eoy + i, p.Hc - 1) * p.Wc + min(eox + j, p.Wc - (even_w ? 2 - j : 1)));
+                    st_off[i][j] = pin[i][j] ? ld_off[i][j] : 0x80000000u;
+                }
+        }
+        rso = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)BF3_IT(it, out_off), 0, 4 * p.Cout * HWo, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(has_res ? p.residual + (size_t)BF3_IT(it, out_off) : p.out), 0, 4 * p.Cout * HWo, 0x00020000);
+        // ---- the four rounds' residual requests behind ONE decision
+#pragma unroll
+        for (int q = 0; q < G::ROUNDS; ++q)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) eres[q][i] = bf3_f2{0.0f, 0.0f};
         if (has_res) {
             if (even_w) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
-                    eres[q][i] = __builtin_bit_cast(bf3_f2, __builtin_amdgcn_raw_buffer_load_b64(rsr, ld_off[i][0], soff, 0));
+                for (int q = 0; q < G::ROUNDS; ++q)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        eres[q][i] = __builtin_bit_cast(bf3_f2, __builtin_amdgcn_raw_buffer_load_b64(rsr, ld_off[i][0], 4u * (coc4[q] * (unsigned)HWo), 0));
             } else {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    eres[q][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][0], soff, 0));
-                    eres[q][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][1], soff, 0));
+                for (int q = 0; q < G::ROUNDS; ++q)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        eres[q][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][0], 4u * (coc4[q] * (unsigned)HWo), 0));
+                        eres[q][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][1], 4u * (coc4[q] * (unsigned)HWo), 0));
+                    }
+            }
+        }
+        // ---- the next item: its first two chunks' halo requested now, staged after the rounds
+        L_next = L + p.grid;
+        more = (flags & BF3_IT_LAST) == 0;
+        if (more) {
+            b0 = (int)BF3_IT(nx, b0); co0 = (int)BF3_IT(nx, co0); co_t = co0 >> 6; oy0 = (int)BF3_IT(nx, oy0); ox0 = (int)BF3_IT(nx, ox0);
+            gn_base = (int)BF3_IT(nx, gn_off);
+            set_sources_item(nx);
+            new_tile = (BF3_IT(nx, flags) & BF3_IT_NEW_TILE) != 0;
+            if (new_tile) plan(std::false_type{});
+            load_halo(0, hs[0]);
+            if (n > 1) load_halo(1, hs[1]);
+            prefetch_gn();
+        }
+        // (the eight are first used HERE, behind the requests: pinned, or their sums -- and a wait per load -- move up to the loads)
+#pragma unroll
+        for (int q = 0; q < G::ROUNDS; ++q) {
+            asm volatile("" : "+s"(ebias[q]), "+s"(eemb[q]));
+            eadd[q] = (0.0f + __uint_as_float(ebias[q])) + __uint_as_float(eemb[q]);
+        }
+    } else {
+        float eadd_v = 0.0f;
+        {
+            const int ln = fresh_lane();
+            const int coc = min(co0 + (ln & 3) * G::RCO + cor, p.Cout - 1);
+            const float* src = ln < 4 ? (p.bias ? p.bias + coc : nullptr)
+                                      : (ln < 8 && p.chan_bias ? p.chan_bias + (size_t)b0 * p.chan_bias_stride + coc : nullptr);
+            if (src) eadd_v = *src;                      // (one load site: a second assignment behind a pending load would be a wait)
+        }
+        // ---- output transform: four rounds of 16 channels through LDS, [position][channel][tile]; in a round one wave = one
+        // channel x 64 tiles.  Everything global goes through buffer resources: the channel is a scalar offset, the lane's pixel a
+        // 32-bit one computed once, and a lane whose pixel is outside the image carries an offset past the image (the range check
+        // drops its store) -- no address arithmetic and no exec masks in the rounds.
+        const int eoy = oy0 + 2 * ety, eox = ox0 + 2 * etx;
+        even_w = (p.Wc & 1) == 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                pin[i][j] = eoy + i < p.Hc && eox + j < p.Wc;
+                // (a lane outside the image re-reads a pixel inside it; with an even width -- the 8-byte residual loads -- the
+                //  clamped column is EVEN, Wc - 2, so that the pair it reads ends with the row: ADVICE r03.  The range check of
+                //  `rsr` below stays as a second line of defence; it relies on gfx9's raw-buffer rule that the scalar offset
+                //  takes part in the check.)
+                ld_off[i][j] = 4u * (unsigned)(min(eoy + i, p.Hc - 1) * p.Wc + min(eox + j, p.Wc - (even_w ? 2 - j : 1)));
+                st_off[i][j] = pin[i][j] ? ld_off[i][j] : 0x80000000u;      // + the channel offset: still past the image (launch_bf3 checks its size)
+            }
+        rso = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)b0 * p.Cout * HWo, 0, 4 * p.Cout * HWo, 0x00020000);
+        // (range-checked like the output: the 8-byte residual load of a lane clamped to the last column of the last row reads one float
+        //  past its image -- past the tensor for the last image; out of range reads return 0 instead)
+        const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(has_res ? p.residual + (size_t)b0 * p.Cout * HWo : p.out), 0, 4 * p.Cout * HWo, 0x00020000);
+
+#pragma unroll
+        for (int q = 0; q < G::ROUNDS; ++q) {
+            const int coc = min(co0 + q * G::RCO + cor, p.Cout - 1);
+            const unsigned soff = 4u * (unsigned)(coc * HWo);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) eres[q][i] = bf3_f2{0.0f, 0.0f};
+            if (has_res) {
+                if (even_w) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        eres[q][i] = __builtin_bit_cast(bf3_f2, __builtin_amdgcn_raw_buffer_load_b64(rsr, ld_off[i][0], soff, 0));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        eres[q][i].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][0], soff, 0));
+                        eres[q][i].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, ld_off[i][1], soff, 0));
+                    }
                 }
             }
         }
-    }
-    float eadd[G::ROUNDS];
 #pragma unroll
-    for (int q = 0; q < G::ROUNDS; ++q)
-        eadd[q] = (0.0f + __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(eadd_v), q))) +
-                  __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(eadd_v), 4 + q));
-    // ---- the next item: its first two chunks' halo requested now, staged after the rounds
-    const int co0_c = co0, b0_c = b0, slot_c = gy * p.groups_x + gx;
-    const int L_next = L + (int)gridDim.x;
-    const bool more = L_next < p.nwg;
-    if (more) {
-        const int gx_c = gx, gy_c = gy;
-        if (img_step) b0 += img_step;
-        else decode(L_next);
-        set_sources();
-        new_tile = gx != gx_c || gy != gy_c;
-        if (new_tile) plan(std::false_type{});
-        load_halo(0, hs[0]);
-        if (n > 1) load_halo(1, hs[1]);
-        prefetch_gn();
+        for (int q = 0; q < G::ROUNDS; ++q)
+            eadd[q] = (0.0f + __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(eadd_v), q))) +
+                      __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(eadd_v), 4 + q));
+        // ---- the next item: its first two chunks' halo requested now, staged after the rounds
+        co0_c = co0; b0_c = b0; slot_c = gy * p.groups_x + gx;
+        L_next = L + (int)gridDim.x;
+        more = L_next < p.nwg;
+        if (more) {
+            const int gx_c = gx, gy_c = gy;
+            if (img_step) b0 += img_step;
+            else decode(L_next);
+            set_sources();
+            new_tile = gx != gx_c || gy != gy_c;
+            if (new_tile) plan(std::false_type{});
+            load_halo(0, hs[0]);
+            if (n > 1) load_halo(1, hs[1]);
+            prefetch_gn();
+        }
     }
 #pragma unroll
     for (int q = 0; q < G::ROUNDS; ++q) {
@@ -670,7 +877,8 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         if (!WINO_TIMING && (p.stats || (!UPS && p.fin_gamma))) {
             // one channel per wave (its 64 lanes = the 64 tiles): (count, sum, M2) of what this workgroup stored of the channel,
             // sums shifted by the first tile's first value
-            const float K = __shfl(vv[0][0], 0);
+            // (lane 0's value: with the item table as a scalar -- the shuffle's lane address was one more register kept across the channel loop)
+            const float K = TAB ? __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(vv[0][0]), 0)) : __shfl(vv[0][0], 0);
             float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -684,7 +892,8 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
                 const float p_sum = fmaf(tile_cnt, K, s1), p_m2 = fmaxf(s2 - s1 * s1 * inv_cnt, 0.0f);
                 if (p.stats) {
                     const int slots = p.groups_x * p.groups_y;
-                    float4* dst = reinterpret_cast<float4*>(p.stats) + ((size_t)b0_c * p.Cout + co) * slots + slot_c;
+                    float4* dst = TAB ? reinterpret_cast<float4*>(p.stats) + ((size_t)stats_base + (size_t)((q * G::RCO + cor) * slots))
+                                      : reinterpret_cast<float4*>(p.stats) + ((size_t)b0_c * p.Cout + co) * slots + slot_c;
                     *dst = make_float4(tile_cnt, p_sum, p_m2, 0.0f);
                 }
                 if (!UPS && p.fin_gamma) *reinterpret_cast<bf3_f2*>(smem + G::FIN_OFF + 2 * (q * G::RCO + cor)) = bf3_f2{p_sum, p_m2};
@@ -702,7 +911,9 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
         // of gn_finalize_kernel (its lanes 0 .. 7 through the 64-lane butterfly; gn_merge.h) and writes the channel's (scale, shift):
         // the bits sisic_groupnorm_finalize would give, without its launch.
         __syncthreads();
-        const int c = tid;
+        // (with the item table from the hardware's lane index, as everywhere in the per-item code: the thread index was a register
+        //  pair kept across the channel loop for this one use, and the table instances have none to spare)
+        const int c = TAB ? wave_u * 64 + fresh_lane() : tid;
         if (c < G::CO_T) {
             const bf3_f2* ps = reinterpret_cast<const bf3_f2*>(smem + G::FIN_OFF) + 8 * (c >> 3);
             double pn[8], s1v[8], m2v[8];
@@ -720,8 +931,9 @@ __global__ void __launch_bounds__(1024, 4) conv_winograd_bf3_kernel(const WinoPa
             const int co = co0_c + c;
             float sc, sh;
             gn_affine(p.fin_gamma[co], p.fin_beta[co], meanf, rstd, sc, sh);
-            p.fin_scale[(size_t)b0_c * p.Cout + co] = sc;
-            p.fin_shift[(size_t)b0_c * p.Cout + co] = sh;
+            const size_t fi = TAB ? (size_t)fin_base + (size_t)c : (size_t)b0_c * p.Cout + co;
+            p.fin_scale[fi] = sc;
+            p.fin_shift[fi] = sh;
             if (p.fin_mean_rstd && (c & 7) == 0) {
                 p.fin_mean_rstd[2 * ((size_t)b0_c * p.fin_groups + (co >> 3))] = meanf;
                 p.fin_mean_rstd[2 * ((size_t)b0_c * p.fin_groups + (co >> 3)) + 1] = rstd;
@@ -1078,6 +1290,56 @@ __global__ void winograd_pack_bf3_kernel(const float* __restrict__ u_first, int 
         winograd_pack_bf3_elem(i, u_first, cout_pad, cout_pad128, out);
 }
 
+// The geometry's item table (p.items): from the context's cache, or filled now by a kernel on the launch stream -- ordered in
+// front of the convolution, legal under stream capture, no host staging.  p.items stays null -- the kernel then derives the
+// items itself -- when SISIC_BF3_ITEM_TABLE=0, when an offset of the geometry does not fit 32 bits, when the cache is full
+// (tables are never evicted: captured graphs hold their addresses) or when a new geometry is first met during a capture.
+static int bf3_item_table(sisic_ctx* ctx, WinoParams& p, hipStream_t s) {
+    constexpr size_t MAX_TABLES = 48, MAX_BYTES = size_t(8) << 20;
+    const char* e = std::getenv("SISIC_BF3_ITEM_TABLE");      // (read per launch: tests and A/B runs switch it inside one process)
+    if (e && std::atoi(e) == 0) return SISIC_OK;
+    const double HWin = (double)p.Hin * p.Win, HWo = (double)p.Hc * p.Wc, lim = 4294967296.0;
+    const double slots = (double)p.groups_x * p.groups_y;
+    if ((double)p.B * std::max(p.c0, p.c1) * HWin >= lim || (double)p.B * p.Cout * HWo >= lim || (double)p.B * (p.c0 + p.c1) >= lim ||
+        (double)p.B * std::max(p.chan_bias_stride, 0) >= lim || (double)p.B * round_up(p.Cout, 64) * slots >= lim || p.chan_bias_stride < 0 ||
+        (size_t)p.nwg * sizeof(Bf3Item) > MAX_BYTES)
+        return SISIC_OK;
+    const int key[9] = {p.B, p.Hin, p.Win, p.ups, p.c0, p.c1, p.Cout, p.grid, p.chan_bias_stride};
+    std::lock_guard<std::mutex> lock(ctx->bf3_items_mutex);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    SISIC_HIP(hipStreamIsCapturing(s, &cap));
+    for (auto& it : ctx->bf3_items) {
+        if (!std::equal(key, key + 9, it.key)) continue;
+        // another stream's launches are not ordered behind the fill until its event has passed
+        if (it.fill_done && cap == hipStreamCaptureStatusNone && hipEventQuery(it.fill_done) == hipSuccess) {
+            (void)hipEventDestroy(it.fill_done);
+            it.fill_done = nullptr;
+        }
+        if (!it.fill_done || it.fill_stream == s) p.items = it.tab;
+        return SISIC_OK;
+    }
+    if (ctx->bf3_items.size() >= MAX_TABLES || cap != hipStreamCaptureStatusNone) return SISIC_OK;
+    sisic_ctx::Bf3Items ent;
+    std::copy(key, key + 9, ent.key);
+    SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&ent.tab), (size_t)p.nwg * sizeof(Bf3Item)));
+    hipLaunchKernelGGL(bf3_item_table_kernel, dim3(cdiv(p.nwg, 256)), dim3(256), 0, s, p, ent.tab);
+    if (hipGetLastError() != hipSuccess) {
+        (void)hipFree(ent.tab);
+        set_error("conv2d(winograd bf16x3): item table kernel failed to launch");
+        return SISIC_EHIP;
+    }
+    ent.fill_stream = s;
+    if (hipEventCreateWithFlags(&ent.fill_done, hipEventDisableTiming) != hipSuccess || hipEventRecord(ent.fill_done, s) != hipSuccess) {
+        // (no event: the table is used once the stream has drained)
+        if (ent.fill_done) (void)hipEventDestroy(ent.fill_done);
+        ent.fill_done = nullptr;
+        SISIC_HIP(hipStreamSynchronize(s));
+    }
+    ctx->bf3_items.push_back(ent);
+    p.items = ent.tab;
+    return SISIC_OK;
+}
+
 template <int PRO, bool UPS>
 static int launch_bf3(sisic_ctx* ctx, WinoParams& p, hipStream_t s) {
     using G = Bf3Geom<PRO>;
@@ -1093,15 +1355,25 @@ static int launch_bf3(sisic_ctx* ctx, WinoParams& p, hipStream_t s) {
     SISIC_REQUIRE((double)p.Cout * p.Hc * p.Wc * 4.0 < 2147483648.0, "conv2d(winograd bf16x3): one image of the output is too large for 31-bit offsets");
     SISIC_REQUIRE(p.nchunks * W_CIC <= G::GN_MAX_CH, "conv2d(winograd bf16x3): more than %d input channels", G::GN_MAX_CH);
     p.nwg = (int)nwg;
-    auto kern = conv_winograd_bf3_kernel<PRO, UPS>;
-    static std::atomic<uint64_t> lds_opt_in{0};
-    SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, lds_opt_in));
     // persistent workgroups (one per CU: its LDS lets no second one in) when there are more items than CUs, unless
     // SISIC_BF3_PERSISTENT=0; the grid a multiple of 8 so that an item's XCD is its workgroup's
     static const bool persistent = [] { const char* e = std::getenv("SISIC_BF3_PERSISTENT"); return !e || std::atoi(e) != 0; }();
     const int cus = ctx->num_cus > 0 ? ctx->num_cus & ~7 : 256;
     const int grid = (persistent && p.nwg > cus && cus >= 8) ? cus : p.nwg;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, p);
+    p.grid = grid;
+    p.items = nullptr;
+    SISIC_TRY(bf3_item_table(ctx, p, s));
+    if (p.items) {
+        auto kern = conv_winograd_bf3_kernel<PRO, UPS, true>;
+        static std::atomic<uint64_t> lds_opt_in{0};
+        SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, lds_opt_in));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, p);
+    } else {
+        auto kern = conv_winograd_bf3_kernel<PRO, UPS, false>;
+        static std::atomic<uint64_t> lds_opt_in{0};
+        SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, lds_opt_in));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, p);
+    }
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

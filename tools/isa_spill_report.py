@@ -8,6 +8,8 @@ name matches: VGPRs / scratch bytes from the metadata comments, every basic bloc
 them ``in Loop: Header=BBx_y Depth=d`` and the header ``Loop Header``) with its MFMA / LDS / global / scratch instruction
 counts, and the list of scratch accesses with the block they sit in.  VERDICT r02 item 6 asked for exactly this: a
 scratch reload in front of an MFMA waits on vmcnt, so spills inside the channel loop would cost; outside they do not.
+Also per kernel: the SGPR spill count of the code object metadata with the v_readlane / v_writelane counts, and -- for kernels
+whose channel loop is followed by output rounds of one barrier each -- the static size of the per-item code.
 """
 import re
 import sys
@@ -25,6 +27,21 @@ def kernels(path):
             body.append(line.rstrip("\n"))
     if name:
         yield name, body
+
+
+SGPR_SPILLS = {}
+
+
+def read_spill_counts(path):
+    """.sgpr_spill_count of every kernel, from the code object metadata at the end of the file"""
+    name = None
+    for line in open(path):
+        m = re.match(r"^\s+\.name:\s+(_Z\w+)", line)
+        if m:
+            name = m.group(1)
+        m = re.match(r"^\s+\.sgpr_spill_count:\s+(\d+)", line)
+        if m and name:
+            SGPR_SPILLS[name] = int(m.group(1))
 
 
 def report(name, body):
@@ -85,12 +102,30 @@ def report(name, body):
                 n_out += hdr is None
                 out.append(f"    {i.split(';')[0].strip():<48} in block {label:<10} {where}")
     out.append(f"  scratch accesses: {n_in} inside loops, {n_out} outside")
+    sgpr_spill = SGPR_SPILLS.get(name)
+    flat = [i for _, _, _, ins in blocks for i in ins]
+    out.append(f"  sgpr spills: {sgpr_spill}; v_readlane {sum(i.startswith('v_readlane') for i in flat)}, "
+               f"v_writelane {sum(i.startswith('v_writelane') for i in flat)}")
+    # Per-item code of a kernel whose channel loop is followed by output rounds with one barrier each (the bf16x3 Winograd
+    # kernels): static instructions, in layout order, from the barrier behind the last MFMA to the next barrier (round 0's),
+    # and from there to the fifth barrier behind the last MFMA (the one behind round 3).
+    mf = [k for k, i in enumerate(flat) if i.startswith("v_mfma")]
+    if mf:
+        bars = [k for k, i in enumerate(flat) if i.startswith("s_barrier") and k > mf[-1]]
+        if len(bars) >= 5:
+            def mix(lo, hi):
+                seg = flat[lo + 1:hi]
+                return (f"{len(seg)} ({sum(i.startswith('v_') for i in seg)} vector, {sum(i.startswith('s_') for i in seg)} scalar, "
+                        f"{sum(i.startswith('ds_') for i in seg)} lds, {sum(i.startswith('buffer_') or i.startswith('global_') for i in seg)} memory)")
+            out.append(f"  per-item code: loop's last barrier -> round 0's barrier {mix(bars[0], bars[1])}")
+            out.append(f"                 round 0's barrier -> barrier behind round 3 {mix(bars[1], bars[4])}")
     return "\n".join(out)
 
 
 def main():
     path = sys.argv[1]
     pat = re.compile(sys.argv[2]) if len(sys.argv) > 2 else None
+    read_spill_counts(path)
     for name, body in kernels(path):
         if pat and not pat.search(name):
             continue
