@@ -443,6 +443,44 @@ int sisic_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* masks
 int sisic_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n_classes,
                       const int* job_frame, float* rows, void* stream);
 
+/* ---- training loader: the reference's augmentation chain on a device-resident dataset (diffusion/train_diffusion.py:72-114)
+ * dataset: dev uint8 [N,H,W,3] (HWC, as PIL lays an RGB image out), H and W positive multiples of 8, not necessarily equal.
+ * params_dev: dev array of B records, one per output image.  gray_mean_scratch: dev int32 [B], written by the first launch.
+ * out: dev float32 [B,3,H,W] in [-1,1] (the output has the dataset's image size, as in the reference).
+ * Two launches on `stream`, no host synchronisation: the rounded mean grey value of each image as it stands in front of its
+ * contrast operation (integer sums: no dependence on reduction order; defined but unused for a record without contrast),
+ * then one thread per output pixel.  For given parameters every stage is PIL's arithmetic, so the uint8 image equals what
+ * torchvision's PIL backend returns bit for bit, in chain order:
+ *   1. crop(box) + resize((W,H), BILINEAR): per axis, 22-bit integer coefficients of at most three taps (an axis whose box
+ *      length equals the output length is copied), the horizontal pass rounded to uint8 before the vertical pass;
+ *   2. horizontal / vertical flip: index reversal;
+ *   3. order[0..2]: 0 brightness, 1 contrast, 2 saturation, -1 skips the slot.  Each is Image.blend(degenerate, image, f):
+ *      t = (float)d + f * (float)(i - d) in float32 without fusing, 0 if t <= 0, 255 if t >= 255, else truncated;
+ *      d = 0, the rounded mean grey, the pixel's grey value; grey = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16;
+ *   4. rotation (nearest, fill 0) when `rotate`: source pixel (xx >> 16, yy >> 16), xx = a2 + y*a1 + x*a0,
+ *      yy = a5 + y*a4 + x*a3 in int32, rot = {a0 .. a5} PIL's 16.16 fixed-point inverse affine map; outside the image: 0;
+ *   5. ToTensor + Normalize(0.5, 0.5): ((float)v / 255 - 0.5) / 0.5 in float32.
+ * An image's output depends on its record alone, never on the batch it is in.
+ * SISIC_EINVAL: a null pointer, N or B < 1, B > 65535, H or W not a positive multiple of 8.  The records live in device
+ * memory and are not read back: their owner validates them before upload (synt_isic_amd.ops.augment does: src out of
+ * range, a box outside the image or larger than the output -- down-scaling needs PIL's widened support and is refused).
+ * The kernels clamp src and the box into range all the same, so that no record makes them read out of bounds.      */
+typedef struct sisic_augment_params {      /* 96 bytes, no padding */
+    int32_t src;                           /* index into the dataset, 0 .. N-1 */
+    int32_t crop_x, crop_y, crop_w, crop_h;/* box in source pixels; 0 < crop_w <= W, 0 < crop_h <= H */
+    int32_t hflip, vflip;
+    int32_t order[3];                      /* permutation of 0 brightness, 1 contrast, 2 saturation; -1 = skip that slot */
+    float   factor[3];                     /* brightness, contrast, saturation factors (indexed by operation, not by slot) */
+    int32_t rotate;                        /* 0: none */
+    int32_t rot[6];                        /* a0 a1 a2 a3 a4 a5 */
+    int32_t reserved[4];                   /* 0 */
+} sisic_augment_params;
+int sisic_augment(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
+                  int32_t* gray_mean_scratch, float* out, void* stream);
+/* The same chain up to and including the rotation: out_hwc dev uint8 [B,H,W,3], the image PIL returns (tests, debugging). */
+int sisic_augment_u8(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
+                     int32_t* gray_mean_scratch, uint8_t* out_hwc, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------- */
 /* When enabled, every conv launch is bracketed by HIP events on its own stream and
  * accumulated per class; reading synchronises the stream.                           */

@@ -63,6 +63,13 @@ class InterventionJob(C.Structure):
                 ("noise_std", C.c_float)]
 
 
+class AugmentParams(C.Structure):
+    """struct sisic_augment_params (96 bytes; synt_isic_amd.ops.AUGMENT_DTYPE is the numpy form)"""
+    _fields_ = [("src", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32),
+                ("crop_h", C.c_int32), ("hflip", C.c_int32), ("vflip", C.c_int32), ("order", C.c_int32 * 3),
+                ("factor", C.c_float * 3), ("rotate", C.c_int32), ("rot", C.c_int32 * 6), ("reserved", C.c_int32 * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -161,6 +168,10 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "sisic_cfi_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.c_void_p, C.c_void_p]),
+    "sisic_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    "sisic_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "sisic_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "sisic_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), c_int64_p, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),

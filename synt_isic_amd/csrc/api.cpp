@@ -222,6 +222,18 @@ int sisic_cfi_metrics(sisic_ctx* ctx, const float* logits_orig, int F, const flo
     return launch_cfi_metrics(ctx, logits_orig, F, logits_mod, J, n_classes, job_frame, rows, static_cast<hipStream_t>(stream));
 }
 
+int sisic_augment(sisic_ctx* ctx, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
+                  int32_t* gray_mean_scratch, float* out, void* stream) {
+    SISIC_REQUIRE(ctx, "augment: null context");
+    return launch_augment(ctx, dataset, N, H, W, params_dev, B, gray_mean_scratch, out, false, static_cast<hipStream_t>(stream));
+}
+
+int sisic_augment_u8(sisic_ctx* ctx, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev,
+                     int B, int32_t* gray_mean_scratch, uint8_t* out_hwc, void* stream) {
+    SISIC_REQUIRE(ctx, "augment_u8: null context");
+    return launch_augment(ctx, dataset, N, H, W, params_dev, B, gray_mean_scratch, out_hwc, true, static_cast<hipStream_t>(stream));
+}
+
 int sisic_profile_enable(sisic_ctx* ctx, int on) {
     SISIC_REQUIRE(ctx, "profile_enable: null context");
     ctx->profiling = on != 0;

@@ -225,4 +225,9 @@ int launch_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* mask
 int launch_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n,
                        const int* job_frame, float* rows, hipStream_t s);
 
+// augment.hip: the training loader's augmentation chain on a device-resident uint8 dataset (include/sisic.h); out is
+// float32 [B,3,H,W] or, with u8, uint8 [B,H,W,3]
+int launch_augment(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
+                   int32_t* gray_mean_scratch, void* out, bool u8, hipStream_t s);
+
 }  // namespace sisic

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -352,6 +353,68 @@ def cfi_metrics(logits_orig: torch.Tensor, logits_mod: torch.Tensor, job_frame) 
                                 _ptr(logits_mod, "logits_mod"), J, n, (C.c_int * J)(*frames), rows.data_ptr(),
                                 _stream(logits_mod.device)))
     return rows
+
+
+# struct sisic_augment_params as a numpy record (96 bytes, the C layout)
+AUGMENT_DTYPE = np.dtype([("src", "<i4"), ("crop_x", "<i4"), ("crop_y", "<i4"), ("crop_w", "<i4"), ("crop_h", "<i4"),
+                          ("hflip", "<i4"), ("vflip", "<i4"), ("order", "<i4", (3,)), ("factor", "<f4", (3,)),
+                          ("rotate", "<i4"), ("rot", "<i4", (6,)), ("reserved", "<i4", (4,))])
+
+
+def validate_augment_params(params: np.ndarray, N: int, H: int, W: int) -> None:
+    """What sisic_augment cannot check itself (its records are in device memory): raises ``SisicError(SISIC_EINVAL)`` naming
+    the first bad record -- src out of range, a box outside the image or larger than the output, an unknown operation."""
+    def refuse(msg):
+        raise _lib.SisicError(_lib.SISIC_EINVAL, "augment: " + msg)
+    if H <= 0 or W <= 0 or H % 8 or W % 8:
+        refuse(f"{H} x {W}: height and width must be positive multiples of 8")
+    if params.dtype != AUGMENT_DTYPE or params.ndim != 1 or len(params) == 0:
+        refuse("params must be a non-empty 1-D array of ops.AUGMENT_DTYPE records")
+    checks = (
+        ((params["src"] < 0) | (params["src"] >= N), lambda r: f"src {r['src']} of {N} images"),
+        ((params["crop_w"] <= 0) | (params["crop_w"] > W) | (params["crop_h"] <= 0) | (params["crop_h"] > H),
+         lambda r: f"a {r['crop_w']} x {r['crop_h']} box for a {W} x {H} output (only 0 < size <= output: down-scaling is refused)"),
+        ((params["crop_x"] < 0) | (params["crop_y"] < 0) | (params["crop_x"].astype(np.int64) + params["crop_w"] > W)
+         | (params["crop_y"].astype(np.int64) + params["crop_h"] > H),
+         lambda r: f"box x {r['crop_x']} y {r['crop_y']} w {r['crop_w']} h {r['crop_h']} leaves the {W} x {H} image"),
+        (((params["order"] < -1) | (params["order"] > 2)).any(axis=1),
+         lambda r: f"order {r['order'].tolist()} (0 brightness, 1 contrast, 2 saturation, -1 skip)"),
+        (~np.isfinite(params["factor"]).all(axis=1), lambda r: f"factor {r['factor'].tolist()} is not finite"),
+    )
+    for bad, describe in checks:
+        if bad.any():
+            i = int(np.argmax(bad))
+            refuse(f"record {i}: " + describe(params[i]))
+
+
+def augment(dataset: torch.Tensor, params: np.ndarray, *, u8: bool = False) -> torch.Tensor:
+    """sisic_augment / sisic_augment_u8: ``dataset`` uint8 [N,H,W,3] on the GPU, ``params`` a host array of AUGMENT_DTYPE
+    records (``data.draw_augment_params``).  Returns fp32 [B,3,H,W] in [-1,1], or with ``u8`` the uint8 [B,H,W,3] image PIL
+    returns for the same parameters.  The records are validated here, then uploaded from pinned memory without blocking; the
+    two launches run on the current stream and nothing synchronises with the host."""
+    lib = _lib.load()
+    if not dataset.is_cuda or dataset.dtype != torch.uint8 or not dataset.is_contiguous() or dataset.dim() != 4 \
+            or dataset.shape[3] != 3:
+        raise ValueError(f"dataset must be a contiguous uint8 [N,H,W,3] tensor on the GPU (got {dataset.dtype}, "
+                         f"{tuple(dataset.shape)}, {dataset.device})")
+    N, H, W, _ = dataset.shape
+    params = np.ascontiguousarray(params)
+    validate_augment_params(params, N, H, W)
+    B = len(params)
+    dev = dataset.device
+    staged = torch.empty(B * AUGMENT_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+    staged.numpy()[:] = params.view(np.uint8)
+    params_dev = staged.to(dev, non_blocking=True)
+    scratch = torch.empty(B, dtype=torch.int32, device=dev)
+    if u8:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        fn = lib.sisic_augment_u8
+    else:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        fn = lib.sisic_augment
+    check(fn(context(dev), dataset.data_ptr(), N, H, W, params_dev.data_ptr(), B, scratch.data_ptr(), out.data_ptr(),
+             _stream(dev)))
+    return out
 
 
 _KINDS = {"conv3x3": 0, "conv1x1": 1, "groupnorm": 2, "attention": 3, "ddpm_step": 4, "other": 5,
