@@ -256,7 +256,9 @@ int sisic_sample_frames(sisic_unet*, float* x, int B, int H, int W, int T, const
  * Philox4x32-10 block per four consecutive elements: counter (e >> 2, i, tag, 0), key (s_b & 0xffffffff, s_b >> 32), words
  * (r0, r1) -> elements 4q, 4q+1 and (r2, r3) -> 4q+2, 4q+3 by Box-Muller (cos, sin) with u1 = ((r >> 8) + 1) * 2^-24,
  * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T; tag 2: the noise
- * interventions of sisic_intervene.  A pure function of
+ * interventions of sisic_intervene; tag 3: the bootstrap resamples and tag 4: the permutation resamples of
+ * sisic_resample_diffs (raw words, step = the resample); tag 16 + k: tensor k of a classifier randomised by
+ * sisic_resnet_randomize (step = the trial).  A pure function of
  * (seed, step, tag, element): independent of the batch, the GPU count, graph or eager mode.  1 <= n_per_image <= 2^34.
  * seeds: HOST uint64 [B], read before the call returns.
  * sisic_noise_fill: out dev float [B, n_per_image];
@@ -353,6 +355,18 @@ int sisic_resnet_num_tensors(const sisic_resnet*);
 const char* sisic_resnet_tensor_name(const sisic_resnet*, int index);
 int sisic_resnet_load(sisic_resnet*, int n, const char* const* names, const float* const* host_ptrs,
                       const int64_t* numels);
+/* The weight randomisation of the sanity check (xai/XAI.py:2056-2059: param.data = randn_like(param) * strength for every
+ * parameter with more than one dimension): the 20 convolution weights and fc.weight are REPLACED, element e of tensor k
+ * (index as in sisic_resnet_tensor_name) by noise_normal(seed, element e, step = trial, tag = 16 + k) * strength, one fp32
+ * multiply -- the values of sisic_noise_fill(out, 1, numel, &seed, trial, 16 + k) times strength.  BatchNorm vectors, running
+ * statistics and fc.bias stay, so the folded biases stay.  The filters are generated on the device in their BatchNorm-folded
+ * form (float)((double)w * gamma / sqrt(var + eps)), the scale in double as at load time, and every packed form is rebuilt in
+ * the buffers the handle owns: nothing is uploaded or allocated.  The device then holds what sisic_resnet_load of that state
+ * dict would leave, bit for bit.  Forward, input gradient and Grad-CAM use the new filters.
+ * sisic_resnet_restore derives the filters of the loaded state dict again (the load path, blocking uploads);
+ * sisic_resnet_load always leaves the handle un-randomised.                                                              */
+int sisic_resnet_randomize(sisic_resnet*, uint64_t seed, uint32_t trial, float strength, void* stream);
+int sisic_resnet_restore(sisic_resnet*, void* stream);
 /* logits[B,num_classes] = classifier.forward(x).  preprocess=1: x is dev [B,3,H,W] in [-1,1] (the
  * sampler's latents) and goes through preprocess_for_classifier (XAI.py:399-431): clamp((x+1)/2,0,1),
  * bilinear resize to 224x224 (H,W <= 224), ImageNet normalisation.  preprocess=0: x is already the
@@ -442,6 +456,22 @@ int sisic_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* masks
  * A frame index out of range returns SISIC_EINVAL.                                                                   */
 int sisic_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n_classes,
                       const int* job_frame, float* rows, void* stream);
+
+/* ---- bootstrap and permutation resamples of the statistics stage (xai/XAI.py:1845-1904) ------------------------------------
+ * The difference of means of n_bootstrap bootstrap resamples and n_permutations random relabellings of two samples, one GPU
+ * thread per resample.  top / bottom: HOST doubles [n_top] / [n_bottom], read before the call returns; boot_out: DEVICE double
+ * [n_bootstrap], perm_out: DEVICE double [n_permutations]; a count of 0 goes with a NULL pointer (that output is not touched).
+ * 1 <= n_top, n_bottom and n_top + n_bottom <= 4096, anything else is SISIC_EINVAL.  Synchronises the stream.
+ * N = n_top + n_bottom, comb = top followed by bottom.  Resample r reads the words w[0..N-1] of the device-noise block stream:
+ * word j is word j & 3 of philox4x32_10(counter (j >> 2, r, tag, 0), key seed) = sisic_noise_bits(n_per_image = N, step = r, tag).
+ *   bootstrap (tag 3):    s1 = sum_{j < n_top} top[(w[j] * n_top) >> 32],  s2 = sum_{j < n_bottom} bottom[(w[n_top + j] * n_bottom) >> 32]
+ *   permutation (tag 4):  selection sampling (Knuth, Algorithm S), a uniform n_top-subset without a stored permutation:
+ *                         need = n_top; for i = 0 .. N-1: if ((w[i] * (N - i)) >> 32 < need) { s1 += comb[i]; need -= 1 } else s2 += comb[i]
+ * (64-bit products; the sums sequential in index order, in double) and the result is s1 / n_top - s2 / n_bottom.  The mean
+ * difference depends only on which subset is chosen, so the permutation draw has the distribution of the reference's
+ * shuffle-and-split.  A function of (values, seed, r) alone: bit-reproducible.                                              */
+int sisic_resample_diffs(sisic_ctx*, const double* top, int n_top, const double* bottom, int n_bottom, uint64_t seed,
+                         int n_bootstrap, int n_permutations, double* boot_out, double* perm_out, void* stream);
 
 /* ---- training loader: the reference's augmentation chain on a device-resident dataset (diffusion/train_diffusion.py:72-114)
  * dataset: dev uint8 [N,H,W,3] (HWC, as PIL lays an RGB image out), H and W positive multiples of 8, not necessarily equal.

@@ -150,6 +150,8 @@ SIGNATURES = {
     "sisic_resnet_num_tensors": (C.c_int, [C.c_void_p]),
     "sisic_resnet_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),
     "sisic_resnet_load": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), c_int64_p]),
+    "sisic_resnet_randomize": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p]),
+    "sisic_resnet_restore": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sisic_resnet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p]),
     "sisic_resnet_stem": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -168,6 +170,8 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "sisic_cfi_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.c_void_p, C.c_void_p]),
+    "sisic_resample_diffs": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_uint64,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sisic_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     "sisic_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

@@ -140,6 +140,41 @@ class HipMelanomaClassifier:
             self._upload()
         return self._handle
 
+    # ---- weight randomisation (the sanity check of xai/XAI.py:2043-2098) ---------------------------
+    RANDOMIZE_TAG0 = 16          # device-noise tag of tensor k: 16 + k (include/sisic.h)
+
+    def randomize_weights(self, seed: int, trial: int, strength: float = 0.01) -> None:
+        """``param.data = randn_like(param) * strength`` for every parameter with more than one dimension (XAI.py:2056-2059), on
+        the device (sisic_resnet_randomize): tensor k holds ``noise_fill([seed], numel, trial, tag=16 + k) * strength``, a
+        function of (seed, trial, strength) alone.  ``state_dict()`` keeps returning the loaded weights; ``restore_weights()``
+        brings them back."""
+        seed = int(seed)
+        if seed < 0 or seed >> 64:
+            raise ValueError("seed must be an integer in 0 .. 2**64-1")
+        h = self.handle
+        check(_lib.load().sisic_resnet_randomize(h, seed, int(trial), float(strength),
+                                                 C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)))
+
+    def restore_weights(self) -> None:
+        """the filters of the loaded state dict again, bit for bit (sisic_resnet_restore)"""
+        h = self.handle
+        check(_lib.load().sisic_resnet_restore(h, C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)))
+
+    def randomized_state_dict(self, seed: int, trial: int, strength: float = 0.01) -> "OrderedDict[str, torch.Tensor]":
+        """The state dict the device holds after ``randomize_weights(seed, trial, strength)``, built with ``ops.noise_fill``:
+        loading it into another classifier gives the same filters (tests, the oracle)."""
+        lib = _lib.load()
+        h = self.handle
+        order = {lib.sisic_resnet_tensor_name(h, i).decode(): i for i in range(lib.sisic_resnet_num_tensors(h))}
+        out = OrderedDict()
+        for name, value in self._params.items():
+            if value.dim() > 1:
+                z = ops.noise_fill([seed], value.numel(), int(trial), tag=self.RANDOMIZE_TAG0 + order[name], device=self._device)
+                out[name] = (z[0] * torch.tensor(float(strength), dtype=torch.float32, device=z.device)).view(value.shape)
+            else:
+                out[name] = value.clone()
+        return out
+
     # ---- forward --------------------------------------------------------------------------------
     # Frames per library call.  The callers in xai.py hand over whole trajectories (N frames = N inference steps, up to
     # 1000) and coalition sets; the library's activation workspace scales with the batch of a call (stem output:

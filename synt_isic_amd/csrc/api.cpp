@@ -222,6 +222,13 @@ int sisic_cfi_metrics(sisic_ctx* ctx, const float* logits_orig, int F, const flo
     return launch_cfi_metrics(ctx, logits_orig, F, logits_mod, J, n_classes, job_frame, rows, static_cast<hipStream_t>(stream));
 }
 
+int sisic_resample_diffs(sisic_ctx* ctx, const double* top, int n_top, const double* bottom, int n_bottom, uint64_t seed,
+                         int n_bootstrap, int n_permutations, double* boot_out, double* perm_out, void* stream) {
+    SISIC_REQUIRE(ctx, "resample_diffs: null context");
+    return launch_resample_diffs(ctx, top, n_top, bottom, n_bottom, seed, n_bootstrap, n_permutations, boot_out, perm_out,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int sisic_augment(sisic_ctx* ctx, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
                   int32_t* gray_mean_scratch, float* out, void* stream) {
     SISIC_REQUIRE(ctx, "augment: null context");

@@ -224,6 +224,13 @@ int launch_intervene(sisic_ctx*, const float* frames, int F, const uint8_t* mask
                      float* intervention_out, float* stats, hipStream_t s);
 int launch_cfi_metrics(sisic_ctx*, const float* logits_orig, int F, const float* logits_mod, int J, int n,
                        const int* job_frame, float* rows, hipStream_t s);
+// bootstrap / permutation resamples of the mean difference (top, bottom: HOST doubles); synchronises s
+int launch_resample_diffs(sisic_ctx*, const double* top, int n_top, const double* bottom, int n_bottom, uint64_t seed,
+                          int n_bootstrap, int n_permutations, double* boot_out, double* perm_out, hipStream_t s);
+// an OIHW weight replaced by noise_normal1(seed, e, trial, tag) * strength: raw = the BN-folded filter (float)((double)w * sc[co]),
+// raw_t (may be NULL) its tap-flipped transposed copy; sc NULL writes the values themselves
+int launch_randomize_weight(sisic_ctx*, float* raw, float* raw_t, const double* sc, int cout, int cin, int k, uint64_t seed,
+                            uint32_t trial, uint32_t tag, float strength, hipStream_t s);
 
 // augment.hip: the training loader's augmentation chain on a device-resident uint8 dataset (include/sisic.h); out is
 // float32 [B,3,H,W] or, with u8, uint8 [B,H,W,3]

@@ -25,6 +25,8 @@ struct FoldedConv {
     float* bias = nullptr;
     // backward-to-input (sisic_resnet_input_gradient): the same convolution with transposed, tap-flipped filters
     float* raw = nullptr;            // BN-folded OIHW weight on the device (the stem's transposed convolution reads it)
+    float* raw_t = nullptr;          // its transposed, tap-flipped copy [cin][cout][k*k] (not for the 7x7 stem)
+    double* sc = nullptr;            // BatchNorm scale gamma / sqrt(var + eps) per output channel, in double (sisic_resnet_randomize)
     float* packed_t = nullptr;       // packed [cout -> cin] filters W'[ci][co][a][b] = W[co][ci][k-1-a][k-1-b]
     float* wino_t = nullptr;         // their Winograd form (3x3 stride 1 only)
 };
@@ -110,49 +112,84 @@ int dev_alloc(sisic_resnet* r, size_t floats, float** out) {
     return SISIC_OK;
 }
 
-int fold(sisic_resnet* r, FoldedConv& c) {
+// BatchNorm scale of output channel co in double: gamma / sqrt(var + eps)
+inline double bn_scale(const sisic_resnet* r, const FoldedConv& c, int co) {
+    return (double)r->host[c.bn_w][co] / std::sqrt((double)r->host[c.bn_v][co] + (double)BN_EPS);
+}
+
+// every device buffer of one convolution (once per sisic_resnet_load; nothing below allocates)
+int fold_alloc(sisic_resnet* r, FoldedConv& c) {
+    if (c.k == 0) return SISIC_OK;
+    const size_t numel = (size_t)c.cout * c.cin * c.k * c.k;
+    SISIC_TRY(dev_alloc(r, numel, &c.raw));
+    SISIC_TRY(dev_alloc(r, (size_t)sisic_conv_packed_numel(c.cout, c.cin, c.k), &c.packed));
+    if (c.k == 3 && c.stride == 1)       // F(2x2,3x3) for the 13 stride-1 3x3 convolutions (conv_winograd.hip)
+        SISIC_TRY(dev_alloc(r, (size_t)winograd_packed_numel(c.cout, c.cin), &c.wino));
+    SISIC_TRY(dev_alloc(r, c.cout, &c.bias));
+    float* sc = nullptr;
+    SISIC_TRY(dev_alloc(r, 2 * (size_t)c.cout, &sc));        // cout doubles (hipMalloc aligns to 256 bytes)
+    c.sc = reinterpret_cast<double*>(sc);
+    if (c.k != 7) {                      // backward filters (the 7x7 stem has its own kernel, classifier_bwd.hip)
+        SISIC_TRY(dev_alloc(r, numel, &c.raw_t));
+        SISIC_TRY(dev_alloc(r, (size_t)sisic_conv_packed_numel(c.cin, c.cout, c.k), &c.packed_t));
+        if (c.k == 3 && c.stride == 1) SISIC_TRY(dev_alloc(r, (size_t)winograd_packed_numel(c.cin, c.cout), &c.wino_t));
+    }
+    return SISIC_OK;
+}
+
+// packed / Winograd forms of raw and raw_t, into the buffers the handle owns
+int fold_pack(sisic_resnet* r, FoldedConv& c, hipStream_t s) {
+    if (c.k == 0) return SISIC_OK;
+    SISIC_TRY(launch_conv_pack(r->ctx, c.raw, c.cout, c.cin, c.k, c.packed, s));
+    if (c.wino) SISIC_TRY(launch_winograd_pack(r->ctx, c.raw, c.cout, c.cin, c.wino, s));
+    if (c.raw_t) {
+        SISIC_TRY(launch_conv_pack(r->ctx, c.raw_t, c.cin, c.cout, c.k, c.packed_t, s));
+        if (c.wino_t) SISIC_TRY(launch_winograd_pack(r->ctx, c.raw_t, c.cin, c.cout, c.wino_t, s));
+    }
+    return SISIC_OK;
+}
+
+// the loaded weight (r->host) folded on the host in float64 and uploaded, then every derived form (sisic_resnet_load and
+// sisic_resnet_restore).  The copies are blocking: the host vectors are locals.
+int fold(sisic_resnet* r, FoldedConv& c, hipStream_t s) {
     if (c.k == 0) return SISIC_OK;
     const std::vector<float>& w = r->host[c.w_idx];
-    const std::vector<float>& g = r->host[c.bn_w];
     const std::vector<float>& be = r->host[c.bn_b];
     const std::vector<float>& m = r->host[c.bn_m];
-    const std::vector<float>& v = r->host[c.bn_v];
     const size_t per = (size_t)c.cin * c.k * c.k;
     std::vector<float> wf(w.size()), bf(c.cout);
+    std::vector<double> scv(c.cout);
     for (int co = 0; co < c.cout; ++co) {
-        const double sc = (double)g[co] / std::sqrt((double)v[co] + (double)BN_EPS);
+        const double sc = bn_scale(r, c, co);
+        scv[co] = sc;
         for (size_t i = 0; i < per; ++i) wf[co * per + i] = (float)((double)w[co * per + i] * sc);
         bf[co] = (float)((double)be[co] - (double)m[co] * sc);
     }
-    float* raw = nullptr;
-    SISIC_TRY(dev_alloc(r, wf.size(), &raw));
-    SISIC_HIP(hipMemcpy(raw, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-    SISIC_TRY(dev_alloc(r, (size_t)sisic_conv_packed_numel(c.cout, c.cin, c.k), &c.packed));
-    SISIC_TRY(launch_conv_pack(r->ctx, raw, c.cout, c.cin, c.k, c.packed, nullptr));
-    if (c.k == 3 && c.stride == 1) {     // F(2x2,3x3) for the 13 stride-1 3x3 convolutions (conv_winograd.hip)
-        SISIC_TRY(dev_alloc(r, (size_t)winograd_packed_numel(c.cout, c.cin), &c.wino));
-        SISIC_TRY(launch_winograd_pack(r->ctx, raw, c.cout, c.cin, c.wino, nullptr));
-    }
-    SISIC_TRY(dev_alloc(r, c.cout, &c.bias));
+    SISIC_HIP(hipMemcpy(c.raw, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
     SISIC_HIP(hipMemcpy(c.bias, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
-    c.raw = raw;
-    if (c.k != 7) {                      // backward filters (the 7x7 stem has its own kernel, classifier_bwd.hip)
+    SISIC_HIP(hipMemcpy(c.sc, scv.data(), scv.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (c.raw_t) {
         const int kk = c.k * c.k;
         std::vector<float> wt(wf.size());
         for (int co = 0; co < c.cout; ++co)
             for (int ci = 0; ci < c.cin; ++ci)
                 for (int t = 0; t < kk; ++t)
                     wt[((size_t)ci * c.cout + co) * kk + (kk - 1 - t)] = wf[((size_t)co * c.cin + ci) * kk + t];
-        float* rawt = nullptr;
-        SISIC_TRY(dev_alloc(r, wt.size(), &rawt));
-        SISIC_HIP(hipMemcpy(rawt, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-        SISIC_TRY(dev_alloc(r, (size_t)sisic_conv_packed_numel(c.cin, c.cout, c.k), &c.packed_t));
-        SISIC_TRY(launch_conv_pack(r->ctx, rawt, c.cin, c.cout, c.k, c.packed_t, nullptr));
-        if (c.k == 3 && c.stride == 1) {
-            SISIC_TRY(dev_alloc(r, (size_t)winograd_packed_numel(c.cin, c.cout), &c.wino_t));
-            SISIC_TRY(launch_winograd_pack(r->ctx, rawt, c.cin, c.cout, c.wino_t, nullptr));
-        }
+        SISIC_HIP(hipMemcpy(c.raw_t, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    return fold_pack(r, c, s);
+}
+
+// fold() of every convolution and the fc weight: the device state of the loaded, un-randomised model
+int derive_from_host(sisic_resnet* r, hipStream_t s) {
+    SISIC_TRY(fold(r, r->stem, s));
+    for (auto& b : r->blocks) {
+        SISIC_TRY(fold(r, b.conv1, s));
+        SISIC_TRY(fold(r, b.conv2, s));
+        SISIC_TRY(fold(r, b.down, s));
+    }
+    SISIC_HIP(hipMemcpy(r->d_fc_w, r->host[r->fc_w].data(), r->host[r->fc_w].size() * sizeof(float), hipMemcpyHostToDevice));
+    SISIC_HIP(hipMemcpy(r->d_fc_b, r->host[r->fc_b].data(), r->host[r->fc_b].size() * sizeof(float), hipMemcpyHostToDevice));
     return SISIC_OK;
 }
 
@@ -256,19 +293,56 @@ int sisic_resnet_load(sisic_resnet* r, int n, const char* const* names, const fl
     for (auto p : r->owned) (void)hipFree(p);
     r->owned.clear();
     r->loaded = false;
-    SISIC_TRY(fold(r, r->stem));
+    // which buffers a convolution has depends on its geometry alone: every pointer below is either set again or stays NULL
+    SISIC_TRY(fold_alloc(r, r->stem));
     for (auto& b : r->blocks) {
-        SISIC_TRY(fold(r, b.conv1));
-        SISIC_TRY(fold(r, b.conv2));
-        SISIC_TRY(fold(r, b.down));
+        SISIC_TRY(fold_alloc(r, b.conv1));
+        SISIC_TRY(fold_alloc(r, b.conv2));
+        SISIC_TRY(fold_alloc(r, b.down));
     }
     SISIC_TRY(dev_alloc(r, r->host[r->fc_w].size(), &r->d_fc_w));
     SISIC_TRY(dev_alloc(r, r->host[r->fc_b].size(), &r->d_fc_b));
-    SISIC_HIP(hipMemcpy(r->d_fc_w, r->host[r->fc_w].data(), r->host[r->fc_w].size() * sizeof(float), hipMemcpyHostToDevice));
-    SISIC_HIP(hipMemcpy(r->d_fc_b, r->host[r->fc_b].data(), r->host[r->fc_b].size() * sizeof(float), hipMemcpyHostToDevice));
+    SISIC_TRY(derive_from_host(r, nullptr));
     SISIC_HIP(hipDeviceSynchronize());
     r->loaded = true;
     return SISIC_OK;
+}
+
+int sisic_resnet_randomize(sisic_resnet* r, uint64_t seed, uint32_t trial, float strength, void* stream) {
+    SISIC_REQUIRE(r, "resnet_randomize: null handle");
+    if (!r->loaded) {
+        set_error("resnet_randomize called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    constexpr uint32_t TAG0 = 16u;           // tag 16 + k: tensor k in sisic_resnet_tensor_name order
+    auto conv = [&](FoldedConv& c) -> int {
+        if (c.k == 0) return SISIC_OK;
+        SISIC_TRY(launch_randomize_weight(r->ctx, c.raw, c.raw_t, c.sc, c.cout, c.cin, c.k, seed, trial, TAG0 + (uint32_t)c.w_idx,
+                                          strength, s));
+        return fold_pack(r, c, s);
+    };
+    SISIC_TRY(conv(r->stem));
+    for (auto& b : r->blocks) {
+        SISIC_TRY(conv(b.conv1));
+        SISIC_TRY(conv(b.conv2));
+        SISIC_TRY(conv(b.down));
+    }
+    return launch_randomize_weight(r->ctx, r->d_fc_w, nullptr, nullptr, r->num_classes, 512, 1, seed, trial,
+                                   TAG0 + (uint32_t)r->fc_w, strength, s);
+}
+
+int sisic_resnet_restore(sisic_resnet* r, void* stream) {
+    SISIC_REQUIRE(r, "resnet_restore: null handle");
+    if (!r->loaded) {
+        set_error("resnet_restore called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SISIC_HIP(hipStreamSynchronize(s));      // launches that still read the filters; the uploads below are blocking copies
+    return derive_from_host(r, s);
 }
 
 int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, int H, int W, int preprocess,

@@ -1,6 +1,9 @@
 // xai_kernels.hip -- stage 2 of the explainability pipeline (xai/XAI.py:1454-1700, :2822-2896) as two launches:
 //   * intervene_kernel   : every counterfactual image of a run -- (frame, region mask, intervention type) jobs -- in one launch
 //   * cfi_metrics_kernel : the classifier's logits of the originals and of the modified images -> every causal-shift number
+// and the device work of stages 5 and 6 (:1845-1904, :2056-2059):
+//   * resample_diffs_kernel   : the bootstrap and permutation resamples of the mean difference, one thread per resample
+//   * randomize_weight_kernel : a classifier weight replaced by seeded normals, written in its BatchNorm-folded forms
 // The reference builds one image at a time with a Python loop over channels and spends 18 batch-1 classifier forwards per
 // image on the metrics.  This is latency work (tens of jobs of 12k-150k floats): one workgroup per job, and every reduction
 // (channel mean, standard deviation, the four statistics) runs in a fixed order, so that a job's bits depend on nothing but
@@ -332,6 +335,131 @@ int launch_cfi_metrics(sisic_ctx* ctx, const float* logits_orig, int F, const fl
                            nj, n, rows + (int64_t)j0 * row);
         SISIC_HIP(hipGetLastError());
     }
+    return SISIC_OK;
+}
+
+// ---- bootstrap and permutation resamples of the statistics stage (xai/XAI.py:1845-1904) -------------------------------------
+// One thread per resample; the N <= 4096 values (top followed by bottom) are staged once per workgroup in LDS as doubles.
+// Resample r reads the words w[0..N-1] of the block stream (seed, step = r, tag): word j is word j & 3 of block j >> 2.  Every
+// sum runs sequentially in index order in double and this file is built without FMA contraction, so a resample's bits are a
+// function of (values, seed, r) alone (include/sisic.h states the two draws).
+constexpr int RS_THREADS = 256;
+constexpr int RS_MAX_VALUES = 4096;
+constexpr uint32_t RS_TAG_BOOTSTRAP = 3u, RS_TAG_PERMUTATION = 4u;
+
+__device__ __forceinline__ uint32_t word_of(const uint4& b, int k) { return k == 0 ? b.x : k == 1 ? b.y : k == 2 ? b.z : b.w; }
+
+// comb: dev double [n_top + n_bottom]; the first boot_blocks workgroups draw bootstrap resamples, the others permutations
+__global__ void __launch_bounds__(RS_THREADS)
+resample_diffs_kernel(const double* __restrict__ comb, int n_top, int n_bottom, uint64_t seed, int n_bootstrap,
+                      int n_permutations, int boot_blocks, double* __restrict__ boot_out, double* __restrict__ perm_out) {
+    __shared__ double vals[RS_MAX_VALUES];
+    const int N = n_top + n_bottom;
+    for (int i = threadIdx.x; i < N; i += RS_THREADS) vals[i] = comb[i];
+    __syncthreads();
+    const bool boot = (int)blockIdx.x < boot_blocks;
+    const int r = ((int)blockIdx.x - (boot ? 0 : boot_blocks)) * RS_THREADS + (int)threadIdx.x;
+    if (r >= (boot ? n_bootstrap : n_permutations)) return;
+    double s1 = 0.0, s2 = 0.0;
+    uint4 blk = make_uint4(0u, 0u, 0u, 0u);
+    if (boot) {
+        for (int j = 0; j < N; ++j) {
+            if ((j & 3) == 0) blk = noise_bits4(seed, (uint32_t)(j >> 2), (uint32_t)r, RS_TAG_BOOTSTRAP);
+            const uint32_t w = word_of(blk, j & 3);
+            if (j < n_top) s1 += vals[__umulhi(w, (uint32_t)n_top)];
+            else s2 += vals[n_top + (int)__umulhi(w, (uint32_t)n_bottom)];
+        }
+        boot_out[r] = s1 / (double)n_top - s2 / (double)n_bottom;
+    } else {
+        // selection sampling (Knuth, TAOCP vol. 2, 3.4.2, Algorithm S): element i joins the n_top-subset with probability
+        // need / (N - i); need reaches 0 exactly when n_top elements have been taken (the last candidates are taken for sure)
+        int need = n_top;
+        for (int i = 0; i < N; ++i) {
+            if ((i & 3) == 0) blk = noise_bits4(seed, (uint32_t)(i >> 2), (uint32_t)r, RS_TAG_PERMUTATION);
+            const uint32_t w = word_of(blk, i & 3);
+            if ((int)__umulhi(w, (uint32_t)(N - i)) < need) {
+                s1 += vals[i];
+                --need;
+            } else {
+                s2 += vals[i];
+            }
+        }
+        perm_out[r] = s1 / (double)n_top - s2 / (double)n_bottom;
+    }
+}
+
+int launch_resample_diffs(sisic_ctx* ctx, const double* top, int n_top, const double* bottom, int n_bottom, uint64_t seed,
+                          int n_bootstrap, int n_permutations, double* boot_out, double* perm_out, hipStream_t s) {
+    SISIC_REQUIRE(top && bottom, "resample_diffs: null top or bottom");
+    SISIC_REQUIRE(n_top >= 1 && n_bottom >= 1 && (int64_t)n_top + n_bottom <= RS_MAX_VALUES,
+                  "resample_diffs: n_top = %d, n_bottom = %d (each at least 1, at most %d together)", n_top, n_bottom, RS_MAX_VALUES);
+    SISIC_REQUIRE(n_bootstrap >= 0 && n_permutations >= 0, "resample_diffs: negative resample count");
+    SISIC_REQUIRE((n_bootstrap == 0) == (boot_out == nullptr), "resample_diffs: boot_out must be NULL exactly when n_bootstrap is 0");
+    SISIC_REQUIRE((n_permutations == 0) == (perm_out == nullptr), "resample_diffs: perm_out must be NULL exactly when n_permutations is 0");
+    if (n_bootstrap == 0 && n_permutations == 0) return SISIC_OK;
+    const int N = n_top + n_bottom;
+    std::vector<double> comb((size_t)N);
+    for (int i = 0; i < n_top; ++i) comb[i] = top[i];
+    for (int i = 0; i < n_bottom; ++i) comb[n_top + i] = bottom[i];
+    // the values travel through a buffer of this call (at most 32 KB): the blocking copy reads the host arrays before the call
+    // returns, and hipFree waits for the kernel.  A once-per-report call whose results the caller reads back at once.
+    void* dev = nullptr;
+    SISIC_HIP(hipSetDevice(ctx->device));
+    SISIC_HIP(hipMalloc(&dev, (size_t)N * sizeof(double)));
+    hipError_t e = hipMemcpy(dev, comb.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const int boot_blocks = cdiv(n_bootstrap, RS_THREADS), perm_blocks = cdiv(n_permutations, RS_THREADS);
+        hipLaunchKernelGGL(resample_diffs_kernel, dim3(boot_blocks + perm_blocks), dim3(RS_THREADS), 0, s,
+                           static_cast<const double*>(dev), n_top, n_bottom, seed, n_bootstrap, n_permutations, boot_blocks,
+                           boot_out, perm_out);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    (void)hipFree(dev);
+    SISIC_HIP(e);
+    return SISIC_OK;
+}
+
+// ---- weight randomisation of the sanity check (xai/XAI.py:2056-2059) ---------------------------------------------------------
+// w[e] = noise_normal1(seed, e, step = trial, tag) * strength replaces an OIHW convolution weight; the kernel writes what
+// resnet.cpp's fold() would upload for it: raw[e] = (float)((double)w[e] * sc[co]) and, where raw_t is given, the tap-flipped
+// transposed copy raw_t[ci][co][kk-1-t].  sc NULL (fc.weight): the values themselves.  One Philox block per four elements.
+__global__ void __launch_bounds__(256)
+randomize_weight_kernel(float* __restrict__ raw, float* __restrict__ raw_t, const double* __restrict__ sc, int64_t numel,
+                        int cout, int cin, int kk, uint64_t seed, uint32_t trial, uint32_t tag, float strength) {
+    const int64_t nq = (numel + 3) >> 2;
+    const int64_t per = (int64_t)cin * kk;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+        const float4 z4 = noise_normal4(seed, (uint32_t)q, trial, tag);
+        const float z[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t e = 4 * q + i;
+            if (e >= numel) break;
+            const float w = z[i] * strength;
+            if (!sc) {
+                raw[e] = w;
+                continue;
+            }
+            const int co = (int)(e / per);
+            const int64_t rem = e - (int64_t)co * per;
+            const int ci = (int)(rem / kk), t = (int)(rem - (int64_t)ci * kk);
+            const float f = (float)((double)w * sc[co]);
+            raw[e] = f;
+            if (raw_t) raw_t[((int64_t)ci * cout + co) * kk + (kk - 1 - t)] = f;
+        }
+    }
+}
+
+int launch_randomize_weight(sisic_ctx* ctx, float* raw, float* raw_t, const double* sc, int cout, int cin, int k, uint64_t seed,
+                            uint32_t trial, uint32_t tag, float strength, hipStream_t s) {
+    SISIC_REQUIRE(raw && cout > 0 && cin > 0 && k > 0, "randomize_weight: bad arguments");
+    const int64_t numel = (int64_t)cout * cin * k * k;
+    const int64_t nq = (numel + 3) >> 2;
+    const int blocks = (int)std::min<int64_t>((nq + 255) / 256, 2048);
+    hipLaunchKernelGGL(randomize_weight_kernel, dim3(blocks), dim3(256), 0, s, raw, raw_t, sc, numel, cout, cin, k * k, seed,
+                       trial, tag, strength);
+    SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 

@@ -355,6 +355,30 @@ def cfi_metrics(logits_orig: torch.Tensor, logits_mod: torch.Tensor, job_frame) 
     return rows
 
 
+RESAMPLE_MAX_VALUES = 4096   # n_top + n_bottom of sisic_resample_diffs (the values live in LDS)
+
+
+def resample_diffs(top, bottom, seed: int, n_bootstrap: int, n_permutations: int, device="cuda"):
+    """sisic_resample_diffs: ``(boot [n_bootstrap], perm [n_permutations])`` float64 device tensors (None for a count of 0) -- the
+    mean differences of the bootstrap resamples (tag 3) and of the random relabellings (tag 4) of two samples, a function of
+    ``(top, bottom, seed)`` alone (include/sisic.h states the draws)."""
+    lib = _lib.load()
+    device = torch.device(device)
+    top = np.ascontiguousarray(np.asarray(top, dtype=np.float64).reshape(-1))
+    bottom = np.ascontiguousarray(np.asarray(bottom, dtype=np.float64).reshape(-1))
+    seed = int(seed)
+    if seed < 0 or seed >> 64:
+        raise ValueError("seed must be an integer in 0 .. 2**64-1")
+    n_bootstrap, n_permutations = int(n_bootstrap), int(n_permutations)
+    boot = torch.empty(n_bootstrap, dtype=torch.float64, device=device) if n_bootstrap > 0 else None
+    perm = torch.empty(n_permutations, dtype=torch.float64, device=device) if n_permutations > 0 else None
+    dp = C.POINTER(C.c_double)
+    check(lib.sisic_resample_diffs(context(device), top.ctypes.data_as(dp), top.size, bottom.ctypes.data_as(dp), bottom.size,
+                                   seed, n_bootstrap, n_permutations, None if boot is None else boot.data_ptr(),
+                                   None if perm is None else perm.data_ptr(), _stream(device)))
+    return boot, perm
+
+
 # struct sisic_augment_params as a numpy record (96 bytes, the C layout)
 AUGMENT_DTYPE = np.dtype([("src", "<i4"), ("crop_x", "<i4"), ("crop_y", "<i4"), ("crop_w", "<i4"), ("crop_h", "<i4"),
                           ("hflip", "<i4"), ("vflip", "<i4"), ("order", "<i4", (3,)), ("factor", "<f4", (3,)),

@@ -27,6 +27,22 @@ Stage 2 of ``run_comprehensive_xai_pipeline`` (XAI.py:2822-2896), counterfactual
 * ``compute_combined_attribution`` -- XAI.py:1236-1291: the weighted sum of the passes above.
 * ``intervention_stage``           -- XAI.py:2829-2875: every (key frame, region, intervention type) in ONE ``sisic_intervene``
                                      launch, ONE classifier batch and ONE ``sisic_cfi_metrics`` launch.
+
+The rest of the run (XAI.py:2733-2821, :1708-2210, :3175-3240) -- plots, the PNG / JSON saving stage and the two normality tests
+aside:
+
+* ``attribution_stage``            -- stage 1 as a stage: per frame ONE combined IG + patch-SHAP map from generators seeded
+                                     ``seed + 2 i`` / ``seed + 2 i + 1`` and its top-k / bottom-k regions, in the layout
+                                     ``intervention_stage`` consumes (the reference computes IG and SHAP three times per frame).
+* ``statistical_validation``       -- stages 4-5: the classical tests in numpy (``xai_stats``: no scipy) and the 1 000 bootstrap +
+                                     10 000 permutation resamples as ONE ``sisic_resample_diffs`` launch drawn from a seed
+                                     (device-noise tags 3 and 4), where the reference loops in the interpreter over numpy's
+                                     global generator.
+* ``sanity_check``                 -- stage 6: weight randomisation, input independence, class sensitivity.  The classifier is
+                                     re-randomised ON THE DEVICE (``sisic_resnet_randomize``: Philox normals written in their
+                                     BatchNorm-folded and packed forms, device-noise tag 16 + tensor) and restored afterwards.
+* ``run_pipeline``                 -- the driver: stages 1-2, Time-SHAP, Grad-CAM, statistics, sanity check -> the reference's
+                                     ``results`` dictionary, a function of its seed.
 """
 from __future__ import annotations
 
@@ -534,3 +550,279 @@ def intervention_stage(classifier: HipMelanomaClassifier, trajectory, timesteps:
         interventions.setdefault(key, {}).setdefault(region, {})[t] = entry
         cfi.setdefault(key, {})[f"{region}_{t}"] = _causal_shift_entry(rows[j], logits.shape[1], int(target_class), True)
     return interventions, cfi
+
+
+# ---- stages 1, 4-6 and the driver (XAI.py:2733-2821, :1708-2210, :2663-3297) ---------------------------------------------------
+BOTTOM_K_PERCENT = 10         # xai/XAI.py:239
+ALPHA_LEVEL = 0.1             # xai/XAI.py:270
+N_BOOTSTRAP = 1000            # xai/XAI.py:271
+N_PERMUTATIONS = 10000        # xai/XAI.py:272
+SHAP_PATCH_SIZE = 16          # compute_shap_approximation's default
+
+
+def _step_key(timestep) -> str:
+    return f"t_{float(timestep):.0f}"
+
+
+@torch.no_grad()
+def attribution_stage(classifier: HipMelanomaClassifier, trajectory, timesteps: Sequence[float], target_class: int, *,
+                      ig_steps: int = IG_N_STEPS, shap_samples: int = SHAP_N_SAMPLES, k_percent: float = TOP_K_PERCENT,
+                      seed: int = 0):
+    """Stage 1 of ``run_comprehensive_xai_pipeline`` (XAI.py:2733-2821): ``(xai_maps, region_data)`` keyed ``t_<timestep>``.
+    ``xai_maps[key]`` = {timestep, attribution_map, method_details, image_shape}, ``region_data[key]`` = {top_k, bottom_k} of
+    ``select_regions`` -- the layout ``intervention_stage`` consumes.
+
+    Frame i's map IS ``compute_combined_attribution(classifier, frame_i, target_class, ("ig", "shap"), [0.5, 0.5],
+    ig_kwargs={"n_steps": ig_steps, "generator": g_ig}, shap_kwargs={"n_samples": shap_samples, "patch_masks": masks})`` with
+    ``g_ig = torch.Generator().manual_seed(seed + 2 i)`` and ``masks = draw_patch_masks(shap_samples, H // 16, W // 16,
+    torch.Generator().manual_seed(seed + 2 i + 1))``.  The reference computes IG and SHAP three times per frame with fresh
+    random draws (two for plots); only the combined map reaches the results, and only it is computed here."""
+    frames = _as_batch(trajectory)
+    if frames.shape[0] != len(timesteps):
+        raise ValueError(f"{frames.shape[0]} frames but {len(timesteps)} timesteps")
+    H, W = frames.shape[-2:]
+    xai_maps: Dict = {}
+    region_data: Dict = {}
+    for i, timestep in enumerate(timesteps):
+        image = frames[i:i + 1]
+        g_ig = torch.Generator().manual_seed(int(seed) + 2 * i)
+        masks = draw_patch_masks(shap_samples, H // SHAP_PATCH_SIZE, W // SHAP_PATCH_SIZE,
+                                 torch.Generator().manual_seed(int(seed) + 2 * i + 1))
+        combined, details = compute_combined_attribution(classifier, image, target_class, ("ig", "shap"), [0.5, 0.5],
+                                                         ig_kwargs={"n_steps": ig_steps, "generator": g_ig},
+                                                         shap_kwargs={"n_samples": shap_samples, "patch_masks": masks})
+        key = _step_key(timestep)
+        xai_maps[key] = {"timestep": timestep, "attribution_map": combined, "method_details": details,
+                         "image_shape": tuple(image.shape)}
+        region_data[key] = {"top_k": select_regions(combined, k_percent=k_percent, region_type="top"),
+                            "bottom_k": select_regions(combined, k_percent=k_percent, region_type="bottom")}
+    return xai_maps, region_data
+
+
+_NORMALITY_SKIPPED = {"skipped": True, "reason": "not computed: informational in the reference, outside the consensus"}
+
+
+def statistical_validation(top_k_shifts, bottom_k_shifts, alpha: float = ALPHA_LEVEL, n_bootstrap: int = N_BOOTSTRAP,
+                           n_permutations: int = N_PERMUTATIONS, seed: int = 0, device="cuda") -> Dict:
+    """``statistical_validation_comprehensive`` (XAI.py:1708-2005): the reference's dictionary, same keys and nesting.  The
+    classical tests are ``xai_stats`` (numpy, no scipy); the 1 000 bootstrap and 10 000 permutation resamples are ONE
+    ``sisic_resample_diffs`` launch drawn from ``seed`` (device-noise tags 3 and 4) instead of two interpreter loops over
+    numpy's global generator: the same distributions, reproducible.  ``normality_tests`` holds the reference's 'skipped' form
+    (Shapiro-Wilk and Kolmogorov-Smirnov do not enter the consensus); ``metadata`` gains ``seed``.  Fewer than two values on
+    either side raise ``ValueError("Insufficient data")``."""
+    from datetime import datetime
+
+    from . import xai_stats
+    top_k = np.asarray(top_k_shifts, dtype=np.float64).reshape(-1)
+    bottom_k = np.asarray(bottom_k_shifts, dtype=np.float64).reshape(-1)
+    if len(top_k) < 2 or len(bottom_k) < 2:
+        raise ValueError("Insufficient data")
+    if n_bootstrap < 1:
+        raise ValueError("n_bootstrap must be at least 1")
+    results = xai_stats.classical_tests(top_k, bottom_k, alpha)
+    boot, perm = ops.resample_diffs(top_k, bottom_k, seed, n_bootstrap, n_permutations, device)
+
+    bootstrap_diffs = boot.cpu().numpy()
+    confidence_level = 1 - alpha
+    ci_lower = np.percentile(bootstrap_diffs, (1 - confidence_level) / 2 * 100)
+    ci_upper = np.percentile(bootstrap_diffs, (1 + confidence_level) / 2 * 100)
+    bootstrap_results = {"bootstrap_diffs": bootstrap_diffs, "mean_diff": np.mean(bootstrap_diffs), "ci_lower": ci_lower,
+                         "ci_upper": ci_upper, "ci_contains_zero": bool(ci_lower <= 0 <= ci_upper),
+                         "confidence_level": confidence_level}
+
+    observed_diff = np.mean(top_k) - np.mean(bottom_k)
+    if len(top_k) >= 2 and len(bottom_k) >= 2 and perm is not None:
+        permuted_diffs = perm.cpu().numpy()
+    else:
+        permuted_diffs = np.array([observed_diff])
+    p_value = np.mean(np.abs(permuted_diffs) >= np.abs(observed_diff)) if permuted_diffs.size > 1 else 1.0
+    permutation_results = {"observed_difference": observed_diff, "permuted_differences": permuted_diffs, "p_value": p_value,
+                           "significant": bool(p_value < alpha), "n_permutations": n_permutations}
+
+    consensus = {
+        "parametric_significant": any(t["significant"] for t in results["parametric_tests"].values()),
+        "nonparametric_significant": any(t["significant"] for t in results["nonparametric_tests"].values()),
+        "bootstrap_significant": not bootstrap_results["ci_contains_zero"],
+        "permutation_significant": permutation_results["significant"],
+    }
+    total_significant = sum(consensus.values())
+    overall = total_significant >= len(consensus) // 2 + 1
+    return {
+        "descriptive_statistics": results["descriptive_statistics"],
+        "parametric_tests": results["parametric_tests"],
+        "nonparametric_tests": results["nonparametric_tests"],
+        "effect_sizes": results["effect_sizes"],
+        "bootstrap_analysis": bootstrap_results,
+        "permutation_analysis": permutation_results,
+        "normality_tests": {"shapiro_wilk": {"top_k": dict(_NORMALITY_SKIPPED), "bottom_k": dict(_NORMALITY_SKIPPED)},
+                            "kolmogorov_smirnov": {"top_k": dict(_NORMALITY_SKIPPED), "bottom_k": dict(_NORMALITY_SKIPPED)}},
+        "variance_tests": results["variance_tests"],
+        "significance_consensus": consensus,
+        "overall_conclusion": {"significant": overall, "significant_tests_count": total_significant,
+                               "total_tests_count": len(consensus), "alpha_level": alpha,
+                               "recommendation": "significant" if overall else "not_significant"},
+        "metadata": {"analysis_timestamp": datetime.now().isoformat(), "n_bootstrap_samples": n_bootstrap,
+                     "n_permutations": n_permutations, "alpha_level": alpha, "seed": seed},
+    }
+
+
+def pearson_correlation(a: torch.Tensor, b: torch.Tensor) -> float:
+    """Pearson's r of two maps in float64 on their device: three plain reductions (no BLAS); NaN where numpy's corrcoef is"""
+    a, b = a.reshape(-1).double(), b.reshape(-1).double()
+    da, db = a - a.mean(), b - b.mean()
+    return float(((da * db).sum() / torch.sqrt((da * da).sum() * (db * db).sum())).item())
+
+
+SANITY_RANDOM_THRESHOLD = 0.1          # XAI.py:2086
+SANITY_INDEPENDENCE_THRESHOLD = 0.3    # XAI.py:2129
+SANITY_SENSITIVITY_THRESHOLD = 0.8     # XAI.py:2164
+
+
+@torch.no_grad()
+def sanity_check(classifier: HipMelanomaClassifier, test_image: torch.Tensor, target_class: int, n_trials: int = 3,
+                 randomization_strength: float = 0.01, seed: int = 0, ig_steps: int = 20, ig_steps_aux: int = 15) -> Dict:
+    """``sanity_check_comprehensive`` (XAI.py:2008-2210): weight randomisation (|r| of the Integrated-Gradients map against the
+    maps of ``n_trials`` re-randomised classifiers, mean < 0.1), input independence (maps of three random inputs, mean |r| < 0.3)
+    and class sensitivity (maps of the other classes among 0..2, mean |r| < 0.8), their score and interpretation.
+
+    IG call c, counted in the reference's order -- the original, the trials, the three independent inputs, the other classes --
+    draws its noise baseline from ``torch.Generator().manual_seed(seed + c)``; independent input j is ``torch.randn`` from
+    ``manual_seed(seed + 1000 + j)``, and the three go through ONE IG call as a batch of three.  Trial t runs under
+    ``classifier.randomize_weights(seed, t, randomization_strength)`` (generated on the device; nothing is uploaded).
+    Correlations: ``pearson_correlation``; NaN counts as 0 in the first test and is skipped in the other two, as in the
+    reference.  The weights are restored in a ``finally``; a library error propagates."""
+    dev = classifier.device
+    image = test_image.to(dev, torch.float32)
+    if image.dim() == 3:
+        image = image.unsqueeze(0)
+    if image.dim() != 4 or image.shape[0] != 1:
+        raise ValueError(f"sanity_check takes one image [1,3,H,W], got {tuple(test_image.shape)}")
+    call = 0
+
+    def baseline_for(img):
+        nonlocal call
+        g = torch.Generator().manual_seed(int(seed) + call)
+        call += 1
+        return make_baseline(img, "noise", g)
+
+    results: Dict = {"weight_randomization_test": {}, "input_independence_test": {}, "model_sensitivity_test": {},
+                     "overall_sanity_score": 0.0}
+    randomized = False
+    try:
+        original = compute_integrated_gradients(classifier, image, target_class, n_steps=ig_steps, baseline=baseline_for(image))
+        correlations_with_random = []
+        for trial in range(n_trials):
+            classifier.randomize_weights(seed, trial, randomization_strength)
+            randomized = True
+            attr = compute_integrated_gradients(classifier, image, target_class, n_steps=ig_steps, baseline=baseline_for(image))
+            r = pearson_correlation(original, attr)
+            correlations_with_random.append(0.0 if np.isnan(r) else abs(r))
+        if randomized:
+            classifier.restore_weights()
+            randomized = False
+        mean_random = np.mean(correlations_with_random)
+        results["weight_randomization_test"] = {
+            "mean_correlation_with_random": mean_random, "correlations_per_trial": correlations_with_random,
+            "test_passed": bool(mean_random < SANITY_RANDOM_THRESHOLD), "threshold": SANITY_RANDOM_THRESHOLD, "n_trials": n_trials}
+
+        n_inputs = 3
+        inputs = torch.cat([torch.randn(image.shape, generator=torch.Generator().manual_seed(int(seed) + 1000 + j),
+                                        dtype=torch.float32) for j in range(n_inputs)]).to(dev)
+        baselines = torch.cat([baseline_for(image) for _ in range(n_inputs)])
+        maps = compute_integrated_gradients(classifier, inputs, target_class, n_steps=ig_steps_aux, baseline=baselines)
+        independence = []
+        for i in range(n_inputs):
+            for j in range(i + 1, n_inputs):
+                r = pearson_correlation(maps[i], maps[j])
+                if not np.isnan(r):
+                    independence.append(abs(r))
+        mean_independence = np.mean(independence) if independence else 0.0
+        results["input_independence_test"] = {
+            "mean_correlation_between_independent": mean_independence, "independence_correlations": independence,
+            "test_passed": bool(mean_independence < SANITY_INDEPENDENCE_THRESHOLD), "threshold": SANITY_INDEPENDENCE_THRESHOLD,
+            "n_independent_inputs": n_inputs}
+
+        different = []
+        for other in range(min(3, classifier.num_classes)):
+            if other == target_class:
+                continue
+            attr = compute_integrated_gradients(classifier, image, other, n_steps=ig_steps_aux, baseline=baseline_for(image))
+            r = pearson_correlation(original, attr)
+            if not np.isnan(r):
+                different.append(abs(r))
+        mean_different = np.mean(different) if different else 1.0
+        results["model_sensitivity_test"] = {
+            "mean_correlation_different_classes": mean_different, "different_class_correlations": different,
+            "test_passed": bool(mean_different < SANITY_SENSITIVITY_THRESHOLD), "threshold": SANITY_SENSITIVITY_THRESHOLD,
+            "classes_tested": len(different)}
+
+        passed = [results[k]["test_passed"] for k in ("weight_randomization_test", "input_independence_test",
+                                                      "model_sensitivity_test")]
+        score = sum(passed) / len(passed)
+        results["overall_sanity_score"] = score
+        results["overall_interpretation"] = "good" if score >= 0.67 else "moderate" if score >= 0.33 else "poor"
+    finally:
+        if randomized:
+            classifier.restore_weights()
+    return results
+
+
+@torch.no_grad()
+def run_pipeline(classifier: HipMelanomaClassifier, trajectory, timesteps: Sequence[float], target_class_id: int,
+                 target_class_name: str, *, seed: int = 0, intervention_types: Sequence[str] = INTERVENTION_TYPES,
+                 ig_steps: int = IG_N_STEPS, shap_samples: int = SHAP_N_SAMPLES) -> Dict:
+    """``run_comprehensive_xai_pipeline`` (XAI.py:2663-3297) without the plots and the saving stage: the reference's ``results``
+    dictionary from stage 1 (``attribution_stage``), stage 2 (``intervention_stage``), Time-SHAP, Grad-CAM, the CFI collection
+    of :3178-3186, ``statistical_validation`` and ``sanity_check`` on the last frame.  Every stage draws from ``seed``: two
+    runs give the same report.  ``visualizations`` stays an empty list.  Only too few CFI values are recorded as
+    ``{'error': 'Insufficient data'}`` (:3221); a library error propagates instead of becoming a string in the report."""
+    from datetime import datetime
+    frames = _as_batch(trajectory)
+    if frames.shape[0] != len(timesteps):
+        raise ValueError(f"{frames.shape[0]} frames but {len(timesteps)} timesteps")
+    types = list(intervention_types)
+    results: Dict = {
+        "metadata": {
+            "target_class_id": target_class_id, "target_class_name": target_class_name, "n_timesteps": frames.shape[0],
+            "timesteps": timesteps, "analysis_timestamp": datetime.now().isoformat(), "seed": seed,
+            "parameters": {"top_k_percent": TOP_K_PERCENT, "bottom_k_percent": BOTTOM_K_PERCENT, "ig_n_steps": ig_steps,
+                           "shap_n_samples": shap_samples, "intervention_types": types, "alpha_level": ALPHA_LEVEL},
+        },
+        "visualizations": [],
+    }
+    xai_maps, region_data = attribution_stage(classifier, frames, timesteps, target_class_id, ig_steps=ig_steps,
+                                              shap_samples=shap_samples, k_percent=TOP_K_PERCENT, seed=seed)
+    results["xai_maps"], results["region_analysis"] = xai_maps, region_data
+    interventions, cfi = intervention_stage(classifier, frames, timesteps, region_data, target_class_id, types, seed=seed)
+    results["interventions"], results["cfi_analysis"] = interventions, cfi
+
+    importance, raw = compute_time_shap(classifier, frames, timesteps, target_class_id)
+    imp_idx = int(np.argmax(importance))
+    results["time_shap"] = {"importance": importance, "raw_data": raw, "most_important_timestep": timesteps[imp_idx],
+                            "most_important_index": imp_idx}
+
+    cams = compute_grad_cam(classifier, frames, timesteps, target_class_id)
+    results["gradcam_summary"] = cams.pop("summary")
+    results["gradcam"] = cams
+    results["gradcam_most_important"] = {"timestep": float(timesteps[imp_idx]), "index": imp_idx,
+                                         "gradcam": cams[_step_key(timesteps[imp_idx])]}
+
+    top_k_shifts, bottom_k_shifts = [], []
+    for step_cfi in cfi.values():
+        for intervention_key, entry in step_cfi.items():
+            if "top_k" in intervention_key:
+                top_k_shifts.append(entry["target_class_analysis"]["cfi"])
+            elif "bottom_k" in intervention_key:
+                bottom_k_shifts.append(entry["target_class_analysis"]["cfi"])
+    try:
+        results["statistical_validation"] = statistical_validation(top_k_shifts, bottom_k_shifts, alpha=ALPHA_LEVEL,
+                                                                   n_bootstrap=N_BOOTSTRAP, n_permutations=N_PERMUTATIONS,
+                                                                   seed=seed, device=classifier.device)
+    except ValueError as e:
+        if str(e) != "Insufficient data":
+            raise
+        results["statistical_validation"] = {"error": "Insufficient data"}
+
+    results["sanity_checks"] = sanity_check(classifier, frames[-1:], target_class_id, n_trials=3, randomization_strength=0.01,
+                                            seed=seed)
+    return results
