@@ -329,6 +329,10 @@ int sisic_unet_train_step(sisic_unet*, const float* images, const float* noise, 
 /* Copy one tensor of the state dict (index as in sisic_unet_tensor_name) to the host: what = 0 parameter, 1 gradient,
  * 2 Adam first moment, 3 Adam second moment.  Synchronises the device.                                                  */
 int sisic_unet_read(sisic_unet*, int what, int index, float* host_out, int64_t numel);
+/* The counterpart of sisic_unet_read (parity-test surface: optimizer tests choose their own gradients): copy one tensor
+ * from the host into the gradient (what = 1), Adam first-moment (2) or second-moment (3) arena.  what = 0 is refused:
+ * parameters have packed forms that must follow them, sisic_unet_load sets them.  Synchronises the device.              */
+int sisic_unet_write(sisic_unet*, int what, int index, const float* host_in, int64_t numel);
 int64_t sisic_unet_train_steps(const sisic_unet*);
 
 /* Single-operator entry points of the backward pass (parity-test surface).

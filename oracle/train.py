@@ -56,12 +56,14 @@ def unet_forward64(params, noisy, timesteps):
         ounet.timestep_embedding = orig
 
 
-def adam_step(sd: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], state=None, lr: float = LR):
-    """torch.optim.Adam(model.parameters(), lr=LR).step() (train_diffusion.py:203, :232) on copies of the tensors.
-    Returns (new state dict, optimizer) -- pass the optimizer back in to take further steps."""
+def adam_step(sd: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], state=None, lr: float = LR,
+              betas=(0.9, 0.999), eps: float = 1e-8):
+    """torch.optim.Adam(model.parameters(), lr=LR).step() (train_diffusion.py:203, :232) on copies of the tensors, in the
+    tensors' own dtype (float64 parameters give a rounding-free reference).  Returns (new state dict, state) -- pass the
+    state back in to take further steps; state[1].state[state[0][name]] holds that tensor's exp_avg / exp_avg_sq / step."""
     if state is None:
         params = OrderedDict((k, torch.nn.Parameter(v.detach().clone())) for k, v in sd.items())
-        opt = torch.optim.Adam(list(params.values()), lr=lr)
+        opt = torch.optim.Adam(list(params.values()), lr=lr, betas=betas, eps=eps)
         state = (params, opt)
     params, opt = state
     for k, p in params.items():

@@ -139,6 +139,7 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
                                         C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p]),
     "sisic_unet_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
+    "sisic_unet_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sisic_unet_train_steps": (C.c_int64, [C.c_void_p]),
     "sisic_conv2d_wgrad": (C.c_int, [C.c_void_p, C.POINTER(ConvArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "sisic_attention_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

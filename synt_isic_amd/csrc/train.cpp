@@ -11,6 +11,8 @@
 // statistics from convolution epilogues, attention), nothing released, every GroupNorm's scale/shift/(mean, rstd) kept.
 // Backward per convolution: bias / time-embedding sums, backward-weight (conv_wgrad_kernel), backward-data as a
 // forward convolution with transposed filters, then GroupNorm+SiLU backward into the input's gradient.
+// Parity-test surface: sisic_unet_read copies a tensor's parameter / gradient / Adam moments to the host, sisic_unet_write
+// puts a gradient or a moment of the caller's choosing into the arena (tests/test_gpu_optimizer.py).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -541,6 +543,20 @@ int sisic_unet_read(sisic_unet* u, int what, int index, float* host_out, int64_t
     SISIC_HIP(hipSetDevice(u->ctx->device));
     SISIC_HIP(hipDeviceSynchronize());
     SISIC_HIP(hipMemcpy(host_out, base + u->offsets[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+    return SISIC_OK;
+}
+
+int sisic_unet_write(sisic_unet* u, int what, int index, const float* host_in, int64_t numel) {
+    SISIC_REQUIRE(u && host_in && index >= 0 && index < (int)u->names.size(), "unet_write: bad arguments");
+    SISIC_REQUIRE(numel == u->numels[index], "unet_write: '%s' has %lld elements", u->names[index].c_str(), (long long)u->numels[index]);
+    SISIC_REQUIRE(what != 0, "unet_write: parameters are set by sisic_unet_load (their packed forms must follow); what = 1 gradient, "
+                             "2 Adam m, 3 Adam v");
+    SISIC_TRY(require_train(u, "unet_write"));
+    float* base = what == 1 ? u->train->grad : (what == 2 ? u->train->adam_m : (what == 3 ? u->train->adam_v : nullptr));
+    SISIC_REQUIRE(base, "unet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    SISIC_HIP(hipMemcpy(base + u->offsets[index], host_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
     return SISIC_OK;
 }
 

@@ -1008,7 +1008,8 @@ int launch_check_finite(sisic_ctx*, const float* g, size_t n, int* flag, hipStre
 }
 
 // torch.optim.Adam (single-tensor form, no weight decay, no amsgrad), in its operation order:
-//   m = lerp(m, g, 1 - b1);  v = v * b2 + (1 - b2) g g;  denom = sqrt(v) / sqrt(bc2) + eps;  p = p - (lr / bc1) * m / denom
+//   m = lerp(m, g, 1 - b1);  v = v * b2 + ((1 - b2) g) g;  denom = sqrt(v) / sqrt(bc2) + eps;  p = p - (lr / bc1) * m / denom
+// addcmul_(g, g, value = 1 - b2) forms (value * g) * g: g * g first would overflow for |g| > 1.85e19 where torch's v stays finite.
 // g is first multiplied by inv_scale (GradScaler.unscale_).
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
                             float one_minus_b1, float b2, float one_minus_b2, float step_size, float bc2_sqrt, float eps,
@@ -1017,7 +1018,7 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float gi = g[i] * inv_scale;
         const float mi = m[i] + one_minus_b1 * (gi - m[i]);
-        const float vi = v[i] * b2 + one_minus_b2 * (gi * gi);
+        const float vi = v[i] * b2 + (one_minus_b2 * gi) * gi;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;

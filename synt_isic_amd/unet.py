@@ -159,6 +159,22 @@ class HipUNet2DModel:
             raise RuntimeError("no backward pass has run: create a HipAdam for this model first")
         return self._read_all(1)
 
+    def set_grads(self, mapping: Dict[str, torch.Tensor]) -> None:
+        """Write {name: tensor} into the gradient arena (sisic_unet_write); tensors not named keep what they hold.  For
+        optimizer tests that choose their own gradients instead of running a backward pass."""
+        if not self._train_begun:
+            raise RuntimeError("no gradient arena: create a HipAdam for this model first")
+        lib = _lib.load()
+        h = self.handle
+        index = {lib.sisic_unet_tensor_name(h, i).decode(): i for i in range(lib.sisic_unet_num_tensors(h))}
+        for name, t in mapping.items():
+            if name not in self._spec:
+                raise KeyError(f"set_grads: no parameter named {name}")
+            if tuple(t.shape) != tuple(self._spec[name]):
+                raise RuntimeError(f"set_grads: size mismatch for {name}: {tuple(t.shape)} vs {tuple(self._spec[name])}")
+            host = t.detach().to("cpu", torch.float32).contiguous()
+            check(lib.sisic_unet_write(h, 1, index[name], C.cast(host.data_ptr(), _lib.c_float_p), host.numel()))
+
     def optimizer_state(self) -> Dict[str, "OrderedDict[str, torch.Tensor]"]:
         return {"exp_avg": self._read_all(2), "exp_avg_sq": self._read_all(3),
                 "step": int(_lib.load().sisic_unet_train_steps(self.handle))}
