@@ -164,6 +164,19 @@ int sisic_groupnorm_finalize(sisic_ctx*, const float* stats0, int c0, int slots0
                              const float* gamma, const float* beta,
                              float* scale, float* shift, void* stream);
 
+/* sisic_conv2d(args) whose launch also CARRIES the finalisation sisic_groupnorm_finalize(stats0 .. shift) would run, as extra
+ * workgroups ahead of the convolution's own: for a GroupNorm that neither reads this convolution's output nor feeds its
+ * prologue (a ResNet block's norm1 beside its 1x1 shortcut), so that it costs no launch.  Same bits as the two calls.
+ * *carried = 1 when the kernel chosen for `args` ran the jobs -- the bf16x3 1x1 kernels (their 32-pixel, 64-pixel and K-split
+ * forms) without a GroupNorm prologue; 0 when it did not: the convolution has run as sisic_conv2d would have, scale / shift are
+ * untouched and the caller runs sisic_groupnorm_finalize itself.  The partials' B need not be the convolution's.             */
+int sisic_conv2d_gn_rider(sisic_ctx*, const sisic_conv_args* args,
+                          const float* stats0, int c0, int slots0,
+                          const float* stats1, int c1, int slots1,
+                          int B, int HW, int groups, float eps,
+                          const float* gamma, const float* beta,
+                          float* scale, float* shift, int* carried, void* stream);
+
 /* Multi-head self-attention core (replaces scaled_dot_product_attention inside
  * diffusers' Attention, heads = C/head_dim, softmax in fp32, scale head_dim^-0.5).
  * qkv: dev [B,3*C,N] (q channels, then k, then v; channel = head*head_dim + d),

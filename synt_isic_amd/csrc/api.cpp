@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "gn_finalize.h"
 
 namespace sisic {
 
@@ -155,6 +156,20 @@ int sisic_groupnorm_finalize(sisic_ctx* ctx, const float* stats0, int c0, int sl
     SISIC_REQUIRE(ctx, "groupnorm_finalize: null context");
     return launch_gn_finalize(ctx, stats0, c0, slots0, stats1, c1, slots1, B, HW, groups, eps, gamma, beta, scale,
                               shift, static_cast<hipStream_t>(stream));
+}
+
+int sisic_conv2d_gn_rider(sisic_ctx* ctx, const sisic_conv_args* args, const float* stats0, int c0, int slots0,
+                          const float* stats1, int c1, int slots1, int B, int HW, int groups, float eps, const float* gamma,
+                          const float* beta, float* scale, float* shift, int* carried, void* stream) {
+    SISIC_REQUIRE(ctx && args && carried, "conv2d_gn_rider: null argument");
+    *carried = 0;
+    SISIC_REQUIRE(HW > 0, "conv2d_gn_rider: HW=%d", HW);
+    GnFinJob q{};
+    SISIC_TRY(make_gn_fin_job(&q, stats0, c0, slots0, stats1, c1, slots1, B, groups, eps, gamma, beta, scale, shift));
+    bool rode = false;
+    SISIC_TRY(launch_conv2d(ctx, *args, static_cast<hipStream_t>(stream), &q, &rode));
+    *carried = rode ? 1 : 0;
+    return SISIC_OK;
 }
 
 int sisic_groupnorm_stats(sisic_ctx* ctx, const float* in0, int c0, const float* in1, int c1, int B, int HW,

@@ -135,7 +135,11 @@ inline int64_t conv_packed_floats(int cout, int cin, int ksize) {
 }
 
 // launchers implemented in the .hip files
-int launch_conv2d(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
+// rider / carried (optional): a GroupNorm finalisation that is independent of this convolution (gn_finalize.h) runs as extra
+// workgroups of its launch where the chosen kernel offers that -- the bf16x3 1x1 kernels without a GroupNorm prologue.
+// *carried says whether THIS launch ran the jobs; false: nothing of the job was touched and the caller launches it itself.
+struct GnFinJob;
+int launch_conv2d(sisic_ctx*, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider = nullptr, bool* carried = nullptr);
 int launch_conv_smallcout(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
 // conv_winograd.hip: F(2x2,3x3) for 3x3 stride-1 convolutions
 int launch_score_head_bwd(sisic_ctx*, const float* logits, const float* fc_w, const float* act, float* g, int B, int C,
@@ -158,7 +162,8 @@ int conv_pointwise_stats_slots(const sisic_conv_args& a);
 int launch_conv_pointwise(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
 // conv_pointwise_bf3.hip: the same GEMM with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 28)
 bool conv_pointwise_bf3_applicable(const sisic_conv_args& a);
-int launch_conv_pointwise_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
+int launch_conv_pointwise_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider = nullptr,
+                              bool* carried = nullptr);
 // conv_s2_bf3.hip: 3x3 stride-2 convolutions with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 36); the split
 // filter (conv_s2_pack_bf3_elem, pack_device.h) travels in sisic_conv_args.w_winograd
 bool conv_s2_bf3_applicable(const sisic_conv_args& a);
@@ -170,6 +175,10 @@ int launch_conv_s2_pack(sisic_ctx*, const float* w, int Cout, int Cin, float* ou
 int launch_gn_finalize(sisic_ctx*, const float* st0, int c0, int slots0, const float* st1, int c1, int slots1, int B,
                        int HW, int groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,
                        hipStream_t s, float* mean_rstd = nullptr);
+// the same finalisation as a checked job (gn_finalize.h), and the stand-alone launch of one
+int make_gn_fin_job(GnFinJob* q, const float* st0, int c0, int slots0, const float* st1, int c1, int slots1, int B, int groups,
+                    float eps, const float* gamma, const float* beta, float* scale, float* shift, float* mean_rstd = nullptr);
+int launch_gn_finalize_job(sisic_ctx*, const GnFinJob& q, hipStream_t s);
 int launch_conv_winograd(sisic_ctx*, const sisic_conv_args& a, const float* u_packed, int cfg, hipStream_t s);
 int launch_winograd_pack(sisic_ctx*, const float* w, int Cout, int Cin, float* packed, hipStream_t s);
 int64_t winograd_packed_numel(int Cout, int Cin);

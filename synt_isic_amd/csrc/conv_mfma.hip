@@ -485,7 +485,8 @@ int launch_conv_pack(sisic_ctx*, const float* w, int Cout, int Cin, int k, float
 //           36: the bf16x3 kernel of conv_s2_bf3.hip
 //   1x1   : 21: 2,2,1,4,TW256 22: 1,1,2,2,TW64  23: 2,1,1,4,TW128
 //   1x1 s2: 31: 2,1,1,4,TW32  32: 2,1,1,4,TW16  33: 1,1,2,2,TW8      7x7 s2: 41: 2,1,1,4,TW32 (CIC 4)
-static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query);
+static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query, const GnFinJob* rider = nullptr,
+                           bool* carried = nullptr);
 
 // Winograd F(2x2,3x3) is taken for 3x3 stride-1 convolutions with transformed filters at hand: when forced by
 // tile_cfg 60..74 / 78 / 79 / 90 / 91, or automatically from 12x12 outputs up and (K-split form) at 8x8 (per-thread load offsets
@@ -571,9 +572,13 @@ bool conv_finalizes(const sisic_conv_args& a) {
     return ((reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.stats_out)) & 15) == 0;
 }
 
-int launch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s) { return dispatch_conv2d(ctx, a, s, nullptr); }
+int launch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider, bool* carried) {
+    return dispatch_conv2d(ctx, a, s, nullptr, rider, carried);
+}
 
-static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query) {
+static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query, const GnFinJob* rider,
+                           bool* carried) {
+    if (carried) *carried = false;            // set by the one launcher that runs rider jobs (conv_pointwise_bf3.hip); every other path leaves it
     SISIC_REQUIRE(a.in0 && a.w_packed && a.out, "conv2d: null tensor");
     SISIC_REQUIRE(a.B > 0 && a.Hin > 0 && a.Win > 0 && a.c0 > 0 && a.c1 >= 0 && a.Cout > 0, "conv2d: bad shape");
     SISIC_REQUIRE((a.c1 == 0) == (a.in1 == nullptr), "conv2d: in1/c1 mismatch");
@@ -652,7 +657,7 @@ static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t
         static const bool pwb_on = [] { const char* e = std::getenv("SISIC_POINTWISE_BF16X3"); return !e || std::atoi(e) != 0; }();
         if ((cfg == 0 && pwb_on && conv_pointwise_bf3_applicable(a)) || (cfg >= 28 && cfg <= 30) || cfg == 34 || cfg == 35) {
             if (slots_query) { *slots_query = conv_pointwise_stats_slots(a); return SISIC_OK; }
-            return launch_conv_pointwise_bf3(ctx, a, s);
+            return launch_conv_pointwise_bf3(ctx, a, s, rider, carried);
         }
         if ((cfg == 0 && pw_on && conv_pointwise_applicable(a)) || cfg == 20) {
             if (slots_query) { *slots_query = conv_pointwise_stats_slots(a); return SISIC_OK; }

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gn_finalize.h"
 
 namespace sisic {
 
@@ -49,6 +50,10 @@ struct PwbParams {
     float* out;
     float* stats;            // optional [B][Cout][HW / 32][4]
     int n_px, n_co_items, nitems, nwg, nchunks;
+    // rider (PRO == 0 instances of conv_pwb_kernel / conv_pwbk_kernel): the first n_rider_wg workgroups of the grid run the jobs
+    // of a GroupNorm finalisation that neither reads nor feeds this convolution (gn_finalize.h), four per workgroup, and leave
+    int n_rider_wg;
+    GnFinJob rider;
 };
 
 constexpr int PWB_WAVES = 4;             // waves (= independent work items) per workgroup
@@ -75,9 +80,19 @@ __device__ __forceinline__ float pwb_silu(float v) { return v * __builtin_amdgcn
 template <int PRO, int NB>
 __global__ void __launch_bounds__(64 * PWB_WAVES, 4) conv_pwb_kernel(const PwbParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    int L = blockIdx.x;
+    if constexpr (PRO == 0) {
+        // rider workgroups: the lowest block indices -- dispatched first, gone before the convolution's tail.  Nothing below
+        // (no LDS, no barrier) has started; the whole workgroup leaves.
+        if (L < p.n_rider_wg) {
+            gn_finalize_job(p.rider, L * GNF_WAVES + (int)(threadIdx.x >> 6), threadIdx.x & 63);
+            return;
+        }
+        L -= p.n_rider_wg;
+    }
     int wg;
     {   // XCD-aware bijective remap (conv_mfma.hip)
-        const int L = blockIdx.x, nwg = p.nwg;
+        const int nwg = p.nwg;
         const int xcd = L & 7, slot = L >> 3, q = nwg >> 3, r = nwg & 7;
         wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     }
@@ -353,9 +368,17 @@ __global__ void __launch_bounds__(64 * PWB_WAVES, 4) conv_pwb_kernel(const PwbPa
 template <int PRO>
 __global__ void __launch_bounds__(64 * PWB_WAVES, 4) conv_pwbk_kernel(const PwbParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    int L = blockIdx.x;
+    if constexpr (PRO == 0) {                 // rider workgroups first (conv_pwb_kernel): before any LDS use and the barrier below
+        if (L < p.n_rider_wg) {
+            gn_finalize_job(p.rider, L * GNF_WAVES + (int)(threadIdx.x >> 6), threadIdx.x & 63);
+            return;
+        }
+        L -= p.n_rider_wg;
+    }
     int item;
     {   // XCD-aware bijective remap (conv_mfma.hip)
-        const int L = blockIdx.x, nwg = p.nwg;
+        const int nwg = p.nwg;
         const int xcd = L & 7, slot = L >> 3, q = nwg >> 3, r = nwg & 7;
         item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     }
@@ -740,11 +763,12 @@ static int launch_pwbk(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     SISIC_REQUIRE(nitems > 0 && nitems < (int64_t(1) << 31), "conv2d(pointwise bf16x3, K-split): grid too large");
     p.nitems = (int)nitems;
     p.nwg = p.nitems;
+    SISIC_REQUIRE((int64_t)p.nwg + p.n_rider_wg < (int64_t(1) << 31), "conv2d(pointwise bf16x3, K-split): grid too large");
     const size_t lds = sizeof(float) * (size_t)(PWB_WAVES * 32 * 64 + (PRO ? 2 * Cin : 0));
     static std::atomic<uint64_t> opt{0};
     auto kern = conv_pwbk_kernel<PRO>;
     SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)lds, opt));
-    hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(64 * PWB_WAVES), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(p.n_rider_wg + p.nwg), dim3(64 * PWB_WAVES), lds, s, p);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -793,16 +817,18 @@ static int launch_pwb(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     SISIC_REQUIRE(nitems > 0 && nitems < (int64_t(1) << 31), "conv2d(pointwise bf16x3): grid too large");
     p.nitems = (int)nitems;
     p.nwg = (int)((nitems + PWB_WAVES - 1) / PWB_WAVES);
+    SISIC_REQUIRE((int64_t)p.nwg + p.n_rider_wg < (int64_t(1) << 31), "conv2d(pointwise bf16x3): grid too large");
     const size_t lds = PRO ? sizeof(float) * (size_t)(PWB_WAVES * 2 * Cin) : 0;
     static std::atomic<uint64_t> opt{0};
     auto kern = conv_pwb_kernel<PRO, NB>;
     SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)lds, opt));
-    hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(64 * PWB_WAVES), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(p.n_rider_wg + p.nwg), dim3(64 * PWB_WAVES), lds, s, p);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
-int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s) {
+int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider, bool* carried) {
+    if (carried) *carried = false;
     SISIC_REQUIRE(conv_pointwise_bf3_applicable(a), "conv2d(pointwise bf16x3): shape not supported by tile_cfg 28");
     PwbParams p{};
     const int Cin = a.c0 + a.c1;
@@ -815,6 +841,16 @@ int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStrea
     p.out = a.out; p.stats = a.stats_out;
     p.nchunks = Cin / 8;
     const int pro = a.gn_scale == nullptr ? 0 : (a.gn_silu ? 2 : 1);
+    // the rider's jobs go with the PRO == 0 instances of the two four-wave kernels (their workgroup is gn_finalize_kernel's: one job
+    // per wave); *carried only once such a launch has been made -- the caller never re-derives which kernel was chosen
+    static_assert(PWB_WAVES == GNF_WAVES, "a rider workgroup runs one finalisation job per wave");
+    auto with_rider = [&]() {
+        if (rider && carried && pro == 0) { p.rider = *rider; p.n_rider_wg = cdiv(rider->n_jobs, GNF_WAVES); }
+    };
+    auto done = [&](int rc) {
+        if (rc == SISIC_OK && p.n_rider_wg > 0) *carried = true;
+        return rc;
+    };
     // 64-pixel items where they give every SIMD at least two waves (1024 SIMDs), 32-pixel items otherwise: a lone wave has
     // nobody to hide its latencies.  (The choice depends on the batch; the bits of an output do not: its chain of MFMAs is the same.)
     // (tile_cfg 29 / 30 force the 32- / 64-pixel form: tests of their bit-equality)
@@ -828,7 +864,8 @@ int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStrea
         if (a.tile_cfg == 35 || (a.tile_cfg == 0 && ks_ok && p.HW <= 256 && a.Cout <= 256 && pwbk_on())) {
             if (pro == 2) return launch_pwbk<2>(ctx, p, Cin, s);
             if (pro == 1) return launch_pwbk<1>(ctx, p, Cin, s);
-            return launch_pwbk<0>(ctx, p, Cin, s);
+            with_rider();
+            return done(launch_pwbk<0>(ctx, p, Cin, s));
         }
     }
     // the staged form (tile_cfg 34 forces it) where a layer has 6 .. 12 channel items and enough 64-pixel workgroups for the chip
@@ -843,11 +880,13 @@ int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStrea
     if (wide) {
         if (pro == 2) return launch_pwb<2, 2>(ctx, p, Cin, s);
         if (pro == 1) return launch_pwb<1, 2>(ctx, p, Cin, s);
-        return launch_pwb<0, 2>(ctx, p, Cin, s);
+        with_rider();
+        return done(launch_pwb<0, 2>(ctx, p, Cin, s));
     }
     if (pro == 2) return launch_pwb<2, 1>(ctx, p, Cin, s);
     if (pro == 1) return launch_pwb<1, 1>(ctx, p, Cin, s);
-    return launch_pwb<0, 1>(ctx, p, Cin, s);
+    with_rider();
+    return done(launch_pwb<0, 1>(ctx, p, Cin, s));
 }
 
 }  // namespace sisic

@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 
+#include "gn_finalize.h"
 #include "unet_internal.h"
 
 using namespace sisic;
@@ -363,7 +364,9 @@ struct Fwd {
         }
     }
 
-    int gn(const Buf* x, const Buf* skip, const NormW& n) {
+    // defer (inference only): where the finalisation would be a launch of its own, hand it back as a job instead -- the caller
+    // has a neighbouring launch to carry it (resnet(): the shortcut) and runs it BEFORE anything reads the pair
+    int gn(const Buf* x, const Buf* skip, const NormW& n, GnFinJob* defer = nullptr, bool* deferred = nullptr) {
         gsc = u->gn_scale; gsh = u->gn_shift; gmr = nullptr; gnorm = &n;
         if (!tr && !skip && x->fin_norm == static_cast<const void*>(&n)) {     // finalized by its producer (conv below)
             gsc = x->fin_scale; gsh = x->fin_shift;
@@ -376,10 +379,16 @@ struct Fwd {
             SISIC_TRY(pool_get(u, (size_t)B * u->cfg.norm_groups * 2, &gmr));
             tr->grads_of_bufs.push_back(gsc); tr->grads_of_bufs.push_back(gsh); tr->grads_of_bufs.push_back(gmr);
         }
-        if (x->stats && (!skip || skip->stats))   // every producer left partials: no pass over the tensors
+        if (x->stats && (!skip || skip->stats)) { // every producer left partials: no pass over the tensors
+            if (defer && !tr) {
+                *deferred = true;
+                return make_gn_fin_job(defer, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
+                                       skip ? skip->slots : 0, B, u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh);
+            }
             return launch_gn_finalize(u->ctx, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
                                       skip ? skip->slots : 0, B, x->H * x->W, u->cfg.norm_groups, u->cfg.norm_eps,
                                       n.gamma, n.beta, gsc, gsh, s, gmr);
+        }
         return launch_gn_stats(u->ctx, x->p, x->C, skip ? skip->p : nullptr, skip ? skip->C : 0, B, x->H * x->W,
                                u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh, s, gmr);
     }
@@ -388,7 +397,8 @@ struct Fwd {
     int conv(const ConvW& c, const float* in0, int c0, const float* in1, int c1, int H, int W, int stride, int ups,
              bool gn_prologue, bool silu, const float* chan_bias, const float* residual, float* out,
              Buf* normed_later = nullptr, Buf* xb = nullptr, Buf* skipb = nullptr, Buf* resb = nullptr, Buf* outb = nullptr,
-             const AttnW* qkv_of = nullptr, const NormW* next_norm = nullptr) {
+             const AttnW* qkv_of = nullptr, const NormW* next_norm = nullptr, const GnFinJob* rider = nullptr,
+             bool* carried = nullptr) {
         sisic_conv_args a{};
         a.in0 = in0; a.c0 = c0; a.in1 = in1; a.c1 = c1;
         a.B = B; a.Hin = H; a.Win = W; a.upsample = ups; a.ksize = c.k; a.stride = stride;
@@ -440,7 +450,7 @@ struct Fwd {
             op.residual = resb; op.out = outb; op.out_ptr = out;
             tr->tape.push_back(op);
         }
-        return launch_conv2d(u->ctx, a, s);
+        return launch_conv2d(u->ctx, a, s, rider, carried);
     }
 
     // out = ResnetBlock2D(cat(x, skip)); consumes nothing (caller releases inputs)
@@ -451,14 +461,32 @@ struct Fwd {
         const int H = x->H, W = x->W;
         const int c1 = skip ? skip->C : 0;
         SISIC_REQUIRE(x->C + c1 == r.cin, "unet: resnet expects %d input channels, got %d", r.cin, x->C + c1);
-        SISIC_TRY(gn(x, skip, r.norm1));
+        // The 1x1 shortcut reads the raw block inputs only: it neither needs norm1 nor does conv1 need it.  In inference, where
+        // norm1's finalisation would be a launch of its own, the shortcut runs FIRST and carries the jobs as extra workgroups
+        // (conv_pointwise_bf3.hip); conv1, next in stream order, is the first reader of the pair.  The launcher says whether its
+        // kernel ran them (the f32 1x1 kernels, latency mode's tiles and shapes the bf16x3 kernels refuse do not): if not, the
+        // stand-alone launch follows.  (SISIC_GN_RIDER=0: the order and launches without any of this.)
+        GnFinJob fin{};
+        bool deferred = false;
+        SISIC_TRY(gn(x, skip, r.norm1, (u->gn_rider && !tr && r.shortcut.k) ? &fin : nullptr, &deferred));
+        Buf* sc = nullptr;
+        if (deferred) {
+            bool carried = false;
+            sc = make(r.cout, H, W, &rc); SISIC_TRY(rc);
+            SISIC_TRY(conv(r.shortcut, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, false, false, nullptr,
+                           nullptr, sc->p, nullptr, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, sc, nullptr, nullptr,
+                           &fin, &carried));
+            if (!carried) SISIC_TRY(launch_gn_finalize_job(u->ctx, fin, s));
+        }
         Buf* h = make(r.cout, H, W, &rc); SISIC_TRY(rc);
         SISIC_TRY(conv(r.conv1, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, true, true,
                        tproj + r.temb_off, nullptr, h->p, h, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, h, nullptr, &r.norm2));
         const float* residual = x->p;
         Buf* resb = const_cast<Buf*>(x);
-        Buf* sc = nullptr;
-        if (r.shortcut.k) {
+        if (sc) {
+            residual = sc->p;
+            resb = sc;
+        } else if (r.shortcut.k) {
             sc = make(r.cout, H, W, &rc); SISIC_TRY(rc);
             SISIC_TRY(conv(r.shortcut, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, false, false, nullptr,
                            nullptr, sc->p, nullptr, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, sc));
@@ -671,6 +699,7 @@ int sisic_unet_create(sisic_ctx* ctx, const sisic_unet_config* cfg, sisic_unet**
     u->freqs.assign(cfg->freqs, cfg->freqs + cfg->n_freqs);
     if (const char* e = std::getenv("SISIC_WINOGRAD")) u->use_winograd = std::atoi(e) != 0;
     if (const char* e = std::getenv("SISIC_FUSED_GN")) u->fuse_gn = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SISIC_GN_RIDER")) u->gn_rider = std::atoi(e) != 0;
     if (const char* e = std::getenv("SISIC_GRAPH")) u->graph_mode = std::atoi(e) != 0 ? 1 : 0;
     u->cfg.freqs = nullptr;
     const int rc = describe(u);

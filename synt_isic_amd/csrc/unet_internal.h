@@ -193,6 +193,8 @@ struct sisic_unet {
     bool use_winograd = true;
     bool fuse_gn = true;            // GroupNorm statistics from convolution epilogues where the kernel offers them
                                     // (SISIC_FUSED_GN=0 in the environment: always the stand-alone statistics pass)
+    bool gn_rider = true;           // inference: a ResNet block's norm1 finalisation rides on its shortcut's launch where the
+                                    // kernel carries it (SISIC_GN_RIDER=0 in the environment: always a launch of its own)
     // SISIC_WINOGRAD=0 in the environment keeps every 3x3 on the direct kernel
     float* eps_buf = nullptr;    // sampling loop scratch [B,C,H,W]
     size_t eps_floats = 0;

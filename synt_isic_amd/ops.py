@@ -147,6 +147,41 @@ def groupnorm_finalize(stats: torch.Tensor, hw: int, gamma: torch.Tensor, beta: 
     return scale, shift
 
 
+def conv2d_gn_rider(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: int, stats: torch.Tensor, hw: int,
+                    gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, *, stats2: Optional[torch.Tensor] = None,
+                    bias=None, x2=None, gn_scale=None, gn_shift=None, gn_silu=False, tile_cfg=0, w_winograd=None,
+                    scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None):
+    """sisic_conv2d_gn_rider: the stride-1 convolution of ``conv2d`` whose launch also carries the GroupNorm finalisation of
+    ``groupnorm_finalize(stats, hw, gamma, beta, groups, eps, stats2)`` where the chosen kernel can.  Returns
+    ``(out, scale, shift, carried)``; with ``carried == 0`` the launch did not run the jobs and ``scale`` / ``shift`` (the
+    tensors passed in, or fresh uninitialised ones) are as they were."""
+    lib = _lib.load()
+    B, c0, H, W = x.shape
+    c1 = 0 if x2 is None else x2.shape[1]
+    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    a = ConvArgs()
+    a.in0 = _ptr(x, "x"); a.in1 = _ptr(x2, "x2"); a.c0 = c0; a.c1 = c1
+    a.B = B; a.Hin = H; a.Win = W
+    a.upsample = 0; a.ksize = ksize; a.stride = 1
+    a.w_packed = _ptr(w_packed, "w_packed"); a.bias = _ptr(bias, "bias"); a.Cout = cout
+    a.gn_scale = _ptr(gn_scale, "gn_scale"); a.gn_shift = _ptr(gn_shift, "gn_shift"); a.gn_silu = int(gn_silu)
+    a.out = out.data_ptr(); a.tile_cfg = tile_cfg
+    a.w_winograd = _ptr(w_winograd, "w_winograd")
+    Bs, s0, slots0, _ = stats.shape
+    s1, slots1 = (0, 0) if stats2 is None else (stats2.shape[1], stats2.shape[2])
+    if scale is None:
+        scale = torch.empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
+    if shift is None:
+        shift = torch.empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
+    if tuple(scale.shape) != (Bs, s0 + s1) or tuple(shift.shape) != (Bs, s0 + s1):
+        raise ValueError(f"scale / shift must be {(Bs, s0 + s1)} tensors")
+    carried = C.c_int(0)
+    check(lib.sisic_conv2d_gn_rider(context(x.device), C.byref(a), _ptr(stats, "stats"), s0, slots0, _ptr(stats2, "stats2"),
+                                    s1, slots1, Bs, hw, groups, float(eps), _ptr(gamma, "gamma"), _ptr(beta, "beta"),
+                                    _ptr(scale, "scale"), _ptr(shift, "shift"), C.byref(carried), _stream(x.device)))
+    return out, scale, shift, carried.value
+
+
 def groupnorm_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float,
                     x2: Optional[torch.Tensor] = None):
     lib = _lib.load()
