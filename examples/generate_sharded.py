@@ -4,7 +4,7 @@ images to rank 0 (the reference loops over images one at a
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \\
         examples/generate_sharded.py --count 512 --T 1000 --size 64 --class-name NV [--weights unet_NV_best.pth] \\
-        [--out images.npy] [--noise host|device]
+        [--out images.npy] [--noise host|device] [--scheduler ddpm|ddim] [--eta 0.0]
 
 Every image's chain depends only on its own seed, so the gathered result is bit-identical to sampling the same
 seeds on one GPU (tests/test_gpu_sampler.py::test_batch_and_shard_independence_small).
@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--noise", choices=("host", "device"), default="host",
                     help="host: one CPU torch.Generator per image (the default); device: x_T from torch's device generator "
                          "and z_t generated in the step kernel -- no host RNG, so the ranks do not compete for CPUs")
+    ap.add_argument("--scheduler", choices=("ddpm", "ddim"), default="ddpm",
+                    help="the step rule: DDPM ancestral sampling (the default), or DDIM -- the rule made for --T of 20 to 100")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM only: 0 is deterministic, 1 has the DDPM rule's sigma")
     a = ap.parse_args()
 
     rank, world, local = sdist.init_from_env()
@@ -53,14 +56,16 @@ def main():
     t0 = time.perf_counter()
     blocks = []
     for i in range(0, len(mine), a.batch):
-        blocks.append(s.generate_seeds(a.class_name, mine[i:i + a.batch], a.T, (a.size, a.size), noise=a.noise).images)
+        blocks.append(s.generate_seeds(a.class_name, mine[i:i + a.batch], a.T, (a.size, a.size), noise=a.noise,
+                                       scheduler=a.scheduler, eta=a.eta).images)
     local_images = torch.cat(blocks) if blocks else torch.empty((0, a.size, a.size, 3), dtype=torch.uint8, device=dev)
     images = sdist.gather_images(local_images, a.count, dst=0)
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     if rank == 0:
         arr = images.cpu().numpy()
-        print(f"{a.count} images {a.size}x{a.size}, T={a.T}, {world} GPU(s), {a.noise} noise: {dt:.2f} s -> {a.count / dt:.3f} images/sec; "
+        rule = f", ddim eta={a.eta:g}" if a.scheduler == "ddim" else ""
+        print(f"{a.count} images {a.size}x{a.size}, T={a.T}, {world} GPU(s), {a.noise} noise{rule}: {dt:.2f} s -> {a.count / dt:.3f} images/sec; "
               f"sha256 {hashlib.sha256(arr.tobytes()).hexdigest()[:16]}", flush=True)
         if a.out:
             np.save(a.out, arr)

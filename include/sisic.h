@@ -192,6 +192,29 @@ int sisic_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z
                     int64_t n, float sqrt_beta_prod, float sqrt_alpha_prod, float c0, float c1,
                     float sigma, float clip, void* stream);
 
+/* The scheduler-step rules of the sampling loop and what the five floats of a step's table row mean under each:
+ *   SISIC_RULE_DDPM  {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma}          sisic_ddpm_step above (ancestral sampling)
+ *   SISIC_RULE_DDIM  {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma}   sisic_ddim_step below
+ * rule_flags: SISIC_RULE_FLAG_CLIPPED_OUTPUT (DDIM only: use_clipped_model_output); 0 under DDPM.                       */
+#define SISIC_RULE_DDPM 0
+#define SISIC_RULE_DDIM 1
+#define SISIC_RULE_FLAG_CLIPPED_OUTPUT 1
+
+/* Fused DDIMScheduler.step (the published rule for epsilon prediction), elementwise over n floats.
+ * With abar_t = alphas_cumprod[t], abar_prev = alphas_cumprod[prev_t] (or the final alpha when prev_t < 0),
+ * variance = ((1 - abar_prev) / (1 - abar_t)) * (1 - abar_t / abar_prev) and sigma = eta * variance^0.5, the row is
+ *   sqrt_beta_prod = (1 - abar_t)^0.5, sqrt_alpha_prod = abar_t^0.5, c_prev = abar_prev^0.5,
+ *   c_dir = (1 - abar_prev - sigma^2)^0.5, sigma
+ * and the step
+ *   x0  = clamp((x - sqrt_beta_prod*eps)/sqrt_alpha_prod, -clip, clip)   (clip<=0: no clamp)
+ *   pe  = eps, or (x - sqrt_alpha_prod*x0)/sqrt_beta_prod when use_clipped_model_output != 0
+ *   out = (c_prev*x0 + c_dir*pe) + sigma*z                               (z==NULL or sigma==0: no noise)
+ * evaluated in exactly that fp32 operation order (no FMA contraction).  out may be x.  sqrt_alpha_prod != 0, and
+ * sqrt_beta_prod != 0 when use_clipped_model_output is set.                                                             */
+int sisic_ddim_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* out,
+                    int64_t n, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev, float c_dir,
+                    float sigma, float clip, int use_clipped_model_output, void* stream);
+
 /* De-normalise image_generator.py:441-447: [B,3,H,W] fp32 -> uint8 [B,H,W,3],
  * trunc(clamp((x+1)/2,0,1)*255).                                                   */
 int sisic_denorm_u8(sisic_ctx*, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream);
@@ -297,6 +320,26 @@ int sisic_sample_frames_rng(sisic_unet*, float* x, int B, int H, int W, int T, c
                             const float* coef, float clip, const uint64_t* seeds, int step0, float* traj,
                             const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
                             void* stream);
+/* sisic_ddim_step with z generated in the kernel: sisic_ddpm_step_rng's arguments and alignment rules, the DDIM row.     */
+int sisic_ddim_step_rng(sisic_ctx*, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
+                        float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream);
+/* sisic_sample_frames and sisic_sample_frames_rng under a chosen step rule:
+ *   for i in 0..T-1:  eps = unet(x, t[i]);  x = step_rule(eps, x, z[i], coef[i])
+ * rule: SISIC_RULE_DDPM (what the entries above run) or SISIC_RULE_DDIM; rule_flags: SISIC_RULE_FLAG_* of that rule.
+ * coef: host float [T*5], the rows of that rule (see SISIC_RULE_* above).  Under either rule the steps with sigma != 0, and
+ * only those, consume a noise row (buffer) or draw (generated noise): a DDIM run at eta = 0 has none, and takes noise NULL
+ * or a buffer of no rows.  In graph mode the rule and its flags are part of what a captured step is, like the noise source:
+ * a DDPM step is never replayed for a DDIM call or the other way round, and alternating re-captures
+ * (sisic_unet_graph_builds).  Everything else as documented at sisic_sample_frames / sisic_sample_frames_rng.            */
+int sisic_sample_frames_rule(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps,
+                             const float* coef, float clip, int rule, int rule_flags, const float* noise, float* traj,
+                             const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
+                             void* stream);
+int sisic_sample_frames_rule_rng(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps,
+                                 const float* coef, float clip, int rule, int rule_flags, const uint64_t* seeds, int step0,
+                                 float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel,
+                                 int* steps_done, void* stream);
 
 /* ---- training step (diffusion/train_diffusion.py:201-266) -----------------------------------
  * fp32 throughout.  The reference wraps the forward in torch.cuda.amp.autocast() (fp16 matmuls/convolutions) and scales the

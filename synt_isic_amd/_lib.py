@@ -22,6 +22,11 @@ SISIC_EHIP = -2
 SISIC_ESTATE = -3
 SISIC_ECANCEL = -4
 
+# step rules of the sampling loop (SISIC_RULE_*) and the DDIM rule's flag
+RULE_DDPM = 0
+RULE_DDIM = 1
+RULE_FLAG_CLIPPED_OUTPUT = 1
+
 c_float_p = C.POINTER(C.c_float)
 c_int64_p = C.POINTER(C.c_int64)
 
@@ -126,6 +131,18 @@ SIGNATURES = {
     "sisic_sample_frames_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                           C.c_float, C.POINTER(C.c_uint64), C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                           C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "sisic_ddim_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                      C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_int, C.c_void_p]),
+    "sisic_sample_frames_rule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
+                                           C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                           C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_sample_frames_rule_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p,
+                                               c_float_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int,
+                                               C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.c_void_p]),
     "sisic_unet_train_begin": (C.c_int, [C.c_void_p]),
     "sisic_unet_train_end": (C.c_int, [C.c_void_p]),
     "sisic_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

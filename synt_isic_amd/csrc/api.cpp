@@ -189,8 +189,16 @@ int sisic_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
                     float sqrt_beta_prod, float sqrt_alpha_prod, float c0, float c1, float sigma, float clip,
                     void* stream) {
     SISIC_REQUIRE(ctx, "ddpm_step: null context");
-    return launch_ddpm_step(ctx, eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip,
-                            static_cast<hipStream_t>(stream));
+    return launch_step(ctx, STEP_RULE_DDPM, 0, eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip,
+                       static_cast<hipStream_t>(stream));
+}
+
+int sisic_ddim_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n,
+                    float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev, float c_dir, float sigma, float clip,
+                    int use_clipped_model_output, void* stream) {
+    SISIC_REQUIRE(ctx, "ddim_step: null context");
+    return launch_step(ctx, STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x, z, out, n,
+                       sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_noise_fill(sisic_ctx* ctx, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
@@ -209,8 +217,17 @@ int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float*
                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
                         float c1, float sigma, float clip, void* stream) {
     SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddpm_step_rng: null context or empty batch");
-    return launch_ddpm_step_rng(ctx, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod,
-                                sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
+    return launch_step_rng(ctx, STEP_RULE_DDPM, 0, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step,
+                           sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
+}
+
+int sisic_ddim_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
+                        float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddim_step_rng: null context or empty batch");
+    return launch_step_rng(ctx, STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x, out,
+                           (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod, sqrt_alpha_prod, c_prev,
+                           c_dir, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {

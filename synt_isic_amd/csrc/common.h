@@ -189,21 +189,27 @@ int launch_gn_stats(sisic_ctx*, const float* in0, int c0, const float* in1, int 
                     float eps, const float* gamma, const float* beta, float* scale, float* shift, hipStream_t s,
                     float* mean_rstd = nullptr);
 int launch_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s);
-int launch_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* out, int64_t n,
-                     float sb, float sa, float c0, float c1, float sigma, float clip, hipStream_t s);
+// The scheduler-step rules of the sampling loop (elementwise.hip; sisic.h SISIC_RULE_*): the row of a step is
+// {sb, sa, c2, c3, sigma} with (c2, c3) = DDPM (c0, c1) or DDIM (c_prev, c_dir).  flags: STEP_FLAG_CLIPPED_OUTPUT (DDIM only).
+enum StepRule { STEP_RULE_DDPM = SISIC_RULE_DDPM, STEP_RULE_DDIM = SISIC_RULE_DDIM };
+enum StepFlag { STEP_FLAG_CLIPPED_OUTPUT = SISIC_RULE_FLAG_CLIPPED_OUTPUT };
+// a known rule, flags it has, sa != 0, and sb != 0 where the rule divides by it
+int check_step_row(int rule, int flags, float sb, float sa);
+int launch_step(sisic_ctx*, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
+                float sb, float sa, float c2, float c3, float sigma, float clip, hipStream_t s);
 // graph-replayed sampling loop (elementwise.hip): per-step parameters selected on the device by a step index
 size_t loop_state_bytes();     // {int step; int step_base; const float* noise_base}
 int launch_loop_select_row(sisic_ctx*, const float* table, int R, const void* state, float* out, hipStream_t s);
 int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s);
-int launch_ddpm_step_indexed(sisic_ctx*, const float* eps, float* x, int64_t n, const void* state, const float* coef,
-                             const int* zrow, float clip, hipStream_t s);
+int launch_step_indexed(sisic_ctx*, int rule, int flags, const float* eps, float* x, int64_t n, const void* state,
+                        const float* coef, const int* zrow, float clip, hipStream_t s);
 // device noise (noise_device.h): the step with z generated in the kernel from the images' seeds (device
 // uint64 [n / n_per_image]), eager and graph-replayed forms; the blocks as a buffer of normals or raw words (HOST seeds)
-int launch_ddpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* out, int64_t n, int64_t n_per_image,
-                         const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
-                         float clip, hipStream_t s);
-int launch_ddpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, int64_t n, int64_t n_per_image, const void* state,
-                                 const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
+int launch_step_rng(sisic_ctx*, int rule, int flags, const float* eps, const float* x, float* out, int64_t n,
+                    int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c2, float c3,
+                    float sigma, float clip, hipStream_t s);
+int launch_step_indexed_rng(sisic_ctx*, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
+                            const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
 int launch_noise_fill(sisic_ctx*, void* out, int B, int64_t n_per_image, const uint64_t* seeds_host, uint32_t step,
                       uint32_t tag, bool bits, hipStream_t s);
 int launch_denorm_u8(sisic_ctx*, const float* x, uint8_t* out, int B, int C, int H, int W, hipStream_t s, int form = 0);

@@ -1,5 +1,6 @@
 // elementwise.hip -- the HBM-bound and tiny kernels of the sampling loop:
 //   * ddpm_step_kernel  : fused DDPMScheduler.step, bit-exact vs torch CPU
+//   * ddim_step_kernel  : fused DDIMScheduler.step (epsilon prediction), bit-exact vs torch CPU
 //   * denorm_u8_kernel  : clamp((x+1)/2,0,1)*255 -> uint8 HWC (image_generator.py:441-447)
 //   * temb_mlp_kernel   : sinusoidal timestep embedding -> Linear -> SiLU -> Linear -> SiLU
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
@@ -24,8 +25,42 @@ __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, f
     return r;
 }
 
+// ---- DDIM step -------------------------------------------------------------------------
+// The published DDIMScheduler.step for epsilon prediction, under the same rounding rules as ddpm_one.  The row of a step is
+// {sb = (1-abar_t)^.5, sa = abar_t^.5, c_prev = abar_prev^.5, c_dir = (1 - abar_prev - sigma^2)^.5, sigma = eta * variance^.5}.
+// CLIPPED (use_clipped_model_output): the direction term uses the epsilon re-derived from the clamped x0.
+template <bool CLIPPED>
+__device__ __forceinline__ float ddim_one(float e, float x, float z, float sb, float sa, float c_prev, float c_dir,
+                                          float sigma, float clip, bool noise) {
+#pragma clang fp contract(off)
+    float x0 = (x - sb * e) / sa;
+    if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+    float pe = e;
+    if constexpr (CLIPPED) pe = (x - sa * x0) / sb;
+    float r = c_prev * x0 + c_dir * pe;
+    if (noise) r = r + sigma * z;
+    return r;
+}
+
+// The step rule as a functor: the row of five scalars and the clip range, applied to one element.  step_body is instantiated
+// once per rule and noise source, so no element pays for a branch on the rule.
+struct DdpmRule {
+    float sb, sa, c0, c1, sigma, clip;
+    __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
+        return ddpm_one(e, x, z, sb, sa, c0, c1, sigma, clip, noise);
+    }
+};
+
+template <bool CLIPPED>
+struct DdimRule {
+    float sb, sa, c_prev, c_dir, sigma, clip;
+    __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
+        return ddim_one<CLIPPED>(e, x, z, sb, sa, c_prev, c_dir, sigma, clip, noise);
+    }
+};
+
 // Where a step's z comes from: a buffer the caller filled, or the counter-based generator of noise_device.h (the device-noise
-// contract).  Both feed the same ddpm_one, so the step's arithmetic after z does not depend on the source.
+// contract).  Both feed the same rule, so the step's arithmetic after z does not depend on the source.
 struct BufferNoise {
     const float* __restrict__ z;
     __device__ __forceinline__ bool present() const { return z != nullptr; }
@@ -51,10 +86,10 @@ struct PhiloxNoise {
 };
 
 // out may alias x (the loop steps in place): every element is read before it is written, by the thread that writes it
-template <class Z>
-__device__ __forceinline__ void ddpm_step_body(const float* __restrict__ eps, const float* x, float* out, int64_t n, float sb,
-                                               float sa, float c0, float c1, float sigma, float clip, bool vec4, const Z zs) {
-    const bool noise = zs.present() && (sigma != 0.0f);
+template <class R, class Z>
+__device__ __forceinline__ void step_body(const float* __restrict__ eps, const float* x, float* out, int64_t n, bool vec4,
+                                          const R rule, const Z zs) {
+    const bool noise = zs.present() && (rule.sigma != 0.0f);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (vec4) {
@@ -67,17 +102,15 @@ __device__ __forceinline__ void ddpm_step_body(const float* __restrict__ eps, co
             float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (noise) zv = zs.get4(i);
             float4 r;
-            r.x = ddpm_one(e.x, xv.x, zv.x, sb, sa, c0, c1, sigma, clip, noise);
-            r.y = ddpm_one(e.y, xv.y, zv.y, sb, sa, c0, c1, sigma, clip, noise);
-            r.z = ddpm_one(e.z, xv.z, zv.z, sb, sa, c0, c1, sigma, clip, noise);
-            r.w = ddpm_one(e.w, xv.w, zv.w, sb, sa, c0, c1, sigma, clip, noise);
+            r.x = rule(e.x, xv.x, zv.x, noise);
+            r.y = rule(e.y, xv.y, zv.y, noise);
+            r.z = rule(e.z, xv.z, zv.z, noise);
+            r.w = rule(e.w, xv.w, zv.w, noise);
             o4[i] = r;
         }
-        for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
-            out[i] = ddpm_one(eps[i], x[i], noise ? zs.get1(i) : 0.f, sb, sa, c0, c1, sigma, clip, noise);
+        for (int64_t i = (n4 << 2) + t0; i < n; i += stride) out[i] = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, noise);
     } else {
-        for (int64_t i = t0; i < n; i += stride)
-            out[i] = ddpm_one(eps[i], x[i], noise ? zs.get1(i) : 0.f, sb, sa, c0, c1, sigma, clip, noise);
+        for (int64_t i = t0; i < n; i += stride) out[i] = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, noise);
     }
 }
 
@@ -85,7 +118,7 @@ __global__ void __launch_bounds__(256)
 ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
                  float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
                  int vec4) {
-    ddpm_step_body(eps, x, out, n, sb, sa, c0, c1, sigma, clip, vec4 != 0, BufferNoise{z});
+    step_body(eps, x, out, n, vec4 != 0, DdpmRule{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
 }
 
 // the same step with z generated in the kernel (sisic_sample_frames_rng, eager form)
@@ -94,13 +127,49 @@ ddpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, 
                      const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
                      float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    ddpm_step_body(eps, x, out, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
+    step_body(eps, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule{sb, sa, c0, c1, sigma, clip}, zs);
 }
 
-int launch_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n, float sb,
-                     float sa, float c0, float c1, float sigma, float clip, hipStream_t s) {
-    SISIC_REQUIRE(eps && x && out && n > 0, "ddpm_step: null tensor or empty");
-    SISIC_REQUIRE(sa != 0.0f, "ddpm_step: sqrt_alpha_prod is zero");
+// the DDIM rule in the same two forms
+template <bool CLIPPED>
+__global__ void __launch_bounds__(256)
+ddim_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* out, int64_t n, float sb,
+                 float sa, float c_prev, float c_dir, float sigma, float clip, int vec4) {
+    step_body(eps, x, out, n, vec4 != 0, DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
+}
+
+template <bool CLIPPED>
+__global__ void __launch_bounds__(256)
+ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
+                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c_prev, float c_dir,
+                     float sigma, float clip, int vec4) {
+    const PhiloxNoise zs{seeds, n_per_image, step};
+    step_body(eps, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
+}
+
+static const char* rule_name(int rule) { return rule == STEP_RULE_DDIM ? "ddim_step" : "ddpm_step"; }
+
+// the rule and its flags as the C ABI passes them; the divisors of the rule's row when they are launch arguments
+static int check_rule(int rule, int flags) {
+    SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM, "step rule %d (0 = DDPM, 1 = DDIM)", rule);
+    SISIC_REQUIRE((flags & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || flags == 0),
+                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM: none)", rule_name(rule), flags);
+    return SISIC_OK;
+}
+
+int check_step_row(int rule, int flags, float sb, float sa) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(sa != 0.0f, "%s: sqrt_alpha_prod is zero", rule_name(rule));
+    SISIC_REQUIRE(!(flags & STEP_FLAG_CLIPPED_OUTPUT) || sb != 0.0f,
+                  "%s: sqrt_beta_prod is zero with use_clipped_model_output", rule_name(rule));
+    return SISIC_OK;
+}
+
+int launch_step(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
+                float sb, float sa, float c2, float c3, float sigma, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps && x && out && n > 0, "%s: null tensor or empty", rule_name(rule));
+    SISIC_TRY(check_step_row(rule, flags, sb, sa));
     const bool noise = z != nullptr && sigma != 0.0f;
     ProfileScope prof(ctx, s, PK_DDPM, (noise ? 16.0 : 12.0) * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) |
@@ -108,8 +177,15 @@ int launch_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const flo
     const int vec4 = (al & 15) == 0;
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c0, c1, sigma, clip,
-                       vec4);
+    if (rule == STEP_RULE_DDPM)
+        hipLaunchKernelGGL(ddpm_step_kernel, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma, clip,
+                           vec4);
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+        hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
+                           clip, vec4);
+    else
+        hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
+                           clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -117,20 +193,28 @@ int launch_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const flo
 // counter word 0 of a block is its index in the image: 32 bits
 static constexpr int64_t NOISE_MAX_PER_IMAGE = (int64_t)1 << 34;
 
-int launch_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int64_t n, int64_t n_per_image,
-                         const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
-                         float clip, hipStream_t s) {
-    SISIC_REQUIRE(eps && x && out && seeds_dev && n > 0, "ddpm_step_rng: null tensor or empty");
+int launch_step_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* x, float* out, int64_t n,
+                    int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c2, float c3,
+                    float sigma, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps && x && out && seeds_dev && n > 0, "%s_rng: null tensor or empty", rule_name(rule));
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "ddpm_step_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
-    SISIC_REQUIRE(sa != 0.0f, "ddpm_step_rng: sqrt_alpha_prod is zero");
+                  "%s_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
+    SISIC_TRY(check_step_row(rule, flags, sb, sa));
     ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out);
     const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(ddpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step, sb,
-                       sa, c0, c1, sigma, clip, vec4);
+    if (rule == STEP_RULE_DDPM)
+        hipLaunchKernelGGL(ddpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step, sb,
+                           sa, c2, c3, sigma, clip, vec4);
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+        hipLaunchKernelGGL(ddim_step_rng_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev,
+                           step, sb, sa, c2, c3, sigma, clip, vec4);
+    else
+        hipLaunchKernelGGL(ddim_step_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev,
+                           step, sb, sa, c2, c3, sigma, clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -140,33 +224,65 @@ int launch_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float
 // argument: the loop keeps {step index, noise base pointer} and its per-step tables (coefficients, noise row of the step
 // or -1) in device memory; this kernel selects its row, ddpm_advance_kernel moves the index on.  Nothing that changes from
 // call to call either: a generated-noise call's first step index is `step_base`, and its seeds lie in a library-owned
-// buffer whose address is part of the captured launch.
+// buffer whose address is part of the captured launch.  The rule and its flag choose the kernel, so they are part of what a
+// captured step is (LoopKey).
 struct LoopState {
     int step;
     int step_base;            // generated noise: the Philox step index is step_base + step (0 in buffer-noise calls)
     const float* noise;       // base of the [n_noise, n] noise rows of this call
 };
 
+// R{sb, sa, c2, c3, sigma, clip}: DdpmRule or DdimRule<>, the row of the current step
+template <class R>
+__device__ __forceinline__ R loop_rule(const float* __restrict__ coef, int step, float clip) {
+    return R{coef[5 * step + 0], coef[5 * step + 1], coef[5 * step + 2], coef[5 * step + 3], coef[5 * step + 4], clip};
+}
+
+template <class R>
+__device__ __forceinline__ void step_indexed_body(const float* __restrict__ eps, float* x, int64_t n,
+                                                  const LoopState* __restrict__ st, const float* __restrict__ coef,
+                                                  const int* __restrict__ zrow, float clip, int vec4) {
+    const int step = st->step;
+    const int zr = zrow[step];
+    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
+    step_body(eps, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+}
+
+template <class R>
+__device__ __forceinline__ void step_indexed_rng_body(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
+                                                      const LoopState* __restrict__ st, const float* __restrict__ coef,
+                                                      const uint64_t* __restrict__ seeds, float clip, int vec4) {
+    const int step = st->step;
+    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+    step_body(eps, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+}
+
 __global__ void __launch_bounds__(256)
 ddpm_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
                          const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    const int step = st->step;
-    const float sb = coef[5 * step + 0], sa = coef[5 * step + 1], c0 = coef[5 * step + 2], c1 = coef[5 * step + 3],
-                sigma = coef[5 * step + 4];
-    const int zr = zrow[step];
-    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    ddpm_step_body(eps, x, x, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
+    step_indexed_body<DdpmRule>(eps, x, n, st, coef, zrow, clip, vec4);
 }
 
 __global__ void __launch_bounds__(256)
 ddpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
                              const LoopState* __restrict__ st, const float* __restrict__ coef,
                              const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    const int step = st->step;
-    const float sb = coef[5 * step + 0], sa = coef[5 * step + 1], c0 = coef[5 * step + 2], c1 = coef[5 * step + 3],
-                sigma = coef[5 * step + 4];
-    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    ddpm_step_body(eps, x, x, n, sb, sa, c0, c1, sigma, clip, vec4 != 0 && zs.vec_ok(), zs);
+    step_indexed_rng_body<DdpmRule>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
+}
+
+template <bool CLIPPED>
+__global__ void __launch_bounds__(256)
+ddim_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
+                         const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
+    step_indexed_body<DdimRule<CLIPPED>>(eps, x, n, st, coef, zrow, clip, vec4);
+}
+
+template <bool CLIPPED>
+__global__ void __launch_bounds__(256)
+ddim_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
+                             const LoopState* __restrict__ st, const float* __restrict__ coef,
+                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
+    step_indexed_rng_body<DdimRule<CLIPPED>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
 }
 
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
@@ -190,32 +306,48 @@ int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s) {
     return SISIC_OK;
 }
 
-int launch_ddpm_step_indexed(sisic_ctx* ctx, const float* eps, float* x, int64_t n, const void* state, const float* coef,
-                             const int* zrow, float clip, hipStream_t s) {
-    SISIC_REQUIRE(eps && x && state && coef && zrow && n > 0, "ddpm_step_indexed: null argument");
+int launch_step_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, const void* state,
+                        const float* coef, const int* zrow, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps && x && state && coef && zrow && n > 0, "%s_indexed: null argument", rule_name(rule));
     ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
     const int vec4 = (al & 15) == 0 && (n & 3) == 0;
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(ddpm_step_indexed_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, static_cast<const LoopState*>(state), coef,
-                       zrow, clip, vec4);
+    const LoopState* st = static_cast<const LoopState*>(state);
+    if (rule == STEP_RULE_DDPM)
+        hipLaunchKernelGGL(ddpm_step_indexed_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+        hipLaunchKernelGGL(ddim_step_indexed_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
+    else
+        hipLaunchKernelGGL(ddim_step_indexed_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
-int launch_ddpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, int64_t n, int64_t n_per_image, const void* state,
-                                 const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
-    SISIC_REQUIRE(eps && x && state && coef && seeds_dev && n > 0, "ddpm_step_indexed_rng: null argument");
+int launch_step_indexed_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
+                            const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps && x && state && coef && seeds_dev && n > 0, "%s_indexed_rng: null argument", rule_name(rule));
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "ddpm_step_indexed_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
+                  "%s_indexed_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
+                  (long long)n_per_image);
     ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
     const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image,
-                       static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4);
+    const LoopState* st = static_cast<const LoopState*>(state);
+    if (rule == STEP_RULE_DDPM)
+        hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
+                           seeds_dev, clip, vec4);
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+        hipLaunchKernelGGL(ddim_step_indexed_rng_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
+                           seeds_dev, clip, vec4);
+    else
+        hipLaunchKernelGGL(ddim_step_indexed_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
+                           seeds_dev, clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

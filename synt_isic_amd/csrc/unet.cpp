@@ -810,25 +810,27 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
 
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
 // launches for every step, so that a captured step can be replayed.
-static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, bool rng, hipStream_t s) {
+static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
+                     hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + 5 * 1000);
     SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
     SISIC_TRY(run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
     if (rng)
-        SISIC_TRY(launch_ddpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state, coef_dev,
-                                               reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
+        SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
+                                          coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
     else
-        SISIC_TRY(launch_ddpm_step_indexed(u->ctx, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev, clip, s));
+        SISIC_TRY(launch_step_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev,
+                                      clip, s));
     return launch_loop_advance(u->ctx, state, s);
 }
 
 // The loop as ONE captured step replayed T-1 times (hipGraph): at batch 1 a step is ~190 launches of 5-20 us kernels and
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
 // rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
-static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, const float* noise,
-                        bool rng, int step0, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
+static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, int rule,
+                        int rule_flags, const float* noise, bool rng, int step0, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
                         hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
@@ -880,7 +882,8 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
-                  u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev);
+                  u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
+                  u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags;
         for (int k = 0; k < 5; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
@@ -888,7 +891,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, rng, s);
+        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
@@ -898,7 +901,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, rng, s);
+            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -911,6 +914,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             u->loop_key.B = B; u->loop_key.H = H; u->loop_key.W = W; u->loop_key.clip = clip; u->loop_key.s = s;
             u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
             u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
+            u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
             for (int k = 0; k < 5; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
@@ -936,10 +940,11 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
     return sisic_sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, traj, nullptr, out_u8, cancel, steps_done, stream);
 }
 
-// The loop behind sisic_sample_frames (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames_rng (seeds: HOST uint64 [B],
-// noise NULL): the two differ in where the scheduler step takes z from, nothing else.
+// The loop behind sisic_sample_frames[_rule] (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames[_rule]_rng (seeds:
+// HOST uint64 [B], noise NULL): the two differ in where the scheduler step takes z from, nothing else.  rule, rule_flags: the
+// step rule whose rows coef holds (SISIC_RULE_*).
 static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
-                         float clip, const float* noise, const uint64_t* seeds, int step0, float* traj, const int* traj_row,
+                         float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0, float* traj, const int* traj_row,
                          uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
     SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
@@ -947,6 +952,10 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
         for (int i = 0; i < T; ++i) SISIC_REQUIRE(traj_row[i] >= -1, "sample: traj_row[%d] = %d (a row of traj, or -1)", i, traj_row[i]);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (steps_done) *steps_done = 0;
+    // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
+    // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
+    if (rule != STEP_RULE_DDPM || rule_flags != 0)
+        for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * 5 + 0], coef[(size_t)i * 5 + 1]));
     SISIC_TRY(check_shape(u, B, H, W));
     // per-step tables for 1000 rows from the first call on (17 MB): a longer run after a shorter one then never moves the
     // time-embedding table, so the captured step (which holds its address) survives a change of T
@@ -973,7 +982,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, noise, rng, step0, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, traj, traj_row, cancel, steps_done, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
@@ -994,11 +1003,12 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
         const float* z = nullptr;
         if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
         if (rng)
-            SISIC_TRY(launch_ddpm_step_rng(u->ctx, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B),
-                                           reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
-                                           c[3], c[4], clip, s));
+            SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B),
+                                      reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
+                                      c[3], c[4], clip, s));
         else
-            SISIC_TRY(launch_ddpm_step(u->ctx, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip, s));
+            SISIC_TRY(launch_step(u->ctx, rule, rule_flags, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip,
+                                  s));
         const int row = traj_row ? traj_row[i] : i;
         if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (steps_done) *steps_done = i + 1;
@@ -1007,19 +1017,34 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     return SISIC_OK;
 }
 
+int sisic_sample_frames_rule(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                             float clip, int rule, int rule_flags, const float* noise, float* traj, const int* traj_row,
+                             uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, traj, traj_row, out_u8,
+                         cancel, steps_done, stream);
+}
+
+int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps,
+                                 const float* coef, float clip, int rule, int rule_flags, const uint64_t* seeds, int step0,
+                                 float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
+                                 void* stream) {
+    SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, traj, traj_row,
+                         out_u8, cancel, steps_done, stream);
+}
+
 int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                         float clip, const float* noise, float* traj, const int* traj_row, uint8_t* out_u8,
                         const volatile int* cancel, int* steps_done, void* stream) {
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, nullptr, 0, traj, traj_row, out_u8, cancel, steps_done,
-                         stream);
+    return sisic_sample_frames_rule(u, x, B, H, W, T, timesteps, coef, clip, SISIC_RULE_DDPM, 0, noise, traj, traj_row, out_u8,
+                                    cancel, steps_done, stream);
 }
 
 int sisic_sample_frames_rng(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                             float clip, const uint64_t* seeds, int step0, float* traj, const int* traj_row, uint8_t* out_u8,
                             const volatile int* cancel, int* steps_done, void* stream) {
-    SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, nullptr, seeds, step0, traj, traj_row, out_u8, cancel,
-                         steps_done, stream);
+    return sisic_sample_frames_rule_rng(u, x, B, H, W, T, timesteps, coef, clip, SISIC_RULE_DDPM, 0, seeds, step0, traj,
+                                        traj_row, out_u8, cancel, steps_done, stream);
 }
 
 }  // extern "C"

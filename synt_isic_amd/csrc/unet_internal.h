@@ -209,6 +209,7 @@ struct sisic_unet {
         const void* ptrs[5] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur at capture time: each can be re-allocated
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
         const void* seeds = nullptr;     // ... from the seeds at this address
+        int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags
     } loop_key;
     bool loop_valid = false;
     int64_t loop_builds = 0;             // captures + instantiations so far (sisic_unet_graph_builds)

@@ -270,6 +270,39 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
     return out
 
 
+def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
+              use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_ddim_step: coef = (sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma), a row of
+    ``HipDDIMScheduler.coefficient_table``.  z None or sigma == 0: no noise is added."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(x)
+    sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
+    check(lib.sisic_ddim_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
+                              x.numel(), sb, sa, c_prev, c_dir, sigma, float(clip), int(bool(use_clipped_model_output)),
+                              _stream(x.device)))
+    return out
+
+
+def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
+                  use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ddim_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
+    ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
+    lib = _lib.load()
+    arr = _seed_array(seeds)
+    B = len(arr)
+    if x.numel() % B:
+        raise ValueError(f"{x.numel()} elements are not {B} equal images")
+    if out is None:
+        out = torch.empty_like(x)
+    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
+    check(lib.sisic_ddim_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+                                  seeds_dev.data_ptr(), int(step), sb, sa, c_prev, c_dir, sigma, float(clip),
+                                  int(bool(use_clipped_model_output)), _stream(x.device)))
+    return out
+
+
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,
                  gn_shift=None, gn_silu=False) -> torch.Tensor:
     """d/dW of ``conv2d`` with the same prologue / index maps: dW [Cout, Cin, k, k] from the forward input(s) and the

@@ -11,6 +11,12 @@ Noise contract (a defined extension): image b owns one C
 for every step with t > 0 in loop order.  Results are independent of the batch an
 image is sampled in and of how images are sharded over GPUs.
 
+``scheduler="ddim"`` (``"ddpm"`` is the default) runs the same loop under the DDIM rule (``HipDDIMScheduler``; ``eta``,
+``use_clipped_model_output``): the same x_T and ``noise_hash`` for a seed in either noise mode, and the same contract for z
+-- only the steps whose sigma is not zero consume a ``z_t[b]``, in loop order.  Under DDPM those are the steps with t > 0;
+under DDIM at eta = 0 there are none: nothing is drawn, no noise buffer exists and no worker thread runs.  (diffusers'
+DDIMScheduler draws a z on every step at eta > 0, also where it multiplies it by a sigma of 0.)
+
 ``noise="device"`` (off by default) is a second contract with the same independence: ``x_T[b]`` from torch's device
 generator seeded with ``seed_b`` (the reference's own spelling on a GPU, so its ``noise_hash``), and every ``z_t[b]``
 generated inside the scheduler-step kernel by Philox4x32-10 keyed with ``seed_b``: no host RNG,
@@ -30,7 +36,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .scheduler import HipDDPMScheduler
+from .scheduler import HipDDIMScheduler, HipDDPMScheduler
 from .unet import HipUNet2DModel
 
 ISIC_CLASSES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")   # xai/XAI.py:196
@@ -75,6 +81,28 @@ def _check_noise_mode(noise: str) -> str:
     if noise not in NOISE_MODES:
         raise ValueError(f"noise must be one of {NOISE_MODES}, got {noise!r}")
     return noise
+
+
+SCHEDULERS = ("ddpm", "ddim")
+
+
+def _check_scheduler(scheduler: str, eta: float, use_clipped_model_output: bool = False) -> str:
+    if scheduler not in SCHEDULERS:
+        raise ValueError(f"scheduler must be one of {SCHEDULERS}, got {scheduler!r}")
+    if scheduler == "ddpm" and (float(eta) != 0.0 or use_clipped_model_output):
+        raise ValueError("eta and use_clipped_model_output belong to scheduler='ddim'; the DDPM rule has neither")
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must lie in 0 .. 1, got {eta!r}")
+    return scheduler
+
+
+def _rule_tables(scheduler, eta: float, use_clipped_model_output: bool):
+    """(host [T,5] coefficient table, SISIC_RULE_* id, rule flags) of a scheduler mirror, by its ``rule`` attribute"""
+    rule = _check_scheduler(getattr(scheduler, "rule", "ddpm"), eta, use_clipped_model_output)
+    if rule == "ddim":
+        flags = _lib.RULE_FLAG_CLIPPED_OUTPUT if use_clipped_model_output else 0
+        return scheduler.coefficient_table(eta).contiguous(), _lib.RULE_DDIM, flags
+    return scheduler.coefficient_table().contiguous(), _lib.RULE_DDPM, 0
 
 
 @dataclass(frozen=True)
@@ -257,6 +285,8 @@ class SampleResult:
     timesteps: List[int] = field(default_factory=list)
     steps_done: int = 0
     cancelled: bool = False                    # the stop flag ended the loop early: images/latents are NOT a result
+    scheduler: str = "ddpm"                    # the step rule of the run ...
+    eta: float = 0.0                           # ... and its eta (DDIM; 0.0 under DDPM)
 
 
 def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence[int]]):
@@ -274,15 +304,20 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
 
 
 @torch.no_grad()
-def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: torch.Tensor,
+def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
-                      cancel_flag: Optional[C.c_int] = None) -> SampleResult:
+                      cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
+                      use_clipped_model_output: bool = False) -> SampleResult:
     """x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
     (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
     ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
-    return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``)."""
+    return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``).
+    scheduler: a ``HipDDPMScheduler`` or a ``HipDDIMScheduler``; its ``rule`` selects the step kernel.  eta and
+    use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not zero under that rule
+    and eta -- none for DDIM at eta = 0, where every noise source gives the same result."""
     if isinstance(noise, NoiseStream):
-        return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices)
+        return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices, eta,
+                             use_clipped_model_output)
     lib = _lib.load()
     dev = x_T.device
     if dev.type != "cuda":
@@ -290,7 +325,7 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: t
     B, Cc, H, W = x_T.shape
     ts = scheduler.timesteps.to(torch.int64).contiguous()
     T = ts.numel()
-    coef = scheduler.coefficient_table().contiguous()
+    coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
     n_noise = int((coef[:, 4] != 0).sum())
     device_noise = noise if isinstance(noise, DeviceNoise) else None
     if device_noise is not None:
@@ -308,7 +343,7 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: t
     done = C.c_int(0)
     clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
     head = (model.handle, x.data_ptr(), B, H, W, T, C.cast(ts.data_ptr(), _lib.c_int64_p),
-            C.cast(coef.data_ptr(), _lib.c_float_p), float(clip))
+            C.cast(coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags)
     tail = (traj.data_ptr() if traj is not None and len(kept) else None,
             rows.ctypes.data_as(C.POINTER(C.c_int)) if rows is not None and len(kept) else None,
             out_u8.data_ptr(),
@@ -316,16 +351,17 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: t
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if device_noise is not None:
         seeds = (C.c_uint64 * B)(*device_noise.seeds)
-        rc = lib.sisic_sample_frames_rng(*head, seeds, int(device_noise.step0), *tail)
+        rc = lib.sisic_sample_frames_rule_rng(*head, seeds, int(device_noise.step0), *tail)
     else:
-        rc = lib.sisic_sample_frames(*head, noise.data_ptr() if noise is not None else None, *tail)
+        rc = lib.sisic_sample_frames_rule(*head, noise.data_ptr() if noise is not None and n_noise else None, *tail)
     if rc != _lib.SISIC_ECANCEL:
         check(rc)
     cancelled = rc == _lib.SISIC_ECANCEL
     if cancelled:
         out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done.value, cancelled=cancelled)
+                        steps_done=done.value, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
+                        eta=float(eta))
 
 
 def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
@@ -344,15 +380,16 @@ def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
     return bounds
 
 
-def _run_streamed(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: torch.Tensor, ns: NoiseStream,
+def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: NoiseStream,
                   return_trajectory: bool, cancel_flag: Optional[C.c_int],
-                  save_indices: Optional[Sequence[int]] = None) -> SampleResult:
+                  save_indices: Optional[Sequence[int]] = None, eta: float = 0.0,
+                  use_clipped_model_output: bool = False) -> SampleResult:
     lib = _lib.load()
     dev = x_T.device
     B, Cc, H, W = x_T.shape
     ts = scheduler.timesteps.to(torch.int64).contiguous()
     T = ts.numel()
-    coef = scheduler.coefficient_table().contiguous()
+    coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
     needs = (coef[:, 4] != 0).to(torch.int64)                   # 1 where the step adds noise
     bounds = segment_bounds(T, ns.seg, B * Cc * H * W)
     counts = [int(needs[a:b].sum()) for a, b in zip(bounds[:-1], bounds[1:])]
@@ -374,14 +411,14 @@ def _run_streamed(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: torch
         done = C.c_int(0)
         last = b == T
         seg_rows = np.ascontiguousarray(rows[a:b]) if traj is not None and len(kept) else None
-        rc = lib.sisic_sample_frames(model.handle, x.data_ptr(), B, H, W, b - a,
-                                     C.cast(ts[a:b].contiguous().data_ptr(), _lib.c_int64_p),
-                                     C.cast(coef[a:b].contiguous().data_ptr(), _lib.c_float_p), float(clip),
-                                     z.data_ptr() if z is not None else None,
-                                     traj.data_ptr() if seg_rows is not None else None,
-                                     seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
-                                     out_u8.data_ptr() if last else None,
-                                     C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream)
+        rc = lib.sisic_sample_frames_rule(model.handle, x.data_ptr(), B, H, W, b - a,
+                                          C.cast(ts[a:b].contiguous().data_ptr(), _lib.c_int64_p),
+                                          C.cast(coef[a:b].contiguous().data_ptr(), _lib.c_float_p), float(clip),
+                                          rule, rule_flags, z.data_ptr() if z is not None else None,
+                                          traj.data_ptr() if seg_rows is not None else None,
+                                          seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
+                                          out_u8.data_ptr() if last else None,
+                                          C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream)
         ns.release(slot)
         done_total += done.value
         if rc != 0:
@@ -392,7 +429,8 @@ def _run_streamed(model: HipUNet2DModel, scheduler: HipDDPMScheduler, x_T: torch
     if cancelled:
         out_u8.zero_()
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done_total, cancelled=cancelled)
+                        steps_done=done_total, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
+                        eta=float(eta))
 
 
 COLOR_BLEND = 0.35            # image_generator.py:532 "alpha"
@@ -472,9 +510,10 @@ class Sampler:
         self.models[class_name] = m
         return m
 
-    def create_scheduler(self, T: int) -> HipDDPMScheduler:
-        """model_manager.py:196-212."""
-        s = HipDDPMScheduler(num_train_timesteps=1000, beta_schedule=self.beta_schedule)
+    def create_scheduler(self, T: int, scheduler: str = "ddpm"):
+        """model_manager.py:196-212; scheduler="ddim": the DDIM mirror over the same tables and timestep grid."""
+        cls = HipDDIMScheduler if _check_scheduler(scheduler, 0.0) == "ddim" else HipDDPMScheduler
+        s = cls(num_train_timesteps=1000, beta_schedule=self.beta_schedule)
         s.set_timesteps(max(1, min(1000, int(T))))
         return s
 
@@ -491,26 +530,42 @@ class Sampler:
 
     def generate_seeds(self, class_name: str, seeds: Sequence[int], T: int, size: Tuple[int, int] = (128, 128),
                        return_trajectory: bool = False, save_every_n: Optional[int] = None,
-                       noise: str = "host") -> SampleResult:
+                       noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
+                       use_clipped_model_output: bool = False) -> SampleResult:
         """save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
         xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise.
         noise: "host" (the default: one CPU generator per image, see the module docstring) or "device" (x_T from torch's
-        device generator, z_t generated in the step kernel: no host RNG, no noise buffers; other images for the same seed)."""
+        device generator, z_t generated in the step kernel: no host RNG, no noise buffers; other images for the same seed).
+        scheduler: "ddpm" (the default) or "ddim" with its ``eta`` (0 = deterministic) and ``use_clipped_model_output``; x_T and
+        ``noise_hashes`` of a seed do not depend on it.  Host-mode z rows go to the steps with sigma != 0 only (module
+        docstring): at eta = 0 nothing beyond x_T is drawn."""
         _check_noise_mode(noise)
+        _check_scheduler(scheduler, eta, use_clipped_model_output)
         if class_name not in self.models:
             raise KeyError(f"no model loaded for class '{class_name}'")
         model = self.models[class_name]
-        sched = self.create_scheduler(T)
+        sched = self.create_scheduler(T, scheduler)
+        rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output)
         save_indices = None
         if return_trajectory and save_every_n is not None:
             save_indices = trajectory_save_indices([int(t) for t in sched.timesteps], save_every_n)
-        n_noise = sum(1 for t in sched.timesteps if int(t) > 0)
+        n_noise = int((_rule_tables(sched, eta, use_clipped_model_output)[0][:, 4] != 0).sum())     # steps with sigma != 0
         H, W = size
         if noise == "device":
             x_T = draw_x_T_device(seeds, (model.config.in_channels, H, W), self.device)
             hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
             res = run_sampling_loop(model, sched, x_T, DeviceNoise(tuple(seeds)), return_trajectory=return_trajectory,
-                                    save_indices=save_indices, cancel_flag=self.cancel)
+                                    save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
+            torch.cuda.current_stream(self.device).synchronize()
+            res.seeds = [int(s) for s in seeds]
+            res.noise_hashes = hashes
+            return res
+        if scheduler == "ddim" and n_noise == 0:
+            # eta = 0: the run draws x_T and nothing else -- no z, no staging buffers, no worker threads
+            x_T, _ = draw_noise(seeds, 0, (model.config.in_channels, H, W))
+            hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
+            res = run_sampling_loop(model, sched, x_T.to(self.device), None, return_trajectory=return_trajectory,
+                                    save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
             res.seeds = [int(s) for s in seeds]
             res.noise_hashes = hashes
@@ -522,7 +577,8 @@ class Sampler:
         try:
             hashes = [noise_hash(ns.x_T[b:b + 1]) for b in range(len(seeds))]
             res = run_sampling_loop(model, sched, ns.x_T.to(self.device), ns if n_noise else None,
-                                    return_trajectory=return_trajectory, save_indices=save_indices, cancel_flag=self.cancel)
+                                    return_trajectory=return_trajectory, save_indices=save_indices, cancel_flag=self.cancel,
+                                    **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
             ns.close()
@@ -532,7 +588,8 @@ class Sampler:
 
     def generate(self, seed: int, class_name: str, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,
-                 save_every_n: Optional[int] = None, noise: str = "host"):
+                 save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
+                 use_clipped_model_output: bool = False):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -544,6 +601,7 @@ class Sampler:
         postprocess=True applies the class colour statistics (``load_color_statistics``) to the uint8 images like
         ``generate_single_image(..., postprocess=True)`` does before saving (image_generator.py:449-452).
         noise: "host" or "device", as in ``generate_seeds``.
+        scheduler, eta, use_clipped_model_output: the step rule, as in ``generate_seeds``.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
         """
         if seed_is_base:
@@ -551,7 +609,8 @@ class Sampler:
         else:
             seeds = [(int(seed) + i) & 0x7FFFFFFF for i in range(count)]
         res = self.generate_images(class_name, seeds, T, size=size, return_trajectory=return_trajectory,
-                                   save_every_n=save_every_n, noise=noise)
+                                   save_every_n=save_every_n, noise=noise, scheduler=scheduler, eta=eta,
+                                   use_clipped_model_output=use_clipped_model_output)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:

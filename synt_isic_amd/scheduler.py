@@ -12,6 +12,9 @@ The beta / alphas_cumprod tables, the integer timestep grid and the per-step sca
 are host data built with the same fp32 torch operations the published algorithm uses
 (SURVEY.md Appendix B); the elementwise update itself runs in the fused HIP kernel
 ``sisic_ddpm_step``.
+
+``HipDDIMScheduler`` mirrors ``diffusers.DDIMScheduler`` the same way (the reference itself holds no DDIM code: the swap
+is described in INTEGRATION.md); its update runs in ``sisic_ddim_step``.
 """
 from __future__ import annotations
 
@@ -42,6 +45,7 @@ def _betas_for_alpha_bar(n: int, max_beta: float = 0.999) -> torch.Tensor:
 
 class HipDDPMScheduler:
     order = 1
+    rule = "ddpm"            # the step rule ``run_sampling_loop`` runs this scheduler's table under
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = True,
@@ -170,3 +174,120 @@ class HipDDPMScheduler:
                                           out.data_ptr(), B, x0[0].numel(),
                                           C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))
         return out
+
+
+@dataclass
+class DDIMSchedulerOutput:
+    """Mirror of ``diffusers.schedulers.scheduling_ddim.DDIMSchedulerOutput`` (``pred_original_sample`` is not produced)."""
+    prev_sample: torch.Tensor
+    pred_original_sample: Optional[torch.Tensor] = None
+
+
+class HipDDIMScheduler:
+    """Drop-in for ``diffusers.DDIMScheduler`` with epsilon prediction: the same beta / alphas_cumprod tables, x_T and UNet as
+    the DDPM mirror, the step rule that was designed for 20 to 100 steps.  Deterministic at ``eta = 0``; at ``eta = 1`` its
+    sigma is the DDPM rule's.
+
+        sched = HipDDIMScheduler(num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2")
+        sched.set_timesteps(50)
+        for t in sched.timesteps:
+            latents = sched.step(model(latents, t).sample, t, latents, eta=0.0).prev_sample
+    """
+    order = 1
+    rule = "ddim"
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", clip_sample: bool = True, set_alpha_to_one: bool = True,
+                 steps_offset: int = 0, prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
+                 timestep_spacing: str = "leading", **unsupported):
+        if unsupported:
+            raise NotImplementedError(f"unsupported DDIMScheduler arguments: {sorted(unsupported)}")
+        if prediction_type != "epsilon":
+            raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
+        if timestep_spacing not in ("leading", "trailing"):
+            raise NotImplementedError("only timestep_spacing='leading' (the diffusers default) or 'trailing'")
+        if beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "squaredcos_cap_v2":
+            self.betas = _betas_for_alpha_bar(num_train_timesteps)
+        else:
+            raise NotImplementedError(f"beta_schedule '{beta_schedule}' is not used by the reference")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, clip_sample=clip_sample,
+                                      set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset,
+                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range,
+                                      timestep_spacing=timestep_spacing)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+
+    # the forward process does not depend on the sampling rule
+    __len__ = HipDDPMScheduler.__len__
+    scale_model_input = HipDDPMScheduler.scale_model_input
+    add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
+    add_noise = HipDDPMScheduler.add_noise
+    previous_timestep = HipDDPMScheduler.previous_timestep      # t - num_train_timesteps // num_inference_steps, both spacings
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        n_train = self.config.num_train_timesteps
+        if num_inference_steps > n_train:
+            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
+        if num_inference_steps < 1:
+            raise ValueError("num_inference_steps must be >= 1")
+        self.num_inference_steps = num_inference_steps
+        if self.config.timestep_spacing == "leading":
+            step_ratio = n_train // num_inference_steps
+            ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
+            ts += self.config.steps_offset
+        else:                                                    # "trailing": the float ratio, no offset
+            step_ratio = n_train / num_inference_steps
+            ts = np.round(np.arange(n_train, 0, -step_ratio)).astype(np.int64)
+            ts -= 1
+        self.timesteps = torch.from_numpy(ts)
+
+    def step_coefficients(self, timestep, eta: float = 0.0) -> Tuple[float, float, float, float, float]:
+        """(sqrt(1-abar_t), sqrt(abar_t), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma) as fp32 values,
+        sigma = eta * variance ** 0.5: the table row of ``sisic_ddim_step``."""
+        t = int(timestep)
+        prev_t = self.previous_timestep(t)
+        alpha_prod_t = self.alphas_cumprod[t]
+        alpha_prod_t_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        beta_prod_t = 1 - alpha_prod_t
+        beta_prod_t_prev = 1 - alpha_prod_t_prev
+        variance = (beta_prod_t_prev / beta_prod_t) * (1 - alpha_prod_t / alpha_prod_t_prev)
+        std_dev_t = float(eta) * variance ** (0.5)
+        c_dir = (1 - alpha_prod_t_prev - std_dev_t ** 2) ** (0.5)
+        return (float(beta_prod_t ** (0.5)), float(alpha_prod_t ** (0.5)), float(alpha_prod_t_prev ** (0.5)), float(c_dir),
+                float(std_dev_t))
+
+    def coefficient_table(self, eta: float = 0.0) -> torch.Tensor:
+        """[T,5] fp32 host table for ``sisic_sample_frames_rule`` under SISIC_RULE_DDIM."""
+        return torch.tensor([self.step_coefficients(t, eta) for t in self.timesteps], dtype=torch.float32)
+
+    @torch.no_grad()
+    def step(self, model_output: torch.Tensor, timestep: Union[int, torch.Tensor], sample: torch.Tensor, eta: float = 0.0,
+             use_clipped_model_output: bool = False, generator: Optional[torch.Generator] = None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """prev_sample = DDIM update on the GPU.  Noise, on the steps with sigma != 0 only: ``variance_noise`` if given, else
+        ``torch.randn`` on the sample's device with ``generator``.  (diffusers also draws on a step whose sigma is 0 at
+        eta > 0, and multiplies the draw by 0: a generator shared with it is one draw further on after such a step.)"""
+        if model_output.device.type != "cuda":
+            raise RuntimeError("HipDDIMScheduler.step runs on MI355X tensors only (no CPU path)")
+        coef = self.step_coefficients(timestep, eta)
+        z = None
+        if coef[4] != 0.0:
+            if variance_noise is not None:
+                z = variance_noise.to(device=sample.device, dtype=torch.float32).contiguous()
+            elif generator is not None and generator.device.type == "cpu":
+                z = torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(sample.device)
+            else:
+                z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
+        prev = ops.ddim_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z, coef, clip,
+                             use_clipped_model_output)
+        if not return_dict:
+            return (prev,)
+        return DDIMSchedulerOutput(prev_sample=prev)
