@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <map>
 #include <mutex>
@@ -106,6 +107,9 @@ inline int ensure_dynamic_lds(sisic_ctx* ctx, const void* kern, int bytes, std::
     return SISIC_OK;
 }
 
+// A process-wide switch in the environment: on unless set to 0.  Callers keep the answer (static const): one read per process.
+inline bool env_on(const char* name) { const char* e = std::getenv(name); return !e || std::atoi(e) != 0; }
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // Latency mode (tile_cfg 78 / 79): ways the input channels of a Winograd convolution are split over workgroups so that ONE
 // image already offers ~256 workgroups.  A function of the layer shape only -- never of the batch -- so that an image's
@@ -135,13 +139,15 @@ inline int64_t conv_packed_floats(int cout, int cin, int ksize) {
 }
 
 // launchers implemented in the .hip files
+// launch_conv2d: plans the convolution once (conv_plan.h: kernel, tile configuration, GroupNorm partial slots, finalisation, rider)
+// and hands (args, plan) to the chosen kernel's launcher below; the launchers act on the plan and do not test the arguments again.
 // rider / carried (optional): a GroupNorm finalisation that is independent of this convolution (gn_finalize.h) runs as extra
-// workgroups of its launch where the chosen kernel offers that -- the bf16x3 1x1 kernels without a GroupNorm prologue.
+// workgroups of its launch where the planned kernel offers that -- the bf16x3 1x1 kernels without a GroupNorm prologue.
 // *carried says whether THIS launch ran the jobs; false: nothing of the job was touched and the caller launches it itself.
 struct GnFinJob;
+struct ConvPlan;
 int launch_conv2d(sisic_ctx*, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider = nullptr, bool* carried = nullptr);
-int launch_conv_smallcout(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
-// conv_winograd.hip: F(2x2,3x3) for 3x3 stride-1 convolutions
+int launch_conv_smallcout(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s);
 int launch_score_head_bwd(sisic_ctx*, const float* logits, const float* fc_w, const float* act, float* g, int B, int C,
                           int HW, int n_classes, int target, hipStream_t s);
 int launch_relu_bwd(sisic_ctx*, const float* dy, const float* y, float* out, int64_t n, hipStream_t s);
@@ -154,21 +160,20 @@ int launch_preprocess_bwd(sisic_ctx*, const float* dp, const float* x, float* dx
 int launch_add_relu(sisic_ctx*, const float* y, const float* identity, float* out, int64_t n, hipStream_t s);
 int launch_gradcam(sisic_ctx*, const float* y, const float* outp, const float* fc_w, const float* bias, float* cam, int B, int C,
                    int h, int w, int S, int target, hipStream_t s);
+// the plan's answers for sisic_conv_stats_slots / sisic_conv_finalizes (conv_plan.cpp); 0 / false where planning fails
 int conv_stats_slots(const sisic_conv_args& a);
 bool conv_finalizes(const sisic_conv_args& a);       // the launch leaves the following GroupNorm's (scale, shift) itself (sisic.h)
-// conv_pointwise.hip: the lean 1x1 kernel (tile_cfg 20)
+// conv_pointwise.hip: the lean 1x1 kernel (tile_cfg 20) and the shapes it takes
 bool conv_pointwise_applicable(const sisic_conv_args& a);
-int conv_pointwise_stats_slots(const sisic_conv_args& a);
-int launch_conv_pointwise(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
-// conv_pointwise_bf3.hip: the same GEMM with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 28)
+int launch_conv_pointwise(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s);
+// conv_pointwise_bf3.hip: the same GEMM with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 28); rider: jobs to run, or NULL
 bool conv_pointwise_bf3_applicable(const sisic_conv_args& a);
-int launch_conv_pointwise_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider = nullptr,
-                              bool* carried = nullptr);
+int launch_conv_pointwise_bf3(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s, const GnFinJob* rider);
 // conv_s2_bf3.hip: 3x3 stride-2 convolutions with fp32-equivalent products on the bf16 matrix pipe (tile_cfg 36); the split
 // filter (conv_s2_pack_bf3_elem, pack_device.h) travels in sisic_conv_args.w_winograd
 bool conv_s2_bf3_applicable(const sisic_conv_args& a);
 int conv_s2_bf3_stats_slots(const sisic_conv_args& a);
-int launch_conv_s2_bf3(sisic_ctx*, const sisic_conv_args& a, hipStream_t s);
+int launch_conv_s2_bf3(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s);
 int64_t conv_s2_packed_floats(int Cout, int Cin);
 int launch_conv_s2_pack(sisic_ctx*, const float* w, int Cout, int Cin, float* out, hipStream_t s);
 // mean_rstd (optional, training): [B, groups, 2] = (mean, rstd) of every (sample, group)
@@ -179,7 +184,8 @@ int launch_gn_finalize(sisic_ctx*, const float* st0, int c0, int slots0, const f
 int make_gn_fin_job(GnFinJob* q, const float* st0, int c0, int slots0, const float* st1, int c1, int slots1, int B, int groups,
                     float eps, const float* gamma, const float* beta, float* scale, float* shift, float* mean_rstd = nullptr);
 int launch_gn_finalize_job(sisic_ctx*, const GnFinJob& q, hipStream_t s);
-int launch_conv_winograd(sisic_ctx*, const sisic_conv_args& a, const float* u_packed, int cfg, hipStream_t s);
+// conv_winograd.hip: F(2x2,3x3) for 3x3 stride-1 convolutions, every Winograd kernel of the plan (filters in a.w_winograd)
+int launch_conv_winograd(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s);
 int launch_winograd_pack(sisic_ctx*, const float* w, int Cout, int Cin, float* packed, hipStream_t s);
 int64_t winograd_packed_numel(int Cout, int Cin);
 // floats of the first Winograd layout [Cin_pad][16][cout_pad]; the wide layout follows it in the same buffer

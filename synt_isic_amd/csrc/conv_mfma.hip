@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_plan.h"
 #include "pack_device.h"
 
 namespace sisic {
@@ -52,7 +52,7 @@ struct ConvParams {
     int relu;
     float* out;
     float* stats;      // optional GroupNorm partials [B][Cout][tiles_y*tiles_x*WN][4] = (count, sum, centred M2, 0)
-    int* slots_query;  // host only: when set, launch_cfg reports the slot count of its tiling instead of launching
+    const void* reserved;   // (unused: holds the place of a former host-only field, so that the kernels' argument layout -- and with it their code -- is unchanged)
     int tiles_x, tiles_y, n_co_tiles, nwg, nchunks;
 };
 
@@ -439,31 +439,20 @@ static int launch_cfg(sisic_ctx* ctx, ConvParams& p, hipStream_t s) {
     p.tiles_y = cdiv(p.Hout, G::TH);
     p.n_co_tiles = p.cout_pad / G::CO_TILE;
     p.nchunks = cdiv(p.c0 + p.c1, CIC);
-    const int64_t nwg = (int64_t)p.B * p.tiles_x * p.tiles_y * p.n_co_tiles;
-    SISIC_REQUIRE(nwg > 0 && nwg < (int64_t(1) << 31), "conv2d: grid of %lld workgroups unsupported", (long long)nwg);
-    p.nwg = (int)nwg;
-    if (p.slots_query) {           // sisic_conv_stats_slots(): report the partial-statistics layout, launch nothing
-        *p.slots_query = p.tiles_x * p.tiles_y * WN;
+    p.nwg = p.B * p.tiles_x * p.tiles_y * p.n_co_tiles;       // (conv_plan checked that the grid fits)
+    static std::atomic<uint64_t> lds_opt_in{0}, lds_opt_in4{0};     // one bit per device (common.h)
+    auto run = [&](auto kern, std::atomic<uint64_t>& opt_in) -> int {
+        SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, opt_in));
+        hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(G::NTHR), G::LDS_BYTES, s, p);
+        SISIC_HIP(hipGetLastError());
         return SISIC_OK;
-    }
+    };
     if constexpr (KS == 1 && STRIDE == 1 && TW == G::PIX && G::EPT % 4 == 0) {
         // flat 1x1 tile: float4 staging when every plane is a whole number of 16-byte aligned float4
         const bool aligned = ((reinterpret_cast<uintptr_t>(p.in0) | reinterpret_cast<uintptr_t>(p.in1)) & 15) == 0;
-        if (p.Wc % 4 == 0 && aligned) {
-            auto kern4 = conv_mfma_kernel<KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP, true>;
-            static std::atomic<uint64_t> lds_opt_in4{0};     // one bit per device (common.h)
-            SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern4), (int)G::LDS_BYTES, lds_opt_in4));
-            hipLaunchKernelGGL(kern4, dim3(p.nwg), dim3(G::NTHR), G::LDS_BYTES, s, p);
-            SISIC_HIP(hipGetLastError());
-            return SISIC_OK;
-        }
+        if (p.Wc % 4 == 0 && aligned) return run(conv_mfma_kernel<KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP, true>, lds_opt_in4);
     }
-    auto kern = conv_mfma_kernel<KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP>;
-    static std::atomic<uint64_t> lds_opt_in{0};     // one bit per device (common.h)
-    SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, lds_opt_in));
-    hipLaunchKernelGGL(kern, dim3(p.nwg), dim3(G::NTHR), G::LDS_BYTES, s, p);
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
+    return run(conv_mfma_kernel<KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP>, lds_opt_in);
 }
 
 int launch_conv_pack(sisic_ctx*, const float* w, int Cout, int Cin, int k, float* packed, hipStream_t s) {
@@ -476,242 +465,52 @@ int launch_conv_pack(sisic_ctx*, const float* w, int Cout, int Cin, int k, float
     return SISIC_OK;
 }
 
-// Tile configurations.  id -> (KS, STRIDE, MT, NT, WM, WN, TW):
-//   3x3 s1:  1: 2,2,1,4,TW64   2: 2,2,1,4,TW32   3: 2,2,1,4,TW16   4: 1,1,2,2,TW8   5: 2,1,1,4,TW16 (PIX128)
-//            6: 2,1,1,4,TW64   7: 2,1,1,4,TW32 (PIX128)   8: 1,2,2,4,TW32   9: 1,2,2,4,TW16 (8 waves, PIX256)
-//           14: 1,1,2,4,TW16  15: 1,1,2,4,TW8 (8 waves, PIX128)   50: vector-ALU kernel for Cout <= 4
-//           16 / 17: cfg 4's 64x64 tile with two K-split wave groups (8 waves), 16- / 8-channel chunks
-//   3x3 s2: 11: 2,1,1,4,TW32  12: 2,1,1,4,TW16  13: 1,1,2,2,TW8   18 / 19: cfg 13's tile with two K-split wave groups, 16- / 8-channel chunks
-//           36: the bf16x3 kernel of conv_s2_bf3.hip
-//   1x1   : 21: 2,2,1,4,TW256 22: 1,1,2,2,TW64  23: 2,1,1,4,TW128
-//   1x1 s2: 31: 2,1,1,4,TW32  32: 2,1,1,4,TW16  33: 1,1,2,2,TW8      7x7 s2: 41: 2,1,1,4,TW32 (CIC 4)
-static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query, const GnFinJob* rider = nullptr,
-                           bool* carried = nullptr);
-
-// Winograd F(2x2,3x3) is taken for 3x3 stride-1 convolutions with transformed filters at hand: when forced by
-// tile_cfg 60..74 / 78 / 79 / 90 / 91, or automatically from 12x12 outputs up and (K-split form) at 8x8 (per-thread load offsets
-// there are 32-bit).  Returns the tile configuration, 0 = not Winograd.
-static int winograd_cfg(const sisic_conv_args& a) {
-    if (!(a.ksize == 3 && a.stride == 1 && a.w_winograd != nullptr && a.Cout > 4) || a.upsample == 2) return 0;
-    if ((a.tile_cfg >= 60 && a.tile_cfg <= 74) || a.tile_cfg == 78 || a.tile_cfg == 79 || (a.tile_cfg >= 90 && a.tile_cfg <= 92)) return a.tile_cfg;
-    if (a.tile_cfg != 0) return 0;
-    const int Hout = a.Hin << (a.upsample ? 1 : 0), Wout = a.Win << (a.upsample ? 1 : 0);
-    const bool fits32 = 16.0 * std::max(a.c0, a.c1) * a.Hin * a.Win < 4294967296.0;
-    if (!fits32) return 0;
-    if (Hout >= 12 && Wout >= 12) {
-        // second geometry (conv_winograd_wide.inc) unless SISIC_WINO_WIDE=0; nearest-2x inputs keep the nine-position form
-        static const bool wide_on = [] { const char* e = std::getenv("SISIC_WINO_WIDE"); return !e || std::atoi(e) != 0; }();
-        // measured per layer (tools/conv_bench.py, profiles/r02/conv_bench_geometries.txt): the 128-channel form wins 8-12 % on
-        // every Cout >= 128 layer, the 64-channel two-workgroups-per-CU form 1-10 % on every Cout <= 64 layer
-        // fp32-equivalent products on the bf16 matrix pipe (conv_winograd_bf3.inc) unless SISIC_WINO_BF16X3=0: 64 channels x
-        // 16 x 16 pixels per workgroup, so only where those tiles are (nearly) full; measured 1.36 - 1.43x the third f32 form on every
-        // such layer of the headline model (profiles/r03/conv_bench_bf16x3.txt), the same error against float64
-        static const bool bf3_on = [] { const char* e = std::getenv("SISIC_WINO_BF16X3"); return !e || std::atoi(e) != 0; }();
-        // (ragged planes too when at least three quarters of the 16x16-pixel tiles' area is inside: the classifier's 56 / 28 / 14)
-        const int th = (Hout + 15) / 16 * 16, tw = (Wout + 15) / 16 * 16;
-        // (nearest-2x inputs as well: all 16 positions on the bf16 pipe beat the f32 form's 9 on every upsample layer of the
-        //  UNet -- 562 -> 512 us over the three, profiles/r03/conv_bench_bf16x3.txt)
-        if (bf3_on && a.Cout % 64 == 0 && 4 * Hout * Wout >= 3 * th * tw && a.c0 + a.c1 >= 16 &&
-            a.c0 + a.c1 <= 2048 &&                                      // (its LDS table of the image's GroupNorm operands)
-            4.0 * a.Cout * Hout * Wout < 2147483648.0)
-            return 74;
-        if (wide_on && !a.upsample) return a.Cout > 64 ? 68 : 69;
-        return 66;
-    }
-    // the 8x8 level (and the classifier's 7x7): four images per workgroup and the input channels split four ways
-    // keep all CUs busy
-    const int Cin = a.c0 + a.c1;
-    static const bool ksplit_on = [] { const char* e = std::getenv("SISIC_KSPLIT"); return !e || std::atoi(e) != 0; }();
-    // (no batch-size condition anywhere in this function: an image's bits must not depend on the batch it is in)
-    if (ksplit_on && Hout <= 8 && Wout <= 8 && Hout >= 5 && Wout >= 5 && Cin >= 128 && Cin % 32 == 0 && a.Cout >= 128) {
-        // second geometry with two images per workgroup (tile_cfg 91): 45 -> 39 us and 67 -> 57 us per launch at B = 64
-        static const bool wide_on = [] { const char* e = std::getenv("SISIC_WINO_WIDE"); return !e || std::atoi(e) != 0; }();
-        // tile_cfg 92: the same split with fp32-equivalent products on the bf16 pipe, four images per workgroup
-        // (conv_winograd_bf3.inc): 38 -> 32 and 59 -> 47 us per launch at B = 64 (profiles/r03/conv_bench_bf16x3.txt)
-        static const bool bf3_on = [] { const char* e = std::getenv("SISIC_WINO_BF16X3"); return !e || std::atoi(e) != 0; }();
-        if (bf3_on && !a.upsample && a.Cout % 64 == 0 && Cin <= 512) return 92;
-        return (wide_on && !a.upsample) ? 91 : 90;
-    }
-    return 0;
-}
-static bool winograd_selected(const sisic_conv_args& a) { return winograd_cfg(a) != 0; }
-
-// GroupNorm partials (sisic_conv_args.stats_out): the Winograd kernels' output transform leaves one slot per
-// workgroup tile of an image (16x16 outputs, or 8x8 for the four-image tilings; the K-split form one per image from
-// its reduction); the direct MFMA kernel one per pixel tile and pixel-wave (the dispatch below is asked which tiling
-// it would launch).  The vector-ALU small-Cout kernel does not produce them.
-int conv_stats_slots(const sisic_conv_args& a) {
-    if (const int cfg = winograd_cfg(a)) {
-        if (cfg >= 90 && cfg <= 92) return 1;
-        const int Hout = a.Hin << (a.upsample ? 1 : 0), Wout = a.Win << (a.upsample ? 1 : 0);
-        if ((cfg == 78 || cfg == 79) && wino_latency_ksplit(a.Cout, a.c0 + a.c1, Hout, Wout) > 1) return wino_latency_segments(Hout, Wout);   // from the plane reduction
-        if ((cfg >= 68 && cfg <= 73) || cfg == 78 || cfg == 79) return ((Hout + 7) / 8) * ((Wout + 15) / 16);   // 8 x 16 output pixels per workgroup
-        const int edge = (cfg == 61 || cfg == 63 || cfg == 65 || cfg == 67) ? 8 : 16;
-        return ((Hout + edge - 1) / edge) * ((Wout + edge - 1) / edge);
-    }
-    int slots = 0;
-    sisic_conv_args q = a;
-    q.stats_out = nullptr;
-    if (dispatch_conv2d(nullptr, q, nullptr, &slots) != SISIC_OK) return 0;
-    return slots;
-}
-
-// sisic_conv_finalizes(): where a workgroup holds whole GroupNorm groups (eight channels) of an image it finalizes them: the
-// K-split 8x8-level forms in their reduction kernel (16 whole channel planes per workgroup: conv_winograd.hip, ReduceFin), the
-// bf16x3 Winograd kernel where one tile is the whole image (16x16 and smaller: conv_winograd_bf3.inc)
-bool conv_finalizes(const sisic_conv_args& a) {
-    if (!a.fin_gamma || a.fin_groups <= 0) return false;
-    const int cfg = winograd_cfg(a);
-    const int Hout = a.Hin << (a.upsample ? 1 : 0), Wout = a.Win << (a.upsample ? 1 : 0);
-    if (a.Cout % a.fin_groups != 0 || a.Cout / a.fin_groups != 8) return false;
-    // the bf16x3 Winograd kernel where ONE 16x16-pixel tile is the whole image: a workgroup holds 64 channels of an image whole
-    if (cfg == 74) return !a.upsample && Hout <= 16 && Wout <= 16 && a.Cout % 64 == 0;
-    if (cfg < 90 || cfg > 92) return false;
-    if (Hout * Wout != 64 || a.Cout % 16 != 0) return false;
-    // (the 16-byte form of the reduction; its scratch slabs are the library's own allocation)
-    return ((reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.stats_out)) & 15) == 0;
-}
-
-int launch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider, bool* carried) {
-    return dispatch_conv2d(ctx, a, s, nullptr, rider, carried);
-}
-
-static int dispatch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, int* slots_query, const GnFinJob* rider,
-                           bool* carried) {
-    if (carried) *carried = false;            // set by the one launcher that runs rider jobs (conv_pointwise_bf3.hip); every other path leaves it
-    SISIC_REQUIRE(a.in0 && a.w_packed && a.out, "conv2d: null tensor");
-    SISIC_REQUIRE(a.B > 0 && a.Hin > 0 && a.Win > 0 && a.c0 > 0 && a.c1 >= 0 && a.Cout > 0, "conv2d: bad shape");
-    SISIC_REQUIRE((a.c1 == 0) == (a.in1 == nullptr), "conv2d: in1/c1 mismatch");
-    SISIC_REQUIRE(a.ksize == 1 || a.ksize == 3 || a.ksize == 7, "conv2d: ksize %d unsupported", a.ksize);
-    SISIC_REQUIRE(a.stride == 1 || a.stride == 2, "conv2d: stride %d unsupported", a.stride);
-    SISIC_REQUIRE(a.ksize != 7 || a.stride == 2, "conv2d: 7x7 is built for stride 2 only (the ResNet stem)");
-    SISIC_REQUIRE(!(a.upsample && a.stride != 1), "conv2d: upsample with stride");
-    SISIC_REQUIRE((a.gn_scale == nullptr) == (a.gn_shift == nullptr), "conv2d: gn_scale/gn_shift mismatch");
-
+// The direct kernel in the tiling the plan chose (SISIC_DIRECT_TILINGS, conv_plan.h)
+static int launch_conv_direct(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s) {
     ConvParams p{};
     p.in0 = a.in0; p.in1 = a.in1; p.c0 = a.c0; p.c1 = a.c1;
     p.B = a.B; p.Hin = a.Hin; p.Win = a.Win;
     p.ups = a.upsample ? 1 : 0;
     p.zero_insert = a.upsample == 2 ? 1 : 0;
     p.Hc = a.Hin << p.ups; p.Wc = a.Win << p.ups;
-    const int pad = a.ksize / 2;
-    p.Hout = (p.Hc + 2 * pad - a.ksize) / a.stride + 1;
-    p.Wout = (p.Wc + 2 * pad - a.ksize) / a.stride + 1;
+    p.Hout = plan.Hout; p.Wout = plan.Wout;
     p.w = a.w_packed; p.cout_pad = conv_cout_pad(a.Cout);
     p.bias = a.bias; p.Cout = a.Cout;
     p.gn_scale = a.gn_scale; p.gn_shift = a.gn_shift; p.gn_silu = a.gn_silu;
     p.chan_bias = a.chan_bias; p.chan_bias_stride = a.chan_bias_stride; p.residual = a.residual; p.relu = a.relu; p.out = a.out;
-    p.stats = a.stats_out; p.slots_query = slots_query;
-
-    const int Cin = a.c0 + a.c1;
-    const double kk = double(a.ksize) * a.ksize;
-    const double out_elems = double(a.B) * a.Cout * p.Hout * p.Wout;
-    const double bytes = 4.0 * (double(a.B) * Cin * a.Hin * a.Win + out_elems) + 4.0 * (Cin * a.Cout * kk + a.Cout) +
-                         (a.residual ? 4.0 * out_elems : 0.0);
-    const double flops = 2.0 * out_elems * Cin * kk;
-    int cfg = a.tile_cfg;
-    const bool use_wino = winograd_selected(a);
-    // F(2x2,3x3): 16 multiplies per 2x2 outputs and channel pair instead of 36
-    SISIC_REQUIRE(a.stats_out == nullptr || conv_stats_slots(a) > 0,
-                  "conv2d: stats_out given but sisic_conv_stats_slots() is 0 for these arguments");
-    // matrix FLOPs actually issued: F(2x2,3x3) multiplies 16 positions per 2x2 outputs instead of 36 taps, and only 9
-    // of them for nearest-2x inputs (conv_winograd.hip, upsample form)
-    const bool wino_ups9 = use_wino && a.upsample && !a.gn_scale && winograd_cfg(a) == 66;
-    ProfileScope prof(slots_query ? nullptr : ctx, s, a.ksize == 1 ? PK_CONV1 : PK_CONV3, bytes, flops,
-                      use_wino ? flops * (wino_ups9 ? 9.0 : 16.0) / 36.0 : flops,
-                      (use_wino && winograd_cfg(a) == 74) ? PK_WINO_BF3 :
-                      (use_wino && !wino_ups9 && (winograd_cfg(a) == 66 || (winograd_cfg(a) >= 68 && winograd_cfg(a) <= 73) || winograd_cfg(a) == 78 || winograd_cfg(a) == 79)) ? PK_WINO_MAIN : -1);
-
-    if (a.ksize == 3 && a.stride == 1 && !a.upsample && a.Cout <= 4 && (cfg == 0 || (cfg >= 50 && cfg <= 52))) {
-        if (slots_query) return SISIC_OK;             // no partials from this kernel (slots stay 0)
-        return launch_conv_smallcout(ctx, a, s);      // conv_out: vector-ALU kernel, conv_small.hip
+    p.stats = a.stats_out;
+    if (a.ksize == 1 && a.stride == 1) {      // 1x1: the image is a flat row of H*W pixels
+        p.Hin = 1; p.Win = a.Hin * a.Win; p.Hc = 1; p.Wc = p.Win; p.Hout = 1; p.Wout = p.Win;
     }
-    // Winograd F(2x2,3x3): 2.25x fewer MFMA FLOPs.  Auto: from 12x12 output up (64 tiles of one image fill a
-    // workgroup); the 8x8 level stays on the direct kernel (too few workgroups of 4 images x 64 channels).
-    if (use_wino) {
-        SISIC_REQUIRE(!slots_query, "conv2d: internal: slot query on the Winograd path");
-        return launch_conv_winograd(ctx, a, a.w_winograd, winograd_cfg(a), s);
+    switch (plan.cfg) {
+#define X(id, KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP) \
+        case id: return launch_cfg<KS, STRIDE, MT, NT, WM, WN, TW, CIC, OCC, KSP>(ctx, p, s);
+        SISIC_DIRECT_TILINGS(X)
+#undef X
     }
-    SISIC_REQUIRE((cfg < 60 || cfg > 74) && cfg != 78 && cfg != 79 && (cfg < 90 || cfg > 92), "conv2d: tile_cfg %d needs w_winograd, ksize 3 and stride 1", cfg);
-    if (a.ksize == 7) {
-        if (cfg == 0) cfg = 41;
-        if (cfg == 41) return launch_cfg<7, 2, 2, 1, 1, 4, 32, 2>(ctx, p, s);   // 2-channel chunks: 4 spill 256 B/lane (13 weight float4 + 15 halo elements per thread)
-        if (cfg == 42) return launch_cfg<7, 2, 2, 1, 1, 4, 32, 4>(ctx, p, s);
-    } else if (a.ksize == 1 && a.stride == 2) {
-        if (cfg == 0) cfg = p.Wout >= 24 ? 31 : (p.Wout >= 12 ? 32 : 33);
-        switch (cfg) {
-            case 31: return launch_cfg<1, 2, 2, 1, 1, 4, 32, 16>(ctx, p, s);
-            case 32: return launch_cfg<1, 2, 2, 1, 1, 4, 16, 16>(ctx, p, s);
-            case 33: return launch_cfg<1, 2, 1, 1, 2, 2, 8, 16>(ctx, p, s);
-        }
-    } else if (a.ksize == 1) {
-        // 1x1: the image is a flat row of H*W pixels
-        p.Hin = 1; p.Win = a.Hin * a.Win; p.Hc = 1; p.Wc = p.Win; p.Hout = 1; p.Wout = p.Win; p.ups = 0;
-        SISIC_REQUIRE(!a.upsample, "conv2d: 1x1 with upsample");
-        // tile_cfg 20: the lean pointwise kernel (conv_pointwise.hip) for the shapes it takes -- whole 128-pixel tiles and
-        // 32-channel chunks -- unless SISIC_POINTWISE=0; the generic tilings below for everything else
-        static const bool pw_on = [] { const char* e = std::getenv("SISIC_POINTWISE"); return !e || std::atoi(e) != 0; }();
-        // tile_cfg 28: the same GEMM with fp32-equivalent products on the bf16 matrix pipe (conv_pointwise_bf3.hip) for whole
-        // 64-pixel x 64-channel tiles -- unless SISIC_POINTWISE_BF16X3=0.  (Shape conditions only: an image's bits must not
-        // depend on the batch it is in.)
-        static const bool pwb_on = [] { const char* e = std::getenv("SISIC_POINTWISE_BF16X3"); return !e || std::atoi(e) != 0; }();
-        if ((cfg == 0 && pwb_on && conv_pointwise_bf3_applicable(a)) || (cfg >= 28 && cfg <= 30) || cfg == 34 || cfg == 35) {
-            if (slots_query) { *slots_query = conv_pointwise_stats_slots(a); return SISIC_OK; }
-            return launch_conv_pointwise_bf3(ctx, a, s, rider, carried);
-        }
-        if ((cfg == 0 && pw_on && conv_pointwise_applicable(a)) || cfg == 20) {
-            if (slots_query) { *slots_query = conv_pointwise_stats_slots(a); return SISIC_OK; }
-            return launch_conv_pointwise(ctx, a, s);
-        }
-        if (cfg == 0) cfg = (p.Wout <= 64) ? 22 : (p.Wout <= 256 ? 25 : 24);   // measured (tools/conv_bench.py, B=64)
-        switch (cfg) {
-            case 21: return launch_cfg<1, 1, 2, 2, 1, 4, 256, 16>(ctx, p, s);
-            case 22: return launch_cfg<1, 1, 1, 1, 2, 2, 64, 16>(ctx, p, s);
-            case 23: return launch_cfg<1, 1, 2, 1, 1, 4, 128, 16>(ctx, p, s);
-            case 24: return launch_cfg<1, 1, 1, 2, 2, 4, 256, 32, 4>(ctx, p, s);
-            case 25: return launch_cfg<1, 1, 1, 1, 2, 4, 128, 32, 4>(ctx, p, s);
-            case 26: return launch_cfg<1, 1, 1, 2, 2, 4, 256, 16, 4>(ctx, p, s);
-            case 27: return launch_cfg<1, 1, 1, 1, 2, 4, 128, 16, 4>(ctx, p, s);
-            // (four-wave tiles at three / six workgroups per CU were measured too -- profiles/r02/conv1x1_tilings_and_contraction.txt,
-            //  cfg 28 / 29: within 2 % of 24 / slower -- and removed: occupancy is not what limits these launches)
-        }
-    } else if (a.stride == 1) {
-        if (cfg == 0) cfg = p.Wout >= 24 ? 8 : (p.Wout >= 12 ? 9 : 16);   // measured (tools/conv_bench.py, B=64)
-        switch (cfg) {
-            case 1: return launch_cfg<3, 1, 2, 2, 1, 4, 64, 8>(ctx, p, s);
-            case 2: return launch_cfg<3, 1, 2, 2, 1, 4, 32, 8>(ctx, p, s);
-            case 3: return launch_cfg<3, 1, 2, 2, 1, 4, 16, 8>(ctx, p, s);
-            case 4: return launch_cfg<3, 1, 1, 1, 2, 2, 8, 8>(ctx, p, s);
-            case 16: return launch_cfg<3, 1, 1, 1, 2, 2, 8, 16, 2, 2>(ctx, p, s);   // 8 waves: 2 K groups x (2x2), 16-channel chunks
-            case 17: return launch_cfg<3, 1, 1, 1, 2, 2, 8, 8, 2, 2>(ctx, p, s);
-            case 5: return launch_cfg<3, 1, 2, 1, 1, 4, 16, 8>(ctx, p, s);
-            case 6: return launch_cfg<3, 1, 2, 1, 1, 4, 64, 8>(ctx, p, s);
-            case 7: return launch_cfg<3, 1, 2, 1, 1, 4, 32, 8>(ctx, p, s);
-            case 8: return launch_cfg<3, 1, 1, 2, 2, 4, 32, 8, 4>(ctx, p, s);
-            case 9: return launch_cfg<3, 1, 1, 2, 2, 4, 16, 8, 4>(ctx, p, s);
-            case 10: return launch_cfg<3, 1, 1, 2, 2, 4, 32, 8, 2>(ctx, p, s);
-            case 14: return launch_cfg<3, 1, 1, 1, 2, 4, 16, 8, 4>(ctx, p, s);
-            case 15: return launch_cfg<3, 1, 1, 1, 2, 4, 8, 8, 4>(ctx, p, s);
-        }
-    } else {
-        // tile_cfg 36: fp32-equivalent products on the bf16 matrix pipe (conv_s2_bf3.hip) where a split filter was supplied -- unless SISIC_S2_BF16X3=0.  (Conditions on the arguments' shape only: an
-        // image's bits must not depend on the batch it is in.)
-        static const bool s2b_on = [] { const char* e = std::getenv("SISIC_S2_BF16X3"); return !e || std::atoi(e) != 0; }();
-        if ((cfg == 0 && s2b_on && conv_s2_bf3_applicable(a)) || cfg == 36) {
-            if (slots_query) { *slots_query = conv_s2_bf3_applicable(a) ? conv_s2_bf3_stats_slots(a) : 0; return SISIC_OK; }
-            return launch_conv_s2_bf3(ctx, a, s);
-        }
-        if (cfg == 0) cfg = p.Wout >= 24 ? 11 : (p.Wout >= 12 ? 12 : 18);   // measured (tools/conv_bench.py, B=64; 16->8: 66 -> 57 us)
-        switch (cfg) {
-            case 11: return launch_cfg<3, 2, 2, 1, 1, 4, 32, 8>(ctx, p, s);
-            case 12: return launch_cfg<3, 2, 2, 1, 1, 4, 16, 8>(ctx, p, s);
-            case 13: return launch_cfg<3, 2, 1, 1, 2, 2, 8, 8>(ctx, p, s);
-            case 18: return launch_cfg<3, 2, 1, 1, 2, 2, 8, 16, 2, 2>(ctx, p, s);   // latency mode: 8x8 pixels, 8 waves = 2 K groups x (2x2)
-            case 19: return launch_cfg<3, 2, 1, 1, 2, 2, 8, 8, 2, 2>(ctx, p, s);
-        }
-    }
-    set_error("conv2d: tile_cfg %d invalid for ksize %d stride %d", cfg, a.ksize, a.stride);
+    set_error("conv2d: internal: no direct tiling %d", plan.cfg);
     return SISIC_EINVAL;
+}
+
+// Plans once (conv_plan.h), opens the profile scope from the plan and hands (a, plan) to the chosen launcher.
+int launch_conv2d(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider, bool* carried) {
+    if (carried) *carried = false;
+    ConvPlan plan;
+    SISIC_TRY(conv_plan(a, &plan));
+    SISIC_REQUIRE(!plan.refusal[0], "%s", plan.refusal);
+    ProfileScope prof(ctx, s, plan.profile_kind, plan.bytes, plan.flops, plan.issued_flops, plan.profile_slot);
+    const GnFinJob* ride = (plan.carries_rider && carried) ? rider : nullptr;
+    int rc;
+    switch (plan.kernel) {
+        case CK_SMALLCOUT: rc = launch_conv_smallcout(ctx, a, plan, s); break;
+        case CK_DIRECT: rc = launch_conv_direct(ctx, a, plan, s); break;
+        case CK_POINTWISE: rc = launch_conv_pointwise(ctx, a, plan, s); break;
+        case CK_POINTWISE_BF3: rc = launch_conv_pointwise_bf3(ctx, a, plan, s, ride); break;
+        case CK_S2_BF3: rc = launch_conv_s2_bf3(ctx, a, plan, s); break;
+        default: rc = launch_conv_winograd(ctx, a, plan, s); break;
+    }
+    if (rc == SISIC_OK && ride) *carried = true;      // the plan's word, once the launch has been made
+    return rc;
 }
 
 }  // namespace sisic

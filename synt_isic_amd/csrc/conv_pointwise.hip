@@ -20,7 +20,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_plan.h"
 
 namespace sisic {
 
@@ -223,8 +223,6 @@ bool conv_pointwise_applicable(const sisic_conv_args& a) {
     return true;
 }
 
-int conv_pointwise_stats_slots(const sisic_conv_args& a) { return a.Hin * a.Win / 32; }       // one slot per 32 pixels, either tile
-
 template <int PRO, int NT>
 static int launch_pw(sisic_ctx* ctx, PwParams& p, int Cin, hipStream_t s) {
     constexpr int PX = PW_PX * NT;
@@ -241,8 +239,7 @@ static int launch_pw(sisic_ctx* ctx, PwParams& p, int Cin, hipStream_t s) {
     return SISIC_OK;
 }
 
-int launch_conv_pointwise(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s) {
-    SISIC_REQUIRE(conv_pointwise_applicable(a), "conv2d(pointwise): shape not supported by tile_cfg 20");
+int launch_conv_pointwise(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan&, hipStream_t s) {
     PwParams p{};
     const int Cin = a.c0 + a.c1;
     p.in0 = a.in0; p.in1 = a.in1; p.c0 = a.c0; p.c1 = a.c1; p.B = a.B; p.HW = a.Hin * a.Win;

@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_plan.h"
 #include "gn_finalize.h"
 
 namespace sisic {
@@ -56,7 +56,6 @@ struct PwbParams {
     GnFinJob rider;
 };
 
-constexpr int PWB_WAVES = 4;             // waves (= independent work items) per workgroup
 
 __device__ __forceinline__ float pwb_half_wave_sum(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
@@ -573,7 +572,6 @@ __global__ void __launch_bounds__(64 * PWB_WAVES, 4) conv_pwbk_kernel(const PwbP
 // split, packed exactly as above -- into LDS ONCE (Cin x 64 pixels x 6 bytes: 96 KB at 256 channels), then every wave runs the
 // contraction of its own channel item with operands that are two LDS reads per chunk and pixel block; filters from global memory
 // two chunks ahead as before.  The chain of MFMAs of an output is the one of the forms above: same bits.
-constexpr int PWBS_MAX_WAVES = 12;
 template <int PRO>
 __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const PwbParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -754,7 +752,6 @@ __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const Pw
     }
 }
 
-static bool pwbk_on() { static const bool on = [] { const char* e = std::getenv("SISIC_POINTWISE_KSPLIT"); return !e || std::atoi(e) != 0; }(); return on; }
 template <int PRO>
 static int launch_pwbk(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     p.n_co_items = p.Cout / 64;
@@ -773,12 +770,7 @@ static int launch_pwbk(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     return SISIC_OK;
 }
 
-// staged form: LDS holds the image's 64 pixels of every input channel as split operands (6 bytes per value) and the GroupNorm table
-static size_t pwbs_lds_bytes(int Cin) { return (size_t)(Cin / 8) * 2 * 64 * 24 + 8 * (size_t)Cin; }
-static bool pwbs_applicable(const sisic_conv_args& a) {
-    const int items = a.Cout / 64;
-    return items >= 6 && items <= PWBS_MAX_WAVES && pwbs_lds_bytes(a.c0 + a.c1) <= 150 * 1024;
-}
+// staged form (LDS: pwbs_lds_bytes, conv_plan.h)
 template <int PRO>
 static int launch_pwbs(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     p.n_co_items = p.Cout / 64;
@@ -827,9 +819,9 @@ static int launch_pwb(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
     return SISIC_OK;
 }
 
-int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s, const GnFinJob* rider, bool* carried) {
-    if (carried) *carried = false;
-    SISIC_REQUIRE(conv_pointwise_bf3_applicable(a), "conv2d(pointwise bf16x3): shape not supported by tile_cfg 28");
+// plan.form: which of the kernel's forms (conv_plan.cpp); rider: jobs this launch runs as extra workgroups, or NULL -- the plan
+// offers them only to the PRO == 0 instances of the two four-wave kernels (their workgroup is gn_finalize_kernel's: one job per wave)
+int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s, const GnFinJob* rider) {
     PwbParams p{};
     const int Cin = a.c0 + a.c1;
     p.in0 = a.in0; p.in1 = a.in1; p.c0 = a.c0; p.c1 = a.c1; p.B = a.B; p.HW = a.Hin * a.Win;
@@ -841,52 +833,18 @@ int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStrea
     p.out = a.out; p.stats = a.stats_out;
     p.nchunks = Cin / 8;
     const int pro = a.gn_scale == nullptr ? 0 : (a.gn_silu ? 2 : 1);
-    // the rider's jobs go with the PRO == 0 instances of the two four-wave kernels (their workgroup is gn_finalize_kernel's: one job
-    // per wave); *carried only once such a launch has been made -- the caller never re-derives which kernel was chosen
     static_assert(PWB_WAVES == GNF_WAVES, "a rider workgroup runs one finalisation job per wave");
-    auto with_rider = [&]() {
-        if (rider && carried && pro == 0) { p.rider = *rider; p.n_rider_wg = cdiv(rider->n_jobs, GNF_WAVES); }
-    };
-    auto done = [&](int rc) {
-        if (rc == SISIC_OK && p.n_rider_wg > 0) *carried = true;
-        return rc;
-    };
-    // 64-pixel items where they give every SIMD at least two waves (1024 SIMDs), 32-pixel items otherwise: a lone wave has
-    // nobody to hide its latencies.  (The choice depends on the batch; the bits of an output do not: its chain of MFMAs is the same.)
-    // (tile_cfg 29 / 30 force the 32- / 64-pixel form: tests of their bit-equality)
-    // the K-split form (tile_cfg 35 forces it) for the 16x16 and 8x8 levels' layers of up to 256 output channels -- by SHAPE only:
-    // its bits are its own.  Measured at batch 64 (profiles/r04/conv_bench_pointwise_forms.txt): 256 -> 256 @16 27.3 vs 34.2 us,
-    // 512 -> 256 @8 13.5 vs 24.9, 512 -> 256 @16 38.0 vs 38.7; NOT for 256 -> 768 (76.8 vs 50.7: twelve channel items already
-    // fill the chip, and four waves per item fetch the item's filters in four strands)
-    {
-        const bool ks_ok = p.nchunks % (4 * PWB_WAVES) == 0;        // (whole groups of four chunks per wave; the concat seam lies on a chunk boundary)
-        if (a.tile_cfg == 35) SISIC_REQUIRE(ks_ok, "conv2d(pointwise bf16x3, K-split): tile_cfg 35 needs a multiple of 128 input channels");
-        if (a.tile_cfg == 35 || (a.tile_cfg == 0 && ks_ok && p.HW <= 256 && a.Cout <= 256 && pwbk_on())) {
-            if (pro == 2) return launch_pwbk<2>(ctx, p, Cin, s);
-            if (pro == 1) return launch_pwbk<1>(ctx, p, Cin, s);
-            with_rider();
-            return done(launch_pwbk<0>(ctx, p, Cin, s));
-        }
+    if (rider) { p.rider = *rider; p.n_rider_wg = cdiv(rider->n_jobs, GNF_WAVES); }
+    switch (plan.form) {
+        case PWB_FORM_KSPLIT:
+            return pro == 2 ? launch_pwbk<2>(ctx, p, Cin, s) : pro == 1 ? launch_pwbk<1>(ctx, p, Cin, s) : launch_pwbk<0>(ctx, p, Cin, s);
+        case PWB_FORM_STAGED:
+            return pro == 2 ? launch_pwbs<2>(ctx, p, Cin, s) : pro == 1 ? launch_pwbs<1>(ctx, p, Cin, s) : launch_pwbs<0>(ctx, p, Cin, s);
+        case PWB_FORM_64PX:
+            return pro == 2 ? launch_pwb<2, 2>(ctx, p, Cin, s) : pro == 1 ? launch_pwb<1, 2>(ctx, p, Cin, s) : launch_pwb<0, 2>(ctx, p, Cin, s);
+        default:
+            return pro == 2 ? launch_pwb<2, 1>(ctx, p, Cin, s) : pro == 1 ? launch_pwb<1, 1>(ctx, p, Cin, s) : launch_pwb<0, 1>(ctx, p, Cin, s);
     }
-    // the staged form (tile_cfg 34 forces it) where a layer has 6 .. 12 channel items and enough 64-pixel workgroups for the chip
-    // (the choice depends on the batch; the bits do not)
-    if (a.tile_cfg == 34) SISIC_REQUIRE(pwbs_applicable(a), "conv2d(pointwise bf16x3, staged): tile_cfg 34 needs 384 .. 768 output channels and at most %d input channels", (150 * 1024) / 392);
-    if (a.tile_cfg == 34 || (a.tile_cfg == 0 && pwbs_applicable(a) && (int64_t)a.B * (p.HW / 64) >= 128)) {
-        if (pro == 2) return launch_pwbs<2>(ctx, p, Cin, s);
-        if (pro == 1) return launch_pwbs<1>(ctx, p, Cin, s);
-        return launch_pwbs<0>(ctx, p, Cin, s);
-    }
-    const bool wide = a.tile_cfg == 29 ? false : (a.tile_cfg == 30 ? true : (int64_t)a.B * (p.HW / 64) * (a.Cout / 64) >= 2048);
-    if (wide) {
-        if (pro == 2) return launch_pwb<2, 2>(ctx, p, Cin, s);
-        if (pro == 1) return launch_pwb<1, 2>(ctx, p, Cin, s);
-        with_rider();
-        return done(launch_pwb<0, 2>(ctx, p, Cin, s));
-    }
-    if (pro == 2) return launch_pwb<2, 1>(ctx, p, Cin, s);
-    if (pro == 1) return launch_pwb<1, 1>(ctx, p, Cin, s);
-    with_rider();
-    return done(launch_pwb<0, 1>(ctx, p, Cin, s));
 }
 
 }  // namespace sisic

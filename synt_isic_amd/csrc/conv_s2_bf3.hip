@@ -26,7 +26,7 @@
 // fetch -- 47 vs 42, 38 vs 38, 49 vs 38 us; filters one tap ahead instead of two, three waves per SIMD instead of four -- level.)
 #include <cstdlib>
 
-#include "common.h"
+#include "conv_plan.h"
 #include "pack_device.h"
 
 namespace sisic {
@@ -298,12 +298,10 @@ bool conv_s2_bf3_applicable(const sisic_conv_args& a) {
 }
 int conv_s2_bf3_stats_slots(const sisic_conv_args& a) { return cdiv((a.Hin + 1) / 2, S2B_TH) * cdiv((a.Win + 1) / 2, S2B_TW); }
 
-int launch_conv_s2_bf3(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s) {
-    SISIC_REQUIRE(conv_s2_bf3_applicable(a), "conv2d(stride-2 bf16x3): tile_cfg 36 needs ksize 3, stride 2, one input without GroupNorm prologue, "
-                  "Cin %% 8 == 0, Cout %% 64 == 0 and the split filter (sisic_conv_s2_pack) in w_winograd");
+int launch_conv_s2_bf3(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s) {
     S2bParams p{};
     p.in = a.in0; p.Cin = a.c0; p.B = a.B; p.H = a.Hin; p.W = a.Win;
-    p.Hout = (a.Hin + 1) / 2; p.Wout = (a.Win + 1) / 2;
+    p.Hout = plan.Hout; p.Wout = plan.Wout;
     p.wb = a.w_winograd; p.n_co64 = a.Cout / 64;
     p.bias = a.bias; p.Cout = a.Cout;
     p.chan_bias = a.chan_bias; p.chan_bias_stride = a.chan_bias_stride; p.residual = a.residual; p.relu = a.relu;

@@ -14,14 +14,14 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_plan.h"
 
 namespace sisic {
 
 // Tile = 32 x CS_TH output pixels.  CS_TH = 32 (256 threads) when the launch has workgroups to spare; 8 (one wave) when it
 // does not (a single 128x128 image is 16 tiles of 32x32).  A pixel's sum runs over the channels in the same order either
 // way, so the choice never changes a bit of the result.
-constexpr int CS_TW = 32, CS_PX = 4, CS_CIC = 2;
+constexpr int CS_PX = 4;             // (CS_TW, CS_CIC: conv_plan.h)
 constexpr int CS_IW = CS_TW + 2;
 constexpr int CS_IWP = 36;                                       // LDS row stride: float4-aligned rows
 template <int CS_TH>
@@ -223,8 +223,8 @@ __global__ void __launch_bounds__(CSGeom<CS_TH>::THR * KS, KS == 1 ? 3 : 4) conv
     }
 }
 
-// Used by launch_conv2d for ksize 3, stride 1, no upsample, Cout <= 4.
-int launch_conv_smallcout(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t s) {
+// ksize 3, stride 1, no upsample, Cout <= 4; plan.form: bit 0 = 32-row tiles (8 otherwise), bit 1 = four channel groups per workgroup
+int launch_conv_smallcout(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s) {
     ConvSmallParams p{};
     p.in0 = a.in0; p.in1 = a.in1; p.c0 = a.c0; p.c1 = a.c1; p.B = a.B; p.H = a.Hin; p.W = a.Win;
     p.w = a.w_packed; p.cout_pad = conv_cout_pad(a.Cout); p.bias = a.bias; p.Cout = a.Cout;
@@ -233,14 +233,10 @@ int launch_conv_smallcout(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t 
     p.out = a.out;
     p.tiles_x = cdiv(a.Win, CS_TW);
     p.nchunks = cdiv(a.c0 + a.c1, CS_CIC);
-    // tile_cfg 50 / 51 force the 32- / 8-row tile (tools/conv_bench.py); otherwise 32 rows from one workgroup per CU up
-    const bool spare = a.tile_cfg == 50 || (a.tile_cfg != 51 && (int64_t)a.B * p.tiles_x * cdiv(a.Hin, 32) >= 256);
+    const bool spare = plan.form & 1, ksplit = plan.form & 2;
     p.tiles_y = cdiv(a.Hin, spare ? 32 : 8);
     const int64_t nwg = (int64_t)a.B * p.tiles_x * p.tiles_y;
     SISIC_REQUIRE(nwg > 0 && nwg < (int64_t(1) << 31), "conv2d(small): grid too large");
-    // four channel groups per workgroup from 32 input channels up (a rule of the layer's shape: the groups' sums are added in
-    // their own order); tile_cfg 52 forces one group
-    const bool ksplit = a.tile_cfg != 52 && p.nchunks % 4 == 0 && p.nchunks >= 16;
     auto go = [&](auto th_tag, auto ks_tag) -> int {
         constexpr int TH = decltype(th_tag)::value, KSV = decltype(ks_tag)::value;
         auto kern = conv3x3_smallcout_kernel<TH, KSV>;
@@ -252,13 +248,8 @@ int launch_conv_smallcout(sisic_ctx* ctx, const sisic_conv_args& a, hipStream_t 
         return SISIC_OK;
     };
     using I = std::integral_constant<int, 1>;
-    if (ksplit) {
-        if (spare) SISIC_TRY(go(std::integral_constant<int, 32>{}, std::integral_constant<int, 4>{}));
-        else SISIC_TRY(go(std::integral_constant<int, 8>{}, std::integral_constant<int, 4>{}));
-    } else {
-        if (spare) SISIC_TRY(go(std::integral_constant<int, 32>{}, I{}));
-        else SISIC_TRY(go(std::integral_constant<int, 8>{}, I{}));
-    }
+    using R32 = std::integral_constant<int, 32>; using R8 = std::integral_constant<int, 8>; using K4 = std::integral_constant<int, 4>;
+    SISIC_TRY(ksplit ? (spare ? go(R32{}, K4{}) : go(R8{}, K4{})) : (spare ? go(R32{}, I{}) : go(R8{}, I{})));
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

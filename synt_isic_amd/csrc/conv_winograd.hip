@@ -20,7 +20,7 @@
 // small multiple of the direct kernel's (tests: same 2e-5 * max(1,|ref|) bound).
 #include <type_traits>
 
-#include "common.h"
+#include "conv_plan.h"
 #include "gn_merge.h"
 #include "pack_device.h"
 
@@ -1027,155 +1027,92 @@ static int launch_wino_pro(sisic_ctx* ctx, WinoParams& p, hipStream_t s) {
     return launch_wino<NIMG, TY, TX, 0, NW>(ctx, p, s);
 }
 
-// tile_cfg 60: 1 image x 8x8 tiles (16x16 output pixels), 8 waves;  61: 4 images x 4x4 tiles (8x8 outputs each), 8 waves;
-//          62 / 63: the same two tilings with 16 waves (one transform position per wave, 4 waves per SIMD)
-//          64..67 = 60..63 with the MFMA-first / stage-first phase stagger between SIMD partner waves
-//          68 / 69: second geometry, 32 tiles per workgroup, filters straight from global memory into registers:
-//              68 = 128 output channels x 16 waves (Cout > 64), 69 = 64 channels x 8 waves, two workgroups per CU
-//          78 / 79: 68 / 69 in latency mode: input channels K-split so that one image fills the chip (wino_latency_ksplit)
-//          (68 / 69 / 78 / 79 / 91 run the THIRD form, conv_winograd_col.inc -- same tiles, same bits, a wave owns a column of
-//           the position grid -- unless SISIC_WINO_COL=0;  70 / 71 force the third form, 72 / 73 the second: A/B and tests)
-//          90: tiling 67 with the input channels split over four workgroups per tile + splitk_reduce_kernel -- for the
-//              8x8 level, where 64 tiles x 64 channels per workgroup leave 3/4 of the CUs without work
-//          91: the same split on the second geometry: 128 channels x (two images x 16 tiles) per workgroup; bit-identical to 90
-int launch_conv_winograd(sisic_ctx* ctx, const sisic_conv_args& a, const float* u_packed, int cfg, hipStream_t s) {
+// The stream's scratch for the partial slabs of a K-split convolution, grown on demand.  It comes from hipMalloc and is therefore
+// at least 16-byte aligned (the reductions' float4 accesses rely on it).
+static int splitk_scratch(sisic_ctx* ctx, hipStream_t s, size_t floats, float** ptr) {
+    std::lock_guard<std::mutex> lock(ctx->splitk_mutex);
+    auto& buf = ctx->splitk[s];
+    if (buf.floats < floats) {
+        SISIC_HIP(hipStreamSynchronize(s));          // earlier launches on this stream may still read the old buffer
+        if (buf.p) SISIC_HIP(hipFree(buf.p));
+        buf.p = nullptr; buf.floats = 0;
+        SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&buf.p), floats * sizeof(float)));
+        buf.floats = floats;
+        ctx->scratch_generation.fetch_add(1);
+    }
+    SISIC_REQUIRE((reinterpret_cast<uintptr_t>(buf.p) & 15) == 0, "conv2d(winograd K-split): scratch is not 16-byte aligned");
+    *ptr = buf.p;
+    return SISIC_OK;
+}
+
+// Every Winograd kernel of the plan (conv_plan.h: the configurations' table; the filters travel in a.w_winograd)
+int launch_conv_winograd(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s) {
+    const WinoCfg& w = *wino_cfg_row(plan.cfg);
+    const float* u_packed = a.w_winograd;
     WinoParams p{};
     p.in0 = a.in0; p.in1 = a.in1; p.c0 = a.c0; p.c1 = a.c1;
     p.B = a.B; p.Hin = a.Hin; p.Win = a.Win;
     p.ups = a.upsample ? 1 : 0;
-    p.Hc = a.Hin << p.ups; p.Wc = a.Win << p.ups;
+    p.Hc = plan.Hout; p.Wc = plan.Wout;
     p.u = u_packed; p.cout_pad = conv_cout_pad(a.Cout);
     p.bias = a.bias; p.Cout = a.Cout;
     p.gn_scale = a.gn_scale; p.gn_shift = a.gn_shift; p.gn_silu = a.gn_silu;
     p.chan_bias = a.chan_bias; p.chan_bias_stride = a.chan_bias_stride; p.residual = a.residual; p.relu = a.relu;
     p.out = a.out;
     p.stats = a.stats_out;
-    SISIC_REQUIRE(4.0 * std::max(a.c0, a.c1) * a.Hin * a.Win * ((cfg == 61 || cfg == 63 || cfg == 65 || cfg == 67 || cfg == 90) ? 4 : 1) < 4294967296.0,
-                  "conv2d(winograd): per-thread load offsets are 32-bit; this tensor needs the direct kernel");
-    p.stagger = ((cfg >= 64 && cfg <= 67) || cfg == 90) ? 1 : 0;
-    p.ksplit = 1;
-    static const bool col_default = [] { const char* e = std::getenv("SISIC_WINO_COL"); return !e || std::atoi(e) != 0; }();
-    if (cfg == 74 && conv_finalizes(a)) {       // (one 16x16-pixel tile per image: conv_mfma.hip)
-        SISIC_REQUIRE(a.fin_beta && a.fin_scale && a.fin_shift, "conv2d: fin_gamma given without fin_beta / fin_scale / fin_shift");
+    p.stagger = w.stagger ? 1 : 0;
+    p.ksplit = plan.ksplit;
+    const size_t HW = (size_t)p.Hc * p.Wc, planes = (size_t)a.B * a.Cout;
+    float* scratch = nullptr;
+    if (plan.ksplit > 1) {
+        SISIC_TRY(splitk_scratch(ctx, s, (size_t)plan.ksplit * planes * HW, &scratch));
+        p.part = scratch;
+    }
+    if (w.geom != WG_FIRST) {       // the second / third geometry's and the bf16x3 kernels' filter layouts follow the first in the buffer
+        p.uw = u_packed + winograd_first_numel(a.Cout, a.c0 + a.c1) + (w.geom == WG_BF3 ? winograd_wide_numel(a.Cout, a.c0 + a.c1) : 0);
+        p.cout_pad = round_up(a.Cout, 128);
+    }
+    if (plan.finalizes && w.geom == WG_BF3 && plan.ksplit == 1) {       // (one 16x16-pixel tile per image: the kernel finalizes)
         p.fin_gamma = a.fin_gamma; p.fin_beta = a.fin_beta; p.fin_scale = a.fin_scale; p.fin_shift = a.fin_shift;
         p.fin_mean_rstd = a.fin_mean_rstd; p.fin_groups = a.fin_groups; p.fin_eps = a.fin_eps;
     }
-    if (cfg == 74) {                // fp32-equivalent products on the bf16 pipe (conv_winograd_bf3.inc)
-        // (a nearest-2x input is read through the staging plan's addresses: all 16 positions are multiplied, where the f32
-        //  upsample form multiplies 9 -- which of the two is faster depends on the plane, conv_mfma.hip)
-        p.uw = u_packed + winograd_first_numel(a.Cout, a.c0 + a.c1) + winograd_wide_numel(a.Cout, a.c0 + a.c1);
-        p.cout_pad = round_up(a.Cout, 128);
-        return launch_bf3_pro(ctx, p, s);
+    const bool pair = w.imgs == 2, wide = w.waves == 16;
+    switch (plan.kernel) {
+        case CK_WINO_FIRST:
+            if (w.imgs == 4) SISIC_TRY(w.waves == 16 ? (launch_wino_pro<4, 4, 4, 16>(ctx, p, s)) : (launch_wino_pro<4, 4, 4, 8>(ctx, p, s)));
+            else SISIC_TRY(w.waves == 16 ? (launch_wino_pro<1, 8, 8, 16>(ctx, p, s)) : (launch_wino_pro<1, 8, 8, 8>(ctx, p, s)));
+            break;
+        case CK_WINO_SECOND:
+            SISIC_TRY(pair ? (launch_wide_pro<128, 16, true>(ctx, p, s)) : wide ? (launch_wide_pro<128, 16>(ctx, p, s)) : (launch_wide_pro<64, 8>(ctx, p, s)));
+            break;
+        case CK_WINO_THIRD:
+            SISIC_TRY(pair ? (launch_col_pro<128, 16, true>(ctx, p, s)) : wide ? (launch_col_pro<128, 16>(ctx, p, s)) : (launch_col_pro<64, 8>(ctx, p, s)));
+            break;
+        default:      // CK_WINO_BF3; K-split: four images per workgroup
+            // (a nearest-2x input is read through the staging plan's addresses: all 16 positions are multiplied, where the f32
+            //  upsample form multiplies 9 -- which of the two is faster depends on the plane, conv_plan.cpp)
+            SISIC_TRY(plan.ksplit > 1 ? launch_bf3q_pro(ctx, p, s) : launch_bf3_pro(ctx, p, s));
     }
-    if ((cfg >= 68 && cfg <= 73) || cfg == 78 || cfg == 79) {           // second / third geometry (conv_winograd_wide.inc, _col.inc)
-        SISIC_REQUIRE(!p.ups, "conv2d(winograd wide): no upsample form");
-        p.uw = u_packed + winograd_first_numel(a.Cout, a.c0 + a.c1);
-        p.cout_pad = round_up(a.Cout, 128);
-        const bool wide = cfg == 68 || cfg == 78 || cfg == 70 || cfg == 72;
-        const bool col = (cfg == 70 || cfg == 71) ? true : ((cfg == 72 || cfg == 73) ? false : col_default);
-        const int K = (cfg == 78 || cfg == 79) ? wino_latency_ksplit(a.Cout, a.c0 + a.c1, p.Hc, p.Wc) : 1;
-        auto launch = [&]() -> int {
-            if (col) return wide ? launch_col_pro<128, 16>(ctx, p, s) : launch_col_pro<64, 8>(ctx, p, s);
-            return wide ? launch_wide_pro<128, 16>(ctx, p, s) : launch_wide_pro<64, 8>(ctx, p, s);
-        };
-        if (K == 1) return launch();
-        // latency mode: the input channels split K ways over workgroups, partial slabs summed by the plane reduction
-        const size_t HW = (size_t)p.Hc * p.Wc, planes = (size_t)a.B * a.Cout;
-        const size_t need = (size_t)K * planes * HW;
-        float* scratch = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(ctx->splitk_mutex);
-            auto& buf = ctx->splitk[s];
-            if (buf.floats < need) {
-                SISIC_HIP(hipStreamSynchronize(s));
-                if (buf.p) SISIC_HIP(hipFree(buf.p));
-                buf.p = nullptr; buf.floats = 0;
-                SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&buf.p), need * sizeof(float)));
-                buf.floats = need;
-                ctx->scratch_generation.fetch_add(1);
-            }
-            scratch = buf.p;
-        }
-        p.ksplit = K;
-        p.part = scratch;
-        SISIC_TRY(launch());
+    if (plan.ksplit == 1) return SISIC_OK;
+    // the partial slabs summed: latency mode's plane reduction, or the 8x8 level's in the form the plan chose
+    if (w.ksplit < 0) {
         const int segs = wino_latency_segments(p.Hc, p.Wc);
-        hipLaunchKernelGGL(splitk_reduce_plane_kernel, dim3((unsigned)(planes * segs)), dim3(256), 0, s, scratch, K, (int)planes,
+        hipLaunchKernelGGL(splitk_reduce_plane_kernel, dim3((unsigned)(planes * segs)), dim3(256), 0, s, scratch, plan.ksplit, (int)planes,
                            (int)HW, segs, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride, a.residual, a.relu, a.out, a.stats_out);
-        SISIC_HIP(hipGetLastError());
-        return SISIC_OK;
+    } else if (plan.form == REDUCE_64PX) {
+        const ReduceFin rf{a.fin_gamma, a.fin_beta, a.fin_scale, a.fin_shift, a.fin_mean_rstd, a.fin_groups, a.fin_eps};
+        auto kern = plan.finalizes ? splitk_reduce64_kernel<true> : splitk_reduce64_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((planes + 15) / 16)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(scratch), (int)planes, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride,
+                           reinterpret_cast<const float4*>(a.residual), a.relu, reinterpret_cast<float4*>(a.out),
+                           reinterpret_cast<float4*>(a.stats_out), rf);
+    } else {
+        hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, s, scratch,
+                           (int)planes, (int)HW, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride, a.residual, a.relu,
+                           a.out, a.stats_out);
     }
-    if (cfg == 90 || cfg == 91 || cfg == 92) {
-        constexpr int K = 4;
-        const size_t HW = (size_t)p.Hc * p.Wc, planes = (size_t)a.B * a.Cout;
-        SISIC_REQUIRE(HW <= 256 && (cdiv(a.c0 + a.c1, W_CIC) % K) == 0,
-                      "conv2d(winograd K-split): needs <= 256 output pixels per image and a multiple of %d input channels", K * W_CIC);
-        const size_t need = (size_t)K * planes * HW;
-        float* scratch = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(ctx->splitk_mutex);
-            auto& buf = ctx->splitk[s];
-            if (buf.floats < need) {
-                SISIC_HIP(hipStreamSynchronize(s));          // earlier launches on this stream may still read the old buffer
-                if (buf.p) SISIC_HIP(hipFree(buf.p));
-                buf.p = nullptr; buf.floats = 0;
-                SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&buf.p), need * sizeof(float)));
-                buf.floats = need;
-                ctx->scratch_generation.fetch_add(1);
-            }
-            scratch = buf.p;
-        }
-        p.ksplit = K;
-        p.part = scratch;
-        if (cfg == 92) {          // bf16x3 products, four images per workgroup (conv_winograd_bf3.inc)
-            SISIC_REQUIRE(!p.ups && p.Hc <= 8 && p.Wc <= 8, "conv2d(winograd bf16x3, 8x8): plain stride-1 convolutions of at most 8x8 pixels");
-            p.uw = u_packed + winograd_first_numel(a.Cout, a.c0 + a.c1) + winograd_wide_numel(a.Cout, a.c0 + a.c1);
-            p.cout_pad = round_up(a.Cout, 128);
-            SISIC_TRY(launch_bf3q_pro(ctx, p, s));
-        } else if (cfg == 91) {   // second geometry, two images per workgroup (conv_winograd_wide.inc, PAIR)
-            SISIC_REQUIRE(!p.ups && p.Hc <= 8 && p.Wc <= 8, "conv2d(winograd wide, image pairs): plain stride-1 convolutions of at most 8x8 pixels");
-            p.uw = u_packed + winograd_first_numel(a.Cout, a.c0 + a.c1);
-            p.cout_pad = round_up(a.Cout, 128);
-            if (col_default) SISIC_TRY((launch_col_pro<128, 16, true>(ctx, p, s)));
-            else SISIC_TRY((launch_wide_pro<128, 16, true>(ctx, p, s)));
-        } else {
-            SISIC_TRY((launch_wino_pro<4, 4, 4, 16>(ctx, p, s)));
-        }
-        const bool al16 = ((reinterpret_cast<uintptr_t>(scratch) | reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.out) |
-                            reinterpret_cast<uintptr_t>(a.stats_out)) & 15) == 0;
-        if (HW == 64 && al16) {
-            const bool fin = conv_finalizes(a);
-            const ReduceFin rf{a.fin_gamma, a.fin_beta, a.fin_scale, a.fin_shift, a.fin_mean_rstd, a.fin_groups, a.fin_eps};
-            if (fin) {
-                SISIC_REQUIRE(a.fin_beta && a.fin_scale && a.fin_shift, "conv2d: fin_gamma given without fin_beta / fin_scale / fin_shift");
-                hipLaunchKernelGGL(splitk_reduce64_kernel<true>, dim3((unsigned)((planes + 15) / 16)), dim3(256), 0, s,
-                                   reinterpret_cast<const float4*>(scratch), (int)planes, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride,
-                                   reinterpret_cast<const float4*>(a.residual), a.relu, reinterpret_cast<float4*>(a.out),
-                                   reinterpret_cast<float4*>(a.stats_out), rf);
-            } else {
-                hipLaunchKernelGGL(splitk_reduce64_kernel<false>, dim3((unsigned)((planes + 15) / 16)), dim3(256), 0, s,
-                                   reinterpret_cast<const float4*>(scratch), (int)planes, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride,
-                                   reinterpret_cast<const float4*>(a.residual), a.relu, reinterpret_cast<float4*>(a.out),
-                                   reinterpret_cast<float4*>(a.stats_out), rf);
-            }
-        }
-        else
-            hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, s, scratch,
-                               (int)planes, (int)HW, a.Cout, a.bias, a.chan_bias, a.chan_bias_stride, a.residual, a.relu,
-                               a.out, a.stats_out);
-        SISIC_HIP(hipGetLastError());
-        return SISIC_OK;
-    }
-    switch (cfg) {
-        case 64: return launch_wino_pro<1, 8, 8, 8>(ctx, p, s);
-        case 65: return launch_wino_pro<4, 4, 4, 8>(ctx, p, s);
-        case 66: return launch_wino_pro<1, 8, 8, 16>(ctx, p, s);
-        case 67: return launch_wino_pro<4, 4, 4, 16>(ctx, p, s);
-        case 61: return launch_wino_pro<4, 4, 4, 8>(ctx, p, s);
-        case 62: return launch_wino_pro<1, 8, 8, 16>(ctx, p, s);
-        case 63: return launch_wino_pro<4, 4, 4, 16>(ctx, p, s);
-        default: return launch_wino_pro<1, 8, 8, 8>(ctx, p, s);
-    }
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
 }
 
 }  // namespace sisic

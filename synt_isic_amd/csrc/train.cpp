@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "conv_plan.h"
 #include "train.h"
 #include "unet_internal.h"
 
@@ -225,10 +226,7 @@ struct Bwd {
             a.w_winograd = (op.stride == 1 && !op.qkv_of && u->use_winograd) ? c.wino_t : nullptr;
             a.out = da;
             if (in_place) { a.out = g0; a.residual = g0; }
-            if (u->latency_mode) {           // the forward's small-batch tile choices (unet.cpp, Fwd::conv) for the data gradient
-                if (c.k == 3 && op.stride == 1 && a.w_winograd && Cin > 4 && Ho >= 12 && Wo >= 12) a.tile_cfg = 79;
-                else if (c.k == 1) a.tile_cfg = 22;
-            }
+            if (u->latency_mode) a.tile_cfg = conv_latency_cfg(a);      // the forward's small-batch tile choices for the data gradient
             SISIC_TRY(launch_conv2d(u->ctx, a, s));
         }
         if (in_place) return SISIC_OK;

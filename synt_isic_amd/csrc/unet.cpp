@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 
+#include "conv_plan.h"
 #include "gn_finalize.h"
 #include "unet_internal.h"
 
@@ -408,17 +409,8 @@ struct Fwd {
         if (gn_prologue) { a.gn_scale = gsc; a.gn_shift = gsh; a.gn_silu = silu ? 1 : 0; }
         a.chan_bias = chan_bias; a.chan_bias_stride = tproj_stride;
         a.residual = residual; a.out = out;
-        if (u->latency_mode) {
-            // single-image latency (the reference's own call pattern, image_generator.py:379: batch 1): the Winograd
-            // convolutions split their input channels over workgroups (tile_cfg 78 / 79) and the 1x1 convolutions take the
-            // 64-pixel tiles, so that one image offers a few hundred workgroups per layer.  Chosen from the layer shape only:
-            // inside this mode an image's bits are again independent of the batch.
-            // (the 64-channel, two-workgroups-per-CU form for every Cout: at one image it is level with or ahead of the
-            //  128-channel form on every layer, profiles/r02/ksplit_in_place_ab.txt rows 76 (128-channel) / 77 (64-channel))
-            if (c.k == 3 && stride == 1 && !ups && a.w_winograd && c.cout > 4 && H >= 12 && W >= 12) a.tile_cfg = 79;
-            else if (c.k == 1 && stride == 1) a.tile_cfg = 22;
-            else if (c.k == 3 && stride == 2) a.tile_cfg = 18;      // 8x8-pixel tiles, two K groups of waves: 189 -> 105 us for the three downsamplers of one 128x128 image
-        }
+        // single-image latency (the reference's own call pattern, image_generator.py:379: batch 1): conv_plan.cpp
+        if (u->latency_mode) a.tile_cfg = conv_latency_cfg(a);
         if (normed_later && u->fuse_gn) {          // a GroupNorm reads this output: have the epilogue leave partials
             const int slots = conv_stats_slots(a);
             if (slots > 0) {

@@ -1145,3 +1145,61 @@ def test_conv_finalizes_its_own_groupnorm_at_the_8x8_level():
             # without stats_out as well
             _, fin2 = ops.conv2d(d(xs), wp, cout, 3, finalize=(d(gamma), d(beta), 32, 1e-5), **kw)
             assert torch.equal(fin2[0], sc) and torch.equal(fin2[1], sh)
+
+
+# (tile_cfg, H, W, upsample, Cout, groups, residual misaligned by one float, what sisic_conv_finalizes must answer)
+_FIN_CASES = [(cfg, 8, 8, 0, 256, 32, False, 1) for cfg in (90, 91, 92, 0)] + \
+             [(cfg, 8, 8, 0, 256, 32, True, 0) for cfg in (90, 91, 92, 0)] + \
+             [(0, 7, 7, 0, 256, 32, False, 0), (0, 8, 8, 0, 256, 16, False, 0), (74, 16, 16, 0, 64, 8, False, 1),
+              (74, 32, 32, 0, 256, 32, False, 0), (74, 8, 8, 1, 256, 32, False, 0)]
+
+
+@pytest.mark.parametrize("cfg,H,W,ups,cout,groups,res_off,expect", _FIN_CASES)
+def test_conv_writes_fin_outputs_exactly_where_the_predicate_says(cfg, H, W, ups, cout, groups, res_off, expect):
+    """The fin_* fields stay set WHATEVER sisic_conv_finalizes() answers (ops.conv2d clears them where it answers 0): the launch
+    overwrites fin_scale / fin_shift -- bit-equal to sisic_groupnorm_finalize on the partials it leaves -- exactly where the
+    predicate says 1; where it says 0 they are untouched (sisic.h: the fields are ignored) and the output is still right."""
+    import ctypes as C
+    from synt_isic_amd import _lib, ops
+    d = lambda t: t.to(DEV).contiguous()
+    B, cin = 5, 128
+    Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
+    x = _rand(B, cin, H, W, seed=720)
+    w = _rand(cout, cin, 3, 3, seed=721, scale=(9 * cin) ** -0.5)
+    b, res = _rand(cout, seed=722), _rand(B, cout, Ho, Wo, seed=723)
+    gamma, beta = 1.0 + 0.1 * _rand(cout, seed=724), 0.1 * _rand(cout, seed=725)
+    gn = (1.0 + 0.3 * _rand(B, cin, seed=726), 0.3 * _rand(B, cin, seed=727))
+    xd, bd, gd, bed, gn0, gn1 = d(x), d(b), d(gamma), d(beta), d(gn[0]), d(gn[1])
+    wp, ww = ops.pack_conv_weight(d(w)), ops.pack_winograd_weight(d(w))
+    res_buf = torch.empty(res.numel() + 1, dtype=torch.float32, device=DEV)
+    res_d = res_buf[1:] if res_off else res_buf[:-1]            # a view one float off the allocation's alignment
+    res_d.copy_(res.reshape(-1))
+    out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=DEV)
+    SENTINEL = -7.25
+    fin_scale = torch.full((B, cout), SENTINEL, dtype=torch.float32, device=DEV)
+    fin_shift = torch.full((B, cout), SENTINEL, dtype=torch.float32, device=DEV)
+    lib = _lib.load()
+    a = _lib.ConvArgs()
+    a.in0 = xd.data_ptr(); a.c0 = cin; a.B = B; a.Hin = H; a.Win = W
+    a.upsample = ups; a.ksize = 3; a.stride = 1
+    a.w_packed = wp.data_ptr(); a.bias = bd.data_ptr(); a.Cout = cout
+    a.gn_scale = gn0.data_ptr(); a.gn_shift = gn1.data_ptr(); a.gn_silu = 1
+    a.residual = res_d.data_ptr(); a.out = out.data_ptr(); a.tile_cfg = cfg
+    a.w_winograd = ww.data_ptr()
+    assert (a.residual % 16 != 0) == res_off
+    slots = lib.sisic_conv_stats_slots(C.byref(a))
+    assert slots > 0
+    stats = torch.empty((B, cout, slots, 4), dtype=torch.float32, device=DEV)
+    a.stats_out = stats.data_ptr()
+    a.fin_gamma = gd.data_ptr(); a.fin_beta = bed.data_ptr(); a.fin_groups = groups; a.fin_eps = 1e-5
+    a.fin_scale = fin_scale.data_ptr(); a.fin_shift = fin_shift.data_ptr()
+    says = lib.sisic_conv_finalizes(C.byref(a))
+    assert says == expect, f"sisic_conv_finalizes answers {says}"
+    _lib.check(lib.sisic_conv2d(ops.context(xd.device), C.byref(a), ops._stream(xd.device)))
+    torch.cuda.synchronize()
+    _close(out, _conv_ref(x, w, b, upsample=bool(ups), gn=gn, gn_silu=True, residual=res), what=f"fin case cfg {cfg} {H}x{W}")
+    if says:
+        sc, sh = ops.groupnorm_finalize(stats, Ho * Wo, gd, bed, groups, 1e-5)
+        assert torch.equal(fin_scale, sc) and torch.equal(fin_shift, sh)
+    else:
+        assert bool((fin_scale == SENTINEL).all()) and bool((fin_shift == SENTINEL).all()), "fin_scale / fin_shift written although the predicate says 0"

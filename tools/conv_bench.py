@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the distinct convolution instances of the reference UNet (B=64, 3x64x64 input) per tile
-configuration through the C ABI.  Tuning aid for the dispatch table in conv_mfma.hip; not a test.
+configuration through the C ABI.  Tuning aid for the configuration tables of conv_plan.h / conv_plan.cpp; not a test.
 
     python tools/conv_bench.py [--batch 64] [--iters 20] [--cfgs all|auto]
 """
