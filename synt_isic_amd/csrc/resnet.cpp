@@ -11,6 +11,7 @@
 #include <map>
 
 #include "common.h"
+#include "workspace.h"
 
 using namespace sisic;
 
@@ -35,12 +36,6 @@ struct Block {
     FoldedConv conv1, conv2, down;   // down.k == 0 when the shortcut is the identity
 };
 
-struct RBlock {
-    float* p;
-    size_t bytes;
-    bool free_;
-};
-
 }  // namespace
 
 struct sisic_resnet {
@@ -56,7 +51,7 @@ struct sisic_resnet {
     float* d_fc_w = nullptr;
     float* d_fc_b = nullptr;
     std::vector<float*> owned;
-    std::vector<RBlock> pool;
+    Pool pool;
     int ws_B = 0, ws_H = 0, ws_W = 0;       // shape the pooled blocks were sized for (see workspace_for)
     bool loaded = false;
 
@@ -193,22 +188,6 @@ int derive_from_host(sisic_resnet* r, hipStream_t s) {
     return SISIC_OK;
 }
 
-int pool_get(sisic_resnet* r, size_t floats, float** out) {
-    const size_t bytes = floats * sizeof(float);
-    for (auto& b : r->pool)
-        if (b.free_ && b.bytes == bytes) { b.free_ = false; *out = b.p; return SISIC_OK; }
-    void* p = nullptr;
-    SISIC_HIP(hipMalloc(&p, bytes));
-    r->pool.push_back({static_cast<float*>(p), bytes, false});
-    *out = static_cast<float*>(p);
-    return SISIC_OK;
-}
-
-void pool_put(sisic_resnet* r, float* p) {
-    for (auto& b : r->pool)
-        if (b.p == p) { b.free_ = true; return; }
-}
-
 // The pool matches blocks by exact size, so every distinct (batch, resolution) would leave its own full set of
 // activation buffers behind (the stem output alone is B*64*112*112*4 bytes).  Like the UNet's check_shape, the pool is
 // therefore emptied whenever the input shape changes: resident workspace = what the current shape needs, whatever the
@@ -216,8 +195,7 @@ void pool_put(sisic_resnet* r, float* p) {
 int workspace_for(sisic_resnet* r, int B, int H, int W) {
     if (r->ws_B == B && r->ws_H == H && r->ws_W == W) return SISIC_OK;
     SISIC_HIP(hipDeviceSynchronize());       // earlier launches may still use the blocks
-    for (auto& b : r->pool) (void)hipFree(b.p);
-    r->pool.clear();
+    r->pool.release_all();
     r->ws_B = B; r->ws_H = H; r->ws_W = W;
     return SISIC_OK;
 }
@@ -234,6 +212,90 @@ int run_conv(sisic_resnet* r, const FoldedConv& c, const float* in, int B, int H
 }
 
 inline int out_dim(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / stride + 1; }
+
+// The forward pass every entry point below runs: [pre-processing ->] stem -> max-pool -> the 8 blocks -> avgpool + fc.
+// Options in, what the caller goes on with out.  Every activation is a block of the caller's scope; what no option keeps
+// goes back to the pool as soon as its last reader has been launched.
+struct Trunk {
+    bool preprocess = true;
+    float* stem_out = nullptr;   // stop after the stem, which writes here (sisic_resnet_stem)
+    bool keep = false;           // keep c1, the max-pool output and every block's t1 and output (the input gradient reads them)
+    bool split_last = false;     // last block: bn2(conv2(.)) alone into ylast, then relu(. + identity) (Grad-CAM reads ylast)
+    float* logits = nullptr;     // where the logits go; nullptr: into a block of the scope, returned here
+    struct Saved { float* t1; float* out; int h, w, bh, bw; };
+    std::vector<Saved> saved;    // keep: one per block
+    float* c1 = nullptr;         // relu(bn1(conv1(.))) [B, 64, c1h, c1w]
+    float* m = nullptr;          // its max-pool
+    int c1h = 0, c1w = 0;
+    float* act = nullptr;        // the last block's output [B, 512, h, w]
+    float* ylast = nullptr;
+    int h = 0, w = 0;
+};
+
+int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int W, Trunk& t, hipStream_t s) {
+    const float* cur = x;
+    int h = H, w = W;
+    float* pre = nullptr;
+    if (t.preprocess) {
+        const int S = 224;                      // CLASSIFIER_IMAGE_SIZE, XAI.py
+        SISIC_TRY(ws.get((size_t)B * 3 * S * S, &pre));
+        SISIC_TRY(launch_preprocess(r->ctx, x, pre, B, H, W, S, S, s));
+        cur = pre; h = S; w = S;
+    }
+    // stem: conv7x7 s2 (+BN) + ReLU, maxpool 3x3 s2
+    t.c1h = out_dim(h, 7, 2); t.c1w = out_dim(w, 7, 2);
+    t.c1 = t.stem_out;
+    if (!t.c1) SISIC_TRY(ws.get((size_t)B * 64 * t.c1h * t.c1w, &t.c1));
+    SISIC_TRY(run_conv(r, r->stem, cur, B, h, w, nullptr, true, t.c1, s));
+    if (pre) ws.put(pre);
+    if (t.stem_out) return SISIC_OK;
+    h = t.c1h; w = t.c1w;
+    if (t.keep) SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "resnet_input_gradient: odd feature map");
+    const int mh = out_dim(h, 3, 2), mw = out_dim(w, 3, 2);
+    SISIC_TRY(ws.get((size_t)B * 64 * mh * mw, &t.m));
+    SISIC_TRY(launch_maxpool(r->ctx, t.c1, t.m, B, 64, h, w, s));
+    if (!t.keep) ws.put(t.c1);
+    float* act = t.m;
+    h = mh; w = mw;
+    for (const Block& b : r->blocks) {
+        const bool split = t.split_last && &b == &r->blocks.back();
+        const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
+        if (t.keep)
+            SISIC_REQUIRE(b.conv1.stride == 1 || (h % 2 == 0 && w % 2 == 0), "resnet_input_gradient: odd feature map %dx%d", h, w);
+        float* t1 = nullptr;
+        SISIC_TRY(ws.get((size_t)B * b.conv1.cout * bh * bw, &t1));
+        SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
+        const float* identity = act;
+        float* ds = nullptr;
+        if (b.down.k) {
+            SISIC_TRY(ws.get((size_t)B * b.down.cout * bh * bw, &ds));
+            SISIC_TRY(run_conv(r, b.down, act, B, h, w, nullptr, false, ds, s));
+            identity = ds;
+        }
+        float* t2 = nullptr;
+        const size_t n_out = (size_t)B * b.conv2.cout * bh * bw;
+        SISIC_TRY(ws.get(n_out, &t2));
+        if (!split) {
+            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, identity, true, t2, s));    // relu(bn2(conv2) + identity)
+        } else {
+            SISIC_TRY(ws.get(n_out, &t.ylast));
+            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, nullptr, false, t.ylast, s));
+            SISIC_TRY(launch_add_relu(r->ctx, t.ylast, identity, t2, (int64_t)n_out, s));
+        }
+        if (ds) ws.put(ds);
+        if (t.keep) {
+            t.saved.push_back({t1, t2, h, w, bh, bw});
+        } else {
+            ws.put(t1);
+            ws.put(act);
+        }
+        act = t2; h = bh; w = bw;
+    }
+    if (!t.logits) SISIC_TRY(ws.get((size_t)B * r->num_classes, &t.logits));
+    SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, t.logits, B, r->blocks.back().conv2.cout, h * w, r->num_classes, s));
+    t.act = act; t.h = h; t.w = w;
+    return SISIC_OK;
+}
 
 }  // namespace
 
@@ -253,15 +315,13 @@ int sisic_resnet_destroy(sisic_resnet* r) {
     if (!r) return SISIC_OK;
     (void)hipDeviceSynchronize();
     for (auto p : r->owned) (void)hipFree(p);
-    for (auto& b : r->pool) (void)hipFree(b.p);
+    r->pool.release_all();
     delete r;
     return SISIC_OK;
 }
 
 int64_t sisic_resnet_workspace_bytes(const sisic_resnet* r) {
-    int64_t n = 0;
-    if (r) for (const auto& b : r->pool) n += (int64_t)b.bytes;
-    return n;
+    return r ? r->pool.bytes() : 0;
 }
 
 int sisic_resnet_num_tensors(const sisic_resnet* r) { return r ? (int)r->names.size() : 0; }
@@ -355,67 +415,11 @@ int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, 
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<float*> live;
-    auto get = [&](size_t floats, float** p) {
-        const int rc = pool_get(r, floats, p);
-        if (rc == SISIC_OK) live.push_back(*p);
-        return rc;
-    };
-    auto put = [&](float* p) {
-        pool_put(r, p);
-        live.erase(std::remove(live.begin(), live.end(), p), live.end());
-    };
-    auto body = [&]() -> int {
-        const float* cur = x;
-        int h = H, w = W;
-        float* pre = nullptr;
-        if (preprocess) {
-            const int S = 224;                      // CLASSIFIER_IMAGE_SIZE, XAI.py
-            SISIC_TRY(get((size_t)B * 3 * S * S, &pre));
-            SISIC_TRY(launch_preprocess(r->ctx, x, pre, B, H, W, S, S, s));
-            cur = pre; h = S; w = S;
-        }
-        // stem: conv7x7 s2 (+BN) + ReLU, maxpool 3x3 s2
-        int oh = out_dim(h, 7, 2), ow = out_dim(w, 7, 2);
-        float* c1 = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * oh * ow, &c1));
-        SISIC_TRY(run_conv(r, r->stem, cur, B, h, w, nullptr, true, c1, s));
-        if (pre) put(pre);
-        h = oh; w = ow;
-        oh = out_dim(h, 3, 2); ow = out_dim(w, 3, 2);
-        float* act = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * oh * ow, &act));
-        SISIC_TRY(launch_maxpool(r->ctx, c1, act, B, 64, h, w, s));
-        put(c1);
-        h = oh; w = ow;
-        int ch = 64;
-        for (const Block& b : r->blocks) {
-            const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
-            float* t1 = nullptr;
-            SISIC_TRY(get((size_t)B * b.conv1.cout * bh * bw, &t1));
-            SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
-            const float* identity = act;
-            float* ds = nullptr;
-            if (b.down.k) {
-                SISIC_TRY(get((size_t)B * b.down.cout * bh * bw, &ds));
-                SISIC_TRY(run_conv(r, b.down, act, B, h, w, nullptr, false, ds, s));
-                identity = ds;
-            }
-            float* t2 = nullptr;
-            SISIC_TRY(get((size_t)B * b.conv2.cout * bh * bw, &t2));
-            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, identity, true, t2, s));    // relu(bn2(conv2) + identity)
-            put(t1);
-            if (ds) put(ds);
-            put(act);
-            act = t2; h = bh; w = bw; ch = b.conv2.cout;
-        }
-        SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, logits, B, ch, h * w, r->num_classes, s));
-        put(act);
-        return SISIC_OK;
-    };
-    const int rc = body();
-    for (float* p : live) pool_put(r, p);
-    return rc;
+    PoolScope ws(r->pool);
+    Trunk t;
+    t.preprocess = preprocess != 0;
+    t.logits = logits;
+    return run_trunk(r, ws, x, B, H, W, t, s);
 }
 
 // The stem's activation relu(bn1(conv1(pre(x)))) alone: what the 3x3/2 max-pool chooses its arg-maxima from.  Parity tests
@@ -430,19 +434,11 @@ int sisic_resnet_stem(sisic_resnet* r, const float* x, float* c1_out, int B, int
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const float* cur = x;
-    int h = H, w = W;
-    float* pre = nullptr;
-    if (preprocess) {
-        const int S = 224;
-        SISIC_TRY(pool_get(r, (size_t)B * 3 * S * S, &pre));
-        const int rc = launch_preprocess(r->ctx, x, pre, B, H, W, S, S, s);
-        if (rc != SISIC_OK) { pool_put(r, pre); return rc; }
-        cur = pre; h = S; w = S;
-    }
-    const int rc = run_conv(r, r->stem, cur, B, h, w, nullptr, true, c1_out, s);
-    if (pre) pool_put(r, pre);
-    return rc;
+    PoolScope ws(r->pool);
+    Trunk t;
+    t.preprocess = preprocess != 0;
+    t.stem_out = c1_out;
+    return run_trunk(r, ws, x, B, H, W, t, s);
 }
 
 // d score / d x for score = log(softmax(logits)[target] + 1e-8) (XAI.py:443-459), x the classifier's raw input in
@@ -460,16 +456,7 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<float*> live;
-    auto get = [&](size_t floats, float** p) {
-        const int rc = pool_get(r, floats, p);
-        if (rc == SISIC_OK) live.push_back(*p);
-        return rc;
-    };
-    auto put = [&](float* p) {
-        pool_put(r, p);
-        live.erase(std::remove(live.begin(), live.end(), p), live.end());
-    };
+    PoolScope ws(r->pool);
     // transposed convolution of `c` applied to g [B, c.cout, gh, gw]; stride 2: zero-insertion input (2gh x 2gw grid)
     auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
         sisic_conv_args a{};
@@ -480,107 +467,65 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
         a.residual = residual; a.out = out;
         return launch_conv2d(r->ctx, a, s);
     };
-    struct Saved { float* t1; float* out; int h, w, bh, bw; };
-    auto body = [&]() -> int {
-        const int S = 224;
-        SISIC_REQUIRE(H <= S && W <= S, "resnet_input_gradient: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
-        float* pre = nullptr;
-        SISIC_TRY(get((size_t)B * 3 * S * S, &pre));
-        SISIC_TRY(launch_preprocess(r->ctx, x, pre, B, H, W, S, S, s));
-        int h = S, w = S;
-        const int c1h = out_dim(h, 7, 2), c1w = out_dim(w, 7, 2);
-        float* c1 = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * c1h * c1w, &c1));
-        SISIC_TRY(run_conv(r, r->stem, pre, B, h, w, nullptr, true, c1, s));
-        put(pre);
-        const int mh = out_dim(c1h, 3, 2), mw = out_dim(c1w, 3, 2);
-        SISIC_REQUIRE(c1h % 2 == 0 && c1w % 2 == 0, "resnet_input_gradient: odd feature map");
-        float* m = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * mh * mw, &m));
-        SISIC_TRY(launch_maxpool(r->ctx, c1, m, B, 64, c1h, c1w, s));
-        std::vector<Saved> saved;
-        float* act = m;
-        h = mh; w = mw;
-        for (const Block& b : r->blocks) {
-            const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
-            SISIC_REQUIRE(b.conv1.stride == 1 || (h % 2 == 0 && w % 2 == 0), "resnet_input_gradient: odd feature map %dx%d", h, w);
-            float* t1 = nullptr;
-            SISIC_TRY(get((size_t)B * b.conv1.cout * bh * bw, &t1));
-            SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
-            const float* identity = act;
-            float* ds = nullptr;
-            if (b.down.k) {
-                SISIC_TRY(get((size_t)B * b.down.cout * bh * bw, &ds));
-                SISIC_TRY(run_conv(r, b.down, act, B, h, w, nullptr, false, ds, s));
-                identity = ds;
-            }
-            float* t2 = nullptr;
-            SISIC_TRY(get((size_t)B * b.conv2.cout * bh * bw, &t2));
-            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, identity, true, t2, s));
-            if (ds) put(ds);
-            saved.push_back({t1, t2, h, w, bh, bw});
-            act = t2; h = bh; w = bw;
-        }
-        const int C = r->blocks.back().conv2.cout;
-        float* logits = nullptr;
-        SISIC_TRY(get((size_t)B * r->num_classes, &logits));
-        SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, logits, B, C, h * w, r->num_classes, s));
-        if (logits_out)
-            SISIC_HIP(hipMemcpyAsync(logits_out, logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const int S = 224;
+    SISIC_REQUIRE(H <= S && W <= S, "resnet_input_gradient: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
+    Trunk t;
+    t.keep = true;
+    SISIC_TRY(run_trunk(r, ws, x, B, H, W, t, s));
+    const std::vector<Trunk::Saved>& saved = t.saved;
+    const int C = r->blocks.back().conv2.cout, c1h = t.c1h, c1w = t.c1w;
+    if (logits_out)
+        SISIC_HIP(hipMemcpyAsync(logits_out, t.logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
 
-        // ---- backward
-        float* g = nullptr;                                   // d score / d (block output), already ReLU-masked
-        SISIC_TRY(get((size_t)B * C * h * w, &g));
-        SISIC_TRY(launch_score_head_bwd(r->ctx, logits, r->d_fc_w, act, g, B, C, h * w, r->num_classes, target, s));
-        put(logits);
-        for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
-            const Block& b = r->blocks[k];
-            const Saved& sv = saved[k];
-            const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
-            float* tmp = nullptr;                             // conv2^T g, then the ReLU mask of t1
-            SISIC_TRY(get(n_mid, &tmp));
-            SISIC_TRY(conv_t(b.conv2, g, sv.bh, sv.bw, nullptr, tmp));
-            SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
-            const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
-            float* da = nullptr;
-            SISIC_TRY(get(n_in, &da));
-            if (!b.down.k) {
-                SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, g, da));                 // + identity path
-            } else {
-                SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
-                float* small = nullptr;
-                SISIC_TRY(get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
-                SISIC_TRY(conv_t(b.down, g, sv.bh, sv.bw, nullptr, small));           // 1x1 at the low resolution
-                SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
-                put(small);
-            }
-            put(tmp);
-            put(g);
-            put(sv.t1);
-            put(sv.out);
-            if (k > 0) {                                       // ReLU of the previous block's output
-                SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));
-            }
-            g = da;
+    // ---- backward
+    float* g = nullptr;                                   // d score / d (block output), already ReLU-masked
+    SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
+    SISIC_TRY(launch_score_head_bwd(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, target, s));
+    ws.put(t.logits);
+    for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
+        const Block& b = r->blocks[k];
+        const Trunk::Saved& sv = saved[k];
+        const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
+        float* tmp = nullptr;                             // conv2^T g, then the ReLU mask of t1
+        SISIC_TRY(ws.get(n_mid, &tmp));
+        SISIC_TRY(conv_t(b.conv2, g, sv.bh, sv.bw, nullptr, tmp));
+        SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
+        const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
+        float* da = nullptr;
+        SISIC_TRY(ws.get(n_in, &da));
+        if (!b.down.k) {
+            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, g, da));                 // + identity path
+        } else {
+            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
+            float* small = nullptr;
+            SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
+            SISIC_TRY(conv_t(b.down, g, sv.bh, sv.bw, nullptr, small));           // 1x1 at the low resolution
+            SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
+            ws.put(small);
         }
-        // g = d score / d (max-pool output)
-        float* dc1 = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * c1h * c1w, &dc1));
-        SISIC_TRY(launch_maxpool_bwd(r->ctx, g, c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
-        put(g);
-        put(m);
-        put(c1);
-        float* dp = nullptr;
-        SISIC_TRY(get((size_t)B * 3 * S * S, &dp));
-        SISIC_TRY(launch_stem_bwd(r->ctx, dc1, r->stem.raw, dp, B, 64, c1h, c1w, S, S, s));
-        put(dc1);
-        SISIC_TRY(launch_preprocess_bwd(r->ctx, dp, x, grad_x, B, H, W, S, S, s));
-        put(dp);
-        return SISIC_OK;
-    };
-    const int rc = body();
-    for (float* p : live) pool_put(r, p);
-    return rc;
+        ws.put(tmp);
+        ws.put(g);
+        ws.put(sv.t1);
+        ws.put(sv.out);
+        if (k > 0) {                                       // ReLU of the previous block's output
+            SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));
+        }
+        g = da;
+    }
+    // g = d score / d (max-pool output)
+    float* dc1 = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
+    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, t.c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
+    ws.put(g);
+    ws.put(t.m);
+    ws.put(t.c1);
+    float* dp = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 3 * S * S, &dp));
+    SISIC_TRY(launch_stem_bwd(r->ctx, dc1, r->stem.raw, dp, B, 64, c1h, c1w, S, S, s));
+    ws.put(dc1);
+    SISIC_TRY(launch_preprocess_bwd(r->ctx, dp, x, grad_x, B, H, W, S, S, s));
+    ws.put(dp);
+    return SISIC_OK;
 }
 
 // Grad-CAM on layer4[-1].conv2 for the raw logit of `target` (xai/XAI.py:2945-3035; see gradcam_kernel): the forward
@@ -597,80 +542,16 @@ int sisic_resnet_gradcam(sisic_resnet* r, const float* x, int B, int H, int W, i
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<float*> live;
-    auto get = [&](size_t floats, float** p) {
-        const int rc = pool_get(r, floats, p);
-        if (rc == SISIC_OK) live.push_back(*p);
-        return rc;
-    };
-    auto put = [&](float* p) {
-        pool_put(r, p);
-        live.erase(std::remove(live.begin(), live.end(), p), live.end());
-    };
-    auto body = [&]() -> int {
-        const int S = 224;
-        SISIC_REQUIRE(H <= S && W <= S, "resnet_gradcam: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
-        float* pre = nullptr;
-        SISIC_TRY(get((size_t)B * 3 * S * S, &pre));
-        SISIC_TRY(launch_preprocess(r->ctx, x, pre, B, H, W, S, S, s));
-        int h = S, w = S;
-        int oh = out_dim(h, 7, 2), ow = out_dim(w, 7, 2);
-        float* c1 = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * oh * ow, &c1));
-        SISIC_TRY(run_conv(r, r->stem, pre, B, h, w, nullptr, true, c1, s));
-        put(pre);
-        h = oh; w = ow;
-        oh = out_dim(h, 3, 2); ow = out_dim(w, 3, 2);
-        float* act = nullptr;
-        SISIC_TRY(get((size_t)B * 64 * oh * ow, &act));
-        SISIC_TRY(launch_maxpool(r->ctx, c1, act, B, 64, h, w, s));
-        put(c1);
-        h = oh; w = ow;
-        float* ylast = nullptr;
-        for (size_t k = 0; k < r->blocks.size(); ++k) {
-            const Block& b = r->blocks[k];
-            const bool last = k + 1 == r->blocks.size();
-            const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
-            float* t1 = nullptr;
-            SISIC_TRY(get((size_t)B * b.conv1.cout * bh * bw, &t1));
-            SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
-            const float* identity = act;
-            float* ds = nullptr;
-            if (b.down.k) {
-                SISIC_TRY(get((size_t)B * b.down.cout * bh * bw, &ds));
-                SISIC_TRY(run_conv(r, b.down, act, B, h, w, nullptr, false, ds, s));
-                identity = ds;
-            }
-            float* t2 = nullptr;
-            const size_t n_out = (size_t)B * b.conv2.cout * bh * bw;
-            SISIC_TRY(get(n_out, &t2));
-            if (!last) {
-                SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, identity, true, t2, s));
-            } else {                                           // keep bn2(conv2(.)) on its own, then relu(. + identity)
-                SISIC_TRY(get(n_out, &ylast));
-                SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, nullptr, false, ylast, s));
-                SISIC_TRY(launch_add_relu(r->ctx, ylast, identity, t2, (int64_t)n_out, s));
-            }
-            put(t1);
-            if (ds) put(ds);
-            put(act);
-            act = t2; h = bh; w = bw;
-        }
-        const FoldedConv& c2 = r->blocks.back().conv2;
-        float* logits = nullptr;
-        SISIC_TRY(get((size_t)B * r->num_classes, &logits));
-        SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, logits, B, c2.cout, h * w, r->num_classes, s));
-        if (logits_out)
-            SISIC_HIP(hipMemcpyAsync(logits_out, logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
-        put(logits);
-        SISIC_TRY(launch_gradcam(r->ctx, ylast, act, r->d_fc_w, c2.bias, cam, B, c2.cout, h, w, S, target, s));
-        put(ylast);
-        put(act);
-        return SISIC_OK;
-    };
-    const int rc = body();
-    for (float* p : live) pool_put(r, p);
-    return rc;
+    const int S = 224;
+    SISIC_REQUIRE(H <= S && W <= S, "resnet_gradcam: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
+    PoolScope ws(r->pool);
+    Trunk t;
+    t.split_last = true;
+    SISIC_TRY(run_trunk(r, ws, x, B, H, W, t, s));
+    const FoldedConv& c2 = r->blocks.back().conv2;
+    if (logits_out)
+        SISIC_HIP(hipMemcpyAsync(logits_out, t.logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return launch_gradcam(r->ctx, t.ylast, t.act, r->d_fc_w, c2.bias, cam, B, c2.cout, t.h, t.w, S, target, s);
 }
 
 int sisic_class_scores(sisic_ctx* ctx, const float* logits, int B, int n_classes, int target, float* prob,

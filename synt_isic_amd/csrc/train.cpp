@@ -31,26 +31,18 @@ float* grad_of(sisic_unet* u, int idx) { return u->train->grad + u->offsets[idx]
 int prepare_backward_conv(sisic_unet* u, ConvW& c, hipStream_t s) {
     if (c.k == 0) return SISIC_OK;
     const int kk = c.k * c.k;
-    auto alloc = [&](size_t floats, float** p) -> int {
-        if (*p) return SISIC_OK;
-        void* q = nullptr;
-        SISIC_HIP(hipMalloc(&q, std::max<size_t>(floats, 4) * sizeof(float)));
-        u->owned.push_back(static_cast<float*>(q));
-        *p = static_cast<float*>(q);
-        return SISIC_OK;
-    };
-    SISIC_TRY(alloc((size_t)c.cout * c.cin * kk, &c.raw_t));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)c.cout * c.cin * kk, &c.raw_t));
     SISIC_TRY(launch_transpose_flip(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, kk, c.raw_t, s));
-    SISIC_TRY(alloc((size_t)sisic_conv_packed_numel(c.cin, c.cout, c.k), &c.packed_t));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)sisic_conv_packed_numel(c.cin, c.cout, c.k), &c.packed_t));
     SISIC_TRY(launch_conv_pack(u->ctx, c.raw_t, c.cin, c.cout, c.k, c.packed_t, s));
     if (c.k == 3 && !c.strided && c.cin > 4) {
-        SISIC_TRY(alloc((size_t)winograd_packed_numel(c.cin, c.cout), &c.wino_t));
+        SISIC_TRY(dev_alloc(u->owned, (size_t)winograd_packed_numel(c.cin, c.cout), &c.wino_t));
         SISIC_TRY(launch_winograd_pack(u->ctx, c.raw_t, c.cin, c.cout, c.wino_t, s));
     }
     return SISIC_OK;
 }
 
-// The job tables of repack.hip: everything prepare_all (unet.cpp) and prepare_backward_weights (below) derive from the raw
+// The job tables of repack.hip: everything unet_prepare_all (unet.cpp) and prepare_backward_weights (below) derive from the raw
 // arena, in dependency order.  Built after those two have run once (they allocate); the destinations do not move afterwards.
 int build_repack_plan(sisic_unet* u) {
     TrainState* tr = u->train.get();
@@ -120,23 +112,13 @@ int prepare_backward_weights(sisic_unet* u, hipStream_t s) {
         if (c != &u->conv_in) SISIC_TRY(prepare_backward_conv(u, *c, s));     // the network input needs no gradient
     for (AttnW* a : unet_attns(u)) {
         const int c = a->c;
-        auto alloc = [&](size_t floats, float** p) -> int {
-            if (*p) return SISIC_OK;
-            void* q = nullptr;
-            SISIC_HIP(hipMalloc(&q, floats * sizeof(float)));
-            u->owned.push_back(static_cast<float*>(q));
-            *p = static_cast<float*>(q);
-            return SISIC_OK;
-        };
-        SISIC_TRY(alloc((size_t)3 * c * c, &a->qkv_raw_t));
+        SISIC_TRY(dev_alloc(u->owned, (size_t)3 * c * c, &a->qkv_raw_t));
         SISIC_TRY(launch_transpose_flip(u->ctx, a->qkv_cat, 3 * c, c, 1, a->qkv_raw_t, s));
-        SISIC_TRY(alloc((size_t)sisic_conv_packed_numel(c, 3 * c, 1), &a->qkv_packed_t));
+        SISIC_TRY(dev_alloc(u->owned, (size_t)sisic_conv_packed_numel(c, 3 * c, 1), &a->qkv_packed_t));
         SISIC_TRY(launch_conv_pack(u->ctx, a->qkv_raw_t, c, 3 * c, 1, a->qkv_packed_t, s));
     }
     return SISIC_OK;
 }
-
-void release_tape(sisic_unet* u) { unet_release_tape(u); }
 
 struct Bwd {
     sisic_unet* u;
@@ -374,7 +356,7 @@ int sisic_unet_train_begin(sisic_unet* u) {
     SISIC_HIP(hipMemset(tr->adam_m, 0, bytes));
     SISIC_HIP(hipMemset(tr->adam_v, 0, bytes));
     tr->step = 0;
-    release_tape(u);
+    unet_release_tape(u);
     SISIC_TRY(prepare_backward_weights(u, nullptr));
     SISIC_HIP(hipDeviceSynchronize());
     return SISIC_OK;
@@ -383,7 +365,7 @@ int sisic_unet_train_begin(sisic_unet* u) {
 int sisic_unet_train_end(sisic_unet* u) {
     if (!u || !u->train) return SISIC_OK;
     (void)hipDeviceSynchronize();
-    release_tape(u);
+    unet_release_tape(u);
     TrainState* tr = u->train.get();
     for (float* p : {tr->grad, tr->adam_m, tr->adam_v, tr->emb, tr->h1, tr->t2, tr->dtproj, tr->garena, tr->wgrad_part, tr->scratch,
                      tr->small, tr->loss_dev, tr->mse_part})
@@ -408,7 +390,7 @@ int sisic_unet_train_forward(sisic_unet* u, const float* sample, const int64_t* 
     SISIC_REQUIRE(sample && timesteps && out, "train_forward: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState* tr = u->train.get();
-    release_tape(u);                                       // a forward without a backward: drop the old tape
+    unet_release_tape(u);                                  // a forward without a backward: drop the old tape
     SISIC_TRY(unet_check_shape(u, B, H, W));
     SISIC_TRY(check_trainable_resolution(u, H, W));
     SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
@@ -428,7 +410,7 @@ int sisic_unet_train_forward(sisic_unet* u, const float* sample, const int64_t* 
     tr->B = B; tr->H = H; tr->W = W;
     const int rc = unet_run_forward(u, sample, u->tproj, u->tproj_R, out, B, H, W, s, tr);
     if (rc != SISIC_OK) {
-        release_tape(u);
+        unet_release_tape(u);
         return rc;
     }
     tr->has_tape = true;
@@ -446,7 +428,7 @@ int sisic_unet_backward(sisic_unet* u, const float* dout, void* stream) {
     SISIC_HIP(hipSetDevice(u->ctx->device));
     Bwd b{u, tr, static_cast<hipStream_t>(stream), tr->B};
     const int rc = b.run(dout);
-    release_tape(u);       // blocks go back to the pool; the stream still orders later reuse behind the kernels above
+    unet_release_tape(u);  // blocks go back to the pool; the stream still orders later reuse behind the kernels above
     return rc;
 }
 

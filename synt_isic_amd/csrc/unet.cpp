@@ -83,8 +83,10 @@ int describe(sisic_unet* u) {
             add_resnet(u, u->down_res[i][j], base + ".resnets." + std::to_string(j), j == 0 ? in_ch : out_ch, out_ch);
             if (cfg.down_attn[i]) add_attn(u, u->down_attn[i][j], base + ".attentions." + std::to_string(j), out_ch);
         }
-        if (i != n - 1)
+        if (i != n - 1) {
             add_conv(u, u->downsamplers[i], "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", out_ch, out_ch, 3);
+            u->downsamplers[i].strided = true;
+        }
     }
     const int mid = boc[n - 1];
     add_resnet(u, u->mid_res[0], "mid_block.resnets.0", mid, mid);
@@ -124,26 +126,16 @@ int describe(sisic_unet* u) {
 }
 
 // ------------------------------------------------------------------ derived weights
-int dev_alloc(sisic_unet* u, size_t floats, float** out) {
-    if (*out) return SISIC_OK;          // already there: prepare_* runs again after every optimizer step
-    void* p = nullptr;
-    SISIC_HIP(hipMalloc(&p, std::max<size_t>(floats, 4) * sizeof(float)));
-    u->owned.push_back(static_cast<float*>(p));
-    *out = static_cast<float*>(p);
-    return SISIC_OK;
-}
-
 int prepare_conv(sisic_unet* u, ConvW& c, hipStream_t s) {
-    if (c.k == 0) return SISIC_OK;
-    SISIC_TRY(dev_alloc(u, (size_t)sisic_conv_packed_numel(c.cout, c.cin, c.k), &c.packed));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)sisic_conv_packed_numel(c.cout, c.cin, c.k), &c.packed));
     SISIC_TRY(launch_conv_pack(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, c.k, c.packed, s));
     c.bias = u->rawp(c.b_idx);
     if (c.k == 3 && !c.strided && c.cout > 4) {
-        SISIC_TRY(dev_alloc(u, (size_t)winograd_packed_numel(c.cout, c.cin), &c.wino));
+        SISIC_TRY(dev_alloc(u->owned, (size_t)winograd_packed_numel(c.cout, c.cin), &c.wino));
         SISIC_TRY(launch_winograd_pack(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, c.wino, s));
     }
     if (c.k == 3 && c.strided) {
-        SISIC_TRY(dev_alloc(u, (size_t)conv_s2_packed_floats(c.cout, c.cin), &c.s2));
+        SISIC_TRY(dev_alloc(u->owned, (size_t)conv_s2_packed_floats(c.cout, c.cin), &c.s2));
         SISIC_TRY(launch_conv_s2_pack(u->ctx, u->rawp(c.w_idx), c.cout, c.cin, c.s2, s));
     }
     return SISIC_OK;
@@ -152,88 +144,43 @@ void prepare_norm(sisic_unet* u, NormW& n) {
     n.gamma = u->rawp(n.w_idx);
     n.beta = u->rawp(n.b_idx);
 }
+// norms and the time-embedding projection (the block's convolutions: unet_prepare_all, with every other convolution)
 int prepare_resnet(sisic_unet* u, ResnetW& r, hipStream_t s) {
     prepare_norm(u, r.norm1);
     prepare_norm(u, r.norm2);
-    SISIC_TRY(prepare_conv(u, r.conv1, s));
-    SISIC_TRY(prepare_conv(u, r.conv2, s));
-    SISIC_TRY(prepare_conv(u, r.shortcut, s));
     // time_emb_proj.weight [cout, hidden] -> columns [temb_off, temb_off+cout) of tproj_wt [hidden][R]
     SISIC_TRY(launch_transpose2d(u->ctx, u->rawp(r.temb_w_idx), r.cout, u->hidden, u->tproj_wt, u->tproj_R, r.temb_off, s));
     SISIC_HIP(hipMemcpyAsync(u->tproj_b + r.temb_off, u->rawp(r.temb_b_idx), (size_t)r.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SISIC_OK;
 }
+// the norm and q,k,v as one [3C, C] 1x1 convolution (to_out: unet_prepare_all, with every other convolution)
 int prepare_attn(sisic_unet* u, AttnW& a, hipStream_t s) {
     prepare_norm(u, a.norm);
     const int c = a.c;
-    // q,k,v as one [3C, C] 1x1 convolution
-    SISIC_TRY(dev_alloc(u, (size_t)3 * c * c, &a.qkv_cat));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)3 * c * c, &a.qkv_cat));
     float* cat = a.qkv_cat;
     const size_t wbytes = (size_t)c * c * sizeof(float);
     SISIC_HIP(hipMemcpyAsync(cat, u->rawp(a.q_w), wbytes, hipMemcpyDeviceToDevice, s));
     SISIC_HIP(hipMemcpyAsync(cat + (size_t)c * c, u->rawp(a.k_w), wbytes, hipMemcpyDeviceToDevice, s));
     SISIC_HIP(hipMemcpyAsync(cat + (size_t)2 * c * c, u->rawp(a.v_w), wbytes, hipMemcpyDeviceToDevice, s));
-    SISIC_TRY(dev_alloc(u, (size_t)sisic_conv_packed_numel(3 * c, c, 1), &a.qkv_packed));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)sisic_conv_packed_numel(3 * c, c, 1), &a.qkv_packed));
     SISIC_TRY(launch_conv_pack(u->ctx, cat, 3 * c, c, 1, a.qkv_packed, s));
-    SISIC_TRY(dev_alloc(u, (size_t)3 * c, &a.qkv_bias));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)3 * c, &a.qkv_bias));
     SISIC_HIP(hipMemcpyAsync(a.qkv_bias, u->rawp(a.q_b), c * sizeof(float), hipMemcpyDeviceToDevice, s));
     SISIC_HIP(hipMemcpyAsync(a.qkv_bias + c, u->rawp(a.k_b), c * sizeof(float), hipMemcpyDeviceToDevice, s));
     SISIC_HIP(hipMemcpyAsync(a.qkv_bias + 2 * c, u->rawp(a.v_b), c * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SISIC_TRY(prepare_conv(u, a.out, s));
     return SISIC_OK;
 }
 
-int prepare_all(sisic_unet* u, hipStream_t s) {
-    const int nin = 2 * u->cfg.n_freqs;
-    SISIC_TRY(dev_alloc(u, u->cfg.n_freqs, &u->d_freqs));
-    SISIC_HIP(hipMemcpyAsync(u->d_freqs, u->freqs.data(), u->freqs.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    SISIC_TRY(dev_alloc(u, (size_t)nin * u->hidden, &u->w1t));
-    SISIC_TRY(dev_alloc(u, (size_t)u->hidden * u->hidden, &u->w2t));
-    SISIC_TRY(dev_alloc(u, (size_t)u->hidden * u->tproj_R, &u->tproj_wt));
-    SISIC_TRY(dev_alloc(u, (size_t)u->tproj_R, &u->tproj_b));
-    SISIC_TRY(launch_transpose2d(u->ctx, u->rawp(u->temb_w1), u->hidden, nin, u->w1t, u->hidden, 0, s));
-    SISIC_TRY(launch_transpose2d(u->ctx, u->rawp(u->temb_w2), u->hidden, u->hidden, u->w2t, u->hidden, 0, s));
-    SISIC_TRY(prepare_conv(u, u->conv_in, s));
-    SISIC_TRY(prepare_conv(u, u->conv_out, s));
-    prepare_norm(u, u->norm_out);
-    for (auto& blk : u->down_res) for (auto& r : blk) SISIC_TRY(prepare_resnet(u, r, s));
-    for (auto& blk : u->up_res) for (auto& r : blk) SISIC_TRY(prepare_resnet(u, r, s));
-    for (auto& r : u->mid_res) SISIC_TRY(prepare_resnet(u, r, s));
-    for (auto& blk : u->down_attn) for (auto& a : blk) SISIC_TRY(prepare_attn(u, a, s));
-    for (auto& blk : u->up_attn) for (auto& a : blk) SISIC_TRY(prepare_attn(u, a, s));
-    SISIC_TRY(prepare_attn(u, u->mid_attn, s));
-    for (auto& c : u->downsamplers) {
-        c.strided = true;
-        SISIC_TRY(prepare_conv(u, c, s));
-    }
-    for (auto& c : u->upsamplers) SISIC_TRY(prepare_conv(u, c, s));
-    return SISIC_OK;
-}
-
-// forget every derived buffer (they were freed): the next prepare_all allocates afresh
-void reset_conv(ConvW& c) { c.packed = c.wino = c.s2 = c.raw_t = c.packed_t = c.wino_t = nullptr; }
-void reset_attn(AttnW& a) {
-    a.qkv_cat = a.qkv_packed = a.qkv_bias = a.qkv_raw_t = a.qkv_packed_t = nullptr;
-    reset_conv(a.out);
-}
-void reset_resnet(ResnetW& r) { reset_conv(r.conv1); reset_conv(r.conv2); reset_conv(r.shortcut); }
+// forget every derived buffer (they were freed): the next unet_prepare_all allocates afresh
 void reset_derived(sisic_unet* u) {
     if (u->train) u->train->repack_ready = false;       // the job tables of repack.hip name the old buffers
     u->d_freqs = u->w1t = u->w2t = u->tproj_wt = u->tproj_b = nullptr;
-    reset_conv(u->conv_in); reset_conv(u->conv_out);
-    for (auto& blk : u->down_res) for (auto& r : blk) reset_resnet(r);
-    for (auto& blk : u->up_res) for (auto& r : blk) reset_resnet(r);
-    for (auto& r : u->mid_res) reset_resnet(r);
-    for (auto& blk : u->down_attn) for (auto& a : blk) reset_attn(a);
-    for (auto& blk : u->up_attn) for (auto& a : blk) reset_attn(a);
-    reset_attn(u->mid_attn);
-    for (auto& c : u->downsamplers) reset_conv(c);
-    for (auto& c : u->upsamplers) reset_conv(c);
+    for (ConvW* c : unet_convs(u)) c->packed = c->wino = c->s2 = c->raw_t = c->packed_t = c->wino_t = nullptr;
+    for (AttnW* a : unet_attns(u)) a->qkv_cat = a->qkv_packed = a->qkv_bias = a->qkv_raw_t = a->qkv_packed_t = nullptr;
 }
 
 // ------------------------------------------------------------------ workspace
-void pool_put(sisic_unet* u, float* p);
-
 void loop_graph_drop(sisic_unet* u) {
     if (u->loop_exec) (void)hipGraphExecDestroy(u->loop_exec);
     if (u->loop_graph) (void)hipGraphDestroy(u->loop_graph);
@@ -243,16 +190,9 @@ void loop_graph_drop(sisic_unet* u) {
 // A recorded training forward (the tape) owns pool blocks.  Whatever frees the pool, or lets a captured step write into
 // blocks the tape took from the free list after the capture, makes the tape unusable: forget it, so that
 // sisic_unet_backward answers SISIC_ESTATE instead of reading freed or overwritten activations.
-void tape_drop(sisic_unet* u, bool return_blocks) {
+void tape_forget(sisic_unet* u) {
     TrainState* tr = u->train.get();
     if (!tr) return;
-    if (return_blocks) {
-        for (auto& b : tr->bufs) {
-            if (b->p) pool_put(u, b->p);
-            if (b->stats) pool_put(u, b->stats);
-        }
-        for (float* p : tr->grads_of_bufs) pool_put(u, p);
-    }
     tr->bufs.clear();
     tr->grads_of_bufs.clear();
     tr->buf_grad.clear();
@@ -262,33 +202,43 @@ void tape_drop(sisic_unet* u, bool return_blocks) {
 
 void pool_release_all(sisic_unet* u) {
     loop_graph_drop(u);                 // a captured step holds addresses of pool blocks
-    tape_drop(u, false);                // ... and so does a recorded training forward
-    for (auto& b : u->pool) (void)hipFree(b.p);
-    u->pool.clear();
+    tape_forget(u);                     // ... and so does a recorded training forward
+    u->pool.release_all();
 }
 
-int pool_get(sisic_unet* u, size_t floats, float** out) {
-    const size_t bytes = floats * sizeof(float);
-    for (auto& b : u->pool) {
-        if (b.free_ && b.bytes == bytes) {
-            b.free_ = false;
-            *out = b.p;
-            return SISIC_OK;
-        }
-    }
-    void* p = nullptr;
-    SISIC_HIP(hipMalloc(&p, bytes));
-    u->pool.push_back({static_cast<float*>(p), bytes, false});
-    *out = static_cast<float*>(p);
+}  // namespace
+
+namespace sisic {
+
+int unet_prepare_all(sisic_unet* u, hipStream_t s) {
+    const int nin = 2 * u->cfg.n_freqs;
+    SISIC_TRY(dev_alloc(u->owned, u->cfg.n_freqs, &u->d_freqs));
+    SISIC_HIP(hipMemcpyAsync(u->d_freqs, u->freqs.data(), u->freqs.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)nin * u->hidden, &u->w1t));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)u->hidden * u->hidden, &u->w2t));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)u->hidden * u->tproj_R, &u->tproj_wt));
+    SISIC_TRY(dev_alloc(u->owned, (size_t)u->tproj_R, &u->tproj_b));
+    SISIC_TRY(launch_transpose2d(u->ctx, u->rawp(u->temb_w1), u->hidden, nin, u->w1t, u->hidden, 0, s));
+    SISIC_TRY(launch_transpose2d(u->ctx, u->rawp(u->temb_w2), u->hidden, u->hidden, u->w2t, u->hidden, 0, s));
+    prepare_norm(u, u->norm_out);
+    for (ConvW* c : unet_convs(u)) SISIC_TRY(prepare_conv(u, *c, s));     // (to_out of every attention block included)
+    for (ResnetW* r : unet_resnets(u)) SISIC_TRY(prepare_resnet(u, *r, s));
+    for (AttnW* a : unet_attns(u)) SISIC_TRY(prepare_attn(u, *a, s));
     return SISIC_OK;
 }
 
-void pool_put(sisic_unet* u, float* p) {
-    for (auto& b : u->pool)
-        if (b.p == p) { b.free_ = true; return; }
+void unet_release_tape(sisic_unet* u) {
+    if (TrainState* tr = u->train.get()) {
+        for (auto& b : tr->bufs) {
+            if (b->p) u->pool.put(b->p);
+            if (b->stats) u->pool.put(b->stats);
+        }
+        for (float* p : tr->grads_of_bufs) u->pool.put(p);
+    }
+    tape_forget(u);
 }
 
-int grow(float** p, size_t* have, size_t want) {
+int unet_grow(float** p, size_t* have, size_t want) {
     if (*have >= want) return SISIC_OK;
     if (*p) SISIC_HIP(hipFree(*p));   // hipFree waits for the device, nothing can still read the old block
     *p = nullptr; *have = 0;
@@ -299,20 +249,20 @@ int grow(float** p, size_t* have, size_t want) {
     return SISIC_OK;
 }
 
-int ensure_rows(sisic_unet* u, size_t t_rows, size_t gn_rows) {
-    SISIC_TRY(grow(&u->t_vals, &u->t_vals_cap, t_rows));
-    SISIC_TRY(grow(&u->temb_act, &u->temb_act_cap, t_rows * u->hidden));
-    SISIC_TRY(grow(&u->tproj, &u->tproj_cap, t_rows * u->tproj_R));
-    SISIC_TRY(grow(&u->gn_scale, &u->gn_scale_cap, gn_rows * u->max_c));
-    SISIC_TRY(grow(&u->gn_shift, &u->gn_shift_cap, gn_rows * u->max_c));
-    SISIC_TRY(grow(&u->gn_scale2, &u->gn_scale2_cap, gn_rows * u->max_c));
-    SISIC_TRY(grow(&u->gn_shift2, &u->gn_shift2_cap, gn_rows * u->max_c));
+int unet_ensure_rows(sisic_unet* u, size_t t_rows, size_t gn_rows) {
+    SISIC_TRY(unet_grow(&u->t_vals, &u->t_vals_cap, t_rows));
+    SISIC_TRY(unet_grow(&u->temb_act, &u->temb_act_cap, t_rows * u->hidden));
+    SISIC_TRY(unet_grow(&u->tproj, &u->tproj_cap, t_rows * u->tproj_R));
+    SISIC_TRY(unet_grow(&u->gn_scale, &u->gn_scale_cap, gn_rows * u->max_c));
+    SISIC_TRY(unet_grow(&u->gn_shift, &u->gn_shift_cap, gn_rows * u->max_c));
+    SISIC_TRY(unet_grow(&u->gn_scale2, &u->gn_scale2_cap, gn_rows * u->max_c));
+    SISIC_TRY(unet_grow(&u->gn_shift2, &u->gn_shift2_cap, gn_rows * u->max_c));
     return SISIC_OK;
 }
 
 // Host -> device upload of a few floats, ordered on the caller's stream.  The source is copied into
 // one of a small ring of pinned slots; a slot is reused only after the copy that read it has finished.
-int stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hipStream_t s) {
+int unet_stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hipStream_t s) {
     if (u->stage_cap < n) {
         SISIC_HIP(hipDeviceSynchronize());
         if (u->stage_host) SISIC_HIP(hipHostFree(u->stage_host));
@@ -335,282 +285,7 @@ int stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hipStrea
     return SISIC_OK;
 }
 
-// ------------------------------------------------------------------ forward
-struct Fwd {
-    sisic_unet* u;
-    hipStream_t s;
-    int B;
-    const float* tproj;   // [B or 1, tproj_R]
-    int tproj_stride;     // tproj_R, or 0 when one row serves every sample
-    std::vector<std::unique_ptr<Buf>> bufs;
-    TrainState* tr = nullptr;     // training mode: record every operation, keep every buffer, save each GroupNorm's statistics
-    float* gsc = nullptr;         // scale / shift the next convolution's prologue reads (the shared pair, or this op's own)
-    float* gsh = nullptr;
-    float* gmr = nullptr;         // training mode: (mean, rstd) of the same GroupNorm
-    const NormW* gnorm = nullptr;
-
-    Buf* make(int C, int H, int W, int* rc) {
-        auto b = std::make_unique<Buf>();
-        b->C = C; b->H = H; b->W = W; b->refs = 1;
-        *rc = pool_get(u, (size_t)B * C * H * W, &b->p);
-        bufs.push_back(std::move(b));
-        return bufs.back().get();
-    }
-    void release(Buf* b) {
-        if (tr) return;           // the backward pass reads every activation
-        if (b && --b->refs == 0 && b->p) {
-            pool_put(u, b->p);
-            b->p = nullptr;
-            if (b->stats) { pool_put(u, b->stats); b->stats = nullptr; }
-        }
-    }
-
-    // defer (inference only): where the finalisation would be a launch of its own, hand it back as a job instead -- the caller
-    // has a neighbouring launch to carry it (resnet(): the shortcut) and runs it BEFORE anything reads the pair
-    int gn(const Buf* x, const Buf* skip, const NormW& n, GnFinJob* defer = nullptr, bool* deferred = nullptr) {
-        gsc = u->gn_scale; gsh = u->gn_shift; gmr = nullptr; gnorm = &n;
-        if (!tr && !skip && x->fin_norm == static_cast<const void*>(&n)) {     // finalized by its producer (conv below)
-            gsc = x->fin_scale; gsh = x->fin_shift;
-            return SISIC_OK;
-        }
-        if (tr) {                 // this GroupNorm's own scale / shift / (mean, rstd): the backward pass needs them
-            const int C = x->C + (skip ? skip->C : 0);
-            SISIC_TRY(pool_get(u, (size_t)B * C, &gsc));
-            SISIC_TRY(pool_get(u, (size_t)B * C, &gsh));
-            SISIC_TRY(pool_get(u, (size_t)B * u->cfg.norm_groups * 2, &gmr));
-            tr->grads_of_bufs.push_back(gsc); tr->grads_of_bufs.push_back(gsh); tr->grads_of_bufs.push_back(gmr);
-        }
-        if (x->stats && (!skip || skip->stats)) { // every producer left partials: no pass over the tensors
-            if (defer && !tr) {
-                *deferred = true;
-                return make_gn_fin_job(defer, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
-                                       skip ? skip->slots : 0, B, u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh);
-            }
-            return launch_gn_finalize(u->ctx, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
-                                      skip ? skip->slots : 0, B, x->H * x->W, u->cfg.norm_groups, u->cfg.norm_eps,
-                                      n.gamma, n.beta, gsc, gsh, s, gmr);
-        }
-        return launch_gn_stats(u->ctx, x->p, x->C, skip ? skip->p : nullptr, skip ? skip->C : 0, B, x->H * x->W,
-                               u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh, s, gmr);
-    }
-
-    // xb / skipb / resb / outb: the buffers behind in0 / in1 / residual / out (training tape; nullptr = network input / output)
-    int conv(const ConvW& c, const float* in0, int c0, const float* in1, int c1, int H, int W, int stride, int ups,
-             bool gn_prologue, bool silu, const float* chan_bias, const float* residual, float* out,
-             Buf* normed_later = nullptr, Buf* xb = nullptr, Buf* skipb = nullptr, Buf* resb = nullptr, Buf* outb = nullptr,
-             const AttnW* qkv_of = nullptr, const NormW* next_norm = nullptr, const GnFinJob* rider = nullptr,
-             bool* carried = nullptr) {
-        sisic_conv_args a{};
-        a.in0 = in0; a.c0 = c0; a.in1 = in1; a.c1 = c1;
-        a.B = B; a.Hin = H; a.Win = W; a.upsample = ups; a.ksize = c.k; a.stride = stride;
-        a.w_packed = c.packed; a.bias = c.bias; a.Cout = c.cout;
-        // (stride 2: the field carries the split filter of the bf16x3 downsampler kernel, sisic.h)
-        a.w_winograd = stride == 1 ? (u->use_winograd ? c.wino : nullptr) : (stride == 2 ? c.s2 : nullptr);
-        if (gn_prologue) { a.gn_scale = gsc; a.gn_shift = gsh; a.gn_silu = silu ? 1 : 0; }
-        a.chan_bias = chan_bias; a.chan_bias_stride = tproj_stride;
-        a.residual = residual; a.out = out;
-        // single-image latency (the reference's own call pattern, image_generator.py:379: batch 1): conv_plan.cpp
-        if (u->latency_mode) a.tile_cfg = conv_latency_cfg(a);
-        if (normed_later && u->fuse_gn) {          // a GroupNorm reads this output: have the epilogue leave partials
-            const int slots = conv_stats_slots(a);
-            if (slots > 0) {
-                SISIC_TRY(pool_get(u, (size_t)B * c.cout * slots * 4, &normed_later->stats));
-                normed_later->slots = slots;
-                a.stats_out = normed_later->stats;
-            }
-        }
-        // next_norm: the GroupNorm that reads this output ALONE, when the caller knows it: where the launch can finalize it
-        // (sisic_conv_finalizes: the 8x8 level's K-split forms) it leaves that layer's (scale, shift) in the shared pair -- which
-        // this very convolution's prologue may still be reading: the finalisation runs in the reduction launch behind it
-        if (normed_later && next_norm && u->fuse_gn && !tr) {
-            a.fin_gamma = next_norm->gamma; a.fin_beta = next_norm->beta; a.fin_groups = u->cfg.norm_groups; a.fin_eps = u->cfg.norm_eps;
-            // (the pair this launch's own prologue is NOT reading: a workgroup finalizes its image while others still read theirs)
-            const bool first_pair_busy = gn_prologue && gsc == u->gn_scale;
-            a.fin_scale = first_pair_busy ? u->gn_scale2 : u->gn_scale;
-            a.fin_shift = first_pair_busy ? u->gn_shift2 : u->gn_shift;
-            if (conv_finalizes(a)) { normed_later->fin_norm = next_norm; normed_later->fin_scale = a.fin_scale; normed_later->fin_shift = a.fin_shift; }
-            else { a.fin_gamma = nullptr; a.fin_beta = nullptr; a.fin_scale = nullptr; a.fin_shift = nullptr; }
-        }
-        if (tr) {
-            TapeOp op;
-            op.kind = TapeOp::CONV;
-            op.w = c; op.qkv_of = qkv_of;
-            op.in0 = xb; op.in1 = skipb; op.in0_ptr = in0; op.in1_ptr = in1;
-            op.c0 = c0; op.c1 = c1; op.H = H; op.W = W; op.stride = stride; op.ups = ups;
-            if (gn_prologue) { op.norm = gnorm; op.gn_scale = gsc; op.gn_shift = gsh; op.gn_mr = gmr; op.silu = silu; }
-            op.temb_off = chan_bias ? (int)(chan_bias - tproj) : -1;
-            op.residual = resb; op.out = outb; op.out_ptr = out;
-            tr->tape.push_back(op);
-        }
-        return launch_conv2d(u->ctx, a, s, rider, carried);
-    }
-
-    // out = ResnetBlock2D(cat(x, skip)); consumes nothing (caller releases inputs)
-    // next_norm: the GroupNorm module that reads the block's output alone, when the caller knows it (conv(): finalized by conv2's
-    // own launch where that is possible)
-    int resnet(const ResnetW& r, const Buf* x, const Buf* skip, Buf** out, const NormW* next_norm = nullptr) {
-        int rc = SISIC_OK;
-        const int H = x->H, W = x->W;
-        const int c1 = skip ? skip->C : 0;
-        SISIC_REQUIRE(x->C + c1 == r.cin, "unet: resnet expects %d input channels, got %d", r.cin, x->C + c1);
-        // The 1x1 shortcut reads the raw block inputs only: it neither needs norm1 nor does conv1 need it.  In inference, where
-        // norm1's finalisation would be a launch of its own, the shortcut runs FIRST and carries the jobs as extra workgroups
-        // (conv_pointwise_bf3.hip); conv1, next in stream order, is the first reader of the pair.  The launcher says whether its
-        // kernel ran them (the f32 1x1 kernels, latency mode's tiles and shapes the bf16x3 kernels refuse do not): if not, the
-        // stand-alone launch follows.  (SISIC_GN_RIDER=0: the order and launches without any of this.)
-        GnFinJob fin{};
-        bool deferred = false;
-        SISIC_TRY(gn(x, skip, r.norm1, (u->gn_rider && !tr && r.shortcut.k) ? &fin : nullptr, &deferred));
-        Buf* sc = nullptr;
-        if (deferred) {
-            bool carried = false;
-            sc = make(r.cout, H, W, &rc); SISIC_TRY(rc);
-            SISIC_TRY(conv(r.shortcut, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, false, false, nullptr,
-                           nullptr, sc->p, nullptr, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, sc, nullptr, nullptr,
-                           &fin, &carried));
-            if (!carried) SISIC_TRY(launch_gn_finalize_job(u->ctx, fin, s));
-        }
-        Buf* h = make(r.cout, H, W, &rc); SISIC_TRY(rc);
-        SISIC_TRY(conv(r.conv1, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, true, true,
-                       tproj + r.temb_off, nullptr, h->p, h, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, h, nullptr, &r.norm2));
-        const float* residual = x->p;
-        Buf* resb = const_cast<Buf*>(x);
-        if (sc) {
-            residual = sc->p;
-            resb = sc;
-        } else if (r.shortcut.k) {
-            sc = make(r.cout, H, W, &rc); SISIC_TRY(rc);
-            SISIC_TRY(conv(r.shortcut, x->p, x->C, skip ? skip->p : nullptr, c1, H, W, 1, 0, false, false, nullptr,
-                           nullptr, sc->p, nullptr, const_cast<Buf*>(x), const_cast<Buf*>(skip), nullptr, sc));
-            residual = sc->p;
-            resb = sc;
-        } else {
-            SISIC_REQUIRE(c1 == 0 && x->C == r.cout, "unet: identity shortcut with mismatched channels");
-        }
-        SISIC_TRY(gn(h, nullptr, r.norm2));
-        Buf* o = make(r.cout, H, W, &rc); SISIC_TRY(rc);
-        SISIC_TRY(conv(r.conv2, h->p, r.cout, nullptr, 0, H, W, 1, 0, true, true, nullptr, residual, o->p, o, h, nullptr,
-                       resb, o, nullptr, next_norm));
-        release(h);
-        release(sc);
-        *out = o;
-        return SISIC_OK;
-    }
-
-    int attention(const AttnW& a, const Buf* x, Buf** out) {
-        int rc = SISIC_OK;
-        const int H = x->H, W = x->W, N = H * W, C = a.c;
-        SISIC_REQUIRE(x->C == C, "unet: attention channel mismatch");
-        SISIC_TRY(gn(x, nullptr, a.norm));
-        Buf* qkv = make(3 * C, H, W, &rc); SISIC_TRY(rc);
-        ConvW cq; cq.cout = 3 * C; cq.cin = C; cq.k = 1; cq.packed = a.qkv_packed; cq.bias = a.qkv_bias;
-        SISIC_TRY(conv(cq, x->p, C, nullptr, 0, H, W, 1, 0, true, false, nullptr, nullptr, qkv->p, nullptr,
-                       const_cast<Buf*>(x), nullptr, nullptr, qkv, &a));
-        Buf* o = make(C, H, W, &rc); SISIC_TRY(rc);
-        SISIC_TRY(launch_attention(u->ctx, qkv->p, o->p, B, C, N, u->cfg.head_dim, s));
-        if (tr) {
-            TapeOp op;
-            op.kind = TapeOp::ATTN;
-            op.qkv = qkv; op.o = o; op.C = C; op.N = N;
-            tr->tape.push_back(op);
-        }
-        release(qkv);
-        Buf* y = make(C, H, W, &rc); SISIC_TRY(rc);
-        SISIC_TRY(conv(a.out, o->p, C, nullptr, 0, H, W, 1, 0, false, false, nullptr, x->p, y->p, y, o, nullptr,
-                       const_cast<Buf*>(x), y));
-        release(o);
-        *out = y;
-        return SISIC_OK;
-    }
-
-    int run(const float* sample, float* out, int H, int W) {
-        const sisic_unet_config& cfg = u->cfg;
-        const int n = cfg.n_blocks;
-        int rc = SISIC_OK;
-        std::vector<Buf*> skips;
-
-        Buf* x = make(u->conv_in.cout, H, W, &rc); SISIC_TRY(rc);
-        SISIC_TRY(conv(u->conv_in, sample, cfg.in_channels, nullptr, 0, H, W, 1, 0, false, false, nullptr, nullptr, x->p, x,
-                       nullptr, nullptr, nullptr, x));
-        x->refs++;                 // held by `x` and by the skip stack
-        skips.push_back(x);
-
-        for (int i = 0; i < n; ++i) {
-            for (int j = 0; j < cfg.layers_per_block; ++j) {
-                Buf* y = nullptr;
-                // who normalises this block's output next (alone: the up path's concatenations have two producers)
-                const NormW* next = cfg.down_attn[i] ? &u->down_attn[i][j].norm
-                                    : (j + 1 < cfg.layers_per_block ? &u->down_res[i][j + 1].norm1 : (i == n - 1 ? &u->mid_res[0].norm1 : nullptr));
-                SISIC_TRY(resnet(u->down_res[i][j], x, nullptr, &y, next));
-                release(x);
-                x = y;
-                if (cfg.down_attn[i]) {
-                    SISIC_TRY(attention(u->down_attn[i][j], x, &y));
-                    release(x);
-                    x = y;
-                }
-                x->refs++;
-                skips.push_back(x);
-            }
-            if (i != n - 1) {
-                const int Ho = (x->H + 2 - 3) / 2 + 1, Wo = (x->W + 2 - 3) / 2 + 1;
-                Buf* y = make(u->downsamplers[i].cout, Ho, Wo, &rc); SISIC_TRY(rc);
-                SISIC_TRY(conv(u->downsamplers[i], x->p, x->C, nullptr, 0, x->H, x->W, 2, 0, false, false, nullptr, nullptr, y->p, y,
-                               x, nullptr, nullptr, y));
-                release(x);
-                x = y;
-                x->refs++;
-                skips.push_back(x);
-            }
-        }
-
-        {
-            Buf* y = nullptr;
-            SISIC_TRY(resnet(u->mid_res[0], x, nullptr, &y, &u->mid_attn.norm)); release(x); x = y;
-            SISIC_TRY(attention(u->mid_attn, x, &y)); release(x); x = y;
-            SISIC_TRY(resnet(u->mid_res[1], x, nullptr, &y)); release(x); x = y;
-        }
-
-        for (int i = 0; i < n; ++i) {
-            const int layers = cfg.layers_per_block + 1;
-            for (int j = 0; j < layers; ++j) {
-                SISIC_REQUIRE(!skips.empty(), "unet: skip stack underflow");
-                Buf* skip = skips.back();
-                skips.pop_back();
-                SISIC_REQUIRE(skip->H == x->H && skip->W == x->W, "unet: skip resolution %dx%d vs %dx%d (H and W must be divisible by %d)",
-                              skip->H, skip->W, x->H, x->W, 1 << (n - 1));
-                Buf* y = nullptr;
-                // (the block's output is normalised alone only when an attention block follows; the next ResNet block normalises
-                //  it together with a skip tensor)
-                SISIC_TRY(resnet(u->up_res[i][j], x, skip, &y, cfg.up_attn[i] ? &u->up_attn[i][j].norm : nullptr));
-                release(x);
-                release(skip);
-                x = y;
-                if (cfg.up_attn[i]) {
-                    SISIC_TRY(attention(u->up_attn[i][j], x, &y));
-                    release(x);
-                    x = y;
-                }
-            }
-            if (i != n - 1) {
-                Buf* y = make(u->upsamplers[i].cout, 2 * x->H, 2 * x->W, &rc); SISIC_TRY(rc);
-                SISIC_TRY(conv(u->upsamplers[i], x->p, x->C, nullptr, 0, x->H, x->W, 1, 1, false, false, nullptr, nullptr, y->p, y,
-                               x, nullptr, nullptr, y));
-                release(x);
-                x = y;
-            }
-        }
-        SISIC_REQUIRE(skips.empty(), "unet: skip stack not consumed");
-        SISIC_REQUIRE(x->H == H && x->W == W, "unet: output resolution mismatch");
-        SISIC_TRY(gn(x, nullptr, u->norm_out));
-        SISIC_TRY(conv(u->conv_out, x->p, x->C, nullptr, 0, H, W, 1, 0, true, true, nullptr, nullptr, out, nullptr, x, nullptr,
-                       nullptr, nullptr));
-        release(x);
-        return SISIC_OK;
-    }
-};
-
-int check_shape(sisic_unet* u, int B, int H, int W) {
+int unet_check_shape(sisic_unet* u, int B, int H, int W) {
     SISIC_REQUIRE(u, "unet: null handle");
     if (!u->loaded) {
         set_error("unet: forward called before sisic_unet_load");
@@ -628,6 +303,321 @@ int check_shape(sisic_unet* u, int B, int H, int W) {
     return SISIC_OK;
 }
 
+}  // namespace sisic
+
+namespace {
+
+// ------------------------------------------------------------------ forward
+// A tensor the executor reads or writes: where it is, its shape, and the pool buffer behind it.  buf is nullptr for the
+// network's own input and output (as TapeOp means it); w, the pointer a convolution writes through, is nullptr for the
+// network input, which is only read.
+struct Act {
+    const float* p = nullptr;
+    float* w = nullptr;
+    int C = 0, H = 0, W = 0;
+    Buf* buf = nullptr;
+    Act() = default;
+    Act(Buf* b) : buf(b) { if (b) { p = w = b->p; C = b->C; H = b->H; W = b->W; } }
+    Act(const float* in, int C_, int H_, int W_) : p(in), C(C_), H(H_), W(W_) {}
+    Act(float* out, int C_, int H_, int W_) : p(out), w(out), C(C_), H(H_), W(W_) {}
+};
+
+// One convolution of the network: out = conv(act(cat(in0, in1))) + bias + chan_bias + residual
+struct ConvOp {
+    const ConvW* w = nullptr;
+    Act in0, in1;                      // in1: the second tensor of a concatenation (empty: none)
+    int stride = 1, ups = 0;           // ups: read in0 through a nearest-2x map
+    bool gn_prologue = false;          // normalise the input with the pair the last gn() chose ...
+    bool silu = false;                 // ... and apply SiLU
+    const float* chan_bias = nullptr;  // per (sample, channel): this block's columns of the time-embedding projection
+    Act residual, out;
+    bool normed = false;               // a GroupNorm reads this output: have the epilogue leave partial statistics
+    const NormW* next_norm = nullptr;  // ... and it is this one, reading the output ALONE: finalize it too where the launch can
+    const AttnW* qkv_of = nullptr;     // the fused q/k/v projection of this attention block (tape)
+    const GnFinJob* rider = nullptr;   // an independent GroupNorm finalisation the launch may carry; *carried: whether it did
+    bool* carried = nullptr;
+};
+
+struct Fwd {
+    sisic_unet* u;
+    hipStream_t s;
+    int B;
+    const float* tproj;   // [B or 1, tproj_R]
+    int tproj_stride;     // tproj_R, or 0 when one row serves every sample
+    TrainState* tr = nullptr;     // training mode: record every operation, keep every buffer, save each GroupNorm's statistics
+    PoolScope scope{u->pool};     // every block of bufs that is still out
+    std::vector<std::unique_ptr<Buf>> bufs;
+    float* gsc = u->gn_scale;     // scale / shift the next convolution's prologue reads (the shared pair, or this op's own)
+    float* gsh = u->gn_shift;
+    float* gmr = nullptr;         // training mode: (mean, rstd) of the same GroupNorm
+    const NormW* gnorm = nullptr;
+
+    Buf* make(int C, int H, int W, int* rc) {
+        auto b = std::make_unique<Buf>();
+        b->C = C; b->H = H; b->W = W; b->refs = 1;
+        *rc = scope.get((size_t)B * C * H * W, &b->p);
+        bufs.push_back(std::move(b));
+        return bufs.back().get();
+    }
+    void release(Buf* b) {
+        if (tr) return;           // the backward pass reads every activation
+        if (b && --b->refs == 0 && b->p) {
+            scope.put(b->p);
+            b->p = nullptr;
+            if (b->stats) { scope.put(b->stats); b->stats = nullptr; }
+        }
+    }
+    void advance(Buf*& x, Buf* y) { release(x); x = y; }
+
+    // defer (inference only): where the finalisation would be a launch of its own, hand it back as a job instead -- the caller
+    // has a neighbouring launch to carry it (resnet(): the shortcut) and runs it BEFORE anything reads the pair
+    int gn(const Buf* x, const Buf* skip, const NormW& n, GnFinJob* defer = nullptr, bool* deferred = nullptr) {
+        gsc = u->gn_scale; gsh = u->gn_shift; gmr = nullptr; gnorm = &n;
+        if (!tr && !skip && x->fin_norm == static_cast<const void*>(&n)) {     // finalized by its producer (conv below)
+            gsc = x->fin_scale; gsh = x->fin_shift;
+            return SISIC_OK;
+        }
+        if (tr) {                 // this GroupNorm's own scale / shift / (mean, rstd): the backward pass needs them
+            const int C = x->C + (skip ? skip->C : 0);
+            SISIC_TRY(u->pool.get((size_t)B * C, &gsc));
+            SISIC_TRY(u->pool.get((size_t)B * C, &gsh));
+            SISIC_TRY(u->pool.get((size_t)B * u->cfg.norm_groups * 2, &gmr));
+            tr->grads_of_bufs.push_back(gsc); tr->grads_of_bufs.push_back(gsh); tr->grads_of_bufs.push_back(gmr);
+        }
+        if (x->stats && (!skip || skip->stats)) { // every producer left partials: no pass over the tensors
+            if (defer && !tr) {
+                *deferred = true;
+                return make_gn_fin_job(defer, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
+                                       skip ? skip->slots : 0, B, u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh);
+            }
+            return launch_gn_finalize(u->ctx, x->stats, x->C, x->slots, skip ? skip->stats : nullptr, skip ? skip->C : 0,
+                                      skip ? skip->slots : 0, B, x->H * x->W, u->cfg.norm_groups, u->cfg.norm_eps,
+                                      n.gamma, n.beta, gsc, gsh, s, gmr);
+        }
+        return launch_gn_stats(u->ctx, x->p, x->C, skip ? skip->p : nullptr, skip ? skip->C : 0, B, x->H * x->W,
+                               u->cfg.norm_groups, u->cfg.norm_eps, n.gamma, n.beta, gsc, gsh, s, gmr);
+    }
+
+    int conv(const ConvOp& op) {
+        const ConvW& c = *op.w;
+        Buf* outb = op.out.buf;
+        sisic_conv_args a{};
+        a.in0 = op.in0.p; a.c0 = op.in0.C; a.in1 = op.in1.p; a.c1 = op.in1.C;
+        a.B = B; a.Hin = op.in0.H; a.Win = op.in0.W; a.upsample = op.ups; a.ksize = c.k; a.stride = op.stride;
+        a.w_packed = c.packed; a.bias = c.bias; a.Cout = c.cout;
+        // (stride 2: the field carries the split filter of the bf16x3 downsampler kernel, sisic.h)
+        a.w_winograd = op.stride == 1 ? (u->use_winograd ? c.wino : nullptr) : (op.stride == 2 ? c.s2 : nullptr);
+        if (op.gn_prologue) { a.gn_scale = gsc; a.gn_shift = gsh; a.gn_silu = op.silu ? 1 : 0; }
+        a.chan_bias = op.chan_bias; a.chan_bias_stride = tproj_stride;
+        a.residual = op.residual.p; a.out = op.out.w;
+        // single-image latency (the reference's own call pattern, image_generator.py:379: batch 1): conv_plan.cpp
+        if (u->latency_mode) a.tile_cfg = conv_latency_cfg(a);
+        if (op.normed && u->fuse_gn) {             // a GroupNorm reads this output: have the epilogue leave partials
+            const int slots = conv_stats_slots(a);
+            if (slots > 0) {
+                SISIC_TRY(scope.get((size_t)B * c.cout * slots * 4, &outb->stats));
+                outb->slots = slots;
+                a.stats_out = outb->stats;
+            }
+        }
+        // next_norm: the GroupNorm that reads this output ALONE, when the caller knows it: where the launch can finalize it
+        // (sisic_conv_finalizes: the 8x8 level's K-split forms) it leaves that layer's (scale, shift) in the shared pair -- which
+        // this very convolution's prologue may still be reading: the finalisation runs in the reduction launch behind it
+        if (op.normed && op.next_norm && u->fuse_gn && !tr) {
+            a.fin_gamma = op.next_norm->gamma; a.fin_beta = op.next_norm->beta; a.fin_groups = u->cfg.norm_groups; a.fin_eps = u->cfg.norm_eps;
+            // (the pair this launch's own prologue is NOT reading: a workgroup finalizes its image while others still read theirs)
+            const bool first_pair_busy = op.gn_prologue && gsc == u->gn_scale;
+            a.fin_scale = first_pair_busy ? u->gn_scale2 : u->gn_scale;
+            a.fin_shift = first_pair_busy ? u->gn_shift2 : u->gn_shift;
+            if (conv_finalizes(a)) { outb->fin_norm = op.next_norm; outb->fin_scale = a.fin_scale; outb->fin_shift = a.fin_shift; }
+            else { a.fin_gamma = nullptr; a.fin_beta = nullptr; a.fin_scale = nullptr; a.fin_shift = nullptr; }
+        }
+        if (tr) {
+            TapeOp t;
+            t.kind = TapeOp::CONV;
+            t.w = c; t.qkv_of = op.qkv_of;
+            t.in0 = op.in0.buf; t.in1 = op.in1.buf; t.in0_ptr = op.in0.p; t.in1_ptr = op.in1.p;
+            t.c0 = op.in0.C; t.c1 = op.in1.C; t.H = op.in0.H; t.W = op.in0.W; t.stride = op.stride; t.ups = op.ups;
+            if (op.gn_prologue) { t.norm = gnorm; t.gn_scale = gsc; t.gn_shift = gsh; t.gn_mr = gmr; t.silu = op.silu; }
+            t.temb_off = op.chan_bias ? (int)(op.chan_bias - tproj) : -1;
+            t.residual = op.residual.buf; t.out = outb; t.out_ptr = op.out.w;
+            tr->tape.push_back(t);
+        }
+        return launch_conv2d(u->ctx, a, s, op.rider, op.carried);
+    }
+
+    // out = ResnetBlock2D(cat(x, skip)); consumes nothing (caller releases inputs)
+    // next_norm: the GroupNorm module that reads the block's output alone, when the caller knows it (conv(): finalized by conv2's
+    // own launch where that is possible)
+    int resnet(const ResnetW& r, Buf* x, Buf* skip, Buf** out, const NormW* next_norm = nullptr) {
+        int rc = SISIC_OK;
+        const int H = x->H, W = x->W;
+        const int c1 = skip ? skip->C : 0;
+        SISIC_REQUIRE(x->C + c1 == r.cin, "unet: resnet expects %d input channels, got %d", r.cin, x->C + c1);
+        // The 1x1 shortcut reads the raw block inputs only: it neither needs norm1 nor does conv1 need it.  In inference, where
+        // norm1's finalisation would be a launch of its own, the shortcut runs FIRST and carries the jobs as extra workgroups
+        // (conv_pointwise_bf3.hip); conv1, next in stream order, is the first reader of the pair.  The launcher says whether its
+        // kernel ran them (the f32 1x1 kernels, latency mode's tiles and shapes the bf16x3 kernels refuse do not): if not, the
+        // stand-alone launch follows.  (SISIC_GN_RIDER=0: the order and launches without any of this.)
+        GnFinJob fin{};
+        bool deferred = false;
+        SISIC_TRY(gn(x, skip, r.norm1, (u->gn_rider && !tr && r.shortcut.k) ? &fin : nullptr, &deferred));
+        Buf* sc = nullptr;
+        auto shortcut = [&]() -> int {
+            bool carried = false;
+            sc = make(r.cout, H, W, &rc); SISIC_TRY(rc);
+            ConvOp op;
+            op.w = &r.shortcut; op.in0 = x; op.in1 = skip; op.out = sc;
+            if (deferred) { op.rider = &fin; op.carried = &carried; }
+            SISIC_TRY(conv(op));
+            if (deferred && !carried) SISIC_TRY(launch_gn_finalize_job(u->ctx, fin, s));
+            return SISIC_OK;
+        };
+        if (deferred) SISIC_TRY(shortcut());
+        Buf* h = make(r.cout, H, W, &rc); SISIC_TRY(rc);
+        {
+            ConvOp op;
+            op.w = &r.conv1; op.in0 = x; op.in1 = skip; op.gn_prologue = true; op.silu = true;
+            op.chan_bias = tproj + r.temb_off; op.out = h; op.normed = true; op.next_norm = &r.norm2;
+            SISIC_TRY(conv(op));
+        }
+        if (r.shortcut.k) {
+            if (!deferred) SISIC_TRY(shortcut());
+        } else {
+            SISIC_REQUIRE(c1 == 0 && x->C == r.cout, "unet: identity shortcut with mismatched channels");
+        }
+        SISIC_TRY(gn(h, nullptr, r.norm2));
+        Buf* o = make(r.cout, H, W, &rc); SISIC_TRY(rc);
+        {
+            ConvOp op;
+            op.w = &r.conv2; op.in0 = h; op.gn_prologue = true; op.silu = true;
+            op.residual = sc ? sc : x; op.out = o; op.normed = true; op.next_norm = next_norm;
+            SISIC_TRY(conv(op));
+        }
+        release(h);
+        release(sc);
+        *out = o;
+        return SISIC_OK;
+    }
+
+    int attention(const AttnW& a, Buf* x, Buf** out) {
+        int rc = SISIC_OK;
+        const int H = x->H, W = x->W, N = H * W, C = a.c;
+        SISIC_REQUIRE(x->C == C, "unet: attention channel mismatch");
+        SISIC_TRY(gn(x, nullptr, a.norm));
+        Buf* qkv = make(3 * C, H, W, &rc); SISIC_TRY(rc);
+        ConvW cq; cq.cout = 3 * C; cq.cin = C; cq.k = 1; cq.packed = a.qkv_packed; cq.bias = a.qkv_bias;
+        {
+            ConvOp op;
+            op.w = &cq; op.in0 = x; op.gn_prologue = true; op.out = qkv; op.qkv_of = &a;
+            SISIC_TRY(conv(op));
+        }
+        Buf* o = make(C, H, W, &rc); SISIC_TRY(rc);
+        SISIC_TRY(launch_attention(u->ctx, qkv->p, o->p, B, C, N, u->cfg.head_dim, s));
+        if (tr) {
+            TapeOp op;
+            op.kind = TapeOp::ATTN;
+            op.qkv = qkv; op.o = o; op.C = C; op.N = N;
+            tr->tape.push_back(op);
+        }
+        release(qkv);
+        Buf* y = make(C, H, W, &rc); SISIC_TRY(rc);
+        {
+            ConvOp op;
+            op.w = &a.out; op.in0 = o; op.residual = x; op.out = y; op.normed = true;
+            SISIC_TRY(conv(op));
+        }
+        release(o);
+        *out = y;
+        return SISIC_OK;
+    }
+
+    // a convolution between blocks (conv_in, the samplers): its output feeds a GroupNorm, nothing else is fused
+    int plain_conv(const ConvW& c, const Act& in, int stride, int ups, Buf* out) {
+        ConvOp op;
+        op.w = &c; op.in0 = in; op.stride = stride; op.ups = ups; op.out = out; op.normed = true;
+        return conv(op);
+    }
+
+    int run(const float* sample, float* out, int H, int W) {
+        const sisic_unet_config& cfg = u->cfg;
+        const int n = cfg.n_blocks;
+        int rc = SISIC_OK;
+        std::vector<Buf*> skips;
+
+        Buf* x = make(u->conv_in.cout, H, W, &rc); SISIC_TRY(rc);
+        SISIC_TRY(plain_conv(u->conv_in, Act(sample, cfg.in_channels, H, W), 1, 0, x));
+        x->refs++;                 // held by `x` and by the skip stack
+        skips.push_back(x);
+
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < cfg.layers_per_block; ++j) {
+                Buf* y = nullptr;
+                // who normalises this block's output next (alone: the up path's concatenations have two producers)
+                const NormW* next = cfg.down_attn[i] ? &u->down_attn[i][j].norm
+                                    : (j + 1 < cfg.layers_per_block ? &u->down_res[i][j + 1].norm1 : (i == n - 1 ? &u->mid_res[0].norm1 : nullptr));
+                SISIC_TRY(resnet(u->down_res[i][j], x, nullptr, &y, next));
+                advance(x, y);
+                if (cfg.down_attn[i]) {
+                    SISIC_TRY(attention(u->down_attn[i][j], x, &y));
+                    advance(x, y);
+                }
+                x->refs++;
+                skips.push_back(x);
+            }
+            if (i != n - 1) {
+                const int Ho = (x->H + 2 - 3) / 2 + 1, Wo = (x->W + 2 - 3) / 2 + 1;
+                Buf* y = make(u->downsamplers[i].cout, Ho, Wo, &rc); SISIC_TRY(rc);
+                SISIC_TRY(plain_conv(u->downsamplers[i], x, 2, 0, y));
+                advance(x, y);
+                x->refs++;
+                skips.push_back(x);
+            }
+        }
+
+        {
+            Buf* y = nullptr;
+            SISIC_TRY(resnet(u->mid_res[0], x, nullptr, &y, &u->mid_attn.norm)); advance(x, y);
+            SISIC_TRY(attention(u->mid_attn, x, &y)); advance(x, y);
+            SISIC_TRY(resnet(u->mid_res[1], x, nullptr, &y)); advance(x, y);
+        }
+
+        for (int i = 0; i < n; ++i) {
+            const int layers = cfg.layers_per_block + 1;
+            for (int j = 0; j < layers; ++j) {
+                SISIC_REQUIRE(!skips.empty(), "unet: skip stack underflow");
+                Buf* skip = skips.back();
+                skips.pop_back();
+                SISIC_REQUIRE(skip->H == x->H && skip->W == x->W, "unet: skip resolution %dx%d vs %dx%d (H and W must be divisible by %d)",
+                              skip->H, skip->W, x->H, x->W, 1 << (n - 1));
+                Buf* y = nullptr;
+                // (the block's output is normalised alone only when an attention block follows; the next ResNet block normalises
+                //  it together with a skip tensor)
+                SISIC_TRY(resnet(u->up_res[i][j], x, skip, &y, cfg.up_attn[i] ? &u->up_attn[i][j].norm : nullptr));
+                advance(x, y);
+                release(skip);
+                if (cfg.up_attn[i]) {
+                    SISIC_TRY(attention(u->up_attn[i][j], x, &y));
+                    advance(x, y);
+                }
+            }
+            if (i != n - 1) {
+                Buf* y = make(u->upsamplers[i].cout, 2 * x->H, 2 * x->W, &rc); SISIC_TRY(rc);
+                SISIC_TRY(plain_conv(u->upsamplers[i], x, 1, 1, y));
+                advance(x, y);
+            }
+        }
+        SISIC_REQUIRE(skips.empty(), "unet: skip stack not consumed");
+        SISIC_REQUIRE(x->H == H && x->W == W, "unet: output resolution mismatch");
+        SISIC_TRY(gn(x, nullptr, u->norm_out));
+        ConvOp op;
+        op.w = &u->conv_out; op.in0 = x; op.gn_prologue = true; op.silu = true; op.out = Act(out, cfg.out_channels, H, W);
+        SISIC_TRY(conv(op));
+        release(x);
+        return SISIC_OK;
+    }
+};
+
 // time embedding + all time_emb_proj rows for `rows` timesteps (t_vals already on the device)
 int time_embed(sisic_unet* u, int rows, hipStream_t s) {
     SISIC_TRY(launch_temb_mlp(u->ctx, u->t_vals, rows, u->d_freqs, u->cfg.n_freqs, u->w1t, u->rawp(u->temb_b1), u->w2t,
@@ -636,40 +626,20 @@ int time_embed(sisic_unet* u, int rows, hipStream_t s) {
     return SISIC_OK;
 }
 
-int run_forward(sisic_unet* u, const float* sample, const float* tproj, int tproj_stride, float* out, int B, int H,
-                int W, hipStream_t s, TrainState* tr = nullptr) {
-    Fwd f{u, s, B, tproj, tproj_stride, {}};
-    f.tr = tr;
-    f.gsc = u->gn_scale; f.gsh = u->gn_shift;
-    const int rc = f.run(sample, out, H, W);
-    if (tr && rc == SISIC_OK) {        // training mode: the tape owns the activations until the backward pass has run
-        for (auto& b : f.bufs) tr->bufs.push_back(std::move(b));
-        return rc;
-    }
-    for (auto& b : f.bufs) {           // inference, and error paths: hand everything back
-        if (b->p) pool_put(u, b->p);
-        if (b->stats) pool_put(u, b->stats);
-    }
-    if (tr) tr->tape.clear();
-    return rc;
-}
-
 }  // namespace
 
-namespace sisic {
-int unet_pool_get(sisic_unet* u, size_t floats, float** out) { return pool_get(u, floats, out); }
-void unet_release_tape(sisic_unet* u) { tape_drop(u, true); }
-void unet_pool_put(sisic_unet* u, float* p) { pool_put(u, p); }
-int unet_grow(float** p, size_t* have, size_t want) { return grow(p, have, want); }
-int unet_check_shape(sisic_unet* u, int B, int H, int W) { return check_shape(u, B, H, W); }
-int unet_ensure_rows(sisic_unet* u, size_t t_rows, size_t gn_rows) { return ensure_rows(u, t_rows, gn_rows); }
-int unet_stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hipStream_t s) { return stage_upload(u, src, n, dst, s); }
-int unet_prepare_all(sisic_unet* u, hipStream_t s) { return prepare_all(u, s); }
-int unet_run_forward(sisic_unet* u, const float* sample, const float* tproj, int tproj_stride, float* out, int B, int H,
-                     int W, hipStream_t s, TrainState* tape) {
-    return run_forward(u, sample, tproj, tproj_stride, out, B, H, W, s, tape);
+int sisic::unet_run_forward(sisic_unet* u, const float* sample, const float* tproj, int tproj_stride, float* out, int B, int H,
+                            int W, hipStream_t s, TrainState* tr) {
+    Fwd f{u, s, B, tproj, tproj_stride, tr};
+    const int rc = f.run(sample, out, H, W);      // inference, and error paths: f.scope hands everything back
+    if (tr && rc == SISIC_OK) {                   // training mode: the tape owns the activations until the backward pass has run
+        for (auto& b : f.bufs) tr->bufs.push_back(std::move(b));
+        f.scope.disown();
+    } else if (tr) {
+        tr->tape.clear();
+    }
+    return rc;
 }
-}  // namespace sisic
 
 extern "C" {
 
@@ -733,9 +703,7 @@ int sisic_unet_set_graph_mode(sisic_unet* u, int mode) {
 int64_t sisic_unet_graph_builds(const sisic_unet* u) { return u ? u->loop_builds : 0; }
 
 int64_t sisic_unet_workspace_bytes(const sisic_unet* u) {
-    int64_t n = 0;
-    if (u) for (const auto& b : u->pool) n += (int64_t)b.bytes;
-    return n;
+    return u ? u->pool.bytes() : 0;
 }
 
 int sisic_unet_num_tensors(const sisic_unet* u) { return u ? (int)u->names.size() : 0; }
@@ -776,7 +744,7 @@ int sisic_unet_load(sisic_unet* u, int n, const char* const* names, const float*
     u->owned.clear();
     reset_derived(u);
     u->loaded = false;
-    SISIC_TRY(prepare_all(u, nullptr));
+    SISIC_TRY(unet_prepare_all(u, nullptr));
     SISIC_HIP(hipDeviceSynchronize());
     u->loaded = true;
     return SISIC_OK;
@@ -786,8 +754,8 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
                        void* stream) {
     SISIC_REQUIRE(u && sample && timesteps && out, "unet_forward: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SISIC_TRY(check_shape(u, B, H, W));
-    SISIC_TRY(ensure_rows(u, (size_t)B, (size_t)B));
+    SISIC_TRY(unet_check_shape(u, B, H, W));
+    SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
     std::vector<float> tv(B);
     bool uniform = true;
     for (int b = 0; b < B; ++b) {
@@ -795,9 +763,9 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
         uniform = uniform && timesteps[b] == timesteps[0];
     }
     const int rows = uniform ? 1 : B;
-    SISIC_TRY(stage_upload(u, tv.data(), (size_t)rows, u->t_vals, s));
+    SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)rows, u->t_vals, s));
     SISIC_TRY(time_embed(u, rows, s));
-    return run_forward(u, sample, u->tproj, uniform ? 0 : u->tproj_R, out, B, H, W, s);
+    return unet_run_forward(u, sample, u->tproj, uniform ? 0 : u->tproj_R, out, B, H, W, s);
 }
 
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
@@ -808,7 +776,7 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + 5 * 1000);
     SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
-    SISIC_TRY(run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
+    SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
     if (rng)
         SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
                                           coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
@@ -829,15 +797,15 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     SISIC_REQUIRE(T <= 1000, "sample: at most 1000 steps per call");
     // the replayed launches write into the pool blocks they were captured with; a tape recorded since then may own some of
     // them: the tape does not survive a graph-replayed run (sisic_unet_backward then answers SISIC_ESTATE)
-    tape_drop(u, true);
+    unet_release_tape(u);
     hipStream_t s = caller;
     if (!s) {                              // the legacy default stream cannot be captured: a blocking stream of our own,
         if (!u->loop_stream) SISIC_HIP(hipStreamCreate(&u->loop_stream));     // implicitly ordered with the default stream
         s = u->loop_stream;
     }
-    SISIC_TRY(grow(&u->x_work, &u->x_work_cap, n));
-    SISIC_TRY(grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)u->tproj_R));
-    SISIC_TRY(grow(&u->loop_tables, &u->loop_tables_cap, (size_t)4 + 5 * 1000 + 1000));
+    SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, n));
+    SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)u->tproj_R));
+    SISIC_TRY(unet_grow(&u->loop_tables, &u->loop_tables_cap, (size_t)4 + 5 * 1000 + 1000));
     // tables of this call: {step = 0, step base, noise base}, coefficients, noise row per step (-1: the step adds no noise)
     std::vector<float> tab(4 + 5 * 1000 + 1000, 0.0f);
     {
@@ -850,7 +818,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         int zi = 0;
         for (int i = 0; i < T; ++i) zr[i] = (noise && coef[(size_t)i * 5 + 4] != 0.0f) ? zi++ : -1;
     }
-    SISIC_TRY(stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
+    SISIC_TRY(unet_stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
     SISIC_HIP(hipMemcpyAsync(u->x_work, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     auto after_step = [&](int i) -> int {
@@ -948,27 +916,27 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
     if (rule != STEP_RULE_DDPM || rule_flags != 0)
         for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * 5 + 0], coef[(size_t)i * 5 + 1]));
-    SISIC_TRY(check_shape(u, B, H, W));
+    SISIC_TRY(unet_check_shape(u, B, H, W));
     // per-step tables for 1000 rows from the first call on (17 MB): a longer run after a shorter one then never moves the
     // time-embedding table, so the captured step (which holds its address) survives a change of T
-    SISIC_TRY(ensure_rows(u, (size_t)std::max(T, 1000), (size_t)B));
+    SISIC_TRY(unet_ensure_rows(u, (size_t)std::max(T, 1000), (size_t)B));
     const int C = u->cfg.in_channels;
     SISIC_REQUIRE(u->cfg.out_channels == C, "sample: in/out channels differ");
     const size_t n = (size_t)B * C * H * W;
-    SISIC_TRY(grow(&u->eps_buf, &u->eps_floats, n));
+    SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, n));
     const bool rng = seeds != nullptr;
     if (rng) {
         // 2^31 step indices is ample (a run has at most 1000) and keeps step0 + i inside the int of the device-side state
         SISIC_REQUIRE(step0 >= 0 && step0 <= INT32_MAX - T, "sample_rng: step0 %d", step0);
         static_assert(sizeof(uint64_t) == 2 * sizeof(float), "seeds are staged as pairs of floats");
-        SISIC_TRY(grow(&u->seeds_dev, &u->seeds_cap, 2 * (size_t)std::max(B, 64)));
-        SISIC_TRY(stage_upload(u, reinterpret_cast<const float*>(seeds), 2 * (size_t)B, u->seeds_dev, s));
+        SISIC_TRY(unet_grow(&u->seeds_dev, &u->seeds_cap, 2 * (size_t)std::max(B, 64)));
+        SISIC_TRY(unet_stage_upload(u, reinterpret_cast<const float*>(seeds), 2 * (size_t)B, u->seeds_dev, s));
     }
 
     // every step's time embedding and time_emb_proj rows in one batch before the loop
     std::vector<float> tv(T);
     for (int i = 0; i < T; ++i) tv[i] = (float)timesteps[i];
-    SISIC_TRY(stage_upload(u, tv.data(), (size_t)T, u->t_vals, s));
+    SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)T, u->t_vals, s));
     SISIC_TRY(time_embed(u, T, s));
 
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
@@ -990,7 +958,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
                 return SISIC_ECANCEL;
             }
         }
-        SISIC_TRY(run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
+        SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
         const float* c = coef + (size_t)i * 5;
         const float* z = nullptr;
         if (noise && c[4] != 0.0f) z = noise + (zi++) * n;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "workspace.h"
 
 namespace sisic {
 
@@ -61,12 +62,6 @@ struct Buf {
     const void* fin_norm = nullptr;   // the GroupNorm module whose (scale, shift) the producing convolution has already left in
     float* fin_scale = nullptr;       // fin_scale / fin_shift (sisic_conv_args.fin_*): its finalisation launch is skipped
     float* fin_shift = nullptr;
-};
-
-struct PoolBlock {
-    float* p;
-    size_t bytes;
-    bool free_;
 };
 
 // One recorded operation of a training-mode forward pass (train.cpp walks the tape backwards).
@@ -140,7 +135,6 @@ struct TrainState {
 
 struct sisic_unet {
     using ConvW = sisic::ConvW; using NormW = sisic::NormW; using ResnetW = sisic::ResnetW; using AttnW = sisic::AttnW;
-    using PoolBlock = sisic::PoolBlock;
     sisic_ctx* ctx = nullptr;
     sisic_unet_config cfg{};
     std::vector<float> freqs;
@@ -173,7 +167,7 @@ struct sisic_unet {
     int max_c = 0;
 
     // workspace
-    std::vector<PoolBlock> pool;
+    sisic::Pool pool;            // activations of a run at (ws_B, ws_H, ws_W); emptied when the shape changes
     int ws_B = 0, ws_H = 0, ws_W = 0;
     float* t_vals = nullptr;     // [B] or [T]
     float* temb_act = nullptr;   // [B or T, hidden]
@@ -236,8 +230,6 @@ struct sisic_unet {
 namespace sisic {
 
 // unet.cpp internals used by train.cpp
-int unet_pool_get(sisic_unet* u, size_t floats, float** out);
-void unet_pool_put(sisic_unet* u, float* p);
 // hand the recorded training forward's blocks back to the pool and forget it (backward then answers SISIC_ESTATE)
 void unet_release_tape(sisic_unet* u);
 // floats of TrainState::small: [B, Cout <= 3 max_c] plane sums, then [2][B][Cin <= max_c] GroupNorm sums or [3C] column sums
@@ -252,7 +244,7 @@ int unet_stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hip
 int unet_prepare_all(sisic_unet* u, hipStream_t s);
 // forward pass; with `tape` set nothing is released and every operation is recorded (training mode)
 int unet_run_forward(sisic_unet* u, const float* sample, const float* tproj, int tproj_stride, float* out, int B, int H,
-                     int W, hipStream_t s, TrainState* tape);
+                     int W, hipStream_t s, TrainState* tape = nullptr);
 
 // every convolution / attention block / residual block of the model, in state-dict order
 inline std::vector<ResnetW*> unet_resnets(sisic_unet* u) {

@@ -239,6 +239,14 @@ def test_input_gradient_matches_autograd_of_the_oracle(clf, clf_sd, B, H, W, tar
     assert strict >= 1
 
 
+def test_input_gradient_reports_the_forward_logits_bit_for_bit(clf):
+    """forward and the forward half of input_gradient are one trunk in resnet.cpp (the same launches on the same pool): at an
+    odd, non-square size, with pre-processing, the logits of the two entry points are the same bits."""
+    x = (torch.rand(2, 3, 48, 40, generator=torch.Generator().manual_seed(48)) * 1.6 - 0.8).to(DEV)
+    _, logits = clf.input_gradient(x, NV)
+    assert logits.shape == (2, 7) and torch.equal(logits, clf(x))
+
+
 REPLAY_TOL = 1e-3       # one ReLU of the 17 flipping at a pre-activation within rounding of zero moves the gradient by ~4e-4
 STRICT_TOL = 1e-5
 
