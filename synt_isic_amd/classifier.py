@@ -206,7 +206,7 @@ class HipMelanomaClassifier:
             raise ValueError(f"classifier input must be [B,3,H,W], got {tuple(x.shape)}")
         x = x.to(torch.float32).contiguous()
         B, _, H, W = x.shape
-        out = torch.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
+        out = ops.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for lo, n in self._chunks(B, self.max_forward_batch):
             check(_lib.load().sisic_resnet_forward(h, x[lo:].data_ptr(), out[lo:].data_ptr(), n, H, W,
@@ -218,8 +218,8 @@ class HipMelanomaClassifier:
     def _scores(self, x: torch.Tensor, target_class: int):
         logits = self.forward(x)
         B = logits.shape[0]
-        prob = torch.empty(B, dtype=torch.float32, device=logits.device)
-        logscore = torch.empty_like(prob)
+        prob = ops.empty(B, dtype=torch.float32, device=logits.device)
+        logscore = ops.empty_like(prob)
         check(_lib.load().sisic_class_scores(ops.context(logits.device), logits.data_ptr(), B, self.num_classes,
                                              int(target_class), prob.data_ptr(), logscore.data_ptr(),
                                              C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)))
@@ -230,7 +230,7 @@ class HipMelanomaClassifier:
         logits = self.forward(x)
         cols = []
         for c in range(self.num_classes):
-            p = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+            p = ops.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
             check(_lib.load().sisic_class_scores(ops.context(logits.device), logits.data_ptr(), logits.shape[0],
                                                  self.num_classes, c, p.data_ptr(), None,
                                                  C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)))
@@ -252,7 +252,7 @@ class HipMelanomaClassifier:
         h = self.handle
         x = x.to(self._device).detach().to(torch.float32).contiguous()
         B, _, H, W = x.shape
-        out = torch.empty((B, 64, 112, 112), dtype=torch.float32, device=x.device)
+        out = ops.empty((B, 64, 112, 112), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for lo, n in self._chunks(B, self.max_forward_batch):
             check(_lib.load().sisic_resnet_stem(h, x[lo:].data_ptr(), out[lo:].data_ptr(), n, H, W, 1, stream))
@@ -269,8 +269,8 @@ class HipMelanomaClassifier:
             raise ValueError(f"classifier input must be [B,3,H,W], got {tuple(x.shape)}")
         x = x.detach().to(torch.float32).contiguous()
         B, _, H, W = x.shape
-        grad = torch.empty_like(x)
-        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
+        grad = ops.empty_like(x)
+        logits = ops.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for lo, n in self._chunks(B, self.max_backward_batch):
             check(_lib.load().sisic_resnet_input_gradient(h, x[lo:].data_ptr(), n, H, W, int(target_class),
@@ -287,8 +287,8 @@ class HipMelanomaClassifier:
             raise ValueError(f"classifier input must be [B,3,H,W], got {tuple(x.shape)}")
         x = x.detach().to(torch.float32).contiguous()
         B, _, H, W = x.shape
-        cam = torch.empty((B, 224, 224), dtype=torch.float32, device=x.device)
-        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
+        cam = ops.empty((B, 224, 224), dtype=torch.float32, device=x.device)
+        logits = ops.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         for lo, n in self._chunks(B, self.max_backward_batch):
             check(_lib.load().sisic_resnet_gradcam(h, x[lo:].data_ptr(), n, H, W, int(target_class),

@@ -1,8 +1,10 @@
 // conv_plan.cpp -- the one place that decides which kernel runs a convolution (conv_plan.h).
 #include "conv_plan.h"
+#include "poison_switch.h"
 
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 
 namespace sisic {
 
@@ -15,6 +17,16 @@ const Switches& switches() {
                              env_on("SISIC_POINTWISE"), env_on("SISIC_POINTWISE_BF16X3"), env_on("SISIC_POINTWISE_KSPLIT"), env_on("SISIC_S2_BF16X3")};
     return sw;
 }
+
+}  // namespace
+
+// the allocation test switch (poison_switch.h, workspace.h): off unless set to a non-zero number
+bool poison_alloc() {
+    static const bool on = [] { const char* e = std::getenv("SISIC_POISON_ALLOC"); return e && std::atoi(e) != 0; }();
+    return on;
+}
+
+namespace {
 
 struct DirectTiling { int cfg, ks, stride, tw, th, wn; };
 constexpr DirectTiling DIRECT[] = {

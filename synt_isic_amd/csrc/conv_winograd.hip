@@ -23,6 +23,7 @@
 #include "conv_plan.h"
 #include "gn_merge.h"
 #include "pack_device.h"
+#include "poison_switch.h"
 
 // Timing-only ablation builds for tools/conv_bench.py (results are wrong): bit 0 skips the MFMAs, bit 1 the
 // output transform, bit 2 the halo staging + input transform.  Never defined in the shipped library.
@@ -1037,6 +1038,10 @@ static int splitk_scratch(sisic_ctx* ctx, hipStream_t s, size_t floats, float** 
         if (buf.p) SISIC_HIP(hipFree(buf.p));
         buf.p = nullptr; buf.floats = 0;
         SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&buf.p), floats * sizeof(float)));
+        if (poison_alloc()) {                        // SISIC_POISON_ALLOC=1: a slab no workgroup writes is NaN, not an old sum
+            SISIC_HIP(hipMemset(buf.p, 0xFF, floats * sizeof(float)));
+            SISIC_HIP(hipDeviceSynchronize());
+        }
         buf.floats = floats;
         ctx->scratch_generation.fetch_add(1);
     }

@@ -102,6 +102,7 @@ void describe(sisic_resnet* r) {
 int dev_alloc(sisic_resnet* r, size_t floats, float** out) {
     void* p = nullptr;
     SISIC_HIP(hipMalloc(&p, std::max<size_t>(floats, 4) * sizeof(float)));
+    SISIC_TRY(poison_fresh(p, std::max<size_t>(floats, 4) * sizeof(float)));
     r->owned.push_back(static_cast<float*>(p));
     *out = static_cast<float*>(p);
     return SISIC_OK;
@@ -415,7 +416,7 @@ int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, 
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PoolScope ws(r->pool);
+    PoolScope ws(r->pool, s);
     Trunk t;
     t.preprocess = preprocess != 0;
     t.logits = logits;
@@ -434,7 +435,7 @@ int sisic_resnet_stem(sisic_resnet* r, const float* x, float* c1_out, int B, int
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PoolScope ws(r->pool);
+    PoolScope ws(r->pool, s);
     Trunk t;
     t.preprocess = preprocess != 0;
     t.stem_out = c1_out;
@@ -456,7 +457,7 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PoolScope ws(r->pool);
+    PoolScope ws(r->pool, s);
     // transposed convolution of `c` applied to g [B, c.cout, gh, gw]; stride 2: zero-insertion input (2gh x 2gw grid)
     auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
         sisic_conv_args a{};
@@ -544,7 +545,7 @@ int sisic_resnet_gradcam(sisic_resnet* r, const float* x, int B, int H, int W, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int S = 224;
     SISIC_REQUIRE(H <= S && W <= S, "resnet_gradcam: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
-    PoolScope ws(r->pool);
+    PoolScope ws(r->pool, s);
     Trunk t;
     t.split_last = true;
     SISIC_TRY(run_trunk(r, ws, x, B, H, W, t, s));

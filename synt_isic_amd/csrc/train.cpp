@@ -92,6 +92,7 @@ int build_repack_plan(sisic_unet* u) {
         for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
         if (tr->repack_dev[p]) { (void)hipFree(tr->repack_dev[p]); tr->repack_dev[p] = nullptr; }
         SISIC_HIP(hipMalloc(&tr->repack_dev[p], std::max<size_t>(ph[p].size(), 1) * sizeof(PackJob)));
+        SISIC_TRY(poison_fresh(tr->repack_dev[p], std::max<size_t>(ph[p].size(), 1) * sizeof(PackJob)));
         SISIC_HIP(hipMemcpy(tr->repack_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
         tr->repack_jobs[p] = (int)ph[p].size();
         tr->repack_blocks[p] = blocks;
@@ -261,6 +262,7 @@ struct Bwd {
             SISIC_HIP(hipStreamSynchronize(s));          // (a table in use is not replaced under a running launch)
             if (tr->scatter_dev) { (void)hipFree(tr->scatter_dev); tr->scatter_dev = nullptr; }
             SISIC_HIP(hipMalloc(&tr->scatter_dev, std::max<size_t>(jobs.size(), 1) * sizeof(PackJob)));
+            SISIC_TRY(poison_fresh(tr->scatter_dev, std::max<size_t>(jobs.size(), 1) * sizeof(PackJob)));
             SISIC_HIP(hipMemcpy(tr->scatter_dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
             tr->scatter_jobs = (int)jobs.size(); tr->scatter_blocks = blocks; tr->scatter_src = dWf;
         }
@@ -339,14 +341,18 @@ int sisic_unet_train_begin(sisic_unet* u) {
         for (float** p : {&tr->grad, &tr->adam_m, &tr->adam_v}) {
             void* q = nullptr;
             SISIC_HIP(hipMalloc(&q, bytes));
+            SISIC_TRY(poison_fresh(q, bytes));       // (all three are zero-filled below, as ever)
             *p = static_cast<float*>(q);
         }
         void* q = nullptr;
         SISIC_HIP(hipMalloc(&q, 4 * sizeof(float)));
+        SISIC_TRY(poison_fresh(q, 4 * sizeof(float)));
         tr->loss_dev = static_cast<float*>(q);
         SISIC_HIP(hipMalloc(&q, sizeof(int)));
+        SISIC_TRY(poison_fresh(q, sizeof(int)));
         tr->flag_dev = static_cast<int*>(q);
         SISIC_HIP(hipMalloc(&q, 2048 * sizeof(float)));
+        SISIC_TRY(poison_fresh(q, 2048 * sizeof(float)));
         tr->mse_part = static_cast<float*>(q);
         u->train = std::move(tr);
     }
@@ -555,6 +561,7 @@ int sisic_conv2d_wgrad(sisic_ctx* ctx, const sisic_conv_args* f, const float* dy
     const size_t need = conv_wgrad_scratch_floats(a);
     void* part = nullptr;
     SISIC_HIP(hipMalloc(&part, need * sizeof(float)));
+    SISIC_TRY(poison_fresh(part, need * sizeof(float)));
     const int rc = launch_conv_wgrad(ctx, a, static_cast<float*>(part), need, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(part);
@@ -576,6 +583,7 @@ int sisic_groupnorm_bwd(sisic_ctx* ctx, const float* da, const float* x, int B, 
     void* p = nullptr;
     const size_t n = (size_t)4 * B * C + (size_t)2 * B * groups;
     SISIC_HIP(hipMalloc(&p, n * sizeof(float)));
+    SISIC_TRY(poison_fresh(p, n * sizeof(float)));
     float* scale = static_cast<float*>(p);
     float* shift = scale + (size_t)B * C;
     float* sums = shift + (size_t)B * C;

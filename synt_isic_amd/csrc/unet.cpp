@@ -244,6 +244,7 @@ int unet_grow(float** p, size_t* have, size_t want) {
     *p = nullptr; *have = 0;
     void* q = nullptr;
     SISIC_HIP(hipMalloc(&q, want * sizeof(float)));
+    SISIC_TRY(poison_fresh(q, want * sizeof(float)));
     *p = static_cast<float*>(q);
     *have = want;
     return SISIC_OK;
@@ -345,7 +346,7 @@ struct Fwd {
     const float* tproj;   // [B or 1, tproj_R]
     int tproj_stride;     // tproj_R, or 0 when one row serves every sample
     TrainState* tr = nullptr;     // training mode: record every operation, keep every buffer, save each GroupNorm's statistics
-    PoolScope scope{u->pool};     // every block of bufs that is still out
+    PoolScope scope{u->pool, s};     // every block of bufs that is still out
     std::vector<std::unique_ptr<Buf>> bufs;
     float* gsc = u->gn_scale;     // scale / shift the next convolution's prologue reads (the shared pair, or this op's own)
     float* gsh = u->gn_shift;
@@ -379,9 +380,9 @@ struct Fwd {
         }
         if (tr) {                 // this GroupNorm's own scale / shift / (mean, rstd): the backward pass needs them
             const int C = x->C + (skip ? skip->C : 0);
-            SISIC_TRY(u->pool.get((size_t)B * C, &gsc));
-            SISIC_TRY(u->pool.get((size_t)B * C, &gsh));
-            SISIC_TRY(u->pool.get((size_t)B * u->cfg.norm_groups * 2, &gmr));
+            SISIC_TRY(u->pool.get((size_t)B * C, &gsc, s));
+            SISIC_TRY(u->pool.get((size_t)B * C, &gsh, s));
+            SISIC_TRY(u->pool.get((size_t)B * u->cfg.norm_groups * 2, &gmr, s));
             tr->grads_of_bufs.push_back(gsc); tr->grads_of_bufs.push_back(gsh); tr->grads_of_bufs.push_back(gmr);
         }
         if (x->stats && (!skip || skip->stats)) { // every producer left partials: no pass over the tensors
@@ -663,6 +664,7 @@ int sisic_unet_create(sisic_ctx* ctx, const sisic_unet_config* cfg, sisic_unet**
     if (const char* e = std::getenv("SISIC_FUSED_GN")) u->fuse_gn = std::atoi(e) != 0;
     if (const char* e = std::getenv("SISIC_GN_RIDER")) u->gn_rider = std::atoi(e) != 0;
     if (const char* e = std::getenv("SISIC_GRAPH")) u->graph_mode = std::atoi(e) != 0 ? 1 : 0;
+    if (poison_alloc()) u->graph_mode = 0;
     u->cfg.freqs = nullptr;
     const int rc = describe(u);
     if (rc != SISIC_OK) { delete u; return rc; }

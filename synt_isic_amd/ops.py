@@ -32,6 +32,16 @@ def context(device: torch.device) -> C.c_void_p:
     return _ctx_by_device[idx]
 
 
+def empty(shape, *, dtype, device, pin_memory=False) -> torch.Tensor:
+    """The package's one allocation point for tensors it hands to the library uninitialised: ``torch.empty``.  (The GPU suite
+    replaces it, and ``empty_like``, with a poisoned, guarded allocation: tests/poison.py.)"""
+    return torch.empty(shape, dtype=dtype, device=device, pin_memory=pin_memory)
+
+
+def empty_like(t: torch.Tensor) -> torch.Tensor:
+    return torch.empty_like(t)
+
+
 def _stream(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -53,7 +63,7 @@ def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     n = lib.sisic_conv_packed_numel(cout, cin, k)
     if n < 0:
         raise ValueError(f"unsupported conv weight shape {tuple(w.shape)}")
-    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    out = empty(n, dtype=torch.float32, device=w.device)
     check(lib.sisic_conv_pack_weights(context(w.device), _ptr(w, "weight"), cout, cin, k, out.data_ptr(),
                                       _stream(w.device)))
     return out
@@ -65,7 +75,7 @@ def pack_winograd_weight(w: torch.Tensor) -> torch.Tensor:
     cout, cin, k, k2 = w.shape
     if k != 3 or k2 != 3:
         raise ValueError("Winograd F(2x2,3x3) needs a 3x3 weight")
-    out = torch.empty(lib.sisic_conv_winograd_numel(cout, cin), dtype=torch.float32, device=w.device)
+    out = empty(lib.sisic_conv_winograd_numel(cout, cin), dtype=torch.float32, device=w.device)
     check(lib.sisic_conv_winograd_pack(context(w.device), _ptr(w, "weight"), cout, cin, out.data_ptr(),
                                        _stream(w.device)))
     return out
@@ -77,7 +87,7 @@ def pack_conv_s2_weight(w: torch.Tensor) -> torch.Tensor:
     cout, cin, k, k2 = w.shape
     if k != 3 or k2 != 3:
         raise ValueError("the stride-2 bf16x3 kernel needs a 3x3 weight")
-    out = torch.empty(lib.sisic_conv_s2_numel(cout, cin), dtype=torch.float32, device=w.device)
+    out = empty(lib.sisic_conv_s2_numel(cout, cin), dtype=torch.float32, device=w.device)
     check(lib.sisic_conv_s2_pack(context(w.device), _ptr(w, "weight"), cout, cin, out.data_ptr(), _stream(w.device)))
     return out
 
@@ -98,7 +108,7 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: int, *, bi
     Ho = (Hc + 2 * pad - ksize) // stride + 1
     Wo = (Wc + 2 * pad - ksize) // stride + 1
     if out is None:
-        out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device)
+        out = empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"out must be a contiguous fp32 {(B, cout, Ho, Wo)} tensor on {x.device}")
     a = ConvArgs()
@@ -115,14 +125,14 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: int, *, bi
     if with_stats:
         slots = lib.sisic_conv_stats_slots(C.byref(a))
         if slots > 0:
-            stats = torch.empty((B, cout, slots, 4), dtype=torch.float32, device=x.device)
+            stats = empty((B, cout, slots, 4), dtype=torch.float32, device=x.device)
             a.stats_out = stats.data_ptr()
     fin = None
     if finalize is not None:
         gamma, beta, groups, eps = finalize
         a.fin_gamma = _ptr(gamma, "gamma"); a.fin_beta = _ptr(beta, "beta"); a.fin_groups = int(groups); a.fin_eps = float(eps)
         if lib.sisic_conv_finalizes(C.byref(a)):
-            fin = (torch.empty((B, cout), dtype=torch.float32, device=x.device), torch.empty((B, cout), dtype=torch.float32, device=x.device))
+            fin = (empty((B, cout), dtype=torch.float32, device=x.device), empty((B, cout), dtype=torch.float32, device=x.device))
             a.fin_scale, a.fin_shift = fin[0].data_ptr(), fin[1].data_ptr()
         else:
             a.fin_gamma = None
@@ -139,8 +149,8 @@ def groupnorm_finalize(stats: torch.Tensor, hw: int, gamma: torch.Tensor, beta: 
     lib = _lib.load()
     B, c0, slots0, _ = stats.shape
     c1, slots1 = (0, 0) if stats2 is None else (stats2.shape[1], stats2.shape[2])
-    scale = torch.empty((B, c0 + c1), dtype=torch.float32, device=stats.device)
-    shift = torch.empty_like(scale)
+    scale = empty((B, c0 + c1), dtype=torch.float32, device=stats.device)
+    shift = empty_like(scale)
     check(lib.sisic_groupnorm_finalize(context(stats.device), _ptr(stats, "stats"), c0, slots0, _ptr(stats2, "stats2"),
                                        c1, slots1, B, hw, groups, float(eps), _ptr(gamma, "gamma"), _ptr(beta, "beta"),
                                        scale.data_ptr(), shift.data_ptr(), _stream(stats.device)))
@@ -158,7 +168,7 @@ def conv2d_gn_rider(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: i
     lib = _lib.load()
     B, c0, H, W = x.shape
     c1 = 0 if x2 is None else x2.shape[1]
-    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    out = empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     a = ConvArgs()
     a.in0 = _ptr(x, "x"); a.in1 = _ptr(x2, "x2"); a.c0 = c0; a.c1 = c1
     a.B = B; a.Hin = H; a.Win = W
@@ -170,9 +180,9 @@ def conv2d_gn_rider(x: torch.Tensor, w_packed: torch.Tensor, cout: int, ksize: i
     Bs, s0, slots0, _ = stats.shape
     s1, slots1 = (0, 0) if stats2 is None else (stats2.shape[1], stats2.shape[2])
     if scale is None:
-        scale = torch.empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
+        scale = empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
     if shift is None:
-        shift = torch.empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
+        shift = empty((Bs, s0 + s1), dtype=torch.float32, device=stats.device)
     if tuple(scale.shape) != (Bs, s0 + s1) or tuple(shift.shape) != (Bs, s0 + s1):
         raise ValueError(f"scale / shift must be {(Bs, s0 + s1)} tensors")
     carried = C.c_int(0)
@@ -188,8 +198,8 @@ def groupnorm_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gr
     B, c0 = x.shape[0], x.shape[1]
     c1 = 0 if x2 is None else x2.shape[1]
     HW = x[0, 0].numel()
-    scale = torch.empty((B, c0 + c1), dtype=torch.float32, device=x.device)
-    shift = torch.empty_like(scale)
+    scale = empty((B, c0 + c1), dtype=torch.float32, device=x.device)
+    shift = empty_like(scale)
     check(lib.sisic_groupnorm_stats(context(x.device), _ptr(x, "x"), c0, _ptr(x2, "x2"), c1, B, HW, groups,
                                     float(eps), _ptr(gamma, "gamma"), _ptr(beta, "beta"), scale.data_ptr(),
                                     shift.data_ptr(), _stream(x.device)))
@@ -201,7 +211,7 @@ def attention(qkv: torch.Tensor, head_dim: int = 8) -> torch.Tensor:
     lib = _lib.load()
     B, C3, N = qkv.shape
     Cc = C3 // 3
-    out = torch.empty((B, Cc, N), dtype=torch.float32, device=qkv.device)
+    out = empty((B, Cc, N), dtype=torch.float32, device=qkv.device)
     check(lib.sisic_attention(context(qkv.device), _ptr(qkv, "qkv"), out.data_ptr(), B, Cc, N, head_dim,
                               _stream(qkv.device)))
     return out
@@ -212,7 +222,7 @@ def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
     """coef = (sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma)."""
     lib = _lib.load()
     if out is None:
-        out = torch.empty_like(x)
+        out = empty_like(x)
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
     check(lib.sisic_ddpm_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
@@ -233,7 +243,7 @@ def noise_fill(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") 
     lib = _lib.load()
     device = torch.device(device)
     arr = _seed_array(seeds)
-    out = torch.empty((len(arr), int(n_per_image)), dtype=torch.float32, device=device)
+    out = empty((len(arr), int(n_per_image)), dtype=torch.float32, device=device)
     check(lib.sisic_noise_fill(context(device), out.data_ptr(), len(arr), int(n_per_image), arr, int(step), int(tag),
                                _stream(device)))
     return out
@@ -246,7 +256,7 @@ def noise_bits(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") 
     device = torch.device(device)
     arr = _seed_array(seeds)
     words = 4 * ((int(n_per_image) + 3) // 4)
-    out = torch.empty((len(arr), words), dtype=torch.int32, device=device)
+    out = empty((len(arr), words), dtype=torch.int32, device=device)
     check(lib.sisic_noise_bits(context(device), out.data_ptr(), len(arr), int(n_per_image), arr, int(step), int(tag),
                                _stream(device)))
     return out
@@ -262,7 +272,7 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
     if x.numel() % B:
         raise ValueError(f"{x.numel()} elements are not {B} equal images")
     if out is None:
-        out = torch.empty_like(x)
+        out = empty_like(x)
     seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
     check(lib.sisic_ddpm_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
@@ -276,7 +286,7 @@ def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
     ``HipDDIMScheduler.coefficient_table``.  z None or sigma == 0: no noise is added."""
     lib = _lib.load()
     if out is None:
-        out = torch.empty_like(x)
+        out = empty_like(x)
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
     check(lib.sisic_ddim_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c_prev, c_dir, sigma, float(clip), int(bool(use_clipped_model_output)),
@@ -294,7 +304,7 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
     if x.numel() % B:
         raise ValueError(f"{x.numel()} elements are not {B} equal images")
     if out is None:
-        out = torch.empty_like(x)
+        out = empty_like(x)
     seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
     check(lib.sisic_ddim_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
@@ -311,7 +321,7 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stri
     B, c0, H, W = x.shape
     c1 = 0 if x2 is None else x2.shape[1]
     cout = dy.shape[1]
-    dw = torch.empty((cout, c0 + c1, ksize, ksize), dtype=torch.float32, device=x.device)
+    dw = empty((cout, c0 + c1, ksize, ksize), dtype=torch.float32, device=x.device)
     a = ConvArgs()
     a.in0 = _ptr(x, "x"); a.in1 = _ptr(x2, "x2"); a.c0 = c0; a.c1 = c1
     a.B = B; a.Hin = H; a.Win = W
@@ -325,7 +335,7 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, hea
     """gradient of ``attention`` w.r.t. qkv [B,3C,N]."""
     lib = _lib.load()
     B, C3, N = qkv.shape
-    dqkv = torch.empty_like(qkv)
+    dqkv = empty_like(qkv)
     check(lib.sisic_attention_bwd(context(qkv.device), _ptr(qkv, "qkv"), _ptr(out, "out"), _ptr(d_out, "d_out"),
                                   dqkv.data_ptr(), B, C3 // 3, N, head_dim, _stream(qkv.device)))
     return dqkv
@@ -338,8 +348,8 @@ def groupnorm_bwd(da: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: 
     B, Cc = x.shape[0], x.shape[1]
     HW = x[0, 0].numel()
     dx = torch.zeros_like(x)
-    dg = torch.empty(Cc, dtype=torch.float32, device=x.device)
-    db = torch.empty_like(dg)
+    dg = empty(Cc, dtype=torch.float32, device=x.device)
+    db = empty_like(dg)
     check(lib.sisic_groupnorm_bwd(context(x.device), _ptr(da, "da"), _ptr(x, "x"), B, Cc, HW, groups, float(eps),
                                   _ptr(gamma, "gamma"), _ptr(beta, "beta"), int(silu), dx.data_ptr(), dg.data_ptr(),
                                   db.data_ptr(), _stream(x.device)))
@@ -355,7 +365,7 @@ def denorm_u8(x: torch.Tensor, form="image_generator") -> torch.Tensor:
     "diffusion_generator" (diffusion_generator.py:231-232, `(x+1)*127.5` -- rounds differently)."""
     lib = _lib.load()
     B, Cc, H, W = x.shape
-    out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=x.device)
+    out = empty((B, H, W, Cc), dtype=torch.uint8, device=x.device)
     f = DENORM_FORMS[form] if isinstance(form, str) else int(form)
     check(lib.sisic_denorm_u8_form(context(x.device), _ptr(x, "x"), out.data_ptr(), B, Cc, H, W, f, _stream(x.device)))
     return out
@@ -397,9 +407,9 @@ def intervene(frames: torch.Tensor, masks: torch.Tensor, jobs, seeds, src_index:
     if src_index is not None and (not src_index.is_cuda or src_index.dtype != torch.int32 or not src_index.is_contiguous()
                                   or tuple(src_index.shape) != (J, Cc, H * W) or src_index.device != frames.device):
         raise ValueError(f"src_index must be a contiguous int32 {(J, Cc, H * W)} tensor on {frames.device}")
-    out = torch.empty((J, Cc, H, W), dtype=torch.float32, device=frames.device)
-    iv = torch.empty_like(out) if with_intervention else None
-    stats = torch.empty((J, 4), dtype=torch.float32, device=frames.device)
+    out = empty((J, Cc, H, W), dtype=torch.float32, device=frames.device)
+    iv = empty_like(out) if with_intervention else None
+    stats = empty((J, 4), dtype=torch.float32, device=frames.device)
     check(lib.sisic_intervene(context(frames.device), _ptr(frames, "frames"), F_, masks.data_ptr(), masks.shape[0], Cc, H, W, J,
                               table, arr, None if src_index is None else src_index.data_ptr(), out.data_ptr(),
                               None if iv is None else iv.data_ptr(), stats.data_ptr(), _stream(frames.device)))
@@ -416,7 +426,7 @@ def cfi_metrics(logits_orig: torch.Tensor, logits_mod: torch.Tensor, job_frame) 
     frames = [int(f) for f in job_frame]
     if len(frames) != J:
         raise ValueError(f"{len(frames)} frame indices for {J} rows of logits")
-    rows = torch.empty((J, CFI_PER_CLASS * n + CFI_TAIL), dtype=torch.float32, device=logits_mod.device)
+    rows = empty((J, CFI_PER_CLASS * n + CFI_TAIL), dtype=torch.float32, device=logits_mod.device)
     check(lib.sisic_cfi_metrics(context(logits_mod.device), _ptr(logits_orig, "logits_orig"), logits_orig.shape[0],
                                 _ptr(logits_mod, "logits_mod"), J, n, (C.c_int * J)(*frames), rows.data_ptr(),
                                 _stream(logits_mod.device)))
@@ -438,8 +448,8 @@ def resample_diffs(top, bottom, seed: int, n_bootstrap: int, n_permutations: int
     if seed < 0 or seed >> 64:
         raise ValueError("seed must be an integer in 0 .. 2**64-1")
     n_bootstrap, n_permutations = int(n_bootstrap), int(n_permutations)
-    boot = torch.empty(n_bootstrap, dtype=torch.float64, device=device) if n_bootstrap > 0 else None
-    perm = torch.empty(n_permutations, dtype=torch.float64, device=device) if n_permutations > 0 else None
+    boot = empty(n_bootstrap, dtype=torch.float64, device=device) if n_bootstrap > 0 else None
+    perm = empty(n_permutations, dtype=torch.float64, device=device) if n_permutations > 0 else None
     dp = C.POINTER(C.c_double)
     check(lib.sisic_resample_diffs(context(device), top.ctypes.data_as(dp), top.size, bottom.ctypes.data_as(dp), bottom.size,
                                    seed, n_bootstrap, n_permutations, None if boot is None else boot.data_ptr(),
@@ -497,12 +507,12 @@ def augment(dataset: torch.Tensor, params: np.ndarray, *, u8: bool = False) -> t
     staged = torch.empty(B * AUGMENT_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
     staged.numpy()[:] = params.view(np.uint8)
     params_dev = staged.to(dev, non_blocking=True)
-    scratch = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = empty(B, dtype=torch.int32, device=dev)
     if u8:
-        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        out = empty((B, H, W, 3), dtype=torch.uint8, device=dev)
         fn = lib.sisic_augment_u8
     else:
-        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        out = empty((B, 3, H, W), dtype=torch.float32, device=dev)
         fn = lib.sisic_augment
     check(fn(context(dev), dataset.data_ptr(), N, H, W, params_dev.data_ptr(), B, scratch.data_ptr(), out.data_ptr(),
              _stream(dev)))

@@ -34,7 +34,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check
 from .scheduler import HipDDIMScheduler, HipDDPMScheduler
 from .unet import HipUNet2DModel
@@ -180,7 +180,7 @@ class NoiseStream:
             self.host, self.dev = buffer_cache["buffers"]
         else:
             self.host = [torch.empty(shape, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-            self.dev = [torch.empty(shape, dtype=torch.float32, device=device) for _ in range(2)]
+            self.dev = [ops.empty(shape, dtype=torch.float32, device=device) for _ in range(2)]
             if buffer_cache is not None:                # one shape at a time: bounded memory
                 buffer_cache["shape"], buffer_cache["buffers"] = key, (self.host, self.dev)
         if buffer_cache is not None and buffer_cache.get("copy_stream_device") == str(device):
@@ -338,8 +338,8 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
         noise = noise.contiguous()
     x = x_T.to(torch.float32).contiguous().clone()
     kept, rows = _frame_rows(T, return_trajectory, save_indices)
-    traj = torch.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
-    out_u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
+    traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
+    out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
     done = C.c_int(0)
     clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
     head = (model.handle, x.data_ptr(), B, H, W, T, C.cast(ts.data_ptr(), _lib.c_int64_p),
@@ -397,8 +397,8 @@ def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: Noise
     kept, rows = _frame_rows(T, return_trajectory, save_indices)
     if return_trajectory and rows is None:
         rows = np.arange(T, dtype=np.int32)                     # a segment's steps go to their rows of the whole run
-    traj = torch.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
-    out_u8 = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
+    traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
+    out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
     clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     done_total, rc = 0, 0

@@ -169,7 +169,7 @@ class HipDDPMScheduler:
         if a.numel() != B:
             raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
         a, c = a.to(x0.device), c.to(x0.device)
-        out = torch.empty_like(x0)
+        out = ops.empty_like(x0)
         check(_lib.load().sisic_add_noise(ops.context(x0.device), x0.data_ptr(), nz.data_ptr(), a.data_ptr(), c.data_ptr(),
                                           out.data_ptr(), B, x0[0].numel(),
                                           C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))

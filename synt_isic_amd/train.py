@@ -30,7 +30,7 @@ from typing import Callable, Iterable, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check
 from .scheduler import HipDDPMScheduler
 from .unet import HipUNet2DModel
@@ -48,7 +48,7 @@ class HipLoss:
 
     def __init__(self, model: HipUNet2DModel, pred: torch.Tensor, target: torch.Tensor, scale: float = 1.0):
         self.model, self.pred, self.target, self.scale = model, pred, target, float(scale)
-        self._loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        self._loss = ops.empty(1, dtype=torch.float32, device=pred.device)
         check(_lib.load().sisic_mse_loss(model.handle, pred.data_ptr(), target.data_ptr(), pred.numel(), 1.0,
                                          self._loss.data_ptr(), None, _stream(pred.device)))
 
@@ -63,7 +63,7 @@ class HipLoss:
 
     def backward(self) -> None:
         """d(scale * loss)/d(parameters) into the model's gradient arena (the tape of the last forward is consumed)."""
-        dpred = torch.empty_like(self.pred)
+        dpred = ops.empty_like(self.pred)
         lib = _lib.load()
         check(lib.sisic_mse_loss(self.model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(),
                                  self.scale, None, dpred.data_ptr(), _stream(self.pred.device)))

@@ -324,7 +324,7 @@ class HipUNet2DModel:
         x = sample.to(torch.float32).contiguous()
         B, _, H, W = x.shape
         t = self._timesteps_host(timestep, B)
-        out = torch.empty((B, self.config.out_channels, H, W), dtype=torch.float32, device=x.device)
+        out = ops.empty((B, self.config.out_channels, H, W), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         if self.training and self._train_begun:
             # training mode with an optimizer: the same kernels, every activation kept for loss.backward()

@@ -167,10 +167,10 @@ def compute_shap_approximation(classifier: HipMelanomaClassifier, image: torch.T
     lib = _lib.load()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     baseline = classifier.get_per_class_score(torch.zeros_like(image), target_class)       # [1]
-    scores = torch.empty(n_samples, dtype=torch.float32, device=dev)
+    scores = ops.empty(n_samples, dtype=torch.float32, device=dev)
     for s0 in range(0, n_samples, chunk):
         s1 = min(n_samples, s0 + chunk)
-        batch = torch.empty((s1 - s0, Cc, H, W), dtype=torch.float32, device=dev)
+        batch = ops.empty((s1 - s0, Cc, H, W), dtype=torch.float32, device=dev)
         check(lib.sisic_mask_patches(ops.context(dev), image.data_ptr(), masks_u8[s0:s1].data_ptr(), batch.data_ptr(),
                                      s1 - s0, Cc, H, W, patch_size, stream))
         scores[s0:s1] = classifier.get_per_class_score(batch, target_class)

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from poison import guard_bands, poison_allocations  # noqa: F401  (autouse: poisoned, guarded allocations -- tests/poison.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"

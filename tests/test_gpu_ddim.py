@@ -8,6 +8,8 @@ import torch
 import ddim_ref
 from test_gpu_device_noise import eager, graph  # noqa: F401  (the two graph-mode fixtures, shared)
 
+from poison import guard_bands, poison_allocations  # noqa: F401  (autouse: poisoned, guarded allocations -- tests/poison.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"

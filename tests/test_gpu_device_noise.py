@@ -10,6 +10,8 @@ import torch
 
 import philox_ref
 
+from poison import guard_bands, poison_allocations  # noqa: F401  (autouse: poisoned, guarded allocations -- tests/poison.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"

@@ -8,6 +8,8 @@ import itertools
 import pytest
 import torch
 
+from poison import guard_bands, poison_allocations  # noqa: F401  (autouse: poisoned, guarded allocations -- tests/poison.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"

@@ -21,6 +21,8 @@ import numpy as np
 import pytest
 import torch
 
+from poison import guard_bands, poison_allocations  # noqa: F401  (autouse: poisoned, guarded allocations -- tests/poison.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
