@@ -4,7 +4,8 @@ images to rank 0 (the reference loops over images one at a
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \\
         examples/generate_sharded.py --count 512 --T 1000 --size 64 --class-name NV [--weights unet_NV_best.pth] \\
-        [--out images.npy] [--noise host|device] [--scheduler ddpm|ddim] [--eta 0.0]
+        [--out images.npy] [--noise host|device] [--scheduler ddpm|ddim|dpmsolver++] [--eta 0.0] \\
+        [--solver-order 2] [--algorithm-type dpmsolver++|sde-dpmsolver++]
 
 Every image's chain depends only on its own seed, so the gathered result is bit-identical to sampling the same
 seeds on one GPU (tests/test_gpu_sampler.py::test_batch_and_shard_independence_small).
@@ -39,9 +40,13 @@ def main():
     ap.add_argument("--noise", choices=("host", "device"), default="host",
                     help="host: one CPU torch.Generator per image (the default); device: x_T from torch's device generator "
                          "and z_t generated in the step kernel -- no host RNG, so the ranks do not compete for CPUs")
-    ap.add_argument("--scheduler", choices=("ddpm", "ddim"), default="ddpm",
-                    help="the step rule: DDPM ancestral sampling (the default), or DDIM -- the rule made for --T of 20 to 100")
+    ap.add_argument("--scheduler", choices=("ddpm", "ddim", "dpmsolver++"), default="ddpm",
+                    help="the step rule: DDPM ancestral sampling (the default), DDIM -- the rule made for --T of 20 to 100 -- or "
+                         "DPM-Solver++(2M), the second-order rule for --T of 10 to 25")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM only: 0 is deterministic, 1 has the DDPM rule's sigma")
+    ap.add_argument("--solver-order", type=int, choices=(1, 2), default=2, help="dpmsolver++ only: 1 is the DDIM rule")
+    ap.add_argument("--algorithm-type", choices=("dpmsolver++", "sde-dpmsolver++"), default="dpmsolver++",
+                    help="dpmsolver++ only: the ODE solver (draws nothing beyond x_T) or its stochastic variant")
     a = ap.parse_args()
 
     rank, world, local = sdist.init_from_env()
@@ -57,7 +62,8 @@ def main():
     blocks = []
     for i in range(0, len(mine), a.batch):
         blocks.append(s.generate_seeds(a.class_name, mine[i:i + a.batch], a.T, (a.size, a.size), noise=a.noise,
-                                       scheduler=a.scheduler, eta=a.eta).images)
+                                       scheduler=a.scheduler, eta=a.eta, solver_order=a.solver_order,
+                                       algorithm_type=a.algorithm_type).images)
     local_images = torch.cat(blocks) if blocks else torch.empty((0, a.size, a.size, 3), dtype=torch.uint8, device=dev)
     images = sdist.gather_images(local_images, a.count, dst=0)
     torch.cuda.synchronize(dev)
@@ -65,6 +71,8 @@ def main():
     if rank == 0:
         arr = images.cpu().numpy()
         rule = f", ddim eta={a.eta:g}" if a.scheduler == "ddim" else ""
+        if a.scheduler == "dpmsolver++":
+            rule = f", {a.algorithm_type} order {a.solver_order}"
         print(f"{a.count} images {a.size}x{a.size}, T={a.T}, {world} GPU(s), {a.noise} noise{rule}: {dt:.2f} s -> {a.count / dt:.3f} images/sec; "
               f"sha256 {hashlib.sha256(arr.tobytes()).hexdigest()[:16]}", flush=True)
         if a.out:

@@ -192,12 +192,16 @@ int sisic_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z
                     int64_t n, float sqrt_beta_prod, float sqrt_alpha_prod, float c0, float c1,
                     float sigma, float clip, void* stream);
 
-/* The scheduler-step rules of the sampling loop and what the five floats of a step's table row mean under each:
- *   SISIC_RULE_DDPM  {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma}          sisic_ddpm_step above (ancestral sampling)
- *   SISIC_RULE_DDIM  {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma}   sisic_ddim_step below
- * rule_flags: SISIC_RULE_FLAG_CLIPPED_OUTPUT (DDIM only: use_clipped_model_output); 0 under DDPM.                       */
+/* The scheduler-step rules of the sampling loop and what the floats of a step's table row mean under each:
+ *   SISIC_RULE_DDPM   {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma}          sisic_ddpm_step above (ancestral sampling)
+ *   SISIC_RULE_DDIM   {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma}   sisic_ddim_step below
+ *   SISIC_RULE_DPMPP  {sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1}      sisic_dpmpp_step below (DPM-Solver++(2M))
+ * A row is SISIC_RULE_ROW_WIDTH(rule) floats: 5, 5, 6.  sigma is column 4 under every rule.
+ * rule_flags: SISIC_RULE_FLAG_CLIPPED_OUTPUT (DDIM only: use_clipped_model_output); 0 under DDPM and DPM-Solver++.        */
 #define SISIC_RULE_DDPM 0
 #define SISIC_RULE_DDIM 1
+#define SISIC_RULE_DPMPP 2
+#define SISIC_RULE_ROW_WIDTH(rule) ((rule) == SISIC_RULE_DPMPP ? 6 : 5)
 #define SISIC_RULE_FLAG_CLIPPED_OUTPUT 1
 
 /* Fused DDIMScheduler.step (the published rule for epsilon prediction), elementwise over n floats.
@@ -214,6 +218,24 @@ int sisic_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z
 int sisic_ddim_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* out,
                     int64_t n, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev, float c_dir,
                     float sigma, float clip, int use_clipped_model_output, void* stream);
+
+/* Fused DPM-Solver++(2M) step (Lu et al. 2022, the second-order multistep data-prediction solver with the midpoint rule, for
+ * epsilon prediction), elementwise over n floats.  With alpha = abar^0.5, sigma_ = (1 - abar)^0.5,
+ * lambda = ln alpha - ln sigma_ at this step's t, the next step's t' (abar = 1 after the last step) and the previous step's
+ * t", h = lambda' - lambda and r = (lambda - lambda")/h, the host folds the published update into
+ *   ODE ("dpmsolver++"):      cx = sigma_'/sigma_,            A = -alpha' * expm1(-h),   sigma = 0
+ *   SDE ("sde-dpmsolver++"):  cx = (sigma_'/sigma_) * exp(-h), A = -alpha' * expm1(-2h),  sigma = sigma_' * (-expm1(-2h))^0.5
+ *   first order:  k0 = A, k1 = 0          second order:  k0 = A * (1 + 1/(2r)), k1 = -A/(2r)
+ * in float64, rounded to fp32 once.  The row is {sqrt_beta_prod = sigma_, sqrt_alpha_prod = alpha, cx, k0, sigma, k1}, the step
+ *   x0   = clamp((x - sqrt_beta_prod*eps)/sqrt_alpha_prod, -clip, clip)  (clip<=0: no clamp)
+ *   out  = ((cx*x + k0*x0) + k1*hist) + sigma*z                          (k1==0: hist is not read; z==NULL or sigma==0: no noise)
+ *   hist = x0
+ * evaluated in exactly that fp32 operation order (no FMA contraction).  hist: dev float [n], the previous step's x0, written
+ * on every step and read only when k1 != 0: the first step of a run (k1 == 0) may be handed uninitialised memory.  out may be
+ * x; hist is a buffer of its own.  sqrt_alpha_prod != 0.                                                                  */
+int sisic_dpmpp_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* hist, float* out,
+                     int64_t n, float sqrt_beta_prod, float sqrt_alpha_prod, float cx, float k0, float sigma, float k1,
+                     float clip, void* stream);
 
 /* De-normalise image_generator.py:441-447: [B,3,H,W] fp32 -> uint8 [B,H,W,3],
  * trunc(clamp((x+1)/2,0,1)*255).                                                   */
@@ -324,14 +346,22 @@ int sisic_sample_frames_rng(sisic_unet*, float* x, int B, int H, int W, int T, c
 int sisic_ddim_step_rng(sisic_ctx*, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
                         float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream);
+/* sisic_dpmpp_step with z generated in the kernel: sisic_ddpm_step_rng's arguments and alignment rules, the DPM-Solver++
+ * row and its history buffer.                                                                                            */
+int sisic_dpmpp_step_rng(sisic_ctx*, const float* eps, const float* x, float* hist, float* out, int B, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float cx,
+                         float k0, float sigma, float k1, float clip, void* stream);
 /* sisic_sample_frames and sisic_sample_frames_rng under a chosen step rule:
  *   for i in 0..T-1:  eps = unet(x, t[i]);  x = step_rule(eps, x, z[i], coef[i])
- * rule: SISIC_RULE_DDPM (what the entries above run) or SISIC_RULE_DDIM; rule_flags: SISIC_RULE_FLAG_* of that rule.
- * coef: host float [T*5], the rows of that rule (see SISIC_RULE_* above).  Under either rule the steps with sigma != 0, and
+ * rule: SISIC_RULE_DDPM (what the entries above run), SISIC_RULE_DDIM or SISIC_RULE_DPMPP; rule_flags: SISIC_RULE_FLAG_* of
+ * that rule.  coef: host float, T rows of the rule's width (SISIC_RULE_ROW_WIDTH; see SISIC_RULE_* above).  Under every rule the steps with sigma != 0, and
  * only those, consume a noise row (buffer) or draw (generated noise): a DDIM run at eta = 0 has none, and takes noise NULL
  * or a buffer of no rows.  In graph mode the rule and its flags are part of what a captured step is, like the noise source:
  * a DDPM step is never replayed for a DDIM call or the other way round, and alternating re-captures
- * (sisic_unet_graph_builds).  Everything else as documented at sisic_sample_frames / sisic_sample_frames_rng.            */
+ * (sisic_unet_graph_builds).  Everything else as documented at sisic_sample_frames / sisic_sample_frames_rng.
+ * SISIC_RULE_DPMPP: the handle owns the history buffer of the run.  A call starts with no history, so row 0 of a call must
+ * be a first-order row (k1 == 0; SISIC_EINVAL otherwise), and a run cut into two calls is NOT bit-equal to the uncut run:
+ * the second call's first step has to be first order where the uncut run's is second order.  Run it in one call.         */
 int sisic_sample_frames_rule(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps,
                              const float* coef, float clip, int rule, int rule_flags, const float* noise, float* traj,
                              const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,

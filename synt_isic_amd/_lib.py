@@ -25,7 +25,9 @@ SISIC_ECANCEL = -4
 # step rules of the sampling loop (SISIC_RULE_*) and the DDIM rule's flag
 RULE_DDPM = 0
 RULE_DDIM = 1
+RULE_DPMPP = 2
 RULE_FLAG_CLIPPED_OUTPUT = 1
+RULE_ROW_WIDTH = {RULE_DDPM: 5, RULE_DDIM: 5, RULE_DPMPP: 6}      # SISIC_RULE_ROW_WIDTH
 
 c_float_p = C.POINTER(C.c_float)
 c_int64_p = C.POINTER(C.c_int64)
@@ -136,6 +138,11 @@ SIGNATURES = {
     "sisic_ddim_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_int, C.c_void_p]),
+    "sisic_dpmpp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "sisic_dpmpp_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                       C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_float, C.c_float, C.c_void_p]),
     "sisic_sample_frames_rule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                            C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                            C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),

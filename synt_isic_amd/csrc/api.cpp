@@ -230,6 +230,22 @@ int sisic_ddim_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float*
                            c_dir, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
+int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
+                     float sqrt_beta_prod, float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip,
+                     void* stream) {
+    SISIC_REQUIRE(ctx, "dpmpp_step: null context");
+    return launch_dpm_step(ctx, eps, x, z, hist, out, n, sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1, clip,
+                           static_cast<hipStream_t>(stream));
+}
+
+int sisic_dpmpp_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int B,
+                         int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod,
+                         float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip, void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "dpmpp_step_rng: null context or empty batch");
+    return launch_dpm_step_rng(ctx, eps, x, hist, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod,
+                               sqrt_alpha_prod, cx, k0, sigma, k1, clip, static_cast<hipStream_t>(stream));
+}
+
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {
     SISIC_REQUIRE(ctx, "denorm_u8: null context");
     return launch_denorm_u8(ctx, x, out, B, C, H, W, static_cast<hipStream_t>(stream));

@@ -197,7 +197,7 @@ int launch_gn_stats(sisic_ctx*, const float* in0, int c0, const float* in1, int 
 int launch_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s);
 // The scheduler-step rules of the sampling loop (elementwise.hip; sisic.h SISIC_RULE_*): the row of a step is
 // {sb, sa, c2, c3, sigma} with (c2, c3) = DDPM (c0, c1) or DDIM (c_prev, c_dir).  flags: STEP_FLAG_CLIPPED_OUTPUT (DDIM only).
-enum StepRule { STEP_RULE_DDPM = SISIC_RULE_DDPM, STEP_RULE_DDIM = SISIC_RULE_DDIM };
+enum StepRule { STEP_RULE_DDPM = SISIC_RULE_DDPM, STEP_RULE_DDIM = SISIC_RULE_DDIM, STEP_RULE_DPMPP = SISIC_RULE_DPMPP };
 enum StepFlag { STEP_FLAG_CLIPPED_OUTPUT = SISIC_RULE_FLAG_CLIPPED_OUTPUT };
 // a known rule, flags it has, sa != 0, and sb != 0 where the rule divides by it
 int check_step_row(int rule, int flags, float sb, float sa);
@@ -216,6 +216,17 @@ int launch_step_rng(sisic_ctx*, int rule, int flags, const float* eps, const flo
                     float sigma, float clip, hipStream_t s);
 int launch_step_indexed_rng(sisic_ctx*, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
                             const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
+// the DPM-Solver++(2M) rule (STEP_RULE_DPMPP): rows of six floats {sb, sa, cx, k0, sigma, k1} and one more stream, the
+// history hist [n] (the previous step's x0: written on every step, read when k1 != 0).  The launchers above refuse this rule.
+int launch_dpm_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
+                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s);
+int launch_dpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* hist, float* out, int64_t n,
+                        int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
+                        float sigma, float k1, float clip, hipStream_t s);
+int launch_dpm_step_indexed(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, const void* state,
+                            const float* coef, const int* zrow, float clip, hipStream_t s);
+int launch_dpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
+                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
 int launch_noise_fill(sisic_ctx*, void* out, int B, int64_t n_per_image, const uint64_t* seeds_host, uint32_t step,
                       uint32_t tag, bool bits, hipStream_t s);
 int launch_denorm_u8(sisic_ctx*, const float* x, uint8_t* out, int B, int C, int H, int W, hipStream_t s, int form = 0);

@@ -1,6 +1,7 @@
 // elementwise.hip -- the HBM-bound and tiny kernels of the sampling loop:
 //   * ddpm_step_kernel  : fused DDPMScheduler.step, bit-exact vs torch CPU
 //   * ddim_step_kernel  : fused DDIMScheduler.step (epsilon prediction), bit-exact vs torch CPU
+//   * dpm_step_kernel   : fused DPM-Solver++(2M) step with its one-step history, bit-exact vs torch CPU
 //   * denorm_u8_kernel  : clamp((x+1)/2,0,1)*255 -> uint8 HWC (image_generator.py:441-447)
 //   * temb_mlp_kernel   : sinusoidal timestep embedding -> Linear -> SiLU -> Linear -> SiLU
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
@@ -147,13 +148,90 @@ ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, 
     step_body(eps, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
 }
 
-static const char* rule_name(int rule) { return rule == STEP_RULE_DDIM ? "ddim_step" : "ddpm_step"; }
+// ---- DPM-Solver++(2M) step -------------------------------------------------------------
+// The second-order multistep rule of Lu et al. 2022 for epsilon prediction, with its coefficients folded on the host: the row
+// of a step is {sb = sigma_t, sa = alpha_t, cx, k0, sigma, k1} (sisic.h SISIC_RULE_DPMPP) and the step
+//   x0 = clamp((x - sb*e)/sa);  out = cx*x + k0*x0 [+ k1*hist] [+ sigma*z];  hist = x0
+// under the rounding rules of ddpm_one.  hist is the previous step's x0: one more stream, read (second-order steps only) and
+// written in place by the thread that owns the element, so a captured step replays as it is.  A first-order step (k1 == 0,
+// uniform over the launch) does not read it: whatever an earlier run left there, NaN included, stays out of the result.
+struct DpmRule {
+    float sb, sa, cx, k0, sigma, k1, clip;
+    // h: the history's element (any value when !second); m0: this step's x0, the next step's history
+    __device__ __forceinline__ float operator()(float e, float x, float z, float h, bool noise, bool second, float& m0) const {
+#pragma clang fp contract(off)
+        float x0 = (x - sb * e) / sa;
+        if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+        float r = cx * x + k0 * x0;
+        if (second) r = r + k1 * h;
+        if (noise) r = r + sigma * z;
+        m0 = x0;
+        return r;
+    }
+};
+
+// step_body with the history stream.  out may alias x; hist aliases nothing else.
+template <class Z>
+__device__ __forceinline__ void dpm_step_body(const float* __restrict__ eps, const float* x, float* hist, float* out, int64_t n,
+                                              bool vec4, const DpmRule rule, const Z zs) {
+    const bool noise = zs.present() && (rule.sigma != 0.0f);
+    const bool second = rule.k1 != 0.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t tail = t0;
+    if (vec4) {
+        const int64_t n4 = n >> 2;
+        const float4* e4 = reinterpret_cast<const float4*>(eps);
+        const float4* x4 = reinterpret_cast<const float4*>(x);
+        float4* h4 = reinterpret_cast<float4*>(hist);
+        float4* o4 = reinterpret_cast<float4*>(out);
+        for (int64_t i = t0; i < n4; i += stride) {
+            const float4 e = e4[i], xv = x4[i];
+            float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), zv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (second) hv = h4[i];
+            if (noise) zv = zs.get4(i);
+            float4 r, m;
+            r.x = rule(e.x, xv.x, zv.x, hv.x, noise, second, m.x);
+            r.y = rule(e.y, xv.y, zv.y, hv.y, noise, second, m.y);
+            r.z = rule(e.z, xv.z, zv.z, hv.z, noise, second, m.z);
+            r.w = rule(e.w, xv.w, zv.w, hv.w, noise, second, m.w);
+            h4[i] = m;
+            o4[i] = r;
+        }
+        tail = (n4 << 2) + t0;
+    }
+    for (int64_t i = tail; i < n; i += stride) {
+        float m;
+        const float r = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
+        hist[i] = m;
+        out[i] = r;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* hist, float* out, int64_t n,
+                float sb, float sa, float cx, float k0, float sigma, float k1, float clip, int vec4) {
+    dpm_step_body(eps, x, hist, out, n, vec4 != 0, DpmRule{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* hist, float* out, int64_t n, int64_t n_per_image,
+                    const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float cx, float k0, float sigma,
+                    float k1, float clip, int vec4) {
+    const PhiloxNoise zs{seeds, n_per_image, step};
+    dpm_step_body(eps, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule{sb, sa, cx, k0, sigma, k1, clip}, zs);
+}
+
+static const char* rule_name(int rule) {
+    return rule == STEP_RULE_DPMPP ? "dpmpp_step" : rule == STEP_RULE_DDIM ? "ddim_step" : "ddpm_step";
+}
 
 // the rule and its flags as the C ABI passes them; the divisors of the rule's row when they are launch arguments
 static int check_rule(int rule, int flags) {
-    SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM, "step rule %d (0 = DDPM, 1 = DDIM)", rule);
+    SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM || rule == STEP_RULE_DPMPP,
+                  "step rule %d (0 = DDPM, 1 = DDIM, 2 = DPM-Solver++)", rule);
     SISIC_REQUIRE((flags & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || flags == 0),
-                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM: none)", rule_name(rule), flags);
+                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM, DPM-Solver++: none)", rule_name(rule), flags);
     return SISIC_OK;
 }
 
@@ -168,6 +246,7 @@ int check_step_row(int rule, int flags, float sb, float sa) {
 int launch_step(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
                 float sb, float sa, float c2, float c3, float sigma, float clip, hipStream_t s) {
     SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
     SISIC_REQUIRE(eps && x && out && n > 0, "%s: null tensor or empty", rule_name(rule));
     SISIC_TRY(check_step_row(rule, flags, sb, sa));
     const bool noise = z != nullptr && sigma != 0.0f;
@@ -197,6 +276,7 @@ int launch_step_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, const
                     int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c2, float c3,
                     float sigma, float clip, hipStream_t s) {
     SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
     SISIC_REQUIRE(eps && x && out && seeds_dev && n > 0, "%s_rng: null tensor or empty", rule_name(rule));
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
                   "%s_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
@@ -215,6 +295,45 @@ int launch_step_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, const
     else
         hipLaunchKernelGGL(ddim_step_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev,
                            step, sb, sa, c2, c3, sigma, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// the DPM-Solver++ step: launch_step / launch_step_rng with the history stream and the sixth scalar of its row
+int launch_dpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
+                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && hist && out && n > 0, "dpmpp_step: null tensor or empty");
+    SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step: the history aliases another tensor");
+    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, 0, sb, sa));
+    const bool noise = z != nullptr && sigma != 0.0f;
+    ProfileScope prof(ctx, s, PK_DDPM, ((noise ? 20.0 : 16.0) + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) |
+                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0;
+    const int64_t work = vec4 ? (n + 3) / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(dpm_step_kernel, dim3(blocks), dim3(256), 0, s, eps, x, z, hist, out, n, sb, sa, cx, k0, sigma, k1, clip,
+                       vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+int launch_dpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int64_t n,
+                        int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
+                        float sigma, float k1, float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && hist && out && seeds_dev && n > 0, "dpmpp_step_rng: null tensor or empty");
+    SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step_rng: the history aliases another tensor");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "dpmpp_step_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
+    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, 0, sb, sa));
+    ProfileScope prof(ctx, s, PK_DDPM, (16.0 + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist) |
+                         reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(dpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, out, n, n_per_image, seeds_dev, step, sb,
+                       sa, cx, k0, sigma, k1, clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -285,6 +404,30 @@ ddim_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n,
     step_indexed_rng_body<DdimRule<CLIPPED>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
 }
 
+// the DPM-Solver++ rule: rows of six floats, and the history buffer of the loop
+__device__ __forceinline__ DpmRule loop_dpm_rule(const float* __restrict__ coef, int step, float clip) {
+    const float* c = coef + 6 * step;
+    return DpmRule{c[0], c[1], c[2], c[3], c[4], c[5], clip};
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_indexed_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, const LoopState* __restrict__ st,
+                        const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
+    const int step = st->step;
+    const int zr = zrow[step];
+    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
+    dpm_step_body(eps, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, int64_t n_per_image,
+                            const LoopState* __restrict__ st, const float* __restrict__ coef,
+                            const uint64_t* __restrict__ seeds, float clip, int vec4) {
+    const int step = st->step;
+    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+    dpm_step_body(eps, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+}
+
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
 __global__ void loop_select_row_kernel(const float* __restrict__ table, int R, const LoopState* __restrict__ st,
                                        float* __restrict__ out) {
@@ -309,6 +452,7 @@ int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s) {
 int launch_step_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, const void* state,
                         const float* coef, const int* zrow, float clip, hipStream_t s) {
     SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
     SISIC_REQUIRE(eps && x && state && coef && zrow && n > 0, "%s_indexed: null argument", rule_name(rule));
     ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
@@ -329,6 +473,7 @@ int launch_step_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, f
 int launch_step_indexed_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
                             const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
     SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
     SISIC_REQUIRE(eps && x && state && coef && seeds_dev && n > 0, "%s_indexed_rng: null argument", rule_name(rule));
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
                   "%s_indexed_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
@@ -348,6 +493,36 @@ int launch_step_indexed_rng(sisic_ctx* ctx, int rule, int flags, const float* ep
     else
         hipLaunchKernelGGL(ddim_step_indexed_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
                            seeds_dev, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+int launch_dpm_step_indexed(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, const void* state,
+                            const float* coef, const int* zrow, float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && hist && state && coef && zrow && n > 0, "dpmpp_step_indexed: null argument");
+    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist);
+    const int vec4 = (al & 15) == 0 && (n & 3) == 0;
+    const int64_t work = vec4 ? (n + 3) / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(dpm_step_indexed_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
+                       static_cast<const LoopState*>(state), coef, zrow, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+int launch_dpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
+                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
+    SISIC_REQUIRE(eps && x && hist && state && coef && seeds_dev && n > 0, "dpmpp_step_indexed_rng: null argument");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "dpmpp_step_indexed_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
+    ProfileScope prof(ctx, s, PK_DDPM, 20.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
+    hipLaunchKernelGGL(dpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, n, n_per_image,
+                       static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

@@ -677,7 +677,7 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)sisic_unet_train_end(u);
     (void)hipDeviceSynchronize();
     pool_release_all(u);
-    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev})
+    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -770,16 +770,27 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
     return unet_run_forward(u, sample, u->tproj, uniform ? 0 : u->tproj_R, out, B, H, W, s);
 }
 
+// the device tables of the replayed loop: 1000 rows of the widest rule's coefficients (a rule's rows lie packed at its own
+// width from the start of the region), then the noise row of each step
+static constexpr size_t LOOP_COEF_FLOATS = 6 * 1000;
+static constexpr size_t LOOP_TABLE_FLOATS = 4 + LOOP_COEF_FLOATS + 1000;
+
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
 // launches for every step, so that a captured step can be replayed.
 static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
                      hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
-    const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + 5 * 1000);
+    const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
     SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
     SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
-    if (rng)
+    if (rule == STEP_RULE_DPMPP && rng)
+        SISIC_TRY(launch_dpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, (int64_t)(n / B), state,
+                                              coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
+    else if (rule == STEP_RULE_DPMPP)
+        SISIC_TRY(launch_dpm_step_indexed(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, state, coef_dev, zrow_dev,
+                                          clip, s));
+    else if (rng)
         SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
                                           coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
     else
@@ -796,6 +807,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
                         hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
+    const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
     SISIC_REQUIRE(T <= 1000, "sample: at most 1000 steps per call");
     // the replayed launches write into the pool blocks they were captured with; a tape recorded since then may own some of
     // them: the tape does not survive a graph-replayed run (sisic_unet_backward then answers SISIC_ESTATE)
@@ -807,18 +819,18 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     }
     SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, n));
     SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)u->tproj_R));
-    SISIC_TRY(unet_grow(&u->loop_tables, &u->loop_tables_cap, (size_t)4 + 5 * 1000 + 1000));
+    SISIC_TRY(unet_grow(&u->loop_tables, &u->loop_tables_cap, LOOP_TABLE_FLOATS));
     // tables of this call: {step = 0, step base, noise base}, coefficients, noise row per step (-1: the step adds no noise)
-    std::vector<float> tab(4 + 5 * 1000 + 1000, 0.0f);
+    std::vector<float> tab(LOOP_TABLE_FLOATS, 0.0f);
     {
         const int first = 0, base = rng ? step0 : 0;
         std::memcpy(&tab[0], &first, sizeof(int));
         std::memcpy(&tab[1], &base, sizeof(int));
         std::memcpy(&tab[2], &noise, sizeof(noise));
-        std::memcpy(&tab[4], coef, (size_t)T * 5 * sizeof(float));
-        int* zr = reinterpret_cast<int*>(&tab[4 + 5 * 1000]);
+        std::memcpy(&tab[4], coef, (size_t)T * cw * sizeof(float));
+        int* zr = reinterpret_cast<int*>(&tab[4 + LOOP_COEF_FLOATS]);
         int zi = 0;
-        for (int i = 0; i < T; ++i) zr[i] = (noise && coef[(size_t)i * 5 + 4] != 0.0f) ? zi++ : -1;
+        for (int i = 0; i < T; ++i) zr[i] = (noise && coef[(size_t)i * cw + 4] != 0.0f) ? zi++ : -1;
     }
     SISIC_TRY(unet_stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
     SISIC_HIP(hipMemcpyAsync(u->x_work, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -837,16 +849,17 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         return *cancel != 0;
     };
     if (cancelled(0)) rc = SISIC_ECANCEL;
+    const void* hist = rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr;      // sized by sample_frames before this call
     // every address baked into the captured launches: the pool and the scratch buffers are sized by the first eager step at a
     // shape, the tables by ensure_rows / grow above
     auto reusable = [&]() -> bool {
         const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
+        const void* ptrs[6] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
                   u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
                   u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags;
-        for (int k = 0; k < 5; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
+        for (int k = 0; k < 6; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
     if (rc == SISIC_OK && !reusable()) {
@@ -860,7 +873,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     if (rc == SISIC_OK && i < T) {
         if (!reusable()) {
             const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[5] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur};
+            const void* ptrs[6] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
             const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, s);
@@ -877,7 +890,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
             u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
             u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
-            for (int k = 0; k < 5; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            for (int k = 0; k < 6; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
         }
@@ -916,8 +929,13 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     if (steps_done) *steps_done = 0;
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
+    const size_t cw = SISIC_RULE_ROW_WIDTH(rule);      // (an unknown rule is refused by check_step_row just below)
     if (rule != STEP_RULE_DDPM || rule_flags != 0)
-        for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * 5 + 0], coef[(size_t)i * 5 + 1]));
+        for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * cw + 0], coef[(size_t)i * cw + 1]));
+    // DPM-Solver++: a call starts with no history (the buffer holds whatever the last run left), so its first step cannot be
+    // a second-order one.  A run cut into two calls therefore differs from the uncut run; callers run it in one call.
+    if (rule == STEP_RULE_DPMPP)
+        SISIC_REQUIRE(coef[5] == 0.0f, "sample: row 0 of a DPM-Solver++ call has k1 = %g (a call starts with no history)", coef[5]);
     SISIC_TRY(unet_check_shape(u, B, H, W));
     // per-step tables for 1000 rows from the first call on (17 MB): a longer run after a shorter one then never moves the
     // time-embedding table, so the captured step (which holds its address) survives a change of T
@@ -926,6 +944,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     SISIC_REQUIRE(u->cfg.out_channels == C, "sample: in/out channels differ");
     const size_t n = (size_t)B * C * H * W;
     SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, n));
+    if (rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
     const bool rng = seeds != nullptr;
     if (rng) {
         // 2^31 step indices is ample (a run has at most 1000) and keeps step0 + i inside the int of the device-side state
@@ -961,10 +980,17 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
             }
         }
         SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
-        const float* c = coef + (size_t)i * 5;
+        const float* c = coef + (size_t)i * cw;
         const float* z = nullptr;
         if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-        if (rng)
+        if (rule == STEP_RULE_DPMPP && rng)
+            SISIC_TRY(launch_dpm_step_rng(u->ctx, u->eps_buf, x, u->hist_buf, x, (int64_t)n, (int64_t)(n / B),
+                                          reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
+                                          c[3], c[4], c[5], clip, s));
+        else if (rule == STEP_RULE_DPMPP)
+            SISIC_TRY(launch_dpm_step(u->ctx, u->eps_buf, x, z, u->hist_buf, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], c[5],
+                                      clip, s));
+        else if (rng)
             SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B),
                                       reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
                                       c[3], c[4], clip, s));

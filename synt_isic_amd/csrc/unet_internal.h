@@ -200,7 +200,8 @@ struct sisic_unet {
     hipGraphExec_t loop_exec = nullptr;
     struct LoopKey {
         int B = 0, H = 0, W = 0; float clip = 0; hipStream_t s = nullptr; bool latency = false; uint64_t gen = 0;
-        const void* ptrs[5] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur at capture time: each can be re-allocated
+        const void* ptrs[6] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur and (DPM-Solver++ steps, else null)
+                                         // hist_buf at capture time: each can be re-allocated
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
         const void* seeds = nullptr;     // ... from the seeds at this address
         int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags
@@ -210,10 +211,12 @@ struct sisic_unet {
     hipStream_t loop_stream = nullptr;   // used when the caller's stream is the legacy default stream (not capturable)
     float* x_work = nullptr;             // the loop's own latent buffer: every address inside the graph is library-owned
     size_t x_work_cap = 0;
-    float* loop_tables = nullptr;        // [state 4 floats][coef 5*T][zrow T] device
+    float* loop_tables = nullptr;        // [state 4 floats][coef: LOOP_COEF_FLOATS, rows of the rule's width][zrow 1000] device
     size_t loop_tables_cap = 0;
     float* tproj_cur = nullptr;
     size_t tproj_cur_cap = 0;
+    float* hist_buf = nullptr;           // SISIC_RULE_DPMPP: the previous step's x0 [B,C,H,W], owned by the running call
+    size_t hist_cap = 0;
     float* seeds_dev = nullptr;          // uint64 [B] seeds of the running sisic_sample_frames_rng call (sized in floats: 2 per seed)
     size_t seeds_cap = 0;
 

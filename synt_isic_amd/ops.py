@@ -313,6 +313,43 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
     return out
 
 
+def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hist: torch.Tensor, coef, clip: float = 0.0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_dpmpp_step: coef = (sigma_t, alpha_t, cx, k0, sigma, k1), a row of
+    ``HipDPMSolverMultistepScheduler.coefficient_table``.  hist: the previous step's x0, a tensor of x's size that the
+    call overwrites with this step's x0 and reads only when k1 != 0.  z None or sigma == 0: no noise is added."""
+    lib = _lib.load()
+    if hist.numel() != x.numel():
+        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
+    if out is None:
+        out = empty_like(x)
+    sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
+    check(lib.sisic_dpmpp_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
+                               _ptr(out, "out"), x.numel(), sb, sa, cx, k0, sigma, k1, float(clip), _stream(x.device)))
+    return out
+
+
+def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, clip: float = 0.0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dpmpp_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
+    ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
+    lib = _lib.load()
+    arr = _seed_array(seeds)
+    B = len(arr)
+    if x.numel() % B:
+        raise ValueError(f"{x.numel()} elements are not {B} equal images")
+    if hist.numel() != x.numel():
+        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
+    if out is None:
+        out = empty_like(x)
+    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
+    check(lib.sisic_dpmpp_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
+                                   x.numel() // B, seeds_dev.data_ptr(), int(step), sb, sa, cx, k0, sigma, k1, float(clip),
+                                   _stream(x.device)))
+    return out
+
+
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,
                  gn_shift=None, gn_silu=False) -> torch.Tensor:
     """d/dW of ``conv2d`` with the same prologue / index maps: dW [Cout, Cin, k, k] from the forward input(s) and the

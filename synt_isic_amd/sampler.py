@@ -17,6 +17,12 @@ image is sampled in and of how images are sharded over GPUs.
 under DDIM at eta = 0 there are none: nothing is drawn, no noise buffer exists and no worker thread runs.  (diffusers'
 DDIMScheduler draws a z on every step at eta > 0, also where it multiplies it by a sigma of 0.)
 
+``scheduler="dpmsolver++"`` runs the loop under DPM-Solver++(2M) (``HipDPMSolverMultistepScheduler``; ``solver_order``,
+``algorithm_type``), the rule for 10 to 25 steps.  The same x_T, ``noise_hash`` and z contract again: the ODE variant draws
+nothing beyond x_T, the SDE variant (``"sde-dpmsolver++"``) one ``z_t[b]`` for every step but the last.  The rule keeps the
+previous step's x0, and a run cut into several library calls would lose it at every cut, so a host-noise SDE run draws all
+its z first (``draw_noise``: T is small under this rule) and runs in one call instead of streaming segments.
+
 ``noise="device"`` (off by default) is a second contract with the same independence: ``x_T[b]`` from torch's device
 generator seeded with ``seed_b`` (the reference's own spelling on a GPU, so its ``noise_hash``), and every ``z_t[b]``
 generated inside the scheduler-step kernel by Philox4x32-10 keyed with ``seed_b``: no host RNG,
@@ -36,7 +42,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .scheduler import HipDDIMScheduler, HipDDPMScheduler
+from .scheduler import HipDDIMScheduler, HipDDPMScheduler, HipDPMSolverMultistepScheduler, check_dpmpp_options
 from .unet import HipUNet2DModel
 
 ISIC_CLASSES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")   # xai/XAI.py:196
@@ -83,22 +89,34 @@ def _check_noise_mode(noise: str) -> str:
     return noise
 
 
-SCHEDULERS = ("ddpm", "ddim")
+SCHEDULERS = ("ddpm", "ddim", "dpmsolver++")
 
 
-def _check_scheduler(scheduler: str, eta: float, use_clipped_model_output: bool = False) -> str:
+def _check_scheduler(scheduler: str, eta: float, use_clipped_model_output: bool = False, solver_order: int = 2,
+                     algorithm_type: str = "dpmsolver++") -> str:
     if scheduler not in SCHEDULERS:
         raise ValueError(f"scheduler must be one of {SCHEDULERS}, got {scheduler!r}")
-    if scheduler == "ddpm" and (float(eta) != 0.0 or use_clipped_model_output):
-        raise ValueError("eta and use_clipped_model_output belong to scheduler='ddim'; the DDPM rule has neither")
+    if scheduler != "ddim" and (float(eta) != 0.0 or use_clipped_model_output):
+        raise ValueError("eta and use_clipped_model_output belong to scheduler='ddim'; the DDPM and DPM-Solver++ rules have "
+                         "neither")
     if not 0.0 <= float(eta) <= 1.0:
         raise ValueError(f"eta must lie in 0 .. 1, got {eta!r}")
+    if scheduler == "dpmsolver++":
+        try:
+            check_dpmpp_options(solver_order, algorithm_type)
+        except NotImplementedError as e:
+            raise ValueError(str(e)) from None
+    elif solver_order != 2 or algorithm_type != "dpmsolver++":
+        raise ValueError("solver_order and algorithm_type belong to scheduler='dpmsolver++'")
     return scheduler
 
 
 def _rule_tables(scheduler, eta: float, use_clipped_model_output: bool):
-    """(host [T,5] coefficient table, SISIC_RULE_* id, rule flags) of a scheduler mirror, by its ``rule`` attribute"""
+    """(host [T, row width] coefficient table, SISIC_RULE_* id, rule flags) of a scheduler mirror, by its ``rule`` attribute.
+    Sigma is column 4 under every rule.  A DPM-Solver++ mirror carries its own solver_order and algorithm_type."""
     rule = _check_scheduler(getattr(scheduler, "rule", "ddpm"), eta, use_clipped_model_output)
+    if rule == "dpmsolver++":
+        return scheduler.coefficient_table().contiguous(), _lib.RULE_DPMPP, 0
     if rule == "ddim":
         flags = _lib.RULE_FLAG_CLIPPED_OUTPUT if use_clipped_model_output else 0
         return scheduler.coefficient_table(eta).contiguous(), _lib.RULE_DDIM, flags
@@ -312,10 +330,14 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
     (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
     ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
     return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``).
-    scheduler: a ``HipDDPMScheduler`` or a ``HipDDIMScheduler``; its ``rule`` selects the step kernel.  eta and
-    use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not zero under that rule
-    and eta -- none for DDIM at eta = 0, where every noise source gives the same result."""
+    scheduler: a ``HipDDPMScheduler``, a ``HipDDIMScheduler`` or a ``HipDPMSolverMultistepScheduler``; its ``rule`` selects
+    the step kernel.  eta and use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not
+    zero under that rule and eta -- none for DDIM at eta = 0 and for the ODE variant of DPM-Solver++, where every noise
+    source gives the same result.  A DPM-Solver++ run takes no ``NoiseStream``: the history lives inside one library call."""
     if isinstance(noise, NoiseStream):
+        if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":
+            raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
+                             "noise buffer, a DeviceNoise or None")
         return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices, eta,
                              use_clipped_model_output)
     lib = _lib.load()
@@ -510,10 +532,18 @@ class Sampler:
         self.models[class_name] = m
         return m
 
-    def create_scheduler(self, T: int, scheduler: str = "ddpm"):
-        """model_manager.py:196-212; scheduler="ddim": the DDIM mirror over the same tables and timestep grid."""
-        cls = HipDDIMScheduler if _check_scheduler(scheduler, 0.0) == "ddim" else HipDDPMScheduler
-        s = cls(num_train_timesteps=1000, beta_schedule=self.beta_schedule)
+    def create_scheduler(self, T: int, scheduler: str = "ddpm", solver_order: int = 2, algorithm_type: str = "dpmsolver++"):
+        """model_manager.py:196-212; scheduler="ddim": the DDIM mirror over the same tables and timestep grid;
+        scheduler="dpmsolver++": the DPM-Solver++ mirror over the same tables and the same grid (its "leading" spacing; the
+        mirror's own default is the published "linspace"), with the clamp of x0 the other two rules apply (clip_sample=True)."""
+        rule = _check_scheduler(scheduler, 0.0, False, solver_order, algorithm_type)
+        if rule == "dpmsolver++":
+            s = HipDPMSolverMultistepScheduler(num_train_timesteps=1000, beta_schedule=self.beta_schedule,
+                                               solver_order=solver_order, algorithm_type=algorithm_type, clip_sample=True,
+                                               timestep_spacing="leading")
+        else:
+            s = (HipDDIMScheduler if rule == "ddim" else HipDDPMScheduler)(num_train_timesteps=1000,
+                                                                          beta_schedule=self.beta_schedule)
         s.set_timesteps(max(1, min(1000, int(T))))
         return s
 
@@ -531,20 +561,24 @@ class Sampler:
     def generate_seeds(self, class_name: str, seeds: Sequence[int], T: int, size: Tuple[int, int] = (128, 128),
                        return_trajectory: bool = False, save_every_n: Optional[int] = None,
                        noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
-                       use_clipped_model_output: bool = False) -> SampleResult:
+                       use_clipped_model_output: bool = False, solver_order: int = 2,
+                       algorithm_type: str = "dpmsolver++") -> SampleResult:
         """save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
         xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise.
         noise: "host" (the default: one CPU generator per image, see the module docstring) or "device" (x_T from torch's
         device generator, z_t generated in the step kernel: no host RNG, no noise buffers; other images for the same seed).
         scheduler: "ddpm" (the default) or "ddim" with its ``eta`` (0 = deterministic) and ``use_clipped_model_output``; x_T and
         ``noise_hashes`` of a seed do not depend on it.  Host-mode z rows go to the steps with sigma != 0 only (module
-        docstring): at eta = 0 nothing beyond x_T is drawn."""
+        docstring): at eta = 0 nothing beyond x_T is drawn.
+        scheduler="dpmsolver++": DPM-Solver++(2M) with ``solver_order`` (1 or 2) and ``algorithm_type`` ("dpmsolver++", which
+        like DDIM at eta = 0 draws nothing beyond x_T, or "sde-dpmsolver++"); it has no eta and no
+        use_clipped_model_output."""
         _check_noise_mode(noise)
-        _check_scheduler(scheduler, eta, use_clipped_model_output)
+        _check_scheduler(scheduler, eta, use_clipped_model_output, solver_order, algorithm_type)
         if class_name not in self.models:
             raise KeyError(f"no model loaded for class '{class_name}'")
         model = self.models[class_name]
-        sched = self.create_scheduler(T, scheduler)
+        sched = self.create_scheduler(T, scheduler, solver_order, algorithm_type)
         rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output)
         save_indices = None
         if return_trajectory and save_every_n is not None:
@@ -560,11 +594,14 @@ class Sampler:
             res.seeds = [int(s) for s in seeds]
             res.noise_hashes = hashes
             return res
-        if scheduler == "ddim" and n_noise == 0:
-            # eta = 0: the run draws x_T and nothing else -- no z, no staging buffers, no worker threads
-            x_T, _ = draw_noise(seeds, 0, (model.config.in_channels, H, W))
+        if scheduler == "dpmsolver++" or (scheduler == "ddim" and n_noise == 0):
+            # DDIM at eta = 0 and the ODE variant of DPM-Solver++: the run draws x_T and nothing else -- no z, no staging
+            # buffers, no worker threads.  The SDE variant: every z of the run up front and ONE library call, because the
+            # segments of a NoiseStream would each start without the history (T is 10 to 25 under this rule).
+            x_T, z = draw_noise(seeds, n_noise, (model.config.in_channels, H, W))
             hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, x_T.to(self.device), None, return_trajectory=return_trajectory,
+            res = run_sampling_loop(model, sched, x_T.to(self.device), z.to(self.device) if n_noise else None,
+                                    return_trajectory=return_trajectory,
                                     save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
             res.seeds = [int(s) for s in seeds]
@@ -589,7 +626,7 @@ class Sampler:
     def generate(self, seed: int, class_name: str, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,
                  save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
-                 use_clipped_model_output: bool = False):
+                 use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++"):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -601,7 +638,7 @@ class Sampler:
         postprocess=True applies the class colour statistics (``load_color_statistics``) to the uint8 images like
         ``generate_single_image(..., postprocess=True)`` does before saving (image_generator.py:449-452).
         noise: "host" or "device", as in ``generate_seeds``.
-        scheduler, eta, use_clipped_model_output: the step rule, as in ``generate_seeds``.
+        scheduler, eta, use_clipped_model_output, solver_order, algorithm_type: the step rule, as in ``generate_seeds``.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
         """
         if seed_is_base:
@@ -610,7 +647,8 @@ class Sampler:
             seeds = [(int(seed) + i) & 0x7FFFFFFF for i in range(count)]
         res = self.generate_images(class_name, seeds, T, size=size, return_trajectory=return_trajectory,
                                    save_every_n=save_every_n, noise=noise, scheduler=scheduler, eta=eta,
-                                   use_clipped_model_output=use_clipped_model_output)
+                                   use_clipped_model_output=use_clipped_model_output, solver_order=solver_order,
+                                   algorithm_type=algorithm_type)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:

@@ -14,7 +14,9 @@ are host data built with the same fp32 torch operations the published algorithm 
 ``sisic_ddpm_step``.
 
 ``HipDDIMScheduler`` mirrors ``diffusers.DDIMScheduler`` the same way (the reference itself holds no DDIM code: the swap
-is described in INTEGRATION.md); its update runs in ``sisic_ddim_step``.
+is described in INTEGRATION.md); its update runs in ``sisic_ddim_step``.  ``HipDPMSolverMultistepScheduler`` mirrors
+``diffusers.DPMSolverMultistepScheduler`` (DPM-Solver++(2M) and its SDE variant); its update, with the one-step history the
+rule needs, runs in ``sisic_dpmpp_step``.
 """
 from __future__ import annotations
 
@@ -291,3 +293,193 @@ class HipDDIMScheduler:
         if not return_dict:
             return (prev,)
         return DDIMSchedulerOutput(prev_sample=prev)
+
+
+DPMPP_ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
+
+
+def check_dpmpp_options(solver_order: int, algorithm_type: str) -> None:
+    """the refusals of the DPM-Solver++ mirror that ``generate`` repeats before it touches the GPU"""
+    if algorithm_type not in DPMPP_ALGORITHMS:
+        raise NotImplementedError(f"algorithm_type must be one of {DPMPP_ALGORITHMS}, got {algorithm_type!r}")
+    if solver_order not in (1, 2):
+        raise NotImplementedError(f"solver_order must be 1 or 2 (the third-order multistep form is out of scope), got "
+                                  f"{solver_order!r}")
+
+
+def dpmpp_coefficient_rows(abar, solver_order: int = 2, algorithm_type: str = "dpmsolver++") -> np.ndarray:
+    """float64 [T,6] rows {sigma_i, alpha_i, cx, k0, sigma, k1} of DPM-Solver++(2M) (Lu et al. 2022, midpoint rule) for a run
+    over ``abar`` = alphas_cumprod at its T timesteps, ending at abar = 1 (sigma = 0: the last step returns its x0).
+
+    Everything is float64 with ``expm1``: A = -alpha' * (exp(-h) - 1), and at the small h of a long run exp(-h) - 1 loses in
+    fp32 as many digits as h has leading zeros -- at T = 1000 (h of 3e-3 and up) the coefficients would be good to about 2e-5
+    relative, where the step kernel itself rounds at 6e-8.  The rows are rounded to fp32 once, by the caller."""
+    check_dpmpp_options(solver_order, algorithm_type)
+    abar = np.asarray(abar, dtype=np.float64)
+    T = abar.shape[0]
+    full = np.concatenate([abar, [1.0]])
+    alpha, sig = np.sqrt(full), np.sqrt(1.0 - full)
+    lam = np.full(T + 1, np.inf)
+    lam[:T] = np.log(alpha[:T]) - np.log(sig[:T])
+    sde = algorithm_type == "sde-dpmsolver++"
+    rows = np.zeros((T, 6), dtype=np.float64)
+    for i in range(T):
+        h = lam[i + 1] - lam[i]
+        if sde:
+            cx = (sig[i + 1] / sig[i]) * np.exp(-h)
+            A = -alpha[i + 1] * np.expm1(-2.0 * h)
+            sigma = sig[i + 1] * np.sqrt(-np.expm1(-2.0 * h))
+        else:
+            cx = sig[i + 1] / sig[i]
+            A = -alpha[i + 1] * np.expm1(-h)
+            sigma = 0.0
+        k0, k1 = A, 0.0
+        if solver_order == 2 and 0 < i < T - 1:                      # first step: no history; last step: h is infinite
+            r = (lam[i] - lam[i - 1]) / h
+            k0, k1 = A * (1.0 + 1.0 / (2.0 * r)), -A / (2.0 * r)
+        rows[i] = (sig[i], alpha[i], cx, k0, sigma, k1)
+    return rows
+
+
+@dataclass
+class DPMSolverSchedulerOutput:
+    """Mirror of diffusers' ``SchedulerOutput``."""
+    prev_sample: torch.Tensor
+
+
+class HipDPMSolverMultistepScheduler:
+    """Drop-in for ``diffusers.DPMSolverMultistepScheduler`` with epsilon prediction: DPM-Solver++(2M), the second-order
+    multistep solver (``solver_type="midpoint"``, ``final_sigmas_type="zero"``), and its stochastic variant
+    ``algorithm_type="sde-dpmsolver++"``.  One UNet call per step like DDIM, which it equals at ``solver_order=1``.
+
+        sched = HipDPMSolverMultistepScheduler(num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2")
+        sched.set_timesteps(20)
+        for t in sched.timesteps:
+            latents = sched.step(model(latents, t).sample, t, latents).prev_sample
+
+    ``step`` is stateful: the object keeps the previous step's predicted x0 and the step index, and ``set_timesteps`` resets
+    both.  ``timestep_spacing``: "linspace" (the published default, from t = N - 1), "trailing", or "leading" -- the grid of
+    the project's DDPM and DDIM mirrors, so that the three rules can run on one grid.  ``clip_sample`` /
+    ``clip_sample_range`` are extensions of this project (the published class has ``thresholding``
+    instead): the clamp of x0 the other two mirrors apply, off by default."""
+    order = 1
+    rule = "dpmsolver++"
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", solver_order: int = 2, prediction_type: str = "epsilon",
+                 algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint", lower_order_final: bool = True,
+                 final_sigmas_type: str = "zero", timestep_spacing: str = "linspace", steps_offset: int = 0,
+                 clip_sample: bool = False, clip_sample_range: float = 1.0, **unsupported):
+        if unsupported:
+            raise NotImplementedError(f"unsupported DPMSolverMultistepScheduler arguments: {sorted(unsupported)}")
+        if prediction_type != "epsilon":
+            raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
+        check_dpmpp_options(solver_order, algorithm_type)
+        if solver_type != "midpoint":
+            raise NotImplementedError("only solver_type='midpoint' (the published default)")
+        if final_sigmas_type != "zero":
+            raise NotImplementedError("only final_sigmas_type='zero': the run ends at sigma = 0 and returns its x0")
+        if timestep_spacing not in ("linspace", "leading", "trailing"):
+            raise NotImplementedError("timestep_spacing must be 'linspace' (the published default), 'leading' or 'trailing'")
+        if beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "squaredcos_cap_v2":
+            self.betas = _betas_for_alpha_bar(num_train_timesteps)
+        else:
+            raise NotImplementedError(f"beta_schedule '{beta_schedule}' is not used by the reference")
+        # lower_order_final has no effect: with final_sigmas_type='zero' the last step is first order whatever it says
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order,
+                                      prediction_type=prediction_type, algorithm_type=algorithm_type,
+                                      solver_type=solver_type, lower_order_final=lower_order_final,
+                                      final_sigmas_type=final_sigmas_type, timestep_spacing=timestep_spacing,
+                                      steps_offset=steps_offset, clip_sample=clip_sample,
+                                      clip_sample_range=clip_sample_range)
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps: Optional[int] = None
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+        self._reset()
+
+    __len__ = HipDDPMScheduler.__len__
+    scale_model_input = HipDDPMScheduler.scale_model_input
+    add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
+    add_noise = HipDDPMScheduler.add_noise
+
+    def _reset(self) -> None:
+        self._hist: Optional[torch.Tensor] = None     # the previous step's x0 (device), None before the first step
+        self._step_index: Optional[int] = None
+        self._tables = None
+
+    @property
+    def step_index(self) -> Optional[int]:
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        n_train = self.config.num_train_timesteps
+        if num_inference_steps > n_train:
+            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
+        if num_inference_steps < 1:
+            raise ValueError("num_inference_steps must be >= 1")
+        self.num_inference_steps = T = num_inference_steps
+        spacing = self.config.timestep_spacing
+        if spacing == "linspace":
+            ts = np.linspace(0, n_train - 1, T + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif spacing == "leading":                               # the grid of the DDPM and DDIM mirrors: ends at t = 0
+            step_ratio = n_train // T
+            ts = (np.arange(0, T) * step_ratio).round()[::-1].copy().astype(np.int64)
+            ts += self.config.steps_offset
+        else:                                                    # "trailing"
+            ts = np.round(np.arange(n_train, 0, -n_train / T)).astype(np.int64) - 1
+        self.timesteps = torch.from_numpy(ts)
+        self._reset()
+
+    def _rows(self, solver_order: int) -> torch.Tensor:
+        abar = self.alphas_cumprod[self.timesteps.to(torch.int64)].numpy().astype(np.float64)
+        return torch.from_numpy(dpmpp_coefficient_rows(abar, solver_order, self.config.algorithm_type).astype(np.float32))
+
+    def coefficient_table(self) -> torch.Tensor:
+        """[T,6] fp32 host table {sigma_t, alpha_t, cx, k0, sigma, k1} for ``sisic_sample_frames_rule`` under
+        SISIC_RULE_DPMPP: float64 arithmetic (``dpmpp_coefficient_rows``), rounded to fp32 here."""
+        return self._rows(self.config.solver_order)
+
+    @torch.no_grad()
+    def step(self, model_output: torch.Tensor, timestep: Union[int, torch.Tensor], sample: torch.Tensor,
+             generator: Optional[torch.Generator] = None, variance_noise: Optional[torch.Tensor] = None,
+             return_dict: bool = True):
+        """prev_sample = DPM-Solver++ update on the GPU.  The first call after ``set_timesteps`` finds its place in
+        ``timesteps`` by ``timestep`` and is first order (there is no history yet); every call then moves one step on.
+        Noise, on the steps with sigma != 0 only (the SDE variant, all but the last): ``variance_noise`` if given, else
+        ``torch.randn`` with ``generator``."""
+        if model_output.device.type != "cuda":
+            raise RuntimeError("HipDPMSolverMultistepScheduler.step runs on MI355X tensors only (no CPU path)")
+        if self._tables is None:
+            self._tables = (self._rows(1), self._rows(self.config.solver_order))
+        if self._step_index is None:
+            at = (self.timesteps == int(timestep)).nonzero()
+            if at.numel() == 0:
+                raise ValueError(f"timestep {int(timestep)} is not one of this run's timesteps")
+            self._step_index = int(at[0])
+        i = self._step_index
+        if i >= self.timesteps.numel():
+            raise RuntimeError("step called past the last timestep; call set_timesteps to start another run")
+        x = sample.to(torch.float32).contiguous()
+        fresh = self._hist is None or self._hist.shape != x.shape or self._hist.device != x.device
+        if fresh:
+            self._hist = ops.empty_like(x)
+        coef = tuple(float(v) for v in self._tables[0 if fresh else 1][i])
+        z = None
+        if coef[4] != 0.0:
+            if variance_noise is not None:
+                z = variance_noise.to(device=x.device, dtype=torch.float32).contiguous()
+            elif generator is not None and generator.device.type == "cpu":
+                z = torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(x.device)
+            else:
+                z = torch.randn(model_output.shape, generator=generator, device=x.device, dtype=torch.float32)
+        clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
+        prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, clip)
+        self._step_index = i + 1
+        if not return_dict:
+            return (prev,)
+        return DPMSolverSchedulerOutput(prev_sample=prev)
