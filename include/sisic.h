@@ -412,11 +412,59 @@ int sisic_unet_optimizer_step(sisic_unet*, double lr, double beta1, double beta2
 int sisic_unet_train_step(sisic_unet*, const float* images, const float* noise, const int64_t* timesteps,
                           const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
                           double beta1, double beta2, double eps, float loss_scale, float* loss_out, int* found_inf, void* stream);
+/* ---- global-norm gradient clipping and an exponential moving average of the weights -----------------------------------
+ * What diffusers' unconditional training example wraps round the same UNet2DModel: torch.nn.utils.clip_grad_norm_ before
+ * the optimizer step and EMAModel.step after it.  Everything here is an addition: a caller of the entry points above gets
+ * the launches it always got.
+ *
+ * sisic_optim_ext (16 bytes; the double comes first so that the struct has no padding):
+ *   ema_decay      at 0, double: the decay of THIS step (EMAModel.get_decay; the caller computes it per step)
+ *   max_grad_norm  at 8, float:  clip_grad_norm_'s max_norm; <= 0 or +inf: the norm is reported, nothing is clipped
+ *   ema_update     at 12, int:   1: ema = ema - (1 - ema_decay) * (ema - p_new) rides in the update pass (needs
+ *                                sisic_unet_ema_begin); on a step that found_inf skips, the EMA moves towards the unchanged
+ *                                weights, as EMAModel.step after a skipped scaler.step does
+ * A NULL pointer means {0, 0, 0}.                                                                                        */
+typedef struct sisic_optim_ext {           /* 16 bytes, no padding */
+    double ema_decay;
+    float  max_grad_norm;
+    int    ema_update;
+} sisic_optim_ext;
+/* sisic_unet_optimizer_step / sisic_unet_train_step with the options above: one statistics pass over the gradient arena
+ * (squares of fp32(g * inv_scale) summed in double in a fixed order; found_inf as before), one 12-byte read-back (one
+ * synchronisation, also when found_inf is NULL), the skip decision on the host, one fused Adam + EMA pass, the same
+ * rebuild of the packed weights.  Adam's arithmetic is that of sisic_unet_optimizer_step on (g * inv_scale) * clip_coef,
+ * clip_coef = min(1, max_grad_norm / (norm + 1e-6)) in fp32 (a NaN norm gives a NaN coefficient, as torch's clamp does).
+ * grad_norm_out (host, may be NULL): the norm of the unscaled gradient before clipping, what clip_grad_norm_ returns.   */
+int sisic_unet_optimizer_step_ext(sisic_unet*, double lr, double beta1, double beta2, double eps, float inv_scale,
+                                  const sisic_optim_ext* ext, int* found_inf, float* grad_norm_out, void* stream);
+int sisic_unet_train_step_ext(sisic_unet*, const float* images, const float* noise, const int64_t* timesteps,
+                              const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
+                              double beta1, double beta2, double eps, float loss_scale, const sisic_optim_ext* ext,
+                              float* loss_out, int* found_inf, float* grad_norm_out, void* stream);
+/* The EMA arena.  ema_begin (after train_begin) allocates it and copies the current weights into it (EMAModel.__init__;
+ * called again: copies again); train_end frees it.  ema_step is EMAModel.step on its own, for an EMA kept beside
+ * sisic_unet_optimizer_step.  ema_swap exchanges the EMA with the trained weights and rebuilds every packed form, so that
+ * every entry point that reads weights (forward, sample, read what = 0) sees the averaged ones; a second call swaps back.
+ * While swapped, the optimizer_step / train_step entry points, ema_step, ema_begin and a reload return SISIC_ESTATE:
+ * training on the averaged weights is always a bug.  ema_active: 0 no arena, 1 arena, 2 arena and currently swapped.     */
+int sisic_unet_ema_begin(sisic_unet*);
+int sisic_unet_ema_step(sisic_unet*, double ema_decay, void* stream);
+int sisic_unet_ema_swap(sisic_unet*, void* stream);
+int sisic_unet_ema_active(const sisic_unet*);
+/* The two kernels on the caller's device vectors (parity-test surface; any n >= 1, pointers aligned to a float; scratch is
+ * allocated per call).  grad_stats writes the record {float total_norm; float clip_coef; int found_inf} (3 x 4 bytes) to
+ * stats_dev.  adam_ema: one Adam step number `step` (>= 1) on p, m, v from g, reading clip_coef from stats_dev (NULL: 1)
+ * and updating ema (NULL: none) with ema_decay; with both NULL it is the kernel of sisic_unet_optimizer_step.            */
+int sisic_grad_stats(sisic_ctx*, const float* g, int64_t n, float inv_scale, float max_norm, void* stats_dev, void* stream);
+int sisic_adam_ema(sisic_ctx*, float* p, const float* g, float* m, float* v, float* ema_or_null, int64_t n, double lr,
+                   double beta1, double beta2, double eps, int64_t step, float inv_scale, const void* stats_dev_or_null,
+                   double ema_decay, void* stream);
 /* Copy one tensor of the state dict (index as in sisic_unet_tensor_name) to the host: what = 0 parameter, 1 gradient,
- * 2 Adam first moment, 3 Adam second moment.  Synchronises the device.                                                  */
+ * 2 Adam first moment, 3 Adam second moment, 4 EMA (after sisic_unet_ema_begin).  Synchronises the device.               */
 int sisic_unet_read(sisic_unet*, int what, int index, float* host_out, int64_t numel);
 /* The counterpart of sisic_unet_read (parity-test surface: optimizer tests choose their own gradients): copy one tensor
- * from the host into the gradient (what = 1), Adam first-moment (2) or second-moment (3) arena.  what = 0 is refused:
+ * from the host into the gradient (what = 1), Adam first-moment (2), second-moment (3) or EMA (4, after
+ * sisic_unet_ema_begin: EMAModel.load_state_dict) arena.  what = 0 is refused:
  * parameters have packed forms that must follow them, sisic_unet_load sets them.  Synchronises the device.              */
 int sisic_unet_write(sisic_unet*, int what, int index, const float* host_in, int64_t numel);
 int64_t sisic_unet_train_steps(const sisic_unet*);

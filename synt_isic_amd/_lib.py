@@ -77,6 +77,16 @@ class AugmentParams(C.Structure):
                 ("factor", C.c_float * 3), ("rotate", C.c_int32), ("rot", C.c_int32 * 6), ("reserved", C.c_int32 * 4)]
 
 
+class OptimExt(C.Structure):
+    """struct sisic_optim_ext (16 bytes, no padding)"""
+    _fields_ = [("ema_decay", C.c_double), ("max_grad_norm", C.c_float), ("ema_update", C.c_int)]
+
+
+class GradStats(C.Structure):
+    """the record sisic_grad_stats writes (3 x 4 bytes)"""
+    _fields_ = [("total_norm", C.c_float), ("clip_coef", C.c_float), ("found_inf", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -165,6 +175,20 @@ SIGNATURES = {
     "sisic_unet_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int64_p, c_float_p, c_float_p, C.c_int,
                                         C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
                                         C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_unet_optimizer_step_ext": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
+                                                C.POINTER(OptimExt), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p]),
+    "sisic_unet_train_step_ext": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int64_p, c_float_p, c_float_p, C.c_int,
+                                            C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
+                                            C.POINTER(OptimExt), C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_float), C.c_void_p]),
+    "sisic_unet_ema_begin": (C.c_int, [C.c_void_p]),
+    "sisic_unet_ema_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "sisic_unet_ema_swap": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sisic_unet_ema_active": (C.c_int, [C.c_void_p]),
+    "sisic_grad_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "sisic_adam_ema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float, C.c_void_p,
+                                 C.c_double, C.c_void_p]),
     "sisic_unet_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sisic_unet_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sisic_unet_train_steps": (C.c_int64, [C.c_void_p]),

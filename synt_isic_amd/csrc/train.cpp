@@ -324,6 +324,63 @@ int check_trainable_resolution(sisic_unet* u, int H, int W) {
     return SISIC_OK;
 }
 
+// every derived form of the weights follows a change of the raw arena (an optimizer step, an EMA swap): three batched
+// launches (repack.hip); the one-launch-per-tensor route of the load path when the buffers have moved since the job tables
+// were built (SISIC_REPACK_BATCH=0: always)
+int repack_after_update(sisic_unet* u, hipStream_t s) {
+    TrainState* tr = u->train.get();
+    static const bool batch_on = [] { const char* e = std::getenv("SISIC_REPACK_BATCH"); return !e || std::atoi(e) != 0; }();
+    if (batch_on && tr->repack_ready) return run_repack_plan(u, s);
+    SISIC_TRY(unet_prepare_all(u, s));
+    SISIC_TRY(prepare_backward_weights(u, s));
+    if (batch_on) {
+        SISIC_HIP(hipStreamSynchronize(s));
+        SISIC_TRY(build_repack_plan(u));
+    }
+    return SISIC_OK;
+}
+
+// training on the averaged weights is always a bug
+int require_not_swapped(sisic_unet* u, const char* what) {
+    if (u->train->ema_swapped) {
+        set_error("%s: the EMA weights are swapped in (sisic_unet_ema_swap): swap the trained weights back first", what);
+        return SISIC_ESTATE;
+    }
+    return SISIC_OK;
+}
+
+// the loop body of sisic_unet_train_step up to the optimizer step: add_noise, forward, MSE, backward, the loss read-back
+int train_step_body(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps, const float* sqrt_alpha_prod,
+                    const float* sqrt_one_minus_alpha_prod, int B, int H, int W, float loss_scale, float* loss_out, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TrainState* tr = u->train.get();
+    const int C = u->cfg.in_channels;
+    const size_t n = (size_t)B * C * H * W;
+    SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, 3 * n));     // noisy | prediction | d prediction
+    float* noisy = u->eps_buf;
+    float* pred = noisy + n;
+    float* dpred = pred + n;
+    // coefficient rows: host -> device through the pinned ring (2B floats)
+    SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
+    SISIC_TRY(unet_grow(&tr->small, &tr->small_cap, train_small_floats(u, B)));
+    std::vector<float> coef(2 * (size_t)B);
+    std::memcpy(coef.data(), sqrt_alpha_prod, B * sizeof(float));
+    std::memcpy(coef.data() + B, sqrt_one_minus_alpha_prod, B * sizeof(float));
+    SISIC_TRY(unet_stage_upload(u, coef.data(), 2 * (size_t)B, tr->small, s));
+    SISIC_TRY(launch_add_noise(u->ctx, images, noise, tr->small, tr->small + B, noisy, B, (size_t)C * H * W, s));
+    SISIC_TRY(sisic_unet_train_forward(u, noisy, timesteps, pred, B, H, W, stream));
+    SISIC_TRY(launch_mse(u->ctx, pred, noise, n, loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
+    SISIC_TRY(sisic_unet_backward(u, dpred, stream));
+    if (loss_out) {
+        SISIC_HIP(hipMemcpyAsync(loss_out, tr->loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+        SISIC_HIP(hipStreamSynchronize(s));
+    }
+    return SISIC_OK;
+}
+
+GradStats* stats_record(TrainState* tr) { return static_cast<GradStats*>(tr->stats_dev); }
+void* stats_scratch(TrainState* tr) { return static_cast<char*>(tr->stats_dev) + 16; }
+
 }  // namespace
 
 extern "C" {
@@ -357,6 +414,7 @@ int sisic_unet_train_begin(sisic_unet* u) {
         u->train = std::move(tr);
     }
     TrainState* tr = u->train.get();
+    SISIC_TRY(require_not_swapped(u, "train_begin"));
     const size_t bytes = u->raw_floats * sizeof(float);
     SISIC_HIP(hipMemset(tr->grad, 0, bytes));
     SISIC_HIP(hipMemset(tr->adam_m, 0, bytes));
@@ -374,8 +432,9 @@ int sisic_unet_train_end(sisic_unet* u) {
     unet_release_tape(u);
     TrainState* tr = u->train.get();
     for (float* p : {tr->grad, tr->adam_m, tr->adam_v, tr->emb, tr->h1, tr->t2, tr->dtproj, tr->garena, tr->wgrad_part, tr->scratch,
-                     tr->small, tr->loss_dev, tr->mse_part})
+                     tr->small, tr->loss_dev, tr->mse_part, tr->ema})
         if (p) (void)hipFree(p);
+    if (tr->stats_dev) (void)hipFree(tr->stats_dev);
     if (tr->scatter_dev) (void)hipFree(tr->scatter_dev);
     for (void* p : tr->repack_dev)
         if (p) (void)hipFree(p);
@@ -456,6 +515,7 @@ int sisic_add_noise(sisic_ctx* ctx, const float* x0, const float* noise, const f
 int sisic_unet_optimizer_step(sisic_unet* u, double lr, double beta1, double beta2, double eps, float inv_scale, int* found_inf,
                               void* stream) {
     SISIC_TRY(require_train(u, "optimizer_step"));
+    SISIC_TRY(require_not_swapped(u, "optimizer_step"));
     TrainState* tr = u->train.get();
     hipStream_t s = static_cast<hipStream_t>(stream);
     SISIC_HIP(hipSetDevice(u->ctx->device));
@@ -471,17 +531,50 @@ int sisic_unet_optimizer_step(sisic_unet* u, double lr, double beta1, double bet
     tr->step += 1;
     SISIC_TRY(launch_adam(u->ctx, u->raw, tr->grad, tr->adam_m, tr->adam_v, u->raw_floats, lr, beta1, beta2, eps, tr->step,
                           inv_scale, s));
-    // every derived form of the weights follows the update: three batched launches (repack.hip); the one-launch-per-tensor
-    // route of the load path when the buffers have moved since the job tables were built (SISIC_REPACK_BATCH=0: always)
-    static const bool batch_on = [] { const char* e = std::getenv("SISIC_REPACK_BATCH"); return !e || std::atoi(e) != 0; }();
-    if (batch_on && tr->repack_ready) return run_repack_plan(u, s);
-    SISIC_TRY(unet_prepare_all(u, s));
-    SISIC_TRY(prepare_backward_weights(u, s));
-    if (batch_on) {
-        SISIC_HIP(hipStreamSynchronize(s));
-        SISIC_TRY(build_repack_plan(u));
+    return repack_after_update(u, s);
+}
+
+// The same step with clipping and / or the EMA: one statistics pass (norm, clip coefficient, found_inf), one 12-byte read-back,
+// the skip decision on the host as above (the step counter feeds the bias corrections and does not advance on a skipped step),
+// one fused update pass, the same repack tail.
+int sisic_unet_optimizer_step_ext(sisic_unet* u, double lr, double beta1, double beta2, double eps, float inv_scale,
+                                  const sisic_optim_ext* ext, int* found_inf, float* grad_norm_out, void* stream) {
+    SISIC_TRY(require_train(u, "optimizer_step_ext"));
+    SISIC_TRY(require_not_swapped(u, "optimizer_step_ext"));
+    TrainState* tr = u->train.get();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    const float max_norm = ext ? ext->max_grad_norm : 0.0f;
+    const bool ema_on = ext && ext->ema_update != 0;
+    const double decay = ext ? ext->ema_decay : 0.0;
+    if (ema_on) {
+        if (!tr->ema) {
+            set_error("optimizer_step_ext: ema_update without an EMA arena (call sisic_unet_ema_begin first)");
+            return SISIC_ESTATE;
+        }
+        SISIC_REQUIRE(decay >= 0.0 && decay <= 1.0, "optimizer_step_ext: ema_decay %g is outside [0, 1]", decay);
     }
-    return SISIC_OK;
+    if (!tr->stats_dev) {
+        const size_t bytes = 16 + grad_stats_scratch_bytes();
+        SISIC_HIP(hipMalloc(&tr->stats_dev, bytes));
+        SISIC_TRY(poison_fresh(tr->stats_dev, bytes));
+    }
+    SISIC_TRY(launch_grad_stats(u->ctx, tr->grad, u->raw_floats, inv_scale, max_norm, stats_record(tr), stats_scratch(tr), s));
+    GradStats host{};
+    SISIC_HIP(hipMemcpyAsync(&host, stats_record(tr), sizeof(GradStats), hipMemcpyDeviceToHost, s));
+    SISIC_HIP(hipStreamSynchronize(s));
+    if (grad_norm_out) *grad_norm_out = host.total_norm;
+    if (found_inf) {                 // without it there is no check, as in sisic_unet_optimizer_step
+        *found_inf = host.found_inf;
+        if (host.found_inf) {        // EMAModel.step runs after scaler.step either way: the shadow moves towards unchanged weights
+            if (ema_on) SISIC_TRY(launch_ema(u->ctx, tr->ema, u->raw, u->raw_floats, decay, s));
+            return SISIC_OK;
+        }
+    }
+    tr->step += 1;
+    SISIC_TRY(launch_adam_ema(u->ctx, u->raw, tr->grad, tr->adam_m, tr->adam_v, ema_on ? tr->ema : nullptr, u->raw_floats, lr, beta1,
+                              beta2, eps, tr->step, inv_scale, stats_record(tr), decay, s));
+    return repack_after_update(u, s);
 }
 
 int sisic_unet_train_step(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
@@ -489,31 +582,74 @@ int sisic_unet_train_step(sisic_unet* u, const float* images, const float* noise
                           double beta1, double beta2, double eps, float loss_scale, float* loss_out, int* found_inf,
                           void* stream) {
     SISIC_TRY(require_train(u, "train_step"));
+    SISIC_TRY(require_not_swapped(u, "train_step"));
     SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step: null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TrainState* tr = u->train.get();
-    const int C = u->cfg.in_channels;
-    const size_t n = (size_t)B * C * H * W;
-    SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, 3 * n));     // noisy | prediction | d prediction
-    float* noisy = u->eps_buf;
-    float* pred = noisy + n;
-    float* dpred = pred + n;
-    // coefficient rows: host -> device through the pinned ring (2B floats)
-    SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
-    SISIC_TRY(unet_grow(&tr->small, &tr->small_cap, train_small_floats(u, B)));
-    std::vector<float> coef(2 * (size_t)B);
-    std::memcpy(coef.data(), sqrt_alpha_prod, B * sizeof(float));
-    std::memcpy(coef.data() + B, sqrt_one_minus_alpha_prod, B * sizeof(float));
-    SISIC_TRY(unet_stage_upload(u, coef.data(), 2 * (size_t)B, tr->small, s));
-    SISIC_TRY(launch_add_noise(u->ctx, images, noise, tr->small, tr->small + B, noisy, B, (size_t)C * H * W, s));
-    SISIC_TRY(sisic_unet_train_forward(u, noisy, timesteps, pred, B, H, W, stream));
-    SISIC_TRY(launch_mse(u->ctx, pred, noise, n, loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
-    SISIC_TRY(sisic_unet_backward(u, dpred, stream));
-    if (loss_out) {
-        SISIC_HIP(hipMemcpyAsync(loss_out, tr->loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-        SISIC_HIP(hipStreamSynchronize(s));
-    }
+    SISIC_TRY(train_step_body(u, images, noise, timesteps, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
+                              stream));
     return sisic_unet_optimizer_step(u, lr, beta1, beta2, eps, 1.0f / loss_scale, found_inf, stream);
+}
+
+int sisic_unet_train_step_ext(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
+                              const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
+                              double beta1, double beta2, double eps, float loss_scale, const sisic_optim_ext* ext, float* loss_out,
+                              int* found_inf, float* grad_norm_out, void* stream) {
+    SISIC_TRY(require_train(u, "train_step_ext"));
+    SISIC_TRY(require_not_swapped(u, "train_step_ext"));
+    SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step_ext: null argument");
+    SISIC_TRY(train_step_body(u, images, noise, timesteps, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
+                              stream));
+    return sisic_unet_optimizer_step_ext(u, lr, beta1, beta2, eps, 1.0f / loss_scale, ext, found_inf, grad_norm_out, stream);
+}
+
+// ---- the EMA arena (diffusers' EMAModel: shadow parameters beside the trained ones)
+int sisic_unet_ema_begin(sisic_unet* u) {
+    SISIC_TRY(require_train(u, "ema_begin"));
+    SISIC_TRY(require_not_swapped(u, "ema_begin"));
+    TrainState* tr = u->train.get();
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    const size_t bytes = u->raw_floats * sizeof(float);
+    if (!tr->ema) {
+        void* q = nullptr;
+        SISIC_HIP(hipMalloc(&q, bytes));
+        SISIC_TRY(poison_fresh(q, bytes));
+        tr->ema = static_cast<float*>(q);
+    }
+    SISIC_HIP(hipDeviceSynchronize());
+    SISIC_HIP(hipMemcpy(tr->ema, u->raw, bytes, hipMemcpyDeviceToDevice));      // EMAModel.__init__: a copy of the parameters
+    SISIC_HIP(hipDeviceSynchronize());
+    return SISIC_OK;
+}
+
+int sisic_unet_ema_active(const sisic_unet* u) {
+    if (!u || !u->train || !u->train->ema) return 0;
+    return u->train->ema_swapped ? 2 : 1;
+}
+
+int sisic_unet_ema_step(sisic_unet* u, double ema_decay, void* stream) {
+    SISIC_TRY(require_train(u, "ema_step"));
+    SISIC_TRY(require_not_swapped(u, "ema_step"));
+    TrainState* tr = u->train.get();
+    if (!tr->ema) {
+        set_error("ema_step: no EMA arena (call sisic_unet_ema_begin first)");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    return launch_ema(u->ctx, tr->ema, u->raw, u->raw_floats, ema_decay, static_cast<hipStream_t>(stream));
+}
+
+int sisic_unet_ema_swap(sisic_unet* u, void* stream) {
+    SISIC_TRY(require_train(u, "ema_swap"));
+    TrainState* tr = u->train.get();
+    if (!tr->ema) {
+        set_error("ema_swap: no EMA arena (call sisic_unet_ema_begin first)");
+        return SISIC_ESTATE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    // the raw arena keeps its address, so the batched repack plan stays valid: exchange the contents, re-derive the packed forms
+    SISIC_TRY(launch_swap_arenas(u->ctx, u->raw, tr->ema, u->raw_floats, s));
+    tr->ema_swapped = !tr->ema_swapped;
+    return repack_after_update(u, s);
 }
 
 int sisic_unet_read(sisic_unet* u, int what, int index, float* host_out, int64_t numel) {
@@ -524,6 +660,7 @@ int sisic_unet_read(sisic_unet* u, int what, int index, float* host_out, int64_t
     else {
         SISIC_TRY(require_train(u, "unet_read"));
         base = what == 1 ? u->train->grad : (what == 2 ? u->train->adam_m : (what == 3 ? u->train->adam_v : nullptr));
+        if (what == 4) base = u->train->ema;             // the EMA arena, once sisic_unet_ema_begin has made it
     }
     SISIC_REQUIRE(base, "unet_read: what = %d (0 parameter, 1 gradient, 2 Adam m, 3 Adam v)", what);
     SISIC_HIP(hipSetDevice(u->ctx->device));
@@ -539,6 +676,7 @@ int sisic_unet_write(sisic_unet* u, int what, int index, const float* host_in, i
                              "2 Adam m, 3 Adam v");
     SISIC_TRY(require_train(u, "unet_write"));
     float* base = what == 1 ? u->train->grad : (what == 2 ? u->train->adam_m : (what == 3 ? u->train->adam_v : nullptr));
+    if (what == 4) base = u->train->ema;                 // the EMA arena, once sisic_unet_ema_begin has made it
     SISIC_REQUIRE(base, "unet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
     SISIC_HIP(hipSetDevice(u->ctx->device));
     SISIC_HIP(hipDeviceSynchronize());
@@ -566,6 +704,28 @@ int sisic_conv2d_wgrad(sisic_ctx* ctx, const sisic_conv_args* f, const float* dy
     (void)hipStreamSynchronize(s);
     (void)hipFree(part);
     return rc;
+}
+
+int sisic_grad_stats(sisic_ctx* ctx, const float* g, int64_t n, float inv_scale, float max_norm, void* stats_dev, void* stream) {
+    SISIC_REQUIRE(ctx && g && stats_dev && n > 0, "grad_stats: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    void* scratch = nullptr;
+    SISIC_HIP(hipMalloc(&scratch, grad_stats_scratch_bytes()));
+    SISIC_TRY(poison_fresh(scratch, grad_stats_scratch_bytes()));
+    const int rc = launch_grad_stats(ctx, g, (size_t)n, inv_scale, max_norm, static_cast<GradStats*>(stats_dev), scratch, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    return rc;
+}
+
+int sisic_adam_ema(sisic_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr, double beta1,
+                   double beta2, double eps, int64_t step, float inv_scale, const void* stats_dev, double ema_decay, void* stream) {
+    SISIC_REQUIRE(ctx && p && g && m && v && n > 0 && step >= 1, "adam_ema: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // neither a record nor an EMA: the unchanged kernel of sisic_unet_optimizer_step
+    if (!stats_dev && !ema) return launch_adam(ctx, p, g, m, v, (size_t)n, lr, beta1, beta2, eps, step, inv_scale, s);
+    return launch_adam_ema(ctx, p, g, m, v, ema, (size_t)n, lr, beta1, beta2, eps, step, inv_scale,
+                           static_cast<const GradStats*>(stats_dev), ema_decay, s);
 }
 
 int sisic_attention_bwd(sisic_ctx* ctx, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,

@@ -75,6 +75,23 @@ int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, flo
 int launch_check_finite(sisic_ctx*, const float* g, size_t n, int* flag, hipStream_t s);
 int launch_adam(sisic_ctx*, float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps,
                 int64_t step, float inv_scale, hipStream_t s);
+// What grad_stats leaves on the device for adam_ema (and the host reads back in one 12-byte copy): the norm of the unscaled
+// gradient, clip_grad_norm_'s coefficient, GradScaler's found_inf.
+struct GradStats {
+    float total_norm;
+    float clip_coef;
+    int found_inf;
+};
+static_assert(sizeof(GradStats) == 12, "the C ABI documents the record as 3 x 4 bytes");
+constexpr int GRAD_STATS_MAX_BLOCKS = 2048;         // block partials the scratch holds
+size_t grad_stats_scratch_bytes();                  // GRAD_STATS_MAX_BLOCKS doubles, then as many ints
+int launch_grad_stats(sisic_ctx*, const float* g, size_t n, float inv_scale, float max_norm, GradStats* stats_dev, void* scratch,
+                      hipStream_t s);
+// ema == nullptr: Adam alone; stats_dev == nullptr: clip coefficient 1
+int launch_adam_ema(sisic_ctx*, float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double b1, double b2,
+                    double eps, int64_t step, float inv_scale, const GradStats* stats_dev, double ema_decay, hipStream_t s);
+int launch_ema(sisic_ctx*, float* ema, const float* p, size_t n, double ema_decay, hipStream_t s);
+int launch_swap_arenas(sisic_ctx*, float* a, float* b, size_t n, hipStream_t s);
 int launch_add_noise(sisic_ctx*, const float* x0, const float* noise, const float* a_dev, const float* c_dev, float* out, int B,
                      size_t per, hipStream_t s);
 

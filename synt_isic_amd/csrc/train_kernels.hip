@@ -13,6 +13,8 @@
 //     with a fixed-order reduction (no atomics: bit-reproducible gradients);
 //   * GroupNorm(+SiLU) backward, attention backward (recomputing softmax per head, d = 8), the small linears of the time
 //     embedding, MSE, add_noise and Adam are HBM- or latency-bound vector kernels.
+#include <initializer_list>
+
 #include "common.h"
 #include "pack_device.h"
 #include "train.h"
@@ -1055,6 +1057,277 @@ int launch_add_noise(sisic_ctx*, const float* x0, const float* noise, const floa
     const size_t total = (size_t)B * per;
     hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, x0, noise,
                        a_dev, c_dev, out, per, total);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// ================================================================ gradient statistics, Adam + EMA, arena swap =========
+// The optimizer step with global-norm clipping and an exponential moving average of the weights: ONE statistics pass over
+// the gradient (grad_stats: norm, clip coefficient, non-finite flag -- what check_finite_kernel reads) and ONE update pass
+// (adam_ema: adam_kernel's arithmetic on the clipped gradient, and the EMA of the updated weight while it is in a register).
+//
+// 16 bytes per lane and access where the pointers allow it: scalar elements [0, head) up to the first 16-byte boundary,
+// n4 vectors of four from there, scalar elements [tail0, n) behind them.  Vectors that do not share their offset within 16
+// bytes have no common boundary: head = n, everything scalar.
+struct VecSplit {
+    size_t head, n4, tail0;
+};
+
+static VecSplit vec_split(std::initializer_list<const void*> ptrs, size_t n) {
+    uintptr_t off = 0;
+    bool first = true, same = true;
+    for (const void* q : ptrs) {
+        if (!q) continue;
+        const uintptr_t o = reinterpret_cast<uintptr_t>(q) & 15;
+        if (first) { off = o; first = false; }
+        same = same && o == off;
+    }
+    VecSplit v;
+    if (!same || (off & 3)) { v.head = n; v.n4 = 0; v.tail0 = n; return v; }
+    v.head = std::min<size_t>(((16 - off) & 15) >> 2, n);
+    v.n4 = (n - v.head) >> 2;
+    v.tail0 = v.head + 4 * v.n4;
+    return v;
+}
+
+// blocks of 256 threads for a grid-stride sweep of a split vector: enough for one element (vector or scalar) per thread, at
+// most per_cu blocks per CU of the device and never more than cap (adam_kernel's 4096 on a 256-CU device)
+static unsigned vec_grid(sisic_ctx* ctx, const VecSplit& vs, size_t n, int per_cu = 16, int cap = 4096) {
+    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const size_t want = (std::max(vs.n4, vs.head + (n - vs.tail0)) + 255) / 256;
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(want, (size_t)std::min(per_cu * cus, cap)));
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// block_sum_256 in double, the same fixed order
+__device__ __forceinline__ double block_sum_256_d(double v, double* red) {
+    v = wave_sum_d(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Pass 1 of torch.nn.utils.clip_grad_norm_ over the unscaled gradient gi = fp32(g[i] * inv_scale), the value Adam consumes:
+// part[block] = sum of (double)gi * (double)gi over the block's grid-stride share, flags[block] = 1 when a g[i] of the share is
+// inf / nan (the test of check_finite_kernel).  A product of two fp32 values is exact in double, so fusing it into the sum or
+// not gives the same bits; every partial sum has a fixed order (thread: head element, its vectors in stride order, tail
+// element; then block_sum_256_d).  Double: 300 gradients of 1e18 overflow an fp32 sum, and a double sum of non-negative terms
+// is ~1e-13 relative from exact in ANY order, far below half an fp32 ulp of the norm.  One f64 FMA per element beside a load
+// stream from HBM: the kernel stays bound by the stream.
+__global__ void __launch_bounds__(256) grad_stats_partial_kernel(const float* __restrict__ g, VecSplit vs, size_t n, float inv_scale,
+                                                                 double* __restrict__ part, int* __restrict__ flags) {
+    __shared__ double red[4];
+    __shared__ int any_bad;
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    double s = 0.0;
+    bool bad = false;
+    auto take = [&](float x) {
+        bad = bad || !isfinite(x);
+        const float gi = x * inv_scale;
+        s += (double)gi * (double)gi;
+    };
+    for (size_t i = tid; i < vs.head; i += stride) take(g[i]);
+    const float4* g4 = reinterpret_cast<const float4*>(g + vs.head);
+    for (size_t i = tid; i < vs.n4; i += stride) {
+        const float4 x = g4[i];
+        take(x.x); take(x.y); take(x.z); take(x.w);
+    }
+    for (size_t i = vs.tail0 + tid; i < n; i += stride) take(g[i]);
+    if (threadIdx.x == 0) any_bad = 0;
+    s = block_sum_256_d(s, red);                    // (its barriers order the store above before the ones below)
+    if (__any(bad) && (threadIdx.x & 63) == 0) any_bad = 1;       // up to four lanes store the same value
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s;
+        flags[blockIdx.x] = any_bad;
+    }
+}
+
+// Pass 2, one block: the block partials in index order per thread, then the block tree; clip_grad_norm_'s arithmetic in fp32:
+//   total_norm = (float)sqrt(sum);  clip_coef = clamp(max_norm / (total_norm + 1e-6), max = 1)
+// The clamp is torch's (x > 1 ? 1 : x), which lets a NaN norm through as a NaN coefficient; fminf would return 1.
+// max_norm <= 0 or +inf: no clipping asked for, the coefficient is exactly 1.
+__global__ void __launch_bounds__(256) grad_stats_final_kernel(const double* __restrict__ part, const int* __restrict__ flags, int nparts,
+                                                               float max_norm, GradStats* __restrict__ out) {
+    __shared__ double red[4];
+    __shared__ int any_bad;
+    double s = 0.0;
+    bool bad = false;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        s += part[i];
+        bad = bad || flags[i] != 0;
+    }
+    if (threadIdx.x == 0) any_bad = 0;
+    s = block_sum_256_d(s, red);
+    if (__any(bad) && (threadIdx.x & 63) == 0) any_bad = 1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float total = (float)sqrt(s);
+        float coef = 1.0f;
+        if (max_norm > 0.0f && max_norm < INFINITY) {
+            coef = max_norm / (total + 1e-6f);
+            coef = coef > 1.0f ? 1.0f : coef;
+        }
+        out->total_norm = total;
+        out->clip_coef = coef;
+        out->found_inf = any_bad;
+    }
+}
+
+size_t grad_stats_scratch_bytes() { return GRAD_STATS_MAX_BLOCKS * (sizeof(double) + sizeof(int)); }
+
+int launch_grad_stats(sisic_ctx* ctx, const float* g, size_t n, float inv_scale, float max_norm, GradStats* stats_dev, void* scratch,
+                      hipStream_t s) {
+    SISIC_REQUIRE(g && stats_dev && scratch && n > 0, "grad_stats: bad arguments");
+    SISIC_REQUIRE((reinterpret_cast<uintptr_t>(g) & 3) == 0, "grad_stats: the gradient is not aligned to a float");
+    const VecSplit vs = vec_split({g}, n);
+    // eight blocks of 256 per CU keep the load stream deep enough; never more blocks than the scratch has slots
+    const int blocks = (int)vec_grid(ctx, vs, n, 8, GRAD_STATS_MAX_BLOCKS);
+    double* part = static_cast<double*>(scratch);
+    int* flags = reinterpret_cast<int*>(part + GRAD_STATS_MAX_BLOCKS);
+    hipLaunchKernelGGL(grad_stats_partial_kernel, dim3(blocks), dim3(256), 0, s, g, vs, n, inv_scale, part, flags);
+    hipLaunchKernelGGL(grad_stats_final_kernel, dim3(1), dim3(256), 0, s, part, flags, blocks, max_norm, stats_dev);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// adam_kernel's update on the clipped gradient -- the same operations in the same order, gi = (g * inv_scale) * clip_coef the
+// only change -- and, with EMA, diffusers' EMAModel.step on the weight just written:
+//   s_param.sub_(one_minus_decay * (s_param - param))      ema = ema - omd * (ema - p_new)      (three fp32 operations)
+struct AdamEmaConsts {
+    float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, inv_scale, one_minus_decay;
+};
+
+template <bool EMA>
+__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamEmaConsts& c, float clip) {
+#pragma clang fp contract(off)
+    const float gi = (g * c.inv_scale) * clip;
+    const float mi = m + c.one_minus_b1 * (gi - m);
+    const float vi = v * c.b2 + (c.one_minus_b2 * gi) * gi;
+    m = mi;
+    v = vi;
+    const float denom = sqrtf(vi) / c.bc2_sqrt + c.eps;
+    const float pn = p - c.step_size * (mi / denom);
+    p = pn;
+    if (EMA) {
+        const float d = e - pn;
+        const float t = c.one_minus_decay * d;
+        e = e - t;
+    }
+}
+
+// stats == nullptr: coefficient 1 (x * 1.0f is x).  The coefficient is one scalar load per thread from the record that
+// grad_stats left on the device: no host round trip between the two kernels.  Every element is read and written by one thread.
+template <bool EMA>
+__global__ void __launch_bounds__(256) adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ ema, VecSplit vs, size_t n,
+                                                       AdamEmaConsts c, const GradStats* __restrict__ stats) {
+    const float clip = stats ? stats->clip_coef : 1.0f;
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    auto scalar = [&](size_t i) {
+        float pi = p[i], mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.0f;
+        adam_ema_elem<EMA>(pi, g[i], mi, vi, ei, c, clip);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (EMA) ema[i] = ei;
+    };
+    for (size_t i = tid; i < vs.head; i += stride) scalar(i);
+    float4* p4 = reinterpret_cast<float4*>(p + vs.head);
+    const float4* g4 = reinterpret_cast<const float4*>(g + vs.head);
+    float4* m4 = reinterpret_cast<float4*>(m + vs.head);
+    float4* v4 = reinterpret_cast<float4*>(v + vs.head);
+    float4* e4 = EMA ? reinterpret_cast<float4*>(ema + vs.head) : nullptr;
+    for (size_t i = tid; i < vs.n4; i += stride) {
+        float4 pv = p4[i], mv = m4[i], vv = v4[i];
+        const float4 gv = g4[i];
+        float4 ev = EMA ? e4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        adam_ema_elem<EMA>(pv.x, gv.x, mv.x, vv.x, ev.x, c, clip);
+        adam_ema_elem<EMA>(pv.y, gv.y, mv.y, vv.y, ev.y, c, clip);
+        adam_ema_elem<EMA>(pv.z, gv.z, mv.z, vv.z, ev.z, c, clip);
+        adam_ema_elem<EMA>(pv.w, gv.w, mv.w, vv.w, ev.w, c, clip);
+        p4[i] = pv; m4[i] = mv; v4[i] = vv;
+        if (EMA) e4[i] = ev;
+    }
+    for (size_t i = vs.tail0 + tid; i < n; i += stride) scalar(i);
+}
+
+int launch_adam_ema(sisic_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double b1, double b2,
+                    double eps, int64_t step, float inv_scale, const GradStats* stats_dev, double ema_decay, hipStream_t s) {
+    SISIC_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam_ema: bad arguments");
+    SISIC_REQUIRE(!ema || (ema_decay >= 0.0 && ema_decay <= 1.0), "adam_ema: ema_decay %g is outside [0, 1]", ema_decay);
+    SISIC_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                    reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(ema)) & 3) == 0, "adam_ema: a vector is not aligned to a float");
+    // the scalars as launch_adam forms them; 1 - decay in double, rounded to fp32 once (EMAModel.step forms it as a Python float)
+    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
+    const AdamEmaConsts c{(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps,
+                          inv_scale, (float)(1.0 - ema_decay)};
+    const VecSplit vs = vec_split({p, g, m, v, ema}, n);
+    const unsigned blocks = vec_grid(ctx, vs, n);
+    if (ema) hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, m, v, ema, vs, n, c, stats_dev);
+    else hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, m, v, ema, vs, n, c, stats_dev);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// EMAModel.step alone (an optimizer step that was skipped, or an EMA kept beside the unfused step): the three operations of
+// adam_ema_elem on the weights as they stand
+__global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ ema, const float* __restrict__ p, VecSplit vs, size_t n,
+                                                  float one_minus_decay) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    auto upd = [&](float e, float pv) {
+#pragma clang fp contract(off)
+        const float d = e - pv;
+        const float t = one_minus_decay * d;
+        return e - t;
+    };
+    for (size_t i = tid; i < vs.head; i += stride) ema[i] = upd(ema[i], p[i]);
+    float4* e4 = reinterpret_cast<float4*>(ema + vs.head);
+    const float4* p4 = reinterpret_cast<const float4*>(p + vs.head);
+    for (size_t i = tid; i < vs.n4; i += stride) {
+        float4 e = e4[i];
+        const float4 pv = p4[i];
+        e.x = upd(e.x, pv.x); e.y = upd(e.y, pv.y); e.z = upd(e.z, pv.z); e.w = upd(e.w, pv.w);
+        e4[i] = e;
+    }
+    for (size_t i = vs.tail0 + tid; i < n; i += stride) ema[i] = upd(ema[i], p[i]);
+}
+
+int launch_ema(sisic_ctx* ctx, float* ema, const float* p, size_t n, double ema_decay, hipStream_t s) {
+    SISIC_REQUIRE(ema && p && n > 0, "ema: bad arguments");
+    SISIC_REQUIRE(ema_decay >= 0.0 && ema_decay <= 1.0, "ema: ema_decay %g is outside [0, 1]", ema_decay);
+    const VecSplit vs = vec_split({ema, p}, n);
+    hipLaunchKernelGGL(ema_kernel, dim3(vec_grid(ctx, vs, n)), dim3(256), 0, s, ema, p, vs, n, (float)(1.0 - ema_decay));
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// a[i] <-> b[i]: the EMA weights into the live arena and back
+__global__ void __launch_bounds__(256) swap_arenas_kernel(float* __restrict__ a, float* __restrict__ b, VecSplit vs, size_t n) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    auto scalar = [&](size_t i) {
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    };
+    for (size_t i = tid; i < vs.head; i += stride) scalar(i);
+    float4* a4 = reinterpret_cast<float4*>(a + vs.head);
+    float4* b4 = reinterpret_cast<float4*>(b + vs.head);
+    for (size_t i = tid; i < vs.n4; i += stride) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y; b4[i] = x;
+    }
+    for (size_t i = vs.tail0 + tid; i < n; i += stride) scalar(i);
+}
+
+int launch_swap_arenas(sisic_ctx* ctx, float* a, float* b, size_t n, hipStream_t s) {
+    SISIC_REQUIRE(a && b && a != b && n > 0, "swap_arenas: bad arguments");
+    const VecSplit vs = vec_split({a, b}, n);
+    hipLaunchKernelGGL(swap_arenas_kernel, dim3(vec_grid(ctx, vs, n)), dim3(256), 0, s, a, b, vs, n);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

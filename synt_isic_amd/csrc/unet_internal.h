@@ -122,6 +122,10 @@ struct TrainState {
     float* loss_dev = nullptr;        // [2]: loss, scratch
     int* flag_dev = nullptr;          // non-finite gradient flag
     float* mse_part = nullptr;
+    // clipping and EMA (the *_ext entry points; nothing here exists until one of them or sisic_unet_ema_begin is called)
+    void* stats_dev = nullptr;        // GradStats record, then grad_stats' block partials
+    float* ema = nullptr;             // EMA of the weights, same layout as sisic_unet::raw
+    bool ema_swapped = false;         // sisic_unet_ema_swap: `raw` holds the averaged weights, `ema` the trained ones
     // every re-layout of every weight as three batched launches (repack.hip); rebuilt when the derived buffers move
     void* repack_dev[3] = {nullptr, nullptr, nullptr};     // PackJob tables on the device, one per phase
     int repack_jobs[3] = {0, 0, 0}, repack_blocks[3] = {0, 0, 0};

@@ -18,15 +18,25 @@ reads like the reference's):
     scaler.step(optimizer); scaler.update()                         sisic_unet_optimizer_step                :232-233
     epoch_loss += loss.item()                                       HipLoss.item()                           :235
 
+Beyond the reference, the three things diffusers' unconditional training example wraps round the same loop (all off unless
+asked for; with none of them the calls above are the only ones made):
+
+    accelerator.clip_grad_norm_(model.parameters(), 1.0)            HipAdam(..., max_grad_norm=1.0)  sisic_unet_optimizer_step_ext
+    ema_model.step(model.parameters())                              HipAdam(..., ema=HipEMA(model))  (rides in the same pass)
+    lr_scheduler.step()                                             HipLambdaLR(optimizer, cosine_schedule_with_warmup(...)).step()
+
 No torch.autograd anywhere: the backward pass is explicit HIP kernels (csrc/train.cpp).  Arithmetic is fp32; the
 GradScaler protocol (scale, unscale, inf check, skip, growth/backoff) is implemented, the autocast-to-fp16 is not.
 ``train_step_fused`` runs the whole loop body in ONE C call (sisic_unet_train_step).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 import os
-from typing import Callable, Iterable, Optional
+from collections import OrderedDict
+from typing import Callable, Dict, Iterable, Optional
 
 import torch
 
@@ -78,30 +88,225 @@ def mse_loss(noise_pred: torch.Tensor, noise: torch.Tensor) -> HipLoss:
     return HipLoss(model, noise_pred.contiguous(), noise.to(device=noise_pred.device, dtype=torch.float32).contiguous())
 
 
+class HipEMA:
+    """``diffusers.training_utils.EMAModel`` for a HipUNet2DModel: the shadow parameters live in the library, beside the
+    trained ones (sisic_unet_ema_begin copies the current weights, as ``EMAModel.__init__`` does).
+
+    Attached to the optimizer -- ``HipAdam(model, ema=ema)`` -- the update rides in the optimizer's own pass over the
+    weights and ``ema.step()`` is NOT called by the loop.  Kept separately it is the published spelling, ``ema.step()``
+    after ``optimizer.step()``: one more launch over the two arenas (sisic_unet_ema_step).  Either way
+    ``optimization_step`` counts every call, a scaler-skipped step included: the shadow then moves towards the unchanged
+    weights, exactly as upstream does.
+
+    ``model=None`` gives the decay schedule alone (``get_decay``), which needs no GPU."""
+
+    def __init__(self, model: Optional[HipUNet2DModel] = None, decay: float = 0.9999, min_decay: float = 0.0,
+                 update_after_step: int = 0, use_ema_warmup: bool = False, inv_gamma: float = 1.0, power: float = 2 / 3):
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"decay must be in [0, 1], got {decay}")
+        if not 0.0 <= float(min_decay) <= 1.0:
+            raise ValueError(f"min_decay must be in [0, 1], got {min_decay}")
+        self.decay, self.min_decay = float(decay), float(min_decay)
+        self.update_after_step, self.use_ema_warmup = int(update_after_step), bool(use_ema_warmup)
+        self.inv_gamma, self.power = inv_gamma, power
+        self.optimization_step = 0
+        self.cur_decay_value = None
+        self._stored = None
+        self.model = model
+        if model is not None:
+            model._ensure_training()
+            check(_lib.load().sisic_unet_ema_begin(model.handle))
+
+    def get_decay(self, optimization_step: int) -> float:
+        """The decay of one step, by the published formula."""
+        step = max(0, optimization_step - self.update_after_step - 1)
+        if step <= 0:
+            return 0.0
+        if self.use_ema_warmup:
+            cur_decay_value = 1 - (1 + step / self.inv_gamma) ** -self.power
+        else:
+            cur_decay_value = (1 + step) / (10 + step)
+        cur_decay_value = min(cur_decay_value, self.decay)
+        cur_decay_value = max(cur_decay_value, self.min_decay)
+        return cur_decay_value
+
+    def _handle(self):
+        if self.model is None:
+            raise RuntimeError("this HipEMA was made without a model: it only computes the decay schedule")
+        h = self.model.handle
+        if not _lib.load().sisic_unet_ema_active(h):
+            raise RuntimeError("the model's library handle was rebuilt (moved to another device?): the EMA went with it; "
+                               "make a new HipEMA")
+        return h
+
+    def _next_decay(self) -> float:
+        return self.get_decay(self.optimization_step + 1)
+
+    def _commit(self, decay: float) -> None:
+        self.optimization_step += 1
+        self.cur_decay_value = decay
+
+    def step(self, parameters=None) -> None:
+        """``ema_model.step(model.parameters())`` after an optimizer step that did not carry the EMA."""
+        h = self._handle()
+        decay = self._next_decay()
+        check(_lib.load().sisic_unet_ema_step(h, decay, _stream(self.model.device)))
+        self._commit(decay)
+
+    def shadow_params(self) -> "OrderedDict[str, torch.Tensor]":
+        self._handle()
+        return self.model._read_all(4)
+
+    def state_dict(self) -> dict:
+        return {"decay": self.decay, "min_decay": self.min_decay, "optimization_step": self.optimization_step,
+                "update_after_step": self.update_after_step, "use_ema_warmup": self.use_ema_warmup,
+                "inv_gamma": self.inv_gamma, "power": self.power, "shadow_params": self.shadow_params()}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        sd = dict(state_dict)
+        decay, min_decay = float(sd.get("decay", self.decay)), float(sd.get("min_decay", self.min_decay))
+        if not 0.0 <= decay <= 1.0 or not 0.0 <= min_decay <= 1.0:
+            raise ValueError("decay and min_decay must be in [0, 1]")
+        self.decay, self.min_decay = decay, min_decay
+        self.optimization_step = int(sd.get("optimization_step", self.optimization_step))
+        self.update_after_step = int(sd.get("update_after_step", self.update_after_step))
+        self.use_ema_warmup = bool(sd.get("use_ema_warmup", self.use_ema_warmup))
+        self.inv_gamma, self.power = sd.get("inv_gamma", self.inv_gamma), sd.get("power", self.power)
+        shadow = sd.get("shadow_params")
+        if shadow is not None:
+            self._handle()
+            missing = [k for k in self.model._spec if k not in shadow]
+            if missing:
+                raise RuntimeError(f"shadow_params lacks {len(missing)} tensors: {missing[:5]}")
+            self.model._write_all(4, {k: shadow[k] for k in self.model._spec}, "HipEMA.load_state_dict")
+
+    def copy_to(self, model: Optional[HipUNet2DModel] = None) -> None:
+        """Load the averaged weights into ``model`` (default: the EMA's own).  This is a ``load_state_dict``: under an
+        existing optimizer the moments start afresh.  To evaluate or save the averaged weights in the middle of a run use
+        ``average_parameters()``, which leaves the optimizer alone."""
+        (model if model is not None else self.model).load_state_dict(self.shadow_params())
+
+    def store(self, model: Optional[HipUNet2DModel] = None) -> None:
+        model = model if model is not None else self.model
+        self._stored = OrderedDict((k, v.detach().cpu().clone()) for k, v in model.state_dict().items())
+
+    def restore(self, model: Optional[HipUNet2DModel] = None) -> None:
+        if self._stored is None:
+            raise RuntimeError("restore() without a store() before it")
+        (model if model is not None else self.model).load_state_dict(self._stored)
+        self._stored = None
+
+    @contextlib.contextmanager
+    def average_parameters(self):
+        """Inside the context the model IS the averaged model (sisic_unet_ema_swap: the two arenas exchange contents and
+        every packed form follows): calls, ``state_dict()`` and sampling see the EMA; optimizer steps raise.  On exit the
+        trained weights are back, bit for bit."""
+        h = self._handle()
+        lib, model = _lib.load(), self.model
+        check(lib.sisic_unet_ema_swap(h, _stream(model.device)))
+        model._params_stale = True
+        model._ema_swapped = True
+        try:
+            yield self
+        finally:
+            check(lib.sisic_unet_ema_swap(h, _stream(model.device)))
+            model._params_stale = True
+            model._ema_swapped = False
+
+
 class HipAdam:
-    """``torch.optim.Adam(model.parameters(), lr)`` for a HipUNet2DModel: the state (m, v, step) lives in the library."""
+    """``torch.optim.Adam(model.parameters(), lr)`` for a HipUNet2DModel: the state (m, v, step) lives in the library.
+
+    ``max_grad_norm``: ``clip_grad_norm_(model.parameters(), max_grad_norm)`` in front of every step; the norm of the last
+    step (unscaled, before clipping: what ``clip_grad_norm_`` returns) is ``optimizer.grad_norm``.  ``ema``: a HipEMA whose
+    update rides in the step.  With neither, ``step()`` is the call it always was."""
 
     def __init__(self, model_or_params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False):
+                 amsgrad: bool = False, max_grad_norm: Optional[float] = None, ema: Optional[HipEMA] = None):
         if weight_decay != 0.0 or amsgrad:
             raise NotImplementedError("the reference uses plain Adam (train_diffusion.py:203)")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
         model = model_or_params if isinstance(model_or_params, HipUNet2DModel) else getattr(model_or_params, "_sisic_model", None)
         if model is None:
             raise RuntimeError("HipAdam needs the HipUNet2DModel (or its .parameters())")
+        if ema is not None and ema.model is not model:
+            raise ValueError("the HipEMA belongs to another model")
         self.model, self.lr, self.betas, self.eps = model, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema = ema
+        self.grad_norm: Optional[float] = None
         model._ensure_training()
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         check(_lib.load().sisic_unet_zero_grad(self.model.handle, _stream(self.model.device)))
 
+    def _extension(self) -> Optional[_lib.OptimExt]:
+        """the options of the *_ext entry points, or None when nothing asks for them (the old entry points are called)"""
+        if self.max_grad_norm is None and self.ema is None:
+            return None
+        ext = _lib.OptimExt()
+        ext.max_grad_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        if self.ema is not None:
+            self.ema._handle()
+            ext.ema_decay, ext.ema_update = self.ema._next_decay(), 1
+        return ext
+
+    def _extension_done(self, ext: _lib.OptimExt, norm: float) -> None:
+        self.grad_norm = float(norm)
+        if self.ema is not None:
+            self.ema._commit(ext.ema_decay)
+
     def step(self, inv_scale: float = 1.0, check_inf: bool = False) -> bool:
         """One Adam update; returns False when it was skipped because a gradient was inf/nan (GradScaler semantics)."""
         found = C.c_int(0)
-        check(_lib.load().sisic_unet_optimizer_step(self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                    float(inv_scale), C.byref(found) if check_inf else None,
-                                                    _stream(self.model.device)))
+        ext = self._extension()
+        if ext is None:
+            check(_lib.load().sisic_unet_optimizer_step(self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                        float(inv_scale), C.byref(found) if check_inf else None,
+                                                        _stream(self.model.device)))
+        else:
+            norm = C.c_float(0.0)
+            check(_lib.load().sisic_unet_optimizer_step_ext(self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                            float(inv_scale), C.byref(ext),
+                                                            C.byref(found) if check_inf else None, C.byref(norm),
+                                                            _stream(self.model.device)))
+            self._extension_done(ext, norm.value)
         self.model._params_stale = True
         return found.value == 0
+
+
+class HipLambdaLR:
+    """``torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda)`` for a HipAdam: ``lr`` is a per-call scalar of the step, so
+    the scheduler only sets ``optimizer.lr`` (to ``base_lr * lr_lambda(0)`` at construction, as torch does)."""
+
+    def __init__(self, optimizer: HipAdam, lr_lambda: Callable[[int], float]):
+        self.optimizer, self.lr_lambda = optimizer, lr_lambda
+        self.base_lr = optimizer.lr
+        self.last_epoch = 0
+        self._last_lr = self.base_lr * lr_lambda(0)
+        optimizer.lr = self._last_lr
+
+    def step(self) -> None:
+        self.last_epoch += 1
+        self._last_lr = self.base_lr * self.lr_lambda(self.last_epoch)
+        self.optimizer.lr = self._last_lr
+
+    def get_last_lr(self):
+        return [self._last_lr]
+
+
+def cosine_schedule_with_warmup(num_warmup_steps: int, num_training_steps: int, num_cycles: float = 0.5) -> Callable[[int], float]:
+    """The lambda of ``diffusers.optimization.get_cosine_schedule_with_warmup``: a linear ramp over the warm-up steps, then
+    the cosine from 1 towards 0 over the remaining ones."""
+
+    def lr_lambda(current_step: int) -> float:
+        if current_step < num_warmup_steps:
+            return float(current_step) / float(max(1, num_warmup_steps))
+        progress = float(current_step - num_warmup_steps) / float(max(1, num_training_steps - num_warmup_steps))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * float(num_cycles) * 2.0 * progress)))
+
+    return lr_lambda
 
 
 class _ScaledLoss:
@@ -152,8 +357,8 @@ class HipGradScaler:
 
 def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images: torch.Tensor, noise: torch.Tensor,
                      timesteps: torch.Tensor, optimizer: HipAdam, scaler: Optional[HipGradScaler] = None):
-    """The loop body of train_diffusion.py:215-233 in one library call (sisic_unet_train_step); returns
-    (loss, step_taken)."""
+    """The loop body of train_diffusion.py:215-233 in one library call (sisic_unet_train_step; sisic_unet_train_step_ext
+    when the optimizer clips or carries an EMA -- the norm is then ``optimizer.grad_norm``); returns (loss, step_taken)."""
     model._ensure_training()
     x0 = images.to(device=model.device, dtype=torch.float32).contiguous()
     nz = noise.to(device=model.device, dtype=torch.float32).contiguous()
@@ -162,11 +367,22 @@ def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images:
     a, c = scheduler.add_noise_coefficients(t)
     loss, found = C.c_float(0.0), C.c_int(0)
     scale = scaler.get_scale() if scaler is not None else 1.0
-    check(_lib.load().sisic_unet_train_step(model.handle, x0.data_ptr(), nz.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
-                                            C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p), B, H, W,
-                                            optimizer.lr, optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
-                                            C.byref(loss), C.byref(found) if scaler is not None and scaler.enabled else None,
-                                            _stream(model.device)))
+    found_ref = C.byref(found) if scaler is not None and scaler.enabled else None
+    ext = optimizer._extension()
+    if ext is None:
+        check(_lib.load().sisic_unet_train_step(model.handle, x0.data_ptr(), nz.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
+                                                C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p), B, H, W,
+                                                optimizer.lr, optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
+                                                C.byref(loss), found_ref, _stream(model.device)))
+    else:
+        norm = C.c_float(0.0)
+        check(_lib.load().sisic_unet_train_step_ext(model.handle, x0.data_ptr(), nz.data_ptr(),
+                                                    C.cast(t.data_ptr(), _lib.c_int64_p), C.cast(a.data_ptr(), _lib.c_float_p),
+                                                    C.cast(c.data_ptr(), _lib.c_float_p), B, H, W, optimizer.lr,
+                                                    optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
+                                                    C.byref(ext), C.byref(loss), found_ref, C.byref(norm),
+                                                    _stream(model.device)))
+        optimizer._extension_done(ext, norm.value)
     model._params_stale = True
     if scaler is not None:
         scaler._found_inf = bool(found.value)
@@ -176,16 +392,31 @@ def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images:
 
 def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_name: str, epochs: int = 50, lr: float = LR,
                 checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
-                log: Optional[Callable[[str], None]] = print):
+                log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
+                ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                lr_schedule: Optional[Callable[[int], float]] = None):
     """``train_class`` of train_diffusion.py:187-266 for one class: epochs over ``loader`` (batches of images in [-1,1],
     [B,3,H,W]), best-loss checkpoint ``unet_{class}_best.pth`` and a checkpoint every 5 epochs.  Returns the per-epoch
-    average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG)."""
+    average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG).
+
+    Beyond the reference, each off by default: ``max_grad_norm`` clips the global gradient norm; ``ema_decay`` keeps an EMA of
+    the weights (``ema_warmup``: EMAModel's warm-up decay) and saves it beside every checkpoint as ``..._ema.pth``;
+    ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch."""
     dev = model.device
     scheduler = HipDDPMScheduler(num_train_timesteps=TIMESTEPS, beta_schedule="squaredcos_cap_v2")
-    optimizer = HipAdam(model, lr=lr)
+    ema = HipEMA(model, decay=ema_decay, use_ema_warmup=ema_warmup) if ema_decay is not None else None
+    optimizer = HipAdam(model, lr=lr, max_grad_norm=max_grad_norm, ema=ema)
+    lr_scheduler = HipLambdaLR(optimizer, lr_schedule) if lr_schedule is not None else None
     scaler = HipGradScaler()
     best_loss = float("inf")
     history = []
+
+    def save(name: str) -> None:
+        torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_{name}.pth"))
+        if ema is not None:
+            with ema.average_parameters():
+                torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_{name}_ema.pth"))
+
     for epoch in range(epochs):
         model.train()
         epoch_loss, n_batches = 0.0, 0
@@ -205,6 +436,8 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
                 scaler.step(optimizer)
                 scaler.update()
                 value = loss.item()
+            if lr_scheduler is not None:
+                lr_scheduler.step()
             epoch_loss += value
             n_batches += 1
         avg_loss = epoch_loss / max(1, n_batches)
@@ -215,9 +448,9 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
             os.makedirs(checkpoint_dir, exist_ok=True)
             if avg_loss < best_loss:
                 best_loss = avg_loss
-                torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_best.pth"))
+                save("best")
             if (epoch + 1) % 5 == 0:
-                torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_epoch_{epoch + 1:02d}.pth"))
+                save(f"epoch_{epoch + 1:02d}")
         elif avg_loss < best_loss:
             best_loss = avg_loss
     return history

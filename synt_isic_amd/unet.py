@@ -89,6 +89,7 @@ class HipUNet2DModel:
         self._tape_input = None               # input of the last training-mode forward (the tape points into it)
         self._latency_mode = False
         self._params_stale = False            # the library's weights have moved on (optimizer steps) since _params was read
+        self._ema_swapped = False             # inside HipEMA.average_parameters(): the library holds the averaged weights
 
     # ------------------------------------------------------------------ nn.Module surface
     @property
@@ -164,16 +165,20 @@ class HipUNet2DModel:
         optimizer tests that choose their own gradients instead of running a backward pass."""
         if not self._train_begun:
             raise RuntimeError("no gradient arena: create a HipAdam for this model first")
+        self._write_all(1, mapping, "set_grads")
+
+    def _write_all(self, what: int, mapping: Dict[str, torch.Tensor], label: str) -> None:
+        """{name: tensor} into one of the library's training arenas: 1 gradient, 2 / 3 Adam moments, 4 EMA"""
         lib = _lib.load()
         h = self.handle
         index = {lib.sisic_unet_tensor_name(h, i).decode(): i for i in range(lib.sisic_unet_num_tensors(h))}
         for name, t in mapping.items():
             if name not in self._spec:
-                raise KeyError(f"set_grads: no parameter named {name}")
+                raise KeyError(f"{label}: no parameter named {name}")
             if tuple(t.shape) != tuple(self._spec[name]):
-                raise RuntimeError(f"set_grads: size mismatch for {name}: {tuple(t.shape)} vs {tuple(self._spec[name])}")
+                raise RuntimeError(f"{label}: size mismatch for {name}: {tuple(t.shape)} vs {tuple(self._spec[name])}")
             host = t.detach().to("cpu", torch.float32).contiguous()
-            check(lib.sisic_unet_write(h, 1, index[name], C.cast(host.data_ptr(), _lib.c_float_p), host.numel()))
+            check(lib.sisic_unet_write(h, what, index[name], C.cast(host.data_ptr(), _lib.c_float_p), host.numel()))
 
     def optimizer_state(self) -> Dict[str, "OrderedDict[str, torch.Tensor]"]:
         return {"exp_avg": self._read_all(2), "exp_avg_sq": self._read_all(3),
@@ -193,6 +198,9 @@ class HipUNet2DModel:
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         """Strict load of a flat ``{name: tensor}`` dict with diffusers key names."""
+        if self._ema_swapped:
+            raise RuntimeError("load_state_dict inside HipEMA.average_parameters(): the trained weights are swapped out and "
+                               "would overwrite the loaded ones on exit")
         sd = normalize_state_dict_keys(dict(state_dict))
         missing = [k for k in self._spec if k not in sd]
         unexpected = [k for k in sd if k not in self._spec]
