@@ -264,6 +264,15 @@ typedef struct sisic_unet_config {
 } sisic_unet_config;
 
 int sisic_unet_create(sisic_ctx*, const sisic_unet_config* cfg, sisic_unet** out);
+/* The class-conditional UNet2DModel(num_class_embeds = N): one more tensor, class_embedding.weight [N, 4 *
+ * block_out_channels[0]], directly after time_embedding.linear_2.bias in the state dict (diffusers registers class_embedding
+ * between time_embedding and down_blocks), in the parameter, gradient, Adam and EMA arenas like every other.  Row
+ * class_labels[b] is added to the time embedding of sample b before its SiLU.  num_class_embeds == 0 is sisic_unet_create.
+ * A conditional handle is driven through the *_cond entry points; on it sisic_unet_forward, sisic_unet_train_forward,
+ * sisic_unet_train_step[_ext] and the sisic_sample* loops return SISIC_EINVAL, as the *_cond entry points do on an
+ * unconditional handle.  Classifier-free guidance keeps its "null" class as one more row: build the model with
+ * n_classes + 1 rows.                                                                                                    */
+int sisic_unet_create_cond(sisic_ctx*, const sisic_unet_config* cfg, int num_class_embeds, sisic_unet** out);
 int sisic_unet_destroy(sisic_unet*);
 /* number / names of the tensors load expects (diffusers state_dict key order) */
 int sisic_unet_num_tensors(const sisic_unet*);
@@ -287,6 +296,11 @@ int64_t sisic_unet_graph_builds(const sisic_unet*);
 /* eps = model(sample, timestep).sample.  timesteps: host int64 [B] (one per sample). */
 int sisic_unet_forward(sisic_unet*, const float* sample, const int64_t* timesteps,
                        float* out, int B, int H, int W, void* stream);
+/* eps = model(sample, timestep, class_labels).sample of a conditional handle.  class_labels: host int64 [B]; a label outside
+ * [0, num_class_embeds) is SISIC_EINVAL before anything is launched.  A sample's output bits depend on its own
+ * (timestep, label) alone, never on the rest of the batch.                                                               */
+int sisic_unet_forward_cond(sisic_unet*, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
+                            float* out, int B, int H, int W, void* stream);
 
 /* The whole reverse-diffusion loop (image_generator.py:395-403) on one stream:
  *   for i in 0..T-1:  eps = unet(x, t[i]);  x = ddpm_step(eps, x, z[i], coef[i])
@@ -371,6 +385,35 @@ int sisic_sample_frames_rule_rng(sisic_unet*, float* x, int B, int H, int W, int
                                  float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel,
                                  int* steps_done, void* stream);
 
+/* ---- class-conditional sampling and classifier-free guidance (Ho & Salimans 2022) ---------------------------------------
+ * sisic_sample_frames_rule / _rule_rng for a conditional handle (sisic_unet_create_cond).  seeds == NULL: host-noise mode
+ * (noise: a buffer or NULL, as in sisic_sample_frames_rule); otherwise device noise (noise must be NULL; seeds, step0 as in
+ * sisic_sample_frames_rule_rng).  class_labels: host int64 [B], one label per image, each in [0, num_class_embeds).
+ *   guidance_scale == 1:  one UNet pass per step at batch B under the given labels; null_label is not read.  This is plain
+ *                         conditional sampling, and bit-identical to a guided run whose unconditional half is ignored.
+ *   any other scale w:    each step runs the UNet ONCE at batch 2B, the B images under their labels first, the same B images
+ *                         under null_label second, and the step rule is applied to
+ *                             eps = eps_u + w * (eps_c - eps_u)
+ *                         formed inside the step kernel in fp32 in exactly that order (subtract, multiply, add; no FMA
+ *                         contraction).  The kernel writes the new x to both halves of a [2B] buffer the handle owns, so the
+ *                         next pass needs no copy.  x, the noise rows, the Philox indexing, the DPM-Solver++ history, traj and
+ *                         out_u8 stay B images wide.  w == 0 is the unconditional model at the cost of a guided step: pass
+ *                         null labels at scale 1 instead.
+ * Before the loop the projected embeddings of every (step, distinct label of the call) are computed in one batch; each row on
+ * its own, so an image's result depends on its own (x, seed, label) alone and not on the batch it is in.  In graph mode a
+ * captured step serves every label list and every w (they live in device tables); what changes its launches is part of its
+ * key: conditional or not, guided or not (a call at w == 1 after one at w != 1 re-captures, and the other way round), and the
+ * buffers -- the embedding table grows with T x distinct labels beyond 1000 rows and never shrinks.  As in the unconditional
+ * loops, x holds the latent after the steps that ran under every exit, a cancelled run (SISIC_ECANCEL) included.         */
+int sisic_sample_frames_cond(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                             float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
+                             const int64_t* class_labels, int null_label, float guidance_scale, float* traj,
+                             const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream);
+/* out = eps_u + w * (eps_c - eps_u) over n floats with the device function the guided step kernels call (parity-test
+ * surface: a caller's own loop over two sisic_unet_forward_cond passes, this and a sisic_*_step reproduces the guided loop
+ * bit for bit).  Any alignment, any n >= 1; out may be either input.                                                      */
+int sisic_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream);
+
 /* ---- training step (diffusion/train_diffusion.py:201-266) -----------------------------------
  * fp32 throughout.  The reference wraps the forward in torch.cuda.amp.autocast() (fp16 matmuls/convolutions) and scales the
  * loss with a GradScaler; here the GradScaler PROTOCOL is implemented (loss_scale multiplies d loss, the optimizer step
@@ -392,6 +435,11 @@ int sisic_add_noise(sisic_ctx*, const float* x0, const float* noise, const float
  * pass takes (136x136 trains, 144x144 does not; inference has no such limit).                                         */
 int sisic_unet_train_forward(sisic_unet*, const float* sample, const int64_t* timesteps, float* out, int B, int H, int W,
                              void* stream);
+/* The same for a conditional handle; the labels (host int64 [B]) are kept with the tape.  sisic_unet_backward then also fills
+ * the gradient of class_embedding.weight: row k is the sum, in ascending sample order and without atomics, of the embedding
+ * gradients of the samples labelled k; the row of a label absent from the batch is written as zero.                     */
+int sisic_unet_train_forward_cond(sisic_unet*, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
+                                  float* out, int B, int H, int W, void* stream);
 /* F.mse_loss(pred, target) (train_diffusion.py:219): loss_dev[0] = mean((pred - target)^2) (NULL: kept internally),
  * dpred = grad_scale * 2 (pred - target) / n (NULL: loss only).  Fixed-order reduction.                               */
 int sisic_mse_loss(sisic_unet*, const float* pred, const float* target, int64_t n, float grad_scale, float* loss_dev,
@@ -441,6 +489,13 @@ int sisic_unet_train_step_ext(sisic_unet*, const float* images, const float* noi
                               const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
                               double beta1, double beta2, double eps, float loss_scale, const sisic_optim_ext* ext,
                               float* loss_out, int* found_inf, float* grad_norm_out, void* stream);
+/* sisic_unet_train_step_ext for a conditional handle: its arguments plus class_labels (host int64 [B]).  ext == NULL is the
+ * plain step of sisic_unet_train_step (no statistics pass; grad_norm_out is not written).                              */
+int sisic_unet_train_step_cond(sisic_unet*, const float* images, const float* noise, const int64_t* timesteps,
+                               const int64_t* class_labels, const float* sqrt_alpha_prod,
+                               const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr, double beta1, double beta2,
+                               double eps, float loss_scale, const sisic_optim_ext* ext, float* loss_out, int* found_inf,
+                               float* grad_norm_out, void* stream);
 /* The EMA arena.  ema_begin (after train_begin) allocates it and copies the current weights into it (EMAModel.__init__;
  * called again: copies again); train_end frees it.  ema_step is EMAModel.step on its own, for an EMA kept beside
  * sisic_unet_optimizer_step.  ema_swap exchanges the EMA with the trained weights and rebuilds every packed form, so that

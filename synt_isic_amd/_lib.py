@@ -118,6 +118,7 @@ SIGNATURES = {
     "sisic_denorm_u8_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p]),
     "sisic_unet_create": (C.c_int, [C.c_void_p, C.POINTER(UNetConfigC), C.POINTER(C.c_void_p)]),
+    "sisic_unet_create_cond": (C.c_int, [C.c_void_p, C.POINTER(UNetConfigC), C.c_int, C.POINTER(C.c_void_p)]),
     "sisic_unet_destroy": (C.c_int, [C.c_void_p]),
     "sisic_unet_num_tensors": (C.c_int, [C.c_void_p]),
     "sisic_unet_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),
@@ -127,6 +128,8 @@ SIGNATURES = {
     "sisic_unet_graph_builds": (C.c_int64, [C.c_void_p]),
     "sisic_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, c_int64_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p]),
+    "sisic_unet_forward_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int64_p, c_int64_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
     "sisic_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                C.c_void_p]),
@@ -160,12 +163,19 @@ SIGNATURES = {
                                                c_float_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int,
                                                C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
                                                C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_sample_frames_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
+                                           C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, c_int64_p,
+                                           C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "sisic_guide_eps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "sisic_unet_train_begin": (C.c_int, [C.c_void_p]),
     "sisic_unet_train_end": (C.c_int, [C.c_void_p]),
     "sisic_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_int64, C.c_void_p]),
     "sisic_unet_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, c_int64_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p]),
+    "sisic_unet_train_forward_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int64_p, c_int64_p, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_int, C.c_void_p]),
     "sisic_mse_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "sisic_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -181,6 +191,10 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
                                             C.POINTER(OptimExt), C.POINTER(C.c_float), C.POINTER(C.c_int),
                                             C.POINTER(C.c_float), C.c_void_p]),
+    "sisic_unet_train_step_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int64_p, c_int64_p, c_float_p, c_float_p,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                             C.c_float, C.POINTER(OptimExt), C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_float), C.c_void_p]),
     "sisic_unet_ema_begin": (C.c_int, [C.c_void_p]),
     "sisic_unet_ema_step": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "sisic_unet_ema_swap": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -7,7 +7,8 @@ up=(Up,AttnUp,Up,Up))``).  This module turns that configuration into
 
   * the ordered ``{name: shape}`` table of the 330 checkpoint tensors
     (diffusers key names) -- the format a strict
-    ``load_state_dict`` expects (model_manager.py:135-143);
+    ``load_state_dict`` expects (model_manager.py:135-143); 331 with the
+    ``class_embedding.weight`` of a class-conditional model (``num_class_embeds``);
   * the flat list of layer records the HIP library is configured with.
 """
 from __future__ import annotations
@@ -15,7 +16,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 
 @dataclass(frozen=True)
@@ -31,6 +32,7 @@ class UNetConfig:
     norm_eps: float = 1e-5
     attention_head_dim: int = 8
     class_embed_type: None = None
+    num_class_embeds: Optional[int] = None      # N: class_embedding = nn.Embedding(N, time_embed_dim); None: unconditional
 
     @property
     def time_embed_dim(self) -> int:
@@ -57,6 +59,9 @@ class UNetConfig:
         for c in self.block_out_channels:
             if c % self.norm_num_groups:
                 raise ValueError("channels must be divisible by norm_num_groups")
+        if self.num_class_embeds is not None and (isinstance(self.num_class_embeds, bool) or
+                                                  not isinstance(self.num_class_embeds, int) or self.num_class_embeds < 1):
+            raise ValueError(f"num_class_embeds must be None or a positive int, got {self.num_class_embeds!r}")
 
 
 @dataclass
@@ -102,6 +107,11 @@ def unet_param_spec(cfg: UNetConfig = UNetConfig()) -> "OrderedDict[str, Tuple[i
     conv("conv_in", boc[0], cfg.in_channels, 3)
     linear("time_embedding.linear_1", temb, boc[0])
     linear("time_embedding.linear_2", temb, temb)
+    # diffusers is not a dependency here, so for the record: UNet2DModel.__init__ registers conv_in, time_proj (no tensors),
+    # time_embedding, class_embedding, down_blocks, mid_block, up_blocks, ... in that order, so the embedding table of a
+    # conditional model sits directly after time_embedding.linear_2.bias in its state dict
+    if cfg.num_class_embeds is not None:
+        spec["class_embedding.weight"] = (cfg.num_class_embeds, temb)
     out_ch = boc[0]
     for i, ch in enumerate(boc):
         in_ch, out_ch = out_ch, ch

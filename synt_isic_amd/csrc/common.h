@@ -227,14 +227,32 @@ int launch_dpm_step_indexed(sisic_ctx*, const float* eps, float* x, float* hist,
                             const float* coef, const int* zrow, float clip, hipStream_t s);
 int launch_dpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
                                 const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
+// classifier-free guidance (elementwise.hip): the same rules on eps = eps_u + w * (eps_c - eps_u), formed in the step kernel; the
+// new x goes to both halves of out [2n].  seeds_dev NULL: z is a buffer (or NULL); else generated noise.  row: the rule's host
+// row (SISIC_RULE_ROW_WIDTH floats).  hist: DPM-Solver++ only.  The indexed form reads w from cond[0] (LoopCond).
+int launch_step_guided(sisic_ctx*, int rule, int flags, const float* eps_c, const float* eps_u, float w, const float* x,
+                       const float* z, const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out,
+                       int64_t n, const float* row, float clip, hipStream_t s);
+int launch_step_guided_indexed(sisic_ctx*, int rule, int flags, const float* eps2, float* x2, float* hist, int64_t n,
+                               int64_t n_per_image, const void* state, const float* coef, const int* zrow,
+                               const uint64_t* seeds_dev, const float* cond, float clip, hipStream_t s);
+int launch_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s);
+// conditional loop: out[b][r] = table[(step * L + slot[b]) * R + r] for the `rows` samples of a pass; cond: LoopCond
+// {w, L, -, -, slot[rows]}; state != NULL: the step index is the loop state's (graph-replayed form)
+constexpr size_t LOOP_COND_HEAD = 4;
+int launch_loop_gather_rows(sisic_ctx*, const float* table, int R, const void* state, int step, const float* cond, int rows,
+                            float* out, hipStream_t s);
 int launch_noise_fill(sisic_ctx*, void* out, int B, int64_t n_per_image, const uint64_t* seeds_host, uint32_t step,
                       uint32_t tag, bool bits, hipStream_t s);
 int launch_denorm_u8(sisic_ctx*, const float* x, uint8_t* out, int B, int C, int H, int W, hipStream_t s, int form = 0);
 // time embedding: sinusoid -> linear1 -> SiLU -> linear2 -> SiLU  (weights transposed [in][out])
 // save_* (optional, training): the sinusoid [B, 2 n_freqs] and the two linear outputs before their SiLU [B, hidden]
+// class_table [N, hidden] with labels (device int [B], each in [0, N): the caller checks), both or neither: the class
+// embedding's row is added to linear_2's output before its SiLU (and save_t2 holds the sum)
 int launch_temb_mlp(sisic_ctx*, const float* t_vals, int B, const float* freqs, int n_freqs, const float* w1t,
                     const float* b1, const float* w2t, const float* b2, int hidden, float* temb_act, hipStream_t s,
-                    float* save_emb = nullptr, float* save_h1 = nullptr, float* save_t2 = nullptr);
+                    float* save_emb = nullptr, float* save_h1 = nullptr, float* save_t2 = nullptr,
+                    const float* class_table = nullptr, const int* labels = nullptr);
 // out[b, r] = sum_k wt[k][r] * x[b][k] + bias[r]
 int launch_linear_t(sisic_ctx*, const float* x, int B, int K, const float* wt, const float* bias, int R,
                     float* out, hipStream_t s);

@@ -86,20 +86,50 @@ struct PhiloxNoise {
     }
 };
 
+// Where a step's eps comes from: the UNet's output as it stands, or (classifier-free guidance) combined from the conditional
+// and the unconditional prediction of one pass at twice the batch.  The rule sees one eps either way.
+struct PlainEps {
+    const float* __restrict__ e;
+    static constexpr bool dup = false;
+    __device__ __forceinline__ float4 get4(int64_t i4) const { return reinterpret_cast<const float4*>(e)[i4]; }
+    __device__ __forceinline__ float get1(int64_t i) const { return e[i]; }
+};
+
+// eps = eps_u + w * (eps_c - eps_u): subtract, multiply, add, each rounded to fp32 (what sisic_guide_eps computes)
+__device__ __forceinline__ float guide_one(float c, float u, float w) {
+#pragma clang fp contract(off)
+    const float d = c - u;
+    const float t = w * d;
+    return u + t;
+}
+
+// dup: the step's result goes to out AND out + n, the two halves of the [2B] latent buffer the next pass reads
+struct GuidedEps {
+    const float* __restrict__ ec;
+    const float* __restrict__ eu;
+    float w;
+    static constexpr bool dup = true;
+    __device__ __forceinline__ float4 get4(int64_t i4) const {
+        const float4 c = reinterpret_cast<const float4*>(ec)[i4], u = reinterpret_cast<const float4*>(eu)[i4];
+        return make_float4(guide_one(c.x, u.x, w), guide_one(c.y, u.y, w), guide_one(c.z, u.z, w), guide_one(c.w, u.w, w));
+    }
+    __device__ __forceinline__ float get1(int64_t i) const { return guide_one(ec[i], eu[i], w); }
+};
+
 // out may alias x (the loop steps in place): every element is read before it is written, by the thread that writes it
-template <class R, class Z>
-__device__ __forceinline__ void step_body(const float* __restrict__ eps, const float* x, float* out, int64_t n, bool vec4,
+// (E::dup: vec4 only with n a multiple of 4, so that out + n is aligned like out)
+template <class R, class Z, class E>
+__device__ __forceinline__ void step_body(const E es, const float* x, float* out, int64_t n, bool vec4,
                                           const R rule, const Z zs) {
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (vec4) {
         const int64_t n4 = n >> 2;
-        const float4* e4 = reinterpret_cast<const float4*>(eps);
         const float4* x4 = reinterpret_cast<const float4*>(x);
         float4* o4 = reinterpret_cast<float4*>(out);
         for (int64_t i = t0; i < n4; i += stride) {
-            const float4 e = e4[i], xv = x4[i];
+            const float4 e = es.get4(i), xv = x4[i];
             float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (noise) zv = zs.get4(i);
             float4 r;
@@ -108,10 +138,19 @@ __device__ __forceinline__ void step_body(const float* __restrict__ eps, const f
             r.z = rule(e.z, xv.z, zv.z, noise);
             r.w = rule(e.w, xv.w, zv.w, noise);
             o4[i] = r;
+            if constexpr (E::dup) o4[n4 + i] = r;
         }
-        for (int64_t i = (n4 << 2) + t0; i < n; i += stride) out[i] = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, noise);
+        for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
+            const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            out[i] = r;
+            if constexpr (E::dup) out[n + i] = r;
+        }
     } else {
-        for (int64_t i = t0; i < n; i += stride) out[i] = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, noise);
+        for (int64_t i = t0; i < n; i += stride) {
+            const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            out[i] = r;
+            if constexpr (E::dup) out[n + i] = r;
+        }
     }
 }
 
@@ -119,7 +158,7 @@ __global__ void __launch_bounds__(256)
 ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
                  float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
                  int vec4) {
-    step_body(eps, x, out, n, vec4 != 0, DdpmRule{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdpmRule{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
 }
 
 // the same step with z generated in the kernel (sisic_sample_frames_rng, eager form)
@@ -128,7 +167,7 @@ ddpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, 
                      const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
                      float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(eps, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule{sb, sa, c0, c1, sigma, clip}, zs);
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule{sb, sa, c0, c1, sigma, clip}, zs);
 }
 
 // the DDIM rule in the same two forms
@@ -136,7 +175,7 @@ template <bool CLIPPED>
 __global__ void __launch_bounds__(256)
 ddim_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* out, int64_t n, float sb,
                  float sa, float c_prev, float c_dir, float sigma, float clip, int vec4) {
-    step_body(eps, x, out, n, vec4 != 0, DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
 }
 
 template <bool CLIPPED>
@@ -145,7 +184,7 @@ ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, 
                      const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c_prev, float c_dir,
                      float sigma, float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(eps, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
 }
 
 // ---- DPM-Solver++(2M) step -------------------------------------------------------------
@@ -170,9 +209,9 @@ struct DpmRule {
     }
 };
 
-// step_body with the history stream.  out may alias x; hist aliases nothing else.
-template <class Z>
-__device__ __forceinline__ void dpm_step_body(const float* __restrict__ eps, const float* x, float* hist, float* out, int64_t n,
+// step_body with the history stream.  out may alias x; hist aliases nothing else (and stays n wide under E::dup).
+template <class Z, class E>
+__device__ __forceinline__ void dpm_step_body(const E es, const float* x, float* hist, float* out, int64_t n,
                                               bool vec4, const DpmRule rule, const Z zs) {
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const bool second = rule.k1 != 0.0f;
@@ -181,12 +220,11 @@ __device__ __forceinline__ void dpm_step_body(const float* __restrict__ eps, con
     int64_t tail = t0;
     if (vec4) {
         const int64_t n4 = n >> 2;
-        const float4* e4 = reinterpret_cast<const float4*>(eps);
         const float4* x4 = reinterpret_cast<const float4*>(x);
         float4* h4 = reinterpret_cast<float4*>(hist);
         float4* o4 = reinterpret_cast<float4*>(out);
         for (int64_t i = t0; i < n4; i += stride) {
-            const float4 e = e4[i], xv = x4[i];
+            const float4 e = es.get4(i), xv = x4[i];
             float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), zv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (second) hv = h4[i];
             if (noise) zv = zs.get4(i);
@@ -197,21 +235,23 @@ __device__ __forceinline__ void dpm_step_body(const float* __restrict__ eps, con
             r.w = rule(e.w, xv.w, zv.w, hv.w, noise, second, m.w);
             h4[i] = m;
             o4[i] = r;
+            if constexpr (E::dup) o4[n4 + i] = r;
         }
         tail = (n4 << 2) + t0;
     }
     for (int64_t i = tail; i < n; i += stride) {
         float m;
-        const float r = rule(eps[i], x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
+        const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
         hist[i] = m;
         out[i] = r;
+        if constexpr (E::dup) out[n + i] = r;
     }
 }
 
 __global__ void __launch_bounds__(256)
 dpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* hist, float* out, int64_t n,
                 float sb, float sa, float cx, float k0, float sigma, float k1, float clip, int vec4) {
-    dpm_step_body(eps, x, hist, out, n, vec4 != 0, DpmRule{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
+    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0, DpmRule{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
 }
 
 __global__ void __launch_bounds__(256)
@@ -219,7 +259,7 @@ dpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* hist, 
                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float cx, float k0, float sigma,
                     float k1, float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    dpm_step_body(eps, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule{sb, sa, cx, k0, sigma, k1, clip}, zs);
+    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule{sb, sa, cx, k0, sigma, k1, clip}, zs);
 }
 
 static const char* rule_name(int rule) {
@@ -364,7 +404,7 @@ __device__ __forceinline__ void step_indexed_body(const float* __restrict__ eps,
     const int step = st->step;
     const int zr = zrow[step];
     const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    step_body(eps, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+    step_body(PlainEps{eps}, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
 }
 
 template <class R>
@@ -373,7 +413,7 @@ __device__ __forceinline__ void step_indexed_rng_body(const float* __restrict__ 
                                                       const uint64_t* __restrict__ seeds, float clip, int vec4) {
     const int step = st->step;
     const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    step_body(eps, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+    step_body(PlainEps{eps}, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
 }
 
 __global__ void __launch_bounds__(256)
@@ -416,7 +456,7 @@ dpm_step_indexed_kernel(const float* __restrict__ eps, float* x, float* hist, in
     const int step = st->step;
     const int zr = zrow[step];
     const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    dpm_step_body(eps, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
 }
 
 __global__ void __launch_bounds__(256)
@@ -425,7 +465,7 @@ dpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, float* hist
                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
     const int step = st->step;
     const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    dpm_step_body(eps, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
 }
 
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
@@ -523,6 +563,205 @@ int launch_dpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, floa
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
     hipLaunchKernelGGL(dpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, n, n_per_image,
                        static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// ---- classifier-free guidance: the same steps reading eps through GuidedEps --------------------------------------------------
+// One UNet pass at batch 2B leaves the conditional predictions in the first n floats of eps2 and the null-label ones in the
+// second n; the step applies its rule to guide_one() of the two and writes the new x to both halves of x2 [2n].  z, the seeds,
+// the history and n are those of the B images.  NZ: 0 a noise buffer, 1 generated noise.  The eager kernels take w and the row
+// as launch arguments; the indexed ones read the row by the loop's step index and w from cond[0] (LoopCond, below), so that a
+// captured step replays under another scale.
+struct StepRow { float v[6]; };     // a rule's row: {sb, sa, c2, c3, sigma} or DPM-Solver++'s six
+
+template <class R>
+__device__ __forceinline__ R row_rule(const StepRow& r, float clip) { return R{r.v[0], r.v[1], r.v[2], r.v[3], r.v[4], clip}; }
+
+template <class R, int NZ>
+__global__ void __launch_bounds__(256)
+step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float w, const float* x, const float* __restrict__ z,
+                   const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* out, int64_t n, StepRow row,
+                   float clip, int vec4) {
+    const GuidedEps es{ec, eu, w};
+    if constexpr (NZ == 0) {
+        step_body(es, x, out, n, vec4 != 0, row_rule<R>(row, clip), BufferNoise{z});
+    } else {
+        const PhiloxNoise zs{seeds, n_per_image, step};
+        step_body(es, x, out, n, vec4 != 0 && zs.vec_ok(), row_rule<R>(row, clip), zs);
+    }
+}
+
+template <int NZ>
+__global__ void __launch_bounds__(256)
+dpm_step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float w, const float* x,
+                       const float* __restrict__ z, const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step,
+                       float* hist, float* out, int64_t n, StepRow row, float clip, int vec4) {
+    const GuidedEps es{ec, eu, w};
+    const DpmRule rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
+    if constexpr (NZ == 0) {
+        dpm_step_body(es, x, hist, out, n, vec4 != 0, rule, BufferNoise{z});
+    } else {
+        const PhiloxNoise zs{seeds, n_per_image, step};
+        dpm_step_body(es, x, hist, out, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+    }
+}
+
+template <class R, int NZ>
+__global__ void __launch_bounds__(256)
+step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, int64_t n, int64_t n_per_image,
+                           const LoopState* __restrict__ st, const float* __restrict__ coef, const int* __restrict__ zrow,
+                           const uint64_t* __restrict__ seeds, const float* __restrict__ cond, float clip, int vec4) {
+    const int step = st->step;
+    const GuidedEps es{eps2, eps2 + n, cond[0]};
+    if constexpr (NZ == 0) {
+        const int zr = zrow[step];
+        const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
+        step_body(es, x2, x2, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+    } else {
+        const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+        step_body(es, x2, x2, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
+    }
+}
+
+template <int NZ>
+__global__ void __launch_bounds__(256)
+dpm_step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, float* hist, int64_t n, int64_t n_per_image,
+                               const LoopState* __restrict__ st, const float* __restrict__ coef, const int* __restrict__ zrow,
+                               const uint64_t* __restrict__ seeds, const float* __restrict__ cond, float clip, int vec4) {
+    const int step = st->step;
+    const GuidedEps es{eps2, eps2 + n, cond[0]};
+    if constexpr (NZ == 0) {
+        const int zr = zrow[step];
+        const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
+        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    } else {
+        const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    }
+}
+
+// z != NULL or seeds_dev == NULL: the noise buffer (or none); seeds_dev: generated noise.  row: the rule's host row.
+// out: [2n] (may be x's own buffer: x is its first n floats); hist: DPM-Solver++ only.
+int launch_step_guided(sisic_ctx* ctx, int rule, int flags, const float* eps_c, const float* eps_u, float w, const float* x,
+                       const float* z, const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out,
+                       int64_t n, const float* row, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps_c && eps_u && x && out && row && n > 0, "%s (guided): null tensor or empty", rule_name(rule));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps_c && hist != eps_u),
+                  "dpmpp_step (guided): the history is missing or aliases another tensor");
+    SISIC_REQUIRE(!seeds_dev || (n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0),
+                  "%s (guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
+    SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
+    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
+    StepRow r{};
+    for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) r.v[k] = row[k];
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps_c) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(x) |
+                         reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0 && (n & 3) == 0 && (!seeds_dev || (n_per_image & 3) == 0);
+    const int64_t work = vec4 ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
+#define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, out, n, r, clip, vec4)
+    if (rule == STEP_RULE_DPMPP) {
+        if (seeds_dev) hipLaunchKernelGGL(dpm_step_guided_kernel<1>, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
+        else hipLaunchKernelGGL(dpm_step_guided_kernel<0>, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
+    } else if (rule == STEP_RULE_DDPM) {
+        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdpmRule, 1>)); else SISIC_GUIDED((step_guided_kernel<DdpmRule, 0>));
+    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<true>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<true>, 0>));
+    } else {
+        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<false>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<false>, 0>));
+    }
+#undef SISIC_GUIDED
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// the graph-replayed form: eps2 [2n] and x2 [2n] are the loop's own buffers, zrow the buffer-noise rows (seeds_dev NULL) or
+// unused (generated noise), cond the loop's LoopCond table (w at cond[0])
+int launch_step_guided_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps2, float* x2, float* hist, int64_t n,
+                               int64_t n_per_image, const void* state, const float* coef, const int* zrow,
+                               const uint64_t* seeds_dev, const float* cond, float clip, hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(eps2 && x2 && state && coef && cond && (zrow || seeds_dev) && n > 0, "%s_indexed (guided): null argument", rule_name(rule));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || hist, "dpmpp_step_indexed (guided): no history buffer");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "%s_indexed (guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
+    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(hist);
+    const int vec4 = (al & 15) == 0 && (n & 3) == 0 && (!seeds_dev || (n_per_image & 3) == 0);
+    const int64_t work = vec4 ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
+    const LoopState* st = static_cast<const LoopState*>(state);
+#define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps2, x2, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4)
+    if (rule == STEP_RULE_DPMPP) {
+        if (seeds_dev) hipLaunchKernelGGL(dpm_step_guided_indexed_kernel<1>, grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
+        else hipLaunchKernelGGL(dpm_step_guided_indexed_kernel<0>, grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
+    } else if (rule == STEP_RULE_DDPM) {
+        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule, 0>));
+    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true>, 0>));
+    } else {
+        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 0>));
+    }
+#undef SISIC_GUIDED
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// the combine alone (sisic_guide_eps): guide_one() on every element, any alignment; out may be either input
+__global__ void __launch_bounds__(256)
+guide_eps_kernel(const float* eps_c, const float* eps_u, float w, float* out, int64_t n, int vec4) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // (plain pointers, not the restrict-qualified GuidedEps: out may be one of the inputs; a thread reads its elements first)
+    int64_t tail = t0;
+    if (vec4) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = t0; i < n4; i += stride) {
+            const float4 c = reinterpret_cast<const float4*>(eps_c)[i], u = reinterpret_cast<const float4*>(eps_u)[i];
+            reinterpret_cast<float4*>(out)[i] = make_float4(guide_one(c.x, u.x, w), guide_one(c.y, u.y, w), guide_one(c.z, u.z, w),
+                                                            guide_one(c.w, u.w, w));
+        }
+        tail = (n4 << 2) + t0;
+    }
+    for (int64_t i = tail; i < n; i += stride) out[i] = guide_one(eps_c[i], eps_u[i], w);
+}
+
+int launch_guide_eps(sisic_ctx* ctx, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s) {
+    SISIC_REQUIRE(eps_c && eps_u && out && n > 0, "guide_eps: null tensor or empty");
+    ProfileScope prof(ctx, s, PK_OTHER, 12.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps_c) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0;
+    const int64_t work = vec4 ? (n + 3) / 4 : n;
+    hipLaunchKernelGGL(guide_eps_kernel, dim3((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), dim3(256), 0, s, eps_c, eps_u,
+                       w, out, n, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// ---- per-sample embedding rows of a conditional loop ---------------------------------------------------------------------------
+// LoopCond, the loop's device table of a conditional call, as floats: [0] w (guidance scale), [1] L (int: distinct labels of the
+// call, the null one included), [2], [3] unused, [4 + b] slot of sample b (int, < L) for the B or 2B samples of a pass.
+// table holds the projected embedding of (step i, slot j) in row i * L + j; sample b of the pass gets its row:
+//     out[b][r] = table[(step * L + slot[b]) * R + r]
+// st != NULL: the step index comes from the loop state (graph-replayed form), else from the argument.
+__global__ void __launch_bounds__(256)
+loop_gather_rows_kernel(const float* __restrict__ table, int R, const LoopState* __restrict__ st, int step,
+                        const float* __restrict__ cond, float* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (r >= R) return;
+    const int* ci = reinterpret_cast<const int*>(cond);
+    const int i = st ? st->step : step;
+    out[(size_t)b * R + r] = table[((size_t)i * ci[1] + ci[4 + b]) * R + r];
+}
+
+int launch_loop_gather_rows(sisic_ctx*, const float* table, int R, const void* state, int step, const float* cond, int rows,
+                            float* out, hipStream_t s) {
+    SISIC_REQUIRE(table && cond && out && R > 0 && rows > 0 && rows <= 65535, "loop_gather_rows: bad arguments");
+    hipLaunchKernelGGL(loop_gather_rows_kernel, dim3(cdiv(R, 256), rows), dim3(256), 0, s, table, R,
+                       static_cast<const LoopState*>(state), step, cond, out);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -636,16 +875,20 @@ int launch_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C,
 __device__ __forceinline__ float silu_acc(float v) { return v / (1.0f + expf(-v)); }
 
 // one workgroup per sample; hidden <= 1024; weights stored transposed [in][hidden]
+// class_table / labels (both or neither): row labels[b] of the class embedding [N, hidden] is added to linear_2's output, one
+// fp32 add, before the SiLU (UNet2DModel: emb = time_embedding(t_emb) + class_embedding(class_labels)); save_t2 keeps the sum
 __global__ void __launch_bounds__(256)
 temb_mlp_kernel(const float* __restrict__ t_vals, const float* __restrict__ freqs, int n_freqs,
                 const float* __restrict__ w1t, const float* __restrict__ b1, const float* __restrict__ w2t,
                 const float* __restrict__ b2, int hidden, float* __restrict__ temb_act, float* __restrict__ save_emb,
-                float* __restrict__ save_h1, float* __restrict__ save_t2) {
+                float* __restrict__ save_h1, float* __restrict__ save_t2, const float* __restrict__ class_table,
+                const int* __restrict__ labels) {
     __shared__ float e[256];
     __shared__ float h[1024];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float t = t_vals[b];
     const int nin = 2 * n_freqs;
+    const float* crow = class_table ? class_table + (size_t)labels[b] * hidden : nullptr;
     for (int k = tid; k < nin; k += blockDim.x) {
         const float arg = t * freqs[k % n_freqs];
         e[k] = (k < n_freqs) ? cosf(arg) : sinf(arg);   // flip_sin_to_cos=True: cos half first
@@ -662,18 +905,21 @@ temb_mlp_kernel(const float* __restrict__ t_vals, const float* __restrict__ freq
     for (int j = tid; j < hidden; j += blockDim.x) {
         float acc = 0.0f;
         for (int k = 0; k < hidden; ++k) acc += w2t[(size_t)k * hidden + j] * h[k];
-        temb_act[(size_t)b * hidden + j] = silu_acc(acc + b2[j]);
-        if (save_t2) save_t2[(size_t)b * hidden + j] = acc + b2[j];
+        float t2 = acc + b2[j];
+        if (crow) t2 = t2 + crow[j];
+        temb_act[(size_t)b * hidden + j] = silu_acc(t2);
+        if (save_t2) save_t2[(size_t)b * hidden + j] = t2;
     }
 }
 
 int launch_temb_mlp(sisic_ctx* ctx, const float* t_vals, int B, const float* freqs, int n_freqs, const float* w1t,
                     const float* b1, const float* w2t, const float* b2, int hidden, float* temb_act, hipStream_t s,
-                    float* save_emb, float* save_h1, float* save_t2) {
+                    float* save_emb, float* save_h1, float* save_t2, const float* class_table, const int* labels) {
     SISIC_REQUIRE(n_freqs > 0 && 2 * n_freqs <= 256 && hidden > 0 && hidden <= 1024, "temb_mlp: sizes unsupported");
+    SISIC_REQUIRE((class_table == nullptr) == (labels == nullptr), "temb_mlp: a class table goes with labels");
     ProfileScope prof(ctx, s, PK_OTHER, 0.0, 0.0);
     hipLaunchKernelGGL(temb_mlp_kernel, dim3(B), dim3(256), 0, s, t_vals, freqs, n_freqs, w1t, b1, w2t, b2, hidden,
-                       temb_act, save_emb, save_h1, save_t2);
+                       temb_act, save_emb, save_h1, save_t2, class_table, labels);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

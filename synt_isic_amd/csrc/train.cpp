@@ -270,6 +270,10 @@ struct Bwd {
         // d ta[b][k] = sum_r dtproj[b][r] * Wfused[r][k]; the fused weight is stored transposed: tproj_wt[k][r]
         SISIC_TRY(launch_linear_dgrad(u->ctx, tr->dtproj, R, u->tproj_wt, B, R, Hd, dta, s, /*w_is_transposed=*/1));
         SISIC_TRY(launch_silu_bwd(u->ctx, dta, tr->t2, (size_t)B * Hd, dt2, s));
+        // class embedding: t2 = linear_2(a1) + E[label], so row k of dE is the sum of dt2 over the samples labelled k
+        if (tr->has_labels)
+            SISIC_TRY(launch_class_embed_grad(u->ctx, dt2, reinterpret_cast<const int*>(tr->labels_dev), B, u->n_class, Hd,
+                                              grad_of(u, u->class_w), s));
         // linear_2: t2 = a1 W2^T + b2, a1 = silu(h1)
         SISIC_TRY(launch_silu_fwd(u->ctx, tr->h1, (size_t)B * Hd, a1, s));
         SISIC_TRY(launch_linear_wgrad(u->ctx, dt2, Hd, a1, B, Hd, Hd, grad_of(u, u->temb_w2), s));
@@ -350,8 +354,13 @@ int require_not_swapped(sisic_unet* u, const char* what) {
 }
 
 // the loop body of sisic_unet_train_step up to the optimizer step: add_noise, forward, MSE, backward, the loss read-back
-int train_step_body(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps, const float* sqrt_alpha_prod,
-                    const float* sqrt_one_minus_alpha_prod, int B, int H, int W, float loss_scale, float* loss_out, void* stream) {
+// class_labels: host int64 [B] of a conditional model, or nullptr
+int train_forward_impl(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels, float* out, int B,
+                       int H, int W, void* stream);
+
+int train_step_body(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps, const int64_t* class_labels,
+                    const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, float loss_scale,
+                    float* loss_out, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState* tr = u->train.get();
     const int C = u->cfg.in_channels;
@@ -368,13 +377,49 @@ int train_step_body(sisic_unet* u, const float* images, const float* noise, cons
     std::memcpy(coef.data() + B, sqrt_one_minus_alpha_prod, B * sizeof(float));
     SISIC_TRY(unet_stage_upload(u, coef.data(), 2 * (size_t)B, tr->small, s));
     SISIC_TRY(launch_add_noise(u->ctx, images, noise, tr->small, tr->small + B, noisy, B, (size_t)C * H * W, s));
-    SISIC_TRY(sisic_unet_train_forward(u, noisy, timesteps, pred, B, H, W, stream));
+    SISIC_TRY(train_forward_impl(u, noisy, timesteps, class_labels, pred, B, H, W, stream));
     SISIC_TRY(launch_mse(u->ctx, pred, noise, n, loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
     SISIC_TRY(sisic_unet_backward(u, dpred, stream));
     if (loss_out) {
         SISIC_HIP(hipMemcpyAsync(loss_out, tr->loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
         SISIC_HIP(hipStreamSynchronize(s));
     }
+    return SISIC_OK;
+}
+
+int train_forward_impl(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels, float* out, int B,
+                       int H, int W, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TrainState* tr = u->train.get();
+    unet_release_tape(u);                                  // a forward without a backward: drop the old tape
+    SISIC_TRY(unet_check_shape(u, B, H, W));
+    SISIC_TRY(check_trainable_resolution(u, H, W));
+    SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
+    const int Hd = u->hidden, nin = 2 * u->cfg.n_freqs;
+    SISIC_TRY(unet_grow(&tr->emb, &tr->emb_cap, (size_t)B * nin));
+    SISIC_TRY(unet_grow(&tr->h1, &tr->h1_cap, (size_t)B * Hd));
+    SISIC_TRY(unet_grow(&tr->t2, &tr->t2_cap, (size_t)B * Hd));
+    SISIC_TRY(unet_grow(&tr->dtproj, &tr->dtproj_cap, (size_t)B * u->tproj_R));
+    SISIC_TRY(unet_grow(&tr->small, &tr->small_cap, train_small_floats(u, B)));
+    std::vector<float> tv(B);
+    for (int b = 0; b < B; ++b) tv[b] = (float)timesteps[b];
+    SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)B, u->t_vals, s));
+    // the labels go on the tape: the backward pass sums the class embedding's gradient rows by them
+    tr->has_labels = class_labels != nullptr;
+    if (class_labels) SISIC_TRY(unet_upload_labels(u, class_labels, B, &tr->labels_dev, &tr->labels_cap, s));
+    // per-sample rows always (the training timesteps differ per image, train_diffusion.py:216), intermediates kept
+    SISIC_TRY(launch_temb_mlp(u->ctx, u->t_vals, B, u->d_freqs, u->cfg.n_freqs, u->w1t, u->rawp(u->temb_b1), u->w2t,
+                              u->rawp(u->temb_b2), Hd, u->temb_act, s, tr->emb, tr->h1, tr->t2,
+                              class_labels ? u->rawp(u->class_w) : nullptr,
+                              class_labels ? reinterpret_cast<const int*>(tr->labels_dev) : nullptr));
+    SISIC_TRY(launch_linear_t(u->ctx, u->temb_act, B, Hd, u->tproj_wt, u->tproj_b, u->tproj_R, u->tproj, s));
+    tr->B = B; tr->H = H; tr->W = W;
+    const int rc = unet_run_forward(u, sample, u->tproj, u->tproj_R, out, B, H, W, s, tr);
+    if (rc != SISIC_OK) {
+        unet_release_tape(u);
+        return rc;
+    }
+    tr->has_tape = true;
     return SISIC_OK;
 }
 
@@ -432,7 +477,7 @@ int sisic_unet_train_end(sisic_unet* u) {
     unet_release_tape(u);
     TrainState* tr = u->train.get();
     for (float* p : {tr->grad, tr->adam_m, tr->adam_v, tr->emb, tr->h1, tr->t2, tr->dtproj, tr->garena, tr->wgrad_part, tr->scratch,
-                     tr->small, tr->loss_dev, tr->mse_part, tr->ema})
+                     tr->small, tr->loss_dev, tr->mse_part, tr->ema, tr->labels_dev})
         if (p) (void)hipFree(p);
     if (tr->stats_dev) (void)hipFree(tr->stats_dev);
     if (tr->scatter_dev) (void)hipFree(tr->scatter_dev);
@@ -453,33 +498,16 @@ int sisic_unet_train_forward(sisic_unet* u, const float* sample, const int64_t* 
                              void* stream) {
     SISIC_TRY(require_train(u, "train_forward"));
     SISIC_REQUIRE(sample && timesteps && out, "train_forward: null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TrainState* tr = u->train.get();
-    unet_release_tape(u);                                  // a forward without a backward: drop the old tape
-    SISIC_TRY(unet_check_shape(u, B, H, W));
-    SISIC_TRY(check_trainable_resolution(u, H, W));
-    SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
-    const int Hd = u->hidden, nin = 2 * u->cfg.n_freqs;
-    SISIC_TRY(unet_grow(&tr->emb, &tr->emb_cap, (size_t)B * nin));
-    SISIC_TRY(unet_grow(&tr->h1, &tr->h1_cap, (size_t)B * Hd));
-    SISIC_TRY(unet_grow(&tr->t2, &tr->t2_cap, (size_t)B * Hd));
-    SISIC_TRY(unet_grow(&tr->dtproj, &tr->dtproj_cap, (size_t)B * u->tproj_R));
-    SISIC_TRY(unet_grow(&tr->small, &tr->small_cap, train_small_floats(u, B)));
-    std::vector<float> tv(B);
-    for (int b = 0; b < B; ++b) tv[b] = (float)timesteps[b];
-    SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)B, u->t_vals, s));
-    // per-sample rows always (the training timesteps differ per image, train_diffusion.py:216), intermediates kept
-    SISIC_TRY(launch_temb_mlp(u->ctx, u->t_vals, B, u->d_freqs, u->cfg.n_freqs, u->w1t, u->rawp(u->temb_b1), u->w2t,
-                              u->rawp(u->temb_b2), Hd, u->temb_act, s, tr->emb, tr->h1, tr->t2));
-    SISIC_TRY(launch_linear_t(u->ctx, u->temb_act, B, Hd, u->tproj_wt, u->tproj_b, u->tproj_R, u->tproj, s));
-    tr->B = B; tr->H = H; tr->W = W;
-    const int rc = unet_run_forward(u, sample, u->tproj, u->tproj_R, out, B, H, W, s, tr);
-    if (rc != SISIC_OK) {
-        unet_release_tape(u);
-        return rc;
-    }
-    tr->has_tape = true;
-    return SISIC_OK;
+    SISIC_TRY(unet_check_labels(u, "train_forward", false, nullptr, B));
+    return train_forward_impl(u, sample, timesteps, nullptr, out, B, H, W, stream);
+}
+
+int sisic_unet_train_forward_cond(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
+                                  float* out, int B, int H, int W, void* stream) {
+    SISIC_TRY(require_train(u, "train_forward_cond"));
+    SISIC_REQUIRE(sample && timesteps && out, "train_forward_cond: null argument");
+    SISIC_TRY(unet_check_labels(u, "train_forward_cond", true, class_labels, B));
+    return train_forward_impl(u, sample, timesteps, class_labels, out, B, H, W, stream);
 }
 
 int sisic_unet_backward(sisic_unet* u, const float* dout, void* stream) {
@@ -584,7 +612,8 @@ int sisic_unet_train_step(sisic_unet* u, const float* images, const float* noise
     SISIC_TRY(require_train(u, "train_step"));
     SISIC_TRY(require_not_swapped(u, "train_step"));
     SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step: null argument");
-    SISIC_TRY(train_step_body(u, images, noise, timesteps, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
+    SISIC_TRY(unet_check_labels(u, "train_step", false, nullptr, B));
+    SISIC_TRY(train_step_body(u, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
                               stream));
     return sisic_unet_optimizer_step(u, lr, beta1, beta2, eps, 1.0f / loss_scale, found_inf, stream);
 }
@@ -596,8 +625,23 @@ int sisic_unet_train_step_ext(sisic_unet* u, const float* images, const float* n
     SISIC_TRY(require_train(u, "train_step_ext"));
     SISIC_TRY(require_not_swapped(u, "train_step_ext"));
     SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step_ext: null argument");
-    SISIC_TRY(train_step_body(u, images, noise, timesteps, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
+    SISIC_TRY(unet_check_labels(u, "train_step_ext", false, nullptr, B));
+    SISIC_TRY(train_step_body(u, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
                               stream));
+    return sisic_unet_optimizer_step_ext(u, lr, beta1, beta2, eps, 1.0f / loss_scale, ext, found_inf, grad_norm_out, stream);
+}
+
+int sisic_unet_train_step_cond(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
+                               const int64_t* class_labels, const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod,
+                               int B, int H, int W, double lr, double beta1, double beta2, double eps, float loss_scale,
+                               const sisic_optim_ext* ext, float* loss_out, int* found_inf, float* grad_norm_out, void* stream) {
+    SISIC_TRY(require_train(u, "train_step_cond"));
+    SISIC_TRY(require_not_swapped(u, "train_step_cond"));
+    SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step_cond: null argument");
+    SISIC_TRY(unet_check_labels(u, "train_step_cond", true, class_labels, B));
+    SISIC_TRY(train_step_body(u, images, noise, timesteps, class_labels, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W,
+                              loss_scale, loss_out, stream));
+    if (!ext) return sisic_unet_optimizer_step(u, lr, beta1, beta2, eps, 1.0f / loss_scale, found_inf, stream);
     return sisic_unet_optimizer_step_ext(u, lr, beta1, beta2, eps, 1.0f / loss_scale, ext, found_inf, grad_norm_out, stream);
 }
 

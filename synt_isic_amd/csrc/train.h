@@ -68,6 +68,9 @@ int launch_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const flo
 int launch_linear_wgrad(sisic_ctx*, const float* dy, int ld, const float* x, int B, int R, int K, float* dW, hipStream_t s);
 int launch_linear_dgrad(sisic_ctx*, const float* dy, int ld, const float* W, int B, int R, int K, float* dx, hipStream_t s,
                         int w_is_transposed);
+// class embedding gradient: dE[k][j] = sum over the samples b with labels[b] == k, in ascending b, of dt[b][j] (no atomics: the
+// same bits every time); every one of the N rows is written, a label absent from the batch leaves its row zero
+int launch_class_embed_grad(sisic_ctx*, const float* dt, const int* labels, int B, int N, int hidden, float* dE, hipStream_t s);
 int launch_silu_fwd(sisic_ctx*, const float* pre, size_t n, float* out, hipStream_t s);
 int launch_silu_bwd(sisic_ctx*, const float* dy, const float* pre, size_t n, float* out, hipStream_t s);
 int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, float grad_scale, float* loss_dev, float* dpred,

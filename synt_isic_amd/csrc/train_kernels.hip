@@ -950,6 +950,25 @@ int launch_silu_fwd(sisic_ctx*, const float* pre, size_t n, float* out, hipStrea
     return SISIC_OK;
 }
 
+// one thread per element of dE [N, hidden]: the rows of dt whose label is the element's row, summed in batch order
+__global__ void __launch_bounds__(256) class_embed_grad_kernel(const float* __restrict__ dt, const int* __restrict__ labels, int B, int N,
+                                                               int hidden, float* __restrict__ dE) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * hidden) return;
+    const int k = i / hidden, j = i - k * hidden;
+    float acc = 0.0f;
+    for (int b = 0; b < B; ++b)
+        if (labels[b] == k) acc += dt[(size_t)b * hidden + j];
+    dE[i] = acc;
+}
+
+int launch_class_embed_grad(sisic_ctx*, const float* dt, const int* labels, int B, int N, int hidden, float* dE, hipStream_t s) {
+    SISIC_REQUIRE(dt && labels && dE && B > 0 && N > 0 && hidden > 0 && (int64_t)N * hidden <= INT32_MAX, "class_embed_grad: bad arguments");
+    hipLaunchKernelGGL(class_embed_grad_kernel, dim3(cdiv(N * hidden, 256)), dim3(256), 0, s, dt, labels, B, N, hidden, dE);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // out = dy * silu'(pre)
 __global__ void silu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ pre, size_t n, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

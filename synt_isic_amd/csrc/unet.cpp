@@ -70,6 +70,9 @@ int describe(sisic_unet* u) {
     u->temb_b1 = u->add("time_embedding.linear_1.bias", u->hidden);
     u->temb_w2 = u->add("time_embedding.linear_2.weight", (int64_t)u->hidden * u->hidden);
     u->temb_b2 = u->add("time_embedding.linear_2.bias", u->hidden);
+    // UNet2DModel registers its modules as conv_in, time_proj, time_embedding, class_embedding, down_blocks, ...: the
+    // nn.Embedding(num_class_embeds, time_embed_dim) of a conditional model has its one tensor here in the state dict
+    if (u->n_class > 0) u->class_w = u->add("class_embedding.weight", (int64_t)u->n_class * u->hidden);
 
     u->down_res.resize(n); u->down_attn.resize(n); u->downsamplers.resize(n);
     int out_ch = boc[0];
@@ -284,6 +287,31 @@ int unet_stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hip
     SISIC_HIP(hipEventRecord(u->stage_ev[slot], s));
     u->stage_used[slot] = true;
     return SISIC_OK;
+}
+
+int unet_check_labels(sisic_unet* u, const char* what, bool cond, const int64_t* labels, int B) {
+    SISIC_REQUIRE(u, "%s: null handle", what);
+    if (!cond) {
+        SISIC_REQUIRE(u->n_class == 0, "%s: the model is class-conditional (sisic_unet_create_cond): call the _cond entry point with labels", what);
+        return SISIC_OK;
+    }
+    SISIC_REQUIRE(u->n_class > 0, "%s: the model has no class embedding (sisic_unet_create): call the entry point without labels", what);
+    SISIC_REQUIRE(labels && B > 0, "%s: null class_labels", what);
+    for (int b = 0; b < B; ++b)
+        SISIC_REQUIRE(labels[b] >= 0 && labels[b] < u->n_class, "%s: class_labels[%d] = %lld is outside [0, %d)", what, b,
+                      (long long)labels[b], u->n_class);
+    return SISIC_OK;
+}
+
+int unet_upload_labels(sisic_unet* u, const int64_t* labels, int B, float** dev, size_t* cap, hipStream_t s) {
+    static_assert(sizeof(int) == sizeof(float), "labels are staged as floats");
+    SISIC_TRY(unet_grow(dev, cap, (size_t)std::max(B, 64)));
+    std::vector<float> bits(B);
+    for (int b = 0; b < B; ++b) {
+        const int v = (int)labels[b];
+        std::memcpy(&bits[b], &v, sizeof(int));
+    }
+    return unet_stage_upload(u, bits.data(), (size_t)B, *dev, s);
 }
 
 int unet_check_shape(sisic_unet* u, int B, int H, int W) {
@@ -619,10 +647,12 @@ struct Fwd {
     }
 };
 
-// time embedding + all time_emb_proj rows for `rows` timesteps (t_vals already on the device)
-int time_embed(sisic_unet* u, int rows, hipStream_t s) {
+// time embedding + all time_emb_proj rows for `rows` timesteps (t_vals already on the device); cond: plus the class embedding's
+// row of each sample (u->labels_dev already on the device)
+int time_embed(sisic_unet* u, int rows, hipStream_t s, bool cond = false) {
     SISIC_TRY(launch_temb_mlp(u->ctx, u->t_vals, rows, u->d_freqs, u->cfg.n_freqs, u->w1t, u->rawp(u->temb_b1), u->w2t,
-                              u->rawp(u->temb_b2), u->hidden, u->temb_act, s));
+                              u->rawp(u->temb_b2), u->hidden, u->temb_act, s, nullptr, nullptr, nullptr,
+                              cond ? u->rawp(u->class_w) : nullptr, cond ? reinterpret_cast<const int*>(u->labels_dev) : nullptr));
     SISIC_TRY(launch_linear_t(u->ctx, u->temb_act, rows, u->hidden, u->tproj_wt, u->tproj_b, u->tproj_R, u->tproj, s));
     return SISIC_OK;
 }
@@ -645,8 +675,13 @@ int sisic::unet_run_forward(sisic_unet* u, const float* sample, const float* tpr
 extern "C" {
 
 int sisic_unet_create(sisic_ctx* ctx, const sisic_unet_config* cfg, sisic_unet** out) {
+    return sisic_unet_create_cond(ctx, cfg, 0, out);
+}
+
+int sisic_unet_create_cond(sisic_ctx* ctx, const sisic_unet_config* cfg, int num_class_embeds, sisic_unet** out) {
     SISIC_REQUIRE(ctx && cfg && out, "unet_create: null argument");
     *out = nullptr;
+    SISIC_REQUIRE(num_class_embeds >= 0, "unet_create: num_class_embeds %d", num_class_embeds);
     SISIC_REQUIRE(cfg->n_blocks >= 1 && cfg->n_blocks <= 8, "unet_create: n_blocks %d", cfg->n_blocks);
     SISIC_REQUIRE(cfg->layers_per_block >= 1, "unet_create: layers_per_block");
     SISIC_REQUIRE(cfg->in_channels > 0 && cfg->out_channels > 0, "unet_create: channels");
@@ -666,6 +701,7 @@ int sisic_unet_create(sisic_ctx* ctx, const sisic_unet_config* cfg, sisic_unet**
     if (const char* e = std::getenv("SISIC_GRAPH")) u->graph_mode = std::atoi(e) != 0 ? 1 : 0;
     if (poison_alloc()) u->graph_mode = 0;
     u->cfg.freqs = nullptr;
+    u->n_class = num_class_embeds;
     const int rc = describe(u);
     if (rc != SISIC_OK) { delete u; return rc; }
     *out = u;
@@ -677,11 +713,12 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)sisic_unet_train_end(u);
     (void)hipDeviceSynchronize();
     pool_release_all(u);
-    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf})
+    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
-    for (float* p : {u->raw, u->t_vals, u->temb_act, u->tproj, u->gn_scale, u->gn_shift, u->gn_scale2, u->gn_shift2, u->eps_buf})
+    for (float* p : {u->raw, u->t_vals, u->temb_act, u->tproj, u->gn_scale, u->gn_shift, u->gn_scale2, u->gn_shift2, u->eps_buf,
+                     u->labels_dev})
         if (p) (void)hipFree(p);
     if (u->stage_host) (void)hipHostFree(u->stage_host);
     for (auto e : u->stage_ev)
@@ -752,22 +789,36 @@ int sisic_unet_load(sisic_unet* u, int n, const char* const* names, const float*
     return SISIC_OK;
 }
 
-int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timesteps, float* out, int B, int H, int W,
-                       void* stream) {
-    SISIC_REQUIRE(u && sample && timesteps && out, "unet_forward: null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// labels: host int64 [B] of a conditional model (checked by the caller), or nullptr
+static int forward_impl(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* labels, float* out, int B,
+                        int H, int W, hipStream_t s) {
     SISIC_TRY(unet_check_shape(u, B, H, W));
     SISIC_TRY(unet_ensure_rows(u, (size_t)B, (size_t)B));
     std::vector<float> tv(B);
-    bool uniform = true;
+    bool uniform = true;      // one embedding row serves every sample: equal timesteps and, with labels, equal labels
     for (int b = 0; b < B; ++b) {
         tv[b] = (float)timesteps[b];
-        uniform = uniform && timesteps[b] == timesteps[0];
+        uniform = uniform && timesteps[b] == timesteps[0] && (!labels || labels[b] == labels[0]);
     }
     const int rows = uniform ? 1 : B;
     SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)rows, u->t_vals, s));
-    SISIC_TRY(time_embed(u, rows, s));
+    if (labels) SISIC_TRY(unet_upload_labels(u, labels, rows, &u->labels_dev, &u->labels_cap, s));
+    SISIC_TRY(time_embed(u, rows, s, labels != nullptr));
     return unet_run_forward(u, sample, u->tproj, uniform ? 0 : u->tproj_R, out, B, H, W, s);
+}
+
+int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timesteps, float* out, int B, int H, int W,
+                       void* stream) {
+    SISIC_REQUIRE(u && sample && timesteps && out, "unet_forward: null argument");
+    SISIC_TRY(unet_check_labels(u, "unet_forward", false, nullptr, B));
+    return forward_impl(u, sample, timesteps, nullptr, out, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+int sisic_unet_forward_cond(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
+                            float* out, int B, int H, int W, void* stream) {
+    SISIC_REQUIRE(u && sample && timesteps && out, "unet_forward_cond: null argument");
+    SISIC_TRY(unet_check_labels(u, "unet_forward_cond", true, class_labels, B));
+    return forward_impl(u, sample, timesteps, class_labels, out, B, H, W, static_cast<hipStream_t>(stream));
 }
 
 // the device tables of the replayed loop: 1000 rows of the widest rule's coefficients (a rule's rows lie packed at its own
@@ -775,24 +826,42 @@ int sisic_unet_forward(sisic_unet* u, const float* sample, const int64_t* timest
 static constexpr size_t LOOP_COEF_FLOATS = 6 * 1000;
 static constexpr size_t LOOP_TABLE_FLOATS = 4 + LOOP_COEF_FLOATS + 1000;
 
+// A conditional call of the loop (sisic_sample_frames_cond): every sample of a pass has its own embedding row, and a guided
+// call runs each pass at twice the batch
+struct CondCall {
+    bool guided = false;     // guidance_scale != 1: conditional rows first, null-label rows second, combined in the step kernel
+    int rows = 0;            // samples per UNet pass: B, or 2B when guided
+    float w = 1.0f;
+};
+
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
-// launches for every step, so that a captured step can be replayed.
+// launches for every step, so that a captured step can be replayed.  cg: a conditional call, or nullptr.
 static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
-                     hipStream_t s) {
+                     const CondCall* cg, hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
-    SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
-    SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
-    if (rule == STEP_RULE_DPMPP && rng)
+    const uint64_t* seeds = reinterpret_cast<const uint64_t*>(u->seeds_dev);
+    if (cg) {
+        SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, state, 0, u->cond_tables, cg->rows, u->tproj_cur, s));
+        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, u->tproj_R, u->eps_buf, cg->rows, H, W, s));
+    } else {
+        SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
+        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
+    }
+    if (cg && cg->guided)
+        SISIC_TRY(launch_step_guided_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work,
+                                             rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, (int64_t)n, (int64_t)(n / B), state,
+                                             coef_dev, zrow_dev, rng ? seeds : nullptr, u->cond_tables, clip, s));
+    else if (rule == STEP_RULE_DPMPP && rng)
         SISIC_TRY(launch_dpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, (int64_t)(n / B), state,
-                                              coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
+                                              coef_dev, seeds, clip, s));
     else if (rule == STEP_RULE_DPMPP)
         SISIC_TRY(launch_dpm_step_indexed(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, state, coef_dev, zrow_dev,
                                           clip, s));
     else if (rng)
         SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
-                                          coef_dev, reinterpret_cast<const uint64_t*>(u->seeds_dev), clip, s));
+                                          coef_dev, seeds, clip, s));
     else
         SISIC_TRY(launch_step_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev,
                                       clip, s));
@@ -803,8 +872,8 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
 // rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
 static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, int rule,
-                        int rule_flags, const float* noise, bool rng, int step0, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
-                        hipStream_t caller) {
+                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, float* traj, const int* traj_row,
+                        const volatile int* cancel, int* steps_done, hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
@@ -817,8 +886,10 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         if (!u->loop_stream) SISIC_HIP(hipStreamCreate(&u->loop_stream));     // implicitly ordered with the default stream
         s = u->loop_stream;
     }
-    SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, n));
-    SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)u->tproj_R));
+    const bool guided = cg && cg->guided;
+    // (a guided call keeps the latent twice, one copy per half of the batch the UNet runs; the step kernel writes both)
+    SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, guided ? 2 * n : n));
+    SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)(cg ? cg->rows : 1) * u->tproj_R));
     SISIC_TRY(unet_grow(&u->loop_tables, &u->loop_tables_cap, LOOP_TABLE_FLOATS));
     // tables of this call: {step = 0, step base, noise base}, coefficients, noise row per step (-1: the step adds no noise)
     std::vector<float> tab(LOOP_TABLE_FLOATS, 0.0f);
@@ -834,6 +905,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     }
     SISIC_TRY(unet_stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
     SISIC_HIP(hipMemcpyAsync(u->x_work, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (guided) SISIC_HIP(hipMemcpyAsync(u->x_work + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     auto after_step = [&](int i) -> int {
         const int row = traj_row ? traj_row[i] : i;          // (kept frames only: XAI.py:751-757 save_indices)
@@ -852,31 +924,35 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     const void* hist = rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr;      // sized by sample_frames before this call
     // every address baked into the captured launches: the pool and the scratch buffers are sized by the first eager step at a
     // shape, the tables by ensure_rows / grow above
+    // (labels and the guidance scale live in cond_tables and change nothing a captured launch holds; whether the call is
+    //  conditional, and whether it is guided, change the launches themselves)
+    const void* cond_tab = cg ? u->cond_tables : nullptr;
     auto reusable = [&]() -> bool {
         const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[6] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist};
+        const void* ptrs[7] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
                   u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
-                  u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags;
-        for (int k = 0; k < 6; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
+                  u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags && u->loop_key.cond == (cg != nullptr) &&
+                  u->loop_key.guided == guided;
+        for (int k = 0; k < 7; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
     if (rc == SISIC_OK && !reusable()) {
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, s);
+        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
     if (rc == SISIC_OK && i < T) {
         if (!reusable()) {
             const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[6] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist};
+            const void* ptrs[7] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, s);
+            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -890,7 +966,8 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
             u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
             u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
-            for (int k = 0; k < 6; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided;
+            for (int k = 0; k < 7; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
         }
@@ -917,11 +994,14 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
 
 // The loop behind sisic_sample_frames[_rule] (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames[_rule]_rng (seeds:
 // HOST uint64 [B], noise NULL): the two differ in where the scheduler step takes z from, nothing else.  rule, rule_flags: the
-// step rule whose rows coef holds (SISIC_RULE_*).
+// step rule whose rows coef holds (SISIC_RULE_*).  labels: sisic_sample_frames_cond (host int64 [B], with null_label and the
+// guidance scale w), or nullptr for an unconditional handle.
 static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
-                         float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0, float* traj, const int* traj_row,
+                         float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
+                         const int64_t* labels, int null_label, float w, float* traj, const int* traj_row,
                          uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
+    SISIC_TRY(unet_check_labels(u, labels ? "sample_cond" : "sample", labels != nullptr, labels, B));
     SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
     if (traj_row)
         for (int i = 0; i < T; ++i) SISIC_REQUIRE(traj_row[i] >= -1, "sample: traj_row[%d] = %d (a row of traj, or -1)", i, traj_row[i]);
@@ -930,20 +1010,48 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);      // (an unknown rule is refused by check_step_row just below)
-    if (rule != STEP_RULE_DDPM || rule_flags != 0)
+    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels)
         for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * cw + 0], coef[(size_t)i * cw + 1]));
     // DPM-Solver++: a call starts with no history (the buffer holds whatever the last run left), so its first step cannot be
     // a second-order one.  A run cut into two calls therefore differs from the uncut run; callers run it in one call.
     if (rule == STEP_RULE_DPMPP)
         SISIC_REQUIRE(coef[5] == 0.0f, "sample: row 0 of a DPM-Solver++ call has k1 = %g (a call starts with no history)", coef[5]);
-    SISIC_TRY(unet_check_shape(u, B, H, W));
+    // a conditional call: the distinct labels of the call (in order of first appearance, the null one last when guided) are the
+    // slots of the embedding table; sample b of a pass reads the row of (step, slot[b])
+    CondCall cc;
+    const CondCall* cg = nullptr;
+    std::vector<int64_t> distinct;
+    std::vector<int> slots;
+    if (labels) {
+        SISIC_REQUIRE(std::isfinite(w), "sample_cond: guidance_scale %g", (double)w);
+        cc.guided = w != 1.0f;
+        cc.rows = cc.guided ? 2 * B : B;
+        cc.w = w;
+        SISIC_REQUIRE(cc.rows <= 65535, "sample_cond: batch %d", B);
+        if (cc.guided)
+            SISIC_REQUIRE(null_label >= 0 && null_label < u->n_class, "sample_cond: null_label %d is outside [0, %d)", null_label, u->n_class);
+        auto slot_of = [&](int64_t label) -> int {
+            const auto it = std::find(distinct.begin(), distinct.end(), label);
+            if (it != distinct.end()) return (int)(it - distinct.begin());
+            distinct.push_back(label);
+            return (int)distinct.size() - 1;
+        };
+        slots.resize(cc.rows);
+        for (int b = 0; b < B; ++b) slots[b] = slot_of(labels[b]);
+        for (int b = B; b < cc.rows; ++b) slots[b] = slot_of(null_label);
+        cg = &cc;
+    }
+    const int rows = cg ? cg->rows : B;                          // samples per UNet pass
+    const size_t L = cg ? distinct.size() : 1;                   // embedding rows per step
+    SISIC_TRY(unet_check_shape(u, rows, H, W));
     // per-step tables for 1000 rows from the first call on (17 MB): a longer run after a shorter one then never moves the
-    // time-embedding table, so the captured step (which holds its address) survives a change of T
-    SISIC_TRY(unet_ensure_rows(u, (size_t)std::max(T, 1000), (size_t)B));
+    // time-embedding table, so the captured step (which holds its address) survives a change of T (and, in a conditional
+    // call, a change of the labels as long as T x distinct labels stays within what the table has grown to)
+    SISIC_TRY(unet_ensure_rows(u, std::max((size_t)T * L, (size_t)1000), (size_t)rows));
     const int C = u->cfg.in_channels;
     SISIC_REQUIRE(u->cfg.out_channels == C, "sample: in/out channels differ");
     const size_t n = (size_t)B * C * H * W;
-    SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, n));
+    SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, (size_t)rows * C * H * W));
     if (rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
     const bool rng = seeds != nullptr;
     if (rng) {
@@ -954,53 +1062,97 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
         SISIC_TRY(unet_stage_upload(u, reinterpret_cast<const float*>(seeds), 2 * (size_t)B, u->seeds_dev, s));
     }
 
-    // every step's time embedding and time_emb_proj rows in one batch before the loop
-    std::vector<float> tv(T);
-    for (int i = 0; i < T; ++i) tv[i] = (float)timesteps[i];
-    SISIC_TRY(unet_stage_upload(u, tv.data(), (size_t)T, u->t_vals, s));
-    SISIC_TRY(time_embed(u, T, s));
+    // every step's time embedding and time_emb_proj rows in one batch before the loop: row i of an unconditional call, row
+    // i * L + j for slot j of a conditional one (linear_t computes each row on its own: a sample's embedding bits depend on its
+    // (t, label) alone)
+    std::vector<float> tv((size_t)T * L);
+    for (size_t i = 0; i < (size_t)T; ++i)
+        for (size_t j = 0; j < L; ++j) tv[i * L + j] = (float)timesteps[i];
+    SISIC_TRY(unet_stage_upload(u, tv.data(), tv.size(), u->t_vals, s));
+    if (cg) {
+        std::vector<int64_t> lab((size_t)T * L);
+        for (size_t i = 0; i < (size_t)T; ++i)
+            for (size_t j = 0; j < L; ++j) lab[i * L + j] = distinct[j];
+        SISIC_TRY(unet_upload_labels(u, lab.data(), (int)lab.size(), &u->labels_dev, &u->labels_cap, s));
+        // the loop's device table of the call: {w, L, -, -, slot[rows]} (elementwise.hip, LoopCond)
+        std::vector<float> ct(LOOP_COND_HEAD + (size_t)rows, 0.0f);
+        const int Li = (int)L;
+        ct[0] = cg->w;
+        std::memcpy(&ct[1], &Li, sizeof(int));
+        std::memcpy(&ct[LOOP_COND_HEAD], slots.data(), (size_t)rows * sizeof(int));
+        SISIC_TRY(unet_grow(&u->cond_tables, &u->cond_tables_cap, LOOP_COND_HEAD + (size_t)std::max(rows, 128)));
+        SISIC_TRY(unet_stage_upload(u, ct.data(), ct.size(), u->cond_tables, s));
+    }
+    SISIC_TRY(time_embed(u, (int)((size_t)T * L), s, cg != nullptr));
 
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, traj, traj_row, cancel, steps_done, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
     }
 
-    size_t zi = 0;
-    for (int i = 0; i < T; ++i) {
-        if (cancel) {
-            if ((i & 7) == 0) SISIC_HIP(hipStreamSynchronize(s));   // bound the run-ahead so a stop request takes effect
-            if (*cancel) {
-                SISIC_HIP(hipStreamSynchronize(s));
-                set_error("sample: cancelled after %d of %d steps", i, T);
-                return SISIC_ECANCEL;
-            }
-        }
-        SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
-        const float* c = coef + (size_t)i * cw;
-        const float* z = nullptr;
-        if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-        if (rule == STEP_RULE_DPMPP && rng)
-            SISIC_TRY(launch_dpm_step_rng(u->ctx, u->eps_buf, x, u->hist_buf, x, (int64_t)n, (int64_t)(n / B),
-                                          reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
-                                          c[3], c[4], c[5], clip, s));
-        else if (rule == STEP_RULE_DPMPP)
-            SISIC_TRY(launch_dpm_step(u->ctx, u->eps_buf, x, z, u->hist_buf, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], c[5],
-                                      clip, s));
-        else if (rng)
-            SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B),
-                                      reinterpret_cast<const uint64_t*>(u->seeds_dev), (uint32_t)(step0 + i), c[0], c[1], c[2],
-                                      c[3], c[4], clip, s));
-        else
-            SISIC_TRY(launch_step(u->ctx, rule, rule_flags, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip,
-                                  s));
-        const int row = traj_row ? traj_row[i] : i;
-        if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (steps_done) *steps_done = i + 1;
+    // a guided call steps a library-owned [2B] copy of the latent (the step kernel writes both halves: the next pass reads
+    // them without a copy); everything else steps x in place
+    const bool guided = cg && cg->guided;
+    float* xe = x;
+    if (guided) {
+        SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, 2 * n));
+        xe = u->x_work;
+        SISIC_HIP(hipMemcpyAsync(xe, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SISIC_HIP(hipMemcpyAsync(xe + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    if (cg) SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)rows * u->tproj_R));
+    const uint64_t* seeds_dev = reinterpret_cast<const uint64_t*>(u->seeds_dev);
+    size_t zi = 0;
+    auto steps = [&]() -> int {
+        for (int i = 0; i < T; ++i) {
+            if (cancel) {
+                if ((i & 7) == 0) SISIC_HIP(hipStreamSynchronize(s));   // bound the run-ahead so a stop request takes effect
+                if (*cancel) {
+                    SISIC_HIP(hipStreamSynchronize(s));
+                    set_error("sample: cancelled after %d of %d steps", i, T);
+                    return SISIC_ECANCEL;
+                }
+            }
+            if (cg) {
+                SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, nullptr, i, u->cond_tables, rows, u->tproj_cur, s));
+                SISIC_TRY(unet_run_forward(u, xe, u->tproj_cur, u->tproj_R, u->eps_buf, rows, H, W, s));
+            } else {
+                SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
+            }
+            const float* c = coef + (size_t)i * cw;
+            const float* z = nullptr;
+            if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
+            if (guided)
+                SISIC_TRY(launch_step_guided(u->ctx, rule, rule_flags, u->eps_buf, u->eps_buf + n, cg->w, xe, z, rng ? seeds_dev : nullptr,
+                                             (int64_t)(n / B), (uint32_t)(step0 + i), rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr,
+                                             xe, (int64_t)n, c, clip, s));
+            else if (rule == STEP_RULE_DPMPP && rng)
+                SISIC_TRY(launch_dpm_step_rng(u->ctx, u->eps_buf, x, u->hist_buf, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
+                                              (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], c[5], clip, s));
+            else if (rule == STEP_RULE_DPMPP)
+                SISIC_TRY(launch_dpm_step(u->ctx, u->eps_buf, x, z, u->hist_buf, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], c[5],
+                                          clip, s));
+            else if (rng)
+                SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
+                                          (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], clip, s));
+            else
+                SISIC_TRY(launch_step(u->ctx, rule, rule_flags, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip,
+                                      s));
+            const int row = traj_row ? traj_row[i] : i;
+            if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, xe, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (steps_done) *steps_done = i + 1;
+        }
+        return SISIC_OK;
+    };
+    const int rc = steps();
+    // x holds the latent after the steps that ran under every exit, as in the other forms of the loop: a cancelled or failed
+    // guided run hands its partially stepped copy back too
+    if (guided) SISIC_HIP(hipMemcpyAsync(x, xe, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc != SISIC_OK) return rc;
     if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
     return SISIC_OK;
 }
@@ -1008,8 +1160,8 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
 int sisic_sample_frames_rule(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                              float clip, int rule, int rule_flags, const float* noise, float* traj, const int* traj_row,
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, traj, traj_row, out_u8,
-                         cancel, steps_done, stream);
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, nullptr, 0, 1.0f, traj,
+                         traj_row, out_u8, cancel, steps_done, stream);
 }
 
 int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps,
@@ -1017,8 +1169,23 @@ int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, i
                                  float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
                                  void* stream) {
     SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, traj, traj_row,
-                         out_u8, cancel, steps_done, stream);
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, nullptr, 0, 1.0f, traj,
+                         traj_row, out_u8, cancel, steps_done, stream);
+}
+
+int sisic_sample_frames_cond(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                             float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
+                             const int64_t* class_labels, int null_label, float guidance_scale, float* traj, const int* traj_row,
+                             uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
+    SISIC_REQUIRE(u && class_labels, "sample_cond: null argument");
+    SISIC_REQUIRE(!(seeds && noise), "sample_cond: a noise buffer and seeds (host noise takes seeds NULL, device noise takes noise NULL)");
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, seeds, step0, class_labels, null_label,
+                         guidance_scale, traj, traj_row, out_u8, cancel, steps_done, stream);
+}
+
+int sisic_guide_eps(sisic_ctx* ctx, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream) {
+    SISIC_REQUIRE(ctx, "guide_eps: null context");
+    return launch_guide_eps(ctx, eps_c, eps_u, w, out, n, static_cast<hipStream_t>(stream));
 }
 
 int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,

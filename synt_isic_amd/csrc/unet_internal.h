@@ -111,6 +111,9 @@ struct TrainState {
     size_t emb_cap = 0, h1_cap = 0, t2_cap = 0;
     float* dtproj = nullptr;          // [B, tproj_R] gradient of the fused time_emb_proj outputs
     size_t dtproj_cap = 0;
+    float* labels_dev = nullptr;      // conditional model: int [B] class labels of the tape (sized in floats)
+    size_t labels_cap = 0;
+    bool has_labels = false;          // the tape was recorded by sisic_unet_train_forward_cond
     float* garena = nullptr;          // activation gradients of one backward pass: one block, zero-filled once
     size_t garena_cap = 0, garena_used = 0;
     float* wgrad_part = nullptr;      // K-split partial weight gradients
@@ -157,6 +160,8 @@ struct sisic_unet {
     ConvW conv_in, conv_out;
     NormW norm_out;
     int temb_w1 = -1, temb_b1 = -1, temb_w2 = -1, temb_b2 = -1;
+    int n_class = 0;                   // sisic_unet_create_cond: rows of class_embedding.weight [n_class, hidden]; 0: unconditional
+    int class_w = -1;
     float* d_freqs = nullptr;
     float* w1t = nullptr;  // [2*n_freqs][hidden]
     float* w2t = nullptr;  // [hidden][hidden]
@@ -174,6 +179,8 @@ struct sisic_unet {
     sisic::Pool pool;            // activations of a run at (ws_B, ws_H, ws_W); emptied when the shape changes
     int ws_B = 0, ws_H = 0, ws_W = 0;
     float* t_vals = nullptr;     // [B] or [T]
+    float* labels_dev = nullptr; // conditional model: int [B] class labels of the running forward (sized in floats)
+    size_t labels_cap = 0;
     float* temb_act = nullptr;   // [B or T, hidden]
     float* tproj = nullptr;      // [B or T, tproj_R]
     float* gn_scale = nullptr;   // [B, max_c]
@@ -204,8 +211,10 @@ struct sisic_unet {
     hipGraphExec_t loop_exec = nullptr;
     struct LoopKey {
         int B = 0, H = 0, W = 0; float clip = 0; hipStream_t s = nullptr; bool latency = false; uint64_t gen = 0;
-        const void* ptrs[6] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur and (DPM-Solver++ steps, else null)
-                                         // hist_buf at capture time: each can be re-allocated
+        const void* ptrs[7] = {};        // tproj, eps_buf, x_work, loop_tables, tproj_cur, (DPM-Solver++ steps, else null)
+                                         // hist_buf and (conditional calls, else null) cond_tables at capture time: each
+                                         // can be re-allocated
+        bool cond = false, guided = false;   // sisic_sample_frames_cond: per-sample embedding rows; two predictions per step
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
         const void* seeds = nullptr;     // ... from the seeds at this address
         int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags
@@ -221,6 +230,8 @@ struct sisic_unet {
     size_t tproj_cur_cap = 0;
     float* hist_buf = nullptr;           // SISIC_RULE_DPMPP: the previous step's x0 [B,C,H,W], owned by the running call
     size_t hist_cap = 0;
+    float* cond_tables = nullptr;        // conditional loop: {w, L, -, -, slot[B or 2B]} (elementwise.hip, LoopCond)
+    size_t cond_tables_cap = 0;
     float* seeds_dev = nullptr;          // uint64 [B] seeds of the running sisic_sample_frames_rng call (sized in floats: 2 per seed)
     size_t seeds_cap = 0;
 
@@ -247,6 +258,10 @@ int unet_grow(float** p, size_t* have, size_t want);
 int unet_check_shape(sisic_unet* u, int B, int H, int W);
 int unet_ensure_rows(sisic_unet* u, size_t t_rows, size_t gn_rows);
 int unet_stage_upload(sisic_unet* u, const float* src, size_t n, float* dst, hipStream_t s);
+// conditional or not, as the entry point expects (cond: a labelled entry point), and every label inside [0, n_class)
+int unet_check_labels(sisic_unet* u, const char* what, bool cond, const int64_t* labels, int B);
+// labels (host int64, already checked) as device ints in *dev, ordered on s
+int unet_upload_labels(sisic_unet* u, const int64_t* labels, int B, float** dev, size_t* cap, hipStream_t s);
 // (re)derive every packed / transposed weight buffer from the raw arena (after load, and after each optimizer step)
 int unet_prepare_all(sisic_unet* u, hipStream_t s);
 // forward pass; with `tape` set nothing is released and every operation is recorded (training mode)

@@ -216,18 +216,28 @@ def draw_augment_params(indices: Sequence[int], epoch: int, seed: int, H: int, W
 
 # ---- the dataset in device memory -----------------------------------------------------------------------------------------
 class DeviceDataset:
-    """uint8 [N,H,W,3] images (numpy or torch), uploaded once; H and W multiples of 8."""
+    """uint8 [N,H,W,3] images (numpy or torch), uploaded once; H and W multiples of 8.  ``labels``: one integer class label
+    per image (a class-conditional model's ``class_labels``), kept on the device as int64; None: an unlabelled dataset."""
 
-    def __init__(self, images_u8, device="cuda"):
+    def __init__(self, images_u8, device="cuda", labels=None):
         t = images_u8 if isinstance(images_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images_u8))
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
             raise ValueError(f"images must be uint8 [N,H,W,3] with N > 0, got {t.dtype} {tuple(t.shape)}")
         if t.shape[1] % 8 or t.shape[2] % 8:
             raise ValueError(f"image height and width must be multiples of 8, got {t.shape[1]} x {t.shape[2]}")
+        if labels is not None:
+            lab = torch.as_tensor(np.asarray(labels) if not isinstance(labels, torch.Tensor) else labels)
+            if lab.dtype.is_floating_point or lab.dtype == torch.bool or lab.dim() != 1:
+                raise ValueError(f"labels must be a 1-D integer array, got {lab.dtype} {tuple(lab.shape)}")
+            if lab.shape[0] != t.shape[0]:
+                raise ValueError(f"{lab.shape[0]} labels for {t.shape[0]} images")
+            if lab.numel() and int(lab.min()) < 0:
+                raise ValueError("labels must be non-negative")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"DeviceDataset lives on an MI355X (torch device 'cuda'); got '{device}'. There is no CPU path.")
         self.images = t.contiguous().to(device)
+        self.labels = None if labels is None else lab.to(torch.int64).contiguous().to(device)
 
     def __len__(self) -> int:
         return self.images.shape[0]
@@ -276,6 +286,19 @@ class DeviceDataset:
         ``sample(n, random_state=42)``, ``convert("RGB").resize((s, s))``, ``enhance_color``), decoded once and uploaded."""
         return cls(cls.load_isic(image_dir, csv_path, class_id, image_size, max_samples), device)
 
+    @classmethod
+    def from_isic_classes(cls, image_dir: str, csv_path: str, class_ids: Sequence[int], image_size: int = 128,
+                          max_samples: int = 500, device="cuda") -> "DeviceDataset":
+        """One labelled dataset over several classes, for ``train.train_conditional``: ``load_isic`` per class (each with its
+        own colour correction and at most ``max_samples`` images), concatenated in the order of ``class_ids``; an image's label
+        is the POSITION of its class in ``class_ids``, so the labels run 0 .. len(class_ids) - 1 whatever the ids are."""
+        class_ids = list(class_ids)
+        if not class_ids or len(set(class_ids)) != len(class_ids):
+            raise ValueError(f"class_ids must be a non-empty list of distinct class ids, got {class_ids}")
+        parts = [cls.load_isic(image_dir, csv_path, cid, image_size, max_samples) for cid in class_ids]
+        labels = np.concatenate([np.full(len(p), k, dtype=np.int64) for k, p in enumerate(parts)])
+        return cls(np.concatenate(parts), device, labels=labels)
+
 
 def epoch_batches(n: int, batch_size: int, epoch: int, seed: int, shuffle: bool = True, drop_last: bool = False):
     """The index batches of one epoch: every index once (``drop_last`` drops a ragged last batch)."""
@@ -289,7 +312,8 @@ class DeviceLoader:
     advances), each item a [B,3,H,W] fp32 device tensor in [-1,1] made by one non-blocking parameter upload and two launches
     on the current stream.  Shuffling and augmentation are functions of (seed, epoch, dataset index): the same seed gives the
     same epochs.  ``augment=False`` yields the images themselves, normalised, through the same kernels.  ``augment_kwargs``
-    go to ``draw_augment_params``.  Drop-in for the DataLoader of ``train.train_class``."""
+    go to ``draw_augment_params``.  Drop-in for the DataLoader of ``train.train_class``.  Over a labelled dataset each item
+    is ``(images, labels)``, the labels an int64 device tensor [B] in the batch's order (``train.train_conditional``)."""
 
     def __init__(self, dataset: DeviceDataset, batch_size: int, *, shuffle: bool = True, seed: int = 0, augment: bool = True,
                  drop_last: bool = False, **augment_kwargs):
@@ -318,5 +342,11 @@ class DeviceLoader:
     def __iter__(self) -> Iterator[torch.Tensor]:
         epoch = self.epoch
         self.epoch += 1
+        labels = getattr(self.dataset, "labels", None)
         for params in self.epoch_params(epoch):
-            yield ops.augment(self.dataset.images, params)
+            images = ops.augment(self.dataset.images, params)
+            if labels is None:
+                yield images
+            else:
+                src = torch.from_numpy(np.ascontiguousarray(params["src"]).astype(np.int64)).to(labels.device)
+                yield images, labels.index_select(0, src)

@@ -229,6 +229,23 @@ def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
     return out
 
 
+def guide_eps(eps_c: torch.Tensor, eps_u: torch.Tensor, guidance_scale: float,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_guide_eps: the classifier-free guidance combine ``eps_u + w * (eps_c - eps_u)``, subtract, multiply, add in fp32
+    with no fused multiply-add -- the device function the guided step kernels of ``sisic_sample_frames_cond`` call, so a loop
+    of two ``model(..., class_labels=)`` calls, this and a scheduler step reproduces the library loop bit for bit."""
+    lib = _lib.load()
+    if eps_c.shape != eps_u.shape:
+        raise ValueError(f"eps_c {tuple(eps_c.shape)} and eps_u {tuple(eps_u.shape)} differ in shape")
+    if out is None:
+        out = empty_like(eps_c)
+    elif out.shape != eps_c.shape:
+        raise ValueError(f"out {tuple(out.shape)} does not have the inputs' shape {tuple(eps_c.shape)}")
+    check(lib.sisic_guide_eps(context(eps_c.device), _ptr(eps_c, "eps_c"), _ptr(eps_u, "eps_u"), float(guidance_scale),
+                              _ptr(out, "out"), eps_c.numel(), _stream(eps_c.device)))
+    return out
+
+
 def _seed_array(seeds):
     """HOST uint64 [B] as the C ABI takes it; seeds are 64-bit unsigned (negative values are refused, not wrapped)."""
     seeds = [int(s) for s in seeds]

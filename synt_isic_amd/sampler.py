@@ -136,6 +136,53 @@ class DeviceNoise:
             raise ValueError("seeds must be integers in 0 .. 2**64-1")
 
 
+@dataclass(frozen=True)
+class Guidance:
+    """What a class-conditional model's loop needs beside the latents (``sisic_sample_frames_cond``): one label per image,
+    the null label of classifier-free guidance and the guidance scale.  Scale 1 is plain conditional sampling, one UNet pass
+    per step; any other scale runs each step once at twice the batch and steps on ``eps_u + scale * (eps_c - eps_u)``."""
+    labels: Tuple[int, ...]
+    null_label: int
+    scale: float = 1.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "labels", tuple(int(v) for v in self.labels))
+        object.__setattr__(self, "scale", check_guidance_scale(self.scale))
+
+
+def check_guidance_scale(guidance_scale) -> float:
+    """a finite real number (negative scales are legal: they push away from the class)"""
+    if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not np.isfinite(guidance_scale):
+        raise ValueError(f"guidance_scale must be a finite number, got {guidance_scale!r}")
+    return float(guidance_scale)
+
+
+def _check_guidance(model: HipUNet2DModel, guidance: Optional[Guidance], B: int) -> None:
+    n = model.config.num_class_embeds
+    if n is None:
+        if guidance is not None:
+            raise ValueError("class labels and guidance need a class-conditional model (num_class_embeds)")
+        return
+    if guidance is None:
+        raise ValueError("a class-conditional model samples under labels: pass guidance=Guidance(labels, null_label, scale)")
+    if len(guidance.labels) != B:
+        raise ValueError(f"{len(guidance.labels)} class labels for a batch of {B}")
+    for v in guidance.labels + (guidance.null_label,):
+        if not 0 <= int(v) < n:
+            raise ValueError(f"class label {v} is outside [0, {n})")
+
+
+def _loop_call(lib, guidance: Optional[Guidance], head, noise_ptr, seeds, step0: int, tail) -> int:
+    """the library loop of one call: the unconditional entry points, or sisic_sample_frames_cond under ``guidance``"""
+    if guidance is None:
+        if seeds is not None:
+            return lib.sisic_sample_frames_rule_rng(*head, seeds, int(step0), *tail)
+        return lib.sisic_sample_frames_rule(*head, noise_ptr, *tail)
+    labels = (C.c_int64 * len(guidance.labels))(*guidance.labels)
+    return lib.sisic_sample_frames_cond(*head, noise_ptr, seeds, int(step0), labels, int(guidance.null_label),
+                                        float(guidance.scale), *tail)
+
+
 def draw_x_T_device(seeds: Sequence[int], chw: Tuple[int, int, int], device: torch.device) -> torch.Tensor:
     """x_T [B,C,H,W] on ``device``, image by image from ``torch.Generator(device=device).manual_seed(seed_b)``: the
     reference's spelling (image_generator.py:369-381), so ``noise_hash`` is what it records for that seed on that device."""
@@ -325,8 +372,9 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
 def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
-                      use_clipped_model_output: bool = False) -> SampleResult:
-    """x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
+                      use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None) -> SampleResult:
+    """guidance: the labels, null label and scale of a class-conditional model (``Guidance``); None for an unconditional one.
+    x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
     (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
     ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
     return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``).
@@ -338,8 +386,10 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
         if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":
             raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
                              "noise buffer, a DeviceNoise or None")
+        _check_guidance(model, guidance, x_T.shape[0])
         return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices, eta,
-                             use_clipped_model_output)
+                             use_clipped_model_output, guidance)
+    _check_guidance(model, guidance, x_T.shape[0])
     lib = _lib.load()
     dev = x_T.device
     if dev.type != "cuda":
@@ -373,9 +423,9 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if device_noise is not None:
         seeds = (C.c_uint64 * B)(*device_noise.seeds)
-        rc = lib.sisic_sample_frames_rule_rng(*head, seeds, int(device_noise.step0), *tail)
+        rc = _loop_call(lib, guidance, head, None, seeds, device_noise.step0, tail)
     else:
-        rc = lib.sisic_sample_frames_rule(*head, noise.data_ptr() if noise is not None and n_noise else None, *tail)
+        rc = _loop_call(lib, guidance, head, noise.data_ptr() if noise is not None and n_noise else None, None, 0, tail)
     if rc != _lib.SISIC_ECANCEL:
         check(rc)
     cancelled = rc == _lib.SISIC_ECANCEL
@@ -405,7 +455,7 @@ def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
 def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: NoiseStream,
                   return_trajectory: bool, cancel_flag: Optional[C.c_int],
                   save_indices: Optional[Sequence[int]] = None, eta: float = 0.0,
-                  use_clipped_model_output: bool = False) -> SampleResult:
+                  use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None) -> SampleResult:
     lib = _lib.load()
     dev = x_T.device
     B, Cc, H, W = x_T.shape
@@ -433,14 +483,15 @@ def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: Noise
         done = C.c_int(0)
         last = b == T
         seg_rows = np.ascontiguousarray(rows[a:b]) if traj is not None and len(kept) else None
-        rc = lib.sisic_sample_frames_rule(model.handle, x.data_ptr(), B, H, W, b - a,
-                                          C.cast(ts[a:b].contiguous().data_ptr(), _lib.c_int64_p),
-                                          C.cast(coef[a:b].contiguous().data_ptr(), _lib.c_float_p), float(clip),
-                                          rule, rule_flags, z.data_ptr() if z is not None else None,
-                                          traj.data_ptr() if seg_rows is not None else None,
-                                          seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
-                                          out_u8.data_ptr() if last else None,
-                                          C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream)
+        seg_ts, seg_coef = ts[a:b].contiguous(), coef[a:b].contiguous()
+        rc = _loop_call(lib, guidance,
+                        (model.handle, x.data_ptr(), B, H, W, b - a, C.cast(seg_ts.data_ptr(), _lib.c_int64_p),
+                         C.cast(seg_coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags),
+                        z.data_ptr() if z is not None else None, None, 0,
+                        (traj.data_ptr() if seg_rows is not None else None,
+                         seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
+                         out_u8.data_ptr() if last else None,
+                         C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream))
         ns.release(slot)
         done_total += done.value
         if rc != 0:
@@ -493,6 +544,7 @@ class Sampler:
         self.beta_schedule = beta_schedule
         self.latency_mode = bool(latency_mode)
         self.models: Dict[str, HipUNet2DModel] = {}
+        self.class_labels: Dict[str, int] = {}        # class name -> its label in the conditional model registered for it
         self.cancel = C.c_int(0)          # cooperative stop flag (image_generator.py:320,396)
         self.last_trajectory_steps: List[int] = []   # step indices of the frames the last generate(..., return_trajectory=True) kept
         self.noise_segment_steps = 64     # steps of noise drawn and uploaded per pipeline stage (NoiseStream)
@@ -532,6 +584,58 @@ class Sampler:
         self.models[class_name] = m
         return m
 
+    def add_conditional_model(self, class_names: Sequence[str], state_dict: Dict[str, torch.Tensor],
+                              **unet_kwargs) -> HipUNet2DModel:
+        """ONE class-conditional model for several class names (``train.train_conditional``'s checkpoint): the label of a
+        name is its index in ``class_names``, the null label of classifier-free guidance is ``len(class_names)``, so the model
+        has ``len(class_names) + 1`` embedding rows.  Every name then works wherever a class name does, and a call may mix
+        them (``generate_seeds(["MEL", "NV", "MEL"], seeds, ...)``)."""
+        names = [str(n) for n in class_names]
+        if isinstance(class_names, str) or not names or len(set(names)) != len(names):
+            raise ValueError(f"class_names must be a non-empty sequence of distinct names, got {class_names!r}")
+        taken = [n for n in names if n in self.models]
+        if taken:
+            raise ValueError(f"a model is already registered for {taken}")
+        rows = unet_kwargs.setdefault("num_class_embeds", len(names) + 1)
+        if rows != len(names) + 1:
+            raise ValueError(f"a conditional model for {len(names)} classes has {len(names) + 1} embedding rows (the last is "
+                             f"the null label), got num_class_embeds={rows}")
+        m = self.add_model(names[0], state_dict, **unet_kwargs)
+        for k, n in enumerate(names):
+            self.models[n] = m
+            self.class_labels[n] = k
+        return m
+
+    def _resolve_classes(self, class_name, n_images: int, guidance_scale) -> Tuple[HipUNet2DModel, List[str], Optional[Guidance]]:
+        """(model, one class name per image, Guidance or None) of a call; every refusal of the public interface is here"""
+        scale = check_guidance_scale(guidance_scale)
+        if isinstance(class_name, str):
+            names = [class_name] * n_images
+        else:
+            names = [str(c) for c in class_name]
+            if len(names) != n_images:
+                raise ValueError(f"{len(names)} class names for {n_images} images: a sequence holds one entry per seed")
+            if not names:
+                raise ValueError("no class name given")
+        for c in names:
+            if c not in self.models:
+                raise KeyError(f"no model loaded for class '{c}'")
+        model = self.models[names[0]]
+        if any(self.models[c] is not model for c in names):
+            raise ValueError("the class names of one call must belong to one conditional model")
+        if model.config.num_class_embeds is None:
+            if len(set(names)) > 1:
+                raise ValueError("an unconditional model generates one class per call")
+            if scale != 1.0:
+                raise ValueError(f"guidance_scale={scale} needs a class-conditional model (add_conditional_model); the model "
+                                 f"of '{names[0]}' is unconditional")
+            return model, names, None
+        null = model.config.num_class_embeds - 1
+        labels = [self.class_labels[c] for c in names]
+        if scale == 0.0:              # the unconditional prediction alone: null labels at scale 1, one pass per step
+            labels, scale = [null] * n_images, 1.0
+        return model, names, Guidance(tuple(labels), null, scale)
+
     def create_scheduler(self, T: int, scheduler: str = "ddpm", solver_order: int = 2, algorithm_type: str = "dpmsolver++"):
         """model_manager.py:196-212; scheduler="ddim": the DDIM mirror over the same tables and timestep grid;
         scheduler="dpmsolver++": the DPM-Solver++ mirror over the same tables and the same grid (its "leading" spacing; the
@@ -551,18 +655,18 @@ class Sampler:
         """Cooperative stop (``stop_generation``, image_generator.py:784-786): the running loop ends at the next step."""
         self.cancel.value = 1
 
-    def generate_images(self, class_name: str, seeds: Sequence[int], T: int, **kwargs) -> SampleResult:
+    def generate_images(self, class_name, seeds: Sequence[int], T: int, **kwargs) -> SampleResult:
         """Start of a generation run in the reference's sense (``generate_images`` clears ``stop_requested`` before
         its first image, image_generator.py:567): resets the stop flag, then samples ``seeds``.  A stop request that
         arrives later ends this run only."""
         self.cancel.value = 0
         return self.generate_seeds(class_name, seeds, T, **kwargs)
 
-    def generate_seeds(self, class_name: str, seeds: Sequence[int], T: int, size: Tuple[int, int] = (128, 128),
+    def generate_seeds(self, class_name, seeds: Sequence[int], T: int, size: Tuple[int, int] = (128, 128),
                        return_trajectory: bool = False, save_every_n: Optional[int] = None,
                        noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
                        use_clipped_model_output: bool = False, solver_order: int = 2,
-                       algorithm_type: str = "dpmsolver++") -> SampleResult:
+                       algorithm_type: str = "dpmsolver++", guidance_scale: float = 1.0) -> SampleResult:
         """save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
         xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise.
         noise: "host" (the default: one CPU generator per image, see the module docstring) or "device" (x_T from torch's
@@ -572,14 +676,18 @@ class Sampler:
         docstring): at eta = 0 nothing beyond x_T is drawn.
         scheduler="dpmsolver++": DPM-Solver++(2M) with ``solver_order`` (1 or 2) and ``algorithm_type`` ("dpmsolver++", which
         like DDIM at eta = 0 draws nothing beyond x_T, or "sde-dpmsolver++"); it has no eta and no
-        use_clipped_model_output."""
+        use_clipped_model_output.
+        class_name: for a model registered with ``add_conditional_model`` also a sequence with one name per seed (a batch may
+        mix classes).  guidance_scale: classifier-free guidance for such a model -- 1 (the default) samples under the labels
+        alone, one UNet pass per step; any other value steps on ``eps_u + scale * (eps_c - eps_u)`` with both predictions from
+        one pass at twice the batch; 0 is the null-label model alone and runs as null labels at scale 1.  x_T, the noise
+        contract and ``noise_hashes`` do not depend on labels or scale.  A scale other than 1 on an unconditional model is a
+        ValueError."""
         _check_noise_mode(noise)
         _check_scheduler(scheduler, eta, use_clipped_model_output, solver_order, algorithm_type)
-        if class_name not in self.models:
-            raise KeyError(f"no model loaded for class '{class_name}'")
-        model = self.models[class_name]
+        model, _, guidance = self._resolve_classes(class_name, len(seeds), guidance_scale)
         sched = self.create_scheduler(T, scheduler, solver_order, algorithm_type)
-        rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output)
+        rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output, guidance=guidance)
         save_indices = None
         if return_trajectory and save_every_n is not None:
             save_indices = trajectory_save_indices([int(t) for t in sched.timesteps], save_every_n)
@@ -623,10 +731,11 @@ class Sampler:
         res.noise_hashes = hashes
         return res
 
-    def generate(self, seed: int, class_name: str, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
+    def generate(self, seed: int, class_name, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,
                  save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
-                 use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++"):
+                 use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++",
+                 guidance_scale: float = 1.0):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -639,16 +748,25 @@ class Sampler:
         ``generate_single_image(..., postprocess=True)`` does before saving (image_generator.py:449-452).
         noise: "host" or "device", as in ``generate_seeds``.
         scheduler, eta, use_clipped_model_output, solver_order, algorithm_type: the step rule, as in ``generate_seeds``.
+        class_name, guidance_scale: as in ``generate_seeds``; a sequence of names gives one image per name (``count`` must be 1
+        or its length), and with seed_is_base image i derives its seed from ITS class name.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
         """
+        if not isinstance(class_name, str):
+            names = [str(c) for c in class_name]
+            if count not in (1, len(names)):
+                raise ValueError(f"{len(names)} class names for count={count}: a sequence holds one entry per image")
+            count = len(names)
+        else:
+            names = [class_name] * count
         if seed_is_base:
-            seeds = [image_seed(seed, class_name, i) for i in range(count)]
+            seeds = [image_seed(seed, names[i], i) for i in range(count)]
         else:
             seeds = [(int(seed) + i) & 0x7FFFFFFF for i in range(count)]
         res = self.generate_images(class_name, seeds, T, size=size, return_trajectory=return_trajectory,
                                    save_every_n=save_every_n, noise=noise, scheduler=scheduler, eta=eta,
                                    use_clipped_model_output=use_clipped_model_output, solver_order=solver_order,
-                                   algorithm_type=algorithm_type)
+                                   algorithm_type=algorithm_type, guidance_scale=guidance_scale)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:
@@ -657,8 +775,11 @@ class Sampler:
             traj = [res.trajectory[i] for i in range(n_frames)] if return_trajectory else None
             return None, traj
         images = res.images.cpu().numpy()
-        if postprocess:
+        if postprocess and isinstance(class_name, str):
             images = apply_color_statistics(images, self.color_statistics.get(class_name))
+        elif postprocess:             # mixed classes: each image towards its own class statistics
+            images = np.concatenate([apply_color_statistics(images[i:i + 1], self.color_statistics.get(names[i]))
+                                     for i in range(count)])
         traj = None
         if return_trajectory:
             # list of per-step (B,3,H,W) tensors, the shape xai_integration.py consumes

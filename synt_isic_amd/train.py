@@ -356,9 +356,12 @@ class HipGradScaler:
 
 
 def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images: torch.Tensor, noise: torch.Tensor,
-                     timesteps: torch.Tensor, optimizer: HipAdam, scaler: Optional[HipGradScaler] = None):
+                     timesteps: torch.Tensor, optimizer: HipAdam, scaler: Optional[HipGradScaler] = None, class_labels=None):
     """The loop body of train_diffusion.py:215-233 in one library call (sisic_unet_train_step; sisic_unet_train_step_ext
-    when the optimizer clips or carries an EMA -- the norm is then ``optimizer.grad_norm``); returns (loss, step_taken)."""
+    when the optimizer clips or carries an EMA -- the norm is then ``optimizer.grad_norm``); returns (loss, step_taken).
+    ``class_labels``: one integer per image for a class-conditional model (sisic_unet_train_step_cond), None otherwise; the
+    library takes them as a host array, so labels on the device cost one small blocking copy per step."""
+    labels = model._labels_host(class_labels, images.shape[0])
     model._ensure_training()
     x0 = images.to(device=model.device, dtype=torch.float32).contiguous()
     nz = noise.to(device=model.device, dtype=torch.float32).contiguous()
@@ -369,7 +372,18 @@ def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images:
     scale = scaler.get_scale() if scaler is not None else 1.0
     found_ref = C.byref(found) if scaler is not None and scaler.enabled else None
     ext = optimizer._extension()
-    if ext is None:
+    if labels is not None:
+        norm = C.c_float(0.0)
+        check(_lib.load().sisic_unet_train_step_cond(model.handle, x0.data_ptr(), nz.data_ptr(),
+                                                     C.cast(t.data_ptr(), _lib.c_int64_p),
+                                                     C.cast(labels.data_ptr(), _lib.c_int64_p),
+                                                     C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p),
+                                                     B, H, W, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
+                                                     optimizer.eps, float(scale), C.byref(ext) if ext is not None else None,
+                                                     C.byref(loss), found_ref, C.byref(norm), _stream(model.device)))
+        if ext is not None:
+            optimizer._extension_done(ext, norm.value)
+    elif ext is None:
         check(_lib.load().sisic_unet_train_step(model.handle, x0.data_ptr(), nz.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
                                                 C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p), B, H, W,
                                                 optimizer.lr, optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
@@ -390,18 +404,22 @@ def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images:
     return loss.value, found.value == 0
 
 
-def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_name: str, epochs: int = 50, lr: float = LR,
-                checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
-                log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
-                ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                lr_schedule: Optional[Callable[[int], float]] = None):
-    """``train_class`` of train_diffusion.py:187-266 for one class: epochs over ``loader`` (batches of images in [-1,1],
-    [B,3,H,W]), best-loss checkpoint ``unet_{class}_best.pth`` and a checkpoint every 5 epochs.  Returns the per-epoch
-    average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG).
+def drop_labels(labels: torch.Tensor, cond_drop_prob: float, null_label: int,
+                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The label dropout of classifier-free guidance training (Ho & Salimans 2022): ONE draw ``torch.rand(B) < cond_drop_prob``
+    from ``generator`` (on the generator's device; the labels' device without one), and the labels it marks become
+    ``null_label``.  ``cond_drop_prob`` 0 still consumes the draw, so that the random stream does not depend on it."""
+    if not 0.0 <= float(cond_drop_prob) <= 1.0:
+        raise ValueError(f"cond_drop_prob must be in [0, 1], got {cond_drop_prob}")
+    dev = generator.device if generator is not None else labels.device
+    drop = torch.rand(labels.shape[0], generator=generator, device=dev) < float(cond_drop_prob)
+    return torch.where(drop.to(labels.device), torch.full_like(labels, int(null_label)), labels)
 
-    Beyond the reference, each off by default: ``max_grad_norm`` clips the global gradient norm; ``ema_decay`` keeps an EMA of
-    the weights (``ema_warmup``: EMAModel's warm-up decay) and saves it beside every checkpoint as ``..._ema.pth``;
-    ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch."""
+
+def _train_loop(model: HipUNet2DModel, loader, name: str, epochs: int, lr: float, checkpoint_dir: Optional[str], fused: bool,
+                generator: Optional[torch.Generator], log, max_grad_norm, ema_decay, ema_warmup: bool, lr_schedule,
+                cond_drop_prob: Optional[float]):
+    """the loop of train_class; cond_drop_prob not None: the loader yields (images, labels) and the model is conditional"""
     dev = model.device
     scheduler = HipDDPMScheduler(num_train_timesteps=TIMESTEPS, beta_schedule="squaredcos_cap_v2")
     ema = HipEMA(model, decay=ema_decay, use_ema_warmup=ema_warmup) if ema_decay is not None else None
@@ -410,26 +428,34 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
     scaler = HipGradScaler()
     best_loss = float("inf")
     history = []
+    conditional = cond_drop_prob is not None
 
-    def save(name: str) -> None:
-        torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_{name}.pth"))
+    def save(tag: str) -> None:
+        torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{name}_{tag}.pth"))
         if ema is not None:
             with ema.average_parameters():
-                torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{class_name}_{name}_ema.pth"))
+                torch.save(model.state_dict(), os.path.join(checkpoint_dir, f"unet_{name}_{tag}_ema.pth"))
 
     for epoch in range(epochs):
         model.train()
         epoch_loss, n_batches = 0.0, 0
-        for images in loader:
+        for item in loader:
+            images, labels = item if conditional else (item, None)
             images = images.to(dev, non_blocking=True)
             noise = torch.randn(images.shape, generator=generator, device=generator.device if generator is not None else dev)
             timesteps = torch.randint(0, TIMESTEPS, (images.size(0),), generator=generator,
                                       device=generator.device if generator is not None else dev).long()
+            if conditional:
+                # the library takes the labels as a host array (they select rows on the host side of the launch): one copy of
+                # 8 B bytes per batch from a DeviceLoader's device labels, beside the loss read-back that synchronises every
+                # step anyway; the dropout then runs on the host
+                labels = drop_labels(torch.as_tensor(labels).to("cpu", torch.int64), cond_drop_prob,
+                                     model.config.num_class_embeds - 1, generator)
             if fused:
-                value, _ = train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler)
+                value, _ = train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, class_labels=labels)
             else:
                 noisy_images = scheduler.add_noise(images, noise, timesteps)
-                noise_pred = model(noisy_images, timesteps).sample
+                noise_pred = model(noisy_images, timesteps, class_labels=labels).sample
                 loss = mse_loss(noise_pred, noise)
                 optimizer.zero_grad(set_to_none=True)
                 scaler.scale(loss).backward()
@@ -454,3 +480,43 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
         elif avg_loss < best_loss:
             best_loss = avg_loss
     return history
+
+
+def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_name: str, epochs: int = 50, lr: float = LR,
+                checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
+                log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
+                ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                lr_schedule: Optional[Callable[[int], float]] = None):
+    """``train_class`` of train_diffusion.py:187-266 for one class: epochs over ``loader`` (batches of images in [-1,1],
+    [B,3,H,W]), best-loss checkpoint ``unet_{class}_best.pth`` and a checkpoint every 5 epochs.  Returns the per-epoch
+    average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG).
+
+    Beyond the reference, each off by default: ``max_grad_norm`` clips the global gradient norm; ``ema_decay`` keeps an EMA of
+    the weights (``ema_warmup``: EMAModel's warm-up decay) and saves it beside every checkpoint as ``..._ema.pth``;
+    ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch."""
+    if model.config.num_class_embeds is not None:
+        raise ValueError("train_class trains an unconditional model; a class-conditional one takes train_conditional")
+    return _train_loop(model, loader, class_name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
+                       ema_warmup, lr_schedule, None)
+
+
+def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: float = 0.1, epochs: int = 50, lr: float = LR,
+                      checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
+                      log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
+                      ema_decay: Optional[float] = None, ema_warmup: bool = False,
+                      lr_schedule: Optional[Callable[[int], float]] = None):
+    """``train_class`` for ONE class-conditional model over all classes: ``loader`` yields ``(images, labels)`` (a
+    ``data.DeviceLoader`` over a labelled ``DeviceDataset``), the labels go to the model as ``class_labels``.  Checkpoints
+    (``unet_{name}_best.pth``, every 5 epochs, the ``_ema`` files), clipping, EMA, schedule and the returned history are
+    train_class's.
+
+    Classifier-free guidance: with probability ``cond_drop_prob`` an image trains under the null label, by convention the
+    LAST row of the table, ``num_class_embeds - 1`` -- build the model with ``n_classes + 1`` rows.  Per batch ``generator``
+    is consumed in a fixed order: the noise (``randn``), the timesteps (``randint``), then the dropout (``drop_labels``:
+    ``torch.rand(B) < cond_drop_prob``)."""
+    if model.config.num_class_embeds is None:
+        raise ValueError("train_conditional needs a class-conditional model (HipUNet2DModel(num_class_embeds=n_classes + 1))")
+    if not 0.0 <= float(cond_drop_prob) <= 1.0:
+        raise ValueError(f"cond_drop_prob must be in [0, 1], got {cond_drop_prob}")
+    return _train_loop(model, loader, name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
+                       ema_warmup, lr_schedule, float(cond_drop_prob))

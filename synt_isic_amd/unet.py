@@ -66,16 +66,17 @@ class HipUNet2DModel:
                  down_block_types: Sequence[str] = ("DownBlock2D", "DownBlock2D", "AttnDownBlock2D", "DownBlock2D"),
                  up_block_types: Sequence[str] = ("UpBlock2D", "AttnUpBlock2D", "UpBlock2D", "UpBlock2D"),
                  class_embed_type=None, norm_num_groups: int = 32, norm_eps: float = 1e-5,
-                 attention_head_dim: int = 8, **unsupported):
+                 attention_head_dim: int = 8, num_class_embeds: Optional[int] = None, **unsupported):
         if class_embed_type is not None:
-            raise NotImplementedError("class_embed_type must be None (the reference's models are unconditional)")
+            raise NotImplementedError("class_embed_type must be None (the reference's models are unconditional; a "
+                                      "class-conditional model is num_class_embeds=N, diffusers' nn.Embedding form)")
         if unsupported:
             raise NotImplementedError(f"unsupported UNet2DModel arguments: {sorted(unsupported)}")
         self.config = UNetConfig(sample_size=sample_size, in_channels=in_channels, out_channels=out_channels,
                                  layers_per_block=layers_per_block, block_out_channels=tuple(block_out_channels),
                                  down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types),
                                  norm_num_groups=norm_num_groups, norm_eps=norm_eps,
-                                 attention_head_dim=attention_head_dim)
+                                 attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds)
         self.config.validate()
         if attention_head_dim != 8:
             raise NotImplementedError("attention_head_dim must be 8 (the HIP attention kernel is built for d=8)")
@@ -260,7 +261,10 @@ class HipUNet2DModel:
         c.n_freqs = freqs.numel()
         c.freqs = C.cast(freqs.data_ptr(), _lib.c_float_p)
         h = C.c_void_p()
-        check(lib.sisic_unet_create(ops.context(self._device), C.byref(c), C.byref(h)))
+        if cfg.num_class_embeds is None:
+            check(lib.sisic_unet_create(ops.context(self._device), C.byref(c), C.byref(h)))
+        else:
+            check(lib.sisic_unet_create_cond(ops.context(self._device), C.byref(c), int(cfg.num_class_embeds), C.byref(h)))
         self._handle = h
         if self._latency_mode:
             check(lib.sisic_unet_set_latency_mode(h, 1))
@@ -319,11 +323,37 @@ class HipUNet2DModel:
             raise ValueError(f"timestep has {t.numel()} entries for a batch of {batch}")
         return t.contiguous()
 
+    def _labels_host(self, class_labels, batch: int) -> Optional[torch.Tensor]:
+        """diffusers' two checks (UNet2DModel.forward), then the labels as host int64 [batch], each inside the table"""
+        n = self.config.num_class_embeds
+        if n is None:
+            if class_labels is not None:
+                raise ValueError("class_embedding needs to be initialized in order to use class conditioning")
+            return None
+        if class_labels is None:
+            raise ValueError("class_labels should be provided when doing class conditioning")
+        if torch.is_tensor(class_labels):
+            if class_labels.dtype.is_floating_point or class_labels.dtype == torch.bool:
+                raise ValueError(f"class_labels must be integers, got {class_labels.dtype}")
+            lab = class_labels.detach().to("cpu").to(torch.int64).reshape(-1)
+        else:
+            lab = torch.as_tensor(class_labels)
+            if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+                raise ValueError(f"class_labels must be integers, got {lab.dtype}")
+            lab = lab.to(torch.int64).reshape(-1)
+        if lab.numel() == 1:
+            lab = lab.expand(batch)
+        elif lab.numel() != batch:
+            raise ValueError(f"class_labels has {lab.numel()} entries for a batch of {batch}")
+        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= n):
+            raise ValueError(f"class_labels must lie in [0, {n}), got {int(lab.min())} .. {int(lab.max())}")
+        return lab.contiguous()
+
     @torch.no_grad()
     def __call__(self, sample: torch.Tensor, timestep: Union[torch.Tensor, float, int],
                  class_labels=None, return_dict: bool = True):
-        if class_labels is not None:
-            raise NotImplementedError("class conditioning is not part of the reference's models")
+        # (before the handle: the two ValueErrors are diffusers' and need no GPU; a malformed sample is refused below)
+        labels = self._labels_host(class_labels, sample.shape[0]) if sample.dim() == 4 else None
         h = self.handle
         if sample.device != self._device:
             raise RuntimeError(f"sample is on {sample.device} but the model is on {self._device}")
@@ -334,14 +364,22 @@ class HipUNet2DModel:
         t = self._timesteps_host(timestep, B)
         out = ops.empty((B, self.config.out_channels, H, W), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        lab = C.cast(labels.data_ptr(), _lib.c_int64_p) if labels is not None else None
         if self.training and self._train_begun:
             # training mode with an optimizer: the same kernels, every activation kept for loss.backward()
-            check(_lib.load().sisic_unet_train_forward(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
-                                                       out.data_ptr(), B, H, W, stream))
+            if labels is not None:
+                check(_lib.load().sisic_unet_train_forward_cond(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p), lab,
+                                                                out.data_ptr(), B, H, W, stream))
+            else:
+                check(_lib.load().sisic_unet_train_forward(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
+                                                           out.data_ptr(), B, H, W, stream))
             out._sisic_model = self
             # the tape refers to the input by address (conv_in's weight gradient reads it in the backward pass): keep the
             # tensor alive until the next forward, as autograd's graph would
             self._tape_input = x
+        elif labels is not None:
+            check(_lib.load().sisic_unet_forward_cond(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p), lab,
+                                                      out.data_ptr(), B, H, W, stream))
         else:
             check(_lib.load().sisic_unet_forward(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p), out.data_ptr(),
                                                  B, H, W, stream))

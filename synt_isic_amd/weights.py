@@ -16,10 +16,11 @@ reference architecture.  The recipe is fixed here once ("fixture descriptor"):
 """
 from __future__ import annotations
 
+import dataclasses
 import hashlib
 import math
 from collections import OrderedDict
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -50,9 +51,25 @@ def _fill(spec, seed: int) -> "OrderedDict[str, torch.Tensor]":
     return sd
 
 
-def synthetic_unet_state_dict(seed: int = DEFAULT_WEIGHT_SEED,
-                              cfg: UNetConfig = UNetConfig()) -> "OrderedDict[str, torch.Tensor]":
-    return _fill(unet_param_spec(cfg), seed)
+CLASS_TABLE_SEED_OFFSET = 0x636C73          # the class embedding's own generator is seeded with seed + this
+
+
+def synthetic_unet_state_dict(seed: int = DEFAULT_WEIGHT_SEED, cfg: UNetConfig = UNetConfig(),
+                              num_class_embeds: Optional[int] = None) -> "OrderedDict[str, torch.Tensor]":
+    """``num_class_embeds=N`` (or a ``cfg`` that has it) adds ``class_embedding.weight`` ~ N(0,1), nn.Embedding's default
+    initialisation, at its place in the state dict.  The table comes from a generator of its own, so the other 330 tensors
+    are those of the unconditional call bit for bit (the goldens are computed from them)."""
+    if num_class_embeds is not None:
+        cfg = dataclasses.replace(cfg, num_class_embeds=num_class_embeds)
+    plain = _fill(unet_param_spec(dataclasses.replace(cfg, num_class_embeds=None)), seed)
+    if cfg.num_class_embeds is None:
+        return plain
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed) + CLASS_TABLE_SEED_OFFSET)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape in unet_param_spec(cfg).items():
+        sd[name] = plain[name] if name in plain else torch.randn(shape, generator=g, dtype=torch.float32)
+    return sd
 
 
 def state_dict_sha256(sd: Dict[str, torch.Tensor]) -> str:
