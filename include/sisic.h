@@ -329,7 +329,8 @@ int sisic_sample_frames(sisic_unet*, float* x, int B, int H, int W, int T, const
  * (r0, r1) -> elements 4q, 4q+1 and (r2, r3) -> 4q+2, 4q+3 by Box-Muller (cos, sin) with u1 = ((r >> 8) + 1) * 2^-24,
  * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T; tag 2: the noise
  * interventions of sisic_intervene; tag 3: the bootstrap resamples and tag 4: the permutation resamples of
- * sisic_resample_diffs (raw words, step = the resample); tag 16 + k: tensor k of a classifier randomised by
+ * sisic_resample_diffs (raw words, step = the resample); tag 5: the known-region noise and tag 6: the jump noise of the
+ * edit epilogue (sisic_*_step_edit below); tag 16 + k: tensor k of a classifier randomised by
  * sisic_resnet_randomize (step = the trial).  A pure function of
  * (seed, step, tag, element): independent of the batch, the GPU count, graph or eager mode.  1 <= n_per_image <= 2^34.
  * seeds: HOST uint64 [B], read before the call returns.
@@ -413,6 +414,57 @@ int sisic_sample_frames_cond(sisic_unet*, float* x, int B, int H, int W, int T, 
  * surface: a caller's own loop over two sisic_unet_forward_cond passes, this and a sisic_*_step reproduces the guided loop
  * bit for bit).  Any alignment, any n >= 1; out may be either input.                                                      */
 int sisic_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream);
+
+/* ---- image editing: the inpainting epilogue of the step kernels (RePaint, Lugmayr et al. 2022) -------
+ * sisic_{ddpm,ddim,dpmpp}_step_rng with an epilogue applied to the rule's result u in the register that holds it, before the
+ * store (no second pass over the latent).  Per element, one fp32 rounding per operation, no FMA contraction, in this order:
+ *     k   = ck * x0k + sk * e1              (sk == 0: k = ck * x0k, e1 is not drawn)
+ *     y   = m * k + (1 - m) * u             (m * k, 1 - m, (1 - m) * u, then the sum)
+ *     out = ja * y + jb * e2                (jb == 0: out = y exactly, ja is not applied, e2 is not drawn)
+ * x0k:  the known image, dev float [B, C, HW] in [-1, 1].  It must be FINITE everywhere, also where the mask is 0: the blend
+ *       multiplies it by (a rounding of) 0, and 0 * NaN is NaN.
+ * mask: dev float [B, 1, HW], broadcast over the C channels; 1 keeps the known pixel, 0 synthesises, values in between blend
+ *       (soft seams).  n_per_image must equal C * HW.
+ * e1, e2: the device-noise contract above with the image's seed at step index `step`, tag 5 (e1, the known region noised to
+ *       the level the step arrives at) and tag 6 (e2, the jump back up the schedule).  z is drawn under tag 0 as in the _rng
+ *       entries, or not at all when sigma == 0.
+ * {ck, sk, ja, jb}: the edit row of the step.  For a step arriving at abar_prev: ck = abar_prev^.5, sk = (1 - abar_prev)^.5
+ *       (the last step: 1, 0).  For a RePaint jump from there up to abar_target: ja = (abar_target / abar_prev)^.5,
+ *       jb = (1 - abar_target / abar_prev)^.5, the j forward steps composed into one Gaussian draw; no jump: 1, 0.
+ * sisic_dpmpp_step_edit: hist stays the model's predicted x0; the epilogue does not touch it.
+ * Alignment: the vector path needs n_per_image % 4 == 0, HW % 4 == 0 (a float4 of the latent then maps to one float4 of the
+ * mask row) and every tensor on a 16-byte line; anything else takes an element-by-element path with the same values.
+ * out may be x; x0k and mask alias no output.  seeds_dev: DEVICE uint64 [B], as in the _rng entries.                      */
+int sisic_ddpm_step_edit(sisic_ctx*, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
+                         float c1, float sigma, float clip, const float* x0k, const float* mask, int C, int64_t HW, float ck,
+                         float sk, float ja, float jb, void* stream);
+int sisic_ddim_step_edit(sisic_ctx*, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
+                         float c_dir, float sigma, float clip, int use_clipped_model_output, const float* x0k,
+                         const float* mask, int C, int64_t HW, float ck, float sk, float ja, float jb, void* stream);
+int sisic_dpmpp_step_edit(sisic_ctx*, const float* eps, const float* x, float* hist, float* out, int B, int64_t n_per_image,
+                          const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float cx,
+                          float k0, float sigma, float k1, float clip, const float* x0k, const float* mask, int C, int64_t HW,
+                          float ck, float sk, float ja, float jb, void* stream);
+/* The sampling loop with the epilogue in every step: sisic_sample_frames_cond's arguments in device-noise mode (seeds: HOST
+ * uint64 [B], REQUIRED; there is no noise buffer), with class_labels == NULL meaning an unconditional handle (null_label and
+ * guidance_scale are then not read), plus
+ *   x0k:       dev float [B, C, H, W], mask: dev float [B, 1, H, W] (as above; neither is x),
+ *   edit_rows: host float [T * 4], row i = {ck, sk, ja, jb} of step i, all finite.
+ * timesteps may go up as well as down: after a jump (jb != 0) the next entry is a noisier level again (the expanded RePaint
+ * schedule; the rule's row of an entry is that of its own timestep on the run's grid).  Step i draws z, e1 and e2 at step
+ * index step0 + i, so a run cut into several calls (T <= 1000 per call) with their offsets is bit-equal to the uncut run
+ * under DDPM and DDIM.  SISIC_RULE_DPMPP: every edit row must have jb == 0 (SISIC_EINVAL otherwise): a jump invalidates the
+ * history.  traj frames are the values after the epilogue.  Eager and graph-replayed: in graph mode the handle keeps its
+ * own copies of x0k, mask and edit_rows, so a captured step serves every image, mask and edit table at a shape; edited or not
+ * is part of the key of a captured step, like the rule and guidance (alternating re-captures: sisic_unet_graph_builds).  A
+ * call of another entry after this one returns the bits it returned before.                                               */
+int sisic_sample_frames_edit(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                             float clip, int rule, int rule_flags, const uint64_t* seeds, int step0,
+                             const int64_t* class_labels, int null_label, float guidance_scale, const float* x0k,
+                             const float* mask, const float* edit_rows, float* traj, const int* traj_row, uint8_t* out_u8,
+                             const volatile int* cancel, int* steps_done, void* stream);
 
 /* ---- training step (diffusion/train_diffusion.py:201-266) -----------------------------------
  * fp32 throughout.  The reference wraps the forward in torch.cuda.amp.autocast() (fp16 matmuls/convolutions) and scales the

@@ -168,6 +168,22 @@ SIGNATURES = {
                                            C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "sisic_guide_eps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sisic_ddpm_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_void_p]),
+    "sisic_ddim_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_void_p]),
+    "sisic_dpmpp_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                        C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.c_void_p]),
+    "sisic_sample_frames_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
+                                           C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, c_int64_p, C.c_int,
+                                           C.c_float, C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.POINTER(C.c_int),
+                                           C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "sisic_unet_train_begin": (C.c_int, [C.c_void_p]),
     "sisic_unet_train_end": (C.c_int, [C.c_void_p]),
     "sisic_add_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -246,6 +246,47 @@ int sisic_dpmpp_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float
                                sqrt_alpha_prod, cx, k0, sigma, k1, clip, static_cast<hipStream_t>(stream));
 }
 
+// the single edited steps: the _rng entries' arguments, the known image, the mask and the edit row
+static int step_edit(sisic_ctx* ctx, const char* what, int rule, int flags, const float* eps, const float* x, float* hist,
+                     float* out, int B, int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, const float* row,
+                     float clip, const float* x0k, const float* mask, int Cn, int64_t HW, float ck, float sk, float ja, float jb,
+                     void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "%s: null context or empty batch", what);
+    SISIC_REQUIRE(Cn > 0 && HW > 0 && (int64_t)Cn * HW == n_per_image, "%s: C = %d, HW = %lld for images of %lld elements", what,
+                  Cn, (long long)HW, (long long)n_per_image);
+    const float erow[4] = {ck, sk, ja, jb};
+    return launch_step_edit(ctx, rule, flags, eps, nullptr, 1.0f, nullptr, x, hist, out, (int64_t)B * n_per_image, n_per_image,
+                            HW, seeds_dev, step, row, erow, nullptr, nullptr, nullptr, x0k, mask, clip,
+                            static_cast<hipStream_t>(stream));
+}
+
+int sisic_ddpm_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
+                         float c1, float sigma, float clip, const float* x0k, const float* mask, int C, int64_t HW, float ck,
+                         float sk, float ja, float jb, void* stream) {
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma};
+    return step_edit(ctx, "ddpm_step_edit", STEP_RULE_DDPM, 0, eps, x, nullptr, out, B, n_per_image, seeds_dev, step, row, clip,
+                     x0k, mask, C, HW, ck, sk, ja, jb, stream);
+}
+
+int sisic_ddim_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
+                         float c_dir, float sigma, float clip, int use_clipped_model_output, const float* x0k,
+                         const float* mask, int C, int64_t HW, float ck, float sk, float ja, float jb, void* stream) {
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma};
+    return step_edit(ctx, "ddim_step_edit", STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x,
+                     nullptr, out, B, n_per_image, seeds_dev, step, row, clip, x0k, mask, C, HW, ck, sk, ja, jb, stream);
+}
+
+int sisic_dpmpp_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int B,
+                          int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod,
+                          float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip, const float* x0k,
+                          const float* mask, int C, int64_t HW, float ck, float sk, float ja, float jb, void* stream) {
+    const float row[6] = {sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1};
+    return step_edit(ctx, "dpmpp_step_edit", STEP_RULE_DPMPP, 0, eps, x, hist, out, B, n_per_image, seeds_dev, step, row, clip,
+                     x0k, mask, C, HW, ck, sk, ja, jb, stream);
+}
+
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {
     SISIC_REQUIRE(ctx, "denorm_u8: null context");
     return launch_denorm_u8(ctx, x, out, B, C, H, W, static_cast<hipStream_t>(stream));

@@ -236,6 +236,14 @@ int launch_step_guided(sisic_ctx*, int rule, int flags, const float* eps_c, cons
 int launch_step_guided_indexed(sisic_ctx*, int rule, int flags, const float* eps2, float* x2, float* hist, int64_t n,
                                int64_t n_per_image, const void* state, const float* coef, const int* zrow,
                                const uint64_t* seeds_dev, const float* cond, float clip, hipStream_t s);
+// every edited step (the inpainting epilogue of elementwise.hip; generated noise only).  eps_u: a guided step, out [2n].
+// state set: the replayed form, which reads its rows from coef_dev / erows_dev (and w from cond); otherwise row / erow are host
+// rows and step, w launch arguments.  hw: H * W, the mask's row [B, 1, hw] is broadcast over n_per_image / hw channels.
+int launch_step_edit(sisic_ctx*, int rule, int flags, const float* eps, const float* eps_u, float w, const float* cond,
+                     const float* x, float* hist, float* out, int64_t n, int64_t n_per_image, int64_t hw,
+                     const uint64_t* seeds_dev, uint32_t step, const float* row, const float* erow, const void* state,
+                     const float* coef_dev, const float* erows_dev, const float* x0k, const float* mask, float clip,
+                     hipStream_t s);
 int launch_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s);
 // conditional loop: out[b][r] = table[(step * L + slot[b]) * R + r] for the `rows` samples of a pass; cond: LoopCond
 // {w, L, -, -, slot[rows]}; state != NULL: the step index is the loop state's (graph-replayed form)

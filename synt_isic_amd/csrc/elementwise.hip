@@ -2,6 +2,7 @@
 //   * ddpm_step_kernel  : fused DDPMScheduler.step, bit-exact vs torch CPU
 //   * ddim_step_kernel  : fused DDIMScheduler.step (epsilon prediction), bit-exact vs torch CPU
 //   * dpm_step_kernel   : fused DPM-Solver++(2M) step with its one-step history, bit-exact vs torch CPU
+//   * step_edit_kernel  : the three steps with the inpainting epilogue (RePaint) applied before the store
 //   * denorm_u8_kernel  : clamp((x+1)/2,0,1)*255 -> uint8 HWC (image_generator.py:441-447)
 //   * temb_mlp_kernel   : sinusoidal timestep embedding -> Linear -> SiLU -> Linear -> SiLU
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
@@ -74,15 +75,16 @@ struct PhiloxNoise {
     const uint64_t* seeds;    // [B] device
     int64_t npi;              // floats per image
     uint32_t step;            // step index of the run (position in its timestep list)
+    uint32_t tag = 0u;        // the stream of the contract (sisic.h): 0 = a step's z; the edit epilogue draws under 5 and 6
     __device__ __forceinline__ bool present() const { return true; }
     __device__ __forceinline__ bool vec_ok() const { return (npi & 3) == 0; }     // otherwise a block straddles two images
     __device__ __forceinline__ float4 get4(int64_t i4) const {
         const int64_t q_per_image = npi >> 2, b = i4 / q_per_image;
-        return noise_normal4(seeds[b], (uint32_t)(i4 - b * q_per_image), step, 0u);
+        return noise_normal4(seeds[b], (uint32_t)(i4 - b * q_per_image), step, tag);
     }
     __device__ __forceinline__ float get1(int64_t i) const {
         const int64_t b = i / npi;
-        return noise_normal1(seeds[b], i - b * npi, step, 0u);
+        return noise_normal1(seeds[b], i - b * npi, step, tag);
     }
 };
 
@@ -116,11 +118,65 @@ struct GuidedEps {
     __device__ __forceinline__ float get1(int64_t i) const { return guide_one(ec[i], eu[i], w); }
 };
 
+// What happens to a step's result before it is stored: nothing, or the inpainting epilogue (RePaint, Lugmayr et al. 2022;
+// DESIGN.md section 2).  The epilogue re-imposes the known image x0k at the noise level the step arrives at, under the mask m
+// (1 = keep the known pixel), and optionally jumps the result back up the schedule.  One fp32 rounding per operation, in this
+// order (sisic.h, sisic_ddpm_step_edit):
+//   k = ck * x0k [+ sk * e1];   y = m * k + (1 - m) * u;   out = jb != 0 ? ja * y + jb * e2 : y
+// e1, e2: the image's Philox normals at this step's index under tags 5 and 6, drawn only where sk / jb are not zero.  x0k and
+// m are two more read streams of the launch (m a third as wide: it is broadcast over the channels), u never leaves its
+// register: the known region costs no second pass over the latent.
+struct NoEdit {
+    static constexpr bool on = false;
+};
+
+constexpr uint32_t NOISE_TAG_KNOWN = 5u, NOISE_TAG_JUMP = 6u;
+
+__device__ __forceinline__ float edit_one(float u, float x0k, float m, float e1, float e2, float ck, float sk, float ja,
+                                          float jb) {
+#pragma clang fp contract(off)
+    float k = ck * x0k;
+    if (sk != 0.0f) k = k + sk * e1;
+    const float a = m * k;
+    const float om = 1.0f - m;
+    const float b = om * u;
+    float y = a + b;
+    if (jb != 0.0f) y = ja * y + jb * e2;
+    return y;
+}
+
+struct InpaintEdit {
+    static constexpr bool on = true;
+    const float* __restrict__ x0k;      // [B, C, HW], finite
+    const float* __restrict__ mask;     // [B, 1, HW]
+    const uint64_t* seeds;              // [B] device
+    int64_t npi, hw;                    // C * HW and HW
+    uint32_t step;
+    float ck, sk, ja, jb;
+    // (get4: npi and hw are multiples of 4, so float4 i4 of the latent lies in one image, one channel and one float4 of m)
+    __device__ __forceinline__ float4 apply4(int64_t i4, float4 u) const {
+        const int64_t q_per_image = npi >> 2, b = i4 / q_per_image, q = i4 - b * q_per_image, hw4 = hw >> 2;
+        const float4 kv = reinterpret_cast<const float4*>(x0k)[i4];
+        const float4 mv = reinterpret_cast<const float4*>(mask)[b * hw4 + q % hw4];
+        float4 e1 = make_float4(0.f, 0.f, 0.f, 0.f), e2 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (sk != 0.0f) e1 = noise_normal4(seeds[b], (uint32_t)q, step, NOISE_TAG_KNOWN);
+        if (jb != 0.0f) e2 = noise_normal4(seeds[b], (uint32_t)q, step, NOISE_TAG_JUMP);
+        return make_float4(edit_one(u.x, kv.x, mv.x, e1.x, e2.x, ck, sk, ja, jb), edit_one(u.y, kv.y, mv.y, e1.y, e2.y, ck, sk, ja, jb),
+                           edit_one(u.z, kv.z, mv.z, e1.z, e2.z, ck, sk, ja, jb), edit_one(u.w, kv.w, mv.w, e1.w, e2.w, ck, sk, ja, jb));
+    }
+    __device__ __forceinline__ float apply1(int64_t i, float u) const {
+        const int64_t b = i / npi, r = i - b * npi;
+        const float e1 = sk != 0.0f ? noise_normal1(seeds[b], r, step, NOISE_TAG_KNOWN) : 0.f;
+        const float e2 = jb != 0.0f ? noise_normal1(seeds[b], r, step, NOISE_TAG_JUMP) : 0.f;
+        return edit_one(u, x0k[i], mask[b * hw + r % hw], e1, e2, ck, sk, ja, jb);
+    }
+};
+
 // out may alias x (the loop steps in place): every element is read before it is written, by the thread that writes it
 // (E::dup: vec4 only with n a multiple of 4, so that out + n is aligned like out)
-template <class R, class Z, class E>
+template <class R, class Z, class E, class D = NoEdit>
 __device__ __forceinline__ void step_body(const E es, const float* x, float* out, int64_t n, bool vec4,
-                                          const R rule, const Z zs) {
+                                          const R rule, const Z zs, const D ed = D{}) {
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -137,17 +193,20 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
             r.y = rule(e.y, xv.y, zv.y, noise);
             r.z = rule(e.z, xv.z, zv.z, noise);
             r.w = rule(e.w, xv.w, zv.w, noise);
+            if constexpr (D::on) r = ed.apply4(i, r);
             o4[i] = r;
             if constexpr (E::dup) o4[n4 + i] = r;
         }
         for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
-            const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            if constexpr (D::on) r = ed.apply1(i, r);
             out[i] = r;
             if constexpr (E::dup) out[n + i] = r;
         }
     } else {
         for (int64_t i = t0; i < n; i += stride) {
-            const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
+            if constexpr (D::on) r = ed.apply1(i, r);
             out[i] = r;
             if constexpr (E::dup) out[n + i] = r;
         }
@@ -210,9 +269,9 @@ struct DpmRule {
 };
 
 // step_body with the history stream.  out may alias x; hist aliases nothing else (and stays n wide under E::dup).
-template <class Z, class E>
+template <class Z, class E, class D = NoEdit>
 __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float* hist, float* out, int64_t n,
-                                              bool vec4, const DpmRule rule, const Z zs) {
+                                              bool vec4, const DpmRule rule, const Z zs, const D ed = D{}) {
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const bool second = rule.k1 != 0.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -233,6 +292,7 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
             r.y = rule(e.y, xv.y, zv.y, hv.y, noise, second, m.y);
             r.z = rule(e.z, xv.z, zv.z, hv.z, noise, second, m.z);
             r.w = rule(e.w, xv.w, zv.w, hv.w, noise, second, m.w);
+            if constexpr (D::on) r = ed.apply4(i, r);      // (the history stays the model's x0)
             h4[i] = m;
             o4[i] = r;
             if constexpr (E::dup) o4[n4 + i] = r;
@@ -241,7 +301,8 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
     }
     for (int64_t i = tail; i < n; i += stride) {
         float m;
-        const float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
+        float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
+        if constexpr (D::on) r = ed.apply1(i, r);
         hist[i] = m;
         out[i] = r;
         if constexpr (E::dup) out[n + i] = r;
@@ -705,6 +766,123 @@ int launch_step_guided_indexed(sisic_ctx* ctx, int rule, int flags, const float*
         if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 0>));
     }
 #undef SISIC_GUIDED
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// ---- the edited steps (sisic_*_step_edit, sisic_sample_frames_edit) -------------------------------------------------------
+// rule x {plain, guided} with the inpainting epilogue, generated noise only.  One kernel serves the eager and the replayed
+// form: with st set, the rule's row, the edit row and the step index are read by the loop's step (and w from cond[0]);
+// otherwise they are the launch's own.
+struct EditStepArgs {
+    const float* ec;                    // eps [n]; guided: the conditional half
+    const float* eu;                    // guided: the null-label half
+    const float* cond;                  // guided, replayed: LoopCond (w at cond[0])
+    const float* x;
+    float* out;                         // may be x; guided: [2n]
+    float* hist;                        // DPM-Solver++
+    const float* x0k;
+    const float* mask;
+    const uint64_t* seeds;
+    const LoopState* st;                // replayed form, or nullptr
+    const float* coef;                  // replayed form: the rule's rows ...
+    const float* erows;                 // ... and the edit rows {ck, sk, ja, jb}
+    int64_t n, npi, hw;
+    StepRow row;
+    float er[4];
+    float w, clip;
+    uint32_t step;
+    int vec4;
+};
+
+template <int WIDTH>
+__device__ __forceinline__ void edit_step_rows(const EditStepArgs& a, StepRow& row, float (&er)[4], uint32_t& step, float& w) {
+    row = a.row;
+    for (int k = 0; k < 4; ++k) er[k] = a.er[k];
+    step = a.step;
+    w = a.w;
+    if (a.st) {
+        const int i = a.st->step;
+        step = (uint32_t)(a.st->step_base + i);
+        for (int k = 0; k < WIDTH; ++k) row.v[k] = a.coef[WIDTH * i + k];
+        for (int k = 0; k < 4; ++k) er[k] = a.erows[4 * i + k];
+        if (a.cond) w = a.cond[0];
+    }
+}
+
+template <class R, bool GUIDED>
+__global__ void __launch_bounds__(256)
+step_edit_kernel(const EditStepArgs a) {
+    StepRow row; float er[4], w; uint32_t step;
+    edit_step_rows<5>(a, row, er, step, w);
+    const PhiloxNoise zs{a.seeds, a.npi, step};
+    const InpaintEdit ed{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
+    if constexpr (GUIDED) step_body(GuidedEps{a.ec, a.eu, w}, a.x, a.out, a.n, a.vec4 != 0, row_rule<R>(row, a.clip), zs, ed);
+    else step_body(PlainEps{a.ec}, a.x, a.out, a.n, a.vec4 != 0, row_rule<R>(row, a.clip), zs, ed);
+}
+
+template <bool GUIDED>
+__global__ void __launch_bounds__(256)
+dpm_step_edit_kernel(const EditStepArgs a) {
+    StepRow row; float er[4], w; uint32_t step;
+    edit_step_rows<6>(a, row, er, step, w);
+    const PhiloxNoise zs{a.seeds, a.npi, step};
+    const InpaintEdit ed{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
+    const DpmRule rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip};
+    if constexpr (GUIDED) dpm_step_body(GuidedEps{a.ec, a.eu, w}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
+    else dpm_step_body(PlainEps{a.ec}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
+}
+
+// One launcher for every edited step.  eps_u: a guided step (out is then [2n]).  state/coef_dev/erows_dev: the replayed form
+// (row, erow, step and w unused; cond holds w when guided); otherwise row [rule's width] and erow [4] are host rows.
+int launch_step_edit(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* eps_u, float w, const float* cond,
+                     const float* x, float* hist, float* out, int64_t n, int64_t n_per_image, int64_t hw,
+                     const uint64_t* seeds_dev, uint32_t step, const float* row, const float* erow, const void* state,
+                     const float* coef_dev, const float* erows_dev, const float* x0k, const float* mask, float clip,
+                     hipStream_t s) {
+    SISIC_TRY(check_rule(rule, flags));
+    const char* name = rule_name(rule);
+    SISIC_REQUIRE(eps && x && out && seeds_dev && x0k && mask && n > 0, "%s_edit: null tensor or empty", name);
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps && hist != eps_u),
+                  "dpmpp_step_edit: the history is missing or aliases another tensor");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "%s_edit: %lld elements are not whole images of %lld", name, (long long)n, (long long)n_per_image);
+    SISIC_REQUIRE(hw > 0 && n_per_image % hw == 0, "%s_edit: an image of %lld elements is not whole channels of %lld", name,
+                  (long long)n_per_image, (long long)hw);
+    SISIC_REQUIRE(x0k != out && mask != out && x0k != hist && mask != hist, "%s_edit: the known image or the mask aliases an output", name);
+    EditStepArgs a{};
+    if (state) {
+        SISIC_REQUIRE(coef_dev && erows_dev && (!eps_u || cond), "%s_edit (indexed): null table", name);
+    } else {
+        SISIC_REQUIRE(row && erow, "%s_edit: null row", name);
+        SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
+        for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) a.row.v[k] = row[k];
+        for (int k = 0; k < 4; ++k) {
+            SISIC_REQUIRE(std::isfinite(erow[k]), "%s_edit: edit row {%g, %g, %g, %g}", name, erow[0], erow[1], erow[2], erow[3]);
+            a.er[k] = erow[k];
+        }
+    }
+    ProfileScope prof(ctx, s, PK_DDPM, (eps_u ? 32.0 : 20.0) * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(x) |
+                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x0k) |
+                         reinterpret_cast<uintptr_t>(mask);
+    a.ec = eps; a.eu = eps_u; a.cond = state ? cond : nullptr; a.x = x; a.out = out; a.hist = hist; a.x0k = x0k; a.mask = mask;
+    a.seeds = seeds_dev; a.st = static_cast<const LoopState*>(state); a.coef = coef_dev; a.erows = erows_dev;
+    a.n = n; a.npi = n_per_image; a.hw = hw; a.w = w; a.clip = clip; a.step = step;
+    a.vec4 = (al & 15) == 0 && (n_per_image & 3) == 0 && (hw & 3) == 0;
+    const int64_t work = a.vec4 ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
+#define SISIC_EDIT(K) hipLaunchKernelGGL(K, grid, block, 0, s, a)
+    if (rule == STEP_RULE_DPMPP) {
+        if (eps_u) SISIC_EDIT(dpm_step_edit_kernel<true>); else SISIC_EDIT(dpm_step_edit_kernel<false>);
+    } else if (rule == STEP_RULE_DDPM) {
+        if (eps_u) SISIC_EDIT((step_edit_kernel<DdpmRule, true>)); else SISIC_EDIT((step_edit_kernel<DdpmRule, false>));
+    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+        if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<true>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<true>, false>));
+    } else {
+        if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<false>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<false>, false>));
+    }
+#undef SISIC_EDIT
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

@@ -713,7 +713,8 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)sisic_unet_train_end(u);
     (void)hipDeviceSynchronize();
     pool_release_all(u);
-    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables})
+    for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables, u->edit_x0k, u->edit_mask,
+                     u->edit_rows})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -834,10 +835,18 @@ struct CondCall {
     float w = 1.0f;
 };
 
+// An edited call of the loop (sisic_sample_frames_edit): the known image, the mask (both device) and the host edit rows [T][4]
+struct EditCall {
+    const float* x0k;
+    const float* mask;
+    const float* rows;
+};
+static constexpr size_t LOOP_EDIT_FLOATS = 4 * 1000;
+
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
 // launches for every step, so that a captured step can be replayed.  cg: a conditional call, or nullptr.
 static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
-                     const CondCall* cg, hipStream_t s) {
+                     const CondCall* cg, bool edit, hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
@@ -849,7 +858,15 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
         SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
         SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
     }
-    if (cg && cg->guided)
+    if (edit) {
+        // (the library's copies of the call's image, mask and rows: a captured step serves every edited call at the shape)
+        const bool guided = cg && cg->guided;
+        SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, 1.0f,
+                                   guided ? u->cond_tables : nullptr,
+                                   u->x_work, rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, u->x_work, (int64_t)n,
+                                   (int64_t)(n / B), (int64_t)H * W, seeds, 0u, nullptr, nullptr, state, coef_dev, u->edit_rows,
+                                   u->edit_x0k, u->edit_mask, clip, s));
+    } else if (cg && cg->guided)
         SISIC_TRY(launch_step_guided_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work,
                                              rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, (int64_t)n, (int64_t)(n / B), state,
                                              coef_dev, zrow_dev, rng ? seeds : nullptr, u->cond_tables, clip, s));
@@ -872,8 +889,8 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
 // rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
 static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, int rule,
-                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, float* traj, const int* traj_row,
-                        const volatile int* cancel, int* steps_done, hipStream_t caller) {
+                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, const EditCall* ed, float* traj,
+                        const int* traj_row, const volatile int* cancel, int* steps_done, hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
@@ -904,6 +921,15 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         for (int i = 0; i < T; ++i) zr[i] = (noise && coef[(size_t)i * cw + 4] != 0.0f) ? zi++ : -1;
     }
     SISIC_TRY(unet_stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
+    if (ed) {
+        const size_t nm = (size_t)B * H * W;
+        SISIC_TRY(unet_grow(&u->edit_x0k, &u->edit_x0k_cap, n));
+        SISIC_TRY(unet_grow(&u->edit_mask, &u->edit_mask_cap, nm));
+        SISIC_TRY(unet_grow(&u->edit_rows, &u->edit_rows_cap, LOOP_EDIT_FLOATS));
+        SISIC_HIP(hipMemcpyAsync(u->edit_x0k, ed->x0k, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SISIC_HIP(hipMemcpyAsync(u->edit_mask, ed->mask, nm * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SISIC_TRY(unet_stage_upload(u, ed->rows, (size_t)T * 4, u->edit_rows, s));
+    }
     SISIC_HIP(hipMemcpyAsync(u->x_work, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (guided) SISIC_HIP(hipMemcpyAsync(u->x_work + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
@@ -927,32 +953,36 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     // (labels and the guidance scale live in cond_tables and change nothing a captured launch holds; whether the call is
     //  conditional, and whether it is guided, change the launches themselves)
     const void* cond_tab = cg ? u->cond_tables : nullptr;
+    const bool edit = ed != nullptr;
+    const void* ex = edit ? u->edit_x0k : nullptr;
+    const void* em = edit ? u->edit_mask : nullptr;
+    const void* er = edit ? u->edit_rows : nullptr;
     auto reusable = [&]() -> bool {
         const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[7] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab};
+        const void* ptrs[10] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
                   u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
                   u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags && u->loop_key.cond == (cg != nullptr) &&
-                  u->loop_key.guided == guided;
-        for (int k = 0; k < 7; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
+                  u->loop_key.guided == guided && u->loop_key.edit == edit;
+        for (int k = 0; k < 10; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
     if (rc == SISIC_OK && !reusable()) {
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, s);
+        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
     if (rc == SISIC_OK && i < T) {
         if (!reusable()) {
             const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[7] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab};
+            const void* ptrs[10] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, s);
+            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -966,8 +996,8 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
             u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
             u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
-            u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided;
-            for (int k = 0; k < 7; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided; u->loop_key.edit = edit;
+            for (int k = 0; k < 10; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
         }
@@ -998,7 +1028,7 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
 // guidance scale w), or nullptr for an unconditional handle.
 static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                          float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
-                         const int64_t* labels, int null_label, float w, float* traj, const int* traj_row,
+                         const int64_t* labels, int null_label, float w, const EditCall* ed, float* traj, const int* traj_row,
                          uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
     SISIC_TRY(unet_check_labels(u, labels ? "sample_cond" : "sample", labels != nullptr, labels, B));
@@ -1010,12 +1040,24 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);      // (an unknown rule is refused by check_step_row just below)
-    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels)
+    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels || ed)
         for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * cw + 0], coef[(size_t)i * cw + 1]));
     // DPM-Solver++: a call starts with no history (the buffer holds whatever the last run left), so its first step cannot be
     // a second-order one.  A run cut into two calls therefore differs from the uncut run; callers run it in one call.
     if (rule == STEP_RULE_DPMPP)
         SISIC_REQUIRE(coef[5] == 0.0f, "sample: row 0 of a DPM-Solver++ call has k1 = %g (a call starts with no history)", coef[5]);
+    if (ed) {
+        // the replayed step reads its edit row on the device and cannot refuse it: the whole table is checked here
+        SISIC_REQUIRE(seeds && ed->x0k && ed->mask && ed->rows, "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
+        SISIC_REQUIRE(T <= 1000, "sample_edit: at most 1000 steps per call");
+        for (int i = 0; i < T; ++i) {
+            const float* r = ed->rows + 4 * (size_t)i;
+            SISIC_REQUIRE(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]),
+                          "sample_edit: edit row %d is {%g, %g, %g, %g}", i, r[0], r[1], r[2], r[3]);
+            SISIC_REQUIRE(rule != STEP_RULE_DPMPP || r[3] == 0.0f,
+                          "sample_edit: edit row %d jumps (jb = %g) under DPM-Solver++: a jump invalidates the history", i, r[3]);
+        }
+    }
     // a conditional call: the distinct labels of the call (in order of first appearance, the null one last when guided) are the
     // slots of the embedding table; sample b of a pass reads the row of (step, slot[b])
     CondCall cc;
@@ -1088,7 +1130,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, ed, traj, traj_row, cancel, steps_done, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
@@ -1126,7 +1168,12 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
             const float* c = coef + (size_t)i * cw;
             const float* z = nullptr;
             if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-            if (guided)
+            if (ed)
+                SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, guided ? cg->w : 1.0f,
+                                           nullptr, xe, rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, xe, (int64_t)n, (int64_t)(n / B),
+                                           (int64_t)H * W, seeds_dev, (uint32_t)(step0 + i), c, ed->rows + 4 * (size_t)i, nullptr,
+                                           nullptr, nullptr, ed->x0k, ed->mask, clip, s));
+            else if (guided)
                 SISIC_TRY(launch_step_guided(u->ctx, rule, rule_flags, u->eps_buf, u->eps_buf + n, cg->w, xe, z, rng ? seeds_dev : nullptr,
                                              (int64_t)(n / B), (uint32_t)(step0 + i), rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr,
                                              xe, (int64_t)n, c, clip, s));
@@ -1160,7 +1207,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
 int sisic_sample_frames_rule(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                              float clip, int rule, int rule_flags, const float* noise, float* traj, const int* traj_row,
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, nullptr, 0, 1.0f, traj,
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, nullptr, 0, 1.0f, nullptr, traj,
                          traj_row, out_u8, cancel, steps_done, stream);
 }
 
@@ -1169,7 +1216,7 @@ int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, i
                                  float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
                                  void* stream) {
     SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, nullptr, 0, 1.0f, traj,
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, nullptr, 0, 1.0f, nullptr, traj,
                          traj_row, out_u8, cancel, steps_done, stream);
 }
 
@@ -1180,7 +1227,20 @@ int sisic_sample_frames_cond(sisic_unet* u, float* x, int B, int H, int W, int T
     SISIC_REQUIRE(u && class_labels, "sample_cond: null argument");
     SISIC_REQUIRE(!(seeds && noise), "sample_cond: a noise buffer and seeds (host noise takes seeds NULL, device noise takes noise NULL)");
     return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, seeds, step0, class_labels, null_label,
-                         guidance_scale, traj, traj_row, out_u8, cancel, steps_done, stream);
+                         guidance_scale, nullptr, traj, traj_row, out_u8, cancel, steps_done, stream);
+}
+
+int sisic_sample_frames_edit(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                             float clip, int rule, int rule_flags, const uint64_t* seeds, int step0, const int64_t* class_labels,
+                             int null_label, float guidance_scale, const float* x0k, const float* mask, const float* edit_rows,
+                             float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
+                             void* stream) {
+    SISIC_REQUIRE(u && seeds && x0k && mask && edit_rows,
+                  "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
+    SISIC_REQUIRE(x0k != x && mask != x, "sample_edit: the known image or the mask is the latent buffer");
+    const EditCall ed{x0k, mask, edit_rows};
+    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, class_labels, null_label,
+                         guidance_scale, &ed, traj, traj_row, out_u8, cancel, steps_done, stream);
 }
 
 int sisic_guide_eps(sisic_ctx* ctx, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream) {

@@ -367,6 +367,65 @@ def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: t
     return out
 
 
+def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out):
+    """the three ``*_step_edit`` wrappers: the ``_rng`` wrapper's arguments, the known image, the mask and the edit row"""
+    lib = _lib.load()
+    arr = _seed_array(seeds)
+    B = len(arr)
+    if x.numel() % B:
+        raise ValueError(f"{x.numel()} elements are not {B} equal images")
+    npi = x.numel() // B
+    if x0k.numel() != x.numel():
+        raise ValueError(f"the known image holds {x0k.numel()} elements for an x of {x.numel()}")
+    if mask.numel() % B or mask.numel() == 0 or npi % (mask.numel() // B):
+        raise ValueError(f"a mask of {mask.numel()} elements is not [B, 1, H, W] for {B} images of {npi} elements")
+    hw = mask.numel() // B
+    if hist is not None and hist.numel() != x.numel():
+        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
+    if out is None:
+        out = empty_like(x)
+    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    ck, sk, ja, jb = (float(v) for v in erow)
+    args = [context(x.device), _ptr(eps, "eps"), _ptr(x, "x")]
+    if hist is not None:
+        args.append(_ptr(hist, "hist"))
+    args += [_ptr(out, "out"), B, npi, seeds_dev.data_ptr(), int(step), *(float(v) for v in row), float(clip)]
+    if flag is not None:
+        args.append(int(bool(flag)))
+    args += [_ptr(x0k, "x0k"), _ptr(mask, "mask"), npi // hw, hw, ck, sk, ja, jb, _stream(x.device)]
+    check(getattr(lib, entry)(*args))
+    return out
+
+
+def ddpm_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
+                   clip: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_ddpm_step_edit: ``ddpm_step_rng`` with the inpainting epilogue (include/sisic.h) fused into the kernel.
+    x0k: the known image, fp32 of x's size, finite; mask: fp32 [B,1,H,W] (1 = keep); erow = (ck, sk, ja, jb).  The epilogue
+    draws under tags 5 (``sk != 0``) and 6 (``jb != 0``) of ``noise_fill`` at the same ``step``."""
+    if len(tuple(coef)) != 5:
+        raise ValueError("a DDPM row holds 5 values")
+    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out)
+
+
+def ddim_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
+                   clip: float = 1.0, use_clipped_model_output: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_ddim_step_edit: ``ddim_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``."""
+    if len(tuple(coef)) != 5:
+        raise ValueError("a DDIM row holds 5 values")
+    return _step_edit("sisic_ddim_step_edit", eps, x, seeds, step, None, coef, use_clipped_model_output, clip, x0k, mask, erow,
+                      out)
+
+
+def dpmpp_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, x0k: torch.Tensor,
+                    mask: torch.Tensor, erow, clip: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_dpmpp_step_edit: ``dpmpp_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``; ``hist`` receives the
+    model's predicted x0, which the epilogue does not touch."""
+    if len(tuple(coef)) != 6:
+        raise ValueError("a DPM-Solver++ row holds 6 values")
+    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out)
+
+
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,
                  gn_shift=None, gn_silu=False) -> torch.Tensor:
     """d/dW of ``conv2d`` with the same prologue / index maps: dW [Cout, Cin, k, k] from the forward input(s) and the

@@ -27,6 +27,13 @@ its z first (``draw_noise``: T is small under this rule) and runs in one call in
 generator seeded with ``seed_b`` (the reference's own spelling on a GPU, so its ``noise_hash``), and every ``z_t[b]``
 generated inside the scheduler-step kernel by Philox4x32-10 keyed with ``seed_b``: no host RNG,
 no noise buffer, no upload.  The two modes give different images for one seed.
+
+Image editing (``init_image``, ``mask``, ``strength``, ``jump_length``, ``n_resample``): image-to-image starts the loop from
+``add_noise(init_image, x_T, t)`` at an intermediate level of the grid (SDEdit) and changes nothing else; inpainting
+(RePaint) additionally re-imposes the known region of ``init_image`` in every step, inside the step kernel, at that step's
+noise level, optionally with the paper's resampling jumps (``scheduler.resample_schedule``).  x_T and ``noise_hash`` of a
+seed are those of a plain run.  Inpainting draws on the device only (``noise="device"``): the known region's noise and the
+jumps are two more streams of the device-noise contract (tags 5 and 6).
 """
 from __future__ import annotations
 
@@ -42,7 +49,8 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .scheduler import HipDDIMScheduler, HipDDPMScheduler, HipDPMSolverMultistepScheduler, check_dpmpp_options
+from .scheduler import (HipDDIMScheduler, HipDDPMScheduler, HipDPMSolverMultistepScheduler, check_dpmpp_options, edit_rows,
+                        resample_schedule)
 from .unet import HipUNet2DModel
 
 ISIC_CLASSES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")   # xai/XAI.py:196
@@ -148,6 +156,20 @@ class Guidance:
     def __post_init__(self):
         object.__setattr__(self, "labels", tuple(int(v) for v in self.labels))
         object.__setattr__(self, "scale", check_guidance_scale(self.scale))
+
+
+@dataclass(frozen=True)
+class Edit:
+    """What an inpainting run needs beside the latents (``sisic_sample_frames_edit``): the known image (GPU fp32 [B,C,H,W] in
+    [-1, 1], finite everywhere), the mask (GPU fp32 [B,1,H,W]; 1 keeps the known pixel, 0 synthesises, values in between
+    blend) and the schedule of UNet passes, ``(index into scheduler.timesteps, jump)`` per pass
+    (``scheduler.resample_schedule``); None is the plain grid, every entry once and no jump."""
+    image: torch.Tensor
+    mask: torch.Tensor
+    schedule: Optional[Sequence[Tuple[int, int]]] = None
+
+
+MAX_CALL_STEPS = 1000        # steps of one library call of the loop (include/sisic.h)
 
 
 def check_guidance_scale(guidance_scale) -> float:
@@ -352,6 +374,9 @@ class SampleResult:
     cancelled: bool = False                    # the stop flag ended the loop early: images/latents are NOT a result
     scheduler: str = "ddpm"                    # the step rule of the run ...
     eta: float = 0.0                           # ... and its eta (DDIM; 0.0 under DDPM)
+    strength: float = 1.0                      # image-to-image / inpainting: the part of the grid the run went through
+    n_resample: int = 1                        # inpainting: RePaint's resampling count (1: no jumps)
+    unet_passes: int = 0                       # UNet passes of the whole run (the grid's steps plus the resampled ones)
 
 
 def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence[int]]):
@@ -372,8 +397,13 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
 def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
-                      use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None) -> SampleResult:
-    """guidance: the labels, null label and scale of a class-conditional model (``Guidance``); None for an unconditional one.
+                      use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
+                      edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS) -> SampleResult:
+    """edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
+    The run has one step per entry of ``edit.schedule`` (``timesteps``, ``steps_done``, the trajectory and ``save_indices``
+    count those passes), and one longer than ``max_call_steps`` (at most 1000, the library's limit per call) is cut into calls
+    with their step offsets: bit-equal to the uncut run under ddpm and ddim; a DPM-Solver++ run is never cut.
+    guidance: the labels, null label and scale of a class-conditional model (``Guidance``); None for an unconditional one.
     x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
     (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
     ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
@@ -382,6 +412,10 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
     the step kernel.  eta and use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not
     zero under that rule and eta -- none for DDIM at eta = 0 and for the ODE variant of DPM-Solver++, where every noise
     source gives the same result.  A DPM-Solver++ run takes no ``NoiseStream``: the history lives inside one library call."""
+    if edit is not None:
+        _check_guidance(model, guidance, x_T.shape[0])
+        return _run_edited(model, scheduler, x_T, noise, edit, return_trajectory, save_indices, cancel_flag, eta,
+                           use_clipped_model_output, guidance, max_call_steps)
     if isinstance(noise, NoiseStream):
         if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":
             raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
@@ -433,7 +467,95 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
         out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
                         steps_done=done.value, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta))
+                        eta=float(eta), unet_passes=T)
+
+
+def check_edit_schedule(rule: str, schedule, T: int) -> List[Tuple[int, int]]:
+    """the schedule of an edited run as a list of (grid index, jump); None: the plain grid.  Jumps belong to ddpm and ddim: a
+    jump invalidates the history DPM-Solver++ keeps."""
+    if schedule is None:
+        return [(i, 0) for i in range(T)]
+    sched = [(int(i), int(j)) for i, j in schedule]
+    if not sched:
+        raise ValueError("an empty edit schedule")
+    if rule == "dpmsolver++" and (any(j for _, j in sched) or [i for i, _ in sched] != list(range(T))):
+        raise ValueError("resampling (n_resample > 1) is offered under scheduler='ddpm' and 'ddim': a jump invalidates the "
+                         "history of DPM-Solver++, which takes a mask with n_resample=1 only")
+    return sched
+
+
+def _run_edited(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, edit: Edit, return_trajectory: bool,
+                save_indices: Optional[Sequence[int]], cancel_flag: Optional[C.c_int], eta: float,
+                use_clipped_model_output: bool, guidance: Optional[Guidance], max_call_steps: int) -> SampleResult:
+    """run_sampling_loop under an ``Edit``: the rule's rows, the timesteps and the edit rows of the expanded schedule, then
+    sisic_sample_frames_edit, in calls of at most ``max_call_steps`` passes"""
+    if not isinstance(noise, DeviceNoise):
+        raise ValueError("inpainting draws on the device only (the known region's noise and the jumps are streams of the "
+                         "device-noise contract): pass noise=DeviceNoise(seeds)")
+    lib = _lib.load()
+    dev = x_T.device
+    if dev.type != "cuda":
+        raise RuntimeError("the sampling loop runs on MI355X only")
+    B, Cc, H, W = x_T.shape
+    if len(noise.seeds) != B:
+        raise ValueError(f"DeviceNoise holds {len(noise.seeds)} seeds for a batch of {B}")
+    max_call_steps = int(max_call_steps)
+    if not 1 <= max_call_steps <= MAX_CALL_STEPS:
+        raise ValueError(f"max_call_steps must lie in 1 .. {MAX_CALL_STEPS}, got {max_call_steps}")
+    image, mask = edit.image, edit.mask
+    if tuple(image.shape) != (B, Cc, H, W) or image.device != dev or image.dtype != torch.float32:
+        raise ValueError(f"the known image must be fp32 {(B, Cc, H, W)} on {dev}, got {image.dtype} {tuple(image.shape)}")
+    if tuple(mask.shape) != (B, 1, H, W) or mask.device != dev or mask.dtype != torch.float32:
+        raise ValueError(f"the mask must be fp32 {(B, 1, H, W)} on {dev}, got {mask.dtype} {tuple(mask.shape)}")
+    image, mask = image.contiguous(), mask.contiguous()
+    grid_ts = scheduler.timesteps.to(torch.int64)
+    rule_name = getattr(scheduler, "rule", "ddpm")
+    schedule = check_edit_schedule(rule_name, edit.schedule, grid_ts.numel())
+    grid_coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
+    idx = torch.tensor([i for i, _ in schedule], dtype=torch.int64)
+    if int(idx.min()) < 0 or int(idx.max()) >= grid_ts.numel():
+        raise ValueError(f"edit schedule indices outside 0..{grid_ts.numel() - 1}")
+    # a pass runs under the row of ITS grid entry (t -> its own previous grid point), wherever the next pass goes
+    ts, coef, erows = grid_ts[idx].contiguous(), grid_coef[idx].contiguous(), edit_rows(scheduler, schedule).contiguous()
+    P = len(schedule)
+    if P > max_call_steps and rule == _lib.RULE_DPMPP:
+        raise ValueError(f"a DPM-Solver++ run of {P} steps is not cut into calls of {max_call_steps} (each cut would lose the "
+                         "history)")
+    x = x_T.to(torch.float32).contiguous().clone()
+    kept, rows = _frame_rows(P, return_trajectory, save_indices)
+    if return_trajectory and rows is None:
+        rows = np.arange(P, dtype=np.int32)
+    traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
+    out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
+    clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    seeds = (C.c_uint64 * B)(*noise.seeds)
+    labels = (C.c_int64 * B)(*guidance.labels) if guidance is not None else None
+    done_total, rc = 0, 0
+    for a in range(0, P, max_call_steps):
+        b = min(P, a + max_call_steps)
+        done = C.c_int(0)
+        seg_rows = np.ascontiguousarray(rows[a:b]) if traj is not None and len(kept) else None
+        seg_ts, seg_coef, seg_erows = ts[a:b].contiguous(), coef[a:b].contiguous(), erows[a:b].contiguous()
+        rc = lib.sisic_sample_frames_edit(
+            model.handle, x.data_ptr(), B, H, W, b - a, C.cast(seg_ts.data_ptr(), _lib.c_int64_p),
+            C.cast(seg_coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags, seeds, int(noise.step0) + a, labels,
+            int(guidance.null_label) if guidance is not None else 0, float(guidance.scale) if guidance is not None else 1.0,
+            image.data_ptr(), mask.data_ptr(), C.cast(seg_erows.data_ptr(), _lib.c_float_p),
+            traj.data_ptr() if seg_rows is not None else None,
+            seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
+            out_u8.data_ptr() if b == P else None, C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
+            stream)
+        done_total += done.value
+        if rc != 0:
+            break
+    if rc != _lib.SISIC_ECANCEL:
+        check(rc)
+    cancelled = rc == _lib.SISIC_ECANCEL
+    if cancelled:
+        out_u8.zero_()
+    return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
+                        steps_done=done_total, cancelled=cancelled, scheduler=rule_name, eta=float(eta), unet_passes=P)
 
 
 def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
@@ -503,7 +625,84 @@ def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: Noise
         out_u8.zero_()
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
                         steps_done=done_total, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta))
+                        eta=float(eta), unet_passes=T)
+
+
+def strength_steps(T: int, strength) -> int:
+    """how many of a T-step grid's entries, counted from its end, an edit of this ``strength`` runs: ``min(int(T * strength),
+    T)``; ``strength`` lies in (0, 1] and must leave at least one step"""
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
+    n = min(int(int(T) * float(strength)), int(T))
+    if n < 1:
+        raise ValueError(f"strength={strength} leaves no step of a {T}-step grid to run")
+    return n
+
+
+def check_edit_options(scheduler: str, noise: str, has_image: bool, has_mask: bool, strength, jump_length, n_resample) -> None:
+    """every refusal of the editing keywords that needs no tensor, before anything touches the GPU"""
+    if isinstance(n_resample, bool) or not isinstance(n_resample, int) or n_resample < 1:
+        raise ValueError(f"n_resample must be a positive integer, got {n_resample!r}")
+    if isinstance(jump_length, bool) or not isinstance(jump_length, int) or jump_length < 1:
+        raise ValueError(f"jump_length must be a positive integer, got {jump_length!r}")
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
+    if not has_image:
+        if has_mask or float(strength) != 1.0 or n_resample != 1:
+            raise ValueError("mask, strength and n_resample edit an image: pass init_image")
+        return
+    if not has_mask:
+        if float(strength) == 1.0:
+            raise ValueError("image-to-image at strength=1 starts from pure noise and would ignore init_image: pass a "
+                             "strength below 1, or a mask")
+        if n_resample != 1:
+            raise ValueError("n_resample resamples the seam of a mask: image-to-image has none")
+        return
+    if noise != "device":
+        raise ValueError("inpainting needs noise='device': the known region's noise and the resampling jumps are drawn in "
+                         "the step kernel (host-noise inpainting is not offered)")
+    if scheduler == "dpmsolver++" and n_resample != 1:
+        raise ValueError("resampling (n_resample > 1) is offered under scheduler='ddpm' and 'ddim': a jump invalidates the "
+                         "history of DPM-Solver++, which takes a mask with n_resample=1 only")
+
+
+def prepare_init_image(init_image, B: int, chw: Tuple[int, int, int], device) -> torch.Tensor:
+    """fp32 [B,C,H,W] on ``device`` from fp32 [B,C,H,W] / [C,H,W] in [-1, 1] or uint8 [B,H,W,C] / [H,W,C] (the inverse of
+    ``denorm_u8``'s scaling: v / 255 * 2 - 1); a single image is broadcast over the batch"""
+    t = torch.as_tensor(init_image)
+    Cc, H, W = chw
+    if t.dtype == torch.uint8:
+        if t.dim() == 3:
+            t = t[None]
+        if t.dim() != 4 or tuple(t.shape[1:]) != (H, W, Cc):
+            raise ValueError(f"a uint8 init_image must be [B,{H},{W},{Cc}] or [{H},{W},{Cc}], got {tuple(t.shape)}")
+        t = (t.to(torch.float32) / 255.0 * 2.0 - 1.0).permute(0, 3, 1, 2)
+    else:
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"init_image must be fp32 in [-1, 1] or uint8, got {t.dtype}")
+        t = t.to(torch.float32)
+        if t.dim() == 3:
+            t = t[None]
+        if t.dim() != 4 or tuple(t.shape[1:]) != (Cc, H, W):
+            raise ValueError(f"an fp32 init_image must be [B,{Cc},{H},{W}] or [{Cc},{H},{W}], got {tuple(t.shape)}")
+    if t.shape[0] not in (1, B):
+        raise ValueError(f"init_image holds {t.shape[0]} images for a batch of {B}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("init_image must be finite everywhere (also under the mask: the blend multiplies it by 0)")
+    return t.expand(B, Cc, H, W).contiguous().to(device)
+
+
+def prepare_mask(mask, B: int, hw: Tuple[int, int], device) -> torch.Tensor:
+    """fp32 [B,1,H,W] on ``device`` from [B,1,H,W], [1,1,H,W] or [H,W]; 1 = keep the known pixel, values within [0, 1]"""
+    t = torch.as_tensor(mask).to(torch.float32)
+    H, W = hw
+    if t.dim() == 2:
+        t = t[None, None]
+    if t.dim() != 4 or tuple(t.shape[1:]) != (1, H, W) or t.shape[0] not in (1, B):
+        raise ValueError(f"mask must be [B,1,{H},{W}] or [{H},{W}], got {tuple(t.shape)}")
+    if not bool(((t >= 0) & (t <= 1)).all()):
+        raise ValueError("mask values must lie in [0, 1] (1 = keep the known pixel)")
+    return t.expand(B, 1, H, W).contiguous().to(device)
 
 
 COLOR_BLEND = 0.35            # image_generator.py:532 "alpha"
@@ -666,8 +865,17 @@ class Sampler:
                        return_trajectory: bool = False, save_every_n: Optional[int] = None,
                        noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
                        use_clipped_model_output: bool = False, solver_order: int = 2,
-                       algorithm_type: str = "dpmsolver++", guidance_scale: float = 1.0) -> SampleResult:
-        """save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
+                       algorithm_type: str = "dpmsolver++", guidance_scale: float = 1.0, init_image=None, mask=None,
+                       strength: float = 1.0, jump_length: int = 10, n_resample: int = 1,
+                       max_call_steps: int = MAX_CALL_STEPS) -> SampleResult:
+        """init_image, mask, strength, jump_length, n_resample: image editing (module docstring).  init_image: fp32 [B,3,H,W]
+        in [-1, 1] or uint8 [B,H,W,3], a single image is broadcast.  Without a mask the call is image-to-image: the run goes
+        through the last ``min(int(T * strength), T)`` entries of the grid, starting from ``add_noise(init_image, x_T, t)`` at
+        the first of them (``strength`` below 1; both noise modes, every rule; DPM-Solver++ starts first order there).  mask
+        ([B,1,H,W] or [H,W], 1 = keep): inpainting, which needs noise="device"; ``strength=1`` starts from x_T itself;
+        ``n_resample > 1`` adds RePaint's resampling jumps of ``jump_length`` levels (ddpm and ddim).  The result records
+        ``strength``, ``n_resample`` and ``unet_passes``.  max_call_steps: the longest library call of an inpainting run.
+        save_every_n: keep only the trajectory frames the reference's XAI run keeps (``trajectory_save_indices``,
         xai/XAI.py:751-777) instead of all T -- 3.1 GB at 64 images x 64x64 x T = 1000 otherwise.
         noise: "host" (the default: one CPU generator per image, see the module docstring) or "device" (x_T from torch's
         device generator, z_t generated in the step kernel: no host RNG, no noise buffers; other images for the same seed).
@@ -685,57 +893,78 @@ class Sampler:
         ValueError."""
         _check_noise_mode(noise)
         _check_scheduler(scheduler, eta, use_clipped_model_output, solver_order, algorithm_type)
+        check_edit_options(scheduler, noise, init_image is not None, mask is not None, strength, jump_length, n_resample)
         model, _, guidance = self._resolve_classes(class_name, len(seeds), guidance_scale)
         sched = self.create_scheduler(T, scheduler, solver_order, algorithm_type)
         rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output, guidance=guidance)
+        H, W = size
+        start = None                     # image-to-image and inpainting below strength 1: x_T -> the noised init_image
+        if init_image is not None:
+            B, chw = len(seeds), (model.config.in_channels, H, W)
+            n_steps = strength_steps(sched.timesteps.numel(), strength)
+            image = prepare_init_image(init_image, B, chw, self.device)
+            # the last n_steps entries of the grid: the rules' rows are those of the grid (a step goes to its own previous grid
+            # point), and DPM-Solver++'s first row there is first order
+            sched.timesteps = sched.timesteps[sched.timesteps.numel() - n_steps:]
+            if float(strength) < 1.0:
+                t0 = sched.timesteps[:1].expand(B)
+                start = lambda x_T: sched.add_noise(image, x_T.to(self.device), t0)      # noqa: E731
+            if mask is not None:
+                passes = resample_schedule(n_steps, jump_length, n_resample) if n_resample > 1 else None
+                rule_args.update(edit=Edit(image, prepare_mask(mask, B, (H, W), self.device), passes),
+                                 max_call_steps=max_call_steps)
         save_indices = None
         if return_trajectory and save_every_n is not None:
-            save_indices = trajectory_save_indices([int(t) for t in sched.timesteps], save_every_n)
+            pass_ts = [int(sched.timesteps[i]) for i, _ in rule_args["edit"].schedule] \
+                if rule_args.get("edit") is not None and rule_args["edit"].schedule is not None else [int(t) for t in sched.timesteps]
+            save_indices = trajectory_save_indices(pass_ts, save_every_n)
         n_noise = int((_rule_tables(sched, eta, use_clipped_model_output)[0][:, 4] != 0).sum())     # steps with sigma != 0
-        H, W = size
+
+        def finish(res: SampleResult, hashes) -> SampleResult:
+            res.seeds = [int(s) for s in seeds]
+            res.noise_hashes = hashes
+            if init_image is not None:
+                res.strength, res.n_resample = float(strength), int(n_resample)
+            return res
         if noise == "device":
             x_T = draw_x_T_device(seeds, (model.config.in_channels, H, W), self.device)
             hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, x_T, DeviceNoise(tuple(seeds)), return_trajectory=return_trajectory,
+            res = run_sampling_loop(model, sched, x_T if start is None else start(x_T), DeviceNoise(tuple(seeds)),
+                                    return_trajectory=return_trajectory,
                                     save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
-            res.seeds = [int(s) for s in seeds]
-            res.noise_hashes = hashes
-            return res
+            return finish(res, hashes)
         if scheduler == "dpmsolver++" or (scheduler == "ddim" and n_noise == 0):
             # DDIM at eta = 0 and the ODE variant of DPM-Solver++: the run draws x_T and nothing else -- no z, no staging
             # buffers, no worker threads.  The SDE variant: every z of the run up front and ONE library call, because the
             # segments of a NoiseStream would each start without the history (T is 10 to 25 under this rule).
             x_T, z = draw_noise(seeds, n_noise, (model.config.in_channels, H, W))
             hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, x_T.to(self.device), z.to(self.device) if n_noise else None,
-                                    return_trajectory=return_trajectory,
+            res = run_sampling_loop(model, sched, x_T.to(self.device) if start is None else start(x_T),
+                                    z.to(self.device) if n_noise else None, return_trajectory=return_trajectory,
                                     save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
-            res.seeds = [int(s) for s in seeds]
-            res.noise_hashes = hashes
-            return res
+            return finish(res, hashes)
         # noise is drawn segment by segment on worker threads while the GPU samples (NoiseStream); the values are
         # those of draw_noise(seeds, n_noise, ...)
         ns = NoiseStream(seeds, (model.config.in_channels, H, W), self.device, self.noise_segment_steps,
                          buffer_cache=self._noise_buffers)
         try:
             hashes = [noise_hash(ns.x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, ns.x_T.to(self.device), ns if n_noise else None,
-                                    return_trajectory=return_trajectory, save_indices=save_indices, cancel_flag=self.cancel,
-                                    **rule_args)
+            res = run_sampling_loop(model, sched, ns.x_T.to(self.device) if start is None else start(ns.x_T),
+                                    ns if n_noise else None, return_trajectory=return_trajectory, save_indices=save_indices,
+                                    cancel_flag=self.cancel, **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
             ns.close()
-        res.seeds = [int(s) for s in seeds]
-        res.noise_hashes = hashes
-        return res
+        return finish(res, hashes)
 
     def generate(self, seed: int, class_name, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,
                  save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
                  use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++",
-                 guidance_scale: float = 1.0):
+                 guidance_scale: float = 1.0, init_image=None, mask=None, strength: float = 1.0, jump_length: int = 10,
+                 n_resample: int = 1):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -748,6 +977,7 @@ class Sampler:
         ``generate_single_image(..., postprocess=True)`` does before saving (image_generator.py:449-452).
         noise: "host" or "device", as in ``generate_seeds``.
         scheduler, eta, use_clipped_model_output, solver_order, algorithm_type: the step rule, as in ``generate_seeds``.
+        init_image, mask, strength, jump_length, n_resample: image-to-image and inpainting, as in ``generate_seeds``.
         class_name, guidance_scale: as in ``generate_seeds``; a sequence of names gives one image per name (``count`` must be 1
         or its length), and with seed_is_base image i derives its seed from ITS class name.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
@@ -766,7 +996,8 @@ class Sampler:
         res = self.generate_images(class_name, seeds, T, size=size, return_trajectory=return_trajectory,
                                    save_every_n=save_every_n, noise=noise, scheduler=scheduler, eta=eta,
                                    use_clipped_model_output=use_clipped_model_output, solver_order=solver_order,
-                                   algorithm_type=algorithm_type, guidance_scale=guidance_scale)
+                                   algorithm_type=algorithm_type, guidance_scale=guidance_scale, init_image=init_image,
+                                   mask=mask, strength=strength, jump_length=jump_length, n_resample=n_resample)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:

@@ -483,3 +483,88 @@ class HipDPMSolverMultistepScheduler:
         if not return_dict:
             return (prev,)
         return DPMSolverSchedulerOutput(prev_sample=prev)
+
+
+# ---- image editing: the RePaint schedule and the rows of the edit epilogue ------------------------------------------------
+def resample_schedule(T: int, jump_length: int = 10, n_resample: int = 1) -> List[Tuple[int, int]]:
+    """RePaint's resampling schedule (Lugmayr et al. 2022, Algorithm 1 with its ``get_schedule_jump``) over a T-step grid:
+    one ``(index into the grid, jump)`` per UNet pass.  In terms of the level L, the number of reverse steps still to go: the
+    run goes down from L = T, and the first ``n_resample - 1`` times it reaches a level in ``range(0, T - jump_length,
+    jump_length)`` it jumps ``jump_length`` levels back up and comes down again.  ``jump`` is the height of the jump taken
+    AFTER the pass (0: none).  ``n_resample == 1`` is the plain grid.  The length is
+    ``T + (n_resample - 1) * jump_length * len(range(0, T - jump_length, jump_length))``."""
+    T, jump_length, n_resample = int(T), int(jump_length), int(n_resample)
+    if T < 1:
+        raise ValueError(f"T must be positive, got {T}")
+    if jump_length < 1:
+        raise ValueError(f"jump_length must be positive, got {jump_length}")
+    if n_resample < 1:
+        raise ValueError(f"n_resample must be positive, got {n_resample}")
+    left = {L: n_resample - 1 for L in range(0, T - jump_length, jump_length)} if n_resample > 1 else {}
+    out: List[Tuple[int, int]] = []
+    L = T
+    while L > 0:
+        i = T - L
+        L -= 1
+        jump = 0
+        if left.get(L, 0) > 0:
+            left[L] -= 1
+            jump = jump_length
+            L += jump_length
+        out.append((i, jump))
+    return out
+
+
+def _abar64(scheduler) -> np.ndarray:
+    """alphas_cumprod in float64: the cumulative product of the scheduler's fp32 ``alphas``, so that a ratio of two entries is
+    the product of the alphas between them to float64 precision (the fp32 table loses that at 6e-8 per entry)"""
+    return np.cumprod(scheduler.alphas.numpy().astype(np.float64))
+
+
+def _abar_prev64(scheduler, abar: np.ndarray, i: int) -> float:
+    """abar at the level grid entry i of ``scheduler.timesteps`` steps to, as the rule's own row of that entry has it"""
+    if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":            # the next grid point; the run ends at abar = 1
+        return float(abar[int(scheduler.timesteps[i + 1])]) if i + 1 < scheduler.timesteps.numel() else 1.0
+    prev_t = scheduler.previous_timestep(int(scheduler.timesteps[i]))
+    if prev_t >= 0:
+        return float(abar[prev_t])
+    final = getattr(scheduler, "final_alpha_cumprod", None)           # DDIM: 1, or alphas_cumprod[0] (set_alpha_to_one=False)
+    return 1.0 if final is None or float(final) == 1.0 else float(abar[0])
+
+
+def edit_rows(scheduler, schedule) -> torch.Tensor:
+    """[len(schedule), 4] fp32 rows ``{ck, sk, ja, jb}`` of the edit epilogue (``sisic_sample_frames_edit``) for a schedule of
+    ``(grid index, jump)`` entries over ``scheduler.timesteps``:
+
+    * ``ck = abar_prev ** 0.5``, ``sk = (1 - abar_prev) ** 0.5`` with abar_prev the level the entry's own rule row steps to
+      (1 at the last level: ``ck = 1, sk = 0``): the known image at the noise level of the step's result;
+    * a jump of j levels: the next pass runs at grid entry ``i + 1 - j``, at ``abar_target``; with ``ratio = abar_target /
+      abar_prev``, ``ja = ratio ** 0.5`` and ``jb = (1 - ratio) ** 0.5`` -- the j forward steps of the paper composed into
+      one Gaussian draw, which has the same distribution; no jump: ``ja = 1, jb = 0``.
+
+    Everything in float64 over the float64 cumulative product of ``scheduler.alphas``, rounded to fp32 once."""
+    rows = edit_rows64(scheduler, schedule)
+    return torch.from_numpy(rows.astype(np.float32))
+
+
+def edit_rows64(scheduler, schedule) -> np.ndarray:
+    """``edit_rows`` before the rounding to fp32"""
+    abar = _abar64(scheduler)
+    n = int(scheduler.timesteps.numel())
+    rows = np.zeros((len(schedule), 4), dtype=np.float64)
+    for p, (i, jump) in enumerate(schedule):
+        i, jump = int(i), int(jump)
+        if not 0 <= i < n:
+            raise ValueError(f"schedule entry {p}: grid index {i} is outside 0..{n - 1}")
+        prev = _abar_prev64(scheduler, abar, i)
+        ja, jb = 1.0, 0.0
+        if jump:
+            target = i + 1 - jump
+            if jump < 0 or not 0 <= target < n:
+                raise ValueError(f"schedule entry {p}: a jump of {jump} from grid index {i} leaves the grid")
+            ratio = float(abar[int(scheduler.timesteps[target])]) / prev
+            if not 0.0 < ratio <= 1.0:
+                raise ValueError(f"schedule entry {p}: a jump of {jump} from grid index {i} does not go up the schedule")
+            ja, jb = math.sqrt(ratio), math.sqrt(1.0 - ratio)
+        rows[p] = (math.sqrt(prev), math.sqrt(max(0.0, 1.0 - prev)), ja, jb)
+    return rows
