@@ -18,8 +18,13 @@
  *   - weights are copied into a library-owned arena at load time; workspace is
  *     library-owned per handle and grows on demand (never inside the sampling loop);
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream);
- *     all work is enqueued asynchronously on it unless stated otherwise;
- *   - handles are not thread-safe; use one handle per (device, stream).
+ *     all work is enqueued asynchronously on it unless stated otherwise: a call returns while the stream may still be
+ *     busy with earlier work, and its results are ordered behind that work.  The calls that wait for the stream say so
+ *     below ("synchronis..."); besides those, a call that has to allocate or grow library memory -- the first call of a
+ *     handle at a shape, a table that grows -- may wait for the device once;
+ *   - handles are not thread-safe; use one handle per (device, stream): a handle serves one stream at a time, and the
+ *     caller synchronises that stream before it passes the handle another one.  Threads that each own a handle and a
+ *     stream may share a context ("Streams").
  */
 #ifndef SISIC_H
 #define SISIC_H
@@ -288,7 +293,9 @@ int sisic_unet_load(sisic_unet*, int n, const char* const* names, const float* c
 int sisic_unet_set_latency_mode(sisic_unet*, int on);
 /* sisic_sample as one captured step (hipGraph) replayed T-1 times instead of ~190 launches per step from the host:
  * mode 1 on, 0 off, -1 (default) on exactly when latency mode is on.  Same kernels, same arithmetic, same bits; the
- * loop then runs on a library-owned copy of x (written back at the end) so that every address in the graph is stable.   */
+ * loop then runs on a library-owned copy of x (written back at the end) so that every address in the graph is stable.
+ * The step is captured on the caller's stream.  The NULL stream cannot be captured: there the graph runs on a blocking stream
+ * the handle owns (ordered with the NULL stream like any blocking stream), and the call synchronises it before it returns.  */
 int sisic_unet_set_graph_mode(sisic_unet*, int mode);
 /* How many times this handle has captured + instantiated the sampling step (a second sisic_sample at the same shape,
  * stream and mode replays the cached graph: the count does not move).                                                  */
@@ -311,6 +318,9 @@ int sisic_unet_forward_cond(sisic_unet*, const float* sample, const int64_t* tim
  * traj: dev [T,B,C,H,W] receiving x after every step, or NULL.
  * out_u8: dev uint8 [B,H,W,C] final de-normalised image, or NULL.
  * cancel: host int* polled between steps (non-zero stops the loop with SISIC_ECANCEL), or NULL.
+ *   A non-NULL cancel makes the call synchronise the stream before step 0 and before every eighth step after it (the
+ *   poll is worth something only while the host runs a bounded number of steps ahead); with NULL the loop is enqueued
+ *   without waiting.  This holds for every sisic_sample* entry.
  * steps_done: host int* receiving the number of completed steps, or NULL.           */
 int sisic_sample(sisic_unet*, float* x, int B, int H, int W, int T, const int64_t* timesteps,
                  const float* coef, float clip, const float* noise, float* traj, uint8_t* out_u8,
@@ -561,7 +571,9 @@ int sisic_unet_ema_active(const sisic_unet*);
 /* The two kernels on the caller's device vectors (parity-test surface; any n >= 1, pointers aligned to a float; scratch is
  * allocated per call).  grad_stats writes the record {float total_norm; float clip_coef; int found_inf} (3 x 4 bytes) to
  * stats_dev.  adam_ema: one Adam step number `step` (>= 1) on p, m, v from g, reading clip_coef from stats_dev (NULL: 1)
- * and updating ema (NULL: none) with ema_decay; with both NULL it is the kernel of sisic_unet_optimizer_step.            */
+ * and updating ema (NULL: none) with ema_decay; with both NULL it is the kernel of sisic_unet_optimizer_step.
+ * sisic_grad_stats: Synchronises the stream: the scratch is freed before the call returns.  sisic_adam_ema allocates
+ * nothing and does not wait.                                                                                           */
 int sisic_grad_stats(sisic_ctx*, const float* g, int64_t n, float inv_scale, float max_norm, void* stats_dev, void* stream);
 int sisic_adam_ema(sisic_ctx*, float* p, const float* g, float* m, float* v, float* ema_or_null, int64_t n, double lr,
                    double beta1, double beta2, double eps, int64_t step, float inv_scale, const void* stats_dev_or_null,
@@ -578,13 +590,15 @@ int64_t sisic_unet_train_steps(const sisic_unet*);
 
 /* Single-operator entry points of the backward pass (parity-test surface).
  * dW of a convolution: arguments as sisic_conv_args (prologue and index maps of the FORWARD convolution), dy = gradient of
- * its output, dw = OIHW [Cout, c0+c1, k, k].                                                                            */
+ * its output, dw = OIHW [Cout, c0+c1, k, k].  Its K-split scratch is allocated per call.
+ * Synchronises the stream: the scratch is freed before the call returns.                                               */
 int sisic_conv2d_wgrad(sisic_ctx*, const sisic_conv_args* fwd_args, const float* dy, float* dw, void* stream);
 /* attention backward: dqkv [B,3C,N] from qkv, the forward output o [B,C,N] and its gradient dO.                         */
 int sisic_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                         int head_dim, void* stream);
 /* GroupNorm(+SiLU) backward: a = act(GroupNorm(x)); given da, ADDS dx to dx_accum and writes dgamma, dbeta.
- * scale/shift: outputs of sisic_groupnorm_stats for x.                                                                  */
+ * scale/shift: outputs of sisic_groupnorm_stats for x (recomputed here, into scratch allocated per call).
+ * Synchronises the stream: the scratch is freed before the call returns.                                               */
 int sisic_groupnorm_bwd(sisic_ctx*, const float* da, const float* x, int B, int C, int HW, int groups, float eps,
                         const float* gamma, const float* beta, int silu, float* dx_accum, float* dgamma, float* dbeta,
                         void* stream);

@@ -188,7 +188,10 @@ struct sisic_unet {
     float* gn_scale2 = nullptr;  // a second pair: a convolution that finalizes the GroupNorm of its own output (sisic_conv_args.fin_*)
     float* gn_shift2 = nullptr;  //   writes the pair its own prologue is NOT reading (later workgroups of the launch still read that one)
     size_t t_vals_cap = 0, temb_act_cap = 0, tproj_cap = 0, gn_scale_cap = 0, gn_shift_cap = 0, gn_scale2_cap = 0, gn_shift2_cap = 0;
-    static constexpr int STAGE_SLOTS = 4;
+    // a slot is reused only after the copy out of it has finished (unet_stage_upload waits for its event), so the ring holds
+    // more slots than one call uploads -- six in a guided, edited, graph-replayed loop on device noise: seeds, timesteps, labels,
+    // the guidance table, the loop tables, the edit rows -- or the call would wait for its own stream
+    static constexpr int STAGE_SLOTS = 8;
     float* stage_host = nullptr; // pinned upload ring
     size_t stage_cap = 0;
     uint64_t stage_next = 0;

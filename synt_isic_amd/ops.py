@@ -46,6 +46,15 @@ def _stream(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def upload(host: torch.Tensor, device) -> torch.Tensor:
+    """A small host tensor on ``device``, copied through pinned memory on the current stream without blocking the host.  (A
+    copy out of pageable memory waits for the stream: a wrapper that made one would synchronise, which include/sisic.h says
+    the entry points behind these wrappers do not.)"""
+    staged = torch.empty(host.shape, dtype=host.dtype, pin_memory=True)
+    staged.copy_(host)
+    return staged.to(device, non_blocking=True)
+
+
 def _ptr(t: Optional[torch.Tensor], name: str = "tensor") -> Optional[int]:
     if t is None:
         return None
@@ -290,7 +299,7 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         raise ValueError(f"{x.numel()} elements are not {B} equal images")
     if out is None:
         out = empty_like(x)
-    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
     check(lib.sisic_ddpm_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
@@ -322,7 +331,7 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         raise ValueError(f"{x.numel()} elements are not {B} equal images")
     if out is None:
         out = empty_like(x)
-    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
     check(lib.sisic_ddim_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c_prev, c_dir, sigma, float(clip),
@@ -359,7 +368,7 @@ def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: t
         raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
     if out is None:
         out = empty_like(x)
-    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
     check(lib.sisic_dpmpp_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
                                    x.numel() // B, seeds_dev.data_ptr(), int(step), sb, sa, cx, k0, sigma, k1, float(clip),
@@ -384,7 +393,7 @@ def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask
         raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
     if out is None:
         out = empty_like(x)
-    seeds_dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).to(x.device)      # the uint64 bit patterns
+    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     ck, sk, ja, jb = (float(v) for v in erow)
     args = [context(x.device), _ptr(eps, "eps"), _ptr(x, "x")]
     if hist is not None:

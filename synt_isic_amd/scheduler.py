@@ -170,7 +170,7 @@ class HipDDPMScheduler:
         a, c = self.add_noise_coefficients(timesteps)
         if a.numel() != B:
             raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
-        a, c = a.to(x0.device), c.to(x0.device)
+        a, c = ops.upload(torch.stack([a, c]), x0.device)          # pinned, non-blocking: the call does not wait for the stream
         out = ops.empty_like(x0)
         check(_lib.load().sisic_add_noise(ops.context(x0.device), x0.data_ptr(), nz.data_ptr(), a.data_ptr(), c.data_ptr(),
                                           out.data_ptr(), B, x0[0].numel(),
