@@ -502,6 +502,25 @@ int sisic_unet_train_forward(sisic_unet*, const float* sample, const int64_t* ti
  * gradients of the samples labelled k; the row of a label absent from the batch is written as zero.                     */
 int sisic_unet_train_forward_cond(sisic_unet*, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
                                   float* out, int B, int H, int W, void* stream);
+/* ---- ResnetBlock2D dropout ("dropout mask contract") ----------------------------------------------
+ * UNet2DModel's `dropout` argument: in every ResnetBlock2D (down, mid and up: 22 in the default architecture)
+ *   h = conv2(dropout(silu(norm2(h))))
+ * and nothing else drops.  It applies exactly where a tape is recorded -- sisic_unet_train_forward[_cond] and the
+ * sisic_unet_train_step* entries; sisic_unet_forward*, every sisic_sample* loop and so every evaluation never drop.  The new
+ * kernels run on the stream those entry points receive.
+ *
+ * The handle holds (p, seed, call).  call starts at first_call and advances by one per tape-recording forward while p > 0.
+ * For sample b, resnet block r (0-based, in execution order) and element e of that sample's [C,H,W] activation: word e & 3 of
+ * the device-noise contract's Philox block with seed seed + b, block e >> 2, step = call, tag = 256 + r (the words
+ * sisic_noise_bits returns for those arguments) gives u = (word >> 8) * 2^-24; the element is kept iff u >= p (an fp32
+ * compare).  A kept value is a * inv_keep, inv_keep = fp32(1.0 / (1.0 - (double)p)): one rounding; a dropped value is +0.  The
+ * backward pass regenerates the mask from (seed, call, r, b, e) -- nothing is stored -- with the values the forward that
+ * recorded the tape used, whatever has been set since.  C*H*W is a multiple of 4 at every level of every model the library
+ * builds; the kernels require it.
+ * set_dropout: 0 <= p < 1 and finite, else SISIC_EINVAL with the previous setting left in force; p == 0 turns dropout off
+ * (the launches of a handle that never had it).  dropout_next_call: the counter value the next tape-recording forward uses. */
+int sisic_unet_set_dropout(sisic_unet*, float p, uint64_t seed, uint32_t first_call);
+uint32_t sisic_unet_dropout_next_call(const sisic_unet*);
 /* F.mse_loss(pred, target) (train_diffusion.py:219): loss_dev[0] = mean((pred - target)^2) (NULL: kept internally),
  * dpred = grad_scale * 2 (pred - target) / n (NULL: loss only).  Fixed-order reduction.                               */
 int sisic_mse_loss(sisic_unet*, const float* pred, const float* target, int64_t n, float grad_scale, float* loss_dev,

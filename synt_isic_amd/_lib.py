@@ -192,6 +192,8 @@ SIGNATURES = {
                                            C.c_void_p]),
     "sisic_unet_train_forward_cond": (C.c_int, [C.c_void_p, C.c_void_p, c_int64_p, c_int64_p, C.c_void_p, C.c_int, C.c_int,
                                                 C.c_int, C.c_void_p]),
+    "sisic_unet_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint32]),
+    "sisic_unet_dropout_next_call": (C.c_uint32, [C.c_void_p]),
     "sisic_mse_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "sisic_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -33,6 +33,7 @@ class UNetConfig:
     attention_head_dim: int = 8
     class_embed_type: None = None
     num_class_embeds: Optional[int] = None      # N: class_embedding = nn.Embedding(N, time_embed_dim); None: unconditional
+    dropout: float = 0.0                        # ResnetBlock2D dropout, training-mode forwards only; adds no tensors
 
     @property
     def time_embed_dim(self) -> int:
@@ -62,6 +63,9 @@ class UNetConfig:
         if self.num_class_embeds is not None and (isinstance(self.num_class_embeds, bool) or
                                                   not isinstance(self.num_class_embeds, int) or self.num_class_embeds < 1):
             raise ValueError(f"num_class_embeds must be None or a positive int, got {self.num_class_embeds!r}")
+        p = self.dropout
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout must be a finite number in [0, 1), got {p!r}")
 
 
 @dataclass

@@ -1,7 +1,8 @@
 // noise_device.h -- the device-noise contract: Philox4x32-10 + Box-Muller, one block per four
 // consecutive elements of an image.  A pure function of (seed, step, tag, element): no state, nothing to synchronise.
 // Included by elementwise.hip and xai_kernels.hip only, both compiled with -ffp-contract=off (csrc/Makefile), so that the step
-// kernels, the stand-alone fill kernel and the noise interventions produce the same bits.
+// kernels, the stand-alone fill kernel and the noise interventions produce the same bits.  train_kernels.hip (built without that
+// flag) takes the raw words only -- noise_bits4 for the dropout masks: integer arithmetic, which no floating-point flag changes.
 #pragma once
 #include <hip/hip_runtime.h>
 

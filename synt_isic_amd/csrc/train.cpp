@@ -234,6 +234,21 @@ struct Bwd {
         return launch_attention_bwd(u->ctx, op.qkv->p, op.o->p, dO, dqkv, B, op.C, op.N, u->cfg.head_dim, s);
     }
 
+    // hd = dropout(silu(norm2(h))): conv2's backward-data has left d hd in hd's gradient buffer (its in-place form); the mask,
+    // regenerated, is applied there in one pass; the GroupNorm+SiLU backward that every normalised input takes runs on the result
+    int dropout_op(const TapeOp& op) {
+        float* dhd = nullptr;
+        float* g0 = nullptr;
+        SISIC_TRY(grad(op.out, &dhd));
+        SISIC_TRY(grad(op.in0, &g0));
+        const int C = op.c0, HW = op.H * op.W;
+        SISIC_TRY(launch_dropout_bwd(u->ctx, dhd, B, C, HW, tr->drop_seed, tr->drop_call, 256u + (uint32_t)op.drop_block, tr->drop_p,
+                                     tr->drop_inv_keep, s));
+        float* sums = tr->small + (size_t)B * C;           // [2][B][C]
+        return launch_gn_bwd(u->ctx, dhd, op.in0_ptr, C, nullptr, 0, B, HW, u->cfg.norm_groups, op.gn_scale, op.gn_shift, op.gn_mr,
+                             op.norm->gamma, 1, sums, g0, nullptr, grad_of(u, op.norm->w_idx), grad_of(u, op.norm->b_idx), s);
+    }
+
     // time embedding: tproj = time_emb_proj(ta), ta = silu(t2), t2 = linear_2(silu(h1)), h1 = linear_1(emb)
     int time_embedding() {
         const int R = u->tproj_R, Hd = u->hidden, nin = 2 * u->cfg.n_freqs;
@@ -296,6 +311,7 @@ struct Bwd {
         SISIC_HIP(hipMemsetAsync(tr->garena, 0, total * sizeof(float), s));
         for (auto it = tr->tape.rbegin(); it != tr->tape.rend(); ++it) {
             if (it->kind == TapeOp::CONV) SISIC_TRY(conv_op(*it, dout));
+            else if (it->kind == TapeOp::DROPOUT) SISIC_TRY(dropout_op(*it));
             else SISIC_TRY(attn_op(*it));
         }
         return time_embedding();
@@ -414,11 +430,15 @@ int train_forward_impl(sisic_unet* u, const float* sample, const int64_t* timest
                               class_labels ? reinterpret_cast<const int*>(tr->labels_dev) : nullptr));
     SISIC_TRY(launch_linear_t(u->ctx, u->temb_act, B, Hd, u->tproj_wt, u->tproj_b, u->tproj_R, u->tproj, s));
     tr->B = B; tr->H = H; tr->W = W;
+    // the dropout of this tape: the handle's setting and counter as they stand now (include/sisic.h, the mask contract)
+    tr->drop_p = u->drop_p; tr->drop_seed = u->drop_seed; tr->drop_call = u->drop_call;
+    tr->drop_inv_keep = (float)(1.0 / (1.0 - (double)u->drop_p));
     const int rc = unet_run_forward(u, sample, u->tproj, u->tproj_R, out, B, H, W, s, tr);
     if (rc != SISIC_OK) {
         unet_release_tape(u);
         return rc;
     }
+    if (tr->drop_p > 0.0f) u->drop_call += 1;
     tr->has_tape = true;
     return SISIC_OK;
 }
@@ -487,6 +507,15 @@ int sisic_unet_train_end(sisic_unet* u) {
     u->train.reset();
     return SISIC_OK;
 }
+
+int sisic_unet_set_dropout(sisic_unet* u, float p, uint64_t seed, uint32_t first_call) {
+    SISIC_REQUIRE(u, "set_dropout: null handle");
+    SISIC_REQUIRE(p >= 0.0f && p < 1.0f, "set_dropout: p = %g must be finite and in [0, 1)", (double)p);     // (false for a NaN)
+    u->drop_p = p; u->drop_seed = seed; u->drop_call = first_call;
+    return SISIC_OK;
+}
+
+uint32_t sisic_unet_dropout_next_call(const sisic_unet* u) { return u ? u->drop_call : 0; }
 
 int sisic_unet_zero_grad(sisic_unet* u, void* stream) {
     SISIC_TRY(require_train(u, "zero_grad"));

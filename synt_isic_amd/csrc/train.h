@@ -54,6 +54,13 @@ int launch_copy_cols(sisic_ctx*, const float* src, int rows, int cols, float* ds
 int launch_gn_bwd(sisic_ctx*, const float* da, const float* in0, int c0, const float* in1, int c1, int B, int HW, int groups,
                   const float* scale, const float* shift, const float* mean_rstd, const float* gamma, int silu,
                   float* sums, float* g0, float* g1, float* dgamma, float* dbeta, hipStream_t s);
+// ResnetBlock2D dropout (the mask contract of include/sisic.h; tag = 256 + the block's index, call = the forward's counter value):
+// out = dropout(silu(h * scale[b,c] + shift[b,c])) over [B, C, HW], and the same mask times inv_keep applied to a gradient in
+// place.  C*HW % 4 == 0 and 16-byte aligned tensors, or SISIC_EINVAL.
+int launch_gn_silu_dropout(sisic_ctx*, const float* h, const float* scale, const float* shift, float* out, int B, int C, int HW,
+                           uint64_t seed, uint32_t call, uint32_t tag, float p, float inv_keep, hipStream_t s);
+int launch_dropout_bwd(sisic_ctx*, float* d, int B, int C, int HW, uint64_t seed, uint32_t call, uint32_t tag, float p, float inv_keep,
+                       hipStream_t s);
 int launch_accum_split(sisic_ctx*, const float* da, int B, int C, int HW, float* g0, int c0, float* g1, int c1, hipStream_t s);
 int launch_accum_pool2(sisic_ctx*, const float* da, int planes, int H, int W, float* g, hipStream_t s);
 int launch_add_inplace(sisic_ctx*, float* dst, const float* src, size_t n, hipStream_t s);

@@ -16,6 +16,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "noise_device.h"
 #include "pack_device.h"
 #include "train.h"
 
@@ -779,6 +780,98 @@ int launch_add_inplace(sisic_ctx*, float* dst, const float* src, size_t n, hipSt
         return SISIC_OK;
     }
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, dst, src, n);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// ================================================================ ResnetBlock2D dropout ==============================
+// The mask contract (include/sisic.h): element e of sample b's [C,H,W] activation in resnet block r of
+// tape-recording forward `call` is kept iff u >= p, u = (word >> 8) * 2^-24 of word e & 3 of
+// noise_bits4(seed + b, e >> 2, step = call, tag = 256 + r); a kept value is a * inv_keep, a dropped one +0.  A pure function of
+// its arguments: the backward pass calls it again instead of reading a stored mask.  (Integer Philox, an exact conversion, one
+// compare, one multiply: nothing here that -ffp-contract could change.)
+__device__ __forceinline__ float4 dropout_apply4(float4 a, uint64_t seed, uint32_t q, uint32_t call, uint32_t tag, float p,
+                                                 float inv_keep) {
+    const uint4 w = noise_bits4(seed, q, call, tag);
+    float4 o;
+    o.x = (float)(w.x >> 8) * 0x1p-24f >= p ? a.x * inv_keep : 0.0f;
+    o.y = (float)(w.y >> 8) * 0x1p-24f >= p ? a.y * inv_keep : 0.0f;
+    o.z = (float)(w.z >> 8) * 0x1p-24f >= p ? a.z * inv_keep : 0.0f;
+    o.w = (float)(w.w >> 8) * 0x1p-24f >= p ? a.w * inv_keep : 0.0f;
+    return o;
+}
+
+// Forward: hd = dropout(silu(h * scale[b,c] + shift[b,c])), the GroupNorm pair being the finalised one of norm2.  One float4 per
+// thread and iteration (n4 = C*HW/4 per sample, total4 = B*n4 < 2^32); HW % 4 != 0 (the 5x7 level of a 40x56 image): the four
+// elements of a block may lie in different channels, so each looks its pair up.
+// HBM-bound: 8 bytes per element (h read, hd written) beside ~25 integer instructions per element for the Philox block.
+__global__ void __launch_bounds__(256)
+gn_silu_dropout_kernel(const float4* __restrict__ h, const float* __restrict__ scale, const float* __restrict__ shift,
+                       float4* __restrict__ out, uint32_t C, uint32_t HW, uint32_t n4, uint32_t total4, uint64_t seed, uint32_t call,
+                       uint32_t tag, float p, float inv_keep) {
+    const bool one_channel = (HW & 3u) == 0u;
+    for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total4; it += (size_t)gridDim.x * 256) {
+        const uint32_t i = (uint32_t)it, b = i / n4, q = i - b * n4, e = 4u * q;
+        const float4 v = h[i];
+        const float* sc = scale + (size_t)b * C;
+        const float* sh = shift + (size_t)b * C;
+        float4 a;
+        if (one_channel) {
+            const uint32_t c = e / HW;
+            const float s0 = sc[c], t0 = sh[c];
+            a.x = silu_fwd(v.x * s0 + t0); a.y = silu_fwd(v.y * s0 + t0); a.z = silu_fwd(v.z * s0 + t0); a.w = silu_fwd(v.w * s0 + t0);
+        } else {
+            const uint32_t cx = e / HW, cy = (e + 1u) / HW, cz = (e + 2u) / HW, cw = (e + 3u) / HW;
+            a.x = silu_fwd(v.x * sc[cx] + sh[cx]); a.y = silu_fwd(v.y * sc[cy] + sh[cy]);
+            a.z = silu_fwd(v.z * sc[cz] + sh[cz]); a.w = silu_fwd(v.w * sc[cw] + sh[cw]);
+        }
+        out[i] = dropout_apply4(a, seed + b, q, call, tag, p, inv_keep);
+    }
+}
+
+// Backward: d_hd -> d_hd * mask * inv_keep in place, the mask regenerated; launch_gn_bwd then reads the result as its da.
+__global__ void __launch_bounds__(256)
+dropout_bwd_kernel(float4* __restrict__ d, uint32_t n4, uint32_t total4, uint64_t seed, uint32_t call, uint32_t tag, float p,
+                   float inv_keep) {
+    for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total4; it += (size_t)gridDim.x * 256) {
+        const uint32_t i = (uint32_t)it, b = i / n4, q = i - b * n4;
+        d[i] = dropout_apply4(d[i], seed + b, q, call, tag, p, inv_keep);
+    }
+}
+
+static int dropout_check(const void* a, const void* b, int B, int C, int HW, float p, uint32_t* n4, uint32_t* total4) {
+    SISIC_REQUIRE(a && b && B > 0 && C > 0 && HW > 0, "dropout: bad arguments");
+    SISIC_REQUIRE(p > 0.0f && p < 1.0f, "dropout: p = %g is outside (0, 1)", (double)p);
+    const int64_t n = (int64_t)C * HW;
+    SISIC_REQUIRE(n % 4 == 0, "dropout: C*H*W = %lld is not a multiple of 4", (long long)n);
+    SISIC_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0, "dropout: tensors must be 16-byte aligned");
+    SISIC_REQUIRE((int64_t)B * (n / 4) < (int64_t(1) << 32), "dropout: B*C*H*W = %lld is too large", (long long)B * n);
+    *n4 = (uint32_t)(n / 4);
+    *total4 = (uint32_t)((int64_t)B * (n / 4));
+    return SISIC_OK;
+}
+
+int launch_gn_silu_dropout(sisic_ctx* ctx, const float* h, const float* scale, const float* shift, float* out, int B, int C, int HW,
+                           uint64_t seed, uint32_t call, uint32_t tag, float p, float inv_keep, hipStream_t s) {
+    uint32_t n4 = 0, total4 = 0;
+    SISIC_REQUIRE(scale && shift, "dropout: null GroupNorm pair");
+    SISIC_TRY(dropout_check(h, out, B, C, HW, p, &n4, &total4));
+    ProfileScope prof(ctx, s, PK_GN, 8.0 * B * C * HW + 8.0 * B * C, 0.0);
+    // (2048 workgroups: eight per CU; the rest of a large tensor by the grid stride)
+    hipLaunchKernelGGL(gn_silu_dropout_kernel, dim3(std::min<uint32_t>((total4 + 255) / 256, 2048)), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(h), scale, shift, reinterpret_cast<float4*>(out), (uint32_t)C, (uint32_t)HW, n4,
+                       total4, seed, call, tag, p, inv_keep);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+int launch_dropout_bwd(sisic_ctx* ctx, float* d, int B, int C, int HW, uint64_t seed, uint32_t call, uint32_t tag, float p,
+                       float inv_keep, hipStream_t s) {
+    uint32_t n4 = 0, total4 = 0;
+    SISIC_TRY(dropout_check(d, d, B, C, HW, p, &n4, &total4));
+    ProfileScope prof(ctx, s, PK_OTHER, 8.0 * B * C * HW, 0.0);
+    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(std::min<uint32_t>((total4 + 255) / 256, 2048)), dim3(256), 0, s,
+                       reinterpret_cast<float4*>(d), n4, total4, seed, call, tag, p, inv_keep);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

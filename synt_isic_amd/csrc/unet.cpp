@@ -20,6 +20,7 @@
 
 #include "conv_plan.h"
 #include "gn_finalize.h"
+#include "train.h"
 #include "unet_internal.h"
 
 using namespace sisic;
@@ -380,6 +381,7 @@ struct Fwd {
     float* gsh = u->gn_shift;
     float* gmr = nullptr;         // training mode: (mean, rstd) of the same GroupNorm
     const NormW* gnorm = nullptr;
+    int resnets_run = 0;          // ResNet blocks so far, in execution order: the block index of the dropout masks
 
     Buf* make(int C, int H, int W, int* rc) {
         auto b = std::make_unique<Buf>();
@@ -516,13 +518,29 @@ struct Fwd {
             SISIC_REQUIRE(c1 == 0 && x->C == r.cout, "unet: identity shortcut with mismatched channels");
         }
         SISIC_TRY(gn(h, nullptr, r.norm2));
+        // Dropout (a tape-recording forward with p > 0 only): h = conv2(dropout(silu(norm2(h)))).  One elementwise launch writes
+        // the dropped activation, which stays on the tape -- conv2 and its weight gradient read it as a plain input
+        const int block = resnets_run++;
+        Buf* hd = nullptr;
+        if (tr && tr->drop_p > 0.0f) {
+            hd = make(r.cout, H, W, &rc); SISIC_TRY(rc);
+            SISIC_TRY(launch_gn_silu_dropout(u->ctx, h->p, gsc, gsh, hd->p, B, r.cout, H * W, tr->drop_seed, tr->drop_call,
+                                             256u + (uint32_t)block, tr->drop_p, tr->drop_inv_keep, s));
+            TapeOp t;
+            t.kind = TapeOp::DROPOUT;
+            t.in0 = h; t.in0_ptr = h->p; t.c0 = r.cout; t.H = H; t.W = W;
+            t.norm = &r.norm2; t.gn_scale = gsc; t.gn_shift = gsh; t.gn_mr = gmr; t.silu = true;
+            t.out = hd; t.drop_block = block;
+            tr->tape.push_back(t);
+        }
         Buf* o = make(r.cout, H, W, &rc); SISIC_TRY(rc);
         {
             ConvOp op;
-            op.w = &r.conv2; op.in0 = h; op.gn_prologue = true; op.silu = true;
+            op.w = &r.conv2; op.in0 = hd ? hd : h; op.gn_prologue = hd == nullptr; op.silu = hd == nullptr;
             op.residual = sc ? sc : x; op.out = o; op.normed = true; op.next_norm = next_norm;
             SISIC_TRY(conv(op));
         }
+        release(hd);
         release(h);
         release(sc);
         *out = o;

@@ -66,7 +66,7 @@ struct Buf {
 
 // One recorded operation of a training-mode forward pass (train.cpp walks the tape backwards).
 struct TapeOp {
-    enum Kind { CONV = 0, ATTN = 1 };
+    enum Kind { CONV = 0, ATTN = 1, DROPOUT = 2 };
     int kind = CONV;
     // ---- CONV: out = conv(act(cat(in0, in1))) + bias + tproj[:, temb_off:] + residual
     ConvW w;                          // by value: the fused q/k/v projection has no ConvW of its own
@@ -89,6 +89,9 @@ struct TapeOp {
     Buf* qkv = nullptr;
     Buf* o = nullptr;
     int C = 0, N = 0;
+    // ---- DROPOUT: out = dropout(silu(in0 * gn_scale + gn_shift)), the mask of resnet block drop_block (TrainState::drop_*);
+    // in0 / in0_ptr, c0, H, W, norm and the gn_* fields as in CONV; the convolution that follows reads `out` with no prologue
+    int drop_block = 0;
 };
 
 // Everything a training run keeps between calls (allocated by sisic_unet_train_begin).
@@ -114,6 +117,11 @@ struct TrainState {
     float* labels_dev = nullptr;      // conditional model: int [B] class labels of the tape (sized in floats)
     size_t labels_cap = 0;
     bool has_labels = false;          // the tape was recorded by sisic_unet_train_forward_cond
+    // dropout of the tape (sisic_unet_set_dropout as it stood when the forward was recorded; drop_p == 0: none): the backward
+    // pass regenerates the masks from these, whatever the handle has been set to since
+    float drop_p = 0.0f, drop_inv_keep = 1.0f;
+    uint64_t drop_seed = 0;
+    uint32_t drop_call = 0;
     float* garena = nullptr;          // activation gradients of one backward pass: one block, zero-filled once
     size_t garena_cap = 0, garena_used = 0;
     float* wgrad_part = nullptr;      // K-split partial weight gradients
@@ -207,6 +215,11 @@ struct sisic_unet {
     float* eps_buf = nullptr;    // sampling loop scratch [B,C,H,W]
     size_t eps_floats = 0;
     std::unique_ptr<sisic::TrainState> train;     // present after sisic_unet_train_begin
+    // ResnetBlock2D dropout (sisic_unet_set_dropout): applied by tape-recording forwards only; drop_call is the counter value
+    // the next one uses
+    float drop_p = 0.0f;
+    uint64_t drop_seed = 0;
+    uint32_t drop_call = 0;
 
     // graph-replayed sampling loop (sisic_sample): one captured step, replayed T-1 times
     int graph_mode = -1;                 // -1: follow latency_mode (SISIC_GRAPH in the environment: 0 / 1 forces)

@@ -25,6 +25,10 @@ asked for; with none of them the calls above are the only ones made):
     ema_model.step(model.parameters())                              HipAdam(..., ema=HipEMA(model))  (rides in the same pass)
     lr_scheduler.step()                                             HipLambdaLR(optimizer, cosine_schedule_with_warmup(...)).step()
 
+and the regulariser of the published model itself, ``UNet2DModel(dropout=p)``: ``HipUNet2DModel(dropout=p)`` drops in every ResNet
+block of the tape-recording forward (spelled-out and fused steps alike), with masks regenerated from a counter in the backward
+pass (include/sisic.h, the mask contract); ``train_class(..., dropout_seed=s)`` seeds them.
+
 No torch.autograd anywhere: the backward pass is explicit HIP kernels (csrc/train.cpp).  Arithmetic is fp32; the
 GradScaler protocol (scale, unscale, inf check, skip, growth/backoff) is implemented, the autocast-to-fp16 is not.
 ``train_step_fused`` runs the whole loop body in ONE C call (sisic_unet_train_step).
@@ -418,9 +422,13 @@ def drop_labels(labels: torch.Tensor, cond_drop_prob: float, null_label: int,
 
 def _train_loop(model: HipUNet2DModel, loader, name: str, epochs: int, lr: float, checkpoint_dir: Optional[str], fused: bool,
                 generator: Optional[torch.Generator], log, max_grad_norm, ema_decay, ema_warmup: bool, lr_schedule,
-                cond_drop_prob: Optional[float]):
+                cond_drop_prob: Optional[float], dropout_seed: int = 0):
     """the loop of train_class; cond_drop_prob not None: the loader yields (images, labels) and the model is conditional"""
     dev = model.device
+    if model.config.dropout > 0:
+        # the masks of this run: seeded here, the counter going on from where the model stands (0 for a new model; a resumed run
+        # that restored it with set_dropout(..., first_call=saved dropout_next_call) continues its stream)
+        model.set_dropout(model.config.dropout, seed=dropout_seed, first_call=model.dropout_next_call)
     scheduler = HipDDPMScheduler(num_train_timesteps=TIMESTEPS, beta_schedule="squaredcos_cap_v2")
     ema = HipEMA(model, decay=ema_decay, use_ema_warmup=ema_warmup) if ema_decay is not None else None
     optimizer = HipAdam(model, lr=lr, max_grad_norm=max_grad_norm, ema=ema)
@@ -486,29 +494,31 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
                 checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
                 log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
                 ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                lr_schedule: Optional[Callable[[int], float]] = None):
+                lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0):
     """``train_class`` of train_diffusion.py:187-266 for one class: epochs over ``loader`` (batches of images in [-1,1],
     [B,3,H,W]), best-loss checkpoint ``unet_{class}_best.pth`` and a checkpoint every 5 epochs.  Returns the per-epoch
     average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG).
 
     Beyond the reference, each off by default: ``max_grad_norm`` clips the global gradient norm; ``ema_decay`` keeps an EMA of
     the weights (``ema_warmup``: EMAModel's warm-up decay) and saves it beside every checkpoint as ``..._ema.pth``;
-    ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch."""
+    ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch.
+    A model built with ``dropout > 0`` trains with it; ``dropout_seed`` seeds its masks (they do not consume ``generator``), and
+    the checkpoints are those of a model without: dropout adds no tensors."""
     if model.config.num_class_embeds is not None:
         raise ValueError("train_class trains an unconditional model; a class-conditional one takes train_conditional")
     return _train_loop(model, loader, class_name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
-                       ema_warmup, lr_schedule, None)
+                       ema_warmup, lr_schedule, None, dropout_seed)
 
 
 def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: float = 0.1, epochs: int = 50, lr: float = LR,
                       checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
                       log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
                       ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                      lr_schedule: Optional[Callable[[int], float]] = None):
+                      lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0):
     """``train_class`` for ONE class-conditional model over all classes: ``loader`` yields ``(images, labels)`` (a
     ``data.DeviceLoader`` over a labelled ``DeviceDataset``), the labels go to the model as ``class_labels``.  Checkpoints
     (``unet_{name}_best.pth``, every 5 epochs, the ``_ema`` files), clipping, EMA, schedule and the returned history are
-    train_class's.
+    train_class's, and so is ``dropout_seed`` for a model built with ``dropout > 0``.
 
     Classifier-free guidance: with probability ``cond_drop_prob`` an image trains under the null label, by convention the
     LAST row of the table, ``num_class_embeds - 1`` -- build the model with ``n_classes + 1`` rows.  Per batch ``generator``
@@ -519,4 +529,4 @@ def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: 
     if not 0.0 <= float(cond_drop_prob) <= 1.0:
         raise ValueError(f"cond_drop_prob must be in [0, 1], got {cond_drop_prob}")
     return _train_loop(model, loader, name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
-                       ema_warmup, lr_schedule, float(cond_drop_prob))
+                       ema_warmup, lr_schedule, float(cond_drop_prob), dropout_seed)

@@ -16,6 +16,7 @@ arguments.  It raises if the model is asked to run anywhere but on an MI355X.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -66,7 +67,7 @@ class HipUNet2DModel:
                  down_block_types: Sequence[str] = ("DownBlock2D", "DownBlock2D", "AttnDownBlock2D", "DownBlock2D"),
                  up_block_types: Sequence[str] = ("UpBlock2D", "AttnUpBlock2D", "UpBlock2D", "UpBlock2D"),
                  class_embed_type=None, norm_num_groups: int = 32, norm_eps: float = 1e-5,
-                 attention_head_dim: int = 8, num_class_embeds: Optional[int] = None, **unsupported):
+                 attention_head_dim: int = 8, num_class_embeds: Optional[int] = None, dropout: float = 0.0, **unsupported):
         if class_embed_type is not None:
             raise NotImplementedError("class_embed_type must be None (the reference's models are unconditional; a "
                                       "class-conditional model is num_class_embeds=N, diffusers' nn.Embedding form)")
@@ -76,7 +77,7 @@ class HipUNet2DModel:
                                  layers_per_block=layers_per_block, block_out_channels=tuple(block_out_channels),
                                  down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types),
                                  norm_num_groups=norm_num_groups, norm_eps=norm_eps,
-                                 attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds)
+                                 attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds, dropout=dropout)
         self.config.validate()
         if attention_head_dim != 8:
             raise NotImplementedError("attention_head_dim must be 8 (the HIP attention kernel is built for d=8)")
@@ -91,6 +92,8 @@ class HipUNet2DModel:
         self._latency_mode = False
         self._params_stale = False            # the library's weights have moved on (optimizer steps) since _params was read
         self._ema_swapped = False             # inside HipEMA.average_parameters(): the library holds the averaged weights
+        self._dropout_seed = 0                # the mask stream of config.dropout (set_dropout): its seed and the counter value
+        self._dropout_call = 0                #   a handle that does not exist yet starts from
 
     # ------------------------------------------------------------------ nn.Module surface
     @property
@@ -106,13 +109,37 @@ class HipUNet2DModel:
         return self
 
     def train(self, mode: bool = True) -> "HipUNet2DModel":
-        """``model.train()`` (diffusion/train_diffusion.py:209).  The network has no dropout or batch statistics, so the
-        mode only decides whether a call records the tape for ``loss.backward()`` (once an optimizer exists, synt_isic_amd.train)."""
+        """``model.train()`` (diffusion/train_diffusion.py:209).  The network has no batch statistics; the mode decides whether
+        a call records the tape for ``loss.backward()`` (once an optimizer exists, synt_isic_amd.train) and, with
+        ``dropout > 0``, whether the ResNet blocks drop: exactly the tape-recording calls do, ``eval()`` calls and every sampling
+        loop never.  A training-mode call of a model with ``dropout > 0`` and no optimizer raises instead of running undropped."""
         self.training = bool(mode)
         return self
 
     def requires_grad_(self, flag: bool = True) -> "HipUNet2DModel":
         return self
+
+    def set_dropout(self, p: float, seed: int = 0, first_call: int = 0) -> "HipUNet2DModel":
+        """``dropout=p`` of the published UNet2DModel from now on (0 turns it off): every ResnetBlock2D computes
+        ``conv2(dropout(silu(norm2(h))))`` in tape-recording forwards.  The masks are a pure function of ``(seed, call, block,
+        sample, element)`` (include/sisic.h, the mask contract); ``call`` starts at ``first_call`` and advances by one per such
+        forward, so ``first_call=k`` reproduces forward k of the stream and ``dropout_next_call`` continues a resumed run."""
+        seed, first_call = int(seed), int(first_call)
+        if not 0 <= seed < 1 << 64 or not 0 <= first_call < 1 << 32:
+            raise ValueError(f"seed must fit 64 bits and first_call 32, got {seed} and {first_call}")
+        config = dataclasses.replace(self.config, dropout=p)
+        config.validate()
+        self.config, self._dropout_seed, self._dropout_call = config, seed, first_call
+        if self._handle is not None:
+            check(_lib.load().sisic_unet_set_dropout(self._handle, float(p), seed, first_call))
+        return self
+
+    @property
+    def dropout_next_call(self) -> int:
+        """the counter value the next tape-recording forward draws its masks with"""
+        if self._handle is not None:
+            return int(_lib.load().sisic_unet_dropout_next_call(self._handle))
+        return self._dropout_call
 
     def set_latency_mode(self, on: bool = True) -> "HipUNet2DModel":
         """Kernel choices for single-image latency (sisic_unet_set_latency_mode): the reference samples one image at a
@@ -268,6 +295,8 @@ class HipUNet2DModel:
         self._handle = h
         if self._latency_mode:
             check(lib.sisic_unet_set_latency_mode(h, 1))
+        if cfg.dropout > 0:
+            check(lib.sisic_unet_set_dropout(h, float(cfg.dropout), self._dropout_seed, self._dropout_call))
         # the library's own view of the expected keys must agree with ours
         n = lib.sisic_unet_num_tensors(h)
         names = [lib.sisic_unet_tensor_name(h, i).decode() for i in range(n)]
@@ -290,6 +319,7 @@ class HipUNet2DModel:
 
     def _release(self) -> None:
         if self._handle is not None:
+            self._dropout_call = int(_lib.load().sisic_unet_dropout_next_call(self._handle))     # a new handle continues the stream
             _lib.load().sisic_unet_destroy(self._handle)
             self._handle = None
             self._uploaded = False
@@ -365,6 +395,10 @@ class HipUNet2DModel:
         out = ops.empty((B, self.config.out_channels, H, W), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         lab = C.cast(labels.data_ptr(), _lib.c_int64_p) if labels is not None else None
+        if self.training and self.config.dropout > 0 and not self._train_begun:
+            raise RuntimeError(f"training-mode call of a model with dropout={self.config.dropout} but no optimizer: dropout is "
+                               "applied by the tape-recording forward, which needs the gradient arenas a HipAdam creates; "
+                               "create the optimizer first, or call model.eval() for an undropped prediction")
         if self.training and self._train_begun:
             # training mode with an optimizer: the same kernels, every activation kept for loss.backward()
             if labels is not None:
