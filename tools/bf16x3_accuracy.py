@@ -1,21 +1,22 @@
 #!/usr/bin/env python3
-"""How accurate would an fp32-equivalent product on the bf16 matrix pipe be?  (NOT built: DESIGN.md section 8.)
+"""How accurate is an fp32-equivalent product on the bf16 matrix pipe?  (The arithmetic of conv_winograd_bf3.inc,
+conv_pointwise_bf3.hip, conv_s2_bf3.hip and the attention scores: DESIGN.md section 4.)
 
-Each fp32 operand is split exactly into three bf16 terms (8 + 8 + 8 significant bits); a product a * b is replaced by the
-six term products with index sum <= 4 (hi*hi, hi*mid, mid*hi, hi*lo, mid*mid, lo*hi), each exact in fp32, accumulated in
-fp32 -- what v_mfma_f32_32x32x16_bf16 would do at 16x the f32 MFMA rate, i.e. 2.7x the matrix throughput of
-v_mfma_f32_32x32x2_f32.  This script emulates both accumulations in numpy for a contraction over K channels of O(1)
+Each fp32 operand is split exactly into three bf16 terms (8 + 8 + 8 significant bits) by TRUNCATION, as the kernels do it:
+hi = the top 16 bits, mid = the top 16 bits of x - hi, lo = the top 16 bits of the rest.  A product a * b is replaced by the
+six term products with index sum <= 4 (hi*hi, mid*mid, hi*mid, mid*hi, hi*lo, lo*hi), each exact in fp32, accumulated in
+fp32 by three v_mfma_f32_32x32x16_bf16 per eight channels (at 16x the f32 MFMA rate, i.e. 2.7x the matrix throughput of
+v_mfma_f32_32x32x2_f32).  This script emulates both accumulations in numpy for a contraction over K channels of O(1)
 operands and reports the error against float64, in units of the largest result -- the quantity the per-kernel parity bound
-(1e-5 * max(1, |ref|)) is stated in.    python tools/bf16x3_accuracy.py
+(1e-5 * max(1, |ref|)) is stated in.  tests/bf3_ref.py states the same arithmetic for the tests (the contract, its mutants,
+each kernel's operand placement).    python tools/bf16x3_accuracy.py
 """
 import numpy as np
 
 
 def to_bf16(x):
-    """round-to-nearest-even truncation of fp32 to bf16, returned as fp32"""
-    u = x.astype(np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return r.astype(np.uint32).view(np.float32)
+    """the top 16 bits of fp32 (truncation: `bits & 0xffff0000` in the kernels), returned as fp32"""
+    return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
 
 
 def split3(x):
@@ -51,9 +52,10 @@ def main():
                     blockp += x2[:, k0:k0 + 8].astype(np.float64) @ y2[k0:k0 + 8, :].astype(np.float64)
                     acc = (acc.astype(np.float64) + blockp).astype(np.float32)
             return np.abs(acc - ref).max() / scale
-        e6 = run([((ah, bh), (ah, bm)), ((am, bh), (am, bm)), ((ah, bl), (al, bh))])
+        # the kernels' three instructions: A = (hi, mid) B = (hi, mid); A = (hi, mid) B = (mid, hi); A = (hi, lo) B = (lo, hi)
+        e6 = run([((ah, bh), (am, bm)), ((ah, bm), (am, bh)), ((ah, bl), (al, bh))])
         z = np.zeros_like
-        e9 = run([((ah, bh), (ah, bm)), ((am, bh), (am, bm)), ((ah, bl), (al, bh)), ((am, bl), (al, bm)), ((al, bl), (z(al), z(bl)))])
+        e9 = run([((ah, bh), (am, bm)), ((ah, bm), (am, bh)), ((ah, bl), (al, bh)), ((am, bl), (al, bm)), ((al, bl), (z(al), z(bl)))])
         print(f"{K:6d} {e32:12.3e} {e6:20.3e} {e9:20.3e} {max(np.abs(ares).max(), np.abs(bres).max()):14.1e}")
 
 
