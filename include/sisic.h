@@ -127,6 +127,13 @@ int sisic_conv_finalizes(const sisic_conv_args* args);
  * args->stats_out, or 0 when the kernel selected for these arguments does not produce them.      */
 int sisic_conv_stats_slots(const sisic_conv_args* args);
 
+/* What sisic_conv2d(args) would run, for tests and tools.  Host only: no device, no stream, nothing is launched.
+ * Returns 0 when the launch would be made, 1 when args->tile_cfg forces a kernel form that does not take these arguments (the
+ * launch's message goes to `refusal`, at most refusal_len bytes, NUL terminated), a negative error code for arguments no kernel
+ * takes.  kernel / cfg / form (each may be NULL): the kernel family, the resolved tile configuration and the family's sub-form
+ * as csrc/conv_plan.h numbers them (1x1 bf16x3 forms: 0 K-split, 1 staged, 2 / 3 64- / 32-pixel items, 4 staged K-split).      */
+int sisic_conv_plan_info(const sisic_conv_args* args, int* kernel, int* cfg, int* form, char* refusal, int refusal_len);
+
 /* Winograd-domain filters U = G g G^T of an OIHW 3x3 weight, computed in float64:
  * number of floats, and dev OIHW -> dev packed [Cin_pad][16][Cout_pad], FOLLOWED by the same filters split into three bf16
  * terms in the operand order of the bf16x3 kernels (pack_device.h).  The buffer must hold sisic_conv_winograd_numel floats:

@@ -102,6 +102,7 @@ SIGNATURES = {
     "sisic_conv2d": (C.c_int, [C.c_void_p, C.POINTER(ConvArgs), C.c_void_p]),
     "sisic_conv_stats_slots": (C.c_int, [C.POINTER(ConvArgs)]),
     "sisic_conv_finalizes": (C.c_int, [C.POINTER(ConvArgs)]),
+    "sisic_conv_plan_info": (C.c_int, [C.POINTER(ConvArgs), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "sisic_groupnorm_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

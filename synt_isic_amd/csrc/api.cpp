@@ -1,8 +1,10 @@
 // api.cpp -- context, error reporting, launch timing and the extern "C" operator entry points
 // of libsisic_hip.so (include/sisic.h).
+#include <cstdio>
 #include <cstring>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "gn_finalize.h"
 
 namespace sisic {
@@ -149,6 +151,18 @@ int sisic_conv2d(sisic_ctx* ctx, const sisic_conv_args* args, void* stream) {
 
 int sisic_conv_stats_slots(const sisic_conv_args* args) { return args ? conv_stats_slots(*args) : 0; }
 int sisic_conv_finalizes(const sisic_conv_args* args) { return args && conv_finalizes(*args) ? 1 : 0; }
+int sisic_conv_plan_info(const sisic_conv_args* args, int* kernel, int* cfg, int* form, char* refusal, int refusal_len) {
+    SISIC_REQUIRE(args && (refusal || refusal_len <= 0), "conv_plan_info: null argument");
+    if (refusal && refusal_len > 0) refusal[0] = 0;
+    ConvPlan plan;
+    SISIC_TRY(conv_plan(*args, &plan));
+    if (kernel) *kernel = (int)plan.kernel;
+    if (cfg) *cfg = plan.cfg;
+    if (form) *form = plan.form;
+    if (!plan.refusal[0]) return 0;
+    if (refusal && refusal_len > 0) std::snprintf(refusal, (size_t)refusal_len, "%s", plan.refusal);
+    return 1;
+}
 
 int sisic_groupnorm_finalize(sisic_ctx* ctx, const float* stats0, int c0, int slots0, const float* stats1, int c1,
                              int slots1, int B, int HW, int groups, float eps, const float* gamma, const float* beta,

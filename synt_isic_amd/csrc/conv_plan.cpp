@@ -11,10 +11,11 @@ namespace sisic {
 namespace {
 
 // the dispatch switches: each read once per process, on unless set to 0
-struct Switches { bool wino_wide, wino_bf3, wino_col, ksplit, pointwise, pointwise_bf3, pointwise_ksplit, s2_bf3; };
+struct Switches { bool wino_wide, wino_bf3, wino_col, ksplit, pointwise, pointwise_bf3, pointwise_ksplit, s2_bf3, pointwise_staged_ksplit; };
 const Switches& switches() {
     static const Switches sw{env_on("SISIC_WINO_WIDE"), env_on("SISIC_WINO_BF16X3"), env_on("SISIC_WINO_COL"), env_on("SISIC_KSPLIT"),
-                             env_on("SISIC_POINTWISE"), env_on("SISIC_POINTWISE_BF16X3"), env_on("SISIC_POINTWISE_KSPLIT"), env_on("SISIC_S2_BF16X3")};
+                             env_on("SISIC_POINTWISE"), env_on("SISIC_POINTWISE_BF16X3"), env_on("SISIC_POINTWISE_KSPLIT"), env_on("SISIC_S2_BF16X3"),
+                             env_on("SISIC_POINTWISE_STAGED_KSPLIT")};
     return sw;
 }
 
@@ -139,10 +140,36 @@ void plan_winograd(const sisic_conv_args& a, ConvPlan& pl) {
     if (pl.finalizes) PLAN_REFUSE_UNLESS(a.fin_beta && a.fin_scale && a.fin_shift, "conv2d: fin_gamma given without fin_beta / fin_scale / fin_shift");
 }
 
+// The layers the automatic choice gives to the staged K-split form (conv_pwbsk_kernel) instead of the K-split form -- unless
+// SISIC_POINTWISE_STAGED_KSPLIT=0.  By layer shape and batch; both forms give the same bits.  Measured, the two forms alternated
+// twice (profiles/r23/conv_bench_pointwise_staged_ksplit.txt), at batch 64 / 128, K-split vs staged K-split in us:
+//   256 -> 256 @16 + residual 30.4 - 31.6 vs 22.8 - 24.2 / 54.4 - 54.9 vs 42.0 - 42.4;   256 + 256 -> 256 @16 38.2 - 39.8 vs 32.0 - 32.4 / 72 vs 62;
+//   256 + 128 -> 256 @16 32.6 vs 25.7 / 57.8 vs 48.8;   128 -> 256 @16 16.9 vs 14.6 / 29.3 vs 25.7
+// -- the 16x16 level's 256-channel layers with whole rounds of one workgroup per CU (256 CUs), which is what was measured.
+// NOT routed, slower there: 256 + 128 -> 128 @32 (58.9 vs 65.2: eight waves and 48 KB leave the CU to one workgroup's latencies) and
+// 256 + 256 -> 256 @8 (13.6 vs 23.5: 64 workgroups for 256 CUs).
+bool pwbsk_routed(const sisic_conv_args& a, bool ks_ok) {
+    const int HW = a.Hin * a.Win, Cin = a.c0 + a.c1;
+    const int64_t nwg = (int64_t)a.B * (HW / 64);
+    return switches().pointwise_staged_ksplit && switches().pointwise_ksplit && ks_ok && a.gn_scale == nullptr && !a.relu && HW == 256 && a.Cout == 256 &&
+           Cin <= 512 && nwg >= 256 && nwg % 256 == 0;
+}
+
 // 1x1 stride 1 with fp32-equivalent products on the bf16 matrix pipe: which of the kernel's forms
 void plan_pointwise_bf3(const sisic_conv_args& a, ConvPlan& pl) {
     const int HW = a.Hin * a.Win, Cin = a.c0 + a.c1;
     pl.kernel = CK_POINTWISE_BF3; pl.cfg = a.tile_cfg ? a.tile_cfg : CFG_PWB; pl.stats_slots = HW / 32;      // one slot per 32 pixels, every form
+    // the staged K-split form (tile_cfg 37 forces it): one workgroup per 64-pixel tile, waves = channel items x K quarters, the
+    // tile's operands split once into LDS.  The bits of the K-split form, so the choice between the two may depend on the batch.
+    // (Its own conditions first: theirs is the message a forced 37 reports.)
+    if (a.tile_cfg == CFG_PWB_STAGED_KSPLIT) {
+        PLAN_REFUSE_UNLESS((Cin / 8) % (4 * PWB_WAVES) == 0, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 needs a multiple of 128 input channels");
+        PLAN_REFUSE_UNLESS(HW % 64 == 0, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 needs whole 64-pixel tiles");
+        PLAN_REFUSE_UNLESS(a.Cout == 64 || a.Cout == 128 || a.Cout == 256, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 needs 64, 128 or 256 output channels");
+        PLAN_REFUSE_UNLESS(a.gn_scale == nullptr, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 has no GroupNorm prologue");
+        PLAN_REFUSE_UNLESS(!a.relu, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 has no relu");
+        PLAN_REFUSE_UNLESS(a.Cout % 64 != 0 || pwbsk_lds_bytes(Cin, a.Cout) <= PWBSK_MAX_LDS, "conv2d(pointwise bf16x3, staged K-split): tile_cfg 37 needs %zu bytes of LDS", pwbsk_lds_bytes(Cin, a.Cout));
+    }
     PLAN_REFUSE_UNLESS(conv_pointwise_bf3_applicable(a), "conv2d(pointwise bf16x3): shape not supported by tile_cfg 28");
     // the K-split form (tile_cfg 35 forces it) for the 16x16 and 8x8 levels' layers of up to 256 output channels -- by SHAPE only:
     // its bits are its own.  Measured at batch 64 (profiles/r04/conv_bench_pointwise_forms.txt): 256 -> 256 @16 27.3 vs 34.2 us,
@@ -154,13 +181,15 @@ void plan_pointwise_bf3(const sisic_conv_args& a, ConvPlan& pl) {
     const bool staged_ok = a.Cout / 64 >= 6 && a.Cout / 64 <= PWBS_MAX_WAVES && pwbs_lds_bytes(Cin) <= 150 * 1024;
     if (a.tile_cfg == CFG_PWB_KSPLIT) PLAN_REFUSE_UNLESS(ks_ok, "conv2d(pointwise bf16x3, K-split): tile_cfg 35 needs a multiple of 128 input channels");
     if (a.tile_cfg == CFG_PWB_STAGED) PLAN_REFUSE_UNLESS(staged_ok, "conv2d(pointwise bf16x3, staged): tile_cfg 34 needs 384 .. 768 output channels and at most %d input channels", (150 * 1024) / 392);
-    if (a.tile_cfg == CFG_PWB_KSPLIT || (a.tile_cfg == 0 && ks_ok && HW <= 256 && a.Cout <= 256 && switches().pointwise_ksplit)) pl.form = PWB_FORM_KSPLIT;
+    if (a.tile_cfg == CFG_PWB_STAGED_KSPLIT || (a.tile_cfg == 0 && pwbsk_routed(a, ks_ok))) pl.form = PWB_FORM_STAGED_KSPLIT;
+    else if (a.tile_cfg == CFG_PWB_KSPLIT || (a.tile_cfg == 0 && ks_ok && HW <= 256 && a.Cout <= 256 && switches().pointwise_ksplit)) pl.form = PWB_FORM_KSPLIT;
     else if (a.tile_cfg == CFG_PWB_STAGED || (a.tile_cfg == 0 && staged_ok && (int64_t)a.B * (HW / 64) >= 128)) pl.form = PWB_FORM_STAGED;
     // 64-pixel items where they give every SIMD at least two waves (1024 SIMDs), 32-pixel items otherwise: a lone wave has
     // nobody to hide its latencies.  (The choice depends on the batch; the bits of an output do not: its chain of MFMAs is the same.)
     else if (a.tile_cfg == CFG_PWB_64PX || (a.tile_cfg != CFG_PWB_32PX && (int64_t)a.B * (HW / 64) * (a.Cout / 64) >= 2048)) pl.form = PWB_FORM_64PX;
     else pl.form = PWB_FORM_32PX;
-    // rider jobs go with the instances without a GroupNorm prologue of the two four-wave kernels (conv_pointwise_bf3.hip)
+    // rider jobs go with the instances without a GroupNorm prologue of the two four-wave kernels and with the staged K-split form
+    // (conv_pointwise_bf3.hip)
     pl.carries_rider = a.gn_scale == nullptr && pl.form != PWB_FORM_STAGED;
 }
 
@@ -178,7 +207,7 @@ int plan_direct(const sisic_conv_args& a, ConvPlan& pl) {
         SISIC_REQUIRE(!a.upsample, "conv2d: 1x1 with upsample");
         // fp32-equivalent products on the bf16 matrix pipe (conv_pointwise_bf3.hip) for whole 64-pixel x 64-channel tiles --
         // unless SISIC_POINTWISE_BF16X3=0.  (Shape conditions only: an image's bits must not depend on the batch it is in.)
-        const bool pwb_forced = (cfg >= CFG_PWB && cfg <= CFG_PWB_64PX) || cfg == CFG_PWB_STAGED || cfg == CFG_PWB_KSPLIT;
+        const bool pwb_forced = (cfg >= CFG_PWB && cfg <= CFG_PWB_64PX) || cfg == CFG_PWB_STAGED || cfg == CFG_PWB_KSPLIT || cfg == CFG_PWB_STAGED_KSPLIT;
         if (pwb_forced || (cfg == 0 && sw.pointwise_bf3 && conv_pointwise_bf3_applicable(a))) {
             plan_pointwise_bf3(a, pl);
             return SISIC_OK;

@@ -13,7 +13,8 @@ namespace sisic {
 // 1 .. 19, 21 .. 27, 31 .. 33, 41, 42: tilings of the direct MFMA kernel, SISIC_DIRECT_TILINGS below
 // 20: the lean 1x1 kernel (conv_pointwise.hip)
 // 28: 1x1 with fp32-equivalent products on the bf16 matrix pipe (conv_pointwise_bf3.hip), form chosen; 29 / 30: its 32- / 64-pixel
-//     items forced (tests of the two forms' bit-equality); 34 / 35: its staged / K-split form forced
+//     items forced (tests of the two forms' bit-equality); 34 / 35: its staged / K-split form forced; 37: its staged K-split form
+//     forced (the bits of 35)
 // 36: 3x3 stride 2 on the bf16 pipe (conv_s2_bf3.hip)
 // 50 .. 52: the vector-ALU kernel for Cout <= 4 (conv_small.hip) with 32-row tiles / 8-row tiles / one channel group forced
 // Winograd F(2x2,3x3), conv_winograd.hip (properties: the table in conv_plan.cpp):
@@ -31,7 +32,7 @@ namespace sisic {
 //           workgroup (bit-identical to 90) / on the bf16x3 kernel with four images per workgroup
 enum ConvCfg : int {
     CFG_AUTO = 0, CFG_POINTWISE = 20, CFG_PWB = 28, CFG_PWB_32PX = 29, CFG_PWB_64PX = 30, CFG_PWB_STAGED = 34, CFG_PWB_KSPLIT = 35,
-    CFG_S2_BF3 = 36, CFG_SMALL_32ROWS = 50, CFG_SMALL_8ROWS = 51, CFG_SMALL_ONE_GROUP = 52,
+    CFG_S2_BF3 = 36, CFG_PWB_STAGED_KSPLIT = 37, CFG_SMALL_32ROWS = 50, CFG_SMALL_8ROWS = 51, CFG_SMALL_ONE_GROUP = 52,
     CFG_WINO_1IMG_8W = 60, CFG_WINO_4IMG_8W = 61, CFG_WINO_1IMG_16W = 62, CFG_WINO_4IMG_16W = 63,
     CFG_WINO_1IMG_8W_STAG = 64, CFG_WINO_4IMG_8W_STAG = 65, CFG_WINO_1IMG_16W_STAG = 66, CFG_WINO_4IMG_16W_STAG = 67,
     CFG_WINO_WIDE128 = 68, CFG_WINO_WIDE64 = 69, CFG_WINO_COL128 = 70, CFG_WINO_COL64 = 71, CFG_WINO_SECOND128 = 72, CFG_WINO_SECOND64 = 73,
@@ -64,7 +65,7 @@ enum ConvCfg : int {
 // conv_s2_bf3.hip; conv_winograd.hip's first geometry (and its nine-position form for nearest-2x inputs), conv_winograd_wide.inc,
 // conv_winograd_col.inc, conv_winograd_bf3.inc -- each of the four also K-split (ConvPlan::ksplit > 1) with a reduction launch behind it
 enum ConvKernel { CK_SMALLCOUT, CK_DIRECT, CK_POINTWISE, CK_POINTWISE_BF3, CK_S2_BF3, CK_WINO_FIRST, CK_WINO_SECOND, CK_WINO_THIRD, CK_WINO_BF3 };
-enum PwbForm { PWB_FORM_KSPLIT, PWB_FORM_STAGED, PWB_FORM_64PX, PWB_FORM_32PX };
+enum PwbForm { PWB_FORM_KSPLIT, PWB_FORM_STAGED, PWB_FORM_64PX, PWB_FORM_32PX, PWB_FORM_STAGED_KSPLIT };
 // the 8x8 level's reduction; REDUCE_64PX: planes of exactly 64 pixels and 16-byte aligned residual / out / stats_out
 enum ReduceForm { REDUCE_ANY, REDUCE_64PX };
 
@@ -89,6 +90,15 @@ constexpr int PWB_WAVES = 4;             // waves (= independent work items) per
 constexpr int PWBS_MAX_WAVES = 12;       // staged form: channel items (= waves) of a workgroup
 // staged form: LDS holds the image's 64 pixels of every input channel as split operands (6 bytes per value) and the GroupNorm table
 inline size_t pwbs_lds_bytes(int Cin) { return (size_t)(Cin / 8) * 2 * 64 * 24 + 8 * (size_t)Cin; }
+// staged K-split form: waves = (Cout / 64 channel items) x (PWB_WAVES K quarters); LDS holds at most PWBSK_CAP chunks of every
+// quarter as split operands (longer contractions run in passes) and later one 32-channel block of every wave's partial accumulators
+constexpr int PWBSK_MAX_WAVES = 16, PWBSK_CAP = 8;
+constexpr size_t PWBSK_MAX_LDS = 128 * 1024;
+inline size_t pwbsk_lds_bytes(int Cin, int Cout) {
+    const int nl = Cin / 8 / PWB_WAVES;
+    const size_t operands = (size_t)PWB_WAVES * (nl < PWBSK_CAP ? nl : PWBSK_CAP) * 2 * 64 * 24, partials = (size_t)PWB_WAVES * (Cout / 64) * 32 * 64 * 4;
+    return operands > partials ? operands : partials;
+}
 
 struct ConvPlan {
     ConvKernel kernel;

@@ -572,6 +572,73 @@ __global__ void __launch_bounds__(64 * PWB_WAVES, 4) conv_pwbk_kernel(const PwbP
 // split, packed exactly as above -- into LDS ONCE (Cin x 64 pixels x 6 bytes: 96 KB at 256 channels), then every wave runs the
 // contraction of its own channel item with operands that are two LDS reads per chunk and pixel block; filters from global memory
 // two chunks ahead as before.  The chain of MFMAs of an output is the one of the forms above: same bits.
+//
+// The operand region is shared with the staged K-split form below (conv_pwbsk_kernel): per LDS slot (one 8-channel chunk) and
+// pixel block, [64 lanes][(hi, mid) 4 dwords] in S_hm and [64 lanes][lo 2 dwords] in S_lo.  These three are the only code that
+// knows the layout.
+// the lane's four channels of absolute chunk c, its pixel pair (full lines: 8 bytes per lane)
+__device__ __forceinline__ void pwbs_load_chunk(const __amdgpu_buffer_rsrc_t rs0, const __amdgpu_buffer_rsrc_t rs1, const int c0, const int HW,
+                                                const int c, const unsigned x_voff, pwb_f2 (&xr)[4]) {
+    const int cc0 = 8 * c;
+    if (cc0 < c0) {                                                 // the concat seam lies on a chunk boundary (launcher)
+        const unsigned soff = 4u * (unsigned)(cc0 * HW);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xr[k] = __builtin_bit_cast(pwb_f2, __builtin_amdgcn_raw_buffer_load_b64(rs0, x_voff, soff + 4u * (unsigned)(k * HW), 0));
+    } else {
+        const unsigned soff = 4u * (unsigned)((cc0 - c0) * HW);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xr[k] = __builtin_bit_cast(pwb_f2, __builtin_amdgcn_raw_buffer_load_b64(rs1, x_voff, soff + 4u * (unsigned)(k * HW), 0));
+    }
+}
+// GroupNorm (+ SiLU) with the lane's four (scale, shift) pairs at gp (PRO != 0), the three-term split and the packed operands of
+// both pixel blocks into LDS slot `slot` (the lane mapping and split of conv_pwb_kernel's `make`)
+template <int PRO>
+__device__ __forceinline__ void pwbs_split_store(const pwb_f2 (&xr)[4], const float* gp, unsigned* const S_hm, unsigned* const S_lo, const int slot,
+                                                 const int lane) {
+    pwb_f4 g01 = {1.0f, 0.0f, 1.0f, 0.0f}, g23 = g01;
+    if constexpr (PRO != 0) {
+        g01 = *reinterpret_cast<const pwb_f4*>(gp);
+        g23 = *reinterpret_cast<const pwb_f4*>(gp + 4);
+    }
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float e = nb ? xr[k].y : xr[k].x;
+            if constexpr (PRO != 0) {
+                const float sc = k == 0 ? g01.x : (k == 1 ? g01.z : (k == 2 ? g23.x : g23.z));
+                const float sh = k == 0 ? g01.y : (k == 1 ? g01.w : (k == 2 ? g23.y : g23.w));
+                e = e * sc + sh;
+                if constexpr (PRO == 2) e = pwb_silu(e);
+            }
+            v[k] = e;
+        }
+        unsigned hi[2], mid[2], lo[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float v0 = v[2 * q], v1 = v[2 * q + 1];
+            const unsigned h0 = __float_as_uint(v0) & 0xffff0000u, h1 = __float_as_uint(v1) & 0xffff0000u;
+            const float r0 = v0 - __uint_as_float(h0), r1 = v1 - __uint_as_float(h1);
+            const unsigned m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
+            const float l0 = r0 - __uint_as_float(m0), l1 = r1 - __uint_as_float(m1);
+            hi[q] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
+            mid[q] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
+            lo[q] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
+        }
+        *reinterpret_cast<pwb_u4*>(S_hm + ((size_t)(slot * 2 + nb) * 64 + lane) * 4) = pwb_u4{hi[0], hi[1], mid[0], mid[1]};
+        *reinterpret_cast<pwb_u2*>(S_lo + ((size_t)(slot * 2 + nb) * 64 + lane) * 2) = pwb_u2{lo[0], lo[1]};
+    }
+}
+// the three B operands of LDS slot `slot`, pixel block nb: two LDS reads
+__device__ __forceinline__ void pwbs_read_b(const unsigned* const S_hm, const unsigned* const S_lo, const int slot, const int nb, const int lane,
+                                            pwb_u4& hm, pwb_u4& mh, pwb_u4& lh) {
+    hm = *reinterpret_cast<const pwb_u4*>(S_hm + ((size_t)(slot * 2 + nb) * 64 + lane) * 4);
+    const pwb_u2 lo = *reinterpret_cast<const pwb_u2*>(S_lo + ((size_t)(slot * 2 + nb) * 64 + lane) * 2);
+    mh = pwb_u4{hm.z, hm.w, hm.x, hm.y};
+    lh = pwb_u4{lo.x, lo.y, hm.x, hm.y};
+}
+
 template <int PRO>
 __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const PwbParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -613,51 +680,8 @@ __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const Pw
     // ---- stage: wave w splits chunks w, w + nwaves, ... (the lane mapping, GroupNorm and split of conv_pwb_kernel's `make`)
     for (int c = wave_u; c < n; c += nwaves) {
         pwb_f2 xr[4];
-        const int cc0 = 8 * c;
-        if (cc0 < p.c0) {
-            const unsigned soff = 4u * (unsigned)(cc0 * HW);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) xr[k] = __builtin_bit_cast(pwb_f2, __builtin_amdgcn_raw_buffer_load_b64(rs0, x_voff, soff + 4u * (unsigned)(k * HW), 0));
-        } else {
-            const unsigned soff = 4u * (unsigned)((cc0 - p.c0) * HW);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) xr[k] = __builtin_bit_cast(pwb_f2, __builtin_amdgcn_raw_buffer_load_b64(rs1, x_voff, soff + 4u * (unsigned)(k * HW), 0));
-        }
-        pwb_f4 g01 = {1.0f, 0.0f, 1.0f, 0.0f}, g23 = g01;
-        if constexpr (PRO != 0) {
-            const float* gp = gnL + 2 * (8 * c + 4 * half);
-            g01 = *reinterpret_cast<const pwb_f4*>(gp);
-            g23 = *reinterpret_cast<const pwb_f4*>(gp + 4);
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float e = nb ? xr[k].y : xr[k].x;
-                if constexpr (PRO != 0) {
-                    const float sc = k == 0 ? g01.x : (k == 1 ? g01.z : (k == 2 ? g23.x : g23.z));
-                    const float sh = k == 0 ? g01.y : (k == 1 ? g01.w : (k == 2 ? g23.y : g23.w));
-                    e = e * sc + sh;
-                    if constexpr (PRO == 2) e = pwb_silu(e);
-                }
-                v[k] = e;
-            }
-            unsigned hi[2], mid[2], lo[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float v0 = v[2 * q], v1 = v[2 * q + 1];
-                const unsigned h0 = __float_as_uint(v0) & 0xffff0000u, h1 = __float_as_uint(v1) & 0xffff0000u;
-                const float r0 = v0 - __uint_as_float(h0), r1 = v1 - __uint_as_float(h1);
-                const unsigned m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-                const float l0 = r0 - __uint_as_float(m0), l1 = r1 - __uint_as_float(m1);
-                hi[q] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-                mid[q] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-                lo[q] = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
-            }
-            *reinterpret_cast<pwb_u4*>(S_hm + ((size_t)(c * NB + nb) * 64 + lane) * 4) = pwb_u4{hi[0], hi[1], mid[0], mid[1]};
-            *reinterpret_cast<pwb_u2*>(S_lo + ((size_t)(c * NB + nb) * 64 + lane) * 2) = pwb_u2{lo[0], lo[1]};
-        }
+        pwbs_load_chunk(rs0, rs1, p.c0, HW, c, x_voff, xr);
+        pwbs_split_store<PRO>(xr, gnL + 2 * (8 * c + 4 * half), S_hm, S_lo, c, lane);
     }
     __syncthreads();
 
@@ -682,9 +706,8 @@ __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const Pw
     auto chunk = [&](int c, const pwb_u4 (&fa)[CB], const pwb_u2 (&fl)[CB]) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            const pwb_u4 hm = *reinterpret_cast<const pwb_u4*>(S_hm + ((size_t)(c * NB + nb) * 64 + lane) * 4);
-            const pwb_u2 lo = *reinterpret_cast<const pwb_u2*>(S_lo + ((size_t)(c * NB + nb) * 64 + lane) * 2);
-            const pwb_u4 mh = {hm.z, hm.w, hm.x, hm.y}, lh = {lo.x, lo.y, hm.x, hm.y};
+            pwb_u4 hm, mh, lh;
+            pwbs_read_b(S_hm, S_lo, c, nb, lane, hm, mh, lh);
 #pragma unroll
             for (int x = 0; x < CB; ++x) {
                 const pwb_u4 a_hl = {fa[x].x, fa[x].y, fl[x].x, fl[x].y};
@@ -750,6 +773,215 @@ __global__ void __launch_bounds__(64 * PWBS_MAX_WAVES) conv_pwbs_kernel(const Pw
             }
         }
     }
+}
+
+// ---- STAGED K-SPLIT form (tile_cfg 37): the two forms above combined for the 16x16 level's layers of up to 256 output channels.
+// The K-split form's four workgroups of a 32-pixel block and 256 output channels each load and split the same activations, and a
+// CU walks two resident rounds of its eight-chunk latency chains.  Here ONE workgroup owns 64 pixels of an image and ALL output
+// channels; its waves are (channel item) x (K quarter) -- 4, 8 or 16 of them:
+//   1  all waves together stage the tile's split operands into LDS once (the staged form's region and helpers; no prologue:
+//      the layers this form is for have none), at most PWBSK_CAP chunks of every K quarter at a time -- 256 input channels, 96 KB;
+//      longer contractions (the shortcuts' 256 + 256 and 256 + 128) run in passes, each the next slice of EVERY quarter, so a
+//      wave's accumulation order over its own quarter is the K-split form's
+//   2  wave (item, kq) runs chunks kq nl .. kq nl + nl - 1 on both pixel blocks: B operands are LDS reads, filters come
+//      straight from the split filter region two chunks ahead (across the passes' barriers)
+//   3  the partial accumulators go through LDS over the operand region, one 32-channel block of every item at a time (sixteen
+//      waves x 32 registers = 128 KB); wave (item, kq) sums -- ((k0 + k1) + k2) + k3, then bias, then residual: the K-split
+//      form's expression -- and stores rows 4 kq .. 4 kq + 3 of the block for the lane's pixel pair.  GroupNorm partials per 32
+//      consecutive pixels over the pair-first tree of the 64-pixel forms, which is the 32-pixel forms' tree (conv_pwb_kernel).
+// Every output and every partial: the bits of the K-split form (tests/test_gpu_pointwise_staged_ksplit.py).
+// Rider workgroups as in the four-wave kernels, one finalisation job per WAVE of this launch's workgroup.
+// timing-only builds (wrong results, never shipped; profiles/r23/pwbsk_phases.txt): bit 0 no staging, bit 1 no channel loop,
+// bit 2 no K-sum through LDS (a wave stores from its own accumulators), bit 3 no filter fetch
+#ifndef PWBSK_VAR
+#define PWBSK_VAR 0
+#endif
+__global__ void __launch_bounds__(64 * PWBSK_MAX_WAVES) conv_pwbsk_kernel(const PwbParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nwaves = PWB_WAVES * p.n_co_items;
+    int L = blockIdx.x;
+    if (L < p.n_rider_wg) {                   // rider workgroups first: before any LDS use and barrier; surplus waves return inside
+        gn_finalize_job(p.rider, L * nwaves + wave_u, lane);
+        return;
+    }
+    L -= p.n_rider_wg;
+    int wg;
+    {   // XCD-aware bijective remap (conv_mfma.hip)
+        const int nwg = p.nwg;
+        const int xcd = L & 7, slot = L >> 3, q = nwg >> 3, r = nwg & 7;
+        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    }
+    const int half = lane >> 5, l31 = lane & 31;
+    int px_t = wg % p.n_px, b = wg / p.n_px;
+    asm volatile("" : "+s"(px_t), "+s"(b));
+    constexpr int CB = 2, NB = 2;
+    const int co_i = wave_u / PWB_WAVES, kq = wave_u % PWB_WAVES;
+    const int px0 = 64 * px_t, co0 = 64 * co_i;
+    const int HW = p.HW;
+    const int nl = p.nchunks / PWB_WAVES, cb = kq * nl;             // this wave's chunks: cb .. cb + nl - 1 (conv_pwbk_kernel's partition)
+    const int cap = nl < PWBSK_CAP ? nl : PWBSK_CAP;                // chunks of a K quarter in LDS at a time
+
+    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in0 + (size_t)b * p.c0 * HW), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.in1 ? p.in1 + (size_t)b * p.c1 * HW : p.in0), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wb), 0, -1, 0x00020000);
+    const unsigned x_voff = 4u * (unsigned)((4 * half) * HW + px0 + NB * l31);
+    const unsigned a_lane16 = 16u * (unsigned)lane, a_lane8 = 8u * (unsigned)lane;
+
+    // LDS: the staged form's operand region, slot = kq cap + (chunk of the pass); later the partials [wave][pixel block][16][64 lanes]
+    unsigned* const S_hm = reinterpret_cast<unsigned*>(smem);
+    unsigned* const S_lo = S_hm + (size_t)(PWB_WAVES * cap) * NB * 64 * 4;
+    float* const P_lds = smem;
+
+    pwb_f32x16 acc[CB][NB];
+#pragma unroll
+    for (int x = 0; x < CB; ++x)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[x][nb][r] = 0.0f;
+    pwb_u4 ua[CB], ub[CB];
+    pwb_u2 ul[CB], um[CB];
+    auto load_f = [&](int c, pwb_u4 (&fa)[CB], pwb_u2 (&fl)[CB]) {
+        const unsigned s0 = 3072u * (unsigned)(c * p.n_co64 + co_i);
+#pragma unroll
+        for (int x = 0; x < CB; ++x) {
+#if (PWBSK_VAR & 8) != 0
+            fa[x] = pwb_u4{a_lane16 + (unsigned)c, a_lane8, s0, a_lane16 ^ s0};
+            fl[x] = pwb_u2{fa[x].z, fa[x].w};
+#else
+            fa[x] = __builtin_amdgcn_raw_buffer_load_b128(rsw, a_lane16, s0 + 1024u * (unsigned)x, 0);
+            fl[x] = __builtin_amdgcn_raw_buffer_load_b64(rsw, a_lane8, s0 + 2048u + 512u * (unsigned)x, 0);
+#endif
+        }
+    };
+    auto chunk = [&](int slot, const pwb_u4 (&fa)[CB], const pwb_u2 (&fl)[CB]) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            pwb_u4 hm, mh, lh;
+            pwbs_read_b(S_hm, S_lo, slot, nb, lane, hm, mh, lh);
+#pragma unroll
+            for (int x = 0; x < CB; ++x) {                          // (the order of conv_pwbk_kernel's mm())
+                const pwb_u4 a_hl = {fa[x].x, fa[x].y, fl[x].x, fl[x].y};
+                acc[x][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pwb_bf16x8, fa[x]), __builtin_bit_cast(pwb_bf16x8, hm), acc[x][nb], 0, 0, 0);
+                acc[x][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pwb_bf16x8, fa[x]), __builtin_bit_cast(pwb_bf16x8, mh), acc[x][nb], 0, 0, 0);
+                acc[x][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pwb_bf16x8, a_hl), __builtin_bit_cast(pwb_bf16x8, lh), acc[x][nb], 0, 0, 0);
+            }
+        }
+    };
+    // the wave's first two filter chunks are on their way while the tile is staged (nl is a multiple of four: the plan)
+    load_f(cb, ua, ul);
+    load_f(cb + 1, ub, um);
+    for (int p0 = 0; p0 < nl; p0 += cap) {                          // a pass: chunks p0 .. p0 + len - 1 of EVERY quarter
+        const int len = nl - p0 < cap ? nl - p0 : cap, nslots = PWB_WAVES * len;
+        if (p0 != 0) __syncthreads();                               // every wave is through the previous pass's operands
+        // ---- stage: two chunks per wave and turn, all sixteen loads of a lane in flight before the first split
+#if (PWBSK_VAR & 1) == 0
+        for (int t = wave_u; t < nslots; t += 2 * nwaves) {
+            const int t1 = t + nwaves;
+            pwb_f2 xa[4], xb[4];
+            pwbs_load_chunk(rs0, rs1, p.c0, HW, (t / len) * nl + p0 + t % len, x_voff, xa);
+            if (t1 < nslots) pwbs_load_chunk(rs0, rs1, p.c0, HW, (t1 / len) * nl + p0 + t1 % len, x_voff, xb);
+            pwbs_split_store<0>(xa, nullptr, S_hm, S_lo, (t / len) * cap + t % len, lane);
+            if (t1 < nslots) pwbs_split_store<0>(xb, nullptr, S_hm, S_lo, (t1 / len) * cap + t1 % len, lane);
+        }
+#endif
+        __syncthreads();
+        // ---- contract: this wave's slice of the pass (len is even)
+#if (PWBSK_VAR & 2) == 0
+        for (int j = 0; j < len; j += 2) {
+            chunk(kq * cap + j, ua, ul);
+            if (p0 + j + 2 < nl) load_f(cb + p0 + j + 2, ua, ul);
+            chunk(kq * cap + j + 1, ub, um);
+            if (p0 + j + 3 < nl) load_f(cb + p0 + j + 3, ub, um);
+        }
+#else
+        acc[0][0][0] += __uint_as_float(ua[0].x ^ ub[1].y ^ ul[0].x ^ um[1].y) + __uint_as_float(S_hm[lane + 64 * kq]);
+#endif
+    }
+
+    // ---- K-sum and epilogue, one 32-channel block of every item per round
+    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)b * p.Cout * HW, 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.residual ? p.residual + (size_t)b * p.Cout * HW : p.out), 0, -1, 0x00020000);
+    const unsigned o_voff = 4u * (unsigned)((4 * half) * HW + px0 + NB * l31);
+    const int slots = HW / 32;
+#pragma unroll
+    for (int x = 0; x < CB; ++x) {
+#if (PWBSK_VAR & 4) == 0
+        __syncthreads();                      // every wave is through its operand reads (x == 0) / the first round's partials
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) P_lds[((wave_u * NB + nb) * 16 + r) * 64 + lane] = acc[x][nb][r];
+        __syncthreads();
+#endif
+        float add[4];
+        pwb_f2 res[4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {      // accumulator row r = 4 kq + rr: channel 8 (r >> 2) + (r & 3) of the block
+            const int cs = co0 + 32 * x + 8 * kq + rr;
+            const int col = cs + 4 * half;
+            add[rr] = 0.0f;
+            if (p.bias) add[rr] += p.bias[col];
+            if (p.chan_bias) add[rr] += p.chan_bias[(size_t)b * p.chan_bias_stride + col];
+            res[rr] = pwb_f2{0.0f, 0.0f};
+            if (p.residual) res[rr] = __builtin_bit_cast(pwb_f2, __builtin_amdgcn_raw_buffer_load_b64(rsr, o_voff, 4u * (unsigned)(cs * HW), 0));
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int r = 4 * kq + rr;
+            const int cs = co0 + 32 * x + 8 * kq + rr;
+            float vv[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                float part[PWB_WAVES];
+#if (PWBSK_VAR & 4) == 0
+#pragma unroll
+                for (int k = 0; k < PWB_WAVES; ++k) part[k] = P_lds[(((co_i * PWB_WAVES + k) * NB + nb) * 16 + r) * 64 + lane];
+#else
+#pragma unroll
+                for (int k = 0; k < PWB_WAVES; ++k) part[k] = acc[x][nb][4 * k + rr];
+#endif
+                float v = ((part[0] + part[1]) + part[2]) + part[3];
+                v = v + add[rr] + (nb ? res[rr].y : res[rr].x);
+                vv[nb] = v;
+            }
+            __builtin_amdgcn_raw_buffer_store_b64(pwb_u2{__float_as_uint(vv[0]), __float_as_uint(vv[1])}, rso, o_voff, 4u * (unsigned)(cs * HW), 0);
+            if (p.stats) {
+                const int co = cs + 4 * half;
+                const float s1 = pwb_row16_sum(vv[0] + vv[1]);
+                const float mean = s1 * (1.0f / 32.0f);
+                const float d0 = vv[0] - mean, d1 = vv[1] - mean;
+                float q0, q1;
+                asm volatile("v_mul_f32 %0, %2, %2\n\tv_mul_f32 %1, %3, %3" : "=&v"(q0), "=&v"(q1) : "v"(d0), "v"(d1));
+                const float q = pwb_row16_sum(q0 + q1);
+                if ((l31 & 15) == 0)
+                    reinterpret_cast<float4*>(p.stats)[((size_t)b * p.Cout + co) * slots + 2 * px_t + (l31 >> 4)] = make_float4(32.0f, s1, q, 0.0f);
+            }
+        }
+    }
+}
+
+// staged K-split form (LDS: pwbsk_lds_bytes, conv_plan.h); the rider's jobs go one per wave of ITS workgroup
+static int launch_pwbsk(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s, const GnFinJob* rider) {
+    p.n_co_items = p.Cout / 64;
+    p.n_px = p.HW / 64;
+    const int nwaves = PWB_WAVES * p.n_co_items;
+    const int64_t nwg = (int64_t)p.B * p.n_px;
+    p.n_rider_wg = rider ? cdiv(rider->n_jobs, nwaves) : 0;
+    SISIC_REQUIRE(nwg > 0 && nwg + p.n_rider_wg < (int64_t(1) << 31), "conv2d(pointwise bf16x3, staged K-split): grid too large");
+    p.nwg = (int)nwg;
+    p.nitems = p.nwg * p.n_co_items;
+    const size_t lds = pwbsk_lds_bytes(Cin, p.Cout);
+    static std::atomic<uint64_t> opt{0};
+    auto kern = conv_pwbsk_kernel;
+    SISIC_TRY(ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kern), (int)PWBSK_MAX_LDS, opt));
+    hipLaunchKernelGGL(kern, dim3(p.n_rider_wg + p.nwg), dim3(64 * nwaves), lds, s, p);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
 }
 
 template <int PRO>
@@ -820,7 +1052,7 @@ static int launch_pwb(sisic_ctx* ctx, PwbParams& p, int Cin, hipStream_t s) {
 }
 
 // plan.form: which of the kernel's forms (conv_plan.cpp); rider: jobs this launch runs as extra workgroups, or NULL -- the plan
-// offers them only to the PRO == 0 instances of the two four-wave kernels (their workgroup is gn_finalize_kernel's: one job per wave)
+// offers them only to the PRO == 0 instances of the two four-wave kernels and to the staged K-split form (one job per wave each)
 int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s, const GnFinJob* rider) {
     PwbParams p{};
     const int Cin = a.c0 + a.c1;
@@ -836,6 +1068,8 @@ int launch_conv_pointwise_bf3(sisic_ctx* ctx, const sisic_conv_args& a, const Co
     static_assert(PWB_WAVES == GNF_WAVES, "a rider workgroup runs one finalisation job per wave");
     if (rider) { p.rider = *rider; p.n_rider_wg = cdiv(rider->n_jobs, GNF_WAVES); }
     switch (plan.form) {
+        case PWB_FORM_STAGED_KSPLIT:          // (no prologue, no relu: the plan)
+            return launch_pwbsk(ctx, p, Cin, s, rider);
         case PWB_FORM_KSPLIT:
             return pro == 2 ? launch_pwbk<2>(ctx, p, Cin, s) : pro == 1 ? launch_pwbk<1>(ctx, p, Cin, s) : launch_pwbk<0>(ctx, p, Cin, s);
         case PWB_FORM_STAGED:

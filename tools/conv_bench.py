@@ -43,6 +43,8 @@ LAYERS = [
     ("1x1 qkv 256->768 @16 gn", 5, 256, 0, 768, 16, 1, 1, 0, 2, 0),
     ("1x1 out 256->256 @16 res", 5, 256, 0, 256, 16, 1, 1, 0, 0, 1),
     ("1x1 sc 256+256->256 @16", 2, 256, 256, 256, 16, 1, 1, 0, 0, 0),
+    ("1x1 sc 256+128->256 @16", 1, 256, 128, 256, 16, 1, 1, 0, 0, 0),
+    ("1x1 sc 128->256 @16", 1, 128, 0, 256, 16, 1, 1, 0, 0, 0),
     ("1x1 sc 256+128->128 @32", 1, 256, 128, 128, 32, 1, 1, 0, 0, 0),
     ("1x1 sc 128+64->64 @64", 1, 128, 64, 64, 64, 1, 1, 0, 0, 0),
     ("1x1 sc 256+256->256 @8", 3, 256, 256, 256, 8, 1, 1, 0, 0, 0),
