@@ -619,7 +619,8 @@ int64_t sisic_unet_train_steps(const sisic_unet*);
  * its output, dw = OIHW [Cout, c0+c1, k, k].  Its K-split scratch is allocated per call.
  * Synchronises the stream: the scratch is freed before the call returns.                                               */
 int sisic_conv2d_wgrad(sisic_ctx*, const sisic_conv_args* fwd_args, const float* dy, float* dw, void* stream);
-/* attention backward: dqkv [B,3C,N] from qkv, the forward output o [B,C,N] and its gradient dO.                         */
+/* attention backward: dqkv [B,3C,N] from qkv, the forward output o [B,C,N] and its gradient dO.  (o must be a valid
+ * pointer but is not read: D_i = dO_i . o_i is formed from the recomputed probabilities)          */
 int sisic_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                         int head_dim, void* stream);
 /* GroupNorm(+SiLU) backward: a = act(GroupNorm(x)); given da, ADDS dx to dx_accum and writes dgamma, dbeta.

@@ -877,18 +877,23 @@ int launch_dropout_bwd(sisic_ctx* ctx, float* d, int B, int C, int HW, uint64_t 
 }
 
 // ================================================================ attention backward ================================
-// One workgroup per (sample, head), d = 8.  q,k,v,dO of the head in LDS ([N][8] rows).  Softmax is recomputed:
-//   pass A (thread = query i):  m_i, l_i (online), D_i = dO_i . O_i,  dQ_i = scale * sum_j P_ij (dO_i . v_j - D_i) k_j
-//   pass B (thread = key j):    dV_j = sum_i P_ij dO_i,  dK_j = scale * sum_i P_ij (dO_i . v_j - D_i) q_i
-// P_ij = exp(scale q_i . k_j - m_i) / l_i.  No atomics: every output row has one owner.  exp = v_exp_f32 (__expf), as in the
+// One workgroup per (sample, head), d = 8.  q * scale, k, v, dO of the head in LDS ([N][8] rows).  Softmax is recomputed:
+//   pass A (thread = query i):  m_i, l_i, D_i = sum_j P_ij (dO_i . v_j) (online),  dQ_i = scale * sum_j P_ij (dO_i . v_j - D_i) k_j
+//   pass B (thread = key j):    dV_j = sum_i P_ij dO_i,  dK_j = sum_i P_ij (dO_i . v_j - D_i) (scale q_i)
+// P_ij = exp(s_ij - m_i) / l_i.  No atomics: every output row has one owner.  exp = v_exp_f32 (__expf), as in the
 // forward kernel: the accurate expf is ~15 vector instructions of the ~40 per (query, key) pair and pass.
+// ONE definition of the score: s_ij = sum_d (scale q_id) k_jd, the scaled query staged once, the same fma chain in both
+// passes -- pass B's exp(s_ij - m_i) / l_i is normalised by the very scores that produced m_i and l_i (with q (scale k) there
+// the two roundings differ by a few ulps of |s|, 1e-5 at |s| = 150, and P_ij with them).  D_i comes from the pass's own P_ij,
+// not from dO_i . O_i with the forward kernel's O: sum_j P_ij (dO_i . v_j - D_i) then vanishes to rounding, which is what
+// keeps a saturated row's dQ at zero under keys of large norm.  `o` is not read.
 constexpr int ATB_THREADS = 256;
 
 __global__ void __launch_bounds__(ATB_THREADS)
 attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o, const float* __restrict__ dO,
                      float* __restrict__ dqkv, int C, int N, float scale) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const qs = smem;                 // [N][8]
+    float* const qs = smem;                 // [N][8], q * scale
     float* const ks_ = qs + (size_t)N * 8;
     float* const vs = ks_ + (size_t)N * 8;
     float* const gs = vs + (size_t)N * 8;   // dO
@@ -901,7 +906,7 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
     const size_t ooff = ((size_t)b * C + h * 8) * N;
     for (int i = threadIdx.x; i < 8 * N; i += ATB_THREADS) {
         const int d = i / N, n = i % N;                       // global reads run along n (contiguous)
-        qs[n * 8 + d] = qkv[qoff + (size_t)d * N + n];
+        qs[n * 8 + d] = qkv[qoff + (size_t)d * N + n] * scale;
         ks_[n * 8 + d] = qkv[koff + (size_t)d * N + n];
         vs[n * 8 + d] = qkv[voff + (size_t)d * N + n];
         gs[n * 8 + d] = dO[ooff + (size_t)d * N + n];
@@ -911,20 +916,24 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
     for (int i = threadIdx.x; i < N; i += ATB_THREADS) {
         float q[8], g[8];
 #pragma unroll
-        for (int d = 0; d < 8; ++d) { q[d] = qs[i * 8 + d] * scale; g[d] = gs[i * 8 + d]; }
-        float m = -INFINITY, l = 0.0f;
+        for (int d = 0; d < 8; ++d) { q[d] = qs[i * 8 + d]; g[d] = gs[i * 8 + d]; }
+        // l = sum_j exp(s_ij - m), a = sum_j exp(s_ij - m) (dO_i . v_j), both rescaled when m grows.  Accumulated in double:
+        // a sequential fp32 sum of 1000 terms is good to ~2e-6, the row's dS then sums to D_i * 2e-6 instead of 0, and a key
+        // of large norm carries that into dQ_i (1.1e-5 of the largest dQ at N = 1024 under |s| = 125; 1.5e-6 with these two)
+        float m = -INFINITY;
+        double l = 0.0, a = 0.0;
         for (int j = 0; j < N; ++j) {
-            float sc = 0.0f;
+            float sc = 0.0f, dp = 0.0f;
 #pragma unroll
-            for (int d = 0; d < 8; ++d) sc += q[d] * ks_[j * 8 + d];
+            for (int d = 0; d < 8; ++d) { sc += q[d] * ks_[j * 8 + d]; dp += g[d] * vs[j * 8 + d]; }
             const float mn = fmaxf(m, sc);
-            l = l * __expf(m - mn) + __expf(sc - mn);
+            const float r = __expf(m - mn), e = __expf(sc - mn);
+            l = l * (double)r + (double)e;
+            a = a * (double)r + (double)(e * dp);
             m = mn;
         }
-        float D = 0.0f;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) D += g[d] * o[ooff + (size_t)d * N + i];
-        const float il = 1.0f / l;
+        const float il = (float)(1.0 / l);
+        const float D = (float)(a / l);
         float dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int j = 0; j < N; ++j) {
             float sc = 0.0f, dp = 0.0f;
@@ -943,7 +952,7 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
     for (int j = threadIdx.x; j < N; j += ATB_THREADS) {
         float k[8], v[8];
 #pragma unroll
-        for (int d = 0; d < 8; ++d) { k[d] = ks_[j * 8 + d] * scale; v[d] = vs[j * 8 + d]; }
+        for (int d = 0; d < 8; ++d) { k[d] = ks_[j * 8 + d]; v[d] = vs[j * 8 + d]; }
         float dk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < N; ++i) {
             float sc = 0.0f, dp = 0.0f;
@@ -956,7 +965,7 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
         }
 #pragma unroll
         for (int d = 0; d < 8; ++d) {
-            dqkv[koff + (size_t)d * N + j] = dk[d] * scale;
+            dqkv[koff + (size_t)d * N + j] = dk[d];              // qs carries the scale
             dqkv[voff + (size_t)d * N + j] = dv[d];
         }
     }
