@@ -216,6 +216,34 @@ int sisic_ddpm_step(sisic_ctx*, const float* eps, const float* x, const float* z
 #define SISIC_RULE_ROW_WIDTH(rule) ((rule) == SISIC_RULE_DPMPP ? 6 : 5)
 #define SISIC_RULE_FLAG_CLIPPED_OUTPUT 1
 
+/* ---- prediction type: what a model's output means ("the step contract per type") ---------------------
+ * Every step rule starts from the model's estimate of x0.  Let o be the model's output (under guidance o_u + w * (o_c - o_u),
+ * formed as ever), sb = sqrt_beta_prod, sa = sqrt_alpha_prod.  x0 before the clamp, one fp32 rounding per operation, no FMA:
+ *   SISIC_PRED_EPSILON   x0 = (x - sb*o)/sa      the model predicts the noise (the default; the bits the library always gave)
+ *   SISIC_PRED_SAMPLE    x0 = o                  the model predicts x0
+ *   SISIC_PRED_V         x0 = sa*x - sb*o        the model predicts v = sa*eps - sb*x0 (Salimans & Ho 2022); no division, so
+ *                                                nothing is amplified where sa is small (the first steps of a cosine schedule)
+ * The clamp follows as documented at each rule.  DDPM and DPM-Solver++ change in this line only (hist stays the clamped x0).
+ * DDIM's direction term pe: EPSILON o; SAMPLE (x - sa*x0)/sb with the UNCLAMPED x0 (needs sb != 0); V sa*o + sb*x; and with
+ * use_clipped_model_output pe = (x - sa*x0_clamped)/sb under every type.  Noise, the edit epilogue and the guided write to
+ * both halves are untouched.  sa == 0 (a zero-terminal-SNR table) stays refused under every type.
+ *
+ * Two owners, both set through stream-less setters (the kernels run on the stream the existing entry points receive):
+ *   the CONTEXT's type says what the `eps` argument of the nine single-step entries means -- sisic_{ddpm,ddim,dpmpp}_step, their
+ *     _rng and their _edit forms -- read when the entry is called.  UNet handles never read it.
+ *   the HANDLE's type says what the UNet's output means: read by every sisic_sample* loop of the handle (plain, _rule, _rng,
+ *     _cond, _edit; eager and graph-replayed) and by sisic_unet_train_step, _ext and _cond (the regression target below).  In
+ *     graph mode the type is part of what a captured step is, like the rule and its flags: alternating types on one handle
+ *     re-captures (sisic_unet_graph_builds), and a call under a type returns the bits it returned before the alternation.
+ *     sisic_unet_forward* is unaffected: the network does not know what its output means.  A caller's rule_flags still accepts
+ *     SISIC_RULE_FLAG_CLIPPED_OUTPUT only.
+ * A type outside 0..2 is SISIC_EINVAL and leaves the setting as it was.                                                   */
+#define SISIC_PRED_EPSILON 0
+#define SISIC_PRED_SAMPLE  1      /* the model predicts x0 */
+#define SISIC_PRED_V       2      /* v = sqrt(abar) * eps - sqrt(1 - abar) * x0 */
+int sisic_set_step_prediction_type(sisic_ctx*, int type);      /* default EPSILON */
+int sisic_step_prediction_type(const sisic_ctx*);
+
 /* Fused DDIMScheduler.step (the published rule for epsilon prediction), elementwise over n floats.
  * With abar_t = alphas_cumprod[t], abar_prev = alphas_cumprod[prev_t] (or the final alpha when prev_t < 0),
  * variance = ((1 - abar_prev) / (1 - abar_t)) * (1 - abar_t / abar_prev) and sigma = eta * variance^0.5, the row is
@@ -528,6 +556,22 @@ int sisic_unet_train_forward_cond(sisic_unet*, const float* sample, const int64_
  * (the launches of a handle that never had it).  dropout_next_call: the counter value the next tape-recording forward uses. */
 int sisic_unet_set_dropout(sisic_unet*, float p, uint64_t seed, uint32_t first_call);
 uint32_t sisic_unet_dropout_next_call(const sisic_unet*);
+/* ---- training objective ------------------------------------------------------------------------------
+ * sisic_unet_set_prediction_type (default SISIC_PRED_EPSILON): besides the sampling loops (above), the regression target of
+ * sisic_unet_train_step, _ext and _cond: EPSILON the noise; SAMPLE the images; V  t = sa_b*noise - sb_b*x0 (two products, one
+ * difference, fp32, no FMA) formed in the loss kernel's registers from the two coefficient rows the step already takes -- no
+ * target tensor is written.  sisic_add_noise(x0 := noise, noise := x0, a = sa, c = -sb) gives the same bits as a tensor
+ * (DDPMScheduler.get_velocity), so a step spelled out of the single entry points equals the fused one bit for bit.
+ * sisic_unet_set_loss_weights: B per-sample weights (HOST fp32, finite; copied and kept until replaced or cleared by NULL or
+ * B == 0), e.g. Min-SNR-gamma.  While set, with c = grad_scale * 2 / n:
+ *     dpred = (c * w_b) * d,     loss = (sum of w_b * d^2) / n,     d = pred - target
+ * in sisic_mse_loss (n % B must be 0, else SISIC_EINVAL) and in the train_step entries (their B must equal the weights' B, else
+ * SISIC_EINVAL before anything is launched: a stale table is an error, never a silent loss).  Same fixed-order reduction; the
+ * weights reach the device through the handle's upload ring on the consuming call's stream.  Weights of all ones give the
+ * loss and dpred bits of no weights.                                                                                     */
+int sisic_unet_set_prediction_type(sisic_unet*, int type);     /* default EPSILON; anything else SISIC_EINVAL, setting unchanged */
+int sisic_unet_prediction_type(const sisic_unet*);
+int sisic_unet_set_loss_weights(sisic_unet*, const float* weights_host, int B);   /* NULL / 0 clears */
 /* F.mse_loss(pred, target) (train_diffusion.py:219): loss_dev[0] = mean((pred - target)^2) (NULL: kept internally),
  * dpred = grad_scale * 2 (pred - target) / n (NULL: loss only).  Fixed-order reduction.                               */
 int sisic_mse_loss(sisic_unet*, const float* pred, const float* target, int64_t n, float grad_scale, float* loss_dev,

@@ -29,6 +29,20 @@ RULE_DPMPP = 2
 RULE_FLAG_CLIPPED_OUTPUT = 1
 RULE_ROW_WIDTH = {RULE_DDPM: 5, RULE_DDIM: 5, RULE_DPMPP: 6}      # SISIC_RULE_ROW_WIDTH
 
+# what a model's output means (SISIC_PRED_*), under the names diffusers gives the three types
+PRED_EPSILON = 0
+PRED_SAMPLE = 1
+PRED_V = 2
+PREDICTION_TYPES = {"epsilon": PRED_EPSILON, "sample": PRED_SAMPLE, "v_prediction": PRED_V}
+
+
+def prediction_code(prediction_type: str) -> int:
+    """SISIC_PRED_* of a diffusers ``prediction_type`` string; anything else is NotImplementedError."""
+    try:
+        return PREDICTION_TYPES[prediction_type]
+    except (KeyError, TypeError):
+        raise NotImplementedError(f"prediction_type {prediction_type!r}: one of {sorted(PREDICTION_TYPES)}") from None
+
 c_float_p = C.POINTER(C.c_float)
 c_int64_p = C.POINTER(C.c_int64)
 
@@ -195,6 +209,11 @@ SIGNATURES = {
                                                 C.c_int, C.c_void_p]),
     "sisic_unet_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint32]),
     "sisic_unet_dropout_next_call": (C.c_uint32, [C.c_void_p]),
+    "sisic_unet_set_prediction_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sisic_unet_prediction_type": (C.c_int, [C.c_void_p]),
+    "sisic_unet_set_loss_weights": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
+    "sisic_set_step_prediction_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sisic_step_prediction_type": (C.c_int, [C.c_void_p]),
     "sisic_mse_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "sisic_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

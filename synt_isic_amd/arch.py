@@ -18,6 +18,7 @@ from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
+PREDICTION_TYPES = ("epsilon", "sample", "v_prediction")      # diffusers' names; _lib.PREDICTION_TYPES numbers them
 
 @dataclass(frozen=True)
 class UNetConfig:
@@ -34,6 +35,8 @@ class UNetConfig:
     class_embed_type: None = None
     num_class_embeds: Optional[int] = None      # N: class_embedding = nn.Embedding(N, time_embed_dim); None: unconditional
     dropout: float = 0.0                        # ResnetBlock2D dropout, training-mode forwards only; adds no tensors
+    prediction_type: str = "epsilon"            # what the output means: "epsilon", "sample" (x0) or "v_prediction"; adds no
+                                                # tensors, does not enter the state dict, never changes the forward pass
 
     @property
     def time_embed_dim(self) -> int:
@@ -66,6 +69,8 @@ class UNetConfig:
         p = self.dropout
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not 0.0 <= p < 1.0:
             raise ValueError(f"dropout must be a finite number in [0, 1), got {p!r}")
+        if self.prediction_type not in PREDICTION_TYPES:
+            raise NotImplementedError(f"prediction_type {self.prediction_type!r}: one of {PREDICTION_TYPES}")
 
 
 @dataclass

@@ -203,16 +203,18 @@ int sisic_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
                     float sqrt_beta_prod, float sqrt_alpha_prod, float c0, float c1, float sigma, float clip,
                     void* stream) {
     SISIC_REQUIRE(ctx, "ddpm_step: null context");
-    return launch_step(ctx, STEP_RULE_DDPM, 0, eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip,
-                       static_cast<hipStream_t>(stream));
+    // (what eps means is the context's: sisic_set_step_prediction_type, here and in the eight entries below)
+    return launch_step(ctx, STEP_RULE_DDPM, step_pred_flags(ctx->step_pred), eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod,
+                       c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_ddim_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n,
                     float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev, float c_dir, float sigma, float clip,
                     int use_clipped_model_output, void* stream) {
     SISIC_REQUIRE(ctx, "ddim_step: null context");
-    return launch_step(ctx, STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x, z, out, n,
-                       sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip, static_cast<hipStream_t>(stream));
+    const int flags = (use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0) | step_pred_flags(ctx->step_pred);
+    return launch_step(ctx, STEP_RULE_DDIM, flags, eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip,
+                       static_cast<hipStream_t>(stream));
 }
 
 int sisic_noise_fill(sisic_ctx* ctx, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
@@ -231,17 +233,17 @@ int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float*
                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
                         float c1, float sigma, float clip, void* stream) {
     SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddpm_step_rng: null context or empty batch");
-    return launch_step_rng(ctx, STEP_RULE_DDPM, 0, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step,
-                           sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
+    return launch_step_rng(ctx, STEP_RULE_DDPM, step_pred_flags(ctx->step_pred), eps, x, out, (int64_t)B * n_per_image, n_per_image,
+                           seeds_dev, step, sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_ddim_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
                         const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
                         float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream) {
     SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddim_step_rng: null context or empty batch");
-    return launch_step_rng(ctx, STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x, out,
-                           (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod, sqrt_alpha_prod, c_prev,
-                           c_dir, sigma, clip, static_cast<hipStream_t>(stream));
+    const int flags = (use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0) | step_pred_flags(ctx->step_pred);
+    return launch_step_rng(ctx, STEP_RULE_DDIM, flags, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step,
+                           sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
@@ -249,7 +251,7 @@ int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const flo
                      void* stream) {
     SISIC_REQUIRE(ctx, "dpmpp_step: null context");
     return launch_dpm_step(ctx, eps, x, z, hist, out, n, sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1, clip,
-                           static_cast<hipStream_t>(stream));
+                           static_cast<hipStream_t>(stream), step_pred_flags(ctx->step_pred));
 }
 
 int sisic_dpmpp_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int B,
@@ -257,7 +259,8 @@ int sisic_dpmpp_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float
                          float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip, void* stream) {
     SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "dpmpp_step_rng: null context or empty batch");
     return launch_dpm_step_rng(ctx, eps, x, hist, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod,
-                               sqrt_alpha_prod, cx, k0, sigma, k1, clip, static_cast<hipStream_t>(stream));
+                               sqrt_alpha_prod, cx, k0, sigma, k1, clip, static_cast<hipStream_t>(stream),
+                               step_pred_flags(ctx->step_pred));
 }
 
 // the single edited steps: the _rng entries' arguments, the known image, the mask and the edit row
@@ -269,9 +272,9 @@ static int step_edit(sisic_ctx* ctx, const char* what, int rule, int flags, cons
     SISIC_REQUIRE(Cn > 0 && HW > 0 && (int64_t)Cn * HW == n_per_image, "%s: C = %d, HW = %lld for images of %lld elements", what,
                   Cn, (long long)HW, (long long)n_per_image);
     const float erow[4] = {ck, sk, ja, jb};
-    return launch_step_edit(ctx, rule, flags, eps, nullptr, 1.0f, nullptr, x, hist, out, (int64_t)B * n_per_image, n_per_image,
-                            HW, seeds_dev, step, row, erow, nullptr, nullptr, nullptr, x0k, mask, clip,
-                            static_cast<hipStream_t>(stream));
+    return launch_step_edit(ctx, rule, flags | step_pred_flags(ctx->step_pred), eps, nullptr, 1.0f, nullptr, x, hist, out,
+                            (int64_t)B * n_per_image, n_per_image, HW, seeds_dev, step, row, erow, nullptr, nullptr, nullptr, x0k,
+                            mask, clip, static_cast<hipStream_t>(stream));
 }
 
 int sisic_ddpm_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
@@ -300,6 +303,16 @@ int sisic_dpmpp_step_edit(sisic_ctx* ctx, const float* eps, const float* x, floa
     return step_edit(ctx, "dpmpp_step_edit", STEP_RULE_DPMPP, 0, eps, x, hist, out, B, n_per_image, seeds_dev, step, row, clip,
                      x0k, mask, C, HW, ck, sk, ja, jb, stream);
 }
+
+int sisic_set_step_prediction_type(sisic_ctx* ctx, int type) {
+    SISIC_REQUIRE(ctx, "set_step_prediction_type: null context");
+    SISIC_REQUIRE(type == SISIC_PRED_EPSILON || type == SISIC_PRED_SAMPLE || type == SISIC_PRED_V,
+                  "set_step_prediction_type: type %d (0 = epsilon, 1 = sample, 2 = v)", type);
+    ctx->step_pred = type;
+    return SISIC_OK;
+}
+
+int sisic_step_prediction_type(const sisic_ctx* ctx) { return ctx ? ctx->step_pred : SISIC_PRED_EPSILON; }
 
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {
     SISIC_REQUIRE(ctx, "denorm_u8: null context");

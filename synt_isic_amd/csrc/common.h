@@ -63,6 +63,7 @@ struct PendingEvent {
 struct sisic_ctx {
     int device = 0;
     int num_cus = 0;
+    int step_pred = 0;              // sisic_set_step_prediction_type: what the single-step entries' eps argument means
     bool profiling = false;
     sisic::ProfileSlot prof[sisic::PK_COUNT];
     std::vector<sisic::PendingEvent> pending;
@@ -196,9 +197,17 @@ int launch_gn_stats(sisic_ctx*, const float* in0, int c0, const float* in1, int 
                     float* mean_rstd = nullptr);
 int launch_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s);
 // The scheduler-step rules of the sampling loop (elementwise.hip; sisic.h SISIC_RULE_*): the row of a step is
-// {sb, sa, c2, c3, sigma} with (c2, c3) = DDPM (c0, c1) or DDIM (c_prev, c_dir).  flags: STEP_FLAG_CLIPPED_OUTPUT (DDIM only).
+// {sb, sa, c2, c3, sigma} with (c2, c3) = DDPM (c0, c1) or DDIM (c_prev, c_dir).  flags: STEP_FLAG_CLIPPED_OUTPUT (DDIM only),
+// and under every rule the prediction type in its private bits (below).
 enum StepRule { STEP_RULE_DDPM = SISIC_RULE_DDPM, STEP_RULE_DDIM = SISIC_RULE_DDIM, STEP_RULE_DPMPP = SISIC_RULE_DPMPP };
 enum StepFlag { STEP_FLAG_CLIPPED_OUTPUT = SISIC_RULE_FLAG_CLIPPED_OUTPUT };
+// What the model's output means (sisic.h SISIC_PRED_*) travels in private bits of `flags`, beside the rule's own: the launchers
+// and the captured step's key (LoopKey::rule_flags) carry it without a parameter of their own.  A caller's rule_flags never has
+// these bits (the public entry points refuse them and add the handle's or the context's type).
+constexpr int STEP_FLAG_PRED_SHIFT = 8;
+constexpr int STEP_FLAG_PRED_MASK = 3 << STEP_FLAG_PRED_SHIFT;
+inline int step_pred(int flags) { return (flags & STEP_FLAG_PRED_MASK) >> STEP_FLAG_PRED_SHIFT; }
+inline int step_pred_flags(int type) { return type << STEP_FLAG_PRED_SHIFT; }
 // a known rule, flags it has, sa != 0, and sb != 0 where the rule divides by it
 int check_step_row(int rule, int flags, float sb, float sa);
 int launch_step(sisic_ctx*, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
@@ -218,15 +227,17 @@ int launch_step_indexed_rng(sisic_ctx*, int rule, int flags, const float* eps, f
                             const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
 // the DPM-Solver++(2M) rule (STEP_RULE_DPMPP): rows of six floats {sb, sa, cx, k0, sigma, k1} and one more stream, the
 // history hist [n] (the previous step's x0: written on every step, read when k1 != 0).  The launchers above refuse this rule.
+// flags: the prediction type's bits only (the rule has no flags of its own).
 int launch_dpm_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
-                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s);
+                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s, int flags = 0);
 int launch_dpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* hist, float* out, int64_t n,
                         int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
-                        float sigma, float k1, float clip, hipStream_t s);
+                        float sigma, float k1, float clip, hipStream_t s, int flags = 0);
 int launch_dpm_step_indexed(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, const void* state,
-                            const float* coef, const int* zrow, float clip, hipStream_t s);
+                            const float* coef, const int* zrow, float clip, hipStream_t s, int flags = 0);
 int launch_dpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
-                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
+                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s,
+                                int flags = 0);
 // classifier-free guidance (elementwise.hip): the same rules on eps = eps_u + w * (eps_c - eps_u), formed in the step kernel; the
 // new x goes to both halves of out [2n].  seeds_dev NULL: z is a buffer (or NULL); else generated noise.  row: the rule's host
 // row (SISIC_RULE_ROW_WIDTH floats).  hist: DPM-Solver++ only.  The indexed form reads w from cond[0] (LoopCond).

@@ -3,6 +3,7 @@
 //   * ddim_step_kernel  : fused DDIMScheduler.step (epsilon prediction), bit-exact vs torch CPU
 //   * dpm_step_kernel   : fused DPM-Solver++(2M) step with its one-step history, bit-exact vs torch CPU
 //   * step_edit_kernel  : the three steps with the inpainting epilogue (RePaint) applied before the store
+//     (every step kernel under each prediction type -- epsilon, sample, v: sisic.h SISIC_PRED_*, a template parameter of the rule)
 //   * denorm_u8_kernel  : clamp((x+1)/2,0,1)*255 -> uint8 HWC (image_generator.py:441-447)
 //   * temb_mlp_kernel   : sinusoidal timestep embedding -> Linear -> SiLU -> Linear -> SiLU
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
@@ -17,10 +18,26 @@ namespace sisic {
 // One IEEE rounding per operation and NO FMA contraction (this file is built with
 // -ffp-contract=off, and the pragma pins it locally): that is what the reference's sequence of
 // separate torch ops produces, so the step is bit-exact against torch on the CPU.
+//
+// P, the prediction type (sisic.h SISIC_PRED_*): what the model's output e means, and so how a rule gets its x0 from it.  A
+// template parameter of every rule, like the rule itself: no element branches on it, and P = PRED_EPS is the code these
+// kernels always were.
+constexpr int PRED_EPS = SISIC_PRED_EPSILON, PRED_SAMPLE = SISIC_PRED_SAMPLE, PRED_V = SISIC_PRED_V;
+
+// x0 before the clamp: epsilon (x - sb*e)/sa; sample e; v (= sa*eps - sb*x0) sa*x - sb*e, with no division
+template <int P>
+__device__ __forceinline__ float pred_x0(float e, float x, float sb, float sa) {
+#pragma clang fp contract(off)
+    if constexpr (P == PRED_SAMPLE) return e;
+    else if constexpr (P == PRED_V) return sa * x - sb * e;
+    else return (x - sb * e) / sa;
+}
+
+template <int P>
 __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, float sa, float c0, float c1,
                                           float sigma, float clip, bool noise) {
 #pragma clang fp contract(off)
-    float x0 = (x - sb * e) / sa;
+    float x0 = pred_x0<P>(e, x, sb, sa);
     if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
     float r = c0 * x0 + c1 * x;
     if (noise) r = r + sigma * z;
@@ -31,14 +48,18 @@ __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, f
 // The published DDIMScheduler.step for epsilon prediction, under the same rounding rules as ddpm_one.  The row of a step is
 // {sb = (1-abar_t)^.5, sa = abar_t^.5, c_prev = abar_prev^.5, c_dir = (1 - abar_prev - sigma^2)^.5, sigma = eta * variance^.5}.
 // CLIPPED (use_clipped_model_output): the direction term uses the epsilon re-derived from the clamped x0.
-template <bool CLIPPED>
+// The direction term's epsilon under the other types: sample (x - sa*x0)/sb with the UNCLAMPED x0; v sa*e + sb*x.
+template <bool CLIPPED, int P>
 __device__ __forceinline__ float ddim_one(float e, float x, float z, float sb, float sa, float c_prev, float c_dir,
                                           float sigma, float clip, bool noise) {
 #pragma clang fp contract(off)
-    float x0 = (x - sb * e) / sa;
+    const float x0u = pred_x0<P>(e, x, sb, sa);
+    float x0 = x0u;
     if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
     float pe = e;
     if constexpr (CLIPPED) pe = (x - sa * x0) / sb;
+    else if constexpr (P == PRED_SAMPLE) pe = (x - sa * x0u) / sb;
+    else if constexpr (P == PRED_V) pe = sa * e + sb * x;
     float r = c_prev * x0 + c_dir * pe;
     if (noise) r = r + sigma * z;
     return r;
@@ -46,18 +67,19 @@ __device__ __forceinline__ float ddim_one(float e, float x, float z, float sb, f
 
 // The step rule as a functor: the row of five scalars and the clip range, applied to one element.  step_body is instantiated
 // once per rule and noise source, so no element pays for a branch on the rule.
+template <int P = PRED_EPS>
 struct DdpmRule {
     float sb, sa, c0, c1, sigma, clip;
     __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
-        return ddpm_one(e, x, z, sb, sa, c0, c1, sigma, clip, noise);
+        return ddpm_one<P>(e, x, z, sb, sa, c0, c1, sigma, clip, noise);
     }
 };
 
-template <bool CLIPPED>
+template <bool CLIPPED, int P = PRED_EPS>
 struct DdimRule {
     float sb, sa, c_prev, c_dir, sigma, clip;
     __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
-        return ddim_one<CLIPPED>(e, x, z, sb, sa, c_prev, c_dir, sigma, clip, noise);
+        return ddim_one<CLIPPED, P>(e, x, z, sb, sa, c_prev, c_dir, sigma, clip, noise);
     }
 };
 
@@ -213,37 +235,39 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
     }
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
                  float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
                  int vec4) {
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdpmRule{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdpmRule<P>{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
 }
 
 // the same step with z generated in the kernel (sisic_sample_frames_rng, eager form)
+template <int P>
 __global__ void __launch_bounds__(256)
 ddpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
                      const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
                      float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule{sb, sa, c0, c1, sigma, clip}, zs);
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule<P>{sb, sa, c0, c1, sigma, clip}, zs);
 }
 
 // the DDIM rule in the same two forms
-template <bool CLIPPED>
+template <bool CLIPPED, int P>
 __global__ void __launch_bounds__(256)
 ddim_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* out, int64_t n, float sb,
                  float sa, float c_prev, float c_dir, float sigma, float clip, int vec4) {
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdimRule<CLIPPED, P>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
 }
 
-template <bool CLIPPED>
+template <bool CLIPPED, int P>
 __global__ void __launch_bounds__(256)
 ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
                      const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c_prev, float c_dir,
                      float sigma, float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
+    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED, P>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
 }
 
 // ---- DPM-Solver++(2M) step -------------------------------------------------------------
@@ -253,12 +277,13 @@ ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, 
 // under the rounding rules of ddpm_one.  hist is the previous step's x0: one more stream, read (second-order steps only) and
 // written in place by the thread that owns the element, so a captured step replays as it is.  A first-order step (k1 == 0,
 // uniform over the launch) does not read it: whatever an earlier run left there, NaN included, stays out of the result.
+template <int P = PRED_EPS>
 struct DpmRule {
     float sb, sa, cx, k0, sigma, k1, clip;
     // h: the history's element (any value when !second); m0: this step's x0, the next step's history
     __device__ __forceinline__ float operator()(float e, float x, float z, float h, bool noise, bool second, float& m0) const {
 #pragma clang fp contract(off)
-        float x0 = (x - sb * e) / sa;
+        float x0 = pred_x0<P>(e, x, sb, sa);
         if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
         float r = cx * x + k0 * x0;
         if (second) r = r + k1 * h;
@@ -269,9 +294,9 @@ struct DpmRule {
 };
 
 // step_body with the history stream.  out may alias x; hist aliases nothing else (and stays n wide under E::dup).
-template <class Z, class E, class D = NoEdit>
+template <class R, class Z, class E, class D = NoEdit>
 __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float* hist, float* out, int64_t n,
-                                              bool vec4, const DpmRule rule, const Z zs, const D ed = D{}) {
+                                              bool vec4, const R rule, const Z zs, const D ed = D{}) {
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const bool second = rule.k1 != 0.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -309,18 +334,20 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
     }
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 dpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* hist, float* out, int64_t n,
                 float sb, float sa, float cx, float k0, float sigma, float k1, float clip, int vec4) {
-    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0, DpmRule{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
+    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0, DpmRule<P>{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 dpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* hist, float* out, int64_t n, int64_t n_per_image,
                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float cx, float k0, float sigma,
                     float k1, float clip, int vec4) {
     const PhiloxNoise zs{seeds, n_per_image, step};
-    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule{sb, sa, cx, k0, sigma, k1, clip}, zs);
+    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule<P>{sb, sa, cx, k0, sigma, k1, clip}, zs);
 }
 
 static const char* rule_name(int rule) {
@@ -331,16 +358,30 @@ static const char* rule_name(int rule) {
 static int check_rule(int rule, int flags) {
     SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM || rule == STEP_RULE_DPMPP,
                   "step rule %d (0 = DDPM, 1 = DDIM, 2 = DPM-Solver++)", rule);
-    SISIC_REQUIRE((flags & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || flags == 0),
-                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM, DPM-Solver++: none)", rule_name(rule), flags);
+    // (the prediction type's private bits ride along: common.h STEP_FLAG_PRED_MASK)
+    const int own = flags & ~STEP_FLAG_PRED_MASK;
+    SISIC_REQUIRE((own & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || own == 0),
+                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM, DPM-Solver++: none)", rule_name(rule), own);
+    SISIC_REQUIRE(step_pred(flags) <= PRED_V, "%s: prediction type %d (0 = epsilon, 1 = sample, 2 = v)", rule_name(rule),
+                  step_pred(flags));
     return SISIC_OK;
 }
+
+// A launch under the prediction type that `flags` carries: the statements see it as the constant P.
+#define SISIC_PRED_SWITCH(flags, ...)                                                  \
+    switch (step_pred(flags)) {                                                        \
+        case PRED_SAMPLE: { constexpr int P = PRED_SAMPLE; __VA_ARGS__; } break;       \
+        case PRED_V: { constexpr int P = PRED_V; __VA_ARGS__; } break;                 \
+        default: { constexpr int P = PRED_EPS; __VA_ARGS__; } break;                   \
+    }
 
 int check_step_row(int rule, int flags, float sb, float sa) {
     SISIC_TRY(check_rule(rule, flags));
     SISIC_REQUIRE(sa != 0.0f, "%s: sqrt_alpha_prod is zero", rule_name(rule));
     SISIC_REQUIRE(!(flags & STEP_FLAG_CLIPPED_OUTPUT) || sb != 0.0f,
                   "%s: sqrt_beta_prod is zero with use_clipped_model_output", rule_name(rule));
+    SISIC_REQUIRE(!(rule == STEP_RULE_DDIM && step_pred(flags) == PRED_SAMPLE) || sb != 0.0f,
+                  "%s: sqrt_beta_prod is zero under sample prediction (the direction term divides by it)", rule_name(rule));
     return SISIC_OK;
 }
 
@@ -357,15 +398,16 @@ int launch_step(sisic_ctx* ctx, int rule, int flags, const float* eps, const flo
     const int vec4 = (al & 15) == 0;
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    if (rule == STEP_RULE_DDPM)
-        hipLaunchKernelGGL(ddpm_step_kernel, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma, clip,
-                           vec4);
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-        hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
-                           clip, vec4);
-    else
-        hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
-                           clip, vec4);
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DDPM)
+            hipLaunchKernelGGL(ddpm_step_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma, clip,
+                               vec4);
+        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+            hipLaunchKernelGGL((ddim_step_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
+                               clip, vec4);
+        else
+            hipLaunchKernelGGL((ddim_step_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
+                               clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -387,25 +429,26 @@ int launch_step_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, const
     const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    if (rule == STEP_RULE_DDPM)
-        hipLaunchKernelGGL(ddpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step, sb,
-                           sa, c2, c3, sigma, clip, vec4);
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-        hipLaunchKernelGGL(ddim_step_rng_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev,
-                           step, sb, sa, c2, c3, sigma, clip, vec4);
-    else
-        hipLaunchKernelGGL(ddim_step_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev,
-                           step, sb, sa, c2, c3, sigma, clip, vec4);
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DDPM)
+            hipLaunchKernelGGL(ddpm_step_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step,
+                               sb, sa, c2, c3, sigma, clip, vec4);
+        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+            hipLaunchKernelGGL((ddim_step_rng_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image,
+                               seeds_dev, step, sb, sa, c2, c3, sigma, clip, vec4);
+        else
+            hipLaunchKernelGGL((ddim_step_rng_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image,
+                               seeds_dev, step, sb, sa, c2, c3, sigma, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
 // the DPM-Solver++ step: launch_step / launch_step_rng with the history stream and the sixth scalar of its row
 int launch_dpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
-                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s) {
+                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s, int flags) {
     SISIC_REQUIRE(eps && x && hist && out && n > 0, "dpmpp_step: null tensor or empty");
     SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step: the history aliases another tensor");
-    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, 0, sb, sa));
+    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, flags, sb, sa));
     const bool noise = z != nullptr && sigma != 0.0f;
     ProfileScope prof(ctx, s, PK_DDPM, ((noise ? 20.0 : 16.0) + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) |
@@ -413,28 +456,28 @@ int launch_dpm_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
     const int vec4 = (al & 15) == 0;
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(dpm_step_kernel, dim3(blocks), dim3(256), 0, s, eps, x, z, hist, out, n, sb, sa, cx, k0, sigma, k1, clip,
-                       vec4);
+    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, z, hist, out, n, sb, sa,
+                                                cx, k0, sigma, k1, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
 int launch_dpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int64_t n,
                         int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
-                        float sigma, float k1, float clip, hipStream_t s) {
+                        float sigma, float k1, float clip, hipStream_t s, int flags) {
     SISIC_REQUIRE(eps && x && hist && out && seeds_dev && n > 0, "dpmpp_step_rng: null tensor or empty");
     SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step_rng: the history aliases another tensor");
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
                   "dpmpp_step_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
-    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, 0, sb, sa));
+    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, flags, sb, sa));
     ProfileScope prof(ctx, s, PK_DDPM, (16.0 + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist) |
                          reinterpret_cast<uintptr_t>(out);
     const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(dpm_step_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, out, n, n_per_image, seeds_dev, step, sb,
-                       sa, cx, k0, sigma, k1, clip, vec4);
+    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, out, n,
+                                                n_per_image, seeds_dev, step, sb, sa, cx, k0, sigma, k1, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -477,56 +520,61 @@ __device__ __forceinline__ void step_indexed_rng_body(const float* __restrict__ 
     step_body(PlainEps{eps}, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 ddpm_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
                          const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    step_indexed_body<DdpmRule>(eps, x, n, st, coef, zrow, clip, vec4);
+    step_indexed_body<DdpmRule<P>>(eps, x, n, st, coef, zrow, clip, vec4);
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 ddpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
                              const LoopState* __restrict__ st, const float* __restrict__ coef,
                              const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    step_indexed_rng_body<DdpmRule>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
+    step_indexed_rng_body<DdpmRule<P>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
 }
 
-template <bool CLIPPED>
+template <bool CLIPPED, int P>
 __global__ void __launch_bounds__(256)
 ddim_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
                          const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    step_indexed_body<DdimRule<CLIPPED>>(eps, x, n, st, coef, zrow, clip, vec4);
+    step_indexed_body<DdimRule<CLIPPED, P>>(eps, x, n, st, coef, zrow, clip, vec4);
 }
 
-template <bool CLIPPED>
+template <bool CLIPPED, int P>
 __global__ void __launch_bounds__(256)
 ddim_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
                              const LoopState* __restrict__ st, const float* __restrict__ coef,
                              const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    step_indexed_rng_body<DdimRule<CLIPPED>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
+    step_indexed_rng_body<DdimRule<CLIPPED, P>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
 }
 
 // the DPM-Solver++ rule: rows of six floats, and the history buffer of the loop
-__device__ __forceinline__ DpmRule loop_dpm_rule(const float* __restrict__ coef, int step, float clip) {
+template <int P>
+__device__ __forceinline__ DpmRule<P> loop_dpm_rule(const float* __restrict__ coef, int step, float clip) {
     const float* c = coef + 6 * step;
-    return DpmRule{c[0], c[1], c[2], c[3], c[4], c[5], clip};
+    return DpmRule<P>{c[0], c[1], c[2], c[3], c[4], c[5], clip};
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 dpm_step_indexed_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, const LoopState* __restrict__ st,
                         const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
     const int step = st->step;
     const int zr = zrow[step];
     const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
 }
 
+template <int P>
 __global__ void __launch_bounds__(256)
 dpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, int64_t n_per_image,
                             const LoopState* __restrict__ st, const float* __restrict__ coef,
                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
     const int step = st->step;
     const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
 }
 
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
@@ -561,12 +609,13 @@ int launch_step_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, f
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
     const LoopState* st = static_cast<const LoopState*>(state);
-    if (rule == STEP_RULE_DDPM)
-        hipLaunchKernelGGL(ddpm_step_indexed_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-        hipLaunchKernelGGL(ddim_step_indexed_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
-    else
-        hipLaunchKernelGGL(ddim_step_indexed_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DDPM)
+            hipLaunchKernelGGL(ddpm_step_indexed_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
+        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+            hipLaunchKernelGGL((ddim_step_indexed_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
+        else
+            hipLaunchKernelGGL((ddim_step_indexed_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -585,35 +634,39 @@ int launch_step_indexed_rng(sisic_ctx* ctx, int rule, int flags, const float* ep
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
     const LoopState* st = static_cast<const LoopState*>(state);
-    if (rule == STEP_RULE_DDPM)
-        hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
-                           seeds_dev, clip, vec4);
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-        hipLaunchKernelGGL(ddim_step_indexed_rng_kernel<true>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
-                           seeds_dev, clip, vec4);
-    else
-        hipLaunchKernelGGL(ddim_step_indexed_rng_kernel<false>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
-                           seeds_dev, clip, vec4);
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DDPM)
+            hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
+                               seeds_dev, clip, vec4);
+        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
+            hipLaunchKernelGGL((ddim_step_indexed_rng_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st,
+                               coef, seeds_dev, clip, vec4);
+        else
+            hipLaunchKernelGGL((ddim_step_indexed_rng_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st,
+                               coef, seeds_dev, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
 int launch_dpm_step_indexed(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, const void* state,
-                            const float* coef, const int* zrow, float clip, hipStream_t s) {
+                            const float* coef, const int* zrow, float clip, hipStream_t s, int flags) {
+    SISIC_TRY(check_rule(STEP_RULE_DPMPP, flags));
     SISIC_REQUIRE(eps && x && hist && state && coef && zrow && n > 0, "dpmpp_step_indexed: null argument");
     ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
     const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist);
     const int vec4 = (al & 15) == 0 && (n & 3) == 0;
     const int64_t work = vec4 ? (n + 3) / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(dpm_step_indexed_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
-                       static_cast<const LoopState*>(state), coef, zrow, clip, vec4);
+    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_indexed_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
+                                                static_cast<const LoopState*>(state), coef, zrow, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
 
 int launch_dpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
-                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
+                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s,
+                                int flags) {
+    SISIC_TRY(check_rule(STEP_RULE_DPMPP, flags));
     SISIC_REQUIRE(eps && x && hist && state && coef && seeds_dev && n > 0, "dpmpp_step_indexed_rng: null argument");
     SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
                   "dpmpp_step_indexed_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
@@ -622,8 +675,8 @@ int launch_dpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, floa
     const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
     const int64_t work = vec4 ? n / 4 : n;
     const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    hipLaunchKernelGGL(dpm_step_indexed_rng_kernel, dim3(blocks), dim3(256), 0, s, eps, x, hist, n, n_per_image,
-                       static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4);
+    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_indexed_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
+                                                n_per_image, static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4))
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -653,13 +706,13 @@ step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, f
     }
 }
 
-template <int NZ>
+template <int NZ, int P>
 __global__ void __launch_bounds__(256)
 dpm_step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float w, const float* x,
                        const float* __restrict__ z, const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step,
                        float* hist, float* out, int64_t n, StepRow row, float clip, int vec4) {
     const GuidedEps es{ec, eu, w};
-    const DpmRule rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
+    const DpmRule<P> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
     if constexpr (NZ == 0) {
         dpm_step_body(es, x, hist, out, n, vec4 != 0, rule, BufferNoise{z});
     } else {
@@ -685,7 +738,7 @@ step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, int64_t n,
     }
 }
 
-template <int NZ>
+template <int NZ, int P>
 __global__ void __launch_bounds__(256)
 dpm_step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, float* hist, int64_t n, int64_t n_per_image,
                                const LoopState* __restrict__ st, const float* __restrict__ coef, const int* __restrict__ zrow,
@@ -695,10 +748,10 @@ dpm_step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, float*
     if constexpr (NZ == 0) {
         const int zr = zrow[step];
         const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
     } else {
         const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule(coef, step, clip), zs);
+        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
     }
 }
 
@@ -723,16 +776,17 @@ int launch_step_guided(sisic_ctx* ctx, int rule, int flags, const float* eps_c, 
     const int64_t work = vec4 ? n / 4 : n;
     const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
 #define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, out, n, r, clip, vec4)
-    if (rule == STEP_RULE_DPMPP) {
-        if (seeds_dev) hipLaunchKernelGGL(dpm_step_guided_kernel<1>, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
-        else hipLaunchKernelGGL(dpm_step_guided_kernel<0>, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
-    } else if (rule == STEP_RULE_DDPM) {
-        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdpmRule, 1>)); else SISIC_GUIDED((step_guided_kernel<DdpmRule, 0>));
-    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<true>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<true>, 0>));
-    } else {
-        if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<false>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<false>, 0>));
-    }
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DPMPP) {
+            if (seeds_dev) hipLaunchKernelGGL((dpm_step_guided_kernel<1, P>), grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
+            else hipLaunchKernelGGL((dpm_step_guided_kernel<0, P>), grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
+        } else if (rule == STEP_RULE_DDPM) {
+            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdpmRule<P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdpmRule<P>, 0>));
+        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<true, P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<true, P>, 0>));
+        } else {
+            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<false, P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<false, P>, 0>));
+        })
 #undef SISIC_GUIDED
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
@@ -755,16 +809,17 @@ int launch_step_guided_indexed(sisic_ctx* ctx, int rule, int flags, const float*
     const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
     const LoopState* st = static_cast<const LoopState*>(state);
 #define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps2, x2, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4)
-    if (rule == STEP_RULE_DPMPP) {
-        if (seeds_dev) hipLaunchKernelGGL(dpm_step_guided_indexed_kernel<1>, grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
-        else hipLaunchKernelGGL(dpm_step_guided_indexed_kernel<0>, grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
-    } else if (rule == STEP_RULE_DDPM) {
-        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule, 0>));
-    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true>, 0>));
-    } else {
-        if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false>, 0>));
-    }
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DPMPP) {
+            if (seeds_dev) hipLaunchKernelGGL((dpm_step_guided_indexed_kernel<1, P>), grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
+            else hipLaunchKernelGGL((dpm_step_guided_indexed_kernel<0, P>), grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
+        } else if (rule == STEP_RULE_DDPM) {
+            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule<P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule<P>, 0>));
+        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true, P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true, P>, 0>));
+        } else {
+            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false, P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false, P>, 0>));
+        })
 #undef SISIC_GUIDED
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
@@ -821,14 +876,14 @@ step_edit_kernel(const EditStepArgs a) {
     else step_body(PlainEps{a.ec}, a.x, a.out, a.n, a.vec4 != 0, row_rule<R>(row, a.clip), zs, ed);
 }
 
-template <bool GUIDED>
+template <bool GUIDED, int P>
 __global__ void __launch_bounds__(256)
 dpm_step_edit_kernel(const EditStepArgs a) {
     StepRow row; float er[4], w; uint32_t step;
     edit_step_rows<6>(a, row, er, step, w);
     const PhiloxNoise zs{a.seeds, a.npi, step};
     const InpaintEdit ed{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
-    const DpmRule rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip};
+    const DpmRule<P> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip};
     if constexpr (GUIDED) dpm_step_body(GuidedEps{a.ec, a.eu, w}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
     else dpm_step_body(PlainEps{a.ec}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
 }
@@ -873,19 +928,22 @@ int launch_step_edit(sisic_ctx* ctx, int rule, int flags, const float* eps, cons
     const int64_t work = a.vec4 ? n / 4 : n;
     const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
 #define SISIC_EDIT(K) hipLaunchKernelGGL(K, grid, block, 0, s, a)
-    if (rule == STEP_RULE_DPMPP) {
-        if (eps_u) SISIC_EDIT(dpm_step_edit_kernel<true>); else SISIC_EDIT(dpm_step_edit_kernel<false>);
-    } else if (rule == STEP_RULE_DDPM) {
-        if (eps_u) SISIC_EDIT((step_edit_kernel<DdpmRule, true>)); else SISIC_EDIT((step_edit_kernel<DdpmRule, false>));
-    } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-        if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<true>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<true>, false>));
-    } else {
-        if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<false>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<false>, false>));
-    }
+    SISIC_PRED_SWITCH(flags,
+        if (rule == STEP_RULE_DPMPP) {
+            if (eps_u) SISIC_EDIT((dpm_step_edit_kernel<true, P>)); else SISIC_EDIT((dpm_step_edit_kernel<false, P>));
+        } else if (rule == STEP_RULE_DDPM) {
+            if (eps_u) SISIC_EDIT((step_edit_kernel<DdpmRule<P>, true>)); else SISIC_EDIT((step_edit_kernel<DdpmRule<P>, false>));
+        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
+            if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<true, P>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<true, P>, false>));
+        } else {
+            if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<false, P>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<false, P>, false>));
+        })
 #undef SISIC_EDIT
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
+
+#undef SISIC_PRED_SWITCH
 
 // the combine alone (sisic_guide_eps): guide_one() on every element, any alignment; out may be either input
 __global__ void __launch_bounds__(256)

@@ -381,6 +381,10 @@ int train_step_body(sisic_unet* u, const float* images, const float* noise, cons
     TrainState* tr = u->train.get();
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
+    // a table left from another batch size is an error, never a silently unweighted (or wrongly weighted) loss
+    const bool weighted = !u->loss_w.empty();
+    SISIC_REQUIRE(!weighted || (int)u->loss_w.size() == B,
+                  "train_step: %d loss weights are set, the batch is %d (sisic_unet_set_loss_weights)", (int)u->loss_w.size(), B);
     SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, 3 * n));     // noisy | prediction | d prediction
     float* noisy = u->eps_buf;
     float* pred = noisy + n;
@@ -394,7 +398,22 @@ int train_step_body(sisic_unet* u, const float* images, const float* noise, cons
     SISIC_TRY(unet_stage_upload(u, coef.data(), 2 * (size_t)B, tr->small, s));
     SISIC_TRY(launch_add_noise(u->ctx, images, noise, tr->small, tr->small + B, noisy, B, (size_t)C * H * W, s));
     SISIC_TRY(train_forward_impl(u, noisy, timesteps, class_labels, pred, B, H, W, stream));
-    SISIC_TRY(launch_mse(u->ctx, pred, noise, n, loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
+    // the objective: the target follows the handle's prediction type -- the noise, the image, or v formed
+    // in the loss kernel's registers from the two rows above (no target tensor) -- and the handle's loss weights apply
+    if (u->pred_type == SISIC_PRED_V || weighted) {
+        SISIC_TRY(unet_grow(&u->objective_dev, &u->objective_cap, 3 * (size_t)B));
+        std::vector<float> rows(coef);
+        if (weighted) rows.insert(rows.end(), u->loss_w.begin(), u->loss_w.end());
+        SISIC_TRY(unet_stage_upload(u, rows.data(), rows.size(), u->objective_dev, s));
+        const bool v = u->pred_type == SISIC_PRED_V;
+        const float* target = u->pred_type == SISIC_PRED_EPSILON ? noise : images;
+        SISIC_TRY(launch_mse_objective(u->ctx, pred, target, v ? noise : nullptr, v ? u->objective_dev : nullptr,
+                                       v ? u->objective_dev + B : nullptr, weighted ? u->objective_dev + 2 * (size_t)B : nullptr, B, n,
+                                       loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
+    } else {
+        SISIC_TRY(launch_mse(u->ctx, pred, u->pred_type == SISIC_PRED_SAMPLE ? images : noise, n, loss_scale, tr->loss_dev, dpred,
+                             tr->mse_part, 2048, s));
+    }
     SISIC_TRY(sisic_unet_backward(u, dpred, stream));
     if (loss_out) {
         SISIC_HIP(hipMemcpyAsync(loss_out, tr->loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
@@ -517,6 +536,19 @@ int sisic_unet_set_dropout(sisic_unet* u, float p, uint64_t seed, uint32_t first
 
 uint32_t sisic_unet_dropout_next_call(const sisic_unet* u) { return u ? u->drop_call : 0; }
 
+int sisic_unet_set_loss_weights(sisic_unet* u, const float* weights_host, int B) {
+    SISIC_REQUIRE(u, "set_loss_weights: null handle");
+    if (!weights_host || B == 0) {
+        u->loss_w.clear();
+        return SISIC_OK;
+    }
+    SISIC_REQUIRE(B > 0, "set_loss_weights: B = %d", B);
+    for (int b = 0; b < B; ++b)
+        SISIC_REQUIRE(std::isfinite(weights_host[b]), "set_loss_weights: weight %d is %g", b, (double)weights_host[b]);
+    u->loss_w.assign(weights_host, weights_host + B);
+    return SISIC_OK;
+}
+
 int sisic_unet_zero_grad(sisic_unet* u, void* stream) {
     SISIC_TRY(require_train(u, "zero_grad"));
     SISIC_HIP(hipMemsetAsync(u->train->grad, 0, u->raw_floats * sizeof(float), static_cast<hipStream_t>(stream)));
@@ -557,6 +589,16 @@ int sisic_unet_backward(sisic_unet* u, const float* dout, void* stream) {
 int sisic_mse_loss(sisic_unet* u, const float* pred, const float* target, int64_t n, float grad_scale, float* loss_dev,
                    float* dpred, void* stream) {
     SISIC_TRY(require_train(u, "mse_loss"));
+    if (!u->loss_w.empty()) {
+        const size_t B = u->loss_w.size();
+        SISIC_REQUIRE(pred && target && n > 0 && (size_t)n % B == 0,
+                      "mse_loss: %lld elements are not %d equal samples (sisic_unet_set_loss_weights)", (long long)n, (int)B);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        SISIC_TRY(unet_grow(&u->objective_dev, &u->objective_cap, 3 * B));
+        SISIC_TRY(unet_stage_upload(u, u->loss_w.data(), B, u->objective_dev, s));
+        return launch_mse_objective(u->ctx, pred, target, nullptr, nullptr, nullptr, u->objective_dev, (int)B, (size_t)n, grad_scale,
+                                    loss_dev ? loss_dev : u->train->loss_dev, dpred, u->train->mse_part, 2048, s);
+    }
     return launch_mse(u->ctx, pred, target, (size_t)n, grad_scale, loss_dev ? loss_dev : u->train->loss_dev, dpred,
                       u->train->mse_part, 2048, static_cast<hipStream_t>(stream));
 }

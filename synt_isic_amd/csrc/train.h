@@ -82,6 +82,11 @@ int launch_silu_fwd(sisic_ctx*, const float* pre, size_t n, float* out, hipStrea
 int launch_silu_bwd(sisic_ctx*, const float* dy, const float* pre, size_t n, float* out, hipStream_t s);
 int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, float grad_scale, float* loss_dev, float* dpred,
                float* part, int nparts, hipStream_t s);
+// launch_mse under another objective: the v target sa[b]*noise - sb[b]*target formed in the register (noise, sa, sb: all or none;
+// `target` is then x0), per-sample weights w (device [B], or NULL), or both; same grid and reduction as launch_mse
+int launch_mse_objective(sisic_ctx*, const float* pred, const float* target, const float* noise, const float* sa, const float* sb,
+                         const float* w, int B, size_t n, float grad_scale, float* loss_dev, float* dpred, float* part, int nparts,
+                         hipStream_t s);
 int launch_check_finite(sisic_ctx*, const float* g, size_t n, int* flag, hipStream_t s);
 int launch_adam(sisic_ctx*, float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps,
                 int64_t step, float inv_scale, hipStream_t s);

@@ -1116,6 +1116,65 @@ int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, flo
     return SISIC_OK;
 }
 
+// The same loss under another objective: the target formed in the register, per-sample weights, or both.
+//   V:  t = sa[b]*noise - sb[b]*x0 (v-prediction: two products, one difference, each rounded -- the bits sisic_add_noise gives for
+//       (x0 := noise, noise := x0, a = sa, c = -sb)); `target` is then x0 and no target tensor exists.  Otherwise t = target[i].
+//   W:  g_b = c * w[b], dpred = g_b * d, and the sum takes w[b] * d^2.
+// Grid, grid-stride, block_sum_256 and mse_final_kernel are those of mse_partial_kernel, and so is the accumulate: that kernel
+// compiles `s += d * d` to ONE fused multiply-add, so this one spells the instruction out, s = fma(w*d, d, s).  With w = 1 the
+// product w*d is d and c*w is c exactly: weights of all ones give the loss and dpred bits of mse_partial_kernel.
+template <bool V, bool W>
+__global__ void __launch_bounds__(256) mse_objective_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                            const float* __restrict__ noise, const float* __restrict__ sa,
+                                                            const float* __restrict__ sb, const float* __restrict__ w, size_t per,
+                                                            size_t n, float gscale, float* __restrict__ dpred,
+                                                            float* __restrict__ part) {
+#pragma clang fp contract(off)
+    __shared__ float red[4];
+    float s = 0.0f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t b = i / per;
+        float t = target[i];
+        if constexpr (V) {
+            const float t0 = sa[b] * noise[i];
+            const float t1 = sb[b] * t;
+            t = t0 - t1;
+        }
+        const float d = pred[i] - t;
+        if constexpr (W) {
+            const float wb = w[b];
+            const float g = gscale * wb;
+            s = __builtin_fmaf(wb * d, d, s);
+            if (dpred) dpred[i] = g * d;
+        } else {
+            s = __builtin_fmaf(d, d, s);
+            if (dpred) dpred[i] = gscale * d;
+        }
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// noise, sa, sb (device [B]): the v target, all three or none; w (device [B]) or NULL; per = n / B
+int launch_mse_objective(sisic_ctx*, const float* pred, const float* target, const float* noise, const float* sa, const float* sb,
+                         const float* w, int B, size_t n, float grad_scale, float* loss_dev, float* dpred, float* part, int nparts,
+                         hipStream_t s) {
+    SISIC_REQUIRE(pred && target && loss_dev && part && n > 0 && nparts > 0 && B > 0 && n % (size_t)B == 0, "mse: bad arguments");
+    SISIC_REQUIRE((noise != nullptr) == (sa != nullptr) && (noise != nullptr) == (sb != nullptr), "mse: the v target takes noise and both rows");
+    SISIC_REQUIRE(noise || w, "mse: neither a v target nor weights (launch_mse)");
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)nparts);
+    const size_t per = n / (size_t)B;
+    const float c = grad_scale * 2.0f / (float)n;
+#define SISIC_MSE_OBJ(V, W) hipLaunchKernelGGL((mse_objective_kernel<V, W>), dim3(blocks), dim3(256), 0, s, pred, target, noise, sa, sb, w, per, n, c, dpred, part)
+    if (noise && w) SISIC_MSE_OBJ(true, true);
+    else if (noise) SISIC_MSE_OBJ(true, false);
+    else SISIC_MSE_OBJ(false, true);
+#undef SISIC_MSE_OBJ
+    hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, part, blocks, 1.0f / (float)n, loss_dev);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // flag |= 1 when any gradient is inf / nan (GradScaler's found_inf)
 __global__ void check_finite_kernel(const float* __restrict__ g, size_t n, int* __restrict__ flag) {
     bool bad = false;

@@ -732,7 +732,7 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)hipDeviceSynchronize();
     pool_release_all(u);
     for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables, u->edit_x0k, u->edit_mask,
-                     u->edit_rows})
+                     u->edit_rows, u->objective_dev})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -759,6 +759,16 @@ int sisic_unet_set_graph_mode(sisic_unet* u, int mode) {
 }
 
 int64_t sisic_unet_graph_builds(const sisic_unet* u) { return u ? u->loop_builds : 0; }
+
+int sisic_unet_set_prediction_type(sisic_unet* u, int type) {
+    SISIC_REQUIRE(u, "set_prediction_type: null handle");
+    SISIC_REQUIRE(type == SISIC_PRED_EPSILON || type == SISIC_PRED_SAMPLE || type == SISIC_PRED_V,
+                  "set_prediction_type: type %d (0 = epsilon, 1 = sample, 2 = v)", type);
+    u->pred_type = type;
+    return SISIC_OK;
+}
+
+int sisic_unet_prediction_type(const sisic_unet* u) { return u ? u->pred_type : SISIC_PRED_EPSILON; }
 
 int64_t sisic_unet_workspace_bytes(const sisic_unet* u) {
     return u ? u->pool.bytes() : 0;
@@ -890,10 +900,10 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
                                              coef_dev, zrow_dev, rng ? seeds : nullptr, u->cond_tables, clip, s));
     else if (rule == STEP_RULE_DPMPP && rng)
         SISIC_TRY(launch_dpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, (int64_t)(n / B), state,
-                                              coef_dev, seeds, clip, s));
+                                              coef_dev, seeds, clip, s, rule_flags));
     else if (rule == STEP_RULE_DPMPP)
         SISIC_TRY(launch_dpm_step_indexed(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, state, coef_dev, zrow_dev,
-                                          clip, s));
+                                          clip, s, rule_flags));
     else if (rng)
         SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
                                           coef_dev, seeds, clip, s));
@@ -1049,6 +1059,11 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
                          const int64_t* labels, int null_label, float w, const EditCall* ed, float* traj, const int* traj_row,
                          uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
+    // a caller's flags are the rule's own; from here on rule_flags also carries the handle's prediction type in its private
+    // bits, down to the launchers and into the key of a captured step
+    SISIC_REQUIRE((rule_flags & ~SISIC_RULE_FLAG_CLIPPED_OUTPUT) == 0, "sample: rule flags %d (SISIC_RULE_FLAG_CLIPPED_OUTPUT or 0)",
+                  rule_flags);
+    rule_flags |= step_pred_flags(u->pred_type);
     SISIC_TRY(unet_check_labels(u, labels ? "sample_cond" : "sample", labels != nullptr, labels, B));
     SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
     if (traj_row)
@@ -1197,10 +1212,10 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
                                              xe, (int64_t)n, c, clip, s));
             else if (rule == STEP_RULE_DPMPP && rng)
                 SISIC_TRY(launch_dpm_step_rng(u->ctx, u->eps_buf, x, u->hist_buf, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
-                                              (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], c[5], clip, s));
+                                              (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], c[5], clip, s, rule_flags));
             else if (rule == STEP_RULE_DPMPP)
                 SISIC_TRY(launch_dpm_step(u->ctx, u->eps_buf, x, z, u->hist_buf, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], c[5],
-                                          clip, s));
+                                          clip, s, rule_flags));
             else if (rng)
                 SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
                                           (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], clip, s));

@@ -220,6 +220,14 @@ struct sisic_unet {
     float drop_p = 0.0f;
     uint64_t drop_seed = 0;
     uint32_t drop_call = 0;
+    // what the output means (sisic_unet_set_prediction_type): read by the sampling loops (as private bits of the step's flags)
+    // and by the fused training step (its target); the forward pass never looks at it
+    int pred_type = SISIC_PRED_EPSILON;
+    // per-sample loss weights (sisic_unet_set_loss_weights): the host copy, and the device rows {sa, sb, w} [3B] of the
+    // objective kernel of the running call
+    std::vector<float> loss_w;
+    float* objective_dev = nullptr;
+    size_t objective_cap = 0;
 
     // graph-replayed sampling loop (sisic_sample): one captured step, replayed T-1 times
     int graph_mode = -1;                 // -1: follow latency_mode (SISIC_GRAPH in the environment: 0 / 1 forces)
@@ -234,7 +242,8 @@ struct sisic_unet {
         bool edit = false;               // sisic_sample_frames_edit: the step kernel carries the inpainting epilogue
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
         const void* seeds = nullptr;     // ... from the seeds at this address
-        int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags
+        int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags, the
+                                         // handle's prediction type in their private bits (common.h STEP_FLAG_PRED_MASK)
     } loop_key;
     bool loop_valid = false;
     int64_t loop_builds = 0;             // captures + instantiations so far (sisic_unet_graph_builds)

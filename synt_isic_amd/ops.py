@@ -18,18 +18,25 @@ from ._lib import ConvArgs, check
 _ctx_by_device = {}
 
 
-def context(device: torch.device) -> C.c_void_p:
-    """One ``sisic_ctx`` per device, created on first use."""
+def context(device: torch.device, step_prediction: str = "epsilon") -> C.c_void_p:
+    """One ``sisic_ctx`` per (device, step prediction type), created on first use.  ``step_prediction`` says what the ``eps``
+    argument of the single-step wrappers below means to the context (sisic_set_step_prediction_type); it is set once, when the
+    context is created, and never changed: the default context stays an epsilon context and no call toggles shared state.
+    Everything but the step wrappers uses the default context."""
+    code = _lib.prediction_code(step_prediction)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"synt_isic_amd runs on MI355X (torch device 'cuda'); got '{device}'. There is no CPU path.")
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _ctx_by_device:
+    key = idx if code == _lib.PRED_EPSILON else (idx, code)
+    if key not in _ctx_by_device:
         lib = _lib.load()
         h = C.c_void_p()
         check(lib.sisic_create(idx, C.byref(h)))
-        _ctx_by_device[idx] = h
-    return _ctx_by_device[idx]
+        if code != _lib.PRED_EPSILON:
+            check(lib.sisic_set_step_prediction_type(h, code))
+        _ctx_by_device[key] = h
+    return _ctx_by_device[key]
 
 
 def empty(shape, *, dtype, device, pin_memory=False) -> torch.Tensor:
@@ -227,13 +234,14 @@ def attention(qkv: torch.Tensor, head_dim: int = 8) -> torch.Tensor:
 
 
 def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """coef = (sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma)."""
+              out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+    """coef = (sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma).  ``prediction_type`` (here and in every step wrapper below):
+    what ``eps`` holds -- "epsilon", "sample" (x0) or "v_prediction" (include/sisic.h SISIC_PRED_*)."""
     lib = _lib.load()
     if out is None:
         out = empty_like(x)
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
+    check(lib.sisic_ddpm_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
     return out
 
@@ -289,7 +297,7 @@ def noise_bits(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") 
 
 
 def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
     """``ddpm_step`` with z generated in the kernel: eps, x are [B, ...] (or flat with B = len(seeds) equal images);
     image b draws ``noise_fill([seeds[b]], n_per_image, step)``."""
     lib = _lib.load()
@@ -301,27 +309,29 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+    check(lib.sisic_ddpm_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
     return out
 
 
 def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
-              use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None,
+              prediction_type: str = "epsilon") -> torch.Tensor:
     """sisic_ddim_step: coef = (sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma), a row of
     ``HipDDIMScheduler.coefficient_table``.  z None or sigma == 0: no noise is added."""
     lib = _lib.load()
     if out is None:
         out = empty_like(x)
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
+    check(lib.sisic_ddim_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c_prev, c_dir, sigma, float(clip), int(bool(use_clipped_model_output)),
                               _stream(x.device)))
     return out
 
 
 def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
-                  use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None,
+                  prediction_type: str = "epsilon") -> torch.Tensor:
     """``ddim_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
     lib = _lib.load()
@@ -333,14 +343,14 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+    check(lib.sisic_ddim_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c_prev, c_dir, sigma, float(clip),
                                   int(bool(use_clipped_model_output)), _stream(x.device)))
     return out
 
 
 def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hist: torch.Tensor, coef, clip: float = 0.0,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
     """sisic_dpmpp_step: coef = (sigma_t, alpha_t, cx, k0, sigma, k1), a row of
     ``HipDPMSolverMultistepScheduler.coefficient_table``.  hist: the previous step's x0, a tensor of x's size that the
     call overwrites with this step's x0 and reads only when k1 != 0.  z None or sigma == 0: no noise is added."""
@@ -350,13 +360,13 @@ def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hi
     if out is None:
         out = empty_like(x)
     sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
+    check(lib.sisic_dpmpp_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
                                _ptr(out, "out"), x.numel(), sb, sa, cx, k0, sigma, k1, float(clip), _stream(x.device)))
     return out
 
 
 def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, clip: float = 0.0,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
     """``dpmpp_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
     lib = _lib.load()
@@ -370,13 +380,13 @@ def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: t
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step_rng(context(x.device), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
+    check(lib.sisic_dpmpp_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
                                    x.numel() // B, seeds_dev.data_ptr(), int(step), sb, sa, cx, k0, sigma, k1, float(clip),
                                    _stream(x.device)))
     return out
 
 
-def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out):
+def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out, prediction_type="epsilon"):
     """the three ``*_step_edit`` wrappers: the ``_rng`` wrapper's arguments, the known image, the mask and the edit row"""
     lib = _lib.load()
     arr = _seed_array(seeds)
@@ -395,7 +405,7 @@ def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     ck, sk, ja, jb = (float(v) for v in erow)
-    args = [context(x.device), _ptr(eps, "eps"), _ptr(x, "x")]
+    args = [context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x")]
     if hist is not None:
         args.append(_ptr(hist, "hist"))
     args += [_ptr(out, "out"), B, npi, seeds_dev.data_ptr(), int(step), *(float(v) for v in row), float(clip)]
@@ -407,32 +417,33 @@ def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask
 
 
 def ddpm_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
-                   clip: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   clip: float = 1.0, out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
     """sisic_ddpm_step_edit: ``ddpm_step_rng`` with the inpainting epilogue (include/sisic.h) fused into the kernel.
     x0k: the known image, fp32 of x's size, finite; mask: fp32 [B,1,H,W] (1 = keep); erow = (ck, sk, ja, jb).  The epilogue
     draws under tags 5 (``sk != 0``) and 6 (``jb != 0``) of ``noise_fill`` at the same ``step``."""
     if len(tuple(coef)) != 5:
         raise ValueError("a DDPM row holds 5 values")
-    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out)
+    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out, prediction_type)
 
 
 def ddim_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
                    clip: float = 1.0, use_clipped_model_output: bool = False,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
     """sisic_ddim_step_edit: ``ddim_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``."""
     if len(tuple(coef)) != 5:
         raise ValueError("a DDIM row holds 5 values")
     return _step_edit("sisic_ddim_step_edit", eps, x, seeds, step, None, coef, use_clipped_model_output, clip, x0k, mask, erow,
-                      out)
+                      out, prediction_type)
 
 
 def dpmpp_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, x0k: torch.Tensor,
-                    mask: torch.Tensor, erow, clip: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    mask: torch.Tensor, erow, clip: float = 0.0, out: Optional[torch.Tensor] = None,
+                    prediction_type: str = "epsilon") -> torch.Tensor:
     """sisic_dpmpp_step_edit: ``dpmpp_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``; ``hist`` receives the
     model's predicted x0, which the epilogue does not touch."""
     if len(tuple(coef)) != 6:
         raise ValueError("a DPM-Solver++ row holds 6 values")
-    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out)
+    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out, prediction_type)
 
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,

@@ -377,6 +377,7 @@ class SampleResult:
     strength: float = 1.0                      # image-to-image / inpainting: the part of the grid the run went through
     n_resample: int = 1                        # inpainting: RePaint's resampling count (1: no jumps)
     unet_passes: int = 0                       # UNet passes of the whole run (the grid's steps plus the resampled ones)
+    prediction_type: str = "epsilon"           # what the model's output meant to the step rule (the model's own property)
 
 
 def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence[int]]):
@@ -467,7 +468,7 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
         out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
                         steps_done=done.value, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta), unet_passes=T)
+                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"))
 
 
 def check_edit_schedule(rule: str, schedule, T: int) -> List[Tuple[int, int]]:
@@ -555,7 +556,8 @@ def _run_edited(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, edit
     if cancelled:
         out_u8.zero_()
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done_total, cancelled=cancelled, scheduler=rule_name, eta=float(eta), unet_passes=P)
+                        steps_done=done_total, cancelled=cancelled, scheduler=rule_name, eta=float(eta), unet_passes=P,
+                        prediction_type=getattr(model, "prediction_type", "epsilon"))
 
 
 def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
@@ -625,7 +627,7 @@ def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: Noise
         out_u8.zero_()
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
                         steps_done=done_total, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta), unet_passes=T)
+                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"))
 
 
 def strength_steps(T: int, strength) -> int:
@@ -774,8 +776,12 @@ class Sampler:
             self.color_statistics = json.load(f)
         return len(self.color_statistics)
 
-    def add_model(self, class_name: str, state_dict: Dict[str, torch.Tensor], **unet_kwargs) -> HipUNet2DModel:
-        m = HipUNet2DModel(**unet_kwargs)
+    def add_model(self, class_name: str, state_dict: Dict[str, torch.Tensor], prediction_type: str = "epsilon",
+                  **unet_kwargs) -> HipUNet2DModel:
+        """``prediction_type``: what the checkpoint was trained to predict ("epsilon", "sample" or "v_prediction").  The model
+        carries it, so every ``generate*`` call and loop uses the matching step arithmetic with nothing new from the caller;
+        ``SampleResult.prediction_type`` records it."""
+        m = HipUNet2DModel(prediction_type=prediction_type, **unet_kwargs)
         m.set_latency_mode(self.latency_mode)
         m.load_state_dict(state_dict)
         m = m.to(self.device)
@@ -784,7 +790,7 @@ class Sampler:
         return m
 
     def add_conditional_model(self, class_names: Sequence[str], state_dict: Dict[str, torch.Tensor],
-                              **unet_kwargs) -> HipUNet2DModel:
+                              prediction_type: str = "epsilon", **unet_kwargs) -> HipUNet2DModel:
         """ONE class-conditional model for several class names (``train.train_conditional``'s checkpoint): the label of a
         name is its index in ``class_names``, the null label of classifier-free guidance is ``len(class_names)``, so the model
         has ``len(class_names) + 1`` embedding rows.  Every name then works wherever a class name does, and a call may mix
@@ -799,7 +805,7 @@ class Sampler:
         if rows != len(names) + 1:
             raise ValueError(f"a conditional model for {len(names)} classes has {len(names) + 1} embedding rows (the last is "
                              f"the null label), got num_class_embeds={rows}")
-        m = self.add_model(names[0], state_dict, **unet_kwargs)
+        m = self.add_model(names[0], state_dict, prediction_type=prediction_type, **unet_kwargs)
         for k, n in enumerate(names):
             self.models[n] = m
             self.class_labels[n] = k

@@ -128,9 +128,11 @@ class HipDDPMScheduler:
     @torch.no_grad()
     def step(self, model_output: torch.Tensor, timestep: Union[int, torch.Tensor], sample: torch.Tensor,
              generator: Optional[torch.Generator] = None, return_dict: bool = True,
-             variance_noise: Optional[torch.Tensor] = None):
+             variance_noise: Optional[torch.Tensor] = None, prediction_type: str = "epsilon"):
         """prev_sample = DDPM ancestral update on the GPU.  Noise: ``variance_noise`` if given, else
-        ``torch.randn`` on the sample's device with ``generator`` (the reference passes none)."""
+        ``torch.randn`` on the sample's device with ``generator`` (the reference passes none).  ``prediction_type``: what
+        ``model_output`` holds -- "epsilon", "sample" or "v_prediction".  It is the MODEL's property (``HipUNet2DModel
+        (prediction_type=)``), so it travels with the call (``model.prediction_type``), not with the scheduler's constructor."""
         if model_output.device.type != "cuda":
             raise RuntimeError("HipDDPMScheduler.step runs on MI355X tensors only (no CPU path)")
         coef = self.step_coefficients(timestep)
@@ -144,7 +146,7 @@ class HipDDPMScheduler:
                 z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         prev = ops.ddpm_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z,
-                             coef, clip)
+                             coef, clip, prediction_type=prediction_type)
         if not return_dict:
             return (prev,)
         return DDPMSchedulerOutput(prev_sample=prev)
@@ -173,6 +175,30 @@ class HipDDPMScheduler:
         a, c = ops.upload(torch.stack([a, c]), x0.device)          # pinned, non-blocking: the call does not wait for the stream
         out = ops.empty_like(x0)
         check(_lib.load().sisic_add_noise(ops.context(x0.device), x0.data_ptr(), nz.data_ptr(), a.data_ptr(), c.data_ptr(),
+                                          out.data_ptr(), B, x0[0].numel(),
+                                          C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))
+        return out
+
+    @torch.no_grad()
+    def get_velocity(self, sample: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """``DDPMScheduler.get_velocity``: v = sqrt(abar_t) * noise - sqrt(1 - abar_t) * sample, the regression target of a
+        v-prediction model, on the GPU.  It is sisic_add_noise with (x0 := noise, noise := sample, a = sqrt(abar),
+        c = -sqrt(1 - abar)): a sum with a negated product rounds exactly as the difference does, so the result equals the
+        torch formula bit for bit -- and the target the fused training step forms in its loss kernel."""
+        if sample.device.type != "cuda":
+            raise RuntimeError("get_velocity runs on MI355X tensors only (no CPU path)")
+        from . import _lib
+        from ._lib import check
+        import ctypes as C
+        x0 = sample.to(torch.float32).contiguous()
+        nz = noise.to(device=x0.device, dtype=torch.float32).contiguous()
+        B = x0.shape[0]
+        a, c = self.add_noise_coefficients(timesteps)
+        if a.numel() != B:
+            raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
+        a, c = ops.upload(torch.stack([a, -c]), x0.device)
+        out = ops.empty_like(x0)
+        check(_lib.load().sisic_add_noise(ops.context(x0.device), nz.data_ptr(), x0.data_ptr(), a.data_ptr(), c.data_ptr(),
                                           out.data_ptr(), B, x0[0].numel(),
                                           C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))
         return out
@@ -231,6 +257,7 @@ class HipDDIMScheduler:
     scale_model_input = HipDDPMScheduler.scale_model_input
     add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
     add_noise = HipDDPMScheduler.add_noise
+    get_velocity = HipDDPMScheduler.get_velocity
     previous_timestep = HipDDPMScheduler.previous_timestep      # t - num_train_timesteps // num_inference_steps, both spacings
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
@@ -272,8 +299,9 @@ class HipDDIMScheduler:
     @torch.no_grad()
     def step(self, model_output: torch.Tensor, timestep: Union[int, torch.Tensor], sample: torch.Tensor, eta: float = 0.0,
              use_clipped_model_output: bool = False, generator: Optional[torch.Generator] = None,
-             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
-        """prev_sample = DDIM update on the GPU.  Noise, on the steps with sigma != 0 only: ``variance_noise`` if given, else
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True, prediction_type: str = "epsilon"):
+        """prev_sample = DDIM update on the GPU (``prediction_type``: as in ``HipDDPMScheduler.step``).
+        Noise, on the steps with sigma != 0 only: ``variance_noise`` if given, else
         ``torch.randn`` on the sample's device with ``generator``.  (diffusers also draws on a step whose sigma is 0 at
         eta > 0, and multiplies the draw by 0: a generator shared with it is one draw further on after such a step.)"""
         if model_output.device.type != "cuda":
@@ -289,7 +317,7 @@ class HipDDIMScheduler:
                 z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         prev = ops.ddim_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z, coef, clip,
-                             use_clipped_model_output)
+                             use_clipped_model_output, prediction_type=prediction_type)
         if not return_dict:
             return (prev,)
         return DDIMSchedulerOutput(prev_sample=prev)
@@ -406,6 +434,7 @@ class HipDPMSolverMultistepScheduler:
     scale_model_input = HipDDPMScheduler.scale_model_input
     add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
     add_noise = HipDDPMScheduler.add_noise
+    get_velocity = HipDDPMScheduler.get_velocity
 
     def _reset(self) -> None:
         self._hist: Optional[torch.Tensor] = None     # the previous step's x0 (device), None before the first step
@@ -447,8 +476,9 @@ class HipDPMSolverMultistepScheduler:
     @torch.no_grad()
     def step(self, model_output: torch.Tensor, timestep: Union[int, torch.Tensor], sample: torch.Tensor,
              generator: Optional[torch.Generator] = None, variance_noise: Optional[torch.Tensor] = None,
-             return_dict: bool = True):
-        """prev_sample = DPM-Solver++ update on the GPU.  The first call after ``set_timesteps`` finds its place in
+             return_dict: bool = True, prediction_type: str = "epsilon"):
+        """prev_sample = DPM-Solver++ update on the GPU (``prediction_type``: as in ``HipDDPMScheduler.step``).
+        The first call after ``set_timesteps`` finds its place in
         ``timesteps`` by ``timestep`` and is first order (there is no history yet); every call then moves one step on.
         Noise, on the steps with sigma != 0 only (the SDE variant, all but the last): ``variance_noise`` if given, else
         ``torch.randn`` with ``generator``."""
@@ -478,7 +508,8 @@ class HipDPMSolverMultistepScheduler:
             else:
                 z = torch.randn(model_output.shape, generator=generator, device=x.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
-        prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, clip)
+        prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, clip,
+                              prediction_type=prediction_type)
         self._step_index = i + 1
         if not return_dict:
             return (prev,)

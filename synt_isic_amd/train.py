@@ -29,6 +29,10 @@ and the regulariser of the published model itself, ``UNet2DModel(dropout=p)``: `
 block of the tape-recording forward (spelled-out and fused steps alike), with masks regenerated from a counter in the backward
 pass (include/sisic.h, the mask contract); ``train_class(..., dropout_seed=s)`` seeds them.
 
+The objective is a choice as well: the target follows ``model.prediction_type`` ("epsilon", "sample", "v_prediction") and
+``snr_gamma`` weights every sample's loss by Min-SNR-gamma (``min_snr_weights``): ``diffusion_loss`` in the spelled-out loop,
+``train_step_fused(..., snr_gamma=)`` in the fused one, ``train_class(..., snr_gamma=)``.  With the defaults nothing changes.
+
 No torch.autograd anywhere: the backward pass is explicit HIP kernels (csrc/train.cpp).  Arithmetic is fp32; the
 GradScaler protocol (scale, unscale, inf check, skip, growth/backoff) is implemented, the autocast-to-fp16 is not.
 ``train_step_fused`` runs the whole loop body in ONE C call (sisic_unet_train_step).
@@ -60,11 +64,28 @@ def _stream(dev) -> C.c_void_p:
 class HipLoss:
     """What ``F.mse_loss(noise_pred, noise)`` returns in the reference's loop: ``.item()`` and ``.backward()``."""
 
-    def __init__(self, model: HipUNet2DModel, pred: torch.Tensor, target: torch.Tensor, scale: float = 1.0):
+    def __init__(self, model: HipUNet2DModel, pred: torch.Tensor, target: torch.Tensor, scale: float = 1.0,
+                 weights: Optional[torch.Tensor] = None):
         self.model, self.pred, self.target, self.scale = model, pred, target, float(scale)
+        # per-sample loss weights (host fp32 [B]) or None: set on the handle for each of the two sisic_mse_loss calls and
+        # cleared after it, so that nothing else is ever weighted by a leftover
+        self.weights = None if weights is None else weights.detach().to("cpu", torch.float32).reshape(-1).contiguous()
         self._loss = ops.empty(1, dtype=torch.float32, device=pred.device)
-        check(_lib.load().sisic_mse_loss(model.handle, pred.data_ptr(), target.data_ptr(), pred.numel(), 1.0,
-                                         self._loss.data_ptr(), None, _stream(pred.device)))
+        self._mse(1.0, self._loss.data_ptr(), None)
+
+    def _mse(self, grad_scale: float, loss_ptr, dpred_ptr) -> None:
+        lib, model = _lib.load(), self.model
+        if self.weights is None:
+            _clear_loss_weights(model)
+            check(lib.sisic_mse_loss(model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(), grad_scale,
+                                     loss_ptr, dpred_ptr, _stream(self.pred.device)))
+            return
+        _set_loss_weights(model, self.weights)
+        try:
+            check(lib.sisic_mse_loss(model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(), grad_scale,
+                                     loss_ptr, dpred_ptr, _stream(self.pred.device)))
+        finally:
+            _clear_loss_weights(model)
 
     def item(self) -> float:
         return float(self._loss.item())
@@ -79,17 +100,82 @@ class HipLoss:
         """d(scale * loss)/d(parameters) into the model's gradient arena (the tape of the last forward is consumed)."""
         dpred = ops.empty_like(self.pred)
         lib = _lib.load()
-        check(lib.sisic_mse_loss(self.model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(),
-                                 self.scale, None, dpred.data_ptr(), _stream(self.pred.device)))
+        self._mse(self.scale, None, dpred.data_ptr())
         check(lib.sisic_unet_backward(self.model.handle, dpred.data_ptr(), _stream(self.pred.device)))
 
 
+def _set_loss_weights(model: HipUNet2DModel, weights: torch.Tensor) -> None:
+    """sisic_unet_set_loss_weights: host fp32 [B], kept by the handle until cleared"""
+    check(_lib.load().sisic_unet_set_loss_weights(model.handle, C.cast(weights.data_ptr(), _lib.c_float_p), weights.numel()))
+    model._loss_weights_set = True
+
+
+def _clear_loss_weights(model: HipUNet2DModel) -> None:
+    """clear the handle's loss weights if this module set any (a model that never had weights makes no call)"""
+    if getattr(model, "_loss_weights_set", False):
+        check(_lib.load().sisic_unet_set_loss_weights(model.handle, None, 0))
+        model._loss_weights_set = False
+
+
 def mse_loss(noise_pred: torch.Tensor, noise: torch.Tensor) -> HipLoss:
-    """``torch.nn.functional.mse_loss(noise_pred, noise)`` for the output of a training-mode ``HipUNet2DModel`` call."""
+    """``torch.nn.functional.mse_loss(noise_pred, noise)`` for the output of a training-mode ``HipUNet2DModel`` call.  Always
+    the plain mean: loss weights left on the handle are cleared first."""
     model = getattr(noise_pred, "_sisic_model", None)
     if model is None:
         raise RuntimeError("mse_loss expects the .sample of a HipUNet2DModel called in training mode")
     return HipLoss(model, noise_pred.contiguous(), noise.to(device=noise_pred.device, dtype=torch.float32).contiguous())
+
+
+def compute_snr(scheduler, timesteps) -> torch.Tensor:
+    """SNR(t) = abar_t / (1 - abar_t) of the scheduler's table, float64 [B] on the host (diffusers' ``compute_snr``)."""
+    t = torch.as_tensor(timesteps).detach().to("cpu").to(torch.int64).reshape(-1)
+    abar = scheduler.alphas_cumprod.to(torch.float64)[t]
+    return abar / (1.0 - abar)
+
+
+def min_snr_weights(scheduler, timesteps, snr_gamma: float, prediction_type: str = "epsilon") -> torch.Tensor:
+    """Min-SNR-gamma loss weights (Hang et al. 2023) per sample, computed in float64 and rounded to fp32 once, host [B]:
+    epsilon ``min(snr, g) / snr``; v_prediction ``min(snr, g) / (snr + 1)``; sample ``min(snr, g)``.  ``snr_gamma`` may be
+    ``inf`` (epsilon: all ones)."""
+    _lib.prediction_code(prediction_type)
+    g = float(snr_gamma)
+    if not g > 0.0:
+        raise ValueError(f"snr_gamma must be positive, got {snr_gamma}")
+    snr = compute_snr(scheduler, timesteps)
+    capped = torch.clamp(snr, max=g)
+    if prediction_type == "epsilon":
+        w = capped / snr
+    elif prediction_type == "v_prediction":
+        w = capped / (snr + 1.0)
+    else:
+        w = capped
+    return w.to(torch.float32)
+
+
+def diffusion_target(model: HipUNet2DModel, scheduler, images: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
+    """what a model of ``model.prediction_type`` regresses on: the noise, the images, or ``scheduler.get_velocity``"""
+    kind = model.prediction_type
+    if kind == "epsilon":
+        return noise
+    if kind == "sample":
+        return images
+    return scheduler.get_velocity(images, noise, timesteps)
+
+
+def diffusion_loss(model_output: torch.Tensor, images: torch.Tensor, noise: torch.Tensor, timesteps, scheduler,
+                   snr_gamma: Optional[float] = None) -> HipLoss:
+    """The loss of the spelled-out loop under the model's objective: ``mse_loss(model_output, target)`` with the target that
+    follows the model's ``prediction_type`` and, with ``snr_gamma``, the per-sample Min-SNR weights of ``min_snr_weights``
+    (set on the handle for the loss's two library calls and cleared after each).  Equal to the fused step bit for bit."""
+    model = getattr(model_output, "_sisic_model", None)
+    if model is None:
+        raise RuntimeError("diffusion_loss expects the .sample of a HipUNet2DModel called in training mode")
+    dev = model_output.device
+    x0 = images.to(device=dev, dtype=torch.float32).contiguous()
+    nz = noise.to(device=dev, dtype=torch.float32).contiguous()
+    target = diffusion_target(model, scheduler, x0, nz, timesteps)
+    weights = None if snr_gamma is None else min_snr_weights(scheduler, timesteps, snr_gamma, model.prediction_type)
+    return HipLoss(model, model_output.contiguous(), target.contiguous(), weights=weights)
 
 
 class HipEMA:
@@ -360,13 +446,27 @@ class HipGradScaler:
 
 
 def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images: torch.Tensor, noise: torch.Tensor,
-                     timesteps: torch.Tensor, optimizer: HipAdam, scaler: Optional[HipGradScaler] = None, class_labels=None):
+                     timesteps: torch.Tensor, optimizer: HipAdam, scaler: Optional[HipGradScaler] = None, class_labels=None,
+                     snr_gamma: Optional[float] = None):
     """The loop body of train_diffusion.py:215-233 in one library call (sisic_unet_train_step; sisic_unet_train_step_ext
     when the optimizer clips or carries an EMA -- the norm is then ``optimizer.grad_norm``); returns (loss, step_taken).
     ``class_labels``: one integer per image for a class-conditional model (sisic_unet_train_step_cond), None otherwise; the
-    library takes them as a host array, so labels on the device cost one small blocking copy per step."""
+    library takes them as a host array, so labels on the device cost one small blocking copy per step.
+    The target follows ``model.prediction_type`` (the handle carries it; v is formed inside the loss kernel).  ``snr_gamma``:
+    Min-SNR-gamma weights of this batch's timesteps (``min_snr_weights``), set on the handle for this call and cleared after."""
     labels = model._labels_host(class_labels, images.shape[0])
     model._ensure_training()
+    if snr_gamma is None:
+        _clear_loss_weights(model)
+        return _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels)
+    _set_loss_weights(model, min_snr_weights(scheduler, timesteps, snr_gamma, model.prediction_type).contiguous())
+    try:
+        return _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels)
+    finally:
+        _clear_loss_weights(model)
+
+
+def _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels):
     x0 = images.to(device=model.device, dtype=torch.float32).contiguous()
     nz = noise.to(device=model.device, dtype=torch.float32).contiguous()
     B, _, H, W = x0.shape
@@ -422,7 +522,7 @@ def drop_labels(labels: torch.Tensor, cond_drop_prob: float, null_label: int,
 
 def _train_loop(model: HipUNet2DModel, loader, name: str, epochs: int, lr: float, checkpoint_dir: Optional[str], fused: bool,
                 generator: Optional[torch.Generator], log, max_grad_norm, ema_decay, ema_warmup: bool, lr_schedule,
-                cond_drop_prob: Optional[float], dropout_seed: int = 0):
+                cond_drop_prob: Optional[float], dropout_seed: int = 0, snr_gamma: Optional[float] = None):
     """the loop of train_class; cond_drop_prob not None: the loader yields (images, labels) and the model is conditional"""
     dev = model.device
     if model.config.dropout > 0:
@@ -460,11 +560,15 @@ def _train_loop(model: HipUNet2DModel, loader, name: str, epochs: int, lr: float
                 labels = drop_labels(torch.as_tensor(labels).to("cpu", torch.int64), cond_drop_prob,
                                      model.config.num_class_embeds - 1, generator)
             if fused:
-                value, _ = train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, class_labels=labels)
+                value, _ = train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, class_labels=labels,
+                                            snr_gamma=snr_gamma)
             else:
                 noisy_images = scheduler.add_noise(images, noise, timesteps)
                 noise_pred = model(noisy_images, timesteps, class_labels=labels).sample
-                loss = mse_loss(noise_pred, noise)
+                if snr_gamma is None and model.prediction_type == "epsilon":
+                    loss = mse_loss(noise_pred, noise)
+                else:
+                    loss = diffusion_loss(noise_pred, images, noise, timesteps, scheduler, snr_gamma=snr_gamma)
                 optimizer.zero_grad(set_to_none=True)
                 scaler.scale(loss).backward()
                 scaler.step(optimizer)
@@ -494,7 +598,8 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
                 checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
                 log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
                 ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0):
+                lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0,
+                snr_gamma: Optional[float] = None):
     """``train_class`` of train_diffusion.py:187-266 for one class: epochs over ``loader`` (batches of images in [-1,1],
     [B,3,H,W]), best-loss checkpoint ``unet_{class}_best.pth`` and a checkpoint every 5 epochs.  Returns the per-epoch
     average losses.  ``generator`` seeds noise / timestep draws (the reference uses the global RNG).
@@ -503,18 +608,21 @@ def train_class(model: HipUNet2DModel, loader: Iterable[torch.Tensor], class_nam
     the weights (``ema_warmup``: EMAModel's warm-up decay) and saves it beside every checkpoint as ``..._ema.pth``;
     ``lr_schedule`` is a lambda step -> factor of ``lr`` (``cosine_schedule_with_warmup``), advanced once per batch.
     A model built with ``dropout > 0`` trains with it; ``dropout_seed`` seeds its masks (they do not consume ``generator``), and
-    the checkpoints are those of a model without: dropout adds no tensors."""
+    the checkpoints are those of a model without: dropout adds no tensors.  The objective is the model's: a model built with
+    ``prediction_type="v_prediction"`` or ``"sample"`` regresses on v or on the images; ``snr_gamma`` weights every sample's
+    loss by Min-SNR-gamma (``min_snr_weights``; 5.0 is the published choice).  The type is not recorded in the checkpoint."""
     if model.config.num_class_embeds is not None:
         raise ValueError("train_class trains an unconditional model; a class-conditional one takes train_conditional")
     return _train_loop(model, loader, class_name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
-                       ema_warmup, lr_schedule, None, dropout_seed)
+                       ema_warmup, lr_schedule, None, dropout_seed, snr_gamma)
 
 
 def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: float = 0.1, epochs: int = 50, lr: float = LR,
                       checkpoint_dir: Optional[str] = None, fused: bool = True, generator: Optional[torch.Generator] = None,
                       log: Optional[Callable[[str], None]] = print, max_grad_norm: Optional[float] = None,
                       ema_decay: Optional[float] = None, ema_warmup: bool = False,
-                      lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0):
+                      lr_schedule: Optional[Callable[[int], float]] = None, dropout_seed: int = 0,
+                      snr_gamma: Optional[float] = None):
     """``train_class`` for ONE class-conditional model over all classes: ``loader`` yields ``(images, labels)`` (a
     ``data.DeviceLoader`` over a labelled ``DeviceDataset``), the labels go to the model as ``class_labels``.  Checkpoints
     (``unet_{name}_best.pth``, every 5 epochs, the ``_ema`` files), clipping, EMA, schedule and the returned history are
@@ -529,4 +637,4 @@ def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: 
     if not 0.0 <= float(cond_drop_prob) <= 1.0:
         raise ValueError(f"cond_drop_prob must be in [0, 1], got {cond_drop_prob}")
     return _train_loop(model, loader, name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
-                       ema_warmup, lr_schedule, float(cond_drop_prob), dropout_seed)
+                       ema_warmup, lr_schedule, float(cond_drop_prob), dropout_seed, snr_gamma)

@@ -67,7 +67,8 @@ class HipUNet2DModel:
                  down_block_types: Sequence[str] = ("DownBlock2D", "DownBlock2D", "AttnDownBlock2D", "DownBlock2D"),
                  up_block_types: Sequence[str] = ("UpBlock2D", "AttnUpBlock2D", "UpBlock2D", "UpBlock2D"),
                  class_embed_type=None, norm_num_groups: int = 32, norm_eps: float = 1e-5,
-                 attention_head_dim: int = 8, num_class_embeds: Optional[int] = None, dropout: float = 0.0, **unsupported):
+                 attention_head_dim: int = 8, num_class_embeds: Optional[int] = None, dropout: float = 0.0,
+                 prediction_type: str = "epsilon", **unsupported):
         if class_embed_type is not None:
             raise NotImplementedError("class_embed_type must be None (the reference's models are unconditional; a "
                                       "class-conditional model is num_class_embeds=N, diffusers' nn.Embedding form)")
@@ -77,7 +78,8 @@ class HipUNet2DModel:
                                  layers_per_block=layers_per_block, block_out_channels=tuple(block_out_channels),
                                  down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types),
                                  norm_num_groups=norm_num_groups, norm_eps=norm_eps,
-                                 attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds, dropout=dropout)
+                                 attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds, dropout=dropout,
+                                 prediction_type=prediction_type)
         self.config.validate()
         if attention_head_dim != 8:
             raise NotImplementedError("attention_head_dim must be 8 (the HIP attention kernel is built for d=8)")
@@ -132,6 +134,23 @@ class HipUNet2DModel:
         self.config, self._dropout_seed, self._dropout_call = config, seed, first_call
         if self._handle is not None:
             check(_lib.load().sisic_unet_set_dropout(self._handle, float(p), seed, first_call))
+        return self
+
+    @property
+    def prediction_type(self) -> str:
+        """what ``model(x, t).sample`` means: "epsilon", "sample" or "v_prediction" (``config.prediction_type``)"""
+        return self.config.prediction_type
+
+    def set_prediction_type(self, prediction_type: str) -> "HipUNet2DModel":
+        """Say what the output means from now on (sisic_unet_set_prediction_type).  The network does not know: ``model(x, t)``
+        returns the same bits.  The sampling loops read it (how the step rule gets its x0: include/sisic.h SISIC_PRED_*) and so
+        does the fused training step (its regression target); a scheduler mirror's ``step`` takes it per call
+        (``prediction_type=model.prediction_type``).  Anything but the three names raises NotImplementedError."""
+        config = dataclasses.replace(self.config, prediction_type=prediction_type)
+        config.validate()
+        self.config = config
+        if self._handle is not None:
+            check(_lib.load().sisic_unet_set_prediction_type(self._handle, _lib.prediction_code(prediction_type)))
         return self
 
     @property
@@ -297,6 +316,8 @@ class HipUNet2DModel:
             check(lib.sisic_unet_set_latency_mode(h, 1))
         if cfg.dropout > 0:
             check(lib.sisic_unet_set_dropout(h, float(cfg.dropout), self._dropout_seed, self._dropout_call))
+        if cfg.prediction_type != "epsilon":
+            check(lib.sisic_unet_set_prediction_type(h, _lib.prediction_code(cfg.prediction_type)))
         # the library's own view of the expected keys must agree with ours
         n = lib.sisic_unet_num_tensors(h)
         names = [lib.sisic_unet_tensor_name(h, i).decode() for i in range(n)]
