@@ -303,6 +303,10 @@ typedef struct sisic_unet_config {
     const float* freqs;              /* host [n_freqs]: sinusoid frequencies (fp32, copied) */
 } sisic_unet_config;
 
+/* Host work only: the configuration is checked, the tensor list (sisic_unet_num_tensors / sisic_unet_tensor_name: diffusers
+ * key names in state-dict order) is built, and the context pointer is KEPT, not read -- no device call is made before
+ * sisic_unet_load.  The description of an architecture can therefore be queried where there is no GPU
+ * (tests/test_arch_ref_cpu.py does, with a stand-in context).                                                           */
 int sisic_unet_create(sisic_ctx*, const sisic_unet_config* cfg, sisic_unet** out);
 /* The class-conditional UNet2DModel(num_class_embeds = N): one more tensor, class_embedding.weight [N, 4 *
  * block_out_channels[0]], directly after time_embedding.linear_2.bias in the state dict (diffusers registers class_embedding
@@ -588,7 +592,9 @@ int sisic_unet_optimizer_step(sisic_unet*, double lr, double beta1, double beta2
                               void* stream);
 /* The whole loop body (train_diffusion.py:215-233) on one stream: add_noise, forward, MSE, backward, optimizer step.
  * images / noise: dev [B,C,H,W]; timesteps and the two add_noise coefficient rows: HOST arrays [B].
- * loss_out (host, may be NULL) receives the unscaled loss (one synchronisation).                                       */
+ * loss_out (host, may be NULL) receives the unscaled loss (one synchronisation).
+ * The target has the input's shape, so the three fused steps need in_channels == out_channels, as the sisic_sample* loops
+ * do: SISIC_EINVAL naming both counts otherwise, before anything is allocated or launched.                              */
 int sisic_unet_train_step(sisic_unet*, const float* images, const float* noise, const int64_t* timesteps,
                           const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
                           double beta1, double beta2, double eps, float loss_scale, float* loss_out, int* found_inf, void* stream);

@@ -380,6 +380,13 @@ int train_step_body(sisic_unet* u, const float* images, const float* noise, cons
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState* tr = u->train.get();
     const int C = u->cfg.in_channels;
+    // The fused step regresses the prediction on a tensor of the INPUT's shape (the noise, the image or v) and lays out
+    // noisy | prediction | d prediction as three blocks of that size: a model whose output has another channel count (the
+    // learned-variance layout, out = 2 in) would write its prediction over d prediction.  As the sampling loops: refused
+    // before any buffer is grown or any launch made.  (The spelled-out loop takes such a model: its target has the output's shape.)
+    SISIC_REQUIRE(u->cfg.out_channels == C,
+                  "train_step: in/out channels differ: the model maps %d input channels to %d output channels, and the fused step's "
+                  "target has the input's shape", C, u->cfg.out_channels);
     const size_t n = (size_t)B * C * H * W;
     // a table left from another batch size is an error, never a silently unweighted (or wrongly weighted) loss
     const bool weighted = !u->loss_w.empty();

@@ -66,6 +66,10 @@ class HipLoss:
 
     def __init__(self, model: HipUNet2DModel, pred: torch.Tensor, target: torch.Tensor, scale: float = 1.0,
                  weights: Optional[torch.Tensor] = None):
+        # the library's loss walks both tensors by the prediction's element count: a target of another shape (the noise of a
+        # model whose out_channels differ from its in_channels) is refused here, before any library call
+        if tuple(target.shape) != tuple(pred.shape):
+            raise RuntimeError(f"mse_loss: the target's shape {tuple(target.shape)} must match the prediction's {tuple(pred.shape)}")
         self.model, self.pred, self.target, self.scale = model, pred, target, float(scale)
         # per-sample loss weights (host fp32 [B]) or None: set on the handle for each of the two sisic_mse_loss calls and
         # cleared after it, so that nothing else is ever weighted by a leftover
