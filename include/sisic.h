@@ -192,7 +192,10 @@ int sisic_conv2d_gn_rider(sisic_ctx*, const sisic_conv_args* args,
 /* Multi-head self-attention core (replaces scaled_dot_product_attention inside
  * diffusers' Attention, heads = C/head_dim, softmax in fp32, scale head_dim^-0.5).
  * qkv: dev [B,3*C,N] (q channels, then k, then v; channel = head*head_dim + d),
- * out: dev [B,C,N].  head_dim must be 8 (the reference's attention_head_dim).     */
+ * out: dev [B,C,N].  head_dim: 8 (the reference's attention_head_dim), 32 or 64; C a
+ * multiple of it; any N >= 1.  8 runs attention.hip, 32 and 64 attention_wide.hip
+ * (exact fp32 products on the matrix pipe); anything else is SISIC_EINVAL ("head_dim").
+ * A sample's bits do not depend on the batch.  No allocation, no synchronisation.  */
 int sisic_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim,
                     void* stream);
 
@@ -298,7 +301,8 @@ typedef struct sisic_unet_config {
     int up_attn[8];                  /* 1 = AttnUpBlock2D   */
     int norm_groups;
     float norm_eps;
-    int head_dim;
+    int head_dim;                    /* 8, 32 or 64; every width that carries attention (down block i, up block
+                                        n_blocks-1-i, the mid block) a multiple of it; at 8: every width */
     int n_freqs;                     /* block_out_channels[0] / 2 */
     const float* freqs;              /* host [n_freqs]: sinusoid frequencies (fp32, copied) */
 } sisic_unet_config;
@@ -670,7 +674,12 @@ int64_t sisic_unet_train_steps(const sisic_unet*);
  * Synchronises the stream: the scratch is freed before the call returns.                                               */
 int sisic_conv2d_wgrad(sisic_ctx*, const sisic_conv_args* fwd_args, const float* dy, float* dw, void* stream);
 /* attention backward: dqkv [B,3C,N] from qkv, the forward output o [B,C,N] and its gradient dO.  (o must be a valid
- * pointer but is not read: D_i = dO_i . o_i is formed from the recomputed probabilities)          */
+ * pointer but is not read: D_i = dO_i . o_i is formed from the recomputed probabilities)
+ * head_dim 8: one workgroup per head with the head's rows in LDS, at most 1170 tokens.  head_dim 32 and 64: tiled over
+ * keys and queries (two launches), at most 65536 tokens; the row statistics between the two launches live in a scratch
+ * buffer of the context, one per stream: the first call on a stream at a larger B * heads * N allocates it and waits for
+ * the stream once, later calls neither allocate nor wait.  More tokens, another head_dim or a C that is no multiple of
+ * it: SISIC_EINVAL before any launch.  No atomics: two calls give equal bits.                                           */
 int sisic_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                         int head_dim, void* stream);
 /* GroupNorm(+SiLU) backward: a = act(GroupNorm(x)); given da, ADDS dx to dx_accum and writes dgamma, dbeta.

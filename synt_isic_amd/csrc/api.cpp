@@ -106,6 +106,8 @@ int sisic_destroy(sisic_ctx* ctx) {
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     for (auto& kv : ctx->splitk)
         if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : ctx->attn_rows)
+        if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& it : ctx->bf3_items) {
         if (it.fill_done) (void)hipEventDestroy(it.fill_done);
         if (it.tab) (void)hipFree(it.tab);

@@ -1,4 +1,5 @@
 // attention.hip -- multi-head self-attention core for 32 heads x d=8 (NCHW token layout).
+// (32 and 64 channels per head: attention_wide.hip; launch_attention below dispatches on head_dim.)
 //
 // Replaces scaled_dot_product_attention inside diffusers' Attention block as configured by
 // the reference (attention_head_dim=8).  The q/k/v and output
@@ -242,7 +243,8 @@ attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int C, 
 
 int launch_attention(sisic_ctx* ctx, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s) {
     SISIC_REQUIRE(qkv && out, "attention: null tensor");
-    SISIC_REQUIRE(head_dim == ATT_D, "attention: head_dim %d unsupported (the reference uses 8)", head_dim);
+    if (head_dim == 32 || head_dim == 64) return launch_attention_wide(ctx, qkv, out, B, C, N, head_dim, s);
+    SISIC_REQUIRE(head_dim == ATT_D, "attention: head_dim %d unsupported (8, 32 and 64 have kernels)", head_dim);
     SISIC_REQUIRE(B > 0 && N > 0 && C > 0 && C % head_dim == 0, "attention: bad shape B=%d C=%d N=%d", B, C, N);
     const int heads = C / head_dim;
     // two query blocks per wave where that still leaves every CU four workgroups (SISIC_ATT_QB=1|2 forces one form: same bits)

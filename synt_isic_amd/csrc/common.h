@@ -73,6 +73,10 @@ struct sisic_ctx {
     struct SplitK { float* p = nullptr; size_t floats = 0; };
     std::map<hipStream_t, SplitK> splitk;
     std::mutex splitk_mutex;
+    // row statistics (m_i, 1/l_i, D_i) that the tiled attention backward pass (attention_wide.hip) hands from its query-owned
+    // kernel to its key-owned kernel: one buffer per stream, grown on demand, for the same reason
+    std::map<hipStream_t, SplitK> attn_rows;
+    std::mutex attn_rows_mutex;
     // item tables of the bf16x3 Winograd kernel (conv_winograd_bf3.inc): one per launch geometry, filled on the device the
     // first time the geometry is met, never moved or freed before the context (captured graphs hold their addresses)
     // (fill_done: recorded behind the fill; until it has passed, only launches on the filling stream use the table)
@@ -196,6 +200,10 @@ int launch_gn_stats(sisic_ctx*, const float* in0, int c0, const float* in1, int 
                     float eps, const float* gamma, const float* beta, float* scale, float* shift, hipStream_t s,
                     float* mean_rstd = nullptr);
 int launch_attention(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s);
+// head_dim 32 and 64 (attention_wide.hip); launch_attention and launch_attention_bwd dispatch to these
+int launch_attention_wide(sisic_ctx*, const float* qkv, float* out, int B, int C, int N, int head_dim, hipStream_t s);
+int launch_attention_bwd_wide(sisic_ctx*, const float* qkv, const float* dO, float* dqkv, int B, int C, int N, int head_dim,
+                              hipStream_t s);
 // The scheduler-step rules of the sampling loop (elementwise.hip; sisic.h SISIC_RULE_*): the row of a step is
 // {sb, sa, c2, c3, sigma} with (c2, c3) = DDPM (c0, c1) or DDIM (c_prev, c_dir).  flags: STEP_FLAG_CLIPPED_OUTPUT (DDIM only),
 // and under every rule the prediction type in its private bits (below).

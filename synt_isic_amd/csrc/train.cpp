@@ -327,9 +327,10 @@ int require_train(sisic_unet* u, const char* what) {
     return SISIC_OK;
 }
 
-// The backward pass keeps an attention block's whole key/value rows in LDS (launch_attention_bwd): a resolution whose
-// attention levels have more tokens than that records a forward that could never be back-propagated.  Refused before anything
-// is recorded, so that no backward pass half-accumulates gradients before it fails.
+// At head_dim 8 the backward pass keeps an attention block's whole key/value rows in LDS (launch_attention_bwd); at 32 and 64 it
+// is tiled and bounded by ATTN_BWD_TILED_MAX_TOKENS (train.h).  A resolution whose attention levels have more tokens than the
+// model's head dimension takes records a forward that could never be back-propagated.  Refused before anything is recorded, so
+// that no backward pass half-accumulates gradients before it fails.
 int check_trainable_resolution(sisic_unet* u, int H, int W) {
     const sisic_unet_config& cfg = u->cfg;
     const int n = cfg.n_blocks;
@@ -337,9 +338,10 @@ int check_trainable_resolution(sisic_unet* u, int H, int W) {
         // down block lvl, up block n-1-lvl and (at the lowest level) the mid block run at H >> lvl x W >> lvl
         if (!(cfg.down_attn[lvl] || cfg.up_attn[n - 1 - lvl] || lvl == n - 1)) continue;
         const int h = H >> lvl, w = W >> lvl;
-        SISIC_REQUIRE((int64_t)h * w <= ATTN_BWD_MAX_TOKENS,
+        const int max_tokens = attn_bwd_max_tokens(cfg.head_dim);     // 1170 at head_dim 8 (LDS), 65536 at 32 and 64 (tiled)
+        SISIC_REQUIRE((int64_t)h * w <= max_tokens,
                       "train_forward: %dx%d cannot be trained: its %dx%d attention level has %lld tokens, the attention backward "
-                      "pass takes at most %d", H, W, h, w, (long long)h * w, ATTN_BWD_MAX_TOKENS);
+                      "pass takes at most %d", H, W, h, w, (long long)h * w, max_tokens);
     }
     return SISIC_OK;
 }

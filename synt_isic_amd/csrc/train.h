@@ -64,12 +64,19 @@ int launch_dropout_bwd(sisic_ctx*, float* d, int B, int C, int HW, uint64_t seed
 int launch_accum_split(sisic_ctx*, const float* da, int B, int C, int HW, float* g0, int c0, float* g1, int c1, hipStream_t s);
 int launch_accum_pool2(sisic_ctx*, const float* da, int planes, int H, int W, float* g, hipStream_t s);
 int launch_add_inplace(sisic_ctx*, float* dst, const float* src, size_t n, hipStream_t s);
-// attention_bwd keeps a head's whole key/value rows in LDS, 32 + 3 floats per token within 160 KB: the most tokens it
-// accepts.  launch_attention_bwd refuses more, and sisic_unet_train_forward refuses a resolution whose attention levels have more.
+// head_dim 8: attention_bwd keeps a head's whole key/value rows in LDS, 32 + 3 floats per token within 160 KB: the most tokens
+// it accepts.  launch_attention_bwd refuses more, and sisic_unet_train_forward refuses a resolution whose attention levels have more.
 constexpr int ATTN_BWD_LDS_BYTES = 160 * 1024;
 constexpr int ATTN_BWD_MAX_TOKENS = 1170;
 static_assert(ATTN_BWD_MAX_TOKENS * 35 * 4 <= ATTN_BWD_LDS_BYTES && (ATTN_BWD_MAX_TOKENS + 1) * 35 * 4 > ATTN_BWD_LDS_BYTES,
               "ATTN_BWD_MAX_TOKENS is the most tokens whose key/value rows fit the LDS");
+// head_dim 32 and 64: the backward pass is tiled over keys and queries (attention_wide.hip) and holds 64 tokens of a head in
+// LDS at a time, so the LDS sets no limit.  What remains is the kernels' 32-bit token arithmetic and the row-statistics scratch
+// (3 floats per sample, head and token): 65536 tokens, a 256 x 256 attention plane, is the most launch_attention_bwd accepts at
+// these widths.  (The pass is quadratic in the tokens: at the bound one head is 2 * 10^12 multiply-adds.)
+constexpr int ATTN_BWD_TILED_MAX_TOKENS = 65536;
+// the bound of a model's head dimension (check_trainable_resolution)
+inline int attn_bwd_max_tokens(int head_dim) { return head_dim == 8 ? ATTN_BWD_MAX_TOKENS : ATTN_BWD_TILED_MAX_TOKENS; }
 int launch_attention_bwd(sisic_ctx*, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                          int head_dim, hipStream_t s);
 int launch_linear_wgrad(sisic_ctx*, const float* dy, int ld, const float* x, int B, int R, int K, float* dW, hipStream_t s);

@@ -973,7 +973,11 @@ attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
 
 int launch_attention_bwd(sisic_ctx* ctx, const float* qkv, const float* o, const float* dO, float* dqkv, int B, int C, int N,
                          int head_dim, hipStream_t s) {
-    SISIC_REQUIRE(qkv && o && dO && dqkv && head_dim == 8 && C % 8 == 0 && N >= 0, "attention_bwd: bad arguments");
+    SISIC_REQUIRE(qkv && o && dO && dqkv, "attention_bwd: null tensor");
+    if (head_dim == 32 || head_dim == 64) return launch_attention_bwd_wide(ctx, qkv, dO, dqkv, B, C, N, head_dim, s);   // `o` is not read
+    SISIC_REQUIRE(head_dim == 8, "attention_bwd: head_dim %d unsupported (8, 32 and 64 have kernels)", head_dim);
+    // (below: d = 8 only, where 8^-1/2 is the literal scale of the launch)
+    SISIC_REQUIRE(C % 8 == 0 && N >= 0, "attention_bwd: bad arguments");
     SISIC_REQUIRE(N <= ATTN_BWD_MAX_TOKENS, "attention_bwd: %d tokens do not fit the LDS (max %d)", N, ATTN_BWD_MAX_TOKENS);
     const size_t lds = ((size_t)N * 32 + 3 * (size_t)N) * sizeof(float);
     static std::atomic<uint64_t> lds_opt_in{0};

@@ -703,12 +703,20 @@ int sisic_unet_create_cond(sisic_ctx* ctx, const sisic_unet_config* cfg, int num
     SISIC_REQUIRE(cfg->n_blocks >= 1 && cfg->n_blocks <= 8, "unet_create: n_blocks %d", cfg->n_blocks);
     SISIC_REQUIRE(cfg->layers_per_block >= 1, "unet_create: layers_per_block");
     SISIC_REQUIRE(cfg->in_channels > 0 && cfg->out_channels > 0, "unet_create: channels");
-    SISIC_REQUIRE(cfg->norm_groups > 0 && cfg->head_dim == 8, "unet_create: head_dim must be 8, groups > 0");
+    SISIC_REQUIRE(cfg->norm_groups > 0, "unet_create: norm_groups %d", cfg->norm_groups);
+    SISIC_REQUIRE(cfg->head_dim == 8 || cfg->head_dim == 32 || cfg->head_dim == 64,
+                  "unet_create: head_dim %d is not one of 8, 32, 64 (the widths the attention kernels are built for)", cfg->head_dim);
     SISIC_REQUIRE(cfg->freqs && cfg->n_freqs * 2 == cfg->block_out_channels[0], "unet_create: freqs table must hold block_out_channels[0]/2 entries");
-    for (int i = 0; i < cfg->n_blocks; ++i)
-        SISIC_REQUIRE(cfg->block_out_channels[i] > 0 && cfg->block_out_channels[i] % cfg->norm_groups == 0 &&
-                          cfg->block_out_channels[i] % cfg->head_dim == 0,
+    for (int i = 0; i < cfg->n_blocks; ++i) {
+        SISIC_REQUIRE(cfg->block_out_channels[i] > 0 && cfg->block_out_channels[i] % cfg->norm_groups == 0,
                       "unet_create: block_out_channels[%d]=%d", i, cfg->block_out_channels[i]);
+        // (head_dim 8 keeps its rule for every width; at 32 and 64 only the widths that carry attention: down block i, up block
+        //  n-1-i and, at the lowest level, the mid block)
+        const bool attn = cfg->down_attn[i] || cfg->up_attn[cfg->n_blocks - 1 - i] || i == cfg->n_blocks - 1;
+        SISIC_REQUIRE((cfg->head_dim != 8 && !attn) || cfg->block_out_channels[i] % cfg->head_dim == 0,
+                      "unet_create: block_out_channels[%d]=%d is no multiple of head_dim %d", i, cfg->block_out_channels[i],
+                      cfg->head_dim);
+    }
     auto* u = new sisic_unet();
     u->ctx = ctx;
     u->cfg = *cfg;

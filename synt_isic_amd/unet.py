@@ -81,8 +81,16 @@ class HipUNet2DModel:
                                  attention_head_dim=attention_head_dim, num_class_embeds=num_class_embeds, dropout=dropout,
                                  prediction_type=prediction_type)
         self.config.validate()
-        if attention_head_dim != 8:
-            raise NotImplementedError("attention_head_dim must be 8 (the HIP attention kernel is built for d=8)")
+        if isinstance(attention_head_dim, bool) or attention_head_dim not in (8, 32, 64):
+            raise NotImplementedError(f"attention_head_dim must be 8, 32 or 64 (the widths the HIP attention kernels are built "
+                                      f"for), got {attention_head_dim!r}")
+        cfg = self.config
+        n = len(cfg.block_out_channels)
+        for i, ch in enumerate(cfg.block_out_channels):      # down block i, up block n-1-i and the mid block share a width
+            if attention_head_dim != 8 and (cfg.down_has_attn[i] or cfg.up_has_attn[n - 1 - i] or i == n - 1) \
+                    and ch % attention_head_dim:      # (8: the library's own check, as before)
+                raise ValueError(f"block_out_channels[{i}] = {ch} carries attention and is no multiple of "
+                                 f"attention_head_dim = {attention_head_dim}")
         self._spec = unet_param_spec(self.config)
         self._params: "OrderedDict[str, torch.Tensor]" = OrderedDict()   # on self._device
         self._device = torch.device("cpu")
