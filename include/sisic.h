@@ -689,7 +689,7 @@ int sisic_groupnorm_bwd(sisic_ctx*, const float* da, const float* x, int B, int 
                         const float* gamma, const float* beta, int silu, float* dx_accum, float* dgamma, float* dbeta,
                         void* stream);
 
-/* ---- ResNet18 classifier (xai/XAI.py:357-471, forward only) ---------------------------- */
+/* ---- ResNet18 classifier (xai/XAI.py:357-471): forward, explanations, training with frozen BatchNorm ---- */
 /* torchvision resnet18 with fc -> num_classes, eval mode (BatchNorm folded at load).  The state dict
  * uses the reference's key names, prefixed "model." (XAI.py:389), float tensors only: conv/fc weights
  * and biases, BatchNorm weight/bias/running_mean/running_var (num_batches_tracked is not a float tensor
@@ -734,6 +734,62 @@ int sisic_resnet_input_gradient(sisic_resnet*, const float* x, int B, int H, int
  * cam: dev [B,224,224]; logits_out: dev [B,n_classes] or NULL.                                            */
 int sisic_resnet_gradcam(sisic_resnet*, const float* x, int B, int H, int W, int target,
                          float* cam, float* logits_out, void* stream);
+
+/* ---- training the classifier with BatchNorm frozen ("classifier training") --------------------------
+ * torchvision.ops.FrozenBatchNorm2d semantics: running statistics, gamma and beta stay the constants they were loaded as, so
+ * the training forward IS the folded forward above, bit for bit, and a trained model needs no other inference path.
+ * Trainable tensors (22): the 20 convolution weights, fc.weight and fc.bias.  BatchNorm in batch-statistics mode is not
+ * implemented.
+ *
+ * train_begin (after sisic_resnet_load) allocates arenas for the un-folded parameters, their gradients and the two Adam
+ * moments, and the scratch of the K-split weight gradients; train_end frees them and leaves the handle as
+ * sisic_resnet_load of the current state dict would leave it.  A reload (sisic_resnet_load) ends training as well.
+ *
+ * Both launching entries take one argument struct that carries the stream as a field:
+ *   x              dev [B,3,H,W]: preprocess = 1 the sampler's latents in [-1,1] (H, W <= 224), 0 the normalised network input;
+ *                  the stem's input (224x224, or HxW) must have even sizes from 8, and so must every plane a stride-2 layer reads
+ *   labels         HOST int64 [B], each in [0, num_classes): checked before anything is launched
+ *   class_weights  HOST float [num_classes] or NULL: torch.nn.functional.cross_entropy(weight = w, reduction = "mean"),
+ *                  i.e. the weighted sum divided by the sum of the picked weights
+ *   logits_out     dev [B,num_classes] or NULL: the forward's logits, the bits of sisic_resnet_forward
+ *   loss           out (loss_backward): the loss; found_inf, grad_norm: out (optimizer_step)
+ *   lr .. eps      torch.optim.Adam's constants, doubles as there; max_grad_norm: clip_grad_norm_'s max_norm, <= 0 or +inf: the
+ *                  norm is reported, nothing is clipped
+ * loss_backward: forward with the activations kept, cross-entropy head, the data-gradient walk of
+ * sisic_resnet_input_gradient down to the stem's output, and at every convolution its weight gradient.  It OVERWRITES the
+ * gradient arena and waits for the stream once (the loss is returned to the host).  No atomics: two calls from one state
+ * give equal bits in every gradient, and an element's summation order is a function of (B, H, W) alone.
+ * optimizer_step: the statistics pass of sisic_grad_stats over the gradient arena, one 12-byte read-back (one
+ * synchronisation), then -- unless a gradient is not finite: found_inf = 1, nothing moves -- the Adam pass of sisic_adam_ema
+ * on g * clip_coef, and every folded, transposed, packed and Winograd form rebuilt on the device in the buffers the handle
+ * owns (the arithmetic of the load path: (float)((double)w * gamma / sqrt(var + eps))).  Nothing is uploaded or allocated.
+ * Without train_begin both return SISIC_ESTATE.                                                                          */
+typedef struct sisic_resnet_train_args {
+    const float*   x;
+    const int64_t* labels;
+    const float*   class_weights;
+    float*         logits_out;
+    void*          stream;
+    double         lr, beta1, beta2, eps;
+    int            B, H, W, preprocess;
+    float          max_grad_norm;
+    float          loss;
+    float          grad_norm;
+    int            found_inf;
+} sisic_resnet_train_args;                 /* 104 bytes, no padding */
+int sisic_resnet_train_begin(sisic_resnet*);
+int sisic_resnet_train_end(sisic_resnet*);
+int sisic_resnet_loss_backward(sisic_resnet*, sisic_resnet_train_args* args);
+int sisic_resnet_optimizer_step(sisic_resnet*, sisic_resnet_train_args* args);
+int sisic_resnet_zero_grad(sisic_resnet*);                    /* zero-fills the gradient arena; synchronises the device */
+int64_t sisic_resnet_train_steps(const sisic_resnet*);        /* optimizer steps that moved the weights; 0 outside training */
+/* Copy one tensor (index as in sisic_resnet_tensor_name) to / from the host: what = 0 parameter, 1 gradient, 2 Adam first
+ * moment, 3 Adam second moment.  Parameters can be read at any time after a load (during training: the trained values);
+ * what = 1..3 need train_begin and one of the 22 trainable tensors (a BatchNorm tensor has no gradient: SISIC_EINVAL).
+ * Writing parameters is refused: their folded and packed forms must follow them, sisic_resnet_load sets them.
+ * Both synchronise the device.                                                                                            */
+int sisic_resnet_read(sisic_resnet*, int what, int index, float* host_out, int64_t numel);
+int sisic_resnet_write(sisic_resnet*, int what, int index, const float* host_in, int64_t numel);
 
 /* Bytes of activation workspace the handle currently keeps resident (its pool).  The pool is sized for the last
  * (B,H,W) seen and released when the shape changes, so this does not grow with the history of batch sizes

@@ -101,6 +101,14 @@ class GradStats(C.Structure):
     _fields_ = [("total_norm", C.c_float), ("clip_coef", C.c_float), ("found_inf", C.c_int)]
 
 
+class ResnetTrainArgs(C.Structure):
+    """struct sisic_resnet_train_args (104 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("labels", c_int64_p), ("class_weights", c_float_p), ("logits_out", C.c_void_p),
+                ("stream", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("preprocess", C.c_int), ("max_grad_norm", C.c_float),
+                ("loss", C.c_float), ("grad_norm", C.c_float), ("found_inf", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -263,6 +271,14 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "sisic_resnet_gradcam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "sisic_resnet_train_begin": (C.c_int, [C.c_void_p]),
+    "sisic_resnet_train_end": (C.c_int, [C.c_void_p]),
+    "sisic_resnet_loss_backward": (C.c_int, [C.c_void_p, C.POINTER(ResnetTrainArgs)]),
+    "sisic_resnet_optimizer_step": (C.c_int, [C.c_void_p, C.POINTER(ResnetTrainArgs)]),
+    "sisic_resnet_zero_grad": (C.c_int, [C.c_void_p]),
+    "sisic_resnet_train_steps": (C.c_int64, [C.c_void_p]),
+    "sisic_resnet_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
+    "sisic_resnet_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sisic_resnet_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sisic_unet_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sisic_class_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

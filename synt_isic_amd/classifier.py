@@ -1,4 +1,5 @@
-"""HipMelanomaClassifier -- drop-in for ``MelanomaClassifierAdaptive`` (xai/XAI.py:357-471), forward only.
+"""HipMelanomaClassifier -- drop-in for ``MelanomaClassifierAdaptive`` (xai/XAI.py:357-471): forward, explanations, and
+training with BatchNorm frozen (``loss_backward`` here, ``HipClassifierAdam`` / ``train_classifier`` in train.py).
 
 The reference wraps ``torchvision.models.resnet18`` (fc -> num_classes) and feeds it diffusion latents in
 [-1,1] through ``preprocess_for_classifier`` (clamp, bilinear resize to 224x224, ImageNet normalisation).
@@ -36,6 +37,8 @@ class HipMelanomaClassifier:
         self._device = torch.device("cpu")
         self._handle: Optional[C.c_void_p] = None
         self._uploaded = False
+        self._params_stale = False      # an optimizer step moved the library's weights: _params follows on the next read
+        self._trainer = None            # the train.HipClassifierAdam that holds the library's training arenas, if any
         self.training = True
 
     # ---- module surface -------------------------------------------------------------------------
@@ -49,19 +52,99 @@ class HipMelanomaClassifier:
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("forward only: training the classifier is out of scope")
+            raise NotImplementedError("BatchNorm in batch-statistics mode is not implemented: the classifier trains with "
+                                      "BatchNorm frozen, through train.HipClassifierAdam and loss_backward, in eval mode")
         return self.eval()
 
     def parameters(self) -> Iterator[torch.Tensor]:
+        self._sync_params()
         return (v for k, v in self._params.items() if "running_" not in k)
 
     def state_dict(self):
+        """the weights as they stand: after ``HipClassifierAdam.step`` the trained tensors (read back from the library once),
+        the BatchNorm tensors unchanged"""
+        self._sync_params()
         return OrderedDict(self._params)
+
+    # ---- training with frozen BatchNorm (train.HipClassifierAdam owns train_begin / train_end) ---------------------
+    def trainable_names(self):
+        """the 22 tensors an optimizer step moves: the 20 convolution weights, fc.weight and fc.bias"""
+        return [n for n in self._spec if n.endswith("conv1.weight") or n.endswith("conv2.weight")
+                or n.endswith("downsample.0.weight") or n.startswith("model.fc.")]
+
+    def _tensor_index(self) -> Dict[str, int]:
+        lib, h = _lib.load(), self.handle
+        return {lib.sisic_resnet_tensor_name(h, i).decode(): i for i in range(lib.sisic_resnet_num_tensors(h))}
+
+    def _sync_params(self) -> None:
+        if not self._params_stale:
+            return
+        self._params_stale = False                       # (before the reads: read_tensor goes through .handle only)
+        for name in self.trainable_names():
+            self._params[name] = self.read_tensor(0, name).to(self._device)
+
+    def read_tensor(self, what: int, name: str) -> torch.Tensor:
+        """one tensor of the library's arenas on the CPU (sisic_resnet_read): what = 0 parameter, 1 gradient, 2 / 3 Adam m / v"""
+        out = torch.empty(self._spec[name], dtype=torch.float32)
+        check(_lib.load().sisic_resnet_read(self.handle, int(what), self._tensor_index()[name],
+                                            C.cast(out.data_ptr(), _lib.c_float_p), out.numel()))
+        return out
+
+    def write_tensor(self, what: int, name: str, value: torch.Tensor) -> None:
+        """the counterpart (sisic_resnet_write): gradients and moments only, parameters are set by load_state_dict"""
+        v = value.detach().to("cpu", torch.float32).contiguous()
+        if tuple(v.shape) != tuple(self._spec[name]):
+            raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {tuple(self._spec[name])}")
+        check(_lib.load().sisic_resnet_write(self.handle, int(what), self._tensor_index()[name],
+                                             C.cast(v.data_ptr(), _lib.c_float_p), v.numel()))
+
+    def grads(self) -> "OrderedDict[str, torch.Tensor]":
+        """the gradients of the last ``loss_backward`` (or ``set_grads``), CPU tensors under the state-dict names"""
+        return OrderedDict((n, self.read_tensor(1, n)) for n in self.trainable_names())
+
+    def set_grads(self, grads: Dict[str, torch.Tensor]) -> None:
+        """gradients of the caller's choosing (optimizer parity tests): every trainable tensor must be given"""
+        names = self.trainable_names()
+        missing = [n for n in names if n not in grads]
+        if missing or len(grads) != len(names):
+            raise ValueError(f"set_grads needs exactly the {len(names)} trainable tensors; missing {missing[:3]}")
+        for n in names:
+            self.write_tensor(1, n, grads[n])
+
+    def loss_backward(self, images: torch.Tensor, labels, class_weights=None, preprocessed: bool = False):
+        """``loss = F.cross_entropy(model(images), labels, weight=class_weights); loss.backward()`` with BatchNorm frozen, in one
+        library call (sisic_resnet_loss_backward): returns ``(loss, logits)``, the loss a float, the logits the forward's own
+        bits.  The gradients replace those of the previous call (``grads()``).  Needs a ``train.HipClassifierAdam``."""
+        h = self.handle
+        if images.device != self._device:
+            images = images.to(self._device)
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"classifier input must be [B,3,H,W], got {tuple(images.shape)}")
+        x = images.detach().to(torch.float32).contiguous()
+        B, _, H, W = x.shape
+        lab = torch.as_tensor(labels).detach().to("cpu", torch.int64).contiguous()
+        if lab.shape != (B,):
+            raise ValueError(f"labels must be [{B}], got {tuple(lab.shape)}")
+        cw = None
+        if class_weights is not None:
+            cw = torch.as_tensor(class_weights).detach().to("cpu", torch.float32).contiguous()
+            if cw.shape != (self.num_classes,):
+                raise ValueError(f"class_weights must be [{self.num_classes}], got {tuple(cw.shape)}")
+        logits = ops.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
+        a = _lib.ResnetTrainArgs()
+        a.x, a.logits_out = x.data_ptr(), logits.data_ptr()
+        a.labels = C.cast(lab.data_ptr(), _lib.c_int64_p)
+        a.class_weights = C.cast(cw.data_ptr(), _lib.c_float_p) if cw is not None else None
+        a.B, a.H, a.W, a.preprocess = B, H, W, 0 if preprocessed else 1
+        a.stream = torch.cuda.current_stream(x.device).cuda_stream
+        check(_lib.load().sisic_resnet_loss_backward(h, C.byref(a)))
+        return float(a.loss), logits
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         """strict=False keeps only keys whose name AND shape match, like load_classifier_with_fallback
         (XAI.py:518-527).  Integer buffers (num_batches_tracked) are ignored either way."""
         sd = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
+        self._sync_params()
         cur = dict(self._params)
         new = OrderedDict()
         for name, shape in self._spec.items():
@@ -93,6 +176,7 @@ class HipMelanomaClassifier:
             device = torch.device("cuda", torch.cuda.current_device())
         if device == self._device:
             return self
+        self._sync_params()
         self._release()
         self._params = OrderedDict((n, v.to(device)) for n, v in self._params.items())
         self._device = device
@@ -115,10 +199,18 @@ class HipMelanomaClassifier:
         names = (C.c_char_p * n)(*[k.encode() for k, _ in host])
         ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in host])
         numels = (C.c_int64 * n)(*[t.numel() for _, t in host])
-        check(lib.sisic_resnet_load(self._handle, n, names, ptrs, numels))
+        check(lib.sisic_resnet_load(self._handle, n, names, ptrs, numels))       # (a reload ends training in the library)
         self._uploaded = True
+        self._params_stale = False
+        self._drop_trainer()
+
+    def _drop_trainer(self) -> None:
+        if self._trainer is not None:
+            self._trainer._active = False
+            self._trainer = None
 
     def _release(self) -> None:
+        self._drop_trainer()
         if self._handle is not None:
             _lib.load().sisic_resnet_destroy(self._handle)
             self._handle = None

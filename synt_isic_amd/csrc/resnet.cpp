@@ -5,12 +5,17 @@
 //     w' = w * gamma / sqrt(var + eps),   b' = beta - mean * gamma / sqrt(var + eps)
 // so every conv+BN(+ReLU)(+identity) is ONE launch of conv_mfma_kernel with its bias / residual / ReLU
 // epilogue.  The pre-processing of XAI.py:399-431 is one fused kernel (classifier.hip).
+//
+// Training (the second half of this file) keeps BatchNorm frozen: the training forward is this forward, the backward pass is
+// the data-gradient walk of sisic_resnet_input_gradient with a weight gradient issued at every convolution, and after the
+// Adam step the folded filters are derived again on the device from the un-folded parameters.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
 
 #include "common.h"
+#include "train.h"
 #include "workspace.h"
 
 using namespace sisic;
@@ -36,6 +41,28 @@ struct Block {
     FoldedConv conv1, conv2, down;   // down.k == 0 when the shortcut is the identity
 };
 
+// sisic_resnet_train_begin .. train_end: the 22 trainable tensors un-folded, side by side in one arena (each at a multiple of
+// four floats; the padding stays zero in all four arenas), so that the statistics and the Adam pass are one launch each
+struct ResnetTrain {
+    std::vector<int64_t> off;        // arena offset of tensor i (sisic_resnet_tensor_name order), -1: frozen (BatchNorm)
+    size_t floats = 0;
+    float* param = nullptr;
+    float* grad = nullptr;
+    float* adam_m = nullptr;
+    float* adam_v = nullptr;
+    float* part = nullptr;           // K-split partial slabs of the weight gradients
+    size_t part_floats = 0;
+    void* stats = nullptr;           // GradStats record, the loss (at byte 12), then the statistics scratch (at byte 16)
+    // every packed and Winograd form of the 19 filters behind the stem, rebuilt after a step by two batched launches
+    // (repack.hip: the jobs carry the arithmetic of launch_conv_pack / launch_winograd_pack): the first layouts from raw and
+    // raw_t, then the Winograd layouts that are derived from the first one
+    void* repack_dev[2] = {nullptr, nullptr};
+    int repack_jobs[2] = {0, 0}, repack_blocks[2] = {0, 0};
+    std::vector<int> labels_host;    // staging of the labels and the class weights of a call
+    std::vector<float> cw_host;
+    int64_t step = 0;
+};
+
 }  // namespace
 
 struct sisic_resnet {
@@ -54,6 +81,7 @@ struct sisic_resnet {
     Pool pool;
     int ws_B = 0, ws_H = 0, ws_W = 0;       // shape the pooled blocks were sized for (see workspace_for)
     bool loaded = false;
+    ResnetTrain* train = nullptr;
 
     int add(const std::string& n, int64_t numel) {
         index[n] = (int)names.size();
@@ -221,6 +249,9 @@ struct Trunk {
     bool preprocess = true;
     float* stem_out = nullptr;   // stop after the stem, which writes here (sisic_resnet_stem)
     bool keep = false;           // keep c1, the max-pool output and every block's t1 and output (the input gradient reads them)
+    bool keep_pre = false;       // keep the pre-processed input as well (the stem's weight gradient reads it)
+    float* pre = nullptr;        // keep_pre with preprocess: the stem's input [B, 3, 224, 224]
+    const char* who = "resnet_input_gradient";
     bool split_last = false;     // last block: bn2(conv2(.)) alone into ylast, then relu(. + identity) (Grad-CAM reads ylast)
     float* logits = nullptr;     // where the logits go; nullptr: into a block of the scope, returned here
     struct Saved { float* t1; float* out; int h, w, bh, bw; };
@@ -248,10 +279,11 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
     t.c1 = t.stem_out;
     if (!t.c1) SISIC_TRY(ws.get((size_t)B * 64 * t.c1h * t.c1w, &t.c1));
     SISIC_TRY(run_conv(r, r->stem, cur, B, h, w, nullptr, true, t.c1, s));
-    if (pre) ws.put(pre);
+    if (pre && t.keep_pre) t.pre = pre;
+    else if (pre) ws.put(pre);
     if (t.stem_out) return SISIC_OK;
     h = t.c1h; w = t.c1w;
-    if (t.keep) SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "resnet_input_gradient: odd feature map");
+    if (t.keep) SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "%s: odd feature map", t.who);
     const int mh = out_dim(h, 3, 2), mw = out_dim(w, 3, 2);
     SISIC_TRY(ws.get((size_t)B * 64 * mh * mw, &t.m));
     SISIC_TRY(launch_maxpool(r->ctx, t.c1, t.m, B, 64, h, w, s));
@@ -262,7 +294,7 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
         const bool split = t.split_last && &b == &r->blocks.back();
         const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
         if (t.keep)
-            SISIC_REQUIRE(b.conv1.stride == 1 || (h % 2 == 0 && w % 2 == 0), "resnet_input_gradient: odd feature map %dx%d", h, w);
+            SISIC_REQUIRE(b.conv1.stride == 1 || (h % 2 == 0 && w % 2 == 0), "%s: odd feature map %dx%d", t.who, h, w);
         float* t1 = nullptr;
         SISIC_TRY(ws.get((size_t)B * b.conv1.cout * bh * bw, &t1));
         SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
@@ -298,6 +330,17 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
     return SISIC_OK;
 }
 
+// the training arenas (the caller has synchronised the device)
+void train_free(sisic_resnet* r) {
+    ResnetTrain* tr = r->train;
+    if (!tr) return;
+    for (float* p : {tr->param, tr->grad, tr->adam_m, tr->adam_v, tr->part}) (void)hipFree(p);
+    (void)hipFree(tr->stats);
+    for (void* p : tr->repack_dev) (void)hipFree(p);
+    delete tr;
+    r->train = nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -315,6 +358,7 @@ int sisic_resnet_create(sisic_ctx* ctx, int num_classes, sisic_resnet** out) {
 int sisic_resnet_destroy(sisic_resnet* r) {
     if (!r) return SISIC_OK;
     (void)hipDeviceSynchronize();
+    train_free(r);
     for (auto p : r->owned) (void)hipFree(p);
     r->pool.release_all();
     delete r;
@@ -351,6 +395,7 @@ int sisic_resnet_load(sisic_resnet* r, int n, const char* const* names, const fl
         r->host[idx].assign(host_ptrs[i], host_ptrs[i] + numels[i]);
     }
     (void)hipDeviceSynchronize();
+    train_free(r);                            // a reload ends training: the arenas described the previous weights
     for (auto p : r->owned) (void)hipFree(p);
     r->owned.clear();
     r->loaded = false;
@@ -373,6 +418,10 @@ int sisic_resnet_randomize(sisic_resnet* r, uint64_t seed, uint32_t trial, float
     SISIC_REQUIRE(r, "resnet_randomize: null handle");
     if (!r->loaded) {
         set_error("resnet_randomize called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    if (r->train) {
+        set_error("resnet_randomize: the handle is training (sisic_resnet_train_end first)");
         return SISIC_ESTATE;
     }
     SISIC_HIP(hipSetDevice(r->ctx->device));
@@ -398,6 +447,10 @@ int sisic_resnet_restore(sisic_resnet* r, void* stream) {
     SISIC_REQUIRE(r, "resnet_restore: null handle");
     if (!r->loaded) {
         set_error("resnet_restore called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    if (r->train) {
+        set_error("resnet_restore: the handle is training (sisic_resnet_train_end first)");
         return SISIC_ESTATE;
     }
     SISIC_HIP(hipSetDevice(r->ctx->device));
@@ -553,6 +606,382 @@ int sisic_resnet_gradcam(sisic_resnet* r, const float* x, int B, int H, int W, i
     if (logits_out)
         SISIC_HIP(hipMemcpyAsync(logits_out, t.logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
     return launch_gradcam(r->ctx, t.ylast, t.act, r->d_fc_w, c2.bias, cam, B, c2.cout, t.h, t.w, S, target, s);
+}
+
+}  // extern "C"
+
+// ================================================================ training with frozen BatchNorm ====================
+namespace {
+
+constexpr int TRAIN_MAX_BATCH = 4096;            // fc_head_bwd_kernel keeps two floats per sample in LDS
+
+int require_train(const sisic_resnet* r, const char* who) {
+    SISIC_REQUIRE(r, "%s: null handle", who);
+    if (!r->loaded) {
+        set_error("%s called before sisic_resnet_load", who);
+        return SISIC_ESTATE;
+    }
+    if (!r->train) {
+        set_error("%s called without sisic_resnet_train_begin", who);
+        return SISIC_ESTATE;
+    }
+    return SISIC_OK;
+}
+
+template <class F>
+int for_each_conv(sisic_resnet* r, F&& f) {
+    SISIC_TRY(f(r->stem));
+    for (auto& b : r->blocks) {
+        SISIC_TRY(f(b.conv1));
+        SISIC_TRY(f(b.conv2));
+        if (b.down.k) SISIC_TRY(f(b.down));
+    }
+    return SISIC_OK;
+}
+
+// The weight gradient of convolution c (not the stem) from its input `in` [B, cin, h, w] and the gradient dy of its output.
+// A 1x1 stride-2 convolution reads the even pixels only: gathered into `even` [B, cin, (h+1)/2, (w+1)/2], its gradient is
+// the 1x1 stride-1 form.  Pointers may be NULL when only the scratch size is asked for.
+WgradArgs wgrad_args(const FoldedConv& c, const float* in, const float* even, int B, int h, int w, const float* dy, float* dw) {
+    WgradArgs a;
+    a.c0 = c.cin; a.B = B; a.Cout = c.cout; a.dy = dy; a.dw = dw;
+    if (c.k == 1 && c.stride == 2) {
+        a.in0 = even; a.Hin = (h - 1) / 2 + 1; a.Win = (w - 1) / 2 + 1; a.ksize = 1; a.stride = 1;
+    } else {
+        a.in0 = in; a.Hin = h; a.Win = w; a.ksize = c.k; a.stride = c.stride;
+    }
+    return a;
+}
+
+// every plane a stride-2 layer reads has even sizes (the zero-insertion form of its transposed convolution, the stem's weight
+// gradient): checked before anything is launched
+int check_train_geometry(int H, int W, int preprocess) {
+    int h = preprocess ? 224 : H, w = preprocess ? 224 : W;
+    SISIC_REQUIRE(!preprocess || (H <= 224 && W <= 224), "resnet_loss_backward: input %dx%d larger than the classifier's 224x224", H, W);
+    SISIC_REQUIRE(h >= 8 && w >= 8 && h % 2 == 0 && w % 2 == 0, "resnet_loss_backward: odd feature map: the stem reads %dx%d (even sizes from 8)", h, w);
+    h /= 2; w /= 2;                                       // stem
+    SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "resnet_loss_backward: odd feature map %dx%d before the max-pool", h, w);
+    h /= 2; w /= 2;                                       // max-pool
+    for (int l = 1; l < 4; ++l) {
+        SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "resnet_loss_backward: odd feature map %dx%d before layer%d", h, w, l + 1);
+        h /= 2; w /= 2;
+    }
+    return SISIC_OK;
+}
+
+GradStats* stats_record(ResnetTrain* tr) { return static_cast<GradStats*>(tr->stats); }
+float* loss_slot(ResnetTrain* tr) { return reinterpret_cast<float*>(static_cast<char*>(tr->stats) + 12); }
+void* stats_scratch(ResnetTrain* tr) { return static_cast<char*>(tr->stats) + 16; }
+
+}  // namespace
+
+extern "C" {
+
+int sisic_resnet_train_begin(sisic_resnet* r) {
+    SISIC_REQUIRE(r, "resnet_train_begin: null handle");
+    if (!r->loaded) {
+        set_error("resnet_train_begin called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    if (r->train) {
+        set_error("resnet_train_begin: the handle is training already");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    auto* tr = new ResnetTrain();
+    r->train = tr;                               // (freed by train_end, a reload or destroy, also after an error below)
+    tr->off.assign(r->names.size(), -1);
+    auto place = [&](int idx) {
+        tr->off[idx] = (int64_t)tr->floats;
+        tr->floats += (size_t)round_up((int)r->numels[idx], 4);
+    };
+    std::vector<char> trainable(r->names.size(), 0);
+    for_each_conv(r, [&](FoldedConv& c) { trainable[c.w_idx] = 1; return SISIC_OK; });
+    trainable[r->fc_w] = trainable[r->fc_b] = 1;
+    for (int i = 0; i < (int)r->names.size(); ++i)
+        if (trainable[i]) place(i);
+    // the partial slabs: the most any layer asks for at any shape (its K-split is capped by the layer's tile count)
+    tr->part_floats = stem_wgrad_scratch_floats();
+    {
+        int h = 56;                              // layer1's plane at the classifier's 224x224; larger inputs reach the same caps
+        for (const Block& b : r->blocks) {
+            const int bh = out_dim(h, 3, b.conv1.stride);
+            tr->part_floats = std::max(tr->part_floats, conv_wgrad_scratch_floats(wgrad_args(b.conv1, nullptr, nullptr, TRAIN_MAX_BATCH, h, h, nullptr, nullptr)));
+            tr->part_floats = std::max(tr->part_floats, conv_wgrad_scratch_floats(wgrad_args(b.conv2, nullptr, nullptr, TRAIN_MAX_BATCH, bh, bh, nullptr, nullptr)));
+            if (b.down.k)
+                tr->part_floats = std::max(tr->part_floats, conv_wgrad_scratch_floats(wgrad_args(b.down, nullptr, nullptr, TRAIN_MAX_BATCH, h, h, nullptr, nullptr)));
+            h = bh;
+        }
+    }
+    const size_t bytes = tr->floats * sizeof(float);
+    for (float** q : {&tr->param, &tr->grad, &tr->adam_m, &tr->adam_v}) {
+        void* p = nullptr;
+        SISIC_HIP(hipMalloc(&p, bytes));
+        *q = static_cast<float*>(p);
+        SISIC_TRY(poison_fresh(p, bytes));
+        SISIC_HIP(hipMemset(p, 0, bytes));
+    }
+    {
+        void* p = nullptr;
+        SISIC_HIP(hipMalloc(&p, tr->part_floats * sizeof(float)));
+        tr->part = static_cast<float*>(p);
+        SISIC_TRY(poison_fresh(p, tr->part_floats * sizeof(float)));
+        const size_t sb = 16 + grad_stats_scratch_bytes();
+        SISIC_HIP(hipMalloc(&tr->stats, sb));
+        SISIC_TRY(poison_fresh(tr->stats, sb));
+    }
+    for (int i = 0; i < (int)r->names.size(); ++i)
+        if (tr->off[i] >= 0)
+            SISIC_HIP(hipMemcpy(tr->param + tr->off[i], r->host[i].data(), r->host[i].size() * sizeof(float), hipMemcpyHostToDevice));
+    {
+        std::vector<PackJob> ph[2];
+        auto plan = [&](const FoldedConv& c) {
+            ph[0].push_back(pack_job_conv(c.raw, c.cout, c.cin, c.k, c.packed));
+            ph[0].push_back(pack_job_conv(c.raw_t, c.cin, c.cout, c.k, c.packed_t));
+            if (c.wino) {
+                ph[0].push_back(pack_job_wino_first(c.raw, c.cout, c.cin, c.wino));
+                ph[1].push_back(pack_job_wino_wide(c.cout, c.cin, c.wino));
+                ph[1].push_back(pack_job_wino_bf3(c.cout, c.cin, c.wino));
+                ph[0].push_back(pack_job_wino_first(c.raw_t, c.cin, c.cout, c.wino_t));
+                ph[1].push_back(pack_job_wino_wide(c.cin, c.cout, c.wino_t));
+                ph[1].push_back(pack_job_wino_bf3(c.cin, c.cout, c.wino_t));
+            }
+        };
+        for (const Block& b : r->blocks) {
+            plan(b.conv1);
+            plan(b.conv2);
+            if (b.down.k) plan(b.down);
+        }
+        for (int p = 0; p < 2; ++p) {
+            int blocks = 0;
+            for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
+            SISIC_HIP(hipMalloc(&tr->repack_dev[p], ph[p].size() * sizeof(PackJob)));
+            SISIC_HIP(hipMemcpy(tr->repack_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
+            tr->repack_jobs[p] = (int)ph[p].size();
+            tr->repack_blocks[p] = blocks;
+        }
+    }
+    SISIC_HIP(hipDeviceSynchronize());
+    return SISIC_OK;
+}
+
+// The device already holds what sisic_resnet_load of the trained state dict would leave (optimizer_step derives every form with
+// the load path's arithmetic); the host copies that sisic_resnet_restore folds from follow here.
+int sisic_resnet_train_end(sisic_resnet* r) {
+    SISIC_TRY(require_train(r, "resnet_train_end"));
+    ResnetTrain* tr = r->train;
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    for (int i = 0; i < (int)r->names.size(); ++i)
+        if (tr->off[i] >= 0)
+            SISIC_HIP(hipMemcpy(r->host[i].data(), tr->param + tr->off[i], r->host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
+    train_free(r);
+    return SISIC_OK;
+}
+
+int64_t sisic_resnet_train_steps(const sisic_resnet* r) { return (r && r->train) ? r->train->step : 0; }
+
+int sisic_resnet_zero_grad(sisic_resnet* r) {
+    SISIC_TRY(require_train(r, "resnet_zero_grad"));
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    SISIC_HIP(hipMemset(r->train->grad, 0, r->train->floats * sizeof(float)));
+    SISIC_HIP(hipDeviceSynchronize());
+    return SISIC_OK;
+}
+
+int sisic_resnet_read(sisic_resnet* r, int what, int index, float* host_out, int64_t numel) {
+    SISIC_REQUIRE(r && host_out && index >= 0 && index < (int)r->names.size(), "resnet_read: bad arguments");
+    SISIC_REQUIRE(numel == r->numels[index], "resnet_read: '%s' has %lld elements", r->names[index].c_str(), (long long)r->numels[index]);
+    SISIC_REQUIRE(what >= 0 && what <= 3, "resnet_read: what = %d (0 parameter, 1 gradient, 2 Adam m, 3 Adam v)", what);
+    if (!r->loaded) {
+        set_error("resnet_read called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    ResnetTrain* tr = r->train;
+    if (what == 0 && (!tr || tr->off[index] < 0)) {       // frozen, or not training: the loaded value
+        std::memcpy(host_out, r->host[index].data(), (size_t)numel * sizeof(float));
+        return SISIC_OK;
+    }
+    SISIC_TRY(require_train(r, "resnet_read"));
+    SISIC_REQUIRE(tr->off[index] >= 0, "resnet_read: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
+    const float* base = what == 0 ? tr->param : (what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v));
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    SISIC_HIP(hipMemcpy(host_out, base + tr->off[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+    return SISIC_OK;
+}
+
+int sisic_resnet_write(sisic_resnet* r, int what, int index, const float* host_in, int64_t numel) {
+    SISIC_REQUIRE(r && host_in && index >= 0 && index < (int)r->names.size(), "resnet_write: bad arguments");
+    SISIC_REQUIRE(numel == r->numels[index], "resnet_write: '%s' has %lld elements", r->names[index].c_str(), (long long)r->numels[index]);
+    SISIC_REQUIRE(what != 0, "resnet_write: parameters are set by sisic_resnet_load (their folded and packed forms must follow); "
+                             "what = 1 gradient, 2 Adam m, 3 Adam v");
+    SISIC_REQUIRE(what >= 1 && what <= 3, "resnet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
+    SISIC_TRY(require_train(r, "resnet_write"));
+    ResnetTrain* tr = r->train;
+    SISIC_REQUIRE(tr->off[index] >= 0, "resnet_write: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
+    float* base = what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v);
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_HIP(hipDeviceSynchronize());
+    SISIC_HIP(hipMemcpy(base + tr->off[index], host_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+    return SISIC_OK;
+}
+
+// loss = cross_entropy(resnet18(x), labels, weight) and its gradient with respect to the 22 trainable tensors.
+// Forward: run_trunk with everything kept.  Backward: the walk of sisic_resnet_input_gradient seeded by d loss / d logits; at
+// each convolution the weight gradient is issued from the tensors the walk holds anyway -- the gradient at conv2's and at
+// downsample's output is g (after the block's ReLU mask), the one at conv1's output is tmp (after its mask), the inputs are the
+// kept activations.  The walk stops at the stem's output: nothing below it is trainable.
+int sisic_resnet_loss_backward(sisic_resnet* r, sisic_resnet_train_args* a) {
+    SISIC_TRY(require_train(r, "resnet_loss_backward"));
+    SISIC_REQUIRE(a && a->x && a->labels && a->B > 0 && a->H > 0 && a->W > 0, "resnet_loss_backward: bad arguments");
+    const int B = a->B, H = a->H, W = a->W, n = r->num_classes;
+    SISIC_REQUIRE(B <= TRAIN_MAX_BATCH, "resnet_loss_backward: batch %d (at most %d)", B, TRAIN_MAX_BATCH);
+    ResnetTrain* tr = r->train;
+    tr->labels_host.resize(B);
+    double picked = 0.0;
+    for (int b = 0; b < B; ++b) {
+        SISIC_REQUIRE(a->labels[b] >= 0 && a->labels[b] < n, "resnet_loss_backward: label %lld of sample %d is outside [0, %d)",
+                      (long long)a->labels[b], b, n);
+        tr->labels_host[b] = (int)a->labels[b];
+        picked += a->class_weights ? (double)a->class_weights[a->labels[b]] : 1.0;
+    }
+    if (a->class_weights) {
+        for (int k = 0; k < n; ++k)
+            SISIC_REQUIRE(std::isfinite(a->class_weights[k]) && a->class_weights[k] >= 0.0f, "resnet_loss_backward: class weight %d is %g", k, a->class_weights[k]);
+        SISIC_REQUIRE(picked > 0.0, "resnet_loss_backward: the weights of the batch's classes sum to zero");
+        tr->cw_host.assign(a->class_weights, a->class_weights + n);
+    }
+    SISIC_TRY(check_train_geometry(H, W, a->preprocess));
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_TRY(workspace_for(r, B, H, W));
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    PoolScope ws(r->pool, s);
+    auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
+        sisic_conv_args ca{};
+        ca.in0 = g; ca.c0 = c.cout; ca.B = B; ca.Hin = gh; ca.Win = gw;
+        ca.ksize = c.k; ca.stride = 1;
+        ca.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
+        ca.w_packed = c.packed_t; ca.w_winograd = c.wino_t; ca.Cout = c.cin;
+        ca.residual = residual; ca.out = out;
+        return launch_conv2d(r->ctx, ca, s);
+    };
+    auto wgrad = [&](const FoldedConv& c, const float* in, const float* even, int h, int w, const float* dy) {
+        const WgradArgs wa = wgrad_args(c, in, even, B, h, w, dy, tr->grad + tr->off[c.w_idx]);
+        return launch_conv_wgrad(r->ctx, wa, tr->part, tr->part_floats, s);
+    };
+    // labels (and class weights) on the device: one block, ints first
+    float* lab = nullptr;
+    SISIC_TRY(ws.get((size_t)B + n, &lab));
+    SISIC_HIP(hipMemcpyAsync(lab, tr->labels_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    if (a->class_weights) SISIC_HIP(hipMemcpyAsync(lab + B, tr->cw_host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+
+    Trunk t;
+    t.preprocess = a->preprocess != 0;
+    t.keep = true;
+    t.keep_pre = true;
+    t.who = "resnet_loss_backward";
+    SISIC_TRY(run_trunk(r, ws, a->x, B, H, W, t, s));
+    const std::vector<Trunk::Saved>& saved = t.saved;
+    const int C = r->blocks.back().conv2.cout, c1h = t.c1h, c1w = t.c1w;
+    if (a->logits_out)
+        SISIC_HIP(hipMemcpyAsync(a->logits_out, t.logits, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+
+    // ---- head
+    float* dlogits = nullptr;
+    SISIC_TRY(ws.get((size_t)B * n, &dlogits));
+    SISIC_TRY(launch_ce_head(r->ctx, t.logits, reinterpret_cast<const int*>(lab), a->class_weights ? lab + B : nullptr, B, n,
+                             loss_slot(tr), dlogits, s));
+    float* g = nullptr;                                   // d loss / d (block output), already ReLU-masked
+    SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
+    SISIC_TRY(launch_fc_head_bwd(r->ctx, dlogits, r->d_fc_w, t.act, g, tr->grad + tr->off[r->fc_w], tr->grad + tr->off[r->fc_b], B, C,
+                                 t.h * t.w, n, s));
+    ws.put(dlogits);
+    ws.put(t.logits);
+    ws.put(lab);
+    // ---- the blocks, last to first
+    for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
+        const Block& b = r->blocks[k];
+        const Trunk::Saved& sv = saved[k];
+        const float* in_act = k > 0 ? saved[k - 1].out : t.m;          // the block's input [B, conv1.cin, sv.h, sv.w]
+        SISIC_TRY(wgrad(b.conv2, sv.t1, nullptr, sv.bh, sv.bw, g));
+        const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
+        float* tmp = nullptr;                             // conv2^T g, then the ReLU mask of t1
+        SISIC_TRY(ws.get(n_mid, &tmp));
+        SISIC_TRY(conv_t(b.conv2, g, sv.bh, sv.bw, nullptr, tmp));
+        SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
+        SISIC_TRY(wgrad(b.conv1, in_act, nullptr, sv.h, sv.w, tmp));
+        const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
+        float* da = nullptr;
+        SISIC_TRY(ws.get(n_in, &da));
+        if (!b.down.k) {
+            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, g, da));                 // + identity path
+        } else {
+            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
+            float* small = nullptr;                                               // first the even pixels of the input ...
+            SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
+            SISIC_TRY(launch_gather_even(r->ctx, in_act, small, B * b.down.cin, sv.h, sv.w, s));      // (ResNet18's downsamples are stride 2)
+            SISIC_TRY(wgrad(b.down, nullptr, small, sv.h, sv.w, g));
+            SISIC_TRY(conv_t(b.down, g, sv.bh, sv.bw, nullptr, small));           // ... then the 1x1 at the low resolution
+            SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
+            ws.put(small);
+        }
+        ws.put(tmp);
+        ws.put(g);
+        ws.put(sv.t1);
+        ws.put(sv.out);
+        if (k > 0) SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));      // ReLU of the previous block's output
+        g = da;
+    }
+    // g = d loss / d (max-pool output)
+    float* dc1 = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
+    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, t.c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
+    ws.put(g);
+    ws.put(t.m);
+    ws.put(t.c1);
+    const int sh = t.preprocess ? 224 : H, sw = t.preprocess ? 224 : W;
+    SISIC_TRY(launch_stem_wgrad(r->ctx, t.pre ? t.pre : a->x, dc1, tr->grad + tr->off[r->stem.w_idx], B, sh, sw, tr->part,
+                                tr->part_floats, s));
+    ws.put(dc1);
+    if (t.pre) ws.put(t.pre);
+    // the chain differentiated the folded filters
+    SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) { return launch_unfold_grad(r->ctx, tr->grad + tr->off[c.w_idx], c.sc, c.cout, c.cin, c.k, s); }));
+    SISIC_HIP(hipMemcpyAsync(&a->loss, loss_slot(tr), sizeof(float), hipMemcpyDeviceToHost, s));
+    SISIC_HIP(hipStreamSynchronize(s));
+    return SISIC_OK;
+}
+
+// clip_grad_norm_ (optional) + torch.optim.Adam on the arenas, then every derived form of the new weights.
+int sisic_resnet_optimizer_step(sisic_resnet* r, sisic_resnet_train_args* a) {
+    SISIC_TRY(require_train(r, "resnet_optimizer_step"));
+    SISIC_REQUIRE(a, "resnet_optimizer_step: null arguments");
+    SISIC_REQUIRE(a->lr >= 0.0 && a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps >= 0.0,
+                  "resnet_optimizer_step: lr %g betas (%g, %g) eps %g", a->lr, a->beta1, a->beta2, a->eps);
+    ResnetTrain* tr = r->train;
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    SISIC_TRY(launch_grad_stats(r->ctx, tr->grad, tr->floats, 1.0f, a->max_grad_norm, stats_record(tr), stats_scratch(tr), s));
+    GradStats host{};
+    SISIC_HIP(hipMemcpyAsync(&host, stats_record(tr), sizeof(GradStats), hipMemcpyDeviceToHost, s));
+    SISIC_HIP(hipStreamSynchronize(s));
+    a->grad_norm = host.total_norm;
+    a->found_inf = host.found_inf;
+    if (host.found_inf) return SISIC_OK;                 // no update: parameters, moments and the step counter stay
+    tr->step += 1;
+    SISIC_TRY(launch_adam_ema(r->ctx, tr->param, tr->grad, tr->adam_m, tr->adam_v, nullptr, tr->floats, a->lr, a->beta1, a->beta2, a->eps,
+                              tr->step, 1.0f, stats_record(tr), 0.0, s));
+    SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) {
+        return launch_refold(r->ctx, tr->param + tr->off[c.w_idx], c.sc, c.raw, c.raw_t, c.cout, c.cin, c.k, s);
+    }));
+    SISIC_TRY(fold_pack(r, r->stem, s));                 // the 7x7 filter: one form, the load path's launch
+    for (int p = 0; p < 2; ++p)
+        SISIC_TRY(launch_pack_batch(r->ctx, static_cast<const PackJob*>(tr->repack_dev[p]), tr->repack_jobs[p], tr->repack_blocks[p], s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, tr->param + tr->off[r->fc_w], (size_t)r->numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, tr->param + tr->off[r->fc_b], (size_t)r->numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return SISIC_OK;
 }
 
 int sisic_class_scores(sisic_ctx* ctx, const float* logits, int B, int n_classes, int target, float* prob,

@@ -22,6 +22,22 @@ struct WgradArgs {
 size_t conv_wgrad_scratch_floats(const WgradArgs& a);
 int launch_conv_wgrad(sisic_ctx*, const WgradArgs& a, float* part, size_t part_floats, hipStream_t s);
 int launch_transpose_flip(sisic_ctx*, const float* w, int Cout, int Cin, int KK, float* wt, hipStream_t s);
+// out[i] = sum over k of part[k][i] in launch_conv_wgrad's fixed order (its reduction kernels, for slabs of another kernel)
+int launch_wgrad_reduce(sisic_ctx*, const float* part, int ksplit, size_t n, float* out, hipStream_t s);
+
+// classifier_train.hip: the classifier's training step with BatchNorm frozen (resnet.cpp)
+// dW [64,3,7,7] of the 7x7 stride-2 padding-3 stem from its input x [B,3,H,W] (H, W even, >= 8) and dy [B,64,H/2,W/2]
+size_t stem_wgrad_scratch_floats();
+int launch_stem_wgrad(sisic_ctx*, const float* x, const float* dy, float* dw, int B, int H, int W, float* part, size_t part_floats,
+                      hipStream_t s);
+int launch_gather_even(sisic_ctx*, const float* in, float* out, int planes, int H, int W, hipStream_t s);
+// labels: device int [B], each in [0, n) (the caller checks); w: device [n] or NULL; loss: device float; dlogits [B, n]
+int launch_ce_head(sisic_ctx*, const float* logits, const int* labels, const float* w, int B, int n, float* loss, float* dlogits,
+                   hipStream_t s);
+int launch_fc_head_bwd(sisic_ctx*, const float* dlogits, const float* fc_w, const float* act, float* g, float* dfc_w, float* dfc_b,
+                       int B, int C, int HW, int n, hipStream_t s);
+int launch_unfold_grad(sisic_ctx*, float* g, const double* sc, int cout, int cin, int k, hipStream_t s);
+int launch_refold(sisic_ctx*, const float* w, const double* sc, float* raw, float* raw_t, int cout, int cin, int k, hipStream_t s);
 
 // repack.hip: one re-layout of one tensor inside a batched launch (pack_batch_kernel)
 struct PackJob {

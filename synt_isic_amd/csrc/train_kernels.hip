@@ -440,6 +440,24 @@ int launch_conv_wgrad(sisic_ctx* ctx, const WgradArgs& a, float* part, size_t pa
     return SISIC_OK;
 }
 
+// The slab sum of launch_conv_wgrad on its own, for a weight-gradient kernel of another file (classifier_train.hip) that
+// leaves [ksplit][n] partial slabs: the same two kernels, the same choice between them, the same summation tree.
+int launch_wgrad_reduce(sisic_ctx*, const float* part, int ksplit, size_t n, float* out, hipStream_t s) {
+    SISIC_REQUIRE(part && out && ksplit > 0 && n > 0, "wgrad_reduce: bad arguments");
+    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if ((n & 3) == 0 && al16(part) && al16(out)) {
+        const size_t n4 = n >> 2;
+        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)std::min<size_t>((n4 + 31) / 32, 8192)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(part), ksplit, n4, reinterpret_cast<float4*>(out),
+                           static_cast<float4*>(nullptr), static_cast<float4*>(nullptr), (size_t)0);
+    } else {
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)std::min<size_t>((n + 31) / 32, 8192)), dim3(256), 0, s, part, ksplit, n,
+                           out, static_cast<float*>(nullptr), static_cast<float*>(nullptr), (size_t)0);
+    }
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // W'[ci][co][KK-1-t] = W[co][ci][t]: the filter of the backward-data convolution
 __global__ void transpose_flip_kernel(const float* __restrict__ w, int Cout, int Cin, int KK, float* __restrict__ wt) {
     const size_t n = (size_t)Cout * Cin * KK;

@@ -642,3 +642,137 @@ def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: 
         raise ValueError(f"cond_drop_prob must be in [0, 1], got {cond_drop_prob}")
     return _train_loop(model, loader, name, epochs, lr, checkpoint_dir, fused, generator, log, max_grad_norm, ema_decay,
                        ema_warmup, lr_schedule, float(cond_drop_prob), dropout_seed, snr_gamma)
+
+
+# ---- the ResNet18 classifier (xai/XAI.py:357-471) with BatchNorm frozen ---------------------------------------------------
+# What the reference leaves to torch: fine-tuning the lesion classifier whose explanations the XAI passes compute.  BatchNorm
+# keeps the constants it was loaded with (torchvision.ops.FrozenBatchNorm2d), which is the function the library's folded
+# forward computes, so the training forward is the inference forward and the trained model needs no other path.  Training is
+# entered through the optimizer object, not through ``clf.train()``, which would promise batch statistics.
+class HipClassifierAdam:
+    """``torch.optim.Adam`` over the 22 trainable tensors of a HipMelanomaClassifier (20 convolution weights, fc.weight,
+    fc.bias); parameters, gradients and moments live in the library (sisic_resnet_train_begin on construction).
+    ``max_grad_norm``: ``clip_grad_norm_`` in front of every step; ``grad_norm`` is the norm of the last step before clipping.
+    ``close()`` ends training (sisic_resnet_train_end): the model is then what loading its ``state_dict()`` would give."""
+
+    def __init__(self, clf, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
+        handle = clf.handle                      # a model on the CPU raises here: MI355X only
+        if clf._trainer is not None:
+            raise RuntimeError("this classifier already has a HipClassifierAdam; close() it first")
+        self.clf, self.lr, self.betas, self.eps = clf, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm: Optional[float] = None
+        check(_lib.load().sisic_resnet_train_begin(handle))
+        self._active = True
+        clf._trainer = self
+
+    def _handle(self):
+        if not self._active:
+            raise RuntimeError("this HipClassifierAdam is closed (close(), or the model was reloaded or moved)")
+        return self.clf.handle
+
+    @property
+    def steps(self) -> int:
+        return int(_lib.load().sisic_resnet_train_steps(self._handle()))
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        check(_lib.load().sisic_resnet_zero_grad(self._handle()))
+
+    def step(self) -> bool:
+        """One Adam update and the rebuild of every folded and packed filter; False: a gradient was inf/nan, nothing moved."""
+        a = _lib.ResnetTrainArgs()
+        a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
+        a.max_grad_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        a.stream = torch.cuda.current_stream(self.clf.device).cuda_stream
+        check(_lib.load().sisic_resnet_optimizer_step(self._handle(), C.byref(a)))
+        self.grad_norm = float(a.grad_norm)
+        if a.found_inf:
+            return False
+        self.clf._params_stale = True
+        return True
+
+    def close(self) -> None:
+        if self._active:
+            self.clf._sync_params()
+            check(_lib.load().sisic_resnet_train_end(self.clf.handle))
+            self._active = False
+            self.clf._trainer = None
+
+
+def balanced_class_weights(labels, num_classes: int) -> torch.Tensor:
+    """inverse class frequency, sklearn's "balanced": N / (num_classes * count[c]); a class without samples gets 0"""
+    lab = torch.as_tensor(labels).detach().to("cpu", torch.int64)
+    count = torch.bincount(lab, minlength=num_classes)[:num_classes].double()
+    w = torch.where(count > 0, lab.numel() / (num_classes * count.clamp(min=1)), torch.zeros_like(count))
+    return w.float()
+
+
+@torch.no_grad()
+def evaluate_classifier(clf, loader) -> Dict[str, object]:
+    """Confusion matrix (rows: true class, columns: predicted), accuracy and balanced accuracy (mean recall over the classes
+    that occur) of ``clf`` over ``loader`` (items ``(images, labels)``), batched forwards.  A ``data.DeviceLoader`` is walked
+    once in dataset order with its augmentation off, whatever its own settings."""
+    clf.handle                                   # a model on the CPU raises here: MI355X only
+    from .data import DeviceLoader
+    if isinstance(loader, DeviceLoader):
+        loader = DeviceLoader(loader.dataset, loader.batch_size, shuffle=False, augment=False)
+    n = clf.num_classes
+    cm = torch.zeros((n, n), dtype=torch.int64)
+    for images, labels in loader:
+        pred = clf.predict(images.to(clf.device)).to("cpu", torch.int64)
+        lab = torch.as_tensor(labels).to("cpu", torch.int64)
+        cm += torch.bincount(lab * n + pred, minlength=n * n).view(n, n)
+    total = int(cm.sum())
+    support = cm.sum(1)
+    recall = cm.diag().double() / support.clamp(min=1).double()
+    return {"confusion_matrix": cm, "accuracy": float(cm.diag().sum()) / max(1, total),
+            "balanced_accuracy": float(recall[support > 0].mean()) if total else 0.0}
+
+
+def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=None, val_loader=None,
+                     save_dir: Optional[str] = None, max_grad_norm: Optional[float] = None,
+                     log: Optional[Callable[[str], None]] = print):
+    """``train_class``'s loop for the classifier: epochs over ``loader`` (items ``(images, labels)``, images in [-1,1] as the
+    sampler makes them -- a ``data.DeviceLoader`` over ``DeviceDataset.from_isic_classes``), cross-entropy, Adam, BatchNorm
+    frozen.  ``class_weights``: None, a [num_classes] tensor, or ``"balanced"`` (inverse class frequency from
+    ``loader.dataset.labels``; ISIC is 67 % NV).  ``val_loader``: ``evaluate_classifier`` after every epoch, its balanced
+    accuracy selects the best checkpoint (otherwise the epoch loss does).  ``save_dir``: ``classifier.pth`` under the
+    reference's key names (``model.`` prefix), which ``load_state_dict`` here and the reference's
+    ``load_classifier_with_fallback`` both take.  Returns the per-epoch history (loss, and the validation record)."""
+    clf.handle                                   # a model on the CPU raises here: MI355X only
+    if isinstance(class_weights, str):
+        if class_weights != "balanced":
+            raise ValueError(f"class_weights {class_weights!r}: None, a tensor or 'balanced'")
+        labels = getattr(getattr(loader, "dataset", None), "labels", None)
+        if labels is None:
+            raise ValueError("class_weights='balanced' needs loader.dataset.labels")
+        class_weights = balanced_class_weights(labels, clf.num_classes)
+    optimizer = HipClassifierAdam(clf, lr=lr, max_grad_norm=max_grad_norm)
+    history = []
+    best = None
+    try:
+        for epoch in range(epochs):
+            epoch_loss, n_batches = 0.0, 0
+            for images, labels in loader:
+                value, _ = clf.loss_backward(images, labels, class_weights=class_weights)
+                optimizer.step()
+                epoch_loss += value
+                n_batches += 1
+            record = {"loss": epoch_loss / max(1, n_batches)}
+            if val_loader is not None:
+                record.update(evaluate_classifier(clf, val_loader))
+            history.append(record)
+            if log:
+                log(f"Loss: {record['loss']:.5f}" + (f"  balanced accuracy: {record['balanced_accuracy']:.4f}"
+                                                     if val_loader is not None else ""))
+            score = record["balanced_accuracy"] if val_loader is not None else -record["loss"]
+            if best is None or score > best:
+                best = score
+                if save_dir:
+                    os.makedirs(save_dir, exist_ok=True)
+                    torch.save(OrderedDict((k, v.cpu()) for k, v in clf.state_dict().items()), os.path.join(save_dir, "classifier.pth"))
+    finally:
+        optimizer.close()
+    return history
