@@ -689,7 +689,51 @@ int sisic_groupnorm_bwd(sisic_ctx*, const float* da, const float* x, int B, int 
                         const float* gamma, const float* beta, int silu, float* dx_accum, float* dgamma, float* dbeta,
                         void* stream);
 
-/* ---- ResNet18 classifier (xai/XAI.py:357-471): forward, explanations, training with frozen BatchNorm ---- */
+/* BatchNorm2d in training mode (batch statistics) over y dev [B,C,HW] (NCHW, a convolution output without bias), forward and
+ * backward, on the caller's tensors.  One argument struct for both; the stream travels in it.
+ *   forward  (sisic_batchnorm_train):     reads y, gamma, beta [C], residual (dev [B,C,HW] or NULL), relu, eps, momentum;
+ *            writes mean, invstd = 1/sqrt(var + eps) [C] (var the biased variance over n = B*HW) and
+ *            out = [relu](gamma (y - mean) invstd + beta [+ residual]); running_mean / running_var ([C], both or neither; NULL: no
+ *            update) receive nn.BatchNorm2d's update rm <- (1-m) rm + m mean, rv <- (1-m) rv + m var n/(n-1), momentum m in (0, 1]
+ *   backward (sisic_batchnorm_train_bwd): reads g = dL/d(out), y, mean, invstd, gamma and act (dev [B,C,HW] or NULL: the
+ *            activation behind the BatchNorm's ReLU; g' = g where act > 0, else 0.  NULL: g' = g); writes dbeta = sum g',
+ *            dgamma = sum g' xhat [C] and dy = gamma invstd (g' - dbeta/n - xhat dgamma/n), xhat = (y - mean) invstd.  dy is a
+ *            buffer of its own (not g).
+ * Moments: each workgroup reduces a slice of a channel to (count, mean, M2) by Welford's update, the slices are merged with
+ * Chan's formula in double (never E[x^2] - E[x]^2).  No atomics: every summation order is a function of (B, C, HW) alone, two
+ * calls give equal bits.  The slice partials live in a scratch buffer of the context, one per stream: the first call on a stream
+ * at a larger C * slices allocates it and waits for the stream once, later calls neither allocate nor wait.
+ * B * HW = 1 ("expected more than 1 value per channel when training"): SISIC_EINVAL before any launch.
+ * out = NULL: the moments (and the running update) alone; dy = NULL: dgamma and dbeta alone -- how tools time each launch.
+ * sisic_add_relu: out = relu(y + residual) over the B * C * HW elements, the elementwise pass the classifier's Grad-CAM path
+ * already runs, here on the caller's tensors: the yardstick the BatchNorm passes are measured against.                      */
+typedef struct sisic_bn_args {
+    const float* y;
+    const float* gamma;
+    const float* beta;
+    const float* residual;
+    float*       running_mean;
+    float*       running_var;
+    float*       out;
+    float*       mean;
+    float*       invstd;
+    const float* g;
+    const float* act;
+    float*       dy;
+    float*       dgamma;
+    float*       dbeta;
+    void*        stream;
+    double       momentum;
+    float        eps;
+    int          relu;
+    int          B, C, HW;
+    int          reserved;                 /* 0 */
+} sisic_bn_args;                           /* 152 bytes, no padding */
+int sisic_batchnorm_train(sisic_ctx*, sisic_bn_args* args);
+int sisic_batchnorm_train_bwd(sisic_ctx*, sisic_bn_args* args);
+int sisic_add_relu(sisic_ctx*, sisic_bn_args* args);
+
+/* ---- ResNet18 classifier (xai/XAI.py:357-471): forward, explanations, training with frozen or batch-statistics BatchNorm ---- */
 /* torchvision resnet18 with fc -> num_classes, eval mode (BatchNorm folded at load).  The state dict
  * uses the reference's key names, prefixed "model." (XAI.py:389), float tensors only: conv/fc weights
  * and biases, BatchNorm weight/bias/running_mean/running_var (num_batches_tracked is not a float tensor
@@ -738,8 +782,9 @@ int sisic_resnet_gradcam(sisic_resnet*, const float* x, int B, int H, int W, int
 /* ---- training the classifier with BatchNorm frozen ("classifier training") --------------------------
  * torchvision.ops.FrozenBatchNorm2d semantics: running statistics, gamma and beta stay the constants they were loaded as, so
  * the training forward IS the folded forward above, bit for bit, and a trained model needs no other inference path.
- * Trainable tensors (22): the 20 convolution weights, fc.weight and fc.bias.  BatchNorm in batch-statistics mode is not
- * implemented.
+ * Trainable tensors (22): the 20 convolution weights, fc.weight and fc.bias.  BatchNorm with batch statistics
+ * (nn.BatchNorm2d in training mode, 62 trainable tensors) is the second mode, entered by sisic_resnet_train_begin_bn and
+ * described behind the entries below; everything in this paragraph and the next ones speaks of the frozen mode.
  *
  * train_begin (after sisic_resnet_load) allocates arenas for the un-folded parameters, their gradients and the two Adam
  * moments, and the scratch of the K-split weight gradients; train_end frees them and leaves the handle as
@@ -790,6 +835,36 @@ int64_t sisic_resnet_train_steps(const sisic_resnet*);        /* optimizer steps
  * Both synchronise the device.                                                                                            */
 int sisic_resnet_read(sisic_resnet*, int what, int index, float* host_out, int64_t numel);
 int sisic_resnet_write(sisic_resnet*, int what, int index, const float* host_in, int64_t numel);
+
+/* ---- training the classifier with batch-statistics BatchNorm (nn.BatchNorm2d in training mode) ----------------------------
+ * train_begin_bn: mode 0 (frozen) is exactly sisic_resnet_train_begin.  mode 1 (batch statistics) takes momentum in (0, 1]
+ * (torch's momentum = None cumulative average is not offered); any other mode or momentum: SISIC_EINVAL.
+ * In mode 1 the trainable tensors are 62 -- the 20 convolution weights, their 20 gamma and 20 beta, fc.weight and fc.bias -- side
+ * by side in the four arenas in state-dict order; the 40 running statistics live in a buffer arena beside them.  A second set of
+ * filter forms (transposed, packed, Winograd, and the transposes' forms) is allocated for the UNFOLDED weights.
+ *   loss_backward   forward: every convolution with its unfolded filters and no bias, then the moments of its output, then the
+ *                   apply pass (sisic_batchnorm_train's kernels); the pre-BatchNorm outputs and (mean, invstd) are kept beside the
+ *                   activations.  The running statistics are updated here, once per call, as torch updates them in the forward.
+ *                   logits_out are the training-mode logits.  backward: the walk of the frozen mode with a BatchNorm backward in
+ *                   front of every weight gradient and transposed convolution (the stem and the downsample branch included), on
+ *                   the unfolded transposed filters.  The geometry checks of the frozen mode, and B * h * w >= 2 at the last
+ *                   plane.  Same determinism: two calls from one state give equal bits in every gradient.
+ *   optimizer_step  the same statistics and Adam passes over the larger arena; then the unfolded forms the training forward
+ *                   reads, and the folded inference forms from (w, gamma, beta, running_mean, running_var): sc = gamma /
+ *                   sqrt(running_var + eps) and bias = (float)(beta - running_mean * sc) formed on the device in double, the load
+ *                   path's arithmetic.  Both rebuilds run on EVERY call, also when found_inf skipped the update: the running
+ *                   statistics moved.  After every optimizer_step the inference side of the handle (sisic_resnet_forward,
+ *                   _input_gradient, _gradcam, _randomize) equals a fresh sisic_resnet_load of the current state dict bit for bit.
+ *                   Between a loss_backward and the next optimizer_step the inference side lags by that one running-statistics
+ *                   update.
+ *   read / write    what = 0 returns the current value of any tensor; what = 1..3 work for the 62 trainable tensors, for a
+ *                   running statistic they return SISIC_EINVAL.
+ *   train_end       copies parameters and buffers back to the host copies (refreshing the inference side first if a
+ *                   loss_backward moved the running statistics since the last optimizer_step) and frees the second set.
+ * train_bn_mode: 0 frozen, 1 batch statistics, -1 outside training.                                                          */
+typedef struct { int mode; double momentum; } sisic_resnet_bn_config;
+int sisic_resnet_train_begin_bn(sisic_resnet*, const sisic_resnet_bn_config* config);
+int sisic_resnet_train_bn_mode(const sisic_resnet*);
 
 /* Bytes of activation workspace the handle currently keeps resident (its pool).  The pool is sized for the last
  * (B,H,W) seen and released when the shape changes, so this does not grow with the history of batch sizes

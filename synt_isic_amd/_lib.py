@@ -109,6 +109,20 @@ class ResnetTrainArgs(C.Structure):
                 ("loss", C.c_float), ("grad_norm", C.c_float), ("found_inf", C.c_int)]
 
 
+class BnArgs(C.Structure):
+    """struct sisic_bn_args (152 bytes, no padding)"""
+    _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("residual", C.c_void_p),
+                ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("out", C.c_void_p), ("mean", C.c_void_p),
+                ("invstd", C.c_void_p), ("g", C.c_void_p), ("act", C.c_void_p), ("dy", C.c_void_p), ("dgamma", C.c_void_p),
+                ("dbeta", C.c_void_p), ("stream", C.c_void_p), ("momentum", C.c_double), ("eps", C.c_float), ("relu", C.c_int),
+                ("B", C.c_int), ("C", C.c_int), ("HW", C.c_int), ("reserved", C.c_int)]
+
+
+class ResnetBnConfig(C.Structure):
+    """struct sisic_resnet_bn_config: mode 0 frozen BatchNorm, 1 batch statistics with ``momentum`` in (0, 1]"""
+    _fields_ = [("mode", C.c_int), ("momentum", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -257,6 +271,9 @@ SIGNATURES = {
                                       C.c_int, C.c_void_p]),
     "sisic_groupnorm_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sisic_batchnorm_train": (C.c_int, [C.c_void_p, C.POINTER(BnArgs)]),
+    "sisic_batchnorm_train_bwd": (C.c_int, [C.c_void_p, C.POINTER(BnArgs)]),
+    "sisic_add_relu": (C.c_int, [C.c_void_p, C.POINTER(BnArgs)]),
     "sisic_resnet_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "sisic_resnet_destroy": (C.c_int, [C.c_void_p]),
     "sisic_resnet_num_tensors": (C.c_int, [C.c_void_p]),
@@ -279,6 +296,8 @@ SIGNATURES = {
     "sisic_resnet_train_steps": (C.c_int64, [C.c_void_p]),
     "sisic_resnet_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
     "sisic_resnet_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int64]),
+    "sisic_resnet_train_begin_bn": (C.c_int, [C.c_void_p, C.POINTER(ResnetBnConfig)]),
+    "sisic_resnet_train_bn_mode": (C.c_int, [C.c_void_p]),
     "sisic_resnet_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sisic_unet_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sisic_class_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

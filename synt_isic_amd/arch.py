@@ -202,3 +202,21 @@ def resnet18_param_spec(num_classes: int = 7) -> "OrderedDict[str, Tuple[int, ..
     spec["model.fc.weight"] = (num_classes, 512)
     spec["model.fc.bias"] = (num_classes,)
     return spec
+
+
+BATCHNORM_MODES = ("frozen", "batch")
+
+
+def resnet18_trainable_names(num_classes: int = 7, batchnorm: str = "frozen"):
+    """The tensors a classifier optimizer step moves, in state-dict order.  ``"frozen"``: the 20 convolution weights, fc.weight
+    and fc.bias (22).  ``"batch"`` (BatchNorm with batch statistics): the 20 gamma and 20 beta as well (62); the 40 running
+    statistics are buffers in both modes."""
+    if batchnorm not in BATCHNORM_MODES:
+        raise ValueError(f"batchnorm {batchnorm!r}: one of {BATCHNORM_MODES}")
+    return [n for n, shape in resnet18_param_spec(num_classes).items()
+            if "running_" not in n and (batchnorm == "batch" or len(shape) == 4 or n.startswith("model.fc."))]
+
+
+def resnet18_buffer_names(num_classes: int = 7):
+    """the 40 running statistics, in state-dict order"""
+    return [n for n in resnet18_param_spec(num_classes) if "running_" in n]

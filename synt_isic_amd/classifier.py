@@ -1,5 +1,6 @@
 """HipMelanomaClassifier -- drop-in for ``MelanomaClassifierAdaptive`` (xai/XAI.py:357-471): forward, explanations, and
-training with BatchNorm frozen (``loss_backward`` here, ``HipClassifierAdam`` / ``train_classifier`` in train.py).
+training with BatchNorm frozen or with batch statistics (``loss_backward`` here, ``HipClassifierAdam`` / ``train_classifier``
+in train.py).
 
 The reference wraps ``torchvision.models.resnet18`` (fc -> num_classes) and feeds it diffusion latents in
 [-1,1] through ``preprocess_for_classifier`` (clamp, bilinear resize to 224x224, ImageNet normalisation).
@@ -16,7 +17,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .arch import resnet18_param_spec
+from .arch import resnet18_buffer_names, resnet18_param_spec, resnet18_trainable_names
 
 NUM_CLASSES = 7                                     # xai/XAI.py:196 ISIC classes
 CLASS_NAMES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")
@@ -38,6 +39,7 @@ class HipMelanomaClassifier:
         self._handle: Optional[C.c_void_p] = None
         self._uploaded = False
         self._params_stale = False      # an optimizer step moved the library's weights: _params follows on the next read
+        self._batches_tracked: "OrderedDict[str, torch.Tensor]" = OrderedDict()    # num_batches_tracked of the loaded dict, if any
         self._trainer = None            # the train.HipClassifierAdam that holds the library's training arenas, if any
         self.training = True
 
@@ -52,8 +54,9 @@ class HipMelanomaClassifier:
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("BatchNorm in batch-statistics mode is not implemented: the classifier trains with "
-                                      "BatchNorm frozen, through train.HipClassifierAdam and loss_backward, in eval mode")
+            raise NotImplementedError("train() does not switch BatchNorm to batch-statistics mode: training is entered through "
+                                      "the optimizer object, train.HipClassifierAdam(clf, batchnorm='batch') for batch statistics "
+                                      "(the default keeps BatchNorm frozen), and loss_backward")
         return self.eval()
 
     def parameters(self) -> Iterator[torch.Tensor]:
@@ -61,16 +64,28 @@ class HipMelanomaClassifier:
         return (v for k, v in self._params.items() if "running_" not in k)
 
     def state_dict(self):
-        """the weights as they stand: after ``HipClassifierAdam.step`` the trained tensors (read back from the library once),
-        the BatchNorm tensors unchanged"""
+        """the weights as they stand: after ``HipClassifierAdam.step`` the trained tensors (read back from the library once).
+        With BatchNorm frozen the BatchNorm tensors are unchanged; with batch statistics gamma, beta and the running statistics
+        are the trained / updated ones, and the ``num_batches_tracked`` entries the loaded dict had (each behind its
+        ``running_var``) have advanced by one per training forward."""
         self._sync_params()
-        return OrderedDict(self._params)
+        out = OrderedDict()
+        for k, v in self._params.items():
+            out[k] = v
+            nbt = k[:-len("running_var")] + "num_batches_tracked"
+            if k.endswith("running_var") and nbt in self._batches_tracked:
+                out[nbt] = self._batches_tracked[nbt].clone()
+        return out
 
-    # ---- training with frozen BatchNorm (train.HipClassifierAdam owns train_begin / train_end) ---------------------
-    def trainable_names(self):
-        """the 22 tensors an optimizer step moves: the 20 convolution weights, fc.weight and fc.bias"""
-        return [n for n in self._spec if n.endswith("conv1.weight") or n.endswith("conv2.weight")
-                or n.endswith("downsample.0.weight") or n.startswith("model.fc.")]
+    # ---- training (train.HipClassifierAdam owns train_begin / train_end) -------------------------------------------
+    def trainable_names(self, batchnorm: str = "frozen"):
+        """the tensors an optimizer step moves, in state-dict order: ``"frozen"`` the 20 convolution weights, fc.weight and
+        fc.bias (22); ``"batch"`` the 20 BatchNorm gamma and 20 beta as well (62)"""
+        return resnet18_trainable_names(self.num_classes, batchnorm)
+
+    def _mode(self) -> str:
+        """the BatchNorm mode of the optimizer that holds the training arenas ("frozen" without one)"""
+        return self._trainer.batchnorm if self._trainer is not None else "frozen"
 
     def _tensor_index(self) -> Dict[str, int]:
         lib, h = _lib.load(), self.handle
@@ -80,7 +95,10 @@ class HipMelanomaClassifier:
         if not self._params_stale:
             return
         self._params_stale = False                       # (before the reads: read_tensor goes through .handle only)
-        for name in self.trainable_names():
+        names = self.trainable_names(self._mode())
+        if self._mode() == "batch":
+            names = names + resnet18_buffer_names(self.num_classes)
+        for name in names:
             self._params[name] = self.read_tensor(0, name).to(self._device)
 
     def read_tensor(self, what: int, name: str) -> torch.Tensor:
@@ -100,11 +118,11 @@ class HipMelanomaClassifier:
 
     def grads(self) -> "OrderedDict[str, torch.Tensor]":
         """the gradients of the last ``loss_backward`` (or ``set_grads``), CPU tensors under the state-dict names"""
-        return OrderedDict((n, self.read_tensor(1, n)) for n in self.trainable_names())
+        return OrderedDict((n, self.read_tensor(1, n)) for n in self.trainable_names(self._mode()))
 
     def set_grads(self, grads: Dict[str, torch.Tensor]) -> None:
         """gradients of the caller's choosing (optimizer parity tests): every trainable tensor must be given"""
-        names = self.trainable_names()
+        names = self.trainable_names(self._mode())
         missing = [n for n in names if n not in grads]
         if missing or len(grads) != len(names):
             raise ValueError(f"set_grads needs exactly the {len(names)} trainable tensors; missing {missing[:3]}")
@@ -112,9 +130,11 @@ class HipMelanomaClassifier:
             self.write_tensor(1, n, grads[n])
 
     def loss_backward(self, images: torch.Tensor, labels, class_weights=None, preprocessed: bool = False):
-        """``loss = F.cross_entropy(model(images), labels, weight=class_weights); loss.backward()`` with BatchNorm frozen, in one
-        library call (sisic_resnet_loss_backward): returns ``(loss, logits)``, the loss a float, the logits the forward's own
-        bits.  The gradients replace those of the previous call (``grads()``).  Needs a ``train.HipClassifierAdam``."""
+        """``loss = F.cross_entropy(model(images), labels, weight=class_weights); loss.backward()`` in one library call
+        (sisic_resnet_loss_backward): returns ``(loss, logits)``, the loss a float, the logits the forward's own bits.  The
+        gradients replace those of the previous call (``grads()``).  Needs a ``train.HipClassifierAdam``; its ``batchnorm`` mode
+        decides whether BatchNorm is frozen or uses (and updates) batch statistics, in which case the logits are the
+        training-mode ones and the running statistics move by one update."""
         h = self.handle
         if images.device != self._device:
             images = images.to(self._device)
@@ -138,12 +158,19 @@ class HipMelanomaClassifier:
         a.B, a.H, a.W, a.preprocess = B, H, W, 0 if preprocessed else 1
         a.stream = torch.cuda.current_stream(x.device).cuda_stream
         check(_lib.load().sisic_resnet_loss_backward(h, C.byref(a)))
+        if self._mode() == "batch":                      # the forward moved the running statistics
+            self._params_stale = True
+            for v in self._batches_tracked.values():
+                v += 1
         return float(a.loss), logits
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         """strict=False keeps only keys whose name AND shape match, like load_classifier_with_fallback
-        (XAI.py:518-527).  Integer buffers (num_batches_tracked) are ignored either way."""
+        (XAI.py:518-527).  Integer buffers (num_batches_tracked) do not reach the library; they are kept on the host, counted up by
+        training forwards with batch statistics, and returned by ``state_dict()``."""
         sd = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
+        tracked = OrderedDict((k, torch.as_tensor(v).detach().to("cpu", torch.int64).clone()) for k, v in state_dict.items()
+                              if k.endswith("num_batches_tracked") and k[:-len("num_batches_tracked")] + "running_var" in self._spec)
         self._sync_params()
         cur = dict(self._params)
         new = OrderedDict()
@@ -163,6 +190,7 @@ class HipMelanomaClassifier:
             if extra:
                 raise RuntimeError(f"unexpected keys in state_dict: {extra[:5]}")
         self._params = new
+        self._batches_tracked = tracked
         self._uploaded = False
         if self._device.type == "cuda":
             self._upload()

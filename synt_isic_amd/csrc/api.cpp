@@ -6,6 +6,7 @@
 #include "common.h"
 #include "conv_plan.h"
 #include "gn_finalize.h"
+#include "train.h"
 
 namespace sisic {
 
@@ -107,6 +108,8 @@ int sisic_destroy(sisic_ctx* ctx) {
     for (auto& kv : ctx->splitk)
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : ctx->attn_rows)
+        if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : ctx->bn_part)
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& it : ctx->bf3_items) {
         if (it.fill_done) (void)hipEventDestroy(it.fill_done);
@@ -357,6 +360,29 @@ int sisic_augment_u8(sisic_ctx* ctx, const uint8_t* dataset, int N, int H, int W
                      int B, int32_t* gray_mean_scratch, uint8_t* out_hwc, void* stream) {
     SISIC_REQUIRE(ctx, "augment_u8: null context");
     return launch_augment(ctx, dataset, N, H, W, params_dev, B, gray_mean_scratch, out_hwc, true, static_cast<hipStream_t>(stream));
+}
+
+int sisic_batchnorm_train(sisic_ctx* ctx, sisic_bn_args* a) {
+    SISIC_REQUIRE(ctx && a, "batchnorm_train: null argument");
+    SISIC_REQUIRE(a->y && a->mean && a->invstd && (!a->out || (a->gamma && a->beta)), "batchnorm_train: y, mean and invstd are required, and gamma and beta with out");
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    SISIC_TRY(launch_bn_moments(ctx, a->y, a->B, a->C, a->HW, a->eps, a->mean, a->invstd, nullptr, a->running_mean, a->running_var,
+                                a->momentum, s));
+    if (!a->out) return SISIC_OK;              // the moments alone
+    return launch_bn_apply(ctx, a->y, a->gamma, a->beta, a->mean, a->invstd, a->residual, a->relu != 0, a->out, a->B, a->C, a->HW, s);
+}
+
+int sisic_batchnorm_train_bwd(sisic_ctx* ctx, sisic_bn_args* a) {
+    SISIC_REQUIRE(ctx && a, "batchnorm_train_bwd: null argument");
+    SISIC_REQUIRE(a->g && a->y && a->gamma && a->mean && a->invstd && a->dgamma && a->dbeta,
+                  "batchnorm_train_bwd: g, y, gamma, mean, invstd, dgamma and dbeta are required");
+    return launch_bn_bwd(ctx, a->g, a->y, a->act, a->mean, a->invstd, a->gamma, a->dy, a->dgamma, a->dbeta, a->B, a->C, a->HW,
+                         static_cast<hipStream_t>(a->stream));
+}
+
+int sisic_add_relu(sisic_ctx* ctx, sisic_bn_args* a) {
+    SISIC_REQUIRE(ctx && a && a->y && a->residual && a->out && a->B > 0 && a->C > 0 && a->HW > 0, "add_relu: y, residual, out and a shape are required");
+    return launch_add_relu(ctx, a->y, a->residual, a->out, (int64_t)a->B * a->C * a->HW, static_cast<hipStream_t>(a->stream));
 }
 
 int sisic_profile_enable(sisic_ctx* ctx, int on) {

@@ -77,6 +77,10 @@ struct sisic_ctx {
     // kernel to its key-owned kernel: one buffer per stream, grown on demand, for the same reason
     std::map<hipStream_t, SplitK> attn_rows;
     std::mutex attn_rows_mutex;
+    // slice partials of the training-mode BatchNorm launches (batchnorm.hip), handed from the slice kernel to the merge
+    // kernel: one buffer per stream, grown on demand, for the same reason
+    std::map<hipStream_t, SplitK> bn_part;
+    std::mutex bn_part_mutex;
     // item tables of the bf16x3 Winograd kernel (conv_winograd_bf3.inc): one per launch geometry, filled on the device the
     // first time the geometry is met, never moved or freed before the context (captured graphs hold their addresses)
     // (fill_done: recorded behind the fill; until it has passed, only launches on the filling stream use the table)

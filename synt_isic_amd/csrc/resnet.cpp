@@ -6,9 +6,13 @@
 // so every conv+BN(+ReLU)(+identity) is ONE launch of conv_mfma_kernel with its bias / residual / ReLU
 // epilogue.  The pre-processing of XAI.py:399-431 is one fused kernel (classifier.hip).
 //
-// Training (the second half of this file) keeps BatchNorm frozen: the training forward is this forward, the backward pass is
+// Training (the second half of this file), BatchNorm frozen: the training forward is this forward, the backward pass is
 // the data-gradient walk of sisic_resnet_input_gradient with a weight gradient issued at every convolution, and after the
 // Adam step the folded filters are derived again on the device from the un-folded parameters.
+// Training with batch statistics (the last part): every convolution runs with its UNFOLDED filters and is followed by the
+// BatchNorm launches of batchnorm.hip; the walk gains a BatchNorm backward in front of every weight gradient, gamma and beta
+// train, the running statistics follow the batches, and every optimizer step derives the folded inference forms again from
+// (w, gamma, beta, running_mean, running_var) with the load path's arithmetic.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -35,6 +39,15 @@ struct FoldedConv {
     double* sc = nullptr;            // BatchNorm scale gamma / sqrt(var + eps) per output channel, in double (sisic_resnet_randomize)
     float* packed_t = nullptr;       // packed [cout -> cin] filters W'[ci][co][a][b] = W[co][ci][k-1-a][k-1-b]
     float* wino_t = nullptr;         // their Winograd form (3x3 stride 1 only)
+    // batch-statistics training only (sisic_resnet_train_begin_bn, mode 1; NULL otherwise): the same forms of the UNFOLDED
+    // weight, which itself lives in the parameter arena.  The 7x7 stem has the packed form alone.
+    struct Plain {
+        float* raw_t = nullptr;
+        float* packed = nullptr;
+        float* wino = nullptr;
+        float* packed_t = nullptr;
+        float* wino_t = nullptr;
+    } u;
 };
 
 struct Block {
@@ -61,6 +74,19 @@ struct ResnetTrain {
     std::vector<int> labels_host;    // staging of the labels and the class weights of a call
     std::vector<float> cw_host;
     int64_t step = 0;
+    // batch-statistics BatchNorm (bn_mode 1): gamma and beta have offsets in `off` like every trainable tensor; the 40 running
+    // statistics live in a buffer arena of their own (boff: offset, -1 for everything else)
+    int bn_mode = 0;
+    double momentum = 0.1;
+    std::vector<int64_t> boff;
+    size_t buf_floats = 0;
+    float* buf = nullptr;
+    bool stats_moved = false;        // a loss_backward updated the running statistics after the folded forms were last derived
+    std::vector<float*> plain_owned; // the second set of filter forms (FoldedConv::u)
+    // the unfolded forms, rebuilt by three batched launches: raw_t / packed / first Winograd layout from the arena, then what
+    // reads those, then the Winograd layouts of the transposed filters
+    void* plain_dev[3] = {nullptr, nullptr, nullptr};
+    int plain_jobs[3] = {0, 0, 0}, plain_blocks[3] = {0, 0, 0};
 };
 
 }  // namespace
@@ -337,6 +363,12 @@ void train_free(sisic_resnet* r) {
     for (float* p : {tr->param, tr->grad, tr->adam_m, tr->adam_v, tr->part}) (void)hipFree(p);
     (void)hipFree(tr->stats);
     for (void* p : tr->repack_dev) (void)hipFree(p);
+    (void)hipFree(tr->buf);
+    for (void* p : tr->plain_dev) (void)hipFree(p);
+    for (float* p : tr->plain_owned) (void)hipFree(p);
+    auto forget = [](FoldedConv& c) { c.u = FoldedConv::Plain(); };
+    forget(r->stem);
+    for (auto& b : r->blocks) { forget(b.conv1); forget(b.conv2); forget(b.down); }
     delete tr;
     r->train = nullptr;
 }
@@ -655,7 +687,7 @@ WgradArgs wgrad_args(const FoldedConv& c, const float* in, const float* even, in
 
 // every plane a stride-2 layer reads has even sizes (the zero-insertion form of its transposed convolution, the stem's weight
 // gradient): checked before anything is launched
-int check_train_geometry(int H, int W, int preprocess) {
+int check_train_geometry(int H, int W, int preprocess, int bn_batch) {
     int h = preprocess ? 224 : H, w = preprocess ? 224 : W;
     SISIC_REQUIRE(!preprocess || (H <= 224 && W <= 224), "resnet_loss_backward: input %dx%d larger than the classifier's 224x224", H, W);
     SISIC_REQUIRE(h >= 8 && w >= 8 && h % 2 == 0 && w % 2 == 0, "resnet_loss_backward: odd feature map: the stem reads %dx%d (even sizes from 8)", h, w);
@@ -666,6 +698,9 @@ int check_train_geometry(int H, int W, int preprocess) {
         SISIC_REQUIRE(h % 2 == 0 && w % 2 == 0, "resnet_loss_backward: odd feature map %dx%d before layer%d", h, w, l + 1);
         h /= 2; w /= 2;
     }
+    // batch statistics: the last plane's BatchNorm needs more than one value per channel
+    SISIC_REQUIRE(bn_batch == 0 || (int64_t)bn_batch * h * w >= 2, "resnet_loss_backward: batch %d at a last plane of %dx%d: BatchNorm "
+                  "with batch statistics expects more than 1 value per channel", bn_batch, h, w);
     return SISIC_OK;
 }
 
@@ -673,11 +708,293 @@ GradStats* stats_record(ResnetTrain* tr) { return static_cast<GradStats*>(tr->st
 float* loss_slot(ResnetTrain* tr) { return reinterpret_cast<float*>(static_cast<char*>(tr->stats) + 12); }
 void* stats_scratch(ResnetTrain* tr) { return static_cast<char*>(tr->stats) + 16; }
 
-}  // namespace
+// ================================================================ batch-statistics BatchNorm ========================
+float* param_of(ResnetTrain* tr, int idx) { return tr->param + tr->off[idx]; }
+float* grad_of(ResnetTrain* tr, int idx) { return tr->grad + tr->off[idx]; }
+float* stat_of(ResnetTrain* tr, int idx) { return tr->buf + tr->boff[idx]; }
 
-extern "C" {
+// every form of the UNFOLDED weights from the parameter arena: what the training forward and the walk read
+int rebuild_plain_forms(sisic_resnet* r, hipStream_t s) {
+    ResnetTrain* tr = r->train;
+    SISIC_TRY(launch_conv_pack(r->ctx, param_of(tr, r->stem.w_idx), r->stem.cout, r->stem.cin, r->stem.k, r->stem.u.packed, s));
+    for (int p = 0; p < 3; ++p)
+        SISIC_TRY(launch_pack_batch(r->ctx, static_cast<const PackJob*>(tr->plain_dev[p]), tr->plain_jobs[p], tr->plain_blocks[p], s));
+    return SISIC_OK;
+}
 
-int sisic_resnet_train_begin(sisic_resnet* r) {
+// The folded inference forms from (w, gamma, beta, running_mean, running_var) as they stand on the device: the scale and the
+// bias in double (launch_bn_fold: fold()'s arithmetic), then the refold and the batched repack of the frozen mode's step.
+int refresh_inference_forms(sisic_resnet* r, hipStream_t s) {
+    ResnetTrain* tr = r->train;
+    SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) {
+        SISIC_TRY(launch_bn_fold(r->ctx, param_of(tr, c.bn_w), param_of(tr, c.bn_b), stat_of(tr, c.bn_m), stat_of(tr, c.bn_v), BN_EPS, c.sc,
+                                 c.bias, c.cout, s));
+        return launch_refold(r->ctx, param_of(tr, c.w_idx), c.sc, c.raw, c.raw_t, c.cout, c.cin, c.k, s);
+    }));
+    SISIC_TRY(fold_pack(r, r->stem, s));
+    for (int p = 0; p < 2; ++p)
+        SISIC_TRY(launch_pack_batch(r->ctx, static_cast<const PackJob*>(tr->repack_dev[p]), tr->repack_jobs[p], tr->repack_blocks[p], s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, param_of(tr, r->fc_w), (size_t)r->numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, param_of(tr, r->fc_b), (size_t)r->numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    tr->stats_moved = false;
+    return SISIC_OK;
+}
+
+// the buffer arena of the running statistics, the second set of filter buffers and its job lists, and the first build of the set
+// (the caller, train_begin, has filled the parameter arena and synchronises the device afterwards)
+int train_begin_plain(sisic_resnet* r) {
+    ResnetTrain* tr = r->train;
+    for_each_conv(r, [&](FoldedConv& c) {
+        for (int idx : {c.bn_m, c.bn_v}) {
+            tr->boff[idx] = (int64_t)tr->buf_floats;
+            tr->buf_floats += (size_t)round_up((int)r->numels[idx], 4);
+        }
+        return SISIC_OK;
+    });
+    {
+        void* p = nullptr;
+        SISIC_HIP(hipMalloc(&p, tr->buf_floats * sizeof(float)));
+        tr->buf = static_cast<float*>(p);
+        SISIC_TRY(poison_fresh(p, tr->buf_floats * sizeof(float)));
+        SISIC_HIP(hipMemset(p, 0, tr->buf_floats * sizeof(float)));
+    }
+    for (int i = 0; i < (int)r->names.size(); ++i)
+        if (tr->boff[i] >= 0)
+            SISIC_HIP(hipMemcpy(tr->buf + tr->boff[i], r->host[i].data(), r->host[i].size() * sizeof(float), hipMemcpyHostToDevice));
+    auto alloc = [&](size_t floats, float** out) {
+        void* p = nullptr;
+        SISIC_HIP(hipMalloc(&p, std::max<size_t>(floats, 4) * sizeof(float)));
+        tr->plain_owned.push_back(static_cast<float*>(p));
+        SISIC_TRY(poison_fresh(p, std::max<size_t>(floats, 4) * sizeof(float)));
+        *out = static_cast<float*>(p);
+        return SISIC_OK;
+    };
+    std::vector<PackJob> ph[3];
+    SISIC_TRY(alloc((size_t)sisic_conv_packed_numel(r->stem.cout, r->stem.cin, r->stem.k), &r->stem.u.packed));
+    auto plan = [&](FoldedConv& c) {
+        const float* w = param_of(tr, c.w_idx);
+        SISIC_TRY(alloc((size_t)c.cout * c.cin * c.k * c.k, &c.u.raw_t));
+        SISIC_TRY(alloc((size_t)sisic_conv_packed_numel(c.cout, c.cin, c.k), &c.u.packed));
+        SISIC_TRY(alloc((size_t)sisic_conv_packed_numel(c.cin, c.cout, c.k), &c.u.packed_t));
+        ph[0].push_back(pack_job_flip(w, c.cout, c.cin, c.k * c.k, c.u.raw_t));
+        ph[0].push_back(pack_job_conv(w, c.cout, c.cin, c.k, c.u.packed));
+        ph[1].push_back(pack_job_conv(c.u.raw_t, c.cin, c.cout, c.k, c.u.packed_t));
+        if (c.wino) {
+            SISIC_TRY(alloc((size_t)winograd_packed_numel(c.cout, c.cin), &c.u.wino));
+            SISIC_TRY(alloc((size_t)winograd_packed_numel(c.cin, c.cout), &c.u.wino_t));
+            ph[0].push_back(pack_job_wino_first(w, c.cout, c.cin, c.u.wino));
+            ph[1].push_back(pack_job_wino_wide(c.cout, c.cin, c.u.wino));
+            ph[1].push_back(pack_job_wino_bf3(c.cout, c.cin, c.u.wino));
+            ph[1].push_back(pack_job_wino_first(c.u.raw_t, c.cin, c.cout, c.u.wino_t));
+            ph[2].push_back(pack_job_wino_wide(c.cin, c.cout, c.u.wino_t));
+            ph[2].push_back(pack_job_wino_bf3(c.cin, c.cout, c.u.wino_t));
+        }
+        return SISIC_OK;
+    };
+    for (Block& b : r->blocks) {
+        SISIC_TRY(plan(b.conv1));
+        SISIC_TRY(plan(b.conv2));
+        if (b.down.k) SISIC_TRY(plan(b.down));
+    }
+    for (int p = 0; p < 3; ++p) {
+        int blocks = 0;
+        for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
+        SISIC_HIP(hipMalloc(&tr->plain_dev[p], ph[p].size() * sizeof(PackJob)));
+        SISIC_HIP(hipMemcpy(tr->plain_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
+        tr->plain_jobs[p] = (int)ph[p].size();
+        tr->plain_blocks[p] = blocks;
+    }
+    return rebuild_plain_forms(r, nullptr);
+}
+
+// what the training forward keeps of one BatchNorm: the convolution's output y and (mean, invstd, var) [3][C]
+struct BnKept {
+    float* y = nullptr;
+    float* st = nullptr;
+    int C = 0, HW = 0;
+};
+
+// loss and the 62 gradients with batch statistics (the caller, sisic_resnet_loss_backward, has checked the arguments, staged the
+// labels and sized the workspace).  Forward: conv (unfolded filters, no bias) -> moments (which also move the running statistics)
+// -> apply, everything kept.  Backward: the walk of the frozen mode with launch_bn_bwd in front of every weight gradient and
+// transposed convolution; the ReLU behind bn1 is masked inside its BatchNorm backward (from the kept t1), the other two
+// BatchNorms of a block and the stem's receive gradients that are masked already.
+int loss_backward_bn(sisic_resnet* r, sisic_resnet_train_args* a) {
+    ResnetTrain* tr = r->train;
+    const int B = a->B, H = a->H, W = a->W, n = r->num_classes;
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    PoolScope ws(r->pool, s);
+    // convolution with the unfolded filters; transposed: of g [B, c.cout, gh, gw] (stride 2: zero-insertion input)
+    auto conv = [&](const FoldedConv& c, const float* in, int h, int w, float* out) {
+        sisic_conv_args ca{};
+        ca.in0 = in; ca.c0 = c.cin; ca.B = B; ca.Hin = h; ca.Win = w;
+        ca.ksize = c.k; ca.stride = c.stride;
+        ca.w_packed = c.u.packed; ca.w_winograd = c.u.wino; ca.Cout = c.cout;
+        ca.out = out;
+        return launch_conv2d(r->ctx, ca, s);
+    };
+    auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
+        sisic_conv_args ca{};
+        ca.in0 = g; ca.c0 = c.cout; ca.B = B; ca.Hin = gh; ca.Win = gw;
+        ca.ksize = c.k; ca.stride = 1;
+        ca.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
+        ca.w_packed = c.u.packed_t; ca.w_winograd = c.u.wino_t; ca.Cout = c.cin;
+        ca.residual = residual; ca.out = out;
+        return launch_conv2d(r->ctx, ca, s);
+    };
+    auto wgrad = [&](const FoldedConv& c, const float* in, const float* even, int h, int w, const float* dy) {
+        const WgradArgs wa = wgrad_args(c, in, even, B, h, w, dy, grad_of(tr, c.w_idx));
+        return launch_conv_wgrad(r->ctx, wa, tr->part, tr->part_floats, s);
+    };
+    // out = [relu](bn(conv(in)) [+ residual]), y and the moments kept
+    auto conv_bn = [&](const FoldedConv& c, const float* in, int h, int w, const float* residual, bool relu, float* out, BnKept& k) {
+        const int oh = out_dim(h, c.k, c.stride), ow = out_dim(w, c.k, c.stride);
+        k.C = c.cout; k.HW = oh * ow;
+        SISIC_TRY(ws.get((size_t)B * k.C * k.HW, &k.y));
+        SISIC_TRY(ws.get(3 * (size_t)k.C, &k.st));
+        SISIC_TRY(conv(c, in, h, w, k.y));
+        SISIC_TRY(launch_bn_moments(r->ctx, k.y, B, k.C, k.HW, BN_EPS, k.st, k.st + k.C, k.st + 2 * k.C, stat_of(tr, c.bn_m),
+                                    stat_of(tr, c.bn_v), tr->momentum, s));
+        return launch_bn_apply(r->ctx, k.y, param_of(tr, c.bn_w), param_of(tr, c.bn_b), k.st, k.st + k.C, residual, relu, out, B, k.C, k.HW, s);
+    };
+    // dy (a new block) = BatchNorm backward of g; dgamma and dbeta into the gradient arena; y and the moments go back to the pool
+    auto bn_bwd = [&](const FoldedConv& c, BnKept& k, const float* g, const float* act, float** dy) {
+        SISIC_TRY(ws.get((size_t)B * k.C * k.HW, dy));
+        SISIC_TRY(launch_bn_bwd(r->ctx, g, k.y, act, k.st, k.st + k.C, param_of(tr, c.bn_w), *dy, grad_of(tr, c.bn_w), grad_of(tr, c.bn_b), B,
+                                k.C, k.HW, s));
+        ws.put(k.y);
+        ws.put(k.st);
+        return SISIC_OK;
+    };
+    float* lab = nullptr;
+    SISIC_TRY(ws.get((size_t)B + n, &lab));
+    SISIC_HIP(hipMemcpyAsync(lab, tr->labels_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    if (a->class_weights) SISIC_HIP(hipMemcpyAsync(lab + B, tr->cw_host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+
+    // ---- forward
+    tr->stats_moved = true;
+    const float* x = a->x;
+    int h = H, w = W;
+    float* pre = nullptr;
+    if (a->preprocess) {
+        const int S = 224;
+        SISIC_TRY(ws.get((size_t)B * 3 * S * S, &pre));
+        SISIC_TRY(launch_preprocess(r->ctx, a->x, pre, B, H, W, S, S, s));
+        x = pre; h = S; w = S;
+    }
+    const int sh = h, sw = w;
+    const int c1h = out_dim(h, 7, 2), c1w = out_dim(w, 7, 2);
+    BnKept stem_k;
+    float* c1 = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &c1));
+    SISIC_TRY(conv_bn(r->stem, x, h, w, nullptr, true, c1, stem_k));
+    h = c1h; w = c1w;
+    const int mh = out_dim(h, 3, 2), mw = out_dim(w, 3, 2);
+    float* m = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 64 * mh * mw, &m));
+    SISIC_TRY(launch_maxpool(r->ctx, c1, m, B, 64, h, w, s));
+    struct Saved { BnKept k1, k2, kd; float* t1; float* out; int h, w, bh, bw; };
+    std::vector<Saved> saved(r->blocks.size());
+    float* act = m;
+    h = mh; w = mw;
+    for (size_t i = 0; i < r->blocks.size(); ++i) {
+        const Block& b = r->blocks[i];
+        Saved& sv = saved[i];
+        sv.h = h; sv.w = w;
+        sv.bh = out_dim(h, 3, b.conv1.stride); sv.bw = out_dim(w, 3, b.conv1.stride);
+        const size_t n_out = (size_t)B * b.conv1.cout * sv.bh * sv.bw;
+        SISIC_TRY(ws.get(n_out, &sv.t1));
+        SISIC_TRY(conv_bn(b.conv1, act, h, w, nullptr, true, sv.t1, sv.k1));
+        const float* identity = act;
+        float* ds = nullptr;
+        if (b.down.k) {
+            SISIC_TRY(ws.get(n_out, &ds));
+            SISIC_TRY(conv_bn(b.down, act, h, w, nullptr, false, ds, sv.kd));
+            identity = ds;
+        }
+        SISIC_TRY(ws.get(n_out, &sv.out));
+        SISIC_TRY(conv_bn(b.conv2, sv.t1, sv.bh, sv.bw, identity, true, sv.out, sv.k2));    // relu(bn2(conv2) + identity): one pass
+        if (ds) ws.put(ds);
+        act = sv.out; h = sv.bh; w = sv.bw;
+    }
+    const int C = r->blocks.back().conv2.cout;
+    float* logits = nullptr;
+    SISIC_TRY(ws.get((size_t)B * n, &logits));
+    SISIC_TRY(launch_avgpool_fc(r->ctx, act, param_of(tr, r->fc_w), param_of(tr, r->fc_b), logits, B, C, h * w, n, s));
+    if (a->logits_out)
+        SISIC_HIP(hipMemcpyAsync(a->logits_out, logits, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+
+    // ---- head
+    float* dlogits = nullptr;
+    SISIC_TRY(ws.get((size_t)B * n, &dlogits));
+    SISIC_TRY(launch_ce_head(r->ctx, logits, reinterpret_cast<const int*>(lab), a->class_weights ? lab + B : nullptr, B, n, loss_slot(tr),
+                             dlogits, s));
+    float* g = nullptr;                                   // d loss / d (block output), already ReLU-masked
+    SISIC_TRY(ws.get((size_t)B * C * h * w, &g));
+    SISIC_TRY(launch_fc_head_bwd(r->ctx, dlogits, param_of(tr, r->fc_w), act, g, grad_of(tr, r->fc_w), grad_of(tr, r->fc_b), B, C, h * w, n, s));
+    ws.put(dlogits);
+    ws.put(logits);
+    ws.put(lab);
+    // ---- the blocks, last to first
+    for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
+        const Block& b = r->blocks[k];
+        Saved& sv = saved[k];
+        const float* in_act = k > 0 ? saved[k - 1].out : m;            // the block's input [B, conv1.cin, sv.h, sv.w]
+        float* dy2 = nullptr;
+        SISIC_TRY(bn_bwd(b.conv2, sv.k2, g, nullptr, &dy2));
+        SISIC_TRY(wgrad(b.conv2, sv.t1, nullptr, sv.bh, sv.bw, dy2));
+        float* tmp = nullptr;                             // conv2^T dy2 = the gradient at t1, before its ReLU mask
+        SISIC_TRY(ws.get((size_t)B * b.conv2.cout * sv.bh * sv.bw, &tmp));
+        SISIC_TRY(conv_t(b.conv2, dy2, sv.bh, sv.bw, nullptr, tmp));
+        ws.put(dy2);
+        float* dy1 = nullptr;
+        SISIC_TRY(bn_bwd(b.conv1, sv.k1, tmp, sv.t1, &dy1));          // the mask of t1 is applied here
+        ws.put(tmp);
+        SISIC_TRY(wgrad(b.conv1, in_act, nullptr, sv.h, sv.w, dy1));
+        const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
+        float* da = nullptr;
+        SISIC_TRY(ws.get(n_in, &da));
+        if (!b.down.k) {
+            SISIC_TRY(conv_t(b.conv1, dy1, sv.bh, sv.bw, g, da));                 // + identity path
+        } else {
+            SISIC_TRY(conv_t(b.conv1, dy1, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
+            float* dyd = nullptr;
+            SISIC_TRY(bn_bwd(b.down, sv.kd, g, nullptr, &dyd));
+            float* small = nullptr;                                               // first the even pixels of the input ...
+            SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
+            SISIC_TRY(launch_gather_even(r->ctx, in_act, small, B * b.down.cin, sv.h, sv.w, s));
+            SISIC_TRY(wgrad(b.down, nullptr, small, sv.h, sv.w, dyd));
+            SISIC_TRY(conv_t(b.down, dyd, sv.bh, sv.bw, nullptr, small));         // ... then the 1x1 at the low resolution
+            SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
+            ws.put(small);
+            ws.put(dyd);
+        }
+        ws.put(dy1);
+        ws.put(g);
+        ws.put(sv.t1);
+        ws.put(sv.out);
+        if (k > 0) SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));      // ReLU of the previous block's output
+        g = da;
+    }
+    // g = d loss / d (max-pool output)
+    float* dc1 = nullptr;
+    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
+    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, c1, dc1, B * 64, c1h, c1w, s));         // includes the stem's ReLU mask
+    ws.put(g);
+    ws.put(m);
+    ws.put(c1);
+    float* dys = nullptr;
+    SISIC_TRY(bn_bwd(r->stem, stem_k, dc1, nullptr, &dys));
+    ws.put(dc1);
+    SISIC_TRY(launch_stem_wgrad(r->ctx, x, dys, grad_of(tr, r->stem.w_idx), B, sh, sw, tr->part, tr->part_floats, s));
+    ws.put(dys);
+    if (pre) ws.put(pre);
+    SISIC_HIP(hipMemcpyAsync(&a->loss, loss_slot(tr), sizeof(float), hipMemcpyDeviceToHost, s));
+    SISIC_HIP(hipStreamSynchronize(s));
+    return SISIC_OK;
+}
+
+int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
     SISIC_REQUIRE(r, "resnet_train_begin: null handle");
     if (!r->loaded) {
         set_error("resnet_train_begin called before sisic_resnet_load");
@@ -691,13 +1008,20 @@ int sisic_resnet_train_begin(sisic_resnet* r) {
     SISIC_HIP(hipDeviceSynchronize());
     auto* tr = new ResnetTrain();
     r->train = tr;                               // (freed by train_end, a reload or destroy, also after an error below)
+    tr->bn_mode = bn_mode;
+    tr->momentum = momentum;
     tr->off.assign(r->names.size(), -1);
+    tr->boff.assign(r->names.size(), -1);
     auto place = [&](int idx) {
         tr->off[idx] = (int64_t)tr->floats;
         tr->floats += (size_t)round_up((int)r->numels[idx], 4);
     };
     std::vector<char> trainable(r->names.size(), 0);
-    for_each_conv(r, [&](FoldedConv& c) { trainable[c.w_idx] = 1; return SISIC_OK; });
+    for_each_conv(r, [&](FoldedConv& c) {
+        trainable[c.w_idx] = 1;
+        if (bn_mode == 1) trainable[c.bn_w] = trainable[c.bn_b] = 1;
+        return SISIC_OK;
+    });
     trainable[r->fc_w] = trainable[r->fc_b] = 1;
     for (int i = 0; i < (int)r->names.size(); ++i)
         if (trainable[i]) place(i);
@@ -762,9 +1086,26 @@ int sisic_resnet_train_begin(sisic_resnet* r) {
             tr->repack_blocks[p] = blocks;
         }
     }
+    if (bn_mode == 1) SISIC_TRY(train_begin_plain(r));
     SISIC_HIP(hipDeviceSynchronize());
     return SISIC_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int sisic_resnet_train_begin(sisic_resnet* r) { return train_begin(r, 0, 0.0); }
+
+int sisic_resnet_train_begin_bn(sisic_resnet* r, const sisic_resnet_bn_config* config) {
+    SISIC_REQUIRE(r && config, "resnet_train_begin_bn: null argument");
+    SISIC_REQUIRE(config->mode == 0 || config->mode == 1, "resnet_train_begin_bn: mode %d (0 frozen, 1 batch statistics)", config->mode);
+    if (config->mode == 0) return train_begin(r, 0, 0.0);
+    SISIC_REQUIRE(config->momentum > 0.0 && config->momentum <= 1.0, "resnet_train_begin_bn: momentum %g is outside (0, 1]", config->momentum);
+    return train_begin(r, 1, config->momentum);
+}
+
+int sisic_resnet_train_bn_mode(const sisic_resnet* r) { return (r && r->train) ? r->train->bn_mode : -1; }
 
 // The device already holds what sisic_resnet_load of the trained state dict would leave (optimizer_step derives every form with
 // the load path's arithmetic); the host copies that sisic_resnet_restore folds from follow here.
@@ -772,10 +1113,14 @@ int sisic_resnet_train_end(sisic_resnet* r) {
     SISIC_TRY(require_train(r, "resnet_train_end"));
     ResnetTrain* tr = r->train;
     SISIC_HIP(hipSetDevice(r->ctx->device));
+    if (tr->bn_mode == 1 && tr->stats_moved) SISIC_TRY(refresh_inference_forms(r, nullptr));
     SISIC_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < (int)r->names.size(); ++i)
+    for (int i = 0; i < (int)r->names.size(); ++i) {
         if (tr->off[i] >= 0)
             SISIC_HIP(hipMemcpy(r->host[i].data(), tr->param + tr->off[i], r->host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (tr->boff[i] >= 0)
+            SISIC_HIP(hipMemcpy(r->host[i].data(), tr->buf + tr->boff[i], r->host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
     train_free(r);
     return SISIC_OK;
 }
@@ -800,11 +1145,18 @@ int sisic_resnet_read(sisic_resnet* r, int what, int index, float* host_out, int
         return SISIC_ESTATE;
     }
     ResnetTrain* tr = r->train;
+    if (what == 0 && tr && tr->boff[index] >= 0) {        // a running statistic of batch-statistics training: its current value
+        SISIC_HIP(hipSetDevice(r->ctx->device));
+        SISIC_HIP(hipDeviceSynchronize());
+        SISIC_HIP(hipMemcpy(host_out, tr->buf + tr->boff[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+        return SISIC_OK;
+    }
     if (what == 0 && (!tr || tr->off[index] < 0)) {       // frozen, or not training: the loaded value
         std::memcpy(host_out, r->host[index].data(), (size_t)numel * sizeof(float));
         return SISIC_OK;
     }
     SISIC_TRY(require_train(r, "resnet_read"));
+    SISIC_REQUIRE(tr->boff[index] < 0, "resnet_read: '%s' is a running statistic: it has no gradient or moment", r->names[index].c_str());
     SISIC_REQUIRE(tr->off[index] >= 0, "resnet_read: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
     const float* base = what == 0 ? tr->param : (what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v));
     SISIC_HIP(hipSetDevice(r->ctx->device));
@@ -821,6 +1173,7 @@ int sisic_resnet_write(sisic_resnet* r, int what, int index, const float* host_i
     SISIC_REQUIRE(what >= 1 && what <= 3, "resnet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
     SISIC_TRY(require_train(r, "resnet_write"));
     ResnetTrain* tr = r->train;
+    SISIC_REQUIRE(tr->boff[index] < 0, "resnet_write: '%s' is a running statistic: it has no gradient or moment", r->names[index].c_str());
     SISIC_REQUIRE(tr->off[index] >= 0, "resnet_write: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
     float* base = what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v);
     SISIC_HIP(hipSetDevice(r->ctx->device));
@@ -854,9 +1207,10 @@ int sisic_resnet_loss_backward(sisic_resnet* r, sisic_resnet_train_args* a) {
         SISIC_REQUIRE(picked > 0.0, "resnet_loss_backward: the weights of the batch's classes sum to zero");
         tr->cw_host.assign(a->class_weights, a->class_weights + n);
     }
-    SISIC_TRY(check_train_geometry(H, W, a->preprocess));
+    SISIC_TRY(check_train_geometry(H, W, a->preprocess, tr->bn_mode == 1 ? B : 0));
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
+    if (tr->bn_mode == 1) return loss_backward_bn(r, a);
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     PoolScope ws(r->pool, s);
     auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
@@ -969,6 +1323,17 @@ int sisic_resnet_optimizer_step(sisic_resnet* r, sisic_resnet_train_args* a) {
     SISIC_HIP(hipStreamSynchronize(s));
     a->grad_norm = host.total_norm;
     a->found_inf = host.found_inf;
+    if (tr->bn_mode == 1) {
+        // batch statistics: the running statistics moved in loss_backward whether or not the update is skipped, so the inference
+        // forms are derived again on every call
+        if (!host.found_inf) {
+            tr->step += 1;
+            SISIC_TRY(launch_adam_ema(r->ctx, tr->param, tr->grad, tr->adam_m, tr->adam_v, nullptr, tr->floats, a->lr, a->beta1, a->beta2,
+                                      a->eps, tr->step, 1.0f, stats_record(tr), 0.0, s));
+            SISIC_TRY(rebuild_plain_forms(r, s));
+        }
+        return refresh_inference_forms(r, s);
+    }
     if (host.found_inf) return SISIC_OK;                 // no update: parameters, moments and the step counter stay
     tr->step += 1;
     SISIC_TRY(launch_adam_ema(r->ctx, tr->param, tr->grad, tr->adam_m, tr->adam_v, nullptr, tr->floats, a->lr, a->beta1, a->beta2, a->eps,

@@ -39,6 +39,24 @@ int launch_fc_head_bwd(sisic_ctx*, const float* dlogits, const float* fc_w, cons
 int launch_unfold_grad(sisic_ctx*, float* g, const double* sc, int cout, int cin, int k, hipStream_t s);
 int launch_refold(sisic_ctx*, const float* w, const double* sc, float* raw, float* raw_t, int cout, int cin, int k, hipStream_t s);
 
+// batchnorm.hip: BatchNorm2d with batch statistics over y [B, C, HW].  B * HW = 1 is SISIC_EINVAL before any launch.
+// moments: mean, invstd = 1/sqrt(var + eps) and (var may be NULL) the biased variance, [C] each; running_mean / running_var
+// (both or neither) receive nn.BatchNorm2d's update with the unbiased variance, momentum in (0, 1].  The slice partials live in
+// the context's per-stream scratch (a larger shape grows it and waits for the stream once).
+int launch_bn_moments(sisic_ctx*, const float* y, int B, int C, int HW, float eps, float* mean, float* invstd, float* var,
+                      float* running_mean, float* running_var, double momentum, hipStream_t s);
+// out = [relu](gamma (y - mean) invstd + beta [+ residual])
+int launch_bn_apply(sisic_ctx*, const float* y, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                    const float* residual, bool relu, float* out, int B, int C, int HW, hipStream_t s);
+// g' = g, or g [act > 0] (act: the kept activation behind the BatchNorm's ReLU, or NULL); dbeta = sum g', dgamma = sum g' xhat,
+// dy = gamma invstd (g' - dbeta/n - xhat dgamma/n); dy is a buffer of its own (NULL: the two sums alone)
+int launch_bn_bwd(sisic_ctx*, const float* g, const float* y, const float* act, const float* mean, const float* invstd,
+                  const float* gamma, float* dy, float* dgamma, float* dbeta, int B, int C, int HW, hipStream_t s);
+// sc = gamma / sqrt(rv + eps) and bias = (float)(beta - rm sc), in double: the fold of sisic_resnet_load
+int launch_bn_fold(sisic_ctx*, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, double* sc,
+                   float* bias, int C, hipStream_t s);
+int bn_slices(int B, int C, int HW);      // slices a channel's moments are split into (a function of the shape alone)
+
 // repack.hip: one re-layout of one tensor inside a batched launch (pack_batch_kernel)
 struct PackJob {
     enum Kind : int { COPY = 0, TRANSPOSE2D, FLIP, CONV_PACK, WINO_FIRST, WINO_WIDE, WINO_BF3, CONV_S2_BF3 };

@@ -489,6 +489,59 @@ def groupnorm_bwd(da: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: 
     return dx, dg, db
 
 
+def batchnorm_train(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, residual=None, relu: bool = False,
+                    running_mean=None, running_var=None, momentum: float = 0.1, apply: bool = True):
+    """``nn.BatchNorm2d`` in training mode on y [B,C,...] (sisic_batchnorm_train): returns ``(out, mean, invstd)`` with
+    ``out = [relu](gamma (y - mean) invstd + beta [+ residual])``, mean and invstd = 1/sqrt(var + eps) of the batch [C].
+    ``running_mean`` / ``running_var`` (both or neither) are updated in place with the unbiased variance.  ``apply=False``: the
+    moments alone, ``out`` is None (what tools time the first launch with)."""
+    lib = _lib.load()
+    B, Cc = y.shape[0], y.shape[1]
+    out = empty_like(y) if apply else None
+    mean = empty(Cc, dtype=torch.float32, device=y.device)
+    invstd = empty_like(mean)
+    a = _lib.BnArgs()
+    a.y = _ptr(y, "y"); a.gamma = _ptr(gamma, "gamma"); a.beta = _ptr(beta, "beta"); a.residual = _ptr(residual, "residual")
+    a.running_mean = _ptr(running_mean, "running_mean"); a.running_var = _ptr(running_var, "running_var")
+    a.out = out.data_ptr() if apply else None; a.mean = mean.data_ptr(); a.invstd = invstd.data_ptr()
+    a.stream = _stream(y.device).value
+    a.momentum = float(momentum); a.eps = float(eps); a.relu = int(bool(relu))
+    a.B, a.C, a.HW = B, Cc, y[0, 0].numel()
+    check(lib.sisic_batchnorm_train(context(y.device), C.byref(a)))
+    return out, mean, invstd
+
+
+def batchnorm_train_bwd(g: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor, act=None,
+                        apply: bool = True):
+    """``(dy, dgamma, dbeta)`` of ``batchnorm_train`` for g = dL/d(out) (sisic_batchnorm_train_bwd).  ``act``: the activation
+    behind the BatchNorm's ReLU; g counts where it is positive (None: no ReLU, or g is masked already).  ``apply=False``: the
+    two sums alone, ``dy`` is None."""
+    lib = _lib.load()
+    B, Cc = y.shape[0], y.shape[1]
+    dy = empty_like(y) if apply else None
+    dgamma = empty(Cc, dtype=torch.float32, device=y.device)
+    dbeta = empty_like(dgamma)
+    a = _lib.BnArgs()
+    a.g = _ptr(g, "g"); a.y = _ptr(y, "y"); a.mean = _ptr(mean, "mean"); a.invstd = _ptr(invstd, "invstd")
+    a.gamma = _ptr(gamma, "gamma"); a.act = _ptr(act, "act")
+    a.dy = dy.data_ptr() if apply else None; a.dgamma = dgamma.data_ptr(); a.dbeta = dbeta.data_ptr()
+    a.stream = _stream(y.device).value
+    a.B, a.C, a.HW = B, Cc, y[0, 0].numel()
+    check(lib.sisic_batchnorm_train_bwd(context(y.device), C.byref(a)))
+    return dy, dgamma, dbeta
+
+
+def add_relu(y: torch.Tensor, identity: torch.Tensor) -> torch.Tensor:
+    """relu(y + identity) (sisic_add_relu): the library's plain elementwise pass, the yardstick of the BatchNorm passes"""
+    out = empty_like(y)
+    a = _lib.BnArgs()
+    a.y = _ptr(y, "y"); a.residual = _ptr(identity, "identity"); a.out = out.data_ptr()
+    a.stream = _stream(y.device).value
+    a.B, a.C, a.HW = 1, 1, y.numel()
+    check(_lib.load().sisic_add_relu(context(y.device), C.byref(a)))
+    return out
+
+
 DENORM_FORMS = {"image_generator": 0, "generate_test": 1, "diffusion_generator": 2}
 
 

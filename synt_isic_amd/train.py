@@ -644,27 +644,40 @@ def train_conditional(model: HipUNet2DModel, loader, name: str, cond_drop_prob: 
                        ema_warmup, lr_schedule, float(cond_drop_prob), dropout_seed, snr_gamma)
 
 
-# ---- the ResNet18 classifier (xai/XAI.py:357-471) with BatchNorm frozen ---------------------------------------------------
-# What the reference leaves to torch: fine-tuning the lesion classifier whose explanations the XAI passes compute.  BatchNorm
-# keeps the constants it was loaded with (torchvision.ops.FrozenBatchNorm2d), which is the function the library's folded
-# forward computes, so the training forward is the inference forward and the trained model needs no other path.  Training is
-# entered through the optimizer object, not through ``clf.train()``, which would promise batch statistics.
+# ---- the ResNet18 classifier (xai/XAI.py:357-471), BatchNorm frozen or with batch statistics ------------------------------
+# What the reference leaves to torch: training the lesion classifier whose explanations the XAI passes compute.
+# batchnorm="frozen" (the default, for fine-tuning a loaded checkpoint): BatchNorm keeps the constants it was loaded with
+# (torchvision.ops.FrozenBatchNorm2d), which is the function the library's folded forward computes, so the training forward is
+# the inference forward.  batchnorm="batch" (for training from random weights, weights.default_init_resnet18_state_dict):
+# nn.BatchNorm2d in training mode -- batch moments in the forward, gamma and beta trained, running statistics updated with
+# ``bn_momentum`` -- and after every step the inference side is the folded form of the current state dict.  Training is entered
+# through the optimizer object, not through ``clf.train()``.
 class HipClassifierAdam:
-    """``torch.optim.Adam`` over the 22 trainable tensors of a HipMelanomaClassifier (20 convolution weights, fc.weight,
-    fc.bias); parameters, gradients and moments live in the library (sisic_resnet_train_begin on construction).
+    """``torch.optim.Adam`` over the trainable tensors of a HipMelanomaClassifier: with ``batchnorm="frozen"`` the 22 (20
+    convolution weights, fc.weight, fc.bias), with ``batchnorm="batch"`` the 62 (the BatchNorm gamma and beta as well; the
+    running statistics follow the batches with ``bn_momentum``, torch's ``momentum``, in (0, 1]).  Parameters, gradients and
+    moments live in the library (sisic_resnet_train_begin / _begin_bn on construction).
     ``max_grad_norm``: ``clip_grad_norm_`` in front of every step; ``grad_norm`` is the norm of the last step before clipping.
     ``close()`` ends training (sisic_resnet_train_end): the model is then what loading its ``state_dict()`` would give."""
 
-    def __init__(self, clf, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+    def __init__(self, clf, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+                 batchnorm: str = "frozen", bn_momentum: float = 0.1):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
+        if batchnorm not in ("frozen", "batch"):
+            raise ValueError(f"batchnorm {batchnorm!r}: 'frozen' or 'batch'")
         handle = clf.handle                      # a model on the CPU raises here: MI355X only
         if clf._trainer is not None:
             raise RuntimeError("this classifier already has a HipClassifierAdam; close() it first")
         self.clf, self.lr, self.betas, self.eps = clf, float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm: Optional[float] = None
-        check(_lib.load().sisic_resnet_train_begin(handle))
+        self.batchnorm, self.bn_momentum = batchnorm, float(bn_momentum)
+        if batchnorm == "batch":
+            cfg = _lib.ResnetBnConfig(1, self.bn_momentum)
+            check(_lib.load().sisic_resnet_train_begin_bn(handle, C.byref(cfg)))
+        else:
+            check(_lib.load().sisic_resnet_train_begin(handle))
         self._active = True
         clf._trainer = self
 
@@ -688,6 +701,8 @@ class HipClassifierAdam:
         a.stream = torch.cuda.current_stream(self.clf.device).cuda_stream
         check(_lib.load().sisic_resnet_optimizer_step(self._handle(), C.byref(a)))
         self.grad_norm = float(a.grad_norm)
+        if self.batchnorm == "batch":
+            self.clf._params_stale = True         # the running statistics moved in loss_backward, whatever the step did
         if a.found_inf:
             return False
         self.clf._params_stale = True
@@ -733,10 +748,11 @@ def evaluate_classifier(clf, loader) -> Dict[str, object]:
 
 def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=None, val_loader=None,
                      save_dir: Optional[str] = None, max_grad_norm: Optional[float] = None,
-                     log: Optional[Callable[[str], None]] = print):
+                     log: Optional[Callable[[str], None]] = print, batchnorm: str = "frozen", bn_momentum: float = 0.1):
     """``train_class``'s loop for the classifier: epochs over ``loader`` (items ``(images, labels)``, images in [-1,1] as the
     sampler makes them -- a ``data.DeviceLoader`` over ``DeviceDataset.from_isic_classes``), cross-entropy, Adam, BatchNorm
-    frozen.  ``class_weights``: None, a [num_classes] tensor, or ``"balanced"`` (inverse class frequency from
+    frozen or, with ``batchnorm="batch"``, with batch statistics (``bn_momentum``: see ``HipClassifierAdam``; validation uses
+    the running statistics, as ``model.eval()`` does).  ``class_weights``: None, a [num_classes] tensor, or ``"balanced"`` (inverse class frequency from
     ``loader.dataset.labels``; ISIC is 67 % NV).  ``val_loader``: ``evaluate_classifier`` after every epoch, its balanced
     accuracy selects the best checkpoint (otherwise the epoch loss does).  ``save_dir``: ``classifier.pth`` under the
     reference's key names (``model.`` prefix), which ``load_state_dict`` here and the reference's
@@ -749,7 +765,7 @@ def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=Non
         if labels is None:
             raise ValueError("class_weights='balanced' needs loader.dataset.labels")
         class_weights = balanced_class_weights(labels, clf.num_classes)
-    optimizer = HipClassifierAdam(clf, lr=lr, max_grad_norm=max_grad_norm)
+    optimizer = HipClassifierAdam(clf, lr=lr, max_grad_norm=max_grad_norm, batchnorm=batchnorm, bn_momentum=bn_momentum)
     history = []
     best = None
     try:

@@ -99,3 +99,26 @@ def synthetic_resnet18_state_dict(seed: int = 4321, num_classes: int = 7) -> "Or
         else:
             sd[name] = 1.0 + 0.1 * torch.randn(shape, generator=g, dtype=torch.float32)
     return sd
+
+
+def default_init_resnet18_state_dict(seed: int = 0, num_classes: int = 7) -> "OrderedDict[str, torch.Tensor]":
+    """What an untrained ``torchvision.models.resnet18()`` (fc -> num_classes) holds, from one seeded CPU generator walking the
+    tensors in state-dict order: convolution weights kaiming-normal with fan-out and ReLU gain (std = sqrt(2 / (cout k k))),
+    BatchNorm gamma 1, beta 0, running statistics (0, 1), and ``nn.Linear``'s default for fc (weight and bias
+    U(+-1/sqrt(fan_in))).  The starting point of training from scratch with batch-statistics BatchNorm."""
+    from .arch import resnet18_param_spec
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape in resnet18_param_spec(num_classes).items():
+        if len(shape) == 4:
+            std = math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
+            sd[name] = torch.randn(shape, generator=g, dtype=torch.float32) * std
+        elif name.startswith("model.fc."):
+            bound = 1.0 / math.sqrt(512.0)
+            sd[name] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2 - 1) * bound
+        elif name.endswith("running_var") or name.endswith(".weight"):
+            sd[name] = torch.ones(shape, dtype=torch.float32)
+        else:
+            sd[name] = torch.zeros(shape, dtype=torch.float32)
+    return sd
