@@ -383,7 +383,8 @@ int sisic_sample_frames(sisic_unet*, float* x, int B, int H, int W, int T, const
  * u2 = (r >> 8) * 2^-24.  tag 0: the per-step noise of the sampling loop; tag 1: reserved for an x_T; tag 2: the noise
  * interventions of sisic_intervene; tag 3: the bootstrap resamples and tag 4: the permutation resamples of
  * sisic_resample_diffs (raw words, step = the resample); tag 5: the known-region noise and tag 6: the jump noise of the
- * edit epilogue (sisic_*_step_edit below); tag 16 + k: tensor k of a classifier randomised by
+ * edit epilogue (sisic_*_step_edit below); tag 7: the z of a noised classifier-training batch (the Python package's
+ * train_classifier(noise_timesteps=...): step 0, one 64-bit seed per image); tag 16 + k: tensor k of a classifier randomised by
  * sisic_resnet_randomize (step = the trial).  A pure function of
  * (seed, step, tag, element): independent of the batch, the GPU count, graph or eager mode.  1 <= n_per_image <= 2^34.
  * seeds: HOST uint64 [B], read before the call returns.
@@ -467,6 +468,64 @@ int sisic_sample_frames_cond(sisic_unet*, float* x, int B, int H, int W, int T, 
  * surface: a caller's own loop over two sisic_unet_forward_cond passes, this and a sisic_*_step reproduces the guided loop
  * bit for bit).  Any alignment, any n >= 1; out may be either input.                                                      */
 int sisic_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream);
+
+/* ---- classifier guidance (Dhariwal & Nichol 2021, Alg. 2) ---------------------------------------------
+ * An UNCONDITIONAL epsilon-prediction model is pushed towards a class by the input gradient of the ResNet18 classifier:
+ *     k = scale * sb;   eps_hat = eps - k * g          (sb = sqrt(1 - abar_t), entry 0 of the step's row)
+ * in fp32, k * g then the subtraction, one rounding per operation and no FMA contraction; the step rule is applied to eps_hat
+ * as it is applied to classifier-free guidance's combined eps.  g = d log(softmax(clf(x_t))[c_b] + 1e-8) / d x_t is
+ * sisic_resnet_input_gradient_targets at the step's latent, pre-processing included, with image b's own target c_b.  The
+ * classifier is not time-conditioned, and its pre-processing clamps: g is zero wherever x_t lies outside [-1, 1].  A non-finite
+ * g propagates into x; nothing guards it.
+ *
+ * sisic_clf_guide_eps: out = eps - (scale * sb) * g over n floats with the device function the guided step kernels call
+ * (parity-test surface, as sisic_guide_eps is).  Any alignment, any n >= 1; out may be eps (not g).
+ *
+ * sisic_sample_frames_clf: sisic_sample_frames_rule_rng's loop with the classifier in it.  Per step, on ONE stream and in this
+ * order: the UNet pass, the gradient walk on the loop's latent, the guided step kernel.  The fields that
+ * sisic_sample_frames_rule_rng has mean what they mean there (x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, seeds,
+ * step0, traj, traj_row, out_u8, cancel); steps_done is an out field.  classifier: a loaded handle of the UNet's context;
+ * targets: HOST int64 [B], image b's class, each in [0, num_classes); scale: finite, 0 gives the bits of the unguided loop.
+ * noise must be NULL: the loop draws its noise on the device (host-noise mode is refused, as is seeds == NULL).
+ * SISIC_EINVAL before anything is launched (steps_done = 0): a conditional handle, a handle whose prediction_type is not
+ * epsilon, a noise buffer or no seeds, a classifier of another context or device, a classifier that is not loaded, H or W
+ * above 224, a target outside [0, num_classes), a scale that is not finite.
+ * In graph mode targets and scale live in a device table the UNet handle owns, so a captured step serves every target list
+ * and every scale.  The classifier's activation blocks are sized by the eager step 0, as the UNet's are; the key of a captured
+ * step holds "classifier-guided", the classifier handle and the generation of its workspace (a value no other state of any
+ * handle in the process has, so a handle destroyed and created again at the same address does not match), which moves whenever the
+ * classifier releases or derives its buffers again (a call at another input shape, sisic_resnet_load, train_begin /
+ * train_end): the next guided call then re-captures (sisic_unet_graph_builds) and never replays onto freed blocks.  Weights
+ * that change in place (sisic_resnet_optimizer_step, sisic_resnet_randomize / _restore) keep their buffers and need no
+ * re-capture.                                                                                                                */
+typedef struct sisic_clf_guide_args {
+    const float* eps;
+    const float* g;
+    float*       out;
+    void*        stream;
+    int64_t      n;
+    float        sb, scale;
+} sisic_clf_guide_args;                    /* 48 bytes, no padding */
+int sisic_clf_guide_eps(sisic_ctx*, sisic_clf_guide_args* args);
+typedef struct sisic_sample_clf_args {
+    float*              x;
+    const int64_t*      timesteps;
+    const float*        coef;
+    const float*        noise;             /* must be NULL */
+    const uint64_t*     seeds;
+    sisic_resnet*       classifier;
+    const int64_t*      targets;
+    float*              traj;
+    const int*          traj_row;
+    uint8_t*            out_u8;
+    const volatile int* cancel;
+    void*               stream;
+    int                 B, H, W, T;
+    int                 rule, rule_flags, step0;
+    int                 steps_done;        /* out */
+    float               clip, scale;
+} sisic_sample_clf_args;                   /* 136 bytes, no padding */
+int sisic_sample_frames_clf(sisic_unet*, sisic_sample_clf_args* args);
 
 /* ---- image editing: the inpainting epilogue of the step kernels (RePaint, Lugmayr et al. 2022) -------
  * sisic_{ddpm,ddim,dpmpp}_step_rng with an epilogue applied to the rule's result u in the register that holds it, before the
@@ -771,6 +830,23 @@ int sisic_resnet_stem(sisic_resnet*, const float* x, float* c1_out, int B, int H
  * xai/XAI.py:1039-1109 take.  grad_x: dev [B,3,H,W]; logits_out: dev [B,n_classes] or NULL.              */
 int sisic_resnet_input_gradient(sisic_resnet*, const float* x, int B, int H, int W, int target,
                                 float* grad_x, float* logits_out, void* stream);
+/* The same gradient with one target per image: row b of grad_x is d log(softmax(logits_b)[targets[b]] + 1e-8) / d x_b.  The
+ * walk is sisic_resnet_input_gradient's, launch for launch; only the head reads its class from a device table, so row b has
+ * the bits of a single-target call with target = targets[b], and the logits are the forward's.  One argument struct that
+ * carries the stream as a field:
+ *   x           dev [B,3,H,W] in [-1,1], H, W <= 224
+ *   targets     HOST int64 [B], each in [0, num_classes): every one is checked before anything is launched (SISIC_EINVAL)
+ *   grad_x      dev [B,3,H,W];  logits_out: dev [B,num_classes] or NULL
+ * The targets travel through a pinned ring of the handle: the call does not wait for its stream.                            */
+typedef struct sisic_resnet_targets_args {
+    const float*   x;
+    const int64_t* targets;
+    float*         grad_x;
+    float*         logits_out;
+    void*          stream;
+    int            B, H, W, reserved;
+} sisic_resnet_targets_args;               /* 56 bytes, no padding */
+int sisic_resnet_input_gradient_targets(sisic_resnet*, sisic_resnet_targets_args* args);
 
 /* Grad-CAM of the class logit on model.layer4[-1].conv2 as pytorch_grad_cam's GradCAM(target_layers=[...conv2]) with
  * ClassifierOutputTarget(target) computes it in xai/XAI.py:2945-3035 (pre-processing included): cam = relu(sum_k

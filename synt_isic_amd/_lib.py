@@ -109,6 +109,27 @@ class ResnetTrainArgs(C.Structure):
                 ("loss", C.c_float), ("grad_norm", C.c_float), ("found_inf", C.c_int)]
 
 
+class ResnetTargetsArgs(C.Structure):
+    """struct sisic_resnet_targets_args (56 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("targets", c_int64_p), ("grad_x", C.c_void_p), ("logits_out", C.c_void_p),
+                ("stream", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("reserved", C.c_int)]
+
+
+class ClfGuideArgs(C.Structure):
+    """struct sisic_clf_guide_args (48 bytes, no padding)"""
+    _fields_ = [("eps", C.c_void_p), ("g", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p), ("n", C.c_int64),
+                ("sb", C.c_float), ("scale", C.c_float)]
+
+
+class SampleClfArgs(C.Structure):
+    """struct sisic_sample_clf_args (136 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("timesteps", c_int64_p), ("coef", c_float_p), ("noise", C.c_void_p),
+                ("seeds", C.POINTER(C.c_uint64)), ("classifier", C.c_void_p), ("targets", c_int64_p), ("traj", C.c_void_p),
+                ("traj_row", C.POINTER(C.c_int)), ("out_u8", C.c_void_p), ("cancel", C.POINTER(C.c_int)), ("stream", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("T", C.c_int), ("rule", C.c_int), ("rule_flags", C.c_int),
+                ("step0", C.c_int), ("steps_done", C.c_int), ("clip", C.c_float), ("scale", C.c_float)]
+
+
 class BnArgs(C.Structure):
     """struct sisic_bn_args (152 bytes, no padding)"""
     _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("residual", C.c_void_p),
@@ -205,6 +226,8 @@ SIGNATURES = {
                                            C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "sisic_guide_eps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sisic_clf_guide_eps": (C.c_int, [C.c_void_p, C.POINTER(ClfGuideArgs)]),
+    "sisic_sample_frames_clf": (C.c_int, [C.c_void_p, C.POINTER(SampleClfArgs)]),
     "sisic_ddpm_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
                                        C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -286,6 +309,7 @@ SIGNATURES = {
     "sisic_resnet_stem": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sisic_resnet_input_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "sisic_resnet_input_gradient_targets": (C.c_int, [C.c_void_p, C.POINTER(ResnetTargetsArgs)]),
     "sisic_resnet_gradcam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "sisic_resnet_train_begin": (C.c_int, [C.c_void_p]),

@@ -378,10 +378,12 @@ class HipMelanomaClassifier:
             check(_lib.load().sisic_resnet_stem(h, x[lo:].data_ptr(), out[lo:].data_ptr(), n, H, W, 1, stream))
         return out
 
-    def input_gradient(self, x: torch.Tensor, target_class: int):
+    def input_gradient(self, x: torch.Tensor, target_class):
         """(d get_per_class_score / d x, logits): the gradient captum's IntegratedGradients and the plain-gradient
         fallback of XAI.py:1039-1109 take, through the pre-processing, with no autograd graph -- the transposed
-        network runs on the same HIP convolution kernels (sisic_resnet_input_gradient)."""
+        network runs on the same HIP convolution kernels (sisic_resnet_input_gradient).
+        target_class: one class for every image, or a sequence / tensor of B classes, image b's own
+        (sisic_resnet_input_gradient_targets: row b has the bits of the single-target call with its class)."""
         h = self.handle
         if x.device != self._device:
             x = x.to(self._device)
@@ -392,9 +394,22 @@ class HipMelanomaClassifier:
         grad = ops.empty_like(x)
         logits = ops.empty((B, self.num_classes), dtype=torch.float32, device=x.device)
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        targets = None
+        if isinstance(target_class, torch.Tensor) and target_class.dim() > 0:
+            targets = [int(v) for v in target_class.tolist()]
+        elif isinstance(target_class, (list, tuple)):
+            targets = [int(v) for v in target_class]
+        if targets is not None and len(targets) != B:
+            raise ValueError(f"{len(targets)} target classes for a batch of {B}")
         for lo, n in self._chunks(B, self.max_backward_batch):
-            check(_lib.load().sisic_resnet_input_gradient(h, x[lo:].data_ptr(), n, H, W, int(target_class),
-                                                          grad[lo:].data_ptr(), logits[lo:].data_ptr(), stream))
+            if targets is None:
+                check(_lib.load().sisic_resnet_input_gradient(h, x[lo:].data_ptr(), n, H, W, int(target_class),
+                                                              grad[lo:].data_ptr(), logits[lo:].data_ptr(), stream))
+            else:
+                a = _lib.ResnetTargetsArgs(x=x[lo:].data_ptr(), targets=(C.c_int64 * n)(*targets[lo:lo + n]),
+                                           grad_x=grad[lo:].data_ptr(), logits_out=logits[lo:].data_ptr(), stream=stream,
+                                           B=n, H=H, W=W)
+                check(_lib.load().sisic_resnet_input_gradient_targets(h, C.byref(a)))
         return grad, logits
 
     def grad_cam(self, x: torch.Tensor, target_class: int):

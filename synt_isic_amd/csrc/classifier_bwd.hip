@@ -5,6 +5,7 @@
 // conv_winograd.hip) with transposed, tap-flipped filters -- stride 2 through the zero-insertion input mode --
 // so this file only holds what is not a convolution:
 //   * score_head_bwd_kernel : d score / d (last activation): softmax/log, Linear, global average pool, ReLU mask
+//   * score_head_bwd_targets_kernel : the same with one target per image (sisic_resnet_input_gradient_targets)
 //   * relu_bwd_kernel       : dy * [y > 0]
 //   * scatter_add_even      : the input side of a transposed 1x1 stride-2 convolution (downsample branch)
 //   * maxpool_bwd_kernel    : MaxPool2d(3, 2, 1) backward with PyTorch's first-maximum tie rule, fused ReLU mask
@@ -44,6 +45,43 @@ int launch_score_head_bwd(sisic_ctx* ctx, const float* logits, const float* fc_w
     ProfileScope prof(ctx, s, PK_OTHER, 8.0 * total, 0.0);
     hipLaunchKernelGGL(score_head_bwd_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s,
                        logits, fc_w, act, g, C, HW, n_classes, target, total);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// The same head with image b's own class, targets[b] (device int [B], each in [0, n_classes): the caller checks) -- classifier
+// guidance steers every image of a batch towards its own class.  An element's arithmetic is score_head_bwd_kernel's, statement
+// by statement, so a table of equal targets gives the bits of the single-target launch.
+__global__ void __launch_bounds__(256)
+score_head_bwd_targets_kernel(const float* __restrict__ logits, const float* __restrict__ fc_w, const float* __restrict__ act,
+                              float* __restrict__ g, int C, int HW, int n_classes, const int* __restrict__ targets, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)((i / HW) % C);
+        const int64_t b = i / ((int64_t)HW * C);
+        const int target = targets[b];
+        const float* lg = logits + b * n_classes;
+        float m = lg[0];
+        for (int k = 1; k < n_classes; ++k) m = fmaxf(m, lg[k]);
+        float sum = 0.0f;
+        for (int k = 0; k < n_classes; ++k) sum += expf(lg[k] - m);
+        const float pt = expf(lg[target] - m) / sum;
+        const float coef = pt / (pt + 1e-8f);
+        float d = 0.0f;
+        for (int k = 0; k < n_classes; ++k) {
+            const float pk = expf(lg[k] - m) / sum;
+            d += fc_w[(size_t)k * C + c] * (coef * ((k == target ? 1.0f : 0.0f) - pk));
+        }
+        g[i] = act[i] > 0.0f ? d / (float)HW : 0.0f;
+    }
+}
+
+int launch_score_head_bwd_targets(sisic_ctx* ctx, const float* logits, const float* fc_w, const float* act, float* g, int B, int C,
+                                  int HW, int n_classes, const int* targets_dev, hipStream_t s) {
+    SISIC_REQUIRE(logits && fc_w && act && g && targets_dev, "score_head_bwd_targets: bad arguments");
+    const int64_t total = (int64_t)B * C * HW;
+    ProfileScope prof(ctx, s, PK_OTHER, 8.0 * total, 0.0);
+    hipLaunchKernelGGL(score_head_bwd_targets_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s,
+                       logits, fc_w, act, g, C, HW, n_classes, targets_dev, total);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }

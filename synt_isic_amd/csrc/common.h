@@ -159,6 +159,9 @@ int launch_conv2d(sisic_ctx*, const sisic_conv_args& a, hipStream_t s, const GnF
 int launch_conv_smallcout(sisic_ctx*, const sisic_conv_args& a, const ConvPlan& plan, hipStream_t s);
 int launch_score_head_bwd(sisic_ctx*, const float* logits, const float* fc_w, const float* act, float* g, int B, int C,
                           int HW, int n_classes, int target, hipStream_t s);
+// the same head with image b's target read from targets_dev (device int [B], each in [0, n_classes): the caller checks)
+int launch_score_head_bwd_targets(sisic_ctx*, const float* logits, const float* fc_w, const float* act, float* g, int B, int C,
+                                  int HW, int n_classes, const int* targets_dev, hipStream_t s);
 int launch_relu_bwd(sisic_ctx*, const float* dy, const float* y, float* out, int64_t n, hipStream_t s);
 int launch_scatter_add_even(sisic_ctx*, float* dst, const float* src, int planes, int H, int W, hipStream_t s);
 int launch_maxpool_bwd(sisic_ctx*, const float* dm, const float* xin, float* dx, int planes, int H, int W, hipStream_t s);
@@ -268,6 +271,29 @@ int launch_step_edit(sisic_ctx*, int rule, int flags, const float* eps, const fl
                      const float* coef_dev, const float* erows_dev, const float* x0k, const float* mask, float clip,
                      hipStream_t s);
 int launch_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s);
+// classifier guidance (elementwise.hip): the same rules on eps_hat = eps - (scale * sb) * g, formed in the step kernel, g the
+// classifier's input gradient at x.  Epsilon prediction and generated noise only.  row: the rule's host row; hist:
+// DPM-Solver++ only.  The indexed form reads scale from clf_tab[0] (LoopClf: {scale, -, -, -, int target[B]}).
+constexpr size_t LOOP_CLF_HEAD = 4;
+int launch_step_clf(sisic_ctx*, int rule, int flags, const float* eps, const float* g, float scale, const float* x,
+                    const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
+                    const float* row, float clip, hipStream_t s);
+int launch_step_clf_indexed(sisic_ctx*, int rule, int flags, const float* eps, const float* g, float* x, float* hist, int64_t n,
+                            int64_t n_per_image, const void* state, const float* coef, const uint64_t* seeds_dev,
+                            const float* clf_tab, float clip, hipStream_t s);
+int launch_clf_guide_eps(sisic_ctx*, const float* eps, const float* g, float sb, float scale, float* out, int64_t n, hipStream_t s);
+// resnet.cpp, for the classifier-guided sampling loop (unet.cpp): what the loop checks before its first launch, and the walk of
+// sisic_resnet_input_gradient with image b's target read from targets_dev (device int [B]; NULL: `target` for every image).
+// The walk checks nothing but the shape: its callers have.
+sisic_ctx* resnet_ctx(const sisic_resnet* r);
+bool resnet_loaded(const sisic_resnet* r);
+int resnet_num_classes(const sisic_resnet* r);
+// renewed whenever the handle's activation blocks or weight buffers are released or derived again (a change of the input shape, a
+// load, train_begin / train_end): a captured step that ran the walk holds their addresses.  Unique in the process: no state of
+// another handle, or of a later handle at the same address, has the same value
+uint64_t resnet_workspace_generation(const sisic_resnet* r);
+int resnet_input_gradient_walk(sisic_resnet* r, const float* x, int B, int H, int W, int target, const int* targets_dev,
+                               float* grad_x, float* logits_out, hipStream_t s);
 // conditional loop: out[b][r] = table[(step * L + slot[b]) * R + r] for the `rows` samples of a pass; cond: LoopCond
 // {w, L, -, -, slot[rows]}; state != NULL: the step index is the loop state's (graph-replayed form)
 constexpr size_t LOOP_COND_HEAD = 4;

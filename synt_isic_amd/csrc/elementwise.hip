@@ -825,6 +825,176 @@ int launch_step_guided_indexed(sisic_ctx* ctx, int rule, int flags, const float*
     return SISIC_OK;
 }
 
+// ---- classifier guidance: the same steps reading eps through ClassifierEps ----------------------------------------------------
+// eps_hat = eps - k * g with k = scale * sb (Dhariwal & Nichol 2021, Alg. 2): g is the classifier's input
+// gradient at the step's latent, sb entry 0 of the step's row.  k is formed in the kernel, so the eager, the indexed and the
+// stand-alone form (sisic_clf_guide_eps) round it the same way.  Epsilon prediction and generated noise only.  The eager kernels
+// take scale and the row as launch arguments; the indexed ones read the row by the loop's step index and scale from
+// clf_tab[0] (LoopClf: {scale, -, -, -, int target[B]}), so that a captured step replays under another scale.
+__device__ __forceinline__ float clf_guide_k(float scale, float sb) {
+#pragma clang fp contract(off)
+    return scale * sb;
+}
+
+__device__ __forceinline__ float clf_guide_one(float e, float g, float k) {
+#pragma clang fp contract(off)
+    const float t = k * g;
+    return e - t;
+}
+
+struct ClassifierEps {
+    const float* __restrict__ e;
+    const float* __restrict__ g;
+    float k;
+    static constexpr bool dup = false;
+    __device__ __forceinline__ float4 get4(int64_t i4) const {
+        const float4 ev = reinterpret_cast<const float4*>(e)[i4], gv = reinterpret_cast<const float4*>(g)[i4];
+        return make_float4(clf_guide_one(ev.x, gv.x, k), clf_guide_one(ev.y, gv.y, k), clf_guide_one(ev.z, gv.z, k),
+                           clf_guide_one(ev.w, gv.w, k));
+    }
+    __device__ __forceinline__ float get1(int64_t i) const { return clf_guide_one(e[i], g[i], k); }
+};
+
+template <class R>
+__global__ void __launch_bounds__(256)
+step_clf_kernel(const float* __restrict__ eps, const float* __restrict__ g, float scale, const float* x,
+                const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* out, int64_t n, StepRow row,
+                float clip, int vec4) {
+    const PhiloxNoise zs{seeds, n_per_image, step};
+    step_body(ClassifierEps{eps, g, clf_guide_k(scale, row.v[0])}, x, out, n, vec4 != 0 && zs.vec_ok(), row_rule<R>(row, clip), zs);
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_clf_kernel(const float* __restrict__ eps, const float* __restrict__ g, float scale, const float* x,
+                    const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
+                    StepRow row, float clip, int vec4) {
+    const PhiloxNoise zs{seeds, n_per_image, step};
+    const DpmRule<PRED_EPS> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
+    dpm_step_body(ClassifierEps{eps, g, clf_guide_k(scale, row.v[0])}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+}
+
+template <class R>
+__global__ void __launch_bounds__(256)
+step_clf_indexed_kernel(const float* __restrict__ eps, const float* __restrict__ g, float* x, int64_t n, int64_t n_per_image,
+                        const LoopState* __restrict__ st, const float* __restrict__ coef, const uint64_t* __restrict__ seeds,
+                        const float* __restrict__ clf_tab, float clip, int vec4) {
+    const int step = st->step;
+    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+    const R rule = loop_rule<R>(coef, step, clip);
+    step_body(ClassifierEps{eps, g, clf_guide_k(clf_tab[0], rule.sb)}, x, x, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+}
+
+__global__ void __launch_bounds__(256)
+dpm_step_clf_indexed_kernel(const float* __restrict__ eps, const float* __restrict__ g, float* x, float* hist, int64_t n,
+                            int64_t n_per_image, const LoopState* __restrict__ st, const float* __restrict__ coef,
+                            const uint64_t* __restrict__ seeds, const float* __restrict__ clf_tab, float clip, int vec4) {
+    const int step = st->step;
+    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
+    const DpmRule<PRED_EPS> rule = loop_dpm_rule<PRED_EPS>(coef, step, clip);
+    dpm_step_body(ClassifierEps{eps, g, clf_guide_k(clf_tab[0], rule.sb)}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+}
+
+static int check_clf_step(int rule, int flags, const char* form) {
+    SISIC_TRY(check_rule(rule, flags));
+    SISIC_REQUIRE(step_pred(flags) == PRED_EPS, "%s (%s): prediction_type %d: classifier guidance takes epsilon-prediction models only",
+                  rule_name(rule), form, step_pred(flags));
+    return SISIC_OK;
+}
+
+// the eager form.  row: the rule's host row; out may be x; hist: DPM-Solver++ only
+int launch_step_clf(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* g, float scale, const float* x,
+                    const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
+                    const float* row, float clip, hipStream_t s) {
+    SISIC_TRY(check_clf_step(rule, flags, "classifier-guided"));
+    SISIC_REQUIRE(eps && g && x && out && seeds_dev && row && n > 0, "%s (classifier-guided): null tensor or empty", rule_name(rule));
+    SISIC_REQUIRE(g != out && eps != out, "%s (classifier-guided): eps or the gradient aliases the output", rule_name(rule));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps && hist != g),
+                  "dpmpp_step (classifier-guided): the history is missing or aliases another tensor");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "%s (classifier-guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
+                  (long long)n_per_image);
+    SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
+    ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
+    StepRow r{};
+    for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) r.v[k] = row[k];
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x) |
+                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
+#define SISIC_CLF(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps, g, scale, x, seeds_dev, n_per_image, step, out, n, r, clip, vec4)
+    if (rule == STEP_RULE_DPMPP)
+        hipLaunchKernelGGL(dpm_step_clf_kernel, grid, block, 0, s, eps, g, scale, x, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
+    else if (rule == STEP_RULE_DDPM) SISIC_CLF((step_clf_kernel<DdpmRule<PRED_EPS>>));
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT) SISIC_CLF((step_clf_kernel<DdimRule<true, PRED_EPS>>));
+    else SISIC_CLF((step_clf_kernel<DdimRule<false, PRED_EPS>>));
+#undef SISIC_CLF
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// the graph-replayed form: eps, g and x are the loop's own buffers, clf_tab its LoopClf table (scale at clf_tab[0])
+int launch_step_clf_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* g, float* x, float* hist, int64_t n,
+                            int64_t n_per_image, const void* state, const float* coef, const uint64_t* seeds_dev,
+                            const float* clf_tab, float clip, hipStream_t s) {
+    SISIC_TRY(check_clf_step(rule, flags, "classifier-guided, indexed"));
+    SISIC_REQUIRE(eps && g && x && state && coef && seeds_dev && clf_tab && n > 0, "%s_indexed (classifier-guided): null argument", rule_name(rule));
+    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || hist, "dpmpp_step_indexed (classifier-guided): no history buffer");
+    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
+                  "%s_indexed (classifier-guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
+                  (long long)n_per_image);
+    ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x) |
+                         reinterpret_cast<uintptr_t>(hist);
+    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
+    const int64_t work = vec4 ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
+    const LoopState* st = static_cast<const LoopState*>(state);
+#define SISIC_CLF(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps, g, x, n, n_per_image, st, coef, seeds_dev, clf_tab, clip, vec4)
+    if (rule == STEP_RULE_DPMPP)
+        hipLaunchKernelGGL(dpm_step_clf_indexed_kernel, grid, block, 0, s, eps, g, x, hist, n, n_per_image, st, coef, seeds_dev, clf_tab, clip, vec4);
+    else if (rule == STEP_RULE_DDPM) SISIC_CLF((step_clf_indexed_kernel<DdpmRule<PRED_EPS>>));
+    else if (flags & STEP_FLAG_CLIPPED_OUTPUT) SISIC_CLF((step_clf_indexed_kernel<DdimRule<true, PRED_EPS>>));
+    else SISIC_CLF((step_clf_indexed_kernel<DdimRule<false, PRED_EPS>>));
+#undef SISIC_CLF
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
+// the combine alone (sisic_clf_guide_eps): clf_guide_one() on every element, any alignment; out may be eps
+__global__ void __launch_bounds__(256)
+clf_guide_eps_kernel(const float* eps, const float* g, float sb, float scale, float* out, int64_t n, int vec4) {
+    const float k = clf_guide_k(scale, sb);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // (plain pointers, not the restrict-qualified ClassifierEps: out may be eps; a thread reads its elements first)
+    int64_t tail = t0;
+    if (vec4) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = t0; i < n4; i += stride) {
+            const float4 e = reinterpret_cast<const float4*>(eps)[i], gv = reinterpret_cast<const float4*>(g)[i];
+            reinterpret_cast<float4*>(out)[i] = make_float4(clf_guide_one(e.x, gv.x, k), clf_guide_one(e.y, gv.y, k),
+                                                            clf_guide_one(e.z, gv.z, k), clf_guide_one(e.w, gv.w, k));
+        }
+        tail = (n4 << 2) + t0;
+    }
+    for (int64_t i = tail; i < n; i += stride) out[i] = clf_guide_one(eps[i], g[i], k);
+}
+
+int launch_clf_guide_eps(sisic_ctx* ctx, const float* eps, const float* g, float sb, float scale, float* out, int64_t n,
+                         hipStream_t s) {
+    SISIC_REQUIRE(eps && g && out && n > 0, "clf_guide_eps: null tensor or empty");
+    SISIC_REQUIRE(g != out, "clf_guide_eps: out aliases the gradient (out may be eps)");
+    ProfileScope prof(ctx, s, PK_OTHER, 12.0 * (double)n, 0.0);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(out);
+    const int vec4 = (al & 15) == 0;
+    const int64_t work = vec4 ? (n + 3) / 4 : n;
+    hipLaunchKernelGGL(clf_guide_eps_kernel, dim3((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), dim3(256), 0, s, eps, g, sb,
+                       scale, out, n, vec4);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // ---- the edited steps (sisic_*_step_edit, sisic_sample_frames_edit) -------------------------------------------------------
 // rule x {plain, guided} with the inpainting epilogue, generated noise only.  One kernel serves the eager and the replayed
 // form: with st set, the rule's row, the edit row and the step index are read by the loop's step (and w from cond[0]);

@@ -106,6 +106,19 @@ struct sisic_resnet {
     std::vector<float*> owned;
     Pool pool;
     int ws_B = 0, ws_H = 0, ws_W = 0;       // shape the pooled blocks were sized for (see workspace_for)
+    // renewed whenever pooled blocks or weight buffers are released or derived again: a captured sampling step that ran the
+    // input-gradient walk (sisic_sample_frames_clf) holds their addresses and is re-captured when this has moved.  Every value
+    // comes from one process-wide counter (next_workspace_generation), so no two states of any two handles share one: a
+    // handle destroyed and created again at the same address never matches a key the old one left behind.
+    uint64_t ws_gen = 0;
+    // sisic_resnet_input_gradient_targets: the call's targets as ints, in a pinned ring; a slot is written again only after
+    // the copy out of it has finished (its event), so the call does not wait for its stream
+    static constexpr int TARGET_SLOTS = 4;
+    int* targets_stage = nullptr;
+    size_t targets_cap = 0;
+    uint64_t targets_next = 0;
+    hipEvent_t targets_ev[TARGET_SLOTS] = {};
+    bool targets_used[TARGET_SLOTS] = {};
     bool loaded = false;
     ResnetTrain* train = nullptr;
 
@@ -120,6 +133,36 @@ struct sisic_resnet {
 namespace {
 
 constexpr float BN_EPS = 1e-5f;   // torchvision BatchNorm2d default
+
+// the next value of sisic_resnet::ws_gen, unique in the process
+uint64_t next_workspace_generation() {
+    static std::atomic<uint64_t> counter{0};
+    return counter.fetch_add(1) + 1;
+}
+
+// targets (host int64, already checked) as ints in dst, ordered on s, through the handle's pinned ring
+int stage_targets(sisic_resnet* r, const int64_t* targets, int B, int* dst, hipStream_t s) {
+    if (r->targets_cap < (size_t)B) {
+        SISIC_HIP(hipDeviceSynchronize());
+        if (r->targets_stage) SISIC_HIP(hipHostFree(r->targets_stage));
+        r->targets_stage = nullptr;
+        const size_t cap = std::max<size_t>((size_t)B, 256);
+        void* p = nullptr;
+        SISIC_HIP(hipHostMalloc(&p, cap * sisic_resnet::TARGET_SLOTS * sizeof(int), hipHostMallocDefault));
+        r->targets_stage = static_cast<int*>(p);
+        r->targets_cap = cap;
+        for (bool& used : r->targets_used) used = false;
+    }
+    const int slot = (int)(r->targets_next++ % sisic_resnet::TARGET_SLOTS);
+    if (!r->targets_ev[slot]) SISIC_HIP(hipEventCreateWithFlags(&r->targets_ev[slot], hipEventDisableTiming));
+    if (r->targets_used[slot]) SISIC_HIP(hipEventSynchronize(r->targets_ev[slot]));
+    int* h = r->targets_stage + (size_t)slot * r->targets_cap;
+    for (int b = 0; b < B; ++b) h[b] = (int)targets[b];
+    SISIC_HIP(hipMemcpyAsync(dst, h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    SISIC_HIP(hipEventRecord(r->targets_ev[slot], s));
+    r->targets_used[slot] = true;
+    return SISIC_OK;
+}
 
 void add_conv_bn(sisic_resnet* r, FoldedConv& c, const std::string& conv, const std::string& bn, int cout, int cin, int k,
                  int stride) {
@@ -251,6 +294,7 @@ int workspace_for(sisic_resnet* r, int B, int H, int W) {
     if (r->ws_B == B && r->ws_H == H && r->ws_W == W) return SISIC_OK;
     SISIC_HIP(hipDeviceSynchronize());       // earlier launches may still use the blocks
     r->pool.release_all();
+    r->ws_gen = next_workspace_generation();
     r->ws_B = B; r->ws_H = H; r->ws_W = W;
     return SISIC_OK;
 }
@@ -382,6 +426,7 @@ int sisic_resnet_create(sisic_ctx* ctx, int num_classes, sisic_resnet** out) {
     auto* r = new sisic_resnet();
     r->ctx = ctx;
     r->num_classes = num_classes;
+    r->ws_gen = next_workspace_generation();
     describe(r);
     *out = r;
     return SISIC_OK;
@@ -393,6 +438,9 @@ int sisic_resnet_destroy(sisic_resnet* r) {
     train_free(r);
     for (auto p : r->owned) (void)hipFree(p);
     r->pool.release_all();
+    if (r->targets_stage) (void)hipHostFree(r->targets_stage);
+    for (auto e : r->targets_ev)
+        if (e) (void)hipEventDestroy(e);
     delete r;
     return SISIC_OK;
 }
@@ -428,6 +476,7 @@ int sisic_resnet_load(sisic_resnet* r, int n, const char* const* names, const fl
     }
     (void)hipDeviceSynchronize();
     train_free(r);                            // a reload ends training: the arenas described the previous weights
+    r->ws_gen = next_workspace_generation();  // every weight buffer moves
     for (auto p : r->owned) (void)hipFree(p);
     r->owned.clear();
     r->loaded = false;
@@ -539,9 +588,42 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
         set_error("resnet_input_gradient called before sisic_resnet_load");
         return SISIC_ESTATE;
     }
+    return resnet_input_gradient_walk(r, x, B, H, W, target, nullptr, grad_x, logits_out, static_cast<hipStream_t>(stream));
+}
+
+// The same walk with one target per image.  The targets reach the device in a block of the pool, ordered on the stream.
+int sisic_resnet_input_gradient_targets(sisic_resnet* r, sisic_resnet_targets_args* a) {
+    SISIC_REQUIRE(r && a && a->x && a->targets && a->grad_x && a->B > 0 && a->H > 0 && a->W > 0,
+                  "resnet_input_gradient_targets: bad arguments");
+    for (int b = 0; b < a->B; ++b)
+        SISIC_REQUIRE(a->targets[b] >= 0 && a->targets[b] < r->num_classes,
+                      "resnet_input_gradient_targets: target %lld of image %d is outside [0, %d)", (long long)a->targets[b], b,
+                      r->num_classes);
+    if (!r->loaded) {
+        set_error("resnet_input_gradient_targets called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_TRY(workspace_for(r, a->B, a->H, a->W));
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    PoolScope ws(r->pool, s);
+    float* tab = nullptr;
+    SISIC_TRY(ws.get((size_t)a->B, &tab));
+    SISIC_TRY(stage_targets(r, a->targets, a->B, reinterpret_cast<int*>(tab), s));
+    return resnet_input_gradient_walk(r, a->x, a->B, a->H, a->W, 0, reinterpret_cast<const int*>(tab), a->grad_x, a->logits_out, s);
+}
+
+}  // extern "C"
+
+sisic_ctx* sisic::resnet_ctx(const sisic_resnet* r) { return r->ctx; }
+bool sisic::resnet_loaded(const sisic_resnet* r) { return r->loaded; }
+int sisic::resnet_num_classes(const sisic_resnet* r) { return r->num_classes; }
+uint64_t sisic::resnet_workspace_generation(const sisic_resnet* r) { return r->ws_gen; }
+
+int sisic::resnet_input_gradient_walk(sisic_resnet* r, const float* x, int B, int H, int W, int target, const int* targets_dev,
+                                      float* grad_x, float* logits_out, hipStream_t s) {
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_TRY(workspace_for(r, B, H, W));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     PoolScope ws(r->pool, s);
     // transposed convolution of `c` applied to g [B, c.cout, gh, gw]; stride 2: zero-insertion input (2gh x 2gw grid)
     auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
@@ -566,7 +648,10 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
     // ---- backward
     float* g = nullptr;                                   // d score / d (block output), already ReLU-masked
     SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
-    SISIC_TRY(launch_score_head_bwd(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, target, s));
+    if (targets_dev)
+        SISIC_TRY(launch_score_head_bwd_targets(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, targets_dev, s));
+    else
+        SISIC_TRY(launch_score_head_bwd(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, target, s));
     ws.put(t.logits);
     for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
         const Block& b = r->blocks[k];
@@ -613,6 +698,8 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
     ws.put(dp);
     return SISIC_OK;
 }
+
+extern "C" {
 
 // Grad-CAM on layer4[-1].conv2 for the raw logit of `target` (xai/XAI.py:2945-3035; see gradcam_kernel): the forward
 // pass with the last block's conv2 (+BatchNorm) output kept before the residual add, then one small kernel per image.
@@ -1008,6 +1095,7 @@ int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
     SISIC_HIP(hipDeviceSynchronize());
     auto* tr = new ResnetTrain();
     r->train = tr;                               // (freed by train_end, a reload or destroy, also after an error below)
+    r->ws_gen = next_workspace_generation();
     tr->bn_mode = bn_mode;
     tr->momentum = momentum;
     tr->off.assign(r->names.size(), -1);
@@ -1122,6 +1210,7 @@ int sisic_resnet_train_end(sisic_resnet* r) {
             SISIC_HIP(hipMemcpy(r->host[i].data(), tr->buf + tr->boff[i], r->host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
     }
     train_free(r);
+    r->ws_gen = next_workspace_generation();
     return SISIC_OK;
 }
 

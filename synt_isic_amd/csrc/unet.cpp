@@ -740,7 +740,7 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)hipDeviceSynchronize();
     pool_release_all(u);
     for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables, u->edit_x0k, u->edit_mask,
-                     u->edit_rows, u->objective_dev})
+                     u->edit_rows, u->objective_dev, u->clf_grad, u->clf_tables})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -879,10 +879,18 @@ struct EditCall {
 };
 static constexpr size_t LOOP_EDIT_FLOATS = 4 * 1000;
 
+// A classifier-guided call of the loop (sisic_sample_frames_clf): the classifier, the images' targets (host) and the scale
+struct ClfCall {
+    sisic_resnet* clf;
+    const int64_t* targets;
+    float scale;
+};
+
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
-// launches for every step, so that a captured step can be replayed.  cg: a conditional call, or nullptr.
+// launches for every step, so that a captured step can be replayed.  cg: a conditional call, or nullptr; cl: a
+// classifier-guided call (the classifier's gradient walk between the UNet pass and the step kernel), or nullptr.
 static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
-                     const CondCall* cg, bool edit, hipStream_t s) {
+                     const CondCall* cg, bool edit, const ClfCall* cl, hipStream_t s) {
     void* state = u->loop_tables;
     const float* coef_dev = u->loop_tables + 4;
     const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
@@ -894,7 +902,14 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
         SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
         SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
     }
-    if (edit) {
+    if (cl) {
+        // the walk on the loop's latent, on the loop's stream, behind the UNet pass; targets and scale from the loop's table
+        SISIC_TRY(resnet_input_gradient_walk(cl->clf, u->x_work, B, H, W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
+                                             u->clf_grad, nullptr, s));
+        SISIC_TRY(launch_step_clf_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->clf_grad, u->x_work,
+                                          rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, (int64_t)n, (int64_t)(n / B), state, coef_dev,
+                                          seeds, u->clf_tables, clip, s));
+    } else if (edit) {
         // (the library's copies of the call's image, mask and rows: a captured step serves every edited call at the shape)
         const bool guided = cg && cg->guided;
         SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, 1.0f,
@@ -925,8 +940,9 @@ static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, i
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
 // rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
 static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, int rule,
-                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, const EditCall* ed, float* traj,
-                        const int* traj_row, const volatile int* cancel, int* steps_done, hipStream_t caller) {
+                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, const EditCall* ed,
+                        const ClfCall* cl, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
+                        hipStream_t caller) {
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
@@ -993,32 +1009,39 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
     const void* ex = edit ? u->edit_x0k : nullptr;
     const void* em = edit ? u->edit_mask : nullptr;
     const void* er = edit ? u->edit_rows : nullptr;
+    // (a classifier-guided call: targets and scale live in clf_tables; the classifier's own blocks and weight buffers are
+    //  covered by the generation of its workspace, read again after the eager step has sized them)
+    const void* cgr = cl ? u->clf_grad : nullptr;
+    const void* ctab = cl ? u->clf_tables : nullptr;
+    const void* clf_handle = cl ? cl->clf : nullptr;
+    auto clf_gen = [&]() -> uint64_t { return cl ? resnet_workspace_generation(cl->clf) : 0; };
     auto reusable = [&]() -> bool {
         const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[10] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er};
+        const void* ptrs[12] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
                   u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
                   u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags && u->loop_key.cond == (cg != nullptr) &&
-                  u->loop_key.guided == guided && u->loop_key.edit == edit;
-        for (int k = 0; k < 10; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
+                  u->loop_key.guided == guided && u->loop_key.edit == edit && u->loop_key.clf == (cl != nullptr) &&
+                  u->loop_key.clf_handle == clf_handle && u->loop_key.clf_gen == clf_gen();
+        for (int k = 0; k < 12; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
     if (rc == SISIC_OK && !reusable()) {
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, s);
+        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, cl, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
     if (rc == SISIC_OK && i < T) {
         if (!reusable()) {
             const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[10] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er};
+            const void* ptrs[12] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, s);
+            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, cl, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -1033,7 +1056,8 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
             u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
             u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided; u->loop_key.edit = edit;
-            for (int k = 0; k < 10; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            u->loop_key.clf = cl != nullptr; u->loop_key.clf_handle = clf_handle; u->loop_key.clf_gen = clf_gen();
+            for (int k = 0; k < 12; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
         }
@@ -1065,7 +1089,7 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
 static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                          float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
                          const int64_t* labels, int null_label, float w, const EditCall* ed, float* traj, const int* traj_row,
-                         uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
+                         uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream, const ClfCall* cl = nullptr) {
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
     // a caller's flags are the rule's own; from here on rule_flags also carries the handle's prediction type in its private
     // bits, down to the launchers and into the key of a captured step
@@ -1081,7 +1105,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);      // (an unknown rule is refused by check_step_row just below)
-    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels || ed)
+    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels || ed || cl)
         for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * cw + 0], coef[(size_t)i * cw + 1]));
     // DPM-Solver++: a call starts with no history (the buffer holds whatever the last run left), so its first step cannot be
     // a second-order one.  A run cut into two calls therefore differs from the uncut run; callers run it in one call.
@@ -1137,6 +1161,18 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, (size_t)rows * C * H * W));
     if (rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
     const bool rng = seeds != nullptr;
+    if (cl) {
+        // the loop's device table of the call: {scale, -, -, -, int target[B]} (elementwise.hip, LoopClf)
+        std::vector<float> ct(LOOP_CLF_HEAD + (size_t)B, 0.0f);
+        ct[0] = cl->scale;
+        for (int b = 0; b < B; ++b) {
+            const int t = (int)cl->targets[b];
+            std::memcpy(&ct[LOOP_CLF_HEAD + b], &t, sizeof(int));
+        }
+        SISIC_TRY(unet_grow(&u->clf_tables, &u->clf_tables_cap, LOOP_CLF_HEAD + (size_t)std::max(B, 128)));
+        SISIC_TRY(unet_stage_upload(u, ct.data(), ct.size(), u->clf_tables, s));
+        SISIC_TRY(unet_grow(&u->clf_grad, &u->clf_grad_cap, n));
+    }
     if (rng) {
         // 2^31 step indices is ample (a run has at most 1000) and keeps step0 + i inside the int of the device-side state
         SISIC_REQUIRE(step0 >= 0 && step0 <= INT32_MAX - T, "sample_rng: step0 %d", step0);
@@ -1171,7 +1207,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, ed, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, ed, cl, traj, traj_row, cancel, steps_done, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
@@ -1209,7 +1245,12 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
             const float* c = coef + (size_t)i * cw;
             const float* z = nullptr;
             if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-            if (ed)
+            if (cl) {
+                SISIC_TRY(resnet_input_gradient_walk(cl->clf, x, B, H, W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
+                                                     u->clf_grad, nullptr, s));
+                SISIC_TRY(launch_step_clf(u->ctx, rule, rule_flags, u->eps_buf, u->clf_grad, cl->scale, x, seeds_dev, (int64_t)(n / B),
+                                          (uint32_t)(step0 + i), rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, x, (int64_t)n, c, clip, s));
+            } else if (ed)
                 SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, guided ? cg->w : 1.0f,
                                            nullptr, xe, rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, xe, (int64_t)n, (int64_t)(n / B),
                                            (int64_t)H * W, seeds_dev, (uint32_t)(step0 + i), c, ed->rows + 4 * (size_t)i, nullptr,
@@ -1287,6 +1328,38 @@ int sisic_sample_frames_edit(sisic_unet* u, float* x, int B, int H, int W, int T
 int sisic_guide_eps(sisic_ctx* ctx, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream) {
     SISIC_REQUIRE(ctx, "guide_eps: null context");
     return launch_guide_eps(ctx, eps_c, eps_u, w, out, n, static_cast<hipStream_t>(stream));
+}
+
+int sisic_clf_guide_eps(sisic_ctx* ctx, sisic_clf_guide_args* a) {
+    SISIC_REQUIRE(ctx && a, "clf_guide_eps: null argument");
+    return launch_clf_guide_eps(ctx, a->eps, a->g, a->sb, a->scale, a->out, a->n, static_cast<hipStream_t>(a->stream));
+}
+
+// every refusal before the first launch; then sample_frames' loop with the classifier in it
+int sisic_sample_frames_clf(sisic_unet* u, sisic_sample_clf_args* a) {
+    SISIC_REQUIRE(u && a, "sample_clf: null argument");
+    a->steps_done = 0;
+    SISIC_REQUIRE(a->x && a->timesteps && a->coef && a->classifier && a->targets && a->B > 0 && a->T > 0, "sample_clf: null argument");
+    SISIC_REQUIRE(u->n_class == 0, "sample_clf: a class-conditional handle (classifier guidance steers an unconditional model; "
+                  "classifier-free guidance is sisic_sample_frames_cond)");
+    SISIC_REQUIRE(u->pred_type == SISIC_PRED_EPSILON, "sample_clf: the handle's prediction_type is %d: classifier guidance takes "
+                  "epsilon-prediction models only", u->pred_type);
+    SISIC_REQUIRE(!a->noise && a->seeds, "sample_clf: host noise (a noise buffer, or no seeds): classifier guidance draws its noise "
+                  "on the device");
+    SISIC_REQUIRE(resnet_ctx(a->classifier) == u->ctx, "sample_clf: the classifier belongs to another context or device");
+    SISIC_REQUIRE(resnet_loaded(a->classifier), "sample_clf: the classifier is not loaded (sisic_resnet_load)");
+    SISIC_REQUIRE(a->H > 0 && a->W > 0 && a->H <= 224 && a->W <= 224, "sample_clf: latent %dx%d larger than the classifier's 224x224",
+                  a->H, a->W);
+    const int nc = resnet_num_classes(a->classifier);
+    for (int b = 0; b < a->B; ++b)
+        SISIC_REQUIRE(a->targets[b] >= 0 && a->targets[b] < nc, "sample_clf: target %lld of image %d is outside [0, %d)",
+                      (long long)a->targets[b], b, nc);
+    SISIC_REQUIRE(std::isfinite(a->scale), "sample_clf: classifier scale %g", (double)a->scale);
+    SISIC_REQUIRE(u->cfg.in_channels == 3, "sample_clf: the classifier reads 3-channel images, the model has %d", u->cfg.in_channels);
+    const ClfCall cl{a->classifier, a->targets, a->scale};
+    return sample_frames(u, a->x, a->B, a->H, a->W, a->T, a->timesteps, a->coef, a->clip, a->rule, a->rule_flags, nullptr, a->seeds,
+                         a->step0, nullptr, 0, 1.0f, nullptr, a->traj, a->traj_row, a->out_u8, a->cancel, &a->steps_done, a->stream,
+                         &cl);
 }
 
 int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,

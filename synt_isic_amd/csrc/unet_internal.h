@@ -235,11 +235,17 @@ struct sisic_unet {
     hipGraphExec_t loop_exec = nullptr;
     struct LoopKey {
         int B = 0, H = 0, W = 0; float clip = 0; hipStream_t s = nullptr; bool latency = false; uint64_t gen = 0;
-        const void* ptrs[10] = {};       // tproj, eps_buf, x_work, loop_tables, tproj_cur, (DPM-Solver++ steps, else null)
-                                         // hist_buf, (conditional calls, else null) cond_tables and (edited calls, else null)
-                                         // edit_x0k, edit_mask, edit_rows at capture time: each can be re-allocated
+        const void* ptrs[12] = {};       // tproj, eps_buf, x_work, loop_tables, tproj_cur, (DPM-Solver++ steps, else null)
+                                         // hist_buf, (conditional calls, else null) cond_tables, (edited calls, else null)
+                                         // edit_x0k, edit_mask, edit_rows and (classifier-guided calls, else null) clf_grad,
+                                         // clf_tables at capture time: each can be re-allocated
         bool cond = false, guided = false;   // sisic_sample_frames_cond: per-sample embedding rows; two predictions per step
         bool edit = false;               // sisic_sample_frames_edit: the step kernel carries the inpainting epilogue
+        // sisic_sample_frames_clf: the step runs the classifier's gradient walk.  The handle and the generation of its workspace
+        // (resnet_workspace_generation): the captured launches hold the classifier's pool blocks and weight buffers
+        bool clf = false;
+        const void* clf_handle = nullptr;
+        uint64_t clf_gen = 0;
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
         const void* seeds = nullptr;     // ... from the seeds at this address
         int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags, the
@@ -264,6 +270,9 @@ struct sisic_unet {
     float* edit_mask = nullptr;          // ... its mask [B,1,H,W] ...
     float* edit_rows = nullptr;          // ... and its edit rows [1000][4], copies at addresses a captured step may hold
     size_t edit_x0k_cap = 0, edit_mask_cap = 0, edit_rows_cap = 0;
+    float* clf_grad = nullptr;           // sisic_sample_frames_clf: the classifier's input gradient at the step's latent [B,C,H,W]
+    float* clf_tables = nullptr;         // ... and the call's {scale, -, -, -, int target[B]} (elementwise.hip, LoopClf)
+    size_t clf_grad_cap = 0, clf_tables_cap = 0;
 
     int add(const std::string& name, int64_t numel) {
         index[name] = (int)names.size();

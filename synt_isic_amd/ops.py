@@ -263,6 +263,25 @@ def guide_eps(eps_c: torch.Tensor, eps_u: torch.Tensor, guidance_scale: float,
     return out
 
 
+def clf_guide_eps(eps: torch.Tensor, g: torch.Tensor, sb: float, scale: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sisic_clf_guide_eps: the classifier-guidance combine ``eps - (scale * sb) * g`` -- ``scale * sb``, times ``g``, then the
+    subtraction, each rounded to fp32 with no fused multiply-add: the device function the guided step kernels of
+    ``sisic_sample_frames_clf`` call.  ``g`` is the classifier's input gradient at the step's latent
+    (``HipMelanomaClassifier.input_gradient``), ``sb`` the step's sqrt(1 - abar_t).  ``out`` may be ``eps``."""
+    lib = _lib.load()
+    if eps.shape != g.shape:
+        raise ValueError(f"eps {tuple(eps.shape)} and g {tuple(g.shape)} differ in shape")
+    if out is None:
+        out = empty_like(eps)
+    elif out.shape != eps.shape:
+        raise ValueError(f"out {tuple(out.shape)} does not have the inputs' shape {tuple(eps.shape)}")
+    a = _lib.ClfGuideArgs(eps=_ptr(eps, "eps"), g=_ptr(g, "g"), out=_ptr(out, "out"), stream=_stream(eps.device), n=eps.numel(),
+                          sb=float(sb), scale=float(scale))
+    check(lib.sisic_clf_guide_eps(context(eps.device), C.byref(a)))
+    return out
+
+
 def _seed_array(seeds):
     """HOST uint64 [B] as the C ABI takes it; seeds are 64-bit unsigned (negative values are refused, not wrapped)."""
     seeds = [int(s) for s in seeds]

@@ -159,6 +159,22 @@ class Guidance:
 
 
 @dataclass(frozen=True)
+class ClassifierGuidance:
+    """What a classifier-guided run needs beside the latents (``sisic_sample_frames_clf``): the classifier, image b's target
+    output and the scale.  Every step then applies its rule to ``eps - (scale * sqrt(1 - abar_t)) * g``, ``g`` the classifier's
+    input gradient of ``log(softmax(clf(x_t))[target_b] + 1e-8)`` at the step's latent.  Scale 0 gives the unguided bits."""
+    classifier: object
+    targets: Tuple[int, ...]
+    scale: float = 1.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "targets", tuple(int(v) for v in self.targets))
+        if isinstance(self.scale, bool) or not isinstance(self.scale, (int, float)) or not np.isfinite(self.scale):
+            raise ValueError(f"classifier_scale must be a finite number, got {self.scale!r}")
+        object.__setattr__(self, "scale", float(self.scale))
+
+
+@dataclass(frozen=True)
 class Edit:
     """What an inpainting run needs beside the latents (``sisic_sample_frames_edit``): the known image (GPU fp32 [B,C,H,W] in
     [-1, 1], finite everywhere), the mask (GPU fp32 [B,1,H,W]; 1 keeps the known pixel, 0 synthesises, values in between
@@ -378,6 +394,8 @@ class SampleResult:
     n_resample: int = 1                        # inpainting: RePaint's resampling count (1: no jumps)
     unet_passes: int = 0                       # UNet passes of the whole run (the grid's steps plus the resampled ones)
     prediction_type: str = "epsilon"           # what the model's output meant to the step rule (the model's own property)
+    classifier_scale: Optional[float] = None   # classifier guidance: its scale (None: the run had none) ...
+    classifier_passes: int = 0                 # ... and the classifier's gradient walks, one per UNet pass
 
 
 def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence[int]]):
@@ -399,8 +417,11 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
                       use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
-                      edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS) -> SampleResult:
-    """edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
+                      edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS,
+                      classifier: Optional[ClassifierGuidance] = None) -> SampleResult:
+    """classifier: classifier guidance (``ClassifierGuidance``) of an unconditional epsilon-prediction model; needs a
+    ``DeviceNoise`` and composes with neither ``guidance`` nor ``edit``.
+    edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
     The run has one step per entry of ``edit.schedule`` (``timesteps``, ``steps_done``, the trajectory and ``save_indices``
     count those passes), and one longer than ``max_call_steps`` (at most 1000, the library's limit per call) is cut into calls
     with their step offsets: bit-equal to the uncut run under ddpm and ddim; a DPM-Solver++ run is never cut.
@@ -413,6 +434,8 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
     the step kernel.  eta and use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not
     zero under that rule and eta -- none for DDIM at eta = 0 and for the ODE variant of DPM-Solver++, where every noise
     source gives the same result.  A DPM-Solver++ run takes no ``NoiseStream``: the history lives inside one library call."""
+    if classifier is not None:
+        _check_classifier_guidance(model, classifier, noise, guidance, edit, x_T.shape[0])
     if edit is not None:
         _check_guidance(model, guidance, x_T.shape[0])
         return _run_edited(model, scheduler, x_T, noise, edit, return_trajectory, save_indices, cancel_flag, eta,
@@ -456,7 +479,16 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
             out_u8.data_ptr(),
             C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if device_noise is not None:
+    if classifier is not None:
+        a = _lib.SampleClfArgs(x=x.data_ptr(), timesteps=head[6], coef=head[7], noise=None,
+                               seeds=(C.c_uint64 * B)(*device_noise.seeds), classifier=classifier.classifier.handle,
+                               targets=(C.c_int64 * B)(*classifier.targets), traj=tail[0], traj_row=tail[1], out_u8=tail[2],
+                               cancel=C.pointer(cancel_flag) if cancel_flag is not None else None, stream=tail[5],
+                               B=B, H=H, W=W, T=T, rule=rule, rule_flags=rule_flags, step0=int(device_noise.step0),
+                               clip=float(clip), scale=classifier.scale)
+        rc = lib.sisic_sample_frames_clf(model.handle, C.byref(a))
+        done = C.c_int(a.steps_done)
+    elif device_noise is not None:
         seeds = (C.c_uint64 * B)(*device_noise.seeds)
         rc = _loop_call(lib, guidance, head, None, seeds, device_noise.step0, tail)
     else:
@@ -468,7 +500,29 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
         out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
                         steps_done=done.value, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"))
+                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"),
+                        classifier_scale=classifier.scale if classifier is not None else None,
+                        classifier_passes=done.value if classifier is not None else 0)
+
+
+def _check_classifier_guidance(model: HipUNet2DModel, classifier: ClassifierGuidance, noise, guidance, edit, B: int) -> None:
+    """every refusal of a classifier-guided run that needs no library call (the library checks them again)"""
+    if guidance is not None or model.config.num_class_embeds is not None:
+        raise ValueError("classifier guidance steers an unconditional model: it does not compose with a class-conditional "
+                         "model or guidance_scale (classifier-free guidance)")
+    if edit is not None:
+        raise ValueError("classifier guidance does not compose with init_image / mask (image-to-image, inpainting)")
+    if getattr(model, "prediction_type", "epsilon") != "epsilon":
+        raise ValueError(f"classifier guidance takes epsilon-prediction models only; this model's prediction_type is "
+                         f"{model.prediction_type!r}")
+    if not isinstance(noise, DeviceNoise):
+        raise ValueError('classifier guidance requires noise="device" (a DeviceNoise): the guided step kernels draw their noise')
+    if len(classifier.targets) != B:
+        raise ValueError(f"{len(classifier.targets)} classifier targets for a batch of {B}")
+    n = int(classifier.classifier.num_classes)
+    for v in classifier.targets:
+        if not 0 <= v < n:
+            raise ValueError(f"classifier target {v} is outside [0, {n})")
 
 
 def check_edit_schedule(rule: str, schedule, T: int) -> List[Tuple[int, int]]:
@@ -751,6 +805,8 @@ class Sampler:
         self.noise_segment_steps = 64     # steps of noise drawn and uploaded per pipeline stage (NoiseStream)
         self.color_statistics: Dict[str, dict] = {}   # class -> color_statistics.json entry (image_generator.py:142-170)
         self._noise_buffers: dict = {}    # pinned/device staging buffers of the last noise shape (NoiseStream)
+        self.classifier = None            # set_classifier: the classifier of generate(..., classifier_scale=) ...
+        self.classifier_index: Dict[str, int] = {}    # ... and class name -> its output
 
     def close(self) -> None:
         """Shut the noise producers' thread pool down and drop the pinned / device staging buffers (the models stay)."""
@@ -811,8 +867,39 @@ class Sampler:
             self.class_labels[n] = k
         return m
 
-    def _resolve_classes(self, class_name, n_images: int, guidance_scale) -> Tuple[HipUNet2DModel, List[str], Optional[Guidance]]:
-        """(model, one class name per image, Guidance or None) of a call; every refusal of the public interface is here"""
+    def set_classifier(self, clf, class_index: Dict[str, int]) -> None:
+        """The classifier ``generate*(..., classifier_scale=)`` steers with, and ``class_index``: class name -> the classifier
+        output that stands for it.  ``clf``: a loaded ``HipMelanomaClassifier`` on this sampler's device."""
+        index = {str(k): int(v) for k, v in dict(class_index).items()}
+        n = int(clf.num_classes)
+        bad = {k: v for k, v in index.items() if not 0 <= v < n}
+        if bad:
+            raise ValueError(f"class_index entries outside the classifier's outputs [0, {n}): {bad}")
+        self.classifier = clf
+        self.classifier_index = index
+
+    def _classifier_guidance(self, names: List[str], model: HipUNet2DModel, classifier_scale, noise: str, guidance_scale,
+                             edited: bool) -> ClassifierGuidance:
+        """the ClassifierGuidance of a generate* call; every refusal of the public interface is here"""
+        if self.classifier is None:
+            raise ValueError("classifier_scale needs a classifier: Sampler.set_classifier(clf, class_index) first")
+        if noise != "device":
+            raise ValueError('classifier_scale requires noise="device"')
+        if check_guidance_scale(guidance_scale) != 1.0 or model.config.num_class_embeds is not None:
+            raise ValueError("classifier_scale steers an unconditional model: it does not compose with guidance_scale or a "
+                             "class-conditional model")
+        if edited:
+            raise ValueError("classifier_scale does not compose with init_image / mask")
+        missing = sorted({c for c in names if c not in self.classifier_index})
+        if missing:
+            raise KeyError(f"set_classifier's class_index has no entry for {missing}")
+        return ClassifierGuidance(self.classifier, tuple(self.classifier_index[c] for c in names), classifier_scale)
+
+    def _resolve_classes(self, class_name, n_images: int, guidance_scale,
+                         one_model_suffices: bool = False) -> Tuple[HipUNet2DModel, List[str], Optional[Guidance]]:
+        """(model, one class name per image, Guidance or None) of a call; every refusal of the public interface is here.
+        one_model_suffices: a classifier-guided call, where the names of an unconditional model's batch may differ (they choose
+        the classifier's targets) as long as they are registered to ONE model."""
         scale = check_guidance_scale(guidance_scale)
         if isinstance(class_name, str):
             names = [class_name] * n_images
@@ -829,7 +916,7 @@ class Sampler:
         if any(self.models[c] is not model for c in names):
             raise ValueError("the class names of one call must belong to one conditional model")
         if model.config.num_class_embeds is None:
-            if len(set(names)) > 1:
+            if len(set(names)) > 1 and not one_model_suffices:
                 raise ValueError("an unconditional model generates one class per call")
             if scale != 1.0:
                 raise ValueError(f"guidance_scale={scale} needs a class-conditional model (add_conditional_model); the model "
@@ -873,8 +960,15 @@ class Sampler:
                        use_clipped_model_output: bool = False, solver_order: int = 2,
                        algorithm_type: str = "dpmsolver++", guidance_scale: float = 1.0, init_image=None, mask=None,
                        strength: float = 1.0, jump_length: int = 10, n_resample: int = 1,
-                       max_call_steps: int = MAX_CALL_STEPS) -> SampleResult:
-        """init_image, mask, strength, jump_length, n_resample: image editing (module docstring).  init_image: fp32 [B,3,H,W]
+                       max_call_steps: int = MAX_CALL_STEPS, classifier_scale: Optional[float] = None) -> SampleResult:
+        """classifier_scale: classifier guidance (Dhariwal & Nichol 2021) of an unconditional epsilon-prediction model with the
+        classifier of ``set_classifier``: every step applies its rule to ``eps - (scale * sqrt(1 - abar_t)) * g``, ``g`` the
+        classifier's input gradient towards image b's class at the step's latent.  ``class_name`` may then be a sequence with one
+        name per image, all registered to one model (``sampler.models[name]`` is the same object); the names choose the targets
+        through ``class_index``.  Requires noise="device"; refused with ``guidance_scale``, ``init_image`` / ``mask`` and on a
+        class-conditional model.  None (the default) is today's run; the result records ``classifier_scale`` and
+        ``classifier_passes``.
+        init_image, mask, strength, jump_length, n_resample: image editing (module docstring).  init_image: fp32 [B,3,H,W]
         in [-1, 1] or uint8 [B,H,W,3], a single image is broadcast.  Without a mask the call is image-to-image: the run goes
         through the last ``min(int(T * strength), T)`` entries of the grid, starting from ``add_noise(init_image, x_T, t)`` at
         the first of them (``strength`` below 1; both noise modes, every rule; DPM-Solver++ starts first order there).  mask
@@ -900,9 +994,12 @@ class Sampler:
         _check_noise_mode(noise)
         _check_scheduler(scheduler, eta, use_clipped_model_output, solver_order, algorithm_type)
         check_edit_options(scheduler, noise, init_image is not None, mask is not None, strength, jump_length, n_resample)
-        model, _, guidance = self._resolve_classes(class_name, len(seeds), guidance_scale)
+        model, names, guidance = self._resolve_classes(class_name, len(seeds), guidance_scale, classifier_scale is not None)
         sched = self.create_scheduler(T, scheduler, solver_order, algorithm_type)
         rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output, guidance=guidance)
+        if classifier_scale is not None:
+            rule_args["classifier"] = self._classifier_guidance(names, model, classifier_scale, noise, guidance_scale,
+                                                                init_image is not None or mask is not None)
         H, W = size
         start = None                     # image-to-image and inpainting below strength 1: x_T -> the noised init_image
         if init_image is not None:
@@ -970,7 +1067,7 @@ class Sampler:
                  save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
                  use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++",
                  guidance_scale: float = 1.0, init_image=None, mask=None, strength: float = 1.0, jump_length: int = 10,
-                 n_resample: int = 1):
+                 n_resample: int = 1, classifier_scale: Optional[float] = None):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -984,6 +1081,7 @@ class Sampler:
         noise: "host" or "device", as in ``generate_seeds``.
         scheduler, eta, use_clipped_model_output, solver_order, algorithm_type: the step rule, as in ``generate_seeds``.
         init_image, mask, strength, jump_length, n_resample: image-to-image and inpainting, as in ``generate_seeds``.
+        classifier_scale: classifier guidance, as in ``generate_seeds``.
         class_name, guidance_scale: as in ``generate_seeds``; a sequence of names gives one image per name (``count`` must be 1
         or its length), and with seed_is_base image i derives its seed from ITS class name.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
@@ -1003,7 +1101,8 @@ class Sampler:
                                    save_every_n=save_every_n, noise=noise, scheduler=scheduler, eta=eta,
                                    use_clipped_model_output=use_clipped_model_output, solver_order=solver_order,
                                    algorithm_type=algorithm_type, guidance_scale=guidance_scale, init_image=init_image,
-                                   mask=mask, strength=strength, jump_length=jump_length, n_resample=n_resample)
+                                   mask=mask, strength=strength, jump_length=jump_length, n_resample=n_resample,
+                                   classifier_scale=classifier_scale)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:

@@ -746,9 +746,38 @@ def evaluate_classifier(clf, loader) -> Dict[str, object]:
             "balanced_accuracy": float(recall[support > 0].mean()) if total else 0.0}
 
 
+CLASSIFIER_NOISE_TAG = 7          # include/sisic.h, device-noise contract: the z of a noised classifier batch
+
+
+def classifier_noise_draws(noise_seed: int, epoch: int, batch_index: int, B: int, noise_timesteps):
+    """(timesteps int64 [B], z seeds list [B]) of one noised classifier batch: a pure function of (seed, epoch, batch index,
+    position).  The 2B raw 64-bit words of numpy's Philox generator under key ``noise_seed`` and counter
+    (epoch, batch_index, 0, 0): word 2b gives image b's timestep, ``t_lo + ((word >> 32) * (t_hi - t_lo + 1) >> 32)`` --
+    uniform on the inclusive range -- and word 2b + 1 is the 64-bit seed its z is drawn under (``ops.noise_fill``, step 0,
+    ``CLASSIFIER_NOISE_TAG``)."""
+    import numpy as np
+    t_lo, t_hi = (int(v) for v in noise_timesteps)
+    if not 0 <= t_lo <= t_hi <= 999:
+        raise ValueError(f"noise_timesteps must be (t_lo, t_hi) with 0 <= t_lo <= t_hi <= 999, got {noise_timesteps!r}")
+    if noise_seed < 0 or noise_seed >> 64 or epoch < 0 or batch_index < 0:
+        raise ValueError("noise_seed must lie in 0 .. 2**64-1, epoch and batch_index must not be negative")
+    words = np.random.Philox(key=int(noise_seed), counter=[int(epoch), int(batch_index), 0, 0]).random_raw(2 * int(B))
+    t = t_lo + (((words[0::2] >> np.uint64(32)) * np.uint64(t_hi - t_lo + 1)) >> np.uint64(32)).astype(np.int64)
+    return torch.from_numpy(t), [int(w) for w in words[1::2]]
+
+
+def noise_classifier_batch(images: torch.Tensor, scheduler, noise_seed: int, epoch: int, batch_index: int, noise_timesteps):
+    """x_t = sqrt(abar_t) * x0 + sqrt(1 - abar_t) * z for one batch (``scheduler.add_noise``, sisic_add_noise) under the draws
+    of ``classifier_noise_draws``; returns (x_t, timesteps)."""
+    t, seeds = classifier_noise_draws(noise_seed, epoch, batch_index, images.shape[0], noise_timesteps)
+    z = ops.noise_fill(seeds, images[0].numel(), 0, CLASSIFIER_NOISE_TAG, device=images.device).reshape(images.shape)
+    return scheduler.add_noise(images, z, t), t
+
+
 def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=None, val_loader=None,
                      save_dir: Optional[str] = None, max_grad_norm: Optional[float] = None,
-                     log: Optional[Callable[[str], None]] = print, batchnorm: str = "frozen", bn_momentum: float = 0.1):
+                     log: Optional[Callable[[str], None]] = print, batchnorm: str = "frozen", bn_momentum: float = 0.1,
+                     noise_timesteps=None, noise_seed: int = 0, noise_scheduler=None):
     """``train_class``'s loop for the classifier: epochs over ``loader`` (items ``(images, labels)``, images in [-1,1] as the
     sampler makes them -- a ``data.DeviceLoader`` over ``DeviceDataset.from_isic_classes``), cross-entropy, Adam, BatchNorm
     frozen or, with ``batchnorm="batch"``, with batch statistics (``bn_momentum``: see ``HipClassifierAdam``; validation uses
@@ -756,8 +785,16 @@ def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=Non
     ``loader.dataset.labels``; ISIC is 67 % NV).  ``val_loader``: ``evaluate_classifier`` after every epoch, its balanced
     accuracy selects the best checkpoint (otherwise the epoch loss does).  ``save_dir``: ``classifier.pth`` under the
     reference's key names (``model.`` prefix), which ``load_state_dict`` here and the reference's
-    ``load_classifier_with_fallback`` both take.  Returns the per-epoch history (loss, and the validation record)."""
+    ``load_classifier_with_fallback`` both take.  Returns the per-epoch history (loss, and the validation record).
+    ``noise_timesteps=(t_lo, t_hi)``: a classifier for classifier guidance sees x_t, not x_0, so every batch is noised before
+    ``loss_backward`` (``noise_classifier_batch``: t per image uniform on the inclusive range, z from the device-noise contract,
+    both pure functions of (``noise_seed``, epoch, batch index, position)) under ``noise_scheduler`` (default: the samplers'
+    1000-step squaredcos_cap_v2 schedule).  None (the default) issues the launches it always has."""
     clf.handle                                   # a model on the CPU raises here: MI355X only
+    if noise_timesteps is not None:
+        classifier_noise_draws(noise_seed, 0, 0, 1, noise_timesteps)      # refuse a bad range before anything is allocated
+        if noise_scheduler is None:
+            noise_scheduler = HipDDPMScheduler(num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2")
     if isinstance(class_weights, str):
         if class_weights != "balanced":
             raise ValueError(f"class_weights {class_weights!r}: None, a tensor or 'balanced'")
@@ -771,7 +808,10 @@ def train_classifier(clf, loader, epochs: int, lr: float = LR, class_weights=Non
     try:
         for epoch in range(epochs):
             epoch_loss, n_batches = 0.0, 0
-            for images, labels in loader:
+            for batch_index, (images, labels) in enumerate(loader):
+                if noise_timesteps is not None:
+                    images, _ = noise_classifier_batch(images.to(clf.device), noise_scheduler, noise_seed, epoch, batch_index,
+                                                       noise_timesteps)
                 value, _ = clf.loss_backward(images, labels, class_weights=class_weights)
                 optimizer.step()
                 epoch_loss += value
