@@ -1063,6 +1063,96 @@ int sisic_augment(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, const
 int sisic_augment_u8(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, const sisic_augment_params* params_dev, int B,
                      int32_t* gray_mean_scratch, uint8_t* out_hwc, void* stream);
 
+/* ---- evaluation of generated sets (synt_isic_amd/evaluate.py) ---------------------------------------------------------------
+ * The pairwise arithmetic of the Frechet and kernel distances, improved precision / recall and the nearest-neighbour audit.
+ * Every entry takes one argument struct that carries the stream as a field, launches on that stream without waiting for it,
+ * allocates nothing, and writes only the outputs named below.  Matrices are row-major fp32 with a leading dimension in
+ * floats (ld >= the row length).  Sums in double run in a fixed order without atomics: two calls give equal bits.       */
+
+/* out[B,512] = the classifier's forward up to and including AdaptiveAvgPool2d(1): what sisic_resnet_forward feeds its Linear.
+ * x, preprocess and the workspace rules are sisic_resnet_forward's; row b does not depend on the batch.                  */
+typedef struct sisic_resnet_features_args {
+    const float* x;                        /* dev [B,3,H,W] */
+    float*       out;                      /* dev [B,512] */
+    void*        stream;
+    int          B, H, W, preprocess;
+} sisic_resnet_features_args;              /* 40 bytes, no padding */
+int sisic_resnet_features(sisic_resnet*, sisic_resnet_features_args* args);
+
+/* mean_out[c] = (1/n) sum_r x[r,c] in double: rows r = g, g + 16, ... summed in order for g = 0 .. 15, the 16 partial sums
+ * added in order of g.                                                                                                  */
+typedef struct sisic_col_means_args {
+    const float* x;                        /* dev [n,d], leading dimension ld */
+    double*      mean_out;                 /* dev double [d] */
+    void*        stream;
+    int64_t      ld;
+    int          n, d;
+} sisic_col_means_args;                    /* 40 bytes, no padding */
+int sisic_col_means(sisic_ctx*, sisic_col_means_args* args);
+
+/* out[n,m] = f(A' B'^T), A' = A - shift_a and B' = B - shift_b (row vectors of length d, each optional), s = a'_i . b'_j formed
+ * on the f32 matrix pipe: exact fp32 products, fp32 accumulation in a fixed order.  The shifts are subtracted
+ * while the operands are staged; no centred copy exists.  b NULL: B = A (ldb and shift_b are still B's own).
+ *   SISIC_GRAM_DOT     f = s
+ *   SISIC_GRAM_SQDIST  f = max(0, |a'_i|^2 + |b'_j|^2 - 2 s), the norms of the shifted rows summed in fp32 by the same launch
+ *   SISIC_GRAM_POLY3   f = (s / d + 1)^3, the kernel of the kernel inception distance
+ * contract_rows = 1 contracts over the row index instead: out[d,d] = A'^T A' from the same [n,d] layout (the covariance
+ * numerator when shift_a is the mean); b and shift_b must be NULL, m is not read, the mode must be SISIC_GRAM_DOT.
+ * Any n, m, d >= 1: edges are handled in the kernel.  SISIC_EINVAL: a null a or out, a size below 1, a leading dimension
+ * below its row length, an unknown mode, contract_rows with b, shift_b or another mode.                                  */
+#define SISIC_GRAM_DOT 0
+#define SISIC_GRAM_SQDIST 1
+#define SISIC_GRAM_POLY3 2
+typedef struct sisic_gram_args {
+    const float* a;                        /* dev [n,d], leading dimension lda */
+    const float* b;                        /* dev [m,d], leading dimension ldb; NULL: a */
+    const float* shift_a;                  /* dev [d] or NULL */
+    const float* shift_b;                  /* dev [d] or NULL */
+    float*       out;                      /* dev [n,m] ([d,d] with contract_rows), leading dimension ldo */
+    void*        stream;
+    int64_t      lda, ldb, ldo;
+    int          n, m, d, mode, contract_rows, reserved;
+} sisic_gram_args;                         /* 96 bytes, no padding */
+int sisic_gram(sisic_ctx*, const sisic_gram_args* args);
+
+/* The k smallest of dist[i,j] - col_offset[j] (one fp32 subtraction; col_offset optional) of every row i, ascending, ties to
+ * the lower column; skip_diagonal = 1 leaves j == i out.  Exact and deterministic; the values must be finite.
+ * SISIC_EINVAL unless 1 <= k <= 8 and k <= m - skip_diagonal (the message names k and m).                                */
+typedef struct sisic_rows_topk_args {
+    const float* dist;                     /* dev [n,m], leading dimension ld */
+    const float* col_offset;               /* dev [m] or NULL */
+    float*       val_out;                  /* dev [n,k] */
+    int32_t*     idx_out;                  /* dev int32 [n,k] */
+    void*        stream;
+    int64_t      ld;
+    int          n, m, k, skip_diagonal;
+} sisic_rows_topk_args;                    /* 64 bytes, no padding */
+int sisic_rows_topk(sisic_ctx*, sisic_rows_topk_args* args);
+
+/* out[i,j] = sum_c (a[i,c] - b[idx[i,j],c])^2: both converted to double before the subtraction, summed in double in a fixed
+ * order (coordinates t, t + 256, ... per lane, then a binary tree), stored as fp32.  An index outside [0, nb) gives NaN.  */
+typedef struct sisic_pair_sqdist_args {
+    const float*   a;                      /* dev [n,d], leading dimension lda */
+    const float*   b;                      /* dev [nb,d], leading dimension ldb */
+    const int32_t* idx;                    /* dev int32 [n,k] */
+    float*         out;                    /* dev [n,k] */
+    void*          stream;
+    int64_t        lda, ldb;
+    int            n, nb, d, k;
+} sisic_pair_sqdist_args;                  /* 72 bytes, no padding */
+int sisic_pair_sqdist(sisic_ctx*, sisic_pair_sqdist_args* args);
+
+/* out[0] = sum of x[n,m] in double (exclude_diagonal = 1: without the entries i == j, on any shape): lane t of one workgroup
+ * sums the columns t, t + 1024, ... of every row in row order, then a binary tree.                                        */
+typedef struct sisic_matrix_sum_args {
+    const float* x;                        /* dev [n,m], leading dimension ld */
+    double*      out;                      /* dev double [1] */
+    void*        stream;
+    int64_t      ld;
+    int          n, m, exclude_diagonal, reserved;
+} sisic_matrix_sum_args;                   /* 48 bytes, no padding */
+int sisic_matrix_sum(sisic_ctx*, sisic_matrix_sum_args* args);
+
 /* ---- instrumentation (bench.py roofline leg) -------------------------------------- */
 /* When enabled, every conv launch is bracketed by HIP events on its own stream and
  * accumulated per class; reading synchronises the stream.                           */

@@ -144,6 +144,51 @@ class ResnetBnConfig(C.Structure):
     _fields_ = [("mode", C.c_int), ("momentum", C.c_double)]
 
 
+# epilogues of sisic_gram (SISIC_GRAM_*)
+GRAM_DOT = 0
+GRAM_SQDIST = 1
+GRAM_POLY3 = 2
+GRAM_MODES = {"dot": GRAM_DOT, "sqdist": GRAM_SQDIST, "poly3": GRAM_POLY3}
+
+
+class ResnetFeaturesArgs(C.Structure):
+    """struct sisic_resnet_features_args (40 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("preprocess", C.c_int)]
+
+
+class ColMeansArgs(C.Structure):
+    """struct sisic_col_means_args (40 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("mean_out", C.c_void_p), ("stream", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int),
+                ("d", C.c_int)]
+
+
+class GramArgs(C.Structure):
+    """struct sisic_gram_args (96 bytes, no padding)"""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("shift_a", C.c_void_p), ("shift_b", C.c_void_p), ("out", C.c_void_p),
+                ("stream", C.c_void_p), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldo", C.c_int64), ("n", C.c_int), ("m", C.c_int),
+                ("d", C.c_int), ("mode", C.c_int), ("contract_rows", C.c_int), ("reserved", C.c_int)]
+
+
+class RowsTopkArgs(C.Structure):
+    """struct sisic_rows_topk_args (64 bytes, no padding)"""
+    _fields_ = [("dist", C.c_void_p), ("col_offset", C.c_void_p), ("val_out", C.c_void_p), ("idx_out", C.c_void_p),
+                ("stream", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int), ("m", C.c_int), ("k", C.c_int),
+                ("skip_diagonal", C.c_int)]
+
+
+class PairSqdistArgs(C.Structure):
+    """struct sisic_pair_sqdist_args (72 bytes, no padding)"""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("idx", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("n", C.c_int), ("nb", C.c_int), ("d", C.c_int), ("k", C.c_int)]
+
+
+class MatrixSumArgs(C.Structure):
+    """struct sisic_matrix_sum_args (48 bytes, no padding)"""
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int), ("m", C.c_int),
+                ("exclude_diagonal", C.c_int), ("reserved", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/sisic.h declares
 SIGNATURES = {
     "sisic_abi_version": (C.c_int, []),
@@ -339,6 +384,12 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p]),
     "sisic_augment_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "sisic_resnet_features": (C.c_int, [C.c_void_p, C.POINTER(ResnetFeaturesArgs)]),
+    "sisic_col_means": (C.c_int, [C.c_void_p, C.POINTER(ColMeansArgs)]),
+    "sisic_gram": (C.c_int, [C.c_void_p, C.POINTER(GramArgs)]),
+    "sisic_rows_topk": (C.c_int, [C.c_void_p, C.POINTER(RowsTopkArgs)]),
+    "sisic_pair_sqdist": (C.c_int, [C.c_void_p, C.POINTER(PairSqdistArgs)]),
+    "sisic_matrix_sum": (C.c_int, [C.c_void_p, C.POINTER(MatrixSumArgs)]),
     "sisic_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "sisic_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), c_int64_p, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -335,6 +335,28 @@ class HipMelanomaClassifier:
 
     __call__ = forward
 
+    FEATURE_DIM = 512
+
+    @torch.no_grad()
+    def features(self, x: torch.Tensor, preprocessed: bool = False) -> torch.Tensor:
+        """The pooled features [B,512]: ``forward`` up to and including ``AdaptiveAvgPool2d(1)`` (sisic_resnet_features), what
+        the final Linear reads.  ``x`` as for ``forward``; walked in chunks of ``max_forward_batch``, and a row does not depend
+        on the chunking."""
+        h = self.handle
+        if x.device != self._device:
+            x = x.to(self._device)
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"classifier input must be [B,3,H,W], got {tuple(x.shape)}")
+        x = x.to(torch.float32).contiguous()
+        B, _, H, W = x.shape
+        out = ops.empty((B, self.FEATURE_DIM), dtype=torch.float32, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        for lo, n in self._chunks(B, self.max_forward_batch):
+            a = _lib.ResnetFeaturesArgs(x=x[lo:].data_ptr(), out=out[lo:].data_ptr(), stream=stream, B=n, H=H, W=W,
+                                        preprocess=0 if preprocessed else 1)
+            check(_lib.load().sisic_resnet_features(h, C.byref(a)))
+        return out
+
     def _scores(self, x: torch.Tensor, target_class: int):
         logits = self.forward(x)
         B = logits.shape[0]

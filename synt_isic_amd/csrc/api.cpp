@@ -385,6 +385,56 @@ int sisic_add_relu(sisic_ctx* ctx, sisic_bn_args* a) {
     return launch_add_relu(ctx, a->y, a->residual, a->out, (int64_t)a->B * a->C * a->HW, static_cast<hipStream_t>(a->stream));
 }
 
+// ---- evaluation of generated sets (eval_kernels.hip) ---------------------------------------------------------------------------
+int sisic_col_means(sisic_ctx* ctx, sisic_col_means_args* a) {
+    SISIC_REQUIRE(ctx && a && a->x && a->mean_out, "col_means: null argument");
+    SISIC_REQUIRE(a->n > 0 && a->d > 0 && a->ld >= a->d, "col_means: n %d, d %d, ld %lld", a->n, a->d, (long long)a->ld);
+    return launch_col_means(ctx, a->x, a->ld, a->n, a->d, a->mean_out, static_cast<hipStream_t>(a->stream));
+}
+
+int sisic_gram(sisic_ctx* ctx, const sisic_gram_args* a) {
+    SISIC_REQUIRE(ctx && a && a->a && a->out, "gram: null argument");
+    SISIC_REQUIRE(a->n > 0 && a->d > 0 && a->lda >= a->d, "gram: n %d, d %d, lda %lld", a->n, a->d, (long long)a->lda);
+    SISIC_REQUIRE(a->mode == SISIC_GRAM_DOT || a->mode == SISIC_GRAM_SQDIST || a->mode == SISIC_GRAM_POLY3, "gram: unknown mode %d",
+                  a->mode);
+    if (a->contract_rows) {
+        SISIC_REQUIRE(!a->b && !a->shift_b && a->mode == SISIC_GRAM_DOT,
+                      "gram: contract_rows computes A'^T A' alone: b and shift_b must be NULL and the mode SISIC_GRAM_DOT (mode %d)", a->mode);
+        SISIC_REQUIRE(a->ldo >= a->d, "gram: ldo %lld below the row length %d", (long long)a->ldo, a->d);
+    } else {
+        SISIC_REQUIRE(a->m > 0 && a->ldo >= a->m, "gram: m %d, ldo %lld", a->m, (long long)a->ldo);
+        SISIC_REQUIRE(!a->b || a->ldb >= a->d, "gram: ldb %lld below the row length %d", (long long)a->ldb, a->d);
+    }
+    return launch_gram(ctx, *a, static_cast<hipStream_t>(a->stream));
+}
+
+int sisic_rows_topk(sisic_ctx* ctx, sisic_rows_topk_args* a) {
+    SISIC_REQUIRE(ctx && a && a->dist && a->val_out && a->idx_out, "rows_topk: null argument");
+    SISIC_REQUIRE(a->n > 0 && a->m > 0 && a->ld >= a->m, "rows_topk: n %d, m %d, ld %lld", a->n, a->m, (long long)a->ld);
+    const int skip = a->skip_diagonal ? 1 : 0;
+    SISIC_REQUIRE(a->k >= 1 && a->k <= 8 && a->k <= a->m - skip,
+                  "rows_topk: k = %d with m = %d columns%s: 1 <= k <= 8 and k <= m - skip_diagonal", a->k, a->m,
+                  skip ? " and the diagonal skipped" : "");
+    return launch_rows_topk(ctx, a->dist, a->ld, a->col_offset, a->n, a->m, a->k, skip, a->val_out, a->idx_out,
+                            static_cast<hipStream_t>(a->stream));
+}
+
+int sisic_pair_sqdist(sisic_ctx* ctx, sisic_pair_sqdist_args* a) {
+    SISIC_REQUIRE(ctx && a && a->a && a->b && a->idx && a->out, "pair_sqdist: null argument");
+    SISIC_REQUIRE(a->n > 0 && a->nb > 0 && a->d > 0 && a->k > 0 && a->lda >= a->d && a->ldb >= a->d,
+                  "pair_sqdist: n %d, nb %d, d %d, k %d, lda %lld, ldb %lld", a->n, a->nb, a->d, a->k, (long long)a->lda,
+                  (long long)a->ldb);
+    SISIC_REQUIRE((int64_t)a->n * a->k <= 0x7fffffff, "pair_sqdist: %lld pairs in one call", (long long)a->n * a->k);
+    return launch_pair_sqdist(ctx, a->a, a->lda, a->b, a->ldb, a->n, a->nb, a->d, a->k, a->idx, a->out,
+                              static_cast<hipStream_t>(a->stream));
+}
+
+int sisic_matrix_sum(sisic_ctx* ctx, sisic_matrix_sum_args* a) {
+    SISIC_REQUIRE(ctx && a && a->x && a->out, "matrix_sum: null argument");
+    SISIC_REQUIRE(a->n > 0 && a->m > 0 && a->ld >= a->m, "matrix_sum: n %d, m %d, ld %lld", a->n, a->m, (long long)a->ld);
+    return launch_matrix_sum(ctx, a->x, a->ld, a->n, a->m, a->exclude_diagonal ? 1 : 0, a->out, static_cast<hipStream_t>(a->stream));
+}
+
 int sisic_profile_enable(sisic_ctx* ctx, int on) {
     SISIC_REQUIRE(ctx, "profile_enable: null context");
     ctx->profiling = on != 0;

@@ -128,6 +128,27 @@ int launch_avgpool_fc(sisic_ctx* ctx, const float* x, const float* w, const floa
     return SISIC_OK;
 }
 
+// AdaptiveAvgPool2d(1) alone (sisic_resnet_features): one thread per (sample, channel), the sum and the scaling of
+// avgpool_fc_kernel above, so the value has the bits that kernel's Linear reads
+__global__ void __launch_bounds__(256)
+avgpool_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t planes, int HW) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= planes) return;
+    const float inv = 1.0f / (float)HW;
+    const float* src = x + p * HW;
+    float acc = 0.0f;
+    for (int i = 0; i < HW; ++i) acc += src[i];
+    out[p] = acc * inv;
+}
+
+int launch_avgpool(sisic_ctx* ctx, const float* x, float* out, int B, int C, int HW, hipStream_t s) {
+    ProfileScope prof(ctx, s, PK_OTHER, 4.0 * B * C * HW, 0.0);
+    const int64_t planes = (int64_t)B * C;
+    hipLaunchKernelGGL(avgpool_kernel, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, s, x, out, planes, HW);
+    SISIC_HIP(hipGetLastError());
+    return SISIC_OK;
+}
+
 // probs = softmax(logits, 1)[:, target];  logscore = log(probs + 1e-8)
 __global__ void class_scores_kernel(const float* __restrict__ logits, int B, int n, int target, float* __restrict__ prob,
                                     float* __restrict__ logscore) {

@@ -320,6 +320,8 @@ int launch_preprocess(sisic_ctx*, const float* x, float* out, int B, int H, int 
 int launch_maxpool(sisic_ctx*, const float* x, float* out, int B, int C, int H, int W, hipStream_t s);
 int launch_avgpool_fc(sisic_ctx*, const float* x, const float* w, const float* bias, float* out, int B, int C, int HW,
                       int n_out, hipStream_t s);
+// AdaptiveAvgPool2d(1) alone: out [B, C], each value the bits avgpool_fc_kernel feeds its Linear
+int launch_avgpool(sisic_ctx*, const float* x, float* out, int B, int C, int HW, hipStream_t s);
 int launch_class_scores(sisic_ctx*, const float* logits, int B, int n, int target, float* prob, float* logscore,
                         hipStream_t s);
 int launch_mask_patches(sisic_ctx*, const float* image, const uint8_t* masks, float* out, int S, int C, int H, int W,
@@ -338,6 +340,15 @@ int launch_resample_diffs(sisic_ctx*, const double* top, int n_top, const double
 // raw_t (may be NULL) its tap-flipped transposed copy; sc NULL writes the values themselves
 int launch_randomize_weight(sisic_ctx*, float* raw, float* raw_t, const double* sc, int cout, int cin, int k, uint64_t seed,
                             uint32_t trial, uint32_t tag, float strength, hipStream_t s);
+
+// eval_kernels.hip: the pairwise arithmetic of the evaluation metrics (include/sisic.h); the entry points check the arguments
+int launch_gram(sisic_ctx*, const sisic_gram_args& g, hipStream_t s);
+int launch_col_means(sisic_ctx*, const float* x, int64_t ld, int n, int d, double* mean_out, hipStream_t s);
+int launch_matrix_sum(sisic_ctx*, const float* x, int64_t ld, int n, int m, int exclude_diagonal, double* out, hipStream_t s);
+int launch_rows_topk(sisic_ctx*, const float* dist, int64_t ld, const float* col_offset, int n, int m, int k, int skip_diagonal,
+                     float* val_out, int32_t* idx_out, hipStream_t s);
+int launch_pair_sqdist(sisic_ctx*, const float* a, int64_t lda, const float* b, int64_t ldb, int n, int nb, int d, int k,
+                       const int32_t* idx, float* out, hipStream_t s);
 
 // augment.hip: the training loader's augmentation chain on a device-resident uint8 dataset (include/sisic.h); out is
 // float32 [B,3,H,W] or, with u8, uint8 [B,H,W,3]

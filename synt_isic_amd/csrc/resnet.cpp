@@ -324,6 +324,7 @@ struct Trunk {
     const char* who = "resnet_input_gradient";
     bool split_last = false;     // last block: bn2(conv2(.)) alone into ylast, then relu(. + identity) (Grad-CAM reads ylast)
     float* logits = nullptr;     // where the logits go; nullptr: into a block of the scope, returned here
+    float* features = nullptr;   // stop at the pooled features [B, 512], written here: no Linear, no logits (sisic_resnet_features)
     struct Saved { float* t1; float* out; int h, w, bh, bw; };
     std::vector<Saved> saved;    // keep: one per block
     float* c1 = nullptr;         // relu(bn1(conv1(.))) [B, 64, c1h, c1w]
@@ -393,6 +394,11 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
             ws.put(act);
         }
         act = t2; h = bh; w = bw;
+    }
+    if (t.features) {
+        SISIC_TRY(launch_avgpool(r->ctx, act, t.features, B, r->blocks.back().conv2.cout, h * w, s));
+        t.act = act; t.h = h; t.w = w;
+        return SISIC_OK;
     }
     if (!t.logits) SISIC_TRY(ws.get((size_t)B * r->num_classes, &t.logits));
     SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, t.logits, B, r->blocks.back().conv2.cout, h * w, r->num_classes, s));
@@ -555,6 +561,23 @@ int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, 
     t.preprocess = preprocess != 0;
     t.logits = logits;
     return run_trunk(r, ws, x, B, H, W, t, s);
+}
+
+// The forward up to and including the global average pool: the features the evaluation metrics are computed on.
+int sisic_resnet_features(sisic_resnet* r, sisic_resnet_features_args* a) {
+    SISIC_REQUIRE(r && a && a->x && a->out && a->B > 0 && a->H > 0 && a->W > 0, "resnet_features: bad arguments");
+    if (!r->loaded) {
+        set_error("resnet_features called before sisic_resnet_load");
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    SISIC_TRY(workspace_for(r, a->B, a->H, a->W));
+    hipStream_t s = static_cast<hipStream_t>(a->stream);
+    PoolScope ws(r->pool, s);
+    Trunk t;
+    t.preprocess = a->preprocess != 0;
+    t.features = a->out;
+    return run_trunk(r, ws, a->x, a->B, a->H, a->W, t, s);
 }
 
 // The stem's activation relu(bn1(conv1(pre(x)))) alone: what the 3x3/2 max-pool chooses its arg-maxima from.  Parity tests

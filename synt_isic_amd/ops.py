@@ -724,6 +724,98 @@ def augment(dataset: torch.Tensor, params: np.ndarray, *, u8: bool = False) -> t
     return out
 
 
+# ---- evaluation of generated sets (include/sisic.h; synt_isic_amd/evaluate.py builds the metrics on these) ------------------------
+def _mat(t: torch.Tensor, name: str):
+    """(pointer, rows, cols, leading dimension) of a row-major fp32 matrix on the GPU; rows may be strided (a column slice)"""
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name} must be a non-empty fp32 [rows, cols] tensor on the GPU (got {t.dtype}, {t.device}, "
+                         f"{tuple(t.shape)})")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be row-major with unit column stride (strides {t.stride()})")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    return t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(ld)
+
+
+def _vec(t: Optional[torch.Tensor], n: int, name: str) -> Optional[int]:
+    if t is None:
+        return None
+    if t.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), got {tuple(t.shape)}")
+    return _ptr(t, name)
+
+
+def col_means(x: torch.Tensor) -> torch.Tensor:
+    """sisic_col_means: the column means of ``x`` [n,d] as float64 [d], summed in double in a fixed order."""
+    p, n, d, ld = _mat(x, "x")
+    out = empty(d, dtype=torch.float64, device=x.device)
+    a = _lib.ColMeansArgs(x=p, mean_out=out.data_ptr(), stream=_stream(x.device), ld=ld, n=n, d=d)
+    check(_lib.load().sisic_col_means(context(x.device), C.byref(a)))
+    return out
+
+
+def gram(a: torch.Tensor, b: Optional[torch.Tensor] = None, *, mode: str = "dot", shift_a: Optional[torch.Tensor] = None,
+         shift_b: Optional[torch.Tensor] = None, contract_rows: bool = False) -> torch.Tensor:
+    """sisic_gram: ``f((a - shift_a) (b - shift_b)^T)`` [n,m] on the f32 matrix pipe, ``mode`` one of ``dot``, ``sqdist``
+    (``max(0, |a'|^2 + |b'|^2 - 2 s)``) and ``poly3`` (``(s / d + 1)^3``); ``b`` None: ``a``.  The shifts (fp32 [d]) are
+    subtracted while the operands are staged.  ``contract_rows``: ``(a - shift_a)^T (a - shift_a)`` [d,d] instead."""
+    if mode not in _lib.GRAM_MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(_lib.GRAM_MODES)}")
+    pa, n, d, lda = _mat(a, "a")
+    pb, m, ldb = None, n, 0
+    if b is not None:
+        pb, m, db, ldb = _mat(b, "b")
+        if db != d or b.device != a.device:
+            raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} differ in row length or device")
+    if contract_rows and (b is not None or shift_b is not None or mode != "dot"):
+        raise ValueError("contract_rows computes (a - shift_a)^T (a - shift_a): no b, no shift_b, mode 'dot'")
+    out = empty((d, d) if contract_rows else (n, m), dtype=torch.float32, device=a.device)
+    g = _lib.GramArgs(a=pa, b=pb, shift_a=_vec(shift_a, d, "shift_a"), shift_b=_vec(shift_b, d, "shift_b"), out=out.data_ptr(),
+                      stream=_stream(a.device), lda=lda, ldb=ldb, ldo=out.shape[1], n=n, m=m, d=d, mode=_lib.GRAM_MODES[mode],
+                      contract_rows=1 if contract_rows else 0)
+    check(_lib.load().sisic_gram(context(a.device), C.byref(g)))
+    return out
+
+
+def rows_topk(dist: torch.Tensor, k: int, *, col_offset: Optional[torch.Tensor] = None, skip_diagonal: bool = False):
+    """sisic_rows_topk: per row of ``dist`` [n,m] the ``k`` (1..8) smallest of ``dist[i,j] - col_offset[j]``, ascending, ties to
+    the lower column, ``j == i`` left out with ``skip_diagonal``: (values fp32 [n,k], columns int32 [n,k])."""
+    p, n, m, ld = _mat(dist, "dist")
+    k = int(k)
+    val = empty((n, max(k, 1)), dtype=torch.float32, device=dist.device)
+    idx = empty((n, max(k, 1)), dtype=torch.int32, device=dist.device)
+    a = _lib.RowsTopkArgs(dist=p, col_offset=_vec(col_offset, m, "col_offset"), val_out=val.data_ptr(), idx_out=idx.data_ptr(),
+                          stream=_stream(dist.device), ld=ld, n=n, m=m, k=k, skip_diagonal=1 if skip_diagonal else 0)
+    check(_lib.load().sisic_rows_topk(context(dist.device), C.byref(a)))
+    return val, idx
+
+
+def pair_sqdist(a: torch.Tensor, b: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """sisic_pair_sqdist: ``sum_c (a[i,c] - b[idx[i,j],c])^2`` [n,k], the differences and the sum in double, stored as fp32."""
+    pa, n, d, lda = _mat(a, "a")
+    pb, nb, db, ldb = _mat(b, "b")
+    if db != d or b.device != a.device:
+        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} differ in row length or device")
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != n or idx.shape[1] < 1 or not idx.is_contiguous() \
+            or idx.device != a.device:
+        raise ValueError(f"idx must be a contiguous int32 [{n}, k] tensor on {a.device}, got {idx.dtype} {tuple(idx.shape)}")
+    out = empty(tuple(idx.shape), dtype=torch.float32, device=a.device)
+    g = _lib.PairSqdistArgs(a=pa, b=pb, idx=idx.data_ptr(), out=out.data_ptr(), stream=_stream(a.device), lda=lda, ldb=ldb, n=n,
+                            nb=nb, d=d, k=int(idx.shape[1]))
+    check(_lib.load().sisic_pair_sqdist(context(a.device), C.byref(g)))
+    return out
+
+
+def matrix_sum(x: torch.Tensor, exclude_diagonal: bool = False) -> torch.Tensor:
+    """sisic_matrix_sum: the sum of ``x`` [n,m] (without the entries ``i == j`` if asked) as a float64 [1] on the device, summed
+    in double in a fixed order."""
+    p, n, m, ld = _mat(x, "x")
+    out = empty(1, dtype=torch.float64, device=x.device)
+    a = _lib.MatrixSumArgs(x=p, out=out.data_ptr(), stream=_stream(x.device), ld=ld, n=n, m=m,
+                           exclude_diagonal=1 if exclude_diagonal else 0)
+    check(_lib.load().sisic_matrix_sum(context(x.device), C.byref(a)))
+    return out
+
+
 _KINDS = {"conv3x3": 0, "conv1x1": 1, "groupnorm": 2, "attention": 3, "ddpm_step": 4, "other": 5,
           "conv3x3_winograd_main": 6, "conv3x3_winograd_bf16x3": 7}
 
