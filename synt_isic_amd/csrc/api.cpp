@@ -204,82 +204,95 @@ int sisic_attention(sisic_ctx* ctx, const float* qkv, float* out, int B, int C, 
     return launch_attention(ctx, qkv, out, B, C, N, head_dim, static_cast<hipStream_t>(stream));
 }
 
+// The single scheduler steps: each entry names its part of one StepLaunch.  What eps means is the context's
+// (sisic_set_step_prediction_type), in all nine.
+static void step_tensors(StepLaunch& L, const sisic_ctx* ctx, int rule, int use_clipped_model_output, const float* eps,
+                         const float* x, float* hist, float* out, int64_t n, const float* row, float clip) {
+    L.rule = rule;
+    L.flags = (use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0) | step_pred_flags(ctx->step_pred);
+    L.eps = eps; L.x = x; L.hist = hist; L.out = out; L.n = n; L.row = row; L.clip = clip;
+}
+
+// the _rng entries: z generated in the kernel
+static int step_rng(sisic_ctx* ctx, const char* what, StepLaunch& L, int rule, int use_clipped_model_output, const float* eps,
+                    const float* x, float* hist, float* out, int B, int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step,
+                    const float* row, float clip, void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "%s: null context or empty batch", what);
+    step_tensors(L, ctx, rule, use_clipped_model_output, eps, x, hist, out, (int64_t)B * n_per_image, row, clip);
+    L.device_noise = true; L.seeds_dev = seeds_dev; L.n_per_image = n_per_image; L.step = step;
+    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+}
+
+// the _edit entries: the _rng entries' arguments, the known image, the mask and the edit row
+static int step_edit(sisic_ctx* ctx, const char* what, int rule, int use_clipped_model_output, const float* eps, const float* x,
+                     float* hist, float* out, int B, int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step,
+                     const float* row, float clip, const float* x0k, const float* mask, int Cn, int64_t HW, float ck, float sk,
+                     float ja, float jb, void* stream) {
+    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "%s: null context or empty batch", what);
+    SISIC_REQUIRE(Cn > 0 && HW > 0 && (int64_t)Cn * HW == n_per_image, "%s: C = %d, HW = %lld for images of %lld elements", what,
+                  Cn, (long long)HW, (long long)n_per_image);
+    const float erow[4] = {ck, sk, ja, jb};
+    StepLaunch L;
+    L.edit = true; L.x0k = x0k; L.mask = mask; L.hw = HW; L.erow = erow;
+    return step_rng(ctx, what, L, rule, use_clipped_model_output, eps, x, hist, out, B, n_per_image, seeds_dev, step, row, clip, stream);
+}
+
 int sisic_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n,
                     float sqrt_beta_prod, float sqrt_alpha_prod, float c0, float c1, float sigma, float clip,
                     void* stream) {
     SISIC_REQUIRE(ctx, "ddpm_step: null context");
-    // (what eps means is the context's: sisic_set_step_prediction_type, here and in the eight entries below)
-    return launch_step(ctx, STEP_RULE_DDPM, step_pred_flags(ctx->step_pred), eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod,
-                       c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma};
+    StepLaunch L;
+    step_tensors(L, ctx, STEP_RULE_DDPM, 0, eps, x, nullptr, out, n, row, clip);
+    L.z = z;
+    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
 }
 
 int sisic_ddim_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n,
                     float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev, float c_dir, float sigma, float clip,
                     int use_clipped_model_output, void* stream) {
     SISIC_REQUIRE(ctx, "ddim_step: null context");
-    const int flags = (use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0) | step_pred_flags(ctx->step_pred);
-    return launch_step(ctx, STEP_RULE_DDIM, flags, eps, x, z, out, n, sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip,
-                       static_cast<hipStream_t>(stream));
-}
-
-int sisic_noise_fill(sisic_ctx* ctx, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
-                     uint32_t tag, void* stream) {
-    SISIC_REQUIRE(ctx, "noise_fill: null context");
-    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, false, static_cast<hipStream_t>(stream));
-}
-
-int sisic_noise_bits(sisic_ctx* ctx, uint32_t* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
-                     uint32_t tag, void* stream) {
-    SISIC_REQUIRE(ctx, "noise_bits: null context");
-    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, true, static_cast<hipStream_t>(stream));
-}
-
-int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
-                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
-                        float c1, float sigma, float clip, void* stream) {
-    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddpm_step_rng: null context or empty batch");
-    return launch_step_rng(ctx, STEP_RULE_DDPM, step_pred_flags(ctx->step_pred), eps, x, out, (int64_t)B * n_per_image, n_per_image,
-                           seeds_dev, step, sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma, clip, static_cast<hipStream_t>(stream));
-}
-
-int sisic_ddim_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
-                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
-                        float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream) {
-    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "ddim_step_rng: null context or empty batch");
-    const int flags = (use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0) | step_pred_flags(ctx->step_pred);
-    return launch_step_rng(ctx, STEP_RULE_DDIM, flags, eps, x, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step,
-                           sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma, clip, static_cast<hipStream_t>(stream));
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma};
+    StepLaunch L;
+    step_tensors(L, ctx, STEP_RULE_DDIM, use_clipped_model_output, eps, x, nullptr, out, n, row, clip);
+    L.z = z;
+    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
 }
 
 int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
                      float sqrt_beta_prod, float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip,
                      void* stream) {
     SISIC_REQUIRE(ctx, "dpmpp_step: null context");
-    return launch_dpm_step(ctx, eps, x, z, hist, out, n, sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1, clip,
-                           static_cast<hipStream_t>(stream), step_pred_flags(ctx->step_pred));
+    const float row[6] = {sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1};
+    StepLaunch L;
+    step_tensors(L, ctx, STEP_RULE_DPMPP, 0, eps, x, hist, out, n, row, clip);
+    L.z = z;
+    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+}
+
+int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c0,
+                        float c1, float sigma, float clip, void* stream) {
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma};
+    StepLaunch L;
+    return step_rng(ctx, "ddpm_step_rng", L, STEP_RULE_DDPM, 0, eps, x, nullptr, out, B, n_per_image, seeds_dev, step, row, clip, stream);
+}
+
+int sisic_ddim_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
+                        const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod, float sqrt_alpha_prod, float c_prev,
+                        float c_dir, float sigma, float clip, int use_clipped_model_output, void* stream) {
+    const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma};
+    StepLaunch L;
+    return step_rng(ctx, "ddim_step_rng", L, STEP_RULE_DDIM, use_clipped_model_output, eps, x, nullptr, out, B, n_per_image, seeds_dev,
+                    step, row, clip, stream);
 }
 
 int sisic_dpmpp_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int B,
                          int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sqrt_beta_prod,
                          float sqrt_alpha_prod, float cx, float k0, float sigma, float k1, float clip, void* stream) {
-    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "dpmpp_step_rng: null context or empty batch");
-    return launch_dpm_step_rng(ctx, eps, x, hist, out, (int64_t)B * n_per_image, n_per_image, seeds_dev, step, sqrt_beta_prod,
-                               sqrt_alpha_prod, cx, k0, sigma, k1, clip, static_cast<hipStream_t>(stream),
-                               step_pred_flags(ctx->step_pred));
-}
-
-// the single edited steps: the _rng entries' arguments, the known image, the mask and the edit row
-static int step_edit(sisic_ctx* ctx, const char* what, int rule, int flags, const float* eps, const float* x, float* hist,
-                     float* out, int B, int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, const float* row,
-                     float clip, const float* x0k, const float* mask, int Cn, int64_t HW, float ck, float sk, float ja, float jb,
-                     void* stream) {
-    SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "%s: null context or empty batch", what);
-    SISIC_REQUIRE(Cn > 0 && HW > 0 && (int64_t)Cn * HW == n_per_image, "%s: C = %d, HW = %lld for images of %lld elements", what,
-                  Cn, (long long)HW, (long long)n_per_image);
-    const float erow[4] = {ck, sk, ja, jb};
-    return launch_step_edit(ctx, rule, flags | step_pred_flags(ctx->step_pred), eps, nullptr, 1.0f, nullptr, x, hist, out,
-                            (int64_t)B * n_per_image, n_per_image, HW, seeds_dev, step, row, erow, nullptr, nullptr, nullptr, x0k,
-                            mask, clip, static_cast<hipStream_t>(stream));
+    const float row[6] = {sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1};
+    StepLaunch L;
+    return step_rng(ctx, "dpmpp_step_rng", L, STEP_RULE_DPMPP, 0, eps, x, hist, out, B, n_per_image, seeds_dev, step, row, clip, stream);
 }
 
 int sisic_ddpm_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
@@ -296,8 +309,8 @@ int sisic_ddim_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float
                          float c_dir, float sigma, float clip, int use_clipped_model_output, const float* x0k,
                          const float* mask, int C, int64_t HW, float ck, float sk, float ja, float jb, void* stream) {
     const float row[5] = {sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma};
-    return step_edit(ctx, "ddim_step_edit", STEP_RULE_DDIM, use_clipped_model_output ? STEP_FLAG_CLIPPED_OUTPUT : 0, eps, x,
-                     nullptr, out, B, n_per_image, seeds_dev, step, row, clip, x0k, mask, C, HW, ck, sk, ja, jb, stream);
+    return step_edit(ctx, "ddim_step_edit", STEP_RULE_DDIM, use_clipped_model_output, eps, x, nullptr, out, B, n_per_image, seeds_dev,
+                     step, row, clip, x0k, mask, C, HW, ck, sk, ja, jb, stream);
 }
 
 int sisic_dpmpp_step_edit(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int B,
@@ -307,6 +320,18 @@ int sisic_dpmpp_step_edit(sisic_ctx* ctx, const float* eps, const float* x, floa
     const float row[6] = {sqrt_beta_prod, sqrt_alpha_prod, cx, k0, sigma, k1};
     return step_edit(ctx, "dpmpp_step_edit", STEP_RULE_DPMPP, 0, eps, x, hist, out, B, n_per_image, seeds_dev, step, row, clip,
                      x0k, mask, C, HW, ck, sk, ja, jb, stream);
+}
+
+int sisic_noise_fill(sisic_ctx* ctx, float* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream) {
+    SISIC_REQUIRE(ctx, "noise_fill: null context");
+    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, false, static_cast<hipStream_t>(stream));
+}
+
+int sisic_noise_bits(sisic_ctx* ctx, uint32_t* out, int B, int64_t n_per_image, const uint64_t* seeds, uint32_t step,
+                     uint32_t tag, void* stream) {
+    SISIC_REQUIRE(ctx, "noise_bits: null context");
+    return launch_noise_fill(ctx, out, B, n_per_image, seeds, step, tag, true, static_cast<hipStream_t>(stream));
 }
 
 int sisic_set_step_prediction_type(sisic_ctx* ctx, int type) {

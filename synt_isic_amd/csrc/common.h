@@ -225,62 +225,55 @@ inline int step_pred(int flags) { return (flags & STEP_FLAG_PRED_MASK) >> STEP_F
 inline int step_pred_flags(int type) { return type << STEP_FLAG_PRED_SHIFT; }
 // a known rule, flags it has, sa != 0, and sb != 0 where the rule divides by it
 int check_step_row(int rule, int flags, float sb, float sa);
-int launch_step(sisic_ctx*, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
-                float sb, float sa, float c2, float c3, float sigma, float clip, hipStream_t s);
 // graph-replayed sampling loop (elementwise.hip): per-step parameters selected on the device by a step index
 size_t loop_state_bytes();     // {int step; int step_base; const float* noise_base}
 int launch_loop_select_row(sisic_ctx*, const float* table, int R, const void* state, float* out, hipStream_t s);
 int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s);
-int launch_step_indexed(sisic_ctx*, int rule, int flags, const float* eps, float* x, int64_t n, const void* state,
-                        const float* coef, const int* zrow, float clip, hipStream_t s);
-// device noise (noise_device.h): the step with z generated in the kernel from the images' seeds (device
-// uint64 [n / n_per_image]), eager and graph-replayed forms; the blocks as a buffer of normals or raw words (HOST seeds)
-int launch_step_rng(sisic_ctx*, int rule, int flags, const float* eps, const float* x, float* out, int64_t n,
-                    int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c2, float c3,
-                    float sigma, float clip, hipStream_t s);
-int launch_step_indexed_rng(sisic_ctx*, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
-                            const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s);
-// the DPM-Solver++(2M) rule (STEP_RULE_DPMPP): rows of six floats {sb, sa, cx, k0, sigma, k1} and one more stream, the
-// history hist [n] (the previous step's x0: written on every step, read when k1 != 0).  The launchers above refuse this rule.
-// flags: the prediction type's bits only (the rule has no flags of its own).
-int launch_dpm_step(sisic_ctx*, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
-                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s, int flags = 0);
-int launch_dpm_step_rng(sisic_ctx*, const float* eps, const float* x, float* hist, float* out, int64_t n,
-                        int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
-                        float sigma, float k1, float clip, hipStream_t s, int flags = 0);
-int launch_dpm_step_indexed(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, const void* state,
-                            const float* coef, const int* zrow, float clip, hipStream_t s, int flags = 0);
-int launch_dpm_step_indexed_rng(sisic_ctx*, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
-                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s,
-                                int flags = 0);
-// classifier-free guidance (elementwise.hip): the same rules on eps = eps_u + w * (eps_c - eps_u), formed in the step kernel; the
-// new x goes to both halves of out [2n].  seeds_dev NULL: z is a buffer (or NULL); else generated noise.  row: the rule's host
-// row (SISIC_RULE_ROW_WIDTH floats).  hist: DPM-Solver++ only.  The indexed form reads w from cond[0] (LoopCond).
-int launch_step_guided(sisic_ctx*, int rule, int flags, const float* eps_c, const float* eps_u, float w, const float* x,
-                       const float* z, const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out,
-                       int64_t n, const float* row, float clip, hipStream_t s);
-int launch_step_guided_indexed(sisic_ctx*, int rule, int flags, const float* eps2, float* x2, float* hist, int64_t n,
-                               int64_t n_per_image, const void* state, const float* coef, const int* zrow,
-                               const uint64_t* seeds_dev, const float* cond, float clip, hipStream_t s);
-// every edited step (the inpainting epilogue of elementwise.hip; generated noise only).  eps_u: a guided step, out [2n].
-// state set: the replayed form, which reads its rows from coef_dev / erows_dev (and w from cond); otherwise row / erow are host
-// rows and step, w launch arguments.  hw: H * W, the mask's row [B, 1, hw] is broadcast over n_per_image / hw channels.
-int launch_step_edit(sisic_ctx*, int rule, int flags, const float* eps, const float* eps_u, float w, const float* cond,
-                     const float* x, float* hist, float* out, int64_t n, int64_t n_per_image, int64_t hw,
-                     const uint64_t* seeds_dev, uint32_t step, const float* row, const float* erow, const void* state,
-                     const float* coef_dev, const float* erows_dev, const float* x0k, const float* mask, float clip,
-                     hipStream_t s);
+// One step of any kind (elementwise.hip step_kernel), described by name.  What its eps is:
+//   STEP_EPS_PLAIN       the model's output as it stands
+//   STEP_EPS_GUIDED      classifier-free guidance: eps_u + w * (eps - eps_u), formed in the kernel; the new x goes to both halves of
+//                        out [2n]
+//   STEP_EPS_CLASSIFIER  classifier guidance: eps - (w * sb) * grad, formed in the kernel, grad the classifier's input gradient at x
+//                        (epsilon prediction and device noise only)
+enum StepEps { STEP_EPS_PLAIN, STEP_EPS_GUIDED, STEP_EPS_CLASSIFIER };
+struct StepLaunch {
+    int rule = STEP_RULE_DDPM;
+    int flags = 0;
+    StepEps source = STEP_EPS_PLAIN;
+    bool device_noise = false;          // z is generated in the kernel from seeds_dev; else read from the buffer z (or none)
+    bool edit = false;                  // the inpainting epilogue (device noise only)
+    const float* eps = nullptr;         // [n]
+    const float* eps_u = nullptr;       // STEP_EPS_GUIDED: the null-label half
+    const float* grad = nullptr;        // STEP_EPS_CLASSIFIER
+    const float* x = nullptr;
+    float* out = nullptr;               // may be x
+    float* hist = nullptr;              // DPM-Solver++: the previous step's x0 [n], written on every step, read when k1 != 0
+    int64_t n = 0;
+    float clip = 0.0f;
+    const uint64_t* seeds_dev = nullptr;    // device uint64 [n / n_per_image]
+    int64_t n_per_image = 0;
+    const float* x0k = nullptr;         // edit: the known image [n] and the mask, whose row [B, 1, hw] is broadcast over the
+    const float* mask = nullptr;        //       n_per_image / hw channels
+    int64_t hw = 0;
+    // the eager form: the rule's host row (SISIC_RULE_ROW_WIDTH floats), the host edit row {ck, sk, ja, jb}, this step's noise
+    // row, its index in the run, and the guidance or classifier scale
+    const float* row = nullptr;
+    const float* erow = nullptr;
+    const float* z = nullptr;
+    uint32_t step = 0;
+    float w = 1.0f;
+    // the replayed form (state set): all of these are read on the device by the loop's step index instead.  coef_dev, zrow_dev
+    // (buffer noise) and erows_dev are the loop's tables; entry 0 of w_tab is w (LoopCond, LoopClf)
+    const void* state = nullptr;
+    const float* coef_dev = nullptr;
+    const int* zrow_dev = nullptr;
+    const float* erows_dev = nullptr;
+    const float* w_tab = nullptr;
+};
+int launch_step(sisic_ctx*, const StepLaunch& L, hipStream_t s);
 int launch_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s);
-// classifier guidance (elementwise.hip): the same rules on eps_hat = eps - (scale * sb) * g, formed in the step kernel, g the
-// classifier's input gradient at x.  Epsilon prediction and generated noise only.  row: the rule's host row; hist:
-// DPM-Solver++ only.  The indexed form reads scale from clf_tab[0] (LoopClf: {scale, -, -, -, int target[B]}).
+// the loop's device table of a classifier-guided call (LoopClf): {scale, -, -, -, int target[B]}
 constexpr size_t LOOP_CLF_HEAD = 4;
-int launch_step_clf(sisic_ctx*, int rule, int flags, const float* eps, const float* g, float scale, const float* x,
-                    const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
-                    const float* row, float clip, hipStream_t s);
-int launch_step_clf_indexed(sisic_ctx*, int rule, int flags, const float* eps, const float* g, float* x, float* hist, int64_t n,
-                            int64_t n_per_image, const void* state, const float* coef, const uint64_t* seeds_dev,
-                            const float* clf_tab, float clip, hipStream_t s);
 int launch_clf_guide_eps(sisic_ctx*, const float* eps, const float* g, float sb, float scale, float* out, int64_t n, hipStream_t s);
 // resnet.cpp, for the classifier-guided sampling loop (unet.cpp): what the loop checks before its first launch, and the walk of
 // sisic_resnet_input_gradient with image b's target read from targets_dev (device int [B]; NULL: `target` for every image).

@@ -1,9 +1,13 @@
 // elementwise.hip -- the HBM-bound and tiny kernels of the sampling loop:
-//   * ddpm_step_kernel  : fused DDPMScheduler.step, bit-exact vs torch CPU
-//   * ddim_step_kernel  : fused DDIMScheduler.step (epsilon prediction), bit-exact vs torch CPU
-//   * dpm_step_kernel   : fused DPM-Solver++(2M) step with its one-step history, bit-exact vs torch CPU
-//   * step_edit_kernel  : the three steps with the inpainting epilogue (RePaint) applied before the store
-//     (every step kernel under each prediction type -- epsilon, sample, v: sisic.h SISIC_PRED_*, a template parameter of the rule)
+//   * step_kernel<Rule, Eps, Noise, Edit>: every scheduler step, eager and graph-replayed, bit-exact vs torch CPU
+//       Rule : DdpmRule      fused DDPMScheduler.step
+//              DdimRule      fused DDIMScheduler.step, with or without use_clipped_model_output
+//              DpmRule       fused DPM-Solver++(2M) step with its one-step history
+//              (each under a prediction type -- epsilon, sample, v: sisic.h SISIC_PRED_*, a template parameter of the rule)
+//       Eps  : PlainEps, GuidedEps (classifier-free guidance), ClassifierEps (classifier guidance)
+//       Noise: BufferNoise (the caller's z), PhiloxNoise (generated in the kernel)
+//       Edit : NoEdit, InpaintEdit (the RePaint epilogue applied before the store)
+//     launch_step(StepLaunch) is the one way in: its table holds the 76 instantiations a caller can reach
 //   * denorm_u8_kernel  : clamp((x+1)/2,0,1)*255 -> uint8 HWC (image_generator.py:441-447)
 //   * temb_mlp_kernel   : sinusoidal timestep embedding -> Linear -> SiLU -> Linear -> SiLU
 //   * linear_t_kernel   : every ResnetBlock2D.time_emb_proj in one launch
@@ -11,6 +15,7 @@
 #include "common.h"
 #include "noise_device.h"
 #include "pack_device.h"
+#include <type_traits>
 
 namespace sisic {
 
@@ -235,41 +240,6 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
     }
 }
 
-template <int P>
-__global__ void __launch_bounds__(256)
-ddpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z,
-                 float* out, int64_t n, float sb, float sa, float c0, float c1, float sigma, float clip,
-                 int vec4) {
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdpmRule<P>{sb, sa, c0, c1, sigma, clip}, BufferNoise{z});
-}
-
-// the same step with z generated in the kernel (sisic_sample_frames_rng, eager form)
-template <int P>
-__global__ void __launch_bounds__(256)
-ddpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
-                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c0, float c1, float sigma,
-                     float clip, int vec4) {
-    const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdpmRule<P>{sb, sa, c0, c1, sigma, clip}, zs);
-}
-
-// the DDIM rule in the same two forms
-template <bool CLIPPED, int P>
-__global__ void __launch_bounds__(256)
-ddim_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* out, int64_t n, float sb,
-                 float sa, float c_prev, float c_dir, float sigma, float clip, int vec4) {
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0, DdimRule<CLIPPED, P>{sb, sa, c_prev, c_dir, sigma, clip}, BufferNoise{z});
-}
-
-template <bool CLIPPED, int P>
-__global__ void __launch_bounds__(256)
-ddim_step_rng_kernel(const float* __restrict__ eps, const float* x, float* out, int64_t n, int64_t n_per_image,
-                     const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float c_prev, float c_dir,
-                     float sigma, float clip, int vec4) {
-    const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(PlainEps{eps}, x, out, n, vec4 != 0 && zs.vec_ok(), DdimRule<CLIPPED, P>{sb, sa, c_prev, c_dir, sigma, clip}, zs);
-}
-
 // ---- DPM-Solver++(2M) step -------------------------------------------------------------
 // The second-order multistep rule of Lu et al. 2022 for epsilon prediction, with its coefficients folded on the host: the row
 // of a step is {sb = sigma_t, sa = alpha_t, cx, k0, sigma, k1} (sisic.h SISIC_RULE_DPMPP) and the step
@@ -334,158 +304,10 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
     }
 }
 
-template <int P>
-__global__ void __launch_bounds__(256)
-dpm_step_kernel(const float* __restrict__ eps, const float* x, const float* __restrict__ z, float* hist, float* out, int64_t n,
-                float sb, float sa, float cx, float k0, float sigma, float k1, float clip, int vec4) {
-    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0, DpmRule<P>{sb, sa, cx, k0, sigma, k1, clip}, BufferNoise{z});
-}
-
-template <int P>
-__global__ void __launch_bounds__(256)
-dpm_step_rng_kernel(const float* __restrict__ eps, const float* x, float* hist, float* out, int64_t n, int64_t n_per_image,
-                    const uint64_t* __restrict__ seeds, uint32_t step, float sb, float sa, float cx, float k0, float sigma,
-                    float k1, float clip, int vec4) {
-    const PhiloxNoise zs{seeds, n_per_image, step};
-    dpm_step_body(PlainEps{eps}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), DpmRule<P>{sb, sa, cx, k0, sigma, k1, clip}, zs);
-}
-
-static const char* rule_name(int rule) {
-    return rule == STEP_RULE_DPMPP ? "dpmpp_step" : rule == STEP_RULE_DDIM ? "ddim_step" : "ddpm_step";
-}
-
-// the rule and its flags as the C ABI passes them; the divisors of the rule's row when they are launch arguments
-static int check_rule(int rule, int flags) {
-    SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM || rule == STEP_RULE_DPMPP,
-                  "step rule %d (0 = DDPM, 1 = DDIM, 2 = DPM-Solver++)", rule);
-    // (the prediction type's private bits ride along: common.h STEP_FLAG_PRED_MASK)
-    const int own = flags & ~STEP_FLAG_PRED_MASK;
-    SISIC_REQUIRE((own & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || own == 0),
-                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM, DPM-Solver++: none)", rule_name(rule), own);
-    SISIC_REQUIRE(step_pred(flags) <= PRED_V, "%s: prediction type %d (0 = epsilon, 1 = sample, 2 = v)", rule_name(rule),
-                  step_pred(flags));
-    return SISIC_OK;
-}
-
-// A launch under the prediction type that `flags` carries: the statements see it as the constant P.
-#define SISIC_PRED_SWITCH(flags, ...)                                                  \
-    switch (step_pred(flags)) {                                                        \
-        case PRED_SAMPLE: { constexpr int P = PRED_SAMPLE; __VA_ARGS__; } break;       \
-        case PRED_V: { constexpr int P = PRED_V; __VA_ARGS__; } break;                 \
-        default: { constexpr int P = PRED_EPS; __VA_ARGS__; } break;                   \
-    }
-
-int check_step_row(int rule, int flags, float sb, float sa) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(sa != 0.0f, "%s: sqrt_alpha_prod is zero", rule_name(rule));
-    SISIC_REQUIRE(!(flags & STEP_FLAG_CLIPPED_OUTPUT) || sb != 0.0f,
-                  "%s: sqrt_beta_prod is zero with use_clipped_model_output", rule_name(rule));
-    SISIC_REQUIRE(!(rule == STEP_RULE_DDIM && step_pred(flags) == PRED_SAMPLE) || sb != 0.0f,
-                  "%s: sqrt_beta_prod is zero under sample prediction (the direction term divides by it)", rule_name(rule));
-    return SISIC_OK;
-}
-
-int launch_step(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* x, const float* z, float* out, int64_t n,
-                float sb, float sa, float c2, float c3, float sigma, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
-    SISIC_REQUIRE(eps && x && out && n > 0, "%s: null tensor or empty", rule_name(rule));
-    SISIC_TRY(check_step_row(rule, flags, sb, sa));
-    const bool noise = z != nullptr && sigma != 0.0f;
-    ProfileScope prof(ctx, s, PK_DDPM, (noise ? 16.0 : 12.0) * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) |
-                         reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0;
-    const int64_t work = vec4 ? (n + 3) / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DDPM)
-            hipLaunchKernelGGL(ddpm_step_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma, clip,
-                               vec4);
-        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-            hipLaunchKernelGGL((ddim_step_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
-                               clip, vec4);
-        else
-            hipLaunchKernelGGL((ddim_step_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, z, out, n, sb, sa, c2, c3, sigma,
-                               clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// counter word 0 of a block is its index in the image: 32 bits
-static constexpr int64_t NOISE_MAX_PER_IMAGE = (int64_t)1 << 34;
-
-int launch_step_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* x, float* out, int64_t n,
-                    int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float c2, float c3,
-                    float sigma, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
-    SISIC_REQUIRE(eps && x && out && seeds_dev && n > 0, "%s_rng: null tensor or empty", rule_name(rule));
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
-    SISIC_TRY(check_step_row(rule, flags, sb, sa));
-    ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DDPM)
-            hipLaunchKernelGGL(ddpm_step_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image, seeds_dev, step,
-                               sb, sa, c2, c3, sigma, clip, vec4);
-        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-            hipLaunchKernelGGL((ddim_step_rng_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image,
-                               seeds_dev, step, sb, sa, c2, c3, sigma, clip, vec4);
-        else
-            hipLaunchKernelGGL((ddim_step_rng_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, out, n, n_per_image,
-                               seeds_dev, step, sb, sa, c2, c3, sigma, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// the DPM-Solver++ step: launch_step / launch_step_rng with the history stream and the sixth scalar of its row
-int launch_dpm_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
-                    float sb, float sa, float cx, float k0, float sigma, float k1, float clip, hipStream_t s, int flags) {
-    SISIC_REQUIRE(eps && x && hist && out && n > 0, "dpmpp_step: null tensor or empty");
-    SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step: the history aliases another tensor");
-    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, flags, sb, sa));
-    const bool noise = z != nullptr && sigma != 0.0f;
-    ProfileScope prof(ctx, s, PK_DDPM, ((noise ? 20.0 : 16.0) + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) |
-                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0;
-    const int64_t work = vec4 ? (n + 3) / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, z, hist, out, n, sb, sa,
-                                                cx, k0, sigma, k1, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-int launch_dpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* hist, float* out, int64_t n,
-                        int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step, float sb, float sa, float cx, float k0,
-                        float sigma, float k1, float clip, hipStream_t s, int flags) {
-    SISIC_REQUIRE(eps && x && hist && out && seeds_dev && n > 0, "dpmpp_step_rng: null tensor or empty");
-    SISIC_REQUIRE(hist != x && hist != out && hist != eps, "dpmpp_step_rng: the history aliases another tensor");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "dpmpp_step_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
-    SISIC_TRY(check_step_row(STEP_RULE_DPMPP, flags, sb, sa));
-    ProfileScope prof(ctx, s, PK_DDPM, (16.0 + (k1 != 0.0f ? 4.0 : 0.0)) * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist) |
-                         reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, out, n,
-                                                n_per_image, seeds_dev, step, sb, sa, cx, k0, sigma, k1, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// ---- the same step with its per-step parameters read from device memory (graph-replayed sampling loop) ----------------
+// ---- the state of the graph-replayed sampling loop ---------------------------------------------------------------------
 // One captured step is replayed for every step of the loop, so nothing that changes from step to step may be a launch
 // argument: the loop keeps {step index, noise base pointer} and its per-step tables (coefficients, noise row of the step
-// or -1) in device memory; this kernel selects its row, ddpm_advance_kernel moves the index on.  Nothing that changes from
+// or -1) in device memory; the step kernel selects its row, loop_advance_kernel moves the index on.  Nothing that changes from
 // call to call either: a generated-noise call's first step index is `step_base`, and its seeds lie in a library-owned
 // buffer whose address is part of the captured launch.  The rule and its flag choose the kernel, so they are part of what a
 // captured step is (LoopKey).
@@ -494,88 +316,6 @@ struct LoopState {
     int step_base;            // generated noise: the Philox step index is step_base + step (0 in buffer-noise calls)
     const float* noise;       // base of the [n_noise, n] noise rows of this call
 };
-
-// R{sb, sa, c2, c3, sigma, clip}: DdpmRule or DdimRule<>, the row of the current step
-template <class R>
-__device__ __forceinline__ R loop_rule(const float* __restrict__ coef, int step, float clip) {
-    return R{coef[5 * step + 0], coef[5 * step + 1], coef[5 * step + 2], coef[5 * step + 3], coef[5 * step + 4], clip};
-}
-
-template <class R>
-__device__ __forceinline__ void step_indexed_body(const float* __restrict__ eps, float* x, int64_t n,
-                                                  const LoopState* __restrict__ st, const float* __restrict__ coef,
-                                                  const int* __restrict__ zrow, float clip, int vec4) {
-    const int step = st->step;
-    const int zr = zrow[step];
-    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    step_body(PlainEps{eps}, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
-}
-
-template <class R>
-__device__ __forceinline__ void step_indexed_rng_body(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
-                                                      const LoopState* __restrict__ st, const float* __restrict__ coef,
-                                                      const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    const int step = st->step;
-    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    step_body(PlainEps{eps}, x, x, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
-}
-
-template <int P>
-__global__ void __launch_bounds__(256)
-ddpm_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
-                         const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    step_indexed_body<DdpmRule<P>>(eps, x, n, st, coef, zrow, clip, vec4);
-}
-
-template <int P>
-__global__ void __launch_bounds__(256)
-ddpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
-                             const LoopState* __restrict__ st, const float* __restrict__ coef,
-                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    step_indexed_rng_body<DdpmRule<P>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
-}
-
-template <bool CLIPPED, int P>
-__global__ void __launch_bounds__(256)
-ddim_step_indexed_kernel(const float* __restrict__ eps, float* x, int64_t n, const LoopState* __restrict__ st,
-                         const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    step_indexed_body<DdimRule<CLIPPED, P>>(eps, x, n, st, coef, zrow, clip, vec4);
-}
-
-template <bool CLIPPED, int P>
-__global__ void __launch_bounds__(256)
-ddim_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, int64_t n, int64_t n_per_image,
-                             const LoopState* __restrict__ st, const float* __restrict__ coef,
-                             const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    step_indexed_rng_body<DdimRule<CLIPPED, P>>(eps, x, n, n_per_image, st, coef, seeds, clip, vec4);
-}
-
-// the DPM-Solver++ rule: rows of six floats, and the history buffer of the loop
-template <int P>
-__device__ __forceinline__ DpmRule<P> loop_dpm_rule(const float* __restrict__ coef, int step, float clip) {
-    const float* c = coef + 6 * step;
-    return DpmRule<P>{c[0], c[1], c[2], c[3], c[4], c[5], clip};
-}
-
-template <int P>
-__global__ void __launch_bounds__(256)
-dpm_step_indexed_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, const LoopState* __restrict__ st,
-                        const float* __restrict__ coef, const int* __restrict__ zrow, float clip, int vec4) {
-    const int step = st->step;
-    const int zr = zrow[step];
-    const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
-}
-
-template <int P>
-__global__ void __launch_bounds__(256)
-dpm_step_indexed_rng_kernel(const float* __restrict__ eps, float* x, float* hist, int64_t n, int64_t n_per_image,
-                            const LoopState* __restrict__ st, const float* __restrict__ coef,
-                            const uint64_t* __restrict__ seeds, float clip, int vec4) {
-    const int step = st->step;
-    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    dpm_step_body(PlainEps{eps}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
-}
 
 // tproj_cur[r] = tproj_table[step][r]: the time-embedding projections of the step about to run
 __global__ void loop_select_row_kernel(const float* __restrict__ table, int R, const LoopState* __restrict__ st,
@@ -598,239 +338,12 @@ int launch_loop_advance(sisic_ctx*, void* state, hipStream_t s) {
     return SISIC_OK;
 }
 
-int launch_step_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, const void* state,
-                        const float* coef, const int* zrow, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
-    SISIC_REQUIRE(eps && x && state && coef && zrow && n > 0, "%s_indexed: null argument", rule_name(rule));
-    ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
-    const int vec4 = (al & 15) == 0 && (n & 3) == 0;
-    const int64_t work = vec4 ? (n + 3) / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    const LoopState* st = static_cast<const LoopState*>(state);
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DDPM)
-            hipLaunchKernelGGL(ddpm_step_indexed_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
-        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-            hipLaunchKernelGGL((ddim_step_indexed_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4);
-        else
-            hipLaunchKernelGGL((ddim_step_indexed_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, st, coef, zrow, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-int launch_step_indexed_rng(sisic_ctx* ctx, int rule, int flags, const float* eps, float* x, int64_t n, int64_t n_per_image,
-                            const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP, "dpmpp_step: the rule takes a history buffer (launch_dpm_step*)");
-    SISIC_REQUIRE(eps && x && state && coef && seeds_dev && n > 0, "%s_indexed_rng: null argument", rule_name(rule));
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s_indexed_rng: %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
-                  (long long)n_per_image);
-    ProfileScope prof(ctx, s, PK_DDPM, 12.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    const LoopState* st = static_cast<const LoopState*>(state);
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DDPM)
-            hipLaunchKernelGGL(ddpm_step_indexed_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st, coef,
-                               seeds_dev, clip, vec4);
-        else if (flags & STEP_FLAG_CLIPPED_OUTPUT)
-            hipLaunchKernelGGL((ddim_step_indexed_rng_kernel<true, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st,
-                               coef, seeds_dev, clip, vec4);
-        else
-            hipLaunchKernelGGL((ddim_step_indexed_rng_kernel<false, P>), dim3(blocks), dim3(256), 0, s, eps, x, n, n_per_image, st,
-                               coef, seeds_dev, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-int launch_dpm_step_indexed(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, const void* state,
-                            const float* coef, const int* zrow, float clip, hipStream_t s, int flags) {
-    SISIC_TRY(check_rule(STEP_RULE_DPMPP, flags));
-    SISIC_REQUIRE(eps && x && hist && state && coef && zrow && n > 0, "dpmpp_step_indexed: null argument");
-    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist);
-    const int vec4 = (al & 15) == 0 && (n & 3) == 0;
-    const int64_t work = vec4 ? (n + 3) / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_indexed_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
-                                                static_cast<const LoopState*>(state), coef, zrow, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-int launch_dpm_step_indexed_rng(sisic_ctx* ctx, const float* eps, float* x, float* hist, int64_t n, int64_t n_per_image,
-                                const void* state, const float* coef, const uint64_t* seeds_dev, float clip, hipStream_t s,
-                                int flags) {
-    SISIC_TRY(check_rule(STEP_RULE_DPMPP, flags));
-    SISIC_REQUIRE(eps && x && hist && state && coef && seeds_dev && n > 0, "dpmpp_step_indexed_rng: null argument");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "dpmpp_step_indexed_rng: %lld elements are not whole images of %lld", (long long)n, (long long)n_per_image);
-    ProfileScope prof(ctx, s, PK_DDPM, 20.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hist);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 2048);
-    SISIC_PRED_SWITCH(flags, hipLaunchKernelGGL(dpm_step_indexed_rng_kernel<P>, dim3(blocks), dim3(256), 0, s, eps, x, hist, n,
-                                                n_per_image, static_cast<const LoopState*>(state), coef, seeds_dev, clip, vec4))
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// ---- classifier-free guidance: the same steps reading eps through GuidedEps --------------------------------------------------
-// One UNet pass at batch 2B leaves the conditional predictions in the first n floats of eps2 and the null-label ones in the
-// second n; the step applies its rule to guide_one() of the two and writes the new x to both halves of x2 [2n].  z, the seeds,
-// the history and n are those of the B images.  NZ: 0 a noise buffer, 1 generated noise.  The eager kernels take w and the row
-// as launch arguments; the indexed ones read the row by the loop's step index and w from cond[0] (LoopCond, below), so that a
-// captured step replays under another scale.
-struct StepRow { float v[6]; };     // a rule's row: {sb, sa, c2, c3, sigma} or DPM-Solver++'s six
-
-template <class R>
-__device__ __forceinline__ R row_rule(const StepRow& r, float clip) { return R{r.v[0], r.v[1], r.v[2], r.v[3], r.v[4], clip}; }
-
-template <class R, int NZ>
-__global__ void __launch_bounds__(256)
-step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float w, const float* x, const float* __restrict__ z,
-                   const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* out, int64_t n, StepRow row,
-                   float clip, int vec4) {
-    const GuidedEps es{ec, eu, w};
-    if constexpr (NZ == 0) {
-        step_body(es, x, out, n, vec4 != 0, row_rule<R>(row, clip), BufferNoise{z});
-    } else {
-        const PhiloxNoise zs{seeds, n_per_image, step};
-        step_body(es, x, out, n, vec4 != 0 && zs.vec_ok(), row_rule<R>(row, clip), zs);
-    }
-}
-
-template <int NZ, int P>
-__global__ void __launch_bounds__(256)
-dpm_step_guided_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float w, const float* x,
-                       const float* __restrict__ z, const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step,
-                       float* hist, float* out, int64_t n, StepRow row, float clip, int vec4) {
-    const GuidedEps es{ec, eu, w};
-    const DpmRule<P> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
-    if constexpr (NZ == 0) {
-        dpm_step_body(es, x, hist, out, n, vec4 != 0, rule, BufferNoise{z});
-    } else {
-        const PhiloxNoise zs{seeds, n_per_image, step};
-        dpm_step_body(es, x, hist, out, n, vec4 != 0 && zs.vec_ok(), rule, zs);
-    }
-}
-
-template <class R, int NZ>
-__global__ void __launch_bounds__(256)
-step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, int64_t n, int64_t n_per_image,
-                           const LoopState* __restrict__ st, const float* __restrict__ coef, const int* __restrict__ zrow,
-                           const uint64_t* __restrict__ seeds, const float* __restrict__ cond, float clip, int vec4) {
-    const int step = st->step;
-    const GuidedEps es{eps2, eps2 + n, cond[0]};
-    if constexpr (NZ == 0) {
-        const int zr = zrow[step];
-        const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-        step_body(es, x2, x2, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
-    } else {
-        const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-        step_body(es, x2, x2, n, vec4 != 0 && zs.vec_ok(), loop_rule<R>(coef, step, clip), zs);
-    }
-}
-
-template <int NZ, int P>
-__global__ void __launch_bounds__(256)
-dpm_step_guided_indexed_kernel(const float* __restrict__ eps2, float* x2, float* hist, int64_t n, int64_t n_per_image,
-                               const LoopState* __restrict__ st, const float* __restrict__ coef, const int* __restrict__ zrow,
-                               const uint64_t* __restrict__ seeds, const float* __restrict__ cond, float clip, int vec4) {
-    const int step = st->step;
-    const GuidedEps es{eps2, eps2 + n, cond[0]};
-    if constexpr (NZ == 0) {
-        const int zr = zrow[step];
-        const BufferNoise zs{zr >= 0 ? st->noise + (int64_t)zr * n : nullptr};
-        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
-    } else {
-        const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-        dpm_step_body(es, x2, hist, x2, n, vec4 != 0 && zs.vec_ok(), loop_dpm_rule<P>(coef, step, clip), zs);
-    }
-}
-
-// z != NULL or seeds_dev == NULL: the noise buffer (or none); seeds_dev: generated noise.  row: the rule's host row.
-// out: [2n] (may be x's own buffer: x is its first n floats); hist: DPM-Solver++ only.
-int launch_step_guided(sisic_ctx* ctx, int rule, int flags, const float* eps_c, const float* eps_u, float w, const float* x,
-                       const float* z, const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out,
-                       int64_t n, const float* row, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(eps_c && eps_u && x && out && row && n > 0, "%s (guided): null tensor or empty", rule_name(rule));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps_c && hist != eps_u),
-                  "dpmpp_step (guided): the history is missing or aliases another tensor");
-    SISIC_REQUIRE(!seeds_dev || (n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0),
-                  "%s (guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
-    SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
-    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
-    StepRow r{};
-    for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) r.v[k] = row[k];
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps_c) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(x) |
-                         reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0 && (n & 3) == 0 && (!seeds_dev || (n_per_image & 3) == 0);
-    const int64_t work = vec4 ? n / 4 : n;
-    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
-#define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, out, n, r, clip, vec4)
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DPMPP) {
-            if (seeds_dev) hipLaunchKernelGGL((dpm_step_guided_kernel<1, P>), grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
-            else hipLaunchKernelGGL((dpm_step_guided_kernel<0, P>), grid, block, 0, s, eps_c, eps_u, w, x, z, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
-        } else if (rule == STEP_RULE_DDPM) {
-            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdpmRule<P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdpmRule<P>, 0>));
-        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<true, P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<true, P>, 0>));
-        } else {
-            if (seeds_dev) SISIC_GUIDED((step_guided_kernel<DdimRule<false, P>, 1>)); else SISIC_GUIDED((step_guided_kernel<DdimRule<false, P>, 0>));
-        })
-#undef SISIC_GUIDED
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// the graph-replayed form: eps2 [2n] and x2 [2n] are the loop's own buffers, zrow the buffer-noise rows (seeds_dev NULL) or
-// unused (generated noise), cond the loop's LoopCond table (w at cond[0])
-int launch_step_guided_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps2, float* x2, float* hist, int64_t n,
-                               int64_t n_per_image, const void* state, const float* coef, const int* zrow,
-                               const uint64_t* seeds_dev, const float* cond, float clip, hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(eps2 && x2 && state && coef && cond && (zrow || seeds_dev) && n > 0, "%s_indexed (guided): null argument", rule_name(rule));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || hist, "dpmpp_step_indexed (guided): no history buffer");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s_indexed (guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n, (long long)n_per_image);
-    ProfileScope prof(ctx, s, PK_DDPM, 24.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(hist);
-    const int vec4 = (al & 15) == 0 && (n & 3) == 0 && (!seeds_dev || (n_per_image & 3) == 0);
-    const int64_t work = vec4 ? n / 4 : n;
-    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
-    const LoopState* st = static_cast<const LoopState*>(state);
-#define SISIC_GUIDED(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps2, x2, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4)
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DPMPP) {
-            if (seeds_dev) hipLaunchKernelGGL((dpm_step_guided_indexed_kernel<1, P>), grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
-            else hipLaunchKernelGGL((dpm_step_guided_indexed_kernel<0, P>), grid, block, 0, s, eps2, x2, hist, n, n_per_image, st, coef, zrow, seeds_dev, cond, clip, vec4);
-        } else if (rule == STEP_RULE_DDPM) {
-            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule<P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdpmRule<P>, 0>));
-        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true, P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<true, P>, 0>));
-        } else {
-            if (seeds_dev) SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false, P>, 1>)); else SISIC_GUIDED((step_guided_indexed_kernel<DdimRule<false, P>, 0>));
-        })
-#undef SISIC_GUIDED
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
 // ---- classifier guidance: the same steps reading eps through ClassifierEps ----------------------------------------------------
 // eps_hat = eps - k * g with k = scale * sb (Dhariwal & Nichol 2021, Alg. 2): g is the classifier's input
 // gradient at the step's latent, sb entry 0 of the step's row.  k is formed in the kernel, so the eager, the indexed and the
-// stand-alone form (sisic_clf_guide_eps) round it the same way.  Epsilon prediction and generated noise only.  The eager kernels
-// take scale and the row as launch arguments; the indexed ones read the row by the loop's step index and scale from
-// clf_tab[0] (LoopClf: {scale, -, -, -, int target[B]}), so that a captured step replays under another scale.
+// stand-alone form (sisic_clf_guide_eps) round it the same way.  Epsilon prediction and generated noise only.  An eager step
+// takes scale and the row as launch arguments; a replayed one reads the row by the loop's step index and scale from entry 0
+// of the loop's table (LoopClf: {scale, -, -, -, int target[B]}), so that a captured step replays under another scale.
 __device__ __forceinline__ float clf_guide_k(float scale, float sb) {
 #pragma clang fp contract(off)
     return scale * sb;
@@ -855,109 +368,210 @@ struct ClassifierEps {
     __device__ __forceinline__ float get1(int64_t i) const { return clf_guide_one(e[i], g[i], k); }
 };
 
-template <class R>
+// ---- the step kernel: one template over {rule, eps source, noise source, edit}, one argument block ---------------------------
+// Every step of the library is step_kernel<R, EPS, NZ, EDIT>(StepArgs).  With st set (the replayed form) the rule's row, the
+// edit row, the step index, w and the noise row are read by the loop's step, one wave-uniform branch at entry; otherwise they
+// are the launch's own.  A feature of the step is a policy struct above and a row of the table below.
+struct StepRow { float v[6]; };     // a rule's row: {sb, sa, c2, c3, sigma} or DPM-Solver++'s six
+
+// what the kernel has to know of a rule beside its arithmetic
+template <class R> struct RuleTraits { static constexpr int width = 5; static constexpr bool history = false; };
+template <int P> struct RuleTraits<DpmRule<P>> { static constexpr int width = 6; static constexpr bool history = true; };
+
+struct StepArgs {
+    const float* eps;                   // eps [n]; GuidedEps: the conditional half
+    const float* eps2;                  // GuidedEps: the null-label half; ClassifierEps: the gradient g
+    const float* x;
+    float* out;                         // may be x; GuidedEps: [2n]
+    float* hist;                        // rules with a history
+    const float* z;                     // BufferNoise, eager: this step's row, or nullptr
+    const uint64_t* seeds;              // PhiloxNoise, InpaintEdit: [n / npi] device
+    const float* x0k;                   // InpaintEdit
+    const float* mask;
+    const LoopState* st;                // replayed form, or nullptr
+    const float* coef;                  // replayed form: the rule's rows ...
+    const int* zrow;                    // ... BufferNoise: the noise row of each step, or -1 ...
+    const float* erows;                 // ... InpaintEdit: the edit rows {ck, sk, ja, jb} ...
+    const float* wtab;                  // ... and the table whose entry 0 is w (LoopCond) or the classifier scale (LoopClf)
+    int64_t n, npi, hw;
+    StepRow row;
+    float er[4];
+    float w, clip;
+    uint32_t step;
+    int vec4;
+};
+
+template <class R, class EPS, class NZ, class EDIT>
 __global__ void __launch_bounds__(256)
-step_clf_kernel(const float* __restrict__ eps, const float* __restrict__ g, float scale, const float* x,
-                const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* out, int64_t n, StepRow row,
-                float clip, int vec4) {
-    const PhiloxNoise zs{seeds, n_per_image, step};
-    step_body(ClassifierEps{eps, g, clf_guide_k(scale, row.v[0])}, x, out, n, vec4 != 0 && zs.vec_ok(), row_rule<R>(row, clip), zs);
+step_kernel(const StepArgs a) {
+    constexpr int WIDTH = RuleTraits<R>::width;
+    StepRow row = a.row;
+    float er[4] = {a.er[0], a.er[1], a.er[2], a.er[3]};
+    uint32_t step = a.step;
+    float w = a.w;
+    const float* z = a.z;
+    if (a.st) {
+        const int i = a.st->step;
+        step = (uint32_t)(a.st->step_base + i);
+        for (int k = 0; k < WIDTH; ++k) row.v[k] = a.coef[WIDTH * i + k];
+        if constexpr (EDIT::on)
+            for (int k = 0; k < 4; ++k) er[k] = a.erows[4 * i + k];
+        if constexpr (!std::is_same_v<EPS, PlainEps>) w = a.wtab[0];
+        if constexpr (std::is_same_v<NZ, BufferNoise>) {
+            const int zr = a.zrow[i];
+            z = zr >= 0 ? a.st->noise + (int64_t)zr * a.n : nullptr;
+        }
+    }
+    const auto es = [&] {
+        if constexpr (std::is_same_v<EPS, GuidedEps>) return GuidedEps{a.eps, a.eps2, w};
+        else if constexpr (std::is_same_v<EPS, ClassifierEps>) return ClassifierEps{a.eps, a.eps2, clf_guide_k(w, row.v[0])};
+        else return PlainEps{a.eps};
+    }();
+    const auto zs = [&] {
+        if constexpr (std::is_same_v<NZ, BufferNoise>) return BufferNoise{z};
+        else return PhiloxNoise{a.seeds, a.npi, step};
+    }();
+    const auto ed = [&] {
+        if constexpr (EDIT::on) return InpaintEdit{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
+        else return NoEdit{};
+    }();
+    // (a noise row chosen on the device is only known here: the launcher's vec4 covers every pointer it could see)
+    const bool vec4 = a.vec4 != 0 && zs.vec_ok();
+    if constexpr (RuleTraits<R>::history)
+        dpm_step_body(es, a.x, a.hist, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip}, zs, ed);
+    else
+        step_body(es, a.x, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], a.clip}, zs, ed);
 }
 
-__global__ void __launch_bounds__(256)
-dpm_step_clf_kernel(const float* __restrict__ eps, const float* __restrict__ g, float scale, const float* x,
-                    const uint64_t* __restrict__ seeds, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
-                    StepRow row, float clip, int vec4) {
-    const PhiloxNoise zs{seeds, n_per_image, step};
-    const DpmRule<PRED_EPS> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], clip};
-    dpm_step_body(ClassifierEps{eps, g, clf_guide_k(scale, row.v[0])}, x, hist, out, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+// The instantiations a caller can reach: every rule and prediction type in six forms, and classifier guidance under epsilon
+// prediction.  The template arguments are a kernel's name in a trace.
+using StepKernel = void (*)(StepArgs);
+enum StepForm { FORM_BUFFER, FORM_DEVICE, FORM_GUIDED_BUFFER, FORM_GUIDED_DEVICE, FORM_EDIT, FORM_GUIDED_EDIT, FORM_CLF, STEP_FORMS };
+
+template <class R, int P>
+static constexpr StepKernel clf_form() {
+    if constexpr (P == PRED_EPS) return step_kernel<R, ClassifierEps, PhiloxNoise, NoEdit>;
+    else return nullptr;
 }
 
-template <class R>
-__global__ void __launch_bounds__(256)
-step_clf_indexed_kernel(const float* __restrict__ eps, const float* __restrict__ g, float* x, int64_t n, int64_t n_per_image,
-                        const LoopState* __restrict__ st, const float* __restrict__ coef, const uint64_t* __restrict__ seeds,
-                        const float* __restrict__ clf_tab, float clip, int vec4) {
-    const int step = st->step;
-    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    const R rule = loop_rule<R>(coef, step, clip);
-    step_body(ClassifierEps{eps, g, clf_guide_k(clf_tab[0], rule.sb)}, x, x, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+template <class R, int P>
+struct StepFormsOf {
+    static constexpr StepKernel k[STEP_FORMS] = {
+        step_kernel<R, PlainEps, BufferNoise, NoEdit>,      step_kernel<R, PlainEps, PhiloxNoise, NoEdit>,
+        step_kernel<R, GuidedEps, BufferNoise, NoEdit>,     step_kernel<R, GuidedEps, PhiloxNoise, NoEdit>,
+        step_kernel<R, PlainEps, PhiloxNoise, InpaintEdit>, step_kernel<R, GuidedEps, PhiloxNoise, InpaintEdit>,
+        clf_form<R, P>()};
+};
+
+// rows: DDPM, DDIM, DDIM with use_clipped_model_output, DPM-Solver++
+template <int P>
+static StepKernel step_kernel_of(int rule, bool clipped, int form) {
+    const StepKernel* rows[4] = {StepFormsOf<DdpmRule<P>, P>::k, StepFormsOf<DdimRule<false, P>, P>::k,
+                                 StepFormsOf<DdimRule<true, P>, P>::k, StepFormsOf<DpmRule<P>, P>::k};
+    return rows[rule == STEP_RULE_DPMPP ? 3 : rule == STEP_RULE_DDIM ? 1 + (clipped ? 1 : 0) : 0][form];
 }
 
-__global__ void __launch_bounds__(256)
-dpm_step_clf_indexed_kernel(const float* __restrict__ eps, const float* __restrict__ g, float* x, float* hist, int64_t n,
-                            int64_t n_per_image, const LoopState* __restrict__ st, const float* __restrict__ coef,
-                            const uint64_t* __restrict__ seeds, const float* __restrict__ clf_tab, float clip, int vec4) {
-    const int step = st->step;
-    const PhiloxNoise zs{seeds, n_per_image, (uint32_t)(st->step_base + step)};
-    const DpmRule<PRED_EPS> rule = loop_dpm_rule<PRED_EPS>(coef, step, clip);
-    dpm_step_body(ClassifierEps{eps, g, clf_guide_k(clf_tab[0], rule.sb)}, x, hist, x, n, vec4 != 0 && zs.vec_ok(), rule, zs);
+static const char* rule_name(int rule) {
+    return rule == STEP_RULE_DPMPP ? "dpmpp_step" : rule == STEP_RULE_DDIM ? "ddim_step" : "ddpm_step";
 }
 
-static int check_clf_step(int rule, int flags, const char* form) {
+// the rule and its flags as the C ABI passes them; the divisors of the rule's row when they are launch arguments
+static int check_rule(int rule, int flags) {
+    SISIC_REQUIRE(rule == STEP_RULE_DDPM || rule == STEP_RULE_DDIM || rule == STEP_RULE_DPMPP,
+                  "step rule %d (0 = DDPM, 1 = DDIM, 2 = DPM-Solver++)", rule);
+    // (the prediction type's private bits ride along: common.h STEP_FLAG_PRED_MASK)
+    const int own = flags & ~STEP_FLAG_PRED_MASK;
+    SISIC_REQUIRE((own & ~STEP_FLAG_CLIPPED_OUTPUT) == 0 && (rule == STEP_RULE_DDIM || own == 0),
+                  "%s: rule flags %d (DDIM: 1 = use_clipped_model_output; DDPM, DPM-Solver++: none)", rule_name(rule), own);
+    SISIC_REQUIRE(step_pred(flags) <= PRED_V, "%s: prediction type %d (0 = epsilon, 1 = sample, 2 = v)", rule_name(rule),
+                  step_pred(flags));
+    return SISIC_OK;
+}
+
+int check_step_row(int rule, int flags, float sb, float sa) {
     SISIC_TRY(check_rule(rule, flags));
-    SISIC_REQUIRE(step_pred(flags) == PRED_EPS, "%s (%s): prediction_type %d: classifier guidance takes epsilon-prediction models only",
-                  rule_name(rule), form, step_pred(flags));
+    SISIC_REQUIRE(sa != 0.0f, "%s: sqrt_alpha_prod is zero", rule_name(rule));
+    SISIC_REQUIRE(!(flags & STEP_FLAG_CLIPPED_OUTPUT) || sb != 0.0f,
+                  "%s: sqrt_beta_prod is zero with use_clipped_model_output", rule_name(rule));
+    SISIC_REQUIRE(!(rule == STEP_RULE_DDIM && step_pred(flags) == PRED_SAMPLE) || sb != 0.0f,
+                  "%s: sqrt_beta_prod is zero under sample prediction (the direction term divides by it)", rule_name(rule));
     return SISIC_OK;
 }
 
-// the eager form.  row: the rule's host row; out may be x; hist: DPM-Solver++ only
-int launch_step_clf(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* g, float scale, const float* x,
-                    const uint64_t* seeds_dev, int64_t n_per_image, uint32_t step, float* hist, float* out, int64_t n,
-                    const float* row, float clip, hipStream_t s) {
-    SISIC_TRY(check_clf_step(rule, flags, "classifier-guided"));
-    SISIC_REQUIRE(eps && g && x && out && seeds_dev && row && n > 0, "%s (classifier-guided): null tensor or empty", rule_name(rule));
-    SISIC_REQUIRE(g != out && eps != out, "%s (classifier-guided): eps or the gradient aliases the output", rule_name(rule));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps && hist != g),
-                  "dpmpp_step (classifier-guided): the history is missing or aliases another tensor");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s (classifier-guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
-                  (long long)n_per_image);
-    SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
-    ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
-    StepRow r{};
-    for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) r.v[k] = row[k];
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x) |
-                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
-    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
-#define SISIC_CLF(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps, g, scale, x, seeds_dev, n_per_image, step, out, n, r, clip, vec4)
-    if (rule == STEP_RULE_DPMPP)
-        hipLaunchKernelGGL(dpm_step_clf_kernel, grid, block, 0, s, eps, g, scale, x, seeds_dev, n_per_image, step, hist, out, n, r, clip, vec4);
-    else if (rule == STEP_RULE_DDPM) SISIC_CLF((step_clf_kernel<DdpmRule<PRED_EPS>>));
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT) SISIC_CLF((step_clf_kernel<DdimRule<true, PRED_EPS>>));
-    else SISIC_CLF((step_clf_kernel<DdimRule<false, PRED_EPS>>));
-#undef SISIC_CLF
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
+// counter word 0 of a block is its index in the image: 32 bits
+static constexpr int64_t NOISE_MAX_PER_IMAGE = (int64_t)1 << 34;
 
-// the graph-replayed form: eps, g and x are the loop's own buffers, clf_tab its LoopClf table (scale at clf_tab[0])
-int launch_step_clf_indexed(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* g, float* x, float* hist, int64_t n,
-                            int64_t n_per_image, const void* state, const float* coef, const uint64_t* seeds_dev,
-                            const float* clf_tab, float clip, hipStream_t s) {
-    SISIC_TRY(check_clf_step(rule, flags, "classifier-guided, indexed"));
-    SISIC_REQUIRE(eps && g && x && state && coef && seeds_dev && clf_tab && n > 0, "%s_indexed (classifier-guided): null argument", rule_name(rule));
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || hist, "dpmpp_step_indexed (classifier-guided): no history buffer");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s_indexed (classifier-guided): %lld elements are not whole images of %lld", rule_name(rule), (long long)n,
-                  (long long)n_per_image);
-    ProfileScope prof(ctx, s, PK_DDPM, 16.0 * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x) |
-                         reinterpret_cast<uintptr_t>(hist);
-    const int vec4 = (al & 15) == 0 && (n_per_image & 3) == 0;
-    const int64_t work = vec4 ? n / 4 : n;
+// The one launcher (common.h StepLaunch): every check, the alignment rule, the grid and the byte count of a step, once.
+int launch_step(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
+    SISIC_TRY(check_rule(L.rule, L.flags));
+    const bool guided = L.source == STEP_EPS_GUIDED, clf = L.source == STEP_EPS_CLASSIFIER;
+    const bool hist = L.rule == STEP_RULE_DPMPP, replayed = L.state != nullptr;
+    char name[64];
+    std::snprintf(name, sizeof(name), "%s%s%s", rule_name(L.rule), replayed ? "_indexed" : "",
+                  clf ? " (classifier-guided)" : L.edit ? "_edit" : guided ? " (guided)" : L.device_noise ? "_rng" : "");
+    // what no kernel is built for
+    SISIC_REQUIRE(!clf || step_pred(L.flags) == PRED_EPS, "%s: prediction_type %d: classifier guidance takes epsilon-prediction models only",
+                  name, step_pred(L.flags));
+    SISIC_REQUIRE(!clf || (L.device_noise && !L.edit), "%s: classifier guidance draws its noise on the device and takes no edit", name);
+    SISIC_REQUIRE(!L.edit || L.device_noise, "%s: an edited step draws its noise on the device", name);
+    SISIC_REQUIRE(!L.device_noise || !L.z, "%s: a noise buffer and seeds", name);
+    // null, whole-image and alias checks
+    const float* eps2 = guided ? L.eps_u : clf ? L.grad : nullptr;
+    SISIC_REQUIRE(L.eps && L.x && L.out && L.n > 0 && (L.source == STEP_EPS_PLAIN || eps2) && (!L.device_noise || L.seeds_dev) &&
+                  (!L.edit || (L.x0k && L.mask)), "%s: null tensor or empty", name);
+    SISIC_REQUIRE(!clf || (L.grad != L.out && L.eps != L.out), "%s: eps or the gradient aliases the output", name);
+    SISIC_REQUIRE(!hist || (L.hist && L.hist != L.x && L.hist != L.out && L.hist != L.eps && L.hist != eps2),
+                  "%s: the history is missing or aliases another tensor", name);
+    if (L.device_noise)
+        SISIC_REQUIRE(L.n_per_image > 0 && L.n_per_image <= NOISE_MAX_PER_IMAGE && L.n % L.n_per_image == 0,
+                      "%s: %lld elements are not whole images of %lld", name, (long long)L.n, (long long)L.n_per_image);
+    if (L.edit) {
+        SISIC_REQUIRE(L.hw > 0 && L.n_per_image % L.hw == 0, "%s: an image of %lld elements is not whole channels of %lld", name,
+                      (long long)L.n_per_image, (long long)L.hw);
+        SISIC_REQUIRE(L.x0k != L.out && L.mask != L.out && L.x0k != L.hist && L.mask != L.hist,
+                      "%s: the known image or the mask aliases an output", name);
+    }
+    StepArgs a{};
+    if (replayed) {
+        // (the tables were checked row by row before the loop's first launch: the kernel reads its row and cannot refuse it)
+        SISIC_REQUIRE(L.coef_dev && (L.device_noise || L.zrow_dev) && (!L.edit || L.erows_dev) && (L.source == STEP_EPS_PLAIN || L.w_tab),
+                      "%s: null table", name);
+    } else {
+        SISIC_REQUIRE(L.row && (!L.edit || L.erow), "%s: null row", name);
+        SISIC_TRY(check_step_row(L.rule, L.flags, L.row[0], L.row[1]));
+        for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(L.rule); ++k) a.row.v[k] = L.row[k];
+        for (int k = 0; L.edit && k < 4; ++k) {
+            SISIC_REQUIRE(std::isfinite(L.erow[k]), "%s: edit row {%g, %g, %g, %g}", name, L.erow[0], L.erow[1], L.erow[2], L.erow[3]);
+            a.er[k] = L.erow[k];
+        }
+    }
+    a.eps = L.eps; a.eps2 = eps2; a.x = L.x; a.out = L.out; a.hist = hist ? L.hist : nullptr;
+    a.z = L.z; a.seeds = L.seeds_dev; a.x0k = L.edit ? L.x0k : nullptr; a.mask = L.edit ? L.mask : nullptr;
+    a.st = static_cast<const LoopState*>(L.state); a.coef = L.coef_dev; a.zrow = L.zrow_dev; a.erows = L.erows_dev; a.wtab = L.w_tab;
+    a.n = L.n; a.npi = L.n_per_image; a.hw = L.hw; a.w = L.w; a.clip = L.clip; a.step = L.step;
+    // 4 bytes per element of every stream read or written (the mask is a channel's worth per image); a row on the device
+    // leaves out what only the row decides, and is never profiled (the replayed loop runs without the profiler)
+    const bool z_read = !replayed && L.z && L.row[4] != 0.0f, hist_read = !replayed && hist && L.row[5] != 0.0f;
+    double streams = (eps2 ? 2.0 : 1.0) + 1.0 + (guided ? 2.0 : 1.0) + (z_read ? 1.0 : 0.0) + (hist ? 1.0 : 0.0) + (hist_read ? 1.0 : 0.0);
+    if (L.edit) streams += 1.0 + (double)L.hw / (double)L.n_per_image;
+    ProfileScope prof(ctx, s, PK_DDPM, 4.0 * streams * (double)L.n, 0.0);
+    // one alignment rule: every pointer of the launch on a 16-byte line; whole float4s per image with generated noise, per
+    // channel with an edit, and per half when the result goes to both halves.  The scalar tail of the bodies takes n % 4.
+    uintptr_t al = 0;
+    for (const void* p : {(const void*)a.eps, (const void*)a.eps2, (const void*)a.x, (const void*)a.out, (const void*)a.hist,
+                          (const void*)a.z, (const void*)a.x0k, (const void*)a.mask})
+        al |= reinterpret_cast<uintptr_t>(p);
+    a.vec4 = (al & 15) == 0 && (!L.device_noise || (L.n_per_image & 3) == 0) && (!L.edit || (L.hw & 3) == 0) && (!guided || (L.n & 3) == 0);
+    const int64_t work = a.vec4 ? (L.n + 3) / 4 : L.n;
     const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
-    const LoopState* st = static_cast<const LoopState*>(state);
-#define SISIC_CLF(K) hipLaunchKernelGGL(K, grid, block, 0, s, eps, g, x, n, n_per_image, st, coef, seeds_dev, clf_tab, clip, vec4)
-    if (rule == STEP_RULE_DPMPP)
-        hipLaunchKernelGGL(dpm_step_clf_indexed_kernel, grid, block, 0, s, eps, g, x, hist, n, n_per_image, st, coef, seeds_dev, clf_tab, clip, vec4);
-    else if (rule == STEP_RULE_DDPM) SISIC_CLF((step_clf_indexed_kernel<DdpmRule<PRED_EPS>>));
-    else if (flags & STEP_FLAG_CLIPPED_OUTPUT) SISIC_CLF((step_clf_indexed_kernel<DdimRule<true, PRED_EPS>>));
-    else SISIC_CLF((step_clf_indexed_kernel<DdimRule<false, PRED_EPS>>));
-#undef SISIC_CLF
-    SISIC_HIP(hipGetLastError());
+    const int form = clf ? FORM_CLF : L.edit ? FORM_EDIT + (guided ? 1 : 0) : (guided ? FORM_GUIDED_BUFFER : FORM_BUFFER) + (L.device_noise ? 1 : 0);
+    const bool clipped = (L.flags & STEP_FLAG_CLIPPED_OUTPUT) != 0;
+    const int P = step_pred(L.flags);
+    const StepKernel kernel = P == PRED_SAMPLE ? step_kernel_of<PRED_SAMPLE>(L.rule, clipped, form)
+                              : P == PRED_V    ? step_kernel_of<PRED_V>(L.rule, clipped, form)
+                                               : step_kernel_of<PRED_EPS>(L.rule, clipped, form);
+    void* args[] = {&a};
+    SISIC_HIP(hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, 0, s));
     return SISIC_OK;
 }
 
@@ -994,126 +608,6 @@ int launch_clf_guide_eps(sisic_ctx* ctx, const float* eps, const float* g, float
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
-
-// ---- the edited steps (sisic_*_step_edit, sisic_sample_frames_edit) -------------------------------------------------------
-// rule x {plain, guided} with the inpainting epilogue, generated noise only.  One kernel serves the eager and the replayed
-// form: with st set, the rule's row, the edit row and the step index are read by the loop's step (and w from cond[0]);
-// otherwise they are the launch's own.
-struct EditStepArgs {
-    const float* ec;                    // eps [n]; guided: the conditional half
-    const float* eu;                    // guided: the null-label half
-    const float* cond;                  // guided, replayed: LoopCond (w at cond[0])
-    const float* x;
-    float* out;                         // may be x; guided: [2n]
-    float* hist;                        // DPM-Solver++
-    const float* x0k;
-    const float* mask;
-    const uint64_t* seeds;
-    const LoopState* st;                // replayed form, or nullptr
-    const float* coef;                  // replayed form: the rule's rows ...
-    const float* erows;                 // ... and the edit rows {ck, sk, ja, jb}
-    int64_t n, npi, hw;
-    StepRow row;
-    float er[4];
-    float w, clip;
-    uint32_t step;
-    int vec4;
-};
-
-template <int WIDTH>
-__device__ __forceinline__ void edit_step_rows(const EditStepArgs& a, StepRow& row, float (&er)[4], uint32_t& step, float& w) {
-    row = a.row;
-    for (int k = 0; k < 4; ++k) er[k] = a.er[k];
-    step = a.step;
-    w = a.w;
-    if (a.st) {
-        const int i = a.st->step;
-        step = (uint32_t)(a.st->step_base + i);
-        for (int k = 0; k < WIDTH; ++k) row.v[k] = a.coef[WIDTH * i + k];
-        for (int k = 0; k < 4; ++k) er[k] = a.erows[4 * i + k];
-        if (a.cond) w = a.cond[0];
-    }
-}
-
-template <class R, bool GUIDED>
-__global__ void __launch_bounds__(256)
-step_edit_kernel(const EditStepArgs a) {
-    StepRow row; float er[4], w; uint32_t step;
-    edit_step_rows<5>(a, row, er, step, w);
-    const PhiloxNoise zs{a.seeds, a.npi, step};
-    const InpaintEdit ed{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
-    if constexpr (GUIDED) step_body(GuidedEps{a.ec, a.eu, w}, a.x, a.out, a.n, a.vec4 != 0, row_rule<R>(row, a.clip), zs, ed);
-    else step_body(PlainEps{a.ec}, a.x, a.out, a.n, a.vec4 != 0, row_rule<R>(row, a.clip), zs, ed);
-}
-
-template <bool GUIDED, int P>
-__global__ void __launch_bounds__(256)
-dpm_step_edit_kernel(const EditStepArgs a) {
-    StepRow row; float er[4], w; uint32_t step;
-    edit_step_rows<6>(a, row, er, step, w);
-    const PhiloxNoise zs{a.seeds, a.npi, step};
-    const InpaintEdit ed{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
-    const DpmRule<P> rule{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip};
-    if constexpr (GUIDED) dpm_step_body(GuidedEps{a.ec, a.eu, w}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
-    else dpm_step_body(PlainEps{a.ec}, a.x, a.hist, a.out, a.n, a.vec4 != 0, rule, zs, ed);
-}
-
-// One launcher for every edited step.  eps_u: a guided step (out is then [2n]).  state/coef_dev/erows_dev: the replayed form
-// (row, erow, step and w unused; cond holds w when guided); otherwise row [rule's width] and erow [4] are host rows.
-int launch_step_edit(sisic_ctx* ctx, int rule, int flags, const float* eps, const float* eps_u, float w, const float* cond,
-                     const float* x, float* hist, float* out, int64_t n, int64_t n_per_image, int64_t hw,
-                     const uint64_t* seeds_dev, uint32_t step, const float* row, const float* erow, const void* state,
-                     const float* coef_dev, const float* erows_dev, const float* x0k, const float* mask, float clip,
-                     hipStream_t s) {
-    SISIC_TRY(check_rule(rule, flags));
-    const char* name = rule_name(rule);
-    SISIC_REQUIRE(eps && x && out && seeds_dev && x0k && mask && n > 0, "%s_edit: null tensor or empty", name);
-    SISIC_REQUIRE(rule != STEP_RULE_DPMPP || (hist && hist != x && hist != out && hist != eps && hist != eps_u),
-                  "dpmpp_step_edit: the history is missing or aliases another tensor");
-    SISIC_REQUIRE(n_per_image > 0 && n_per_image <= NOISE_MAX_PER_IMAGE && n % n_per_image == 0,
-                  "%s_edit: %lld elements are not whole images of %lld", name, (long long)n, (long long)n_per_image);
-    SISIC_REQUIRE(hw > 0 && n_per_image % hw == 0, "%s_edit: an image of %lld elements is not whole channels of %lld", name,
-                  (long long)n_per_image, (long long)hw);
-    SISIC_REQUIRE(x0k != out && mask != out && x0k != hist && mask != hist, "%s_edit: the known image or the mask aliases an output", name);
-    EditStepArgs a{};
-    if (state) {
-        SISIC_REQUIRE(coef_dev && erows_dev && (!eps_u || cond), "%s_edit (indexed): null table", name);
-    } else {
-        SISIC_REQUIRE(row && erow, "%s_edit: null row", name);
-        SISIC_TRY(check_step_row(rule, flags, row[0], row[1]));
-        for (int k = 0; k < (int)SISIC_RULE_ROW_WIDTH(rule); ++k) a.row.v[k] = row[k];
-        for (int k = 0; k < 4; ++k) {
-            SISIC_REQUIRE(std::isfinite(erow[k]), "%s_edit: edit row {%g, %g, %g, %g}", name, erow[0], erow[1], erow[2], erow[3]);
-            a.er[k] = erow[k];
-        }
-    }
-    ProfileScope prof(ctx, s, PK_DDPM, (eps_u ? 32.0 : 20.0) * (double)n, 0.0);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(x) |
-                         reinterpret_cast<uintptr_t>(hist) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x0k) |
-                         reinterpret_cast<uintptr_t>(mask);
-    a.ec = eps; a.eu = eps_u; a.cond = state ? cond : nullptr; a.x = x; a.out = out; a.hist = hist; a.x0k = x0k; a.mask = mask;
-    a.seeds = seeds_dev; a.st = static_cast<const LoopState*>(state); a.coef = coef_dev; a.erows = erows_dev;
-    a.n = n; a.npi = n_per_image; a.hw = hw; a.w = w; a.clip = clip; a.step = step;
-    a.vec4 = (al & 15) == 0 && (n_per_image & 3) == 0 && (hw & 3) == 0;
-    const int64_t work = a.vec4 ? n / 4 : n;
-    const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
-#define SISIC_EDIT(K) hipLaunchKernelGGL(K, grid, block, 0, s, a)
-    SISIC_PRED_SWITCH(flags,
-        if (rule == STEP_RULE_DPMPP) {
-            if (eps_u) SISIC_EDIT((dpm_step_edit_kernel<true, P>)); else SISIC_EDIT((dpm_step_edit_kernel<false, P>));
-        } else if (rule == STEP_RULE_DDPM) {
-            if (eps_u) SISIC_EDIT((step_edit_kernel<DdpmRule<P>, true>)); else SISIC_EDIT((step_edit_kernel<DdpmRule<P>, false>));
-        } else if (flags & STEP_FLAG_CLIPPED_OUTPUT) {
-            if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<true, P>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<true, P>, false>));
-        } else {
-            if (eps_u) SISIC_EDIT((step_edit_kernel<DdimRule<false, P>, true>)); else SISIC_EDIT((step_edit_kernel<DdimRule<false, P>, false>));
-        })
-#undef SISIC_EDIT
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-#undef SISIC_PRED_SWITCH
 
 // the combine alone (sisic_guide_eps): guide_one() on every element, any alignment; out may be either input
 __global__ void __launch_bounds__(256)

@@ -886,63 +886,103 @@ struct ClfCall {
     float scale;
 };
 
+// One call of the sampling loop as its public entry point describes it (sisic.h): what every form of the loop is given.
+struct LoopCall {
+    float* x = nullptr;
+    int B = 0, H = 0, W = 0, T = 0;
+    const int64_t* timesteps = nullptr;
+    const float* coef = nullptr;
+    float clip = 0.0f;
+    int rule = SISIC_RULE_DDPM, rule_flags = 0;     // (sample_frames adds the handle's prediction type to the flags)
+    const float* noise = nullptr;                   // the noise buffer of sisic_sample_frames[_rule], or
+    const uint64_t* seeds = nullptr;                // HOST uint64 [B]: the step generates its noise, step index step0 + i
+    int step0 = 0;
+    const int64_t* labels = nullptr;                // sisic_sample_frames_cond: host int64 [B], with null_label and the scale w
+    int null_label = 0;
+    float w = 1.0f;
+    const EditCall* ed = nullptr;
+    const ClfCall* cl = nullptr;
+    float* traj = nullptr;
+    const int* traj_row = nullptr;
+    uint8_t* out_u8 = nullptr;
+    const volatile int* cancel = nullptr;
+    int* steps_done = nullptr;
+    void* stream = nullptr;
+    const CondCall* cg = nullptr;                   // set by sample_frames for a conditional call
+};
+
+// The step launch of a call (common.h StepLaunch) on the latent x.  i >= 0: the eager form of step i, with its host row, its
+// step index, w and its noise row z.  i < 0: the replayed form, which reads all of these by the loop's step from the device
+// tables (and the library's copies of an edited call's image, mask and rows: a captured step serves every edited call at the
+// shape).
+static StepLaunch loop_step_launch(const sisic_unet* u, const LoopCall& c, float* x, size_t n, int i, const float* z) {
+    const bool guided = c.cg && c.cg->guided;
+    StepLaunch L;
+    L.rule = c.rule; L.flags = c.rule_flags; L.clip = c.clip;
+    L.source = c.cl ? STEP_EPS_CLASSIFIER : guided ? STEP_EPS_GUIDED : STEP_EPS_PLAIN;
+    L.eps = u->eps_buf;
+    if (guided) L.eps_u = u->eps_buf + n;
+    if (c.cl) L.grad = u->clf_grad;
+    L.x = x; L.out = x; L.n = (int64_t)n;
+    if (c.rule == STEP_RULE_DPMPP) L.hist = u->hist_buf;
+    L.device_noise = c.seeds != nullptr;
+    if (c.seeds) L.seeds_dev = reinterpret_cast<const uint64_t*>(u->seeds_dev);
+    L.n_per_image = (int64_t)(n / c.B);
+    L.edit = c.ed != nullptr;
+    L.hw = (int64_t)c.H * c.W;
+    if (i >= 0) {
+        L.row = c.coef + (size_t)i * SISIC_RULE_ROW_WIDTH(c.rule);
+        L.z = z;
+        L.step = (uint32_t)(c.step0 + i);
+        L.w = c.cl ? c.cl->scale : guided ? c.cg->w : 1.0f;
+        if (c.ed) { L.x0k = c.ed->x0k; L.mask = c.ed->mask; L.erow = c.ed->rows + 4 * (size_t)i; }
+    } else {
+        L.state = u->loop_tables;
+        L.coef_dev = u->loop_tables + 4;
+        L.zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
+        L.w_tab = c.cl ? u->clf_tables : guided ? u->cond_tables : nullptr;
+        if (c.ed) { L.x0k = u->edit_x0k; L.mask = u->edit_mask; L.erows_dev = u->edit_rows; }
+    }
+    return L;
+}
+
 // One denoising step with every per-step parameter selected on the device (elementwise.hip, LoopState): identical
-// launches for every step, so that a captured step can be replayed.  cg: a conditional call, or nullptr; cl: a
-// classifier-guided call (the classifier's gradient walk between the UNet pass and the step kernel), or nullptr.
-static int loop_step(sisic_unet* u, int B, int H, int W, size_t n, float clip, int rule, int rule_flags, bool rng,
-                     const CondCall* cg, bool edit, const ClfCall* cl, hipStream_t s) {
+// launches for every step, so that a captured step can be replayed.  A classifier-guided call runs the classifier's gradient
+// walk between the UNet pass and the step kernel.
+static int loop_step(sisic_unet* u, const LoopCall& c, size_t n, hipStream_t s) {
     void* state = u->loop_tables;
-    const float* coef_dev = u->loop_tables + 4;
-    const int* zrow_dev = reinterpret_cast<const int*>(u->loop_tables + 4 + LOOP_COEF_FLOATS);
-    const uint64_t* seeds = reinterpret_cast<const uint64_t*>(u->seeds_dev);
-    if (cg) {
-        SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, state, 0, u->cond_tables, cg->rows, u->tproj_cur, s));
-        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, u->tproj_R, u->eps_buf, cg->rows, H, W, s));
+    if (c.cg) {
+        SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, state, 0, u->cond_tables, c.cg->rows, u->tproj_cur, s));
+        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, u->tproj_R, u->eps_buf, c.cg->rows, c.H, c.W, s));
     } else {
         SISIC_TRY(launch_loop_select_row(u->ctx, u->tproj, u->tproj_R, state, u->tproj_cur, s));
-        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, B, H, W, s));
+        SISIC_TRY(unet_run_forward(u, u->x_work, u->tproj_cur, 0, u->eps_buf, c.B, c.H, c.W, s));
     }
-    if (cl) {
-        // the walk on the loop's latent, on the loop's stream, behind the UNet pass; targets and scale from the loop's table
-        SISIC_TRY(resnet_input_gradient_walk(cl->clf, u->x_work, B, H, W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
-                                             u->clf_grad, nullptr, s));
-        SISIC_TRY(launch_step_clf_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->clf_grad, u->x_work,
-                                          rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, (int64_t)n, (int64_t)(n / B), state, coef_dev,
-                                          seeds, u->clf_tables, clip, s));
-    } else if (edit) {
-        // (the library's copies of the call's image, mask and rows: a captured step serves every edited call at the shape)
-        const bool guided = cg && cg->guided;
-        SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, 1.0f,
-                                   guided ? u->cond_tables : nullptr,
-                                   u->x_work, rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, u->x_work, (int64_t)n,
-                                   (int64_t)(n / B), (int64_t)H * W, seeds, 0u, nullptr, nullptr, state, coef_dev, u->edit_rows,
-                                   u->edit_x0k, u->edit_mask, clip, s));
-    } else if (cg && cg->guided)
-        SISIC_TRY(launch_step_guided_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work,
-                                             rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, (int64_t)n, (int64_t)(n / B), state,
-                                             coef_dev, zrow_dev, rng ? seeds : nullptr, u->cond_tables, clip, s));
-    else if (rule == STEP_RULE_DPMPP && rng)
-        SISIC_TRY(launch_dpm_step_indexed_rng(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, (int64_t)(n / B), state,
-                                              coef_dev, seeds, clip, s, rule_flags));
-    else if (rule == STEP_RULE_DPMPP)
-        SISIC_TRY(launch_dpm_step_indexed(u->ctx, u->eps_buf, u->x_work, u->hist_buf, (int64_t)n, state, coef_dev, zrow_dev,
-                                          clip, s, rule_flags));
-    else if (rng)
-        SISIC_TRY(launch_step_indexed_rng(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, (int64_t)(n / B), state,
-                                          coef_dev, seeds, clip, s));
-    else
-        SISIC_TRY(launch_step_indexed(u->ctx, rule, rule_flags, u->eps_buf, u->x_work, (int64_t)n, state, coef_dev, zrow_dev,
-                                      clip, s));
+    // the walk on the loop's latent, on the loop's stream, behind the UNet pass; targets and scale from the loop's table
+    if (c.cl)
+        SISIC_TRY(resnet_input_gradient_walk(c.cl->clf, u->x_work, c.B, c.H, c.W, 0,
+                                             reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD), u->clf_grad, nullptr, s));
+    SISIC_TRY(launch_step(u->ctx, loop_step_launch(u, c, u->x_work, n, -1, nullptr), s));
     return launch_loop_advance(u->ctx, state, s);
 }
 
 // The loop as ONE captured step replayed T-1 times (hipGraph): at batch 1 a step is ~190 launches of 5-20 us kernels and
 // the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
-// rng: the step generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
-static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, const float* coef, float clip, int rule,
-                        int rule_flags, const float* noise, bool rng, int step0, const CondCall* cg, const EditCall* ed,
-                        const ClfCall* cl, float* traj, const int* traj_row, const volatile int* cancel, int* steps_done,
-                        hipStream_t caller) {
+// A call with seeds generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
+static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
+    float* const x = c.x;
+    const int B = c.B, H = c.H, W = c.W, T = c.T, rule = c.rule, rule_flags = c.rule_flags, step0 = c.step0;
+    const float* const coef = c.coef;
+    const float* const noise = c.noise;
+    const float clip = c.clip;
+    const bool rng = c.seeds != nullptr;
+    const CondCall* const cg = c.cg;
+    const EditCall* const ed = c.ed;
+    const ClfCall* const cl = c.cl;
+    float* const traj = c.traj;
+    const int* const traj_row = c.traj_row;
+    const volatile int* const cancel = c.cancel;
+    int* const steps_done = c.steps_done;
     const int C = u->cfg.in_channels;
     const size_t n = (size_t)B * C * H * W;
     const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
@@ -1031,7 +1071,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
         // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
         // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
         // the time of a replayed one at batch 1.)
-        rc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, cl, s);
+        rc = loop_step(u, c, n, s);
         if (rc == SISIC_OK) rc = after_step(0);
         i = 1;
     }
@@ -1041,7 +1081,7 @@ static int sample_graph(sisic_unet* u, float* x, int B, int H, int W, int T, con
             const void* ptrs[12] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            const int crc = loop_step(u, B, H, W, n, clip, rule, rule_flags, rng, cg, edit, cl, s);
+            const int crc = loop_step(u, c, n, s);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (crc != SISIC_OK || e != hipSuccess || !g) {
@@ -1085,22 +1125,37 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
 // The loop behind sisic_sample_frames[_rule] (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames[_rule]_rng (seeds:
 // HOST uint64 [B], noise NULL): the two differ in where the scheduler step takes z from, nothing else.  rule, rule_flags: the
 // step rule whose rows coef holds (SISIC_RULE_*).  labels: sisic_sample_frames_cond (host int64 [B], with null_label and the
-// guidance scale w), or nullptr for an unconditional handle.
-static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
-                         float clip, int rule, int rule_flags, const float* noise, const uint64_t* seeds, int step0,
-                         const int64_t* labels, int null_label, float w, const EditCall* ed, float* traj, const int* traj_row,
-                         uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream, const ClfCall* cl = nullptr) {
+// guidance scale w), or nullptr for an unconditional handle.  (c: this function's own copy, which gains the prediction type in
+// its flags and the conditional call's rows.)
+static int sample_frames(sisic_unet* u, LoopCall c) {
+    float* const x = c.x;
+    const int B = c.B, H = c.H, W = c.W, T = c.T, rule = c.rule, step0 = c.step0, null_label = c.null_label;
+    int rule_flags = c.rule_flags;
+    const int64_t* const timesteps = c.timesteps;
+    const int64_t* const labels = c.labels;
+    const float* const coef = c.coef;
+    const float* const noise = c.noise;
+    const uint64_t* const seeds = c.seeds;
+    const float clip = c.clip, w = c.w;
+    const EditCall* const ed = c.ed;
+    const ClfCall* const cl = c.cl;
+    float* const traj = c.traj;
+    const int* const traj_row = c.traj_row;
+    uint8_t* const out_u8 = c.out_u8;
+    const volatile int* const cancel = c.cancel;
+    int* const steps_done = c.steps_done;
     SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
     // a caller's flags are the rule's own; from here on rule_flags also carries the handle's prediction type in its private
     // bits, down to the launchers and into the key of a captured step
     SISIC_REQUIRE((rule_flags & ~SISIC_RULE_FLAG_CLIPPED_OUTPUT) == 0, "sample: rule flags %d (SISIC_RULE_FLAG_CLIPPED_OUTPUT or 0)",
                   rule_flags);
     rule_flags |= step_pred_flags(u->pred_type);
+    c.rule_flags = rule_flags;
     SISIC_TRY(unet_check_labels(u, labels ? "sample_cond" : "sample", labels != nullptr, labels, B));
     SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
     if (traj_row)
         for (int i = 0; i < T; ++i) SISIC_REQUIRE(traj_row[i] >= -1, "sample: traj_row[%d] = %d (a row of traj, or -1)", i, traj_row[i]);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
     if (steps_done) *steps_done = 0;
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
@@ -1147,6 +1202,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
         for (int b = 0; b < B; ++b) slots[b] = slot_of(labels[b]);
         for (int b = B; b < cc.rows; ++b) slots[b] = slot_of(null_label);
         cg = &cc;
+        c.cg = cg;
     }
     const int rows = cg ? cg->rows : B;                          // samples per UNet pass
     const size_t L = cg ? distinct.size() : 1;                   // embedding rows per step
@@ -1207,7 +1263,7 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, x, B, H, W, T, coef, clip, rule, rule_flags, noise, rng, step0, cg, ed, cl, traj, traj_row, cancel, steps_done, s);
+        const int rc = sample_graph(u, c, s);
         if (rc != SISIC_OK) return rc;
         if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
         return SISIC_OK;
@@ -1224,7 +1280,6 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
         SISIC_HIP(hipMemcpyAsync(xe + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (cg) SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)rows * u->tproj_R));
-    const uint64_t* seeds_dev = reinterpret_cast<const uint64_t*>(u->seeds_dev);
     size_t zi = 0;
     auto steps = [&]() -> int {
         for (int i = 0; i < T; ++i) {
@@ -1242,35 +1297,13 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
             } else {
                 SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
             }
-            const float* c = coef + (size_t)i * cw;
             const float* z = nullptr;
-            if (noise && c[4] != 0.0f) z = noise + (zi++) * n;
-            if (cl) {
+            if (noise && coef[(size_t)i * cw + 4] != 0.0f) z = noise + (zi++) * n;
+            if (cl)
                 SISIC_TRY(resnet_input_gradient_walk(cl->clf, x, B, H, W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
                                                      u->clf_grad, nullptr, s));
-                SISIC_TRY(launch_step_clf(u->ctx, rule, rule_flags, u->eps_buf, u->clf_grad, cl->scale, x, seeds_dev, (int64_t)(n / B),
-                                          (uint32_t)(step0 + i), rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, x, (int64_t)n, c, clip, s));
-            } else if (ed)
-                SISIC_TRY(launch_step_edit(u->ctx, rule, rule_flags, u->eps_buf, guided ? u->eps_buf + n : nullptr, guided ? cg->w : 1.0f,
-                                           nullptr, xe, rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, xe, (int64_t)n, (int64_t)(n / B),
-                                           (int64_t)H * W, seeds_dev, (uint32_t)(step0 + i), c, ed->rows + 4 * (size_t)i, nullptr,
-                                           nullptr, nullptr, ed->x0k, ed->mask, clip, s));
-            else if (guided)
-                SISIC_TRY(launch_step_guided(u->ctx, rule, rule_flags, u->eps_buf, u->eps_buf + n, cg->w, xe, z, rng ? seeds_dev : nullptr,
-                                             (int64_t)(n / B), (uint32_t)(step0 + i), rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr,
-                                             xe, (int64_t)n, c, clip, s));
-            else if (rule == STEP_RULE_DPMPP && rng)
-                SISIC_TRY(launch_dpm_step_rng(u->ctx, u->eps_buf, x, u->hist_buf, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
-                                              (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], c[5], clip, s, rule_flags));
-            else if (rule == STEP_RULE_DPMPP)
-                SISIC_TRY(launch_dpm_step(u->ctx, u->eps_buf, x, z, u->hist_buf, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], c[5],
-                                          clip, s, rule_flags));
-            else if (rng)
-                SISIC_TRY(launch_step_rng(u->ctx, rule, rule_flags, u->eps_buf, x, x, (int64_t)n, (int64_t)(n / B), seeds_dev,
-                                          (uint32_t)(step0 + i), c[0], c[1], c[2], c[3], c[4], clip, s));
-            else
-                SISIC_TRY(launch_step(u->ctx, rule, rule_flags, u->eps_buf, x, z, x, (int64_t)n, c[0], c[1], c[2], c[3], c[4], clip,
-                                      s));
+            // (xe is x unless the call is guided)
+            SISIC_TRY(launch_step(u->ctx, loop_step_launch(u, c, xe, n, i, z), s));
             const int row = traj_row ? traj_row[i] : i;
             if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, xe, n * sizeof(float), hipMemcpyDeviceToDevice, s));
             if (steps_done) *steps_done = i + 1;
@@ -1289,8 +1322,12 @@ static int sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, co
 int sisic_sample_frames_rule(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                              float clip, int rule, int rule_flags, const float* noise, float* traj, const int* traj_row,
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, nullptr, 0, nullptr, 0, 1.0f, nullptr, traj,
-                         traj_row, out_u8, cancel, steps_done, stream);
+    LoopCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
+    c.rule = rule; c.rule_flags = rule_flags;
+    c.noise = noise;
+    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
+    return sample_frames(u, c);
 }
 
 int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps,
@@ -1298,8 +1335,12 @@ int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, i
                                  float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
                                  void* stream) {
     SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, nullptr, 0, 1.0f, nullptr, traj,
-                         traj_row, out_u8, cancel, steps_done, stream);
+    LoopCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
+    c.rule = rule; c.rule_flags = rule_flags;
+    c.seeds = seeds; c.step0 = step0;
+    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
+    return sample_frames(u, c);
 }
 
 int sisic_sample_frames_cond(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
@@ -1308,8 +1349,13 @@ int sisic_sample_frames_cond(sisic_unet* u, float* x, int B, int H, int W, int T
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && class_labels, "sample_cond: null argument");
     SISIC_REQUIRE(!(seeds && noise), "sample_cond: a noise buffer and seeds (host noise takes seeds NULL, device noise takes noise NULL)");
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, noise, seeds, step0, class_labels, null_label,
-                         guidance_scale, nullptr, traj, traj_row, out_u8, cancel, steps_done, stream);
+    LoopCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
+    c.rule = rule; c.rule_flags = rule_flags;
+    c.noise = noise; c.seeds = seeds; c.step0 = step0;
+    c.labels = class_labels; c.null_label = null_label; c.w = guidance_scale;
+    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
+    return sample_frames(u, c);
 }
 
 int sisic_sample_frames_edit(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
@@ -1321,8 +1367,14 @@ int sisic_sample_frames_edit(sisic_unet* u, float* x, int B, int H, int W, int T
                   "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
     SISIC_REQUIRE(x0k != x && mask != x, "sample_edit: the known image or the mask is the latent buffer");
     const EditCall ed{x0k, mask, edit_rows};
-    return sample_frames(u, x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, nullptr, seeds, step0, class_labels, null_label,
-                         guidance_scale, &ed, traj, traj_row, out_u8, cancel, steps_done, stream);
+    LoopCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
+    c.rule = rule; c.rule_flags = rule_flags;
+    c.seeds = seeds; c.step0 = step0;
+    c.labels = class_labels; c.null_label = null_label; c.w = guidance_scale;
+    c.ed = &ed;
+    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
+    return sample_frames(u, c);
 }
 
 int sisic_guide_eps(sisic_ctx* ctx, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, void* stream) {
@@ -1357,9 +1409,14 @@ int sisic_sample_frames_clf(sisic_unet* u, sisic_sample_clf_args* a) {
     SISIC_REQUIRE(std::isfinite(a->scale), "sample_clf: classifier scale %g", (double)a->scale);
     SISIC_REQUIRE(u->cfg.in_channels == 3, "sample_clf: the classifier reads 3-channel images, the model has %d", u->cfg.in_channels);
     const ClfCall cl{a->classifier, a->targets, a->scale};
-    return sample_frames(u, a->x, a->B, a->H, a->W, a->T, a->timesteps, a->coef, a->clip, a->rule, a->rule_flags, nullptr, a->seeds,
-                         a->step0, nullptr, 0, 1.0f, nullptr, a->traj, a->traj_row, a->out_u8, a->cancel, &a->steps_done, a->stream,
-                         &cl);
+    LoopCall c;
+    c.x = a->x; c.B = a->B; c.H = a->H; c.W = a->W; c.T = a->T; c.timesteps = a->timesteps; c.coef = a->coef; c.clip = a->clip;
+    c.rule = a->rule; c.rule_flags = a->rule_flags;
+    c.seeds = a->seeds; c.step0 = a->step0;
+    c.cl = &cl;
+    c.traj = a->traj; c.traj_row = a->traj_row; c.out_u8 = a->out_u8; c.cancel = a->cancel; c.steps_done = &a->steps_done;
+    c.stream = a->stream;
+    return sample_frames(u, c);
 }
 
 int sisic_sample_frames(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
