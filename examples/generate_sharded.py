@@ -47,6 +47,11 @@ def main():
     ap.add_argument("--solver-order", type=int, choices=(1, 2), default=2, help="dpmsolver++ only: 1 is the DDIM rule")
     ap.add_argument("--algorithm-type", choices=("dpmsolver++", "sde-dpmsolver++"), default="dpmsolver++",
                     help="dpmsolver++ only: the ODE solver (draws nothing beyond x_T) or its stochastic variant")
+    ap.add_argument("--thresholding", action="store_true",
+                    help="dynamic thresholding of x0 (Imagen): per image, clamp to the --dynamic-thresholding-ratio quantile of "
+                         "|x0| (at least 1, at most --sample-max-value) and divide by it, in place of the static clamp")
+    ap.add_argument("--dynamic-thresholding-ratio", type=float, default=0.995)
+    ap.add_argument("--sample-max-value", type=float, default=1.0)
     a = ap.parse_args()
 
     rank, world, local = sdist.init_from_env()
@@ -63,7 +68,9 @@ def main():
     for i in range(0, len(mine), a.batch):
         blocks.append(s.generate_seeds(a.class_name, mine[i:i + a.batch], a.T, (a.size, a.size), noise=a.noise,
                                        scheduler=a.scheduler, eta=a.eta, solver_order=a.solver_order,
-                                       algorithm_type=a.algorithm_type).images)
+                                       algorithm_type=a.algorithm_type, thresholding=a.thresholding,
+                                       dynamic_thresholding_ratio=a.dynamic_thresholding_ratio,
+                                       sample_max_value=a.sample_max_value).images)
     local_images = torch.cat(blocks) if blocks else torch.empty((0, a.size, a.size, 3), dtype=torch.uint8, device=dev)
     images = sdist.gather_images(local_images, a.count, dst=0)
     torch.cuda.synchronize(dev)
@@ -73,6 +80,8 @@ def main():
         rule = f", ddim eta={a.eta:g}" if a.scheduler == "ddim" else ""
         if a.scheduler == "dpmsolver++":
             rule = f", {a.algorithm_type} order {a.solver_order}"
+        if a.thresholding:
+            rule += f", thresholding {a.dynamic_thresholding_ratio:g} max {a.sample_max_value:g}"
         print(f"{a.count} images {a.size}x{a.size}, T={a.T}, {world} GPU(s), {a.noise} noise{rule}: {dt:.2f} s -> {a.count / dt:.3f} images/sec; "
               f"sha256 {hashlib.sha256(arr.tobytes()).hexdigest()[:16]}", flush=True)
         if a.out:

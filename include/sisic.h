@@ -527,6 +527,55 @@ typedef struct sisic_sample_clf_args {
 } sisic_sample_clf_args;                   /* 136 bytes, no padding */
 int sisic_sample_frames_clf(sisic_unet*, sisic_sample_clf_args* args);
 
+/* ---- dynamic thresholding of x0 (Saharia et al. 2022, Imagen section 2.3) ------------------------------
+ * The published schedulers' `thresholding`: per image, a high percentile s of |x0| replaces the static clamp range, and x0 is
+ * divided by it.  For image b, with x0 the rule's estimate BEFORE any clamp (from the step's eps as the rule sees it: after
+ * the guidance combine, under the prediction type), n = n_per_image and a_0 <= ... <= a_{n-1} the image's |x0| in order:
+ *     r = fl32(fl32(ratio) * fl32(n - 1));   lo = floor(r);   hi = ceil(r);   w = fl32(r - lo);   d = fl32(a_hi - a_lo)
+ *     q = w < 0.5 ? fma(w, d, a_lo) : fma(fl32(w - 1), d, a_hi)            ONE rounding: a fused multiply-add
+ *     s = min(max(q, 1), sample_max_value);      x0' = min(max(x0, -s), s) / s
+ * which is _threshold_sample with torch.quantile(abs, ratio, dim=1) spelled out, bit for bit.  A NaN anywhere in an image
+ * gives s = NaN and a NaN image; infinities follow the formula.  Thresholding takes precedence over `clip` (the published
+ * `if thresholding ... elif clip_sample`): the clip argument of a thresholded step is not read.  sample_max_value = 1 makes
+ * s exactly 1: the bits of clip = 1.  DDIM's use_clipped_model_output re-derives its epsilon from x0'; DPM-Solver++ stores x0'
+ * in its history.  s is exact selection by integer counting (radix select on the bit patterns of |x0|, one workgroup per
+ * image), so two calls give equal bits; it is one more launch ahead of the step kernel on the step's stream.
+ *
+ * Two owners, as the prediction type has, both set through stream-less setters:
+ *   the CONTEXT's setting is read by the nine single-step entries.  The _rng and _edit entries know their images; the three
+ *     buffer-noise entries take n_per_image from sisic_set_step_image_elems (0, the default: refused while thresholding is on).
+ *     s lies in a buffer the context owns per stream, grown (freed and allocated again, behind a synchronise of that stream) when a
+ *     call brings more images than any before it on the stream: a caller who captures a thresholded single step into a graph of
+ *     their own holds that address, and must capture again after a call with a larger batch on the same stream.
+ *   the HANDLE's setting is read by every sisic_sample* loop of the handle, eager and graph-replayed, latency mode included.
+ *     s [B] (B, not 2B, in a guided call) is owned by the handle.  The setting is part of what a captured step is: on -> off ->
+ *     on re-captures, and never replays the other chain.
+ * ratio = 0 switches thresholding off (the default).  SISIC_EINVAL, with the previous setting left in force: ratio outside
+ * [0, 1] or not finite; sample_max_value below 1 or not finite.  A thresholded launch with n_per_image above 2^24 is
+ * SISIC_EINVAL (n - 1 must be exact in fp32).
+ *
+ * sisic_x0_threshold: the selection alone, s [B] for images of n_per_image elements, under the context's prediction type.
+ * source 0: eps as it stands; 1: classifier-free guidance, eps2 the null-label half and w the scale (eps2 + w * (eps - eps2));
+ * 2: classifier guidance, eps2 the gradient g and w the scale (eps - (w * sb) * g; epsilon prediction only).  ratio may be 0
+ * here (the image's smallest |x0|).  Any alignment.  s may alias none of eps, eps2 and x (SISIC_EINVAL), and in a thresholded step
+ * none of the step's outputs.  A refused call has launched nothing.                                                                         */
+int sisic_set_step_thresholding(sisic_ctx*, float ratio, float sample_max_value);
+int sisic_set_step_image_elems(sisic_ctx*, int64_t n_per_image);
+int sisic_unet_set_thresholding(sisic_unet*, float ratio, float sample_max_value);
+typedef struct sisic_x0_threshold_args {
+    const float* eps;
+    const float* eps2;                     /* source 1, 2; else NULL */
+    const float* x;
+    float*       s;                        /* out: [B] */
+    void*        stream;
+    int64_t      n_per_image;
+    int          B, source;
+    float        sb, sa, w;
+    float        ratio, sample_max_value;
+    float        reserved;                 /* 0 */
+} sisic_x0_threshold_args;                 /* 80 bytes, no padding */
+int sisic_x0_threshold(sisic_ctx*, sisic_x0_threshold_args* args);
+
 /* ---- image editing: the inpainting epilogue of the step kernels (RePaint, Lugmayr et al. 2022) -------
  * sisic_{ddpm,ddim,dpmpp}_step_rng with an epilogue applied to the rule's result u in the register that holds it, before the
  * store (no second pass over the latent).  Per element, one fp32 rounding per operation, no FMA contraction, in this order:

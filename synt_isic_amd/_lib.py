@@ -115,6 +115,13 @@ class ResnetTargetsArgs(C.Structure):
                 ("stream", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("reserved", C.c_int)]
 
 
+class X0ThresholdArgs(C.Structure):
+    """struct sisic_x0_threshold_args (80 bytes, no padding)"""
+    _fields_ = [("eps", C.c_void_p), ("eps2", C.c_void_p), ("x", C.c_void_p), ("s", C.c_void_p), ("stream", C.c_void_p),
+                ("n_per_image", C.c_int64), ("B", C.c_int), ("source", C.c_int), ("sb", C.c_float), ("sa", C.c_float),
+                ("w", C.c_float), ("ratio", C.c_float), ("sample_max_value", C.c_float), ("reserved", C.c_float)]
+
+
 class ClfGuideArgs(C.Structure):
     """struct sisic_clf_guide_args (48 bytes, no padding)"""
     _fields_ = [("eps", C.c_void_p), ("g", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p), ("n", C.c_int64),
@@ -303,6 +310,10 @@ SIGNATURES = {
     "sisic_unet_prediction_type": (C.c_int, [C.c_void_p]),
     "sisic_unet_set_loss_weights": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
     "sisic_set_step_prediction_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sisic_set_step_thresholding": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "sisic_set_step_image_elems": (C.c_int, [C.c_void_p, C.c_int64]),
+    "sisic_unet_set_thresholding": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "sisic_x0_threshold": (C.c_int, [C.c_void_p, C.POINTER(X0ThresholdArgs)]),
     "sisic_step_prediction_type": (C.c_int, [C.c_void_p]),
     "sisic_mse_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),

@@ -111,6 +111,8 @@ int sisic_destroy(sisic_ctx* ctx) {
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : ctx->bn_part)
         if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : ctx->thr_s)
+        if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& it : ctx->bf3_items) {
         if (it.fill_done) (void)hipEventDestroy(it.fill_done);
         if (it.tab) (void)hipFree(it.tab);
@@ -213,6 +215,21 @@ static void step_tensors(StepLaunch& L, const sisic_ctx* ctx, int rule, int use_
     L.eps = eps; L.x = x; L.hist = hist; L.out = out; L.n = n; L.row = row; L.clip = clip;
 }
 
+// launch_step under the context's thresholding setting (sisic_set_step_thresholding): off, the launch as it is; on, the images
+// are the entry's own (n_per_image) or the context's (sisic_set_step_image_elems), and s lies in the context's buffer of the stream
+static int step_launch(sisic_ctx* ctx, const char* what, StepLaunch& L, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ctx->step_thr_ratio > 0.0f) {
+        if (L.n_per_image <= 0) L.n_per_image = ctx->step_npi;
+        SISIC_REQUIRE(L.n_per_image > 0 && L.n > 0 && L.n % L.n_per_image == 0,
+                      "%s: thresholding is on and %lld elements are not whole images of %lld (sisic_set_step_image_elems)", what,
+                      (long long)L.n, (long long)L.n_per_image);
+        L.thr_ratio = ctx->step_thr_ratio; L.thr_max = ctx->step_thr_max;
+        SISIC_TRY(step_threshold_scratch(ctx, s, L.n / L.n_per_image, &L.thr_s));
+    }
+    return launch_step(ctx, L, s);
+}
+
 // the _rng entries: z generated in the kernel
 static int step_rng(sisic_ctx* ctx, const char* what, StepLaunch& L, int rule, int use_clipped_model_output, const float* eps,
                     const float* x, float* hist, float* out, int B, int64_t n_per_image, const uint64_t* seeds_dev, uint32_t step,
@@ -220,7 +237,7 @@ static int step_rng(sisic_ctx* ctx, const char* what, StepLaunch& L, int rule, i
     SISIC_REQUIRE(ctx && B > 0 && n_per_image > 0, "%s: null context or empty batch", what);
     step_tensors(L, ctx, rule, use_clipped_model_output, eps, x, hist, out, (int64_t)B * n_per_image, row, clip);
     L.device_noise = true; L.seeds_dev = seeds_dev; L.n_per_image = n_per_image; L.step = step;
-    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+    return step_launch(ctx, what, L, stream);
 }
 
 // the _edit entries: the _rng entries' arguments, the known image, the mask and the edit row
@@ -245,7 +262,7 @@ int sisic_ddpm_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
     StepLaunch L;
     step_tensors(L, ctx, STEP_RULE_DDPM, 0, eps, x, nullptr, out, n, row, clip);
     L.z = z;
-    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+    return step_launch(ctx, "step", L, stream);
 }
 
 int sisic_ddim_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* out, int64_t n,
@@ -256,7 +273,7 @@ int sisic_ddim_step(sisic_ctx* ctx, const float* eps, const float* x, const floa
     StepLaunch L;
     step_tensors(L, ctx, STEP_RULE_DDIM, use_clipped_model_output, eps, x, nullptr, out, n, row, clip);
     L.z = z;
-    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+    return step_launch(ctx, "step", L, stream);
 }
 
 int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const float* z, float* hist, float* out, int64_t n,
@@ -267,7 +284,7 @@ int sisic_dpmpp_step(sisic_ctx* ctx, const float* eps, const float* x, const flo
     StepLaunch L;
     step_tensors(L, ctx, STEP_RULE_DPMPP, 0, eps, x, hist, out, n, row, clip);
     L.z = z;
-    return launch_step(ctx, L, static_cast<hipStream_t>(stream));
+    return step_launch(ctx, "step", L, stream);
 }
 
 int sisic_ddpm_step_rng(sisic_ctx* ctx, const float* eps, const float* x, float* out, int B, int64_t n_per_image,
@@ -343,6 +360,37 @@ int sisic_set_step_prediction_type(sisic_ctx* ctx, int type) {
 }
 
 int sisic_step_prediction_type(const sisic_ctx* ctx) { return ctx ? ctx->step_pred : SISIC_PRED_EPSILON; }
+
+int sisic_set_step_thresholding(sisic_ctx* ctx, float ratio, float sample_max_value) {
+    SISIC_REQUIRE(ctx, "set_step_thresholding: null context");
+    SISIC_TRY(check_thresholding("set_step_thresholding", ratio, sample_max_value));
+    ctx->step_thr_ratio = ratio > 0.0f ? ratio : 0.0f;
+    ctx->step_thr_max = sample_max_value;
+    return SISIC_OK;
+}
+
+int sisic_set_step_image_elems(sisic_ctx* ctx, int64_t n_per_image) {
+    SISIC_REQUIRE(ctx, "set_step_image_elems: null context");
+    SISIC_REQUIRE(n_per_image >= 0 && n_per_image <= ((int64_t)1 << 24), "set_step_image_elems: %lld elements per image (0 .. 2^24)",
+                  (long long)n_per_image);
+    ctx->step_npi = n_per_image;
+    return SISIC_OK;
+}
+
+int sisic_x0_threshold(sisic_ctx* ctx, sisic_x0_threshold_args* a) {
+    SISIC_REQUIRE(ctx && a, "x0_threshold: null argument");
+    SISIC_REQUIRE(a->B > 0 && a->n_per_image > 0, "x0_threshold: empty batch");
+    SISIC_REQUIRE(a->source >= 0 && a->source <= 2, "x0_threshold: eps source %d (0 = plain, 1 = guided, 2 = classifier)", a->source);
+    const float row[6] = {a->sb, a->sa, 0.0f, 0.0f, 0.0f, 0.0f};
+    StepLaunch L;
+    L.rule = STEP_RULE_DDPM;
+    L.flags = step_pred_flags(ctx->step_pred);
+    L.source = a->source == 1 ? STEP_EPS_GUIDED : a->source == 2 ? STEP_EPS_CLASSIFIER : STEP_EPS_PLAIN;
+    L.eps = a->eps; L.eps_u = a->eps2; L.grad = a->eps2; L.x = a->x; L.row = row; L.w = a->w;
+    L.n_per_image = a->n_per_image; L.n = (int64_t)a->B * a->n_per_image;
+    L.thr_s = a->s; L.thr_ratio = a->ratio; L.thr_max = a->sample_max_value;
+    return launch_x0_threshold(ctx, L, static_cast<hipStream_t>(a->stream));
+}
 
 int sisic_denorm_u8(sisic_ctx* ctx, const float* x, uint8_t* out, int B, int C, int H, int W, void* stream) {
     SISIC_REQUIRE(ctx, "denorm_u8: null context");

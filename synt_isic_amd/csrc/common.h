@@ -64,6 +64,10 @@ struct sisic_ctx {
     int device = 0;
     int num_cus = 0;
     int step_pred = 0;              // sisic_set_step_prediction_type: what the single-step entries' eps argument means
+    // sisic_set_step_thresholding: the single-step entries clamp x0 dynamically (ratio 0: off); the entries that are not told
+    // the image size take it from sisic_set_step_image_elems
+    float step_thr_ratio = 0.0f, step_thr_max = 1.0f;
+    int64_t step_npi = 0;
     bool profiling = false;
     sisic::ProfileSlot prof[sisic::PK_COUNT];
     std::vector<sisic::PendingEvent> pending;
@@ -81,6 +85,10 @@ struct sisic_ctx {
     // kernel: one buffer per stream, grown on demand, for the same reason
     std::map<hipStream_t, SplitK> bn_part;
     std::mutex bn_part_mutex;
+    // every image's s of a thresholded single step (elementwise.hip), handed from the quantile kernel to the step kernel: one
+    // buffer per stream, grown on demand, for the same reason
+    std::map<hipStream_t, SplitK> thr_s;
+    std::mutex thr_s_mutex;
     // item tables of the bf16x3 Winograd kernel (conv_winograd_bf3.inc): one per launch geometry, filled on the device the
     // first time the geometry is met, never moved or freed before the context (captured graphs hold their addresses)
     // (fill_done: recorded behind the fill; until it has passed, only launches on the filling stream use the table)
@@ -250,8 +258,12 @@ struct StepLaunch {
     float* hist = nullptr;              // DPM-Solver++: the previous step's x0 [n], written on every step, read when k1 != 0
     int64_t n = 0;
     float clip = 0.0f;
+    // dynamic thresholding (thr_s set): the launcher first writes every image's s = clamp(quantile(|x0|, thr_ratio), 1, thr_max)
+    // to thr_s [n / n_per_image] (launch_x0_threshold), then runs the step with clamp(x0, -s, s) / s in place of `clip`
+    float* thr_s = nullptr;
+    float thr_ratio = 0.0f, thr_max = 1.0f;
     const uint64_t* seeds_dev = nullptr;    // device uint64 [n / n_per_image]
-    int64_t n_per_image = 0;
+    int64_t n_per_image = 0;                // device noise, an edit, thresholding
     const float* x0k = nullptr;         // edit: the known image [n] and the mask, whose row [B, 1, hw] is broadcast over the
     const float* mask = nullptr;        //       n_per_image / hw channels
     int64_t hw = 0;
@@ -271,6 +283,11 @@ struct StepLaunch {
     const float* w_tab = nullptr;
 };
 int launch_step(sisic_ctx*, const StepLaunch& L, hipStream_t s);
+// the quantile launch alone: what launch_step runs first when L.thr_s is set (ratio in [0, 1], max >= 1, images of at most 2^24)
+int launch_x0_threshold(sisic_ctx*, const StepLaunch& L, hipStream_t s);
+int check_thresholding(const char* what, float ratio, float max_value);
+// the s buffer of the context's own thresholded steps on stream s (one per stream, grown on demand): [images] floats
+int step_threshold_scratch(sisic_ctx*, hipStream_t s, int64_t images, float** out);
 int launch_guide_eps(sisic_ctx*, const float* eps_c, const float* eps_u, float w, float* out, int64_t n, hipStream_t s);
 // the loop's device table of a classifier-guided call (LoopClf): {scale, -, -, -, int target[B]}
 constexpr size_t LOOP_CLF_HEAD = 4;

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "noise_device.h"
 #include "pack_device.h"
+#include "poison_switch.h"
 #include <type_traits>
 
 namespace sisic {
@@ -38,12 +39,25 @@ __device__ __forceinline__ float pred_x0(float e, float x, float sb, float sa) {
     else return (x - sb * e) / sa;
 }
 
-template <int P>
+// The clamp of x0.  THR = false: the static range `clip` (0: none).  THR = true, dynamic thresholding (Saharia et al. 2022;
+// DESIGN.md section 2): clip is the image's s from x0_quantile_kernel below, and x0 becomes clamp(x0, -s, s) / s.  s = 1 divides
+// by one: the bits of the static clip = 1.  A NaN s passes the clamp and poisons the quotient, as torch.clamp's NaN does.
+template <bool THR>
+__device__ __forceinline__ float clamp_x0(float x0, float clip) {
+#pragma clang fp contract(off)
+    if constexpr (THR) {
+        return fminf(fmaxf(x0, -clip), clip) / clip;
+    } else {
+        if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+        return x0;
+    }
+}
+
+template <int P, bool THR>
 __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, float sa, float c0, float c1,
                                           float sigma, float clip, bool noise) {
 #pragma clang fp contract(off)
-    float x0 = pred_x0<P>(e, x, sb, sa);
-    if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+    float x0 = clamp_x0<THR>(pred_x0<P>(e, x, sb, sa), clip);
     float r = c0 * x0 + c1 * x;
     if (noise) r = r + sigma * z;
     return r;
@@ -54,13 +68,12 @@ __device__ __forceinline__ float ddpm_one(float e, float x, float z, float sb, f
 // {sb = (1-abar_t)^.5, sa = abar_t^.5, c_prev = abar_prev^.5, c_dir = (1 - abar_prev - sigma^2)^.5, sigma = eta * variance^.5}.
 // CLIPPED (use_clipped_model_output): the direction term uses the epsilon re-derived from the clamped x0.
 // The direction term's epsilon under the other types: sample (x - sa*x0)/sb with the UNCLAMPED x0; v sa*e + sb*x.
-template <bool CLIPPED, int P>
+template <bool CLIPPED, int P, bool THR>
 __device__ __forceinline__ float ddim_one(float e, float x, float z, float sb, float sa, float c_prev, float c_dir,
                                           float sigma, float clip, bool noise) {
 #pragma clang fp contract(off)
     const float x0u = pred_x0<P>(e, x, sb, sa);
-    float x0 = x0u;
-    if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+    const float x0 = clamp_x0<THR>(x0u, clip);
     float pe = e;
     if constexpr (CLIPPED) pe = (x - sa * x0) / sb;
     else if constexpr (P == PRED_SAMPLE) pe = (x - sa * x0u) / sb;
@@ -72,19 +85,19 @@ __device__ __forceinline__ float ddim_one(float e, float x, float z, float sb, f
 
 // The step rule as a functor: the row of five scalars and the clip range, applied to one element.  step_body is instantiated
 // once per rule and noise source, so no element pays for a branch on the rule.
-template <int P = PRED_EPS>
+template <int P = PRED_EPS, bool THR = false>
 struct DdpmRule {
     float sb, sa, c0, c1, sigma, clip;
     __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
-        return ddpm_one<P>(e, x, z, sb, sa, c0, c1, sigma, clip, noise);
+        return ddpm_one<P, THR>(e, x, z, sb, sa, c0, c1, sigma, clip, noise);
     }
 };
 
-template <bool CLIPPED, int P = PRED_EPS>
+template <bool CLIPPED, int P = PRED_EPS, bool THR = false>
 struct DdimRule {
     float sb, sa, c_prev, c_dir, sigma, clip;
     __device__ __forceinline__ float operator()(float e, float x, float z, bool noise) const {
-        return ddim_one<CLIPPED, P>(e, x, z, sb, sa, c_prev, c_dir, sigma, clip, noise);
+        return ddim_one<CLIPPED, P, THR>(e, x, z, sb, sa, c_prev, c_dir, sigma, clip, noise);
     }
 };
 
@@ -199,11 +212,26 @@ struct InpaintEdit {
     }
 };
 
+// Where the clamp's range comes from: the rule's own scalar, or (dynamic thresholding) the image's s, which replaces the scalar
+// element by element.  (of4: npi is a multiple of 4 on the vector path, so float4 i4 lies in one image)
+struct ScalarClip {
+    static constexpr bool on = false;
+};
+
+struct ImageThreshold {
+    static constexpr bool on = true;
+    const float* __restrict__ s;        // [n / npi]
+    int64_t npi;
+    __device__ __forceinline__ float of4(int64_t i4) const { return s[i4 / (npi >> 2)]; }
+    __device__ __forceinline__ float of1(int64_t i) const { return s[i / npi]; }
+};
+
 // out may alias x (the loop steps in place): every element is read before it is written, by the thread that writes it
 // (E::dup: vec4 only with n a multiple of 4, so that out + n is aligned like out)
-template <class R, class Z, class E, class D = NoEdit>
+template <class R, class Z, class E, class D = NoEdit, class C = ScalarClip>
 __device__ __forceinline__ void step_body(const E es, const float* x, float* out, int64_t n, bool vec4,
-                                          const R rule, const Z zs, const D ed = D{}) {
+                                          const R rule0, const Z zs, const D ed = D{}, const C cs = C{}) {
+    R rule = rule0;
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -215,6 +243,7 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
             const float4 e = es.get4(i), xv = x4[i];
             float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (noise) zv = zs.get4(i);
+            if constexpr (C::on) rule.clip = cs.of4(i);
             float4 r;
             r.x = rule(e.x, xv.x, zv.x, noise);
             r.y = rule(e.y, xv.y, zv.y, noise);
@@ -225,6 +254,7 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
             if constexpr (E::dup) o4[n4 + i] = r;
         }
         for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
+            if constexpr (C::on) rule.clip = cs.of1(i);
             float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
             if constexpr (D::on) r = ed.apply1(i, r);
             out[i] = r;
@@ -232,6 +262,7 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
         }
     } else {
         for (int64_t i = t0; i < n; i += stride) {
+            if constexpr (C::on) rule.clip = cs.of1(i);
             float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, noise);
             if constexpr (D::on) r = ed.apply1(i, r);
             out[i] = r;
@@ -247,14 +278,13 @@ __device__ __forceinline__ void step_body(const E es, const float* x, float* out
 // under the rounding rules of ddpm_one.  hist is the previous step's x0: one more stream, read (second-order steps only) and
 // written in place by the thread that owns the element, so a captured step replays as it is.  A first-order step (k1 == 0,
 // uniform over the launch) does not read it: whatever an earlier run left there, NaN included, stays out of the result.
-template <int P = PRED_EPS>
+template <int P = PRED_EPS, bool THR = false>
 struct DpmRule {
     float sb, sa, cx, k0, sigma, k1, clip;
     // h: the history's element (any value when !second); m0: this step's x0, the next step's history
     __device__ __forceinline__ float operator()(float e, float x, float z, float h, bool noise, bool second, float& m0) const {
 #pragma clang fp contract(off)
-        float x0 = pred_x0<P>(e, x, sb, sa);
-        if (clip > 0.0f) x0 = fminf(fmaxf(x0, -clip), clip);
+        const float x0 = clamp_x0<THR>(pred_x0<P>(e, x, sb, sa), clip);
         float r = cx * x + k0 * x0;
         if (second) r = r + k1 * h;
         if (noise) r = r + sigma * z;
@@ -264,9 +294,10 @@ struct DpmRule {
 };
 
 // step_body with the history stream.  out may alias x; hist aliases nothing else (and stays n wide under E::dup).
-template <class R, class Z, class E, class D = NoEdit>
+template <class R, class Z, class E, class D = NoEdit, class C = ScalarClip>
 __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float* hist, float* out, int64_t n,
-                                              bool vec4, const R rule, const Z zs, const D ed = D{}) {
+                                              bool vec4, const R rule0, const Z zs, const D ed = D{}, const C cs = C{}) {
+    R rule = rule0;
     const bool noise = zs.present() && (rule.sigma != 0.0f);
     const bool second = rule.k1 != 0.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -282,6 +313,7 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
             float4 hv = make_float4(0.f, 0.f, 0.f, 0.f), zv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (second) hv = h4[i];
             if (noise) zv = zs.get4(i);
+            if constexpr (C::on) rule.clip = cs.of4(i);
             float4 r, m;
             r.x = rule(e.x, xv.x, zv.x, hv.x, noise, second, m.x);
             r.y = rule(e.y, xv.y, zv.y, hv.y, noise, second, m.y);
@@ -296,6 +328,7 @@ __device__ __forceinline__ void dpm_step_body(const E es, const float* x, float*
     }
     for (int64_t i = tail; i < n; i += stride) {
         float m;
+        if constexpr (C::on) rule.clip = cs.of1(i);
         float r = rule(es.get1(i), x[i], noise ? zs.get1(i) : 0.f, second ? hist[i] : 0.f, noise, second, m);
         if constexpr (D::on) r = ed.apply1(i, r);
         hist[i] = m;
@@ -376,7 +409,7 @@ struct StepRow { float v[6]; };     // a rule's row: {sb, sa, c2, c3, sigma} or 
 
 // what the kernel has to know of a rule beside its arithmetic
 template <class R> struct RuleTraits { static constexpr int width = 5; static constexpr bool history = false; };
-template <int P> struct RuleTraits<DpmRule<P>> { static constexpr int width = 6; static constexpr bool history = true; };
+template <int P, bool THR> struct RuleTraits<DpmRule<P, THR>> { static constexpr int width = 6; static constexpr bool history = true; };
 
 struct StepArgs {
     const float* eps;                   // eps [n]; GuidedEps: the conditional half
@@ -399,9 +432,10 @@ struct StepArgs {
     float w, clip;
     uint32_t step;
     int vec4;
+    const float* thr;                   // ImageThreshold: s [n / npi], written by x0_quantile_kernel ahead of this launch
 };
 
-template <class R, class EPS, class NZ, class EDIT>
+template <class R, class EPS, class NZ, class EDIT, class CLIP = ScalarClip>
 __global__ void __launch_bounds__(256)
 step_kernel(const StepArgs a) {
     constexpr int WIDTH = RuleTraits<R>::width;
@@ -435,12 +469,16 @@ step_kernel(const StepArgs a) {
         if constexpr (EDIT::on) return InpaintEdit{a.x0k, a.mask, a.seeds, a.npi, a.hw, step, er[0], er[1], er[2], er[3]};
         else return NoEdit{};
     }();
+    const auto cs = [&] {
+        if constexpr (CLIP::on) return ImageThreshold{a.thr, a.npi};
+        else return ScalarClip{};
+    }();
     // (a noise row chosen on the device is only known here: the launcher's vec4 covers every pointer it could see)
     const bool vec4 = a.vec4 != 0 && zs.vec_ok();
     if constexpr (RuleTraits<R>::history)
-        dpm_step_body(es, a.x, a.hist, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip}, zs, ed);
+        dpm_step_body(es, a.x, a.hist, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], row.v[5], a.clip}, zs, ed, cs);
     else
-        step_body(es, a.x, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], a.clip}, zs, ed);
+        step_body(es, a.x, a.out, a.n, vec4, R{row.v[0], row.v[1], row.v[2], row.v[3], row.v[4], a.clip}, zs, ed, cs);
 }
 
 // The instantiations a caller can reach: every rule and prediction type in six forms, and classifier guidance under epsilon
@@ -448,27 +486,30 @@ step_kernel(const StepArgs a) {
 using StepKernel = void (*)(StepArgs);
 enum StepForm { FORM_BUFFER, FORM_DEVICE, FORM_GUIDED_BUFFER, FORM_GUIDED_DEVICE, FORM_EDIT, FORM_GUIDED_EDIT, FORM_CLF, STEP_FORMS };
 
-template <class R, int P>
+template <class R, int P, class C>
 static constexpr StepKernel clf_form() {
-    if constexpr (P == PRED_EPS) return step_kernel<R, ClassifierEps, PhiloxNoise, NoEdit>;
+    if constexpr (P == PRED_EPS) return step_kernel<R, ClassifierEps, PhiloxNoise, NoEdit, C>;
     else return nullptr;
 }
 
-template <class R, int P>
+template <class R, int P, class C = ScalarClip>
 struct StepFormsOf {
     static constexpr StepKernel k[STEP_FORMS] = {
-        step_kernel<R, PlainEps, BufferNoise, NoEdit>,      step_kernel<R, PlainEps, PhiloxNoise, NoEdit>,
-        step_kernel<R, GuidedEps, BufferNoise, NoEdit>,     step_kernel<R, GuidedEps, PhiloxNoise, NoEdit>,
-        step_kernel<R, PlainEps, PhiloxNoise, InpaintEdit>, step_kernel<R, GuidedEps, PhiloxNoise, InpaintEdit>,
-        clf_form<R, P>()};
+        step_kernel<R, PlainEps, BufferNoise, NoEdit, C>,      step_kernel<R, PlainEps, PhiloxNoise, NoEdit, C>,
+        step_kernel<R, GuidedEps, BufferNoise, NoEdit, C>,     step_kernel<R, GuidedEps, PhiloxNoise, NoEdit, C>,
+        step_kernel<R, PlainEps, PhiloxNoise, InpaintEdit, C>, step_kernel<R, GuidedEps, PhiloxNoise, InpaintEdit, C>,
+        clf_form<R, P, C>()};
 };
 
-// rows: DDPM, DDIM, DDIM with use_clipped_model_output, DPM-Solver++
+// rows: DDPM, DDIM, DDIM with use_clipped_model_output, DPM-Solver++; the same four again under dynamic thresholding
 template <int P>
-static StepKernel step_kernel_of(int rule, bool clipped, int form) {
-    const StepKernel* rows[4] = {StepFormsOf<DdpmRule<P>, P>::k, StepFormsOf<DdimRule<false, P>, P>::k,
-                                 StepFormsOf<DdimRule<true, P>, P>::k, StepFormsOf<DpmRule<P>, P>::k};
-    return rows[rule == STEP_RULE_DPMPP ? 3 : rule == STEP_RULE_DDIM ? 1 + (clipped ? 1 : 0) : 0][form];
+static StepKernel step_kernel_of(int rule, bool clipped, int form, bool thr) {
+    using T = ImageThreshold;
+    const StepKernel* rows[8] = {StepFormsOf<DdpmRule<P>, P>::k, StepFormsOf<DdimRule<false, P>, P>::k,
+                                 StepFormsOf<DdimRule<true, P>, P>::k, StepFormsOf<DpmRule<P>, P>::k,
+                                 StepFormsOf<DdpmRule<P, true>, P, T>::k, StepFormsOf<DdimRule<false, P, true>, P, T>::k,
+                                 StepFormsOf<DdimRule<true, P, true>, P, T>::k, StepFormsOf<DpmRule<P, true>, P, T>::k};
+    return rows[(thr ? 4 : 0) + (rule == STEP_RULE_DPMPP ? 3 : rule == STEP_RULE_DDIM ? 1 + (clipped ? 1 : 0) : 0)][form];
 }
 
 static const char* rule_name(int rule) {
@@ -501,6 +542,299 @@ int check_step_row(int rule, int flags, float sb, float sa) {
 // counter word 0 of a block is its index in the image: 32 bits
 static constexpr int64_t NOISE_MAX_PER_IMAGE = (int64_t)1 << 34;
 
+// ---- dynamic thresholding: the image's s ---------------------------------------------------------------
+// s[b] = clamp(quantile(|x0| of image b, ratio), 1, max) with torch.quantile's linear interpolation, spelled out (sisic.h,
+// sisic_x0_threshold): with a_0 <= ... <= a_{n-1} the image's |x0|, r = ratio * (n - 1) in fp32, lo = floor(r), hi = ceil(r),
+// w = r - lo, d = a_hi - a_lo:  q = w < 0.5 ? fma(w, d, a_lo) : fma(w - 1, d, a_hi) -- ONE rounding, torch's lerp.
+// One workgroup owns one image.  The keys are the bit patterns of |x0| (non-negative floats order as their bits do): an image
+// of up to 49152 elements on the vector path keeps them in registers, 48 a thread, formed once from loads issued together; any
+// other forms them again from (eps, x) on every pass.  Radix select from the top, 8 bits per pass over the 31 key bits, an integer histogram in
+// LDS.  The last pass leaves a_lo and the count of keys <= a_lo; a_hi is a_lo where that count reaches lo + 2 (or hi == lo),
+// else the smallest key above a_lo, one more pass.  Everything before the float formula is integer counting: two calls give
+// equal bits whatever order the waves arrive in.  A key above 0x7f800000 (a NaN) makes s NaN, as torch does.
+constexpr int QUANT_THREADS = 1024;
+constexpr int QUANT_CACHE = 48;                                    // keys a thread keeps in registers (12 float4)
+constexpr int64_t QUANT_CACHE_MAX = (int64_t)QUANT_CACHE * QUANT_THREADS;
+constexpr uint32_t QUANT_NO_KEY = 0xffffffffu;                     // a register slot behind the image's end: above every key
+constexpr int64_t THRESHOLD_MAX_PER_IMAGE = (int64_t)1 << 24;      // n - 1 is exact in fp32
+
+struct QuantArgs {
+    const float* eps;                   // as StepArgs: eps, the second stream of a guided or classifier source, x
+    const float* eps2;
+    const float* x;
+    const LoopState* st;                // replayed form: (sb, sa) from row st->step of coef, w from wtab[0]
+    const float* coef;
+    const float* wtab;
+    float* s;                           // [images]
+    int64_t npi;
+    float sb, sa, w;
+    float wq, maxv;                     // the interpolation weight r - lo; sample_max_value
+    uint32_t lo, hi;
+    int width;                          // floats per row of coef
+    int vec4;
+};
+
+// The histogram of a pass: 256 bins in QUANT_COPIES interleaved copies, a lane counting in copy (lane % QUANT_COPIES).  Pass 0 sees
+// the exponent byte, a handful of values: the copies lie in different banks and cut the lanes that meet on one address by that
+// factor.  (Counting a wave's equal digits with ballots first, one atomic per distinct digit, was measured at 98 us for one
+// image of 49152 against this form's time in profiles/r34/threshold.txt: the loop over the distinct digits costs more than
+// the conflicts it saves.)
+constexpr int QUANT_COPIES = 8;
+
+template <int P, class EPS, bool CACHED>
+__global__ void __launch_bounds__(QUANT_THREADS)
+x0_quantile_kernel(const QuantArgs a) {
+    __shared__ uint32_t hist[256 * QUANT_COPIES];
+    __shared__ uint32_t bins[256];      // the copies summed
+    __shared__ uint32_t sel[4];         // {prefix, rank inside the prefix, keys in the chosen bin, successor}
+    __shared__ int has_nan;
+    float sb = a.sb, sa = a.sa, w = a.w;
+    if (a.st) {
+        const int i = a.st->step;
+        sb = a.coef[a.width * i];
+        sa = a.coef[a.width * i + 1];
+        if constexpr (!std::is_same_v<EPS, PlainEps>) w = a.wtab[0];
+    }
+    const auto es = [&] {
+        if constexpr (std::is_same_v<EPS, GuidedEps>) return GuidedEps{a.eps, a.eps2, w};
+        else if constexpr (std::is_same_v<EPS, ClassifierEps>) return ClassifierEps{a.eps, a.eps2, clf_guide_k(w, sb)};
+        else return PlainEps{a.eps};
+    }();
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * a.npi;
+    const bool vec4 = a.vec4 != 0;
+    // f(key, valid) on every key of the image, every thread making the same number of trips
+    const int64_t items = vec4 ? a.npi >> 2 : a.npi;
+    auto key_of = [&](float e, float x) -> uint32_t { return __float_as_uint(pred_x0<P>(e, x, sb, sa)) & 0x7fffffffu; };
+    // CACHED: the loads of the image in one basic block (an index behind the end reads the last item and keeps no key), so
+    // that they are in flight together; the passes then run on registers
+    uint32_t kc[CACHED ? QUANT_CACHE : 1];
+    if constexpr (CACHED) {
+        // (the launcher chooses CACHED for the vector path only.)  Two batches of six float4 per stream: the loads of a batch
+        // first, then its keys, each pinned to a register so that the passes keep 48 keys and not the values they came from
+        constexpr int HALF = QUANT_CACHE / 8;
+        auto pin = [](uint32_t k) -> uint32_t { asm volatile("" : "+v"(k)); return k; };
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float4 e[HALF], xv[HALF];
+#pragma unroll
+            for (int v = 0; v < HALF; ++v) {
+                const int64_t j = (int64_t)(h * HALF + v) * QUANT_THREADS + tid, jc = j < items ? j : items - 1;
+                e[v] = es.get4((base >> 2) + jc);
+                xv[v] = reinterpret_cast<const float4*>(a.x)[(base >> 2) + jc];
+            }
+#pragma unroll
+            for (int v = 0; v < HALF; ++v) {
+                const int u = h * HALF + v;
+                const bool valid = (int64_t)u * QUANT_THREADS + tid < items;
+                kc[4 * u + 0] = pin(valid ? key_of(e[v].x, xv[v].x) : QUANT_NO_KEY);
+                kc[4 * u + 1] = pin(valid ? key_of(e[v].y, xv[v].y) : QUANT_NO_KEY);
+                kc[4 * u + 2] = pin(valid ? key_of(e[v].z, xv[v].z) : QUANT_NO_KEY);
+                kc[4 * u + 3] = pin(valid ? key_of(e[v].w, xv[v].w) : QUANT_NO_KEY);
+            }
+        }
+    }
+    // (slot u holds a key of item u / 4; whole rounds behind the image's end are skipped)
+    auto for_keys = [&](auto&& f) {
+        if constexpr (CACHED) {
+#pragma unroll
+            for (int u = 0; u < QUANT_CACHE; ++u) {
+                if ((int64_t)(u / 4) * QUANT_THREADS >= items) break;
+                f(kc[u], kc[u] != QUANT_NO_KEY);
+            }
+            return;
+        }
+        for (int64_t j0 = 0; j0 < items; j0 += QUANT_THREADS) {
+            const int64_t j = j0 + tid;
+            const bool valid = j < items;
+            if (vec4) {
+                float4 e = make_float4(0.f, 0.f, 0.f, 0.f), xv = e;
+                if (valid) {
+                    e = es.get4((base >> 2) + j);
+                    xv = reinterpret_cast<const float4*>(a.x)[(base >> 2) + j];
+                }
+                f(key_of(e.x, xv.x), valid);
+                f(key_of(e.y, xv.y), valid);
+                f(key_of(e.z, xv.z), valid);
+                f(key_of(e.w, xv.w), valid);
+            } else {
+                float e = 0.f, xv = 0.f;
+                if (valid) {
+                    e = es.get1(base + j);
+                    xv = a.x[base + j];
+                }
+                f(key_of(e, xv), valid);
+            }
+        }
+    };
+    for (int k = tid; k < 256 * QUANT_COPIES; k += QUANT_THREADS) hist[k] = 0u;
+    if (tid == 0) { sel[0] = 0u; sel[1] = a.lo; sel[2] = 0u; sel[3] = 0xffffffffu; has_nan = 0; }
+    __syncthreads();
+    uint32_t prefix = 0u;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sh = pass == 3 ? 0 : 23 - 8 * pass, top = pass == 3 ? 7 : sh + 8;
+        const uint32_t dmask = pass == 3 ? 0x7fu : 0xffu;
+        const uint32_t copy = tid & (QUANT_COPIES - 1);
+        if (pass == 0) {
+            for_keys([&](uint32_t key, bool valid) {
+                if (valid && key > 0x7f800000u) has_nan = 1;
+                if (valid) atomicAdd(&hist[(key >> 23) * QUANT_COPIES + copy], 1u);
+            });
+        } else {
+            for_keys([&](uint32_t key, bool valid) {
+                if (valid && (key >> top) == (prefix >> top)) atomicAdd(&hist[((key >> sh) & dmask) * QUANT_COPIES + copy], 1u);
+            });
+        }
+        __syncthreads();
+        if (tid < 256) {
+            uint32_t c = 0u;
+            for (int r = 0; r < QUANT_COPIES; ++r) {
+                c += hist[tid * QUANT_COPIES + r];
+                hist[tid * QUANT_COPIES + r] = 0u;      // (for the next pass: counting resumes two barriers on)
+            }
+            bins[tid] = c;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            const uint32_t k = sel[1];
+            const uint32_t c0 = bins[4 * tid], c1 = bins[4 * tid + 1], c2 = bins[4 * tid + 2], c3 = bins[4 * tid + 3];
+            const uint32_t c = c0 + c1 + c2 + c3;
+            uint32_t incl = c;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
+                if (tid >= o) incl += v;
+            }
+            const uint32_t excl = incl - c;
+            if (k >= excl && k < incl) {        // one lane: the four bins that hold rank k
+                uint32_t kk = k - excl, d = 4u * tid, cnt = c0;
+                if (kk >= c0) { kk -= c0; d += 1; cnt = c1;
+                    if (kk >= c1) { kk -= c1; d += 1; cnt = c2;
+                        if (kk >= c2) { kk -= c2; d += 1; cnt = c3; } } }
+                sel[0] = prefix | (d << sh);
+                sel[1] = kk;
+                sel[2] = cnt;
+            }
+        }
+        __syncthreads();
+        prefix = sel[0];
+    }
+    const uint32_t a_lo = prefix;
+    const uint32_t cnt_le = (a.lo - sel[1]) + sel[2];       // keys below a_lo, and the keys equal to it
+    uint32_t a_hi = a_lo;
+    if (a.hi != a.lo && cnt_le < a.lo + 2u) {               // (uniform over the workgroup)
+        uint32_t m = 0xffffffffu;
+        for_keys([&](uint32_t key, bool valid) {
+            if (valid && key > a_lo && key < m) m = key;
+        });
+        atomicMin(&sel[3], m);
+        __syncthreads();
+        a_hi = sel[3];
+    }
+    if (tid == 0) {
+        const float lo_v = __uint_as_float(a_lo), hi_v = __uint_as_float(a_hi);
+        const float d = hi_v - lo_v;
+        const float q = a.wq < 0.5f ? __builtin_fmaf(a.wq, d, lo_v) : __builtin_fmaf(a.wq - 1.0f, d, hi_v);
+        float sv = fminf(fmaxf(q, 1.0f), a.maxv);
+        if (q != q) sv = q;                                 // (fmaxf would drop the NaN that torch.clamp keeps)
+        if (has_nan) sv = __uint_as_float(0x7fc00000u);
+        a.s[blockIdx.x] = sv;
+    }
+}
+
+using QuantKernel = void (*)(QuantArgs);
+template <int P, bool CACHED>
+static QuantKernel quant_kernel_of(StepEps source) {
+    if (source == STEP_EPS_GUIDED) return x0_quantile_kernel<P, GuidedEps, CACHED>;
+    if constexpr (P == PRED_EPS)
+        if (source == STEP_EPS_CLASSIFIER) return x0_quantile_kernel<P, ClassifierEps, CACHED>;
+    return source == STEP_EPS_PLAIN ? x0_quantile_kernel<P, PlainEps, CACHED> : nullptr;
+}
+
+template <int P>
+static QuantKernel quant_kernel_of(StepEps source, bool cached) {
+    return cached ? quant_kernel_of<P, true>(source) : quant_kernel_of<P, false>(source);
+}
+
+// [a, a + na) and [b, b + nb) floats share an element
+static bool ranges_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + 4u * (uintptr_t)nb && b0 < a0 + 4u * (uintptr_t)na;
+}
+
+int check_thresholding(const char* what, float ratio, float max_value) {
+    SISIC_REQUIRE(std::isfinite(ratio) && ratio >= 0.0f && ratio <= 1.0f, "%s: dynamic_thresholding_ratio %g is outside [0, 1]", what,
+                  (double)ratio);
+    SISIC_REQUIRE(std::isfinite(max_value) && max_value >= 1.0f, "%s: sample_max_value %g is below 1 or not finite", what,
+                  (double)max_value);
+    return SISIC_OK;
+}
+
+// The launch of x0_quantile_kernel for the step L describes: L.thr_s [L.n / L.n_per_image] gets every image's s.  Reads what
+// the step reads (eps, x, the row's sb and sa, w) and nothing the step writes: the step follows it on the same stream.
+int launch_x0_threshold(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
+    SISIC_TRY(check_rule(L.rule, L.flags));
+    SISIC_TRY(check_thresholding("x0_threshold", L.thr_ratio, L.thr_max));
+    const bool guided = L.source == STEP_EPS_GUIDED, clf = L.source == STEP_EPS_CLASSIFIER, replayed = L.state != nullptr;
+    const float* eps2 = guided ? L.eps_u : clf ? L.grad : nullptr;
+    SISIC_REQUIRE(L.eps && L.x && L.thr_s && L.n > 0 && (L.source == STEP_EPS_PLAIN || eps2), "x0_threshold: null tensor or empty");
+    SISIC_REQUIRE(!clf || step_pred(L.flags) == PRED_EPS, "x0_threshold: prediction_type %d: classifier guidance takes "
+                  "epsilon-prediction models only", step_pred(L.flags));
+    SISIC_REQUIRE(L.n_per_image > 0 && L.n % L.n_per_image == 0, "x0_threshold: %lld elements are not whole images of %lld",
+                  (long long)L.n, (long long)L.n_per_image);
+    SISIC_REQUIRE(L.n_per_image <= THRESHOLD_MAX_PER_IMAGE, "x0_threshold: an image of %lld elements (at most 2^24: the rank is "
+                  "formed in fp32)", (long long)L.n_per_image);
+    SISIC_REQUIRE(L.n / L.n_per_image <= INT32_MAX, "x0_threshold: %lld images", (long long)(L.n / L.n_per_image));
+    SISIC_REQUIRE(!ranges_overlap(L.thr_s, L.n / L.n_per_image, L.eps, L.n) && !ranges_overlap(L.thr_s, L.n / L.n_per_image, eps2, L.n) &&
+                  !ranges_overlap(L.thr_s, L.n / L.n_per_image, L.x, L.n), "x0_threshold: s aliases eps, its second stream or x");
+    QuantArgs a{};
+    if (replayed) {
+        SISIC_REQUIRE(L.coef_dev && (L.source == STEP_EPS_PLAIN || L.w_tab), "x0_threshold: null table");
+    } else {
+        SISIC_REQUIRE(L.row, "x0_threshold: null row");
+        SISIC_TRY(check_step_row(L.rule, L.flags, L.row[0], L.row[1]));
+        a.sb = L.row[0]; a.sa = L.row[1];
+    }
+    a.eps = L.eps; a.eps2 = eps2; a.x = L.x; a.s = L.thr_s; a.npi = L.n_per_image;
+    a.st = static_cast<const LoopState*>(L.state); a.coef = L.coef_dev; a.wtab = L.w_tab; a.w = L.w;
+    a.width = (int)SISIC_RULE_ROW_WIDTH(L.rule);
+    // the rank in fp32, as torch.quantile forms it from a float32 q
+    const float r = L.thr_ratio * (float)(L.n_per_image - 1);
+    const float lo = std::floor(r), hi = std::ceil(r);
+    a.lo = (uint32_t)lo; a.hi = (uint32_t)hi; a.wq = r - lo; a.maxv = L.thr_max;
+    const uintptr_t al = reinterpret_cast<uintptr_t>(a.eps) | reinterpret_cast<uintptr_t>(a.eps2) | reinterpret_cast<uintptr_t>(a.x);
+    a.vec4 = (al & 15) == 0 && (L.n_per_image & 3) == 0;
+    ProfileScope prof(ctx, s, PK_DDPM, 4.0 * (a.vec4 && L.n_per_image <= QUANT_CACHE_MAX ? 1.0 : 5.0) * (eps2 ? 3.0 : 2.0) * (double)L.n, 0.0);
+    const int P = step_pred(L.flags);
+    const bool cached = a.vec4 && L.n_per_image <= QUANT_CACHE_MAX;
+    const QuantKernel kernel = P == PRED_SAMPLE ? quant_kernel_of<PRED_SAMPLE>(L.source, cached)
+                               : P == PRED_V    ? quant_kernel_of<PRED_V>(L.source, cached)
+                                                : quant_kernel_of<PRED_EPS>(L.source, cached);
+    SISIC_REQUIRE(kernel, "x0_threshold: eps source %d", (int)L.source);
+    void* args[] = {&a};
+    SISIC_HIP(hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3((unsigned)(L.n / L.n_per_image)), dim3(QUANT_THREADS), args, 0, s));
+    return SISIC_OK;
+}
+
+int step_threshold_scratch(sisic_ctx* ctx, hipStream_t s, int64_t images, float** out) {
+    std::lock_guard<std::mutex> lock(ctx->thr_s_mutex);
+    auto& buf = ctx->thr_s[s];
+    const size_t floats = (size_t)std::max<int64_t>(images, 64);
+    if (buf.floats < floats) {
+        SISIC_HIP(hipStreamSynchronize(s));          // earlier launches on this stream may still read the old buffer
+        if (buf.p) SISIC_HIP(hipFree(buf.p));
+        buf.p = nullptr; buf.floats = 0;
+        SISIC_HIP(hipMalloc(reinterpret_cast<void**>(&buf.p), floats * sizeof(float)));
+        if (poison_alloc()) {                        // SISIC_POISON_ALLOC=1: an s no workgroup writes is NaN
+            SISIC_HIP(hipMemset(buf.p, 0xFF, floats * sizeof(float)));
+            SISIC_HIP(hipDeviceSynchronize());
+        }
+        buf.floats = floats;
+        ctx->scratch_generation.fetch_add(1);
+    }
+    *out = buf.p;
+    return SISIC_OK;
+}
+
 // The one launcher (common.h StepLaunch): every check, the alignment rule, the grid and the byte count of a step, once.
 int launch_step(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
     SISIC_TRY(check_rule(L.rule, L.flags));
@@ -525,6 +859,13 @@ int launch_step(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
     if (L.device_noise)
         SISIC_REQUIRE(L.n_per_image > 0 && L.n_per_image <= NOISE_MAX_PER_IMAGE && L.n % L.n_per_image == 0,
                       "%s: %lld elements are not whole images of %lld", name, (long long)L.n, (long long)L.n_per_image);
+    // dynamic thresholding: s must lie apart from everything the step writes (what it reads is launch_x0_threshold's to check)
+    const bool thr = L.thr_s != nullptr;
+    if (thr) {
+        const int64_t images = L.n_per_image > 0 ? (L.n + L.n_per_image - 1) / L.n_per_image : 1;
+        SISIC_REQUIRE(!ranges_overlap(L.thr_s, images, L.out, guided ? 2 * L.n : L.n) && (!hist || !ranges_overlap(L.thr_s, images, L.hist, L.n)),
+                      "%s: s aliases an output of the step", name);
+    }
     if (L.edit) {
         SISIC_REQUIRE(L.hw > 0 && L.n_per_image % L.hw == 0, "%s: an image of %lld elements is not whole channels of %lld", name,
                       (long long)L.n_per_image, (long long)L.hw);
@@ -548,7 +889,10 @@ int launch_step(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
     a.eps = L.eps; a.eps2 = eps2; a.x = L.x; a.out = L.out; a.hist = hist ? L.hist : nullptr;
     a.z = L.z; a.seeds = L.seeds_dev; a.x0k = L.edit ? L.x0k : nullptr; a.mask = L.edit ? L.mask : nullptr;
     a.st = static_cast<const LoopState*>(L.state); a.coef = L.coef_dev; a.zrow = L.zrow_dev; a.erows = L.erows_dev; a.wtab = L.w_tab;
-    a.n = L.n; a.npi = L.n_per_image; a.hw = L.hw; a.w = L.w; a.clip = L.clip; a.step = L.step;
+    a.n = L.n; a.npi = L.n_per_image; a.hw = L.hw; a.w = L.w; a.clip = L.clip; a.step = L.step; a.thr = L.thr_s;
+    // every refusal of the step lies above: the quantile launch (which checks the images and the setting, and may refuse too)
+    // goes directly before the step's own, so that a refused call has launched nothing
+    if (thr) SISIC_TRY(launch_x0_threshold(ctx, L, s));
     // 4 bytes per element of every stream read or written (the mask is a channel's worth per image); a row on the device
     // leaves out what only the row decides, and is never profiled (the replayed loop runs without the profiler)
     const bool z_read = !replayed && L.z && L.row[4] != 0.0f, hist_read = !replayed && hist && L.row[5] != 0.0f;
@@ -561,15 +905,15 @@ int launch_step(sisic_ctx* ctx, const StepLaunch& L, hipStream_t s) {
     for (const void* p : {(const void*)a.eps, (const void*)a.eps2, (const void*)a.x, (const void*)a.out, (const void*)a.hist,
                           (const void*)a.z, (const void*)a.x0k, (const void*)a.mask})
         al |= reinterpret_cast<uintptr_t>(p);
-    a.vec4 = (al & 15) == 0 && (!L.device_noise || (L.n_per_image & 3) == 0) && (!L.edit || (L.hw & 3) == 0) && (!guided || (L.n & 3) == 0);
+    a.vec4 = (al & 15) == 0 && (!(L.device_noise || thr) || (L.n_per_image & 3) == 0) && (!L.edit || (L.hw & 3) == 0) && (!guided || (L.n & 3) == 0);
     const int64_t work = a.vec4 ? (L.n + 3) / 4 : L.n;
     const dim3 grid((unsigned)std::min<int64_t>((work + 255) / 256, 2048)), block(256);
     const int form = clf ? FORM_CLF : L.edit ? FORM_EDIT + (guided ? 1 : 0) : (guided ? FORM_GUIDED_BUFFER : FORM_BUFFER) + (L.device_noise ? 1 : 0);
     const bool clipped = (L.flags & STEP_FLAG_CLIPPED_OUTPUT) != 0;
     const int P = step_pred(L.flags);
-    const StepKernel kernel = P == PRED_SAMPLE ? step_kernel_of<PRED_SAMPLE>(L.rule, clipped, form)
-                              : P == PRED_V    ? step_kernel_of<PRED_V>(L.rule, clipped, form)
-                                               : step_kernel_of<PRED_EPS>(L.rule, clipped, form);
+    const StepKernel kernel = P == PRED_SAMPLE ? step_kernel_of<PRED_SAMPLE>(L.rule, clipped, form, thr)
+                              : P == PRED_V    ? step_kernel_of<PRED_V>(L.rule, clipped, form, thr)
+                                               : step_kernel_of<PRED_EPS>(L.rule, clipped, form, thr);
     void* args[] = {&a};
     SISIC_HIP(hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, 0, s));
     return SISIC_OK;

@@ -740,7 +740,7 @@ int sisic_unet_destroy(sisic_unet* u) {
     (void)hipDeviceSynchronize();
     pool_release_all(u);
     for (float* p : {u->x_work, u->loop_tables, u->tproj_cur, u->seeds_dev, u->hist_buf, u->cond_tables, u->edit_x0k, u->edit_mask,
-                     u->edit_rows, u->objective_dev, u->clf_grad, u->clf_tables})
+                     u->edit_rows, u->objective_dev, u->clf_grad, u->clf_tables, u->thr_s})
         if (p) (void)hipFree(p);
     if (u->loop_stream) (void)hipStreamDestroy(u->loop_stream);
     for (auto p : u->owned) (void)hipFree(p);
@@ -777,6 +777,14 @@ int sisic_unet_set_prediction_type(sisic_unet* u, int type) {
 }
 
 int sisic_unet_prediction_type(const sisic_unet* u) { return u ? u->pred_type : SISIC_PRED_EPSILON; }
+
+int sisic_unet_set_thresholding(sisic_unet* u, float ratio, float sample_max_value) {
+    SISIC_REQUIRE(u, "set_thresholding: null handle");
+    SISIC_TRY(check_thresholding("set_thresholding", ratio, sample_max_value));
+    u->thr_ratio = ratio > 0.0f ? ratio : 0.0f;
+    u->thr_max = sample_max_value;
+    return SISIC_OK;
+}
 
 int64_t sisic_unet_workspace_bytes(const sisic_unet* u) {
     return u ? u->pool.bytes() : 0;
@@ -928,6 +936,8 @@ static StepLaunch loop_step_launch(const sisic_unet* u, const LoopCall& c, float
     L.device_noise = c.seeds != nullptr;
     if (c.seeds) L.seeds_dev = reinterpret_cast<const uint64_t*>(u->seeds_dev);
     L.n_per_image = (int64_t)(n / c.B);
+    // (the handle's thresholding: sample_frames has sized thr_s; the quantile launch is launch_step's first)
+    if (u->thr_ratio > 0.0f) { L.thr_s = u->thr_s; L.thr_ratio = u->thr_ratio; L.thr_max = u->thr_max; }
     L.edit = c.ed != nullptr;
     L.hw = (int64_t)c.H * c.W;
     if (i >= 0) {
@@ -1054,17 +1064,19 @@ static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
     const void* cgr = cl ? u->clf_grad : nullptr;
     const void* ctab = cl ? u->clf_tables : nullptr;
     const void* clf_handle = cl ? cl->clf : nullptr;
+    const void* thr = u->thr_ratio > 0.0f ? u->thr_s : nullptr;          // (sized by sample_frames before this call)
     auto clf_gen = [&]() -> uint64_t { return cl ? resnet_workspace_generation(cl->clf) : 0; };
     auto reusable = [&]() -> bool {
         const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[12] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab};
+        const void* ptrs[13] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab, thr};
         bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
                   u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
                   u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
                   u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags && u->loop_key.cond == (cg != nullptr) &&
                   u->loop_key.guided == guided && u->loop_key.edit == edit && u->loop_key.clf == (cl != nullptr) &&
-                  u->loop_key.clf_handle == clf_handle && u->loop_key.clf_gen == clf_gen();
-        for (int k = 0; k < 12; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
+                  u->loop_key.clf_handle == clf_handle && u->loop_key.clf_gen == clf_gen() &&
+                  u->loop_key.thr_ratio == u->thr_ratio && u->loop_key.thr_max == u->thr_max;
+        for (int k = 0; k < 13; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
         return ok;
     };
     if (rc == SISIC_OK && !reusable()) {
@@ -1078,7 +1090,7 @@ static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
     if (rc == SISIC_OK && i < T) {
         if (!reusable()) {
             const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[12] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab};
+            const void* ptrs[13] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab, thr};
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
             const int crc = loop_step(u, c, n, s);
@@ -1097,7 +1109,8 @@ static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
             u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
             u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided; u->loop_key.edit = edit;
             u->loop_key.clf = cl != nullptr; u->loop_key.clf_handle = clf_handle; u->loop_key.clf_gen = clf_gen();
-            for (int k = 0; k < 12; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            u->loop_key.thr_ratio = u->thr_ratio; u->loop_key.thr_max = u->thr_max;
+            for (int k = 0; k < 13; ++k) u->loop_key.ptrs[k] = ptrs[k];
             u->loop_valid = true;
             u->loop_builds += 1;
         }
@@ -1216,6 +1229,12 @@ static int sample_frames(sisic_unet* u, LoopCall c) {
     const size_t n = (size_t)B * C * H * W;
     SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, (size_t)rows * C * H * W));
     if (rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
+    // dynamic thresholding: every image's s of the step, [B] (a guided call steps B images)
+    if (u->thr_ratio > 0.0f) {
+        SISIC_REQUIRE((size_t)C * H * W <= ((size_t)1 << 24), "sample: thresholding takes images of at most 2^24 elements, these have %zu",
+                      (size_t)C * H * W);
+        SISIC_TRY(unet_grow(&u->thr_s, &u->thr_s_cap, (size_t)std::max(B, 64)));
+    }
     const bool rng = seeds != nullptr;
     if (cl) {
         // the loop's device table of the call: {scale, -, -, -, int target[B]} (elementwise.hip, LoopClf)

@@ -235,12 +235,15 @@ struct sisic_unet {
     hipGraphExec_t loop_exec = nullptr;
     struct LoopKey {
         int B = 0, H = 0, W = 0; float clip = 0; hipStream_t s = nullptr; bool latency = false; uint64_t gen = 0;
-        const void* ptrs[12] = {};       // tproj, eps_buf, x_work, loop_tables, tproj_cur, (DPM-Solver++ steps, else null)
+        const void* ptrs[13] = {};       // tproj, eps_buf, x_work, loop_tables, tproj_cur, (DPM-Solver++ steps, else null)
                                          // hist_buf, (conditional calls, else null) cond_tables, (edited calls, else null)
                                          // edit_x0k, edit_mask, edit_rows and (classifier-guided calls, else null) clf_grad,
                                          // clf_tables at capture time: each can be re-allocated
         bool cond = false, guided = false;   // sisic_sample_frames_cond: per-sample embedding rows; two predictions per step
         bool edit = false;               // sisic_sample_frames_edit: the step kernel carries the inpainting epilogue
+        // sisic_unet_set_thresholding: the step runs the quantile launch and the thresholded step kernel (ratio 0: neither), both
+        // of which hold the setting as launch arguments; ptrs[12] is thr_s, or null
+        float thr_ratio = 0.0f, thr_max = 1.0f;
         // sisic_sample_frames_clf: the step runs the classifier's gradient walk.  The handle and the generation of its workspace
         // (resnet_workspace_generation): the captured launches hold the classifier's pool blocks and weight buffers
         bool clf = false;
@@ -273,6 +276,10 @@ struct sisic_unet {
     float* clf_grad = nullptr;           // sisic_sample_frames_clf: the classifier's input gradient at the step's latent [B,C,H,W]
     float* clf_tables = nullptr;         // ... and the call's {scale, -, -, -, int target[B]} (elementwise.hip, LoopClf)
     size_t clf_grad_cap = 0, clf_tables_cap = 0;
+    // dynamic thresholding (sisic_unet_set_thresholding; ratio 0: off): read by every sampling loop of the handle
+    float thr_ratio = 0.0f, thr_max = 1.0f;
+    float* thr_s = nullptr;              // every image's s of the step [B]: written by the quantile launch, read by the step kernel
+    size_t thr_s_cap = 0;
 
     int add(const std::string& name, int64_t numel) {
         index[name] = (int)names.size();

@@ -39,6 +39,86 @@ def context(device: torch.device, step_prediction: str = "epsilon") -> C.c_void_
     return _ctx_by_device[key]
 
 
+def check_threshold(threshold):
+    """``(ratio, sample_max_value)`` of a thresholded step as two floats, or ValueError: ratio inside [0, 1], the maximum finite
+    and at least 1 (what the library refuses with SISIC_EINVAL, refused here before anything is set)."""
+    try:
+        ratio, max_value = (float(v) for v in threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"threshold {threshold!r}: a pair (dynamic_thresholding_ratio, sample_max_value)") from None
+    if not (np.isfinite(ratio) and 0.0 <= ratio <= 1.0):
+        raise ValueError(f"dynamic_thresholding_ratio {ratio} is outside [0, 1]")
+    if not (np.isfinite(max_value) and max_value >= 1.0):
+        raise ValueError(f"sample_max_value {max_value} is below 1 or not finite")
+    return ratio, max_value
+
+
+THRESHOLD_MAX_PER_IMAGE = 1 << 24
+
+
+def _step_context(x: torch.Tensor, prediction_type: str, threshold, B: Optional[int] = None) -> C.c_void_p:
+    """The context of a single-step wrapper.  ``threshold`` None: the shared context of the prediction type, which no call
+    changes.  ``threshold=(ratio, max)``: dynamic thresholding (sisic_set_step_thresholding) on a second context per
+    prediction type that only thresholded steps use; its setting and its image size are host state the entry reads when it
+    is called, so they are set before every call.  Images: ``B`` of them, or x's leading dimension."""
+    if threshold is None:
+        return context(x.device, prediction_type)
+    ratio, max_value = check_threshold(threshold)
+    if ratio == 0.0:
+        raise ValueError("threshold=(0, ...) switches thresholding off: pass threshold=None")
+    if B is None:
+        if x.dim() < 2:
+            raise ValueError("a thresholded step takes x as [B, ...]: the images are its leading dimension")
+        B = x.shape[0]
+    npi = x.numel() // B
+    if npi > THRESHOLD_MAX_PER_IMAGE:
+        raise ValueError(f"thresholding takes images of at most 2**24 elements, these have {npi}")
+    lib = _lib.load()
+    code = _lib.prediction_code(prediction_type)
+    device = torch.device(x.device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, code, "threshold")
+    if key not in _ctx_by_device:
+        h = C.c_void_p()
+        check(lib.sisic_create(idx, C.byref(h)))
+        check(lib.sisic_set_step_prediction_type(h, code))
+        _ctx_by_device[key] = h
+    h = _ctx_by_device[key]
+    check(lib.sisic_set_step_thresholding(h, ratio, max_value))
+    check(lib.sisic_set_step_image_elems(h, npi))
+    return h
+
+
+def x0_threshold(eps: torch.Tensor, x: torch.Tensor, sb: float, sa: float, ratio: float, sample_max_value: float = 1.0, *,
+                 prediction_type: str = "epsilon", eps_u: Optional[torch.Tensor] = None, guidance_scale: float = 1.0,
+                 grad: Optional[torch.Tensor] = None, classifier_scale: float = 0.0) -> torch.Tensor:
+    """sisic_x0_threshold: every image's ``s = clamp(quantile(|x0|, ratio), 1, sample_max_value)`` of dynamic thresholding
+    (include/sisic.h), fp32 [B] for x = [B, ...].  x0 is the rule's estimate before any clamp, from ``eps`` as the step sees
+    it: as it stands, combined with ``eps_u`` under ``guidance_scale`` (classifier-free guidance), or with the classifier's
+    gradient ``grad`` under ``classifier_scale``."""
+    lib = _lib.load()
+    if x.dim() < 2:
+        raise ValueError("x0_threshold takes x as [B, ...]: the images are its leading dimension")
+    ratio, max_value = check_threshold((ratio, sample_max_value))
+    if eps_u is not None and grad is not None:
+        raise ValueError("eps_u and grad: one guidance at a time")
+    second = eps_u if eps_u is not None else grad
+    for name, t in (("eps", eps), ("eps_u / grad", second)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f"{name} holds {t.numel()} elements for an x of {x.numel()}")
+    B = x.shape[0]
+    if x.numel() // B > THRESHOLD_MAX_PER_IMAGE:
+        raise ValueError(f"thresholding takes images of at most 2**24 elements, these have {x.numel() // B}")
+    s = empty((B,), dtype=torch.float32, device=x.device)
+    a = _lib.X0ThresholdArgs(eps=_ptr(eps, "eps"), eps2=_ptr(second, "eps_u / grad"), x=_ptr(x, "x"), s=s.data_ptr(),
+                             stream=_stream(x.device), n_per_image=x.numel() // B, B=B,
+                             source=1 if eps_u is not None else 2 if grad is not None else 0, sb=float(sb), sa=float(sa),
+                             w=float(guidance_scale if eps_u is not None else classifier_scale), ratio=ratio,
+                             sample_max_value=max_value, reserved=0.0)
+    check(lib.sisic_x0_threshold(context(x.device, prediction_type), C.byref(a)))
+    return s
+
+
 def empty(shape, *, dtype, device, pin_memory=False) -> torch.Tensor:
     """The package's one allocation point for tensors it hands to the library uninitialised: ``torch.empty``.  (The GPU suite
     replaces it, and ``empty_like``, with a poisoned, guarded allocation: tests/poison.py.)"""
@@ -234,14 +314,16 @@ def attention(qkv: torch.Tensor, head_dim: int = 8) -> torch.Tensor:
 
 
 def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
-              out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """coef = (sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma).  ``prediction_type`` (here and in every step wrapper below):
-    what ``eps`` holds -- "epsilon", "sample" (x0) or "v_prediction" (include/sisic.h SISIC_PRED_*)."""
+    what ``eps`` holds -- "epsilon", "sample" (x0) or "v_prediction" (include/sisic.h SISIC_PRED_*).  ``threshold`` (likewise):
+    None, or ``(dynamic_thresholding_ratio, sample_max_value)`` for dynamic thresholding of x0 in place of ``clip``, which is
+    then not read; x is [B, ...] (or, in the ``_rng`` and ``_edit`` wrappers, len(seeds) equal images)."""
     lib = _lib.load()
     if out is None:
         out = empty_like(x)
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
+    check(lib.sisic_ddpm_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
     return out
 
@@ -316,7 +398,7 @@ def noise_bits(seeds, n_per_image: int, step: int, tag: int = 0, device="cuda") 
 
 
 def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
-                  out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``ddpm_step`` with z generated in the kernel: eps, x are [B, ...] (or flat with B = len(seeds) equal images);
     image b draws ``noise_fill([seeds[b]], n_per_image, step)``."""
     lib = _lib.load()
@@ -328,21 +410,21 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+    check(lib.sisic_ddpm_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
     return out
 
 
 def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
               use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None,
-              prediction_type: str = "epsilon") -> torch.Tensor:
+              prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_ddim_step: coef = (sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma), a row of
     ``HipDDIMScheduler.coefficient_table``.  z None or sigma == 0: no noise is added."""
     lib = _lib.load()
     if out is None:
         out = empty_like(x)
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
+    check(lib.sisic_ddim_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
                               x.numel(), sb, sa, c_prev, c_dir, sigma, float(clip), int(bool(use_clipped_model_output)),
                               _stream(x.device)))
     return out
@@ -350,7 +432,7 @@ def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
 
 def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
                   use_clipped_model_output: bool = False, out: Optional[torch.Tensor] = None,
-                  prediction_type: str = "epsilon") -> torch.Tensor:
+                  prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``ddim_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
     lib = _lib.load()
@@ -362,14 +444,14 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
+    check(lib.sisic_ddim_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
                                   seeds_dev.data_ptr(), int(step), sb, sa, c_prev, c_dir, sigma, float(clip),
                                   int(bool(use_clipped_model_output)), _stream(x.device)))
     return out
 
 
 def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hist: torch.Tensor, coef, clip: float = 0.0,
-               out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_dpmpp_step: coef = (sigma_t, alpha_t, cx, k0, sigma, k1), a row of
     ``HipDPMSolverMultistepScheduler.coefficient_table``.  hist: the previous step's x0, a tensor of x's size that the
     call overwrites with this step's x0 and reads only when k1 != 0.  z None or sigma == 0: no noise is added."""
@@ -379,13 +461,13 @@ def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hi
     if out is None:
         out = empty_like(x)
     sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
+    check(lib.sisic_dpmpp_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
                                _ptr(out, "out"), x.numel(), sb, sa, cx, k0, sigma, k1, float(clip), _stream(x.device)))
     return out
 
 
 def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, clip: float = 0.0,
-                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``dpmpp_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
     lib = _lib.load()
@@ -399,13 +481,14 @@ def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: t
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step_rng(context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
+    check(lib.sisic_dpmpp_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
                                    x.numel() // B, seeds_dev.data_ptr(), int(step), sb, sa, cx, k0, sigma, k1, float(clip),
                                    _stream(x.device)))
     return out
 
 
-def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out, prediction_type="epsilon"):
+def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out, prediction_type="epsilon",
+               threshold=None):
     """the three ``*_step_edit`` wrappers: the ``_rng`` wrapper's arguments, the known image, the mask and the edit row"""
     lib = _lib.load()
     arr = _seed_array(seeds)
@@ -424,7 +507,7 @@ def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask
         out = empty_like(x)
     seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
     ck, sk, ja, jb = (float(v) for v in erow)
-    args = [context(x.device, prediction_type), _ptr(eps, "eps"), _ptr(x, "x")]
+    args = [_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x")]
     if hist is not None:
         args.append(_ptr(hist, "hist"))
     args += [_ptr(out, "out"), B, npi, seeds_dev.data_ptr(), int(step), *(float(v) for v in row), float(clip)]
@@ -436,33 +519,33 @@ def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask
 
 
 def ddpm_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
-                   clip: float = 1.0, out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+                   clip: float = 1.0, out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_ddpm_step_edit: ``ddpm_step_rng`` with the inpainting epilogue (include/sisic.h) fused into the kernel.
     x0k: the known image, fp32 of x's size, finite; mask: fp32 [B,1,H,W] (1 = keep); erow = (ck, sk, ja, jb).  The epilogue
     draws under tags 5 (``sk != 0``) and 6 (``jb != 0``) of ``noise_fill`` at the same ``step``."""
     if len(tuple(coef)) != 5:
         raise ValueError("a DDPM row holds 5 values")
-    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out, prediction_type)
+    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out, prediction_type, threshold)
 
 
 def ddim_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
                    clip: float = 1.0, use_clipped_model_output: bool = False,
-                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon") -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_ddim_step_edit: ``ddim_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``."""
     if len(tuple(coef)) != 5:
         raise ValueError("a DDIM row holds 5 values")
     return _step_edit("sisic_ddim_step_edit", eps, x, seeds, step, None, coef, use_clipped_model_output, clip, x0k, mask, erow,
-                      out, prediction_type)
+                      out, prediction_type, threshold)
 
 
 def dpmpp_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, x0k: torch.Tensor,
                     mask: torch.Tensor, erow, clip: float = 0.0, out: Optional[torch.Tensor] = None,
-                    prediction_type: str = "epsilon") -> torch.Tensor:
+                    prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_dpmpp_step_edit: ``dpmpp_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``; ``hist`` receives the
     model's predicted x0, which the epilogue does not touch."""
     if len(tuple(coef)) != 6:
         raise ValueError("a DPM-Solver++ row holds 6 values")
-    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out, prediction_type)
+    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out, prediction_type, threshold)
 
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,

@@ -396,6 +396,7 @@ class SampleResult:
     prediction_type: str = "epsilon"           # what the model's output meant to the step rule (the model's own property)
     classifier_scale: Optional[float] = None   # classifier guidance: its scale (None: the run had none) ...
     classifier_passes: int = 0                 # ... and the classifier's gradient walks, one per UNet pass
+    thresholding: Optional[Tuple[float, float]] = None   # dynamic thresholding of x0: (ratio, sample_max_value), or None
 
 
 def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence[int]]):
@@ -412,14 +413,51 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
     return kept, rows
 
 
+def check_thresholding(thresholding, dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0):
+    """the three published thresholding arguments as ``(ratio, sample_max_value)`` or None (off); ValueError for a ratio
+    outside (0, 1] or a maximum below 1 -- before anything touches the GPU"""
+    if not thresholding:
+        return None
+    ratio, max_value = ops.check_threshold((dynamic_thresholding_ratio, sample_max_value))
+    if ratio == 0.0:
+        raise ValueError("dynamic_thresholding_ratio 0 with thresholding=True: the library reads ratio 0 as 'off'")
+    return ratio, max_value
+
+
 @torch.no_grad()
-def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
-                      noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
-                      cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
-                      use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
-                      edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS,
-                      classifier: Optional[ClassifierGuidance] = None) -> SampleResult:
-    """classifier: classifier guidance (``ClassifierGuidance``) of an unconditional epsilon-prediction model; needs a
+def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, *, thresholding: Optional[bool] = None,
+                      dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, **kwargs) -> SampleResult:
+    """``_run_sampling_loop`` (whose keyword arguments these are) under dynamic thresholding of x0:
+    ``thresholding`` True with its two published companions, False, or None (the default) for what the scheduler object was
+    set to (its constructor or ``set_thresholding``).  The model's handle is set from them on EVERY call, on or off, so no
+    setting outlives the call that made it; under thresholding the scheduler's ``clip_sample`` is not read.  ``SampleResult.thresholding`` records (ratio, max) or
+    None."""
+    if thresholding is None:
+        threshold = getattr(scheduler, "threshold", None)
+    else:
+        threshold = check_thresholding(thresholding, dynamic_thresholding_ratio, sample_max_value)
+    if threshold is not None and x_T[0].numel() > ops.THRESHOLD_MAX_PER_IMAGE:
+        raise ValueError(f"thresholding takes images of at most 2**24 elements, these have {x_T[0].numel()}")
+    res = _run_sampling_loop(model, scheduler, x_T, noise, threshold=threshold, **kwargs)
+    res.thresholding = threshold
+    return res
+
+
+def _set_thresholding(lib, model: HipUNet2DModel, threshold) -> None:
+    """the handle's thresholding setting of the call about to run: (ratio, max), or off"""
+    ratio, max_value = threshold if threshold is not None else (0.0, 1.0)
+    check(lib.sisic_unet_set_thresholding(model.handle, ratio, max_value))
+
+
+@torch.no_grad()
+def _run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
+                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
+                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
+                       use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
+                       edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS,
+                       classifier: Optional[ClassifierGuidance] = None, threshold=None) -> SampleResult:
+    """threshold: (ratio, sample_max_value) of dynamic thresholding or None, as ``run_sampling_loop`` resolved it.
+    classifier: classifier guidance (``ClassifierGuidance``) of an unconditional epsilon-prediction model; needs a
     ``DeviceNoise`` and composes with neither ``guidance`` nor ``edit``.
     edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
     The run has one step per entry of ``edit.schedule`` (``timesteps``, ``steps_done``, the trajectory and ``save_indices``
@@ -439,19 +477,20 @@ def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
     if edit is not None:
         _check_guidance(model, guidance, x_T.shape[0])
         return _run_edited(model, scheduler, x_T, noise, edit, return_trajectory, save_indices, cancel_flag, eta,
-                           use_clipped_model_output, guidance, max_call_steps)
+                           use_clipped_model_output, guidance, max_call_steps, threshold)
     if isinstance(noise, NoiseStream):
         if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":
             raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
                              "noise buffer, a DeviceNoise or None")
         _check_guidance(model, guidance, x_T.shape[0])
         return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices, eta,
-                             use_clipped_model_output, guidance)
+                             use_clipped_model_output, guidance, threshold)
     _check_guidance(model, guidance, x_T.shape[0])
     lib = _lib.load()
     dev = x_T.device
     if dev.type != "cuda":
         raise RuntimeError("the sampling loop runs on MI355X only")
+    _set_thresholding(lib, model, threshold)
     B, Cc, H, W = x_T.shape
     ts = scheduler.timesteps.to(torch.int64).contiguous()
     T = ts.numel()
@@ -541,7 +580,8 @@ def check_edit_schedule(rule: str, schedule, T: int) -> List[Tuple[int, int]]:
 
 def _run_edited(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, edit: Edit, return_trajectory: bool,
                 save_indices: Optional[Sequence[int]], cancel_flag: Optional[C.c_int], eta: float,
-                use_clipped_model_output: bool, guidance: Optional[Guidance], max_call_steps: int) -> SampleResult:
+                use_clipped_model_output: bool, guidance: Optional[Guidance], max_call_steps: int,
+                threshold=None) -> SampleResult:
     """run_sampling_loop under an ``Edit``: the rule's rows, the timesteps and the edit rows of the expanded schedule, then
     sisic_sample_frames_edit, in calls of at most ``max_call_steps`` passes"""
     if not isinstance(noise, DeviceNoise):
@@ -551,6 +591,7 @@ def _run_edited(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, edit
     dev = x_T.device
     if dev.type != "cuda":
         raise RuntimeError("the sampling loop runs on MI355X only")
+    _set_thresholding(lib, model, threshold)
     B, Cc, H, W = x_T.shape
     if len(noise.seeds) != B:
         raise ValueError(f"DeviceNoise holds {len(noise.seeds)} seeds for a batch of {B}")
@@ -633,9 +674,10 @@ def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
 def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: NoiseStream,
                   return_trajectory: bool, cancel_flag: Optional[C.c_int],
                   save_indices: Optional[Sequence[int]] = None, eta: float = 0.0,
-                  use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None) -> SampleResult:
+                  use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None, threshold=None) -> SampleResult:
     lib = _lib.load()
     dev = x_T.device
+    _set_thresholding(lib, model, threshold)
     B, Cc, H, W = x_T.shape
     ts = scheduler.timesteps.to(torch.int64).contiguous()
     T = ts.numel()
@@ -960,8 +1002,14 @@ class Sampler:
                        use_clipped_model_output: bool = False, solver_order: int = 2,
                        algorithm_type: str = "dpmsolver++", guidance_scale: float = 1.0, init_image=None, mask=None,
                        strength: float = 1.0, jump_length: int = 10, n_resample: int = 1,
-                       max_call_steps: int = MAX_CALL_STEPS, classifier_scale: Optional[float] = None) -> SampleResult:
-        """classifier_scale: classifier guidance (Dhariwal & Nichol 2021) of an unconditional epsilon-prediction model with the
+                       max_call_steps: int = MAX_CALL_STEPS, classifier_scale: Optional[float] = None,
+                       thresholding: bool = False, dynamic_thresholding_ratio: float = 0.995,
+                       sample_max_value: float = 1.0) -> SampleResult:
+        """thresholding, dynamic_thresholding_ratio, sample_max_value: dynamic thresholding of x0 (Saharia et al. 2022), the
+        published schedulers' arguments of these names: per image and step, s = the ``ratio`` quantile of |x0| clamped to
+        [1, ``sample_max_value``], and x0 becomes clamp(x0, -s, s) / s in place of the static clamp.  Every rule, both noise modes,
+        every guidance and edit.  Off (the default) is today's run; the result records ``thresholding``.
+        classifier_scale: classifier guidance (Dhariwal & Nichol 2021) of an unconditional epsilon-prediction model with the
         classifier of ``set_classifier``: every step applies its rule to ``eps - (scale * sqrt(1 - abar_t)) * g``, ``g`` the
         classifier's input gradient towards image b's class at the step's latent.  ``class_name`` may then be a sequence with one
         name per image, all registered to one model (``sampler.models[name]`` is the same object); the names choose the targets
@@ -996,7 +1044,10 @@ class Sampler:
         check_edit_options(scheduler, noise, init_image is not None, mask is not None, strength, jump_length, n_resample)
         model, names, guidance = self._resolve_classes(class_name, len(seeds), guidance_scale, classifier_scale is not None)
         sched = self.create_scheduler(T, scheduler, solver_order, algorithm_type)
-        rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output, guidance=guidance)
+        check_thresholding(thresholding, dynamic_thresholding_ratio, sample_max_value)
+        rule_args = dict(eta=eta, use_clipped_model_output=use_clipped_model_output, guidance=guidance,
+                         thresholding=bool(thresholding), dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                         sample_max_value=sample_max_value)
         if classifier_scale is not None:
             rule_args["classifier"] = self._classifier_guidance(names, model, classifier_scale, noise, guidance_scale,
                                                                 init_image is not None or mask is not None)
@@ -1067,7 +1118,8 @@ class Sampler:
                  save_every_n: Optional[int] = None, noise: str = "host", scheduler: str = "ddpm", eta: float = 0.0,
                  use_clipped_model_output: bool = False, solver_order: int = 2, algorithm_type: str = "dpmsolver++",
                  guidance_scale: float = 1.0, init_image=None, mask=None, strength: float = 1.0, jump_length: int = 10,
-                 n_resample: int = 1, classifier_scale: Optional[float] = None):
+                 n_resample: int = 1, classifier_scale: Optional[float] = None, thresholding: bool = False,
+                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0):
         """``generate(seed, class, T)``: returns (uint8 [count,H,W,3] numpy, trajectory list | None).
 
         save_every_n: with return_trajectory, the list holds only the frames of ``trajectory_save_indices`` (every n-th
@@ -1082,6 +1134,7 @@ class Sampler:
         scheduler, eta, use_clipped_model_output, solver_order, algorithm_type: the step rule, as in ``generate_seeds``.
         init_image, mask, strength, jump_length, n_resample: image-to-image and inpainting, as in ``generate_seeds``.
         classifier_scale: classifier guidance, as in ``generate_seeds``.
+        thresholding, dynamic_thresholding_ratio, sample_max_value: dynamic thresholding of x0, as in ``generate_seeds``.
         class_name, guidance_scale: as in ``generate_seeds``; a sequence of names gives one image per name (``count`` must be 1
         or its length), and with seed_is_base image i derives its seed from ITS class name.
         Always returns a tuple (the reference's bare ``return False`` on early exit is a latent bug).
@@ -1102,7 +1155,8 @@ class Sampler:
                                    use_clipped_model_output=use_clipped_model_output, solver_order=solver_order,
                                    algorithm_type=algorithm_type, guidance_scale=guidance_scale, init_image=init_image,
                                    mask=mask, strength=strength, jump_length=jump_length, n_resample=n_resample,
-                                   classifier_scale=classifier_scale)
+                                   classifier_scale=classifier_scale, thresholding=thresholding,
+                                   dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value)
         self.last_trajectory_steps = list(res.trajectory_steps)
         n_frames = sum(1 for i in res.trajectory_steps if i < res.steps_done)       # kept frames of the completed steps
         if res.cancelled:

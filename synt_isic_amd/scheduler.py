@@ -45,6 +45,38 @@ def _betas_for_alpha_bar(n: int, max_beta: float = 0.999) -> torch.Tensor:
                         dtype=torch.float32)
 
 
+def _threshold_of(thresholding: bool, dynamic_thresholding_ratio: float, sample_max_value: float):
+    """the three published thresholding arguments as the ``threshold`` of the step wrappers: None, or a checked (ratio, max).
+    The published classes hand ratio 0 to torch.quantile; here it is refused with the rest, because ratio 0 is how the library
+    spells "off"."""
+    if not thresholding:
+        return None
+    ratio, max_value = ops.check_threshold((dynamic_thresholding_ratio, sample_max_value))
+    if ratio == 0.0:
+        raise ValueError("dynamic_thresholding_ratio 0 with thresholding=True: the library reads ratio 0 as 'off'")
+    return ratio, max_value
+
+
+_THRESHOLD_ARGS = {"thresholding", "dynamic_thresholding_ratio", "sample_max_value"}
+_THRESHOLD_HINT = " (dynamic thresholding: call set_thresholding() on the scheduler)"
+
+
+def _set_thresholding(self, thresholding: bool = True, dynamic_thresholding_ratio: float = 0.995,
+                      sample_max_value: float = 1.0) -> None:
+    """Dynamic thresholding of x0 (Saharia et al. 2022) for this scheduler's ``step`` and for ``run_sampling_loop``: the
+    published ``thresholding``, ``dynamic_thresholding_ratio`` and ``sample_max_value``, kept in ``self.threshold`` as (ratio, max)
+    or None (and in ``config`` where the constructor takes them).  It takes
+    precedence over ``clip_sample``.  ``HipDDPMScheduler`` also takes the three in its constructor; the constructors of the
+    DDIM and DPM-Solver++ mirrors keep refusing them, as they always have, and this method is their way in.  ValueError for a
+    ratio outside (0, 1] or a maximum below 1."""
+    self.threshold = _threshold_of(thresholding, dynamic_thresholding_ratio, sample_max_value)
+    # (config holds what the constructor takes, so that cls(**vars(config)) builds the scheduler again: the DDPM mirror's does)
+    if hasattr(self.config, "thresholding"):
+        self.config.thresholding = bool(thresholding)
+        self.config.dynamic_thresholding_ratio = dynamic_thresholding_ratio
+        self.config.sample_max_value = sample_max_value
+
+
 class HipDDPMScheduler:
     order = 1
     rule = "ddpm"            # the step rule ``run_sampling_loop`` runs this scheduler's table under
@@ -52,9 +84,11 @@ class HipDDPMScheduler:
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = True,
                  prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
-                 timestep_spacing: str = "leading", steps_offset: int = 0, **unsupported):
+                 timestep_spacing: str = "leading", steps_offset: int = 0, thresholding: bool = False,
+                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, **unsupported):
         if unsupported:
             raise NotImplementedError(f"unsupported DDPMScheduler arguments: {sorted(unsupported)}")
+        self.threshold = _threshold_of(thresholding, dynamic_thresholding_ratio, sample_max_value)
         if prediction_type != "epsilon":
             raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
         if variance_type != "fixed_small":
@@ -71,13 +105,17 @@ class HipDDPMScheduler:
                                       beta_end=beta_end, beta_schedule=beta_schedule, variance_type=variance_type,
                                       clip_sample=clip_sample, prediction_type=prediction_type,
                                       clip_sample_range=clip_sample_range, timestep_spacing=timestep_spacing,
-                                      steps_offset=steps_offset)
+                                      steps_offset=steps_offset, thresholding=thresholding,
+                                      dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                                      sample_max_value=sample_max_value)
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.one = torch.tensor(1.0)
         self.init_noise_sigma = 1.0
         self.num_inference_steps: Optional[int] = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+
+    set_thresholding = _set_thresholding
 
     def __len__(self) -> int:
         return self.config.num_train_timesteps
@@ -146,7 +184,7 @@ class HipDDPMScheduler:
                 z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         prev = ops.ddpm_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z,
-                             coef, clip, prediction_type=prediction_type)
+                             coef, clip, prediction_type=prediction_type, threshold=self.threshold)
         if not return_dict:
             return (prev,)
         return DDPMSchedulerOutput(prev_sample=prev)
@@ -229,7 +267,9 @@ class HipDDIMScheduler:
                  steps_offset: int = 0, prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
                  timestep_spacing: str = "leading", **unsupported):
         if unsupported:
-            raise NotImplementedError(f"unsupported DDIMScheduler arguments: {sorted(unsupported)}")
+            raise NotImplementedError(f"unsupported DDIMScheduler arguments: {sorted(unsupported)}"
+                                      + _THRESHOLD_HINT * bool(_THRESHOLD_ARGS & set(unsupported)))
+        self.threshold = None
         if prediction_type != "epsilon":
             raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
         if timestep_spacing not in ("leading", "trailing"):
@@ -252,6 +292,7 @@ class HipDDIMScheduler:
         self.num_inference_steps: Optional[int] = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
 
+    set_thresholding = _set_thresholding
     # the forward process does not depend on the sampling rule
     __len__ = HipDDPMScheduler.__len__
     scale_model_input = HipDDPMScheduler.scale_model_input
@@ -317,7 +358,7 @@ class HipDDIMScheduler:
                 z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         prev = ops.ddim_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z, coef, clip,
-                             use_clipped_model_output, prediction_type=prediction_type)
+                             use_clipped_model_output, prediction_type=prediction_type, threshold=self.threshold)
         if not return_dict:
             return (prev,)
         return DDIMSchedulerOutput(prev_sample=prev)
@@ -388,8 +429,9 @@ class HipDPMSolverMultistepScheduler:
     ``step`` is stateful: the object keeps the previous step's predicted x0 and the step index, and ``set_timesteps`` resets
     both.  ``timestep_spacing``: "linspace" (the published default, from t = N - 1), "trailing", or "leading" -- the grid of
     the project's DDPM and DDIM mirrors, so that the three rules can run on one grid.  ``clip_sample`` /
-    ``clip_sample_range`` are extensions of this project (the published class has ``thresholding``
-    instead): the clamp of x0 the other two mirrors apply, off by default."""
+    ``clip_sample_range`` are extensions of this project: the static clamp of x0 the other two mirrors apply, off by
+    default.  The published class's ``thresholding`` is offered through ``set_thresholding`` (the constructor keeps
+    refusing the argument, as it always has); under it ``clip_sample`` is not read."""
     order = 1
     rule = "dpmsolver++"
 
@@ -399,7 +441,9 @@ class HipDPMSolverMultistepScheduler:
                  final_sigmas_type: str = "zero", timestep_spacing: str = "linspace", steps_offset: int = 0,
                  clip_sample: bool = False, clip_sample_range: float = 1.0, **unsupported):
         if unsupported:
-            raise NotImplementedError(f"unsupported DPMSolverMultistepScheduler arguments: {sorted(unsupported)}")
+            raise NotImplementedError(f"unsupported DPMSolverMultistepScheduler arguments: {sorted(unsupported)}"
+                                      + _THRESHOLD_HINT * bool(_THRESHOLD_ARGS & set(unsupported)))
+        self.threshold = None
         if prediction_type != "epsilon":
             raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
         check_dpmpp_options(solver_order, algorithm_type)
@@ -430,6 +474,7 @@ class HipDPMSolverMultistepScheduler:
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
         self._reset()
 
+    set_thresholding = _set_thresholding
     __len__ = HipDDPMScheduler.__len__
     scale_model_input = HipDDPMScheduler.scale_model_input
     add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
@@ -509,7 +554,7 @@ class HipDPMSolverMultistepScheduler:
                 z = torch.randn(model_output.shape, generator=generator, device=x.device, dtype=torch.float32)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, clip,
-                              prediction_type=prediction_type)
+                              prediction_type=prediction_type, threshold=self.threshold)
         self._step_index = i + 1
         if not return_dict:
             return (prev,)
