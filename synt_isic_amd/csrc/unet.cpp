@@ -976,121 +976,110 @@ static int loop_step(sisic_unet* u, const LoopCall& c, size_t n, hipStream_t s) 
     return launch_loop_advance(u->ctx, state, s);
 }
 
-// The loop as ONE captured step replayed T-1 times (hipGraph): at batch 1 a step is ~190 launches of 5-20 us kernels and
-// the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
+// Step i of the eager form on the latent xs: the UNet pass under the step's own embedding rows, the classifier's walk of a
+// classifier-guided call, then the step kernel with the host row and the next unused noise row (*zi counts them).
+static int eager_step(sisic_unet* u, const LoopCall& c, float* xs, size_t n, hipStream_t s, int i, size_t* zi) {
+    if (c.cg) {
+        SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, nullptr, i, u->cond_tables, c.cg->rows, u->tproj_cur, s));
+        SISIC_TRY(unet_run_forward(u, xs, u->tproj_cur, u->tproj_R, u->eps_buf, c.cg->rows, c.H, c.W, s));
+    } else {
+        SISIC_TRY(unet_run_forward(u, xs, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, c.B, c.H, c.W, s));
+    }
+    const float* z = nullptr;
+    if (c.noise && c.coef[(size_t)i * SISIC_RULE_ROW_WIDTH(c.rule) + 4] != 0.0f) z = c.noise + ((*zi)++) * n;
+    if (c.cl)
+        SISIC_TRY(resnet_input_gradient_walk(c.cl->clf, xs, c.B, c.H, c.W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
+                                             u->clf_grad, nullptr, s));
+    return launch_step(u->ctx, loop_step_launch(u, c, xs, n, i, z), s);
+}
+
+// The replayed form: the loop as ONE captured step replayed T-1 times (hipGraph): at batch 1 a step is ~190 launches of 5-20 us
+// kernels and the host cannot issue them as fast as the GPU retires them (measured: 3.0 ms of kernels in a 4.5 ms step).
 // A call with seeds generates its noise from u->seeds_dev (already uploaded on the caller's stream) with step index step0 + i.
-static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
-    float* const x = c.x;
-    const int B = c.B, H = c.H, W = c.W, T = c.T, rule = c.rule, rule_flags = c.rule_flags, step0 = c.step0;
-    const float* const coef = c.coef;
-    const float* const noise = c.noise;
-    const float clip = c.clip;
+//
+// What it sets up before the loop: the stream the steps run on (*sp), the device tables of the call, the library's copies of an
+// edited call's image, mask and rows, and the call's latent in x_work (every address inside the graph is library-owned).
+static int replay_begin(sisic_unet* u, const LoopCall& c, size_t n, hipStream_t* sp) {
     const bool rng = c.seeds != nullptr;
-    const CondCall* const cg = c.cg;
-    const EditCall* const ed = c.ed;
-    const ClfCall* const cl = c.cl;
-    float* const traj = c.traj;
-    const int* const traj_row = c.traj_row;
-    const volatile int* const cancel = c.cancel;
-    int* const steps_done = c.steps_done;
-    const int C = u->cfg.in_channels;
-    const size_t n = (size_t)B * C * H * W;
-    const size_t cw = SISIC_RULE_ROW_WIDTH(rule);
-    SISIC_REQUIRE(T <= 1000, "sample: at most 1000 steps per call");
+    const size_t cw = SISIC_RULE_ROW_WIDTH(c.rule);
+    SISIC_REQUIRE(c.T <= 1000, "sample: at most 1000 steps per call");
     // the replayed launches write into the pool blocks they were captured with; a tape recorded since then may own some of
     // them: the tape does not survive a graph-replayed run (sisic_unet_backward then answers SISIC_ESTATE)
     unet_release_tape(u);
-    hipStream_t s = caller;
-    if (!s) {                              // the legacy default stream cannot be captured: a blocking stream of our own,
+    if (!*sp) {                            // the legacy default stream cannot be captured: a blocking stream of our own,
         if (!u->loop_stream) SISIC_HIP(hipStreamCreate(&u->loop_stream));     // implicitly ordered with the default stream
-        s = u->loop_stream;
+        *sp = u->loop_stream;
     }
-    const bool guided = cg && cg->guided;
+    hipStream_t s = *sp;
+    const bool guided = c.cg && c.cg->guided;
     // (a guided call keeps the latent twice, one copy per half of the batch the UNet runs; the step kernel writes both)
     SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, guided ? 2 * n : n));
-    SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)(cg ? cg->rows : 1) * u->tproj_R));
+    SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)(c.cg ? c.cg->rows : 1) * u->tproj_R));
     SISIC_TRY(unet_grow(&u->loop_tables, &u->loop_tables_cap, LOOP_TABLE_FLOATS));
     // tables of this call: {step = 0, step base, noise base}, coefficients, noise row per step (-1: the step adds no noise)
     std::vector<float> tab(LOOP_TABLE_FLOATS, 0.0f);
     {
-        const int first = 0, base = rng ? step0 : 0;
+        const int first = 0, base = rng ? c.step0 : 0;
         std::memcpy(&tab[0], &first, sizeof(int));
         std::memcpy(&tab[1], &base, sizeof(int));
-        std::memcpy(&tab[2], &noise, sizeof(noise));
-        std::memcpy(&tab[4], coef, (size_t)T * cw * sizeof(float));
+        std::memcpy(&tab[2], &c.noise, sizeof(c.noise));
+        std::memcpy(&tab[4], c.coef, (size_t)c.T * cw * sizeof(float));
         int* zr = reinterpret_cast<int*>(&tab[4 + LOOP_COEF_FLOATS]);
         int zi = 0;
-        for (int i = 0; i < T; ++i) zr[i] = (noise && coef[(size_t)i * cw + 4] != 0.0f) ? zi++ : -1;
+        for (int i = 0; i < c.T; ++i) zr[i] = (c.noise && c.coef[(size_t)i * cw + 4] != 0.0f) ? zi++ : -1;
     }
     SISIC_TRY(unet_stage_upload(u, tab.data(), tab.size(), u->loop_tables, s));
-    if (ed) {
-        const size_t nm = (size_t)B * H * W;
+    if (c.ed) {
+        const size_t nm = (size_t)c.B * c.H * c.W;
         SISIC_TRY(unet_grow(&u->edit_x0k, &u->edit_x0k_cap, n));
         SISIC_TRY(unet_grow(&u->edit_mask, &u->edit_mask_cap, nm));
         SISIC_TRY(unet_grow(&u->edit_rows, &u->edit_rows_cap, LOOP_EDIT_FLOATS));
-        SISIC_HIP(hipMemcpyAsync(u->edit_x0k, ed->x0k, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SISIC_HIP(hipMemcpyAsync(u->edit_mask, ed->mask, nm * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SISIC_TRY(unet_stage_upload(u, ed->rows, (size_t)T * 4, u->edit_rows, s));
+        SISIC_HIP(hipMemcpyAsync(u->edit_x0k, c.ed->x0k, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SISIC_HIP(hipMemcpyAsync(u->edit_mask, c.ed->mask, nm * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SISIC_TRY(unet_stage_upload(u, c.ed->rows, (size_t)c.T * 4, u->edit_rows, s));
     }
-    SISIC_HIP(hipMemcpyAsync(u->x_work, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (guided) SISIC_HIP(hipMemcpyAsync(u->x_work + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(u->x_work, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (guided) SISIC_HIP(hipMemcpyAsync(u->x_work + n, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return SISIC_OK;
+}
 
-    auto after_step = [&](int i) -> int {
-        const int row = traj_row ? traj_row[i] : i;          // (kept frames only: XAI.py:751-757 save_indices)
-        if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, u->x_work, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (steps_done) *steps_done = i + 1;
-        return SISIC_OK;
-    };
-    int rc = SISIC_OK;
-    int i = 0;
-    auto cancelled = [&](int at) -> bool {
-        if (!cancel) return false;
-        if ((at & 7) == 0) (void)hipStreamSynchronize(s);
-        return *cancel != 0;
-    };
-    if (cancelled(0)) rc = SISIC_ECANCEL;
-    const void* hist = rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr;      // sized by sample_frames before this call
+// The key of the captured step that the call (u, c) on stream s replays (unet_internal.h says why each field is there), from the
+// handle as it stands: read before step 0 and again behind it, because the eager step sizes the pool and the scratch buffers.
+static sisic_unet::LoopKey loop_key_of(const sisic_unet* u, const LoopCall& c, hipStream_t s) {
+    sisic_unet::LoopKey k;
+    k.B = c.B; k.H = c.H; k.W = c.W; k.clip = c.clip; k.s = s; k.latency = u->latency_mode;
+    k.gen = u->ctx->scratch_generation.load();
     // every address baked into the captured launches: the pool and the scratch buffers are sized by the first eager step at a
-    // shape, the tables by ensure_rows / grow above
+    // shape, the tables by ensure_rows / grow, hist_buf and thr_s by sample_frames before the loop
+    const void* ptrs[] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur,
+                          c.rule == STEP_RULE_DPMPP ? u->hist_buf : nullptr, c.cg ? u->cond_tables : nullptr,
+                          c.ed ? u->edit_x0k : nullptr, c.ed ? u->edit_mask : nullptr, c.ed ? u->edit_rows : nullptr,
+                          c.cl ? u->clf_grad : nullptr, c.cl ? u->clf_tables : nullptr, u->thr_ratio > 0.0f ? u->thr_s : nullptr};
+    static_assert(sizeof(ptrs) == sizeof(k.ptrs), "LoopKey::ptrs holds every address of the list");
+    std::copy(std::begin(ptrs), std::end(ptrs), k.ptrs);
     // (labels and the guidance scale live in cond_tables and change nothing a captured launch holds; whether the call is
     //  conditional, and whether it is guided, change the launches themselves)
-    const void* cond_tab = cg ? u->cond_tables : nullptr;
-    const bool edit = ed != nullptr;
-    const void* ex = edit ? u->edit_x0k : nullptr;
-    const void* em = edit ? u->edit_mask : nullptr;
-    const void* er = edit ? u->edit_rows : nullptr;
+    k.cond = c.cg != nullptr; k.guided = c.cg && c.cg->guided; k.edit = c.ed != nullptr;
+    k.thr_ratio = u->thr_ratio; k.thr_max = u->thr_max;
     // (a classifier-guided call: targets and scale live in clf_tables; the classifier's own blocks and weight buffers are
-    //  covered by the generation of its workspace, read again after the eager step has sized them)
-    const void* cgr = cl ? u->clf_grad : nullptr;
-    const void* ctab = cl ? u->clf_tables : nullptr;
-    const void* clf_handle = cl ? cl->clf : nullptr;
-    const void* thr = u->thr_ratio > 0.0f ? u->thr_s : nullptr;          // (sized by sample_frames before this call)
-    auto clf_gen = [&]() -> uint64_t { return cl ? resnet_workspace_generation(cl->clf) : 0; };
-    auto reusable = [&]() -> bool {
-        const uint64_t gen = u->ctx->scratch_generation.load();
-        const void* ptrs[13] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab, thr};
-        bool ok = u->loop_valid && u->loop_key.B == B && u->loop_key.H == H && u->loop_key.W == W &&
-                  u->loop_key.clip == clip && u->loop_key.s == s && u->loop_key.latency == u->latency_mode &&
-                  u->loop_key.gen == gen && u->loop_key.rng == rng && (!rng || u->loop_key.seeds == u->seeds_dev) &&
-                  u->loop_key.rule == rule && u->loop_key.rule_flags == rule_flags && u->loop_key.cond == (cg != nullptr) &&
-                  u->loop_key.guided == guided && u->loop_key.edit == edit && u->loop_key.clf == (cl != nullptr) &&
-                  u->loop_key.clf_handle == clf_handle && u->loop_key.clf_gen == clf_gen() &&
-                  u->loop_key.thr_ratio == u->thr_ratio && u->loop_key.thr_max == u->thr_max;
-        for (int k = 0; k < 13; ++k) ok = ok && u->loop_key.ptrs[k] == ptrs[k];
-        return ok;
-    };
-    if (rc == SISIC_OK && !reusable()) {
-        // step 0 eagerly: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes.  (A call that finds
-        // its graph -- every call after the first at a shape -- replays from step 0: the eager step is ~190 launches, twice
-        // the time of a replayed one at batch 1.)
-        rc = loop_step(u, c, n, s);
-        if (rc == SISIC_OK) rc = after_step(0);
-        i = 1;
-    }
-    if (rc == SISIC_OK && i < T) {
-        if (!reusable()) {
-            const uint64_t gen = u->ctx->scratch_generation.load();
-            const void* ptrs[13] = {u->tproj, u->eps_buf, u->x_work, u->loop_tables, u->tproj_cur, hist, cond_tab, ex, em, er, cgr, ctab, thr};
+    //  covered by the generation of its workspace)
+    k.clf = c.cl != nullptr;
+    k.clf_handle = c.cl ? c.cl->clf : nullptr;
+    k.clf_gen = c.cl ? resnet_workspace_generation(c.cl->clf) : 0;
+    k.rng = c.seeds != nullptr;
+    k.seeds = k.rng ? u->seeds_dev : nullptr;
+    k.rule = c.rule; k.rule_flags = c.rule_flags;
+    return k;
+}
+
+// Step i of the replayed form.  Until the call has its graph (*ready): a call that finds it replays from step 0; one that does
+// not runs step 0 eagerly (loop_step: sizes the pool and every scratch buffer, opts the kernels in to their LDS sizes -- ~190
+// launches, twice the time of a replayed step at batch 1) and captures before its first replay.
+static int replay_step(sisic_unet* u, const LoopCall& c, size_t n, hipStream_t s, int i, bool* ready) {
+    if (!*ready) {
+        const sisic_unet::LoopKey want = loop_key_of(u, c, s);
+        if (!(u->loop_valid && want == u->loop_key)) {
+            if (i == 0) return loop_step(u, c, n, s);
             loop_graph_drop(u);
             SISIC_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
             const int crc = loop_step(u, c, n, s);
@@ -1103,36 +1092,14 @@ static int sample_graph(sisic_unet* u, const LoopCall& c, hipStream_t caller) {
             }
             u->loop_graph = g;
             SISIC_HIP(hipGraphInstantiate(&u->loop_exec, g, nullptr, nullptr, 0));
-            u->loop_key.B = B; u->loop_key.H = H; u->loop_key.W = W; u->loop_key.clip = clip; u->loop_key.s = s;
-            u->loop_key.latency = u->latency_mode; u->loop_key.gen = gen;
-            u->loop_key.rng = rng; u->loop_key.seeds = u->seeds_dev;
-            u->loop_key.rule = rule; u->loop_key.rule_flags = rule_flags;
-            u->loop_key.cond = cg != nullptr; u->loop_key.guided = guided; u->loop_key.edit = edit;
-            u->loop_key.clf = cl != nullptr; u->loop_key.clf_handle = clf_handle; u->loop_key.clf_gen = clf_gen();
-            u->loop_key.thr_ratio = u->thr_ratio; u->loop_key.thr_max = u->thr_max;
-            for (int k = 0; k < 13; ++k) u->loop_key.ptrs[k] = ptrs[k];
+            u->loop_key = want;
             u->loop_valid = true;
             u->loop_builds += 1;
         }
-        for (; i < T; ++i) {
-            if (cancelled(i)) { rc = SISIC_ECANCEL; break; }
-            SISIC_HIP(hipGraphLaunch(u->loop_exec, s));
-            SISIC_TRY(after_step(i));
-        }
+        *ready = true;
     }
-    SISIC_HIP(hipMemcpyAsync(x, u->x_work, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (s != caller) SISIC_HIP(hipStreamSynchronize(s));      // hand the result back to the default stream's order
-    if (rc == SISIC_ECANCEL) {
-        SISIC_HIP(hipStreamSynchronize(s));
-        set_error("sample: cancelled after %d of %d steps", steps_done ? *steps_done : i, T);
-    }
-    return rc;
-}
-
-int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
-                 float clip, const float* noise, float* traj, uint8_t* out_u8, const volatile int* cancel,
-                 int* steps_done, void* stream) {
-    return sisic_sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, traj, nullptr, out_u8, cancel, steps_done, stream);
+    SISIC_HIP(hipGraphLaunch(u->loop_exec, s));
+    return SISIC_OK;
 }
 
 // The loop behind sisic_sample_frames[_rule] (noise: a buffer or NULL; seeds NULL) and sisic_sample_frames[_rule]_rng (seeds:
@@ -1140,71 +1107,59 @@ int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int6
 // step rule whose rows coef holds (SISIC_RULE_*).  labels: sisic_sample_frames_cond (host int64 [B], with null_label and the
 // guidance scale w), or nullptr for an unconditional handle.  (c: this function's own copy, which gains the prediction type in
 // its flags and the conditional call's rows.)
+//
+// One loop over the steps with two forms of "run step i": eager_step, today's launches with the host row, and replay_step, the
+// captured step.  Each form sets up what it needs before the loop; the poll of the stop flag, the trajectory copy, steps_done
+// and everything behind the loop are the same for both.
 static int sample_frames(sisic_unet* u, LoopCall c) {
-    float* const x = c.x;
-    const int B = c.B, H = c.H, W = c.W, T = c.T, rule = c.rule, step0 = c.step0, null_label = c.null_label;
-    int rule_flags = c.rule_flags;
-    const int64_t* const timesteps = c.timesteps;
-    const int64_t* const labels = c.labels;
-    const float* const coef = c.coef;
-    const float* const noise = c.noise;
-    const uint64_t* const seeds = c.seeds;
-    const float clip = c.clip, w = c.w;
-    const EditCall* const ed = c.ed;
-    const ClfCall* const cl = c.cl;
-    float* const traj = c.traj;
-    const int* const traj_row = c.traj_row;
-    uint8_t* const out_u8 = c.out_u8;
-    const volatile int* const cancel = c.cancel;
-    int* const steps_done = c.steps_done;
-    SISIC_REQUIRE(u && x && timesteps && coef && T > 0, "sample: null argument");
-    // a caller's flags are the rule's own; from here on rule_flags also carries the handle's prediction type in its private
+    SISIC_REQUIRE(u && c.x && c.timesteps && c.coef && c.T > 0, "sample: null argument");
+    const int B = c.B, H = c.H, W = c.W, T = c.T;
+    // a caller's flags are the rule's own; from here on c.rule_flags also carries the handle's prediction type in its private
     // bits, down to the launchers and into the key of a captured step
-    SISIC_REQUIRE((rule_flags & ~SISIC_RULE_FLAG_CLIPPED_OUTPUT) == 0, "sample: rule flags %d (SISIC_RULE_FLAG_CLIPPED_OUTPUT or 0)",
-                  rule_flags);
-    rule_flags |= step_pred_flags(u->pred_type);
-    c.rule_flags = rule_flags;
-    SISIC_TRY(unet_check_labels(u, labels ? "sample_cond" : "sample", labels != nullptr, labels, B));
-    SISIC_REQUIRE(!traj_row || traj, "sample: traj_row without a trajectory buffer");
-    if (traj_row)
-        for (int i = 0; i < T; ++i) SISIC_REQUIRE(traj_row[i] >= -1, "sample: traj_row[%d] = %d (a row of traj, or -1)", i, traj_row[i]);
+    SISIC_REQUIRE((c.rule_flags & ~SISIC_RULE_FLAG_CLIPPED_OUTPUT) == 0, "sample: rule flags %d (SISIC_RULE_FLAG_CLIPPED_OUTPUT or 0)",
+                  c.rule_flags);
+    c.rule_flags |= step_pred_flags(u->pred_type);
+    SISIC_TRY(unet_check_labels(u, c.labels ? "sample_cond" : "sample", c.labels != nullptr, c.labels, B));
+    SISIC_REQUIRE(!c.traj_row || c.traj, "sample: traj_row without a trajectory buffer");
+    if (c.traj_row)
+        for (int i = 0; i < T; ++i) SISIC_REQUIRE(c.traj_row[i] >= -1, "sample: traj_row[%d] = %d (a row of traj, or -1)", i, c.traj_row[i]);
     hipStream_t s = static_cast<hipStream_t>(c.stream);
-    if (steps_done) *steps_done = 0;
+    if (c.steps_done) *c.steps_done = 0;
     // the eager DDPM step checks its divisor launch by launch, as it always has; a rule chosen by the caller is checked for
     // the whole table before the first launch (the replayed step reads its row on the device and cannot refuse it)
-    const size_t cw = SISIC_RULE_ROW_WIDTH(rule);      // (an unknown rule is refused by check_step_row just below)
-    if (rule != STEP_RULE_DDPM || rule_flags != 0 || labels || ed || cl)
-        for (int i = 0; i < T; ++i) SISIC_TRY(check_step_row(rule, rule_flags, coef[(size_t)i * cw + 0], coef[(size_t)i * cw + 1]));
+    const size_t cw = SISIC_RULE_ROW_WIDTH(c.rule);      // (an unknown rule is refused by check_step_row just below)
+    if (c.rule != STEP_RULE_DDPM || c.rule_flags != 0 || c.labels || c.ed || c.cl)
+        for (int i = 0; i < T; ++i)
+            SISIC_TRY(check_step_row(c.rule, c.rule_flags, c.coef[(size_t)i * cw + 0], c.coef[(size_t)i * cw + 1]));
     // DPM-Solver++: a call starts with no history (the buffer holds whatever the last run left), so its first step cannot be
     // a second-order one.  A run cut into two calls therefore differs from the uncut run; callers run it in one call.
-    if (rule == STEP_RULE_DPMPP)
-        SISIC_REQUIRE(coef[5] == 0.0f, "sample: row 0 of a DPM-Solver++ call has k1 = %g (a call starts with no history)", coef[5]);
-    if (ed) {
+    if (c.rule == STEP_RULE_DPMPP)
+        SISIC_REQUIRE(c.coef[5] == 0.0f, "sample: row 0 of a DPM-Solver++ call has k1 = %g (a call starts with no history)", c.coef[5]);
+    if (c.ed) {
         // the replayed step reads its edit row on the device and cannot refuse it: the whole table is checked here
-        SISIC_REQUIRE(seeds && ed->x0k && ed->mask && ed->rows, "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
+        SISIC_REQUIRE(c.seeds && c.ed->x0k && c.ed->mask && c.ed->rows, "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
         SISIC_REQUIRE(T <= 1000, "sample_edit: at most 1000 steps per call");
         for (int i = 0; i < T; ++i) {
-            const float* r = ed->rows + 4 * (size_t)i;
+            const float* r = c.ed->rows + 4 * (size_t)i;
             SISIC_REQUIRE(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]),
                           "sample_edit: edit row %d is {%g, %g, %g, %g}", i, r[0], r[1], r[2], r[3]);
-            SISIC_REQUIRE(rule != STEP_RULE_DPMPP || r[3] == 0.0f,
+            SISIC_REQUIRE(c.rule != STEP_RULE_DPMPP || r[3] == 0.0f,
                           "sample_edit: edit row %d jumps (jb = %g) under DPM-Solver++: a jump invalidates the history", i, r[3]);
         }
     }
     // a conditional call: the distinct labels of the call (in order of first appearance, the null one last when guided) are the
     // slots of the embedding table; sample b of a pass reads the row of (step, slot[b])
     CondCall cc;
-    const CondCall* cg = nullptr;
     std::vector<int64_t> distinct;
     std::vector<int> slots;
-    if (labels) {
-        SISIC_REQUIRE(std::isfinite(w), "sample_cond: guidance_scale %g", (double)w);
-        cc.guided = w != 1.0f;
+    if (c.labels) {
+        SISIC_REQUIRE(std::isfinite(c.w), "sample_cond: guidance_scale %g", (double)c.w);
+        cc.guided = c.w != 1.0f;
         cc.rows = cc.guided ? 2 * B : B;
-        cc.w = w;
+        cc.w = c.w;
         SISIC_REQUIRE(cc.rows <= 65535, "sample_cond: batch %d", B);
         if (cc.guided)
-            SISIC_REQUIRE(null_label >= 0 && null_label < u->n_class, "sample_cond: null_label %d is outside [0, %d)", null_label, u->n_class);
+            SISIC_REQUIRE(c.null_label >= 0 && c.null_label < u->n_class, "sample_cond: null_label %d is outside [0, %d)", c.null_label, u->n_class);
         auto slot_of = [&](int64_t label) -> int {
             const auto it = std::find(distinct.begin(), distinct.end(), label);
             if (it != distinct.end()) return (int)(it - distinct.begin());
@@ -1212,13 +1167,13 @@ static int sample_frames(sisic_unet* u, LoopCall c) {
             return (int)distinct.size() - 1;
         };
         slots.resize(cc.rows);
-        for (int b = 0; b < B; ++b) slots[b] = slot_of(labels[b]);
-        for (int b = B; b < cc.rows; ++b) slots[b] = slot_of(null_label);
-        cg = &cc;
-        c.cg = cg;
+        for (int b = 0; b < B; ++b) slots[b] = slot_of(c.labels[b]);
+        for (int b = B; b < cc.rows; ++b) slots[b] = slot_of(c.null_label);
+        c.cg = &cc;
     }
-    const int rows = cg ? cg->rows : B;                          // samples per UNet pass
-    const size_t L = cg ? distinct.size() : 1;                   // embedding rows per step
+    const bool guided = c.cg && c.cg->guided;
+    const int rows = c.cg ? c.cg->rows : B;                      // samples per UNet pass
+    const size_t L = c.cg ? distinct.size() : 1;                 // embedding rows per step
     SISIC_TRY(unet_check_shape(u, rows, H, W));
     // per-step tables for 1000 rows from the first call on (17 MB): a longer run after a shorter one then never moves the
     // time-embedding table, so the captured step (which holds its address) survives a change of T (and, in a conditional
@@ -1228,32 +1183,31 @@ static int sample_frames(sisic_unet* u, LoopCall c) {
     SISIC_REQUIRE(u->cfg.out_channels == C, "sample: in/out channels differ");
     const size_t n = (size_t)B * C * H * W;
     SISIC_TRY(unet_grow(&u->eps_buf, &u->eps_floats, (size_t)rows * C * H * W));
-    if (rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
+    if (c.rule == STEP_RULE_DPMPP) SISIC_TRY(unet_grow(&u->hist_buf, &u->hist_cap, n));
     // dynamic thresholding: every image's s of the step, [B] (a guided call steps B images)
     if (u->thr_ratio > 0.0f) {
         SISIC_REQUIRE((size_t)C * H * W <= ((size_t)1 << 24), "sample: thresholding takes images of at most 2^24 elements, these have %zu",
                       (size_t)C * H * W);
         SISIC_TRY(unet_grow(&u->thr_s, &u->thr_s_cap, (size_t)std::max(B, 64)));
     }
-    const bool rng = seeds != nullptr;
-    if (cl) {
+    if (c.cl) {
         // the loop's device table of the call: {scale, -, -, -, int target[B]} (elementwise.hip, LoopClf)
         std::vector<float> ct(LOOP_CLF_HEAD + (size_t)B, 0.0f);
-        ct[0] = cl->scale;
+        ct[0] = c.cl->scale;
         for (int b = 0; b < B; ++b) {
-            const int t = (int)cl->targets[b];
+            const int t = (int)c.cl->targets[b];
             std::memcpy(&ct[LOOP_CLF_HEAD + b], &t, sizeof(int));
         }
         SISIC_TRY(unet_grow(&u->clf_tables, &u->clf_tables_cap, LOOP_CLF_HEAD + (size_t)std::max(B, 128)));
         SISIC_TRY(unet_stage_upload(u, ct.data(), ct.size(), u->clf_tables, s));
         SISIC_TRY(unet_grow(&u->clf_grad, &u->clf_grad_cap, n));
     }
-    if (rng) {
+    if (c.seeds) {
         // 2^31 step indices is ample (a run has at most 1000) and keeps step0 + i inside the int of the device-side state
-        SISIC_REQUIRE(step0 >= 0 && step0 <= INT32_MAX - T, "sample_rng: step0 %d", step0);
+        SISIC_REQUIRE(c.step0 >= 0 && c.step0 <= INT32_MAX - T, "sample_rng: step0 %d", c.step0);
         static_assert(sizeof(uint64_t) == 2 * sizeof(float), "seeds are staged as pairs of floats");
         SISIC_TRY(unet_grow(&u->seeds_dev, &u->seeds_cap, 2 * (size_t)std::max(B, 64)));
-        SISIC_TRY(unet_stage_upload(u, reinterpret_cast<const float*>(seeds), 2 * (size_t)B, u->seeds_dev, s));
+        SISIC_TRY(unet_stage_upload(u, reinterpret_cast<const float*>(c.seeds), 2 * (size_t)B, u->seeds_dev, s));
     }
 
     // every step's time embedding and time_emb_proj rows in one batch before the loop: row i of an unconditional call, row
@@ -1261,9 +1215,9 @@ static int sample_frames(sisic_unet* u, LoopCall c) {
     // (t, label) alone)
     std::vector<float> tv((size_t)T * L);
     for (size_t i = 0; i < (size_t)T; ++i)
-        for (size_t j = 0; j < L; ++j) tv[i * L + j] = (float)timesteps[i];
+        for (size_t j = 0; j < L; ++j) tv[i * L + j] = (float)c.timesteps[i];
     SISIC_TRY(unet_stage_upload(u, tv.data(), tv.size(), u->t_vals, s));
-    if (cg) {
+    if (c.cg) {
         std::vector<int64_t> lab((size_t)T * L);
         for (size_t i = 0; i < (size_t)T; ++i)
             for (size_t j = 0; j < L; ++j) lab[i * L + j] = distinct[j];
@@ -1271,81 +1225,86 @@ static int sample_frames(sisic_unet* u, LoopCall c) {
         // the loop's device table of the call: {w, L, -, -, slot[rows]} (elementwise.hip, LoopCond)
         std::vector<float> ct(LOOP_COND_HEAD + (size_t)rows, 0.0f);
         const int Li = (int)L;
-        ct[0] = cg->w;
+        ct[0] = c.cg->w;
         std::memcpy(&ct[1], &Li, sizeof(int));
         std::memcpy(&ct[LOOP_COND_HEAD], slots.data(), (size_t)rows * sizeof(int));
         SISIC_TRY(unet_grow(&u->cond_tables, &u->cond_tables_cap, LOOP_COND_HEAD + (size_t)std::max(rows, 128)));
         SISIC_TRY(unet_stage_upload(u, ct.data(), ct.size(), u->cond_tables, s));
     }
-    SISIC_TRY(time_embed(u, (int)((size_t)T * L), s, cg != nullptr));
+    SISIC_TRY(time_embed(u, (int)((size_t)T * L), s, c.cg != nullptr));
 
+    // xs: the latent the steps run on, ls: their stream.  The replayed form steps the library's x_work, on a stream of the
+    // library's own when the caller's is the legacy default stream; the eager form steps x in place on the caller's stream,
+    // except that a guided call steps a library-owned [2B] copy (the step kernel writes both halves: the next pass reads them
+    // without a copy).
     const bool use_graph = (u->graph_mode < 0 ? u->latency_mode : u->graph_mode != 0) && !u->ctx->profiling && T >= 4 && T <= 1000;
+    float* xs = c.x;
+    hipStream_t ls = s;
     if (use_graph) {
         if (!s) SISIC_HIP(hipStreamSynchronize(s));           // the embeddings above ran on the default stream
-        const int rc = sample_graph(u, c, s);
-        if (rc != SISIC_OK) return rc;
-        if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
-        return SISIC_OK;
+        SISIC_TRY(replay_begin(u, c, n, &ls));
+        xs = u->x_work;
+    } else {
+        if (guided) {
+            SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, 2 * n));
+            xs = u->x_work;
+            SISIC_HIP(hipMemcpyAsync(xs, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            SISIC_HIP(hipMemcpyAsync(xs + n, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        if (c.cg) SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)rows * u->tproj_R));
     }
-
-    // a guided call steps a library-owned [2B] copy of the latent (the step kernel writes both halves: the next pass reads
-    // them without a copy); everything else steps x in place
-    const bool guided = cg && cg->guided;
-    float* xe = x;
-    if (guided) {
-        SISIC_TRY(unet_grow(&u->x_work, &u->x_work_cap, 2 * n));
-        xe = u->x_work;
-        SISIC_HIP(hipMemcpyAsync(xe, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SISIC_HIP(hipMemcpyAsync(xe + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (cg) SISIC_TRY(unet_grow(&u->tproj_cur, &u->tproj_cur_cap, (size_t)rows * u->tproj_R));
-    size_t zi = 0;
+    int i = 0;
+    size_t zi = 0;                 // eager form: noise rows used so far
+    bool ready = false;            // replayed form: the call has found or captured its graph
     auto steps = [&]() -> int {
-        for (int i = 0; i < T; ++i) {
-            if (cancel) {
-                if ((i & 7) == 0) SISIC_HIP(hipStreamSynchronize(s));   // bound the run-ahead so a stop request takes effect
-                if (*cancel) {
-                    SISIC_HIP(hipStreamSynchronize(s));
-                    set_error("sample: cancelled after %d of %d steps", i, T);
-                    return SISIC_ECANCEL;
-                }
+        for (; i < T; ++i) {
+            if (c.cancel) {
+                if ((i & 7) == 0) SISIC_HIP(hipStreamSynchronize(ls));   // bound the run-ahead so a stop request takes effect
+                if (*c.cancel) return SISIC_ECANCEL;
             }
-            if (cg) {
-                SISIC_TRY(launch_loop_gather_rows(u->ctx, u->tproj, u->tproj_R, nullptr, i, u->cond_tables, rows, u->tproj_cur, s));
-                SISIC_TRY(unet_run_forward(u, xe, u->tproj_cur, u->tproj_R, u->eps_buf, rows, H, W, s));
-            } else {
-                SISIC_TRY(unet_run_forward(u, x, u->tproj + (size_t)i * u->tproj_R, 0, u->eps_buf, B, H, W, s));
-            }
-            const float* z = nullptr;
-            if (noise && coef[(size_t)i * cw + 4] != 0.0f) z = noise + (zi++) * n;
-            if (cl)
-                SISIC_TRY(resnet_input_gradient_walk(cl->clf, x, B, H, W, 0, reinterpret_cast<const int*>(u->clf_tables + LOOP_CLF_HEAD),
-                                                     u->clf_grad, nullptr, s));
-            // (xe is x unless the call is guided)
-            SISIC_TRY(launch_step(u->ctx, loop_step_launch(u, c, xe, n, i, z), s));
-            const int row = traj_row ? traj_row[i] : i;
-            if (traj && row >= 0) SISIC_HIP(hipMemcpyAsync(traj + (size_t)row * n, xe, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (steps_done) *steps_done = i + 1;
+            SISIC_TRY(use_graph ? replay_step(u, c, n, ls, i, &ready) : eager_step(u, c, xs, n, ls, i, &zi));
+            const int row = c.traj_row ? c.traj_row[i] : i;          // (kept frames only: XAI.py:751-757 save_indices)
+            if (c.traj && row >= 0) SISIC_HIP(hipMemcpyAsync(c.traj + (size_t)row * n, xs, n * sizeof(float), hipMemcpyDeviceToDevice, ls));
+            if (c.steps_done) *c.steps_done = i + 1;
         }
         return SISIC_OK;
     };
     const int rc = steps();
-    // x holds the latent after the steps that ran under every exit, as in the other forms of the loop: a cancelled or failed
-    // guided run hands its partially stepped copy back too
-    if (guided) SISIC_HIP(hipMemcpyAsync(x, xe, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // x holds the latent after the steps that ran under every exit: a cancelled or failed run hands its partially stepped copy
+    // back too
+    if (xs != c.x) SISIC_HIP(hipMemcpyAsync(c.x, xs, n * sizeof(float), hipMemcpyDeviceToDevice, ls));
+    if (ls != s) SISIC_HIP(hipStreamSynchronize(ls));         // hand the result back to the default stream's order
+    if (rc == SISIC_ECANCEL) {
+        SISIC_HIP(hipStreamSynchronize(ls));
+        set_error("sample: cancelled after %d of %d steps", i, T);
+    }
     if (rc != SISIC_OK) return rc;
-    if (out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, x, out_u8, B, C, H, W, s));
+    if (c.out_u8) SISIC_TRY(launch_denorm_u8(u->ctx, c.x, c.out_u8, B, C, H, W, s));
     return SISIC_OK;
+}
+
+int sisic_sample(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
+                 float clip, const float* noise, float* traj, uint8_t* out_u8, const volatile int* cancel,
+                 int* steps_done, void* stream) {
+    return sisic_sample_frames(u, x, B, H, W, T, timesteps, coef, clip, noise, traj, nullptr, out_u8, cancel, steps_done, stream);
+}
+
+// what every public entry point of the loop passes on as it was given; each adds its own fields
+static LoopCall loop_call(float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef, float clip, int rule,
+                          int rule_flags, float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel,
+                          int* steps_done, void* stream) {
+    LoopCall c;
+    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
+    c.rule = rule; c.rule_flags = rule_flags;
+    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
+    return c;
 }
 
 int sisic_sample_frames_rule(sisic_unet* u, float* x, int B, int H, int W, int T, const int64_t* timesteps, const float* coef,
                              float clip, int rule, int rule_flags, const float* noise, float* traj, const int* traj_row,
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
-    LoopCall c;
-    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
-    c.rule = rule; c.rule_flags = rule_flags;
+    LoopCall c = loop_call(x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, traj, traj_row, out_u8, cancel, steps_done, stream);
     c.noise = noise;
-    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
     return sample_frames(u, c);
 }
 
@@ -1354,11 +1313,8 @@ int sisic_sample_frames_rule_rng(sisic_unet* u, float* x, int B, int H, int W, i
                                  float* traj, const int* traj_row, uint8_t* out_u8, const volatile int* cancel, int* steps_done,
                                  void* stream) {
     SISIC_REQUIRE(seeds, "sample_rng: seeds is NULL");
-    LoopCall c;
-    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
-    c.rule = rule; c.rule_flags = rule_flags;
+    LoopCall c = loop_call(x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, traj, traj_row, out_u8, cancel, steps_done, stream);
     c.seeds = seeds; c.step0 = step0;
-    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
     return sample_frames(u, c);
 }
 
@@ -1368,12 +1324,9 @@ int sisic_sample_frames_cond(sisic_unet* u, float* x, int B, int H, int W, int T
                              uint8_t* out_u8, const volatile int* cancel, int* steps_done, void* stream) {
     SISIC_REQUIRE(u && class_labels, "sample_cond: null argument");
     SISIC_REQUIRE(!(seeds && noise), "sample_cond: a noise buffer and seeds (host noise takes seeds NULL, device noise takes noise NULL)");
-    LoopCall c;
-    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
-    c.rule = rule; c.rule_flags = rule_flags;
+    LoopCall c = loop_call(x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, traj, traj_row, out_u8, cancel, steps_done, stream);
     c.noise = noise; c.seeds = seeds; c.step0 = step0;
     c.labels = class_labels; c.null_label = null_label; c.w = guidance_scale;
-    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
     return sample_frames(u, c);
 }
 
@@ -1386,13 +1339,10 @@ int sisic_sample_frames_edit(sisic_unet* u, float* x, int B, int H, int W, int T
                   "sample_edit: null argument (the known image, the mask, the edit rows and the seeds are required)");
     SISIC_REQUIRE(x0k != x && mask != x, "sample_edit: the known image or the mask is the latent buffer");
     const EditCall ed{x0k, mask, edit_rows};
-    LoopCall c;
-    c.x = x; c.B = B; c.H = H; c.W = W; c.T = T; c.timesteps = timesteps; c.coef = coef; c.clip = clip;
-    c.rule = rule; c.rule_flags = rule_flags;
+    LoopCall c = loop_call(x, B, H, W, T, timesteps, coef, clip, rule, rule_flags, traj, traj_row, out_u8, cancel, steps_done, stream);
     c.seeds = seeds; c.step0 = step0;
     c.labels = class_labels; c.null_label = null_label; c.w = guidance_scale;
     c.ed = &ed;
-    c.traj = traj; c.traj_row = traj_row; c.out_u8 = out_u8; c.cancel = cancel; c.steps_done = steps_done; c.stream = stream;
     return sample_frames(u, c);
 }
 
@@ -1428,13 +1378,10 @@ int sisic_sample_frames_clf(sisic_unet* u, sisic_sample_clf_args* a) {
     SISIC_REQUIRE(std::isfinite(a->scale), "sample_clf: classifier scale %g", (double)a->scale);
     SISIC_REQUIRE(u->cfg.in_channels == 3, "sample_clf: the classifier reads 3-channel images, the model has %d", u->cfg.in_channels);
     const ClfCall cl{a->classifier, a->targets, a->scale};
-    LoopCall c;
-    c.x = a->x; c.B = a->B; c.H = a->H; c.W = a->W; c.T = a->T; c.timesteps = a->timesteps; c.coef = a->coef; c.clip = a->clip;
-    c.rule = a->rule; c.rule_flags = a->rule_flags;
+    LoopCall c = loop_call(a->x, a->B, a->H, a->W, a->T, a->timesteps, a->coef, a->clip, a->rule, a->rule_flags, a->traj, a->traj_row,
+                           a->out_u8, a->cancel, &a->steps_done, a->stream);
     c.seeds = a->seeds; c.step0 = a->step0;
     c.cl = &cl;
-    c.traj = a->traj; c.traj_row = a->traj_row; c.out_u8 = a->out_u8; c.cancel = a->cancel; c.steps_done = &a->steps_done;
-    c.stream = a->stream;
     return sample_frames(u, c);
 }
 

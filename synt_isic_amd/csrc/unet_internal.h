@@ -2,9 +2,12 @@
 // pool.  Shared by unet.cpp (inference executor, sampling loop) and train.cpp (tape-recording forward, backward, Adam).
 #pragma once
 
+#include <algorithm>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "common.h"
@@ -250,9 +253,17 @@ struct sisic_unet {
         const void* clf_handle = nullptr;
         uint64_t clf_gen = 0;
         bool rng = false;                // the captured step generates its noise (sisic_sample_frames_rng) ...
-        const void* seeds = nullptr;     // ... from the seeds at this address
+        const void* seeds = nullptr;     // ... from the seeds at this address (null for a step that does not)
         int rule = 0, rule_flags = 0;    // the step rule the captured step-kernel applies (SISIC_RULE_*) and its flags, the
                                          // handle's prediction type in their private bits (common.h STEP_FLAG_PRED_MASK)
+        // every field above, once: a field that is not listed here is not part of the key
+        auto scalars() const {
+            return std::tie(B, H, W, clip, s, latency, gen, cond, guided, edit, thr_ratio, thr_max, clf, clf_handle, clf_gen, rng,
+                            seeds, rule, rule_flags);
+        }
+        bool operator==(const LoopKey& o) const {
+            return scalars() == o.scalars() && std::equal(std::begin(ptrs), std::end(ptrs), std::begin(o.ptrs));
+        }
     } loop_key;
     bool loop_valid = false;
     int64_t loop_builds = 0;             // captures + instantiations so far (sisic_unet_graph_builds)

@@ -169,9 +169,7 @@ class ClassifierGuidance:
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(int(v) for v in self.targets))
-        if isinstance(self.scale, bool) or not isinstance(self.scale, (int, float)) or not np.isfinite(self.scale):
-            raise ValueError(f"classifier_scale must be a finite number, got {self.scale!r}")
-        object.__setattr__(self, "scale", float(self.scale))
+        object.__setattr__(self, "scale", _finite_number("classifier_scale", self.scale))
 
 
 @dataclass(frozen=True)
@@ -188,11 +186,15 @@ class Edit:
 MAX_CALL_STEPS = 1000        # steps of one library call of the loop (include/sisic.h)
 
 
+def _finite_number(name: str, value) -> float:
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not np.isfinite(value):
+        raise ValueError(f"{name} must be a finite number, got {value!r}")
+    return float(value)
+
+
 def check_guidance_scale(guidance_scale) -> float:
     """a finite real number (negative scales are legal: they push away from the class)"""
-    if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not np.isfinite(guidance_scale):
-        raise ValueError(f"guidance_scale must be a finite number, got {guidance_scale!r}")
-    return float(guidance_scale)
+    return _finite_number("guidance_scale", guidance_scale)
 
 
 def _check_guidance(model: HipUNet2DModel, guidance: Optional[Guidance], B: int) -> None:
@@ -208,17 +210,6 @@ def _check_guidance(model: HipUNet2DModel, guidance: Optional[Guidance], B: int)
     for v in guidance.labels + (guidance.null_label,):
         if not 0 <= int(v) < n:
             raise ValueError(f"class label {v} is outside [0, {n})")
-
-
-def _loop_call(lib, guidance: Optional[Guidance], head, noise_ptr, seeds, step0: int, tail) -> int:
-    """the library loop of one call: the unconditional entry points, or sisic_sample_frames_cond under ``guidance``"""
-    if guidance is None:
-        if seeds is not None:
-            return lib.sisic_sample_frames_rule_rng(*head, seeds, int(step0), *tail)
-        return lib.sisic_sample_frames_rule(*head, noise_ptr, *tail)
-    labels = (C.c_int64 * len(guidance.labels))(*guidance.labels)
-    return lib.sisic_sample_frames_cond(*head, noise_ptr, seeds, int(step0), labels, int(guidance.null_label),
-                                        float(guidance.scale), *tail)
 
 
 def draw_x_T_device(seeds: Sequence[int], chw: Tuple[int, int, int], device: torch.device) -> torch.Tensor:
@@ -449,101 +440,6 @@ def _set_thresholding(lib, model: HipUNet2DModel, threshold) -> None:
     check(lib.sisic_unet_set_thresholding(model.handle, ratio, max_value))
 
 
-@torch.no_grad()
-def _run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
-                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
-                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
-                       use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
-                       edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS,
-                       classifier: Optional[ClassifierGuidance] = None, threshold=None) -> SampleResult:
-    """threshold: (ratio, sample_max_value) of dynamic thresholding or None, as ``run_sampling_loop`` resolved it.
-    classifier: classifier guidance (``ClassifierGuidance``) of an unconditional epsilon-prediction model; needs a
-    ``DeviceNoise`` and composes with neither ``guidance`` nor ``edit``.
-    edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
-    The run has one step per entry of ``edit.schedule`` (``timesteps``, ``steps_done``, the trajectory and ``save_indices``
-    count those passes), and one longer than ``max_call_steps`` (at most 1000, the library's limit per call) is cut into calls
-    with their step offsets: bit-equal to the uncut run under ddpm and ddim; a DPM-Solver++ run is never cut.
-    guidance: the labels, null label and scale of a class-conditional model (``Guidance``); None for an unconditional one.
-    x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
-    (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
-    ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
-    return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``).
-    scheduler: a ``HipDDPMScheduler``, a ``HipDDIMScheduler`` or a ``HipDPMSolverMultistepScheduler``; its ``rule`` selects
-    the step kernel.  eta and use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not
-    zero under that rule and eta -- none for DDIM at eta = 0 and for the ODE variant of DPM-Solver++, where every noise
-    source gives the same result.  A DPM-Solver++ run takes no ``NoiseStream``: the history lives inside one library call."""
-    if classifier is not None:
-        _check_classifier_guidance(model, classifier, noise, guidance, edit, x_T.shape[0])
-    if edit is not None:
-        _check_guidance(model, guidance, x_T.shape[0])
-        return _run_edited(model, scheduler, x_T, noise, edit, return_trajectory, save_indices, cancel_flag, eta,
-                           use_clipped_model_output, guidance, max_call_steps, threshold)
-    if isinstance(noise, NoiseStream):
-        if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":
-            raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
-                             "noise buffer, a DeviceNoise or None")
-        _check_guidance(model, guidance, x_T.shape[0])
-        return _run_streamed(model, scheduler, x_T, noise, return_trajectory, cancel_flag, save_indices, eta,
-                             use_clipped_model_output, guidance, threshold)
-    _check_guidance(model, guidance, x_T.shape[0])
-    lib = _lib.load()
-    dev = x_T.device
-    if dev.type != "cuda":
-        raise RuntimeError("the sampling loop runs on MI355X only")
-    _set_thresholding(lib, model, threshold)
-    B, Cc, H, W = x_T.shape
-    ts = scheduler.timesteps.to(torch.int64).contiguous()
-    T = ts.numel()
-    coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
-    n_noise = int((coef[:, 4] != 0).sum())
-    device_noise = noise if isinstance(noise, DeviceNoise) else None
-    if device_noise is not None:
-        if len(device_noise.seeds) != B:
-            raise ValueError(f"DeviceNoise holds {len(device_noise.seeds)} seeds for a batch of {B}")
-        noise = None
-    if noise is not None:
-        if tuple(noise.shape) != (n_noise, B, Cc, H, W) or noise.device != dev or noise.dtype != torch.float32:
-            raise ValueError(f"noise must be fp32 {(n_noise, B, Cc, H, W)} on {dev}, got {tuple(noise.shape)}")
-        noise = noise.contiguous()
-    x = x_T.to(torch.float32).contiguous().clone()
-    kept, rows = _frame_rows(T, return_trajectory, save_indices)
-    traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
-    out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
-    done = C.c_int(0)
-    clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
-    head = (model.handle, x.data_ptr(), B, H, W, T, C.cast(ts.data_ptr(), _lib.c_int64_p),
-            C.cast(coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags)
-    tail = (traj.data_ptr() if traj is not None and len(kept) else None,
-            rows.ctypes.data_as(C.POINTER(C.c_int)) if rows is not None and len(kept) else None,
-            out_u8.data_ptr(),
-            C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if classifier is not None:
-        a = _lib.SampleClfArgs(x=x.data_ptr(), timesteps=head[6], coef=head[7], noise=None,
-                               seeds=(C.c_uint64 * B)(*device_noise.seeds), classifier=classifier.classifier.handle,
-                               targets=(C.c_int64 * B)(*classifier.targets), traj=tail[0], traj_row=tail[1], out_u8=tail[2],
-                               cancel=C.pointer(cancel_flag) if cancel_flag is not None else None, stream=tail[5],
-                               B=B, H=H, W=W, T=T, rule=rule, rule_flags=rule_flags, step0=int(device_noise.step0),
-                               clip=float(clip), scale=classifier.scale)
-        rc = lib.sisic_sample_frames_clf(model.handle, C.byref(a))
-        done = C.c_int(a.steps_done)
-    elif device_noise is not None:
-        seeds = (C.c_uint64 * B)(*device_noise.seeds)
-        rc = _loop_call(lib, guidance, head, None, seeds, device_noise.step0, tail)
-    else:
-        rc = _loop_call(lib, guidance, head, noise.data_ptr() if noise is not None and n_noise else None, None, 0, tail)
-    if rc != _lib.SISIC_ECANCEL:
-        check(rc)
-    cancelled = rc == _lib.SISIC_ECANCEL
-    if cancelled:
-        out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
-    return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done.value, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"),
-                        classifier_scale=classifier.scale if classifier is not None else None,
-                        classifier_passes=done.value if classifier is not None else 0)
-
-
 def _check_classifier_guidance(model: HipUNet2DModel, classifier: ClassifierGuidance, noise, guidance, edit, B: int) -> None:
     """every refusal of a classifier-guided run that needs no library call (the library checks them again)"""
     if guidance is not None or model.config.num_class_embeds is not None:
@@ -578,83 +474,6 @@ def check_edit_schedule(rule: str, schedule, T: int) -> List[Tuple[int, int]]:
     return sched
 
 
-def _run_edited(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, edit: Edit, return_trajectory: bool,
-                save_indices: Optional[Sequence[int]], cancel_flag: Optional[C.c_int], eta: float,
-                use_clipped_model_output: bool, guidance: Optional[Guidance], max_call_steps: int,
-                threshold=None) -> SampleResult:
-    """run_sampling_loop under an ``Edit``: the rule's rows, the timesteps and the edit rows of the expanded schedule, then
-    sisic_sample_frames_edit, in calls of at most ``max_call_steps`` passes"""
-    if not isinstance(noise, DeviceNoise):
-        raise ValueError("inpainting draws on the device only (the known region's noise and the jumps are streams of the "
-                         "device-noise contract): pass noise=DeviceNoise(seeds)")
-    lib = _lib.load()
-    dev = x_T.device
-    if dev.type != "cuda":
-        raise RuntimeError("the sampling loop runs on MI355X only")
-    _set_thresholding(lib, model, threshold)
-    B, Cc, H, W = x_T.shape
-    if len(noise.seeds) != B:
-        raise ValueError(f"DeviceNoise holds {len(noise.seeds)} seeds for a batch of {B}")
-    max_call_steps = int(max_call_steps)
-    if not 1 <= max_call_steps <= MAX_CALL_STEPS:
-        raise ValueError(f"max_call_steps must lie in 1 .. {MAX_CALL_STEPS}, got {max_call_steps}")
-    image, mask = edit.image, edit.mask
-    if tuple(image.shape) != (B, Cc, H, W) or image.device != dev or image.dtype != torch.float32:
-        raise ValueError(f"the known image must be fp32 {(B, Cc, H, W)} on {dev}, got {image.dtype} {tuple(image.shape)}")
-    if tuple(mask.shape) != (B, 1, H, W) or mask.device != dev or mask.dtype != torch.float32:
-        raise ValueError(f"the mask must be fp32 {(B, 1, H, W)} on {dev}, got {mask.dtype} {tuple(mask.shape)}")
-    image, mask = image.contiguous(), mask.contiguous()
-    grid_ts = scheduler.timesteps.to(torch.int64)
-    rule_name = getattr(scheduler, "rule", "ddpm")
-    schedule = check_edit_schedule(rule_name, edit.schedule, grid_ts.numel())
-    grid_coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
-    idx = torch.tensor([i for i, _ in schedule], dtype=torch.int64)
-    if int(idx.min()) < 0 or int(idx.max()) >= grid_ts.numel():
-        raise ValueError(f"edit schedule indices outside 0..{grid_ts.numel() - 1}")
-    # a pass runs under the row of ITS grid entry (t -> its own previous grid point), wherever the next pass goes
-    ts, coef, erows = grid_ts[idx].contiguous(), grid_coef[idx].contiguous(), edit_rows(scheduler, schedule).contiguous()
-    P = len(schedule)
-    if P > max_call_steps and rule == _lib.RULE_DPMPP:
-        raise ValueError(f"a DPM-Solver++ run of {P} steps is not cut into calls of {max_call_steps} (each cut would lose the "
-                         "history)")
-    x = x_T.to(torch.float32).contiguous().clone()
-    kept, rows = _frame_rows(P, return_trajectory, save_indices)
-    if return_trajectory and rows is None:
-        rows = np.arange(P, dtype=np.int32)
-    traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
-    out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
-    clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    seeds = (C.c_uint64 * B)(*noise.seeds)
-    labels = (C.c_int64 * B)(*guidance.labels) if guidance is not None else None
-    done_total, rc = 0, 0
-    for a in range(0, P, max_call_steps):
-        b = min(P, a + max_call_steps)
-        done = C.c_int(0)
-        seg_rows = np.ascontiguousarray(rows[a:b]) if traj is not None and len(kept) else None
-        seg_ts, seg_coef, seg_erows = ts[a:b].contiguous(), coef[a:b].contiguous(), erows[a:b].contiguous()
-        rc = lib.sisic_sample_frames_edit(
-            model.handle, x.data_ptr(), B, H, W, b - a, C.cast(seg_ts.data_ptr(), _lib.c_int64_p),
-            C.cast(seg_coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags, seeds, int(noise.step0) + a, labels,
-            int(guidance.null_label) if guidance is not None else 0, float(guidance.scale) if guidance is not None else 1.0,
-            image.data_ptr(), mask.data_ptr(), C.cast(seg_erows.data_ptr(), _lib.c_float_p),
-            traj.data_ptr() if seg_rows is not None else None,
-            seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
-            out_u8.data_ptr() if b == P else None, C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done),
-            stream)
-        done_total += done.value
-        if rc != 0:
-            break
-    if rc != _lib.SISIC_ECANCEL:
-        check(rc)
-    cancelled = rc == _lib.SISIC_ECANCEL
-    if cancelled:
-        out_u8.zero_()
-    return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done_total, cancelled=cancelled, scheduler=rule_name, eta=float(eta), unet_passes=P,
-                        prediction_type=getattr(model, "prediction_type", "epsilon"))
-
-
 def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
     """Step boundaries of the segments a streamed run is cut into (``NoiseStream``): ``seg`` steps each, except that a run
     whose segment is a noticeable amount of RNG (more than 1 M normals: one 128x128 image draws 3 M per 64 steps, 64 images
@@ -671,67 +490,253 @@ def segment_bounds(T: int, seg: int, per_step: int) -> List[int]:
     return bounds
 
 
-def _run_streamed(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, ns: NoiseStream,
-                  return_trajectory: bool, cancel_flag: Optional[C.c_int],
-                  save_indices: Optional[Sequence[int]] = None, eta: float = 0.0,
-                  use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None, threshold=None) -> SampleResult:
+@dataclass(frozen=True)
+class PlannedCall:
+    """One library call of a run (``plan_calls``)."""
+    k: int                         # its place in the plan
+    a: int                         # the steps [a, b) of the run it takes
+    b: int
+    z_first: int                   # the run's noise rows [z_first, z_first + z_rows): one per step whose sigma is not zero
+    z_rows: int
+    rows: Optional[np.ndarray]     # its slice of the run's frame-row table (int32 [b - a]; -1: not kept); None: no trajectory
+    step0: int                     # device noise: the step index of its first step
+    last: bool                     # the one call that writes the images
+
+
+def plan_calls(noisy: Sequence[bool], cuts: Sequence[int], kept: Sequence[int], step0: int = 0) -> List[PlannedCall]:
+    """The library calls of a run, as data: ``noisy[i]`` says whether step i adds noise, ``cuts`` are the step boundaries of the
+    calls (``[0, T]``: one call; ``segment_bounds`` for a ``NoiseStream``; every ``max_call_steps`` passes of an edited run),
+    ``kept`` the steps whose frame the trajectory keeps (none: no trajectory) and ``step0`` the step index of step 0."""
+    T, cuts = len(noisy), [int(c) for c in cuts]
+    if len(cuts) < 2 or cuts[0] != 0 or cuts[-1] != T or any(b <= a for a, b in zip(cuts[:-1], cuts[1:])):
+        raise ValueError(f"the calls {cuts} do not tile the {T} steps of the run")
+    kept, rows = _frame_rows(T, True, kept)         # (a cut run's steps go to their rows of the whole run)
+    before = [0]
+    for flag in noisy:
+        before.append(before[-1] + bool(flag))
+    return [PlannedCall(k, a, b, before[a], before[b] - before[a], np.ascontiguousarray(rows[a:b]) if kept else None,
+                        int(step0) + a, b == T) for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:]))]
+
+
+class _NoiseSource:
+    """Where the calls of a run take their z from.  ``seeds``: the seed array of a run whose step kernel draws (else None);
+    ``start`` sees the plan before the first call, ``z_ptr`` gives a call's noise rows in device memory (None: it has none) and
+    ``enqueued`` follows the call.  This one adds no noise."""
+    seeds = None
+
+    def start(self, plan: List[PlannedCall]) -> None:
+        pass
+
+    def z_ptr(self, call: PlannedCall) -> Optional[int]:
+        return None
+
+    def enqueued(self, call: PlannedCall) -> None:
+        pass
+
+
+class _BufferNoise(_NoiseSource):
+    """a resident buffer [n_noise,B,C,H,W]"""
+
+    def __init__(self, z: torch.Tensor):
+        self.z = z
+
+    def z_ptr(self, call):
+        return self.z[call.z_first:].data_ptr() if call.z_rows else None
+
+
+class _SeedNoise(_NoiseSource):
+    """a ``DeviceNoise``: the step kernel draws, no buffer"""
+
+    def __init__(self, seeds: Sequence[int]):
+        self.seeds = (C.c_uint64 * len(seeds))(*seeds)
+
+
+class _StreamNoise(_NoiseSource):
+    """a ``NoiseStream``: call k reads slot k & 1 while the stream draws call k + 1's rows into the other slot"""
+
+    def __init__(self, ns: NoiseStream):
+        self.ns = ns
+
+    def start(self, plan):
+        self.plan = plan
+        self.ns.prefetch(0, plan[0].z_rows)
+
+    def z_ptr(self, call):
+        z = self.ns.acquire(call.k & 1, call.z_rows)
+        if call.k + 1 < len(self.plan):
+            self.ns.prefetch((call.k & 1) ^ 1, self.plan[call.k + 1].z_rows)    # drawn while the GPU runs this call
+        return z.data_ptr() if z is not None else None
+
+    def enqueued(self, call):
+        self.ns.release(call.k & 1)
+
+
+def _library_call(lib, model: HipUNet2DModel, x: torch.Tensor, tables, clip: float, rule: int, rule_flags: int, call: PlannedCall,
+                  z_ptr, seeds, guidance: Optional[Guidance], edit: Optional[Edit], classifier: Optional[ClassifierGuidance],
+                  traj, out_u8, cancel_flag, stream) -> Tuple[int, int]:
+    """(return code, steps done) of one library call of the loop, through the entry point of its kind of run: _clf under a
+    ``ClassifierGuidance``, _edit under an ``Edit``, _cond under labels, else _rule_rng with seeds and _rule without.
+    tables: the run's (timesteps, coefficient rows, edit rows or None) on the host; the call takes its steps' rows."""
+    B, _, H, W = x.shape
+    ts, coef, erows = (t[call.a:call.b].contiguous() if t is not None else None for t in tables)
+    done = C.c_int(0)
+    head = (model.handle, x.data_ptr(), B, H, W, call.b - call.a, C.cast(ts.data_ptr(), _lib.c_int64_p),
+            C.cast(coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags)
+    tail = (traj.data_ptr() if call.rows is not None else None,
+            call.rows.ctypes.data_as(C.POINTER(C.c_int)) if call.rows is not None else None,
+            out_u8.data_ptr() if call.last else None,
+            C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream)
+    step0 = call.step0 if seeds is not None else 0
+    if classifier is not None:
+        a = _lib.SampleClfArgs(x=head[1], timesteps=head[6], coef=head[7], noise=None, seeds=seeds,
+                               classifier=classifier.classifier.handle, targets=(C.c_int64 * B)(*classifier.targets),
+                               traj=tail[0], traj_row=tail[1], out_u8=tail[2],
+                               cancel=C.pointer(cancel_flag) if cancel_flag is not None else None, stream=stream,
+                               B=B, H=H, W=W, T=head[5], rule=rule, rule_flags=rule_flags, step0=step0, clip=float(clip),
+                               scale=classifier.scale)
+        return lib.sisic_sample_frames_clf(model.handle, C.byref(a)), a.steps_done
+    cond = (None, 0, 1.0)
+    if guidance is not None:
+        cond = ((C.c_int64 * B)(*guidance.labels), int(guidance.null_label), float(guidance.scale))
+    if edit is not None:
+        rc = lib.sisic_sample_frames_edit(*head, seeds, step0, *cond, edit.image.data_ptr(), edit.mask.data_ptr(),
+                                          C.cast(erows.data_ptr(), _lib.c_float_p), *tail)
+    elif guidance is not None:
+        rc = lib.sisic_sample_frames_cond(*head, z_ptr, seeds, step0, *cond, *tail)
+    elif seeds is not None:
+        rc = lib.sisic_sample_frames_rule_rng(*head, seeds, step0, *tail)
+    else:
+        rc = lib.sisic_sample_frames_rule(*head, z_ptr, *tail)
+    return rc, done.value
+
+
+def _check_edit(edit: Edit, x_T: torch.Tensor) -> Edit:
+    """the known image and the mask of an edited run at the latents' shape and device, contiguous"""
+    (B, Cc, H, W), dev = x_T.shape, x_T.device
+    image, mask = edit.image, edit.mask
+    if tuple(image.shape) != (B, Cc, H, W) or image.device != dev or image.dtype != torch.float32:
+        raise ValueError(f"the known image must be fp32 {(B, Cc, H, W)} on {dev}, got {image.dtype} {tuple(image.shape)}")
+    if tuple(mask.shape) != (B, 1, H, W) or mask.device != dev or mask.dtype != torch.float32:
+        raise ValueError(f"the mask must be fp32 {(B, 1, H, W)} on {dev}, got {mask.dtype} {tuple(mask.shape)}")
+    return Edit(image.contiguous(), mask.contiguous(), edit.schedule)
+
+
+@torch.no_grad()
+def _run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
+                       noise, *, return_trajectory: bool = False, save_indices: Optional[Sequence[int]] = None,
+                       cancel_flag: Optional[C.c_int] = None, eta: float = 0.0,
+                       use_clipped_model_output: bool = False, guidance: Optional[Guidance] = None,
+                       edit: Optional[Edit] = None, max_call_steps: int = MAX_CALL_STEPS,
+                       classifier: Optional[ClassifierGuidance] = None, threshold=None) -> SampleResult:
+    """threshold: (ratio, sample_max_value) of dynamic thresholding or None, as ``run_sampling_loop`` resolved it.
+    classifier: classifier guidance (``ClassifierGuidance``) of an unconditional epsilon-prediction model; needs a
+    ``DeviceNoise`` and composes with neither ``guidance`` nor ``edit``.
+    edit: an inpainting run (``Edit``): the known region is re-imposed inside every step kernel; needs a ``DeviceNoise``.
+    The run has one step per entry of ``edit.schedule`` (``timesteps``, ``steps_done``, the trajectory and ``save_indices``
+    count those passes), and one longer than ``max_call_steps`` (at most 1000, the library's limit per call) is cut into calls
+    with their step offsets: bit-equal to the uncut run under ddpm and ddim; a DPM-Solver++ run is never cut.
+    guidance: the labels, null label and scale of a class-conditional model (``Guidance``); None for an unconditional one.
+    x_T: GPU fp32 [B,C,H,W]; noise: GPU fp32 [n_noise,B,C,H,W], None (no noise added), a ``NoiseStream``
+    (the loop then runs segment by segment while the stream draws and uploads the next segment's noise), or a
+    ``DeviceNoise`` (the step kernel generates z_t from the images' seeds: one call for the whole run, no buffer).
+    return_trajectory keeps x after every step, or after the steps in ``save_indices`` only (``trajectory_save_indices``).
+    scheduler: a ``HipDDPMScheduler``, a ``HipDDIMScheduler`` or a ``HipDPMSolverMultistepScheduler``; its ``rule`` selects
+    the step kernel.  eta and use_clipped_model_output are the DDIM rule's.  n_noise is the number of steps whose sigma is not
+    zero under that rule and eta -- none for DDIM at eta = 0 and for the ODE variant of DPM-Solver++, where every noise
+    source gives the same result.  A DPM-Solver++ run takes no ``NoiseStream``: the history lives inside one library call.
+
+    Every kind of run goes the same way: the checks, the rule's tables, the plan of its library calls (``plan_calls``: one call,
+    unless a ``NoiseStream``'s segments or an edited run's ``max_call_steps`` cut it), then call by call with the noise of its
+    source."""
+    B, Cc, H, W = x_T.shape
+    rule_name = getattr(scheduler, "rule", "ddpm")
+    if classifier is not None:
+        _check_classifier_guidance(model, classifier, noise, guidance, edit, B)
+    if isinstance(noise, NoiseStream) and rule_name == "dpmsolver++":
+        raise ValueError("a DPM-Solver++ run is not cut into segments (each cut would lose the history): pass the whole "
+                         "noise buffer, a DeviceNoise or None")
+    _check_guidance(model, guidance, B)
+    if edit is not None and not isinstance(noise, DeviceNoise):
+        raise ValueError("inpainting draws on the device only (the known region's noise and the jumps are streams of the "
+                         "device-noise contract): pass noise=DeviceNoise(seeds)")
     lib = _lib.load()
     dev = x_T.device
+    if dev.type != "cuda":
+        raise RuntimeError("the sampling loop runs on MI355X only")
     _set_thresholding(lib, model, threshold)
-    B, Cc, H, W = x_T.shape
+    if isinstance(noise, DeviceNoise) and len(noise.seeds) != B:
+        raise ValueError(f"DeviceNoise holds {len(noise.seeds)} seeds for a batch of {B}")
     ts = scheduler.timesteps.to(torch.int64).contiguous()
-    T = ts.numel()
+    erows = None
+    if edit is not None:
+        max_call_steps = int(max_call_steps)
+        if not 1 <= max_call_steps <= MAX_CALL_STEPS:
+            raise ValueError(f"max_call_steps must lie in 1 .. {MAX_CALL_STEPS}, got {max_call_steps}")
+        edit = _check_edit(edit, x_T)
+        schedule = check_edit_schedule(rule_name, edit.schedule, ts.numel())
     coef, rule, rule_flags = _rule_tables(scheduler, eta, use_clipped_model_output)
-    needs = (coef[:, 4] != 0).to(torch.int64)                   # 1 where the step adds noise
-    bounds = segment_bounds(T, ns.seg, B * Cc * H * W)
-    counts = [int(needs[a:b].sum()) for a, b in zip(bounds[:-1], bounds[1:])]
+    if edit is not None:
+        idx = torch.tensor([i for i, _ in schedule], dtype=torch.int64)
+        if int(idx.min()) < 0 or int(idx.max()) >= ts.numel():
+            raise ValueError(f"edit schedule indices outside 0..{ts.numel() - 1}")
+        # a pass runs under the row of ITS grid entry (t -> its own previous grid point), wherever the next pass goes
+        ts, coef, erows = ts[idx].contiguous(), coef[idx].contiguous(), edit_rows(scheduler, schedule).contiguous()
+        if len(schedule) > max_call_steps and rule == _lib.RULE_DPMPP:
+            raise ValueError(f"a DPM-Solver++ run of {len(schedule)} steps is not cut into calls of {max_call_steps} (each cut "
+                             "would lose the history)")
+    T = ts.numel()                                              # steps of the run: UNet passes
+    noisy = (coef[:, 4] != 0).tolist()
+    cuts, step0 = [0, T], 0
+    if isinstance(noise, DeviceNoise):
+        source, step0 = _SeedNoise(noise.seeds), noise.step0
+        if edit is not None:
+            cuts = list(range(0, T, max_call_steps)) + [T]
+    elif isinstance(noise, NoiseStream):
+        source, cuts = _StreamNoise(noise), segment_bounds(T, noise.seg, B * Cc * H * W)
+    else:
+        if noise is not None:
+            if tuple(noise.shape) != (sum(noisy), B, Cc, H, W) or noise.device != dev or noise.dtype != torch.float32:
+                raise ValueError(f"noise must be fp32 {(sum(noisy), B, Cc, H, W)} on {dev}, got {tuple(noise.shape)}")
+            noise = noise.contiguous()
+        source = _BufferNoise(noise) if noise is not None else _NoiseSource()
+    kept = _frame_rows(T, return_trajectory, save_indices)[0]
+    plan = plan_calls(noisy, cuts, kept, step0)
     x = x_T.to(torch.float32).contiguous().clone()
-    kept, rows = _frame_rows(T, return_trajectory, save_indices)
-    if return_trajectory and rows is None:
-        rows = np.arange(T, dtype=np.int32)                     # a segment's steps go to their rows of the whole run
     traj = ops.empty((len(kept), B, Cc, H, W), dtype=torch.float32, device=dev) if return_trajectory else None
     out_u8 = ops.empty((B, H, W, Cc), dtype=torch.uint8, device=dev)
     clip = scheduler.config.clip_sample_range if scheduler.config.clip_sample else 0.0
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    done_total, rc = 0, 0
-    ns.prefetch(0, counts[0])
-    for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
-        slot = k & 1
-        z = ns.acquire(slot, counts[k])
-        if k + 1 < len(counts):
-            ns.prefetch(slot ^ 1, counts[k + 1])                # drawn while the GPU runs this segment
-        done = C.c_int(0)
-        last = b == T
-        seg_rows = np.ascontiguousarray(rows[a:b]) if traj is not None and len(kept) else None
-        seg_ts, seg_coef = ts[a:b].contiguous(), coef[a:b].contiguous()
-        rc = _loop_call(lib, guidance,
-                        (model.handle, x.data_ptr(), B, H, W, b - a, C.cast(seg_ts.data_ptr(), _lib.c_int64_p),
-                         C.cast(seg_coef.data_ptr(), _lib.c_float_p), float(clip), rule, rule_flags),
-                        z.data_ptr() if z is not None else None, None, 0,
-                        (traj.data_ptr() if seg_rows is not None else None,
-                         seg_rows.ctypes.data_as(C.POINTER(C.c_int)) if seg_rows is not None else None,
-                         out_u8.data_ptr() if last else None,
-                         C.byref(cancel_flag) if cancel_flag is not None else None, C.byref(done), stream))
-        ns.release(slot)
-        done_total += done.value
+    steps_done, rc = 0, 0
+    source.start(plan)
+    for call in plan:
+        rc, done = _library_call(lib, model, x, (ts, coef, erows), clip, rule, rule_flags, call, source.z_ptr(call), source.seeds,
+                                 guidance, edit, classifier, traj, out_u8, cancel_flag, stream)
+        source.enqueued(call)
+        steps_done += done
         if rc != 0:
             break
     if rc != _lib.SISIC_ECANCEL:
         check(rc)
     cancelled = rc == _lib.SISIC_ECANCEL
     if cancelled:
-        out_u8.zero_()
+        out_u8.zero_()                         # never hand uninitialised pixels to a caller that ignores `cancelled`
     return SampleResult(images=out_u8, latents=x, trajectory=traj, trajectory_steps=kept, timesteps=[int(t) for t in ts],
-                        steps_done=done_total, cancelled=cancelled, scheduler=getattr(scheduler, "rule", "ddpm"),
-                        eta=float(eta), unet_passes=T, prediction_type=getattr(model, "prediction_type", "epsilon"))
+                        steps_done=steps_done, cancelled=cancelled, scheduler=rule_name, eta=float(eta), unet_passes=T,
+                        prediction_type=getattr(model, "prediction_type", "epsilon"),
+                        classifier_scale=classifier.scale if classifier is not None else None,
+                        classifier_passes=steps_done if classifier is not None else 0)
+
+
+def _check_strength(strength) -> float:
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
+    return float(strength)
 
 
 def strength_steps(T: int, strength) -> int:
     """how many of a T-step grid's entries, counted from its end, an edit of this ``strength`` runs: ``min(int(T * strength),
     T)``; ``strength`` lies in (0, 1] and must leave at least one step"""
-    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
-        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
-    n = min(int(int(T) * float(strength)), int(T))
+    n = min(int(int(T) * _check_strength(strength)), int(T))
     if n < 1:
         raise ValueError(f"strength={strength} leaves no step of a {T}-step grid to run")
     return n
@@ -743,8 +748,7 @@ def check_edit_options(scheduler: str, noise: str, has_image: bool, has_mask: bo
         raise ValueError(f"n_resample must be a positive integer, got {n_resample!r}")
     if isinstance(jump_length, bool) or not isinstance(jump_length, int) or jump_length < 1:
         raise ValueError(f"jump_length must be a positive integer, got {jump_length!r}")
-    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
-        raise ValueError(f"strength must lie in (0, 1], got {strength!r}")
+    _check_strength(strength)
     if not has_image:
         if has_mask or float(strength) != 1.0 or n_resample != 1:
             raise ValueError("mask, strength and n_resample edit an image: pass init_image")
@@ -1074,44 +1078,35 @@ class Sampler:
             save_indices = trajectory_save_indices(pass_ts, save_every_n)
         n_noise = int((_rule_tables(sched, eta, use_clipped_model_output)[0][:, 4] != 0).sum())     # steps with sigma != 0
 
-        def finish(res: SampleResult, hashes) -> SampleResult:
-            res.seeds = [int(s) for s in seeds]
-            res.noise_hashes = hashes
-            if init_image is not None:
-                res.strength, res.n_resample = float(strength), int(n_resample)
-            return res
-        if noise == "device":
-            x_T = draw_x_T_device(seeds, (model.config.in_channels, H, W), self.device)
-            hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, x_T if start is None else start(x_T), DeviceNoise(tuple(seeds)),
-                                    return_trajectory=return_trajectory,
-                                    save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
-            torch.cuda.current_stream(self.device).synchronize()
-            return finish(res, hashes)
-        if scheduler == "dpmsolver++" or (scheduler == "ddim" and n_noise == 0):
-            # DDIM at eta = 0 and the ODE variant of DPM-Solver++: the run draws x_T and nothing else -- no z, no staging
-            # buffers, no worker threads.  The SDE variant: every z of the run up front and ONE library call, because the
-            # segments of a NoiseStream would each start without the history (T is 10 to 25 under this rule).
-            x_T, z = draw_noise(seeds, n_noise, (model.config.in_channels, H, W))
-            hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, x_T.to(self.device) if start is None else start(x_T),
-                                    z.to(self.device) if n_noise else None, return_trajectory=return_trajectory,
-                                    save_indices=save_indices, cancel_flag=self.cancel, **rule_args)
-            torch.cuda.current_stream(self.device).synchronize()
-            return finish(res, hashes)
-        # noise is drawn segment by segment on worker threads while the GPU samples (NoiseStream); the values are
-        # those of draw_noise(seeds, n_noise, ...)
-        ns = NoiseStream(seeds, (model.config.in_channels, H, W), self.device, self.noise_segment_steps,
-                         buffer_cache=self._noise_buffers)
+        chw = (model.config.in_channels, H, W)
+        ns = None
         try:
-            hashes = [noise_hash(ns.x_T[b:b + 1]) for b in range(len(seeds))]
-            res = run_sampling_loop(model, sched, ns.x_T.to(self.device) if start is None else start(ns.x_T),
-                                    ns if n_noise else None, return_trajectory=return_trajectory, save_indices=save_indices,
-                                    cancel_flag=self.cancel, **rule_args)
+            if noise == "device":
+                x_T, source = draw_x_T_device(seeds, chw, self.device), DeviceNoise(tuple(seeds))
+            elif scheduler == "dpmsolver++" or (scheduler == "ddim" and n_noise == 0):
+                # DDIM at eta = 0 and the ODE variant of DPM-Solver++: the run draws x_T and nothing else -- no z, no staging
+                # buffers, no worker threads.  The SDE variant: every z of the run up front and ONE library call, because the
+                # segments of a NoiseStream would each start without the history (T is 10 to 25 under this rule).
+                x_T, z = draw_noise(seeds, n_noise, chw)
+                source = z.to(self.device) if n_noise else None
+            else:
+                # noise is drawn segment by segment on worker threads while the GPU samples (NoiseStream); the values are
+                # those of draw_noise(seeds, n_noise, ...)
+                ns = NoiseStream(seeds, chw, self.device, self.noise_segment_steps, buffer_cache=self._noise_buffers)
+                x_T, source = ns.x_T, ns if n_noise else None
+            hashes = [noise_hash(x_T[b:b + 1]) for b in range(len(seeds))]
+            res = run_sampling_loop(model, sched, x_T.to(self.device) if start is None else start(x_T), source,
+                                    return_trajectory=return_trajectory, save_indices=save_indices, cancel_flag=self.cancel,
+                                    **rule_args)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
-            ns.close()
-        return finish(res, hashes)
+            if ns is not None:
+                ns.close()
+        res.seeds = [int(s) for s in seeds]
+        res.noise_hashes = hashes
+        if init_image is not None:
+            res.strength, res.n_resample = float(strength), int(n_resample)
+        return res
 
     def generate(self, seed: int, class_name, T: int, *, count: int = 1, size: Tuple[int, int] = (128, 128),
                  return_trajectory: bool = False, seed_is_base: bool = False, postprocess: bool = False,

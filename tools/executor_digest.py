@@ -19,6 +19,7 @@ import torch  # noqa: E402
 from synt_isic_amd import _lib, ops  # noqa: E402
 from synt_isic_amd.classifier import HipMelanomaClassifier  # noqa: E402
 from synt_isic_amd.sampler import Sampler  # noqa: E402
+from synt_isic_amd.scheduler import resample_schedule  # noqa: E402
 from synt_isic_amd.train import HipAdam, mse_loss  # noqa: E402
 from synt_isic_amd.weights import synthetic_resnet18_state_dict, synthetic_unet_state_dict  # noqa: E402
 
@@ -63,16 +64,47 @@ def unet_items(sd) -> None:
     m = s.add_model("NV", sd)
     unet_forward(s, "b2_64", 2, 64)             # every shortcut's GroupNorm rider is carried
     unet_forward(s, "b1_32", 1, 32)             # the 4x4 shortcuts are not: the stand-alone finalisation follows
-    # sampling: eager and graph-replayed, host and device noise, DDPM and DDIM
+    # sampling: eager and graph-replayed, host and device noise, DDPM and DDIM, then every other form of the loop
+    cm = s.add_conditional_model(["MEL", "BCC"], synthetic_unet_state_dict(num_class_embeds=3))
+    s.set_classifier(HipMelanomaClassifier(num_classes=7).load_state_dict(synthetic_resnet18_state_dict()).to(DEV).eval(),
+                     {"NV": 1})
+    image = rand((2, 3, 32, 32), 41).clamp(-1, 1)
+    mask = (torch.rand((2, 1, 32, 32), generator=torch.Generator().manual_seed(42)) < 0.5).float()
+    passes = len(resample_schedule(8, 3, 2))
+    forms = {          # name -> (class names, model, keywords of generate_seeds); "streamed_<n>": NoiseStream segments of n steps
+        "dpmpp_ode": ("NV", m, dict(scheduler="dpmsolver++")),
+        "dpmpp_sde": ("NV", m, dict(scheduler="dpmsolver++", algorithm_type="sde-dpmsolver++")),
+        "dpmpp_sde_device": ("NV", m, dict(scheduler="dpmsolver++", algorithm_type="sde-dpmsolver++", noise="device")),
+        "guided": (["MEL", "BCC"], cm, dict(guidance_scale=3.0)),
+        "edited_jumps_two_calls": ("NV", m, dict(noise="device", init_image=image, mask=mask, n_resample=2, jump_length=3,
+                                                 max_call_steps=(passes + 1) // 2)),
+        "classifier_guided": ("NV", m, dict(noise="device", classifier_scale=2.0)),
+        "thresholded": ("NV", m, dict(thresholding=True, dynamic_thresholding_ratio=0.995, sample_max_value=2.0)),
+        # T = 8 as library calls of 3, 3 and 2 steps (eager in both modes: a replayed call has at least 4 steps), and of 4 and 4
+        "streamed_3_strided": ("NV", m, dict(return_trajectory=True, save_every_n=3)),
+        "streamed_4_strided": ("NV", m, dict(return_trajectory=True, save_every_n=3)),
+    }
     for graph in (0, 1):
         m.set_graph_mode(graph)
+        cm.set_graph_mode(graph)
+        mode = "graph" if graph else "eager"
         for noise in ("host", "device"):
             for rule, eta in (("ddpm", 0.0), ("ddim", 0.5)):
                 r = s.generate_seeds("NV", [3, 4], 8, (32, 32), noise=noise, scheduler=rule, eta=eta)
-                tag = f"sample.{'graph' if graph else 'eager'}.{noise}.{rule}"
+                tag = f"sample.{mode}.{noise}.{rule}"
                 emit(f"{tag}.latents", sha(r.latents))
                 emit(f"{tag}.images", sha(r.images))
                 emit(f"{tag}.graph_builds", _lib.load().sisic_unet_graph_builds(m.handle))
+        for name, (classes, model, kw) in forms.items():
+            s.noise_segment_steps = int(name.split("_")[1]) if name.startswith("streamed") else 64
+            r = s.generate_seeds(classes, [3, 4], 8, (32, 32), **kw)
+            tag = f"sample.{mode}.{name}"
+            emit(f"{tag}.latents", sha(r.latents))
+            emit(f"{tag}.images", sha(r.images))
+            if r.trajectory is not None:
+                emit(f"{tag}.trajectory", f"{sha(r.trajectory)} steps={r.trajectory_steps}")
+            emit(f"{tag}.calls", f"steps_done={r.steps_done} unet_passes={r.unet_passes}")
+            emit(f"{tag}.graph_builds", _lib.load().sisic_unet_graph_builds(model.handle))
     s.close()
     lat = Sampler(DEV, latency_mode=True)
     lat.add_model("NV", sd)
