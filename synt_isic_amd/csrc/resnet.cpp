@@ -9,10 +9,10 @@
 // Training (the second half of this file), BatchNorm frozen: the training forward is this forward, the backward pass is
 // the data-gradient walk of sisic_resnet_input_gradient with a weight gradient issued at every convolution, and after the
 // Adam step the folded filters are derived again on the device from the un-folded parameters.
-// Training with batch statistics (the last part): every convolution runs with its UNFOLDED filters and is followed by the
-// BatchNorm launches of batchnorm.hip; the walk gains a BatchNorm backward in front of every weight gradient, gamma and beta
-// train, the running statistics follow the batches, and every optimizer step derives the folded inference forms again from
-// (w, gamma, beta, running_mean, running_var) with the load path's arithmetic.
+// Training with batch statistics (an option of the same forward and the same walk): every convolution runs with its UNFOLDED
+// filters and is followed by the BatchNorm launches of batchnorm.hip; the walk gains a BatchNorm backward in front of every
+// weight gradient, gamma and beta train, the running statistics follow the batches, and every optimizer step derives the
+// folded inference forms again from (w, gamma, beta, running_mean, running_var) with the load path's arithmetic.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -299,18 +299,67 @@ int workspace_for(sisic_resnet* r, int B, int H, int W) {
     return SISIC_OK;
 }
 
-int run_conv(sisic_resnet* r, const FoldedConv& c, const float* in, int B, int H, int W, const float* residual, bool relu,
-             float* out, hipStream_t s) {
+// What every entry point that runs the network starts with, behind its own argument checks.
+int begin_run(sisic_resnet* r, const char* who, int B, int H, int W) {
+    if (!r->loaded) {
+        set_error("%s called before sisic_resnet_load", who);
+        return SISIC_ESTATE;
+    }
+    SISIC_HIP(hipSetDevice(r->ctx->device));
+    return workspace_for(r, B, H, W);
+}
+
+// The filter forms one launch reads: the BatchNorm-folded set with its bias, or (batch-statistics training) the forms of the
+// unfolded weight, which has no bias because its BatchNorm follows.  A view; the buffers stay with the FoldedConv.
+struct ConvForms {
+    const float* packed;
+    const float* wino;
+    const float* packed_t;
+    const float* wino_t;
+    const float* bias;
+};
+
+ConvForms forms_of(const FoldedConv& c, bool plain) {
+    if (plain) return {c.u.packed, c.u.wino, c.u.packed_t, c.u.wino_t, nullptr};
+    return {c.packed, c.wino, c.packed_t, c.wino_t, c.bias};
+}
+
+int conv_fwd(sisic_resnet* r, const FoldedConv& c, const ConvForms& f, const float* in, int B, int H, int W, const float* residual,
+             bool relu, float* out, hipStream_t s) {
     sisic_conv_args a{};
     a.in0 = in; a.c0 = c.cin; a.B = B; a.Hin = H; a.Win = W;
     a.ksize = c.k; a.stride = c.stride;
-    a.w_packed = c.packed; a.bias = c.bias; a.Cout = c.cout;
-    a.w_winograd = c.wino;
+    a.w_packed = f.packed; a.bias = f.bias; a.Cout = c.cout;
+    a.w_winograd = f.wino;
     a.residual = residual; a.relu = relu ? 1 : 0; a.out = out;
     return launch_conv2d(r->ctx, a, s);
 }
 
+// transposed convolution of `c` applied to g [B, c.cout, gh, gw]; stride 2: zero-insertion input (2gh x 2gw grid)
+int conv_t(sisic_resnet* r, const FoldedConv& c, const ConvForms& f, const float* g, int B, int gh, int gw, const float* residual,
+           float* out, hipStream_t s) {
+    sisic_conv_args a{};
+    a.in0 = g; a.c0 = c.cout; a.B = B; a.Hin = gh; a.Win = gw;
+    a.ksize = c.k; a.stride = 1;
+    a.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
+    a.w_packed = f.packed_t; a.w_winograd = f.wino_t; a.Cout = c.cin;
+    a.residual = residual; a.out = out;
+    return launch_conv2d(r->ctx, a, s);
+}
+
 inline int out_dim(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / stride + 1; }
+
+// training: tensor idx in the parameter and gradient arenas, and (batch statistics) in the arena of the running statistics
+float* param_of(ResnetTrain* tr, int idx) { return tr->param + tr->off[idx]; }
+float* grad_of(ResnetTrain* tr, int idx) { return tr->grad + tr->off[idx]; }
+float* stat_of(ResnetTrain* tr, int idx) { return tr->buf + tr->boff[idx]; }
+
+// what the training forward keeps of one BatchNorm: the convolution's output y and (mean, invstd, var) [3][C]
+struct BnKept {
+    float* y = nullptr;
+    float* st = nullptr;
+    int C = 0, HW = 0;
+};
 
 // The forward pass every entry point below runs: [pre-processing ->] stem -> max-pool -> the 8 blocks -> avgpool + fc.
 // Options in, what the caller goes on with out.  Every activation is a block of the caller's scope; what no option keeps
@@ -320,13 +369,17 @@ struct Trunk {
     float* stem_out = nullptr;   // stop after the stem, which writes here (sisic_resnet_stem)
     bool keep = false;           // keep c1, the max-pool output and every block's t1 and output (the input gradient reads them)
     bool keep_pre = false;       // keep the pre-processed input as well (the stem's weight gradient reads it)
+    // train with batch statistics (implies keep and keep_pre): every convolution step is conv (unfolded filters, no bias) ->
+    // moments (which also move the running statistics) -> apply, its y and moments kept; the head reads fc from the arena
+    ResnetTrain* bn = nullptr;
     float* pre = nullptr;        // keep_pre with preprocess: the stem's input [B, 3, 224, 224]
     const char* who = "resnet_input_gradient";
     bool split_last = false;     // last block: bn2(conv2(.)) alone into ylast, then relu(. + identity) (Grad-CAM reads ylast)
     float* logits = nullptr;     // where the logits go; nullptr: into a block of the scope, returned here
     float* features = nullptr;   // stop at the pooled features [B, 512], written here: no Linear, no logits (sisic_resnet_features)
-    struct Saved { float* t1; float* out; int h, w, bh, bw; };
+    struct Saved { float* t1; float* out; int h, w, bh, bw; BnKept k1, k2, kd; };
     std::vector<Saved> saved;    // keep: one per block
+    BnKept stem_k;               // bn: the stem's BatchNorm
     float* c1 = nullptr;         // relu(bn1(conv1(.))) [B, 64, c1h, c1w]
     float* m = nullptr;          // its max-pool
     int c1h = 0, c1w = 0;
@@ -335,7 +388,26 @@ struct Trunk {
     int h = 0, w = 0;
 };
 
+// One convolution step of the trunk: out = [relu](conv(in) [+ residual]) with the folded filters and their bias in one launch.
+// t.bn: out = [relu](bn(conv(in)) [+ residual]) with the unfolded filters and the batch's statistics, y and the moments kept in k.
+int conv_step(sisic_resnet* r, PoolScope& ws, const Trunk& t, const FoldedConv& c, const float* in, int B, int h, int w,
+              const float* residual, bool relu, float* out, BnKept& k, hipStream_t s) {
+    if (!t.bn) return conv_fwd(r, c, forms_of(c, false), in, B, h, w, residual, relu, out, s);
+    k.C = c.cout; k.HW = out_dim(h, c.k, c.stride) * out_dim(w, c.k, c.stride);
+    SISIC_TRY(ws.get((size_t)B * k.C * k.HW, &k.y));
+    SISIC_TRY(ws.get(3 * (size_t)k.C, &k.st));
+    SISIC_TRY(conv_fwd(r, c, forms_of(c, true), in, B, h, w, nullptr, false, k.y, s));
+    SISIC_TRY(launch_bn_moments(r->ctx, k.y, B, k.C, k.HW, BN_EPS, k.st, k.st + k.C, k.st + 2 * k.C, stat_of(t.bn, c.bn_m),
+                                stat_of(t.bn, c.bn_v), t.bn->momentum, s));
+    return launch_bn_apply(r->ctx, k.y, param_of(t.bn, c.bn_w), param_of(t.bn, c.bn_b), k.st, k.st + k.C, residual, relu, out, B, k.C,
+                           k.HW, s);
+}
+
 int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int W, Trunk& t, hipStream_t s) {
+    if (t.bn) {
+        t.keep = t.keep_pre = true;
+        t.bn->stats_moved = true;
+    }
     const float* cur = x;
     int h = H, w = W;
     float* pre = nullptr;
@@ -349,7 +421,7 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
     t.c1h = out_dim(h, 7, 2); t.c1w = out_dim(w, 7, 2);
     t.c1 = t.stem_out;
     if (!t.c1) SISIC_TRY(ws.get((size_t)B * 64 * t.c1h * t.c1w, &t.c1));
-    SISIC_TRY(run_conv(r, r->stem, cur, B, h, w, nullptr, true, t.c1, s));
+    SISIC_TRY(conv_step(r, ws, t, r->stem, cur, B, h, w, nullptr, true, t.c1, t.stem_k, s));
     if (pre && t.keep_pre) t.pre = pre;
     else if (pre) ws.put(pre);
     if (t.stem_out) return SISIC_OK;
@@ -366,29 +438,30 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
         const int bh = out_dim(h, 3, b.conv1.stride), bw = out_dim(w, 3, b.conv1.stride);
         if (t.keep)
             SISIC_REQUIRE(b.conv1.stride == 1 || (h % 2 == 0 && w % 2 == 0), "%s: odd feature map %dx%d", t.who, h, w);
+        BnKept k1, k2, kd;
         float* t1 = nullptr;
         SISIC_TRY(ws.get((size_t)B * b.conv1.cout * bh * bw, &t1));
-        SISIC_TRY(run_conv(r, b.conv1, act, B, h, w, nullptr, true, t1, s));
+        SISIC_TRY(conv_step(r, ws, t, b.conv1, act, B, h, w, nullptr, true, t1, k1, s));
         const float* identity = act;
         float* ds = nullptr;
         if (b.down.k) {
             SISIC_TRY(ws.get((size_t)B * b.down.cout * bh * bw, &ds));
-            SISIC_TRY(run_conv(r, b.down, act, B, h, w, nullptr, false, ds, s));
+            SISIC_TRY(conv_step(r, ws, t, b.down, act, B, h, w, nullptr, false, ds, kd, s));
             identity = ds;
         }
         float* t2 = nullptr;
         const size_t n_out = (size_t)B * b.conv2.cout * bh * bw;
         SISIC_TRY(ws.get(n_out, &t2));
         if (!split) {
-            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, identity, true, t2, s));    // relu(bn2(conv2) + identity)
+            SISIC_TRY(conv_step(r, ws, t, b.conv2, t1, B, bh, bw, identity, true, t2, k2, s));    // relu(bn2(conv2) + identity)
         } else {
             SISIC_TRY(ws.get(n_out, &t.ylast));
-            SISIC_TRY(run_conv(r, b.conv2, t1, B, bh, bw, nullptr, false, t.ylast, s));
+            SISIC_TRY(conv_step(r, ws, t, b.conv2, t1, B, bh, bw, nullptr, false, t.ylast, k2, s));
             SISIC_TRY(launch_add_relu(r->ctx, t.ylast, identity, t2, (int64_t)n_out, s));
         }
         if (ds) ws.put(ds);
         if (t.keep) {
-            t.saved.push_back({t1, t2, h, w, bh, bw});
+            t.saved.push_back({t1, t2, h, w, bh, bw, k1, k2, kd});
         } else {
             ws.put(t1);
             ws.put(act);
@@ -401,7 +474,9 @@ int run_trunk(sisic_resnet* r, PoolScope& ws, const float* x, int B, int H, int 
         return SISIC_OK;
     }
     if (!t.logits) SISIC_TRY(ws.get((size_t)B * r->num_classes, &t.logits));
-    SISIC_TRY(launch_avgpool_fc(r->ctx, act, r->d_fc_w, r->d_fc_b, t.logits, B, r->blocks.back().conv2.cout, h * w, r->num_classes, s));
+    const float* fc_w = t.bn ? param_of(t.bn, r->fc_w) : r->d_fc_w;
+    const float* fc_b = t.bn ? param_of(t.bn, r->fc_b) : r->d_fc_b;
+    SISIC_TRY(launch_avgpool_fc(r->ctx, act, fc_w, fc_b, t.logits, B, r->blocks.back().conv2.cout, h * w, r->num_classes, s));
     t.act = act; t.h = h; t.w = w;
     return SISIC_OK;
 }
@@ -549,12 +624,7 @@ int sisic_resnet_restore(sisic_resnet* r, void* stream) {
 int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, int H, int W, int preprocess,
                          void* stream) {
     SISIC_REQUIRE(r && x && logits && B > 0 && H > 0 && W > 0, "resnet_forward: bad arguments");
-    if (!r->loaded) {
-        set_error("resnet_forward called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, B, H, W));
+    SISIC_TRY(begin_run(r, "resnet_forward", B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
     PoolScope ws(r->pool, s);
     Trunk t;
@@ -566,12 +636,7 @@ int sisic_resnet_forward(sisic_resnet* r, const float* x, float* logits, int B, 
 // The forward up to and including the global average pool: the features the evaluation metrics are computed on.
 int sisic_resnet_features(sisic_resnet* r, sisic_resnet_features_args* a) {
     SISIC_REQUIRE(r && a && a->x && a->out && a->B > 0 && a->H > 0 && a->W > 0, "resnet_features: bad arguments");
-    if (!r->loaded) {
-        set_error("resnet_features called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, a->B, a->H, a->W));
+    SISIC_TRY(begin_run(r, "resnet_features", a->B, a->H, a->W));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     PoolScope ws(r->pool, s);
     Trunk t;
@@ -585,12 +650,7 @@ int sisic_resnet_features(sisic_resnet* r, sisic_resnet_features_args* a) {
 // max-abs statement instead of a statistical one.
 int sisic_resnet_stem(sisic_resnet* r, const float* x, float* c1_out, int B, int H, int W, int preprocess, void* stream) {
     SISIC_REQUIRE(r && x && c1_out && B > 0 && H > 0 && W > 0, "resnet_stem: bad arguments");
-    if (!r->loaded) {
-        set_error("resnet_stem called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, B, H, W));
+    SISIC_TRY(begin_run(r, "resnet_stem", B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
     PoolScope ws(r->pool, s);
     Trunk t;
@@ -607,10 +667,6 @@ int sisic_resnet_input_gradient(sisic_resnet* r, const float* x, int B, int H, i
                                 float* logits_out, void* stream) {
     SISIC_REQUIRE(r && x && grad_x && B > 0 && H > 0 && W > 0, "resnet_input_gradient: bad arguments");
     SISIC_REQUIRE(target >= 0 && target < r->num_classes, "resnet_input_gradient: class %d of %d", target, r->num_classes);
-    if (!r->loaded) {
-        set_error("resnet_input_gradient called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
     return resnet_input_gradient_walk(r, x, B, H, W, target, nullptr, grad_x, logits_out, static_cast<hipStream_t>(stream));
 }
 
@@ -622,12 +678,7 @@ int sisic_resnet_input_gradient_targets(sisic_resnet* r, sisic_resnet_targets_ar
         SISIC_REQUIRE(a->targets[b] >= 0 && a->targets[b] < r->num_classes,
                       "resnet_input_gradient_targets: target %lld of image %d is outside [0, %d)", (long long)a->targets[b], b,
                       r->num_classes);
-    if (!r->loaded) {
-        set_error("resnet_input_gradient_targets called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, a->B, a->H, a->W));
+    SISIC_TRY(begin_run(r, "resnet_input_gradient_targets", a->B, a->H, a->W));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     PoolScope ws(r->pool, s);
     float* tab = nullptr;
@@ -636,94 +687,6 @@ int sisic_resnet_input_gradient_targets(sisic_resnet* r, sisic_resnet_targets_ar
     return resnet_input_gradient_walk(r, a->x, a->B, a->H, a->W, 0, reinterpret_cast<const int*>(tab), a->grad_x, a->logits_out, s);
 }
 
-}  // extern "C"
-
-sisic_ctx* sisic::resnet_ctx(const sisic_resnet* r) { return r->ctx; }
-bool sisic::resnet_loaded(const sisic_resnet* r) { return r->loaded; }
-int sisic::resnet_num_classes(const sisic_resnet* r) { return r->num_classes; }
-uint64_t sisic::resnet_workspace_generation(const sisic_resnet* r) { return r->ws_gen; }
-
-int sisic::resnet_input_gradient_walk(sisic_resnet* r, const float* x, int B, int H, int W, int target, const int* targets_dev,
-                                      float* grad_x, float* logits_out, hipStream_t s) {
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, B, H, W));
-    PoolScope ws(r->pool, s);
-    // transposed convolution of `c` applied to g [B, c.cout, gh, gw]; stride 2: zero-insertion input (2gh x 2gw grid)
-    auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
-        sisic_conv_args a{};
-        a.in0 = g; a.c0 = c.cout; a.B = B; a.Hin = gh; a.Win = gw;
-        a.ksize = c.k; a.stride = 1;
-        a.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
-        a.w_packed = c.packed_t; a.w_winograd = c.wino_t; a.Cout = c.cin;
-        a.residual = residual; a.out = out;
-        return launch_conv2d(r->ctx, a, s);
-    };
-    const int S = 224;
-    SISIC_REQUIRE(H <= S && W <= S, "resnet_input_gradient: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
-    Trunk t;
-    t.keep = true;
-    SISIC_TRY(run_trunk(r, ws, x, B, H, W, t, s));
-    const std::vector<Trunk::Saved>& saved = t.saved;
-    const int C = r->blocks.back().conv2.cout, c1h = t.c1h, c1w = t.c1w;
-    if (logits_out)
-        SISIC_HIP(hipMemcpyAsync(logits_out, t.logits, (size_t)B * r->num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
-
-    // ---- backward
-    float* g = nullptr;                                   // d score / d (block output), already ReLU-masked
-    SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
-    if (targets_dev)
-        SISIC_TRY(launch_score_head_bwd_targets(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, targets_dev, s));
-    else
-        SISIC_TRY(launch_score_head_bwd(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, r->num_classes, target, s));
-    ws.put(t.logits);
-    for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
-        const Block& b = r->blocks[k];
-        const Trunk::Saved& sv = saved[k];
-        const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
-        float* tmp = nullptr;                             // conv2^T g, then the ReLU mask of t1
-        SISIC_TRY(ws.get(n_mid, &tmp));
-        SISIC_TRY(conv_t(b.conv2, g, sv.bh, sv.bw, nullptr, tmp));
-        SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
-        const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
-        float* da = nullptr;
-        SISIC_TRY(ws.get(n_in, &da));
-        if (!b.down.k) {
-            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, g, da));                 // + identity path
-        } else {
-            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
-            float* small = nullptr;
-            SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
-            SISIC_TRY(conv_t(b.down, g, sv.bh, sv.bw, nullptr, small));           // 1x1 at the low resolution
-            SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
-            ws.put(small);
-        }
-        ws.put(tmp);
-        ws.put(g);
-        ws.put(sv.t1);
-        ws.put(sv.out);
-        if (k > 0) {                                       // ReLU of the previous block's output
-            SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));
-        }
-        g = da;
-    }
-    // g = d score / d (max-pool output)
-    float* dc1 = nullptr;
-    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
-    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, t.c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
-    ws.put(g);
-    ws.put(t.m);
-    ws.put(t.c1);
-    float* dp = nullptr;
-    SISIC_TRY(ws.get((size_t)B * 3 * S * S, &dp));
-    SISIC_TRY(launch_stem_bwd(r->ctx, dc1, r->stem.raw, dp, B, 64, c1h, c1w, S, S, s));
-    ws.put(dc1);
-    SISIC_TRY(launch_preprocess_bwd(r->ctx, dp, x, grad_x, B, H, W, S, S, s));
-    ws.put(dp);
-    return SISIC_OK;
-}
-
-extern "C" {
-
 // Grad-CAM on layer4[-1].conv2 for the raw logit of `target` (xai/XAI.py:2945-3035; see gradcam_kernel): the forward
 // pass with the last block's conv2 (+BatchNorm) output kept before the residual add, then one small kernel per image.
 // cam: dev [B,224,224] in [0,1] (pytorch_grad_cam's double min-max scaling), logits_out: dev [B,n_classes] or NULL.
@@ -731,12 +694,7 @@ int sisic_resnet_gradcam(sisic_resnet* r, const float* x, int B, int H, int W, i
                          void* stream) {
     SISIC_REQUIRE(r && x && cam && B > 0 && H > 0 && W > 0, "resnet_gradcam: bad arguments");
     SISIC_REQUIRE(target >= 0 && target < r->num_classes, "resnet_gradcam: class %d of %d", target, r->num_classes);
-    if (!r->loaded) {
-        set_error("resnet_gradcam called before sisic_resnet_load");
-        return SISIC_ESTATE;
-    }
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, B, H, W));
+    SISIC_TRY(begin_run(r, "resnet_gradcam", B, H, W));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int S = 224;
     SISIC_REQUIRE(H <= S && W <= S, "resnet_gradcam: input %dx%d larger than the classifier's %dx%d", H, W, S, S);
@@ -819,10 +777,6 @@ float* loss_slot(ResnetTrain* tr) { return reinterpret_cast<float*>(static_cast<
 void* stats_scratch(ResnetTrain* tr) { return static_cast<char*>(tr->stats) + 16; }
 
 // ================================================================ batch-statistics BatchNorm ========================
-float* param_of(ResnetTrain* tr, int idx) { return tr->param + tr->off[idx]; }
-float* grad_of(ResnetTrain* tr, int idx) { return tr->grad + tr->off[idx]; }
-float* stat_of(ResnetTrain* tr, int idx) { return tr->buf + tr->boff[idx]; }
-
 // every form of the UNFOLDED weights from the parameter arena: what the training forward and the walk read
 int rebuild_plain_forms(sisic_resnet* r, hipStream_t s) {
     ResnetTrain* tr = r->train;
@@ -917,167 +871,125 @@ int train_begin_plain(sisic_resnet* r) {
     return rebuild_plain_forms(r, nullptr);
 }
 
-// what the training forward keeps of one BatchNorm: the convolution's output y and (mean, invstd, var) [3][C]
-struct BnKept {
-    float* y = nullptr;
-    float* st = nullptr;
-    int C = 0, HW = 0;
+// ================================================================ the backward walk ==================================
+// the labels (and class weights) a loss_backward call staged on the host, on the device: one block, ints first
+int stage_labels(PoolScope& ws, ResnetTrain* tr, int B, int n, bool class_weights, float** lab, hipStream_t s) {
+    SISIC_TRY(ws.get((size_t)B + n, lab));
+    SISIC_HIP(hipMemcpyAsync(*lab, tr->labels_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    if (class_weights) SISIC_HIP(hipMemcpyAsync(*lab + B, tr->cw_host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    return SISIC_OK;
+}
+
+// the weight gradient of c (wgrad_args) into the gradient arena
+int wgrad(sisic_resnet* r, ResnetTrain* tr, const FoldedConv& c, const float* in, const float* even, int B, int h, int w, const float* dy,
+          hipStream_t s) {
+    const WgradArgs wa = wgrad_args(c, in, even, B, h, w, dy, grad_of(tr, c.w_idx));
+    return launch_conv_wgrad(r->ctx, wa, tr->part, tr->part_floats, s);
+}
+
+// dy (a new block) = BatchNorm backward of g (masked by act > 0 first when act is given); dgamma and dbeta into the gradient arena;
+// y and the moments go back to the pool
+int bn_bwd(sisic_resnet* r, PoolScope& ws, ResnetTrain* tr, const FoldedConv& c, const BnKept& k, const float* g, const float* act, int B,
+           float** dy, hipStream_t s) {
+    SISIC_TRY(ws.get((size_t)B * k.C * k.HW, dy));
+    SISIC_TRY(launch_bn_bwd(r->ctx, g, k.y, act, k.st, k.st + k.C, param_of(tr, c.bn_w), *dy, grad_of(tr, c.bn_w), grad_of(tr, c.bn_b), B,
+                            k.C, k.HW, s));
+    ws.put(k.y);
+    ws.put(k.st);
+    return SISIC_OK;
+}
+
+// What the walk is asked for.  train == nullptr: the input gradient of the score of `target` (or of targets_dev[b]) into grad_x,
+// through the stem and the pre-processing; nothing on this path synchronises, waits on the host or allocates on a warm pool (a
+// captured sampling step runs it).  train: the cross-entropy loss against the staged labels and the weight gradients, down to
+// the stem's; with the trunk's `bn` option a BatchNorm backward stands in front of every weight gradient and transposed
+// convolution and the unfolded filters are read, without it the gradients of the folded filters are unfolded at the end.
+struct Walk {
+    int target = 0;
+    const int* targets_dev = nullptr;
+    float* grad_x = nullptr;
+    ResnetTrain* train = nullptr;
+    float* lab = nullptr;            // stage_labels' block
+    bool class_weights = false;
+    float* loss_out = nullptr;       // host
 };
 
-// loss and the 62 gradients with batch statistics (the caller, sisic_resnet_loss_backward, has checked the arguments, staged the
-// labels and sized the workspace).  Forward: conv (unfolded filters, no bias) -> moments (which also move the running statistics)
-// -> apply, everything kept.  Backward: the walk of the frozen mode with launch_bn_bwd in front of every weight gradient and
-// transposed convolution; the ReLU behind bn1 is masked inside its BatchNorm backward (from the kept t1), the other two
-// BatchNorms of a block and the stem's receive gradients that are masked already.
-int loss_backward_bn(sisic_resnet* r, sisic_resnet_train_args* a) {
-    ResnetTrain* tr = r->train;
-    const int B = a->B, H = a->H, W = a->W, n = r->num_classes;
-    hipStream_t s = static_cast<hipStream_t>(a->stream);
-    PoolScope ws(r->pool, s);
-    // convolution with the unfolded filters; transposed: of g [B, c.cout, gh, gw] (stride 2: zero-insertion input)
-    auto conv = [&](const FoldedConv& c, const float* in, int h, int w, float* out) {
-        sisic_conv_args ca{};
-        ca.in0 = in; ca.c0 = c.cin; ca.B = B; ca.Hin = h; ca.Win = w;
-        ca.ksize = c.k; ca.stride = c.stride;
-        ca.w_packed = c.u.packed; ca.w_winograd = c.u.wino; ca.Cout = c.cout;
-        ca.out = out;
-        return launch_conv2d(r->ctx, ca, s);
-    };
-    auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
-        sisic_conv_args ca{};
-        ca.in0 = g; ca.c0 = c.cout; ca.B = B; ca.Hin = gh; ca.Win = gw;
-        ca.ksize = c.k; ca.stride = 1;
-        ca.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
-        ca.w_packed = c.u.packed_t; ca.w_winograd = c.u.wino_t; ca.Cout = c.cin;
-        ca.residual = residual; ca.out = out;
-        return launch_conv2d(r->ctx, ca, s);
-    };
-    auto wgrad = [&](const FoldedConv& c, const float* in, const float* even, int h, int w, const float* dy) {
-        const WgradArgs wa = wgrad_args(c, in, even, B, h, w, dy, grad_of(tr, c.w_idx));
-        return launch_conv_wgrad(r->ctx, wa, tr->part, tr->part_floats, s);
-    };
-    // out = [relu](bn(conv(in)) [+ residual]), y and the moments kept
-    auto conv_bn = [&](const FoldedConv& c, const float* in, int h, int w, const float* residual, bool relu, float* out, BnKept& k) {
-        const int oh = out_dim(h, c.k, c.stride), ow = out_dim(w, c.k, c.stride);
-        k.C = c.cout; k.HW = oh * ow;
-        SISIC_TRY(ws.get((size_t)B * k.C * k.HW, &k.y));
-        SISIC_TRY(ws.get(3 * (size_t)k.C, &k.st));
-        SISIC_TRY(conv(c, in, h, w, k.y));
-        SISIC_TRY(launch_bn_moments(r->ctx, k.y, B, k.C, k.HW, BN_EPS, k.st, k.st + k.C, k.st + 2 * k.C, stat_of(tr, c.bn_m),
-                                    stat_of(tr, c.bn_v), tr->momentum, s));
-        return launch_bn_apply(r->ctx, k.y, param_of(tr, c.bn_w), param_of(tr, c.bn_b), k.st, k.st + k.C, residual, relu, out, B, k.C, k.HW, s);
-    };
-    // dy (a new block) = BatchNorm backward of g; dgamma and dbeta into the gradient arena; y and the moments go back to the pool
-    auto bn_bwd = [&](const FoldedConv& c, BnKept& k, const float* g, const float* act, float** dy) {
-        SISIC_TRY(ws.get((size_t)B * k.C * k.HW, dy));
-        SISIC_TRY(launch_bn_bwd(r->ctx, g, k.y, act, k.st, k.st + k.C, param_of(tr, c.bn_w), *dy, grad_of(tr, c.bn_w), grad_of(tr, c.bn_b), B,
-                                k.C, k.HW, s));
-        ws.put(k.y);
-        ws.put(k.st);
-        return SISIC_OK;
-    };
-    float* lab = nullptr;
-    SISIC_TRY(ws.get((size_t)B + n, &lab));
-    SISIC_HIP(hipMemcpyAsync(lab, tr->labels_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    if (a->class_weights) SISIC_HIP(hipMemcpyAsync(lab + B, tr->cw_host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-
-    // ---- forward
-    tr->stats_moved = true;
-    const float* x = a->x;
-    int h = H, w = W;
-    float* pre = nullptr;
-    if (a->preprocess) {
-        const int S = 224;
-        SISIC_TRY(ws.get((size_t)B * 3 * S * S, &pre));
-        SISIC_TRY(launch_preprocess(r->ctx, a->x, pre, B, H, W, S, S, s));
-        x = pre; h = S; w = S;
-    }
-    const int sh = h, sw = w;
-    const int c1h = out_dim(h, 7, 2), c1w = out_dim(w, 7, 2);
-    BnKept stem_k;
-    float* c1 = nullptr;
-    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &c1));
-    SISIC_TRY(conv_bn(r->stem, x, h, w, nullptr, true, c1, stem_k));
-    h = c1h; w = c1w;
-    const int mh = out_dim(h, 3, 2), mw = out_dim(w, 3, 2);
-    float* m = nullptr;
-    SISIC_TRY(ws.get((size_t)B * 64 * mh * mw, &m));
-    SISIC_TRY(launch_maxpool(r->ctx, c1, m, B, 64, h, w, s));
-    struct Saved { BnKept k1, k2, kd; float* t1; float* out; int h, w, bh, bw; };
-    std::vector<Saved> saved(r->blocks.size());
-    float* act = m;
-    h = mh; w = mw;
-    for (size_t i = 0; i < r->blocks.size(); ++i) {
-        const Block& b = r->blocks[i];
-        Saved& sv = saved[i];
-        sv.h = h; sv.w = w;
-        sv.bh = out_dim(h, 3, b.conv1.stride); sv.bw = out_dim(w, 3, b.conv1.stride);
-        const size_t n_out = (size_t)B * b.conv1.cout * sv.bh * sv.bw;
-        SISIC_TRY(ws.get(n_out, &sv.t1));
-        SISIC_TRY(conv_bn(b.conv1, act, h, w, nullptr, true, sv.t1, sv.k1));
-        const float* identity = act;
-        float* ds = nullptr;
-        if (b.down.k) {
-            SISIC_TRY(ws.get(n_out, &ds));
-            SISIC_TRY(conv_bn(b.down, act, h, w, nullptr, false, ds, sv.kd));
-            identity = ds;
-        }
-        SISIC_TRY(ws.get(n_out, &sv.out));
-        SISIC_TRY(conv_bn(b.conv2, sv.t1, sv.bh, sv.bw, identity, true, sv.out, sv.k2));    // relu(bn2(conv2) + identity): one pass
-        if (ds) ws.put(ds);
-        act = sv.out; h = sv.bh; w = sv.bw;
-    }
-    const int C = r->blocks.back().conv2.cout;
-    float* logits = nullptr;
-    SISIC_TRY(ws.get((size_t)B * n, &logits));
-    SISIC_TRY(launch_avgpool_fc(r->ctx, act, param_of(tr, r->fc_w), param_of(tr, r->fc_b), logits, B, C, h * w, n, s));
-    if (a->logits_out)
-        SISIC_HIP(hipMemcpyAsync(a->logits_out, logits, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+// The transposed network behind run_trunk(t) with its activations kept: the head, the eight blocks last to first (at each the
+// gradient g at the block's output, already ReLU-masked, becomes the one at its input), the max-pool, then the mode's tail.  A
+// weight gradient is issued from the tensors the walk holds anyway -- the gradient at conv2's and at downsample's output is g,
+// the one at conv1's output is tmp after the mask of t1 (with batch statistics: their BatchNorm backwards dy2, dyd and dy1, the
+// last of which applies the mask from the kept t1), the inputs are the kept activations.  Every block of the pool the forward
+// kept goes back here.  x: the trunk's input [B, 3, H, W].
+int backward_walk(sisic_resnet* r, PoolScope& ws, const Trunk& t, const float* x, int B, int H, int W, const Walk& o, float* logits_out,
+                  hipStream_t s) {
+    ResnetTrain* tr = o.train;
+    const bool bn = t.bn != nullptr;
+    const int n = r->num_classes, C = r->blocks.back().conv2.cout, c1h = t.c1h, c1w = t.c1w;
+    const std::vector<Trunk::Saved>& saved = t.saved;
+    if (logits_out) SISIC_HIP(hipMemcpyAsync(logits_out, t.logits, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     // ---- head
-    float* dlogits = nullptr;
-    SISIC_TRY(ws.get((size_t)B * n, &dlogits));
-    SISIC_TRY(launch_ce_head(r->ctx, logits, reinterpret_cast<const int*>(lab), a->class_weights ? lab + B : nullptr, B, n, loss_slot(tr),
-                             dlogits, s));
-    float* g = nullptr;                                   // d loss / d (block output), already ReLU-masked
-    SISIC_TRY(ws.get((size_t)B * C * h * w, &g));
-    SISIC_TRY(launch_fc_head_bwd(r->ctx, dlogits, param_of(tr, r->fc_w), act, g, grad_of(tr, r->fc_w), grad_of(tr, r->fc_b), B, C, h * w, n, s));
-    ws.put(dlogits);
-    ws.put(logits);
-    ws.put(lab);
+    float* g = nullptr;
+    if (!tr) {
+        SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
+        if (o.targets_dev)
+            SISIC_TRY(launch_score_head_bwd_targets(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, n, o.targets_dev, s));
+        else
+            SISIC_TRY(launch_score_head_bwd(r->ctx, t.logits, r->d_fc_w, t.act, g, B, C, t.h * t.w, n, o.target, s));
+        ws.put(t.logits);
+    } else {
+        float* dlogits = nullptr;
+        SISIC_TRY(ws.get((size_t)B * n, &dlogits));
+        SISIC_TRY(launch_ce_head(r->ctx, t.logits, reinterpret_cast<const int*>(o.lab), o.class_weights ? o.lab + B : nullptr, B, n,
+                                 loss_slot(tr), dlogits, s));
+        SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
+        SISIC_TRY(launch_fc_head_bwd(r->ctx, dlogits, bn ? param_of(tr, r->fc_w) : r->d_fc_w, t.act, g, grad_of(tr, r->fc_w),
+                                     grad_of(tr, r->fc_b), B, C, t.h * t.w, n, s));
+        ws.put(dlogits);
+        ws.put(t.logits);
+        ws.put(o.lab);
+    }
     // ---- the blocks, last to first
     for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
         const Block& b = r->blocks[k];
-        Saved& sv = saved[k];
-        const float* in_act = k > 0 ? saved[k - 1].out : m;            // the block's input [B, conv1.cin, sv.h, sv.w]
-        float* dy2 = nullptr;
-        SISIC_TRY(bn_bwd(b.conv2, sv.k2, g, nullptr, &dy2));
-        SISIC_TRY(wgrad(b.conv2, sv.t1, nullptr, sv.bh, sv.bw, dy2));
+        const Trunk::Saved& sv = saved[k];
+        const float* in_act = k > 0 ? saved[k - 1].out : t.m;          // the block's input [B, conv1.cin, sv.h, sv.w]
+        const ConvForms f1 = forms_of(b.conv1, bn), f2 = forms_of(b.conv2, bn), fd = forms_of(b.down, bn);
+        float* dy2 = g;                                   // the gradient at conv2's output
+        if (bn) SISIC_TRY(bn_bwd(r, ws, tr, b.conv2, sv.k2, g, nullptr, B, &dy2, s));
+        if (tr) SISIC_TRY(wgrad(r, tr, b.conv2, sv.t1, nullptr, B, sv.bh, sv.bw, dy2, s));
+        const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
         float* tmp = nullptr;                             // conv2^T dy2 = the gradient at t1, before its ReLU mask
-        SISIC_TRY(ws.get((size_t)B * b.conv2.cout * sv.bh * sv.bw, &tmp));
-        SISIC_TRY(conv_t(b.conv2, dy2, sv.bh, sv.bw, nullptr, tmp));
-        ws.put(dy2);
-        float* dy1 = nullptr;
-        SISIC_TRY(bn_bwd(b.conv1, sv.k1, tmp, sv.t1, &dy1));          // the mask of t1 is applied here
-        ws.put(tmp);
-        SISIC_TRY(wgrad(b.conv1, in_act, nullptr, sv.h, sv.w, dy1));
+        SISIC_TRY(ws.get(n_mid, &tmp));
+        SISIC_TRY(conv_t(r, b.conv2, f2, dy2, B, sv.bh, sv.bw, nullptr, tmp, s));
+        float* dy1 = tmp;                                 // the gradient at conv1's output, masked
+        if (bn) {
+            ws.put(dy2);
+            SISIC_TRY(bn_bwd(r, ws, tr, b.conv1, sv.k1, tmp, sv.t1, B, &dy1, s));
+            ws.put(tmp);
+        } else {
+            SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
+        }
+        if (tr) SISIC_TRY(wgrad(r, tr, b.conv1, in_act, nullptr, B, sv.h, sv.w, dy1, s));
         const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
         float* da = nullptr;
         SISIC_TRY(ws.get(n_in, &da));
         if (!b.down.k) {
-            SISIC_TRY(conv_t(b.conv1, dy1, sv.bh, sv.bw, g, da));                 // + identity path
+            SISIC_TRY(conv_t(r, b.conv1, f1, dy1, B, sv.bh, sv.bw, g, da, s));        // + identity path
         } else {
-            SISIC_TRY(conv_t(b.conv1, dy1, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
-            float* dyd = nullptr;
-            SISIC_TRY(bn_bwd(b.down, sv.kd, g, nullptr, &dyd));
-            float* small = nullptr;                                               // first the even pixels of the input ...
+            SISIC_TRY(conv_t(r, b.conv1, f1, dy1, B, sv.bh, sv.bw, nullptr, da, s));  // stride 2: zero-insertion input
+            float* dyd = g;                               // the gradient at downsample's output
+            if (bn) SISIC_TRY(bn_bwd(r, ws, tr, b.down, sv.kd, g, nullptr, B, &dyd, s));
+            float* small = nullptr;
             SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
-            SISIC_TRY(launch_gather_even(r->ctx, in_act, small, B * b.down.cin, sv.h, sv.w, s));
-            SISIC_TRY(wgrad(b.down, nullptr, small, sv.h, sv.w, dyd));
-            SISIC_TRY(conv_t(b.down, dyd, sv.bh, sv.bw, nullptr, small));         // ... then the 1x1 at the low resolution
+            if (tr) {                                     // first the even pixels of the input (ResNet18's downsamples are stride 2) ...
+                SISIC_TRY(launch_gather_even(r->ctx, in_act, small, B * b.down.cin, sv.h, sv.w, s));
+                SISIC_TRY(wgrad(r, tr, b.down, nullptr, small, B, sv.h, sv.w, dyd, s));
+            }
+            SISIC_TRY(conv_t(r, b.down, fd, dyd, B, sv.bh, sv.bw, nullptr, small, s));  // ... then the 1x1 at the low resolution
             SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
             ws.put(small);
-            ws.put(dyd);
+            if (bn) ws.put(dyd);
         }
         ws.put(dy1);
         ws.put(g);
@@ -1086,20 +998,35 @@ int loss_backward_bn(sisic_resnet* r, sisic_resnet_train_args* a) {
         if (k > 0) SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));      // ReLU of the previous block's output
         g = da;
     }
-    // g = d loss / d (max-pool output)
+    // ---- g = the gradient at the max-pool output
     float* dc1 = nullptr;
     SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
-    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, c1, dc1, B * 64, c1h, c1w, s));         // includes the stem's ReLU mask
+    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, t.c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
     ws.put(g);
-    ws.put(m);
-    ws.put(c1);
-    float* dys = nullptr;
-    SISIC_TRY(bn_bwd(r->stem, stem_k, dc1, nullptr, &dys));
-    ws.put(dc1);
-    SISIC_TRY(launch_stem_wgrad(r->ctx, x, dys, grad_of(tr, r->stem.w_idx), B, sh, sw, tr->part, tr->part_floats, s));
+    ws.put(t.m);
+    ws.put(t.c1);
+    const int sh = t.preprocess ? 224 : H, sw = t.preprocess ? 224 : W;             // the stem's input plane
+    if (!tr) {
+        float* dp = nullptr;
+        SISIC_TRY(ws.get((size_t)B * 3 * sh * sw, &dp));
+        SISIC_TRY(launch_stem_bwd(r->ctx, dc1, r->stem.raw, dp, B, 64, c1h, c1w, sh, sw, s));
+        ws.put(dc1);
+        SISIC_TRY(launch_preprocess_bwd(r->ctx, dp, x, o.grad_x, B, H, W, sh, sw, s));
+        ws.put(dp);
+        return SISIC_OK;
+    }
+    // training stops at the stem's weight gradient: nothing below it is trainable
+    float* dys = dc1;                                     // the gradient at the stem convolution's output
+    if (bn) {
+        SISIC_TRY(bn_bwd(r, ws, tr, r->stem, t.stem_k, dc1, nullptr, B, &dys, s));
+        ws.put(dc1);
+    }
+    SISIC_TRY(launch_stem_wgrad(r->ctx, t.pre ? t.pre : x, dys, grad_of(tr, r->stem.w_idx), B, sh, sw, tr->part, tr->part_floats, s));
     ws.put(dys);
-    if (pre) ws.put(pre);
-    SISIC_HIP(hipMemcpyAsync(&a->loss, loss_slot(tr), sizeof(float), hipMemcpyDeviceToHost, s));
+    if (t.pre) ws.put(t.pre);
+    if (!bn)                                              // the chain differentiated the folded filters
+        SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) { return launch_unfold_grad(r->ctx, grad_of(tr, c.w_idx), c.sc, c.cout, c.cin, c.k, s); }));
+    SISIC_HIP(hipMemcpyAsync(o.loss_out, loss_slot(tr), sizeof(float), hipMemcpyDeviceToHost, s));
     SISIC_HIP(hipStreamSynchronize(s));
     return SISIC_OK;
 }
@@ -1204,6 +1131,28 @@ int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
 
 }  // namespace
 
+sisic_ctx* sisic::resnet_ctx(const sisic_resnet* r) { return r->ctx; }
+bool sisic::resnet_loaded(const sisic_resnet* r) { return r->loaded; }
+int sisic::resnet_num_classes(const sisic_resnet* r) { return r->num_classes; }
+uint64_t sisic::resnet_workspace_generation(const sisic_resnet* r) { return r->ws_gen; }
+
+// The input gradient (sisic_resnet_input_gradient[_targets], and each classifier-guided step of sisic_sample_frames_clf, there
+// under stream capture): the forward with the activations kept, then the walk in its input-gradient form.
+int sisic::resnet_input_gradient_walk(sisic_resnet* r, const float* x, int B, int H, int W, int target, const int* targets_dev,
+                                      float* grad_x, float* logits_out, hipStream_t s) {
+    SISIC_TRY(begin_run(r, "resnet_input_gradient", B, H, W));
+    PoolScope ws(r->pool, s);
+    SISIC_REQUIRE(H <= 224 && W <= 224, "resnet_input_gradient: input %dx%d larger than the classifier's %dx%d", H, W, 224, 224);
+    Trunk t;
+    t.keep = true;
+    SISIC_TRY(run_trunk(r, ws, x, B, H, W, t, s));
+    Walk o;
+    o.target = target;
+    o.targets_dev = targets_dev;
+    o.grad_x = grad_x;
+    return backward_walk(r, ws, t, x, B, H, W, o, logits_out, s);
+}
+
 extern "C" {
 
 int sisic_resnet_train_begin(sisic_resnet* r) { return train_begin(r, 0, 0.0); }
@@ -1294,11 +1243,9 @@ int sisic_resnet_write(sisic_resnet* r, int what, int index, const float* host_i
     return SISIC_OK;
 }
 
-// loss = cross_entropy(resnet18(x), labels, weight) and its gradient with respect to the 22 trainable tensors.
-// Forward: run_trunk with everything kept.  Backward: the walk of sisic_resnet_input_gradient seeded by d loss / d logits; at
-// each convolution the weight gradient is issued from the tensors the walk holds anyway -- the gradient at conv2's and at
-// downsample's output is g (after the block's ReLU mask), the one at conv1's output is tmp (after its mask), the inputs are the
-// kept activations.  The walk stops at the stem's output: nothing below it is trainable.
+// loss = cross_entropy(resnet18(x), labels, weight) and its gradient with respect to the trainable tensors: the 22 with BatchNorm
+// frozen, the 62 with batch statistics (which also move the running statistics).  The checks, run_trunk with everything kept,
+// then backward_walk seeded by d loss / d logits.
 int sisic_resnet_loss_backward(sisic_resnet* r, sisic_resnet_train_args* a) {
     SISIC_TRY(require_train(r, "resnet_loss_backward"));
     SISIC_REQUIRE(a && a->x && a->labels && a->B > 0 && a->H > 0 && a->W > 0, "resnet_loss_backward: bad arguments");
@@ -1320,104 +1267,22 @@ int sisic_resnet_loss_backward(sisic_resnet* r, sisic_resnet_train_args* a) {
         tr->cw_host.assign(a->class_weights, a->class_weights + n);
     }
     SISIC_TRY(check_train_geometry(H, W, a->preprocess, tr->bn_mode == 1 ? B : 0));
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_TRY(workspace_for(r, B, H, W));
-    if (tr->bn_mode == 1) return loss_backward_bn(r, a);
+    SISIC_TRY(begin_run(r, "resnet_loss_backward", B, H, W));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
     PoolScope ws(r->pool, s);
-    auto conv_t = [&](const FoldedConv& c, const float* g, int gh, int gw, const float* residual, float* out) {
-        sisic_conv_args ca{};
-        ca.in0 = g; ca.c0 = c.cout; ca.B = B; ca.Hin = gh; ca.Win = gw;
-        ca.ksize = c.k; ca.stride = 1;
-        ca.upsample = (c.k == 3 && c.stride == 2) ? 2 : 0;
-        ca.w_packed = c.packed_t; ca.w_winograd = c.wino_t; ca.Cout = c.cin;
-        ca.residual = residual; ca.out = out;
-        return launch_conv2d(r->ctx, ca, s);
-    };
-    auto wgrad = [&](const FoldedConv& c, const float* in, const float* even, int h, int w, const float* dy) {
-        const WgradArgs wa = wgrad_args(c, in, even, B, h, w, dy, tr->grad + tr->off[c.w_idx]);
-        return launch_conv_wgrad(r->ctx, wa, tr->part, tr->part_floats, s);
-    };
-    // labels (and class weights) on the device: one block, ints first
-    float* lab = nullptr;
-    SISIC_TRY(ws.get((size_t)B + n, &lab));
-    SISIC_HIP(hipMemcpyAsync(lab, tr->labels_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    if (a->class_weights) SISIC_HIP(hipMemcpyAsync(lab + B, tr->cw_host.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-
+    Walk o;
+    o.train = tr;
+    o.class_weights = a->class_weights != nullptr;
+    o.loss_out = &a->loss;
+    SISIC_TRY(stage_labels(ws, tr, B, n, o.class_weights, &o.lab, s));
     Trunk t;
     t.preprocess = a->preprocess != 0;
     t.keep = true;
     t.keep_pre = true;
     t.who = "resnet_loss_backward";
+    if (tr->bn_mode == 1) t.bn = tr;
     SISIC_TRY(run_trunk(r, ws, a->x, B, H, W, t, s));
-    const std::vector<Trunk::Saved>& saved = t.saved;
-    const int C = r->blocks.back().conv2.cout, c1h = t.c1h, c1w = t.c1w;
-    if (a->logits_out)
-        SISIC_HIP(hipMemcpyAsync(a->logits_out, t.logits, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-
-    // ---- head
-    float* dlogits = nullptr;
-    SISIC_TRY(ws.get((size_t)B * n, &dlogits));
-    SISIC_TRY(launch_ce_head(r->ctx, t.logits, reinterpret_cast<const int*>(lab), a->class_weights ? lab + B : nullptr, B, n,
-                             loss_slot(tr), dlogits, s));
-    float* g = nullptr;                                   // d loss / d (block output), already ReLU-masked
-    SISIC_TRY(ws.get((size_t)B * C * t.h * t.w, &g));
-    SISIC_TRY(launch_fc_head_bwd(r->ctx, dlogits, r->d_fc_w, t.act, g, tr->grad + tr->off[r->fc_w], tr->grad + tr->off[r->fc_b], B, C,
-                                 t.h * t.w, n, s));
-    ws.put(dlogits);
-    ws.put(t.logits);
-    ws.put(lab);
-    // ---- the blocks, last to first
-    for (int k = (int)r->blocks.size() - 1; k >= 0; --k) {
-        const Block& b = r->blocks[k];
-        const Trunk::Saved& sv = saved[k];
-        const float* in_act = k > 0 ? saved[k - 1].out : t.m;          // the block's input [B, conv1.cin, sv.h, sv.w]
-        SISIC_TRY(wgrad(b.conv2, sv.t1, nullptr, sv.bh, sv.bw, g));
-        const size_t n_mid = (size_t)B * b.conv2.cout * sv.bh * sv.bw;
-        float* tmp = nullptr;                             // conv2^T g, then the ReLU mask of t1
-        SISIC_TRY(ws.get(n_mid, &tmp));
-        SISIC_TRY(conv_t(b.conv2, g, sv.bh, sv.bw, nullptr, tmp));
-        SISIC_TRY(launch_relu_bwd(r->ctx, tmp, sv.t1, tmp, (int64_t)n_mid, s));
-        SISIC_TRY(wgrad(b.conv1, in_act, nullptr, sv.h, sv.w, tmp));
-        const size_t n_in = (size_t)B * b.conv1.cin * sv.h * sv.w;
-        float* da = nullptr;
-        SISIC_TRY(ws.get(n_in, &da));
-        if (!b.down.k) {
-            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, g, da));                 // + identity path
-        } else {
-            SISIC_TRY(conv_t(b.conv1, tmp, sv.bh, sv.bw, nullptr, da));           // stride 2: zero-insertion input
-            float* small = nullptr;                                               // first the even pixels of the input ...
-            SISIC_TRY(ws.get((size_t)B * b.down.cin * sv.bh * sv.bw, &small));
-            SISIC_TRY(launch_gather_even(r->ctx, in_act, small, B * b.down.cin, sv.h, sv.w, s));      // (ResNet18's downsamples are stride 2)
-            SISIC_TRY(wgrad(b.down, nullptr, small, sv.h, sv.w, g));
-            SISIC_TRY(conv_t(b.down, g, sv.bh, sv.bw, nullptr, small));           // ... then the 1x1 at the low resolution
-            SISIC_TRY(launch_scatter_add_even(r->ctx, da, small, B * b.down.cin, sv.h, sv.w, s));
-            ws.put(small);
-        }
-        ws.put(tmp);
-        ws.put(g);
-        ws.put(sv.t1);
-        ws.put(sv.out);
-        if (k > 0) SISIC_TRY(launch_relu_bwd(r->ctx, da, saved[k - 1].out, da, (int64_t)n_in, s));      // ReLU of the previous block's output
-        g = da;
-    }
-    // g = d loss / d (max-pool output)
-    float* dc1 = nullptr;
-    SISIC_TRY(ws.get((size_t)B * 64 * c1h * c1w, &dc1));
-    SISIC_TRY(launch_maxpool_bwd(r->ctx, g, t.c1, dc1, B * 64, c1h, c1w, s));       // includes the stem's ReLU mask
-    ws.put(g);
-    ws.put(t.m);
-    ws.put(t.c1);
-    const int sh = t.preprocess ? 224 : H, sw = t.preprocess ? 224 : W;
-    SISIC_TRY(launch_stem_wgrad(r->ctx, t.pre ? t.pre : a->x, dc1, tr->grad + tr->off[r->stem.w_idx], B, sh, sw, tr->part,
-                                tr->part_floats, s));
-    ws.put(dc1);
-    if (t.pre) ws.put(t.pre);
-    // the chain differentiated the folded filters
-    SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) { return launch_unfold_grad(r->ctx, tr->grad + tr->off[c.w_idx], c.sc, c.cout, c.cin, c.k, s); }));
-    SISIC_HIP(hipMemcpyAsync(&a->loss, loss_slot(tr), sizeof(float), hipMemcpyDeviceToHost, s));
-    SISIC_HIP(hipStreamSynchronize(s));
-    return SISIC_OK;
+    return backward_walk(r, ws, t, a->x, B, H, W, o, a->logits_out, s);
 }
 
 // clip_grad_norm_ (optional) + torch.optim.Adam on the arenas, then every derived form of the new weights.

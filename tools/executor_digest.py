@@ -20,7 +20,8 @@ from synt_isic_amd import _lib, ops  # noqa: E402
 from synt_isic_amd.classifier import HipMelanomaClassifier  # noqa: E402
 from synt_isic_amd.sampler import Sampler  # noqa: E402
 from synt_isic_amd.scheduler import resample_schedule  # noqa: E402
-from synt_isic_amd.train import HipAdam, mse_loss  # noqa: E402
+from synt_isic_amd.arch import resnet18_buffer_names  # noqa: E402
+from synt_isic_amd.train import HipAdam, HipClassifierAdam, mse_loss  # noqa: E402
 from synt_isic_amd.weights import synthetic_resnet18_state_dict, synthetic_unet_state_dict  # noqa: E402
 
 DEV = torch.device("cuda", 0)
@@ -130,7 +131,8 @@ def train_items(sd) -> None:
 
 
 def classifier_items() -> None:
-    clf = HipMelanomaClassifier(num_classes=7).load_state_dict(synthetic_resnet18_state_dict()).to(DEV).eval()
+    sd = synthetic_resnet18_state_dict()
+    clf = HipMelanomaClassifier(num_classes=7).load_state_dict(sd).to(DEV).eval()
     x = (rand((2, 3, 48, 40), 31) * 0.8).to(DEV)
     emit("clf.logits", sha(clf(x)))
     emit("clf.logits.workspace_bytes", clf.workspace_bytes())
@@ -144,6 +146,38 @@ def classifier_items() -> None:
     emit("clf.grad_cam.workspace_bytes", clf.workspace_bytes())
     emit("clf.logits_b3", sha(clf((rand((3, 3, 48, 40), 32) * 0.8).to(DEV))))          # the shape change empties the pool
     emit("clf.logits_b3.workspace_bytes", clf.workspace_bytes())
+    grad, logits = clf.input_gradient(x, [1, 4])
+    emit("clf.input_gradient_targets", sha(grad) + " logits=" + sha(logits))
+    emit("clf.input_gradient_targets.workspace_bytes", clf.workspace_bytes())
+    emit("clf.features", sha(clf.features(x)))
+    emit("clf.features.workspace_bytes", clf.workspace_bytes())
+    # training, BatchNorm frozen and with batch statistics: the raw input through the 224x224 resize, then pre-processed inputs at
+    # the smallest plane the geometry check admits (32x32: a last plane of 1x1) and at a non-square one
+    cw = torch.tensor([1.0, 0.5, 2.0, 1.5, 0.25, 3.0, 0.75])
+    batches = (("raw_48x40", x, [1, 4], False),
+               ("pre_32x32", rand((2, 3, 32, 32), 33).to(DEV), [0, 6], True),
+               ("pre_64x96", rand((3, 3, 64, 96), 34).to(DEV), [2, 5, 3], True))
+    for mode in ("frozen", "batch"):
+        clf.load_state_dict(sd)                  # the weights the previous section's step moved
+        opt = HipClassifierAdam(clf, batchnorm=mode)
+        for tag, images, labels, preprocessed in batches:
+            loss, logits = clf.loss_backward(images, labels, class_weights=cw, preprocessed=preprocessed)
+            name = f"clf.train.{mode}.{tag}"
+            emit(f"{name}.loss", float(loss).hex() + " logits=" + sha(logits))
+            grads = clf.grads()
+            emit(f"{name}.grads", f"{sha(*grads.values())} n={len(grads)}")
+            if mode == "batch":
+                stats = [clf.read_tensor(0, n) for n in resnet18_buffer_names(clf.num_classes)]
+                emit(f"{name}.running_stats", f"{sha(*stats)} n={len(stats)}")
+            emit(f"{name}.workspace_bytes", clf.workspace_bytes())
+        opt.step()
+        emit(f"clf.train.{mode}.logits_after_step", sha(clf(x)))
+        emit(f"clf.train.{mode}.logits_after_step.workspace_bytes", clf.workspace_bytes())
+        opt.close()
+    clf.load_state_dict(sd)
+    grad, logits = clf.input_gradient(x, 1)      # the first item's bits again
+    emit("clf.input_gradient_after_training", sha(grad) + " logits=" + sha(logits))
+    emit("clf.input_gradient_after_training.workspace_bytes", clf.workspace_bytes())
 
 
 def main() -> None:
