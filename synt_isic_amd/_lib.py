@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 _LIB_PATH = os.environ.get("SISIC_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                              "libsisic_hip.so")
@@ -22,12 +22,37 @@ SISIC_EHIP = -2
 SISIC_ESTATE = -3
 SISIC_ECANCEL = -4
 
-# step rules of the sampling loop (SISIC_RULE_*) and the DDIM rule's flag
-RULE_DDPM = 0
-RULE_DDIM = 1
-RULE_DPMPP = 2
-RULE_FLAG_CLIPPED_OUTPUT = 1
-RULE_ROW_WIDTH = {RULE_DDPM: 5, RULE_DDIM: 5, RULE_DPMPP: 6}      # SISIC_RULE_ROW_WIDTH
+
+class StepRule(NamedTuple):
+    """One step rule of the sampling loop, as every layer above the C ABI needs it described."""
+    name: str                   # the public name: ``scheduler=`` of generate(), the ``rule`` of a scheduler mirror
+    id: int                     # SISIC_RULE_*
+    row_width: int              # SISIC_RULE_ROW_WIDTH: floats per row of its coefficient table
+    stem: str                   # sisic_<stem>_step, sisic_<stem>_step_rng, sisic_<stem>_step_edit
+    title: str                  # as messages spell it
+    takes_hist: bool            # its step reads and writes the previous step's x0
+    clipped_output_flag: int    # SISIC_RULE_FLAG_CLIPPED_OUTPUT where its step takes use_clipped_model_output, else 0
+
+
+# the one place a rule is described; everything below, ops._step, the scheduler mirrors and the sampler read it
+RULES = {r.name: r for r in (StepRule("ddpm", 0, 5, "ddpm", "DDPM", False, 0),
+                             StepRule("ddim", 1, 5, "ddim", "DDIM", False, 1),
+                             StepRule("dpmsolver++", 2, 6, "dpmpp", "DPM-Solver++", True, 0))}
+RULE_DDPM, RULE_DDIM, RULE_DPMPP = (r.id for r in RULES.values())
+RULE_FLAG_CLIPPED_OUTPUT = RULES["ddim"].clipped_output_flag
+RULE_ROW_WIDTH = {r.id: r.row_width for r in RULES.values()}
+STEP_FORMS = ("", "_rng", "_edit")      # suffix of the entry: z from a buffer; drawn in the kernel; that plus the edit epilogue
+
+
+def _step_argtypes(rule: StepRule, form: str) -> list:
+    """the argument types of ``sisic_<stem>_step<form>`` in the order include/sisic.h declares (``ops._step`` fills them)"""
+    p, f = C.c_void_p, C.c_float
+    tensors = [p, p] + [p] * (form == "") + [p] * rule.takes_hist + [p]             # eps, x, [z], [hist], out
+    size = [C.c_int64] if form == "" else [C.c_int, C.c_int64, p, C.c_uint32]       # n, or B, n_per_image, seeds, step
+    scalars = [f] * (rule.row_width + 1) + [C.c_int] * bool(rule.clipped_output_flag)   # the row, clip, [flag]
+    edit = [p, p, C.c_int, C.c_int64, f, f, f, f] if form == "_edit" else []        # x0k, mask, C, HW, ck, sk, ja, jb
+    return [p] + tensors + size + scalars + edit + [p]                              # ctx ... stream
+
 
 # what a model's output means (SISIC_PRED_*), under the names diffusers gives the three types
 PRED_EPSILON = 0
@@ -222,8 +247,6 @@ SIGNATURES = {
                                         C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "sisic_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sisic_ddpm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sisic_denorm_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "sisic_denorm_u8_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p]),
@@ -250,22 +273,9 @@ SIGNATURES = {
                                    C.c_uint32, C.c_void_p]),
     "sisic_noise_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint32,
                                    C.c_uint32, C.c_void_p]),
-    "sisic_ddpm_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
-                                      C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                      C.c_void_p]),
     "sisic_sample_frames_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                           C.c_float, C.POINTER(C.c_uint64), C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                           C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
-    "sisic_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]),
-    "sisic_ddim_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
-                                      C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                      C.c_int, C.c_void_p]),
-    "sisic_dpmpp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
-    "sisic_dpmpp_step_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
-                                       C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_float, C.c_float, C.c_void_p]),
     "sisic_sample_frames_rule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                            C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                            C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
@@ -280,18 +290,6 @@ SIGNATURES = {
     "sisic_guide_eps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "sisic_clf_guide_eps": (C.c_int, [C.c_void_p, C.POINTER(ClfGuideArgs)]),
     "sisic_sample_frames_clf": (C.c_int, [C.c_void_p, C.POINTER(SampleClfArgs)]),
-    "sisic_ddpm_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
-                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_void_p]),
-    "sisic_ddim_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
-                                       C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_void_p]),
-    "sisic_dpmpp_step_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
-                                        C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_float,
-                                        C.c_float, C.c_float, C.c_void_p]),
     "sisic_sample_frames_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p, c_float_p,
                                            C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, c_int64_p, C.c_int,
                                            C.c_float, C.c_void_p, C.c_void_p, c_float_p, C.c_void_p, C.POINTER(C.c_int),
@@ -406,6 +404,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sisic_profile_reset": (C.c_int, [C.c_void_p]),
 }
+SIGNATURES.update({f"sisic_{r.stem}_step{form}": (C.c_int, _step_argtypes(r, form))
+                   for r in RULES.values() for form in STEP_FORMS})
 
 
 def lib_path() -> str:

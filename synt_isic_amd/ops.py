@@ -18,25 +18,31 @@ from ._lib import ConvArgs, check
 _ctx_by_device = {}
 
 
+def _context(device, code: int, tag: Optional[str] = None) -> C.c_void_p:
+    """The ``sisic_ctx`` of ``_ctx_by_device`` for a device, a step prediction type (SISIC_PRED_*) and a tag, created on first
+    use.  The key is the device index alone for the default context (epsilon, no tag), which is the only one whose step
+    prediction type is never set; ``(index, code)`` for the other untagged ones."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"synt_isic_amd runs on MI355X (torch device 'cuda'); got '{device}'. There is no CPU path.")
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, code, tag) if tag is not None else idx if code == _lib.PRED_EPSILON else (idx, code)
+    if key not in _ctx_by_device:
+        lib = _lib.load()
+        h = C.c_void_p()
+        check(lib.sisic_create(idx, C.byref(h)))
+        if key != idx:
+            check(lib.sisic_set_step_prediction_type(h, code))
+        _ctx_by_device[key] = h
+    return _ctx_by_device[key]
+
+
 def context(device: torch.device, step_prediction: str = "epsilon") -> C.c_void_p:
     """One ``sisic_ctx`` per (device, step prediction type), created on first use.  ``step_prediction`` says what the ``eps``
     argument of the single-step wrappers below means to the context (sisic_set_step_prediction_type); it is set once, when the
     context is created, and never changed: the default context stays an epsilon context and no call toggles shared state.
     Everything but the step wrappers uses the default context."""
-    code = _lib.prediction_code(step_prediction)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"synt_isic_amd runs on MI355X (torch device 'cuda'); got '{device}'. There is no CPU path.")
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = idx if code == _lib.PRED_EPSILON else (idx, code)
-    if key not in _ctx_by_device:
-        lib = _lib.load()
-        h = C.c_void_p()
-        check(lib.sisic_create(idx, C.byref(h)))
-        if code != _lib.PRED_EPSILON:
-            check(lib.sisic_set_step_prediction_type(h, code))
-        _ctx_by_device[key] = h
-    return _ctx_by_device[key]
+    return _context(device, _lib.prediction_code(step_prediction))
 
 
 def check_threshold(threshold):
@@ -62,7 +68,7 @@ def _step_context(x: torch.Tensor, prediction_type: str, threshold, B: Optional[
     prediction type that only thresholded steps use; its setting and its image size are host state the entry reads when it
     is called, so they are set before every call.  Images: ``B`` of them, or x's leading dimension."""
     if threshold is None:
-        return context(x.device, prediction_type)
+        return _context(x.device, _lib.prediction_code(prediction_type))
     ratio, max_value = check_threshold(threshold)
     if ratio == 0.0:
         raise ValueError("threshold=(0, ...) switches thresholding off: pass threshold=None")
@@ -74,16 +80,7 @@ def _step_context(x: torch.Tensor, prediction_type: str, threshold, B: Optional[
     if npi > THRESHOLD_MAX_PER_IMAGE:
         raise ValueError(f"thresholding takes images of at most 2**24 elements, these have {npi}")
     lib = _lib.load()
-    code = _lib.prediction_code(prediction_type)
-    device = torch.device(x.device)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, code, "threshold")
-    if key not in _ctx_by_device:
-        h = C.c_void_p()
-        check(lib.sisic_create(idx, C.byref(h)))
-        check(lib.sisic_set_step_prediction_type(h, code))
-        _ctx_by_device[key] = h
-    h = _ctx_by_device[key]
+    h = _context(x.device, _lib.prediction_code(prediction_type), "threshold")
     check(lib.sisic_set_step_thresholding(h, ratio, max_value))
     check(lib.sisic_set_step_image_elems(h, npi))
     return h
@@ -313,19 +310,70 @@ def attention(qkv: torch.Tensor, head_dim: int = 8) -> torch.Tensor:
     return out
 
 
+_DDPM, _DDIM, _DPMPP = _lib.RULES.values()
+_step_entries = {}              # (stem, form) -> the function of the library (``_lib.load()``: one per process), once looked up
+
+
+def _step(rule: _lib.StepRule, eps, x, coef, clip, out, prediction_type, threshold, z=None, hist=None, flag=False, seeds=None,
+          step=0, x0k=None, mask=None, erow=None) -> torch.Tensor:
+    """The nine single-step wrappers below: ``sisic_<stem>_step<form>`` of ``rule`` (_lib.RULES), its arguments in the order
+    include/sisic.h declares.  The form is what the call carries: no ``seeds``, the buffer form with its ``z``; ``seeds`` and
+    ``step``, the ``_rng`` form; with ``x0k``, ``mask`` and ``erow`` as well, the ``_edit`` form.  Every check runs before
+    anything is allocated or set; nothing here waits for the stream."""
+    form = "" if seeds is None else "_rng" if x0k is None else "_edit"
+    row = tuple(map(float, coef))
+    if len(row) != rule.row_width:
+        raise ValueError(f"a {rule.title} row holds {rule.row_width} values")
+    n, B = x.numel(), None
+    if form:
+        arr = _seed_array(seeds)
+        B = len(arr)
+        if n % B:
+            raise ValueError(f"{n} elements are not {B} equal images")
+        if form == "_edit":
+            if x0k.numel() != n:
+                raise ValueError(f"the known image holds {x0k.numel()} elements for an x of {n}")
+            if mask.numel() % B or mask.numel() == 0 or (n // B) % (mask.numel() // B):
+                raise ValueError(f"a mask of {mask.numel()} elements is not [B, 1, H, W] for {B} images of {n // B} elements")
+            hw = mask.numel() // B
+            ck, sk, ja, jb = (float(v) for v in erow)
+    if rule.takes_hist and hist.numel() != n:
+        raise ValueError(f"hist holds {hist.numel()} elements for an x of {n}")
+    ctx = _step_context(x, prediction_type, threshold, B)
+    if out is None:
+        out = empty_like(x)
+    args = [ctx, _ptr(eps, "eps"), _ptr(x, "x")]
+    if not form:
+        args.append(_ptr(z, "z"))
+    if rule.takes_hist:
+        args.append(_ptr(hist, "hist"))
+    args.append(_ptr(out, "out"))
+    if form:
+        seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
+        args += (B, n // B, seeds_dev.data_ptr(), int(step))
+    else:
+        args.append(n)
+    args += row
+    args.append(float(clip))
+    if rule.clipped_output_flag:
+        args.append(int(bool(flag)))
+    if form == "_edit":
+        args += (_ptr(x0k, "x0k"), _ptr(mask, "mask"), n // B // hw, hw, ck, sk, ja, jb)
+    args.append(_stream(x.device))
+    entry = _step_entries.get((rule.stem, form))
+    if entry is None:
+        entry = _step_entries[rule.stem, form] = getattr(_lib.load(), f"sisic_{rule.stem}_step{form}")
+    check(entry(*args))
+    return out
+
+
 def ddpm_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
               out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """coef = (sqrt_beta_prod, sqrt_alpha_prod, c0, c1, sigma).  ``prediction_type`` (here and in every step wrapper below):
     what ``eps`` holds -- "epsilon", "sample" (x0) or "v_prediction" (include/sisic.h SISIC_PRED_*).  ``threshold`` (likewise):
     None, or ``(dynamic_thresholding_ratio, sample_max_value)`` for dynamic thresholding of x0 in place of ``clip``, which is
     then not read; x is [B, ...] (or, in the ``_rng`` and ``_edit`` wrappers, len(seeds) equal images)."""
-    lib = _lib.load()
-    if out is None:
-        out = empty_like(x)
-    sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
-                              x.numel(), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
-    return out
+    return _step(_DDPM, eps, x, coef, clip, out, prediction_type, threshold, z)
 
 
 def guide_eps(eps_c: torch.Tensor, eps_u: torch.Tensor, guidance_scale: float,
@@ -401,18 +449,7 @@ def ddpm_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
                   out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``ddpm_step`` with z generated in the kernel: eps, x are [B, ...] (or flat with B = len(seeds) equal images);
     image b draws ``noise_fill([seeds[b]], n_per_image, step)``."""
-    lib = _lib.load()
-    arr = _seed_array(seeds)
-    B = len(arr)
-    if x.numel() % B:
-        raise ValueError(f"{x.numel()} elements are not {B} equal images")
-    if out is None:
-        out = empty_like(x)
-    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
-    sb, sa, c0, c1, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddpm_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
-                                  seeds_dev.data_ptr(), int(step), sb, sa, c0, c1, sigma, float(clip), _stream(x.device)))
-    return out
+    return _step(_DDPM, eps, x, coef, clip, out, prediction_type, threshold, seeds=seeds, step=step)
 
 
 def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coef, clip: float = 1.0,
@@ -420,14 +457,7 @@ def ddim_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], coe
               prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_ddim_step: coef = (sqrt_beta_prod, sqrt_alpha_prod, c_prev, c_dir, sigma), a row of
     ``HipDDIMScheduler.coefficient_table``.  z None or sigma == 0: no noise is added."""
-    lib = _lib.load()
-    if out is None:
-        out = empty_like(x)
-    sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(out, "out"),
-                              x.numel(), sb, sa, c_prev, c_dir, sigma, float(clip), int(bool(use_clipped_model_output)),
-                              _stream(x.device)))
-    return out
+    return _step(_DDIM, eps, x, coef, clip, out, prediction_type, threshold, z, None, use_clipped_model_output)
 
 
 def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, clip: float = 1.0,
@@ -435,19 +465,8 @@ def ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, cl
                   prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``ddim_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
-    lib = _lib.load()
-    arr = _seed_array(seeds)
-    B = len(arr)
-    if x.numel() % B:
-        raise ValueError(f"{x.numel()} elements are not {B} equal images")
-    if out is None:
-        out = empty_like(x)
-    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
-    sb, sa, c_prev, c_dir, sigma = (float(v) for v in coef)
-    check(lib.sisic_ddim_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(out, "out"), B, x.numel() // B,
-                                  seeds_dev.data_ptr(), int(step), sb, sa, c_prev, c_dir, sigma, float(clip),
-                                  int(bool(use_clipped_model_output)), _stream(x.device)))
-    return out
+    return _step(_DDIM, eps, x, coef, clip, out, prediction_type, threshold, flag=use_clipped_model_output,
+                 seeds=seeds, step=step)
 
 
 def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hist: torch.Tensor, coef, clip: float = 0.0,
@@ -455,67 +474,14 @@ def dpmpp_step(eps: torch.Tensor, x: torch.Tensor, z: Optional[torch.Tensor], hi
     """sisic_dpmpp_step: coef = (sigma_t, alpha_t, cx, k0, sigma, k1), a row of
     ``HipDPMSolverMultistepScheduler.coefficient_table``.  hist: the previous step's x0, a tensor of x's size that the
     call overwrites with this step's x0 and reads only when k1 != 0.  z None or sigma == 0: no noise is added."""
-    lib = _lib.load()
-    if hist.numel() != x.numel():
-        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
-    if out is None:
-        out = empty_like(x)
-    sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step(_step_context(x, prediction_type, threshold), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(z, "z"), _ptr(hist, "hist"),
-                               _ptr(out, "out"), x.numel(), sb, sa, cx, k0, sigma, k1, float(clip), _stream(x.device)))
-    return out
+    return _step(_DPMPP, eps, x, coef, clip, out, prediction_type, threshold, z, hist)
 
 
 def dpmpp_step_rng(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, clip: float = 0.0,
                    out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """``dpmpp_step`` with z generated in the kernel, as ``ddpm_step_rng``: image b draws
     ``noise_fill([seeds[b]], n_per_image, step)``, and nothing when sigma == 0."""
-    lib = _lib.load()
-    arr = _seed_array(seeds)
-    B = len(arr)
-    if x.numel() % B:
-        raise ValueError(f"{x.numel()} elements are not {B} equal images")
-    if hist.numel() != x.numel():
-        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
-    if out is None:
-        out = empty_like(x)
-    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
-    sb, sa, cx, k0, sigma, k1 = (float(v) for v in coef)
-    check(lib.sisic_dpmpp_step_rng(_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x"), _ptr(hist, "hist"), _ptr(out, "out"), B,
-                                   x.numel() // B, seeds_dev.data_ptr(), int(step), sb, sa, cx, k0, sigma, k1, float(clip),
-                                   _stream(x.device)))
-    return out
-
-
-def _step_edit(entry: str, eps, x, seeds, step, hist, row, flag, clip, x0k, mask, erow, out, prediction_type="epsilon",
-               threshold=None):
-    """the three ``*_step_edit`` wrappers: the ``_rng`` wrapper's arguments, the known image, the mask and the edit row"""
-    lib = _lib.load()
-    arr = _seed_array(seeds)
-    B = len(arr)
-    if x.numel() % B:
-        raise ValueError(f"{x.numel()} elements are not {B} equal images")
-    npi = x.numel() // B
-    if x0k.numel() != x.numel():
-        raise ValueError(f"the known image holds {x0k.numel()} elements for an x of {x.numel()}")
-    if mask.numel() % B or mask.numel() == 0 or npi % (mask.numel() // B):
-        raise ValueError(f"a mask of {mask.numel()} elements is not [B, 1, H, W] for {B} images of {npi} elements")
-    hw = mask.numel() // B
-    if hist is not None and hist.numel() != x.numel():
-        raise ValueError(f"hist holds {hist.numel()} elements for an x of {x.numel()}")
-    if out is None:
-        out = empty_like(x)
-    seeds_dev = upload(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64), x.device)      # the uint64 bit patterns
-    ck, sk, ja, jb = (float(v) for v in erow)
-    args = [_step_context(x, prediction_type, threshold, B), _ptr(eps, "eps"), _ptr(x, "x")]
-    if hist is not None:
-        args.append(_ptr(hist, "hist"))
-    args += [_ptr(out, "out"), B, npi, seeds_dev.data_ptr(), int(step), *(float(v) for v in row), float(clip)]
-    if flag is not None:
-        args.append(int(bool(flag)))
-    args += [_ptr(x0k, "x0k"), _ptr(mask, "mask"), npi // hw, hw, ck, sk, ja, jb, _stream(x.device)]
-    check(getattr(lib, entry)(*args))
-    return out
+    return _step(_DPMPP, eps, x, coef, clip, out, prediction_type, threshold, hist=hist, seeds=seeds, step=step)
 
 
 def ddpm_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
@@ -523,19 +489,16 @@ def ddpm_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x
     """sisic_ddpm_step_edit: ``ddpm_step_rng`` with the inpainting epilogue (include/sisic.h) fused into the kernel.
     x0k: the known image, fp32 of x's size, finite; mask: fp32 [B,1,H,W] (1 = keep); erow = (ck, sk, ja, jb).  The epilogue
     draws under tags 5 (``sk != 0``) and 6 (``jb != 0``) of ``noise_fill`` at the same ``step``."""
-    if len(tuple(coef)) != 5:
-        raise ValueError("a DDPM row holds 5 values")
-    return _step_edit("sisic_ddpm_step_edit", eps, x, seeds, step, None, coef, None, clip, x0k, mask, erow, out, prediction_type, threshold)
+    return _step(_DDPM, eps, x, coef, clip, out, prediction_type, threshold, seeds=seeds, step=step, x0k=x0k,
+                 mask=mask, erow=erow)
 
 
 def ddim_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, coef, x0k: torch.Tensor, mask: torch.Tensor, erow,
                    clip: float = 1.0, use_clipped_model_output: bool = False,
                    out: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_ddim_step_edit: ``ddim_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``."""
-    if len(tuple(coef)) != 5:
-        raise ValueError("a DDIM row holds 5 values")
-    return _step_edit("sisic_ddim_step_edit", eps, x, seeds, step, None, coef, use_clipped_model_output, clip, x0k, mask, erow,
-                      out, prediction_type, threshold)
+    return _step(_DDIM, eps, x, coef, clip, out, prediction_type, threshold, flag=use_clipped_model_output,
+                 seeds=seeds, step=step, x0k=x0k, mask=mask, erow=erow)
 
 
 def dpmpp_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: torch.Tensor, coef, x0k: torch.Tensor,
@@ -543,9 +506,21 @@ def dpmpp_step_edit(eps: torch.Tensor, x: torch.Tensor, seeds, step: int, hist: 
                     prediction_type: str = "epsilon", threshold=None) -> torch.Tensor:
     """sisic_dpmpp_step_edit: ``dpmpp_step_rng`` with the inpainting epilogue, as ``ddpm_step_edit``; ``hist`` receives the
     model's predicted x0, which the epilogue does not touch."""
-    if len(tuple(coef)) != 6:
-        raise ValueError("a DPM-Solver++ row holds 6 values")
-    return _step_edit("sisic_dpmpp_step_edit", eps, x, seeds, step, hist, coef, None, clip, x0k, mask, erow, out, prediction_type, threshold)
+    return _step(_DPMPP, eps, x, coef, clip, out, prediction_type, threshold, hist=hist, seeds=seeds,
+                 step=step, x0k=x0k, mask=mask, erow=erow)
+
+
+def add_noise(x0: torch.Tensor, noise: torch.Tensor, a: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """sisic_add_noise: ``out[b] = a[b] * x0[b] + c[b] * noise[b]`` (two products and one sum, each rounded to fp32) for
+    x0 = [B, ...] and ``noise`` of its size, with HOST fp32 rows a, c of B values."""
+    B = x0.shape[0]
+    if a.numel() != B:
+        raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
+    a, c = upload(torch.stack([a, c]), x0.device)          # pinned, non-blocking: the call does not wait for the stream
+    out = empty_like(x0)
+    check(_lib.load().sisic_add_noise(context(x0.device), _ptr(x0, "x0"), _ptr(noise, "noise"), a.data_ptr(), c.data_ptr(),
+                                      out.data_ptr(), B, x0[0].numel(), _stream(x0.device)))
+    return out
 
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, *, x2=None, stride=1, upsample=False, gn_scale=None,

@@ -49,8 +49,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .scheduler import (HipDDIMScheduler, HipDDPMScheduler, HipDPMSolverMultistepScheduler, check_dpmpp_options, edit_rows,
-                        resample_schedule)
+from .scheduler import MIRRORS, check_dpmpp_options, check_thresholding, edit_rows, resample_schedule      # noqa: F401
 from .unet import HipUNet2DModel
 
 ISIC_CLASSES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")   # xai/XAI.py:196
@@ -97,19 +96,20 @@ def _check_noise_mode(noise: str) -> str:
     return noise
 
 
-SCHEDULERS = ("ddpm", "ddim", "dpmsolver++")
+SCHEDULERS = tuple(_lib.RULES)
 
 
 def _check_scheduler(scheduler: str, eta: float, use_clipped_model_output: bool = False, solver_order: int = 2,
                      algorithm_type: str = "dpmsolver++") -> str:
-    if scheduler not in SCHEDULERS:
+    mirror = MIRRORS.get(scheduler) if isinstance(scheduler, str) else None
+    if mirror is None:
         raise ValueError(f"scheduler must be one of {SCHEDULERS}, got {scheduler!r}")
-    if scheduler != "ddim" and (float(eta) != 0.0 or use_clipped_model_output):
+    if not mirror._takes_eta and (float(eta) != 0.0 or use_clipped_model_output):
         raise ValueError("eta and use_clipped_model_output belong to scheduler='ddim'; the DDPM and DPM-Solver++ rules have "
                          "neither")
     if not 0.0 <= float(eta) <= 1.0:
         raise ValueError(f"eta must lie in 0 .. 1, got {eta!r}")
-    if scheduler == "dpmsolver++":
+    if mirror._takes_solver_options:
         try:
             check_dpmpp_options(solver_order, algorithm_type)
         except NotImplementedError as e:
@@ -120,15 +120,12 @@ def _check_scheduler(scheduler: str, eta: float, use_clipped_model_output: bool 
 
 
 def _rule_tables(scheduler, eta: float, use_clipped_model_output: bool):
-    """(host [T, row width] coefficient table, SISIC_RULE_* id, rule flags) of a scheduler mirror, by its ``rule`` attribute.
-    Sigma is column 4 under every rule.  A DPM-Solver++ mirror carries its own solver_order and algorithm_type."""
-    rule = _check_scheduler(getattr(scheduler, "rule", "ddpm"), eta, use_clipped_model_output)
-    if rule == "dpmsolver++":
-        return scheduler.coefficient_table().contiguous(), _lib.RULE_DPMPP, 0
-    if rule == "ddim":
-        flags = _lib.RULE_FLAG_CLIPPED_OUTPUT if use_clipped_model_output else 0
-        return scheduler.coefficient_table(eta).contiguous(), _lib.RULE_DDIM, flags
-    return scheduler.coefficient_table().contiguous(), _lib.RULE_DDPM, 0
+    """(host [T, row width] coefficient table, SISIC_RULE_* id, rule flags) of a scheduler mirror (its ``rule_table``), with the
+    refusals of eta and use_clipped_model_output under a rule that has neither.  Sigma is column 4 under every rule.  A
+    DPM-Solver++ mirror carries its own solver_order and algorithm_type."""
+    _check_scheduler(scheduler.rule, eta, use_clipped_model_output)
+    rule, table, flags = scheduler.rule_table(eta, use_clipped_model_output)
+    return table, rule.id, flags
 
 
 @dataclass(frozen=True)
@@ -404,17 +401,6 @@ def _frame_rows(T: int, return_trajectory: bool, save_indices: Optional[Sequence
     return kept, rows
 
 
-def check_thresholding(thresholding, dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0):
-    """the three published thresholding arguments as ``(ratio, sample_max_value)`` or None (off); ValueError for a ratio
-    outside (0, 1] or a maximum below 1 -- before anything touches the GPU"""
-    if not thresholding:
-        return None
-    ratio, max_value = ops.check_threshold((dynamic_thresholding_ratio, sample_max_value))
-    if ratio == 0.0:
-        raise ValueError("dynamic_thresholding_ratio 0 with thresholding=True: the library reads ratio 0 as 'off'")
-    return ratio, max_value
-
-
 @torch.no_grad()
 def run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor, noise, *, thresholding: Optional[bool] = None,
                       dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, **kwargs) -> SampleResult:
@@ -649,7 +635,7 @@ def _run_sampling_loop(model: HipUNet2DModel, scheduler, x_T: torch.Tensor,
     unless a ``NoiseStream``'s segments or an edited run's ``max_call_steps`` cut it), then call by call with the noise of its
     source."""
     B, Cc, H, W = x_T.shape
-    rule_name = getattr(scheduler, "rule", "ddpm")
+    rule_name = scheduler.rule
     if classifier is not None:
         _check_classifier_guidance(model, classifier, noise, guidance, edit, B)
     if isinstance(noise, NoiseStream) and rule_name == "dpmsolver++":
@@ -978,14 +964,10 @@ class Sampler:
         """model_manager.py:196-212; scheduler="ddim": the DDIM mirror over the same tables and timestep grid;
         scheduler="dpmsolver++": the DPM-Solver++ mirror over the same tables and the same grid (its "leading" spacing; the
         mirror's own default is the published "linspace"), with the clamp of x0 the other two rules apply (clip_sample=True)."""
-        rule = _check_scheduler(scheduler, 0.0, False, solver_order, algorithm_type)
-        if rule == "dpmsolver++":
-            s = HipDPMSolverMultistepScheduler(num_train_timesteps=1000, beta_schedule=self.beta_schedule,
-                                               solver_order=solver_order, algorithm_type=algorithm_type, clip_sample=True,
-                                               timestep_spacing="leading")
-        else:
-            s = (HipDDIMScheduler if rule == "ddim" else HipDDPMScheduler)(num_train_timesteps=1000,
-                                                                          beta_schedule=self.beta_schedule)
+        mirror = MIRRORS[_check_scheduler(scheduler, 0.0, False, solver_order, algorithm_type)]
+        own = dict(solver_order=solver_order, algorithm_type=algorithm_type, clip_sample=True,
+                   timestep_spacing="leading") if mirror._takes_solver_options else {}
+        s = mirror(num_train_timesteps=1000, beta_schedule=self.beta_schedule, **own)
         s.set_timesteps(max(1, min(1000, int(T))))
         return s
 

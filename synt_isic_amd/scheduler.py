@@ -28,7 +28,7 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 @dataclass
@@ -45,8 +45,9 @@ def _betas_for_alpha_bar(n: int, max_beta: float = 0.999) -> torch.Tensor:
                         dtype=torch.float32)
 
 
-def _threshold_of(thresholding: bool, dynamic_thresholding_ratio: float, sample_max_value: float):
-    """the three published thresholding arguments as the ``threshold`` of the step wrappers: None, or a checked (ratio, max).
+def check_thresholding(thresholding, dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0):
+    """the three published thresholding arguments as the ``threshold`` of the step wrappers: None (off), or a checked
+    ``(ratio, sample_max_value)``; ValueError for a ratio outside (0, 1] or a maximum below 1 -- before anything touches the GPU.
     The published classes hand ratio 0 to torch.quantile; here it is refused with the rest, because ratio 0 is how the library
     spells "off"."""
     if not thresholding:
@@ -61,61 +62,67 @@ _THRESHOLD_ARGS = {"thresholding", "dynamic_thresholding_ratio", "sample_max_val
 _THRESHOLD_HINT = " (dynamic thresholding: call set_thresholding() on the scheduler)"
 
 
-def _set_thresholding(self, thresholding: bool = True, dynamic_thresholding_ratio: float = 0.995,
-                      sample_max_value: float = 1.0) -> None:
-    """Dynamic thresholding of x0 (Saharia et al. 2022) for this scheduler's ``step`` and for ``run_sampling_loop``: the
-    published ``thresholding``, ``dynamic_thresholding_ratio`` and ``sample_max_value``, kept in ``self.threshold`` as (ratio, max)
-    or None (and in ``config`` where the constructor takes them).  It takes
-    precedence over ``clip_sample``.  ``HipDDPMScheduler`` also takes the three in its constructor; the constructors of the
-    DDIM and DPM-Solver++ mirrors keep refusing them, as they always have, and this method is their way in.  ValueError for a
-    ratio outside (0, 1] or a maximum below 1."""
-    self.threshold = _threshold_of(thresholding, dynamic_thresholding_ratio, sample_max_value)
-    # (config holds what the constructor takes, so that cls(**vars(config)) builds the scheduler again: the DDPM mirror's does)
-    if hasattr(self.config, "thresholding"):
-        self.config.thresholding = bool(thresholding)
-        self.config.dynamic_thresholding_ratio = dynamic_thresholding_ratio
-        self.config.sample_max_value = sample_max_value
+def _timestep_grid(spacing: str, n_train: int, T: int, steps_offset: int) -> np.ndarray:
+    """the T descending int64 timesteps of a run under one of the three published spacings"""
+    if spacing == "linspace":                                    # from t = n_train - 1
+        return np.linspace(0, n_train - 1, T + 1).round()[::-1][:-1].copy().astype(np.int64)
+    if spacing == "leading":                                     # the integer ratio: ends at t = steps_offset
+        ts = (np.arange(0, T) * (n_train // T)).round()[::-1].copy().astype(np.int64)
+        ts += steps_offset
+        return ts
+    return np.round(np.arange(n_train, 0, -n_train / T)).astype(np.int64) - 1      # "trailing": the float ratio, no offset
 
 
-class HipDDPMScheduler:
+class _HipScheduler:
+    """What the three mirrors share: the forward process (beta tables, ``add_noise``, ``get_velocity``), which does not depend
+    on the sampling rule, the timestep grids, thresholding, and the host side of ``step`` around the one ``ops.*_step`` call.
+    A mirror adds its constructor (signature, refusals, ``config`` fields), its rows and that call."""
     order = 1
-    rule = "ddpm"            # the step rule ``run_sampling_loop`` runs this scheduler's table under
+    rule: str                   # a name of _lib.RULES: the step rule ``run_sampling_loop`` runs this scheduler's table under
+    _published: str             # the diffusers class it mirrors, as messages name it
+    _output: type               # the dataclass ``step`` returns
+    _takes_eta = False          # ``coefficient_table`` and ``step`` take eta and use_clipped_model_output
+    _takes_solver_options = False       # the constructor takes solver_order and algorithm_type
 
-    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
-                 beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = True,
-                 prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
-                 timestep_spacing: str = "leading", steps_offset: int = 0, thresholding: bool = False,
-                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, **unsupported):
+    def _begin(self, unsupported: dict, prediction_type: str, thresholding=(False, 0.995, 1.0)) -> None:
+        """the refusals every constructor starts with, and ``threshold``"""
         if unsupported:
-            raise NotImplementedError(f"unsupported DDPMScheduler arguments: {sorted(unsupported)}")
-        self.threshold = _threshold_of(thresholding, dynamic_thresholding_ratio, sample_max_value)
+            raise NotImplementedError(f"unsupported {self._published} arguments: {sorted(unsupported)}"
+                                      + _THRESHOLD_HINT * bool(_THRESHOLD_ARGS & set(unsupported)))
+        self.threshold = check_thresholding(*thresholding)
         if prediction_type != "epsilon":
             raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
-        if variance_type != "fixed_small":
-            raise NotImplementedError("only variance_type='fixed_small' (the diffusers default the reference uses)")
-        if timestep_spacing != "leading":
-            raise NotImplementedError("only timestep_spacing='leading' (the diffusers default the reference uses)")
-        if beta_schedule == "linear":
-            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "squaredcos_cap_v2":
-            self.betas = _betas_for_alpha_bar(num_train_timesteps)
+
+    def _setup(self, config: SimpleNamespace) -> None:
+        """``config`` (the constructor's arguments, so that ``cls(**vars(config))`` builds the scheduler again) and the tables"""
+        n = config.num_train_timesteps
+        if config.beta_schedule == "linear":
+            self.betas = torch.linspace(config.beta_start, config.beta_end, n, dtype=torch.float32)
+        elif config.beta_schedule == "squaredcos_cap_v2":
+            self.betas = _betas_for_alpha_bar(n)
         else:
-            raise NotImplementedError(f"beta_schedule '{beta_schedule}' is not used by the reference")
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
-                                      beta_end=beta_end, beta_schedule=beta_schedule, variance_type=variance_type,
-                                      clip_sample=clip_sample, prediction_type=prediction_type,
-                                      clip_sample_range=clip_sample_range, timestep_spacing=timestep_spacing,
-                                      steps_offset=steps_offset, thresholding=thresholding,
-                                      dynamic_thresholding_ratio=dynamic_thresholding_ratio,
-                                      sample_max_value=sample_max_value)
+            raise NotImplementedError(f"beta_schedule '{config.beta_schedule}' is not used by the reference")
+        self.config = config
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.one = torch.tensor(1.0)
         self.init_noise_sigma = 1.0
         self.num_inference_steps: Optional[int] = None
-        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+        self.timesteps = torch.from_numpy(np.arange(0, n)[::-1].copy())
 
-    set_thresholding = _set_thresholding
+    def set_thresholding(self, thresholding: bool = True, dynamic_thresholding_ratio: float = 0.995,
+                         sample_max_value: float = 1.0) -> None:
+        """Dynamic thresholding of x0 (Saharia et al. 2022) for this scheduler's ``step`` and for ``run_sampling_loop``: the
+        published ``thresholding``, ``dynamic_thresholding_ratio`` and ``sample_max_value``, kept in ``self.threshold`` as (ratio, max)
+        or None (and in ``config`` where the constructor takes them).  It takes
+        precedence over ``clip_sample``.  ``HipDDPMScheduler`` also takes the three in its constructor; the constructors of the
+        DDIM and DPM-Solver++ mirrors keep refusing them, as they always have, and this method is their way in.  ValueError for a
+        ratio outside (0, 1] or a maximum below 1."""
+        self.threshold = check_thresholding(thresholding, dynamic_thresholding_ratio, sample_max_value)
+        # (config holds what the constructor takes, so that cls(**vars(config)) builds the scheduler again: the DDPM mirror's does)
+        if hasattr(self.config, "thresholding"):
+            self.config.thresholding = bool(thresholding)
+            self.config.dynamic_thresholding_ratio = dynamic_thresholding_ratio
+            self.config.sample_max_value = sample_max_value
 
     def __len__(self) -> int:
         return self.config.num_train_timesteps
@@ -130,15 +137,113 @@ class HipDDPMScheduler:
         if num_inference_steps < 1:
             raise ValueError("num_inference_steps must be >= 1")
         self.num_inference_steps = num_inference_steps
-        step_ratio = n_train // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
-        ts += self.config.steps_offset
         # kept on the host: the loop only needs int(t); device= is accepted for API compatibility
-        self.timesteps = torch.from_numpy(ts)
+        self.timesteps = torch.from_numpy(_timestep_grid(self.config.timestep_spacing, n_train, num_inference_steps,
+                                                         self.config.steps_offset))
+
+    def rule_table(self, eta: float = 0.0, use_clipped_model_output: bool = False):
+        """``(rule, table, flags)`` for the library's loops: this scheduler's record of ``_lib.RULES``, its host [T, row width]
+        fp32 coefficient table over ``timesteps`` (under ``eta`` where the rule has one) and its SISIC_RULE_FLAG_* bits.  Sigma
+        is column 4 under every rule."""
+        rule = _lib.RULES[self.rule]
+        table = self.coefficient_table(eta) if self._takes_eta else self.coefficient_table()
+        return rule, table.contiguous(), rule.clipped_output_flag if use_clipped_model_output else 0
+
+    def _draw(self, noisy: bool, model_output: torch.Tensor, device, generator, variance_noise) -> Optional[torch.Tensor]:
+        """z of a ``step``, or None on a step that adds no noise: ``variance_noise`` if given, else ``torch.randn`` with
+        ``generator`` where the generator lives"""
+        if not noisy:
+            return None
+        if variance_noise is not None:
+            return variance_noise.to(device=device, dtype=torch.float32).contiguous()
+        if generator is not None and generator.device.type == "cpu":
+            return torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(device)
+        return torch.randn(model_output.shape, generator=generator, device=device, dtype=torch.float32)
+
+    def _on_gpu(self, model_output: torch.Tensor) -> None:
+        if model_output.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__}.step runs on MI355X tensors only (no CPU path)")
+
+    def _clip(self) -> float:
+        return self.config.clip_sample_range if self.config.clip_sample else 0.0
+
+    def _result(self, prev: torch.Tensor, return_dict: bool):
+        return self._output(prev_sample=prev) if return_dict else (prev,)
+
+    def add_noise_coefficients(self, timesteps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(alphas_cumprod[t] ** 0.5, (1 - alphas_cumprod[t]) ** 0.5) as fp32 host rows, the scalars of ``add_noise``."""
+        t = torch.as_tensor(timesteps).detach().to("cpu").to(torch.int64).reshape(-1)
+        acp = self.alphas_cumprod[t]
+        return (acp ** 0.5).contiguous(), ((1 - acp) ** 0.5).contiguous()
+
+    @staticmethod
+    def _fp32_pair(lead: torch.Tensor, other: torch.Tensor, what: str):
+        if lead.device.type != "cuda":
+            raise RuntimeError(f"{what} runs on MI355X tensors only (no CPU path)")
+        lead = lead.to(torch.float32).contiguous()
+        return lead, other.to(device=lead.device, dtype=torch.float32).contiguous()
+
+    @torch.no_grad()
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """``DDPMScheduler.add_noise`` (diffusion/train_diffusion.py:217):
+        noisy = sqrt(abar_t) * x0 + sqrt(1 - abar_t) * noise with one timestep per sample, on the GPU (sisic_add_noise)."""
+        x0, nz = self._fp32_pair(original_samples, noise, "HipDDPMScheduler.add_noise")
+        a, c = self.add_noise_coefficients(timesteps)
+        return ops.add_noise(x0, nz, a, c)
+
+    @torch.no_grad()
+    def get_velocity(self, sample: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """``DDPMScheduler.get_velocity``: v = sqrt(abar_t) * noise - sqrt(1 - abar_t) * sample, the regression target of a
+        v-prediction model, on the GPU.  It is sisic_add_noise with (x0 := noise, noise := sample, a = sqrt(abar),
+        c = -sqrt(1 - abar)): a sum with a negated product rounds exactly as the difference does, so the result equals the
+        torch formula bit for bit -- and the target the fused training step forms in its loss kernel."""
+        x, nz = self._fp32_pair(sample, noise, "get_velocity")
+        a, c = self.add_noise_coefficients(timesteps)
+        return ops.add_noise(nz, x, a, -c)
+
+
+class _StridedScheduler(_HipScheduler):
+    """The DDPM and DDIM mirrors: a step goes from t to ``t - num_train_timesteps // num_inference_steps`` (both spacings), and
+    past t = 0 to ``_abar_end``."""
 
     def previous_timestep(self, timestep: int) -> int:
         n = self.num_inference_steps if self.num_inference_steps else self.config.num_train_timesteps
         return int(timestep) - self.config.num_train_timesteps // n
+
+    def abar_prev(self, i: int, abar: Optional[np.ndarray] = None) -> float:
+        """abar (float64) at the level grid entry i of ``timesteps`` steps to, as the rule's own row of that entry has it;
+        ``abar``: ``_abar64(self)``, for a caller that asks about many entries"""
+        abar = _abar64(self) if abar is None else abar
+        prev_t = self.previous_timestep(int(self.timesteps[i]))
+        return float(abar[prev_t]) if prev_t >= 0 else self._abar_end(abar)
+
+    def _abar_end(self, abar: np.ndarray) -> float:
+        return 1.0
+
+
+class HipDDPMScheduler(_StridedScheduler):
+    rule = "ddpm"
+    _published = "DDPMScheduler"
+    _output = DDPMSchedulerOutput
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = True,
+                 prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
+                 timestep_spacing: str = "leading", steps_offset: int = 0, thresholding: bool = False,
+                 dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0, **unsupported):
+        self._begin(unsupported, prediction_type, (thresholding, dynamic_thresholding_ratio, sample_max_value))
+        if variance_type != "fixed_small":
+            raise NotImplementedError("only variance_type='fixed_small' (the diffusers default the reference uses)")
+        if timestep_spacing != "leading":
+            raise NotImplementedError("only timestep_spacing='leading' (the diffusers default the reference uses)")
+        self._setup(SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start,
+                                    beta_end=beta_end, beta_schedule=beta_schedule, variance_type=variance_type,
+                                    clip_sample=clip_sample, prediction_type=prediction_type,
+                                    clip_sample_range=clip_sample_range, timestep_spacing=timestep_spacing,
+                                    steps_offset=steps_offset, thresholding=thresholding,
+                                    dynamic_thresholding_ratio=dynamic_thresholding_ratio,
+                                    sample_max_value=sample_max_value))
+        self.one = torch.tensor(1.0)
 
     def step_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
         """(sqrt(1-abar_t), sqrt(abar_t), c0, c1, sigma) as fp32 values, sigma = 0 at t == 0."""
@@ -171,75 +276,12 @@ class HipDDPMScheduler:
         ``torch.randn`` on the sample's device with ``generator`` (the reference passes none).  ``prediction_type``: what
         ``model_output`` holds -- "epsilon", "sample" or "v_prediction".  It is the MODEL's property (``HipUNet2DModel
         (prediction_type=)``), so it travels with the call (``model.prediction_type``), not with the scheduler's constructor."""
-        if model_output.device.type != "cuda":
-            raise RuntimeError("HipDDPMScheduler.step runs on MI355X tensors only (no CPU path)")
+        self._on_gpu(model_output)
         coef = self.step_coefficients(timestep)
-        z = None
-        if int(timestep) > 0:
-            if variance_noise is not None:
-                z = variance_noise.to(device=sample.device, dtype=torch.float32).contiguous()
-            elif generator is not None and generator.device.type == "cpu":
-                z = torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(sample.device)
-            else:
-                z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
+        z = self._draw(int(timestep) > 0, model_output, sample.device, generator, variance_noise)
         prev = ops.ddpm_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z,
-                             coef, clip, prediction_type=prediction_type, threshold=self.threshold)
-        if not return_dict:
-            return (prev,)
-        return DDPMSchedulerOutput(prev_sample=prev)
-
-    def add_noise_coefficients(self, timesteps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(alphas_cumprod[t] ** 0.5, (1 - alphas_cumprod[t]) ** 0.5) as fp32 host rows, the scalars of ``add_noise``."""
-        t = torch.as_tensor(timesteps).detach().to("cpu").to(torch.int64).reshape(-1)
-        acp = self.alphas_cumprod[t]
-        return (acp ** 0.5).contiguous(), ((1 - acp) ** 0.5).contiguous()
-
-    @torch.no_grad()
-    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        """``DDPMScheduler.add_noise`` (diffusion/train_diffusion.py:217):
-        noisy = sqrt(abar_t) * x0 + sqrt(1 - abar_t) * noise with one timestep per sample, on the GPU (sisic_add_noise)."""
-        if original_samples.device.type != "cuda":
-            raise RuntimeError("HipDDPMScheduler.add_noise runs on MI355X tensors only (no CPU path)")
-        from . import _lib
-        from ._lib import check
-        import ctypes as C
-        x0 = original_samples.to(torch.float32).contiguous()
-        nz = noise.to(device=x0.device, dtype=torch.float32).contiguous()
-        B = x0.shape[0]
-        a, c = self.add_noise_coefficients(timesteps)
-        if a.numel() != B:
-            raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
-        a, c = ops.upload(torch.stack([a, c]), x0.device)          # pinned, non-blocking: the call does not wait for the stream
-        out = ops.empty_like(x0)
-        check(_lib.load().sisic_add_noise(ops.context(x0.device), x0.data_ptr(), nz.data_ptr(), a.data_ptr(), c.data_ptr(),
-                                          out.data_ptr(), B, x0[0].numel(),
-                                          C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))
-        return out
-
-    @torch.no_grad()
-    def get_velocity(self, sample: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        """``DDPMScheduler.get_velocity``: v = sqrt(abar_t) * noise - sqrt(1 - abar_t) * sample, the regression target of a
-        v-prediction model, on the GPU.  It is sisic_add_noise with (x0 := noise, noise := sample, a = sqrt(abar),
-        c = -sqrt(1 - abar)): a sum with a negated product rounds exactly as the difference does, so the result equals the
-        torch formula bit for bit -- and the target the fused training step forms in its loss kernel."""
-        if sample.device.type != "cuda":
-            raise RuntimeError("get_velocity runs on MI355X tensors only (no CPU path)")
-        from . import _lib
-        from ._lib import check
-        import ctypes as C
-        x0 = sample.to(torch.float32).contiguous()
-        nz = noise.to(device=x0.device, dtype=torch.float32).contiguous()
-        B = x0.shape[0]
-        a, c = self.add_noise_coefficients(timesteps)
-        if a.numel() != B:
-            raise ValueError(f"{a.numel()} timesteps for a batch of {B}")
-        a, c = ops.upload(torch.stack([a, -c]), x0.device)
-        out = ops.empty_like(x0)
-        check(_lib.load().sisic_add_noise(ops.context(x0.device), nz.data_ptr(), x0.data_ptr(), a.data_ptr(), c.data_ptr(),
-                                          out.data_ptr(), B, x0[0].numel(),
-                                          C.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)))
-        return out
+                             coef, self._clip(), prediction_type=prediction_type, threshold=self.threshold)
+        return self._result(prev, return_dict)
 
 
 @dataclass
@@ -249,7 +291,7 @@ class DDIMSchedulerOutput:
     pred_original_sample: Optional[torch.Tensor] = None
 
 
-class HipDDIMScheduler:
+class HipDDIMScheduler(_StridedScheduler):
     """Drop-in for ``diffusers.DDIMScheduler`` with epsilon prediction: the same beta / alphas_cumprod tables, x_T and UNet as
     the DDPM mirror, the step rule that was designed for 20 to 100 steps.  Deterministic at ``eta = 0``; at ``eta = 1`` its
     sigma is the DDPM rule's.
@@ -259,64 +301,27 @@ class HipDDIMScheduler:
         for t in sched.timesteps:
             latents = sched.step(model(latents, t).sample, t, latents, eta=0.0).prev_sample
     """
-    order = 1
     rule = "ddim"
+    _published = "DDIMScheduler"
+    _output = DDIMSchedulerOutput
+    _takes_eta = True
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", clip_sample: bool = True, set_alpha_to_one: bool = True,
                  steps_offset: int = 0, prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
                  timestep_spacing: str = "leading", **unsupported):
-        if unsupported:
-            raise NotImplementedError(f"unsupported DDIMScheduler arguments: {sorted(unsupported)}"
-                                      + _THRESHOLD_HINT * bool(_THRESHOLD_ARGS & set(unsupported)))
-        self.threshold = None
-        if prediction_type != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
+        self._begin(unsupported, prediction_type)
         if timestep_spacing not in ("leading", "trailing"):
             raise NotImplementedError("only timestep_spacing='leading' (the diffusers default) or 'trailing'")
-        if beta_schedule == "linear":
-            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "squaredcos_cap_v2":
-            self.betas = _betas_for_alpha_bar(num_train_timesteps)
-        else:
-            raise NotImplementedError(f"beta_schedule '{beta_schedule}' is not used by the reference")
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                                      beta_schedule=beta_schedule, clip_sample=clip_sample,
-                                      set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset,
-                                      prediction_type=prediction_type, clip_sample_range=clip_sample_range,
-                                      timestep_spacing=timestep_spacing)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._setup(SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                    beta_schedule=beta_schedule, clip_sample=clip_sample,
+                                    set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset,
+                                    prediction_type=prediction_type, clip_sample_range=clip_sample_range,
+                                    timestep_spacing=timestep_spacing))
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps: Optional[int] = None
-        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
 
-    set_thresholding = _set_thresholding
-    # the forward process does not depend on the sampling rule
-    __len__ = HipDDPMScheduler.__len__
-    scale_model_input = HipDDPMScheduler.scale_model_input
-    add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
-    add_noise = HipDDPMScheduler.add_noise
-    get_velocity = HipDDPMScheduler.get_velocity
-    previous_timestep = HipDDPMScheduler.previous_timestep      # t - num_train_timesteps // num_inference_steps, both spacings
-
-    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
-        n_train = self.config.num_train_timesteps
-        if num_inference_steps > n_train:
-            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
-        if num_inference_steps < 1:
-            raise ValueError("num_inference_steps must be >= 1")
-        self.num_inference_steps = num_inference_steps
-        if self.config.timestep_spacing == "leading":
-            step_ratio = n_train // num_inference_steps
-            ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
-            ts += self.config.steps_offset
-        else:                                                    # "trailing": the float ratio, no offset
-            step_ratio = n_train / num_inference_steps
-            ts = np.round(np.arange(n_train, 0, -step_ratio)).astype(np.int64)
-            ts -= 1
-        self.timesteps = torch.from_numpy(ts)
+    def _abar_end(self, abar: np.ndarray) -> float:              # 1, or alphas_cumprod[0] (set_alpha_to_one=False)
+        return 1.0 if float(self.final_alpha_cumprod) == 1.0 else float(abar[0])
 
     def step_coefficients(self, timestep, eta: float = 0.0) -> Tuple[float, float, float, float, float]:
         """(sqrt(1-abar_t), sqrt(abar_t), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma) as fp32 values,
@@ -345,23 +350,12 @@ class HipDDIMScheduler:
         Noise, on the steps with sigma != 0 only: ``variance_noise`` if given, else
         ``torch.randn`` on the sample's device with ``generator``.  (diffusers also draws on a step whose sigma is 0 at
         eta > 0, and multiplies the draw by 0: a generator shared with it is one draw further on after such a step.)"""
-        if model_output.device.type != "cuda":
-            raise RuntimeError("HipDDIMScheduler.step runs on MI355X tensors only (no CPU path)")
+        self._on_gpu(model_output)
         coef = self.step_coefficients(timestep, eta)
-        z = None
-        if coef[4] != 0.0:
-            if variance_noise is not None:
-                z = variance_noise.to(device=sample.device, dtype=torch.float32).contiguous()
-            elif generator is not None and generator.device.type == "cpu":
-                z = torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(sample.device)
-            else:
-                z = torch.randn(model_output.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
-        prev = ops.ddim_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z, coef, clip,
-                             use_clipped_model_output, prediction_type=prediction_type, threshold=self.threshold)
-        if not return_dict:
-            return (prev,)
-        return DDIMSchedulerOutput(prev_sample=prev)
+        z = self._draw(coef[4] != 0.0, model_output, sample.device, generator, variance_noise)
+        prev = ops.ddim_step(model_output.to(torch.float32).contiguous(), sample.to(torch.float32).contiguous(), z, coef,
+                             self._clip(), use_clipped_model_output, prediction_type=prediction_type, threshold=self.threshold)
+        return self._result(prev, return_dict)
 
 
 DPMPP_ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
@@ -416,7 +410,7 @@ class DPMSolverSchedulerOutput:
     prev_sample: torch.Tensor
 
 
-class HipDPMSolverMultistepScheduler:
+class HipDPMSolverMultistepScheduler(_HipScheduler):
     """Drop-in for ``diffusers.DPMSolverMultistepScheduler`` with epsilon prediction: DPM-Solver++(2M), the second-order
     multistep solver (``solver_type="midpoint"``, ``final_sigmas_type="zero"``), and its stochastic variant
     ``algorithm_type="sde-dpmsolver++"``.  One UNet call per step like DDIM, which it equals at ``solver_order=1``.
@@ -432,20 +426,17 @@ class HipDPMSolverMultistepScheduler:
     ``clip_sample_range`` are extensions of this project: the static clamp of x0 the other two mirrors apply, off by
     default.  The published class's ``thresholding`` is offered through ``set_thresholding`` (the constructor keeps
     refusing the argument, as it always has); under it ``clip_sample`` is not read."""
-    order = 1
     rule = "dpmsolver++"
+    _published = "DPMSolverMultistepScheduler"
+    _output = DPMSolverSchedulerOutput
+    _takes_solver_options = True
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", solver_order: int = 2, prediction_type: str = "epsilon",
                  algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint", lower_order_final: bool = True,
                  final_sigmas_type: str = "zero", timestep_spacing: str = "linspace", steps_offset: int = 0,
                  clip_sample: bool = False, clip_sample_range: float = 1.0, **unsupported):
-        if unsupported:
-            raise NotImplementedError(f"unsupported DPMSolverMultistepScheduler arguments: {sorted(unsupported)}"
-                                      + _THRESHOLD_HINT * bool(_THRESHOLD_ARGS & set(unsupported)))
-        self.threshold = None
-        if prediction_type != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon' (what the reference trains and samples with)")
+        self._begin(unsupported, prediction_type)
         check_dpmpp_options(solver_order, algorithm_type)
         if solver_type != "midpoint":
             raise NotImplementedError("only solver_type='midpoint' (the published default)")
@@ -453,33 +444,15 @@ class HipDPMSolverMultistepScheduler:
             raise NotImplementedError("only final_sigmas_type='zero': the run ends at sigma = 0 and returns its x0")
         if timestep_spacing not in ("linspace", "leading", "trailing"):
             raise NotImplementedError("timestep_spacing must be 'linspace' (the published default), 'leading' or 'trailing'")
-        if beta_schedule == "linear":
-            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "squaredcos_cap_v2":
-            self.betas = _betas_for_alpha_bar(num_train_timesteps)
-        else:
-            raise NotImplementedError(f"beta_schedule '{beta_schedule}' is not used by the reference")
         # lower_order_final has no effect: with final_sigmas_type='zero' the last step is first order whatever it says
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                                      beta_schedule=beta_schedule, solver_order=solver_order,
-                                      prediction_type=prediction_type, algorithm_type=algorithm_type,
-                                      solver_type=solver_type, lower_order_final=lower_order_final,
-                                      final_sigmas_type=final_sigmas_type, timestep_spacing=timestep_spacing,
-                                      steps_offset=steps_offset, clip_sample=clip_sample,
-                                      clip_sample_range=clip_sample_range)
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps: Optional[int] = None
-        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
+        self._setup(SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                    beta_schedule=beta_schedule, solver_order=solver_order,
+                                    prediction_type=prediction_type, algorithm_type=algorithm_type,
+                                    solver_type=solver_type, lower_order_final=lower_order_final,
+                                    final_sigmas_type=final_sigmas_type, timestep_spacing=timestep_spacing,
+                                    steps_offset=steps_offset, clip_sample=clip_sample,
+                                    clip_sample_range=clip_sample_range))
         self._reset()
-
-    set_thresholding = _set_thresholding
-    __len__ = HipDDPMScheduler.__len__
-    scale_model_input = HipDDPMScheduler.scale_model_input
-    add_noise_coefficients = HipDDPMScheduler.add_noise_coefficients
-    add_noise = HipDDPMScheduler.add_noise
-    get_velocity = HipDDPMScheduler.get_velocity
 
     def _reset(self) -> None:
         self._hist: Optional[torch.Tensor] = None     # the previous step's x0 (device), None before the first step
@@ -491,23 +464,13 @@ class HipDPMSolverMultistepScheduler:
         return self._step_index
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
-        n_train = self.config.num_train_timesteps
-        if num_inference_steps > n_train:
-            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
-        if num_inference_steps < 1:
-            raise ValueError("num_inference_steps must be >= 1")
-        self.num_inference_steps = T = num_inference_steps
-        spacing = self.config.timestep_spacing
-        if spacing == "linspace":
-            ts = np.linspace(0, n_train - 1, T + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif spacing == "leading":                               # the grid of the DDPM and DDIM mirrors: ends at t = 0
-            step_ratio = n_train // T
-            ts = (np.arange(0, T) * step_ratio).round()[::-1].copy().astype(np.int64)
-            ts += self.config.steps_offset
-        else:                                                    # "trailing"
-            ts = np.round(np.arange(n_train, 0, -n_train / T)).astype(np.int64) - 1
-        self.timesteps = torch.from_numpy(ts)
+        super().set_timesteps(num_inference_steps, device)
         self._reset()
+
+    def abar_prev(self, i: int, abar: Optional[np.ndarray] = None) -> float:
+        """abar (float64) at the level grid entry i of ``timesteps`` steps to: the next grid point; the run ends at abar = 1"""
+        abar = _abar64(self) if abar is None else abar
+        return float(abar[int(self.timesteps[i + 1])]) if i + 1 < self.timesteps.numel() else 1.0
 
     def _rows(self, solver_order: int) -> torch.Tensor:
         abar = self.alphas_cumprod[self.timesteps.to(torch.int64)].numpy().astype(np.float64)
@@ -527,8 +490,7 @@ class HipDPMSolverMultistepScheduler:
         ``timesteps`` by ``timestep`` and is first order (there is no history yet); every call then moves one step on.
         Noise, on the steps with sigma != 0 only (the SDE variant, all but the last): ``variance_noise`` if given, else
         ``torch.randn`` with ``generator``."""
-        if model_output.device.type != "cuda":
-            raise RuntimeError("HipDPMSolverMultistepScheduler.step runs on MI355X tensors only (no CPU path)")
+        self._on_gpu(model_output)
         if self._tables is None:
             self._tables = (self._rows(1), self._rows(self.config.solver_order))
         if self._step_index is None:
@@ -544,21 +506,14 @@ class HipDPMSolverMultistepScheduler:
         if fresh:
             self._hist = ops.empty_like(x)
         coef = tuple(float(v) for v in self._tables[0 if fresh else 1][i])
-        z = None
-        if coef[4] != 0.0:
-            if variance_noise is not None:
-                z = variance_noise.to(device=x.device, dtype=torch.float32).contiguous()
-            elif generator is not None and generator.device.type == "cpu":
-                z = torch.randn(model_output.shape, generator=generator, dtype=torch.float32).to(x.device)
-            else:
-                z = torch.randn(model_output.shape, generator=generator, device=x.device, dtype=torch.float32)
-        clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
-        prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, clip,
+        z = self._draw(coef[4] != 0.0, model_output, x.device, generator, variance_noise)
+        prev = ops.dpmpp_step(model_output.to(torch.float32).contiguous(), x, z, self._hist, coef, self._clip(),
                               prediction_type=prediction_type, threshold=self.threshold)
         self._step_index = i + 1
-        if not return_dict:
-            return (prev,)
-        return DPMSolverSchedulerOutput(prev_sample=prev)
+        return self._result(prev, return_dict)
+
+
+MIRRORS = {cls.rule: cls for cls in (HipDDPMScheduler, HipDDIMScheduler, HipDPMSolverMultistepScheduler)}
 
 
 # ---- image editing: the RePaint schedule and the rows of the edit epilogue ------------------------------------------------
@@ -597,17 +552,6 @@ def _abar64(scheduler) -> np.ndarray:
     return np.cumprod(scheduler.alphas.numpy().astype(np.float64))
 
 
-def _abar_prev64(scheduler, abar: np.ndarray, i: int) -> float:
-    """abar at the level grid entry i of ``scheduler.timesteps`` steps to, as the rule's own row of that entry has it"""
-    if getattr(scheduler, "rule", "ddpm") == "dpmsolver++":            # the next grid point; the run ends at abar = 1
-        return float(abar[int(scheduler.timesteps[i + 1])]) if i + 1 < scheduler.timesteps.numel() else 1.0
-    prev_t = scheduler.previous_timestep(int(scheduler.timesteps[i]))
-    if prev_t >= 0:
-        return float(abar[prev_t])
-    final = getattr(scheduler, "final_alpha_cumprod", None)           # DDIM: 1, or alphas_cumprod[0] (set_alpha_to_one=False)
-    return 1.0 if final is None or float(final) == 1.0 else float(abar[0])
-
-
 def edit_rows(scheduler, schedule) -> torch.Tensor:
     """[len(schedule), 4] fp32 rows ``{ck, sk, ja, jb}`` of the edit epilogue (``sisic_sample_frames_edit``) for a schedule of
     ``(grid index, jump)`` entries over ``scheduler.timesteps``:
@@ -632,7 +576,7 @@ def edit_rows64(scheduler, schedule) -> np.ndarray:
         i, jump = int(i), int(jump)
         if not 0 <= i < n:
             raise ValueError(f"schedule entry {p}: grid index {i} is outside 0..{n - 1}")
-        prev = _abar_prev64(scheduler, abar, i)
+        prev = scheduler.abar_prev(i, abar)
         ja, jb = 1.0, 0.0
         if jump:
             target = i + 1 - jump

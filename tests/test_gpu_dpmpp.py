@@ -270,9 +270,10 @@ def test_a_call_starts_without_history(eager):
     from synt_isic_amd.sampler import run_sampling_loop
     whole = _dpm(T)
 
-    class Cut:
-        rule, config = "dpmsolver++", whole.config
-        timesteps = whole.timesteps[1:]
+    class Cut(type(whole)):                      # the mirror of the whole run, from its second grid entry on
+        def __init__(self):
+            vars(self).update(vars(whole))
+            self.timesteps = whole.timesteps[1:]
 
         def coefficient_table(self):
             return whole.coefficient_table()[1:]

@@ -78,7 +78,7 @@ def _python_loop(model, sched, eta, x_T, seeds, image, mask, schedule, labels=No
     then the restated blend.  Returns every frame."""
     from synt_isic_amd import ops
     sched.set_timesteps(sched.timesteps.numel())                         # a new run (DPM-Solver++: no history)
-    tab = sched.coefficient_table(eta) if sched.rule == "ddim" else sched.coefficient_table()
+    tab = sched.rule_table(eta)[1]
     rows = _ref_rows(sched, schedule)
     kw = dict(eta=eta) if sched.rule == "ddim" else {}
     x, frames = x_T.clone(), []

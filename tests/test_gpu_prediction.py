@@ -38,7 +38,7 @@ def _scheduler(rule, steps=T):
 
 
 def _table(sched, eta):
-    return sched.coefficient_table(eta) if sched.rule == "ddim" else sched.coefficient_table()
+    return sched.rule_table(eta)[1]
 
 
 def _x_T(seeds, chw=CHW):

@@ -206,7 +206,7 @@ def _sched(rule, threshold=THR, Tn=T, **kw):
 
 
 def _table(sched, eta=0.0):
-    return sched.coefficient_table(eta) if sched.rule == "ddim" else sched.coefficient_table()
+    return sched.rule_table(eta)[1]
 
 
 @pytest.mark.parametrize("rule,clipped", RULE_CASES)

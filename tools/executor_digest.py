@@ -1,22 +1,33 @@
 #!/usr/bin/env python3
 """One line per item with a sha256 of its raw bytes: what the two network executors (csrc/unet.cpp with csrc/train.cpp, and
 csrc/resnet.cpp) compute, launch and keep as workspace, at the smallest shapes that reach every branch of their host code.
-Two builds of the library that print the same file run the same launches on the same pool blocks.
+Two builds of the library that print the same file run the same launches on the same pool blocks.  The ``step.`` lines are the
+Python step layer on top of one library (the scheduler mirrors' host tables and refusals first, without the GPU; every single-step
+wrapper's marshalling last): two trees of the package that print the same lines compute the same bits.
 
     SISIC_LIB_PATH=<library> python tools/executor_digest.py > digest.txt
+    python tools/executor_digest.py --host-only          the step layer's host lines alone: needs no GPU (compare two trees on one
+                                                         machine: the DDPM / DDIM tables are fp32 torch host arithmetic, CPU-dependent)
+    python tools/executor_digest.py --step-layer         the step layer's lines alone
+    python tools/executor_digest.py --step-layer-items   with any of the above: every item of the step layer on its own line (by
+                                                         default one line per mirror case / wrapper: the sha256 of its items)
+    python tools/executor_digest.py --step-layer-times   wall time per call of the wrappers and the mirrors' step
 
 The kernels have no atomics: two runs of one library print the same file."""
 import hashlib
 import os
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from synt_isic_amd import _lib, ops  # noqa: E402
+from synt_isic_amd import scheduler as sch  # noqa: E402
 from synt_isic_amd.classifier import HipMelanomaClassifier  # noqa: E402
 from synt_isic_amd.sampler import Sampler  # noqa: E402
 from synt_isic_amd.scheduler import resample_schedule  # noqa: E402
@@ -180,6 +191,182 @@ def classifier_items() -> None:
     emit("clf.input_gradient_after_training.workspace_bytes", clf.workspace_bytes())
 
 
+# ---- the Python step layer (ops.*_step*, the scheduler mirrors, sampler._check_scheduler): names of both sides of its fold only
+NEW_MIRROR_METHODS = {"rule_table", "abar_prev"}        # what the fold added to every mirror: left out of the attribute lists
+
+
+ITEMS = "--step-layer-items" in sys.argv           # every item of the step layer on a line of its own, not one line per group
+_groups = {}
+
+
+def item(group: str, name: str, value) -> None:
+    """an item of the step layer: its own line under --step-layer-items, else part of its group's line (``close_groups``)"""
+    if ITEMS:
+        emit(f"{group}.{name}", value)
+    else:
+        _groups.setdefault(group, []).append(f"{name}\t{value}\n")
+
+
+def close_groups() -> None:
+    """one line per group: the sha256 of its items' lines, which --step-layer-items prints one by one to find a difference"""
+    for group, lines in _groups.items():
+        emit(group, f"{hashlib.sha256(''.join(lines).encode()).hexdigest()} items={len(lines)}")
+    _groups.clear()
+
+
+def said(fn) -> str:
+    """what a call that should be refused says"""
+    try:
+        fn()
+    except Exception as e:          # noqa: BLE001
+        return f"{type(e).__name__}: {e}"
+    return "accepted"
+
+
+def mirror_cases():
+    """(tag, class, constructor keywords, etas of its coefficient_table) over every mirror's constructor options"""
+    for beta in ("linear", "squaredcos_cap_v2"):
+        yield f"ddpm.{beta}", sch.HipDDPMScheduler, dict(beta_schedule=beta), (None,)
+        for spacing in ("leading", "trailing"):
+            for one in (True, False):
+                yield (f"ddim.{beta}.{spacing}.one{int(one)}", sch.HipDDIMScheduler,
+                       dict(beta_schedule=beta, timestep_spacing=spacing, set_alpha_to_one=one), (0.0, 0.5, 1.0))
+        for spacing in ("linspace", "leading", "trailing"):
+            for order in (1, 2):
+                for alg in sch.DPMPP_ALGORITHMS:
+                    yield (f"dpmpp.{beta}.{spacing}.o{order}.{alg}", sch.HipDPMSolverMultistepScheduler,
+                           dict(beta_schedule=beta, timestep_spacing=spacing, solver_order=order, algorithm_type=alg), (None,))
+
+
+def step_layer_host() -> None:
+    """tables, grids, configs and refusals of the mirrors: no GPU"""
+    from synt_isic_amd.sampler import _check_scheduler
+    np.seterr(all="ignore")         # DPM-Solver++ on a grid with two equal neighbours divides by zero: its bits are printed as they are
+    classes = (sch.HipDDPMScheduler, sch.HipDDIMScheduler, sch.HipDPMSolverMultistepScheduler)
+    for tag, cls, kw, etas in mirror_cases():
+        for T in (1, 2, 7, 50, 1000):
+            s = cls(**kw)
+            s.set_timesteps(T)
+            item(f"step.host.{tag}", f"T{T}.timesteps", sha(s.timesteps))
+            for eta in etas:
+                table = s.coefficient_table() if eta is None else s.coefficient_table(eta)
+                item(f"step.host.{tag}", f"T{T}.table.eta{eta}", f"{sha(table)} {tuple(table.shape)}")
+            item(f"step.host.{tag}", f"T{T}.edit_rows", sha(sch.edit_rows(s, resample_schedule(T, 3, 2))))
+        s = cls(**kw)
+        item(f"step.host.{tag}", "config", list(vars(s.config).items()))
+        before = s.threshold
+        s.set_thresholding(True, 0.9, 2.0)
+        item(f"step.host.{tag}", "threshold", f"{before} -> {s.threshold}; config {list(vars(s.config).items())}")
+    for cls in classes:
+        name = cls.__name__
+        item(f"step.host.{name}", "public", sorted(n for n in dir(cls) if not n.startswith("_") and n not in NEW_MIRROR_METHODS))
+        for what, kw in (("thresholding", dict(thresholding=True)), ("v_prediction", dict(prediction_type="v_prediction")),
+                         ("scaled_linear", dict(beta_schedule="scaled_linear")), ("unknown", dict(rescale_betas_zero_snr=True)),
+                         ("thresholding_ratio_0", dict(thresholding=True, dynamic_thresholding_ratio=0.0))):
+            item(f"step.host.{name}", f"refusal.{what}", said(lambda: cls(**kw)))
+        for T in (0, 1001):
+            item(f"step.host.{name}", f"refusal.set_timesteps_{T}", said(lambda: cls().set_timesteps(T)))
+    for args in (("heun", 0.0), ("ddpm", 0.5), ("ddpm", 0.0, True), ("dpmsolver++", 0.5), ("dpmsolver++", 0.0, True), ("ddim", 1.5),
+                 ("ddim", -0.1), ("dpmsolver++", 0.0, False, 3), ("dpmsolver++", 0.0, False, 2, "dpmsolver"),
+                 ("ddpm", 0.0, False, 1), ("ddim", 0.0, False, 2, "sde-dpmsolver++"), (None, 0.0)):
+        item("step.host.check_scheduler", str(args), said(lambda: _check_scheduler(*args)))
+    close_groups()
+
+
+def shifted(t: torch.Tensor) -> torch.Tensor:
+    """the same values one float past an allocation's start: contiguous, off every 16-byte line"""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:].copy_(t.reshape(-1))
+    return buf[1:].view(t.shape)
+
+
+# rows with sigma != 0; the second DPM-Solver++ row reads hist (k1 != 0)
+STEP_ROWS = {"ddpm": ((0.6, 0.8, 0.3, 0.7, 0.25),), "ddim": ((0.6, 0.8, 0.9, 0.35, 0.25),),
+             "dpmpp": ((0.6, 0.8, 0.7, 0.4, 0.25, 0.0), (0.55, 0.835, 0.75, 0.45, 0.2, -0.15))}
+
+
+def step_layer_gpu() -> None:
+    """every wrapper's marshalling at [2,3,5,7] (210 elements: a scalar tail; 105 per image: image 1 off the 16-byte lines),
+    aligned and shifted by one float; the mirrors' ``step`` under the three noise sources; add_noise and get_velocity"""
+    shape, seeds, step = (2, 3, 5, 7), (3, 2 ** 63 + 5), 4
+    base = dict(x=rand(shape, 51).to(DEV), eps=rand(shape, 52).to(DEV), z=rand(shape, 53).to(DEV),
+                x0k=rand(shape, 54).clamp(-1, 1).to(DEV),
+                mask=(torch.rand((2, 1, 5, 7), generator=torch.Generator().manual_seed(55)) < 0.5).float().to(DEV))
+    erow = (0.9, 0.43, 0.95, 0.31)
+    for place in ("aligned", "shifted"):
+        t = base if place == "aligned" else {k: shifted(v) for k, v in base.items()}
+        for stem, rows in STEP_ROWS.items():
+            for flag in ((False, True) if stem == "ddim" else (None,)):
+                for form in ("", "_rng", "_edit"):
+                    fn = getattr(ops, f"{stem}_step{form}")
+                    for pred in ("epsilon", "sample", "v_prediction"):
+                        for thr in (None, (0.9, 2.0)):
+                            kw = dict(clip=1.0, prediction_type=pred, threshold=thr)
+                            if flag is not None:
+                                kw["use_clipped_model_output"] = flag
+                            hist = torch.zeros_like(t["x"]) if stem == "dpmpp" else None
+                            x, shas = t["x"], []
+                            for row in rows:
+                                lead = (t["eps"], x) + ((t["z"],) if form == "" else (seeds, step))
+                                lead += (hist,) if hist is not None else ()
+                                tail = (t["x0k"], t["mask"], erow) if form == "_edit" else ()
+                                x = fn(*lead, row, *tail, **kw)
+                                shas.append(sha(x) if hist is None else f"{sha(x)} hist={sha(hist)}")
+                            item(f"step.gpu.{place}.{stem}{form}", f"flag{flag}.{pred}.thr{thr}", " ".join(shas))
+    eps, x0 = base["eps"], base["x"]
+    for tag, cls, kw, step_kw in (("ddpm", sch.HipDDPMScheduler, {}, {}), ("ddim", sch.HipDDIMScheduler, {}, dict(eta=0.5)),
+                                  ("dpmpp", sch.HipDPMSolverMultistepScheduler, dict(algorithm_type="sde-dpmsolver++"), {})):
+        sources = {"variance_noise": lambda: dict(variance_noise=base["z"]),
+                   "cpu_generator": lambda: dict(generator=torch.Generator().manual_seed(7)),
+                   "device_generator": lambda: dict(generator=torch.Generator(device=DEV).manual_seed(7))}
+        for name, source in sources.items():
+            s = cls(beta_schedule="squaredcos_cap_v2", **kw)
+            s.set_timesteps(10)
+            x, noise_kw = x0, source()
+            for t_ in s.timesteps[:2]:
+                x = s.step(eps, t_, x, **step_kw, **noise_kw).prev_sample
+            item(f"step.gpu.mirror.{tag}", name, sha(x))
+        ts = torch.tensor([37, 640])
+        item(f"step.gpu.mirror.{tag}", "add_noise", sha(s.add_noise(x0, eps, ts)))
+        item(f"step.gpu.mirror.{tag}", "get_velocity", sha(s.get_velocity(x0, eps, ts)))
+    torch.cuda.synchronize()
+    close_groups()
+
+
+def step_layer_times(calls: int = 2000) -> None:
+    """host cost of the layer: wall microseconds per call of each buffer-form wrapper and each mirror's ``step`` on [2,3,8,8],
+    nothing synchronised before the last call has been issued"""
+    shape = (2, 3, 8, 8)
+    x, eps, z = (rand(shape, 60 + i).to(DEV) for i in range(3))
+    hist = torch.zeros_like(x)
+    wrappers = {"ops.ddpm_step": lambda: ops.ddpm_step(eps, x, z, STEP_ROWS["ddpm"][0]),
+                "ops.ddim_step": lambda: ops.ddim_step(eps, x, z, STEP_ROWS["ddim"][0]),
+                "ops.dpmpp_step": lambda: ops.dpmpp_step(eps, x, z, hist, STEP_ROWS["dpmpp"][1])}
+    for name, call in wrappers.items():
+        call()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            call()
+        torch.cuda.synchronize()
+        emit(f"time.{name}.us_per_call", f"{(time.perf_counter() - t0) / calls * 1e6:.2f}")
+    for tag, cls, kw in (("ddpm", sch.HipDDPMScheduler, {}), ("ddim", sch.HipDDIMScheduler, {}),
+                         ("dpmpp", sch.HipDPMSolverMultistepScheduler, dict(timestep_spacing="leading"))):
+        s = cls(beta_schedule="squaredcos_cap_v2", **kw)
+        spent, timed = 0.0, 0
+        while timed < calls:            # runs of the whole 1000-step grid; the first step of a run (DPM-Solver++ builds its tables) untimed
+            s.set_timesteps(1000)
+            s.step(eps, s.timesteps[0], x)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t_ in s.timesteps[1:min(1000, 1 + calls - timed)]:
+                s.step(eps, t_, x)
+                timed += 1
+            torch.cuda.synchronize()
+            spent += time.perf_counter() - t0
+        emit(f"time.{cls.__name__}.step.us_per_call", f"{spent / timed * 1e6:.2f}")
+
+
 def main() -> None:
     sd = synthetic_unet_state_dict()
     if "--rider0-child" in sys.argv:             # SISIC_GN_RIDER is read when a model is created: a process of its own
@@ -187,6 +374,13 @@ def main() -> None:
         s.add_model("NV", sd)
         unet_forward(s, "b2_64_rider0", 2, 64)
         return
+    if "--step-layer-times" in sys.argv:
+        return step_layer_times()
+    step_layer_host()                            # first, and without the GPU: a machine that has none compares these lines
+    if "--host-only" in sys.argv:
+        return
+    if "--step-layer" in sys.argv:
+        return step_layer_gpu()
     print("library:", _lib.lib_path(), file=sys.stderr)
     unet_items(sd)
     sys.stdout.flush()
@@ -194,6 +388,7 @@ def main() -> None:
                    env=dict(os.environ, SISIC_GN_RIDER="0"))
     train_items(sd)
     classifier_items()
+    step_layer_gpu()
 
 
 if __name__ == "__main__":
