@@ -712,8 +712,11 @@ int sisic_unet_train_step(sisic_unet*, const float* images, const float* noise, 
                           double beta1, double beta2, double eps, float loss_scale, float* loss_out, int* found_inf, void* stream);
 /* ---- global-norm gradient clipping and an exponential moving average of the weights -----------------------------------
  * What diffusers' unconditional training example wraps round the same UNet2DModel: torch.nn.utils.clip_grad_norm_ before
- * the optimizer step and EMAModel.step after it.  Everything here is an addition: a caller of the entry points above gets
- * the launches it always got.
+ * the optimizer step and EMAModel.step after it.  One path: every optimizer step of the library, the entry points above
+ * included, is the same two passes -- a statistics pass over the gradient (run if and only if ext != NULL or found_inf !=
+ * NULL; its 12-byte read-back is the one synchronisation) and one fused Adam + EMA pass, which reads the clip coefficient
+ * from the statistics record when the first pass ran and takes it as 1 otherwise.  A plain step with found_inf == NULL is
+ * the second pass alone: one launch, nothing waits.  The training kernels have no atomics at all.
  *
  * sisic_optim_ext (16 bytes; the double comes first so that the struct has no padding):
  *   ema_decay      at 0, double: the decay of THIS step (EMAModel.get_decay; the caller computes it per step)
@@ -759,7 +762,8 @@ int sisic_unet_ema_active(const sisic_unet*);
 /* The two kernels on the caller's device vectors (parity-test surface; any n >= 1, pointers aligned to a float; scratch is
  * allocated per call).  grad_stats writes the record {float total_norm; float clip_coef; int found_inf} (3 x 4 bytes) to
  * stats_dev.  adam_ema: one Adam step number `step` (>= 1) on p, m, v from g, reading clip_coef from stats_dev (NULL: 1)
- * and updating ema (NULL: none) with ema_decay; with both NULL it is the kernel of sisic_unet_optimizer_step.
+ * and updating ema (NULL: none) with ema_decay; with both NULL it is the update sisic_unet_optimizer_step launches (the
+ * same kernel: there is one).
  * sisic_grad_stats: Synchronises the stream: the scratch is freed before the call returns.  sisic_adam_ema allocates
  * nothing and does not wait.                                                                                           */
 int sisic_grad_stats(sisic_ctx*, const float* g, int64_t n, float inv_scale, float max_norm, void* stats_dev, void* stream);

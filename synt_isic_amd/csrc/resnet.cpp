@@ -860,14 +860,7 @@ int train_begin_plain(sisic_resnet* r) {
         SISIC_TRY(plan(b.conv2));
         if (b.down.k) SISIC_TRY(plan(b.down));
     }
-    for (int p = 0; p < 3; ++p) {
-        int blocks = 0;
-        for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
-        SISIC_HIP(hipMalloc(&tr->plain_dev[p], ph[p].size() * sizeof(PackJob)));
-        SISIC_HIP(hipMemcpy(tr->plain_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
-        tr->plain_jobs[p] = (int)ph[p].size();
-        tr->plain_blocks[p] = blocks;
-    }
+    for (int p = 0; p < 3; ++p) SISIC_TRY(upload_pack_table(ph[p], &tr->plain_dev[p], &tr->plain_jobs[p], &tr->plain_blocks[p]));
     return rebuild_plain_forms(r, nullptr);
 }
 
@@ -1115,14 +1108,7 @@ int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
             plan(b.conv2);
             if (b.down.k) plan(b.down);
         }
-        for (int p = 0; p < 2; ++p) {
-            int blocks = 0;
-            for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
-            SISIC_HIP(hipMalloc(&tr->repack_dev[p], ph[p].size() * sizeof(PackJob)));
-            SISIC_HIP(hipMemcpy(tr->repack_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
-            tr->repack_jobs[p] = (int)ph[p].size();
-            tr->repack_blocks[p] = blocks;
-        }
+        for (int p = 0; p < 2; ++p) SISIC_TRY(upload_pack_table(ph[p], &tr->repack_dev[p], &tr->repack_jobs[p], &tr->repack_blocks[p]));
     }
     if (bn_mode == 1) SISIC_TRY(train_begin_plain(r));
     SISIC_HIP(hipDeviceSynchronize());
@@ -1294,27 +1280,22 @@ int sisic_resnet_optimizer_step(sisic_resnet* r, sisic_resnet_train_args* a) {
     ResnetTrain* tr = r->train;
     SISIC_HIP(hipSetDevice(r->ctx->device));
     hipStream_t s = static_cast<hipStream_t>(a->stream);
-    SISIC_TRY(launch_grad_stats(r->ctx, tr->grad, tr->floats, 1.0f, a->max_grad_norm, stats_record(tr), stats_scratch(tr), s));
-    GradStats host{};
-    SISIC_HIP(hipMemcpyAsync(&host, stats_record(tr), sizeof(GradStats), hipMemcpyDeviceToHost, s));
-    SISIC_HIP(hipStreamSynchronize(s));
-    a->grad_norm = host.total_norm;
-    a->found_inf = host.found_inf;
+    AdamStepArgs o;
+    o.p = tr->param; o.g = tr->grad; o.m = tr->adam_m; o.v = tr->adam_v; o.n = tr->floats;
+    o.lr = a->lr; o.beta1 = a->beta1; o.beta2 = a->beta2; o.eps = a->eps; o.max_norm = a->max_grad_norm;
+    o.step = &tr->step; o.stats = stats_record(tr); o.scratch = stats_scratch(tr);
+    o.want_stats = o.skip_on_inf = true;
+    AdamStepResult res;
+    SISIC_TRY(adam_step(r->ctx, o, &res, s));
+    a->grad_norm = res.norm;
+    a->found_inf = res.found_inf;
     if (tr->bn_mode == 1) {
         // batch statistics: the running statistics moved in loss_backward whether or not the update is skipped, so the inference
         // forms are derived again on every call
-        if (!host.found_inf) {
-            tr->step += 1;
-            SISIC_TRY(launch_adam_ema(r->ctx, tr->param, tr->grad, tr->adam_m, tr->adam_v, nullptr, tr->floats, a->lr, a->beta1, a->beta2,
-                                      a->eps, tr->step, 1.0f, stats_record(tr), 0.0, s));
-            SISIC_TRY(rebuild_plain_forms(r, s));
-        }
+        if (!res.skipped) SISIC_TRY(rebuild_plain_forms(r, s));
         return refresh_inference_forms(r, s);
     }
-    if (host.found_inf) return SISIC_OK;                 // no update: parameters, moments and the step counter stay
-    tr->step += 1;
-    SISIC_TRY(launch_adam_ema(r->ctx, tr->param, tr->grad, tr->adam_m, tr->adam_v, nullptr, tr->floats, a->lr, a->beta1, a->beta2, a->eps,
-                              tr->step, 1.0f, stats_record(tr), 0.0, s));
+    if (res.skipped) return SISIC_OK;                    // no update: parameters, moments and the step counter stay
     SISIC_TRY(for_each_conv(r, [&](FoldedConv& c) {
         return launch_refold(r->ctx, tr->param + tr->off[c.w_idx], c.sc, c.raw, c.raw_t, c.cout, c.cin, c.k, s);
     }));

@@ -6,8 +6,11 @@
 //     loss = F.mse_loss(noise_pred, noise)                             sisic_mse_loss            (loss and d loss / d pred)
 //     scaler.scale(loss).backward()                                    sisic_unet_backward       (walks the tape backwards)
 //     scaler.step(optimizer); scaler.update()                          sisic_unet_optimizer_step (unscale, inf check, Adam)
-// and sisic_unet_train_step runs the five in one call on one stream.  The forward is the inference executor of unet.cpp
-// in tape mode: same kernels (Winograd / direct MFMA convolutions with fused GroupNorm+SiLU prologues, GroupNorm
+// and sisic_unet_train_step runs the five in one call on one stream.  One path: the three fused steps (plain, _ext, _cond) fill
+// the arguments of one train_step; every optimizer step, the classifier's included, is adam_step (train.h: a statistics pass
+// when clipping, the norm or found_inf is asked for, then one fused Adam + EMA pass); every loss is one kernel
+// (mse_objective_kernel); every job table goes up through upload_pack_table.  The training kernels have no atomics at all.
+// The forward is the inference executor of unet.cpp in tape mode: same kernels (Winograd / direct MFMA convolutions with fused GroupNorm+SiLU prologues, GroupNorm
 // statistics from convolution epilogues, attention), nothing released, every GroupNorm's scale/shift/(mean, rstd) kept.
 // Backward per convolution: bias / time-embedding sums, backward-weight (conv_wgrad_kernel), backward-data as a
 // forward convolution with transposed filters, then GroupNorm+SiLU backward into the input's gradient.
@@ -16,12 +19,34 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "conv_plan.h"
 #include "train.h"
 #include "unet_internal.h"
 
 using namespace sisic;
+
+int sisic::upload_pack_table(std::vector<PackJob>& jobs, void** dev, int* njobs, int* nblocks) {
+    int blocks = 0;
+    for (PackJob& j : jobs) { j.first_block = blocks; blocks += pack_job_blocks(j); }
+    if (*dev) { (void)hipFree(*dev); *dev = nullptr; }
+    const size_t bytes = std::max<size_t>(jobs.size(), 1) * sizeof(PackJob);         // (an empty table still has an address)
+    SISIC_HIP(hipMalloc(dev, bytes));
+    SISIC_TRY(poison_fresh(*dev, bytes));
+    if (!jobs.empty()) SISIC_HIP(hipMemcpy(*dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    *njobs = (int)jobs.size();
+    *nblocks = blocks;
+    return SISIC_OK;
+}
+
+// what TrainState owns on the device (the tape's pool blocks are the handle's: unet_release_tape)
+TrainState::~TrainState() {
+    for (void* p : {(void*)grad, (void*)adam_m, (void*)adam_v, (void*)emb, (void*)h1, (void*)t2, (void*)dtproj, (void*)labels_dev,
+                    (void*)garena, (void*)wgrad_part, (void*)scratch, (void*)small, (void*)loss_dev, (void*)mse_part, stats_dev,
+                    (void*)ema, repack_dev[0], repack_dev[1], repack_dev[2], scatter_dev})
+        if (p) (void)hipFree(p);
+}
 
 namespace {
 
@@ -87,16 +112,7 @@ int build_repack_plan(sisic_unet* u) {
         ph[1].push_back(pack_job_flip(a->qkv_cat, 3 * c, c, 1, a->qkv_raw_t));
         ph[2].push_back(pack_job_conv(a->qkv_raw_t, c, 3 * c, 1, a->qkv_packed_t));
     }
-    for (int p = 0; p < 3; ++p) {
-        int blocks = 0;
-        for (PackJob& j : ph[p]) { j.first_block = blocks; blocks += pack_job_blocks(j); }
-        if (tr->repack_dev[p]) { (void)hipFree(tr->repack_dev[p]); tr->repack_dev[p] = nullptr; }
-        SISIC_HIP(hipMalloc(&tr->repack_dev[p], std::max<size_t>(ph[p].size(), 1) * sizeof(PackJob)));
-        SISIC_TRY(poison_fresh(tr->repack_dev[p], std::max<size_t>(ph[p].size(), 1) * sizeof(PackJob)));
-        SISIC_HIP(hipMemcpy(tr->repack_dev[p], ph[p].data(), ph[p].size() * sizeof(PackJob), hipMemcpyHostToDevice));
-        tr->repack_jobs[p] = (int)ph[p].size();
-        tr->repack_blocks[p] = blocks;
-    }
+    for (int p = 0; p < 3; ++p) SISIC_TRY(upload_pack_table(ph[p], &tr->repack_dev[p], &tr->repack_jobs[p], &tr->repack_blocks[p]));
     tr->repack_ready = true;
     return SISIC_OK;
 }
@@ -252,7 +268,7 @@ struct Bwd {
     // time embedding: tproj = time_emb_proj(ta), ta = silu(t2), t2 = linear_2(silu(h1)), h1 = linear_1(emb)
     int time_embedding() {
         const int R = u->tproj_R, Hd = u->hidden, nin = 2 * u->cfg.n_freqs;
-        const size_t need = (size_t)R * Hd + R + (size_t)6 * B * Hd;
+        const size_t need = (size_t)R * Hd + R + (size_t)5 * B * Hd;
         SISIC_TRY(unet_grow(&tr->wgrad_part, &tr->wgrad_part_cap, need));
         float* dWf = tr->wgrad_part;                // [R][Hd]
         float* dbf = dWf + (size_t)R * Hd;          // [R]
@@ -261,7 +277,6 @@ struct Bwd {
         float* a1 = dt2 + (size_t)B * Hd;
         float* da1 = a1 + (size_t)B * Hd;
         float* dh1 = da1 + (size_t)B * Hd;
-        float* ones = dh1 + (size_t)B * Hd;         // scratch [B][Hd]
         // fused projection of the 22 residual blocks
         SISIC_TRY(launch_linear_wgrad(u->ctx, tr->dtproj, R, u->temb_act, B, R, Hd, dWf, s));
         SISIC_TRY(launch_col_sums(u->ctx, tr->dtproj, B, R, R, dbf, 0, s));
@@ -272,14 +287,9 @@ struct Bwd {
                 jobs.push_back(pack_job_copy(dWf + (size_t)r->temb_off * Hd, grad_of(u, r->temb_w_idx), (size_t)r->cout * Hd));
                 jobs.push_back(pack_job_copy(dbf + r->temb_off, grad_of(u, r->temb_b_idx), (size_t)r->cout));
             }
-            int blocks = 0;
-            for (PackJob& j : jobs) { j.first_block = blocks; blocks += pack_job_blocks(j); }
             SISIC_HIP(hipStreamSynchronize(s));          // (a table in use is not replaced under a running launch)
-            if (tr->scatter_dev) { (void)hipFree(tr->scatter_dev); tr->scatter_dev = nullptr; }
-            SISIC_HIP(hipMalloc(&tr->scatter_dev, std::max<size_t>(jobs.size(), 1) * sizeof(PackJob)));
-            SISIC_TRY(poison_fresh(tr->scatter_dev, std::max<size_t>(jobs.size(), 1) * sizeof(PackJob)));
-            SISIC_HIP(hipMemcpy(tr->scatter_dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
-            tr->scatter_jobs = (int)jobs.size(); tr->scatter_blocks = blocks; tr->scatter_src = dWf;
+            SISIC_TRY(upload_pack_table(jobs, &tr->scatter_dev, &tr->scatter_jobs, &tr->scatter_blocks));
+            tr->scatter_src = dWf;
         }
         SISIC_TRY(launch_pack_batch(u->ctx, static_cast<const PackJob*>(tr->scatter_dev), tr->scatter_jobs, tr->scatter_blocks, s));
         // d ta[b][k] = sum_r dtproj[b][r] * Wfused[r][k]; the fused weight is stored transposed: tproj_wt[k][r]
@@ -298,7 +308,6 @@ struct Bwd {
         // linear_1: h1 = emb W1^T + b1
         SISIC_TRY(launch_linear_wgrad(u->ctx, dh1, Hd, tr->emb, B, Hd, nin, grad_of(u, u->temb_w1), s));
         SISIC_TRY(launch_col_sums(u->ctx, dh1, B, Hd, Hd, grad_of(u, u->temb_b1), 0, s));
-        (void)ones;
         return SISIC_OK;
     }
 
@@ -371,6 +380,26 @@ int require_not_swapped(sisic_unet* u, const char* what) {
     return SISIC_OK;
 }
 
+// The one loss launch: stages the rows the objective reads -- {sa, sb} of the v target (coef: host [2B], with noise; else
+// nullptr), then the handle's loss weights when it has any -- into objective_dev and runs the one kernel.  B: the samples n is
+// divided into (the caller has checked the weight table against it).
+int mse_objective(sisic_unet* u, const float* pred, const float* target, const float* noise, const float* coef, int B, size_t n,
+                  float grad_scale, float* loss_dev, float* dpred, hipStream_t s) {
+    const bool weighted = !u->loss_w.empty();
+    const float* rows = nullptr;
+    if (noise || weighted) {
+        std::vector<float> host;
+        if (noise) host.assign(coef, coef + 2 * (size_t)B);
+        if (weighted) host.insert(host.end(), u->loss_w.begin(), u->loss_w.end());
+        SISIC_TRY(unet_grow(&u->objective_dev, &u->objective_cap, 3 * (size_t)B));
+        SISIC_TRY(unet_stage_upload(u, host.data(), host.size(), u->objective_dev, s));
+        rows = u->objective_dev;
+    }
+    const float* w = weighted ? rows + (noise ? 2 * (size_t)B : 0) : nullptr;
+    return launch_mse_objective(u->ctx, pred, target, noise, noise ? rows : nullptr, noise ? rows + B : nullptr, w, B, n, grad_scale,
+                                loss_dev, dpred, u->train->mse_part, 2048, s);
+}
+
 // the loop body of sisic_unet_train_step up to the optimizer step: add_noise, forward, MSE, backward, the loss read-back
 // class_labels: host int64 [B] of a conditional model, or nullptr
 int train_forward_impl(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels, float* out, int B,
@@ -409,20 +438,9 @@ int train_step_body(sisic_unet* u, const float* images, const float* noise, cons
     SISIC_TRY(train_forward_impl(u, noisy, timesteps, class_labels, pred, B, H, W, stream));
     // the objective: the target follows the handle's prediction type -- the noise, the image, or v formed
     // in the loss kernel's registers from the two rows above (no target tensor) -- and the handle's loss weights apply
-    if (u->pred_type == SISIC_PRED_V || weighted) {
-        SISIC_TRY(unet_grow(&u->objective_dev, &u->objective_cap, 3 * (size_t)B));
-        std::vector<float> rows(coef);
-        if (weighted) rows.insert(rows.end(), u->loss_w.begin(), u->loss_w.end());
-        SISIC_TRY(unet_stage_upload(u, rows.data(), rows.size(), u->objective_dev, s));
-        const bool v = u->pred_type == SISIC_PRED_V;
-        const float* target = u->pred_type == SISIC_PRED_EPSILON ? noise : images;
-        SISIC_TRY(launch_mse_objective(u->ctx, pred, target, v ? noise : nullptr, v ? u->objective_dev : nullptr,
-                                       v ? u->objective_dev + B : nullptr, weighted ? u->objective_dev + 2 * (size_t)B : nullptr, B, n,
-                                       loss_scale, tr->loss_dev, dpred, tr->mse_part, 2048, s));
-    } else {
-        SISIC_TRY(launch_mse(u->ctx, pred, u->pred_type == SISIC_PRED_SAMPLE ? images : noise, n, loss_scale, tr->loss_dev, dpred,
-                             tr->mse_part, 2048, s));
-    }
+    const bool v = u->pred_type == SISIC_PRED_V;
+    SISIC_TRY(mse_objective(u, pred, u->pred_type == SISIC_PRED_EPSILON ? noise : images, v ? noise : nullptr, v ? coef.data() : nullptr,
+                            B, n, loss_scale, tr->loss_dev, dpred, s));
     SISIC_TRY(sisic_unet_backward(u, dpred, stream));
     if (loss_out) {
         SISIC_HIP(hipMemcpyAsync(loss_out, tr->loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
@@ -474,6 +492,71 @@ int train_forward_impl(sisic_unet* u, const float* sample, const int64_t* timest
 GradStats* stats_record(TrainState* tr) { return static_cast<GradStats*>(tr->stats_dev); }
 void* stats_scratch(TrainState* tr) { return static_cast<char*>(tr->stats_dev) + 16; }
 
+// The optimizer step of the three entry points that take one.  ext_entry: the call came through an _ext entry point (its
+// statistics pass always runs, and grad_norm_out is written); otherwise the pass runs only for found_inf.
+int optimizer_step(sisic_unet* u, const char* who, bool ext_entry, double lr, double beta1, double beta2, double eps, float inv_scale,
+                   const sisic_optim_ext* ext, int* found_inf, float* grad_norm_out, hipStream_t s) {
+    SISIC_TRY(require_train(u, who));
+    SISIC_TRY(require_not_swapped(u, who));
+    TrainState* tr = u->train.get();
+    SISIC_HIP(hipSetDevice(u->ctx->device));
+    const bool ema_on = ext && ext->ema_update != 0;
+    if (ema_on) {
+        if (!tr->ema) {
+            set_error("%s: ema_update without an EMA arena (call sisic_unet_ema_begin first)", who);
+            return SISIC_ESTATE;
+        }
+        SISIC_REQUIRE(ext->ema_decay >= 0.0 && ext->ema_decay <= 1.0, "%s: ema_decay %g is outside [0, 1]", who, ext->ema_decay);
+    }
+    AdamStepArgs a;
+    a.p = u->raw; a.g = tr->grad; a.m = tr->adam_m; a.v = tr->adam_v; a.n = u->raw_floats;
+    a.ema = ema_on ? tr->ema : nullptr; a.ema_decay = ema_on ? ext->ema_decay : 0.0;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+    a.inv_scale = inv_scale; a.max_norm = ext ? ext->max_grad_norm : 0.0f;
+    a.step = &tr->step; a.stats = stats_record(tr); a.scratch = stats_scratch(tr);
+    a.want_stats = ext_entry || found_inf;       // GradScaler.step: without found_inf there is no check and no skip
+    a.skip_on_inf = found_inf != nullptr;
+    AdamStepResult r;
+    SISIC_TRY(adam_step(u->ctx, a, &r, s));
+    if (ext_entry && grad_norm_out) *grad_norm_out = r.norm;
+    if (found_inf) *found_inf = r.found_inf;
+    return r.skipped ? SISIC_OK : repack_after_update(u, s);
+}
+
+// The fused step of the three entry points: the checks, the loop body, the optimizer step.  `who` names the entry point in
+// every refusal; cond: the entry takes labels; ext_entry: as optimizer_step.
+struct TrainStepArgs {
+    const char* who;
+    bool cond, ext_entry;
+    const float* images; const float* noise; const int64_t* timesteps; const int64_t* class_labels;
+    const float* sqrt_alpha_prod; const float* sqrt_one_minus_alpha_prod;
+    int B, H, W;
+    double lr, beta1, beta2, eps;
+    float loss_scale;
+    const sisic_optim_ext* ext;
+    float* loss_out; int* found_inf; float* grad_norm_out;
+    void* stream;
+};
+
+int train_step(sisic_unet* u, const TrainStepArgs& a) {
+    SISIC_TRY(require_train(u, a.who));
+    SISIC_TRY(require_not_swapped(u, a.who));
+    SISIC_REQUIRE(a.images && a.noise && a.timesteps && a.sqrt_alpha_prod && a.sqrt_one_minus_alpha_prod, "%s: null argument", a.who);
+    SISIC_TRY(unet_check_labels(u, a.who, a.cond, a.class_labels, a.B));
+    SISIC_TRY(train_step_body(u, a.images, a.noise, a.timesteps, a.class_labels, a.sqrt_alpha_prod, a.sqrt_one_minus_alpha_prod, a.B, a.H,
+                              a.W, a.loss_scale, a.loss_out, a.stream));
+    return optimizer_step(u, a.ext_entry ? "optimizer_step_ext" : "optimizer_step", a.ext_entry, a.lr, a.beta1, a.beta2, a.eps,
+                          1.0f / a.loss_scale, a.ext, a.found_inf, a.grad_norm_out, static_cast<hipStream_t>(a.stream));
+}
+
+int train_forward(sisic_unet* u, const char* who, bool cond, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
+                  float* out, int B, int H, int W, void* stream) {
+    SISIC_TRY(require_train(u, who));
+    SISIC_REQUIRE(sample && timesteps && out, "%s: null argument", who);
+    SISIC_TRY(unet_check_labels(u, who, cond, class_labels, B));
+    return train_forward_impl(u, sample, timesteps, class_labels, out, B, H, W, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -487,23 +570,18 @@ int sisic_unet_train_begin(sisic_unet* u) {
     SISIC_HIP(hipSetDevice(u->ctx->device));
     if (!u->train) {
         auto tr = std::make_unique<TrainState>();
-        const size_t bytes = u->raw_floats * sizeof(float);
-        for (float** p : {&tr->grad, &tr->adam_m, &tr->adam_v}) {
+        // (a failure below frees what has been allocated: ~TrainState)
+        auto alloc = [](size_t bytes, auto** out) {
             void* q = nullptr;
             SISIC_HIP(hipMalloc(&q, bytes));
-            SISIC_TRY(poison_fresh(q, bytes));       // (all three are zero-filled below, as ever)
-            *p = static_cast<float*>(q);
-        }
-        void* q = nullptr;
-        SISIC_HIP(hipMalloc(&q, 4 * sizeof(float)));
-        SISIC_TRY(poison_fresh(q, 4 * sizeof(float)));
-        tr->loss_dev = static_cast<float*>(q);
-        SISIC_HIP(hipMalloc(&q, sizeof(int)));
-        SISIC_TRY(poison_fresh(q, sizeof(int)));
-        tr->flag_dev = static_cast<int*>(q);
-        SISIC_HIP(hipMalloc(&q, 2048 * sizeof(float)));
-        SISIC_TRY(poison_fresh(q, 2048 * sizeof(float)));
-        tr->mse_part = static_cast<float*>(q);
+            *out = static_cast<std::remove_reference_t<decltype(*out)>>(q);
+            return poison_fresh(q, bytes);
+        };
+        for (float** p : {&tr->grad, &tr->adam_m, &tr->adam_v})
+            SISIC_TRY(alloc(u->raw_floats * sizeof(float), p));            // (all three are zero-filled below, as ever)
+        SISIC_TRY(alloc(4 * sizeof(float), &tr->loss_dev));
+        SISIC_TRY(alloc(2048 * sizeof(float), &tr->mse_part));
+        SISIC_TRY(alloc(16 + grad_stats_scratch_bytes(), &tr->stats_dev));
         u->train = std::move(tr);
     }
     TrainState* tr = u->train.get();
@@ -523,15 +601,6 @@ int sisic_unet_train_end(sisic_unet* u) {
     if (!u || !u->train) return SISIC_OK;
     (void)hipDeviceSynchronize();
     unet_release_tape(u);
-    TrainState* tr = u->train.get();
-    for (float* p : {tr->grad, tr->adam_m, tr->adam_v, tr->emb, tr->h1, tr->t2, tr->dtproj, tr->garena, tr->wgrad_part, tr->scratch,
-                     tr->small, tr->loss_dev, tr->mse_part, tr->ema, tr->labels_dev})
-        if (p) (void)hipFree(p);
-    if (tr->stats_dev) (void)hipFree(tr->stats_dev);
-    if (tr->scatter_dev) (void)hipFree(tr->scatter_dev);
-    for (void* p : tr->repack_dev)
-        if (p) (void)hipFree(p);
-    if (tr->flag_dev) (void)hipFree(tr->flag_dev);
     u->train.reset();
     return SISIC_OK;
 }
@@ -566,18 +635,12 @@ int sisic_unet_zero_grad(sisic_unet* u, void* stream) {
 
 int sisic_unet_train_forward(sisic_unet* u, const float* sample, const int64_t* timesteps, float* out, int B, int H, int W,
                              void* stream) {
-    SISIC_TRY(require_train(u, "train_forward"));
-    SISIC_REQUIRE(sample && timesteps && out, "train_forward: null argument");
-    SISIC_TRY(unet_check_labels(u, "train_forward", false, nullptr, B));
-    return train_forward_impl(u, sample, timesteps, nullptr, out, B, H, W, stream);
+    return train_forward(u, "train_forward", false, sample, timesteps, nullptr, out, B, H, W, stream);
 }
 
 int sisic_unet_train_forward_cond(sisic_unet* u, const float* sample, const int64_t* timesteps, const int64_t* class_labels,
                                   float* out, int B, int H, int W, void* stream) {
-    SISIC_TRY(require_train(u, "train_forward_cond"));
-    SISIC_REQUIRE(sample && timesteps && out, "train_forward_cond: null argument");
-    SISIC_TRY(unet_check_labels(u, "train_forward_cond", true, class_labels, B));
-    return train_forward_impl(u, sample, timesteps, class_labels, out, B, H, W, stream);
+    return train_forward(u, "train_forward_cond", true, sample, timesteps, class_labels, out, B, H, W, stream);
 }
 
 int sisic_unet_backward(sisic_unet* u, const float* dout, void* stream) {
@@ -598,18 +661,12 @@ int sisic_unet_backward(sisic_unet* u, const float* dout, void* stream) {
 int sisic_mse_loss(sisic_unet* u, const float* pred, const float* target, int64_t n, float grad_scale, float* loss_dev,
                    float* dpred, void* stream) {
     SISIC_TRY(require_train(u, "mse_loss"));
-    if (!u->loss_w.empty()) {
-        const size_t B = u->loss_w.size();
-        SISIC_REQUIRE(pred && target && n > 0 && (size_t)n % B == 0,
-                      "mse_loss: %lld elements are not %d equal samples (sisic_unet_set_loss_weights)", (long long)n, (int)B);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        SISIC_TRY(unet_grow(&u->objective_dev, &u->objective_cap, 3 * B));
-        SISIC_TRY(unet_stage_upload(u, u->loss_w.data(), B, u->objective_dev, s));
-        return launch_mse_objective(u->ctx, pred, target, nullptr, nullptr, nullptr, u->objective_dev, (int)B, (size_t)n, grad_scale,
-                                    loss_dev ? loss_dev : u->train->loss_dev, dpred, u->train->mse_part, 2048, s);
-    }
-    return launch_mse(u->ctx, pred, target, (size_t)n, grad_scale, loss_dev ? loss_dev : u->train->loss_dev, dpred,
-                      u->train->mse_part, 2048, static_cast<hipStream_t>(stream));
+    const bool weighted = !u->loss_w.empty();
+    const size_t B = weighted ? u->loss_w.size() : 1;
+    SISIC_REQUIRE(!weighted || (pred && target && n > 0 && (size_t)n % B == 0),
+                  "mse_loss: %lld elements are not %d equal samples (sisic_unet_set_loss_weights)", (long long)n, (int)B);
+    return mse_objective(u, pred, target, nullptr, nullptr, (int)B, (size_t)n, grad_scale, loss_dev ? loss_dev : u->train->loss_dev, dpred,
+                         static_cast<hipStream_t>(stream));
 }
 
 int sisic_add_noise(sisic_ctx* ctx, const float* x0, const float* noise, const float* sqrt_alpha_prod,
@@ -620,109 +677,44 @@ int sisic_add_noise(sisic_ctx* ctx, const float* x0, const float* noise, const f
                             static_cast<hipStream_t>(stream));
 }
 
+// scaler.step(optimizer): one update launch; with found_inf the statistics pass, its 12-byte read-back and the skip decision first
 int sisic_unet_optimizer_step(sisic_unet* u, double lr, double beta1, double beta2, double eps, float inv_scale, int* found_inf,
                               void* stream) {
-    SISIC_TRY(require_train(u, "optimizer_step"));
-    SISIC_TRY(require_not_swapped(u, "optimizer_step"));
-    TrainState* tr = u->train.get();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    SISIC_HIP(hipSetDevice(u->ctx->device));
-    if (found_inf) {                 // GradScaler.step: skip the update when a gradient is inf / nan
-        SISIC_HIP(hipMemsetAsync(tr->flag_dev, 0, sizeof(int), s));
-        SISIC_TRY(launch_check_finite(u->ctx, tr->grad, u->raw_floats, tr->flag_dev, s));
-        int flag = 0;
-        SISIC_HIP(hipMemcpyAsync(&flag, tr->flag_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-        SISIC_HIP(hipStreamSynchronize(s));
-        *found_inf = flag;
-        if (flag) return SISIC_OK;
-    }
-    tr->step += 1;
-    SISIC_TRY(launch_adam(u->ctx, u->raw, tr->grad, tr->adam_m, tr->adam_v, u->raw_floats, lr, beta1, beta2, eps, tr->step,
-                          inv_scale, s));
-    return repack_after_update(u, s);
+    return optimizer_step(u, "optimizer_step", false, lr, beta1, beta2, eps, inv_scale, nullptr, found_inf, nullptr,
+                          static_cast<hipStream_t>(stream));
 }
 
-// The same step with clipping and / or the EMA: one statistics pass (norm, clip coefficient, found_inf), one 12-byte read-back,
-// the skip decision on the host as above (the step counter feeds the bias corrections and does not advance on a skipped step),
-// one fused update pass, the same repack tail.
+// The same step with clipping and / or the EMA: the statistics pass always runs (norm, clip coefficient, found_inf).
 int sisic_unet_optimizer_step_ext(sisic_unet* u, double lr, double beta1, double beta2, double eps, float inv_scale,
                                   const sisic_optim_ext* ext, int* found_inf, float* grad_norm_out, void* stream) {
-    SISIC_TRY(require_train(u, "optimizer_step_ext"));
-    SISIC_TRY(require_not_swapped(u, "optimizer_step_ext"));
-    TrainState* tr = u->train.get();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    SISIC_HIP(hipSetDevice(u->ctx->device));
-    const float max_norm = ext ? ext->max_grad_norm : 0.0f;
-    const bool ema_on = ext && ext->ema_update != 0;
-    const double decay = ext ? ext->ema_decay : 0.0;
-    if (ema_on) {
-        if (!tr->ema) {
-            set_error("optimizer_step_ext: ema_update without an EMA arena (call sisic_unet_ema_begin first)");
-            return SISIC_ESTATE;
-        }
-        SISIC_REQUIRE(decay >= 0.0 && decay <= 1.0, "optimizer_step_ext: ema_decay %g is outside [0, 1]", decay);
-    }
-    if (!tr->stats_dev) {
-        const size_t bytes = 16 + grad_stats_scratch_bytes();
-        SISIC_HIP(hipMalloc(&tr->stats_dev, bytes));
-        SISIC_TRY(poison_fresh(tr->stats_dev, bytes));
-    }
-    SISIC_TRY(launch_grad_stats(u->ctx, tr->grad, u->raw_floats, inv_scale, max_norm, stats_record(tr), stats_scratch(tr), s));
-    GradStats host{};
-    SISIC_HIP(hipMemcpyAsync(&host, stats_record(tr), sizeof(GradStats), hipMemcpyDeviceToHost, s));
-    SISIC_HIP(hipStreamSynchronize(s));
-    if (grad_norm_out) *grad_norm_out = host.total_norm;
-    if (found_inf) {                 // without it there is no check, as in sisic_unet_optimizer_step
-        *found_inf = host.found_inf;
-        if (host.found_inf) {        // EMAModel.step runs after scaler.step either way: the shadow moves towards unchanged weights
-            if (ema_on) SISIC_TRY(launch_ema(u->ctx, tr->ema, u->raw, u->raw_floats, decay, s));
-            return SISIC_OK;
-        }
-    }
-    tr->step += 1;
-    SISIC_TRY(launch_adam_ema(u->ctx, u->raw, tr->grad, tr->adam_m, tr->adam_v, ema_on ? tr->ema : nullptr, u->raw_floats, lr, beta1,
-                              beta2, eps, tr->step, inv_scale, stats_record(tr), decay, s));
-    return repack_after_update(u, s);
+    return optimizer_step(u, "optimizer_step_ext", true, lr, beta1, beta2, eps, inv_scale, ext, found_inf, grad_norm_out,
+                          static_cast<hipStream_t>(stream));
 }
 
 int sisic_unet_train_step(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
                           const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
                           double beta1, double beta2, double eps, float loss_scale, float* loss_out, int* found_inf,
                           void* stream) {
-    SISIC_TRY(require_train(u, "train_step"));
-    SISIC_TRY(require_not_swapped(u, "train_step"));
-    SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step: null argument");
-    SISIC_TRY(unet_check_labels(u, "train_step", false, nullptr, B));
-    SISIC_TRY(train_step_body(u, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
-                              stream));
-    return sisic_unet_optimizer_step(u, lr, beta1, beta2, eps, 1.0f / loss_scale, found_inf, stream);
+    return train_step(u, {"train_step", false, false, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H,
+                          W, lr, beta1, beta2, eps, loss_scale, nullptr, loss_out, found_inf, nullptr, stream});
 }
 
 int sisic_unet_train_step_ext(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
                               const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod, int B, int H, int W, double lr,
                               double beta1, double beta2, double eps, float loss_scale, const sisic_optim_ext* ext, float* loss_out,
                               int* found_inf, float* grad_norm_out, void* stream) {
-    SISIC_TRY(require_train(u, "train_step_ext"));
-    SISIC_TRY(require_not_swapped(u, "train_step_ext"));
-    SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step_ext: null argument");
-    SISIC_TRY(unet_check_labels(u, "train_step_ext", false, nullptr, B));
-    SISIC_TRY(train_step_body(u, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W, loss_scale, loss_out,
-                              stream));
-    return sisic_unet_optimizer_step_ext(u, lr, beta1, beta2, eps, 1.0f / loss_scale, ext, found_inf, grad_norm_out, stream);
+    return train_step(u, {"train_step_ext", false, true, images, noise, timesteps, nullptr, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B,
+                          H, W, lr, beta1, beta2, eps, loss_scale, ext, loss_out, found_inf, grad_norm_out, stream});
 }
 
+// ext == NULL: the plain step (no statistics pass unless found_inf asks; grad_norm_out is not written)
 int sisic_unet_train_step_cond(sisic_unet* u, const float* images, const float* noise, const int64_t* timesteps,
                                const int64_t* class_labels, const float* sqrt_alpha_prod, const float* sqrt_one_minus_alpha_prod,
                                int B, int H, int W, double lr, double beta1, double beta2, double eps, float loss_scale,
                                const sisic_optim_ext* ext, float* loss_out, int* found_inf, float* grad_norm_out, void* stream) {
-    SISIC_TRY(require_train(u, "train_step_cond"));
-    SISIC_TRY(require_not_swapped(u, "train_step_cond"));
-    SISIC_REQUIRE(images && noise && timesteps && sqrt_alpha_prod && sqrt_one_minus_alpha_prod, "train_step_cond: null argument");
-    SISIC_TRY(unet_check_labels(u, "train_step_cond", true, class_labels, B));
-    SISIC_TRY(train_step_body(u, images, noise, timesteps, class_labels, sqrt_alpha_prod, sqrt_one_minus_alpha_prod, B, H, W,
-                              loss_scale, loss_out, stream));
-    if (!ext) return sisic_unet_optimizer_step(u, lr, beta1, beta2, eps, 1.0f / loss_scale, found_inf, stream);
-    return sisic_unet_optimizer_step_ext(u, lr, beta1, beta2, eps, 1.0f / loss_scale, ext, found_inf, grad_norm_out, stream);
+    return train_step(u, {"train_step_cond", true, ext != nullptr, images, noise, timesteps, class_labels, sqrt_alpha_prod,
+                          sqrt_one_minus_alpha_prod, B, H, W, lr, beta1, beta2, eps, loss_scale, ext, loss_out, found_inf, grad_norm_out,
+                          stream});
 }
 
 // ---- the EMA arena (diffusers' EMAModel: shadow parameters beside the trained ones)
@@ -846,8 +838,6 @@ int sisic_adam_ema(sisic_ctx* ctx, float* p, const float* g, float* m, float* v,
                    double beta2, double eps, int64_t step, float inv_scale, const void* stats_dev, double ema_decay, void* stream) {
     SISIC_REQUIRE(ctx && p && g && m && v && n > 0 && step >= 1, "adam_ema: bad arguments");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // neither a record nor an EMA: the unchanged kernel of sisic_unet_optimizer_step
-    if (!stats_dev && !ema) return launch_adam(ctx, p, g, m, v, (size_t)n, lr, beta1, beta2, eps, step, inv_scale, s);
     return launch_adam_ema(ctx, p, g, m, v, ema, (size_t)n, lr, beta1, beta2, eps, step, inv_scale,
                            static_cast<const GradStats*>(stats_dev), ema_decay, s);
 }

@@ -1,6 +1,8 @@
 // train.h -- launchers of train_kernels.hip (used by train.cpp and by the single-operator C entry points).
 #pragma once
 
+#include <vector>
+
 #include "common.h"
 
 namespace sisic {
@@ -69,6 +71,9 @@ struct PackJob {
 };
 int pack_job_blocks(const PackJob& j);
 int launch_pack_batch(sisic_ctx*, const PackJob* dev_jobs, int njobs, int nblocks, hipStream_t s);
+// a job table onto the device: assigns every job's first_block, frees the table *dev held, allocates at least one slot, poisons
+// the fresh block and copies.  Blocking; a table a running launch still reads must not be replaced (the caller waits first).
+int upload_pack_table(std::vector<PackJob>& jobs, void** dev, int* njobs, int* nblocks);
 PackJob pack_job_copy(const float* src, float* dst, size_t n);
 PackJob pack_job_transpose2d(const float* in, int rows, int cols, float* out, int out_ld, int out_col0);
 PackJob pack_job_flip(const float* w, int Cout, int Cin, int KK, float* wt);
@@ -121,16 +126,12 @@ int launch_linear_dgrad(sisic_ctx*, const float* dy, int ld, const float* W, int
 int launch_class_embed_grad(sisic_ctx*, const float* dt, const int* labels, int B, int N, int hidden, float* dE, hipStream_t s);
 int launch_silu_fwd(sisic_ctx*, const float* pre, size_t n, float* out, hipStream_t s);
 int launch_silu_bwd(sisic_ctx*, const float* dy, const float* pre, size_t n, float* out, hipStream_t s);
-int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, float grad_scale, float* loss_dev, float* dpred,
-               float* part, int nparts, hipStream_t s);
-// launch_mse under another objective: the v target sa[b]*noise - sb[b]*target formed in the register (noise, sa, sb: all or none;
-// `target` is then x0), per-sample weights w (device [B], or NULL), or both; same grid and reduction as launch_mse
+// loss_dev[0] = mean(w_b (pred - t)^2) and dpred = grad_scale * 2 w_b (pred - t) / n in one launch plus a one-block finish, in a
+// fixed order.  t = target, or the v target sa[b]*noise - sb[b]*target formed in the register (noise, sa, sb: all or none;
+// `target` is then x0); w: per-sample weights (device [B]) or NULL.  With neither, B only has to divide n.
 int launch_mse_objective(sisic_ctx*, const float* pred, const float* target, const float* noise, const float* sa, const float* sb,
                          const float* w, int B, size_t n, float grad_scale, float* loss_dev, float* dpred, float* part, int nparts,
                          hipStream_t s);
-int launch_check_finite(sisic_ctx*, const float* g, size_t n, int* flag, hipStream_t s);
-int launch_adam(sisic_ctx*, float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps,
-                int64_t step, float inv_scale, hipStream_t s);
 // What grad_stats leaves on the device for adam_ema (and the host reads back in one 12-byte copy): the norm of the unscaled
 // gradient, clip_grad_norm_'s coefficient, GradScaler's found_inf.
 struct GradStats {
@@ -147,6 +148,29 @@ int launch_grad_stats(sisic_ctx*, const float* g, size_t n, float inv_scale, flo
 int launch_adam_ema(sisic_ctx*, float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double b1, double b2,
                     double eps, int64_t step, float inv_scale, const GradStats* stats_dev, double ema_decay, hipStream_t s);
 int launch_ema(sisic_ctx*, float* ema, const float* p, size_t n, double ema_decay, hipStream_t s);
+// The one optimizer update of the library (the UNet's plain and extended steps and the classifier's): when want_stats,
+// launch_grad_stats, one 12-byte read-back and one stream synchronisation; the skip decision on the host (skip_on_inf and a
+// non-finite gradient); then launch_adam_ema -- reading the record when the statistics pass ran, coefficient 1 otherwise -- or,
+// on a skipped step, launch_ema alone when there is an EMA.  *step advances only when the update runs.  Without want_stats
+// nothing waits for the stream and norm / found_inf come back 0.  The caller re-derives its packed weights afterwards.
+struct AdamStepArgs {
+    float* p = nullptr; const float* g = nullptr; float* m = nullptr; float* v = nullptr;
+    size_t n = 0;
+    float* ema = nullptr;               // EMA arena of this step, or nullptr
+    double ema_decay = 0.0;
+    double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0;
+    float inv_scale = 1.0f, max_norm = 0.0f;
+    int64_t* step = nullptr;
+    GradStats* stats = nullptr;         // the record and grad_stats' scratch (needed with want_stats only)
+    void* scratch = nullptr;
+    bool want_stats = false, skip_on_inf = false;
+};
+struct AdamStepResult {
+    float norm = 0.0f;
+    int found_inf = 0;
+    bool skipped = false;
+};
+int adam_step(sisic_ctx*, const AdamStepArgs& a, AdamStepResult* out, hipStream_t s);
 int launch_swap_arenas(sisic_ctx*, float* a, float* b, size_t n, hipStream_t s);
 int launch_add_noise(sisic_ctx*, const float* x0, const float* noise, const float* a_dev, const float* c_dev, float* out, int B,
                      size_t per, hipStream_t s);

@@ -1106,20 +1106,6 @@ int launch_silu_bwd(sisic_ctx*, const float* dy, const float* pre, size_t n, flo
 }
 
 // ================================================================ loss, optimizer ===================================
-// loss = mean((pred - target)^2)  (F.mse_loss, train_diffusion.py:219);  dpred = grad_scale * 2 (pred - target) / n
-__global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, size_t n,
-                                                          float gscale, float* __restrict__ dpred, float* __restrict__ part) {
-    __shared__ float red[4];
-    float s = 0.0f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float d = pred[i] - target[i];
-        s += d * d;
-        if (dpred) dpred[i] = gscale * d;
-    }
-    s = block_sum_256(s, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
 __global__ void __launch_bounds__(256) mse_final_kernel(const float* __restrict__ part, int nparts, float inv_n, float* __restrict__ loss) {
     __shared__ float red[4];
     float s = 0.0f;
@@ -1128,23 +1114,14 @@ __global__ void __launch_bounds__(256) mse_final_kernel(const float* __restrict_
     if (threadIdx.x == 0) loss[0] = s * inv_n;
 }
 
-int launch_mse(sisic_ctx*, const float* pred, const float* target, size_t n, float grad_scale, float* loss_dev, float* dpred,
-               float* part, int nparts, hipStream_t s) {
-    SISIC_REQUIRE(pred && target && loss_dev && part && n > 0 && nparts > 0, "mse: bad arguments");
-    const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)nparts);
-    hipLaunchKernelGGL(mse_partial_kernel, dim3(blocks), dim3(256), 0, s, pred, target, n, grad_scale * 2.0f / (float)n, dpred, part);
-    hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, part, blocks, 1.0f / (float)n, loss_dev);
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// The same loss under another objective: the target formed in the register, per-sample weights, or both.
+// loss = mean(w_b (pred - t)^2)  (F.mse_loss, train_diffusion.py:219, under the objective of DESIGN.md section 6);
+// dpred = grad_scale * 2 w_b (pred - t) / n.  ONE kernel for every objective:
 //   V:  t = sa[b]*noise - sb[b]*x0 (v-prediction: two products, one difference, each rounded -- the bits sisic_add_noise gives for
 //       (x0 := noise, noise := x0, a = sa, c = -sb)); `target` is then x0 and no target tensor exists.  Otherwise t = target[i].
-//   W:  g_b = c * w[b], dpred = g_b * d, and the sum takes w[b] * d^2.
-// Grid, grid-stride, block_sum_256 and mse_final_kernel are those of mse_partial_kernel, and so is the accumulate: that kernel
-// compiles `s += d * d` to ONE fused multiply-add, so this one spells the instruction out, s = fma(w*d, d, s).  With w = 1 the
-// product w*d is d and c*w is c exactly: weights of all ones give the loss and dpred bits of mse_partial_kernel.
+//   W:  g_b = c * w[b], dpred = g_b * d, and the sum takes w[b] * d^2.  Otherwise w_b = 1.
+// The accumulate is ONE fused multiply-add, spelled out: s = fma(w*d, d, s).  With w = 1 the product w*d is d and c*w is c
+// exactly: weights of all ones give the loss and dpred bits of the plain instance.  The sample index b = i / per exists only
+// under V or W: the plain instance carries no division.
 template <bool V, bool W>
 __global__ void __launch_bounds__(256) mse_objective_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                             const float* __restrict__ noise, const float* __restrict__ sa,
@@ -1155,7 +1132,8 @@ __global__ void __launch_bounds__(256) mse_objective_kernel(const float* __restr
     __shared__ float red[4];
     float s = 0.0f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t b = i / per;
+        size_t b = 0;
+        if constexpr (V || W) b = i / per;
         float t = target[i];
         if constexpr (V) {
             const float t0 = sa[b] * noise[i];
@@ -1177,67 +1155,23 @@ __global__ void __launch_bounds__(256) mse_objective_kernel(const float* __restr
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// noise, sa, sb (device [B]): the v target, all three or none; w (device [B]) or NULL; per = n / B
+// noise, sa, sb (device [B]): the v target, all three or none; w (device [B]) or NULL; per = n / B (with neither, B only has
+// to divide n: 1 will do)
 int launch_mse_objective(sisic_ctx*, const float* pred, const float* target, const float* noise, const float* sa, const float* sb,
                          const float* w, int B, size_t n, float grad_scale, float* loss_dev, float* dpred, float* part, int nparts,
                          hipStream_t s) {
     SISIC_REQUIRE(pred && target && loss_dev && part && n > 0 && nparts > 0 && B > 0 && n % (size_t)B == 0, "mse: bad arguments");
     SISIC_REQUIRE((noise != nullptr) == (sa != nullptr) && (noise != nullptr) == (sb != nullptr), "mse: the v target takes noise and both rows");
-    SISIC_REQUIRE(noise || w, "mse: neither a v target nor weights (launch_mse)");
     const int blocks = (int)std::min<size_t>((n + 255) / 256, (size_t)nparts);
     const size_t per = n / (size_t)B;
     const float c = grad_scale * 2.0f / (float)n;
 #define SISIC_MSE_OBJ(V, W) hipLaunchKernelGGL((mse_objective_kernel<V, W>), dim3(blocks), dim3(256), 0, s, pred, target, noise, sa, sb, w, per, n, c, dpred, part)
     if (noise && w) SISIC_MSE_OBJ(true, true);
     else if (noise) SISIC_MSE_OBJ(true, false);
-    else SISIC_MSE_OBJ(false, true);
+    else if (w) SISIC_MSE_OBJ(false, true);
+    else SISIC_MSE_OBJ(false, false);
 #undef SISIC_MSE_OBJ
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, part, blocks, 1.0f / (float)n, loss_dev);
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// flag |= 1 when any gradient is inf / nan (GradScaler's found_inf)
-__global__ void check_finite_kernel(const float* __restrict__ g, size_t n, int* __restrict__ flag) {
-    bool bad = false;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        bad = bad || !isfinite(g[i]);
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-int launch_check_finite(sisic_ctx*, const float* g, size_t n, int* flag, hipStream_t s) {
-    hipLaunchKernelGGL(check_finite_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, s, g, n, flag);
-    SISIC_HIP(hipGetLastError());
-    return SISIC_OK;
-}
-
-// torch.optim.Adam (single-tensor form, no weight decay, no amsgrad), in its operation order:
-//   m = lerp(m, g, 1 - b1);  v = v * b2 + ((1 - b2) g) g;  denom = sqrt(v) / sqrt(bc2) + eps;  p = p - (lr / bc1) * m / denom
-// addcmul_(g, g, value = 1 - b2) forms (value * g) * g: g * g first would overflow for |g| > 1.85e19 where torch's v stays finite.
-// g is first multiplied by inv_scale (GradScaler.unscale_).
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                            float one_minus_b1, float b2, float one_minus_b2, float step_size, float bc2_sqrt, float eps,
-                            float inv_scale) {
-#pragma clang fp contract(off)
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * inv_scale;
-        const float mi = m[i] + one_minus_b1 * (gi - m[i]);
-        const float vi = v[i] * b2 + (one_minus_b2 * gi) * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step_size * (mi / denom);
-    }
-}
-
-int launch_adam(sisic_ctx*, float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps,
-                int64_t step, float inv_scale, hipStream_t s) {
-    // the scalars as torch forms them: Python doubles (1 - beta, lr / bias_correction1, sqrt(bias_correction2)) rounded to
-    // fp32 once, when they meet the fp32 tensors
-    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, p, g, m, v, n,
-                       (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps,
-                       inv_scale);
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
 }
@@ -1265,8 +1199,10 @@ int launch_add_noise(sisic_ctx*, const float* x0, const float* noise, const floa
 
 // ================================================================ gradient statistics, Adam + EMA, arena swap =========
 // The optimizer step with global-norm clipping and an exponential moving average of the weights: ONE statistics pass over
-// the gradient (grad_stats: norm, clip coefficient, non-finite flag -- what check_finite_kernel reads) and ONE update pass
-// (adam_ema: adam_kernel's arithmetic on the clipped gradient, and the EMA of the updated weight while it is in a register).
+// the gradient (grad_stats: norm, clip coefficient, non-finite flag) and ONE update pass (adam_ema: torch.optim.Adam's
+// arithmetic on the clipped gradient, and the EMA of the updated weight while it is in a register).  Every optimizer step of
+// the library -- the UNet's plain and extended ones, the classifier's -- is adam_step below: these two passes, or the second
+// alone.  No kernel here has an atomic.
 //
 // 16 bytes per lane and access where the pointers allow it: scalar elements [0, head) up to the first 16-byte boundary,
 // n4 vectors of four from there, scalar elements [tail0, n) behind them.  Vectors that do not share their offset within 16
@@ -1293,7 +1229,7 @@ static VecSplit vec_split(std::initializer_list<const void*> ptrs, size_t n) {
 }
 
 // blocks of 256 threads for a grid-stride sweep of a split vector: enough for one element (vector or scalar) per thread, at
-// most per_cu blocks per CU of the device and never more than cap (adam_kernel's 4096 on a 256-CU device)
+// most per_cu blocks per CU of the device and never more than cap (4096: 16 per CU on a 256-CU device)
 static unsigned vec_grid(sisic_ctx* ctx, const VecSplit& vs, size_t n, int per_cu = 16, int cap = 4096) {
     const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const size_t want = (std::max(vs.n4, vs.head + (n - vs.tail0)) + 255) / 256;
@@ -1318,7 +1254,7 @@ __device__ __forceinline__ double block_sum_256_d(double v, double* red) {
 
 // Pass 1 of torch.nn.utils.clip_grad_norm_ over the unscaled gradient gi = fp32(g[i] * inv_scale), the value Adam consumes:
 // part[block] = sum of (double)gi * (double)gi over the block's grid-stride share, flags[block] = 1 when a g[i] of the share is
-// inf / nan (the test of check_finite_kernel).  A product of two fp32 values is exact in double, so fusing it into the sum or
+// inf / nan (GradScaler's found_inf).  A product of two fp32 values is exact in double, so fusing it into the sum or
 // not gives the same bits; every partial sum has a fixed order (thread: head element, its vectors in stride order, tail
 // element; then block_sum_256_d).  Double: 300 gradients of 1e18 overflow an fp32 sum, and a double sum of non-negative terms
 // is ~1e-13 relative from exact in ANY order, far below half an fp32 ulp of the norm.  One f64 FMA per element beside a load
@@ -1400,8 +1336,11 @@ int launch_grad_stats(sisic_ctx* ctx, const float* g, size_t n, float inv_scale,
     return SISIC_OK;
 }
 
-// adam_kernel's update on the clipped gradient -- the same operations in the same order, gi = (g * inv_scale) * clip_coef the
-// only change -- and, with EMA, diffusers' EMAModel.step on the weight just written:
+// torch.optim.Adam (single-tensor form, no weight decay, no amsgrad), in its operation order, contraction off:
+//   m = lerp(m, g, 1 - b1);  v = v * b2 + ((1 - b2) g) g;  denom = sqrt(v) / sqrt(bc2) + eps;  p = p - (lr / bc1) * m / denom
+// addcmul_(g, g, value = 1 - b2) forms (value * g) * g: g * g first would overflow for |g| > 1.85e19 where torch's v stays finite.
+// g is first multiplied by inv_scale (GradScaler.unscale_) and then by the clip coefficient: gi = (g * inv_scale) * clip_coef.
+// With EMA, diffusers' EMAModel.step on the weight just written:
 //   s_param.sub_(one_minus_decay * (s_param - param))      ema = ema - omd * (ema - p_new)      (three fp32 operations)
 struct AdamEmaConsts {
     float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, inv_scale, one_minus_decay;
@@ -1465,7 +1404,8 @@ int launch_adam_ema(sisic_ctx* ctx, float* p, const float* g, float* m, float* v
     SISIC_REQUIRE(!ema || (ema_decay >= 0.0 && ema_decay <= 1.0), "adam_ema: ema_decay %g is outside [0, 1]", ema_decay);
     SISIC_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                     reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(ema)) & 3) == 0, "adam_ema: a vector is not aligned to a float");
-    // the scalars as launch_adam forms them; 1 - decay in double, rounded to fp32 once (EMAModel.step forms it as a Python float)
+    // the scalars as torch forms them: Python doubles (1 - beta, lr / bias_correction1, sqrt(bias_correction2), 1 - decay) rounded
+    // to fp32 once, when they meet the fp32 tensors
     const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
     const AdamEmaConsts c{(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps,
                           inv_scale, (float)(1.0 - ema_decay)};
@@ -1507,6 +1447,26 @@ int launch_ema(sisic_ctx* ctx, float* ema, const float* p, size_t n, double ema_
     hipLaunchKernelGGL(ema_kernel, dim3(vec_grid(ctx, vs, n)), dim3(256), 0, s, ema, p, vs, n, (float)(1.0 - ema_decay));
     SISIC_HIP(hipGetLastError());
     return SISIC_OK;
+}
+
+// The one optimizer update (train.h).  The statistics pass and its read-back run only when asked for; without them the update
+// reads no record (coefficient 1) and nothing waits for the stream.
+int adam_step(sisic_ctx* ctx, const AdamStepArgs& a, AdamStepResult* out, hipStream_t s) {
+    SISIC_REQUIRE(out && a.step && (!a.want_stats || (a.stats && a.scratch)), "adam_step: bad arguments");
+    GradStats host{};
+    if (a.want_stats) {
+        SISIC_TRY(launch_grad_stats(ctx, a.g, a.n, a.inv_scale, a.max_norm, a.stats, a.scratch, s));
+        SISIC_HIP(hipMemcpyAsync(&host, a.stats, sizeof(GradStats), hipMemcpyDeviceToHost, s));
+        SISIC_HIP(hipStreamSynchronize(s));
+    }
+    out->norm = host.total_norm;
+    out->found_inf = host.found_inf;
+    out->skipped = a.skip_on_inf && host.found_inf != 0;
+    if (out->skipped)                // EMAModel.step runs after scaler.step either way: the shadow moves towards unchanged weights
+        return a.ema ? launch_ema(ctx, a.ema, a.p, a.n, a.ema_decay, s) : SISIC_OK;
+    *a.step += 1;                    // (feeds the bias corrections: it does not advance on a skipped step)
+    return launch_adam_ema(ctx, a.p, a.g, a.m, a.v, a.ema, a.n, a.lr, a.beta1, a.beta2, a.eps, *a.step, a.inv_scale,
+                           a.want_stats ? a.stats : nullptr, a.ema_decay, s);
 }
 
 // a[i] <-> b[i]: the EMA weights into the live arena and back

@@ -99,6 +99,10 @@ struct TapeOp {
 
 // Everything a training run keeps between calls (allocated by sisic_unet_train_begin).
 struct TrainState {
+    TrainState() = default;
+    TrainState(const TrainState&) = delete;
+    TrainState& operator=(const TrainState&) = delete;
+    ~TrainState();                    // frees every device buffer below (train.cpp); the tape's pool blocks belong to the handle
     float* grad = nullptr;            // gradient arena, same layout as sisic_unet::raw
     float* adam_m = nullptr;
     float* adam_v = nullptr;
@@ -134,10 +138,9 @@ struct TrainState {
     float* small = nullptr;           // per-(sample, channel) sums and similar
     size_t small_cap = 0;
     float* loss_dev = nullptr;        // [2]: loss, scratch
-    int* flag_dev = nullptr;          // non-finite gradient flag
     float* mse_part = nullptr;
-    // clipping and EMA (the *_ext entry points; nothing here exists until one of them or sisic_unet_ema_begin is called)
-    void* stats_dev = nullptr;        // GradStats record, then grad_stats' block partials
+    void* stats_dev = nullptr;        // GradStats record, then grad_stats' block partials (at byte 16)
+    // the EMA (nothing here exists until sisic_unet_ema_begin is called)
     float* ema = nullptr;             // EMA of the weights, same layout as sisic_unet::raw
     bool ema_swapped = false;         // sisic_unet_ema_swap: `raw` holds the averaged weights, `ema` the trained ones
     // every re-layout of every weight as three batched launches (repack.hip); rebuilt when the derived buffers move

@@ -78,18 +78,9 @@ class HipLoss:
         self._mse(1.0, self._loss.data_ptr(), None)
 
     def _mse(self, grad_scale: float, loss_ptr, dpred_ptr) -> None:
-        lib, model = _lib.load(), self.model
-        if self.weights is None:
-            _clear_loss_weights(model)
-            check(lib.sisic_mse_loss(model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(), grad_scale,
-                                     loss_ptr, dpred_ptr, _stream(self.pred.device)))
-            return
-        _set_loss_weights(model, self.weights)
-        try:
-            check(lib.sisic_mse_loss(model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(), grad_scale,
-                                     loss_ptr, dpred_ptr, _stream(self.pred.device)))
-        finally:
-            _clear_loss_weights(model)
+        with _loss_weights(self.model, self.weights):
+            check(_lib.load().sisic_mse_loss(self.model.handle, self.pred.data_ptr(), self.target.data_ptr(), self.pred.numel(),
+                                             grad_scale, loss_ptr, dpred_ptr, _stream(self.pred.device)))
 
     def item(self) -> float:
         return float(self._loss.item())
@@ -108,17 +99,27 @@ class HipLoss:
         check(lib.sisic_unet_backward(self.model.handle, dpred.data_ptr(), _stream(self.pred.device)))
 
 
-def _set_loss_weights(model: HipUNet2DModel, weights: torch.Tensor) -> None:
-    """sisic_unet_set_loss_weights: host fp32 [B], kept by the handle until cleared"""
-    check(_lib.load().sisic_unet_set_loss_weights(model.handle, C.cast(weights.data_ptr(), _lib.c_float_p), weights.numel()))
-    model._loss_weights_set = True
-
-
 def _clear_loss_weights(model: HipUNet2DModel) -> None:
     """clear the handle's loss weights if this module set any (a model that never had weights makes no call)"""
     if getattr(model, "_loss_weights_set", False):
         check(_lib.load().sisic_unet_set_loss_weights(model.handle, None, 0))
         model._loss_weights_set = False
+
+
+@contextlib.contextmanager
+def _loss_weights(model: HipUNet2DModel, weights: Optional[torch.Tensor]):
+    """The handle's loss weights for the library calls inside the block: ``weights`` (host fp32 [B]; sisic_unet_set_loss_weights
+    keeps them until cleared) or, with None, none -- a leftover is cleared first.  Cleared on the way out, also after an exception."""
+    _clear_loss_weights(model)
+    if weights is None:
+        yield
+        return
+    check(_lib.load().sisic_unet_set_loss_weights(model.handle, C.cast(weights.data_ptr(), _lib.c_float_p), weights.numel()))
+    model._loss_weights_set = True
+    try:
+        yield
+    finally:
+        _clear_loss_weights(model)
 
 
 def mse_loss(noise_pred: torch.Tensor, noise: torch.Tensor) -> HipLoss:
@@ -313,7 +314,8 @@ class HipAdam:
 
     ``max_grad_norm``: ``clip_grad_norm_(model.parameters(), max_grad_norm)`` in front of every step; the norm of the last
     step (unscaled, before clipping: what ``clip_grad_norm_`` returns) is ``optimizer.grad_norm``.  ``ema``: a HipEMA whose
-    update rides in the step.  With neither, ``step()`` is the call it always was."""
+    update rides in the step.  With neither, ``step()`` calls the plain entry point: the same update pass, and the statistics
+    pass in front of it only when ``check_inf`` asks."""
 
     def __init__(self, model_or_params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False, max_grad_norm: Optional[float] = None, ema: Optional[HipEMA] = None):
@@ -336,7 +338,7 @@ class HipAdam:
         check(_lib.load().sisic_unet_zero_grad(self.model.handle, _stream(self.model.device)))
 
     def _extension(self) -> Optional[_lib.OptimExt]:
-        """the options of the *_ext entry points, or None when nothing asks for them (the old entry points are called)"""
+        """the options of the *_ext entry points, or None when nothing asks for them (the plain entry points are called)"""
         if self.max_grad_norm is None and self.ema is None:
             return None
         ext = _lib.OptimExt()
@@ -353,18 +355,15 @@ class HipAdam:
 
     def step(self, inv_scale: float = 1.0, check_inf: bool = False) -> bool:
         """One Adam update; returns False when it was skipped because a gradient was inf/nan (GradScaler semantics)."""
-        found = C.c_int(0)
+        found, norm = C.c_int(0), C.c_float(0.0)
         ext = self._extension()
-        if ext is None:
-            check(_lib.load().sisic_unet_optimizer_step(self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                        float(inv_scale), C.byref(found) if check_inf else None,
-                                                        _stream(self.model.device)))
-        else:
-            norm = C.c_float(0.0)
-            check(_lib.load().sisic_unet_optimizer_step_ext(self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                            float(inv_scale), C.byref(ext),
-                                                            C.byref(found) if check_inf else None, C.byref(norm),
-                                                            _stream(self.model.device)))
+        args = [self.model.handle, self.lr, self.betas[0], self.betas[1], self.eps, float(inv_scale)]
+        args += [C.byref(ext)] if ext is not None else []
+        args += [C.byref(found) if check_inf else None]
+        args += [C.byref(norm)] if ext is not None else []
+        fn = "sisic_unet_optimizer_step" if ext is None else "sisic_unet_optimizer_step_ext"
+        check(getattr(_lib.load(), fn)(*args, _stream(self.model.device)))
+        if ext is not None:
             self._extension_done(ext, norm.value)
         self.model._params_stale = True
         return found.value == 0
@@ -460,14 +459,9 @@ def train_step_fused(model: HipUNet2DModel, scheduler: HipDDPMScheduler, images:
     Min-SNR-gamma weights of this batch's timesteps (``min_snr_weights``), set on the handle for this call and cleared after."""
     labels = model._labels_host(class_labels, images.shape[0])
     model._ensure_training()
-    if snr_gamma is None:
-        _clear_loss_weights(model)
+    weights = None if snr_gamma is None else min_snr_weights(scheduler, timesteps, snr_gamma, model.prediction_type).contiguous()
+    with _loss_weights(model, weights):
         return _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels)
-    _set_loss_weights(model, min_snr_weights(scheduler, timesteps, snr_gamma, model.prediction_type).contiguous())
-    try:
-        return _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels)
-    finally:
-        _clear_loss_weights(model)
 
 
 def _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, scaler, labels):
@@ -476,34 +470,23 @@ def _train_step_fused(model, scheduler, images, noise, timesteps, optimizer, sca
     B, _, H, W = x0.shape
     t = torch.as_tensor(timesteps).detach().to("cpu").to(torch.int64).reshape(-1).contiguous()
     a, c = scheduler.add_noise_coefficients(t)
-    loss, found = C.c_float(0.0), C.c_int(0)
+    loss, found, norm = C.c_float(0.0), C.c_int(0), C.c_float(0.0)
     scale = scaler.get_scale() if scaler is not None else 1.0
     found_ref = C.byref(found) if scaler is not None and scaler.enabled else None
     ext = optimizer._extension()
-    if labels is not None:
-        norm = C.c_float(0.0)
-        check(_lib.load().sisic_unet_train_step_cond(model.handle, x0.data_ptr(), nz.data_ptr(),
-                                                     C.cast(t.data_ptr(), _lib.c_int64_p),
-                                                     C.cast(labels.data_ptr(), _lib.c_int64_p),
-                                                     C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p),
-                                                     B, H, W, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
-                                                     optimizer.eps, float(scale), C.byref(ext) if ext is not None else None,
-                                                     C.byref(loss), found_ref, C.byref(norm), _stream(model.device)))
-        if ext is not None:
-            optimizer._extension_done(ext, norm.value)
-    elif ext is None:
-        check(_lib.load().sisic_unet_train_step(model.handle, x0.data_ptr(), nz.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
-                                                C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p), B, H, W,
-                                                optimizer.lr, optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
-                                                C.byref(loss), found_ref, _stream(model.device)))
-    else:
-        norm = C.c_float(0.0)
-        check(_lib.load().sisic_unet_train_step_ext(model.handle, x0.data_ptr(), nz.data_ptr(),
-                                                    C.cast(t.data_ptr(), _lib.c_int64_p), C.cast(a.data_ptr(), _lib.c_float_p),
-                                                    C.cast(c.data_ptr(), _lib.c_float_p), B, H, W, optimizer.lr,
-                                                    optimizer.betas[0], optimizer.betas[1], optimizer.eps, float(scale),
-                                                    C.byref(ext), C.byref(loss), found_ref, C.byref(norm),
-                                                    _stream(model.device)))
+    # one argument list for the three entry points: labels go in behind the timesteps (sisic_unet_train_step_cond), the options
+    # and the norm where the chosen symbol takes them (_cond takes both always, ext may be NULL; _ext when there are options)
+    cond, extended = labels is not None, labels is not None or ext is not None
+    args = [model.handle, x0.data_ptr(), nz.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p)]
+    args += [C.cast(labels.data_ptr(), _lib.c_int64_p)] if cond else []
+    args += [C.cast(a.data_ptr(), _lib.c_float_p), C.cast(c.data_ptr(), _lib.c_float_p), B, H, W, optimizer.lr, optimizer.betas[0],
+             optimizer.betas[1], optimizer.eps, float(scale)]
+    args += [C.byref(ext) if ext is not None else None] if extended else []
+    args += [C.byref(loss), found_ref]
+    args += [C.byref(norm)] if extended else []
+    fn = "sisic_unet_train_step_cond" if cond else "sisic_unet_train_step_ext" if ext is not None else "sisic_unet_train_step"
+    check(getattr(_lib.load(), fn)(*args, _stream(model.device)))
+    if ext is not None:
         optimizer._extension_done(ext, norm.value)
     model._params_stale = True
     if scaler is not None:

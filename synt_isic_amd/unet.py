@@ -430,12 +430,10 @@ class HipUNet2DModel:
                                "create the optimizer first, or call model.eval() for an undropped prediction")
         if self.training and self._train_begun:
             # training mode with an optimizer: the same kernels, every activation kept for loss.backward()
-            if labels is not None:
-                check(_lib.load().sisic_unet_train_forward_cond(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p), lab,
-                                                                out.data_ptr(), B, H, W, stream))
-            else:
-                check(_lib.load().sisic_unet_train_forward(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p),
-                                                           out.data_ptr(), B, H, W, stream))
+            fn = "sisic_unet_train_forward" if labels is None else "sisic_unet_train_forward_cond"
+            labs = () if labels is None else (lab,)           # the one argument the conditional entry point takes more
+            check(getattr(_lib.load(), fn)(h, x.data_ptr(), C.cast(t.data_ptr(), _lib.c_int64_p), *labs, out.data_ptr(), B, H, W,
+                                           stream))
             out._sisic_model = self
             # the tape refers to the input by address (conv_in's weight gradient reads it in the backward pass): keep the
             # tensor alive until the next forward, as autograd's graph would

@@ -3,6 +3,8 @@ test_optim_ext_cpu.py and test_gpu_optim_ext.py, as ddim_ref / dpmpp_ref are by 
 
     get_decay            diffusers.training_utils.EMAModel.get_decay
     ema_update           EMAModel.step on one tensor: s.sub_(one_minus_decay * (s - p)), fp32
+    adam_update          the library's Adam update on one vector (torch.optim.Adam's operation order on the unscaled, clipped
+                         gradient), fp32, one rounded operation at a time
     clip_stats           torch.nn.utils.clip_grad_norm_: the norm from a float64 sum of squares of the fp32 values g * inv_scale,
                          the coefficient in fp32 from that norm
     clip_coef_of         the coefficient alone, from a given fp32 norm
@@ -32,6 +34,34 @@ def ema_update(shadow: torch.Tensor, param: torch.Tensor, decay: float) -> torch
     one_minus_decay = 1 - decay
     shadow.sub_(one_minus_decay * (shadow - param))
     return shadow
+
+
+def adam_update(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, inv_scale: float, clip: float, *,
+                lr: float, beta1: float, beta2: float, eps: float):
+    """One step of the library's Adam update, in place on ``p``, ``m``, ``v`` (fp32, on the host): one rounded fp32 operation
+    per line in the kernel's order (adam_ema_elem), nothing fused.  The scalars are formed in double and rounded to fp32 once,
+    as launch_adam_ema forms them; fp32 divide and sqrt are correctly rounded on both sides."""
+    assert all(t.dtype == torch.float32 and t.device.type == "cpu" for t in (p, g, m, v))
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)          # noqa: E731
+    bc1, bc2 = 1.0 - beta1 ** step, 1.0 - beta2 ** step
+    omb1, b2, omb2 = f32(1.0 - beta1), f32(beta2), f32(1.0 - beta2)
+    step_size, bc2_sqrt, eps32 = f32(lr / bc1), f32(math.sqrt(bc2)), f32(eps)
+    gi = g * f32(inv_scale)
+    gi = gi * f32(clip)
+    d = gi - m
+    d = omb1 * d
+    m.add_(d)                       # m + omb1 * (gi - m)
+    t = omb2 * gi
+    t = t * gi
+    v.mul_(b2)
+    v.add_(t)                       # v * b2 + (omb2 * gi) * gi
+    denom = torch.from_numpy(np.sqrt(v.numpy()))      # numpy's fp32 sqrt is the correctly rounded one; torch.sqrt on the CPU is not
+    denom = denom / bc2_sqrt
+    denom = denom + eps32
+    u = m / denom
+    u = step_size * u
+    p.sub_(u)                       # p - step_size * (m / denom)
+    return p, m, v
 
 
 def clip_coef_of(total_norm: np.float32, max_norm: float) -> np.float32:

@@ -9,8 +9,8 @@ test_gpu_optimizer.py.
 The bars, and where they come from:
   * total_norm: 1 fp32 ulp from float32(sqrt(float64 sum of squares)).  A double sum of non-negative terms in any order is
     ~1e-13 relative from exact, far inside half an fp32 ulp (6e-8) except at a rounding boundary: hence 1 ulp, not 0.
-  * clip_coef, the fused update against the parent kernel, the EMA: bit for bit.  Both sides perform the same fp32 operations
-    in the same order on the same inputs.
+  * clip_coef, the fused update against its torch fp32 restatement (optim_ext_ref.adam_update), the EMA: bit for bit.  Both
+    sides perform the same fp32 operations in the same order on the same inputs.
   * parameters under active clipping: test_gpu_optimizer.py's yardstick, restated here -- at most ADAM_BAR times as far from a
     float64 torch.optim.Adam on the same clipped fp32 gradients as torch's own fp32 Adam is.
 """
@@ -29,7 +29,7 @@ from poison import guard_bands, poison_allocations, unwritten  # noqa: F401  (au
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-ADAM_BAR = 2.0               # the project's bar for adam_kernel's operation order (test_gpu_optimizer.py)
+ADAM_BAR = 2.0               # the project's bar for the Adam update's operation order (test_gpu_optimizer.py)
 ADAM = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8)
 BIG = 5_000_003
 CASES = [(1, 0), (3, 0), (255, 0), (1025, 0), (BIG, 0), (1025, 1)]
@@ -149,12 +149,25 @@ def _state(n, offset, seed):
     return [_dev(t, offset) for t in (p0, torch.zeros(n), torch.zeros(n))]
 
 
+def _host_state(n, seed):
+    """_state's values on the host, for ref.adam_update"""
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randn(n, generator=gen) * 0.05, torch.zeros(n), torch.zeros(n)
+
+
+def _same_bits(dev_tensors, host_tensors):
+    return all(torch.equal(d.cpu(), h) for d, h in zip(dev_tensors, host_tensors))
+
+
 @pytest.mark.parametrize("n,offset", CASES, ids=CASE_IDS)
 def test_fused_update_equals_the_parent_kernel_on_the_clipped_gradient(n, offset):
-    """sisic_adam_ema reading the coefficient c from the record, against adam_kernel (the null-record, null-EMA route) fed
-    g' = (g * 1) * c formed in torch fp32: p, m and v bit for bit over three steps."""
+    """sisic_adam_ema reading the coefficient c from the record, and the null-record, null-EMA route fed g' = (g * 1) * c formed
+    in torch fp32, against the torch fp32 restatement of the update (ref.adam_update, one rounded operation per line -- the
+    anchor that the deleted scalar adam_kernel was; that kernel gave the restatement's bits): p, m and v bit for bit over
+    three steps."""
     pa, ma, va = _state(n, offset, 21)
     pb, mb, vb = _state(n, offset, 21)
+    want = _host_state(n, 21)
     clipped = 0
     for step in (1, 2, 3):
         g = _grad(n, 30 + step)
@@ -166,7 +179,9 @@ def test_fused_update_equals_the_parent_kernel_on_the_clipped_gradient(n, offset
         assert g2.dtype == torch.float32
         _adam_ema(pb, g2, mb, vb, None, step)
         torch.cuda.synchronize()
+        ref.adam_update(*want[:1], g, *want[1:], step, 1.0, float(coef), **ADAM)
         assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb), f"step {step}"
+        assert _same_bits((pa, ma, va), want), f"step {step}: not the restatement's bits"
         assert bool(torch.isfinite(pa).all())
     assert n < 255 or clipped == 3
 
@@ -175,20 +190,24 @@ def test_fused_update_equals_the_parent_kernel_on_the_clipped_gradient(n, offset
 @pytest.mark.parametrize("n,offset", CASES, ids=CASE_IDS)
 def test_fused_ema_equals_the_published_update(n, offset, decay):
     """ema = ema - (1 - decay) * (ema - p_new) on the p read back after each of three steps; p, m, v beside it equal the
-    parent kernel's (coefficient 1: no record)."""
+    no-EMA route's and the torch fp32 restatement's (ref.adam_update, coefficient 1: no record) bit for bit."""
     from synt_isic_amd import ops
     pa, ma, va = _state(n, offset, 22)
     pb, mb, vb = _state(n, offset, 22)
+    host = _host_state(n, 22)
     gen = torch.Generator().manual_seed(23)
     ema = _dev(pa.cpu() + 0.01 * torch.randn(n, generator=gen), offset)
     want = ema.clone()
     bystander = ops.empty(n, dtype=torch.float32, device=DEV)              # a would-be EMA buffer that no call is given
     for step in (1, 2, 3):
-        gd = _dev(_grad(n, 40 + step), offset)
+        g = _grad(n, 40 + step)
+        gd = _dev(g, offset)
         _adam_ema(pa, gd, ma, va, ema, step, decay=decay)
         _adam_ema(pb, gd, mb, vb, None, step)
         torch.cuda.synchronize()
+        ref.adam_update(*host[:1], g, *host[1:], step, 1.0, 1.0, **ADAM)
         assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb), f"step {step}"
+        assert _same_bits((pa, ma, va), host), f"step {step}: not the restatement's bits"
         ref.ema_update(want, pa.clone(), decay)
         assert torch.equal(ema, want), f"step {step}: {(ema != want).sum().item()} of {n} EMA elements differ"
     if decay == 0.0:                                                       # e - 1 * (e - p): p up to the rounding of e - p

@@ -298,7 +298,7 @@ def _library_order(model):
 
 def _poison_position(model, arena, where):
     """(tensor name, element index): element 0 of the library's first tensor, the last element of its last, or an odd index in
-    a tensor in the middle of the arena, far past the 2048 x 256 elements of check_finite_kernel's first grid-stride trip."""
+    a tensor in the middle of the arena, far past the 2048 x 256 x 4 elements of grad_stats' first grid-stride trip."""
     order = _library_order(model)
     assert sorted(order) == sorted(arena.names)
     numel = lambda n: math.prod(arena.shapes[n])
@@ -369,6 +369,46 @@ def test_one_non_finite_gradient_element_skips_the_step(synthetic_sd, arena, gra
     model.set_grads(arena.named(grad_seq[3]))
     assert opt.step() is True
     _compare(model, arena, default_run["snap"][4], f"(c) {where} step 4 without the check")
+
+
+def test_the_checked_and_the_unchecked_plain_step_are_one_update(synthetic_sd, arena, grad_seq, shared_model):
+    """The plain step with check_inf (a statistics pass, its record read by the update: coefficient exactly 1) and without (one
+    launch, no record) on the same gradients under inv_scale = fp32(1/3): bit-equal weights, moments and step count after two
+    steps.  Then ONE planted NaN: the checked step moves nothing; the unchecked one is taken, and the NaN is in the planted
+    element's weight and moments and nowhere else."""
+    from synt_isic_amd.train import HipAdam
+    inv_scale = float(torch.tensor(1.0 / 3.0, dtype=torch.float32))
+    states = {}
+    for check_inf in (True, False):
+        model = _reset(shared_model, synthetic_sd)
+        opt = HipAdam(model)
+        for g in grad_seq[:2]:
+            model.set_grads(arena.named(g))
+            assert opt.step(inv_scale=inv_scale, check_inf=check_inf) is True
+        states[check_inf] = (model.state_dict(), model.optimizer_state())
+    for sd, st in states.values():
+        assert st["step"] == 2 and not _equal(sd, synthetic_sd)
+    assert _equal(states[True][0], states[False][0])
+    assert _equal(states[True][1]["exp_avg"], states[False][1]["exp_avg"])
+    assert _equal(states[True][1]["exp_avg_sq"], states[False][1]["exp_avg_sq"])
+    # the model stands after the unchecked run's second step
+    name, index = _poison_position(model, arena, "middle")
+    bad = arena.named(grad_seq[2])[name].clone()
+    bad.reshape(-1)[index] = math.nan
+    model.set_grads(arena.named(grad_seq[2]))
+    model.set_grads({name: bad})
+    assert opt.step(inv_scale=inv_scale, check_inf=True) is False
+    sd, st = model.state_dict(), model.optimizer_state()
+    assert st["step"] == 2 and _equal(sd, states[False][0])
+    assert _equal(st["exp_avg"], states[False][1]["exp_avg"]) and _equal(st["exp_avg_sq"], states[False][1]["exp_avg_sq"])
+    assert opt.step(inv_scale=inv_scale, check_inf=False) is True
+    sd, st = model.state_dict(), model.optimizer_state()
+    assert st["step"] == 3
+    for what in (sd, st["exp_avg"], st["exp_avg_sq"]):
+        nan = torch.isnan(arena.flat(what))
+        assert int(nan.sum()) == 1 and bool(torch.isnan(what[name].reshape(-1)[index]))
+        assert bool(torch.isfinite(arena.flat(what)[~nan]).all())
+    assert any(not torch.equal(sd[k].cpu(), states[False][0][k].cpu()) for k in sd if k != name)
 
 
 def test_grad_scaler_bookkeeping_matches_torch_amp_update_scale(synthetic_sd, arena, grad_seq, shared_model):

@@ -9,6 +9,7 @@ wrapper's marshalling last): two trees of the package that print the same lines 
     python tools/executor_digest.py --host-only          the step layer's host lines alone: needs no GPU (compare two trees on one
                                                          machine: the DDPM / DDIM tables are fp32 torch host arithmetic, CPU-dependent)
     python tools/executor_digest.py --step-layer         the step layer's lines alone
+    python tools/executor_digest.py --train              the training lines alone (train.* and clf.*), after the host lines
     python tools/executor_digest.py --step-layer-items   with any of the above: every item of the step layer on its own line (by
                                                          default one line per mirror case / wrapper: the sha256 of its items)
     python tools/executor_digest.py --step-layer-times   wall time per call of the wrappers and the mirrors' step
@@ -139,6 +140,97 @@ def train_items(sd) -> None:
     opt.step()
     emit("train.forward_after_step", sha(m(x, t).sample))
     emit("train.workspace_bytes", _lib.load().sisic_unet_workspace_bytes(m.handle))
+
+
+def _train_state(m, ema=None) -> str:
+    """weights | m | v after a step, the step count and (with an EMA) the shadow weights"""
+    st = m.optimizer_state()
+    line = f"{sha(*m.state_dict().values(), *st['exp_avg'].values(), *st['exp_avg_sq'].values())} step={st['step']}"
+    return line if ema is None else f"{line} ema={sha(*ema.shadow_params().values())}"
+
+
+def train_step_items(sd) -> None:
+    """One training step at batch 2, 32x32 (every level, both attention widths in use, the K-split weight gradient) from fresh
+    weights and moments, fused and spelled out, under every optimizer option, scaler, label and objective: loss, gradients and
+    weights | m | v each; a scaler-skipped step with the EMA on; sisic_mse_loss alone."""
+    import ctypes as C
+    from synt_isic_amd.train import HipEMA, HipGradScaler, diffusion_loss, train_step_fused
+    from synt_isic_amd.unet import HipUNet2DModel
+    sched = sch.HipDDPMScheduler(num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2")
+    x, noise, t = rand((2, 3, 32, 32), 21).clamp(-1, 1).to(DEV), rand((2, 3, 32, 32), 22).to(DEV), torch.tensor([37, 640])
+    options = {"plain": (None, False), "clip": (1e-3, False), "ema": (None, True), "both": (1e-3, True)}
+
+    def step(tag, m, weights, fused, option, scaled, labels=None, snr_gamma=None):
+        m.load_state_dict(weights)               # fresh moments, step 0
+        m.train()
+        max_norm, with_ema = options[option]
+        ema = HipEMA(m, decay=0.9999) if with_ema else None
+        opt = HipAdam(m, lr=1e-4, max_grad_norm=max_norm, ema=ema)
+        scaler = HipGradScaler() if scaled else None
+        if fused:
+            value, taken = train_step_fused(m, sched, x, noise, t, opt, scaler, class_labels=labels, snr_gamma=snr_gamma)
+        else:
+            pred = m(sched.add_noise(x, noise, t), t, class_labels=labels).sample
+            if snr_gamma is None and m.prediction_type == "epsilon":
+                loss = mse_loss(pred, noise)
+            else:
+                loss = diffusion_loss(pred, x, noise, t, sched, snr_gamma=snr_gamma)
+            opt.zero_grad()
+            if scaler is None:
+                loss.backward()
+                taken = opt.step()
+            else:
+                scaler.scale(loss).backward()
+                taken = scaler.step(opt)
+                scaler.update()
+            value = loss.item()
+        emit(f"train.{tag}.loss", f"{float(value).hex()} taken={taken} norm={opt.grad_norm}")
+        emit(f"train.{tag}.grads", sha(*m.grads().values()))
+        emit(f"train.{tag}.state", _train_state(m, ema))
+        return opt, ema
+
+    m = HipUNet2DModel()
+    m.load_state_dict(sd)
+    m = m.to(DEV)
+    for fused in (True, False):
+        form = "fused" if fused else "spelled"
+        for option in options:
+            for scaled in (False, True):
+                step(f"{form}.{option}.scaler{int(scaled)}", m, sd, fused, option, scaled)
+        for kind, gamma in (("v_prediction", 5.0), ("sample", None)):
+            m.set_prediction_type(kind)
+            step(f"{form}.{kind}.snr{gamma}", m, sd, fused, "plain", True, snr_gamma=gamma)
+        m.set_prediction_type("epsilon")
+    # a step the scaler skips, the EMA on: two clean steps first (the EMA then lags the weights), then one planted inf
+    opt, ema = step("skip.clean1", m, sd, True, "both", True)
+    scaler = HipGradScaler()
+    train_step_fused(m, sched, x, noise, t, opt, scaler)
+    emit("train.skip.before", _train_state(m, ema))
+    name, g = next(iter(m.grads().items()))
+    g.view(-1)[g.numel() // 2] = float("inf")
+    m.set_grads({name: g})
+    emit("train.skip.taken", scaler.step(opt))
+    emit("train.skip.after", _train_state(m, ema))
+    # sisic_mse_loss alone, 210 elements (a partial block): no weights, and weights of ones
+    lib = _lib.load()
+    pred, target = rand((2, 3, 5, 7), 23).to(DEV), rand((2, 3, 5, 7), 24).to(DEV)
+    ones = torch.ones(2)
+    for tag, w in (("plain", None), ("ones", ones)):
+        loss, dpred = ops.empty(1, dtype=torch.float32, device=DEV), ops.empty_like(pred)
+        _lib.check(lib.sisic_unet_set_loss_weights(m.handle, C.cast(w.data_ptr(), _lib.c_float_p) if w is not None else None,
+                                                   2 if w is not None else 0))
+        _lib.check(lib.sisic_mse_loss(m.handle, pred.data_ptr(), target.data_ptr(), pred.numel(), 3.0, loss.data_ptr(),
+                                      dpred.data_ptr(), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)))
+        _lib.check(lib.sisic_unet_set_loss_weights(m.handle, None, 0))
+        emit(f"train.mse_loss.{tag}", f"loss={sha(loss)} dpred={sha(dpred)}")
+    # the class-conditional model, with the extension and without
+    csd = synthetic_unet_state_dict(num_class_embeds=3)
+    cm = HipUNet2DModel(num_class_embeds=3)
+    cm.load_state_dict(csd)
+    cm = cm.to(DEV)
+    for fused in (True, False):
+        for option in ("plain", "both"):
+            step(f"cond.{'fused' if fused else 'spelled'}.{option}", cm, csd, fused, option, True, labels=torch.tensor([2, 0]))
 
 
 def classifier_items() -> None:
@@ -382,11 +474,16 @@ def main() -> None:
     if "--step-layer" in sys.argv:
         return step_layer_gpu()
     print("library:", _lib.lib_path(), file=sys.stderr)
+    if "--train" in sys.argv:
+        train_items(sd)
+        train_step_items(sd)
+        return classifier_items()
     unet_items(sd)
     sys.stdout.flush()
     subprocess.run([sys.executable, os.path.abspath(__file__), "--rider0-child"], check=True, timeout=300,
                    env=dict(os.environ, SISIC_GN_RIDER="0"))
     train_items(sd)
+    train_step_items(sd)
     classifier_items()
     step_layer_gpu()
 
