@@ -11,12 +11,13 @@ from __future__ import annotations
 
 import ctypes as C
 from collections import OrderedDict
-from typing import Dict, Iterator, Optional
+from typing import Dict, Iterator
 
 import torch
 
 from . import _lib, ops
 from ._lib import check
+from ._module import HipModule
 from .arch import resnet18_buffer_names, resnet18_param_spec, resnet18_trainable_names
 
 NUM_CLASSES = 7                                     # xai/XAI.py:196 ISIC classes
@@ -24,7 +25,9 @@ CLASS_NAMES = ("MEL", "NV", "BCC", "AKIEC", "BKL", "DF", "VASC")
 CLASSIFIER_IMAGE_SIZE = 224
 
 
-class HipMelanomaClassifier:
+class HipMelanomaClassifier(HipModule):
+    _PREFIX, _NAME, _NO_CPU_PATH, _KEYS = "sisic_resnet", "HipMelanomaClassifier", "no CPU path", "classifier keys"
+
     def __init__(self, num_classes: int = NUM_CLASSES, architecture: str = "resnet18", pretrained: bool = False):
         if architecture not in ("resnet18", "auto"):
             raise NotImplementedError("only the built-in resnet18 architecture of the reference is implemented")
@@ -33,21 +36,12 @@ class HipMelanomaClassifier:
                                       "state dict to load_state_dict instead")
         self.num_classes = num_classes
         self.architecture = "resnet18"
-        self._spec = resnet18_param_spec(num_classes)
-        self._params: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-        self._device = torch.device("cpu")
-        self._handle: Optional[C.c_void_p] = None
-        self._uploaded = False
-        self._params_stale = False      # an optimizer step moved the library's weights: _params follows on the next read
+        super().__init__(resnet18_param_spec(num_classes))
         self._batches_tracked: "OrderedDict[str, torch.Tensor]" = OrderedDict()    # num_batches_tracked of the loaded dict, if any
         self._trainer = None            # the train.HipClassifierAdam that holds the library's training arenas, if any
         self.training = True
 
     # ---- module surface -------------------------------------------------------------------------
-    @property
-    def device(self) -> torch.device:
-        return self._device
-
     def eval(self):
         self.training = False
         return self
@@ -87,34 +81,10 @@ class HipMelanomaClassifier:
         """the BatchNorm mode of the optimizer that holds the training arenas ("frozen" without one)"""
         return self._trainer.batchnorm if self._trainer is not None else "frozen"
 
-    def _tensor_index(self) -> Dict[str, int]:
-        lib, h = _lib.load(), self.handle
-        return {lib.sisic_resnet_tensor_name(h, i).decode(): i for i in range(lib.sisic_resnet_num_tensors(h))}
-
-    def _sync_params(self) -> None:
-        if not self._params_stale:
-            return
-        self._params_stale = False                       # (before the reads: read_tensor goes through .handle only)
+    def _stale_names(self):
+        """what an optimizer step moves: the trainable tensors of the trainer's mode, and with batch statistics the buffers"""
         names = self.trainable_names(self._mode())
-        if self._mode() == "batch":
-            names = names + resnet18_buffer_names(self.num_classes)
-        for name in names:
-            self._params[name] = self.read_tensor(0, name).to(self._device)
-
-    def read_tensor(self, what: int, name: str) -> torch.Tensor:
-        """one tensor of the library's arenas on the CPU (sisic_resnet_read): what = 0 parameter, 1 gradient, 2 / 3 Adam m / v"""
-        out = torch.empty(self._spec[name], dtype=torch.float32)
-        check(_lib.load().sisic_resnet_read(self.handle, int(what), self._tensor_index()[name],
-                                            C.cast(out.data_ptr(), _lib.c_float_p), out.numel()))
-        return out
-
-    def write_tensor(self, what: int, name: str, value: torch.Tensor) -> None:
-        """the counterpart (sisic_resnet_write): gradients and moments only, parameters are set by load_state_dict"""
-        v = value.detach().to("cpu", torch.float32).contiguous()
-        if tuple(v.shape) != tuple(self._spec[name]):
-            raise ValueError(f"{name}: shape {tuple(v.shape)}, expected {tuple(self._spec[name])}")
-        check(_lib.load().sisic_resnet_write(self.handle, int(what), self._tensor_index()[name],
-                                             C.cast(v.data_ptr(), _lib.c_float_p), v.numel()))
+        return names + resnet18_buffer_names(self.num_classes) if self._mode() == "batch" else names
 
     def grads(self) -> "OrderedDict[str, torch.Tensor]":
         """the gradients of the last ``loss_backward`` (or ``set_grads``), CPU tensors under the state-dict names"""
@@ -189,76 +159,22 @@ class HipMelanomaClassifier:
             extra = [k for k in sd if k not in self._spec]
             if extra:
                 raise RuntimeError(f"unexpected keys in state_dict: {extra[:5]}")
-        self._params = new
         self._batches_tracked = tracked
-        self._uploaded = False
-        if self._device.type == "cuda":
-            self._upload()
+        self._set_params(new)
         return self
 
-    def to(self, device=None, *a, **k):
-        if device is None:
-            return self
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device == self._device:
-            return self
-        self._sync_params()
-        self._release()
-        self._params = OrderedDict((n, v.to(device)) for n, v in self._params.items())
-        self._device = device
-        if device.type == "cuda" and self._params:
-            self._upload()
-        return self
-
-    # ---- library handle -------------------------------------------------------------------------
-    def _upload(self) -> None:
-        lib = _lib.load()
-        if self._handle is None:
-            h = C.c_void_p()
-            check(lib.sisic_resnet_create(ops.context(self._device), self.num_classes, C.byref(h)))
-            self._handle = h
-            names = [lib.sisic_resnet_tensor_name(h, i).decode() for i in range(lib.sisic_resnet_num_tensors(h))]
-            if sorted(names) != sorted(self._spec):
-                raise RuntimeError("libsisic_hip.so and synt_isic_amd.arch disagree on the classifier keys")
-        host = [(n, v.detach().to("cpu", torch.float32).contiguous()) for n, v in self._params.items()]
-        n = len(host)
-        names = (C.c_char_p * n)(*[k.encode() for k, _ in host])
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in host])
-        numels = (C.c_int64 * n)(*[t.numel() for _, t in host])
-        check(lib.sisic_resnet_load(self._handle, n, names, ptrs, numels))       # (a reload ends training in the library)
-        self._uploaded = True
-        self._params_stale = False
-        self._drop_trainer()
+    # ---- library handle (the shell's hooks) -----------------------------------------------------
+    def _create_handle(self) -> None:
+        h = C.c_void_p()
+        check(_lib.load().sisic_resnet_create(ops.context(self._device), self.num_classes, C.byref(h)))
+        self._handle = h
 
     def _drop_trainer(self) -> None:
         if self._trainer is not None:
             self._trainer._active = False
             self._trainer = None
 
-    def _release(self) -> None:
-        self._drop_trainer()
-        if self._handle is not None:
-            _lib.load().sisic_resnet_destroy(self._handle)
-            self._handle = None
-            self._uploaded = False
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        if self._device.type != "cuda":
-            raise RuntimeError("HipMelanomaClassifier runs on MI355X only: call .to('cuda') first (no CPU path)")
-        if not self._params:
-            raise RuntimeError("HipMelanomaClassifier has no weights: call load_state_dict() first")
-        if not self._uploaded:
-            self._upload()
-        return self._handle
+    _after_upload = _before_release = _drop_trainer          # a reload ends training in the library, and so does a move
 
     # ---- weight randomisation (the sanity check of xai/XAI.py:2043-2098) ---------------------------
     RANDOMIZE_TAG0 = 16          # device-noise tag of tensor k: 16 + k (include/sisic.h)
@@ -283,9 +199,7 @@ class HipMelanomaClassifier:
     def randomized_state_dict(self, seed: int, trial: int, strength: float = 0.01) -> "OrderedDict[str, torch.Tensor]":
         """The state dict the device holds after ``randomize_weights(seed, trial, strength)``, built with ``ops.noise_fill``:
         loading it into another classifier gives the same filters (tests, the oracle)."""
-        lib = _lib.load()
-        h = self.handle
-        order = {lib.sisic_resnet_tensor_name(h, i).decode(): i for i in range(lib.sisic_resnet_num_tensors(h))}
+        order = self._tensor_index()
         out = OrderedDict()
         for name, value in self._params.items():
             if value.dim() > 1:

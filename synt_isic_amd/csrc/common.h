@@ -366,3 +366,5 @@ int launch_augment(sisic_ctx*, const uint8_t* dataset, int N, int H, int W, cons
                    int32_t* gray_mean_scratch, void* out, bool u8, hipStream_t s);
 
 }  // namespace sisic
+
+#include "tensor_dir.h"

@@ -94,9 +94,7 @@ struct ResnetTrain {
 struct sisic_resnet {
     sisic_ctx* ctx = nullptr;
     int num_classes = 0;
-    std::vector<std::string> names;
-    std::vector<int64_t> numels;
-    std::map<std::string, int> index;
+    TensorDir dir;                          // expected state dict
     std::vector<std::vector<float>> host;   // host copies (folding happens on the host)
     FoldedConv stem;
     std::vector<Block> blocks;
@@ -121,13 +119,6 @@ struct sisic_resnet {
     bool targets_used[TARGET_SLOTS] = {};
     bool loaded = false;
     ResnetTrain* train = nullptr;
-
-    int add(const std::string& n, int64_t numel) {
-        index[n] = (int)names.size();
-        names.push_back(n);
-        numels.push_back(numel);
-        return (int)names.size() - 1;
-    }
 };
 
 namespace {
@@ -167,14 +158,15 @@ int stage_targets(sisic_resnet* r, const int64_t* targets, int B, int* dst, hipS
 void add_conv_bn(sisic_resnet* r, FoldedConv& c, const std::string& conv, const std::string& bn, int cout, int cin, int k,
                  int stride) {
     c.cout = cout; c.cin = cin; c.k = k; c.stride = stride;
-    c.w_idx = r->add(conv + ".weight", (int64_t)cout * cin * k * k);
-    c.bn_w = r->add(bn + ".weight", cout);
-    c.bn_b = r->add(bn + ".bias", cout);
-    c.bn_m = r->add(bn + ".running_mean", cout);
-    c.bn_v = r->add(bn + ".running_var", cout);
+    c.w_idx = r->dir.add(conv + ".weight", (int64_t)cout * cin * k * k);
+    c.bn_w = r->dir.add(bn + ".weight", cout);
+    c.bn_b = r->dir.add(bn + ".bias", cout);
+    c.bn_m = r->dir.add(bn + ".running_mean", cout);
+    c.bn_v = r->dir.add(bn + ".running_var", cout);
 }
 
 void describe(sisic_resnet* r) {
+    r->dir.noun = "float tensors";              // (num_batches_tracked, an integer tensor of the state dict, never comes here)
     const std::string pre = "model.";           // XAI.py:389: self.model = models.resnet18(...)
     add_conv_bn(r, r->stem, pre + "conv1", pre + "bn1", 64, 3, 7, 2);
     const int widths[4] = {64, 128, 256, 512};
@@ -192,8 +184,8 @@ void describe(sisic_resnet* r) {
             in_ch = widths[l];
         }
     }
-    r->fc_w = r->add(pre + "fc.weight", (int64_t)r->num_classes * 512);
-    r->fc_b = r->add(pre + "fc.bias", r->num_classes);
+    r->fc_w = r->dir.add(pre + "fc.weight", (int64_t)r->num_classes * 512);
+    r->fc_b = r->dir.add(pre + "fc.bias", r->num_classes);
 }
 
 int dev_alloc(sisic_resnet* r, size_t floats, float** out) {
@@ -530,31 +522,18 @@ int64_t sisic_resnet_workspace_bytes(const sisic_resnet* r) {
     return r ? r->pool.bytes() : 0;
 }
 
-int sisic_resnet_num_tensors(const sisic_resnet* r) { return r ? (int)r->names.size() : 0; }
+int sisic_resnet_num_tensors(const sisic_resnet* r) { return r ? r->dir.size() : 0; }
 
-const char* sisic_resnet_tensor_name(const sisic_resnet* r, int i) {
-    if (!r || i < 0 || i >= (int)r->names.size()) return nullptr;
-    return r->names[i].c_str();
-}
+const char* sisic_resnet_tensor_name(const sisic_resnet* r, int i) { return r ? r->dir.name(i) : nullptr; }
 
 int sisic_resnet_load(sisic_resnet* r, int n, const char* const* names, const float* const* host_ptrs,
                       const int64_t* numels) {
     SISIC_REQUIRE(r && names && host_ptrs && numels, "resnet_load: null argument");
-    SISIC_REQUIRE(n == (int)r->names.size(), "resnet_load: state dict has %d float tensors, expected %d", n, (int)r->names.size());
+    std::vector<int> slot;                    // a refused state dict leaves the handle as it was: nothing below has run
+    SISIC_TRY(r->dir.match("resnet_load", n, names, host_ptrs, numels, &slot));
     SISIC_HIP(hipSetDevice(r->ctx->device));
-    r->host.assign(r->names.size(), {});
-    std::vector<char> seen(r->names.size(), 0);
-    for (int i = 0; i < n; ++i) {
-        SISIC_REQUIRE(names[i] && host_ptrs[i], "resnet_load: entry %d is null", i);
-        auto it = r->index.find(names[i]);
-        SISIC_REQUIRE(it != r->index.end(), "resnet_load: unexpected key '%s'", names[i]);
-        const int idx = it->second;
-        SISIC_REQUIRE(!seen[idx], "resnet_load: duplicate key '%s'", names[i]);
-        SISIC_REQUIRE(numels[i] == r->numels[idx], "resnet_load: '%s' has %lld elements, expected %lld", names[i],
-                      (long long)numels[i], (long long)r->numels[idx]);
-        seen[idx] = 1;
-        r->host[idx].assign(host_ptrs[i], host_ptrs[i] + numels[i]);
-    }
+    r->host.assign(r->dir.size(), {});
+    for (int i = 0; i < n; ++i) r->host[slot[i]].assign(host_ptrs[i], host_ptrs[i] + numels[i]);
     (void)hipDeviceSynchronize();
     train_free(r);                            // a reload ends training: the arenas described the previous weights
     r->ws_gen = next_workspace_generation();  // every weight buffer moves
@@ -798,8 +777,8 @@ int refresh_inference_forms(sisic_resnet* r, hipStream_t s) {
     SISIC_TRY(fold_pack(r, r->stem, s));
     for (int p = 0; p < 2; ++p)
         SISIC_TRY(launch_pack_batch(r->ctx, static_cast<const PackJob*>(tr->repack_dev[p]), tr->repack_jobs[p], tr->repack_blocks[p], s));
-    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, param_of(tr, r->fc_w), (size_t)r->numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, param_of(tr, r->fc_b), (size_t)r->numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, param_of(tr, r->fc_w), (size_t)r->dir.numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, param_of(tr, r->fc_b), (size_t)r->dir.numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
     tr->stats_moved = false;
     return SISIC_OK;
 }
@@ -811,7 +790,7 @@ int train_begin_plain(sisic_resnet* r) {
     for_each_conv(r, [&](FoldedConv& c) {
         for (int idx : {c.bn_m, c.bn_v}) {
             tr->boff[idx] = (int64_t)tr->buf_floats;
-            tr->buf_floats += (size_t)round_up((int)r->numels[idx], 4);
+            tr->buf_floats += (size_t)round_up((int)r->dir.numels[idx], 4);
         }
         return SISIC_OK;
     });
@@ -822,7 +801,7 @@ int train_begin_plain(sisic_resnet* r) {
         SISIC_TRY(poison_fresh(p, tr->buf_floats * sizeof(float)));
         SISIC_HIP(hipMemset(p, 0, tr->buf_floats * sizeof(float)));
     }
-    for (int i = 0; i < (int)r->names.size(); ++i)
+    for (int i = 0; i < r->dir.size(); ++i)
         if (tr->boff[i] >= 0)
             SISIC_HIP(hipMemcpy(tr->buf + tr->boff[i], r->host[i].data(), r->host[i].size() * sizeof(float), hipMemcpyHostToDevice));
     auto alloc = [&](size_t floats, float** out) {
@@ -1041,20 +1020,20 @@ int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
     r->ws_gen = next_workspace_generation();
     tr->bn_mode = bn_mode;
     tr->momentum = momentum;
-    tr->off.assign(r->names.size(), -1);
-    tr->boff.assign(r->names.size(), -1);
+    tr->off.assign(r->dir.size(), -1);
+    tr->boff.assign(r->dir.size(), -1);
     auto place = [&](int idx) {
         tr->off[idx] = (int64_t)tr->floats;
-        tr->floats += (size_t)round_up((int)r->numels[idx], 4);
+        tr->floats += (size_t)round_up((int)r->dir.numels[idx], 4);
     };
-    std::vector<char> trainable(r->names.size(), 0);
+    std::vector<char> trainable(r->dir.size(), 0);
     for_each_conv(r, [&](FoldedConv& c) {
         trainable[c.w_idx] = 1;
         if (bn_mode == 1) trainable[c.bn_w] = trainable[c.bn_b] = 1;
         return SISIC_OK;
     });
     trainable[r->fc_w] = trainable[r->fc_b] = 1;
-    for (int i = 0; i < (int)r->names.size(); ++i)
+    for (int i = 0; i < r->dir.size(); ++i)
         if (trainable[i]) place(i);
     // the partial slabs: the most any layer asks for at any shape (its K-split is capped by the layer's tile count)
     tr->part_floats = stem_wgrad_scratch_floats();
@@ -1086,7 +1065,7 @@ int train_begin(sisic_resnet* r, int bn_mode, double momentum) {
         SISIC_HIP(hipMalloc(&tr->stats, sb));
         SISIC_TRY(poison_fresh(tr->stats, sb));
     }
-    for (int i = 0; i < (int)r->names.size(); ++i)
+    for (int i = 0; i < r->dir.size(); ++i)
         if (tr->off[i] >= 0)
             SISIC_HIP(hipMemcpy(tr->param + tr->off[i], r->host[i].data(), r->host[i].size() * sizeof(float), hipMemcpyHostToDevice));
     {
@@ -1161,7 +1140,7 @@ int sisic_resnet_train_end(sisic_resnet* r) {
     SISIC_HIP(hipSetDevice(r->ctx->device));
     if (tr->bn_mode == 1 && tr->stats_moved) SISIC_TRY(refresh_inference_forms(r, nullptr));
     SISIC_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < (int)r->names.size(); ++i) {
+    for (int i = 0; i < r->dir.size(); ++i) {
         if (tr->off[i] >= 0)
             SISIC_HIP(hipMemcpy(r->host[i].data(), tr->param + tr->off[i], r->host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
         if (tr->boff[i] >= 0)
@@ -1183,50 +1162,40 @@ int sisic_resnet_zero_grad(sisic_resnet* r) {
     return SISIC_OK;
 }
 
-int sisic_resnet_read(sisic_resnet* r, int what, int index, float* host_out, int64_t numel) {
-    SISIC_REQUIRE(r && host_out && index >= 0 && index < (int)r->names.size(), "resnet_read: bad arguments");
-    SISIC_REQUIRE(numel == r->numels[index], "resnet_read: '%s' has %lld elements", r->names[index].c_str(), (long long)r->numels[index]);
-    SISIC_REQUIRE(what >= 0 && what <= 3, "resnet_read: what = %d (0 parameter, 1 gradient, 2 Adam m, 3 Adam v)", what);
-    if (!r->loaded) {
+// sisic_resnet_read / _write: tensor `index` of arena `what` to the host, or (write) from it; synchronises unless the host has it
+static int resnet_transfer(sisic_resnet* r, const char* who, bool write, int what, int index, float* host, int64_t numel) {
+    SISIC_REQUIRE(r, "%s: bad arguments", who);
+    SISIC_TRY(r->dir.check_access(who, index, numel, host));
+    SISIC_REQUIRE(!write || what != 0, "%s: parameters are set by sisic_resnet_load (their folded and packed forms must follow); "
+                                       "what = 1 gradient, 2 Adam m, 3 Adam v", who);
+    SISIC_REQUIRE(what >= 0 && what <= 3, "%s: what = %d (%s1 gradient, 2 Adam m, 3 Adam v)", who, what, write ? "" : "0 parameter, ");
+    if (!write && !r->loaded) {
         set_error("resnet_read called before sisic_resnet_load");
         return SISIC_ESTATE;
     }
     ResnetTrain* tr = r->train;
+    float* dev = nullptr;
     if (what == 0 && tr && tr->boff[index] >= 0) {        // a running statistic of batch-statistics training: its current value
-        SISIC_HIP(hipSetDevice(r->ctx->device));
-        SISIC_HIP(hipDeviceSynchronize());
-        SISIC_HIP(hipMemcpy(host_out, tr->buf + tr->boff[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+        dev = tr->buf + tr->boff[index];
+    } else if (what == 0 && (!tr || tr->off[index] < 0)) {   // frozen, or not training: the loaded value
+        std::memcpy(host, r->host[index].data(), (size_t)numel * sizeof(float));
         return SISIC_OK;
+    } else {
+        SISIC_TRY(require_train(r, who));
+        SISIC_REQUIRE(tr->boff[index] < 0, "%s: '%s' is a running statistic: it has no gradient or moment", who, r->dir.name(index));
+        SISIC_REQUIRE(tr->off[index] >= 0, "%s: '%s' is frozen (BatchNorm): it has no gradient or moment", who, r->dir.name(index));
+        dev = (what == 0 ? tr->param : what == 1 ? tr->grad : what == 2 ? tr->adam_m : tr->adam_v) + tr->off[index];
     }
-    if (what == 0 && (!tr || tr->off[index] < 0)) {       // frozen, or not training: the loaded value
-        std::memcpy(host_out, r->host[index].data(), (size_t)numel * sizeof(float));
-        return SISIC_OK;
-    }
-    SISIC_TRY(require_train(r, "resnet_read"));
-    SISIC_REQUIRE(tr->boff[index] < 0, "resnet_read: '%s' is a running statistic: it has no gradient or moment", r->names[index].c_str());
-    SISIC_REQUIRE(tr->off[index] >= 0, "resnet_read: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
-    const float* base = what == 0 ? tr->param : (what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v));
     SISIC_HIP(hipSetDevice(r->ctx->device));
     SISIC_HIP(hipDeviceSynchronize());
-    SISIC_HIP(hipMemcpy(host_out, base + tr->off[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+    SISIC_HIP(hipMemcpy(write ? dev : host, write ? host : dev, (size_t)numel * sizeof(float), write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return SISIC_OK;
 }
 
-int sisic_resnet_write(sisic_resnet* r, int what, int index, const float* host_in, int64_t numel) {
-    SISIC_REQUIRE(r && host_in && index >= 0 && index < (int)r->names.size(), "resnet_write: bad arguments");
-    SISIC_REQUIRE(numel == r->numels[index], "resnet_write: '%s' has %lld elements", r->names[index].c_str(), (long long)r->numels[index]);
-    SISIC_REQUIRE(what != 0, "resnet_write: parameters are set by sisic_resnet_load (their folded and packed forms must follow); "
-                             "what = 1 gradient, 2 Adam m, 3 Adam v");
-    SISIC_REQUIRE(what >= 1 && what <= 3, "resnet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
-    SISIC_TRY(require_train(r, "resnet_write"));
-    ResnetTrain* tr = r->train;
-    SISIC_REQUIRE(tr->boff[index] < 0, "resnet_write: '%s' is a running statistic: it has no gradient or moment", r->names[index].c_str());
-    SISIC_REQUIRE(tr->off[index] >= 0, "resnet_write: '%s' is frozen (BatchNorm): it has no gradient or moment", r->names[index].c_str());
-    float* base = what == 1 ? tr->grad : (what == 2 ? tr->adam_m : tr->adam_v);
-    SISIC_HIP(hipSetDevice(r->ctx->device));
-    SISIC_HIP(hipDeviceSynchronize());
-    SISIC_HIP(hipMemcpy(base + tr->off[index], host_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    return SISIC_OK;
+int sisic_resnet_read(sisic_resnet* r, int what, int index, float* out, int64_t numel) { return resnet_transfer(r, "resnet_read", false, what, index, out, numel); }
+
+int sisic_resnet_write(sisic_resnet* r, int what, int index, const float* in, int64_t numel) {
+    return resnet_transfer(r, "resnet_write", true, what, index, const_cast<float*>(in), numel);
 }
 
 // loss = cross_entropy(resnet18(x), labels, weight) and its gradient with respect to the trainable tensors: the 22 with BatchNorm
@@ -1302,8 +1271,8 @@ int sisic_resnet_optimizer_step(sisic_resnet* r, sisic_resnet_train_args* a) {
     SISIC_TRY(fold_pack(r, r->stem, s));                 // the 7x7 filter: one form, the load path's launch
     for (int p = 0; p < 2; ++p)
         SISIC_TRY(launch_pack_batch(r->ctx, static_cast<const PackJob*>(tr->repack_dev[p]), tr->repack_jobs[p], tr->repack_blocks[p], s));
-    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, tr->param + tr->off[r->fc_w], (size_t)r->numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, tr->param + tr->off[r->fc_b], (size_t)r->numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_w, tr->param + tr->off[r->fc_w], (size_t)r->dir.numels[r->fc_w] * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SISIC_HIP(hipMemcpyAsync(r->d_fc_b, tr->param + tr->off[r->fc_b], (size_t)r->dir.numels[r->fc_b] * sizeof(float), hipMemcpyDeviceToDevice, s));
     return SISIC_OK;
 }
 

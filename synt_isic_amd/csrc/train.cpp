@@ -768,36 +768,30 @@ int sisic_unet_ema_swap(sisic_unet* u, void* stream) {
     return repack_after_update(u, s);
 }
 
-int sisic_unet_read(sisic_unet* u, int what, int index, float* host_out, int64_t numel) {
-    SISIC_REQUIRE(u && host_out && index >= 0 && index < (int)u->names.size(), "unet_read: bad arguments");
-    SISIC_REQUIRE(numel == u->numels[index], "unet_read: '%s' has %lld elements", u->names[index].c_str(), (long long)u->numels[index]);
-    const float* base = nullptr;
-    if (what == 0) base = u->raw;
-    else {
-        SISIC_TRY(require_train(u, "unet_read"));
-        base = what == 1 ? u->train->grad : (what == 2 ? u->train->adam_m : (what == 3 ? u->train->adam_v : nullptr));
-        if (what == 4) base = u->train->ema;             // the EMA arena, once sisic_unet_ema_begin has made it
+// sisic_unet_read / _write: tensor `index` of arena `what` to the host, or (write) from it; synchronises
+static int unet_transfer(sisic_unet* u, const char* who, bool write, int what, int index, float* host, int64_t numel) {
+    SISIC_REQUIRE(u, "%s: bad arguments", who);
+    SISIC_TRY(u->dir.check_access(who, index, numel, host));
+    SISIC_REQUIRE(!write || what != 0, "%s: parameters are set by sisic_unet_load (their packed forms must follow); what = 1 gradient, "
+                                       "2 Adam m, 3 Adam v", who);
+    float* base = u->raw;
+    if (what != 0) {
+        SISIC_TRY(require_train(u, who));
+        TrainState* tr = u->train.get();                 // (4: the EMA arena, once sisic_unet_ema_begin has made it)
+        base = what == 1 ? tr->grad : what == 2 ? tr->adam_m : what == 3 ? tr->adam_v : what == 4 ? tr->ema : nullptr;
     }
-    SISIC_REQUIRE(base, "unet_read: what = %d (0 parameter, 1 gradient, 2 Adam m, 3 Adam v)", what);
+    SISIC_REQUIRE(base, "%s: what = %d (%s1 gradient, 2 Adam m, 3 Adam v)", who, what, write ? "" : "0 parameter, ");
     SISIC_HIP(hipSetDevice(u->ctx->device));
     SISIC_HIP(hipDeviceSynchronize());
-    SISIC_HIP(hipMemcpy(host_out, base + u->offsets[index], (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+    float* dev = base + u->offsets[index];
+    SISIC_HIP(hipMemcpy(write ? dev : host, write ? host : dev, (size_t)numel * sizeof(float), write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return SISIC_OK;
 }
 
-int sisic_unet_write(sisic_unet* u, int what, int index, const float* host_in, int64_t numel) {
-    SISIC_REQUIRE(u && host_in && index >= 0 && index < (int)u->names.size(), "unet_write: bad arguments");
-    SISIC_REQUIRE(numel == u->numels[index], "unet_write: '%s' has %lld elements", u->names[index].c_str(), (long long)u->numels[index]);
-    SISIC_REQUIRE(what != 0, "unet_write: parameters are set by sisic_unet_load (their packed forms must follow); what = 1 gradient, "
-                             "2 Adam m, 3 Adam v");
-    SISIC_TRY(require_train(u, "unet_write"));
-    float* base = what == 1 ? u->train->grad : (what == 2 ? u->train->adam_m : (what == 3 ? u->train->adam_v : nullptr));
-    if (what == 4) base = u->train->ema;                 // the EMA arena, once sisic_unet_ema_begin has made it
-    SISIC_REQUIRE(base, "unet_write: what = %d (1 gradient, 2 Adam m, 3 Adam v)", what);
-    SISIC_HIP(hipSetDevice(u->ctx->device));
-    SISIC_HIP(hipDeviceSynchronize());
-    SISIC_HIP(hipMemcpy(base + u->offsets[index], host_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-    return SISIC_OK;
+int sisic_unet_read(sisic_unet* u, int what, int index, float* out, int64_t numel) { return unet_transfer(u, "unet_read", false, what, index, out, numel); }
+
+int sisic_unet_write(sisic_unet* u, int what, int index, const float* in, int64_t numel) {
+    return unet_transfer(u, "unet_write", true, what, index, const_cast<float*>(in), numel);
 }
 
 int64_t sisic_unet_train_steps(const sisic_unet* u) { return (u && u->train) ? u->train->step : 0; }

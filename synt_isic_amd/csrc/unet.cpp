@@ -119,11 +119,10 @@ int describe(sisic_unet* u) {
     add_norm(u, u->norm_out, "conv_norm_out", boc[0]);
     add_conv(u, u->conv_out, "conv_out", cfg.out_channels, boc[0], 3);
 
-    u->offsets.resize(u->names.size());
     size_t off = 0;
-    for (size_t i = 0; i < u->names.size(); ++i) {
-        u->offsets[i] = off;
-        off += ((size_t)u->numels[i] + 3) / 4 * 4;   // keep every tensor 16-byte aligned
+    for (int64_t numel : u->dir.numels) {
+        u->offsets.push_back(off);
+        off += ((size_t)numel + 3) / 4 * 4;          // keep every tensor 16-byte aligned
     }
     u->raw_floats = off;
     return SISIC_OK;
@@ -790,36 +789,20 @@ int64_t sisic_unet_workspace_bytes(const sisic_unet* u) {
     return u ? u->pool.bytes() : 0;
 }
 
-int sisic_unet_num_tensors(const sisic_unet* u) { return u ? (int)u->names.size() : 0; }
+int sisic_unet_num_tensors(const sisic_unet* u) { return u ? u->dir.size() : 0; }
 
-const char* sisic_unet_tensor_name(const sisic_unet* u, int i) {
-    if (!u || i < 0 || i >= (int)u->names.size()) return nullptr;
-    return u->names[i].c_str();
-}
+const char* sisic_unet_tensor_name(const sisic_unet* u, int i) { return u ? u->dir.name(i) : nullptr; }
 
 int sisic_unet_load(sisic_unet* u, int n, const char* const* names, const float* const* host_ptrs,
                     const int64_t* numels) {
     SISIC_REQUIRE(u && names && host_ptrs && numels, "unet_load: null argument");
-    SISIC_REQUIRE(n == (int)u->names.size(), "unet_load: state dict has %d tensors, expected %d", n, (int)u->names.size());
+    std::vector<int> slot;                    // a refused state dict leaves the handle as it was: nothing below has run
+    SISIC_TRY(u->dir.match("unet_load", n, names, host_ptrs, numels, &slot));
     SISIC_HIP(hipSetDevice(u->ctx->device));
-    if (!u->raw) {
-        void* p = nullptr;
-        SISIC_HIP(hipMalloc(&p, u->raw_floats * sizeof(float)));
-        u->raw = static_cast<float*>(p);
-    }
+    if (!u->raw) SISIC_HIP(hipMalloc(&u->raw, u->raw_floats * sizeof(float)));
     SISIC_HIP(hipMemset(u->raw, 0, u->raw_floats * sizeof(float)));
-    std::vector<char> seen(u->names.size(), 0);
-    for (int i = 0; i < n; ++i) {
-        SISIC_REQUIRE(names[i] && host_ptrs[i], "unet_load: entry %d is null", i);
-        auto it = u->index.find(names[i]);
-        SISIC_REQUIRE(it != u->index.end(), "unet_load: unexpected key '%s'", names[i]);
-        const int idx = it->second;
-        SISIC_REQUIRE(!seen[idx], "unet_load: duplicate key '%s'", names[i]);
-        SISIC_REQUIRE(numels[i] == u->numels[idx], "unet_load: '%s' has %lld elements, expected %lld", names[i],
-                      (long long)numels[i], (long long)u->numels[idx]);
-        seen[idx] = 1;
-        SISIC_HIP(hipMemcpy(u->raw + u->offsets[idx], host_ptrs[i], (size_t)numels[i] * sizeof(float), hipMemcpyHostToDevice));
-    }
+    for (int i = 0; i < n; ++i)
+        SISIC_HIP(hipMemcpy(u->raw + u->offsets[slot[i]], host_ptrs[i], (size_t)numels[i] * sizeof(float), hipMemcpyHostToDevice));
     // (re)build derived buffers.  A captured sampling step holds the addresses of the packed filters freed below: drop it
     // (a replay after load_state_dict would read freed memory).
     SISIC_HIP(hipDeviceSynchronize());

@@ -160,11 +160,8 @@ struct sisic_unet {
     sisic_unet_config cfg{};
     std::vector<float> freqs;
 
-    // expected state dict
-    std::vector<std::string> names;
-    std::vector<int64_t> numels;
+    sisic::TensorDir dir;              // expected state dict
     std::vector<size_t> offsets;       // float offset of each raw tensor in `raw`
-    std::map<std::string, int> index;
     float* raw = nullptr;              // device arena with the raw tensors
     size_t raw_floats = 0;
     std::vector<float*> owned;         // derived device buffers (packed weights, ...)
@@ -295,12 +292,7 @@ struct sisic_unet {
     float* thr_s = nullptr;              // every image's s of the step [B]: written by the quantile launch, read by the step kernel
     size_t thr_s_cap = 0;
 
-    int add(const std::string& name, int64_t numel) {
-        index[name] = (int)names.size();
-        names.push_back(name);
-        numels.push_back(numel);
-        return (int)names.size() - 1;
-    }
+    int add(const std::string& name, int64_t numel) { return dir.add(name, numel); }
     const float* rawp(int idx) const { return raw + offsets[idx]; }
 };
 

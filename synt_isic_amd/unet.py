@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import UNetConfigC, check
+from ._module import HipModule
 from .arch import UNetConfig, normalize_state_dict_keys, unet_param_spec
 from . import ops
 
@@ -61,7 +62,9 @@ class _ParameterView:
         return next(self._it)
 
 
-class HipUNet2DModel:
+class HipUNet2DModel(HipModule):
+    _PREFIX, _NAME, _NO_CPU_PATH, _KEYS = "sisic_unet", "HipUNet2DModel", "there is no CPU path", "state-dict keys"
+
     def __init__(self, sample_size: int = 128, in_channels: int = 3, out_channels: int = 3,
                  layers_per_block: int = 2, block_out_channels: Sequence[int] = (64, 128, 256, 256),
                  down_block_types: Sequence[str] = ("DownBlock2D", "DownBlock2D", "AttnDownBlock2D", "DownBlock2D"),
@@ -91,25 +94,16 @@ class HipUNet2DModel:
                     and ch % attention_head_dim:      # (8: the library's own check, as before)
                 raise ValueError(f"block_out_channels[{i}] = {ch} carries attention and is no multiple of "
                                  f"attention_head_dim = {attention_head_dim}")
-        self._spec = unet_param_spec(self.config)
-        self._params: "OrderedDict[str, torch.Tensor]" = OrderedDict()   # on self._device
-        self._device = torch.device("cpu")
-        self._handle: Optional[C.c_void_p] = None
-        self._uploaded = False
+        super().__init__(unet_param_spec(self.config))
         self.training = True                  # nn.Module default until .eval()
         self._train_begun = False             # gradient / Adam arenas exist in the library (HipAdam creates them)
         self._tape_input = None               # input of the last training-mode forward (the tape points into it)
         self._latency_mode = False
-        self._params_stale = False            # the library's weights have moved on (optimizer steps) since _params was read
         self._ema_swapped = False             # inside HipEMA.average_parameters(): the library holds the averaged weights
         self._dropout_seed = 0                # the mask stream of config.dropout (set_dropout): its seed and the counter value
         self._dropout_call = 0                #   a handle that does not exist yet starts from
 
     # ------------------------------------------------------------------ nn.Module surface
-    @property
-    def device(self) -> torch.device:
-        return self._device
-
     @property
     def dtype(self) -> torch.dtype:
         return torch.float32
@@ -188,27 +182,6 @@ class HipUNet2DModel:
             check(_lib.load().sisic_unet_train_begin(self.handle))
             self._train_begun = True
 
-    def _refresh_params(self) -> None:
-        """after optimizer steps: read the current weights back from the library"""
-        if not self._params_stale or self._handle is None:
-            return
-        new = OrderedDict()
-        for name, t in self._read_all(0).items():
-            new[name] = t.to(self._device)
-        self._params = new
-        self._params_stale = False
-
-    def _read_all(self, what: int) -> "OrderedDict[str, torch.Tensor]":
-        lib = _lib.load()
-        h = self.handle
-        out = OrderedDict()
-        index = {lib.sisic_unet_tensor_name(h, i).decode(): i for i in range(lib.sisic_unet_num_tensors(h))}
-        for name, shape in self._spec.items():
-            t = torch.empty(tuple(shape), dtype=torch.float32)
-            check(lib.sisic_unet_read(h, what, index[name], C.cast(t.data_ptr(), _lib.c_float_p), t.numel()))
-            out[name] = t
-        return out
-
     def grads(self) -> "OrderedDict[str, torch.Tensor]":
         """{name: d loss / d parameter} of the last backward pass, on the host (what ``p.grad`` holds in the reference)."""
         if not self._train_begun:
@@ -221,19 +194,6 @@ class HipUNet2DModel:
         if not self._train_begun:
             raise RuntimeError("no gradient arena: create a HipAdam for this model first")
         self._write_all(1, mapping, "set_grads")
-
-    def _write_all(self, what: int, mapping: Dict[str, torch.Tensor], label: str) -> None:
-        """{name: tensor} into one of the library's training arenas: 1 gradient, 2 / 3 Adam moments, 4 EMA"""
-        lib = _lib.load()
-        h = self.handle
-        index = {lib.sisic_unet_tensor_name(h, i).decode(): i for i in range(lib.sisic_unet_num_tensors(h))}
-        for name, t in mapping.items():
-            if name not in self._spec:
-                raise KeyError(f"{label}: no parameter named {name}")
-            if tuple(t.shape) != tuple(self._spec[name]):
-                raise RuntimeError(f"{label}: size mismatch for {name}: {tuple(t.shape)} vs {tuple(self._spec[name])}")
-            host = t.detach().to("cpu", torch.float32).contiguous()
-            check(lib.sisic_unet_write(h, what, index[name], C.cast(host.data_ptr(), _lib.c_float_p), host.numel()))
 
     def optimizer_state(self) -> Dict[str, "OrderedDict[str, torch.Tensor]"]:
         return {"exp_avg": self._read_all(2), "exp_avg_sq": self._read_all(3),
@@ -269,36 +229,10 @@ class HipUNet2DModel:
             if tuple(t.shape) != tuple(shape):
                 raise RuntimeError(f"size mismatch for {name}: checkpoint {tuple(t.shape)} vs model {tuple(shape)}")
             new[name] = t.detach().to(device=self._device, dtype=torch.float32).contiguous().clone()
-        self._params = new
-        self._uploaded = False
-        self._params_stale = False
-        if self._device.type == "cuda":
-            self._upload()
+        self._set_params(new)
         return self
 
-    def to(self, device=None, *args, **kwargs) -> "HipUNet2DModel":
-        if device is None:
-            return self
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device == self._device:
-            return self
-        self._refresh_params()
-        self._release()
-        self._params = OrderedDict((k, v.to(device)) for k, v in self._params.items())
-        self._device = device
-        if device.type == "cuda" and self._params:
-            self._upload()
-        return self
-
-    def cuda(self, index: Optional[int] = None) -> "HipUNet2DModel":
-        return self.to(torch.device("cuda", index if index is not None else torch.cuda.current_device()))
-
-    def cpu(self) -> "HipUNet2DModel":
-        return self.to("cpu")
-
-    # ------------------------------------------------------------------ library handle
+    # ------------------------------------------------------------------ library handle (the shell's hooks)
     def _create_handle(self) -> None:
         lib = _lib.load()
         cfg = self.config
@@ -326,49 +260,15 @@ class HipUNet2DModel:
             check(lib.sisic_unet_set_dropout(h, float(cfg.dropout), self._dropout_seed, self._dropout_call))
         if cfg.prediction_type != "epsilon":
             check(lib.sisic_unet_set_prediction_type(h, _lib.prediction_code(cfg.prediction_type)))
-        # the library's own view of the expected keys must agree with ours
-        n = lib.sisic_unet_num_tensors(h)
-        names = [lib.sisic_unet_tensor_name(h, i).decode() for i in range(n)]
-        if sorted(names) != sorted(self._spec):
-            raise RuntimeError("libsisic_hip.so and synt_isic_amd.arch disagree on the state-dict keys")
 
-    def _upload(self) -> None:
-        if self._handle is None:
-            self._create_handle()
-        lib = _lib.load()
-        host = [(k, v.detach().to("cpu", torch.float32).contiguous()) for k, v in self._params.items()]
-        n = len(host)
-        names = (C.c_char_p * n)(*[k.encode() for k, _ in host])
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for _, t in host])
-        numels = (C.c_int64 * n)(*[t.numel() for _, t in host])
-        check(lib.sisic_unet_load(self._handle, n, names, ptrs, numels))
-        self._uploaded = True
+    def _after_upload(self) -> None:
         if self._train_begun:                 # new weights under an existing optimizer: fresh moments, like a new Adam
-            check(lib.sisic_unet_train_begin(self._handle))
+            check(_lib.load().sisic_unet_train_begin(self._handle))
 
-    def _release(self) -> None:
+    def _before_release(self) -> None:
         if self._handle is not None:
             self._dropout_call = int(_lib.load().sisic_unet_dropout_next_call(self._handle))     # a new handle continues the stream
-            _lib.load().sisic_unet_destroy(self._handle)
-            self._handle = None
-            self._uploaded = False
             self._train_begun = False
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    @property
-    def handle(self) -> C.c_void_p:
-        if self._device.type != "cuda":
-            raise RuntimeError("HipUNet2DModel runs on MI355X only: call .to('cuda') first (there is no CPU path)")
-        if not self._params:
-            raise RuntimeError("HipUNet2DModel has no weights: call load_state_dict() first")
-        if not self._uploaded:
-            self._upload()
-        return self._handle
 
     # ------------------------------------------------------------------ forward
     def _timesteps_host(self, timestep, batch: int) -> torch.Tensor:

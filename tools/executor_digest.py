@@ -10,6 +10,7 @@ wrapper's marshalling last): two trees of the package that print the same lines 
                                                          machine: the DDPM / DDIM tables are fp32 torch host arithmetic, CPU-dependent)
     python tools/executor_digest.py --step-layer         the step layer's lines alone
     python tools/executor_digest.py --train              the training lines alone (train.* and clf.*), after the host lines
+    python tools/executor_digest.py --shell              the model wrappers' lines alone (shell.*), after the host lines
     python tools/executor_digest.py --step-layer-items   with any of the above: every item of the step layer on its own line (by
                                                          default one line per mirror case / wrapper: the sha256 of its items)
     python tools/executor_digest.py --step-layer-times   wall time per call of the wrappers and the mirrors' step
@@ -283,6 +284,113 @@ def classifier_items() -> None:
     emit("clf.input_gradient_after_training.workspace_bytes", clf.workspace_bytes())
 
 
+def shell_items(sd) -> None:
+    """The handle-owning shell of both model classes through one sequence: load, state dict, to(cpu), to(cuda), forward, an
+    optimizer, one backward and one step at batch 2, 32x32, what the step left, a device round trip with stale host copies, a
+    reload under the live optimizer, forward; then what every refusal of the shell says."""
+    from synt_isic_amd.unet import HipUNet2DModel
+    x, noise, t = rand((2, 3, 32, 32), 71).to(DEV), rand((2, 3, 32, 32), 72).to(DEV), torch.tensor([37, 640])
+    csd = synthetic_resnet18_state_dict()
+
+    def unet_step(m, opt):
+        m.train()
+        opt.zero_grad()
+        mse_loss(m(x, t).sample, noise).backward()
+        opt.step()
+        st = m.optimizer_state()
+        return sha(*st["exp_avg"].values(), *st["exp_avg_sq"].values()) + f" step={st['step']}"
+
+    def clf_step(m, opt):
+        opt.zero_grad()
+        m.loss_backward(x, [1, 4], preprocessed=True)
+        opt.step()
+        names = m.trainable_names(opt.batchnorm)
+        return sha(*[m.read_tensor(w, n) for w in (2, 3) for n in names]) + f" step={opt.steps}"
+
+    cases = (("unet", HipUNet2DModel, sd, lambda m: m.eval()(x, t).sample, lambda m: HipAdam(m.train(), lr=1e-4), unet_step),
+             ("clf", lambda: HipMelanomaClassifier(num_classes=7), csd, lambda m: m(x, preprocessed=True),
+              lambda m: HipClassifierAdam(m, batchnorm="batch"), clf_step))
+    for tag, make, weights, forward, optimizer, step in cases:
+        m = make()
+        m.load_state_dict(weights)
+        emit(f"shell.{tag}.state_dict", f"{sha(*m.state_dict().values())} keys={sha_text(m.state_dict())} device={m.device}")
+        m = m.to("cpu").to("cuda")
+        emit(f"shell.{tag}.device", f"{m.device} params={sorted({str(p.device) for p in m.parameters()})}")
+        emit(f"shell.{tag}.forward", sha(forward(m)))
+        opt = optimizer(m)
+        emit(f"shell.{tag}.moments", step(m, opt))
+        emit(f"shell.{tag}.grads", f"{sha(*m.grads().values())} n={len(m.grads())}")
+        emit(f"shell.{tag}.state_dict_after_step", f"{sha(*m.state_dict().values())} keys={sha_text(m.state_dict())}")
+        step(m, opt)                                         # host copies stale again: the move reads them back first
+        m = m.to("cpu")
+        emit(f"shell.{tag}.state_dict_on_cpu", f"{sha(*m.state_dict().values())} device={m.device}")
+        m = m.to(DEV)
+        emit(f"shell.{tag}.forward_after_round_trip", sha(forward(m)))
+        opt = optimizer(m)
+        emit(f"shell.{tag}.moments_after_round_trip", step(m, opt))
+        m.load_state_dict(weights)                           # under the live optimizer
+        emit(f"shell.{tag}.forward_after_reload", sha(forward(m)))
+        emit(f"shell.{tag}.state_dict_after_reload", sha(*m.state_dict().values()))
+        if tag == "unet":
+            emit("shell.unet.moments_after_reload", step(m, opt))
+        else:
+            emit("shell.clf.optimizer_after_reload", f"active={opt._active} trainer={m._trainer} " + said(lambda: opt.steps))
+    # refusals: the handle, the arenas, the two load_state_dicts
+    um, cm = HipUNet2DModel(), HipMelanomaClassifier(num_classes=7)
+    for tag, fresh, weights in (("unet", um, sd), ("clf", cm, csd)):
+        emit(f"shell.{tag}.refusal.handle_on_cpu", said(lambda: fresh.handle))
+        fresh.to(DEV)
+        emit(f"shell.{tag}.refusal.handle_without_weights", said(lambda: fresh.handle))
+        first, last = next(iter(weights)), next(reversed(weights))
+        emit(f"shell.{tag}.refusal.load_missing", said(lambda: fresh.load_state_dict({k: v for k, v in weights.items() if k != last})))
+        emit(f"shell.{tag}.refusal.load_extra", said(lambda: fresh.load_state_dict(dict(weights, extra=torch.zeros(1)))))
+        emit(f"shell.{tag}.refusal.load_shape", said(lambda: fresh.load_state_dict(dict(weights, **{first: torch.zeros(3)}))))
+        emit(f"shell.{tag}.refusal.load_nonstrict_without_weights",
+             said(lambda: fresh.load_state_dict({k: v for k, v in weights.items() if k != last}, strict=False)))
+        emit(f"shell.{tag}.refusal.handle_after_refused_loads", said(lambda: fresh.handle))
+        fresh.load_state_dict(weights)
+        emit(f"shell.{tag}.nonstrict_extra", said(lambda: fresh.load_state_dict(dict(weights, extra=torch.zeros(1)), strict=False)))
+        emit(f"shell.{tag}.nonstrict_fallback", said(lambda: fresh.load_state_dict(
+            dict({k: v * 2 for k, v in weights.items() if k != last}, **{first: torch.zeros(3)}), strict=False)))
+        emit(f"shell.{tag}.nonstrict_fallback.state_dict", sha(*fresh.state_dict().values()))
+        fresh.load_state_dict(weights)
+    name, shape = next(iter(um._spec.items()))
+    emit("shell.unet.refusal.grads_without_optimizer", said(um.grads))
+    emit("shell.unet.refusal.set_grads_without_optimizer", said(lambda: um.set_grads({name: torch.zeros(shape)})))
+    emit("shell.unet.refusal.write_all_without_optimizer", said(lambda: um._write_all(1, {name: torch.zeros(shape)}, "digest")))
+    HipAdam(um, lr=1e-4)
+    emit("shell.unet.refusal.set_grads_unknown", said(lambda: um.set_grads({"no.such.weight": torch.zeros(1)})))
+    emit("shell.unet.refusal.set_grads_shape", said(lambda: um.set_grads({name: torch.zeros(3)})))
+    emit("shell.unet.refusal.write_all_parameters", said(lambda: um._write_all(0, {name: torch.zeros(shape)}, "digest")))
+    emit("shell.unet.refusal.write_all_what_9", said(lambda: um._write_all(9, {name: torch.zeros(shape)}, "digest")))
+    emit("shell.unet.refusal.read_all_what_9", said(lambda: um._read_all(9)))
+    um.set_grads({name: torch.ones(shape)})
+    emit("shell.unet.set_grads", sha(um.grads()[name]))
+    bn, fc = "model.bn1.weight", "model.fc.bias"
+    emit("shell.clf.refusal.read_without_optimizer", said(lambda: cm.read_tensor(1, fc)))
+    emit("shell.clf.refusal.write_without_optimizer", said(lambda: cm.write_tensor(1, fc, torch.zeros(7))))
+    emit("shell.clf.read_parameter_without_optimizer", sha(cm.read_tensor(0, bn)))
+    opt = HipClassifierAdam(cm)
+    emit("shell.clf.refusal.read_frozen", said(lambda: cm.read_tensor(1, bn)))
+    emit("shell.clf.refusal.write_frozen", said(lambda: cm.write_tensor(2, bn, torch.zeros(64))))
+    emit("shell.clf.read_frozen_parameter", sha(cm.read_tensor(0, bn)))
+    emit("shell.clf.refusal.read_unknown", said(lambda: cm.read_tensor(0, "no.such.weight")))
+    emit("shell.clf.refusal.read_what_9", said(lambda: cm.read_tensor(9, fc)))
+    emit("shell.clf.refusal.write_shape", said(lambda: cm.write_tensor(1, fc, torch.zeros(3))))
+    emit("shell.clf.refusal.write_unknown", said(lambda: cm.write_tensor(1, "no.such.weight", torch.zeros(3))))
+    emit("shell.clf.refusal.write_parameters", said(lambda: cm.write_tensor(0, fc, torch.zeros(7))))
+    emit("shell.clf.refusal.write_what_9", said(lambda: cm.write_tensor(9, fc, torch.zeros(7))))
+    emit("shell.clf.refusal.set_grads_missing", said(lambda: cm.set_grads({fc: torch.zeros(7)})))
+    cm.write_tensor(1, fc, torch.ones(7))
+    emit("shell.clf.write_tensor", sha(cm.read_tensor(1, fc)))
+    opt.close()
+    emit("shell.clf.refusal.closed_optimizer", said(lambda: opt.steps))
+
+
+def sha_text(names) -> str:
+    return hashlib.sha256("\n".join(names).encode()).hexdigest()[:16]
+
+
 # ---- the Python step layer (ops.*_step*, the scheduler mirrors, sampler._check_scheduler): names of both sides of its fold only
 NEW_MIRROR_METHODS = {"rule_table", "abar_prev"}        # what the fold added to every mirror: left out of the attribute lists
 
@@ -474,6 +582,8 @@ def main() -> None:
     if "--step-layer" in sys.argv:
         return step_layer_gpu()
     print("library:", _lib.lib_path(), file=sys.stderr)
+    if "--shell" in sys.argv:
+        return shell_items(sd)
     if "--train" in sys.argv:
         train_items(sd)
         train_step_items(sd)
@@ -485,6 +595,7 @@ def main() -> None:
     train_items(sd)
     train_step_items(sd)
     classifier_items()
+    shell_items(sd)
     step_layer_gpu()
 
 
